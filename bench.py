@@ -2,15 +2,18 @@
 """bench.py — Stark252 NTT throughput (BASELINE.json configs[1]: NTT size 2^22 on one MI355X) with roofline and
 CPU-baseline objects.  One "step" = one forward natural-order NTT of 2^22 elements per GPU, inputs resident in HBM.
 
-python bench.py --gpus N --steps K --warmup W
+python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   * started by torch.distributed.run (WORLD_SIZE in the environment): one rank per GPU, as launched;
   * started as a plain command with N > 1: this process spawns the N ranks itself, BEFORE anything touches the GPU, and
     passes rank 0's JSON line through.
 The NTT workload shards by column with no data-path collective (weak scaling: value = butterflies of all ranks / max time).
 Before the timed region every leg runs until at least WARM_MS of device time has passed, whatever --warmup says: a cold
-MI355X needs ~100 ms to reach its clocks and a 20-step run would otherwise measure the ramp.
+MI355X needs ~100 ms to reach its clocks and a 20-step run would otherwise measure the ramp.  The timed steps then start from
+the seeded input again, so that the last step's output depends on the arguments alone; --dump-outputs DIR writes a fixed,
+seeded sample of it (the Montgomery limbs the caller of sp_ntt_dev receives, as float64) to DIR/ntt_output.npy.
 
-The "proof" objects of the same JSON line are BASELINE.json's second figure: whole-proof generation of the 2^20-row Cairo
+A plain run measures the NTT alone.  --full adds the rest of the JSON line: the Merkle (hash pass) roofline, the CPU oracle
+baselines, and the "proof" objects, BASELINE.json's second figure: whole-proof generation of the 2^20-row Cairo
 fibonacci trace (configs[2]) and of the 70k-step program of benches/criterion_prover_70k.rs (configs[3], "proof_cfg4") on the
 N GPUs - in process for N = 1; for N > 1 sharded over the library's RCCL communicator in one child process per rank under
 a time limit, so that the headline line survives whatever happens there.  "rccl" reports what that communicator moved.
@@ -89,6 +92,31 @@ def warm_until(ctx, fn, min_ms=WARM_MS, chunk=10, max_calls=100000):
         total += ctx.timer_stop()
         calls += chunk
     return calls
+
+
+def ntt_input(torch, n, rank):
+    """The seeded input of one rank: uniformly random residues < 2^251 (< p) as (n, 8) int32, the device layout (8 x u32 little-endian
+    Montgomery limbs)."""
+    g = torch.Generator(device="cpu").manual_seed(0x5EED0000 + rank)
+    host = torch.randint(0, 2**31 - 1, (n, 8), dtype=torch.int64, generator=g).to(torch.int32)
+    host2 = torch.randint(0, 2, (n, 8), dtype=torch.int64, generator=g).to(torch.int32)
+    host = host | (host2 << 31)
+    host[:, 7] &= 0x07FFFFFF
+    return host
+
+
+DUMP_ROWS = 1 << 16    # 4 MiB of float64 limbs per rank: eight ranks stay below 64 MB
+
+
+def dump_ntt_output(torch, data, rank, out_dir):
+    """The transformed vector as the caller of sp_ntt_dev receives it - 8 x u32 Montgomery limbs per element, exact in float64 - at a
+    fixed, seeded sample of DUMP_ROWS element indices (ascending; every element when the vector is that small)."""
+    import numpy as np
+    n = data.shape[0]
+    rows = np.sort(np.random.default_rng(0x5EED).choice(n, size=min(n, DUMP_ROWS), replace=False))
+    limbs = data[torch.from_numpy(rows).to(data.device)].cpu().numpy().view(np.uint32).astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "ntt_output.npy" if rank == 0 else f"ntt_output_rank{rank}.npy"), limbs)
 
 
 def cpu_baseline(log_n=22):
@@ -1109,8 +1137,11 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--log-n", type=int, default=LOG_N)
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="write a seeded sample of the last timed step's output to DIR/ntt_output.npy (ntt_output_rank<r>.npy for ranks > 0)")
+    ap.add_argument("--full", action="store_true", help="also measure the Merkle roofline, the whole proofs and the CPU baselines (the options below)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--proof", type=int, default=-1, help="also time whole-proof generation (default: on; N > 1 in child processes)")
+    ap.add_argument("--proof", type=int, default=-1, help="with --full, also time whole-proof generation (default: on; N > 1 in child processes)")
     ap.add_argument("--proof-timeout", type=int, default=360, help="seconds the child processes of the N > 1 proof timing may take")
     ap.add_argument("--proof-child", type=str, default=None, help=argparse.SUPPRESS)
     ap.add_argument("--rccl-preflight", type=str, default=None, help=argparse.SUPPRESS)
@@ -1130,6 +1161,8 @@ def main():
                     "Keccak and Poseidon; ~169 GB of HBM, ~40 s) over the timing-only transport -> summary.cfg5_projected (a projection; tools/project_cfg5.py)")
     ap.add_argument("--project-ranks", type=int, default=8, help="N = 1 only: also PROJECT (not measure) an N-rank sharded proof from rank 0's share on this GPU (0: off)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.cpu_proof_child:
         return cpu_proof_child(args)
     if args.cold_child:
@@ -1178,13 +1211,8 @@ def main():
             except Exception:
                 numa_node = -1
         n = 1 << args.log_n
-        # synthetic input: uniformly random residues < 2^251 (< p), written directly in the device layout
-        # (8 x u32 little-endian Montgomery limbs) so that the timed region starts with the data resident in HBM.
-        g = torch.Generator(device="cpu").manual_seed(0x5EED0000 + rank)
-        host = torch.randint(0, 2**31 - 1, (n, 8), dtype=torch.int64, generator=g).to(torch.int32)
-        host2 = torch.randint(0, 2, (n, 8), dtype=torch.int64, generator=g).to(torch.int32)
-        host = host | (host2 << 31)
-        host[:, 7] &= 0x07FFFFFF
+        # synthetic input written directly in the device layout, so that the timed region starts with the data resident in HBM
+        host = ntt_input(torch, n, rank)
         data = host.to(dev).contiguous()
         ctx = api.Context(device=dev_index)
 
@@ -1205,6 +1233,10 @@ def main():
         self_warm = warm_until(ctx, lambda: ctx.ntt_dev(data.data_ptr(), n))   # clock ramp, independent of --warmup
         for _ in range(args.warmup):
             ctx.ntt_dev(data.data_ptr(), n)
+        # the transform is in place and the self-warm-up runs a timing-dependent number of calls: the timed steps start from the seeded
+        # input again, so that what they compute depends on the arguments alone (--dump-outputs)
+        ctx.sync()
+        data.copy_(host)
         barrier("barrier before the timed region")
         t0 = time.perf_counter()
         ctx.timer_start()                    # HIP events on the context stream bracket the timed region
@@ -1220,6 +1252,8 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
             guard.stage = "proofs"
+        if args.dump_outputs:
+            dump_ntt_output(torch, data, rank, args.dump_outputs)
 
         # HBM bytes per NTT from the committed PMC passes of this very kernel source (tools/profile_round.sh); a profile taken
         # from other sources is reported as stale instead of being passed off as a measurement of this build
@@ -1257,12 +1291,12 @@ def main():
                          "mul_issue_ceiling_per_s": MUL_ISSUE_CEILING, "mul_issue_frac": rate / MUL_ISSUE_CEILING,
                          "valu_ceiling_butterflies_per_s": VALU_BUTTERFLY_CEILING, "valu_frac": rate / VALU_BUTTERFLY_CEILING},
         }
-        if rank == 0:
+        if rank == 0 and args.full:
             try:
                 out["roofline_merkle"] = merkle_roofline(torch, ctx, dev)
             except Exception as e:
                 out["roofline_merkle"] = {"error": repr(e)}
-        if args.proof != 0:
+        if args.full and args.proof != 0:
             try:
                 if world == 1:
                     out["proof"] = proof_benchmark(api, ctx, args.proof_fib, args.proof_blowup, 1, None)
@@ -1323,7 +1357,7 @@ def main():
                             out["proof"] = res
             except Exception as e:  # the headline metric must survive a failure of the secondary one
                 out["proof"] = {"error": repr(e)}
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
             try:
                 out["cpu_baseline"]["proof"] = cpu_proof_sample(api, ctx)

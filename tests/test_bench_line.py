@@ -1,5 +1,5 @@
 """bench.py's pure pieces (no GPU): the compact JSON line keeps the contract keys and ends with `summary`; the configs[2] CPU figure is the
-same-host ratio of the two full oracle runs; the error line carries the contract keys."""
+same-host ratio of the two full oracle runs; the error line carries the contract keys; --dump-outputs writes a fixed sample of exact limbs."""
 import argparse
 import json
 import os
@@ -43,3 +43,20 @@ def test_error_line_has_the_contract_keys():
     args = argparse.Namespace(steps=20, warmup=5, log_n=22)
     line = bench.error_line(args, 8, "rank 3 exited with code 1", stage="rendezvous")
     assert all(k in line for k in CONTRACT) and line["value"] is None and line["n_gpus"] == 8 and line["error"] and line["stage"] == "rendezvous"
+
+
+def test_dump_is_a_fixed_sample_of_exact_limbs(tmp_path):
+    import numpy as np
+    import torch
+    data = torch.randint(-2**31, 2**31 - 1, (1 << 17, 8), dtype=torch.int32, generator=torch.Generator().manual_seed(1))
+    bench.dump_ntt_output(torch, data, 0, str(tmp_path))
+    bench.dump_ntt_output(torch, data.clone(), 3, str(tmp_path))
+    got = np.load(tmp_path / "ntt_output.npy")
+    assert got.dtype == np.float64 and got.shape == (bench.DUMP_ROWS, 8) and 8 * got.nbytes <= 64 * 10**6     # eight ranks within 64 MB
+    assert np.array_equal(np.load(tmp_path / "ntt_output_rank3.npy"), got)
+    where = {row.tobytes(): i for i, row in enumerate(data.numpy().view(np.uint32))}
+    rows = [where[r.astype(np.uint32).tobytes()] for r in got]                  # every dumped row is one element's limbs, unchanged
+    assert all(a < b for a, b in zip(rows, rows[1:]))                          # distinct elements in ascending order
+    small = data[:1000]
+    bench.dump_ntt_output(torch, small, 0, str(tmp_path / "small"))           # a vector below the sample size: all of it, in order
+    assert np.array_equal(np.load(tmp_path / "small" / "ntt_output.npy"), small.numpy().view(np.uint32).astype(np.float64))

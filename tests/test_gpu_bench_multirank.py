@@ -19,7 +19,7 @@ def test_two_ranks_with_a_failing_rccl_preflight_fall_back_to_staged_hooks():
     env = dict(os.environ, SP_BENCH_FORCE_DEVICE="0", SP_BENCH_TRANSPORT="rccl")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--log-n", "16",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--log-n", "16",
                         "--proof-fib", "2000", "--proof-blowup", "4", "--cfg4-fib", "1000", "--cfg4-blowup", "2"],
                        env=env, capture_output=True, text=True, timeout=900)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -58,7 +58,7 @@ def main():
     write_kb = sum(mult_w[k] * t / c for k, (c, t) in wp.items())
     passes = fp
     res = {
-        "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) on `bench.py --proof 0 --steps 20 --warmup 3`",
+        "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) on `bench.py --full --proof 0 --steps 20 --warmup 3`",
         "log_n": log_n,
         "launches_per_ntt": launches,
         "transforms_in_fetch_pass": ntts_f,
