@@ -73,9 +73,9 @@ const char* sp_version(void);
 /* Version of this header: bumped whenever a structure (sp_air_desc, sp_openings, sp_cairo_public_inputs, sp_proof_options) changes
  * layout, an entry point or option key is added, or a call changes meaning (4: round 5's sp_comm_measure / sp_comm_time_ms /
  * sp_proof_options_* / sp_proof_file_verify / SP_OPT_HOST_RANKS family and sp_set_collective keeping the prover across re-installs
- * of the same world; 5: sp_fe_mul).  A binding compares it (and sp_air_desc_size against its own idea of the struct) when it loads the library, so
+ * of the same world; 5: sp_fe_mul; 6: sp_air_limits, sp_air_prove beyond 64 columns and 3 boundary rows).  A binding compares it (and sp_air_desc_size against its own idea of the struct) when it loads the library, so
  * a stale build fails at load time with "rebuild the library" instead of with a missing symbol or shifted fields later. */
-#define SP_ABI_VERSION 5
+#define SP_ABI_VERSION 6
 int sp_abi_version(void);
 uint64_t sp_air_desc_size(void);
 const char* sp_last_error(void);          /* thread-local description of the last failure */
@@ -406,16 +406,16 @@ typedef struct { uint32_t col; uint32_t pad; uint64_t step; uint8_t value[32]; /
  * auxiliary trace (context encoding) to aux_rows_out and return 0. */
 typedef int (*sp_aux_trace_fn)(void* user, const uint8_t* rap, uint32_t n_rap, uint8_t* aux_rows_out);
 typedef struct {
-    uint32_t main_cols, aux_cols;            /* AirContext::trace_columns = main_cols + aux_cols (<= 64) */
+    uint32_t main_cols, aux_cols;            /* AirContext::trace_columns = main_cols + aux_cols (<= 1024) */
     uint32_t n_offsets; uint32_t offsets[8]; /* transition_offsets */
     uint32_t n_transitions; uint32_t degrees[64]; uint32_t exemptions[64]; /* transition_degrees / transition_exemptions */
     uint32_t num_transition_exemptions;      /* AirContext::num_transition_exemptions */
     uint32_t degree_bound_factor;            /* composition_poly_degree_bound() / trace_length (1 or 2) */
-    uint32_t n_ops; const sp_air_op* ops;    /* <= 2048 ops, <= 64 values alive at any point of the program */
-    uint32_t n_consts; const uint8_t* consts; /* canonical BE */
+    uint32_t n_ops; const sp_air_op* ops;    /* <= 65535 ops, <= 64 values alive at any point of the program */
+    uint32_t n_consts; const uint8_t* consts; /* <= 4096, canonical BE */
     uint32_t n_rap;                          /* build_rap_challenges: this many transcript_to_field samples */
     uint32_t aux_kind;                       /* build_auxiliary_trace: 0 none, 1 fibonacci_rap permutation column, 2 aux_fn */
-    uint32_t n_boundary; const sp_air_boundary* boundary;   /* <= 16, at most 3 distinct steps */
+    uint32_t n_boundary; const sp_air_boundary* boundary;   /* <= 4096, on any rows (several per column allowed) */
     sp_aux_trace_fn aux_fn; void* aux_user;  /* aux_kind 2 */
 } sp_air_desc;
 
@@ -423,6 +423,9 @@ typedef struct {
  * main_trace: row-major n x air->main_cols, context encoding, host memory.  *proof_out is malloc'd (sp_free). */
 int sp_air_prove(sp_ctx* ctx, const sp_air_desc* air, const uint8_t* main_trace, uint64_t n, const sp_proof_options* opt,
                  uint8_t** proof_out, uint64_t* proof_len);
+/* The bounds sp_air_prove accepts, in order: columns (main + aux), transition constraints, frame rows, boundary constraints,
+ * constants, ops, values alive at once, 0 (reserved).  A binding can refuse a descriptor before proving. */
+int sp_air_limits(uint32_t out[8]);
 
 /* verify::<Stark252PrimeField, A> (reference src/starks/verifier.rs:559-657) on the host CPU: 1 accept, 0 reject (also for
  * malformed proofs or descriptors). */

@@ -108,9 +108,20 @@ class AirBuilder:
     def boundary(self, col, step, value):
         self.bcs.append((col, step, value % P))
 
+    def check_limits(self):
+        """Raises ValueError naming the first bound of sp_air_limits (api.air_limits) this AIR exceeds."""
+        from .api import air_limits
+        lim = air_limits()
+        have = {"columns": self.main_cols + self.aux_cols, "transitions": len(self.degrees), "frame_rows": len(self.offsets),
+                "boundary_constraints": len(self.bcs), "constants": len(self.consts), "ops": len(self.ops)}
+        for name, value in have.items():
+            if value > lim[name]:
+                raise ValueError(f"AIR exceeds the {name} limit of sp_air_prove: {value} > {lim[name]}")
+
     def build(self):
-        """Returns (AirDescC, keepalive)."""
+        """Returns (AirDescC, keepalive).  Raises ValueError if the AIR exceeds a bound of sp_air_limits."""
         _check_layout()
+        self.check_limits()
         d = AirDescC()
         d.main_cols, d.aux_cols = self.main_cols, self.aux_cols
         d.n_offsets = len(self.offsets)

@@ -440,6 +440,16 @@ def last_error():
     return _lib.load().sp_last_error().decode(errors="replace")
 
 
+AIR_LIMIT_NAMES = ("columns", "transitions", "frame_rows", "boundary_constraints", "constants", "ops", "live_values")
+
+
+def air_limits():
+    """sp_air_limits: the bounds sp_air_prove accepts, {name: value} in the order of AIR_LIMIT_NAMES (columns = main + aux)."""
+    out = (ctypes.c_uint32 * 8)()
+    check(_lib.load().sp_air_limits(out))
+    return {name: int(out[i]) for i, name in enumerate(AIR_LIMIT_NAMES)}
+
+
 def air_verify(proof, desc, options, merkle_backend=0):
     """sp_air_verify(_backend): the library's CPU verifier for an AIR given as a constraint program."""
     lib = _lib.load()

@@ -3,6 +3,7 @@
 #include "cairo_host.h"
 #include "cairo_air_host.h"
 #include "poseidon.h"
+#include "stark_kernels.h"
 #include <array>
 #include "common.h"
 #include <cstring>
@@ -89,6 +90,13 @@ extern "C" {
 const char* sp_version(void) { return "stark252-hip 0.3 (gfx950)"; }
 int sp_abi_version(void) { return SP_ABI_VERSION; }
 uint64_t sp_air_desc_size(void) { return sizeof(sp_air_desc); }
+int sp_air_limits(uint32_t out[8]) {
+    if (!out) return SP_E_INVALID_ARG;
+    const uint32_t lim[8] = {(uint32_t)sp::AIR_MAX_COLS, (uint32_t)sp::AIR_MAX_TRANSITIONS, (uint32_t)sp::AIR_MAX_OFFSETS, (uint32_t)sp::AIR_MAX_BOUNDARY,
+                             (uint32_t)sp::AIR_MAX_CONSTS, (uint32_t)sp::AIR_MAX_OPS, (uint32_t)sp::AIR_MAX_LIVE, 0u};
+    std::memcpy(out, lim, sizeof(lim));
+    return SP_OK;
+}
 const char* sp_last_error(void) { return g_last_error.c_str(); }
 int sp_host_bind_to_device(int device, int* node_out) {
     if (device < 0) return SP_E_INVALID_ARG;

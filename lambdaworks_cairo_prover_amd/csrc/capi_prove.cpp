@@ -24,6 +24,7 @@ extern "C" {
 
 int sp_prove_setup(sp_ctx* c, uint64_t n, uint32_t main_cols, uint32_t aux_cols, int has_rc, const sp_proof_options* opt) {
     if (!c || !opt) return SP_E_INVALID_ARG;
+    if ((uint64_t)main_cols + aux_cols > 64) { sp_set_error("sp_prove_setup: the round-level entry points take up to 64 columns (sp_air_prove: up to 1024)"); return SP_E_INVALID_ARG; }
     ProverHolder* h = holder(c, true);
     ProofOptionsHost o{opt->blowup_factor, opt->fri_number_of_queries, opt->coset_offset, opt->grinding_factor};
     return h->prover.setup(n, main_cols, aux_cols, has_rc != 0, o);
@@ -90,6 +91,7 @@ static int warm_small_proofs(sp_ctx* c, const ProofOptionsHost& o) {
 
 int sp_prewarm(sp_ctx* c, uint64_t n, uint32_t main_cols, uint32_t aux_cols, int has_rc, const sp_proof_options* opt, uint32_t flags) {
     if (!c || !opt) return SP_E_INVALID_ARG;
+    if ((uint64_t)main_cols + aux_cols > 64) { sp_set_error("sp_prewarm: up to 64 columns"); return SP_E_INVALID_ARG; }
     if (flags == 0) flags = SP_PREWARM_ALL;
     ProverHolder* h = holder(c, true);
     ProofOptionsHost o{opt->blowup_factor, opt->fri_number_of_queries, opt->coset_offset, opt->grinding_factor};
@@ -386,8 +388,10 @@ int sp_air_prove(sp_ctx* c, const sp_air_desc* d, const uint8_t* main_trace, uin
         a.boundary.push_back(sp::BoundaryConstraint{d->boundary[i].col, d->boundary[i].step, fe_from_bytes_be(d->boundary[i].value)});
     sp::ProofOptionsHost o{opt->blowup_factor, opt->fri_number_of_queries, opt->coset_offset, opt->grinding_factor};
     std::vector<uint8_t> proof;
-    int rc = sp::air_prove(c, a, main_trace, n, o, proof);
+    float ms[5] = {0, 0, 0, 0, 0};
+    int rc = sp::air_prove(c, a, main_trace, n, o, proof, ms);
     if (rc != SP_OK) return rc;
+    std::memcpy(c->round_ms, ms, sizeof(ms));
     uint8_t* out = (uint8_t*)std::malloc(proof.size());
     if (!out) return SP_E_ALLOC;
     std::memcpy(out, proof.data(), proof.size());

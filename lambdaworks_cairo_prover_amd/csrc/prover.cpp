@@ -108,7 +108,7 @@ int StarkProver::setup_impl(uint64_t n, uint32_t main_cols, uint32_t aux_cols, b
     offsets_ = {0, 1};
     int k = sp_log2_exact(n), lb = sp_log2_exact(opt.blowup_factor);
     if (k < 1 || lb < 1 || k + lb > 30 || (1u << lb) > CAIRO_MAX_BLOWUP) { sp_set_error("setup: trace length and blowup factor must be powers of two (blowup 2 .. 128, at most 2^30 LDE points)"); return SP_E_INVALID_ARG; }
-    if (main_cols + aux_cols > 64) return SP_E_INVALID_ARG;
+    if (main_cols + aux_cols > (uint32_t)AIR_MAX_COLS) { sp_set_error("setup: more than 1024 trace columns (main + aux)"); return SP_E_INVALID_ARG; }
     SP_HIP_CHECK(hipSetDevice(c_->device));
     if (c_->world < 1 || (c_->world & (c_->world - 1)) || c_->rank < 0 || c_->rank >= c_->world) {
         sp_set_error("setup: world size must be a power of two");
@@ -125,7 +125,7 @@ int StarkProver::setup_impl(uint64_t n, uint32_t main_cols, uint32_t aux_cols, b
     free_all();
     ready_ = false; stage_ = 0;
     d_auxws_ = nullptr; auxws_bytes_ = 0; auxws_pm_cap_ = 0; d_hfull_ = nullptr; d_hnat_ = nullptr; h_full_ = false;
-    d_air_prog_ = nullptr; d_ex_roots_ = nullptr; ex_roots_cap_ = 0;
+    d_air_buf_ = nullptr; air_buf_cap_ = 0; d_ex_roots_ = nullptr; ex_roots_cap_ = 0;
     d_flags_all_ = nullptr;
     d_gather_ = nullptr; gather_cap_ = 0; d_fullN_ = nullptr; d_small_ = nullptr; d_deepx_ = nullptr; deepx_cap_ = 0; d_cstage_ = nullptr; d_local_ = nullptr; d_recv_ = nullptr; d_roots_ = nullptr;
     opt_ = opt; n_ = n; logn_ = (uint32_t)k; logb_ = (uint32_t)lb; logN_ = logn_ + logb_; N_ = n << lb;
@@ -185,7 +185,9 @@ int StarkProver::setup_impl(uint64_t n, uint32_t main_cols, uint32_t aux_cols, b
         SP_TRY(alloc_tree(tree_aux_, N_, G_ > 1));
         SP_TRY(alloc_tree(tree_comp_, N_, G_ > 1));
         SP_TRY(alloc((void**)&d_comp_consts_, sizeof(CompositionConsts)));
-        SP_TRY(alloc((void**)&d_deep_consts_, sizeof(DeepConsts)));
+        // DeepConsts, then gamma_{j,k} as [frame rows][columns]: one upload per proof
+        SP_TRY(alloc((void**)&d_deep_consts_, deep_gammas_at() + sizeof(fe) * AIR_MAX_OFFSETS * C_));
+        d_deep_gammas_ = reinterpret_cast<fe*>(reinterpret_cast<uint8_t*>(d_deep_consts_) + deep_gammas_at());
         SP_TRY(alloc((void**)&d_nonce_, sizeof(unsigned long long)));
         // FRI: layers of at least 2^opt_fri_shard_min_log leaves (and at least 2 G^2, so that every rank owns whole blocks of the
         // digest exchange) stay sharded; from layer fri_rep_ on every rank holds the whole layer.  The last, uncommitted fold
@@ -969,16 +971,16 @@ int StarkProver::composition(const fe rap[3], const std::vector<BoundaryConstrai
             return SP_E_UNSUPPORTED;
         }
     }
-    return composition_core(K, points, nullptr, nullptr, true, root_out);
+    return composition_core(&K, points, nullptr, nullptr, nullptr, true, root_out);
 }
 
 int StarkProver::composition_air(const AirDescHost& air, const std::vector<fe>& rap, const std::vector<fe>& b_alpha, const std::vector<fe>& b_beta,
                                  const std::vector<fe>& t_alpha, const std::vector<fe>& t_beta, uint8_t root_out[32]) {
     if (stage_ != 3 && !(stage_ == 2 && Ca_ == 0)) { sp_set_error("composition: trace segments not committed"); return SP_E_STATE; }
     const uint32_t T = (uint32_t)air.degrees.size(), B = (uint32_t)air.boundary.size(), R = (uint32_t)air.offsets.size();
-    if (T == 0 || T > AIR_MAX_TRANSITIONS || B > COMP_MAX_BOUNDARY || R == 0 || R > AIR_MAX_OFFSETS || air.exemptions.size() != T ||
+    if (T == 0 || T > AIR_MAX_TRANSITIONS || B > AIR_MAX_BOUNDARY || R == 0 || R > AIR_MAX_OFFSETS || air.exemptions.size() != T ||
         t_alpha.size() != T || t_beta.size() != T || b_alpha.size() != B || b_beta.size() != B || air.ops.size() > AIR_MAX_OPS ||
-        air.consts.size() + rap.size() > AIR_MAX_CONSTS || rap.size() != air.n_rap || air.main_cols != Cm_ || air.aux_cols != Ca_ ||
+        air.consts.size() > AIR_MAX_CONSTS || air.consts.size() + rap.size() > 65535 || rap.size() != air.n_rap || air.main_cols != Cm_ || air.aux_cols != Ca_ ||
         air.degree_bound_factor < 1) {
         sp_set_error("composition_air: descriptor out of range or inconsistent with the committed trace");
         return SP_E_INVALID_ARG;
@@ -987,9 +989,9 @@ int StarkProver::composition_air(const AirDescHost& air, const std::vector<fe>& 
     const uint32_t b = 1u << logb_, f = air.degree_bound_factor;
     // --- validate the program (every operand refers to an earlier value, cells exist) and build the device copy: every
     //     value gets a slot of the per-point value file, released after its last use (the program is straight-line)
-    std::unique_ptr<AirProgram> prog_holder(new AirProgram());
-    AirProgram& prog = *prog_holder;
+    AirProgram prog;
     std::memset(&prog, 0, sizeof(prog));
+    std::vector<AirOpDev> dops;
     prog.n_ops = (uint32_t)air.ops.size();
     prog.n_offsets = R;
     for (uint32_t k = 0; k < R; ++k) prog.offsets[k] = air.offsets[k];
@@ -1028,7 +1030,6 @@ int StarkProver::composition_air(const AirDescHost& air, const std::vector<fe>& 
         for (int sl = AIR_MAX_LIVE - 1; sl >= 0; --sl) free_slots.push_back((uint16_t)sl);
         std::vector<std::vector<uint32_t>> dying(n_src);    // values whose last use is op t
         for (uint32_t t = 0; t < n_src; ++t) if (live[t] && air.ops[t].op != 5) dying[last_use[t]].push_back(t);
-        uint32_t emitted = 0;
         for (uint32_t t = 0; t < n_src; ++t) {
             if (!live[t]) continue;
             const AirOpHost& o = air.ops[t];
@@ -1043,12 +1044,10 @@ int StarkProver::composition_air(const AirDescHost& air, const std::vector<fe>& 
                 d.dst = free_slots.back(); free_slots.pop_back();
                 slot_of[t] = d.dst;
             }
-            prog.ops[emitted++] = d;
+            dops.push_back(d);
         }
-        prog.n_ops = emitted;
+        prog.n_ops = (uint32_t)dops.size();
     }
-    for (size_t i = 0; i < air.consts.size(); ++i) prog.consts[i] = air.consts[i];
-    for (size_t i = 0; i < rap.size(); ++i) prog.consts[air.consts.size() + i] = rap[i];
     // --- transition exemptions (traits.rs:49-79, evaluator.rs:299-323): distinct non-zero counts; with
     //     num_transition_exemptions == 1 every exempted constraint uses the first of them
     std::vector<uint32_t> uniq;
@@ -1076,32 +1075,66 @@ int StarkProver::composition_air(const AirDescHost& air, const std::vector<fe>& 
         SP_TRY(alloc((void**)&d_ex_roots_, sizeof(fe) * std::max<uint32_t>(max_ex, 64)));
         ex_roots_cap_ = std::max<uint32_t>(max_ex, 64);
     }
-    if (!d_air_prog_) SP_TRY(alloc((void**)&d_air_prog_, sizeof(AirProgram)));
     if (max_ex) {
         std::vector<fe> er(max_ex);
         for (uint32_t j = 0; j < max_ex; ++j) er[j] = fe_pow_u64(g_, n_ - 1 - j);
         SP_HIP_CHECK(hipMemcpyAsync(d_ex_roots_, er.data(), sizeof(fe) * max_ex, hipMemcpyHostToDevice, c_->stream));
         SP_HIP_CHECK(sp_stream_wait_polling(c_->stream));
     }
-    SP_HIP_CHECK(hipMemcpyAsync(d_air_prog_, &prog, sizeof(prog), hipMemcpyHostToDevice, c_->stream));
-    SP_HIP_CHECK(sp_stream_wait_polling(c_->stream));  // prog is a stack object
-    // --- boundary data and per-coset constants
+    // --- boundary constraints grouped by row (first appearance order): one factor (x - g^s) per distinct row
     std::vector<uint64_t> steps;
-    CompositionConsts K;
-    std::memset(&K, 0, composition_consts_bytes(1u << logb_));   // (the per-coset tables only as far as this proof's blowup factor reaches)
+    std::vector<std::vector<uint32_t>> by_row;
+    std::unordered_map<uint64_t, uint32_t> group_of;
     for (uint32_t j = 0; j < B; ++j) {
         const BoundaryConstraint& bc = air.boundary[j];
-        if (bc.col >= C_ || bc.step >= n_) return SP_E_INVALID_ARG;
-        auto it = std::find(steps.begin(), steps.end(), bc.step);
-        if (it == steps.end()) { steps.push_back(bc.step); it = steps.end() - 1; }
-        K.bden[j] = (uint32_t)(it - steps.begin());
-        K.bcol[j] = bc.col; K.bvalue[j] = bc.value; K.bstep[j] = bc.step;
+        if (bc.col >= C_ || bc.step >= n_) { sp_set_error("composition_air: boundary constraint outside the trace"); return SP_E_INVALID_ARG; }
+        auto ins = group_of.emplace(bc.step, (uint32_t)steps.size());
+        if (ins.second) { steps.push_back(bc.step); by_row.emplace_back(); }
+        by_row[ins.first->second].push_back(j);
     }
-    if (steps.size() > 3) { sp_set_error("composition: more than 3 distinct boundary steps"); return SP_E_UNSUPPORTED; }
-    std::vector<fe> points;
-    for (uint64_t st : steps) points.push_back(fe_pow_u64(g_, st));
-    K.h = h_;
-    K.n_boundary = B; K.n_transitions = T; K.main_cols = Cm_;
+    const uint32_t nd = (uint32_t)steps.size();
+    std::vector<uint32_t> order;                       // constraint at grouped position j'
+    std::vector<uint32_t> gend(nd);
+    for (uint32_t g = 0; g < nd; ++g) { order.insert(order.end(), by_row[g].begin(), by_row[g].end()); gend[g] = (uint32_t)order.size(); }
+    // --- the device copy: program header, ops, constants (then the RAP challenges) and the per-proof tables in one buffer sized by
+    //     this proof (grown on demand, kept across proofs), one upload
+    const uint32_t nterm = T + B;
+    size_t at = 0;
+    auto place = [&at](size_t bytes) { const size_t o = at; at = (at + bytes + 255) & ~size_t(255); return o; };
+    const size_t o_prog = place(sizeof(AirProgram)), o_ops = place(sizeof(AirOpDev) * dops.size()),
+                 o_consts = place(sizeof(fe) * (air.consts.size() + rap.size())), o_zf = place(sizeof(fe) * b),
+                 o_coef = place(sizeof(fe) * b * nterm), o_bval = place(sizeof(fe) * B), o_gpt = place(sizeof(fe) * nd),
+                 o_bstep = place(sizeof(uint64_t) * B), o_bcol = place(sizeof(uint32_t) * B), o_gend = place(sizeof(uint32_t) * nd);
+    if (at > air_buf_cap_) {
+        release(d_air_buf_, air_buf_cap_);
+        d_air_buf_ = nullptr; air_buf_cap_ = 0;
+        SP_TRY(alloc((void**)&d_air_buf_, at));
+        air_buf_cap_ = at;
+    }
+    std::vector<uint8_t>& up = h_air_up_;
+    up.assign(at, 0);
+    auto host_at = [&](size_t off) { return up.data() + off; };
+    auto dev_at = [&](size_t off) { return d_air_buf_ + off; };
+    prog.ops = reinterpret_cast<const AirOpDev*>(dev_at(o_ops));
+    prog.consts = reinterpret_cast<const fe*>(dev_at(o_consts));
+    std::memcpy(host_at(o_prog), &prog, sizeof(prog));
+    if (!dops.empty()) std::memcpy(host_at(o_ops), dops.data(), sizeof(AirOpDev) * dops.size());
+    fe* hconst = reinterpret_cast<fe*>(host_at(o_consts));
+    for (size_t i = 0; i < air.consts.size(); ++i) hconst[i] = air.consts[i];
+    for (size_t i = 0; i < rap.size(); ++i) hconst[air.consts.size() + i] = rap[i];
+    fe* hzf = reinterpret_cast<fe*>(host_at(o_zf));
+    fe* hcoef = reinterpret_cast<fe*>(host_at(o_coef));
+    fe* hbval = reinterpret_cast<fe*>(host_at(o_bval));
+    fe* hgpt = reinterpret_cast<fe*>(host_at(o_gpt));
+    uint64_t* hbstep = reinterpret_cast<uint64_t*>(host_at(o_bstep));
+    uint32_t* hbcol = reinterpret_cast<uint32_t*>(host_at(o_bcol));
+    std::memcpy(host_at(o_gend), gend.data(), sizeof(uint32_t) * nd);
+    for (uint32_t jp = 0; jp < B; ++jp) {
+        const BoundaryConstraint& bc = air.boundary[order[jp]];
+        hbval[jp] = bc.value; hbstep[jp] = bc.step; hbcol[jp] = bc.col;
+    }
+    std::vector<fe> points(nd);
+    for (uint32_t g = 0; g < nd; ++g) hgpt[g] = points[g] = fe_pow_u64(g_, steps[g]);
     {
         fe hn = fe_pow_u64(h_, n_);
         fe wb = host_primitive_root((int)logb_);
@@ -1109,35 +1142,60 @@ int StarkProver::composition_air(const AirDescHost& air, const std::vector<fe>& 
         fe xn = hn;
         for (uint32_t c = 0; c < b; ++c) {
             // degree adjustments x^(D - n (deg - 1)) and x^(D - n) with D = f n are powers of x^n (evaluator.rs:142-154, :78-82)
-            for (uint32_t k = 0; k < T; ++k) K.coef[c][k] = fe_add(fe_mul(t_alpha[k], fe_pow_u64(xn, f - air.degrees[k] + 1)), t_beta[k]);
-            for (uint32_t j = 0; j < B; ++j) K.coef[c][T + j] = fe_add(fe_mul(b_alpha[j], fe_pow_u64(xn, f - 1)), b_beta[j]);
+            fe* row = hcoef + (size_t)c * nterm;
+            for (uint32_t k = 0; k < T; ++k) row[k] = fe_add(fe_mul(t_alpha[k], fe_pow_u64(xn, f - air.degrees[k] + 1)), t_beta[k]);
+            const fe xb = fe_pow_u64(xn, f - 1);
+            for (uint32_t jp = 0; jp < B; ++jp) row[T + jp] = fe_add(fe_mul(b_alpha[order[jp]], xb), b_beta[order[jp]]);
             zf[c] = fe_sub(xn, fe_one());
             xn = fe_mul(xn, wb);
         }
         host_batch_inverse(zf);
-        for (uint32_t c = 0; c < b; ++c) K.zerofier[c] = zf[c];
+        for (uint32_t c = 0; c < b; ++c) hzf[c] = zf[c];
     }
+    SP_HIP_CHECK(hipMemcpyAsync(d_air_buf_, up.data(), at, hipMemcpyHostToDevice, c_->stream));
+    AirCompTables tabs;
+    tabs.h = h_; tabs.T = T; tabs.B = B; tabs.ndist = nd;
+    tabs.zerofier = reinterpret_cast<const fe*>(dev_at(o_zf));
+    tabs.coef = reinterpret_cast<const fe*>(dev_at(o_coef));
+    tabs.bvalue = reinterpret_cast<const fe*>(dev_at(o_bval));
+    tabs.bcol = reinterpret_cast<const uint32_t*>(dev_at(o_bcol));
+    tabs.bstep = reinterpret_cast<const uint64_t*>(dev_at(o_bstep));
+    tabs.gpoint = reinterpret_cast<const fe*>(dev_at(o_gpt));
+    tabs.gend = reinterpret_cast<const uint32_t*>(dev_at(o_gend));
     offsets_ = air.offsets;
-    return composition_core(K, points, d_air_prog_, d_ex_roots_, allow_sub, root_out);
+    return composition_core(nullptr, points, reinterpret_cast<const AirProgram*>(dev_at(o_prog)), &tabs, d_ex_roots_, allow_sub, root_out);
 }
 
-// Shared second half of round 2: K (per-coset coefficients, zerofier, boundary data) is complete; `points` are the distinct
-// boundary points g^step.  prog_dev == nullptr: the Cairo kernels; otherwise the constraint program of a generic AIR.
+// Shared second half of round 2.  Cairo (prog_dev == nullptr): K (per-coset coefficients, zerofier, boundary data) is complete and
+// `points` are the distinct boundary points g^step, one inverse array each.  A program AIR: its tables (air_tabs) are uploaded,
+// `points` lists its distinct boundary points, and one inverse array 1 / Z_B(x) serves all of them.
 // allow_sub_coset: the caller knows deg H < 2n for a constraint-satisfying trace.
-int StarkProver::composition_core(const CompositionConsts& K, const std::vector<fe>& points, const AirProgram* prog_dev,
-                                  const fe* ex_roots_dev, bool allow_sub_coset, uint8_t root_out[32]) {
+int StarkProver::composition_core(const CompositionConsts* K, const std::vector<fe>& points, const AirProgram* prog_dev,
+                                  const AirCompTables* air_tabs, const fe* ex_roots_dev, bool allow_sub_coset, uint8_t root_out[32]) {
     const fe* roots = nullptr;
     SP_TRY(c_->ntt->roots((int)logN_, &roots));
     fe* comp = nullptr;                      // [N] whole-domain composition evaluations (exceptional paths only, fetched below)
     const uint32_t nd = (uint32_t)points.size();
     auto evaluate = [&](uint64_t count, uint32_t stride_log, const fe* binv, fe* out) -> int {
-        if (prog_dev) return air_composition(c_->stream, d_lde_, count, Nl_, stride_log, logN_, logb_, roots, d_comp_consts_, prog_dev, ex_roots_dev, binv, out, logG_, rank_);
+        if (prog_dev) return air_composition(c_->stream, d_lde_, count, Nl_, stride_log, logN_, logb_, roots, *air_tabs, prog_dev, ex_roots_dev, binv, out, logG_, rank_);
         return cairo_composition(c_->stream, d_lde_, count, Nl_, stride_log, logN_, logb_, roots, d_comp_consts_, binv, out, logG_, rank_);
+    };
+    // boundary inverses of `count` points x_i = hp w^i (roots of 2^logM, shard map sm): Cairo [nd][count] 1 / (x - g^s), a program
+    // AIR [count] 1 / Z_B(x); scratch: [3 count]
+    const fe* d_bpts = prog_dev ? air_tabs->gpoint : nullptr;
+    auto boundary_inverses = [&](fe* binv, fe* inv_scratch, uint64_t count, uint32_t logM, const fe* roots_m, const fe& hp, ShardMap sm) -> int {
+        if (!nd) return SP_OK;
+        if (prog_dev) {
+            SP_TRY(boundary_vanishing(c_->stream, binv, count, logM, roots_m, hp, d_bpts, nd, sm));
+            return batch_inverse(c_->stream, binv, inv_scratch, count, c_->d_flag);
+        }
+        SP_TRY(coset_minus_points(c_->stream, binv, count, logM, roots_m, hp, points.data(), nd, sm));
+        return batch_inverse(c_->stream, binv, inv_scratch, (uint64_t)nd * count, c_->d_flag);
     };
     SP_HIP_CHECK(hipSetDevice(c_->device));
     const bool prechecked = check_pending_ && !prog_dev;   // composition_precheck queued the constraint check (and cleared the flag) already
     check_pending_ = false;
-    SP_HIP_CHECK(hipMemcpyAsync(d_comp_consts_, &K, composition_consts_bytes(1u << logb_), hipMemcpyHostToDevice, c_->stream));
+    if (!prog_dev) SP_HIP_CHECK(hipMemcpyAsync(d_comp_consts_, K, composition_consts_bytes(1u << logb_), hipMemcpyHostToDevice, c_->stream));
     if (!prechecked) SP_HIP_CHECK(hipMemsetAsync(c_->d_flag, 0, sizeof(int), c_->stream));
     // A trace that satisfies its constraints gives deg H < 2n, and then 2n evaluations fix H.  Decide that EXACTLY by
     // checking the constraints on the trace itself (n rows, no divisions): clean -> evaluate the composition on the 2n
@@ -1151,7 +1209,7 @@ int StarkProver::composition_core(const CompositionConsts& K, const std::vector<
     // evaluations are all-gathered and the pair (0, b/2) is interpolated everywhere
     bool pair_path = allow_sub_coset && !sub_coset && G_ > 1 && logb_ == logG_ && d_post_comp0_;
     if (sub_coset || pair_path) {
-        if (prog_dev) SP_TRY(air_trace_check(c_->stream, d_trace_, n_, d_comp_consts_, prog_dev, c_->d_flag));
+        if (prog_dev) SP_TRY(air_trace_check(c_->stream, d_trace_, n_, *air_tabs, prog_dev, c_->d_flag));
         else if (!prechecked) SP_TRY(cairo_trace_check(c_->stream, d_trace_, n_, d_comp_consts_, c_->d_flag, check_row0(), check_rows()));
         if (!prog_dev && world_ > 1 && n_ >= 256ull * world_) {
             // every rank checked its own n / world rows of the (replicated) trace: one flag per rank, combined everywhere
@@ -1182,14 +1240,13 @@ int StarkProver::composition_core(const CompositionConsts& K, const std::vector<
         const fe hp = fe_mul(h_, fe_pow_u64(wN, rank_));
         fe* binv = d_scratch_;                    // [ndist][2n]
         fe* inv_scratch = d_scratch_ + 3 * M;     // [3 * 2n]
-        bool pref = bpre_valid_ && nd == bpre_points_.size();
+        bool pref = !prog_dev && bpre_valid_ && nd == bpre_points_.size();
         for (uint32_t j = 0; pref && j < nd; ++j) pref = fe_eq(points[j], bpre_points_[j]);
         if (nd && pref) {                         // computed beside round 1 (prefetch_boundary_inverses)
             binv = d_bpre_;
             SP_HIP_CHECK(hipStreamWaitEvent(c_->stream, ev_side_bnd_, 0));
-        } else if (nd) {
-            SP_TRY(coset_minus_points(c_->stream, binv, M, logn_ + 1, roots_m, hp, points.data(), nd, ShardMap{0, 0, 0}));
-            SP_TRY(batch_inverse(c_->stream, binv, inv_scratch, (uint64_t)nd * M, c_->d_flag));
+        } else {
+            SP_TRY(boundary_inverses(binv, inv_scratch, M, logn_ + 1, roots_m, hp, ShardMap{0, 0, 0}));
         }
         if (nd && pref) SP_HIP_CHECK(hipMemcpyAsync(&flag_pref, d_flag_side_ + 1, sizeof(int), hipMemcpyDeviceToHost, c_->stream));
         fe* comp2 = d_h12s_;                      // [2n] evaluations H(h w_2n^i), then [H1s | H2s]
@@ -1205,10 +1262,7 @@ int StarkProver::composition_core(const CompositionConsts& K, const std::vector<
     } else if (pair_path) {
         fe* binv = d_scratch_;                  // [ndist][n]
         fe* inv_scratch = d_scratch_ + 3 * Nl_;  // [3 n]
-        if (nd) {
-            SP_TRY(coset_minus_points(c_->stream, binv, Nl_, logN_, roots, h_, points.data(), nd, shard_map()));
-            SP_TRY(batch_inverse(c_->stream, binv, inv_scratch, (uint64_t)nd * Nl_, c_->d_flag));
-        }
+        SP_TRY(boundary_inverses(binv, inv_scratch, Nl_, logN_, roots, h_, shard_map()));
         SP_TRY(evaluate(Nl_, 0, binv, d_local_));                   // H on this rank's coset
         SP_HIP_CHECK(hipMemcpyAsync(&flag, c_->d_flag, sizeof(int), hipMemcpyDeviceToHost, c_->stream));
         SP_TRY(ensure_gather((uint64_t)world_ * Nl_));
@@ -1226,10 +1280,7 @@ int StarkProver::composition_core(const CompositionConsts& K, const std::vector<
         fe* comp_local = G_ == 1 ? comp : d_local_;
         fe* binv = d_scratch_;                  // [ndist][Nl]
         fe* inv_scratch = d_scratch_ + 3 * Nl_;  // [3 Nl]
-        if (nd) {
-            SP_TRY(coset_minus_points(c_->stream, binv, Nl_, logN_, roots, h_, points.data(), nd, shard_map()));
-            SP_TRY(batch_inverse(c_->stream, binv, inv_scratch, (uint64_t)nd * Nl_, c_->d_flag));
-        }
+        SP_TRY(boundary_inverses(binv, inv_scratch, Nl_, logN_, roots, h_, shard_map()));
         SP_TRY(evaluate(Nl_, 0, binv, comp_local));
         if (G_ > 1) {  // composition-polynomial reduction: all-gather the per-coset evaluations
             SP_TRY(ensure_gather((uint64_t)world_ * Nl_));
@@ -1370,11 +1421,12 @@ int StarkProver::ood(const fe& z, fe* h1_z2, fe* h2_z2, std::vector<fe>& trace_o
         std::vector<fe> mine;
         SP_TRY(eval_bitrev(c_, d_coeffs_ + (uint64_t)first_col(rank_) * n_, n_, cpr, logn_, ys, d_scratch_, scratch_elems(), mine, &prefetch));
         const size_t blk = (size_t)cpr * R;
-        if (!d_small_) SP_TRY(alloc((void**)&d_small_, sizeof(fe) * (1 + (size_t)world_) * 64 * AIR_MAX_OFFSETS));
+        const size_t blk_cap = (size_t)C_ * AIR_MAX_OFFSETS;   // >= cpr * R: one block per rank
+        if (!d_small_) SP_TRY(alloc((void**)&d_small_, sizeof(fe) * (1 + (size_t)world_) * blk_cap));
         SP_HIP_CHECK(hipMemcpyAsync(d_small_, mine.data(), blk * sizeof(fe), hipMemcpyHostToDevice, c_->stream));
-        SP_TRY(all_gather(d_small_, d_small_ + 64 * AIR_MAX_OFFSETS, blk * sizeof(fe)));
+        SP_TRY(all_gather(d_small_, d_small_ + blk_cap, blk * sizeof(fe)));
         std::vector<fe> all(blk * world_);
-        SP_HIP_CHECK(hipMemcpy(all.data(), d_small_ + 64 * AIR_MAX_OFFSETS, all.size() * sizeof(fe), hipMemcpyDeviceToHost));
+        SP_HIP_CHECK(hipMemcpy(all.data(), d_small_ + blk_cap, all.size() * sizeof(fe), hipMemcpyDeviceToHost));
         tr.resize((size_t)C_ * R);
         for (uint32_t role = 0; role < G_; ++role)
             std::copy(all.begin() + (size_t)role * blk, all.begin() + (size_t)(role + 1) * blk, tr.begin() + (size_t)first_col(role) * R);
@@ -1402,18 +1454,22 @@ int StarkProver::deep_fri_begin(const fe& gamma, const fe& gamma_p, const std::v
     SP_HIP_CHECK(hipSetDevice(c_->device));
     const fe* roots = nullptr;
     SP_TRY(c_->ntt->roots((int)logN_, &roots));
+    if (R > AIR_MAX_OFFSETS) return SP_E_INVALID_ARG;
     DeepConsts K;
     std::memset(&K, 0, sizeof(K));
     K.gamma_h1 = gamma; K.gamma_h2 = gamma_p;
     K.c_h = fe_add(fe_mul(gamma, h1_z2_), fe_mul(gamma_p, h2_z2_));
     K.cols = C_; K.rows = R;
     for (uint32_t k = 0; k < AIR_MAX_OFFSETS; ++k) K.c_t[k] = fe_zero();
+    std::vector<uint8_t> up(deep_gammas_at() + sizeof(fe) * R * C_);
+    fe* gam = reinterpret_cast<fe*>(up.data() + deep_gammas_at());
     for (uint32_t j = 0; j < C_; ++j)
         for (uint32_t k = 0; k < R; ++k) {
-            K.gammas[k][j] = tg[(size_t)j * R + k];  // reference prover.rs:457-476: gamma index = j * frame_len + k
+            gam[(size_t)k * C_ + j] = tg[(size_t)j * R + k];  // reference prover.rs:457-476: gamma index = j * frame_len + k
             K.c_t[k] = fe_add(K.c_t[k], fe_mul(tg[(size_t)j * R + k], trace_ood_[(size_t)k * C_ + j]));
         }
-    SP_HIP_CHECK(hipMemcpyAsync(d_deep_consts_, &K, sizeof(K), hipMemcpyHostToDevice, c_->stream));
+    std::memcpy(up.data(), &K, sizeof(K));
+    SP_HIP_CHECK(hipMemcpyAsync(d_deep_consts_, up.data(), up.size(), hipMemcpyHostToDevice, c_->stream));
     SP_HIP_CHECK(sp_stream_wait_polling(c_->stream));
     fe pts[AIR_MAX_OFFSETS + 1];                       // z g^ofs_k for every frame row, then z^2
     for (uint32_t k = 0; k < R; ++k) pts[k] = fe_mul(z_, fe_pow_u64(g_, offsets_[k]));
@@ -1450,9 +1506,9 @@ int StarkProver::deep_fri_begin(const fe& gamma, const fe& gamma_p, const std::v
         if (fri_sharded(0) && logb_ == logG_) {
             // one coset per rank and a sharded layer 0: the n points of that coset in natural order ARE this rank's share of the layer
             // (local index = row of the coset), so the quotient form is written there and nothing is interpolated or extended
-            SP_TRY(deep_composition(c_->stream, d_lde_, d_h12_, d_h12_ + Nl_, n_, Nl_, shift, d_deep_consts_, inv, d_fri_evals_[0], lde_order(), R));
+            SP_TRY(deep_composition(c_->stream, d_lde_, d_h12_, d_h12_ + Nl_, n_, Nl_, shift, d_deep_consts_, d_deep_gammas_, inv, d_fri_evals_[0], lde_order(), R));
         } else {
-        SP_TRY(deep_composition(c_->stream, d_lde_, d_h12_, d_h12_ + Nl_, n_, Nl_, shift, d_deep_consts_, inv, p0n, lde_order(), R));
+        SP_TRY(deep_composition(c_->stream, d_lde_, d_h12_, d_h12_ + Nl_, n_, Nl_, shift, d_deep_consts_, d_deep_gammas_, inv, p0n, lde_order(), R));
         // coefficients c_j h^j in bit-reversed order: inverse DFT over the coset, times n^-1 w_N^(-c0 j)
         SP_TRY(c_->ntt->dif_natural_to_bitrev_inverse(p0n, (int)logn_, 1, n_, d_post_deep_));   // n^-1 w_N^(-c0 j): setup()
         // FRI layer 0: the evaluations this rank holds (local natural order) when the layer is sharded, the whole domain otherwise
@@ -1470,7 +1526,7 @@ int StarkProver::deep_fri_begin(const fe& gamma, const fe& gamma_p, const std::v
         SP_TRY(coset_minus_points(c_->stream, inv, Nl_, logN_, roots, h_, pts, npts, shard_map()));
         SP_TRY(batch_inverse(c_->stream, inv, inv_scratch, (uint64_t)npts * Nl_, c_->d_flag));
         fe* p0_local = (G_ == 1 || fri_sharded(0)) ? d_fri_evals_[0] : d_local_;   // local natural order
-        SP_TRY(deep_composition(c_->stream, d_lde_, d_h12_, d_h12_ + Nl_, Nl_, Nl_, 0, d_deep_consts_, inv, p0_local, lde_order(), R));
+        SP_TRY(deep_composition(c_->stream, d_lde_, d_h12_, d_h12_ + Nl_, Nl_, Nl_, 0, d_deep_consts_, d_deep_gammas_, inv, p0_local, lde_order(), R));
         if (G_ > 1 && !fri_sharded(0)) {
             SP_TRY(ensure_gather((uint64_t)world_ * Nl_));
             SP_TRY(all_gather(p0_local, d_gather_, Nl_ * sizeof(fe), true));

@@ -175,9 +175,14 @@ class StarkProver : public sp_deletable {
     // per-level power tables of up to five points, which dominate for tiny traces)
     // order of the evaluations inside the trace / composition LDE columns this rank holds (coset-major, common.h)
     LdeOrder lde_order() const { return LdeOrder{1u, logb_ - logG_, logn_}; }
-    uint64_t scratch_elems() const { return std::max<uint64_t>(std::max<uint64_t>(Nl_ * 7, 4 * n_), 8192); }
-    int composition_core(const CompositionConsts& K, const std::vector<fe>& points, const AirProgram* prog_dev, const fe* ex_roots_dev,
-                         bool allow_sub_coset, uint8_t root_out[32]);
+    // (beyond 64 columns also the first level of the out-of-domain fold of C columns at up to AIR_MAX_OFFSETS points, eval_bitrev in
+    // prover.cpp: up to 64 columns the terms above hold it)
+    uint64_t scratch_elems() const {
+        const uint64_t ood = C_ <= 64 ? 0 : 2ull * C_ * AIR_MAX_OFFSETS * std::max<uint64_t>(1, n_ >> 8) + 8ull * AIR_MAX_OFFSETS * 256;
+        return std::max<uint64_t>(std::max<uint64_t>(std::max<uint64_t>(Nl_ * 7, 4 * n_), 8192), ood);
+    }
+    int composition_core(const CompositionConsts* K, const std::vector<fe>& points, const AirProgram* prog_dev, const AirCompTables* air_tabs,
+                         const fe* ex_roots_dev, bool allow_sub_coset, uint8_t root_out[32]);
 
     sp_ctx* c_;
     ProofOptionsHost opt_{};
@@ -247,8 +252,12 @@ class StarkProver : public sp_deletable {
     CompositionConsts* d_comp_consts_chk_ = nullptr;   // the constants of an early constraint check (composition_precheck)
     std::unique_ptr<CompositionConsts> h_comp_chk_;    // its host copy (stays put until the upload has happened)
     bool check_pending_ = false;
-    AirProgram* d_air_prog_ = nullptr; fe* d_ex_roots_ = nullptr; uint32_t ex_roots_cap_ = 0;
+    // program AIRs: header, ops, constants and per-proof tables in one buffer (composition_air), grown on demand
+    uint8_t* d_air_buf_ = nullptr; size_t air_buf_cap_ = 0; std::vector<uint8_t> h_air_up_;
+    fe* d_ex_roots_ = nullptr; uint32_t ex_roots_cap_ = 0;
     DeepConsts* d_deep_consts_ = nullptr;
+    fe* d_deep_gammas_ = nullptr;                      // [AIR_MAX_OFFSETS][C], behind the DeepConsts in the same allocation
+    static size_t deep_gammas_at() { return (sizeof(DeepConsts) + 255) & ~size_t(255); }
     unsigned long long* d_nonce_ = nullptr;
     uint8_t* d_fri_chain_ = nullptr; uint32_t fri_chain_layers_ = 0;   // [state 32 B][L x constants][L x zeta constants][L x roots]
     void* h_pin_ = nullptr;   // 4 KB of pinned host memory for readback()
@@ -302,7 +311,9 @@ struct ProverHolder : public sp_deletable {
     Openings open;
     std::vector<uint8_t> trace_evals, comp_evals, fri_evals, fri_evals_sym;
     float round_ms[5] = {0, 0, 0, 0, 0};
+    hipEvent_t air_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // round timing of air_prove (created once, kept)
     explicit ProverHolder(sp_ctx* c) : prover(c) {}
+    ~ProverHolder() override { for (auto& e : air_ev) if (e) (void)hipEventDestroy(e); }
 };
 ProverHolder* prover_holder(sp_ctx* c, bool create);
 
@@ -313,7 +324,8 @@ int cairo_prove(sp_ctx* ctx, const uint8_t* main_trace, uint64_t n, uint32_t col
                 StarkProver::TraceSource src = StarkProver::TRACE_HOST_ROWS, int col_enc = -1, uint64_t col_stride = 0);
 // Whole proof for an AIR given as a constraint program: `prove::<F, A>` (reference src/starks/prover.rs:532-766) + serialize.
 // main_trace: row-major n x air.main_cols in the context encoding (host memory).
+// round_ms (nullable): device time of rounds 1 - 4 in [1..4], as cairo_prove.
 int air_prove(sp_ctx* ctx, const AirDescHost& air, const uint8_t* main_trace, uint64_t n, const ProofOptionsHost& opt,
-              std::vector<uint8_t>& proof_out);
+              std::vector<uint8_t>& proof_out, float round_ms[5] = nullptr);
 
 }  // namespace sp

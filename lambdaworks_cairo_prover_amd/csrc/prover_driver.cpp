@@ -268,16 +268,28 @@ int cairo_prove(sp_ctx* ctx, const uint8_t* main_trace, uint64_t n, uint32_t col
 // the descriptor - RAP challenges (n_rap field samples), auxiliary trace (by kind, built on the host: the example AIRs are
 // tiny), boundary constraints, transition program.
 int air_prove(sp_ctx* ctx, const AirDescHost& air, const uint8_t* main_trace, uint64_t n, const ProofOptionsHost& opt,
-              std::vector<uint8_t>& proof_out) {
+              std::vector<uint8_t>& proof_out, float round_ms[5]) {
     try {
-        if (air.main_cols == 0 || air.main_cols + air.aux_cols > 64) { sp_set_error("air_prove: column count out of range"); return SP_E_INVALID_ARG; }
+        if (air.main_cols == 0 || (uint64_t)air.main_cols + air.aux_cols > (uint64_t)AIR_MAX_COLS) {
+            sp_set_error("air_prove: column count out of range (1 .. 1024 columns, main + aux)");
+            return SP_E_INVALID_ARG;
+        }
+        if (air.boundary.size() > (size_t)AIR_MAX_BOUNDARY) { sp_set_error("air_prove: more than 4096 boundary constraints"); return SP_E_INVALID_ARG; }
+        if (air.consts.size() > (size_t)AIR_MAX_CONSTS) { sp_set_error("air_prove: more than 4096 constants"); return SP_E_INVALID_ARG; }
+        if (air.consts.size() + air.n_rap > 65535) { sp_set_error("air_prove: constants and RAP challenges exceed the 16-bit operand range"); return SP_E_INVALID_ARG; }
+        if (air.ops.size() > (size_t)AIR_MAX_OPS) { sp_set_error("air_prove: more than 65535 ops"); return SP_E_INVALID_ARG; }
         StarkProver* P = &prover_holder(ctx, true)->prover;   // kept (with its device buffers) across proofs of the same shape on this context
         if (opt.fri_number_of_queries == 0) { sp_set_error("prove: fri_number_of_queries must be at least 1 (the reference emits a proof without openings for 0; this prover does not)"); return SP_E_INVALID_ARG; }
+        hipEvent_t* ev = prover_holder(ctx, true)->air_ev;
+        if (round_ms)
+            for (int k = 0; k < 5; ++k) if (!ev[k]) SP_HIP_CHECK(hipEventCreate(&ev[k]));
+        auto mark = [&](int k) -> int { if (round_ms) SP_HIP_CHECK(hipEventRecord(ev[k], ctx->stream)); return SP_OK; };
         SP_TRY(P->setup(n, air.main_cols, air.aux_cols, false, opt));
         HostTranscript tr;
         uint8_t root[32];
         std::vector<std::array<uint8_t, 32>> roots;
         // ---- round 1 (reference prover.rs:187-224)
+        SP_TRY(mark(0));
         SP_TRY(P->commit_trace(0, main_trace, air.main_cols, root));
         roots.emplace_back(); std::memcpy(roots.back().data(), root, 32);
         tr.append(root, 32);
@@ -320,6 +332,7 @@ int air_prove(sp_ctx* ctx, const AirDescHost& air, const uint8_t* main_trace, ui
             tr.append(root, 32);
         }
         // ---- round 2 (reference prover.rs:597-635)
+        SP_TRY(mark(1));
         const size_t B = air.boundary.size(), T = air.degrees.size();
         std::vector<fe> b_alpha(B), b_beta(B), t_alpha(T), t_beta(T);
         for (auto& x : b_alpha) x = tr.to_field();
@@ -329,6 +342,7 @@ int air_prove(sp_ctx* ctx, const AirDescHost& air, const uint8_t* main_trace, ui
         SP_TRY(P->composition_air(air, rap, b_alpha, b_beta, t_alpha, t_beta, root));
         uint8_t comp_root[32]; std::memcpy(comp_root, root, 32);
         tr.append(root, 32);
+        SP_TRY(mark(2));
         // ---- round 3 (reference prover.rs:652-684)
         const uint32_t logn = (uint32_t)sp_log2_exact(n), logN = logn + (uint32_t)sp_log2_exact(opt.blowup_factor);
         fe hinv = fe_inv(fe_from_u64(opt.coset_offset));
@@ -339,6 +353,7 @@ int air_prove(sp_ctx* ctx, const AirDescHost& air, const uint8_t* main_trace, ui
         SP_TRY(P->ood(z, &h1z, &h2z, ood));
         tr.append_felt(h1z); tr.append_felt(h2z);
         for (auto& e : ood) tr.append_felt(e);
+        SP_TRY(mark(3));
         // ---- round 4 (reference prover.rs:327-404)
         fe gamma = tr.to_field(), gamma_p = tr.to_field();
         std::vector<fe> tg((size_t)P->frame_rows() * P->cols());
@@ -382,7 +397,12 @@ int air_prove(sp_ctx* ctx, const AirDescHost& air, const uint8_t* main_trace, ui
         for (auto& x : iotas) x = tr.to_usize() % P->N();
         Openings& o = prover_holder(ctx, true)->open;     // (kept with the prover: its arrays are reused by the next proof)
         SP_TRY(P->open(iotas, o, true));   // opened values as wire bytes (encoded on the device)
+        SP_TRY(mark(4));
         SP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        if (round_ms) {
+            round_ms[0] = 0.f;
+            for (int r = 0; r < 4; ++r) SP_HIP_CHECK(hipEventElapsedTime(&round_ms[r + 1], ev[r], ev[r + 1]));
+        }
         serialize_proof(n, roots, P->cols(), ood, comp_root, h1z, h2z, fri_roots, last_value, iotas, o, nonce, proof_out);
         return SP_OK;
     } catch (const std::exception& e) {

@@ -397,7 +397,7 @@ int StarkProver::commit_trace_pipelined(int segment, const uint8_t* rows_host, u
     // usable when all of it has landed, so narrow groups keep the compute stream fed; and since the gather writes a chunk column by
     // column (host_gather_block) wider groups no longer stream better either - four-column groups: 30.1 ms at config #4, pairs 29.3.
     static const uint32_t maxw_env = [] { const char* e = std::getenv("SP_UPLOAD_MAXW"); return e ? (uint32_t)std::min(8, std::max(2, std::atoi(e))) : 0u; }();
-    const uint32_t maxw = maxw_env ? maxw_env : 2u;
+    const uint32_t maxw0 = maxw_env ? maxw_env : 2u;
     // Columns that cross as bitmaps go eight at a time: the threads read 256 contiguous bytes of every row per pass instead of one
     // 64-byte line (tools/experiments/gather_bench.cpp on an MI355X host, 24 threads, 16 flag columns of 2^19 rows: 3.5 ms as eight
     // pair-wide passes, 1.8 ms as two 8-wide ones, 1.6 ms as one) and the link carries next to nothing for them either way.  In the
@@ -410,11 +410,17 @@ int StarkProver::commit_trace_pipelined(int segment, const uint8_t* rows_host, u
     {
         const uint32_t c_end = c_begin + cols, p_end = std::min(c_end, std::max(c_begin, binary_cols));
         for (uint32_t c = c_begin; c < p_end;) { const uint32_t w = std::min(packw, p_end - c); packed_g.push_back(Group{c, w}); c += w; }
-        for (uint32_t done = 0, left = c_end - p_end; done < left;) {
-            uint32_t w = done < 2 ? 1u : std::min<uint32_t>(maxw, std::max<uint32_t>(2, 2 * ((done + 1) / 2)));
-            if (left - done <= w + 1) w = left - done;     // no one-column tail
-            wide_g.push_back(Group{p_end + done, w});
-            done += w;
+        // (a table wider than the group timers reach - UPLOAD_MAX_GROUPS, a program AIR of up to 1024 columns - takes wider groups,
+        // just wide enough that every group has its timers)
+        for (uint32_t maxw = maxw0;; maxw *= 2) {
+            wide_g.clear();
+            for (uint32_t done = 0, left = c_end - p_end; done < left;) {
+                uint32_t w = done < 2 ? 1u : std::min<uint32_t>(maxw, std::max<uint32_t>(2, 2 * ((done + 1) / 2)));
+                if (left - done <= w + 1) w = left - done;     // no one-column tail
+                wide_g.push_back(Group{p_end + done, w});
+                done += w;
+            }
+            if (packed_g.size() + wide_g.size() <= (size_t)UPLOAD_MAX_GROUPS || maxw >= cols) break;
         }
     }
     const uint32_t groups = (uint32_t)(packed_g.size() + wide_g.size());

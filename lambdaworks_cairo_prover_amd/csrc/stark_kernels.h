@@ -13,7 +13,7 @@ namespace sp {
 constexpr int CAIRO_MAX_TRANSITIONS = 50;
 constexpr int CAIRO_MAX_BOUNDARY = 8;
 constexpr int CAIRO_MAX_BLOWUP = 128;       // ProofOptions::blowup_factor is a u8 power of two (options.rs:21-26)
-// program AIRs (sp_air_desc): up to 64 transition constraints and 16 boundary constraints share the constant block below
+// the Cairo AIR's constant block (program AIRs keep theirs in AirCompTables, sized by the proof)
 constexpr int COMP_MAX_BOUNDARY = 16;
 constexpr int COMP_MAX_TERMS = 64 + COMP_MAX_BOUNDARY;
 
@@ -65,7 +65,10 @@ int cairo_composition(hipStream_t st, const fe* lde, uint64_t count, uint64_t co
 int cairo_trace_check(hipStream_t st, const fe* trace, uint64_t n, const CompositionConsts* consts_dev, int* flag_dev, uint64_t row0 = 0, uint64_t rows = 0);
 
 // ---- AIRs given as a constraint program (include/stark252_hip.h sp_air_desc; reference trait src/starks/traits.rs:15-119)
-constexpr int AIR_MAX_OPS = 2048, AIR_MAX_LIVE = 64, AIR_MAX_CONSTS = 96, AIR_MAX_OFFSETS = 8, AIR_MAX_EXEMPT_KINDS = 4, AIR_MAX_TRANSITIONS = 64;
+// Bounds of sp_air_prove (sp_air_limits reports them): columns, transitions, frame rows, boundary constraints (on any rows),
+// constants (RAP challenges come after them), ops (what the 16-bit operand indices of sp_air_op address), values alive at once.
+constexpr int AIR_MAX_COLS = 1024, AIR_MAX_TRANSITIONS = 64, AIR_MAX_OFFSETS = 8, AIR_MAX_BOUNDARY = 4096, AIR_MAX_CONSTS = 4096,
+              AIR_MAX_OPS = 65535, AIR_MAX_LIVE = 64, AIR_MAX_EXEMPT_KINDS = 4;
 // Device form of one op: the host assigns every value a slot of a small per-point value file (liveness analysis in
 // composition_air), so a long straight-line program needs AIR_MAX_LIVE values per point, not one per op.
 //   0 LOAD(a = row, b = col) -> dst   1 CONST(a = idx) -> dst   2 ADD / 3 SUB / 4 MUL (a, b = slots) -> dst   5 OUT(a = constraint, b = slot)
@@ -75,15 +78,38 @@ struct AirProgram {
     uint32_t ex_kind[AIR_MAX_TRANSITIONS];    // per constraint: 0 = enforced on every row, else 1 + index into ex_count
     uint32_t ex_count[AIR_MAX_EXEMPT_KINDS];  // rows exempted for that kind (the last ex_count rows of the trace)
     uint32_t ex_rows[AIR_MAX_TRANSITIONS];    // per constraint: its own exemption count (trace check)
-    AirOpDev ops[AIR_MAX_OPS];
-    fe consts[AIR_MAX_CONSTS];                // constants followed by the RAP challenges
+    const AirOpDev* ops;                      // [n_ops]   (device arrays sized by the program, beside this header)
+    const fe* consts;                         // constants followed by the RAP challenges
 };
-// ConstraintEvaluator::evaluate (evaluator.rs:38-260) for a program AIR; K carries the per-coset coefficients, zerofier and
-// boundary data exactly as for Cairo (its Cairo-only fields are ignored); ex_roots[j] = g^(n-1-j).
+// Per-proof composition data of a program AIR, in device memory sized by the proof (every lane of a launch reads the same
+// entry: uniform loads).  Boundary constraints are grouped by row: group g holds constraints [gend[g-1], gend[g]) on the row
+// whose point is gpoint[g] = g^step.
+struct AirCompTables {
+    fe h;                      // coset offset
+    uint32_t T, B, ndist;      // transitions, boundary constraints, distinct boundary rows
+    const fe* zerofier;        // [b]  1/(x^n - 1) per coset (evaluator.rs:156-171)
+    const fe* coef;            // [b][T + B]  alpha_k x^(D - D_k) + beta_k per coset: transitions, then boundary (in group order)
+    const fe* bvalue;          // [B]
+    const uint32_t* bcol;      // [B]
+    const uint64_t* bstep;     // [B]  (trace check)
+    const fe* gpoint;          // [ndist]
+    const uint32_t* gend;      // [ndist]
+};
+// zb[i] = prod_g (x_i - point[g]) over the ndist boundary points (device array), x_i = h w_N^i as coset_minus_points maps
+// i (shard included); the caller inverts it with batch_inverse.  Reference evaluator.rs:56-116 divides every boundary
+// constraint by its own zerofier; the sum of those quotients over one common denominator is what air_composition adds.
+int boundary_vanishing(hipStream_t st, fe* zb, uint64_t N, uint32_t logN, const fe* roots_N, const fe& h, const fe* points_dev, uint32_t ndist,
+                       ShardMap shard = ShardMap{0, 0, 0});
+// ConstraintEvaluator::evaluate (evaluator.rs:38-260) for a program AIR.  Transition terms as for Cairo; the boundary terms
+// sum_j coef_j (t_col_j(x) - v_j) / (x - g^step_j) accumulate row group by row group as one fraction A / Z_B(x)
+// (A <- A (x - g^s) + S_s P, P <- P (x - g^s)), finished with zbinv[i] = 1 / Z_B(x_i) (boundary_vanishing + batch_inverse).
+// ex_roots[j] = g^(n-1-j).
 int air_composition(hipStream_t st, const fe* lde, uint64_t count, uint64_t col_len, uint32_t stride_log, uint32_t logN, uint32_t logb,
-                    const fe* roots_N, const CompositionConsts* consts_dev, const AirProgram* prog_dev, const fe* ex_roots,
-                    const fe* binv, fe* out, uint32_t shard_log = 0, uint32_t shard_rank = 0);
-int air_trace_check(hipStream_t st, const fe* trace, uint64_t n, const CompositionConsts* consts_dev, const AirProgram* prog_dev, int* flag_dev);
+                    const fe* roots_N, AirCompTables tabs, const AirProgram* prog_dev, const fe* ex_roots,
+                    const fe* zbinv, fe* out, uint32_t shard_log = 0, uint32_t shard_rank = 0);
+// validate_trace (debug.rs:13-104): the transition constraints on every row (one thread per row), then the boundary
+// values (one thread per constraint); *flag_dev |= 1 on any violation.
+int air_trace_check(hipStream_t st, const fe* trace, uint64_t n, AirCompTables tabs, const AirProgram* prog_dev, int* flag_dev);
 
 // Split of the composition polynomial (reference src/starks/prover.rs:250-252, evaluation_table.rs:27-33):
 // X = unscaled bit-reversed size-N inverse transform of the N evaluations; writes the h-scaled bit-reversed coefficient
@@ -106,15 +132,14 @@ struct DeepConsts {
     fe gamma_h1, gamma_h2;       // gamma, gamma'
     fe c_h;                      // gamma*H1(z^2) + gamma'*H2(z^2)
     fe c_t[AIR_MAX_OFFSETS];     // sum_j gamma_{j,k} t_j(z g^ofs_k)
-    fe gammas[AIR_MAX_OFFSETS][64];  // gamma_{j,k}, k = frame row, j = column (<= 61 columns)
     uint32_t cols, rows;         // rows = number of frame rows (transition offsets): 2 for Cairo
 };
 // compute_deep_composition_poly (reference src/starks/prover.rs:410-482) in evaluation form:
 // p0(x) = sum_k (sum_j g_jk t_j(x) - c_tk) / (x - z g^ofs_k) + (g H1 + g' H2 - c_h) / (x - z^2);
-// inv: [rows + 1][count] = 1/(x - z g^ofs_k) for each frame row, then 1/(x - z^2).
-// `count` points, point q = element (q << shift) of every column (columns at col_stride).
+// inv: [rows + 1][count] = 1/(x - z g^ofs_k) for each frame row, then 1/(x - z^2); gammas: [rows][cols] gamma_{j,k}
+// (device memory sized by the shape).  `count` points, point q = element (q << shift) of every column (columns at col_stride).
 int deep_composition(hipStream_t st, const fe* lde, const fe* h1, const fe* h2, uint64_t count, uint64_t col_stride, uint32_t shift,
-                     const DeepConsts* consts_dev, const fe* inv, fe* out, LdeOrder order, uint32_t frame_rows = 2);
+                     const DeepConsts* consts_dev, const fe* gammas, const fe* inv, fe* out, LdeOrder order, uint32_t frame_rows = 2);
 
 // fold_polynomial + FriLayer::new (reference src/starks/fri/fri_functions.rs:4-27, fri_commitment.rs:30-47) in evaluation
 // form: next[i] = (cur[i] + cur[i+M/2]) / 2 + zeta * (cur[i] - cur[i+M/2]) / (2 x_i),  x_i = offset * w_M^i, i < M/2.

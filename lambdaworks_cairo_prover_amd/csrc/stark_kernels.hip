@@ -409,7 +409,7 @@ int fold_eval_level(hipStream_t st, const fe* in, uint64_t in_vec_stride, uint32
 template <int MAXR>
 __global__ void __launch_bounds__(256) deep_kernel(const fe* __restrict__ lde, const fe* __restrict__ h1, const fe* __restrict__ h2, uint64_t count,
                                                    uint64_t col_stride, uint32_t shift, const DeepConsts* __restrict__ K,
-                                                   const fe* __restrict__ inv, fe* __restrict__ out, LdeOrder ord) {
+                                                   const fe* __restrict__ gammas, const fe* __restrict__ inv, fe* __restrict__ out, LdeOrder ord) {
     uint64_t q = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (q >= count) return;
     const uint64_t i = ord.at(q << shift);   // coset-major columns: the one coset of the n-point evaluation is contiguous
@@ -423,7 +423,7 @@ __global__ void __launch_bounds__(256) deep_kernel(const fe* __restrict__ lde, c
 #pragma unroll
         for (int k = 0; k < MAXR; ++k)
             if ((uint32_t)k < R) {
-                a[k] = fe_add_raw(a[k], fe_mul_lazy(t, K->gammas[k][j]));
+                a[k] = fe_add_raw(a[k], fe_mul_lazy(t, gammas[(uint64_t)k * C + j]));
                 if ((j & 7u) == 7u) a[k] = fe_reduce_lazy_2p(a[k]);
             }
     }
@@ -437,10 +437,10 @@ __global__ void __launch_bounds__(256) deep_kernel(const fe* __restrict__ lde, c
     sk_st(out + q, r);
 }
 int deep_composition(hipStream_t st, const fe* lde, const fe* h1, const fe* h2, uint64_t count, uint64_t col_stride, uint32_t shift,
-                     const DeepConsts* consts_dev, const fe* inv, fe* out, LdeOrder order, uint32_t frame_rows) {
+                     const DeepConsts* consts_dev, const fe* gammas, const fe* inv, fe* out, LdeOrder order, uint32_t frame_rows) {
     // (the accumulators of unused frame rows would still take registers: two instantiations)
-    if (frame_rows <= 2) hipLaunchKernelGGL(deep_kernel<2>, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, lde, h1, h2, count, col_stride, shift, consts_dev, inv, out, order);
-    else hipLaunchKernelGGL(deep_kernel<AIR_MAX_OFFSETS>, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, lde, h1, h2, count, col_stride, shift, consts_dev, inv, out, order);
+    if (frame_rows <= 2) hipLaunchKernelGGL(deep_kernel<2>, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, lde, h1, h2, count, col_stride, shift, consts_dev, gammas, inv, out, order);
+    else hipLaunchKernelGGL(deep_kernel<AIR_MAX_OFFSETS>, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, lde, h1, h2, count, col_stride, shift, consts_dev, gammas, inv, out, order);
     SP_HIP_CHECK(hipGetLastError());
     return SP_OK;
 }
@@ -595,13 +595,32 @@ int interleave_shards(hipStream_t st, const void* gathered, void* out, uint64_t 
 }
 
 // ---------------------------------------------------------------------------------------------- program AIRs
-// The constraint program runs once per point with its values in a per-thread array (scratch): these AIRs are the small
-// examples of the reference (a handful of ops), throughput is not the point here, identical field elements are.
+// The constraint program runs once per point with its values in a per-thread array (scratch); the ops, constants and the
+// per-proof tables are device arrays sized by the program and the proof, read at one address by every lane.
+__global__ void __launch_bounds__(256) boundary_vanishing_kernel(fe* zb, uint64_t N, uint32_t logN, const fe* __restrict__ roots, fe h,
+                                                                 const fe* __restrict__ points, uint32_t ndist, ShardMap sm) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    const fe x = fe_mul(root_pow(roots, shard_global_index((uint32_t)i, sm), logN), h);
+    fe p = fe_sub(x, sk_ld(points));
+    for (uint32_t g = 1; g < ndist; ++g) p = p * (x - sk_ld(points + g));
+    sk_st(zb + i, p);
+}
+int boundary_vanishing(hipStream_t st, fe* zb, uint64_t N, uint32_t logN, const fe* roots_N, const fe& h, const fe* points_dev, uint32_t ndist, ShardMap sm) {
+    if (ndist == 0) return SP_E_INVALID_ARG;
+    hipLaunchKernelGGL(boundary_vanishing_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, zb, N, logN, roots_N, h, points_dev, ndist, sm);
+    SP_HIP_CHECK(hipGetLastError());
+    return SP_OK;
+}
+
+// CHECK = false: composition evaluations, point i = element e = i << stride_log of every LDE column (as cairo_composition);
+// CHECK = true: the transition constraints on the trace itself (natural-order columns of n rows): *flag |= 1 if one is non-zero on a
+// row it is enforced on (the boundary values: air_boundary_check_kernel).
 template <bool CHECK>
 __global__ void __launch_bounds__(256) air_composition_kernel(const fe* __restrict__ cols, uint64_t count, uint64_t col_len, uint32_t stride_log,
                                                               uint32_t logN, uint32_t logb, const fe* __restrict__ roots,
-                                                              const CompositionConsts* __restrict__ K, const AirProgram* __restrict__ Pg,
-                                                              const fe* __restrict__ ex_roots, const fe* __restrict__ binv,
+                                                              const AirCompTables K, const AirProgram* __restrict__ Pg,
+                                                              const fe* __restrict__ ex_roots, const fe* __restrict__ zbinv,
                                                               fe* __restrict__ out, int* __restrict__ flag, uint32_t shard_log, uint32_t shard_rank) {
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= count) return;
@@ -611,13 +630,15 @@ __global__ void __launch_bounds__(256) air_composition_kernel(const fe* __restri
     const LdeOrder ord{CHECK ? 0u : 1u, logb - shard_log, logN - logb};
     const uint32_t iglob = CHECK ? 0u : shard_global_index((uint32_t)e, sm);
     const uint32_t c = iglob & (b - 1);
-    const uint32_t T = K->n_transitions, B = K->n_boundary;
+    const uint32_t T = K.T, B = K.B;
+    const AirOpDev* __restrict__ ops = Pg->ops;
+    const fe* __restrict__ consts = Pg->consts;
     fe v[AIR_MAX_LIVE];
     fe cons[AIR_MAX_TRANSITIONS];
     for (uint32_t k = 0; k < T; ++k) cons[k] = fe_zero();
     const uint32_t n_ops = Pg->n_ops;
     for (uint32_t t = 0; t < n_ops; ++t) {
-        const AirOpDev o = Pg->ops[t];
+        const AirOpDev o = ops[t];
         fe r = fe_zero();
         switch (o.op) {
             case 0: {   // frame row = trace row + offset: LDE index + offset * blowup (frame.rs:40-59), same coset
@@ -625,7 +646,7 @@ __global__ void __launch_bounds__(256) air_composition_kernel(const fe* __restri
                 r = sk_ld(cols + (uint64_t)o.b * col_len + ord.at(row));
                 break;
             }
-            case 1: r = Pg->consts[o.a]; break;
+            case 1: r = sk_ld(consts + o.a); break;
             case 2: r = v[o.a] + v[o.b]; break;
             case 3: r = v[o.a] - v[o.b]; break;
             case 4: r = v[o.a] * v[o.b]; break;
@@ -637,46 +658,68 @@ __global__ void __launch_bounds__(256) air_composition_kernel(const fe* __restri
         bool bad = false;
         for (uint32_t k = 0; k < T; ++k)
             if (i + Pg->ex_rows[k] < count && !fe_is_zero(cons[k])) bad = true;   // enforced on rows 0 .. n - 1 - exemptions
-        for (uint32_t j = 0; j < B; ++j)
-            if (i == K->bstep[j] && !fe_eq(sk_ld(cols + (uint64_t)K->bcol[j] * col_len + i), K->bvalue[j])) bad = true;
         if (bad) atomicOr(flag, 1);
         return;
     }
-    const fe x = root_pow(roots, iglob, logN) * K->h;
+    const fe x = root_pow(roots, iglob, logN) * K.h;
     fe exv[AIR_MAX_EXEMPT_KINDS];
     for (int q = 0; q < AIR_MAX_EXEMPT_KINDS; ++q) {
         fe p = fe_one();
         for (uint32_t j = 0; j < Pg->ex_count[q]; ++j) p = p * (x - sk_ld(ex_roots + j));
         exv[q] = p;
     }
+    const fe* __restrict__ coef = K.coef + (uint64_t)c * (T + B);
     fe acc = fe_zero();
     for (uint32_t k = 0; k < T; ++k) {
-        fe term = K->coef[c][k] * cons[k];
+        fe term = sk_ld(coef + k) * cons[k];
         const uint32_t ek = Pg->ex_kind[k];
         if (ek) term = term * exv[ek - 1];
         acc = acc + term;
     }
-    fe total = K->zerofier[c] * acc;
-    for (uint32_t j = 0; j < B; ++j) {
-        fe num = sk_ld(cols + (uint64_t)K->bcol[j] * col_len + ord.at(e)) - K->bvalue[j];
-        total = total + K->coef[c][T + j] * num * sk_ld(binv + (uint64_t)K->bden[j] * count + i);
+    fe total = sk_ld(K.zerofier + c) * acc;
+    if (K.ndist) {
+        // sum_s S_s / (x - g^s) as A / P over the rows s seen so far: three products per row, one inverse (zbinv) per point
+        const uint64_t at = ord.at(e);
+        fe A = fe_zero(), P = fe_one();
+        uint32_t j = 0;
+        for (uint32_t g = 0; g < K.ndist; ++g) {
+            fe S = fe_zero();
+            for (const uint32_t end = K.gend[g]; j < end; ++j)
+                S = S + sk_ld(coef + T + j) * (sk_ld(cols + (uint64_t)K.bcol[j] * col_len + at) - sk_ld(K.bvalue + j));
+            const fe d = x - sk_ld(K.gpoint + g);
+            A = A * d + S * P;
+            P = P * d;
+        }
+        total = total + A * sk_ld(zbinv + i);
     }
     sk_st(out + i, total);
 }
 
 int air_composition(hipStream_t st, const fe* lde, uint64_t count, uint64_t col_len, uint32_t stride_log, uint32_t logN, uint32_t logb,
-                    const fe* roots_N, const CompositionConsts* consts_dev, const AirProgram* prog_dev, const fe* ex_roots,
-                    const fe* binv, fe* out, uint32_t shard_log, uint32_t shard_rank) {
+                    const fe* roots_N, AirCompTables tabs, const AirProgram* prog_dev, const fe* ex_roots,
+                    const fe* zbinv, fe* out, uint32_t shard_log, uint32_t shard_rank) {
     if ((1u << logb) > CAIRO_MAX_BLOWUP) { sp_set_error("composition: blowup factor > 128 unsupported"); return SP_E_UNSUPPORTED; }
     hipLaunchKernelGGL(air_composition_kernel<false>, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, lde, count, col_len, stride_log,
-                       logN, logb, roots_N, consts_dev, prog_dev, ex_roots, binv, out, (int*)nullptr, shard_log, shard_rank);
+                       logN, logb, roots_N, tabs, prog_dev, ex_roots, zbinv, out, (int*)nullptr, shard_log, shard_rank);
     SP_HIP_CHECK(hipGetLastError());
     return SP_OK;
 }
-int air_trace_check(hipStream_t st, const fe* trace, uint64_t n, const CompositionConsts* consts_dev, const AirProgram* prog_dev, int* flag_dev) {
+
+// one thread per boundary constraint: trace[col][step] == value (validate_trace, debug.rs:88-104)
+__global__ void __launch_bounds__(256) air_boundary_check_kernel(const fe* __restrict__ trace, uint64_t n, const AirCompTables K, int* __restrict__ flag) {
+    const uint32_t j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= K.B) return;
+    if (!fe_eq(sk_ld(trace + (uint64_t)K.bcol[j] * n + K.bstep[j]), sk_ld(K.bvalue + j))) atomicOr(flag, 1);
+}
+
+int air_trace_check(hipStream_t st, const fe* trace, uint64_t n, AirCompTables tabs, const AirProgram* prog_dev, int* flag_dev) {
     hipLaunchKernelGGL(air_composition_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, trace, n, n, 0u, 0u, 0u,
-                       (const fe*)nullptr, consts_dev, prog_dev, (const fe*)nullptr, (const fe*)nullptr, (fe*)nullptr, flag_dev, 0u, 0u);
+                       (const fe*)nullptr, tabs, prog_dev, (const fe*)nullptr, (const fe*)nullptr, (fe*)nullptr, flag_dev, 0u, 0u);
     SP_HIP_CHECK(hipGetLastError());
+    if (tabs.B) {
+        hipLaunchKernelGGL(air_boundary_check_kernel, dim3((tabs.B + 255) / 256), dim3(256), 0, st, trace, n, tabs, flag_dev);
+        SP_HIP_CHECK(hipGetLastError());
+    }
     return SP_OK;
 }
 

@@ -411,7 +411,7 @@ int air_verify_host(const uint8_t* proof_bytes, size_t len, uint32_t main_cols, 
                     const std::vector<std::array<uint16_t, 3>>& ops /*op, a, b*/, const std::vector<fe>& consts, uint32_t n_rap,
                     const std::vector<BoundaryConstraint>& boundary, uint8_t blowup, uint64_t queries, uint64_t coset_offset, uint8_t grinding) {
     const uint32_t C = main_cols + aux_cols, T = (uint32_t)degrees.size(), R = (uint32_t)offsets.size();
-    if (T == 0 || R == 0 || exemptions.size() != T || bound_factor < 1) return 0;
+    if (T == 0 || R == 0 || exemptions.size() != T || bound_factor < 1 || C < main_cols) return 0;   // (C < main_cols: the sum wrapped)
     for (size_t t = 0; t < ops.size(); ++t) {   // same well-formedness rules as the prover
         const uint16_t op = ops[t][0], a = ops[t][1], b = ops[t][2];
         bool ok = true;
