@@ -73,9 +73,10 @@ const char* sp_version(void);
 /* Version of this header: bumped whenever a structure (sp_air_desc, sp_openings, sp_cairo_public_inputs, sp_proof_options) changes
  * layout, an entry point or option key is added, or a call changes meaning (4: round 5's sp_comm_measure / sp_comm_time_ms /
  * sp_proof_options_* / sp_proof_file_verify / SP_OPT_HOST_RANKS family and sp_set_collective keeping the prover across re-installs
- * of the same world; 5: sp_fe_mul; 6: sp_air_limits, sp_air_prove beyond 64 columns and 3 boundary rows).  A binding compares it (and sp_air_desc_size against its own idea of the struct) when it loads the library, so
+ * of the same world; 5: sp_fe_mul; 6: sp_air_limits, sp_air_prove beyond 64 columns and 3 boundary rows; 7: sp_air_prove_aux, sp_air_aux_desc,
+ * sp_air_aux_desc_size).  A binding compares it (and sp_air_desc_size against its own idea of the struct) when it loads the library, so
  * a stale build fails at load time with "rebuild the library" instead of with a missing symbol or shifted fields later. */
-#define SP_ABI_VERSION 6
+#define SP_ABI_VERSION 7
 int sp_abi_version(void);
 uint64_t sp_air_desc_size(void);
 const char* sp_last_error(void);          /* thread-local description of the last failure */
@@ -414,7 +415,8 @@ typedef struct {
     uint32_t n_ops; const sp_air_op* ops;    /* <= 65535 ops, <= 64 values alive at any point of the program */
     uint32_t n_consts; const uint8_t* consts; /* <= 4096, canonical BE */
     uint32_t n_rap;                          /* build_rap_challenges: this many transcript_to_field samples */
-    uint32_t aux_kind;                       /* build_auxiliary_trace: 0 none, 1 fibonacci_rap permutation column, 2 aux_fn */
+    uint32_t aux_kind;                       /* build_auxiliary_trace: 0 none, 1 fibonacci_rap permutation column, 2 aux_fn,
+                                              * 3 (SP_AIR_AUX_PROGRAM) an sp_air_aux_desc given to sp_air_prove_aux */
     uint32_t n_boundary; const sp_air_boundary* boundary;   /* <= 4096, on any rows (several per column allowed) */
     sp_aux_trace_fn aux_fn; void* aux_user;  /* aux_kind 2 */
 } sp_air_desc;
@@ -426,6 +428,34 @@ int sp_air_prove(sp_ctx* ctx, const sp_air_desc* air, const uint8_t* main_trace,
 /* The bounds sp_air_prove accepts, in order: columns (main + aux), transition constraints, frame rows, boundary constraints,
  * constants, ops, values alive at once, 0 (reserved).  A binding can refuse a descriptor before proving. */
 int sp_air_limits(uint32_t out[8]);
+
+/* Auxiliary (RAP) columns built on the device from a straight-line program over the main-trace row and the RAP challenges
+ * (permutation arguments, multiset checks, LogUp lookups).  The program runs once per row i; its ops use the sp_air_op encoding:
+ *   op 0 LOAD  a = row shift s (0 .. 7): main column b of row (i + s) mod n
+ *   op 1 CONST a = index into the aux program's consts; indices >= n_consts are the RAP challenges
+ *   op 2 ADD, 3 SUB, 4 MUL   a, b = indices of earlier ops          (no OUT)
+ * Auxiliary column k (trace column main_cols + k) takes N = value of op num_op and D = value of op den_op (D = 1 for
+ * SP_AIR_AUX_NO_DEN) on every row:
+ *   SP_AIR_AUX_PRODUCT  z_0 = 1, z_i = z_(i-1) N(i-1) / D(i-1)
+ *   SP_AIR_AUX_SUM      z_0 = 0, z_i = z_(i-1) + N(i-1) / D(i-1)
+ * A zero D on any row is SP_E_ZERO_INVERSE.  Bounds: those of the constraint program (sp_air_limits: 65535 ops, 4096 constants,
+ * 64 values alive at once). */
+#define SP_AIR_AUX_PROGRAM 3
+#define SP_AIR_AUX_PRODUCT 0
+#define SP_AIR_AUX_SUM 1
+#define SP_AIR_AUX_NO_DEN 0xFFFFFFFFu
+typedef struct { uint32_t kind, num_op, den_op, pad; } sp_air_aux_column;
+typedef struct {
+    uint32_t n_ops; const sp_air_op* ops;
+    uint32_t n_consts; const uint8_t* consts;   /* canonical BE */
+    uint32_t n_cols; const sp_air_aux_column* cols;
+} sp_air_aux_desc;
+/* sp_air_prove for an AIR with air->aux_kind == SP_AIR_AUX_PROGRAM and aux->n_cols == air->aux_cols >= 1: the same transcript,
+ * rounds and proof bytes as sp_air_prove of the same trace columns, with the auxiliary segment built and committed on the device
+ * (every rank of a sharded context builds all of it from its whole copy of the main trace). */
+int sp_air_prove_aux(sp_ctx* ctx, const sp_air_desc* air, const sp_air_aux_desc* aux, const uint8_t* main_trace, uint64_t n,
+                     const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len);
+uint64_t sp_air_aux_desc_size(void);
 
 /* verify::<Stark252PrimeField, A> (reference src/starks/verifier.rs:559-657) on the host CPU: 1 accept, 0 reject (also for
  * malformed proofs or descriptors). */

@@ -47,8 +47,28 @@ def _check_layout():
         raise ImportError(f"AirDescC is {ctypes.sizeof(AirDescC)} bytes, the library's sp_air_desc {want}: the binding is out of date")
 
 
-AUX_NONE, AUX_FIBONACCI_RAP, AUX_CALLBACK = 0, 1, 2
+AUX_NONE, AUX_FIBONACCI_RAP, AUX_CALLBACK, AUX_PROGRAM = 0, 1, 2, 3
+AUX_PRODUCT, AUX_SUM = 0, 1          # sp_air_aux_column.kind
+AUX_NO_DEN = 0xFFFFFFFF              # sp_air_aux_column.den_op: D = 1
+AUX_MAX_SHIFT = 7
 _RAP_TAG = 0x8000
+
+
+class AirAuxColumnC(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_uint32), ("num_op", ctypes.c_uint32), ("den_op", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
+
+
+class AirAuxDescC(ctypes.Structure):
+    _fields_ = [("n_ops", ctypes.c_uint32), ("ops", ctypes.POINTER(AirOpC)),
+                ("n_consts", ctypes.c_uint32), ("consts", ctypes.c_void_p),
+                ("n_cols", ctypes.c_uint32), ("cols", ctypes.POINTER(AirAuxColumnC))]
+
+
+def _check_aux_layout():
+    from . import _lib
+    want = _lib.load().sp_air_aux_desc_size()
+    if ctypes.sizeof(AirAuxDescC) != want:
+        raise ImportError(f"AirAuxDescC is {ctypes.sizeof(AirAuxDescC)} bytes, the library's sp_air_aux_desc {want}: the binding is out of date")
 
 
 class Value:
@@ -69,6 +89,132 @@ class Value:
     def __rsub__(self, o): return self._lift(o) - self
 
 
+class AuxProgram:
+    """The auxiliary program of an AIR built with aux_kind=AUX_PROGRAM (sp_air_aux_desc): evaluated once per trace row i on the
+    device.  load(shift, col) reads main column `col` of row (i + shift) mod n; product(N, D) and running_sum(N, D) each declare the
+    next auxiliary column: z_0 = 1, z_i = z_(i-1) N(i-1) / D(i-1), or z_0 = 0, z_i = z_(i-1) + N(i-1) / D(i-1) (D = 1 when None)."""
+
+    def __init__(self, main_cols, n_rap):
+        self.main_cols, self.n_rap = main_cols, n_rap
+        self.ops, self.consts, self.cols = [], [], []
+        self._const_at = {}
+
+    def _emit(self, op, a, b):
+        self.ops.append((op, a, b))
+        return Value(self, len(self.ops) - 1)
+
+    def load(self, shift, col):
+        if not 0 <= shift <= AUX_MAX_SHIFT:
+            raise ValueError(f"aux program: row shift {shift} outside 0 .. {AUX_MAX_SHIFT}")
+        if not 0 <= col < self.main_cols:
+            raise ValueError(f"aux program: column {col} is not a main column (main_cols = {self.main_cols})")
+        return self._emit(OP_LOAD, shift, col)
+
+    def const(self, v):
+        v %= P
+        if v not in self._const_at:
+            self._const_at[v] = len(self.consts)
+            self.consts.append(v)
+        return self._emit(OP_CONST, self._const_at[v], 0)
+
+    def rap(self, i):
+        if not 0 <= i < self.n_rap:
+            raise ValueError(f"aux program: RAP challenge {i} of {self.n_rap}")
+        return self._emit(OP_CONST, _RAP_TAG | i, 0)
+
+    def _column(self, kind, num, den):
+        num = num if isinstance(num, Value) else self.const(num)
+        if den is not None and not isinstance(den, Value):
+            den = self.const(den)
+        self.cols.append((kind, num.i, AUX_NO_DEN if den is None else den.i))
+
+    def product(self, num, den=None):
+        self._column(AUX_PRODUCT, num, den)
+
+    def running_sum(self, num, den=None):
+        self._column(AUX_SUM, num, den)
+
+    def resolved_ops(self):
+        """The ops as the library reads them: RAP challenges follow the constants."""
+        return [(op, len(self.consts) + (a & ~_RAP_TAG) if op == OP_CONST and a & _RAP_TAG else a, b) for op, a, b in self.ops]
+
+    def evaluate(self, rows, rap):
+        """The auxiliary columns in Python integers (the semantics of sp_air_prove_aux): rows = n x main_cols field elements (any
+        sequence of rows, or a numpy array of Python ints); returns an (n, len(cols)) numpy object array.  Each op is one vectorised
+        numpy operation over all rows; the inverses are one batch inversion; the scans run row by row."""
+        import numpy as np
+        m = np.empty((len(rows), self.main_cols), dtype=object)
+        m[:, :] = rows if not isinstance(rows, np.ndarray) else rows.astype(object)
+        n = m.shape[0]
+        consts = list(self.consts) + [int(r) % P for r in rap]
+        vals = []
+        for op, a, b in self.resolved_ops():
+            if op == OP_LOAD:
+                v = np.roll(m[:, b], -a)
+            elif op == OP_CONST:
+                v = np.full(n, consts[a], dtype=object)
+            elif op == OP_ADD:
+                v = (vals[a] + vals[b]) % P
+            elif op == OP_SUB:
+                v = (vals[a] - vals[b]) % P
+            elif op == OP_MUL:
+                v = (vals[a] * vals[b]) % P
+            else:
+                raise ValueError(f"aux program: op {op}")
+            vals.append(v)
+        dens = [k for k, (_, _, d) in enumerate(self.cols) if d != AUX_NO_DEN]
+        flat = [int(x) for k in dens for x in vals[self.cols[k][2]]]
+        inv = _batch_inverse(flat)
+        out = np.empty((n, len(self.cols)), dtype=object)
+        for k, (kind, num_op, den_op) in enumerate(self.cols):
+            t = vals[num_op]
+            if den_op != AUX_NO_DEN:
+                j = dens.index(k)
+                t = (t * np.array(inv[j * n:(j + 1) * n], dtype=object)) % P
+            if kind == AUX_SUM:
+                out[0, k] = 0
+                out[1:, k] = np.cumsum(t[:-1]) % P
+                continue
+            z, col = 1, out[:, k]
+            for i in range(n):
+                col[i] = z
+                z = z * int(t[i]) % P
+        return out
+
+
+def _batch_inverse(xs):
+    """Montgomery's trick over Python integers; ValueError on a zero (sp_air_prove_aux answers SP_E_ZERO_INVERSE there)."""
+    pre, acc = [], 1
+    for x in xs:
+        if x % P == 0:
+            raise ValueError("aux program: a denominator is zero")
+        pre.append(acc)
+        acc = acc * x % P
+    inv = pow(acc, P - 2, P)
+    out = [0] * len(xs)
+    for i in range(len(xs) - 1, -1, -1):
+        out[i] = inv * pre[i] % P
+        inv = inv * xs[i] % P
+    return out
+
+
+def trace_to_ints(trace):
+    """(n, cols, 32) canonical big-endian bytes -> (n, cols) numpy object array of Python ints."""
+    import numpy as np
+    a = np.ascontiguousarray(trace, dtype=np.uint8)
+    limbs = a.reshape(a.shape[0], a.shape[1], 4, 8).view(">u8")[..., 0].astype(object)
+    return ((limbs[..., 0] << 192) | (limbs[..., 1] << 128) | (limbs[..., 2] << 64) | limbs[..., 3])
+
+
+def ints_to_bytes(values):
+    """(n, cols) Python ints (reduced mod P) -> (n, cols, 32) canonical big-endian bytes."""
+    import numpy as np
+    v = np.asarray(values, dtype=object) % P
+    mask = (1 << 64) - 1
+    limbs = np.stack([((v >> s) & mask).astype(np.uint64) for s in (192, 128, 64, 0)], axis=-1)
+    return np.ascontiguousarray(limbs.astype(">u8")).view(np.uint8).reshape(v.shape[0], v.shape[1], 32)
+
+
 class AirBuilder:
     def __init__(self, main_cols, offsets, degree_bound_factor, aux_cols=0, n_rap=0, aux_kind=AUX_NONE, num_transition_exemptions=1,
                  aux_builder=None):
@@ -79,6 +225,8 @@ class AirBuilder:
         self.degree_bound_factor, self.n_rap, self.aux_kind = degree_bound_factor, n_rap, aux_kind
         self.num_transition_exemptions = num_transition_exemptions
         self.ops, self.consts, self.degrees, self.exemptions, self.bcs = [], [], [], [], []
+        # aux_kind AUX_PROGRAM: the auxiliary columns as a program over the main-trace row (sp_air_prove_aux)
+        self.aux = AuxProgram(main_cols, n_rap) if aux_kind == AUX_PROGRAM else None
 
     def _emit(self, op, a, b):
         self.ops.append((op, a, b))
@@ -117,11 +265,28 @@ class AirBuilder:
         for name, value in have.items():
             if value > lim[name]:
                 raise ValueError(f"AIR exceeds the {name} limit of sp_air_prove: {value} > {lim[name]}")
+        if self.aux is not None:
+            if len(self.aux.cols) != self.aux_cols:
+                raise ValueError(f"aux program declares {len(self.aux.cols)} auxiliary columns, the AIR has aux_cols = {self.aux_cols}")
+            for name, value in (("constants", len(self.aux.consts)), ("ops", len(self.aux.ops))):
+                if value > lim[name]:
+                    raise ValueError(f"aux program exceeds the {name} limit of sp_air_prove_aux: {value} > {lim[name]}")
+            if len(self.aux.consts) + self.n_rap > 65535:
+                raise ValueError("aux program: constants and RAP challenges exceed the 16-bit operand range")
 
-    def build(self):
-        """Returns (AirDescC, keepalive).  Raises ValueError if the AIR exceeds a bound of sp_air_limits."""
+    def build(self, aux_as_callback=False, main_trace=None):
+        """Returns (AirDescC, keepalive).  Raises ValueError if the AIR exceeds a bound of sp_air_limits.
+
+        With an aux program (aux_kind AUX_PROGRAM) the returned desc carries its AirAuxDescC (desc.aux_desc), and
+        api.Context.air_prove proves it with sp_air_prove_aux.  aux_as_callback=True returns the same AIR as aux_kind AUX_CALLBACK
+        instead, its callback evaluating the aux program in Python over `main_trace` ((n, main_cols, 32) canonical big-endian
+        bytes, or n rows of ints): what the CPU oracle and sp_air_prove accept."""
         _check_layout()
         self.check_limits()
+        if self.aux is not None and aux_as_callback:
+            if main_trace is None:
+                raise ValueError("build(aux_as_callback=True) needs the main trace the callback evaluates the aux program over")
+            return self._build_aux_callback(main_trace)
         d = AirDescC()
         d.main_cols, d.aux_cols = self.main_cols, self.aux_cols
         d.n_offsets = len(self.offsets)
@@ -164,7 +329,56 @@ class AirBuilder:
                     return -1
             cb = AUX_TRACE_FN(_aux)
             d.aux_fn = cb
-        return d, (ops, consts, bcs, cb)
+        keep = (ops, consts, bcs, cb)
+        if self.aux is not None:
+            aux_desc, aux_keep = self._aux_desc()
+            d.aux_desc = aux_desc
+            keep = keep + (aux_desc, aux_keep)
+        return d, keep
+
+    def _aux_desc(self):
+        _check_aux_layout()
+        p = self.aux
+        ops = (AirOpC * max(1, len(p.ops)))()
+        for i, (op, a, b) in enumerate(p.resolved_ops()):
+            ops[i].op, ops[i].a, ops[i].b = op, a, b
+        consts = ctypes.create_string_buffer(b"".join(c.to_bytes(32, "big") for c in p.consts), max(1, 32 * len(p.consts)))
+        cols = (AirAuxColumnC * max(1, len(p.cols)))()
+        for k, (kind, num_op, den_op) in enumerate(p.cols):
+            cols[k].kind, cols[k].num_op, cols[k].den_op = kind, num_op, den_op
+        x = AirAuxDescC()
+        x.n_ops, x.ops = len(p.ops), ctypes.cast(ops, ctypes.POINTER(AirOpC))
+        x.n_consts, x.consts = len(p.consts), ctypes.cast(consts, ctypes.c_void_p)
+        x.n_cols, x.cols = len(p.cols), ctypes.cast(cols, ctypes.POINTER(AirAuxColumnC))
+        return x, (ops, consts, cols)
+
+    def _build_aux_callback(self, main_trace):
+        import numpy as np
+        rows = main_trace
+        if isinstance(rows, np.ndarray) and rows.dtype == np.uint8:
+            rows = trace_to_ints(rows)
+        program, aux_kind = self.aux, self.aux_kind
+        self.aux_kind, self.aux = AUX_CALLBACK, None
+        try:
+            d, keep = self.build()
+        finally:
+            self.aux_kind, self.aux = aux_kind, program
+        aux_cols = self.aux_cols
+
+        def _aux(user, rap_ptr, n_rap, out_ptr):   # canonical big-endian contexts (the default encoding)
+            try:
+                raw = ctypes.string_at(rap_ptr, 32 * n_rap)
+                flat = ints_to_bytes(program.evaluate(rows, [int.from_bytes(raw[32 * i:32 * i + 32], "big") for i in range(n_rap)]))
+                assert flat.shape[1] == aux_cols
+                ctypes.memmove(out_ptr, flat.ctypes.data, flat.nbytes)
+                return 0
+            except Exception:  # never let an exception cross the C boundary
+                import traceback
+                traceback.print_exc()
+                return -1
+        cb = AUX_TRACE_FN(_aux)
+        d.aux_fn = cb
+        return d, keep + (cb,)
 
 
 # ---- the reference's example AIRs in program form (src/starks/example/*.rs) ------------------------------------------
@@ -206,4 +420,17 @@ def fibonacci_rap(trace_length, steps):
     gamma = b.rap(0)
     b.constraint(b.load(1, 2) * (b.load(0, 1) + gamma) - b.load(0, 2) * (b.load(0, 0) + gamma), 2, 1)
     b.boundary(0, 0, 1); b.boundary(0, 1, 1); b.boundary(2, 0, 1)
+    return b
+
+
+def fibonacci_rap_program(trace_length, steps):
+    """fibonacci_rap with its permutation column as an aux program (sp_air_prove_aux): z_0 = 1, z_i = z_(i-1) (a + gamma) / (b + gamma)
+    of row i - 1 - the column aux_kind AUX_FIBONACCI_RAP builds on the host."""
+    b = AirBuilder(2, [0, 1, 2], 1, aux_cols=1, n_rap=1, aux_kind=AUX_PROGRAM, num_transition_exemptions=2)
+    b.constraint(b.load(2, 0) - b.load(1, 0) - b.load(0, 0), 1, 3 + trace_length - steps - 1)
+    gamma = b.rap(0)
+    b.constraint(b.load(1, 2) * (b.load(0, 1) + gamma) - b.load(0, 2) * (b.load(0, 0) + gamma), 2, 1)
+    b.boundary(0, 0, 1); b.boundary(0, 1, 1); b.boundary(2, 0, 1)
+    g = b.aux.rap(0)
+    b.aux.product(b.aux.load(0, 0) + g, b.aux.load(0, 1) + g)
     return b

@@ -220,14 +220,20 @@ class Context:
                 "dma_ms": round(v[5], 3), "dma_gbs": round(v[6], 1), "exposed_ms": round(v[7], 3), "max_stall_ms": round(v[8], 3), "host_ms": round(v[9], 3)}
 
     def air_prove(self, desc, main_trace, options):
-        """sp_air_prove: desc = lambdaworks_cairo_prover_amd.air.AirDescC (AirBuilder.build()[0]); main_trace (n, cols, 32)."""
+        """sp_air_prove: desc = lambdaworks_cairo_prover_amd.air.AirDescC (AirBuilder.build()[0]); main_trace (n, cols, 32).
+        A desc that carries an auxiliary program (AirBuilder with aux_kind=air.AUX_PROGRAM) goes to sp_air_prove_aux."""
         a = np.ascontiguousarray(main_trace, dtype=np.uint8)
         n, cols = a.shape[0], a.shape[1]
         assert cols == desc.main_cols
         opt = options.to_c()
         out = ctypes.POINTER(ctypes.c_uint8)()
         ln = ctypes.c_uint64()
-        check(self._lib.sp_air_prove(self._h, ctypes.byref(desc), _u8p(a), ctypes.c_uint64(n), ctypes.byref(opt), ctypes.byref(out), ctypes.byref(ln)))
+        aux = getattr(desc, "aux_desc", None)
+        if aux is not None:
+            check(self._lib.sp_air_prove_aux(self._h, ctypes.byref(desc), ctypes.byref(aux), _u8p(a), ctypes.c_uint64(n), ctypes.byref(opt),
+                                             ctypes.byref(out), ctypes.byref(ln)))
+        else:
+            check(self._lib.sp_air_prove(self._h, ctypes.byref(desc), _u8p(a), ctypes.c_uint64(n), ctypes.byref(opt), ctypes.byref(out), ctypes.byref(ln)))
         proof = ctypes.string_at(out, ln.value)
         self._lib.sp_free(out)
         return proof

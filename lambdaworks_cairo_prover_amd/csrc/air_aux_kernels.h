@@ -1,0 +1,27 @@
+// Auxiliary (RAP) columns of a program AIR on the device (include/stark252_hip.h sp_air_aux_desc): per-row numerators and
+// denominators from a straight-line program over the main trace, then one exclusive scan per column (grand product or running
+// sum).  The Cairo counterpart is aux_kernels.h; these kernels leave it alone.
+#pragma once
+#include "common.h"
+#include "stark_kernels.h"
+
+namespace sp {
+
+// An aux program on the device is an AirOpDev list (slots assigned by air_assign_slots) whose OUT ops (op 5) write a result:
+// OUT a < AIR_AUX_DEN_TAG stores the value as N of chunk column a at num[a * n + i]; OUT a = AIR_AUX_DEN_TAG + d stores it as
+// denominator d at den[d * n + i].  LOAD a = row shift (0 .. 7), b = main column: row (i + a) mod n of the natural-order trace.
+constexpr uint16_t AIR_AUX_DEN_TAG = 0x8000;
+constexpr uint32_t AIR_AUX_MAX_SHIFT = 7;
+
+// One thread per row: evaluates the program once and writes every N and D it names (column-major, coalesced across rows).
+// trace: [main_cols][n] natural order; consts: the aux constants followed by the RAP challenges.
+int air_aux_terms(hipStream_t st, const fe* trace, uint64_t n, const AirOpDev* ops, uint32_t n_ops, const fe* consts, fe* num, fe* den);
+// num[col_of[d] * n + i] *= dinv[d * n + i]  for d < n_den, i < n
+int air_aux_apply_den(hipStream_t st, fe* num, const fe* dinv, const uint32_t* col_of, uint32_t n_den, uint64_t n);
+// In-place EXCLUSIVE scan of K columns of n elements (column k at data + k * n), shifted by one row: out[0] = identity,
+// out[i] = x[0] op .. op x[i-1].  kinds[k] = 0: product (identity 1), 1: sum (identity 0).  One launch per phase for all
+// columns: block totals, scan of the totals, apply.  block_tot: K * air_aux_scan_blocks(n) elements.
+uint64_t air_aux_scan_blocks(uint64_t n);
+int air_aux_scan(hipStream_t st, fe* data, uint64_t n, uint32_t K, const uint32_t* kinds, fe* block_tot);
+
+}  // namespace sp

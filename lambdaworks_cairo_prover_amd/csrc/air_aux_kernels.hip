@@ -1,0 +1,156 @@
+// Auxiliary columns of a program AIR on gfx950 (see air_aux_kernels.h).
+#include "air_aux_kernels.h"
+
+namespace sp {
+
+__device__ __forceinline__ fe aa_ld(const fe* p) {
+    const uint4* q = reinterpret_cast<const uint4*>(p);
+    uint4 lo = q[0], hi = q[1];
+    fe r;
+    r.v[0] = lo.x; r.v[1] = lo.y; r.v[2] = lo.z; r.v[3] = lo.w;
+    r.v[4] = hi.x; r.v[5] = hi.y; r.v[6] = hi.z; r.v[7] = hi.w;
+    return r;
+}
+__device__ __forceinline__ void aa_st(fe* p, const fe& a) {
+    uint4* q = reinterpret_cast<uint4*>(p);
+    q[0] = make_uint4(a.v[0], a.v[1], a.v[2], a.v[3]);
+    q[1] = make_uint4(a.v[4], a.v[5], a.v[6], a.v[7]);
+}
+
+// ---- per-row terms ------------------------------------------------------------------------------------------
+// The value file is a per-thread array (scratch), as in air_composition_kernel; every lane reads the same op and constant.
+__global__ void __launch_bounds__(256) air_aux_terms_kernel(const fe* __restrict__ trace, uint64_t n, const AirOpDev* __restrict__ ops, uint32_t n_ops,
+                                                            const fe* __restrict__ consts, fe* __restrict__ num, fe* __restrict__ den) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    fe v[AIR_MAX_LIVE];
+    for (uint32_t t = 0; t < n_ops; ++t) {
+        const AirOpDev o = ops[t];
+        fe r = fe_zero();
+        switch (o.op) {
+            case 0: r = aa_ld(trace + (uint64_t)o.b * n + ((i + o.a) & (n - 1))); break;   // n is a power of two
+            case 1: r = aa_ld(consts + o.a); break;
+            case 2: r = fe_add(v[o.a], v[o.b]); break;
+            case 3: r = fe_sub(v[o.a], v[o.b]); break;
+            case 4: r = fe_mul(v[o.a], v[o.b]); break;
+            default: {
+                fe* dst = o.a < AIR_AUX_DEN_TAG ? num + (uint64_t)o.a * n : den + (uint64_t)(o.a - AIR_AUX_DEN_TAG) * n;
+                aa_st(dst + i, v[o.b]);
+                continue;
+            }
+        }
+        v[o.dst] = r;
+    }
+}
+
+int air_aux_terms(hipStream_t st, const fe* trace, uint64_t n, const AirOpDev* ops, uint32_t n_ops, const fe* consts, fe* num, fe* den) {
+    if (n == 0 || (n & (n - 1))) return SP_E_INVALID_ARG;
+    hipLaunchKernelGGL(air_aux_terms_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, trace, n, ops, n_ops, consts, num, den);
+    SP_HIP_CHECK(hipGetLastError());
+    return SP_OK;
+}
+
+__global__ void __launch_bounds__(256) air_aux_apply_den_kernel(fe* __restrict__ num, const fe* __restrict__ dinv, const uint32_t* __restrict__ col_of, uint64_t n) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t d = blockIdx.y;
+    fe* p = num + (uint64_t)col_of[d] * n + i;
+    aa_st(p, fe_mul(aa_ld(p), aa_ld(dinv + (uint64_t)d * n + i)));
+}
+
+int air_aux_apply_den(hipStream_t st, fe* num, const fe* dinv, const uint32_t* col_of, uint32_t n_den, uint64_t n) {
+    if (n_den == 0) return SP_OK;
+    hipLaunchKernelGGL(air_aux_apply_den_kernel, dim3((unsigned)((n + 255) / 256), n_den), dim3(256), 0, st, num, dinv, col_of, n);
+    SP_HIP_CHECK(hipGetLastError());
+    return SP_OK;
+}
+
+// ---- multi-column exclusive scan --------------------------------------------------------------------------------
+// Same three-phase shape as prefix_product (aux_kernels.hip), with a column index in grid.y and the operation chosen by the
+// column's kind (uniform over a block).
+constexpr int AS_PER_THREAD = 8;
+constexpr int AS_BLOCK = 256 * AS_PER_THREAD;   // 2048 elements per block
+
+__device__ __forceinline__ fe as_op(uint32_t kind, const fe& a, const fe& b) { return kind ? fe_add(a, b) : fe_mul(a, b); }
+__device__ __forceinline__ fe as_id(uint32_t kind) { return kind ? fe_zero() : fe_one(); }
+
+// inclusive scan of the 256 per-thread partials of a block through LDS; returns this thread's EXCLUSIVE prefix
+__device__ __forceinline__ fe as_block_exclusive(uint32_t kind, fe mine, fe* sh, fe* block_total) {
+    const uint32_t t = threadIdx.x;
+    sh[t] = mine;
+    __syncthreads();
+    for (uint32_t off = 1; off < 256; off <<= 1) {
+        fe other = sh[t >= off ? t - off : 0];
+        __syncthreads();
+        if (t >= off) sh[t] = as_op(kind, other, sh[t]);
+        __syncthreads();
+    }
+    fe excl = t == 0 ? as_id(kind) : sh[t - 1];
+    if (block_total) *block_total = sh[255];
+    return excl;
+}
+
+__global__ void __launch_bounds__(256) as_block_totals_kernel(const fe* __restrict__ data, uint64_t n, const uint32_t* __restrict__ kinds, fe* __restrict__ block_tot) {
+    __shared__ fe sh[256];
+    const uint32_t k = blockIdx.y, kind = kinds[k];
+    const fe* col = data + (uint64_t)k * n;
+    const uint64_t base = (uint64_t)blockIdx.x * AS_BLOCK + (uint64_t)threadIdx.x * AS_PER_THREAD;
+    fe acc = as_id(kind);
+    for (int j = 0; j < AS_PER_THREAD; ++j)
+        if (base + j < n) acc = as_op(kind, acc, aa_ld(col + base + j));
+    fe tot;
+    (void)as_block_exclusive(kind, acc, sh, &tot);
+    if (threadIdx.x == 0) aa_st(block_tot + (uint64_t)k * gridDim.x + blockIdx.x, tot);
+}
+
+// one block per column: the `count` block totals of column blockIdx.x -> their exclusive prefixes, in place
+__global__ void __launch_bounds__(256) as_scan_totals_kernel(fe* __restrict__ block_tot, uint64_t count, const uint32_t* __restrict__ kinds) {
+    __shared__ fe sh[256];
+    const uint32_t kind = kinds[blockIdx.x];
+    fe* tot = block_tot + (uint64_t)blockIdx.x * count;
+    const uint64_t per = (count + 255) / 256, base = (uint64_t)threadIdx.x * per;
+    fe acc = as_id(kind);
+    for (uint64_t j = 0; j < per; ++j)
+        if (base + j < count) acc = as_op(kind, acc, aa_ld(tot + base + j));
+    fe run = as_block_exclusive(kind, acc, sh, nullptr);
+    for (uint64_t j = 0; j < per; ++j)
+        if (base + j < count) {
+            const fe cur = aa_ld(tot + base + j);
+            aa_st(tot + base + j, run);
+            run = as_op(kind, run, cur);
+        }
+}
+
+__global__ void __launch_bounds__(256) as_apply_kernel(fe* __restrict__ data, uint64_t n, const uint32_t* __restrict__ kinds, const fe* __restrict__ block_prefix) {
+    __shared__ fe sh[256];
+    const uint32_t k = blockIdx.y, kind = kinds[k];
+    fe* col = data + (uint64_t)k * n;
+    const uint64_t base = (uint64_t)blockIdx.x * AS_BLOCK + (uint64_t)threadIdx.x * AS_PER_THREAD;
+    fe vals[AS_PER_THREAD];
+    fe acc = as_id(kind);
+#pragma unroll
+    for (int j = 0; j < AS_PER_THREAD; ++j) {
+        vals[j] = (base + j < n) ? aa_ld(col + base + j) : as_id(kind);
+        acc = as_op(kind, acc, vals[j]);
+    }
+    fe run = as_op(kind, aa_ld(block_prefix + (uint64_t)k * gridDim.x + blockIdx.x), as_block_exclusive(kind, acc, sh, nullptr));
+#pragma unroll
+    for (int j = 0; j < AS_PER_THREAD; ++j) {
+        if (base + j < n) aa_st(col + base + j, run);   // exclusive: row i gets the elements before it
+        run = as_op(kind, run, vals[j]);
+    }
+}
+
+uint64_t air_aux_scan_blocks(uint64_t n) { return (n + AS_BLOCK - 1) / AS_BLOCK; }
+
+int air_aux_scan(hipStream_t st, fe* data, uint64_t n, uint32_t K, const uint32_t* kinds, fe* block_tot) {
+    if (n == 0 || K == 0) return SP_OK;
+    const uint64_t blocks = air_aux_scan_blocks(n);
+    hipLaunchKernelGGL(as_block_totals_kernel, dim3((unsigned)blocks, K), dim3(256), 0, st, data, n, kinds, block_tot);
+    hipLaunchKernelGGL(as_scan_totals_kernel, dim3(K), dim3(256), 0, st, block_tot, blocks, kinds);
+    hipLaunchKernelGGL(as_apply_kernel, dim3((unsigned)blocks, K), dim3(256), 0, st, data, n, kinds, block_tot);
+    SP_HIP_CHECK(hipGetLastError());
+    return SP_OK;
+}
+
+}  // namespace sp

@@ -90,6 +90,7 @@ extern "C" {
 const char* sp_version(void) { return "stark252-hip 0.3 (gfx950)"; }
 int sp_abi_version(void) { return SP_ABI_VERSION; }
 uint64_t sp_air_desc_size(void) { return sizeof(sp_air_desc); }
+uint64_t sp_air_aux_desc_size(void) { return sizeof(sp_air_aux_desc); }
 int sp_air_limits(uint32_t out[8]) {
     if (!out) return SP_E_INVALID_ARG;
     const uint32_t lim[8] = {(uint32_t)sp::AIR_MAX_COLS, (uint32_t)sp::AIR_MAX_TRANSITIONS, (uint32_t)sp::AIR_MAX_OFFSETS, (uint32_t)sp::AIR_MAX_BOUNDARY,

@@ -368,9 +368,8 @@ int sp_last_round_ms(sp_ctx* c, float out[5]) {
     return SP_OK;
 }
 
-int sp_air_prove(sp_ctx* c, const sp_air_desc* d, const uint8_t* main_trace, uint64_t n, const sp_proof_options* opt,
-                 uint8_t** proof_out, uint64_t* proof_len) {
-    if (!c || !d || !main_trace || !opt || !proof_out || !proof_len) return SP_E_INVALID_ARG;
+static int air_prove_common(sp_ctx* c, const sp_air_desc* d, const sp::AirAuxHost* aux, const uint8_t* main_trace, uint64_t n,
+                            const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len) {
     c->prewarm_cancel.store(0, std::memory_order_release);
     if (d->n_offsets == 0 || d->n_offsets > 8 || d->n_transitions == 0 || d->n_transitions > 64 || (d->n_ops && !d->ops) ||
         (d->n_consts && !d->consts) || (d->n_boundary && !d->boundary)) { sp_set_error("sp_air_prove: malformed descriptor"); return SP_E_INVALID_ARG; }
@@ -389,7 +388,7 @@ int sp_air_prove(sp_ctx* c, const sp_air_desc* d, const uint8_t* main_trace, uin
     sp::ProofOptionsHost o{opt->blowup_factor, opt->fri_number_of_queries, opt->coset_offset, opt->grinding_factor};
     std::vector<uint8_t> proof;
     float ms[5] = {0, 0, 0, 0, 0};
-    int rc = sp::air_prove(c, a, main_trace, n, o, proof, ms);
+    int rc = sp::air_prove(c, a, main_trace, n, o, proof, ms, aux);
     if (rc != SP_OK) return rc;
     std::memcpy(c->round_ms, ms, sizeof(ms));
     uint8_t* out = (uint8_t*)std::malloc(proof.size());
@@ -397,6 +396,31 @@ int sp_air_prove(sp_ctx* c, const sp_air_desc* d, const uint8_t* main_trace, uin
     std::memcpy(out, proof.data(), proof.size());
     *proof_out = out; *proof_len = proof.size();
     return SP_OK;
+}
+
+int sp_air_prove(sp_ctx* c, const sp_air_desc* d, const uint8_t* main_trace, uint64_t n, const sp_proof_options* opt,
+                 uint8_t** proof_out, uint64_t* proof_len) {
+    if (!c || !d || !main_trace || !opt || !proof_out || !proof_len) return SP_E_INVALID_ARG;
+    return air_prove_common(c, d, nullptr, main_trace, n, opt, proof_out, proof_len);
+}
+
+int sp_air_prove_aux(sp_ctx* c, const sp_air_desc* d, const sp_air_aux_desc* x, const uint8_t* main_trace, uint64_t n,
+                     const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len) {
+    if (!c || !d || !x || !main_trace || !opt || !proof_out || !proof_len) return SP_E_INVALID_ARG;
+    if (d->aux_kind != SP_AIR_AUX_PROGRAM || d->aux_cols == 0 || x->n_cols != d->aux_cols) {
+        sp_set_error("sp_air_prove_aux: needs aux_kind SP_AIR_AUX_PROGRAM and aux->n_cols == air->aux_cols >= 1");
+        return SP_E_INVALID_ARG;
+    }
+    if ((x->n_ops && !x->ops) || (x->n_consts && !x->consts) || !x->cols) { sp_set_error("sp_air_prove_aux: malformed auxiliary program"); return SP_E_INVALID_ARG; }
+    if (x->n_ops > (uint32_t)sp::AIR_MAX_OPS || x->n_consts > (uint32_t)sp::AIR_MAX_CONSTS) {
+        sp_set_error("sp_air_prove_aux: the auxiliary program exceeds 65535 ops or 4096 constants");
+        return SP_E_INVALID_ARG;
+    }
+    sp::AirAuxHost aux;
+    for (uint32_t i = 0; i < x->n_ops; ++i) aux.ops.push_back(sp::AirOpHost{x->ops[i].op, x->ops[i].a, x->ops[i].b});
+    for (uint32_t i = 0; i < x->n_consts; ++i) aux.consts.push_back(fe_from_bytes_be(x->consts + 32 * (size_t)i));
+    for (uint32_t k = 0; k < x->n_cols; ++k) aux.cols.push_back(sp::AirAuxColumnHost{x->cols[k].kind, x->cols[k].num_op, x->cols[k].den_op});
+    return air_prove_common(c, d, &aux, main_trace, n, opt, proof_out, proof_len);
 }
 
 }  // extern "C"

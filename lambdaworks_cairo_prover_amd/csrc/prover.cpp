@@ -126,6 +126,7 @@ int StarkProver::setup_impl(uint64_t n, uint32_t main_cols, uint32_t aux_cols, b
     ready_ = false; stage_ = 0;
     d_auxws_ = nullptr; auxws_bytes_ = 0; auxws_pm_cap_ = 0; d_hfull_ = nullptr; d_hnat_ = nullptr; h_full_ = false;
     d_air_buf_ = nullptr; air_buf_cap_ = 0; d_ex_roots_ = nullptr; ex_roots_cap_ = 0;
+    d_auxp_buf_ = nullptr; auxp_buf_cap_ = 0; d_auxp_ws_ = nullptr; auxp_ws_cap_ = 0;
     d_flags_all_ = nullptr;
     d_gather_ = nullptr; gather_cap_ = 0; d_fullN_ = nullptr; d_small_ = nullptr; d_deepx_ = nullptr; deepx_cap_ = 0; d_cstage_ = nullptr; d_local_ = nullptr; d_recv_ = nullptr; d_roots_ = nullptr;
     opt_ = opt; n_ = n; logn_ = (uint32_t)k; logb_ = (uint32_t)lb; logN_ = logn_ + logb_; N_ = n << lb;
@@ -876,6 +877,136 @@ int StarkProver::commit_aux_cairo(const PublicInputs& pub, const fe rap[3], uint
     return commit_segment_resident(1, Ca_, root_out);
 }
 
+int validate_aux_program(const AirAuxHost& aux, uint32_t main_cols, uint32_t n_rap) {
+    const size_t n_ops = aux.ops.size();
+    if (n_ops == 0 || n_ops > (size_t)AIR_MAX_OPS) { sp_set_error("aux program: 1 .. 65535 ops"); return SP_E_INVALID_ARG; }
+    if (aux.consts.size() > (size_t)AIR_MAX_CONSTS) { sp_set_error("aux program: more than 4096 constants"); return SP_E_INVALID_ARG; }
+    if (aux.consts.size() + n_rap > 65535) { sp_set_error("aux program: constants and RAP challenges exceed the 16-bit operand range"); return SP_E_INVALID_ARG; }
+    if (aux.cols.empty() || aux.cols.size() > (size_t)AIR_MAX_COLS) { sp_set_error("aux program: 1 .. 1024 auxiliary columns"); return SP_E_INVALID_ARG; }
+    for (size_t t = 0; t < n_ops; ++t) {
+        const AirOpHost& o = aux.ops[t];
+        bool ok;
+        switch (o.op) {
+            case 0: ok = o.a <= AIR_AUX_MAX_SHIFT && o.b < main_cols; break;
+            case 1: ok = o.a < aux.consts.size() + n_rap; break;
+            case 2: case 3: case 4: ok = o.a < t && o.b < t; break;
+            default: ok = false;   // (no OUT: the columns name their ops)
+        }
+        if (!ok) {
+            sp_set_error("aux program: malformed op " + std::to_string(t) + " (LOAD needs a shift of 0 .. 7 and a main column, CONST a constant or a RAP "
+                         "challenge, ADD / SUB / MUL earlier ops; there is no OUT)");
+            return SP_E_INVALID_ARG;
+        }
+    }
+    for (size_t k = 0; k < aux.cols.size(); ++k) {
+        const AirAuxColumnHost& c = aux.cols[k];
+        if (c.kind > SP_AIR_AUX_SUM || c.num_op >= n_ops || (c.den_op != SP_AIR_AUX_NO_DEN && c.den_op >= n_ops)) {
+            sp_set_error("aux program: column " + std::to_string(k) + " has an unknown kind or names an op beyond the program");
+            return SP_E_INVALID_ARG;
+        }
+    }
+    return SP_OK;
+}
+
+// Chunks of columns bound the workspace: a chunk holds at most max(1, AUXP_CHUNK_ELEMS / n) columns, so its denominators take
+// at most max(2^22, n) elements (128 MB up to 2^22 rows, 32 bytes a row beyond) and the batch inversion as much scratch again,
+// whatever the number of auxiliary columns.  The numerators are written straight into the trace columns they become.
+static constexpr uint64_t AUXP_CHUNK_ELEMS = 1ull << 22;
+
+int StarkProver::commit_aux_program(const AirAuxHost& aux, const std::vector<fe>& rap, uint8_t root_out[32]) {
+    const uint32_t K = (uint32_t)aux.cols.size();
+    if (stage_ != 2 || K == 0 || K != Ca_) { sp_set_error("commit_aux_program: main segment not committed or auxiliary column count differs"); return SP_E_STATE; }
+    SP_TRY(validate_aux_program(aux, Cm_, (uint32_t)rap.size()));
+    SP_HIP_CHECK(hipSetDevice(c_->device));
+    const uint32_t chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(K, AUXP_CHUNK_ELEMS / n_));
+    const uint64_t nb = air_aux_scan_blocks(n_);
+    // --- per chunk: the program with an OUT behind every op whose value is an N or a D of the chunk's columns (a value then lives
+    //     only until it is stored), slots by air_assign_slots (which drops what the chunk does not need)
+    struct Chunk { uint32_t k0, kc, n_den; std::vector<AirOpDev> ops; std::vector<uint32_t> kinds, col_of; size_t o_ops, o_kinds, o_col; };
+    std::vector<Chunk> chunks;
+    uint32_t max_den = 0;
+    const uint32_t n_src = (uint32_t)aux.ops.size();
+    for (uint32_t k0 = 0; k0 < K; k0 += chunk) {
+        Chunk ch{};
+        ch.k0 = k0; ch.kc = std::min(chunk, K - k0);
+        std::vector<std::vector<uint32_t>> outs(n_src);
+        for (uint32_t k = 0; k < ch.kc; ++k) {
+            const AirAuxColumnHost& c = aux.cols[k0 + k];
+            ch.kinds.push_back(c.kind);
+            outs[c.num_op].push_back(k);
+            if (c.den_op != SP_AIR_AUX_NO_DEN) { outs[c.den_op].push_back(AIR_AUX_DEN_TAG + ch.n_den); ch.col_of.push_back(k); ++ch.n_den; }
+        }
+        std::vector<AirOpHost> ext;
+        std::vector<uint32_t> at(n_src);
+        ext.reserve(n_src + 2 * ch.kc);
+        for (uint32_t t = 0; t < n_src; ++t) {
+            AirOpHost o = aux.ops[t];
+            if (o.op >= 2) { o.a = at[o.a]; o.b = at[o.b]; }
+            at[t] = (uint32_t)ext.size();
+            ext.push_back(o);
+            for (uint32_t code : outs[t]) ext.push_back(AirOpHost{5, code, at[t]});
+        }
+        SP_TRY(air_assign_slots(ext, ch.ops, "aux program: more than 64 values alive at once"));
+        max_den = std::max(max_den, ch.n_den);
+        chunks.push_back(std::move(ch));
+    }
+    // --- one upload: constants (then the RAP challenges), and per chunk its ops, column kinds and denominator -> column table
+    size_t bytes = 0;
+    auto place = [&bytes](size_t b) { const size_t o = bytes; bytes = (bytes + b + 255) & ~size_t(255); return o; };
+    const size_t o_consts = place(sizeof(fe) * std::max<size_t>(1, aux.consts.size() + rap.size()));
+    for (Chunk& ch : chunks) {
+        ch.o_ops = place(sizeof(AirOpDev) * ch.ops.size());
+        ch.o_kinds = place(sizeof(uint32_t) * ch.kc);
+        ch.o_col = place(sizeof(uint32_t) * std::max<uint32_t>(1, ch.n_den));
+    }
+    if (bytes > auxp_buf_cap_) {
+        release(d_auxp_buf_, auxp_buf_cap_);
+        d_auxp_buf_ = nullptr; auxp_buf_cap_ = 0;
+        SP_TRY(alloc((void**)&d_auxp_buf_, bytes));
+        auxp_buf_cap_ = bytes;
+    }
+    std::vector<uint8_t>& up = h_auxp_up_;
+    up.assign(bytes, 0);
+    fe* hconst = reinterpret_cast<fe*>(up.data() + o_consts);
+    for (size_t i = 0; i < aux.consts.size(); ++i) hconst[i] = aux.consts[i];
+    for (size_t i = 0; i < rap.size(); ++i) hconst[aux.consts.size() + i] = rap[i];
+    for (const Chunk& ch : chunks) {
+        std::memcpy(up.data() + ch.o_ops, ch.ops.data(), sizeof(AirOpDev) * ch.ops.size());
+        std::memcpy(up.data() + ch.o_kinds, ch.kinds.data(), sizeof(uint32_t) * ch.kc);
+        if (ch.n_den) std::memcpy(up.data() + ch.o_col, ch.col_of.data(), sizeof(uint32_t) * ch.n_den);
+    }
+    SP_HIP_CHECK(hipMemcpyAsync(d_auxp_buf_, up.data(), bytes, hipMemcpyHostToDevice, c_->stream));
+    // --- workspace: [max_den][n] denominators, as much batch-inversion scratch, [chunk][nb] scan block totals
+    const uint64_t ws = 2 * (uint64_t)max_den * n_ + (uint64_t)chunk * nb;
+    if (ws > auxp_ws_cap_) {
+        release(d_auxp_ws_, auxp_ws_cap_ * sizeof(fe));
+        d_auxp_ws_ = nullptr; auxp_ws_cap_ = 0;
+        SP_TRY(alloc((void**)&d_auxp_ws_, sizeof(fe) * ws));
+        auxp_ws_cap_ = ws;
+    }
+    fe* den = d_auxp_ws_;
+    fe* scratch = den + (uint64_t)max_den * n_;
+    fe* block_tot = scratch + (uint64_t)max_den * n_;
+    const fe* consts_dev = reinterpret_cast<const fe*>(d_auxp_buf_ + o_consts);
+    SP_HIP_CHECK(hipMemsetAsync(c_->d_flag, 0, sizeof(int), c_->stream));
+    for (const Chunk& ch : chunks) {
+        fe* cols = d_trace_ + (uint64_t)(Cm_ + ch.k0) * n_;
+        const uint32_t* kinds = reinterpret_cast<const uint32_t*>(d_auxp_buf_ + ch.o_kinds);
+        SP_TRY(air_aux_terms(c_->stream, d_trace_, n_, reinterpret_cast<const AirOpDev*>(d_auxp_buf_ + ch.o_ops), (uint32_t)ch.ops.size(), consts_dev, cols, den));
+        if (ch.n_den) {
+            SP_TRY(batch_inverse(c_->stream, den, scratch, (uint64_t)ch.n_den * n_, c_->d_flag));
+            SP_TRY(air_aux_apply_den(c_->stream, cols, den, reinterpret_cast<const uint32_t*>(d_auxp_buf_ + ch.o_col), ch.n_den, n_));
+        }
+        SP_TRY(air_aux_scan(c_->stream, cols, n_, ch.kc, kinds, block_tot));
+    }
+    // the zero-denominator flag rides behind the columns; the read-back of the root below waits for it
+    if (!h_wide_ && hipHostMalloc(reinterpret_cast<void**>(&h_wide_), 64, hipHostMallocDefault) != hipSuccess) { h_wide_ = nullptr; sp_set_error("pinned flag slot: allocation failed"); return SP_E_ALLOC; }
+    SP_HIP_CHECK(hipMemcpyAsync(h_wide_ + 5, c_->d_flag, sizeof(int), hipMemcpyDeviceToHost, c_->stream));
+    SP_TRY(commit_segment_resident(1, K, root_out));
+    if (h_wide_[5]) { sp_set_error("commit_aux_program: an auxiliary column's denominator is zero on some row"); return SP_E_ZERO_INVERSE; }
+    return SP_OK;
+}
+
 int StarkProver::composition_precheck(const fe rap[3], const std::vector<BoundaryConstraint>& bcs, uint32_t n_transitions) {
     check_pending_ = false;
     if (stage_ != 3 && !(stage_ == 2 && Ca_ == 0)) { sp_set_error("composition_precheck: trace segments not committed"); return SP_E_STATE; }
@@ -974,6 +1105,47 @@ int StarkProver::composition(const fe rap[3], const std::vector<BoundaryConstrai
     return composition_core(&K, points, nullptr, nullptr, nullptr, true, root_out);
 }
 
+// Values nobody reads (directly or through other unread values) are not part of the program the device runs: giving such a value
+// "any" slot would overwrite a live one when all AIR_MAX_LIVE are taken.  Liveness backwards from the OUT ops, then slots.
+int air_assign_slots(const std::vector<AirOpHost>& ops, std::vector<AirOpDev>& dops, const char* live_error) {
+    const uint32_t n_src = (uint32_t)ops.size();
+    dops.clear();
+    std::vector<uint8_t> live(n_src, 0);
+    for (uint32_t t = n_src; t-- > 0;) {
+        const AirOpHost& o = ops[t];
+        if (o.op == 5) { live[t] = 1; live[o.b] = 1; }
+        else if (live[t] && o.op >= 2 && o.op <= 4) { live[o.a] = 1; live[o.b] = 1; }
+    }
+    std::vector<uint32_t> last_use(n_src, 0);
+    for (uint32_t t = 0; t < n_src; ++t) {
+        if (!live[t]) continue;
+        const AirOpHost& o = ops[t];
+        if (o.op >= 2 && o.op <= 4) { last_use[o.a] = t; last_use[o.b] = t; }
+        else if (o.op == 5) last_use[o.b] = t;
+    }
+    std::vector<uint16_t> slot_of(n_src, 0), free_slots;
+    for (int sl = AIR_MAX_LIVE - 1; sl >= 0; --sl) free_slots.push_back((uint16_t)sl);
+    std::vector<std::vector<uint32_t>> dying(n_src);    // values whose last use is op t
+    for (uint32_t t = 0; t < n_src; ++t) if (live[t] && ops[t].op != 5) dying[last_use[t]].push_back(t);
+    for (uint32_t t = 0; t < n_src; ++t) {
+        if (!live[t]) continue;
+        const AirOpHost& o = ops[t];
+        AirOpDev d{};
+        d.op = o.op;
+        if (o.op >= 2 && o.op <= 4) { d.a = slot_of[o.a]; d.b = slot_of[o.b]; }
+        else if (o.op == 5) { d.a = (uint16_t)o.a; d.b = slot_of[o.b]; }
+        else { d.a = (uint16_t)o.a; d.b = (uint16_t)o.b; }
+        for (uint32_t v : dying[t]) free_slots.push_back(slot_of[v]);   // operands read before the result is written
+        if (o.op != 5) {
+            if (free_slots.empty()) { sp_set_error(live_error); return SP_E_UNSUPPORTED; }
+            d.dst = free_slots.back(); free_slots.pop_back();
+            slot_of[t] = d.dst;
+        }
+        dops.push_back(d);
+    }
+    return SP_OK;
+}
+
 int StarkProver::composition_air(const AirDescHost& air, const std::vector<fe>& rap, const std::vector<fe>& b_alpha, const std::vector<fe>& b_beta,
                                  const std::vector<fe>& t_alpha, const std::vector<fe>& t_beta, uint8_t root_out[32]) {
     if (stage_ != 3 && !(stage_ == 2 && Ca_ == 0)) { sp_set_error("composition: trace segments not committed"); return SP_E_STATE; }
@@ -996,58 +1168,20 @@ int StarkProver::composition_air(const AirDescHost& air, const std::vector<fe>& 
     prog.n_offsets = R;
     for (uint32_t k = 0; k < R; ++k) prog.offsets[k] = air.offsets[k];
     std::vector<bool> produced(T, false);
-    std::vector<uint32_t> last_use(prog.n_ops, 0);
     for (uint32_t t = 0; t < prog.n_ops; ++t) {
         const AirOpHost& o = air.ops[t];
         bool ok = true;
         switch (o.op) {
             case 0: ok = o.a < R && o.b < C_; break;
             case 1: ok = o.a < air.consts.size() + rap.size(); break;
-            case 2: case 3: case 4: ok = o.a < t && o.b < t && air.ops[o.a].op != 5 && air.ops[o.b].op != 5; if (ok) { last_use[o.a] = t; last_use[o.b] = t; } break;
-            case 5: ok = o.a < T && o.b < t && air.ops[o.b].op != 5; if (ok) { produced[o.a] = true; last_use[o.b] = t; } break;
+            case 2: case 3: case 4: ok = o.a < t && o.b < t && air.ops[o.a].op != 5 && air.ops[o.b].op != 5; break;
+            case 5: ok = o.a < T && o.b < t && air.ops[o.b].op != 5; if (ok) produced[o.a] = true; break;
             default: ok = false;
         }
         if (!ok) { sp_set_error("composition_air: malformed constraint program"); return SP_E_INVALID_ARG; }
     }
-    {
-        // Values nobody reads (directly or through other unread values) are not part of the program the device runs: giving such
-        // a value "any" slot would overwrite a live one when all 64 are taken.  Liveness backwards from the OUT ops, then slots.
-        const uint32_t n_src = prog.n_ops;
-        std::vector<uint8_t> live(n_src, 0);
-        for (uint32_t t = n_src; t-- > 0;) {
-            const AirOpHost& o = air.ops[t];
-            if (o.op == 5) { live[t] = 1; live[o.b] = 1; }
-            else if (live[t] && o.op >= 2 && o.op <= 4) { live[o.a] = 1; live[o.b] = 1; }
-        }
-        std::fill(last_use.begin(), last_use.end(), 0u);
-        for (uint32_t t = 0; t < n_src; ++t) {
-            if (!live[t]) continue;
-            const AirOpHost& o = air.ops[t];
-            if (o.op >= 2 && o.op <= 4) { last_use[o.a] = t; last_use[o.b] = t; }
-            else if (o.op == 5) last_use[o.b] = t;
-        }
-        std::vector<uint16_t> slot_of(n_src, 0), free_slots;
-        for (int sl = AIR_MAX_LIVE - 1; sl >= 0; --sl) free_slots.push_back((uint16_t)sl);
-        std::vector<std::vector<uint32_t>> dying(n_src);    // values whose last use is op t
-        for (uint32_t t = 0; t < n_src; ++t) if (live[t] && air.ops[t].op != 5) dying[last_use[t]].push_back(t);
-        for (uint32_t t = 0; t < n_src; ++t) {
-            if (!live[t]) continue;
-            const AirOpHost& o = air.ops[t];
-            AirOpDev d{};
-            d.op = o.op;
-            if (o.op >= 2 && o.op <= 4) { d.a = slot_of[o.a]; d.b = slot_of[o.b]; }
-            else if (o.op == 5) { d.a = o.a; d.b = slot_of[o.b]; }
-            else { d.a = o.a; d.b = o.b; }
-            for (uint32_t v : dying[t]) free_slots.push_back(slot_of[v]);   // operands read before the result is written
-            if (o.op != 5) {
-                if (free_slots.empty()) { sp_set_error("composition_air: more than 64 values alive at once in the constraint program"); return SP_E_UNSUPPORTED; }
-                d.dst = free_slots.back(); free_slots.pop_back();
-                slot_of[t] = d.dst;
-            }
-            dops.push_back(d);
-        }
-        prog.n_ops = (uint32_t)dops.size();
-    }
+    SP_TRY(air_assign_slots(air.ops, dops, "composition_air: more than 64 values alive at once in the constraint program"));
+    prog.n_ops = (uint32_t)dops.size();
     // --- transition exemptions (traits.rs:49-79, evaluator.rs:299-323): distinct non-zero counts; with
     //     num_transition_exemptions == 1 every exempted constraint uses the first of them
     std::vector<uint32_t> uniq;

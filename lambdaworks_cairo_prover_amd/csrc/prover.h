@@ -5,6 +5,7 @@
 #include "stark_kernels.h"
 #include "cairo_air_host.h"
 #include "aux_kernels.h"
+#include "air_aux_kernels.h"
 #include "trace_kernels.h"
 #include "cairo_host.h"
 #include <vector>
@@ -17,7 +18,7 @@ namespace sp {
 struct ProofOptionsHost { uint8_t blowup_factor; uint64_t fri_number_of_queries; uint64_t coset_offset; uint8_t grinding_factor; };
 
 // Host form of sp_air_desc (include/stark252_hip.h).
-struct AirOpHost { uint8_t op; uint16_t a, b; };   // as the caller wrote it: operands are indices of earlier ops
+struct AirOpHost { uint8_t op; uint32_t a, b; };   // as the caller wrote it: operands are indices of earlier ops
 struct AirDescHost {
     uint32_t main_cols = 0, aux_cols = 0;
     std::vector<uint32_t> offsets, degrees, exemptions;
@@ -28,6 +29,20 @@ struct AirDescHost {
     sp_aux_trace_fn aux_fn = nullptr; void* aux_user = nullptr;   // aux_kind 2: build_auxiliary_trace supplied by the caller
     std::vector<BoundaryConstraint> boundary;
 };
+// Host form of sp_air_aux_desc: the auxiliary program of an AIR with aux_kind SP_AIR_AUX_PROGRAM.
+struct AirAuxColumnHost { uint32_t kind, num_op, den_op; };
+struct AirAuxHost {
+    std::vector<AirOpHost> ops;
+    std::vector<fe> consts;
+    std::vector<AirAuxColumnHost> cols;
+};
+// Checks an auxiliary program against its AIR (operands refer to earlier ops, LOADs to main columns at shifts 0 .. 7, CONSTs to
+// the constants or the n_rap challenges, every column's ops exist).  SP_E_INVALID_ARG with sp_last_error() set otherwise.
+int validate_aux_program(const AirAuxHost& aux, uint32_t main_cols, uint32_t n_rap);
+// Value slots of a straight-line program (ops 0 - 4 produce a value, op 5 OUT consumes op b): values that no OUT reads, directly
+// or through other values, are dropped; every other value gets one of AIR_MAX_LIVE slots, released after its last use.  The ops
+// must already be validated.  SP_E_UNSUPPORTED with `live_error` as sp_last_error() when more than AIR_MAX_LIVE are alive at once.
+int air_assign_slots(const std::vector<AirOpHost>& ops, std::vector<AirOpDev>& out, const char* live_error);
 
 struct Openings {
     uint32_t n_queries = 0, n_layers = 0, n_cols = 0, depth0 = 0;
@@ -58,6 +73,9 @@ class StarkProver : public sp_deletable {
                      int col_enc = -1, uint64_t col_stride = 0);
     // round 1, Cairo auxiliary segment built on the device from the resident main trace (reference cairo/air.rs:660-729)
     int commit_aux_cairo(const PublicInputs& pub, const fe rap[3], uint8_t root_out[32]);
+    // round 1, auxiliary segment of a program AIR built on the device from an auxiliary program (validate_aux_program first) and
+    // the RAP challenges: per-row N and D, one batch inversion, an exclusive product / sum scan per column, commit_segment_resident
+    int commit_aux_program(const AirAuxHost& aux, const std::vector<fe>& rap, uint8_t root_out[32]);
     // round 2: constraint composition, H1/H2 split, LDE and commitment
     int composition(const fe rap[3], const std::vector<BoundaryConstraint>& bcs, const std::vector<fe>& b_alpha,
                     const std::vector<fe>& b_beta, const std::vector<fe>& t_alpha, const std::vector<fe>& t_beta,
@@ -255,6 +273,10 @@ class StarkProver : public sp_deletable {
     // program AIRs: header, ops, constants and per-proof tables in one buffer (composition_air), grown on demand
     uint8_t* d_air_buf_ = nullptr; size_t air_buf_cap_ = 0; std::vector<uint8_t> h_air_up_;
     fe* d_ex_roots_ = nullptr; uint32_t ex_roots_cap_ = 0;
+    // auxiliary programs (commit_aux_program): ops, constants and column tables of every chunk in one buffer, and the N / D
+    // workspace (denominators, batch-inversion scratch, scan block totals); both grown on demand and kept across proofs of a shape
+    uint8_t* d_auxp_buf_ = nullptr; size_t auxp_buf_cap_ = 0; std::vector<uint8_t> h_auxp_up_;
+    fe* d_auxp_ws_ = nullptr; uint64_t auxp_ws_cap_ = 0;
     DeepConsts* d_deep_consts_ = nullptr;
     fe* d_deep_gammas_ = nullptr;                      // [AIR_MAX_OFFSETS][C], behind the DeepConsts in the same allocation
     static size_t deep_gammas_at() { return (sizeof(DeepConsts) + 255) & ~size_t(255); }
@@ -325,7 +347,8 @@ int cairo_prove(sp_ctx* ctx, const uint8_t* main_trace, uint64_t n, uint32_t col
 // Whole proof for an AIR given as a constraint program: `prove::<F, A>` (reference src/starks/prover.rs:532-766) + serialize.
 // main_trace: row-major n x air.main_cols in the context encoding (host memory).
 // round_ms (nullable): device time of rounds 1 - 4 in [1..4], as cairo_prove.
+// aux (nullable): the auxiliary program of an AIR with aux_kind SP_AIR_AUX_PROGRAM (sp_air_prove_aux).
 int air_prove(sp_ctx* ctx, const AirDescHost& air, const uint8_t* main_trace, uint64_t n, const ProofOptionsHost& opt,
-              std::vector<uint8_t>& proof_out, float round_ms[5] = nullptr);
+              std::vector<uint8_t>& proof_out, float round_ms[5] = nullptr, const AirAuxHost* aux = nullptr);
 
 }  // namespace sp

@@ -265,10 +265,10 @@ int cairo_prove(sp_ctx* ctx, const uint8_t* main_trace, uint64_t n, uint32_t col
 }
 
 // prove::<F, A> for a program AIR (reference src/starks/prover.rs:532-766): same rounds, the AIR-specific parts come from
-// the descriptor - RAP challenges (n_rap field samples), auxiliary trace (by kind, built on the host: the example AIRs are
-// tiny), boundary constraints, transition program.
+// the descriptor - RAP challenges (n_rap field samples), auxiliary trace (by kind: the fibonacci_rap column and the caller's
+// callback on the host - the example AIRs are tiny -, an auxiliary program on the device), boundary constraints, transition program.
 int air_prove(sp_ctx* ctx, const AirDescHost& air, const uint8_t* main_trace, uint64_t n, const ProofOptionsHost& opt,
-              std::vector<uint8_t>& proof_out, float round_ms[5]) {
+              std::vector<uint8_t>& proof_out, float round_ms[5], const AirAuxHost* aux) {
     try {
         if (air.main_cols == 0 || (uint64_t)air.main_cols + air.aux_cols > (uint64_t)AIR_MAX_COLS) {
             sp_set_error("air_prove: column count out of range (1 .. 1024 columns, main + aux)");
@@ -278,6 +278,13 @@ int air_prove(sp_ctx* ctx, const AirDescHost& air, const uint8_t* main_trace, ui
         if (air.consts.size() > (size_t)AIR_MAX_CONSTS) { sp_set_error("air_prove: more than 4096 constants"); return SP_E_INVALID_ARG; }
         if (air.consts.size() + air.n_rap > 65535) { sp_set_error("air_prove: constants and RAP challenges exceed the 16-bit operand range"); return SP_E_INVALID_ARG; }
         if (air.ops.size() > (size_t)AIR_MAX_OPS) { sp_set_error("air_prove: more than 65535 ops"); return SP_E_INVALID_ARG; }
+        if (aux) {
+            if (air.aux_kind != SP_AIR_AUX_PROGRAM || air.aux_cols == 0 || aux->cols.size() != air.aux_cols) {
+                sp_set_error("air_prove: an auxiliary program needs aux_kind SP_AIR_AUX_PROGRAM and one column per auxiliary column");
+                return SP_E_INVALID_ARG;
+            }
+            SP_TRY(validate_aux_program(*aux, air.main_cols, air.n_rap));
+        }
         StarkProver* P = &prover_holder(ctx, true)->prover;   // kept (with its device buffers) across proofs of the same shape on this context
         if (opt.fri_number_of_queries == 0) { sp_set_error("prove: fri_number_of_queries must be at least 1 (the reference emits a proof without openings for 0; this prover does not)"); return SP_E_INVALID_ARG; }
         hipEvent_t* ev = prover_holder(ctx, true)->air_ev;
@@ -302,6 +309,11 @@ int air_prove(sp_ctx* ctx, const AirDescHost& air, const uint8_t* main_trace, ui
             if (!rap.empty()) SP_TRY(sp_fe_from_device(ctx->enc, reinterpret_cast<const uint8_t*>(rap.data()), rap.size(), rap_bytes.data()));
             if (air.aux_fn(air.aux_user, rap_bytes.data(), (uint32_t)rap.size(), aux_rows.data()) != 0) { sp_set_error("air_prove: the auxiliary-trace callback failed"); return SP_E_INVALID_ARG; }
             SP_TRY(P->commit_trace(1, aux_rows.data(), air.aux_cols, root));
+            roots.emplace_back(); std::memcpy(roots.back().data(), root, 32);
+            tr.append(root, 32);
+        } else if (air.aux_cols && air.aux_kind == SP_AIR_AUX_PROGRAM && aux) {
+            // the auxiliary program on the device, from the resident main trace (every rank holds all of it: no exchange)
+            SP_TRY(P->commit_aux_program(*aux, rap, root));
             roots.emplace_back(); std::memcpy(roots.back().data(), root, 32);
             tr.append(root, 32);
         } else if (air.aux_cols) {
