@@ -28,7 +28,8 @@ struct NttPassArgs {
     fe* dst;
     uint64_t src_vec_stride, dst_vec_stride;  // elements between consecutive vectors of the batch
     const fe* small_tw;   // s = 0 pass: w_R^(+-e), e in [0, R/2)   (direction chosen by the host)
-    const fe* big_tw;     // strided passes: w_M^e, e in [0, M/2)  (forward roots; the inverse butterfly uses w^-e = -w^(M/2-e))
+    const fe* big_tw;     // strided passes: w_M^e, e in [0, M/2)  (forward roots; the inverse butterfly uses w^-e = -w^(M/2-e));
+                          // with stage_tw the engine's pyramid of per-stage tables: w_(2^J)^x at entry 2^(J-1) + x, x < 2^(J-1)
     const fe* post_table; // DIF only, nullable: multiply the element stored at position pos by post_table[pos]
     const fe* scalar;     // nullable: multiply every stored element by *scalar (device pointer)
     uint32_t logM;        // transform size (twiddles are powers of w_(2^logM))
@@ -45,6 +46,7 @@ struct NttPassArgs {
     uint64_t src_coset_stride, dst_coset_stride;
     // 1 on every pass but the last one of a transform: the stored data is only brought below 2p; 0: canonical values.
     uint32_t weak_out;
+    uint32_t stage_tw;    // 1: big_tw is the pyramid, stage J reads its own dense table (adjacent columns = adjacent entries)
     uint32_t radix4;      // two stages per LDS round trip (filled in by the launcher)
     uint32_t batch;       // vectors per launch (filled in by the launcher)
     uint32_t xcd_map;     // 1: XCD-aware block -> (tile, vector) mapping (needs tiles % 8 == 0)
@@ -57,8 +59,13 @@ class NttEngine {
   public:
     explicit NttEngine(hipStream_t stream) : stream_(stream) {}
     ~NttEngine();
-    // device table w_(2^k)^e, e in [0, 2^(k-1)); cached per k
+    // device table w_(2^k)^e, e in [0, 2^(k-1)); cached per k (a slice of the pyramid below where one covers k).  The pointer
+    // stays valid until the engine is destroyed.
     int roots(int k, const fe** out);
+    // Pyramid of per-stage twiddle tables covering every stage J <= k: entry 2^(J-1) + x = w_(2^J)^x, x < 2^(J-1) (2^k' entries for
+    // some k' >= k; the slice at 2^(J-1) is roots(J)).  *out = nullptr when the device has no room for it: the transforms then
+    // address the single table roots(k) with a stride, as they do when built with -DSP_NTT_STAGE_TW=0.
+    int stage_tables(int k, const fe** out);
     // device table w_(2^k)^(-e), e in [0, 2^(k-1)); only for small k (pass twiddles)
     int inv_roots_small(int k, const fe** out);
 
@@ -91,7 +98,11 @@ class NttEngine {
   private:
     int launch_pass(bool dif, int load_mode, int store_mode, const NttPassArgs& a, uint32_t batch);
     hipStream_t stream_;
-    std::map<int, fe*> roots_;
+    // twiddles of a whole transform: pyramid + stage_tw = 1, or roots(k) + stage_tw = 0
+    int transform_twiddles(int k, NttPassArgs* a);
+    std::map<int, fe*> roots_;       // stand-alone tables (no pyramid covered k and none could be allocated)
+    std::vector<fe*> pyramids_;      // the last one is the largest; older ones stay alive for kernels in flight and cached roots()
+    int pyramid_log_ = -1;
     std::map<int, fe*> inv_small_;
     fe* d_scalar_ = nullptr;
 };

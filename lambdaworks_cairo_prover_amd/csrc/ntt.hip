@@ -2,6 +2,12 @@
 #include "ntt.h"
 #include <algorithm>
 
+// 1: the strided passes of whole transforms read every stage's twiddles from that stage's own dense table (NttEngine::stage_tables);
+// 0: from the single table w_M^e with a stride, as the LDE passes do.  Same values either way (A/B: tools/sweep_ntt_variants.sh).
+#ifndef SP_NTT_STAGE_TW
+#define SP_NTT_STAGE_TW 1
+#endif
+
 namespace sp {
 
 // ---------------------------------------------------------------------------------------------- device helpers
@@ -44,6 +50,9 @@ __device__ __forceinline__ uint32_t bitrev(uint32_t x, uint32_t bits) { return b
 //    of its own butterflies: w_M^(((i << a.s) + column) << (logM - a.s - j)), i = row mod 2^(j-1); the global column of
 //    local column c is (c << shard_log) | shard_rank.  Stages j < r go to LDS (entry (2^(j-1) - 1 + i) * G + gl), the
 //    twiddles of stage r serve one butterfly each and go straight to registers.  There is no inter-pass twiddle product.
+//    With a.stage_tw the same value w_(2^J)^x, J = a.s + j, x = (i << a.s) + column, comes from stage J's own dense table
+//    (entry 2^(J-1) + x of the pyramid): the G columns of a tile row are G adjacent entries, so no fetched 128-byte line
+//    carries twiddles of other stages (every 2^(logM-J)-th entry of the single table: a line per twiddle from stride 4 on).
 //  * Deferred reduction (fp.h): p > 2^251, so every 256-bit value is < 32p.  Pass input < 2p.  DIT: t = v w < 2p and the
 //    outputs u + t, u - t + 2p grow by 2p per stage - no correction for the <= 10 stages of a pass.  DIF: x + y doubles
 //    the bound, (y - x + kb p) w is < 2p again; the sum is brought back below 2p every third stage (kb = 2, 4, 8).
@@ -109,10 +118,13 @@ __global__ void __launch_bounds__(NTT_THREADS) ntt_pass_kernel(NttPassArgs a) {
     }
     auto global_tw = [&](uint32_t jm1, uint32_t i, uint32_t gl) -> fe {
         const uint32_t col = ((lo0 + gl) << a.tw_shift) | tw_low;
-        const uint32_t e = ((i << sg) + col) << (logM - sg - jm1 - 1u);
-        if (!DIF) return ld_fe(a.big_tw + e);
-        if (e == 0) return fe_neg_one();
-        return ld_fe(a.big_tw + ((1u << (logM - 1)) - e));
+        const uint32_t x = (i << sg) + col, h = 1u << (sg + jm1);   // w_(2^J)^x, x < h = 2^(J-1)
+        // single table: entry x << (logM - J); pyramid: entry h + x.  The inverse butterfly mirrors x -> h - x in both.
+        const bool pyr = SP_NTT_STAGE_TW && a.stage_tw;
+        const uint32_t sh = pyr ? 0u : logM - sg - jm1 - 1u, off = pyr ? h : 0u;
+        if (!DIF) return ld_fe(a.big_tw + off + (x << sh));
+        if (x == 0) return fe_neg_one();
+        return ld_fe(a.big_tw + off + ((h - x) << sh));
     };
     constexpr int BPT = (1 << (NTT_TILE_LOG - 1)) / NTT_THREADS;   // butterflies per thread and stage (at most)
     fe tw_last[(GLOBAL_TW && !CONTIG) ? BPT : 1];
@@ -390,32 +402,72 @@ fe host_primitive_root(int k) {
 
 NttEngine::~NttEngine() {
     for (auto& kv : roots_) (void)hipFree(kv.second);
+    for (fe* p : pyramids_) (void)hipFree(p);
     for (auto& kv : inv_small_) (void)hipFree(kv.second);
     if (d_scalar_) (void)hipFree(d_scalar_);
 }
 
-static int gen_table(hipStream_t st, fe w, int bits, uint32_t count, fe** out) {
-    fe* d = nullptr;
-    SP_HIP_CHECK(hipMalloc(&d, sizeof(fe) * (size_t)std::max<uint32_t>(count, 1)));
+// d[e] = w^e, e < count
+static int fill_table(hipStream_t st, fe w, int bits, uint32_t count, fe* d) {
     RootGenArgs args;
     fe cur = w;
     for (int i = 0; i < 32; ++i) { args.pw[i] = cur; cur = fe_sqr(cur); }
     uint32_t blocks = (count + 255) / 256;
     hipLaunchKernelGGL(gen_roots_kernel, dim3(blocks), dim3(256), 0, st, d, count, (uint32_t)bits, args);
     SP_HIP_CHECK(hipGetLastError());
+    return SP_OK;
+}
+static int gen_table(hipStream_t st, fe w, int bits, uint32_t count, fe** out) {
+    fe* d = nullptr;
+    SP_HIP_CHECK(hipMalloc(&d, sizeof(fe) * (size_t)std::max<uint32_t>(count, 1)));
+    const int rc = fill_table(st, w, bits, count, d);
+    if (rc != SP_OK) { (void)hipFree(d); return rc; }
     *out = d;
+    return SP_OK;
+}
+
+// One allocation of 2^kp entries holds the tables of every J <= kp (entry 0 = w_1^0 = 1 serves J = 0).  Every table is generated
+// from its own root like a stand-alone roots(J): host_primitive_root(J) = host_primitive_root(kp)^(2^(kp-J)) and all entries are
+// canonical, so a slice holds the bytes roots(J) always held.  A larger size builds a new pyramid; the smaller ones are kept
+// because kernels in flight and the callers' cached roots() pointers still read them.
+int NttEngine::stage_tables(int k, const fe** out) {
+    *out = nullptr;
+    if (!SP_NTT_STAGE_TW || k > 31) return SP_OK;
+    if (k > pyramid_log_) {
+        const int kp = std::max(k, NTT_TILE_LOG);    // one small pyramid serves all pass-local tables
+        fe* d = nullptr;
+        if (hipMalloc(&d, sizeof(fe) << kp) != hipSuccess) { (void)hipGetLastError(); return SP_OK; }   // no room: single-table addressing
+        int rc = fill_table(stream_, fe_one(), 0, 1, d);
+        for (int J = 1; J <= kp && rc == SP_OK; ++J) rc = fill_table(stream_, host_primitive_root(J), J, 1u << (J - 1), d + (1u << (J - 1)));
+        if (rc != SP_OK) { (void)hipFree(d); return rc; }
+        pyramids_.push_back(d);
+        pyramid_log_ = kp;
+    }
+    *out = pyramids_.back();
     return SP_OK;
 }
 
 int NttEngine::roots(int k, const fe** out) {
     auto it = roots_.find(k);
     if (it == roots_.end()) {
+        const fe* pyr = nullptr;
+        SP_TRY(stage_tables(k, &pyr));
+        if (pyr) { *out = pyr + (k == 0 ? 0u : (1u << (k - 1))); return SP_OK; }
         fe* d = nullptr;
         uint32_t count = k == 0 ? 1u : (1u << (k - 1));
         SP_TRY(gen_table(stream_, host_primitive_root(k), k, count, &d));
         it = roots_.emplace(k, d).first;
     }
     *out = it->second;
+    return SP_OK;
+}
+
+int NttEngine::transform_twiddles(int k, NttPassArgs* a) {
+    const fe* pyr = nullptr;
+    SP_TRY(stage_tables(k, &pyr));
+    a->stage_tw = pyr ? 1u : 0u;
+    a->big_tw = pyr;
+    if (!pyr) SP_TRY(roots(k, &a->big_tw));
     return SP_OK;
 }
 int NttEngine::inv_roots_small(int k, const fe** out) {
@@ -511,15 +563,15 @@ static std::vector<PassGeom> geometry(int k, int first_stride_log, int first_con
 
 int NttEngine::dit_bitrev_to_natural(fe* data, int k, uint32_t batch, uint64_t stride) {
     if (k == 0) return SP_OK;
-    const fe* big = nullptr;
-    SP_TRY(roots(k, &big));
+    NttPassArgs tw{};
+    SP_TRY(transform_twiddles(k, &tw));
     std::vector<PassGeom> geo = geometry(k, 0, NTT_MAX_CONTIG_LOG, ((uint64_t)batch << k) * sizeof(fe));
     for (size_t i = 0; i < geo.size(); ++i) {
         const PassGeom& p = geo[i];
         NttPassArgs a{};
         a.src = data; a.dst = data; a.src_vec_stride = a.dst_vec_stride = stride;
         SP_TRY(roots(p.r, &a.small_tw));
-        a.big_tw = big; a.logM = k; a.logL = k; a.s = p.s; a.r = p.r; a.g = p.g;
+        a.big_tw = tw.big_tw; a.stage_tw = tw.stage_tw; a.logM = k; a.logL = k; a.s = p.s; a.r = p.r; a.g = p.g;
         a.weak_out = i + 1 < geo.size();
         SP_TRY(launch_pass(false, NTT_LOAD_INPLACE, NTT_STORE_INPLACE, a, batch));
     }
@@ -527,8 +579,8 @@ int NttEngine::dit_bitrev_to_natural(fe* data, int k, uint32_t batch, uint64_t s
 }
 
 int NttEngine::dif_natural_to_bitrev_inverse(fe* data, int k, uint32_t batch, uint64_t stride, const fe* post_table, const fe* src) {
-    const fe* big = nullptr;
-    SP_TRY(roots(k, &big));
+    NttPassArgs tw{};
+    SP_TRY(transform_twiddles(k, &tw));
     // beyond one tile the contiguous pass is kept short (2^7 rows x 8 contiguous runs): a 2^10-row pass stages a 16 KB
     // twiddle table per 32 KB tile and fits only three work-groups per CU (measured 55 % of the strided passes' rate)
     constexpr int contig_cap = 7;
@@ -540,7 +592,7 @@ int NttEngine::dif_natural_to_bitrev_inverse(fe* data, int k, uint32_t batch, ui
         a.src = (src && i + 1 == geo.size()) ? src : data;  // the first pass executed may read another array (same stride)
         a.dst = data; a.src_vec_stride = a.dst_vec_stride = stride;
         SP_TRY(inv_roots_small(p.r, &a.small_tw));
-        a.big_tw = big; a.logM = k; a.logL = k; a.s = p.s; a.r = p.r; a.g = p.g;
+        a.big_tw = tw.big_tw; a.stage_tw = tw.stage_tw; a.logM = k; a.logL = k; a.s = p.s; a.r = p.r; a.g = p.g;
         a.weak_out = i != 0;
         if (i == 0) a.post_table = post_table;
         SP_TRY(launch_pass(true, NTT_LOAD_INPLACE, NTT_STORE_INPLACE, a, batch));
@@ -549,8 +601,8 @@ int NttEngine::dif_natural_to_bitrev_inverse(fe* data, int k, uint32_t batch, ui
 }
 
 int NttEngine::forward_natural(const fe* src, fe* dst, int k, uint32_t batch, uint64_t ss, uint64_t ds, fe* final_dst) {
-    const fe* big = nullptr;
-    SP_TRY(roots(k, &big));
+    NttPassArgs tw{};
+    SP_TRY(transform_twiddles(k, &tw));
     std::vector<PassGeom> geo = geometry(k, 0, k <= NTT_TILE_LOG ? NTT_TILE_LOG : NTT_TILE_LOG - NTT_STRIDED_G_LOG, ((uint64_t)batch << k) * sizeof(fe));
     if (geo.empty()) geo.push_back({0, 0, 0});
     bool first = true;
@@ -566,7 +618,7 @@ int NttEngine::forward_natural(const fe* src, fe* dst, int k, uint32_t batch, ui
         a.src_vec_stride = cur_stride; a.dst_vec_stride = out_stride;
         cur = out; cur_stride = out_stride; ++pi;
         SP_TRY(roots(p.r, &a.small_tw));
-        a.big_tw = big; a.logM = k; a.logL = k; a.s = p.s; a.r = p.r; a.g = p.g;
+        a.big_tw = tw.big_tw; a.stage_tw = tw.stage_tw; a.logM = k; a.logL = k; a.s = p.s; a.r = p.r; a.g = p.g;
         a.weak_out = pi < geo.size();
         SP_TRY(launch_pass(false, first ? NTT_LOAD_GATHER_BITREV : NTT_LOAD_INPLACE, NTT_STORE_INPLACE, a, batch));
         first = false;
@@ -580,8 +632,8 @@ int NttEngine::forward_natural(const fe* src, fe* dst, int k, uint32_t batch, ui
 int NttEngine::inverse_natural(fe* data, fe* tmp, int k, uint32_t batch, uint64_t stride) {
     // Un-passes run last-to-first: the first one goes data -> tmp, the middle ones stay in tmp, and the final
     // bit-reversal scatter goes tmp -> data (a scatter must never run in place: other tiles still read their rows).
-    const fe* big = nullptr;
-    SP_TRY(roots(k, &big));
+    NttPassArgs tw{};
+    SP_TRY(transform_twiddles(k, &tw));
     std::vector<PassGeom> geo = geometry(k, 0, k <= NTT_TILE_LOG ? NTT_TILE_LOG : NTT_TILE_LOG - NTT_STRIDED_G_LOG, ((uint64_t)batch << k) * sizeof(fe));
     if (geo.empty()) geo.push_back({0, 0, 0});
     if (!d_scalar_) SP_HIP_CHECK(hipMalloc(&d_scalar_, sizeof(fe)));
@@ -599,7 +651,7 @@ int NttEngine::inverse_natural(fe* data, fe* tmp, int k, uint32_t batch, uint64_
         a.dst = (i == 0) ? data : tmp;
         a.src_vec_stride = a.dst_vec_stride = stride;
         SP_TRY(inv_roots_small(p.r, &a.small_tw));
-        a.big_tw = big; a.logM = k; a.logL = k; a.s = p.s; a.r = p.r; a.g = p.g;
+        a.big_tw = tw.big_tw; a.stage_tw = tw.stage_tw; a.logM = k; a.logL = k; a.s = p.s; a.r = p.r; a.g = p.g;
         a.weak_out = i != 0;
         int sm = NTT_STORE_INPLACE;
         if (i == 0) { sm = NTT_STORE_SCATTER_BITREV; a.scalar = d_scalar_; }
