@@ -1,0 +1,43 @@
+// Host forms of the C views of include/stark252_hip.h that the prover and the verifier share: proof options, sp_air_desc,
+// sp_air_aux_desc, and the well-formedness rules of their straight-line programs.  Host only (no device headers).
+#pragma once
+#include "cairo_air_host.h"
+#include <vector>
+
+namespace sp {
+
+struct ProofOptionsHost { uint8_t blowup_factor; uint64_t fri_number_of_queries; uint64_t coset_offset; uint8_t grinding_factor; };
+inline ProofOptionsHost proof_options_from_c(const sp_proof_options* o) {
+    return ProofOptionsHost{o->blowup_factor, o->fri_number_of_queries, o->coset_offset, o->grinding_factor};
+}
+
+// Host form of sp_air_desc.
+struct AirOpHost { uint8_t op; uint32_t a, b; };   // as the caller wrote it: operands are indices of earlier ops
+struct AirDescHost {
+    uint32_t main_cols = 0, aux_cols = 0;
+    std::vector<uint32_t> offsets, degrees, exemptions;
+    uint32_t num_transition_exemptions = 1, degree_bound_factor = 1;
+    std::vector<AirOpHost> ops;
+    std::vector<fe> consts;
+    uint32_t n_rap = 0, aux_kind = 0;
+    sp_aux_trace_fn aux_fn = nullptr; void* aux_user = nullptr;   // aux_kind 2: build_auxiliary_trace supplied by the caller
+    std::vector<BoundaryConstraint> boundary;
+};
+// sp_air_desc -> AirDescHost; false for a malformed descriptor (counts out of range, a count without its array).  capi_host.cpp
+bool air_desc_from_c(const sp_air_desc* d, AirDescHost& out);
+
+// Host form of sp_air_aux_desc: the auxiliary program of an AIR with aux_kind SP_AIR_AUX_PROGRAM.
+struct AirAuxColumnHost { uint32_t kind, num_op, den_op; };
+struct AirAuxHost {
+    std::vector<AirOpHost> ops;
+    std::vector<fe> consts;
+    std::vector<AirAuxColumnHost> cols;
+};
+
+// The rules of a straight-line program (op 0 LOAD, 1 CONST, 2 ADD, 3 SUB, 4 MUL, 5 OUT): a LOAD has a < load_a_end and
+// b < load_b_end, a CONST names one of n_values constants or RAP challenges, ADD / SUB / MUL take two earlier ops that are not
+// OUTs, an OUT one of n_out targets and such an op (n_out 0: no OUT at all).  Returns the index of the first op that breaks
+// them, ops.size() when none does.  verifier.cpp
+size_t air_program_first_bad_op(const std::vector<AirOpHost>& ops, uint32_t load_a_end, uint32_t load_b_end, size_t n_values, uint32_t n_out);
+
+}  // namespace sp

@@ -1,10 +1,9 @@
 // C ABI: host-only entry points (Cairo front-end, encoding helpers). See include/stark252_hip.h.
 #include "../../include/stark252_hip.h"
 #include "cairo_host.h"
-#include "cairo_air_host.h"
+#include "air_desc.h"
 #include "poseidon.h"
 #include "stark_kernels.h"
-#include <array>
 #include "common.h"
 #include <cstring>
 #include <cstdlib>
@@ -56,12 +55,7 @@ bool cairo_run_device_inputs(const sp_cairo_run* run, const TracePlan** plan, Tr
 }
 static thread_local std::string g_last_error;
 void sp_set_error(const std::string& s) { g_last_error = s; }
-namespace sp {
-int air_verify_host(const uint8_t* proof_bytes, size_t len, uint32_t main_cols, uint32_t aux_cols, const std::vector<uint32_t>& offsets,
-                    const std::vector<uint32_t>& degrees, const std::vector<uint32_t>& exemptions, uint32_t bound_factor,
-                    const std::vector<std::array<uint16_t, 3>>& ops, const std::vector<fe>& consts, uint32_t n_rap,
-                    const std::vector<BoundaryConstraint>& boundary, uint8_t blowup, uint64_t queries, uint64_t coset_offset, uint8_t grinding);
-}
+namespace sp { int air_verify_host(const uint8_t* proof_bytes, size_t len, const AirDescHost& air, const ProofOptionsHost& opt); }
 namespace sp { void set_verify_merkle_backend(int backend); int host_bind_calling_thread_to_device_node(int device, int* node_out); }
 namespace sp { int cairo_verify_host(const uint8_t* proof_bytes, size_t len, const PublicInputs& pub, uint8_t blowup, uint64_t queries, uint64_t coset_offset, uint8_t grinding); }
 
@@ -82,6 +76,23 @@ PublicInputs public_inputs_from_c(const sp_cairo_public_inputs* p) {
     }
     r.num_steps = p->num_steps;
     return r;
+}
+
+bool air_desc_from_c(const sp_air_desc* d, AirDescHost& a) {
+    if (d->n_offsets == 0 || d->n_offsets > 8 || d->n_transitions == 0 || d->n_transitions > 64 || (d->n_ops && !d->ops) ||
+        (d->n_consts && !d->consts) || (d->n_boundary && !d->boundary)) return false;
+    a.main_cols = d->main_cols; a.aux_cols = d->aux_cols;
+    a.offsets.assign(d->offsets, d->offsets + d->n_offsets);
+    a.degrees.assign(d->degrees, d->degrees + d->n_transitions);
+    a.exemptions.assign(d->exemptions, d->exemptions + d->n_transitions);
+    a.num_transition_exemptions = d->num_transition_exemptions;
+    a.degree_bound_factor = d->degree_bound_factor;
+    for (uint32_t i = 0; i < d->n_ops; ++i) a.ops.push_back(AirOpHost{d->ops[i].op, d->ops[i].a, d->ops[i].b});
+    for (uint32_t i = 0; i < d->n_consts; ++i) a.consts.push_back(fe_from_bytes_be(d->consts + 32 * (size_t)i));
+    a.n_rap = d->n_rap; a.aux_kind = d->aux_kind; a.aux_fn = d->aux_fn; a.aux_user = d->aux_user;
+    for (uint32_t i = 0; i < d->n_boundary; ++i)
+        a.boundary.push_back(BoundaryConstraint{d->boundary[i].col, d->boundary[i].step, fe_from_bytes_be(d->boundary[i].value)});
+    return true;
 }
 }  // namespace sp
 
@@ -420,18 +431,9 @@ int sp_cairo_verify_backend(const uint8_t* proof, uint64_t proof_len, const sp_c
 int sp_air_verify(const uint8_t* proof, uint64_t proof_len, const sp_air_desc* d, const sp_proof_options* opt) {
     if (!proof || !d || !opt) return SP_E_INVALID_ARG;
     try {
-        if (d->n_offsets == 0 || d->n_offsets > 8 || d->n_transitions == 0 || d->n_transitions > 64 || (d->n_ops && !d->ops) ||
-            (d->n_consts && !d->consts) || (d->n_boundary && !d->boundary)) { sp_set_error("malformed: AIR descriptor"); return 0; }
-        std::vector<uint32_t> offsets(d->offsets, d->offsets + d->n_offsets), degrees(d->degrees, d->degrees + d->n_transitions),
-            exemptions(d->exemptions, d->exemptions + d->n_transitions);
-        std::vector<std::array<uint16_t, 3>> ops;
-        for (uint32_t i = 0; i < d->n_ops; ++i) ops.push_back({d->ops[i].op, d->ops[i].a, d->ops[i].b});
-        std::vector<fe> consts;
-        for (uint32_t i = 0; i < d->n_consts; ++i) consts.push_back(fe_from_bytes_be(d->consts + 32 * (size_t)i));
-        std::vector<sp::BoundaryConstraint> bcs;
-        for (uint32_t i = 0; i < d->n_boundary; ++i) bcs.push_back(sp::BoundaryConstraint{d->boundary[i].col, d->boundary[i].step, fe_from_bytes_be(d->boundary[i].value)});
-        const int ok = sp::air_verify_host(proof, proof_len, d->main_cols, d->aux_cols, offsets, degrees, exemptions, d->degree_bound_factor, ops, consts,
-                                           d->n_rap, bcs, opt->blowup_factor, opt->fri_number_of_queries, opt->coset_offset, opt->grinding_factor);
+        sp::AirDescHost air;
+        if (!sp::air_desc_from_c(d, air)) { sp_set_error("malformed: AIR descriptor"); return 0; }
+        const int ok = sp::air_verify_host(proof, proof_len, air, sp::proof_options_from_c(opt));
         sp_set_error(ok == 1 ? "" : "rejected: a verification step failed");
         return ok;
     } catch (const std::exception& e) { sp_set_error(e.what()); return 0; }

@@ -13,11 +13,18 @@ bool cairo_run_device_inputs(const sp_cairo_run* run, const TracePlan** plan, Tr
 using namespace sp;
 
 namespace {
-ProverHolder* holder(sp_ctx* c, bool create) { return prover_holder(c, create); }
 int dec(sp_ctx* c, const uint8_t* in, uint64_t n, fe* out) { return sp_fe_to_device(c->enc, in, n, reinterpret_cast<uint8_t*>(out)); }
 int enc(sp_ctx* c, const fe* in, uint64_t n, uint8_t* out) { return sp_fe_from_device(c->enc, reinterpret_cast<const uint8_t*>(in), n, out); }
 
-PublicInputs to_host_pub(const sp_cairo_public_inputs* p) { return public_inputs_from_c(p); }
+// The tail of the whole-proof entry points: the round times on the context, the proof in a malloc'd buffer (sp_free).
+int publish_proof(sp_ctx* c, const float ms[5], const std::vector<uint8_t>& bytes, uint8_t** proof_out, uint64_t* proof_len) {
+    std::memcpy(c->round_ms, ms, sizeof(float) * 5);
+    uint8_t* out = (uint8_t*)std::malloc(bytes.size());
+    if (!out) return SP_E_ALLOC;
+    std::memcpy(out, bytes.data(), bytes.size());
+    *proof_out = out; *proof_len = bytes.size();
+    return SP_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -25,8 +32,8 @@ extern "C" {
 int sp_prove_setup(sp_ctx* c, uint64_t n, uint32_t main_cols, uint32_t aux_cols, int has_rc, const sp_proof_options* opt) {
     if (!c || !opt) return SP_E_INVALID_ARG;
     if ((uint64_t)main_cols + aux_cols > 64) { sp_set_error("sp_prove_setup: the round-level entry points take up to 64 columns (sp_air_prove: up to 1024)"); return SP_E_INVALID_ARG; }
-    ProverHolder* h = holder(c, true);
-    ProofOptionsHost o{opt->blowup_factor, opt->fri_number_of_queries, opt->coset_offset, opt->grinding_factor};
+    ProverHolder* h = prover_holder(c, true);
+    const ProofOptionsHost o = proof_options_from_c(opt);
     return h->prover.setup(n, main_cols, aux_cols, has_rc != 0, o);
 }
 
@@ -93,8 +100,8 @@ int sp_prewarm(sp_ctx* c, uint64_t n, uint32_t main_cols, uint32_t aux_cols, int
     if (!c || !opt) return SP_E_INVALID_ARG;
     if ((uint64_t)main_cols + aux_cols > 64) { sp_set_error("sp_prewarm: up to 64 columns"); return SP_E_INVALID_ARG; }
     if (flags == 0) flags = SP_PREWARM_ALL;
-    ProverHolder* h = holder(c, true);
-    ProofOptionsHost o{opt->blowup_factor, opt->fri_number_of_queries, opt->coset_offset, opt->grinding_factor};
+    ProverHolder* h = prover_holder(c, true);
+    const ProofOptionsHost o = proof_options_from_c(opt);
     // the shape first: ONE arena allocation of the real size (the small proofs below are carved out of it, nothing is re-allocated)
     sp_ctx* ctx = c;
     double _tp = wall_ms();
@@ -128,7 +135,7 @@ int sp_prewarm_cancel(sp_ctx* c) {
 
 int sp_commit_trace(sp_ctx* c, int segment, const uint8_t* rows, uint64_t n, uint32_t cols, uint8_t root_out[32]) {
     if (!c) return SP_E_INVALID_ARG;
-    ProverHolder* h = holder(c, false);
+    ProverHolder* h = prover_holder(c, false);
     if (!h) { sp_set_error("sp_prove_setup not called"); return SP_E_STATE; }
     if (n != h->prover.n()) return SP_E_INVALID_ARG;
     return h->prover.commit_trace(segment, rows, cols, root_out);
@@ -137,7 +144,7 @@ int sp_commit_trace(sp_ctx* c, int segment, const uint8_t* rows, uint64_t n, uin
 int sp_commit_trace_columns(sp_ctx* c, int segment, const uint8_t* cols, uint64_t n, uint32_t n_cols, uint64_t col_stride, int device_layout,
                             uint8_t root_out[32]) {
     if (!c) return SP_E_INVALID_ARG;
-    ProverHolder* h = holder(c, false);
+    ProverHolder* h = prover_holder(c, false);
     if (!h) { sp_set_error("sp_prove_setup not called"); return SP_E_STATE; }
     if (n != h->prover.n()) return SP_E_INVALID_ARG;
     return h->prover.commit_trace(segment, cols, n_cols, root_out, StarkProver::TRACE_HOST_COLUMNS, device_layout ? -1 : c->enc, col_stride);
@@ -145,19 +152,19 @@ int sp_commit_trace_columns(sp_ctx* c, int segment, const uint8_t* cols, uint64_
 
 int sp_cairo_commit_aux(sp_ctx* c, const uint8_t* rap, const sp_cairo_public_inputs* pub, uint8_t root_out[32]) {
     if (!c || !rap || !pub || !root_out) return SP_E_INVALID_ARG;
-    ProverHolder* h = holder(c, false);
+    ProverHolder* h = prover_holder(c, false);
     if (!h) { sp_set_error("sp_prove_setup not called"); return SP_E_STATE; }
     try {
         fe r[3];
         SP_TRY(dec(c, rap, 3, r));
-        PublicInputs p = to_host_pub(pub);
+        PublicInputs p = public_inputs_from_c(pub);
         return h->prover.commit_aux_cairo(p, r, root_out);
     } catch (const std::exception& e) { sp_set_error(e.what()); return SP_E_INVALID_ARG; }
 }
 
 int sp_composition(sp_ctx* c, const uint8_t* rap, const sp_boundary_constraint* bc, uint32_t nb, const uint8_t* coeffs, uint32_t T, uint8_t root_out[32]) {
     if (!c || !rap || (!bc && nb) || !coeffs || !root_out) return SP_E_INVALID_ARG;
-    ProverHolder* h = holder(c, false);
+    ProverHolder* h = prover_holder(c, false);
     if (!h) { sp_set_error("sp_prove_setup not called"); return SP_E_STATE; }
     try {
         fe r[3];
@@ -178,7 +185,7 @@ int sp_composition(sp_ctx* c, const uint8_t* rap, const sp_boundary_constraint* 
 
 int sp_ood(sp_ctx* c, const uint8_t z[32], uint8_t* out) {
     if (!c || !z || !out) return SP_E_INVALID_ARG;
-    ProverHolder* h = holder(c, false);
+    ProverHolder* h = prover_holder(c, false);
     if (!h) { sp_set_error("sp_prove_setup not called"); return SP_E_STATE; }
     fe zz, h1, h2;
     SP_TRY(dec(c, z, 1, &zz));
@@ -191,7 +198,7 @@ int sp_ood(sp_ctx* c, const uint8_t z[32], uint8_t* out) {
 
 int sp_deep_fri_commit_begin(sp_ctx* c, const uint8_t* gammas, uint8_t root0_out[32]) {
     if (!c || !gammas || !root0_out) return SP_E_INVALID_ARG;
-    ProverHolder* h = holder(c, false);
+    ProverHolder* h = prover_holder(c, false);
     if (!h) { sp_set_error("sp_prove_setup not called"); return SP_E_STATE; }
     std::vector<fe> g(2 + 2 * (size_t)h->prover.cols());
     SP_TRY(dec(c, gammas, g.size(), g.data()));
@@ -201,7 +208,7 @@ int sp_deep_fri_commit_begin(sp_ctx* c, const uint8_t* gammas, uint8_t root0_out
 
 int sp_fri_fold_commit(sp_ctx* c, const uint8_t zeta[32], uint8_t out[32], int* is_last) {
     if (!c || !zeta || !out || !is_last) return SP_E_INVALID_ARG;
-    ProverHolder* h = holder(c, false);
+    ProverHolder* h = prover_holder(c, false);
     if (!h) { sp_set_error("sp_prove_setup not called"); return SP_E_STATE; }
     fe zt, last;
     SP_TRY(dec(c, zeta, 1, &zt));
@@ -212,14 +219,14 @@ int sp_fri_fold_commit(sp_ctx* c, const uint8_t zeta[32], uint8_t out[32], int* 
 
 int sp_grind(sp_ctx* c, const uint8_t challenge[32], uint8_t factor, uint64_t* nonce_out) {
     if (!c || !challenge || !nonce_out) return SP_E_INVALID_ARG;
-    ProverHolder* h = holder(c, false);   // never replaces a prover another entry point owns
+    ProverHolder* h = prover_holder(c, false);   // never replaces a prover another entry point owns
     if (!h || !h->prover.ready()) { sp_set_error("sp_prove_setup not called"); return SP_E_STATE; }
     return h->prover.grind(challenge, factor, nonce_out);
 }
 
 int sp_open(sp_ctx* c, const uint64_t* iotas, uint32_t q, sp_openings* out) {
     if (!c || !iotas || !out) return SP_E_INVALID_ARG;
-    ProverHolder* h = holder(c, false);
+    ProverHolder* h = prover_holder(c, false);
     if (!h) { sp_set_error("sp_prove_setup not called"); return SP_E_STATE; }
     std::vector<uint64_t> io(iotas, iotas + q);
     SP_TRY(h->prover.open(io, h->open));
@@ -245,20 +252,20 @@ static int cairo_prove_impl(sp_ctx* c, const uint8_t* main_trace, uint64_t n, ui
 int sp_cairo_prove(sp_ctx* c, const uint8_t* main_trace, uint64_t n, uint32_t cols, const sp_cairo_public_inputs* pub,
                    const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len) {
     if (!pub) return SP_E_INVALID_ARG;
-    try { return cairo_prove_impl(c, main_trace, n, cols, to_host_pub(pub), opt, proof_out, proof_len, StarkProver::TRACE_HOST_ROWS); }
+    try { return cairo_prove_impl(c, main_trace, n, cols, public_inputs_from_c(pub), opt, proof_out, proof_len, StarkProver::TRACE_HOST_ROWS); }
     catch (const std::exception& e) { sp_set_error(e.what()); return SP_E_INVALID_ARG; }
 }
 int sp_cairo_prove_dev(sp_ctx* c, const void* main_trace_dev, uint64_t n, uint32_t cols, const sp_cairo_public_inputs* pub,
                        const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len) {
     if (!pub) return SP_E_INVALID_ARG;
-    try { return cairo_prove_impl(c, static_cast<const uint8_t*>(main_trace_dev), n, cols, to_host_pub(pub), opt, proof_out, proof_len, StarkProver::TRACE_DEVICE_ROWS); }
+    try { return cairo_prove_impl(c, static_cast<const uint8_t*>(main_trace_dev), n, cols, public_inputs_from_c(pub), opt, proof_out, proof_len, StarkProver::TRACE_DEVICE_ROWS); }
     catch (const std::exception& e) { sp_set_error(e.what()); return SP_E_INVALID_ARG; }
 }
 int sp_cairo_prove_columns(sp_ctx* c, const uint8_t* main_trace_cols, uint64_t n, uint32_t cols, uint64_t col_stride, int device_layout,
                            const sp_cairo_public_inputs* pub, const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len) {
     if (!pub || !c) return SP_E_INVALID_ARG;
     try {
-        return cairo_prove_impl(c, main_trace_cols, n, cols, to_host_pub(pub), opt, proof_out, proof_len, StarkProver::TRACE_HOST_COLUMNS,
+        return cairo_prove_impl(c, main_trace_cols, n, cols, public_inputs_from_c(pub), opt, proof_out, proof_len, StarkProver::TRACE_HOST_COLUMNS,
                                 device_layout ? -1 : c->enc, col_stride);
     } catch (const std::exception& e) { sp_set_error(e.what()); return SP_E_INVALID_ARG; }
 }
@@ -334,17 +341,10 @@ static int cairo_prove_impl(sp_ctx* c, const uint8_t* main_trace, uint64_t n, ui
     if (!c || !main_trace || !opt || !proof_out || !proof_len) return SP_E_INVALID_ARG;
     c->prewarm_cancel.store(0, std::memory_order_release);   // (a sp_prewarm_cancel that found no prewarm to stop ends here, not in some later prewarm)
     try {
-        ProofOptionsHost o{opt->blowup_factor, opt->fri_number_of_queries, opt->coset_offset, opt->grinding_factor};
         std::vector<uint8_t> bytes;
         float ms[5] = {0, 0, 0, 0, 0};
-        int rc = cairo_prove(c, main_trace, n, cols, p, o, bytes, ms, src, col_enc, col_stride);
-        if (rc != SP_OK) return rc;
-        std::memcpy(c->round_ms, ms, sizeof(ms));
-        *proof_out = (uint8_t*)std::malloc(bytes.size());
-        if (!*proof_out) return SP_E_ALLOC;
-        std::memcpy(*proof_out, bytes.data(), bytes.size());
-        *proof_len = bytes.size();
-        return SP_OK;
+        SP_TRY(cairo_prove(c, main_trace, n, cols, p, proof_options_from_c(opt), bytes, ms, src, col_enc, col_stride));
+        return publish_proof(c, ms, bytes, proof_out, proof_len);
     } catch (const std::exception& e) { sp_set_error(e.what()); return SP_E_INVALID_ARG; }
 }
 
@@ -371,31 +371,12 @@ int sp_last_round_ms(sp_ctx* c, float out[5]) {
 static int air_prove_common(sp_ctx* c, const sp_air_desc* d, const sp::AirAuxHost* aux, const uint8_t* main_trace, uint64_t n,
                             const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len) {
     c->prewarm_cancel.store(0, std::memory_order_release);
-    if (d->n_offsets == 0 || d->n_offsets > 8 || d->n_transitions == 0 || d->n_transitions > 64 || (d->n_ops && !d->ops) ||
-        (d->n_consts && !d->consts) || (d->n_boundary && !d->boundary)) { sp_set_error("sp_air_prove: malformed descriptor"); return SP_E_INVALID_ARG; }
     sp::AirDescHost a;
-    a.main_cols = d->main_cols; a.aux_cols = d->aux_cols;
-    a.offsets.assign(d->offsets, d->offsets + d->n_offsets);
-    a.degrees.assign(d->degrees, d->degrees + d->n_transitions);
-    a.exemptions.assign(d->exemptions, d->exemptions + d->n_transitions);
-    a.num_transition_exemptions = d->num_transition_exemptions;
-    a.degree_bound_factor = d->degree_bound_factor;
-    for (uint32_t i = 0; i < d->n_ops; ++i) a.ops.push_back(sp::AirOpHost{d->ops[i].op, d->ops[i].a, d->ops[i].b});
-    for (uint32_t i = 0; i < d->n_consts; ++i) a.consts.push_back(fe_from_bytes_be(d->consts + 32 * (size_t)i));
-    a.n_rap = d->n_rap; a.aux_kind = d->aux_kind; a.aux_fn = d->aux_fn; a.aux_user = d->aux_user;
-    for (uint32_t i = 0; i < d->n_boundary; ++i)
-        a.boundary.push_back(sp::BoundaryConstraint{d->boundary[i].col, d->boundary[i].step, fe_from_bytes_be(d->boundary[i].value)});
-    sp::ProofOptionsHost o{opt->blowup_factor, opt->fri_number_of_queries, opt->coset_offset, opt->grinding_factor};
+    if (!air_desc_from_c(d, a)) { sp_set_error("sp_air_prove: malformed descriptor"); return SP_E_INVALID_ARG; }
     std::vector<uint8_t> proof;
     float ms[5] = {0, 0, 0, 0, 0};
-    int rc = sp::air_prove(c, a, main_trace, n, o, proof, ms, aux);
-    if (rc != SP_OK) return rc;
-    std::memcpy(c->round_ms, ms, sizeof(ms));
-    uint8_t* out = (uint8_t*)std::malloc(proof.size());
-    if (!out) return SP_E_ALLOC;
-    std::memcpy(out, proof.data(), proof.size());
-    *proof_out = out; *proof_len = proof.size();
-    return SP_OK;
+    SP_TRY(sp::air_prove(c, a, main_trace, n, proof_options_from_c(opt), proof, ms, aux));
+    return publish_proof(c, ms, proof, proof_out, proof_len);
 }
 
 int sp_air_prove(sp_ctx* c, const sp_air_desc* d, const uint8_t* main_trace, uint64_t n, const sp_proof_options* opt,

@@ -883,20 +883,11 @@ int validate_aux_program(const AirAuxHost& aux, uint32_t main_cols, uint32_t n_r
     if (aux.consts.size() > (size_t)AIR_MAX_CONSTS) { sp_set_error("aux program: more than 4096 constants"); return SP_E_INVALID_ARG; }
     if (aux.consts.size() + n_rap > 65535) { sp_set_error("aux program: constants and RAP challenges exceed the 16-bit operand range"); return SP_E_INVALID_ARG; }
     if (aux.cols.empty() || aux.cols.size() > (size_t)AIR_MAX_COLS) { sp_set_error("aux program: 1 .. 1024 auxiliary columns"); return SP_E_INVALID_ARG; }
-    for (size_t t = 0; t < n_ops; ++t) {
-        const AirOpHost& o = aux.ops[t];
-        bool ok;
-        switch (o.op) {
-            case 0: ok = o.a <= AIR_AUX_MAX_SHIFT && o.b < main_cols; break;
-            case 1: ok = o.a < aux.consts.size() + n_rap; break;
-            case 2: case 3: case 4: ok = o.a < t && o.b < t; break;
-            default: ok = false;   // (no OUT: the columns name their ops)
-        }
-        if (!ok) {
-            sp_set_error("aux program: malformed op " + std::to_string(t) + " (LOAD needs a shift of 0 .. 7 and a main column, CONST a constant or a RAP "
-                         "challenge, ADD / SUB / MUL earlier ops; there is no OUT)");
-            return SP_E_INVALID_ARG;
-        }
+    const size_t bad = air_program_first_bad_op(aux.ops, AIR_AUX_MAX_SHIFT + 1, main_cols, aux.consts.size() + n_rap, 0);   // (no OUT: the columns name their ops)
+    if (bad < n_ops) {
+        sp_set_error("aux program: malformed op " + std::to_string(bad) + " (LOAD needs a shift of 0 .. 7 and a main column, CONST a constant or a RAP "
+                     "challenge, ADD / SUB / MUL earlier ops; there is no OUT)");
+        return SP_E_INVALID_ARG;
     }
     for (size_t k = 0; k < aux.cols.size(); ++k) {
         const AirAuxColumnHost& c = aux.cols[k];
@@ -1167,19 +1158,7 @@ int StarkProver::composition_air(const AirDescHost& air, const std::vector<fe>& 
     prog.n_ops = (uint32_t)air.ops.size();
     prog.n_offsets = R;
     for (uint32_t k = 0; k < R; ++k) prog.offsets[k] = air.offsets[k];
-    std::vector<bool> produced(T, false);
-    for (uint32_t t = 0; t < prog.n_ops; ++t) {
-        const AirOpHost& o = air.ops[t];
-        bool ok = true;
-        switch (o.op) {
-            case 0: ok = o.a < R && o.b < C_; break;
-            case 1: ok = o.a < air.consts.size() + rap.size(); break;
-            case 2: case 3: case 4: ok = o.a < t && o.b < t && air.ops[o.a].op != 5 && air.ops[o.b].op != 5; break;
-            case 5: ok = o.a < T && o.b < t && air.ops[o.b].op != 5; if (ok) produced[o.a] = true; break;
-            default: ok = false;
-        }
-        if (!ok) { sp_set_error("composition_air: malformed constraint program"); return SP_E_INVALID_ARG; }
-    }
+    if (air_program_first_bad_op(air.ops, R, C_, air.consts.size() + rap.size(), T) < air.ops.size()) { sp_set_error("composition_air: malformed constraint program"); return SP_E_INVALID_ARG; }
     SP_TRY(air_assign_slots(air.ops, dops, "composition_air: more than 64 values alive at once in the constraint program"));
     prog.n_ops = (uint32_t)dops.size();
     // --- transition exemptions (traits.rs:49-79, evaluator.rs:299-323): distinct non-zero counts; with

@@ -3,7 +3,7 @@
 #pragma once
 #include "ctx.h"
 #include "stark_kernels.h"
-#include "cairo_air_host.h"
+#include "air_desc.h"
 #include "aux_kernels.h"
 #include "air_aux_kernels.h"
 #include "trace_kernels.h"
@@ -15,27 +15,6 @@
 
 namespace sp {
 
-struct ProofOptionsHost { uint8_t blowup_factor; uint64_t fri_number_of_queries; uint64_t coset_offset; uint8_t grinding_factor; };
-
-// Host form of sp_air_desc (include/stark252_hip.h).
-struct AirOpHost { uint8_t op; uint32_t a, b; };   // as the caller wrote it: operands are indices of earlier ops
-struct AirDescHost {
-    uint32_t main_cols = 0, aux_cols = 0;
-    std::vector<uint32_t> offsets, degrees, exemptions;
-    uint32_t num_transition_exemptions = 1, degree_bound_factor = 1;
-    std::vector<AirOpHost> ops;
-    std::vector<fe> consts;
-    uint32_t n_rap = 0, aux_kind = 0;
-    sp_aux_trace_fn aux_fn = nullptr; void* aux_user = nullptr;   // aux_kind 2: build_auxiliary_trace supplied by the caller
-    std::vector<BoundaryConstraint> boundary;
-};
-// Host form of sp_air_aux_desc: the auxiliary program of an AIR with aux_kind SP_AIR_AUX_PROGRAM.
-struct AirAuxColumnHost { uint32_t kind, num_op, den_op; };
-struct AirAuxHost {
-    std::vector<AirOpHost> ops;
-    std::vector<fe> consts;
-    std::vector<AirAuxColumnHost> cols;
-};
 // Checks an auxiliary program against its AIR (operands refer to earlier ops, LOADs to main columns at shifts 0 .. 7, CONSTs to
 // the constants or the n_rap challenges, every column's ops exist).  SP_E_INVALID_ARG with sp_last_error() set otherwise.
 int validate_aux_program(const AirAuxHost& aux, uint32_t main_cols, uint32_t n_rap);
@@ -333,9 +312,9 @@ struct ProverHolder : public sp_deletable {
     Openings open;
     std::vector<uint8_t> trace_evals, comp_evals, fri_evals, fri_evals_sym;
     float round_ms[5] = {0, 0, 0, 0, 0};
-    hipEvent_t air_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // round timing of air_prove (created once, kept)
+    hipEvent_t round_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // round timing of the whole-proof drivers (created once, kept)
     explicit ProverHolder(sp_ctx* c) : prover(c) {}
-    ~ProverHolder() override { for (auto& e : air_ev) if (e) (void)hipEventDestroy(e); }
+    ~ProverHolder() override { for (auto& e : round_ev) if (e) (void)hipEventDestroy(e); }
 };
 ProverHolder* prover_holder(sp_ctx* c, bool create);
 
@@ -346,9 +325,9 @@ int cairo_prove(sp_ctx* ctx, const uint8_t* main_trace, uint64_t n, uint32_t col
                 StarkProver::TraceSource src = StarkProver::TRACE_HOST_ROWS, int col_enc = -1, uint64_t col_stride = 0);
 // Whole proof for an AIR given as a constraint program: `prove::<F, A>` (reference src/starks/prover.rs:532-766) + serialize.
 // main_trace: row-major n x air.main_cols in the context encoding (host memory).
-// round_ms (nullable): device time of rounds 1 - 4 in [1..4], as cairo_prove.
+// round_ms: device time of rounds 1 - 4 in [1..4], as cairo_prove.
 // aux (nullable): the auxiliary program of an AIR with aux_kind SP_AIR_AUX_PROGRAM (sp_air_prove_aux).
 int air_prove(sp_ctx* ctx, const AirDescHost& air, const uint8_t* main_trace, uint64_t n, const ProofOptionsHost& opt,
-              std::vector<uint8_t>& proof_out, float round_ms[5] = nullptr, const AirAuxHost* aux = nullptr);
+              std::vector<uint8_t>& proof_out, float round_ms[5], const AirAuxHost* aux = nullptr);
 
 }  // namespace sp

@@ -1,7 +1,7 @@
-// Whole-proof drivers on top of the round-level prover (see prover.h): the host side of the Fiat-Shamir transcript, the proof
-// writer, generate_cairo_proof (reference src/cairo/air.rs:1165-1171) and prove::<F, A> for program AIRs (src/starks/prover.rs:532-766).
+// Whole-proof drivers on top of the round-level prover (see prover.h): the proof writer, rounds 2 - 4 with the host side of the
+// Fiat-Shamir transcript (transcript.h), generate_cairo_proof (reference src/cairo/air.rs:1165-1171) and prove::<F, A> for program AIRs (src/starks/prover.rs:532-766).
 #include "prover_internal.h"
-#include "keccak.h"
+#include "transcript.h"
 #include <array>
 #include <cstring>
 #include <cstdio>
@@ -12,33 +12,6 @@ namespace sp {
 
 // ============================================================================================ whole proof (host driver)
 namespace {
-
-// DefaultTranscript of lambdaworks-crypto @ a17b951 and the sampling rules of
-// reference src/starks/transcript.rs:13-79.
-struct HostTranscript {
-    std::vector<uint8_t> buf;
-    void append(const uint8_t* d, size_t n) { buf.insert(buf.end(), d, d + n); }
-    void append_felt(const fe& x) { uint8_t b[32]; fe_to_bytes_be(x, b); append(b, 32); }
-    void challenge(uint8_t out[32]) {
-        uint8_t d[32];
-        sp_keccak256_host(buf.data(), buf.size(), d);
-        for (int i = 0; i < 32; ++i) out[i] = d[31 - i];
-        buf.assign(out, out + 32);
-    }
-    fe to_field() {
-        uint8_t r[32];
-        challenge(r);
-        r[0] &= 0x07;  // 251 random bits (transcript.rs:24-43)
-        return fe_from_bytes_be(r);
-    }
-    uint64_t to_usize() {
-        uint8_t r[32];
-        challenge(r);
-        uint64_t v = 0;
-        for (int i = 0; i < 8; ++i) v = (v << 8) | r[i];
-        return v;
-    }
-};
 
 // Writes the proof in one pass into a buffer of its final size (every length of the format is known before the first byte).
 struct ProofWriter {
@@ -53,18 +26,26 @@ struct ProofWriter {
     void path(const digest32* p, uint32_t depth) { u64(depth); raw(p, (size_t)depth * 32); }
 };
 
-bool z_in_domains(const fe& z, const fe& hinv, uint32_t logn, uint32_t logN) {  // transcript.rs:53-69
-    fe a = fe_mul(z, hinv), b = z;
-    for (uint32_t i = 0; i < logN; ++i) a = fe_sqr(a);
-    for (uint32_t i = 0; i < logn; ++i) b = fe_sqr(b);
-    return fe_eq(a, fe_one()) || fe_eq(b, fe_one());
-}
+typedef std::array<uint8_t, 32> Root;
+
+// One whole proof between its entry point and the proof writer: what begin_proof and round 1 leave for rounds 2 - 4.
+struct ProofRun {
+    ProverHolder* H = nullptr;   // the prover kept (with its device buffers) across proofs of the same shape on this context
+    Transcript tr;
+    std::vector<Root> roots;     // of the trace segments, in the order of their commitment
+    double _tp = 0, head_ms = 0; // SP_TIMING's previous point; SP_TAIL_TIMING: wall time from the entry to the first event
+    void trace_committed(const uint8_t root[32]) {
+        roots.emplace_back();
+        std::memcpy(roots.back().data(), root, 32);
+        tr.append(root, 32);
+    }
+};
 
 }  // namespace
 
 // StarkProof serialization (reference proof/stark.rs:161-218, fri/fri_decommit.rs:24-45, frame.rs:86-106).
 // roots: the trace-segment roots (one or two); ood: frame rows x C evaluations.
-static void serialize_proof(uint64_t n, const std::vector<std::array<uint8_t, 32>>& roots, uint32_t C, const std::vector<fe>& ood,
+static void serialize_proof(uint64_t n, const std::vector<Root>& roots, uint32_t C, const std::vector<fe>& ood,
                             const uint8_t comp_root[32], const fe& h1z, const fe& h2z, const std::vector<std::vector<uint8_t>>& fri_roots,
                             const fe& last_value, const std::vector<uint64_t>& iotas, const Openings& o, uint64_t nonce,
                             std::vector<uint8_t>& proof_out) {
@@ -134,130 +115,138 @@ ProverHolder* prover_holder(sp_ctx* c, bool create) {
     return h;
 }
 
+// What every whole proof starts with: the context's prover at this shape, the round timers and the mark in front of round 1.
+static int begin_proof(sp_ctx* ctx, uint64_t n, uint32_t main_cols, uint32_t aux_cols, bool has_rc, const ProofOptionsHost& opt, ProofRun& run) {
+    run.H = prover_holder(ctx, true);
+    if (opt.fri_number_of_queries == 0) { sp_set_error("prove: fri_number_of_queries must be at least 1 (the reference emits a proof without openings for 0; this prover does not)"); return SP_E_INVALID_ARG; }
+    for (auto& e : run.H->round_ev) if (!e) SP_HIP_CHECK(hipEventCreate(&e));
+    double& _tp = run._tp;
+    const double t_entry = _tp = wall_ms();
+    SP_TRY(run.H->prover.setup(n, main_cols, aux_cols, has_rc, opt));
+    SP_TIMEPOINT("setup (alloc + tables)");
+    SP_HIP_CHECK(hipEventRecord(run.H->round_ev[0], ctx->stream));
+    run.head_ms = wall_ms() - t_entry;
+    return SP_OK;
+}
+
+// Rounds 2 - 4 and the proof bytes, from the transcript as round 1 left it (both segment roots appended, round_ev[1] recorded).
+// B, T: numbers of boundary and transition constraints; composition(b_alpha, b_beta, t_alpha, t_beta, root_out) runs round 2 of
+// this AIR with the four sampled coefficient vectors.
+template <class Composition>
+static int finish_proof(sp_ctx* ctx, ProofRun& run, size_t B, size_t T, const ProofOptionsHost& opt, Composition&& composition,
+                        std::vector<uint8_t>& proof_out, float round_ms[5]) {
+    static const bool tail_timing = std::getenv("SP_TAIL_TIMING") != nullptr;
+    StarkProver* P = &run.H->prover;
+    hipEvent_t* ev = run.H->round_ev;
+    Transcript& tr = run.tr;
+    double& _tp = run._tp;
+    uint8_t root[32];
+    // ---- round 2 (reference prover.rs:597-635)
+    std::vector<fe> b_alpha(B), b_beta(B), t_alpha(T), t_beta(T);
+    for (auto& x : b_alpha) x = tr.to_field();
+    for (auto& x : b_beta) x = tr.to_field();
+    for (auto& x : t_alpha) x = tr.to_field();
+    for (auto& x : t_beta) x = tr.to_field();
+    SP_TRY(composition(b_alpha, b_beta, t_alpha, t_beta, root));
+    uint8_t comp_root[32]; std::memcpy(comp_root, root, 32);
+    SP_TIMEPOINT("r2 composition");
+    tr.append(root, 32);
+    SP_HIP_CHECK(hipEventRecord(ev[2], ctx->stream));
+    // ---- round 3 (reference prover.rs:652-684)
+    const uint32_t logn = (uint32_t)sp_log2_exact(P->n()), logN = logn + (uint32_t)sp_log2_exact(opt.blowup_factor);
+    const fe z = sample_z_outside_domains(tr, fe_inv(fe_from_u64(opt.coset_offset)), logn, logN);
+    fe h1z, h2z;
+    std::vector<fe> ood;
+    SP_TRY(P->ood(z, &h1z, &h2z, ood));
+    SP_TIMEPOINT("r3 ood");
+    tr.append_felt(h1z); tr.append_felt(h2z);
+    for (auto& e : ood) tr.append_felt(e);
+    SP_HIP_CHECK(hipEventRecord(ev[3], ctx->stream));
+    // ---- round 4 (reference prover.rs:327-404)
+    fe gamma = tr.to_field(), gamma_p = tr.to_field();
+    std::vector<fe> tg((size_t)P->frame_rows() * P->cols());
+    for (auto& x : tg) x = tr.to_field();
+    SP_TRY(P->deep_fri_begin(gamma, gamma_p, tg, root));
+    std::vector<std::vector<uint8_t>> fri_roots;
+    fri_roots.emplace_back(root, root + 32);
+    tr.append(root, 32);
+    fe last_value;
+    for (;;) {
+        fe zeta = tr.to_field();
+        // From the first layer this rank holds whole (layer 0 on one GPU; behind the sharded layers otherwise) the layers follow
+        // each other on the device without a host round trip; the transcript catches up afterwards.
+        if (P->fri_chain_available()) {
+            std::vector<Root> rest;
+            SP_TRY(P->fri_commit_chain(zeta, tr.buf.data(), rest, &last_value));
+            for (auto& r : rest) {
+                fri_roots.emplace_back(r.begin(), r.end());
+                tr.append(r.data(), 32);
+                (void)tr.to_field();      // zeta_k: the device sampled the same value
+            }
+            break;
+        }
+        int is_last = 0;
+        SP_TRY(P->fri_fold_commit(zeta, root, &last_value, &is_last));
+        if (is_last) break;
+        fri_roots.emplace_back(root, root + 32);
+        tr.append(root, 32);
+    }
+    SP_TIMEPOINT("r4 deep + fri commit");
+    tr.append_felt(last_value);
+    uint8_t gch[32];
+    tr.challenge(gch);
+    uint64_t nonce = 0;
+    SP_TRY(P->grind(gch, opt.grinding_factor, &nonce));
+    tr.append_u64_be(nonce);
+    SP_TIMEPOINT("r4 grinding");
+    std::vector<uint64_t> iotas(opt.fri_number_of_queries);
+    for (auto& x : iotas) x = tr.to_usize() % P->N();
+    Openings& o = run.H->open;         // (kept with the prover: its arrays are reused by the next proof)
+    SP_TRY(P->open(iotas, o, true));   // opened values as wire bytes (encoded on the device)
+    SP_TIMEPOINT("r4 openings");
+    const double t_open = wall_ms();
+    SP_HIP_CHECK(hipEventRecord(ev[4], ctx->stream));
+    SP_HIP_CHECK(hipEventSynchronize(ev[4]));
+    round_ms[0] = 0.f;
+    for (int r = 0; r < 4; ++r) SP_HIP_CHECK(hipEventElapsedTime(&round_ms[r + 1], ev[r], ev[r + 1]));
+    const double t_ser0 = wall_ms();
+    serialize_proof(P->n(), run.roots, P->cols(), ood, comp_root, h1z, h2z, fri_roots, last_value, iotas, o, nonce, proof_out);
+    if (tail_timing) std::fprintf(stderr, "[sp_tail] before the first event %.3f ms, events + bookkeeping after open() %.3f ms, serialize %.3f ms\n", run.head_ms,
+                                  t_ser0 - t_open, wall_ms() - t_ser0);
+    return SP_OK;
+}
+
 int cairo_prove(sp_ctx* ctx, const uint8_t* main_trace, uint64_t n, uint32_t cols, const PublicInputs& pub,
                 const ProofOptionsHost& opt, std::vector<uint8_t>& proof_out, float round_ms[5],
                 StarkProver::TraceSource src, int col_enc, uint64_t col_stride) {
     try {
         CairoAirInfo air = cairo_air_info(pub);
         if (cols != air.main_columns) { sp_set_error("cairo_prove: main trace must have 34 columns (43 with the range-check builtin)"); return SP_E_INVALID_ARG; }
-        StarkProver* P = &prover_holder(ctx, true)->prover;   // kept (with its device buffers) across proofs of the same shape on this context
-        struct Events {   // released on every exit path
-            hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-            ~Events() { for (auto& x : e) if (x) (void)hipEventDestroy(x); }
-        } evs;
-        hipEvent_t* ev = evs.e;
-        for (auto& e : evs.e) SP_HIP_CHECK(hipEventCreate(&e));
-        double _tp = wall_ms();
-        static const bool tail_timing = std::getenv("SP_TAIL_TIMING") != nullptr;
-        const double t_entry = wall_ms();
-        if (opt.fri_number_of_queries == 0) { sp_set_error("prove: fri_number_of_queries must be at least 1 (the reference emits a proof without openings for 0; this prover does not)"); return SP_E_INVALID_ARG; }
-        SP_TRY(P->setup(n, air.main_columns, air.aux_columns, air.has_rc_builtin, opt));
-        SP_TIMEPOINT("setup (alloc + tables)");
-        HostTranscript tr;
+        ProofRun run;
+        SP_TRY(begin_proof(ctx, n, air.main_columns, air.aux_columns, air.has_rc_builtin, opt, run));
+        StarkProver* P = &run.H->prover;
+        double& _tp = run._tp;
         uint8_t root[32];
         // ---- round 1 (reference prover.rs:187-224)
-        SP_HIP_CHECK(hipEventRecord(ev[0], ctx->stream));
-        const double t_ev0 = wall_ms();
         P->request_aux_presort(pub);                    // the sorts of the auxiliary trace: beside round 1 too
         if (pub.num_steps >= 1 && pub.num_steps <= n)   // round 2's boundary denominators need no challenge: beside round 1
             SP_TRY(P->prefetch_boundary_inverses({0, pub.num_steps - 1, n - 1}));
         P->hint_binary_columns(16);                     // the instruction flags (air.rs:29-46): one bit per cell over PCIe from a row-major host table
         SP_TRY(P->commit_trace(0, main_trace, cols, root, src, col_enc, col_stride));
-        uint8_t main_root[32]; std::memcpy(main_root, root, 32);
         SP_TIMEPOINT("r1 commit main (H2D+iNTT+LDE+Merkle)");
-        tr.append(root, 32);
-        fe rap[3] = {tr.to_field(), tr.to_field(), tr.to_field()};
+        run.trace_committed(root);
+        fe rap[3] = {run.tr.to_field(), run.tr.to_field(), run.tr.to_field()};
         SP_TRY(P->commit_aux_cairo(pub, rap, root));
         SP_TIMEPOINT("r1 aux trace + commit (device)");
-        uint8_t aux_root[32]; std::memcpy(aux_root, root, 32);
-        tr.append(root, 32);
-        SP_HIP_CHECK(hipEventRecord(ev[1], ctx->stream));
-        // ---- round 2 (reference prover.rs:597-635)
+        run.trace_committed(root);
+        SP_HIP_CHECK(hipEventRecord(run.H->round_ev[1], ctx->stream));
         std::vector<BoundaryConstraint> bcs = boundary_constraints(pub, rap, n, air.has_rc_builtin);
         const uint32_t T = air.num_transition_constraints;
-        SP_TRY(P->composition_precheck(rap, bcs, T));   // runs while the challenges below are sampled
-        std::vector<fe> b_alpha(bcs.size()), b_beta(bcs.size()), t_alpha(T), t_beta(T);
-        for (auto& x : b_alpha) x = tr.to_field();
-        for (auto& x : b_beta) x = tr.to_field();
-        for (auto& x : t_alpha) x = tr.to_field();
-        for (auto& x : t_beta) x = tr.to_field();
-        SP_TRY(P->composition(rap, bcs, b_alpha, b_beta, t_alpha, t_beta, air.transition_degrees, air.transition_exemptions, root));
-        uint8_t comp_root[32]; std::memcpy(comp_root, root, 32);
-        SP_TIMEPOINT("r2 composition");
-        tr.append(root, 32);
-        SP_HIP_CHECK(hipEventRecord(ev[2], ctx->stream));
-        // ---- round 3 (reference prover.rs:652-684)
-        const uint32_t logn = (uint32_t)sp_log2_exact(n), logN = logn + (uint32_t)sp_log2_exact(opt.blowup_factor);
-        fe hinv = fe_inv(fe_from_u64(opt.coset_offset));
-        fe z;
-        do { z = tr.to_field(); } while (z_in_domains(z, hinv, logn, logN));
-        fe h1z, h2z;
-        std::vector<fe> ood;
-        SP_TRY(P->ood(z, &h1z, &h2z, ood));
-        SP_TIMEPOINT("r3 ood");
-        tr.append_felt(h1z); tr.append_felt(h2z);
-        for (auto& e : ood) tr.append_felt(e);
-        SP_HIP_CHECK(hipEventRecord(ev[3], ctx->stream));
-        // ---- round 4 (reference prover.rs:327-404)
-        fe gamma = tr.to_field(), gamma_p = tr.to_field();
-        std::vector<fe> tg(2 * (size_t)P->cols());
-        for (auto& x : tg) x = tr.to_field();
-        SP_TRY(P->deep_fri_begin(gamma, gamma_p, tg, root));
-        std::vector<std::vector<uint8_t>> fri_roots;
-        fri_roots.emplace_back(root, root + 32);
-        tr.append(root, 32);
-        fe last_value;
-        for (;;) {
-            fe zeta = tr.to_field();
-            // From the first layer this rank holds whole (layer 0 on one GPU; behind the sharded layers otherwise) the layers follow
-            // each other on the device without a host round trip; the transcript catches up afterwards.
-            if (P->fri_chain_available()) {
-                std::vector<std::array<uint8_t, 32>> rest;
-                SP_TRY(P->fri_commit_chain(zeta, tr.buf.data(), rest, &last_value));
-                for (auto& r : rest) {
-                    fri_roots.emplace_back(r.begin(), r.end());
-                    tr.append(r.data(), 32);
-                    (void)tr.to_field();      // zeta_k: the device sampled the same value
-                }
-                break;
-            }
-            int is_last = 0;
-            SP_TRY(P->fri_fold_commit(zeta, root, &last_value, &is_last));
-            if (is_last) break;
-            fri_roots.emplace_back(root, root + 32);
-            tr.append(root, 32);
-        }
-        SP_TIMEPOINT("r4 deep + fri commit");
-        tr.append_felt(last_value);
-        uint8_t gch[32];
-        tr.challenge(gch);
-        uint64_t nonce = 0;
-        SP_TRY(P->grind(gch, opt.grinding_factor, &nonce));
-        {
-            uint8_t nb[8];
-            for (int i = 0; i < 8; ++i) nb[i] = (uint8_t)(nonce >> (56 - 8 * i));
-            tr.append(nb, 8);
-        }
-        SP_TIMEPOINT("r4 grinding");
-        std::vector<uint64_t> iotas(opt.fri_number_of_queries);
-        for (auto& x : iotas) x = tr.to_usize() % P->N();
-        Openings& o = prover_holder(ctx, true)->open;     // (kept with the prover: its arrays are reused by the next proof)
-        SP_TRY(P->open(iotas, o, true));   // opened values as wire bytes (encoded on the device)
-        SP_TIMEPOINT("r4 openings");
-        const double t_open = wall_ms();
-        SP_HIP_CHECK(hipEventRecord(ev[4], ctx->stream));
-        SP_HIP_CHECK(hipEventSynchronize(ev[4]));
-        if (round_ms) {
-            round_ms[0] = 0.f;
-            for (int r = 0; r < 4; ++r) SP_HIP_CHECK(hipEventElapsedTime(&round_ms[r + 1], ev[r], ev[r + 1]));
-        }
-        std::vector<std::array<uint8_t, 32>> roots(2);
-        std::memcpy(roots[0].data(), main_root, 32); std::memcpy(roots[1].data(), aux_root, 32);
-        const double t_ser0 = wall_ms();
-        serialize_proof(n, roots, P->cols(), ood, comp_root, h1z, h2z, fri_roots, last_value, iotas, o, nonce, proof_out);
-        if (tail_timing) std::fprintf(stderr, "[sp_tail] before the first event %.3f ms, events + bookkeeping after open() %.3f ms, serialize %.3f ms\n", t_ev0 - t_entry,
-                                      t_ser0 - t_open, wall_ms() - t_ser0);
-        return SP_OK;
+        SP_TRY(P->composition_precheck(rap, bcs, T));   // runs while finish_proof samples the round 2 challenges
+        auto composition = [&](const std::vector<fe>& b_alpha, const std::vector<fe>& b_beta, const std::vector<fe>& t_alpha, const std::vector<fe>& t_beta, uint8_t* root_out) {
+            return P->composition(rap, bcs, b_alpha, b_beta, t_alpha, t_beta, air.transition_degrees, air.transition_exemptions, root_out);
+        };
+        return finish_proof(ctx, run, bcs.size(), T, opt, composition, proof_out, round_ms);
     } catch (const std::exception& e) {
         sp_set_error(std::string("cairo_prove: ") + e.what());
         return SP_E_INVALID_ARG;
@@ -285,21 +274,14 @@ int air_prove(sp_ctx* ctx, const AirDescHost& air, const uint8_t* main_trace, ui
             }
             SP_TRY(validate_aux_program(*aux, air.main_cols, air.n_rap));
         }
-        StarkProver* P = &prover_holder(ctx, true)->prover;   // kept (with its device buffers) across proofs of the same shape on this context
-        if (opt.fri_number_of_queries == 0) { sp_set_error("prove: fri_number_of_queries must be at least 1 (the reference emits a proof without openings for 0; this prover does not)"); return SP_E_INVALID_ARG; }
-        hipEvent_t* ev = prover_holder(ctx, true)->air_ev;
-        if (round_ms)
-            for (int k = 0; k < 5; ++k) if (!ev[k]) SP_HIP_CHECK(hipEventCreate(&ev[k]));
-        auto mark = [&](int k) -> int { if (round_ms) SP_HIP_CHECK(hipEventRecord(ev[k], ctx->stream)); return SP_OK; };
-        SP_TRY(P->setup(n, air.main_cols, air.aux_cols, false, opt));
-        HostTranscript tr;
+        ProofRun run;
+        SP_TRY(begin_proof(ctx, n, air.main_cols, air.aux_cols, false, opt, run));
+        StarkProver* P = &run.H->prover;
+        Transcript& tr = run.tr;
         uint8_t root[32];
-        std::vector<std::array<uint8_t, 32>> roots;
         // ---- round 1 (reference prover.rs:187-224)
-        SP_TRY(mark(0));
         SP_TRY(P->commit_trace(0, main_trace, air.main_cols, root));
-        roots.emplace_back(); std::memcpy(roots.back().data(), root, 32);
-        tr.append(root, 32);
+        run.trace_committed(root);
         std::vector<fe> rap(air.n_rap);
         for (auto& x : rap) x = tr.to_field();
         if (air.aux_cols && air.aux_kind == 2) {
@@ -309,13 +291,11 @@ int air_prove(sp_ctx* ctx, const AirDescHost& air, const uint8_t* main_trace, ui
             if (!rap.empty()) SP_TRY(sp_fe_from_device(ctx->enc, reinterpret_cast<const uint8_t*>(rap.data()), rap.size(), rap_bytes.data()));
             if (air.aux_fn(air.aux_user, rap_bytes.data(), (uint32_t)rap.size(), aux_rows.data()) != 0) { sp_set_error("air_prove: the auxiliary-trace callback failed"); return SP_E_INVALID_ARG; }
             SP_TRY(P->commit_trace(1, aux_rows.data(), air.aux_cols, root));
-            roots.emplace_back(); std::memcpy(roots.back().data(), root, 32);
-            tr.append(root, 32);
+            run.trace_committed(root);
         } else if (air.aux_cols && air.aux_kind == SP_AIR_AUX_PROGRAM && aux) {
             // the auxiliary program on the device, from the resident main trace (every rank holds all of it: no exchange)
             SP_TRY(P->commit_aux_program(*aux, rap, root));
-            roots.emplace_back(); std::memcpy(roots.back().data(), root, 32);
-            tr.append(root, 32);
+            run.trace_committed(root);
         } else if (air.aux_cols) {
             if (air.aux_kind != 1 || air.aux_cols != 1 || air.main_cols < 2 || air.n_rap < 1) {
                 sp_set_error("air_prove: unknown auxiliary-trace kind (1 = fibonacci_rap permutation column, 2 = caller-supplied)");
@@ -340,83 +320,13 @@ int air_prove(sp_ctx* ctx, const AirDescHost& air, const uint8_t* main_trace, ui
                 else { uint64_t l[4]; fe_to_lw_limbs(zacc, l); std::memcpy(&aux_rows[(size_t)i * 32], l, 32); }
             }
             SP_TRY(P->commit_trace(1, aux_rows.data(), 1, root));
-            roots.emplace_back(); std::memcpy(roots.back().data(), root, 32);
-            tr.append(root, 32);
+            run.trace_committed(root);
         }
-        // ---- round 2 (reference prover.rs:597-635)
-        SP_TRY(mark(1));
-        const size_t B = air.boundary.size(), T = air.degrees.size();
-        std::vector<fe> b_alpha(B), b_beta(B), t_alpha(T), t_beta(T);
-        for (auto& x : b_alpha) x = tr.to_field();
-        for (auto& x : b_beta) x = tr.to_field();
-        for (auto& x : t_alpha) x = tr.to_field();
-        for (auto& x : t_beta) x = tr.to_field();
-        SP_TRY(P->composition_air(air, rap, b_alpha, b_beta, t_alpha, t_beta, root));
-        uint8_t comp_root[32]; std::memcpy(comp_root, root, 32);
-        tr.append(root, 32);
-        SP_TRY(mark(2));
-        // ---- round 3 (reference prover.rs:652-684)
-        const uint32_t logn = (uint32_t)sp_log2_exact(n), logN = logn + (uint32_t)sp_log2_exact(opt.blowup_factor);
-        fe hinv = fe_inv(fe_from_u64(opt.coset_offset));
-        fe z;
-        do { z = tr.to_field(); } while (z_in_domains(z, hinv, logn, logN));
-        fe h1z, h2z;
-        std::vector<fe> ood;
-        SP_TRY(P->ood(z, &h1z, &h2z, ood));
-        tr.append_felt(h1z); tr.append_felt(h2z);
-        for (auto& e : ood) tr.append_felt(e);
-        SP_TRY(mark(3));
-        // ---- round 4 (reference prover.rs:327-404)
-        fe gamma = tr.to_field(), gamma_p = tr.to_field();
-        std::vector<fe> tg((size_t)P->frame_rows() * P->cols());
-        for (auto& x : tg) x = tr.to_field();
-        SP_TRY(P->deep_fri_begin(gamma, gamma_p, tg, root));
-        std::vector<std::vector<uint8_t>> fri_roots;
-        fri_roots.emplace_back(root, root + 32);
-        tr.append(root, 32);
-        fe last_value;
-        for (;;) {
-            fe zeta = tr.to_field();
-            // From the first layer this rank holds whole (layer 0 on one GPU; behind the sharded layers otherwise) the layers follow
-            // each other on the device without a host round trip; the transcript catches up afterwards.
-            if (P->fri_chain_available()) {
-                std::vector<std::array<uint8_t, 32>> rest;
-                SP_TRY(P->fri_commit_chain(zeta, tr.buf.data(), rest, &last_value));
-                for (auto& r : rest) {
-                    fri_roots.emplace_back(r.begin(), r.end());
-                    tr.append(r.data(), 32);
-                    (void)tr.to_field();      // zeta_k: the device sampled the same value
-                }
-                break;
-            }
-            int is_last = 0;
-            SP_TRY(P->fri_fold_commit(zeta, root, &last_value, &is_last));
-            if (is_last) break;
-            fri_roots.emplace_back(root, root + 32);
-            tr.append(root, 32);
-        }
-        tr.append_felt(last_value);
-        uint8_t gch[32];
-        tr.challenge(gch);
-        uint64_t nonce = 0;
-        SP_TRY(P->grind(gch, opt.grinding_factor, &nonce));
-        {
-            uint8_t nb[8];
-            for (int i = 0; i < 8; ++i) nb[i] = (uint8_t)(nonce >> (56 - 8 * i));
-            tr.append(nb, 8);
-        }
-        std::vector<uint64_t> iotas(opt.fri_number_of_queries);
-        for (auto& x : iotas) x = tr.to_usize() % P->N();
-        Openings& o = prover_holder(ctx, true)->open;     // (kept with the prover: its arrays are reused by the next proof)
-        SP_TRY(P->open(iotas, o, true));   // opened values as wire bytes (encoded on the device)
-        SP_TRY(mark(4));
-        SP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        if (round_ms) {
-            round_ms[0] = 0.f;
-            for (int r = 0; r < 4; ++r) SP_HIP_CHECK(hipEventElapsedTime(&round_ms[r + 1], ev[r], ev[r + 1]));
-        }
-        serialize_proof(n, roots, P->cols(), ood, comp_root, h1z, h2z, fri_roots, last_value, iotas, o, nonce, proof_out);
-        return SP_OK;
+        SP_HIP_CHECK(hipEventRecord(run.H->round_ev[1], ctx->stream));
+        auto composition = [&](const std::vector<fe>& b_alpha, const std::vector<fe>& b_beta, const std::vector<fe>& t_alpha, const std::vector<fe>& t_beta, uint8_t* root_out) {
+            return P->composition_air(air, rap, b_alpha, b_beta, t_alpha, t_beta, root_out);
+        };
+        return finish_proof(ctx, run, air.boundary.size(), air.degrees.size(), opt, composition, proof_out, round_ms);
     } catch (const std::exception& e) {
         sp_set_error(std::string("air_prove: ") + e.what());
         return SP_E_INVALID_ARG;

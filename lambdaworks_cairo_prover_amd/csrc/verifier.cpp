@@ -2,9 +2,9 @@
 // (steps 1-4 :59-557) for the Cairo AIR, plus the CLI proof-file framing of reference src/main.rs:98-102.
 // O(queries * log N) hashes — host code, no device work. Unlike the reference (verifier.rs:411-422 discards the fold
 // result) the trace-opening Merkle checks are enforced.
-#include "cairo_air_host.h"
+#include "air_desc.h"
 #include "common.h"
-#include "keccak.h"
+#include "transcript.h"
 #include "poseidon.h"
 #include <algorithm>
 #include <array>
@@ -160,14 +160,6 @@ Proof parse(const uint8_t* data, size_t len) {
     if (r.pos != len) throw std::runtime_error("non-canonical framing: trailing bytes behind the nonce");
     return p;
 }
-struct Tr {
-    std::vector<uint8_t> buf;
-    void append(const uint8_t* d, size_t n) { buf.insert(buf.end(), d, d + n); }
-    void felt(const fe& x) { uint8_t b[32]; fe_to_bytes_be(x, b); append(b, 32); }
-    void challenge(uint8_t out[32]) { uint8_t d[32]; sp_keccak256_host(buf.data(), buf.size(), d); for (int i = 0; i < 32; ++i) out[i] = d[31 - i]; buf.assign(out, out + 32); }
-    fe field() { uint8_t r[32]; challenge(r); r[0] &= 0x07; return fe_from_bytes_be(r); }
-    uint64_t usize() { uint8_t r[32]; challenge(r); uint64_t v = 0; for (int i = 0; i < 8; ++i) v = (v << 8) | r[i]; return v; }
-};
 // the hash of the commitments being checked (sp_*_verify_backend; thread-local: the entry points are context-free)
 thread_local int t_merkle_backend = SP_MERKLE_KECCAK256;
 Dig poseidon_dig(const fe& h) {
@@ -243,34 +235,27 @@ static int verify_host(const uint8_t* proof_bytes, size_t len, const VerifySpec&
     auto root_of = [&](int order) { fe w = fe_from_bytes_be((const uint8_t*)"\x00\x52\x82\xdb\x87\x52\x9c\xfa\x3f\x04\x64\x51\x9c\x8b\x0f\xa5\xad\x18\x71\x48\xe1\x1a\x61\x61\x60\x70\x02\x4f\x42\xf8\xef\x94"); for (int i = order; i < 192; ++i) w = fe_sqr(w); return w; };
     const fe g = root_of(k), w = root_of(k + lb);
     // ---- step 1: replay the transcript (verifier.rs:59-206)
-    Tr t;
+    Transcript t;
     t.append(pr.trace_roots[0].data(), 32);
     std::vector<fe> rap(air.n_rap);
-    for (auto& x : rap) x = t.field();
+    for (auto& x : rap) x = t.to_field();
     if (n_roots > 1) t.append(pr.trace_roots[1].data(), 32);
     std::vector<BoundaryConstraint> bcs = air.boundary(rap);
     std::vector<fe> ba(bcs.size()), bb(bcs.size()), ta(T), tb(T);
-    for (auto& x : ba) x = t.field();
-    for (auto& x : bb) x = t.field();
-    for (auto& x : ta) x = t.field();
-    for (auto& x : tb) x = t.field();
+    for (auto& x : ba) x = t.to_field();
+    for (auto& x : bb) x = t.to_field();
+    for (auto& x : ta) x = t.to_field();
+    for (auto& x : tb) x = t.to_field();
     t.append(pr.comp_root.data(), 32);
-    fe z;
-    for (;;) {
-        z = t.field();
-        fe a = fe_mul(z, hinv), b = z;
-        for (int i = 0; i < k + lb; ++i) a = fe_sqr(a);
-        for (int i = 0; i < k; ++i) b = fe_sqr(b);
-        if (!fe_eq(a, fe_one()) && !fe_eq(b, fe_one())) break;
-    }
-    t.felt(pr.h1z); t.felt(pr.h2z);
-    for (auto& e : pr.ood) t.felt(e);
-    fe gamma = t.field(), gamma_p = t.field();
+    const fe z = sample_z_outside_domains(t, hinv, (uint32_t)k, (uint32_t)(k + lb));
+    t.append_felt(pr.h1z); t.append_felt(pr.h2z);
+    for (auto& e : pr.ood) t.append_felt(e);
+    fe gamma = t.to_field(), gamma_p = t.to_field();
     std::vector<fe> tg((size_t)R * C);
-    for (auto& x : tg) x = t.field();
+    for (auto& x : tg) x = t.to_field();
     std::vector<fe> zetas;
-    for (auto& r : pr.fri_roots) { t.append(r.data(), 32); zetas.push_back(t.field()); }
-    t.felt(pr.fri_last);
+    for (auto& r : pr.fri_roots) { t.append(r.data(), 32); zetas.push_back(t.to_field()); }
+    t.append_felt(pr.fri_last);
     uint8_t gch[32];
     t.challenge(gch);
     {
@@ -281,13 +266,11 @@ static int verify_host(const uint8_t* proof_bytes, size_t len, const VerifySpec&
         uint64_t head = 0;
         for (int i = 0; i < 8; ++i) head = (head << 8) | dg[i];
         int tz = head == 0 ? 64 : __builtin_ctzll(head);
-        uint8_t nb[8];
-        for (int i = 0; i < 8; ++i) nb[i] = (uint8_t)(pr.nonce >> (56 - 8 * i));
-        t.append(nb, 8);
+        t.append_u64_be(pr.nonce);
         if (tz < (int)grinding) return 0;
     }
     std::vector<uint64_t> iotas(queries);
-    for (auto& x : iotas) x = t.usize() % N;
+    for (auto& x : iotas) x = t.to_usize() % N;
     // ---- step 2: composition polynomial at z (verifier.rs:208-317)
     {
         fe zn = fe_pow_u64(z, n);
@@ -406,34 +389,22 @@ int cairo_verify_host(const uint8_t* proof_bytes, size_t len, const PublicInputs
 }
 
 // `verify::<F, A>` for a program AIR (include/stark252_hip.h sp_air_desc); ops as in AirOpDev of stark_kernels.h.
-int air_verify_host(const uint8_t* proof_bytes, size_t len, uint32_t main_cols, uint32_t aux_cols, const std::vector<uint32_t>& offsets,
-                    const std::vector<uint32_t>& degrees, const std::vector<uint32_t>& exemptions, uint32_t bound_factor,
-                    const std::vector<std::array<uint16_t, 3>>& ops /*op, a, b*/, const std::vector<fe>& consts, uint32_t n_rap,
-                    const std::vector<BoundaryConstraint>& boundary, uint8_t blowup, uint64_t queries, uint64_t coset_offset, uint8_t grinding) {
-    const uint32_t C = main_cols + aux_cols, T = (uint32_t)degrees.size(), R = (uint32_t)offsets.size();
-    if (T == 0 || R == 0 || exemptions.size() != T || bound_factor < 1 || C < main_cols) return 0;   // (C < main_cols: the sum wrapped)
-    for (size_t t = 0; t < ops.size(); ++t) {   // same well-formedness rules as the prover
-        const uint16_t op = ops[t][0], a = ops[t][1], b = ops[t][2];
-        bool ok = true;
-        switch (op) {
-            case 0: ok = a < R && b < C; break;
-            case 1: ok = a < consts.size() + n_rap; break;
-            case 2: case 3: case 4: ok = a < t && b < t && ops[a][0] != 5 && ops[b][0] != 5; break;
-            case 5: ok = a < T && b < t && ops[b][0] != 5; break;
-            default: ok = false;
-        }
-        if (!ok) throw std::runtime_error("malformed: constraint program");
-    }
+int air_verify_host(const uint8_t* proof_bytes, size_t len, const AirDescHost& air, const ProofOptionsHost& opt) {
+    const uint32_t C = air.main_cols + air.aux_cols, T = (uint32_t)air.degrees.size(), R = (uint32_t)air.offsets.size();
+    if (T == 0 || R == 0 || air.exemptions.size() != T || air.degree_bound_factor < 1 || C < air.main_cols) return 0;   // (C < main_cols: the sum wrapped)
+    const std::vector<AirOpHost>& ops = air.ops;
+    const std::vector<fe>& consts = air.consts;
+    if (air_program_first_bad_op(ops, R, C, consts.size() + air.n_rap, T) < ops.size()) throw std::runtime_error("malformed: constraint program");
     VerifySpec spec;
-    spec.main_cols = main_cols; spec.aux_cols = aux_cols; spec.offsets = offsets; spec.degrees = degrees; spec.exemptions = exemptions;
-    spec.bound_factor = bound_factor; spec.n_rap = n_rap;
-    spec.boundary = [&boundary](const std::vector<fe>&) { return boundary; };
+    spec.main_cols = air.main_cols; spec.aux_cols = air.aux_cols; spec.offsets = air.offsets; spec.degrees = air.degrees; spec.exemptions = air.exemptions;
+    spec.bound_factor = air.degree_bound_factor; spec.n_rap = air.n_rap;
+    spec.boundary = [&air](const std::vector<fe>&) { return air.boundary; };
     spec.transition = [&ops, &consts, C, T](const fe* frame, const std::vector<fe>& rap, fe* out) {
         std::vector<fe> v(ops.size(), fe_zero());
         for (uint32_t k = 0; k < T; ++k) out[k] = fe_zero();
         for (size_t t = 0; t < ops.size(); ++t) {
-            const uint16_t op = ops[t][0], a = ops[t][1], b = ops[t][2];
-            switch (op) {
+            const uint32_t a = ops[t].a, b = ops[t].b;
+            switch (ops[t].op) {
                 case 0: v[t] = frame[(size_t)a * C + b]; break;
                 case 1: v[t] = a < consts.size() ? consts[a] : rap[a - consts.size()]; break;
                 case 2: v[t] = fe_add(v[a], v[b]); break;
@@ -443,7 +414,24 @@ int air_verify_host(const uint8_t* proof_bytes, size_t len, uint32_t main_cols, 
             }
         }
     };
-    return verify_host(proof_bytes, len, spec, blowup, queries, coset_offset, grinding);
+    return verify_host(proof_bytes, len, spec, opt.blowup_factor, opt.fri_number_of_queries, opt.coset_offset, opt.grinding_factor);
+}
+
+size_t air_program_first_bad_op(const std::vector<AirOpHost>& ops, uint32_t load_a_end, uint32_t load_b_end, size_t n_values, uint32_t n_out) {
+    auto value = [&](uint32_t i, size_t t) { return i < t && ops[i].op != 5; };   // an earlier op that produces a value
+    for (size_t t = 0; t < ops.size(); ++t) {
+        const AirOpHost& o = ops[t];
+        bool ok;
+        switch (o.op) {
+            case 0: ok = o.a < load_a_end && o.b < load_b_end; break;
+            case 1: ok = o.a < n_values; break;
+            case 2: case 3: case 4: ok = value(o.a, t) && value(o.b, t); break;
+            case 5: ok = o.a < n_out && value(o.b, t); break;
+            default: ok = false;
+        }
+        if (!ok) return t;
+    }
+    return ops.size();
 }
 
 }  // namespace sp
