@@ -1,48 +1,12 @@
 // Round-by-round STARK prover on the device (see prover.h). Host code only: it sequences kernels on the context
 // stream, keeps every polynomial / evaluation / tree resident in HBM and moves only roots, challenges and openings.
 #include "prover_internal.h"
-#include "cairo_host.h"
-#include <array>
-#include "keccak.h"
-#include <algorithm>
 #include <unordered_map>
 #include <cstring>
 #include <cmath>
-#include <stdexcept>
 #include <functional>
-#include <memory>
 
 namespace sp {
-
-void host_pool_delete(HostPool* p);
-
-StarkProver::~StarkProver() {
-    free_all();
-    if (arena_) (void)hipFree(arena_);
-    arena_ = nullptr; arena_cap_ = 0;
-    c_->prover_device_bytes = 0;
-    for (auto& e : ev_dma_) if (e) (void)hipEventDestroy(e);
-    for (auto& u : up_ev_) for (hipEvent_t e : {u.dma0, u.dma1, u.ready, u.done}) if (e) (void)hipEventDestroy(e);
-    if (up_start_) (void)hipEventDestroy(up_start_);
-    if (copy_stream_) (void)hipStreamDestroy(copy_stream_);
-    if (pool_) host_pool_delete(pool_);
-    for (auto& p : h_stage_) { if (p) (void)hipHostFree(p); p = nullptr; }
-    if (h_pin_) (void)hipHostFree(h_pin_);
-    if (h_open_pin_) (void)hipHostFree(h_open_pin_);
-    if (h_wide_) (void)hipHostFree(h_wide_);
-    for (hipEvent_t e : {ev_side_fork_, ev_side_deep_, ev_side_bnd_, ev_side_aux_, ev_side_presort_}) if (e) (void)hipEventDestroy(e);
-    if (side_stream_) (void)hipStreamDestroy(side_stream_);
-    if (ev_comm_fork_) (void)hipEventDestroy(ev_comm_fork_);
-    for (auto& e : ev_comm_done_) if (e) (void)hipEventDestroy(e);
-    if (comm_stream_) (void)hipStreamDestroy(comm_stream_);
-}
-
-int StarkProver::ensure_side() {
-    if (!side_stream_) SP_HIP_CHECK(hipStreamCreateWithFlags(&side_stream_, hipStreamNonBlocking));
-    for (hipEvent_t* e : {&ev_side_fork_, &ev_side_deep_, &ev_side_bnd_, &ev_side_aux_, &ev_side_presort_})
-        if (!*e) SP_HIP_CHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
-    return SP_OK;
-}
 
 int StarkProver::wait_stream() {
     SP_HIP_CHECK(sp_stream_wait_polling(c_->stream));
@@ -51,305 +15,13 @@ int StarkProver::wait_stream() {
 
 int StarkProver::readback(void* dst_host, const void* src_dev, size_t bytes) {
     if (bytes > 4096) { sp_set_error("readback: more than the 4 KB pinned slot"); return SP_E_INVALID_ARG; }
-    if (!h_pin_ && hipHostMalloc(&h_pin_, 4096, hipHostMallocDefault) != hipSuccess) { h_pin_ = nullptr; sp_set_error("pinned read-back slot: allocation failed"); return SP_E_ALLOC; }
-    SP_HIP_CHECK(hipMemcpyAsync(h_pin_, src_dev, bytes, hipMemcpyDeviceToHost, c_->stream));
+    SP_TRY(ensure_pin());
+    SP_HIP_CHECK(hipMemcpyAsync(h_pin_.p, src_dev, bytes, hipMemcpyDeviceToHost, c_->stream));
     SP_TRY(wait_stream());
-    memcpy(dst_host, h_pin_, bytes);
+    memcpy(dst_host, h_pin_.p, bytes);
     return SP_OK;
 }
 
-void StarkProver::free_all() {
-    (void)hipSetDevice(c_->device);
-    (void)hipStreamSynchronize(c_->stream);
-    if (copy_stream_) (void)hipStreamSynchronize(copy_stream_);
-    if (side_stream_) (void)hipStreamSynchronize(side_stream_);
-    if (comm_stream_) (void)hipStreamSynchronize(comm_stream_);
-    d_bpre_ = nullptr; bpre_cap_ = 0; bpre_valid_ = false; deep_pref_ = false; d_flag_side_ = nullptr;
-    d_fri_chain_ = nullptr; fri_chain_layers_ = 0; d_comp_consts_chk_ = nullptr; check_pending_ = false; presorted_ = false; presort_pub_ = nullptr;
-    d_flagbits_ = nullptr; flagbits_words_ = 0;     // carved from the arena / allocs_ like the rest: gone with the shape
-    // (the page-locked upload ring does not depend on the shape: it stays until the prover goes)
-    for (void* p : allocs_) (void)hipFree(p);
-    allocs_.clear();
-    alloc_bytes_ = 0;
-    arena_off_ = 0;      // the arena itself stays: the next shape is carved out of it
-    publish_device_bytes();
-}
-
-int StarkProver::alloc(void** p, size_t bytes) {
-    const uint64_t aligned = ((uint64_t)(bytes ? bytes : 1) + 255) & ~(uint64_t)255;
-    if (measuring_) { *p = reinterpret_cast<void*>(uintptr_t(256)); measured_ += aligned; return SP_OK; }   // (sizing pass of setup_impl)
-    if (arena_ && arena_off_ + aligned <= arena_cap_) {
-        *p = arena_ + arena_off_;
-        arena_off_ += aligned;
-        return SP_OK;
-    }
-    *p = nullptr;
-    if (hipMalloc(p, bytes ? bytes : 1) != hipSuccess) {
-        (void)hipGetLastError();
-        sp_set_error("hipMalloc failed (" + std::to_string(bytes) + " bytes)");
-        return SP_E_ALLOC;
-    }
-    allocs_.push_back(*p);
-    alloc_bytes_ += bytes;
-    publish_device_bytes();
-    return SP_OK;
-}
-
-int StarkProver::setup(uint64_t n, uint32_t main_cols, uint32_t aux_cols, bool has_rc, const ProofOptionsHost& opt) {
-    const int rc = setup_impl(n, main_cols, aux_cols, has_rc, opt);
-    if (rc != SP_OK) {   // a failed (re)shaping leaves nothing behind: the next setup() of the same shape starts from scratch
-        free_all();
-        n_ = 0; ready_ = false; stage_ = 0;
-    }
-    return rc;
-}
-
-int StarkProver::setup_impl(uint64_t n, uint32_t main_cols, uint32_t aux_cols, bool has_rc, const ProofOptionsHost& opt) {
-    offsets_ = {0, 1};
-    int k = sp_log2_exact(n), lb = sp_log2_exact(opt.blowup_factor);
-    if (k < 1 || lb < 1 || k + lb > 30 || (1u << lb) > CAIRO_MAX_BLOWUP) { sp_set_error("setup: trace length and blowup factor must be powers of two (blowup 2 .. 128, at most 2^30 LDE points)"); return SP_E_INVALID_ARG; }
-    if (main_cols + aux_cols > (uint32_t)AIR_MAX_COLS) { sp_set_error("setup: more than 1024 trace columns (main + aux)"); return SP_E_INVALID_ARG; }
-    SP_HIP_CHECK(hipSetDevice(c_->device));
-    if (c_->world < 1 || (c_->world & (c_->world - 1)) || c_->rank < 0 || c_->rank >= c_->world) {
-        sp_set_error("setup: world size must be a power of two");
-        return SP_E_INVALID_ARG;
-    }
-    if (c_->world > 1 && !c_->allgather) { sp_set_error("setup: world > 1 needs sp_set_collective / sp_comm_init_rccl"); return SP_E_STATE; }
-    if (ready_ && (arena_ || !allocs_.empty()) && n == n_ && main_cols == Cm_ && aux_cols == Ca_ && has_rc == has_rc_ && opt.blowup_factor == opt_.blowup_factor &&
-        opt.coset_offset == opt_.coset_offset && (uint32_t)c_->world == world_ && (uint32_t)c_->rank == wrank_ && c_->opt_shard_interpolation == shard_mode_) {
-        // same shape as the previous proof on this context: keep every device buffer and table
-        opt_ = opt; stage_ = 1; fri_layer_ = 0;
-        bpre_valid_ = false; deep_pref_ = false; check_pending_ = false; presorted_ = false; presort_pub_ = nullptr;
-        return SP_OK;
-    }
-    free_all();
-    ready_ = false; stage_ = 0;
-    d_auxws_ = nullptr; auxws_bytes_ = 0; auxws_pm_cap_ = 0; d_hfull_ = nullptr; d_hnat_ = nullptr; h_full_ = false;
-    d_air_buf_ = nullptr; air_buf_cap_ = 0; d_ex_roots_ = nullptr; ex_roots_cap_ = 0;
-    d_auxp_buf_ = nullptr; auxp_buf_cap_ = 0; d_auxp_ws_ = nullptr; auxp_ws_cap_ = 0;
-    d_flags_all_ = nullptr;
-    d_gather_ = nullptr; gather_cap_ = 0; d_fullN_ = nullptr; d_small_ = nullptr; d_deepx_ = nullptr; deepx_cap_ = 0; d_cstage_ = nullptr; d_local_ = nullptr; d_recv_ = nullptr; d_roots_ = nullptr;
-    opt_ = opt; n_ = n; logn_ = (uint32_t)k; logb_ = (uint32_t)lb; logN_ = logn_ + logb_; N_ = n << lb;
-    Cm_ = main_cols; Ca_ = aux_cols; C_ = main_cols + aux_cols; has_rc_ = has_rc;
-    world_ = (uint32_t)c_->world; wrank_ = (uint32_t)c_->rank; shard_mode_ = c_->opt_shard_interpolation;
-    // one or more LDE cosets per group; with more ranks than cosets the surplus ranks replicate a role (moving half a coset's
-    // LDE over one xGMI link costs more than computing it)
-    G_ = std::min<uint32_t>(world_, 1u << lb); logG_ = (uint32_t)sp_log2_exact(G_); rank_ = wrank_ & (G_ - 1);
-    Nl_ = N_ >> logG_;
-    // Interpolation by column with an all-gather of the coefficients, or on every rank?  A rank saves
-    // (1 - 1/G) of the size-n inverse transforms (n log n / 2 butterflies per column at ~1.35e11 / s) and receives (1 - 1/G) of the
-    // coefficients (32 n bytes per column over G - 1 links): sharding pays when  64 x 1.35e11 < (G - 1) x link bytes/s x log2 n.
-    // (sp_model_shard_interpolation.)  On 46 GB/s per link that needs (G - 1) log2 n > 188 - no shape this prover sees - so mode 2
-    // interpolates everywhere unless the fabric is faster: the rate sp_comm_measure found (sp_comm_init_rccl runs it once per
-    // communicator) or the one the caller states (SP_OPT_LINK_GBS wins); an exchange that overlaps the transforms completely
-    // (stream-ordered transport) is worth at most the inverse transforms it replaces, 3 - 5 ms at 2^20 rows.
-    shard_interp_ = false;
-    if (G_ > 1) {
-        if (c_->opt_shard_interpolation == 1) shard_interp_ = true;
-        else if (c_->opt_shard_interpolation == 2) shard_interp_ = sp_model_shard_interpolation(c_->link_gbs_for_model(), G_, (uint32_t)k) == 1;
-        // SP_COMM_LOG: the mode and the rate it was chosen from, once per set-up shape and rank (what a first multi-GPU run is read by)
-        static const bool comm_log = std::getenv("SP_COMM_LOG") != nullptr;
-        if (comm_log)
-            std::fprintf(stderr, "[stark252 rank %u/%u] 2^%d rows, %u groups: interpolation %s (SP_OPT_SHARD_INTERPOLATION = %d; link %.1f GB/s per direction - %s; by column pays above %.1f)\n",
-                         wrank_, world_, k, G_, shard_interp_ ? "by column + coefficient all-gather" : "on every rank", c_->opt_shard_interpolation, c_->link_gbs_for_model(),
-                         c_->opt_link_gbs_explicit ? "stated" : (c_->measured_link[1] > 0 ? "measured all-gather rate / 1.25" : "assumed"),
-                         64.0 * 1.35e11 / ((double)(G_ - 1) * (double)k) / 1e9);
-    }
-    if (G_ > 1 && N_ < 2ull * G_ * G_) { sp_set_error("setup: the LDE domain is too small for this many ranks"); return SP_E_INVALID_ARG; }
-    double _tp = wall_ms();
-    sp_ctx* ctx = c_;
-    h_ = fe_from_u64(opt.coset_offset);
-    if (fe_is_zero(h_)) return SP_E_INVALID_ARG;
-    hinv_ = fe_inv(h_);
-    half_ = fe_inv(fe_from_u64(2)); binv_ = fe_inv(fe_from_u64(1ull << lb));
-    g_ = host_primitive_root((int)logn_);
-    // Every buffer whose size setup() knows, in one pass that runs twice: first to size the arena, then to carve it.
-    auto allocate_all = [&]() -> int {
-        SP_TRY(alloc((void**)&d_coeffs_, sizeof(fe) * n_ * C_));
-        SP_TRY(alloc((void**)&d_trace_, sizeof(fe) * n_ * C_));
-        SP_TRY(alloc((void**)&d_lde_, sizeof(fe) * std::max<uint64_t>(Nl_, n_) * C_));  // >= n per column: also stages the raw rows
-        SP_TRY(alloc((void**)&d_t1_, sizeof(fe) * n_));
-        SP_TRY(alloc((void**)&d_t2_, sizeof(fe) * n_));
-        SP_TRY(alloc((void**)&d_h12s_, sizeof(fe) * n_ * 2));
-        SP_TRY(alloc((void**)&d_h12_, sizeof(fe) * Nl_ * 2));
-        SP_TRY(alloc((void**)&d_scratch_, sizeof(fe) * scratch_elems()));
-        if (G_ > 1) {
-            SP_TRY(alloc((void**)&d_local_, sizeof(fe) * Nl_));
-            SP_TRY(alloc((void**)&d_recv_, sizeof(fe) * Nl_));
-            SP_TRY(alloc((void**)&d_roots_, sizeof(digest32) * world_));
-            if (shard_interp_) {
-                cpr_max_ = (std::max(Cm_, Ca_) + G_ - 1) / G_;
-                SP_TRY(alloc((void**)&d_cstage_, sizeof(fe) * (uint64_t)world_ * cpr_max_ * n_));
-            }
-        }
-        SP_TRY(alloc_tree(tree_main_, N_, G_ > 1));
-        SP_TRY(alloc_tree(tree_aux_, N_, G_ > 1));
-        SP_TRY(alloc_tree(tree_comp_, N_, G_ > 1));
-        SP_TRY(alloc((void**)&d_comp_consts_, sizeof(CompositionConsts)));
-        // DeepConsts, then gamma_{j,k} as [frame rows][columns]: one upload per proof
-        SP_TRY(alloc((void**)&d_deep_consts_, deep_gammas_at() + sizeof(fe) * AIR_MAX_OFFSETS * C_));
-        d_deep_gammas_ = reinterpret_cast<fe*>(reinterpret_cast<uint8_t*>(d_deep_consts_) + deep_gammas_at());
-        SP_TRY(alloc((void**)&d_nonce_, sizeof(unsigned long long)));
-        // FRI: layers of at least 2^opt_fri_shard_min_log leaves (and at least 2 G^2, so that every rank owns whole blocks of the
-        // digest exchange) stay sharded; from layer fri_rep_ on every rank holds the whole layer.  The last, uncommitted fold
-        // output (layer log n) is always replicated.
-        fri_rep_ = 0;
-        if (G_ > 1)
-            while (fri_rep_ < logn_ && (N_ >> fri_rep_) >= std::max<uint64_t>(1ull << c_->opt_fri_shard_min_log, 2ull * G_ * G_)) ++fri_rep_;
-        d_fri_evals_.clear(); fri_trees_.clear();
-        for (uint32_t l = 0; l <= logn_; ++l) {
-            fe* e = nullptr;
-            const uint64_t M = N_ >> l;
-            SP_TRY(alloc((void**)&e, sizeof(fe) * (fri_sharded(l) ? M >> logG_ : M)));
-            d_fri_evals_.push_back(e);
-            if (l < logn_) { TreeBuf t; SP_TRY(alloc_tree(t, M, fri_sharded(l))); fri_trees_.push_back(t); }
-        }
-        SP_TRY(alloc((void**)&d_post_comp_, sizeof(fe) * 2 * n_));
-        SP_TRY(alloc((void**)&d_post_deep_, sizeof(fe) * n_));
-        d_post_comp0_ = nullptr;
-        if (G_ > 1 && logG_ == logb_) SP_TRY(alloc((void**)&d_post_comp0_, sizeof(fe) * 2 * n_));
-        return SP_OK;
-    };
-    measuring_ = true; measured_ = 0;
-    const int rc_measure = allocate_all();
-    measuring_ = false;
-    SP_TRY(rc_measure);
-    {
-        // room for what a Cairo proof allocates on first use (auxiliary-trace workspace, side-stream inverses): those allocations find
-        // their place in the arena too instead of costing a hipMalloc each
-        size_t sort_tmp = 0;
-        const uint64_t lazy = (Ca_ == 18 ? aux_workspace_bytes(n_, 4096, &sort_tmp) : 0) + sizeof(fe) * 19 * n_ + (4u << 20);
-        const uint64_t need = measured_ + lazy;
-        if (arena_cap_ < need) {
-            if (arena_) (void)hipFree(arena_);
-            arena_ = nullptr; arena_cap_ = 0;
-            void* a = nullptr;
-            if (hipMalloc(&a, need) == hipSuccess) { arena_ = static_cast<uint8_t*>(a); arena_cap_ = need; }
-            else (void)hipGetLastError();     // no single block of that size: the buffers are allocated one by one
-        }
-        arena_off_ = 0;
-        publish_device_bytes();
-    }
-    SP_TRY(allocate_all());
-    d_memcols_ = d_trace_ + 19 * n_;  // pc .. off_op1 columns of the main trace (input of the Cairo auxiliary trace)
-    SP_TIMEPOINT("  setup: device allocations");
-    // T1[q] = n^-1 h^rev(q): turns the unscaled DIF output into h-scaled coefficients c_k h^k (bit-reversed order)
-    fe ninv = fe_inv(fe_from_u64(n_));
-    SP_TRY(gen_power_table(c_->stream, d_t1_, n_, logn_, h_, ninv));
-    // T2[q] = N^-1 h^-rev(q): composition-polynomial split
-    fe Ninv = fe_inv(fe_from_u64(N_));
-    SP_TRY(gen_power_table(c_->stream, d_t2_, n_, logn_, hinv_, Ninv));
-    const fe* roots = nullptr;
-    SP_TRY(c_->ntt->roots((int)logN_, &roots));
-    // post factors of the 2n-point composition split and of the one-coset DEEP interpolation: functions of the shape and of
-    // this rank's first coset only, so they are generated once per setup instead of once per proof
-    {
-        const fe wN = host_primitive_root((int)logN_);
-        const fe u = fe_inv(fe_pow_u64(wN, rank_));  // w_N^-c0
-        const fe minv = fe_inv(fe_from_u64(2 * n_));
-        const fe base = fe_mul(hinv_, fe_sqr(u));
-        SP_TRY(gen_power_table(c_->stream, d_post_comp_, n_, logn_, base, minv));
-        SP_TRY(gen_power_table(c_->stream, d_post_comp_ + n_, n_, logn_, base, fe_mul(minv, fe_mul(hinv_, u))));
-        SP_TRY(gen_power_table(c_->stream, d_post_deep_, n_, logn_, u, fe_inv(fe_from_u64(n_))));
-        if (d_post_comp0_) {   // one coset per rank: the composition pair (0, b/2) is interpolated with c0 = 0 everywhere
-            SP_TRY(gen_power_table(c_->stream, d_post_comp0_, n_, logn_, hinv_, minv));
-            SP_TRY(gen_power_table(c_->stream, d_post_comp0_ + n_, n_, logn_, hinv_, fe_mul(minv, hinv_)));
-        }
-    }
-    SP_TIMEPOINT("  setup: tables");
-    ready_ = true;
-    stage_ = 1;
-    return SP_OK;
-}
-
-// sp_prewarm, first half: everything a first proof would otherwise create on its critical path that is not device memory of the
-// shape - the page-locked read-back slots (hipHostMalloc costs ~1 ms a piece), the side stream and its events, the copy stream
-// and the upload timers, and for callers of the row-major entry points the page-locked ring and the parked gather threads.
-int StarkProver::warm_plumbing(bool host_rows) {
-    SP_HIP_CHECK(hipSetDevice(c_->device));
-    if (!h_pin_ && hipHostMalloc(&h_pin_, 4096, hipHostMallocDefault) != hipSuccess) { h_pin_ = nullptr; return SP_E_ALLOC; }
-    if (!h_wide_ && hipHostMalloc(reinterpret_cast<void**>(&h_wide_), 64, hipHostMallocDefault) != hipSuccess) { h_wide_ = nullptr; return SP_E_ALLOC; }
-    SP_TRY(ensure_side());
-    SP_TRY(ensure_upload((uint32_t)UPLOAD_MAX_GROUPS));
-    if (host_rows) SP_TRY(ensure_ring_and_pool());
-    return SP_OK;
-}
-// sp_prewarm, second half: round 1's kernel sequence at the REAL shape on whatever the arena holds (the transforms have no
-// data-dependent control flow and accept any 256-bit operand; the hash kernels convert and absorb whatever they read) - the
-// size-specific kernel variants take their first launch here, and the device reaches its clocks before the trace exists.
-int StarkProver::warm_round1() {
-    if (!ready_ || stage_ != 1) return SP_E_STATE;
-    SP_HIP_CHECK(hipSetDevice(c_->device));
-    SP_HIP_CHECK(hipMemsetAsync(d_trace_, 0, sizeof(fe) * n_ * C_, c_->stream));
-    // Column slice by column slice, with a look at sp_prewarm_cancel's flag between slices: a caller whose trace is ready does not wait
-    // for the rest of the ramp.  The whole of it costs 15 ms at config #4's shape and 50 ms at config #3's and makes the first proof
-    // 1 - 2 ms faster than a fifth of it does (tools/experiments/ab_prewarm_r1.sh; SP_PREWARM_R1_FRAC bounds it for experiments).
-    static const double frac = [] { const char* e = std::getenv("SP_PREWARM_R1_FRAC"); return e ? std::min(1.0, std::max(0.0, std::atof(e))) : 1.0; }();
-    auto cancelled = [this] { return c_->prewarm_cancel.load(std::memory_order_acquire) != 0; };
-    bool stop = false;
-    for (int seg = 0; seg < 2 && !stop; ++seg) {
-        const uint32_t col0 = seg ? Cm_ : 0, cols = seg ? Ca_ : Cm_;
-        if (!cols) continue;
-        const uint32_t tc = std::max<uint32_t>(1, (uint32_t)(cols * frac)), slice = std::max<uint32_t>(1, cols / 8);
-        for (uint32_t c0 = 0; c0 < tc && !stop; c0 += slice) {
-            const uint32_t w = std::min(slice, tc - c0);
-            SP_TRY(c_->ntt->dif_natural_to_bitrev_inverse(d_coeffs_ + (uint64_t)(col0 + c0) * n_, (int)logn_, w, n_, d_t1_, d_trace_ + (uint64_t)(col0 + c0) * n_));
-            SP_TRY(c_->ntt->lde_coset_major(d_coeffs_ + (uint64_t)(col0 + c0) * n_, d_lde_ + (uint64_t)(col0 + c0) * Nl_, (int)logn_, (int)logb_, w, n_, Nl_, (int)logG_, (int)rank_));
-            SP_TRY(wait_stream());
-            stop = cancelled();
-        }
-        if (stop || tc < cols) break;
-        TreeBuf& t = seg ? tree_aux_ : tree_main_;
-        const MerkleHash mh = merkle_hash(false);
-        if (t.top == t.sub) {
-            SP_TRY(merkle_hash_leaves(c_->stream, d_lde_ + (uint64_t)col0 * Nl_, Nl_, cols, Nl_, t.sub, lde_order(), mh));
-            SP_TRY(merkle_reduce(c_->stream, t.sub, Nl_, nullptr, mh));
-        } else {
-            SP_TRY(merkle_hash_leaves_flat(c_->stream, d_lde_ + (uint64_t)col0 * Nl_, Nl_, cols, Nl_, reinterpret_cast<digest32*>(d_local_), lde_order(), mh));
-            SP_TRY(merkle_reduce(c_->stream, t.sub, t.sub_leaves, nullptr, mh));
-        }
-        SP_TRY(wait_stream());
-        stop = cancelled();
-    }
-    // the composition columns' shape too: two columns, the 2n-point inverse transform
-    SP_TRY(c_->ntt->dif_natural_to_bitrev_inverse(d_h12s_, (int)logn_ + 1, 1, 2 * n_, d_post_comp_));
-    SP_TRY(c_->ntt->lde_coset_major(d_h12s_, d_h12_, (int)logn_, (int)logb_, 2, n_, Nl_, (int)logG_, (int)rank_));
-    SP_TRY(wait_stream());
-    return SP_OK;
-}
-
-int StarkProver::alloc_tree(TreeBuf& t, uint64_t leaves_total, bool sharded) {
-    t.sub_leaves = sharded ? leaves_total >> logG_ : leaves_total;
-    SP_TRY(alloc((void**)&t.sub, sizeof(digest32) * (2 * t.sub_leaves - 1)));
-    t.top = t.sub;
-    if (sharded) SP_TRY(alloc((void**)&t.top, sizeof(digest32) * (2ull * G_ - 1)));
-    return SP_OK;
-}
-
-// Frees a buffer this prover outgrew (everything that could still read it has finished first).
-void StarkProver::release(void* p, size_t bytes) {
-    if (!p) return;
-    (void)hipStreamSynchronize(c_->stream);
-    if (side_stream_) (void)hipStreamSynchronize(side_stream_);
-    if (copy_stream_) (void)hipStreamSynchronize(copy_stream_);
-    auto it = std::find(allocs_.begin(), allocs_.end(), p);
-    if (it == allocs_.end()) return;     // carved out of the arena: the space comes back with the next setup()
-    allocs_.erase(it);
-    (void)hipFree(p);
-    alloc_bytes_ -= std::min<uint64_t>(alloc_bytes_, bytes);
-    publish_device_bytes();
-}
-
-int StarkProver::ensure_gather(uint64_t elems) {
-    if (elems <= gather_cap_) return SP_OK;
-    release(d_gather_, sizeof(fe) * gather_cap_);
-    d_gather_ = nullptr; gather_cap_ = 0;
-    SP_TRY(alloc((void**)&d_gather_, sizeof(fe) * elems));
-    gather_cap_ = elems;
-    return SP_OK;
-}
-
-// DEEP inverses beyond the shared scratch (many frame rows on a small blowup): one buffer, grown on demand, kept across proofs
 // DEEP denominators of round 4 on the side stream while round 3 evaluates the polynomials at z (same arrays, same batch
 // inversion as deep_fri_begin's inline path; valid-trace form only: one coset of n points).
 int StarkProver::prefetch_deep_inverses() {
@@ -358,7 +30,7 @@ int StarkProver::prefetch_deep_inverses() {
     const uint32_t R = (uint32_t)offsets_.size(), npts = R + 1;
     SP_TRY(ensure_side());
     SP_TRY(ensure_deep_scratch((2ull * npts + 1) * n_));
-    if (!d_flag_side_) SP_TRY(alloc((void**)&d_flag_side_, 4 * sizeof(int)));
+    SP_TRY(ensure_side_flags());
     fe pts[AIR_MAX_OFFSETS + 1];
     for (uint32_t k = 0; k < R; ++k) pts[k] = fe_mul(z_, fe_pow_u64(g_, offsets_[k]));
     pts[R] = fe_sqr(z_);
@@ -367,9 +39,9 @@ int StarkProver::prefetch_deep_inverses() {
     const fe hp = fe_mul(h_, fe_pow_u64(host_primitive_root((int)logN_), rank_));
     SP_HIP_CHECK(hipEventRecord(ev_side_fork_, c_->stream));          // (the buffer's previous readers are behind this point)
     SP_HIP_CHECK(hipStreamWaitEvent(side_stream_, ev_side_fork_, 0));
-    SP_HIP_CHECK(hipMemsetAsync(d_flag_side_, 0, sizeof(int), side_stream_));
-    SP_TRY(coset_minus_points(side_stream_, d_deepx_, n_, logn_, roots_n, hp, pts, npts, ShardMap{0, 0, 0}));
-    SP_TRY(batch_inverse(side_stream_, d_deepx_, d_deepx_ + (uint64_t)npts * n_, (uint64_t)npts * n_, d_flag_side_));
+    SP_HIP_CHECK(hipMemsetAsync(side_flag(SIDE_DEEP_INV), 0, sizeof(int), side_stream_));
+    SP_TRY(coset_minus_points(side_stream_, od_.deepx.p, n_, logn_, roots_n, hp, pts, npts, ShardMap{0, 0, 0}));
+    SP_TRY(batch_inverse(side_stream_, od_.deepx.p, od_.deepx.p + (uint64_t)npts * n_, (uint64_t)npts * n_, side_flag(SIDE_DEEP_INV)));
     SP_HIP_CHECK(hipEventRecord(ev_side_deep_, side_stream_));
     deep_pref_ = true;
     return SP_OK;
@@ -386,8 +58,8 @@ int StarkProver::prefetch_boundary_inverses(const std::vector<uint64_t>& steps_i
     SP_HIP_CHECK(hipSetDevice(c_->device));
     SP_TRY(ensure_side());
     const uint64_t M = 2 * n_;
-    if (bpre_cap_ < 6 * M) { SP_TRY(alloc((void**)&d_bpre_, sizeof(fe) * 6 * M)); bpre_cap_ = 6 * M; }
-    if (!d_flag_side_) SP_TRY(alloc((void**)&d_flag_side_, 4 * sizeof(int)));
+    SP_TRY(grow(od_.bpre, 6 * M));
+    SP_TRY(ensure_side_flags());
     bpre_points_.clear();
     for (uint64_t s : steps) bpre_points_.push_back(fe_pow_u64(g_, s));
     const fe* roots_m = nullptr;
@@ -396,119 +68,11 @@ int StarkProver::prefetch_boundary_inverses(const std::vector<uint64_t>& steps_i
     const uint32_t nd = (uint32_t)bpre_points_.size();
     SP_HIP_CHECK(hipEventRecord(ev_side_fork_, c_->stream));
     SP_HIP_CHECK(hipStreamWaitEvent(side_stream_, ev_side_fork_, 0));
-    SP_HIP_CHECK(hipMemsetAsync(d_flag_side_ + 1, 0, sizeof(int), side_stream_));
-    SP_TRY(coset_minus_points(side_stream_, d_bpre_, M, logn_ + 1, roots_m, hp, bpre_points_.data(), nd, ShardMap{0, 0, 0}));
-    SP_TRY(batch_inverse(side_stream_, d_bpre_, d_bpre_ + 3 * M, (uint64_t)nd * M, d_flag_side_ + 1));
+    SP_HIP_CHECK(hipMemsetAsync(side_flag(SIDE_BND_INV), 0, sizeof(int), side_stream_));
+    SP_TRY(coset_minus_points(side_stream_, od_.bpre.p, M, logn_ + 1, roots_m, hp, bpre_points_.data(), nd, ShardMap{0, 0, 0}));
+    SP_TRY(batch_inverse(side_stream_, od_.bpre.p, od_.bpre.p + 3 * M, (uint64_t)nd * M, side_flag(SIDE_BND_INV)));
     SP_HIP_CHECK(hipEventRecord(ev_side_bnd_, side_stream_));
     bpre_valid_ = true;
-    return SP_OK;
-}
-
-int StarkProver::ensure_deep_scratch(uint64_t elems) {
-    if (elems <= deepx_cap_) return SP_OK;
-    release(d_deepx_, sizeof(fe) * deepx_cap_);
-    d_deepx_ = nullptr; deepx_cap_ = 0; deep_pref_ = false;
-    SP_TRY(alloc((void**)&d_deepx_, sizeof(fe) * elems));
-    deepx_cap_ = elems;
-    return SP_OK;
-}
-
-// [N] scratch for the paths that need the whole domain on every rank (constraint-violating traces, G = b)
-int StarkProver::full_domain_buffer(fe** out) {
-    if (!fri_sharded(0)) { *out = d_fri_evals_[0]; return SP_OK; }   // free until round 4
-    if (!d_fullN_) SP_TRY(alloc((void**)&d_fullN_, sizeof(fe) * N_));
-    *out = d_fullN_;
-    return SP_OK;
-}
-
-// Blocking all-gather through the context hook: every rank contributes bytes_per_rank, recv = [world][bytes_per_rank]
-// (the first G slots are the G distinct roles).
-namespace {
-// brackets one stream-ordered exchange with two events on the stream it is enqueued on (sp_comm_time_ms reads them back)
-struct CommSpan {
-    sp_ctx* c; hipStream_t st; bool on = false;
-    CommSpan(sp_ctx* ctx, hipStream_t stream) : c(ctx), st(stream) {
-        if (c->comm_ev_used + 2 > 8192) return;
-        hipEvent_t e = c->comm_event();
-        if (e && hipEventRecord(e, st) == hipSuccess) on = true; else if (e) --c->comm_ev_used;
-    }
-    ~CommSpan() {
-        if (!on) return;
-        hipEvent_t e = c->comm_event();
-        if (!e || hipEventRecord(e, st) != hipSuccess) c->comm_ev_used -= e ? 2 : 1;      // (an unpaired begin is dropped)
-    }
-};
-struct BlockingSpan {
-    sp_ctx* c; double t0;
-    explicit BlockingSpan(sp_ctx* ctx) : c(ctx), t0(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count()) {}
-    ~BlockingSpan() { c->stat_comm_blocking_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count() - t0; }
-};
-}  // namespace
-
-int StarkProver::all_gather(const void* send_dev, void* recv_dev, uint64_t bytes_per_rank, bool stream_ordered) {
-    if (stream_ordered && comm_async()) {
-        int rc;
-        { CommSpan span(c_, c_->stream); rc = c_->allgather_async(c_->allgather_user, send_dev, recv_dev, bytes_per_rank, c_->stream); }
-        if (rc != 0) { sp_set_error("stream-ordered all-gather failed (" + std::to_string(rc) + ")"); return SP_E_HIP; }
-        c_->stat_ag_calls += 1; c_->stat_ag_bytes += bytes_per_rank; c_->stat_recv_bytes += bytes_per_rank * (world_ - 1);
-        return SP_OK;
-    }
-    SP_HIP_CHECK(sp_stream_wait_polling(c_->stream));
-    int rc;
-    { BlockingSpan span(c_); rc = c_->allgather(c_->allgather_user, send_dev, recv_dev, bytes_per_rank); }
-    if (rc != 0) { sp_set_error("all-gather hook failed (" + std::to_string(rc) + ")"); return SP_E_HIP; }
-    c_->stat_ag_calls += 1; c_->stat_ag_bytes += bytes_per_rank; c_->stat_recv_bytes += bytes_per_rank * (world_ - 1);
-    return SP_OK;
-}
-
-int StarkProver::all_gather_begin(const void* send_dev, void* recv_dev, uint64_t bytes_per_rank, int slot) {
-    if (slot < 0 || slot >= COMM_BLOCKS) return SP_E_INVALID_ARG;
-    if (!comm_async()) return all_gather(send_dev, recv_dev, bytes_per_rank);
-    if (!comm_stream_) {
-        SP_HIP_CHECK(hipStreamCreateWithFlags(&comm_stream_, hipStreamNonBlocking));
-        SP_HIP_CHECK(hipEventCreateWithFlags(&ev_comm_fork_, hipEventDisableTiming));
-        for (auto& e : ev_comm_done_) SP_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-    SP_HIP_CHECK(hipEventRecord(ev_comm_fork_, c_->stream));            // the send block is complete behind this point
-    SP_HIP_CHECK(hipStreamWaitEvent(comm_stream_, ev_comm_fork_, 0));
-    int rc;
-    { CommSpan span(c_, comm_stream_); rc = c_->allgather_async(c_->allgather_user, send_dev, recv_dev, bytes_per_rank, comm_stream_); }
-    if (rc != 0) { sp_set_error("stream-ordered all-gather failed (" + std::to_string(rc) + ")"); return SP_E_HIP; }
-    SP_HIP_CHECK(hipEventRecord(ev_comm_done_[slot], comm_stream_));
-    c_->stat_ag_calls += 1; c_->stat_ag_bytes += bytes_per_rank; c_->stat_recv_bytes += bytes_per_rank * (world_ - 1);
-    return SP_OK;
-}
-int StarkProver::all_gather_end(int slot) {
-    if (!comm_async()) return SP_OK;
-    SP_HIP_CHECK(hipStreamWaitEvent(c_->stream, ev_comm_done_[slot], 0));
-    return SP_OK;
-}
-
-// Block d of `send` goes to the rank with role d; recv[s] = what role s addressed to this rank.  One all-to-all when the
-// hook exists (every rank is its own role then); otherwise an all-gather of the whole send array and a local selection.
-int StarkProver::exchange_blocks(const void* send_dev, void* recv_dev, uint64_t bytes, bool stream_ordered) {
-    if (stream_ordered && comm_async() && c_->alltoall_async && world_ == G_) {
-        int rc;
-        { CommSpan span(c_, c_->stream); rc = c_->alltoall_async(c_->allgather_user, send_dev, recv_dev, bytes, c_->stream); }
-        if (rc != 0) { sp_set_error("stream-ordered all-to-all failed (" + std::to_string(rc) + ")"); return SP_E_HIP; }
-        c_->stat_a2a_calls += 1; c_->stat_a2a_bytes += bytes * (G_ - 1); c_->stat_recv_bytes += bytes * (G_ - 1);
-        return SP_OK;
-    }
-    if (c_->alltoall && world_ == G_) {   // (also with a stream-ordered all-gather but no such all-to-all: one host round trip beats G times the bytes)
-        SP_HIP_CHECK(sp_stream_wait_polling(c_->stream));
-        int rc;
-        { BlockingSpan span(c_); rc = c_->alltoall(c_->allgather_user, send_dev, recv_dev, bytes); }
-        if (rc != 0) { sp_set_error("all-to-all hook failed (" + std::to_string(rc) + ")"); return SP_E_HIP; }
-        c_->stat_a2a_calls += 1; c_->stat_a2a_bytes += bytes * (G_ - 1); c_->stat_recv_bytes += bytes * (G_ - 1);
-        return SP_OK;
-    }
-    const uint64_t per_rank = bytes * G_;
-    SP_TRY(ensure_gather((per_rank * world_ + sizeof(fe) - 1) / sizeof(fe)));
-    SP_TRY(all_gather(send_dev, d_gather_, per_rank, stream_ordered));
-    const uint8_t* g = reinterpret_cast<const uint8_t*>(d_gather_);
-    for (uint32_t src = 0; src < G_; ++src)   // the first G slots are the G roles
-        SP_HIP_CHECK(hipMemcpyAsync(static_cast<uint8_t*>(recv_dev) + (uint64_t)src * bytes, g + (uint64_t)src * per_rank + (uint64_t)rank_ * bytes, bytes,
-                                    hipMemcpyDeviceToDevice, c_->stream));
     return SP_OK;
 }
 
@@ -613,21 +177,18 @@ int StarkProver::commit_trace(int segment, const uint8_t* rows_host, uint32_t co
 // trace VALUES and the interpolation follows as configured (SP_OPT_SHARD_INTERPOLATION).
 int StarkProver::commit_trace_rows_sharded(int segment, const uint8_t* rows_host, uint32_t cols, uint8_t root_out[32], uint32_t binary_cols) {
     const uint32_t col0 = segment == 0 ? 0 : Cm_;
-    const uint32_t cpr = (cols + G_ - 1) / G_;
-    auto first_col = [&](uint32_t role) { return std::min(role * cpr, cols - cpr); };
+    const uint32_t cpr = cols_per_role(cols);
     fe* trace = d_trace_ + (uint64_t)col0 * n_;
     {
-        // (a rank whose window holds a cell that breaks the 0 / 1 hint must not leave the others waiting in the all-gather: the verdict
-        // of the window upload is agreed on first - one flag per rank through the same all-gather)
         // The verdict of the window upload is agreed on before the all-gather of the trace - one word per rank through the same
         // transport - so that a rank whose window breaks the 0 / 1 hint, or whose upload failed, does not leave the others waiting.
-        const int rc = commit_trace_pipelined(segment, rows_host, cols, root_out, first_col(rank_), cpr, true, binary_cols);
-        if (!d_flags_all_) SP_TRY(alloc((void**)&d_flags_all_, sizeof(int) * world_));
+        const int rc = commit_trace_pipelined(segment, rows_host, cols, root_out, role_first_col(rank_, cols), cpr, true, binary_cols);
+        SP_TRY(grow(od_.flags_all, world_));
         const int mine = rc == SP_OK ? 0 : (rc == SP_RETRY_RAW_UPLOAD ? 1 : 2);
         SP_HIP_CHECK(hipMemcpyAsync(c_->d_flag, &mine, sizeof(int), hipMemcpyHostToDevice, c_->stream));
-        SP_TRY(all_gather(c_->d_flag, d_flags_all_, sizeof(int)));
+        SP_TRY(all_gather(c_->d_flag, od_.flags_all.p, sizeof(int)));
         std::vector<int> flags(world_, 0);
-        SP_HIP_CHECK(hipMemcpy(flags.data(), d_flags_all_, sizeof(int) * world_, hipMemcpyDeviceToHost));
+        SP_HIP_CHECK(hipMemcpy(flags.data(), od_.flags_all.p, sizeof(int) * world_, hipMemcpyDeviceToHost));
         if (rc != SP_OK && rc != SP_RETRY_RAW_UPLOAD) return rc;
         int worst = 0;
         for (int f : flags) worst = std::max(worst, f);
@@ -638,11 +199,11 @@ int StarkProver::commit_trace_rows_sharded(int segment, const uint8_t* rows_host
     const uint64_t block = (uint64_t)cpr * n_;
     fe* stage = nullptr;
     if ((uint64_t)world_ * block <= std::max<uint64_t>(Nl_, n_) * cols) stage = d_lde_ + (uint64_t)col0 * std::max<uint64_t>(Nl_, n_);
-    else { SP_TRY(ensure_gather((uint64_t)world_ * block)); stage = d_gather_; }
-    SP_TRY(all_gather(trace + (uint64_t)first_col(rank_) * n_, stage, block * sizeof(fe), true));
+    else { SP_TRY(ensure_gather((uint64_t)world_ * block)); stage = od_.gather.p; }
+    SP_TRY(all_gather(trace + (uint64_t)role_first_col(rank_, cols) * n_, stage, block * sizeof(fe), true));
     for (uint32_t role = 0; role < G_; ++role) {      // (the first G slots are the G roles; the own block is in place already)
         if (role == rank_) continue;
-        SP_HIP_CHECK(hipMemcpyAsync(trace + (uint64_t)first_col(role) * n_, stage + (uint64_t)role * block, block * sizeof(fe), hipMemcpyDeviceToDevice, c_->stream));
+        SP_HIP_CHECK(hipMemcpyAsync(trace + (uint64_t)role_first_col(role, cols) * n_, stage + (uint64_t)role * block, block * sizeof(fe), hipMemcpyDeviceToDevice, c_->stream));
     }
     if (segment == 0) SP_TRY(launch_aux_presort());
     SP_TRY(commit_segment_resident(segment, cols, root_out));
@@ -663,14 +224,13 @@ int StarkProver::commit_trace_built(const TraceBuildInput& in, uint8_t root_out[
     const uint8_t* image = I.current(&image_pinned);
     constexpr uint32_t REG_CHUNKS = 4;
     SP_TRY(ensure_upload(REG_CHUNKS));
-    if (!h_wide_ && hipHostMalloc(reinterpret_cast<void**>(&h_wide_), 64, hipHostMallocDefault) != hipSuccess) { h_wide_ = nullptr; sp_set_error("pinned flag slot: allocation failed"); return SP_E_ALLOC; }
+    SP_TRY(ensure_host_flags());
     // staging: the image and the builder's scratch sit in this segment's (not yet written) LDE area when they fit
     const size_t need = (size_t)I.bytes + main_trace_scratch_bytes(P.steps);
     uint8_t* stage = reinterpret_cast<uint8_t*>(d_lde_);
-    struct Tmp { void* p = nullptr; hipStream_t st; ~Tmp() { if (p) { (void)hipStreamSynchronize(st); (void)hipFree(p); } } } tmp;
-    tmp.st = c_->stream;
+    ScopedDevAlloc tmp(c_->stream);
     if (need > sizeof(fe) * std::max<uint64_t>(Nl_, n_) * Cm_) {
-        if (hipMalloc(&tmp.p, need) != hipSuccess) { (void)hipGetLastError(); sp_set_error("commit_trace: staging allocation failed"); return SP_E_ALLOC; }
+        SP_TRY(tmp.alloc(need, "commit_trace"));
         stage = static_cast<uint8_t*>(tmp.p);
     }
     // The memory (and the two hole lists behind it) first, then the register states in four chunks on the copy stream: the rows of a
@@ -707,11 +267,11 @@ int StarkProver::commit_trace_built(const TraceBuildInput& in, uint8_t root_out[
         chunks_used = k + 1;
     }
     SP_TRY(cairo_main_trace_finish(c_->stream, a, stage + I.bytes, c_->d_flag));
-    SP_HIP_CHECK(hipMemcpyAsync(h_wide_ + 4, c_->d_flag, sizeof(int), hipMemcpyDeviceToHost, c_->stream));
+    SP_HIP_CHECK(hipMemcpyAsync(&host_flags().trace_build_oob, c_->d_flag, sizeof(int), hipMemcpyDeviceToHost, c_->stream));
     const double host_ms = wall_ms() - t0;
     SP_TRY(launch_aux_presort());
     SP_TRY(commit_segment_resident(0, Cm_, root_out));        // (its read-back of the root waits for everything above)
-    if (h_wide_[4]) { sp_set_error("commit_trace: a trace row reads beyond the run's memory image"); return SP_E_INVALID_ARG; }
+    if (host_flags().trace_build_oob) { sp_set_error("commit_trace: a trace row reads beyond the run's memory image"); return SP_E_INVALID_ARG; }
     return finish_upload_stats(chunks_used, I.bytes, 0.0, host_ms, image_pinned ? 4 : 5);
 }
 
@@ -727,8 +287,7 @@ int StarkProver::commit_segment_resident(int segment, uint32_t cols, uint8_t roo
         // With a stream-ordered transport the cpr columns go in up to four blocks: the exchange of block k runs on the
         // communication stream beside the inverse transforms of block k + 1 and the LDE of block k - 1; a blocking transport
         // keeps the one exchange (every call is a host round trip through the hook).
-        const uint32_t cpr = (cols + G_ - 1) / G_;
-        auto first_col = [&](uint32_t role) { return std::min(role * cpr, cols - cpr); };
+        const uint32_t cpr = cols_per_role(cols);
         const uint32_t K = comm_async() ? std::min<uint32_t>(cpr, (uint32_t)COMM_BLOCKS) : 1u;
         const uint32_t bc = (cpr + K - 1) / K;
         std::vector<uint8_t> extended(cols, 0);
@@ -744,12 +303,12 @@ int StarkProver::commit_segment_resident(int segment, uint32_t cols, uint8_t roo
             const Block& b = blocks[k];
             SP_TRY(all_gather_end((int)k));
             for (uint32_t role = 0; role < G_; ++role)
-                SP_HIP_CHECK(hipMemcpyAsync(coeffs + (uint64_t)(first_col(role) + b.j0) * n_, b.stage + (uint64_t)role * b.w * n_, (uint64_t)b.w * n_ * sizeof(fe),
+                SP_HIP_CHECK(hipMemcpyAsync(coeffs + (uint64_t)(role_first_col(role, cols) + b.j0) * n_, b.stage + (uint64_t)role * b.w * n_, (uint64_t)b.w * n_ * sizeof(fe),
                                             hipMemcpyDeviceToDevice, c_->stream));
             if (K == 1) return SP_OK;          // one exchange: the whole segment is extended in one launch below
             for (uint32_t role = 0; role < G_; ++role)
                 for (uint32_t j = 0; j < b.w;) {   // runs of columns not extended yet (the ranges of the last roles overlap)
-                    const uint32_t c = first_col(role) + b.j0 + j;
+                    const uint32_t c = role_first_col(role, cols) + b.j0 + j;
                     if (extended[c]) { ++j; continue; }
                     uint32_t run = 0;
                     while (j + run < b.w && !extended[c + run]) { extended[c + run] = 1; ++run; }
@@ -761,7 +320,7 @@ int StarkProver::commit_segment_resident(int segment, uint32_t cols, uint8_t roo
         for (size_t k = 0; k < blocks.size(); ++k) {
             const Block& b = blocks[k];
             fe* mine = b.stage + (uint64_t)wrank_ * b.w * n_;      // in place: slot `rank` of the receive block is the send buffer
-            SP_TRY(c_->ntt->dif_natural_to_bitrev_inverse(mine, (int)logn_, b.w, n_, d_t1_, d_trace_ + (uint64_t)(col0 + first_col(rank_) + b.j0) * n_));
+            SP_TRY(c_->ntt->dif_natural_to_bitrev_inverse(mine, (int)logn_, b.w, n_, d_t1_, d_trace_ + (uint64_t)(col0 + role_first_col(rank_, cols) + b.j0) * n_));
             SP_TRY(all_gather_begin(mine, b.stage, (uint64_t)b.w * n_ * sizeof(fe), (int)k));
             if (k > 0) SP_TRY(finish(k - 1));
         }
@@ -802,20 +361,6 @@ int StarkProver::public_memory_lists(const PublicInputs& pub) {
     return SP_OK;
 }
 
-int StarkProver::ensure_aux_workspace(uint64_t pm) {
-    if (d_auxws_ && pm <= auxws_pm_cap_) return SP_OK;
-    size_t sort_tmp = 0;
-    uint64_t cap = std::max<uint64_t>(pm, 1024);
-    size_t bytes = aux_workspace_bytes(n_, cap, &sort_tmp);
-    release(d_auxws_, auxws_bytes_);   // (a context reused with a growing public memory must not keep every workspace it outgrew)
-    d_auxws_ = nullptr; auxws_bytes_ = 0; auxws_pm_cap_ = 0; presorted_ = false;
-    void* base = nullptr;
-    SP_TRY(alloc(&base, bytes));
-    d_auxws_ = base; auxws_bytes_ = bytes; auxws_pm_cap_ = cap;
-    aux_workspace_carve(auxws_, base, n_, cap, sort_tmp);
-    return SP_OK;
-}
-
 // The sorts of the auxiliary trace need the main trace and the public memory but no challenge: side stream, from the moment
 // the natural-order main columns are queued on the compute stream (request_aux_presort + commit_trace(0, ..)).
 int StarkProver::launch_aux_presort() {
@@ -826,14 +371,15 @@ int StarkProver::launch_aux_presort() {
     const uint64_t pm = pm_addr_h_.size();
     SP_TRY(ensure_aux_workspace(pm));
     SP_TRY(ensure_side());
-    if (!d_flag_side_) SP_TRY(alloc((void**)&d_flag_side_, 4 * sizeof(int)));
+    SP_TRY(ensure_side_flags());
     SP_HIP_CHECK(hipEventRecord(ev_side_fork_, c_->stream));          // the main trace columns are behind this point
     SP_HIP_CHECK(hipStreamWaitEvent(side_stream_, ev_side_fork_, 0));
-    SP_HIP_CHECK(hipMemsetAsync(d_flag_side_ + 2, 0, 2 * sizeof(int), side_stream_));
-    SP_TRY(cairo_aux_presort(side_stream_, auxws_, d_memcols_, n_, pm_addr_h_.data(), pm_val_h_.data(), pm, d_flag_side_ + 2, d_flag_side_ + 3));
+    SP_HIP_CHECK(hipMemsetAsync(side_flag(SIDE_PRESORT_MALFORMED), 0, 2 * sizeof(int), side_stream_));   // (and SIDE_PRESORT_WIDE_KEY behind it)
+    SP_TRY(cairo_aux_presort(side_stream_, auxws_, d_memcols_, n_, pm_addr_h_.data(), pm_val_h_.data(), pm, side_flag(SIDE_PRESORT_MALFORMED), side_flag(SIDE_PRESORT_WIDE_KEY)));
     // the "address beyond the key bits" flag travels to the host behind the sorts: commit_aux_cairo reads it without a round trip of its own
-    if (!h_wide_ && hipHostMalloc(reinterpret_cast<void**>(&h_wide_), 64, hipHostMallocDefault) != hipSuccess) { h_wide_ = nullptr; sp_set_error("pinned flag slot: allocation failed"); return SP_E_ALLOC; }
-    SP_HIP_CHECK(hipMemcpyAsync(h_wide_, d_flag_side_ + 2, 2 * sizeof(int), hipMemcpyDeviceToHost, side_stream_));   // [0]: malformed-input flag, [1]: key beyond the presort's bits
+    SP_TRY(ensure_host_flags());
+    static_assert(offsetof(HostFlags, presort_wide_key) == offsetof(HostFlags, presort_malformed) + sizeof(int), "one copy moves both presort flags");
+    SP_HIP_CHECK(hipMemcpyAsync(&host_flags().presort_malformed, side_flag(SIDE_PRESORT_MALFORMED), 2 * sizeof(int), hipMemcpyDeviceToHost, side_stream_));
     SP_HIP_CHECK(hipEventRecord(ev_side_presort_, side_stream_));
     presorted_ = true;
     return SP_OK;
@@ -848,7 +394,7 @@ int StarkProver::commit_aux_cairo(const PublicInputs& pub, const fe rap[3], uint
     if (pre) {   // an address beyond the key bits the presort looked at (a trace with a discontinuous memory): sort again, all 64 bits
         SP_HIP_CHECK(hipStreamWaitEvent(c_->stream, ev_side_presort_, 0));
         SP_HIP_CHECK(hipEventSynchronize(ev_side_presort_));   // (the sorts ended beside round 1's transforms: no wait in practice)
-        if (h_wide_[1] || h_wide_[0] == 2) pre = false;
+        if (host_flags().presort_wide_key || host_flags().presort_malformed == 2) pre = false;
     }
     else SP_TRY(public_memory_lists(pub));     // (the presort built them from the same public inputs)
     const uint64_t pm = pm_addr_h_.size();
@@ -861,12 +407,12 @@ int StarkProver::commit_aux_cairo(const PublicInputs& pub, const fe rap[3], uint
     int flag = 0, flag_pre = 0;
     // An address beyond 2^64 (no VM writes one, but the reference proves whatever table it is given): the presort has already said so,
     // or the 64-bit sort below does - then once more with the four-limb sort.
-    bool all_limbs = presort_ran && h_wide_[0] == 2;
+    bool all_limbs = presort_ran && host_flags().presort_malformed == 2;
     for (int attempt = 0; attempt < 2; ++attempt) {
         SP_TRY(cairo_aux_trace_device(c_->stream, auxws_, d_memcols_, n_, pm_addr_h_.data(), pm_val_h_.data(), pm, rap, aux_out, c_->d_flag,
                                       side_stream_, ev_side_fork_, ev_side_aux_, pre, all_limbs));
         SP_HIP_CHECK(hipMemcpyAsync(&flag, c_->d_flag, sizeof(int), hipMemcpyDeviceToHost, c_->stream));
-        if (pre) SP_HIP_CHECK(hipMemcpyAsync(&flag_pre, d_flag_side_ + 2, sizeof(int), hipMemcpyDeviceToHost, c_->stream));
+        if (pre) SP_HIP_CHECK(hipMemcpyAsync(&flag_pre, side_flag(SIDE_PRESORT_MALFORMED), sizeof(int), hipMemcpyDeviceToHost, c_->stream));
         SP_HIP_CHECK(sp_stream_wait_polling(c_->stream));  // flags
         if (!flag) flag = flag_pre;
         if (flag != 2 || all_limbs) break;
@@ -950,12 +496,7 @@ int StarkProver::commit_aux_program(const AirAuxHost& aux, const std::vector<fe>
         ch.o_kinds = place(sizeof(uint32_t) * ch.kc);
         ch.o_col = place(sizeof(uint32_t) * std::max<uint32_t>(1, ch.n_den));
     }
-    if (bytes > auxp_buf_cap_) {
-        release(d_auxp_buf_, auxp_buf_cap_);
-        d_auxp_buf_ = nullptr; auxp_buf_cap_ = 0;
-        SP_TRY(alloc((void**)&d_auxp_buf_, bytes));
-        auxp_buf_cap_ = bytes;
-    }
+    SP_TRY(grow(od_.auxp_buf, bytes));
     std::vector<uint8_t>& up = h_auxp_up_;
     up.assign(bytes, 0);
     fe* hconst = reinterpret_cast<fe*>(up.data() + o_consts);
@@ -966,35 +507,30 @@ int StarkProver::commit_aux_program(const AirAuxHost& aux, const std::vector<fe>
         std::memcpy(up.data() + ch.o_kinds, ch.kinds.data(), sizeof(uint32_t) * ch.kc);
         if (ch.n_den) std::memcpy(up.data() + ch.o_col, ch.col_of.data(), sizeof(uint32_t) * ch.n_den);
     }
-    SP_HIP_CHECK(hipMemcpyAsync(d_auxp_buf_, up.data(), bytes, hipMemcpyHostToDevice, c_->stream));
+    SP_HIP_CHECK(hipMemcpyAsync(od_.auxp_buf.p, up.data(), bytes, hipMemcpyHostToDevice, c_->stream));
     // --- workspace: [max_den][n] denominators, as much batch-inversion scratch, [chunk][nb] scan block totals
     const uint64_t ws = 2 * (uint64_t)max_den * n_ + (uint64_t)chunk * nb;
-    if (ws > auxp_ws_cap_) {
-        release(d_auxp_ws_, auxp_ws_cap_ * sizeof(fe));
-        d_auxp_ws_ = nullptr; auxp_ws_cap_ = 0;
-        SP_TRY(alloc((void**)&d_auxp_ws_, sizeof(fe) * ws));
-        auxp_ws_cap_ = ws;
-    }
-    fe* den = d_auxp_ws_;
+    SP_TRY(grow(od_.auxp_ws, ws));
+    fe* den = od_.auxp_ws.p;
     fe* scratch = den + (uint64_t)max_den * n_;
     fe* block_tot = scratch + (uint64_t)max_den * n_;
-    const fe* consts_dev = reinterpret_cast<const fe*>(d_auxp_buf_ + o_consts);
+    const fe* consts_dev = reinterpret_cast<const fe*>(od_.auxp_buf.p + o_consts);
     SP_HIP_CHECK(hipMemsetAsync(c_->d_flag, 0, sizeof(int), c_->stream));
     for (const Chunk& ch : chunks) {
         fe* cols = d_trace_ + (uint64_t)(Cm_ + ch.k0) * n_;
-        const uint32_t* kinds = reinterpret_cast<const uint32_t*>(d_auxp_buf_ + ch.o_kinds);
-        SP_TRY(air_aux_terms(c_->stream, d_trace_, n_, reinterpret_cast<const AirOpDev*>(d_auxp_buf_ + ch.o_ops), (uint32_t)ch.ops.size(), consts_dev, cols, den));
+        const uint32_t* kinds = reinterpret_cast<const uint32_t*>(od_.auxp_buf.p + ch.o_kinds);
+        SP_TRY(air_aux_terms(c_->stream, d_trace_, n_, reinterpret_cast<const AirOpDev*>(od_.auxp_buf.p + ch.o_ops), (uint32_t)ch.ops.size(), consts_dev, cols, den));
         if (ch.n_den) {
             SP_TRY(batch_inverse(c_->stream, den, scratch, (uint64_t)ch.n_den * n_, c_->d_flag));
-            SP_TRY(air_aux_apply_den(c_->stream, cols, den, reinterpret_cast<const uint32_t*>(d_auxp_buf_ + ch.o_col), ch.n_den, n_));
+            SP_TRY(air_aux_apply_den(c_->stream, cols, den, reinterpret_cast<const uint32_t*>(od_.auxp_buf.p + ch.o_col), ch.n_den, n_));
         }
         SP_TRY(air_aux_scan(c_->stream, cols, n_, ch.kc, kinds, block_tot));
     }
     // the zero-denominator flag rides behind the columns; the read-back of the root below waits for it
-    if (!h_wide_ && hipHostMalloc(reinterpret_cast<void**>(&h_wide_), 64, hipHostMallocDefault) != hipSuccess) { h_wide_ = nullptr; sp_set_error("pinned flag slot: allocation failed"); return SP_E_ALLOC; }
-    SP_HIP_CHECK(hipMemcpyAsync(h_wide_ + 5, c_->d_flag, sizeof(int), hipMemcpyDeviceToHost, c_->stream));
+    SP_TRY(ensure_host_flags());
+    SP_HIP_CHECK(hipMemcpyAsync(&host_flags().auxp_zero_den, c_->d_flag, sizeof(int), hipMemcpyDeviceToHost, c_->stream));
     SP_TRY(commit_segment_resident(1, K, root_out));
-    if (h_wide_[5]) { sp_set_error("commit_aux_program: an auxiliary column's denominator is zero on some row"); return SP_E_ZERO_INVERSE; }
+    if (host_flags().auxp_zero_den) { sp_set_error("commit_aux_program: an auxiliary column's denominator is zero on some row"); return SP_E_ZERO_INVERSE; }
     return SP_OK;
 }
 
@@ -1007,7 +543,7 @@ int StarkProver::composition_precheck(const fe rap[3], const std::vector<Boundar
     const bool sub_coset = logb_ >= logG_ + 1, pair_path = !sub_coset && G_ > 1 && logb_ == logG_ && d_post_comp0_;
     if (!sub_coset && !pair_path) return SP_OK;
     SP_HIP_CHECK(hipSetDevice(c_->device));
-    if (!d_comp_consts_chk_) SP_TRY(alloc((void**)&d_comp_consts_chk_, sizeof(CompositionConsts)));
+    SP_TRY(grow(od_.comp_consts_chk, 1));
     if (!h_comp_chk_) h_comp_chk_.reset(new CompositionConsts());
     CompositionConsts& K = *h_comp_chk_;
     std::memset(&K, 0, composition_consts_bytes(1u << logb_));   // (the per-coset tables only as far as this proof's blowup factor reaches)
@@ -1020,9 +556,9 @@ int StarkProver::composition_precheck(const fe rap[3], const std::vector<Boundar
     K.two = fe_from_u64(2);
     K.b15 = fe_from_u64(1ULL << 15); K.b16 = fe_from_u64(1ULL << 16); K.b32 = fe_from_u64(1ULL << 32); K.b48 = fe_from_u64(1ULL << 48);
     K.n_boundary = B; K.n_transitions = n_transitions; K.main_cols = Cm_; K.has_rc_builtin = has_rc_ ? 1 : 0;
-    SP_HIP_CHECK(hipMemcpyAsync(d_comp_consts_chk_, &K, composition_consts_bytes(1u << logb_), hipMemcpyHostToDevice, c_->stream));
+    SP_HIP_CHECK(hipMemcpyAsync(od_.comp_consts_chk.p, &K, composition_consts_bytes(1u << logb_), hipMemcpyHostToDevice, c_->stream));
     SP_HIP_CHECK(hipMemsetAsync(c_->d_flag, 0, sizeof(int), c_->stream));
-    SP_TRY(cairo_trace_check(c_->stream, d_trace_, n_, d_comp_consts_chk_, c_->d_flag, check_row0(), check_rows()));
+    SP_TRY(cairo_trace_check(c_->stream, d_trace_, n_, od_.comp_consts_chk.p, c_->d_flag, check_row0(), check_rows()));
     check_pending_ = true;
     return SP_OK;
 }
@@ -1184,14 +720,11 @@ int StarkProver::composition_air(const AirDescHost& air, const std::vector<fe>& 
     }
     deg_bound = std::max<uint64_t>(deg_bound, (n_ - 1) + n_ * (f - 1));   // boundary terms
     const bool allow_sub = deg_bound <= 2 * n_;                            // deg H < 2n: 2n evaluations fix it
-    if (max_ex > ex_roots_cap_) {
-        SP_TRY(alloc((void**)&d_ex_roots_, sizeof(fe) * std::max<uint32_t>(max_ex, 64)));
-        ex_roots_cap_ = std::max<uint32_t>(max_ex, 64);
-    }
     if (max_ex) {
+        SP_TRY(grow(od_.ex_roots, std::max<uint32_t>(max_ex, 64)));
         std::vector<fe> er(max_ex);
         for (uint32_t j = 0; j < max_ex; ++j) er[j] = fe_pow_u64(g_, n_ - 1 - j);
-        SP_HIP_CHECK(hipMemcpyAsync(d_ex_roots_, er.data(), sizeof(fe) * max_ex, hipMemcpyHostToDevice, c_->stream));
+        SP_HIP_CHECK(hipMemcpyAsync(od_.ex_roots.p, er.data(), sizeof(fe) * max_ex, hipMemcpyHostToDevice, c_->stream));
         SP_HIP_CHECK(sp_stream_wait_polling(c_->stream));
     }
     // --- boundary constraints grouped by row (first appearance order): one factor (x - g^s) per distinct row
@@ -1218,16 +751,11 @@ int StarkProver::composition_air(const AirDescHost& air, const std::vector<fe>& 
                  o_consts = place(sizeof(fe) * (air.consts.size() + rap.size())), o_zf = place(sizeof(fe) * b),
                  o_coef = place(sizeof(fe) * b * nterm), o_bval = place(sizeof(fe) * B), o_gpt = place(sizeof(fe) * nd),
                  o_bstep = place(sizeof(uint64_t) * B), o_bcol = place(sizeof(uint32_t) * B), o_gend = place(sizeof(uint32_t) * nd);
-    if (at > air_buf_cap_) {
-        release(d_air_buf_, air_buf_cap_);
-        d_air_buf_ = nullptr; air_buf_cap_ = 0;
-        SP_TRY(alloc((void**)&d_air_buf_, at));
-        air_buf_cap_ = at;
-    }
+    SP_TRY(grow(od_.air_buf, at));
     std::vector<uint8_t>& up = h_air_up_;
     up.assign(at, 0);
     auto host_at = [&](size_t off) { return up.data() + off; };
-    auto dev_at = [&](size_t off) { return d_air_buf_ + off; };
+    auto dev_at = [&](size_t off) { return od_.air_buf.p + off; };
     prog.ops = reinterpret_cast<const AirOpDev*>(dev_at(o_ops));
     prog.consts = reinterpret_cast<const fe*>(dev_at(o_consts));
     std::memcpy(host_at(o_prog), &prog, sizeof(prog));
@@ -1265,7 +793,7 @@ int StarkProver::composition_air(const AirDescHost& air, const std::vector<fe>& 
         host_batch_inverse(zf);
         for (uint32_t c = 0; c < b; ++c) hzf[c] = zf[c];
     }
-    SP_HIP_CHECK(hipMemcpyAsync(d_air_buf_, up.data(), at, hipMemcpyHostToDevice, c_->stream));
+    SP_HIP_CHECK(hipMemcpyAsync(od_.air_buf.p, up.data(), at, hipMemcpyHostToDevice, c_->stream));
     AirCompTables tabs;
     tabs.h = h_; tabs.T = T; tabs.B = B; tabs.ndist = nd;
     tabs.zerofier = reinterpret_cast<const fe*>(dev_at(o_zf));
@@ -1276,7 +804,7 @@ int StarkProver::composition_air(const AirDescHost& air, const std::vector<fe>& 
     tabs.gpoint = reinterpret_cast<const fe*>(dev_at(o_gpt));
     tabs.gend = reinterpret_cast<const uint32_t*>(dev_at(o_gend));
     offsets_ = air.offsets;
-    return composition_core(nullptr, points, reinterpret_cast<const AirProgram*>(dev_at(o_prog)), &tabs, d_ex_roots_, allow_sub, root_out);
+    return composition_core(nullptr, points, reinterpret_cast<const AirProgram*>(dev_at(o_prog)), &tabs, od_.ex_roots.p, allow_sub, root_out);
 }
 
 // Shared second half of round 2.  Cairo (prog_dev == nullptr): K (per-coset coefficients, zerofier, boundary data) is complete and
@@ -1326,10 +854,10 @@ int StarkProver::composition_core(const CompositionConsts* K, const std::vector<
         else if (!prechecked) SP_TRY(cairo_trace_check(c_->stream, d_trace_, n_, d_comp_consts_, c_->d_flag, check_row0(), check_rows()));
         if (!prog_dev && world_ > 1 && n_ >= 256ull * world_) {
             // every rank checked its own n / world rows of the (replicated) trace: one flag per rank, combined everywhere
-            if (!d_flags_all_) SP_TRY(alloc((void**)&d_flags_all_, sizeof(int) * world_));
-            SP_TRY(all_gather(c_->d_flag, d_flags_all_, sizeof(int), true));
+            SP_TRY(grow(od_.flags_all, world_));
+            SP_TRY(all_gather(c_->d_flag, od_.flags_all.p, sizeof(int), true));
             std::vector<int> flags(world_, 0);
-            SP_HIP_CHECK(hipMemcpyAsync(flags.data(), d_flags_all_, sizeof(int) * world_, hipMemcpyDeviceToHost, c_->stream));
+            SP_HIP_CHECK(hipMemcpyAsync(flags.data(), od_.flags_all.p, sizeof(int) * world_, hipMemcpyDeviceToHost, c_->stream));
             SP_HIP_CHECK(sp_stream_wait_polling(c_->stream));  // (also: K is a stack object)
             for (int f : flags) flag |= f;
         } else {
@@ -1356,12 +884,12 @@ int StarkProver::composition_core(const CompositionConsts* K, const std::vector<
         bool pref = !prog_dev && bpre_valid_ && nd == bpre_points_.size();
         for (uint32_t j = 0; pref && j < nd; ++j) pref = fe_eq(points[j], bpre_points_[j]);
         if (nd && pref) {                         // computed beside round 1 (prefetch_boundary_inverses)
-            binv = d_bpre_;
+            binv = od_.bpre.p;
             SP_HIP_CHECK(hipStreamWaitEvent(c_->stream, ev_side_bnd_, 0));
         } else {
             SP_TRY(boundary_inverses(binv, inv_scratch, M, logn_ + 1, roots_m, hp, ShardMap{0, 0, 0}));
         }
-        if (nd && pref) SP_HIP_CHECK(hipMemcpyAsync(&flag_pref, d_flag_side_ + 1, sizeof(int), hipMemcpyDeviceToHost, c_->stream));
+        if (nd && pref) SP_HIP_CHECK(hipMemcpyAsync(&flag_pref, side_flag(SIDE_BND_INV), sizeof(int), hipMemcpyDeviceToHost, c_->stream));
         fe* comp2 = d_h12s_;                      // [2n] evaluations H(h w_2n^i), then [H1s | H2s]
         SP_TRY(evaluate(M, logb_ - logG_ - 1, binv, comp2));
         SP_HIP_CHECK(hipMemcpyAsync(&flag, c_->d_flag, sizeof(int), hipMemcpyDeviceToHost, c_->stream));
@@ -1379,12 +907,12 @@ int StarkProver::composition_core(const CompositionConsts* K, const std::vector<
         SP_TRY(evaluate(Nl_, 0, binv, d_local_));                   // H on this rank's coset
         SP_HIP_CHECK(hipMemcpyAsync(&flag, c_->d_flag, sizeof(int), hipMemcpyDeviceToHost, c_->stream));
         SP_TRY(ensure_gather((uint64_t)world_ * Nl_));
-        SP_TRY(all_gather(d_local_, d_gather_, Nl_ * sizeof(fe), true));
+        SP_TRY(all_gather(d_local_, od_.gather.p, Nl_ * sizeof(fe), true));
         pair_flag_pending = true;                                    // (checked behind the commitment's read-back, which waits for the stream)
         const uint32_t other = G_ >> 1;                              // the rank that holds coset b/2
-        if (other != 1) SP_HIP_CHECK(hipMemcpyAsync(d_gather_ + n_, d_gather_ + (uint64_t)other * n_, n_ * sizeof(fe), hipMemcpyDeviceToDevice, c_->stream));
+        if (other != 1) SP_HIP_CHECK(hipMemcpyAsync(od_.gather.p + n_, od_.gather.p + (uint64_t)other * n_, n_ * sizeof(fe), hipMemcpyDeviceToDevice, c_->stream));
         fe* comp2 = d_h12s_;                                         // H(h w_2n^i): even i from coset 0, odd i from coset b/2
-        SP_TRY(interleave_shards(c_->stream, d_gather_, comp2, n_, ShardMap{1, 1, 0}));
+        SP_TRY(interleave_shards(c_->stream, od_.gather.p, comp2, n_, ShardMap{1, 1, 0}));
         SP_TRY(c_->ntt->dif_natural_to_bitrev_inverse(comp2, (int)logn_ + 1, 1, 2 * n_, d_post_comp0_));   // post factors of c0 = 0
         h_full_ = false;
         SP_TRY(c_->ntt->lde_coset_major(d_h12s_, d_h12_, (int)logn_, (int)logb_, 2, n_, Nl_, (int)logG_, (int)rank_));
@@ -1397,8 +925,8 @@ int StarkProver::composition_core(const CompositionConsts* K, const std::vector<
         SP_TRY(evaluate(Nl_, 0, binv, comp_local));
         if (G_ > 1) {  // composition-polynomial reduction: all-gather the per-coset evaluations
             SP_TRY(ensure_gather((uint64_t)world_ * Nl_));
-            SP_TRY(all_gather(comp_local, d_gather_, Nl_ * sizeof(fe), true));
-            SP_TRY(interleave_shards(c_->stream, d_gather_, comp, n_, shard_map()));
+            SP_TRY(all_gather(comp_local, od_.gather.p, Nl_ * sizeof(fe), true));
+            SP_TRY(interleave_shards(c_->stream, od_.gather.p, comp, n_, shard_map()));
         }
         // --- interpolate_offset_fft + even/odd split (reference evaluation_table.rs:27-33, prover.rs:250-252)
         SP_TRY(c_->ntt->dif_natural_to_bitrev_inverse(comp, (int)logN_, 1, N_, nullptr));
@@ -1415,16 +943,16 @@ int StarkProver::composition_core(const CompositionConsts* K, const std::vector<
         } else {
             // the trace violates its constraints: deg H >= 2n and the reference still proves it (longer H1, H2).  Every rank
             // holds all of H, evaluates H1, H2 on the whole domain and keeps the points of its own cosets.
-            if (!d_hfull_) SP_TRY(alloc((void**)&d_hfull_, sizeof(fe) * N_));
+            SP_TRY(grow(od_.hfull, N_));
             fe* t_half = d_scratch_;  // N/2 entries: N^-1 h^(-rev_{N/2}(q))
             if ((N_ >> 1) > scratch_elems()) { sp_set_error("composition: scratch too small"); return SP_E_ALLOC; }
             fe Ninv = fe_inv(fe_from_u64(N_));
             SP_TRY(gen_power_table(c_->stream, t_half, N_ >> 1, logN_ - 1, hinv_, Ninv));
-            SP_TRY(split_composition_full(c_->stream, comp, N_, t_half, hinv_, d_hfull_, d_hfull_ + (N_ >> 1)));
+            SP_TRY(split_composition_full(c_->stream, comp, N_, t_half, hinv_, od_.hfull.p, od_.hfull.p + (N_ >> 1)));
             // H1, H2 of N/2 coefficients each: natural-order evaluations first, then into the coset-major order of every other column
-            if (!d_hnat_) SP_TRY(alloc((void**)&d_hnat_, sizeof(fe) * N_ * 2));
-            SP_TRY(c_->ntt->lde_from_bitrev(d_hfull_, d_hnat_, (int)logN_ - 1, 1, 2, N_ >> 1, N_));
-            SP_TRY(natural_to_coset_major(c_->stream, d_hnat_, N_, d_h12_, Nl_, 2, lde_order(), logG_, rank_));
+            SP_TRY(grow(od_.hnat, 2 * N_));
+            SP_TRY(c_->ntt->lde_from_bitrev(od_.hfull.p, od_.hnat.p, (int)logN_ - 1, 1, 2, N_ >> 1, N_));
+            SP_TRY(natural_to_coset_major(c_->stream, od_.hnat.p, N_, d_h12_, Nl_, 2, lde_order(), logG_, rank_));
         }
     }
     bpre_valid_ = false;
@@ -1529,20 +1057,19 @@ int StarkProver::ood(const fe& z, fe* h1_z2, fe* h2_z2, std::vector<fe>& trace_o
     if (G_ > 1 && C_ >= G_) {
         // the polynomials are independent: role s evaluates the cpr columns from min(s cpr, C - cpr) on, the R values per column
         // are all-gathered (a few KB) - 1/G of the Horner-equivalent work per rank instead of all of it on every rank
-        const uint32_t cpr = (C_ + G_ - 1) / G_;
-        auto first_col = [&](uint32_t role) { return std::min(role * cpr, C_ - cpr); };
+        const uint32_t cpr = cols_per_role(C_);
         std::vector<fe> mine;
-        SP_TRY(eval_bitrev(c_, d_coeffs_ + (uint64_t)first_col(rank_) * n_, n_, cpr, logn_, ys, d_scratch_, scratch_elems(), mine, &prefetch));
+        SP_TRY(eval_bitrev(c_, d_coeffs_ + (uint64_t)role_first_col(rank_, C_) * n_, n_, cpr, logn_, ys, d_scratch_, scratch_elems(), mine, &prefetch));
         const size_t blk = (size_t)cpr * R;
         const size_t blk_cap = (size_t)C_ * AIR_MAX_OFFSETS;   // >= cpr * R: one block per rank
-        if (!d_small_) SP_TRY(alloc((void**)&d_small_, sizeof(fe) * (1 + (size_t)world_) * blk_cap));
-        SP_HIP_CHECK(hipMemcpyAsync(d_small_, mine.data(), blk * sizeof(fe), hipMemcpyHostToDevice, c_->stream));
-        SP_TRY(all_gather(d_small_, d_small_ + blk_cap, blk * sizeof(fe)));
+        SP_TRY(grow(od_.small, (1 + (uint64_t)world_) * blk_cap));
+        SP_HIP_CHECK(hipMemcpyAsync(od_.small.p, mine.data(), blk * sizeof(fe), hipMemcpyHostToDevice, c_->stream));
+        SP_TRY(all_gather(od_.small.p, od_.small.p + blk_cap, blk * sizeof(fe)));
         std::vector<fe> all(blk * world_);
-        SP_HIP_CHECK(hipMemcpy(all.data(), d_small_ + blk_cap, all.size() * sizeof(fe), hipMemcpyDeviceToHost));
+        SP_HIP_CHECK(hipMemcpy(all.data(), od_.small.p + blk_cap, all.size() * sizeof(fe), hipMemcpyDeviceToHost));
         tr.resize((size_t)C_ * R);
         for (uint32_t role = 0; role < G_; ++role)
-            std::copy(all.begin() + (size_t)role * blk, all.begin() + (size_t)(role + 1) * blk, tr.begin() + (size_t)first_col(role) * R);
+            std::copy(all.begin() + (size_t)role * blk, all.begin() + (size_t)(role + 1) * blk, tr.begin() + (size_t)role_first_col(role, C_) * R);
     } else {
         SP_TRY(eval_bitrev(c_, d_coeffs_, n_, C_, logn_, ys, d_scratch_, scratch_elems(), tr, &prefetch));
     }
@@ -1552,7 +1079,7 @@ int StarkProver::ood(const fe& z, fe* h1_z2, fe* h2_z2, std::vector<fe>& trace_o
     std::vector<fe> yh = {fe_mul(fe_sqr(z), hinv_)};
     std::vector<fe> hv;
     if (!h_full_) SP_TRY(eval_bitrev(c_, d_h12s_, n_, 2, logn_, yh, d_scratch_, scratch_elems(), hv));
-    else SP_TRY(eval_bitrev(c_, d_hfull_, N_ >> 1, 2, logN_ - 1, yh, d_scratch_, scratch_elems(), hv));
+    else SP_TRY(eval_bitrev(c_, od_.hfull.p, N_ >> 1, 2, logN_ - 1, yh, d_scratch_, scratch_elems(), hv));
     h1_z2_ = hv[0]; h2_z2_ = hv[1];
     *h1_z2 = hv[0]; *h2_z2 = hv[1];
     trace_ood_ = trace_ood;
@@ -1606,10 +1133,10 @@ int StarkProver::deep_fri_begin(const fe& gamma, const fe& gamma_p, const std::v
         fe* p0n = d_scratch_ + 2ull * npts * n_;               // [n]
         if ((2ull * npts + 1) * n_ > scratch_elems()) {   // many frame rows on a small blowup: the inverses outgrow the shared scratch
             SP_TRY(ensure_deep_scratch((2ull * npts + 1) * n_));
-            inv = d_deepx_; inv_scratch = inv + (uint64_t)npts * n_; p0n = inv + 2ull * npts * n_;
+            inv = od_.deepx.p; inv_scratch = inv + (uint64_t)npts * n_; p0n = inv + 2ull * npts * n_;
         }
-        if (deep_pref_ && d_deepx_ && deepx_cap_ >= (2ull * npts + 1) * n_) {   // computed beside round 3 (prefetch_deep_inverses)
-            inv = d_deepx_; p0n = inv + 2ull * npts * n_;
+        if (deep_pref_ && od_.deepx.cap >= (2ull * npts + 1) * n_) {   // computed beside round 3 (prefetch_deep_inverses)
+            inv = od_.deepx.p; p0n = inv + 2ull * npts * n_;
             SP_HIP_CHECK(hipStreamWaitEvent(c_->stream, ev_side_deep_, 0));
             used_pref = true;
         } else {
@@ -1633,7 +1160,7 @@ int StarkProver::deep_fri_begin(const fe& gamma, const fe& gamma_p, const std::v
         fe* inv = d_scratch_;
         if (2ull * npts * Nl_ > scratch_elems()) {   // more than two frame rows: the inverses outgrow the shared scratch
             SP_TRY(ensure_deep_scratch(2ull * npts * Nl_));
-            inv = d_deepx_;
+            inv = od_.deepx.p;
         }
         fe* inv_scratch = inv + (uint64_t)npts * Nl_;
         SP_TRY(coset_minus_points(c_->stream, inv, Nl_, logN_, roots, h_, pts, npts, shard_map()));
@@ -1642,8 +1169,8 @@ int StarkProver::deep_fri_begin(const fe& gamma, const fe& gamma_p, const std::v
         SP_TRY(deep_composition(c_->stream, d_lde_, d_h12_, d_h12_ + Nl_, Nl_, Nl_, 0, d_deep_consts_, d_deep_gammas_, inv, p0_local, lde_order(), R));
         if (G_ > 1 && !fri_sharded(0)) {
             SP_TRY(ensure_gather((uint64_t)world_ * Nl_));
-            SP_TRY(all_gather(p0_local, d_gather_, Nl_ * sizeof(fe), true));
-            SP_TRY(interleave_shards(c_->stream, d_gather_, d_fri_evals_[0], n_, shard_map()));
+            SP_TRY(all_gather(p0_local, od_.gather.p, Nl_ * sizeof(fe), true));
+            SP_TRY(interleave_shards(c_->stream, od_.gather.p, d_fri_evals_[0], n_, shard_map()));
         }
     }
     // FRI layer 0 (reference fri/mod.rs:27-33)
@@ -1651,7 +1178,7 @@ int StarkProver::deep_fri_begin(const fe& gamma, const fe& gamma_p, const std::v
     fri_offset_ = h_; fri_offset_inv_ = hinv_;
     int flag = 0, flag_pref = 0;
     SP_HIP_CHECK(hipMemcpyAsync(&flag, c_->d_flag, sizeof(int), hipMemcpyDeviceToHost, c_->stream));
-    if (used_pref) SP_HIP_CHECK(hipMemcpyAsync(&flag_pref, d_flag_side_, sizeof(int), hipMemcpyDeviceToHost, c_->stream));
+    if (used_pref) SP_HIP_CHECK(hipMemcpyAsync(&flag_pref, side_flag(SIDE_DEEP_INV), sizeof(int), hipMemcpyDeviceToHost, c_->stream));
     deep_pref_ = false;
     SP_TRY(commit_local(d_fri_evals_[0], 0, 1, fri_trees_[0].sub_leaves, LdeOrder{0, 0, 0}, fri_trees_[0], root0_out, true));   // synchronises
     flag |= flag_pref;
@@ -1677,8 +1204,8 @@ int StarkProver::fri_fold_commit(const fe& zeta, uint8_t root_out[32], fe* last_
         SP_TRY(fri_fold(c_->stream, d_fri_evals_[k], next_local, Ml, logN_, k, roots, half, cst, logG_, rank_));
         if (!fri_sharded(k + 1)) {   // from here on the layers are small: gather this one once and continue on every rank
             SP_TRY(ensure_gather((uint64_t)world_ * (Ml >> 1)));
-            SP_TRY(all_gather(next_local, d_gather_, (Ml >> 1) * sizeof(fe), true));
-            SP_TRY(interleave_shards(c_->stream, d_gather_, d_fri_evals_[k + 1], (Ml >> 1), ShardMap{logG_, logG_, 0}));
+            SP_TRY(all_gather(next_local, od_.gather.p, (Ml >> 1) * sizeof(fe), true));
+            SP_TRY(interleave_shards(c_->stream, od_.gather.p, d_fri_evals_[k + 1], (Ml >> 1), ShardMap{logG_, logG_, 0}));
         }
     } else {
         SP_TRY(fri_fold(c_->stream, d_fri_evals_[k], d_fri_evals_[k + 1], M, logN_, k, roots, half, cst));
@@ -1710,12 +1237,9 @@ int StarkProver::fri_commit_chain(const fe& zeta0, const uint8_t state32[32], st
     const fe* roots = nullptr;
     SP_TRY(c_->ntt->roots((int)logN_, &roots));
     const uint32_t L = logn_;
-    if (!d_fri_chain_ || fri_chain_layers_ < L) {
-        SP_TRY(alloc((void**)&d_fri_chain_, 32 + (size_t)L * 96));
-        fri_chain_layers_ = L;
-    }
-    uint64_t* d_state = reinterpret_cast<uint64_t*>(d_fri_chain_);
-    fe* d_cmul = reinterpret_cast<fe*>(d_fri_chain_ + 32);
+    SP_TRY(grow(od_.fri_chain, 32 + (size_t)L * 96));
+    uint64_t* d_state = reinterpret_cast<uint64_t*>(od_.fri_chain.p);
+    fe* d_cmul = reinterpret_cast<fe*>(od_.fri_chain.p + 32);
     fe* d_cst = d_cmul + L;
     uint64_t* d_roots = reinterpret_cast<uint64_t*>(d_cst + L);
     // constants half / offset_k of every layer (offset_k = h^(2^k)) and the transcript state, in one upload
@@ -1725,7 +1249,7 @@ int StarkProver::fri_commit_chain(const fe& zeta0, const uint8_t state32[32], st
     const uint32_t k0 = fri_layer_ - 1;           // the layer to fold first (0 on one GPU; the first replicated layer otherwise)
     fe oi = fri_offset_inv_;
     for (uint32_t k = k0; k < L; ++k) { const fe c = fe_mul(half_, oi); std::memcpy(up.data() + 32 + (size_t)k * 32, &c, 32); oi = fe_sqr(oi); }
-    SP_HIP_CHECK(hipMemcpyAsync(d_fri_chain_, up.data(), up.size(), hipMemcpyHostToDevice, c_->stream));
+    SP_HIP_CHECK(hipMemcpyAsync(od_.fri_chain.p, up.data(), up.size(), hipMemcpyHostToDevice, c_->stream));
     const fe cst0 = fe_mul(fe_mul(zeta0, half_), fri_offset_inv_);
     for (uint32_t k = k0; k < L; ++k) {           // fold layer k into layer k + 1 and commit it
         const uint64_t M = N_ >> k;
@@ -1740,8 +1264,8 @@ int StarkProver::fri_commit_chain(const fe& zeta0, const uint8_t state32[32], st
             SP_TRY(fri_fold(c_->stream, d_fri_evals_[k], next_local, Ml, logN_, k, roots, half_, cst0, logG_, rank_, c_dev));
             if (!sharded_k1) {   // from here on the layers are small: gathered once, continued on every rank
                 SP_TRY(ensure_gather((uint64_t)world_ * (Ml >> 1)));
-                SP_TRY(all_gather(next_local, d_gather_, (Ml >> 1) * sizeof(fe), true));
-                SP_TRY(interleave_shards(c_->stream, d_gather_, d_fri_evals_[k + 1], (Ml >> 1), ShardMap{logG_, logG_, 0}));
+                SP_TRY(all_gather(next_local, od_.gather.p, (Ml >> 1) * sizeof(fe), true));
+                SP_TRY(interleave_shards(c_->stream, od_.gather.p, d_fri_evals_[k + 1], (Ml >> 1), ShardMap{logG_, logG_, 0}));
             }
         } else if (fuse) {
             SP_TRY(fri_fold_hash(c_->stream, d_fri_evals_[k], d_fri_evals_[k + 1], M, logN_, k, roots, half_, cst0, c_dev,
@@ -1871,10 +1395,10 @@ int StarkProver::open(const std::vector<uint64_t>& iotas, Openings& o, bool valu
     const size_t job_bytes = (jobs.size() * sizeof(GatherJob) + 255) & ~size_t(255);
     const size_t blk_bytes = items * 32;
     const size_t need = idx_bytes + job_bytes + blk_bytes * (G_ > 1 ? 1 + (size_t)world_ : 1);
-    struct Tmp { void* p = nullptr; ~Tmp() { if (p) (void)hipFree(p); } } tmp;   // many queries on a tiny domain: own staging buffer
+    ScopedDevAlloc tmp(st);                  // many queries on a tiny domain: own staging buffer
     uint8_t* base = reinterpret_cast<uint8_t*>(d_scratch_);
     if (need > scratch_elems() * sizeof(fe)) {
-        if (hipMalloc(&tmp.p, need) != hipSuccess) { sp_set_error("open: staging allocation failed"); return SP_E_ALLOC; }
+        SP_TRY(tmp.alloc(need, "open"));
         base = static_cast<uint8_t*>(tmp.p);
     }
     uint64_t* d_idx = reinterpret_cast<uint64_t*>(base);
@@ -1890,19 +1414,13 @@ int StarkProver::open(const std::vector<uint64_t>& iotas, Openings& o, bool valu
     if (values_canonical_be) SP_TRY(encode_elements(st, SP_FE_CANON_BE, blk, value_items, reinterpret_cast<uint8_t*>(blk)));   // in place, element by element
     // the download lands in a page-locked buffer kept across proofs (a pageable destination is staged by the runtime: ~2 MB per proof)
     const size_t host_items = items * (G_ > 1 ? world_ : 1);
-    if (h_open_cap_ < host_items * sizeof(fe)) {
-        if (h_open_pin_) (void)hipHostFree(h_open_pin_);
-        h_open_pin_ = nullptr; h_open_cap_ = 0;
-        const size_t cap = host_items * sizeof(fe) + (host_items * sizeof(fe)) / 4;
-        if (hipHostMalloc(&h_open_pin_, cap, hipHostMallocDefault) != hipSuccess) { h_open_pin_ = nullptr; (void)hipGetLastError(); sp_set_error("open: page-locked download buffer: allocation failed"); return SP_E_ALLOC; }
-        h_open_cap_ = cap;
-    }
-    const fe* host = static_cast<const fe*>(h_open_pin_);
+    SP_TRY(h_open_pin_.ensure(host_items * sizeof(fe), "open: page-locked download buffer", (host_items * sizeof(fe)) / 4));
+    const fe* host = static_cast<const fe*>(h_open_pin_.p);
     if (G_ > 1) {
         SP_TRY(all_gather(blk, all_dev, blk_bytes, true));
-        SP_HIP_CHECK(hipMemcpyAsync(h_open_pin_, all_dev, host_items * sizeof(fe), hipMemcpyDeviceToHost, st));
+        SP_HIP_CHECK(hipMemcpyAsync(h_open_pin_.p, all_dev, host_items * sizeof(fe), hipMemcpyDeviceToHost, st));
     } else {
-        SP_HIP_CHECK(hipMemcpyAsync(h_open_pin_, blk, host_items * sizeof(fe), hipMemcpyDeviceToHost, st));
+        SP_HIP_CHECK(hipMemcpyAsync(h_open_pin_.p, blk, host_items * sizeof(fe), hipMemcpyDeviceToHost, st));
     }
     SP_HIP_CHECK(sp_stream_wait_polling(st));   // (hidx is a local)
     auto slot = [&](uint32_t owner) -> const fe* { return host + (G_ > 1 ? (size_t)owner * items : 0); };

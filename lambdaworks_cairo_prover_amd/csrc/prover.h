@@ -34,6 +34,37 @@ struct Openings {
 
 class HostPool;   // prover.cpp: parked host threads for the upload pipeline
 
+// Device memory that setup() does not carve: allocated on first use or grown on demand by StarkProver::grow, `cap` elements of T.
+template <class T> struct DevBuf { T* p = nullptr; uint64_t cap = 0; };
+// Page-locked host memory, kept until the prover goes.  ensure() sets "<what>: allocation failed" and returns SP_E_ALLOC.
+struct PinnedBuf {
+    void* p = nullptr; size_t bytes = 0;
+    PinnedBuf() = default; PinnedBuf(const PinnedBuf&) = delete; PinnedBuf& operator=(const PinnedBuf&) = delete;
+    ~PinnedBuf() { if (p) (void)hipHostFree(p); }
+    int ensure(size_t need, const char* what, size_t headroom = 0) {   // (headroom: extra bytes when it has to be allocated anew)
+        if (need <= bytes) return SP_OK;
+        if (p) { (void)hipHostFree(p); p = nullptr; bytes = 0; }
+        if (hipHostMalloc(&p, need + headroom, hipHostMallocDefault) != hipSuccess) { p = nullptr; (void)hipGetLastError(); sp_set_error(std::string(what) + ": allocation failed"); return SP_E_ALLOC; }
+        bytes = need + headroom;
+        return SP_OK;
+    }
+};
+// A staging buffer of one call outside the arena (plain hipMalloc); freed once `st` has finished with it.
+struct ScopedDevAlloc {
+    void* p = nullptr; hipStream_t st;
+    explicit ScopedDevAlloc(hipStream_t stream) : st(stream) {}   ScopedDevAlloc(const ScopedDevAlloc&) = delete;
+    ~ScopedDevAlloc() { if (p) { (void)hipStreamSynchronize(st); (void)hipFree(p); } }
+    int alloc(size_t bytes, const char* who) {
+        if (hipMalloc(&p, bytes) == hipSuccess) return SP_OK;
+        p = nullptr; (void)hipGetLastError(); sp_set_error(std::string(who) + ": staging allocation failed"); return SP_E_ALLOC;
+    }
+};
+// The pinned flag slot (64 bytes): flags that ride to the host behind the work they belong to.  presort_malformed and presort_wide_key
+// stay adjacent and in the order of SIDE_PRESORT_MALFORMED, SIDE_PRESORT_WIDE_KEY: launch_aux_presort fills both with one copy.
+struct HostFlags { int presort_malformed, presort_wide_key, _pad[2], trace_build_oob, auxp_zero_den; };
+// flags of the side-stream work (device): DEEP inverses, boundary inverses, the presort's malformed input / key beyond its bits
+enum SideFlag { SIDE_DEEP_INV = 0, SIDE_BND_INV, SIDE_PRESORT_MALFORMED, SIDE_PRESORT_WIDE_KEY, SIDE_FLAGS };
+
 class StarkProver : public sp_deletable {
   public:
     StarkProver(sp_ctx* ctx) : c_(ctx) {}
@@ -108,12 +139,24 @@ class StarkProver : public sp_deletable {
     // subtree roots; root = top[0].
     struct TreeBuf { digest32* sub = nullptr; digest32* top = nullptr; uint64_t sub_leaves = 0; };
     void free_all();
+    // what the calls of one proof leave for each other: cleared by every setup()
+    void reset_proof_flags() { bpre_valid_ = deep_pref_ = check_pending_ = presorted_ = h_full_ = false; presort_pub_ = nullptr; }
     // small device -> host read-back on the compute stream through a pinned slot, waiting by polling the stream (a blocking
     // synchronisation costs ~20 us of wake-up per Fiat-Shamir round trip; a proof has ~35 of them)
     int readback(void* dst_host, const void* src_dev, size_t bytes);
     int wait_stream();
     int alloc(void** p, size_t bytes);
     void release(void* p, size_t bytes);
+    // The one grow path of the on-demand buffers: nothing to do while `elems` fit, otherwise the old block is released (release() waits
+    // for its readers; a first allocation waits for nothing) and a new one allocated.  *moved: what pointed into the old block is gone.
+    template <class T> int grow(DevBuf<T>& b, uint64_t elems, bool* moved = nullptr) {
+        if (moved) *moved = elems > b.cap;
+        if (elems <= b.cap) return SP_OK;
+        release(b.p, sizeof(T) * b.cap);   b = {};
+        SP_TRY(alloc(reinterpret_cast<void**>(&b.p), sizeof(T) * elems));
+        b.cap = elems;
+        return SP_OK;
+    }
     std::vector<uint8_t> h_up_fri_, h_up_open_;   // host sides of small asynchronous uploads (fri_commit_chain, open)
     std::vector<uint64_t> h_idx_open_;
     int alloc_tree(TreeBuf& t, uint64_t leaves_total, bool sharded);
@@ -140,7 +183,6 @@ class StarkProver : public sp_deletable {
     // src/cairo/air.rs:29-46: 47 % of the table): the row-major upload sends them as one bit per cell.  A hint, checked cell by cell by
     // the gather threads - a table that breaks it (an invalid trace) is uploaded again in full, so the bytes never depend on it.
     uint32_t binary_cols_hint_ = 0;
-    uint64_t* d_flagbits_ = nullptr; uint64_t flagbits_words_ = 0;
     static constexpr int SP_RETRY_RAW_UPLOAD = 1000;   // internal: the packed upload met a cell that is neither 0 nor 1
     // several ranks, row-major host table: every rank uploads the columns of its role only, the trace columns are all-gathered
     int commit_trace_rows_sharded(int segment, const uint8_t* rows_host, uint32_t cols, uint8_t root_out[32], uint32_t binary_cols = 0);
@@ -193,18 +235,36 @@ class StarkProver : public sp_deletable {
     uint64_t Nl_ = 0;
     fe* d_local_ = nullptr;    // [Nl] 32-byte items: local leaf digests (send side of the exchange)
     fe* d_recv_ = nullptr;     // [Nl] 32-byte items: the digests of this rank's contiguous leaf range, by source rank
-    fe* d_gather_ = nullptr; uint64_t gather_cap_ = 0;   // all-gather landing zone, grown on demand
     fe* d_cstage_ = nullptr; uint32_t cpr_max_ = 0;       // [world][cpr_max][n] coefficient all-gather (column-sharded interpolation)
     digest32* d_roots_ = nullptr;                          // [world] subtree roots
-    fe* d_small_ = nullptr;                                // out-of-domain values of this rank's columns and their all-gather
-    fe* d_fullN_ = nullptr;                                // [N] whole-domain scratch when FRI layer 0 is sharded (exceptional paths)
-    int* d_flags_all_ = nullptr;                           // [world] flags of the row-sharded trace check
+    // Every device buffer that is allocated on first use or grown on demand (grow()); free_all() resets the struct as a whole.
+    struct OnDemand {
+        DevBuf<fe> gather;                       // all-gather landing zone
+        DevBuf<fe> small;                        // out-of-domain values of this rank's columns and their all-gather
+        DevBuf<fe> fullN;                        // [N] whole-domain scratch when FRI layer 0 is sharded (exceptional paths)
+        DevBuf<int> flags_all;                   // [world] flags of the row-sharded trace check
+        DevBuf<fe> deepx;                        // DEEP inverses when they outgrow the shared scratch
+        DevBuf<uint64_t> flagbits;               // the 0 / 1 columns of a row-major upload as bitmaps (binary_cols_hint_)
+        DevBuf<CompositionConsts> comp_consts_chk;   // the constants of an early constraint check (composition_precheck)
+        DevBuf<uint8_t> air_buf; DevBuf<fe> ex_roots;   // program AIRs (composition_air): header, ops, constants and per-proof tables in one buffer; exempted rows' roots
+        // auxiliary programs (commit_aux_program): ops, constants and column tables of every chunk in one buffer, and the N / D
+        // workspace (denominators, batch-inversion scratch, scan block totals); kept across proofs of a shape
+        DevBuf<uint8_t> auxp_buf; DevBuf<fe> auxp_ws;
+        DevBuf<uint8_t> fri_chain;               // [state 32 B][L x constants][L x zeta constants][L x roots]
+        DevBuf<int> side_flags;                  // [SIDE_FLAGS]
+        DevBuf<fe> bpre;                         // [3][2n] boundary inverses + [3][2n] scratch
+        DevBuf<uint8_t> auxws;                   // workspace of the Cairo auxiliary trace, carved into auxws_ for auxws_pm_ public cells
+        DevBuf<fe> hfull, hnat;                  // general (degree >= 2n) composition polynomial: N/2 coefficients per half; its natural-order staging
+    } od_;
     // the slice of the trace rows this rank checks in round 2 (the Cairo constraint check is row-local: the trace is replicated)
     uint64_t check_row0() const { return (world_ > 1 && n_ >= 256ull * world_) ? (n_ / world_) * wrank_ : 0; }
     uint64_t check_rows() const { return (world_ > 1 && n_ >= 256ull * world_) ? (wrank_ + 1 == world_ ? n_ - (n_ / world_) * wrank_ : n_ / world_) : n_; }
-    int ensure_gather(uint64_t elems);
+    int ensure_gather(uint64_t elems) { return grow(od_.gather, elems); }
     int ensure_deep_scratch(uint64_t elems);
-    fe* d_deepx_ = nullptr; uint64_t deepx_cap_ = 0;   // DEEP inverses when they outgrow the shared scratch
+    // columns by role (several ranks): role r works on the cols_per_role columns from role_first_col on (the last blocks overlap
+    // instead of being ragged)
+    uint32_t cols_per_role(uint32_t cols) const { return (cols + G_ - 1) / G_; }
+    uint32_t role_first_col(uint32_t role, uint32_t cols) const { return std::min(role * cols_per_role(cols), cols - cols_per_role(cols)); }
     int full_domain_buffer(fe** out);
     // stream_ordered: the caller consumes the result on the compute stream only (or waits for that stream itself): with a transport
     // that can enqueue on a stream the exchange takes its place between the kernels instead of costing a host round trip
@@ -218,6 +278,8 @@ class StarkProver : public sp_deletable {
     bool comm_async() const { return c_->allgather_async != nullptr; }
     int all_gather_begin(const void* send_dev, void* recv_dev, uint64_t bytes_per_rank, int slot);
     int all_gather_end(int slot);
+    void count_all_gather(uint64_t bytes_per_rank) { c_->stat_ag_calls += 1; c_->stat_ag_bytes += bytes_per_rank; c_->stat_recv_bytes += bytes_per_rank * (world_ - 1); }
+    void count_all_to_all(uint64_t bytes) { c_->stat_a2a_calls += 1; c_->stat_a2a_bytes += bytes * (G_ - 1); c_->stat_recv_bytes += bytes * (G_ - 1); }
     // recv[s] = the block rank s addressed to this role: send = [G][bytes], recv = [G][bytes]
     int exchange_blocks(const void* send_dev, void* recv_dev, uint64_t bytes_per_block, bool stream_ordered = false);
     ShardMap shard_map() const { return ShardMap{logb_, logG_, rank_}; }
@@ -246,24 +308,19 @@ class StarkProver : public sp_deletable {
     fe fri_offset_, fri_offset_inv_;        // h^(2^layer) and its inverse
     fe half_, binv_;                        // 1/2, 1/blowup
     CompositionConsts* d_comp_consts_ = nullptr;
-    CompositionConsts* d_comp_consts_chk_ = nullptr;   // the constants of an early constraint check (composition_precheck)
-    std::unique_ptr<CompositionConsts> h_comp_chk_;    // its host copy (stays put until the upload has happened)
+    std::unique_ptr<CompositionConsts> h_comp_chk_;    // host copy of od_.comp_consts_chk (stays put until the upload has happened)
     bool check_pending_ = false;
-    // program AIRs: header, ops, constants and per-proof tables in one buffer (composition_air), grown on demand
-    uint8_t* d_air_buf_ = nullptr; size_t air_buf_cap_ = 0; std::vector<uint8_t> h_air_up_;
-    fe* d_ex_roots_ = nullptr; uint32_t ex_roots_cap_ = 0;
-    // auxiliary programs (commit_aux_program): ops, constants and column tables of every chunk in one buffer, and the N / D
-    // workspace (denominators, batch-inversion scratch, scan block totals); both grown on demand and kept across proofs of a shape
-    uint8_t* d_auxp_buf_ = nullptr; size_t auxp_buf_cap_ = 0; std::vector<uint8_t> h_auxp_up_;
-    fe* d_auxp_ws_ = nullptr; uint64_t auxp_ws_cap_ = 0;
+    std::vector<uint8_t> h_air_up_, h_auxp_up_;        // host sides of the uploads into od_.air_buf and od_.auxp_buf
     DeepConsts* d_deep_consts_ = nullptr;
     fe* d_deep_gammas_ = nullptr;                      // [AIR_MAX_OFFSETS][C], behind the DeepConsts in the same allocation
     static size_t deep_gammas_at() { return (sizeof(DeepConsts) + 255) & ~size_t(255); }
     unsigned long long* d_nonce_ = nullptr;
-    uint8_t* d_fri_chain_ = nullptr; uint32_t fri_chain_layers_ = 0;   // [state 32 B][L x constants][L x zeta constants][L x roots]
-    void* h_pin_ = nullptr;   // 4 KB of pinned host memory for readback()
-    void* h_open_pin_ = nullptr; size_t h_open_cap_ = 0;   // page-locked landing zone of the openings' download (kept across proofs)
-    int* h_wide_ = nullptr;   // pinned: the presort's "wide address" flag, copied behind the sorts on the side stream
+    PinnedBuf h_pin_;         // 4 KB for readback()
+    PinnedBuf h_open_pin_;    // landing zone of the openings' download (kept across proofs)
+    PinnedBuf h_flags_;       // HostFlags
+    int ensure_pin() { return h_pin_.ensure(4096, "pinned read-back slot"); }
+    int ensure_host_flags() { return h_flags_.ensure(64, "pinned flag slot"); }
+    HostFlags& host_flags() { return *static_cast<HostFlags*>(h_flags_.p); }
     // Side stream: latency-bound work that does not wait for the next challenge runs beside the compute stream instead of in
     // its way - a batch inversion is one chain of ~260 dependent field products (~0.3 ms whatever the size).
     //   * boundary denominators 1 / (x - g^step) of round 2 (shape and public inputs only): during round 1;
@@ -271,12 +328,12 @@ class StarkProver : public sp_deletable {
     //   * the range-check half of the Cairo auxiliary trace beside its memory half.
     hipStream_t side_stream_ = nullptr;
     hipEvent_t ev_side_fork_ = nullptr, ev_side_deep_ = nullptr, ev_side_bnd_ = nullptr, ev_side_aux_ = nullptr;
-    int* d_flag_side_ = nullptr;            // [4] flags of the side-stream work: DEEP inverses, boundary inverses, presort
     int ensure_side();
+    int ensure_side_flags() { return grow(od_.side_flags, SIDE_FLAGS); }
+    int* side_flag(SideFlag f) { return od_.side_flags.p + f; }
     int prefetch_deep_inverses();           // from ood(): z_ is set
     bool deep_pref_ = false;
-    fe* d_bpre_ = nullptr; uint64_t bpre_cap_ = 0;   // [3][2n] boundary inverses + [3][2n] scratch
-    std::vector<fe> bpre_points_; bool bpre_valid_ = false;
+    std::vector<fe> bpre_points_; bool bpre_valid_ = false;   // od_.bpre holds the inverses for these points
     // the challenge-free part of the Cairo auxiliary trace (sorts) beside round 1's transforms and hashing
     const PublicInputs* presort_pub_ = nullptr; bool presorted_ = false;
     hipEvent_t ev_side_presort_ = nullptr;
@@ -293,10 +350,8 @@ class StarkProver : public sp_deletable {
     void hint_binary_columns(uint32_t count) { binary_cols_hint_ = count; }
   private:
     fe* d_memcols_ = nullptr;               // natural-order main-trace columns 19..29 kept for the auxiliary trace
-    void* d_auxws_ = nullptr; size_t auxws_bytes_ = 0; uint64_t auxws_pm_cap_ = 0;
-    AuxWorkspace auxws_{};
-    fe* d_hfull_ = nullptr; bool h_full_ = false;  // general (degree >= 2n) composition polynomial: N/2 coefficients per half
-    fe* d_hnat_ = nullptr;    // natural-order staging of the same (exceptional path)
+    AuxWorkspace auxws_{}; uint64_t auxws_pm_ = 0;
+    bool h_full_ = false;     // the composition polynomial of this proof has degree >= 2n: its halves are in od_.hfull
     fe* d_post_comp_ = nullptr; fe* d_post_deep_ = nullptr;   // shape-only post-factor tables (setup)
     fe* d_post_comp0_ = nullptr;                               // the same for c0 = 0 (one coset per rank)
     fe z_; fe h1_z2_, h2_z2_;

@@ -1,4 +1,4 @@
-// Helpers shared by the translation units of the prover (prover.cpp, prover_upload.cpp, prover_driver.cpp).
+// Helpers shared by the translation units of the prover (prover.cpp, prover_setup.cpp, prover_upload.cpp, prover_driver.cpp).
 #pragma once
 #include "prover.h"
 #include <chrono>

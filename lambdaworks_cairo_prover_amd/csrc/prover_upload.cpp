@@ -481,7 +481,7 @@ int StarkProver::commit_trace_pipelined(int segment, const uint8_t* rows_host, u
     struct Chunk { uint32_t g, c, cw, slot; uint64_t r0, rows, first_block, blocks; bool last_of_group, packed; };
     if (binary_cols) {
         const uint64_t words = (uint64_t)binary_cols * (n_ >> 6);
-        if (flagbits_words_ < words) { SP_TRY(alloc((void**)&d_flagbits_, words * 8)); flagbits_words_ = words; }
+        SP_TRY(grow(od_.flagbits, words));
     }
     uint64_t zero_img[4] = {0, 0, 0, 0}, one_img[4] = {0, 0, 0, 0};      // 0 and 1 as the table encodes them
     {
@@ -555,7 +555,7 @@ int StarkProver::commit_trace_pipelined(int segment, const uint8_t* rows_host, u
                 uint8_t* slot = static_cast<uint8_t*>(h_stage_[ck.slot]);
                 if (ck.packed) {
                     for (uint32_t j = 0; j < ck.cw; ++j)   // a column's bits of this chunk: rows / 8 bytes
-                        SP_HIP_CHECK(hipMemcpyAsync(d_flagbits_ + ((uint64_t)(ck.c + j) * n_ + ck.r0) / 64, slot + (size_t)j * (ck.rows / 8), (size_t)ck.rows / 8,
+                        SP_HIP_CHECK(hipMemcpyAsync(od_.flagbits.p + ((uint64_t)(ck.c + j) * n_ + ck.r0) / 64, slot + (size_t)j * (ck.rows / 8), (size_t)ck.rows / 8,
                                                     hipMemcpyHostToDevice, copy_stream_));
                 } else
                 for (uint32_t j = 0; j < ck.cw; ++j)   // column by column, straight into the trace area (host encoding; decoded in place below)
@@ -570,7 +570,7 @@ int StarkProver::commit_trace_pipelined(int segment, const uint8_t* rows_host, u
                     // host encoding -> device layout, in place, in front of the group's transforms on the compute stream (an ordinary
                     // kernel of the proof: the rows -> columns kernels this replaces ran on a highest-priority stream beside the
                     // transforms and made those 1.3 - 2.2 x slower for as long as the upload lasted - tools/upload_interference.py)
-                    if (ck.packed) SP_TRY(expand_bit_columns(c_->stream, d_flagbits_ + (uint64_t)gc0 * (n_ >> 6), n_, w, trace + (uint64_t)gc0 * n_));
+                    if (ck.packed) SP_TRY(expand_bit_columns(c_->stream, od_.flagbits.p + (uint64_t)gc0 * (n_ >> 6), n_, w, trace + (uint64_t)gc0 * n_));
                     else
                     SP_TRY(decode_elements(c_->stream, c_->enc, reinterpret_cast<const uint8_t*>(trace + (uint64_t)gc0 * n_), (uint64_t)w * n_, trace + (uint64_t)gc0 * n_));
                     if (!window_only) {
