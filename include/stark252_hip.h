@@ -74,7 +74,8 @@ const char* sp_version(void);
  * layout, an entry point or option key is added, or a call changes meaning (4: round 5's sp_comm_measure / sp_comm_time_ms /
  * sp_proof_options_* / sp_proof_file_verify / SP_OPT_HOST_RANKS family and sp_set_collective keeping the prover across re-installs
  * of the same world; 5: sp_fe_mul; 6: sp_air_limits, sp_air_prove beyond 64 columns and 3 boundary rows; 7: sp_air_prove_aux, sp_air_aux_desc,
- * sp_air_aux_desc_size).  A binding compares it (and sp_air_desc_size against its own idea of the struct) when it loads the library, so
+ * sp_air_aux_desc_size, sp_air_prove_periodic, sp_air_verify_periodic, sp_air_periodic_desc_size, sp_air_periodic_limits,
+ * sp_air_periodic_eval, sp_air_periodic_lde).  A binding compares it (and sp_air_desc_size against its own idea of the struct) when it loads the library, so
  * a stale build fails at load time with "rebuild the library" instead of with a missing symbol or shifted fields later. */
 #define SP_ABI_VERSION 7
 int sp_abi_version(void);
@@ -398,6 +399,7 @@ int sp_last_round_ms(sp_ctx* ctx, float out[5]);
  *   op 1 CONST a = index into consts; indices >= n_consts are the RAP challenges   -> value
  *   op 2 ADD, 3 SUB, 4 MUL   a, b = indices of earlier ops                          -> value
  *   op 5 OUT   a = constraint index, b = index of the op holding its value
+ *   op 6 PERIODIC  a = frame row, b = periodic column                                -> value  (sp_air_prove_periodic only, see below)
  * The reference's examples (src/starks/example/{simple_fibonacci,fibonacci_2_columns,quadratic_air,fibonacci_rap,
  * dummy_air}.rs) are given in this form by lambdaworks_cairo_prover_amd/air.py. */
 typedef struct { uint8_t op; uint8_t pad; uint16_t a; uint16_t b; uint16_t pad2; } sp_air_op;
@@ -456,6 +458,39 @@ typedef struct {
 int sp_air_prove_aux(sp_ctx* ctx, const sp_air_desc* air, const sp_air_aux_desc* aux, const uint8_t* main_trace, uint64_t n,
                      const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len);
 uint64_t sp_air_aux_desc_size(void);
+
+/* Periodic columns (NO reference counterpart: the reference's `AIR` trait has none): public sequences of `period` values that repeat
+ * down the trace - round constants, every-k-th-row selectors, builtin schedules.  period is a power of two, 1 <= period <= n.  With g
+ * the trace-domain generator and w_p = g^(n/period), q is the polynomial of degree < period with q(w_p^j) = values[j]; the column's
+ * polynomial is P(x) = q(x^(n/period)), so P(g^i) = values[i mod period] and deg P < n.  A constraint program reads it with
+ *   op 6 PERIODIC  a = frame row (index into `offsets`), b = periodic column index   -> value  P at that frame row's point
+ * In a constraint's declared degree a periodic value counts as a trace cell does (one factor of degree < n): the degree adjustments of
+ * the composition polynomial do not change.  The columns are NOT committed and do not enter the transcript, the proof format is
+ * unchanged: like the program's constants they are part of the statement prover and verifier both hold.  sp_air_prove,
+ * sp_air_prove_aux, sp_air_verify and sp_air_verify_backend answer a program that contains op 6 as they answer any unknown op
+ * (SP_E_INVALID_ARG / 0); an auxiliary program (sp_air_aux_desc) cannot read periodic columns and is refused the same way. */
+#define SP_AIR_OP_PERIODIC 6
+typedef struct { uint32_t period, pad; const uint8_t* values; /* period x 32, canonical BE */ } sp_air_periodic_column;
+typedef struct { uint32_t n_cols, pad; const sp_air_periodic_column* cols; } sp_air_periodic_desc;
+uint64_t sp_air_periodic_desc_size(void);
+/* out = {periodic columns at most (64), 0, 0, 0 (reserved)}; a period is a power of two with 1 <= period <= n. */
+int sp_air_periodic_limits(uint32_t out[4]);
+/* sp_air_prove (aux == NULL) or sp_air_prove_aux (aux != NULL, air->aux_kind == SP_AIR_AUX_PROGRAM) for an AIR whose constraint
+ * program reads the periodic columns of `periodic` (n_cols 0 .. 64).  The device holds period x blowup evaluations per column (every
+ * rank of a sharded context all of them).  SP_E_INVALID_ARG for a period that is no power of two or exceeds n, null values, more
+ * than 64 columns, an op 6 naming a column >= n_cols. */
+int sp_air_prove_periodic(sp_ctx* ctx, const sp_air_desc* air, const sp_air_aux_desc* aux, const sp_air_periodic_desc* periodic,
+                          const uint8_t* main_trace, uint64_t n, const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len);
+/* sp_air_verify_backend for such an AIR: 1 accept, 0 reject (also for the malformed descriptors above).  The verifier evaluates
+ * P_k(z g^offsets[r]) itself (sp_air_periodic_eval's routine). */
+int sp_air_verify_periodic(const uint8_t* proof, uint64_t proof_len, const sp_air_desc* air, const sp_air_periodic_desc* periodic,
+                           const sp_proof_options* opt, int merkle_backend);
+/* Test seams.  sp_air_periodic_eval (host): out = P(point) for a trace of n rows, canonical BE in and out - q interpolated from the
+ * values, evaluated at point^(n/period).  sp_air_periodic_lde (device): the table the composition kernel reads, in natural order:
+ * out[k] = P(coset w_N^k) for k < period x blowup (N = n x blowup; the evaluations repeat with that period), canonical BE.  n, blowup and
+ * the period are powers of two with blowup >= 2, n x blowup <= 2^30 and 1 <= period <= n (SP_E_INVALID_ARG otherwise), as a proof's are. */
+int sp_air_periodic_eval(const sp_air_periodic_column* col, uint64_t n, const uint8_t point[32], uint8_t out[32]);
+int sp_air_periodic_lde(sp_ctx* ctx, const sp_air_periodic_column* col, uint64_t n, uint32_t blowup, const uint8_t coset[32], uint8_t* out);
 
 /* verify::<Stark252PrimeField, A> (reference src/starks/verifier.rs:559-657) on the host CPU: 1 accept, 0 reject (also for
  * malformed proofs or descriptors). */

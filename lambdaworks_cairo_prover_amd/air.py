@@ -8,12 +8,16 @@ context (columns, transition offsets / degrees / exemptions), `compute_transitio
     b.constraint(r2 - r1 - r0, degree=1, exemptions=2)
     b.boundary(col=0, step=0, value=1); b.boundary(0, 1, 1)
     desc = b.build()
+
+Periodic columns (an extension beyond the reference's trait): AirBuilder(..., periodic=[values0, values1, ...]) declares public
+sequences that repeat down the trace (each a power-of-two number of values, at most the trace length); b.periodic(row, k) reads
+column k at frame row `row`.  In a constraint's declared degree such a value counts as a trace cell.  See mimc_chain below.
 """
 import ctypes
 
 P = 2**251 + 17 * 2**192 + 1
 
-OP_LOAD, OP_CONST, OP_ADD, OP_SUB, OP_MUL, OP_OUT = range(6)
+OP_LOAD, OP_CONST, OP_ADD, OP_SUB, OP_MUL, OP_OUT, OP_PERIODIC = range(7)
 MAX_OFFSETS, MAX_TRANSITIONS = 8, 64
 AUX_TRACE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint8))
 
@@ -71,6 +75,35 @@ def _check_aux_layout():
         raise ImportError(f"AirAuxDescC is {ctypes.sizeof(AirAuxDescC)} bytes, the library's sp_air_aux_desc {want}: the binding is out of date")
 
 
+class AirPeriodicColumnC(ctypes.Structure):
+    _fields_ = [("period", ctypes.c_uint32), ("pad", ctypes.c_uint32), ("values", ctypes.c_void_p)]
+
+
+class AirPeriodicDescC(ctypes.Structure):
+    _fields_ = [("n_cols", ctypes.c_uint32), ("pad", ctypes.c_uint32), ("cols", ctypes.POINTER(AirPeriodicColumnC))]
+
+
+def _check_periodic_layout():
+    from . import _lib
+    want = _lib.load().sp_air_periodic_desc_size()
+    if ctypes.sizeof(AirPeriodicDescC) != want:
+        raise ImportError(f"AirPeriodicDescC is {ctypes.sizeof(AirPeriodicDescC)} bytes, the library's sp_air_periodic_desc {want}: the binding is out of date")
+
+
+def periodic_desc(columns):
+    """[values0, values1, ...] (ints) -> (AirPeriodicDescC, keepalive): sp_air_periodic_desc, canonical big-endian values."""
+    _check_periodic_layout()
+    cols = (AirPeriodicColumnC * max(1, len(columns)))()
+    bufs = []
+    for k, values in enumerate(columns):
+        buf = ctypes.create_string_buffer(b"".join((int(v) % P).to_bytes(32, "big") for v in values), max(1, 32 * len(values)))
+        bufs.append(buf)
+        cols[k].period, cols[k].values = len(values), ctypes.cast(buf, ctypes.c_void_p)
+    d = AirPeriodicDescC()
+    d.n_cols, d.cols = len(columns), ctypes.cast(cols, ctypes.POINTER(AirPeriodicColumnC))
+    return d, (cols, bufs)
+
+
 class Value:
     """An SSA value of the constraint program; arithmetic operators emit ops into the owning builder."""
 
@@ -121,6 +154,10 @@ class AuxProgram:
         if not 0 <= i < self.n_rap:
             raise ValueError(f"aux program: RAP challenge {i} of {self.n_rap}")
         return self._emit(OP_CONST, _RAP_TAG | i, 0)
+
+    def periodic(self, row, k):
+        raise ValueError("aux program: an auxiliary program cannot read periodic columns (sp_air_prove_periodic refuses op 6 there); "
+                         "only the constraint program can")
 
     def _column(self, kind, num, den):
         num = num if isinstance(num, Value) else self.const(num)
@@ -217,9 +254,14 @@ def ints_to_bytes(values):
 
 class AirBuilder:
     def __init__(self, main_cols, offsets, degree_bound_factor, aux_cols=0, n_rap=0, aux_kind=AUX_NONE, num_transition_exemptions=1,
-                 aux_builder=None):
-        """aux_builder(rap: list[int]) -> (n, aux_cols) nested list of ints: the AIR's build_auxiliary_trace (aux_kind AUX_CALLBACK)."""
+                 aux_builder=None, periodic=None):
+        """aux_builder(rap: list[int]) -> (n, aux_cols) nested list of ints: the AIR's build_auxiliary_trace (aux_kind AUX_CALLBACK).
+        periodic: the periodic columns, one list of values each (a power-of-two number of them; the trace must be at least as long)."""
         assert 1 <= len(offsets) <= MAX_OFFSETS
+        self.periodic_cols = [[int(v) % P for v in values] for values in (periodic or [])]
+        for k, values in enumerate(self.periodic_cols):
+            if len(values) == 0 or len(values) & (len(values) - 1):
+                raise ValueError(f"periodic column {k}: its period {len(values)} is not a power of two")
         self.aux_builder = aux_builder
         self.main_cols, self.aux_cols, self.offsets = main_cols, aux_cols, list(offsets)
         self.degree_bound_factor, self.n_rap, self.aux_kind = degree_bound_factor, n_rap, aux_kind
@@ -236,6 +278,14 @@ class AirBuilder:
         """Cell (frame row `row` = index into the transition offsets, column `col` of main||aux)."""
         assert row < len(self.offsets) and col < self.main_cols + self.aux_cols
         return self._emit(OP_LOAD, row, col)
+
+    def periodic(self, row, k):
+        """Periodic column k at frame row `row` (index into the transition offsets): op 6."""
+        if not 0 <= row < len(self.offsets):
+            raise ValueError(f"periodic: frame row {row} of {len(self.offsets)}")
+        if not 0 <= k < len(self.periodic_cols):
+            raise ValueError(f"periodic: column {k} is not one of the AIR's {len(self.periodic_cols)} periodic columns")
+        return self._emit(OP_PERIODIC, row, k)
 
     def const(self, v):
         v %= P
@@ -265,6 +315,11 @@ class AirBuilder:
         for name, value in have.items():
             if value > lim[name]:
                 raise ValueError(f"AIR exceeds the {name} limit of sp_air_prove: {value} > {lim[name]}")
+        if self.periodic_cols:
+            from .api import air_periodic_limits
+            most = air_periodic_limits()["periodic_columns"]
+            if len(self.periodic_cols) > most:
+                raise ValueError(f"AIR exceeds the periodic_columns limit of sp_air_prove_periodic: {len(self.periodic_cols)} > {most}")
         if self.aux is not None:
             if len(self.aux.cols) != self.aux_cols:
                 raise ValueError(f"aux program declares {len(self.aux.cols)} auxiliary columns, the AIR has aux_cols = {self.aux_cols}")
@@ -277,6 +332,8 @@ class AirBuilder:
     def build(self, aux_as_callback=False, main_trace=None):
         """Returns (AirDescC, keepalive).  Raises ValueError if the AIR exceeds a bound of sp_air_limits.
 
+        With periodic columns the returned desc carries their AirPeriodicDescC (desc.periodic_desc): api.Context.air_prove proves it with
+        sp_air_prove_periodic, api.air_verify checks it with sp_air_verify_periodic.
         With an aux program (aux_kind AUX_PROGRAM) the returned desc carries its AirAuxDescC (desc.aux_desc), and
         api.Context.air_prove proves it with sp_air_prove_aux.  aux_as_callback=True returns the same AIR as aux_kind AUX_CALLBACK
         instead, its callback evaluating the aux program in Python over `main_trace` ((n, main_cols, 32) canonical big-endian
@@ -330,6 +387,10 @@ class AirBuilder:
             cb = AUX_TRACE_FN(_aux)
             d.aux_fn = cb
         keep = (ops, consts, bcs, cb)
+        if self.periodic_cols:
+            per_desc, per_keep = periodic_desc(self.periodic_cols)
+            d.periodic_desc = per_desc
+            keep = keep + (per_desc, per_keep)
         if self.aux is not None:
             aux_desc, aux_keep = self._aux_desc()
             d.aux_desc = aux_desc
@@ -434,3 +495,26 @@ def fibonacci_rap_program(trace_length, steps):
     g = b.aux.rap(0)
     b.aux.product(b.aux.load(0, 0) + g, b.aux.load(0, 1) + g)
     return b
+
+
+# ---- periodic columns: a worked example ---------------------------------------------------------------------------------
+def mimc_chain(n, period, x0, keys):
+    """x_(i+1) = (x_i + K_(i mod period))^3 on one column: a MiMC-style chain whose round constants `keys` (period of them, a power
+    of two <= n) are a periodic column.  The constraint x' - (x + K)^3 has degree 3 (K counts as a trace cell), so the composition
+    degree bound is 2n; the last row is exempt; x_0 = x0."""
+    if len(keys) != period or period > n:
+        raise ValueError(f"mimc_chain: {len(keys)} keys for period {period} on {n} rows (the period is the number of keys, at most n)")
+    b = AirBuilder(1, [0, 1], 2, periodic=[keys])
+    t = b.load(0, 0) + b.periodic(0, 0)
+    b.constraint(b.load(1, 0) - t * t * t, degree=3, exemptions=1)
+    b.boundary(0, 0, x0)
+    return b
+
+
+def mimc_chain_trace(n, x0, keys):
+    """The chain's trace as (n, 1) Python ints (ints_to_bytes gives the bytes sp_air_prove_periodic takes)."""
+    rows, x = [], x0 % P
+    for i in range(n):
+        rows.append([x])
+        x = pow((x + keys[i % len(keys)]) % P, 3, P)
+    return rows

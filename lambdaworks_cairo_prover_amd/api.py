@@ -221,7 +221,8 @@ class Context:
 
     def air_prove(self, desc, main_trace, options):
         """sp_air_prove: desc = lambdaworks_cairo_prover_amd.air.AirDescC (AirBuilder.build()[0]); main_trace (n, cols, 32).
-        A desc that carries an auxiliary program (AirBuilder with aux_kind=air.AUX_PROGRAM) goes to sp_air_prove_aux."""
+        A desc that carries an auxiliary program (AirBuilder with aux_kind=air.AUX_PROGRAM) goes to sp_air_prove_aux, one that
+        carries periodic columns (AirBuilder(..., periodic=[...])) to sp_air_prove_periodic - with its auxiliary program, if any."""
         a = np.ascontiguousarray(main_trace, dtype=np.uint8)
         n, cols = a.shape[0], a.shape[1]
         assert cols == desc.main_cols
@@ -229,7 +230,11 @@ class Context:
         out = ctypes.POINTER(ctypes.c_uint8)()
         ln = ctypes.c_uint64()
         aux = getattr(desc, "aux_desc", None)
-        if aux is not None:
+        per = getattr(desc, "periodic_desc", None)
+        if per is not None:
+            check(self._lib.sp_air_prove_periodic(self._h, ctypes.byref(desc), None if aux is None else ctypes.byref(aux), ctypes.byref(per), _u8p(a),
+                                                  ctypes.c_uint64(n), ctypes.byref(opt), ctypes.byref(out), ctypes.byref(ln)))
+        elif aux is not None:
             check(self._lib.sp_air_prove_aux(self._h, ctypes.byref(desc), ctypes.byref(aux), _u8p(a), ctypes.c_uint64(n), ctypes.byref(opt),
                                              ctypes.byref(out), ctypes.byref(ln)))
         else:
@@ -237,6 +242,15 @@ class Context:
         proof = ctypes.string_at(out, ln.value)
         self._lib.sp_free(out)
         return proof
+
+    def air_periodic_lde(self, values, n, blowup, coset):
+        """sp_air_periodic_lde: the table the composition kernel reads for one periodic column (`values`: ints, a power-of-two number
+        of them) on a trace of n rows, in natural order: (period * blowup, 32) canonical big-endian, row k = P(coset w_N^k)."""
+        from . import air
+        d, keep = air.periodic_desc([list(values)])
+        out = np.empty((len(values) * blowup, 32), dtype=np.uint8)
+        check(self._lib.sp_air_periodic_lde(self._h, d.cols, ctypes.c_uint64(n), ctypes.c_uint32(blowup), int(coset).to_bytes(32, "big"), _u8p(out)))
+        return out
 
     def last_proof_info(self):
         """{'composition_path': 1 (2n points) | 2 (whole domain) | 3 (whole domain, deg H >= 2n), 'fri_sharded_layers', 'groups', ...}"""
@@ -456,10 +470,30 @@ def air_limits():
     return {name: int(out[i]) for i, name in enumerate(AIR_LIMIT_NAMES)}
 
 
+def air_periodic_limits():
+    """sp_air_periodic_limits: {"periodic_columns": 64}; a period is a power of two, 1 <= period <= n."""
+    out = (ctypes.c_uint32 * 4)()
+    check(_lib.load().sp_air_periodic_limits(out))
+    return {"periodic_columns": int(out[0])}
+
+
+def air_periodic_eval(values, n, point):
+    """sp_air_periodic_eval (host): P(point) of the periodic column `values` (ints) on a trace of n rows, as an int."""
+    from . import air
+    d, keep = air.periodic_desc([list(values)])
+    out = ctypes.create_string_buffer(32)
+    check(_lib.load().sp_air_periodic_eval(d.cols, ctypes.c_uint64(n), (int(point) % P).to_bytes(32, "big"), out))
+    return int.from_bytes(out.raw, "big")
+
+
 def air_verify(proof, desc, options, merkle_backend=0):
-    """sp_air_verify(_backend): the library's CPU verifier for an AIR given as a constraint program."""
+    """sp_air_verify(_backend): the library's CPU verifier for an AIR given as a constraint program (sp_air_verify_periodic for a
+    desc that carries periodic columns)."""
     lib = _lib.load()
     opt = options.to_c()
+    per = getattr(desc, "periodic_desc", None)
+    if per is not None:
+        return lib.sp_air_verify_periodic(proof, ctypes.c_uint64(len(proof)), ctypes.byref(desc), ctypes.byref(per), ctypes.byref(opt), int(merkle_backend)) == 1
     return lib.sp_air_verify_backend(proof, ctypes.c_uint64(len(proof)), ctypes.byref(desc), ctypes.byref(opt), int(merkle_backend)) == 1
 
 

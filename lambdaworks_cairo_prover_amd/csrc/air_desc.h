@@ -1,5 +1,5 @@
 // Host forms of the C views of include/stark252_hip.h that the prover and the verifier share: proof options, sp_air_desc,
-// sp_air_aux_desc, and the well-formedness rules of their straight-line programs.  Host only (no device headers).
+// sp_air_aux_desc, sp_air_periodic_desc, and the well-formedness rules of their straight-line programs.  Host only (no device headers).
 #pragma once
 #include "cairo_air_host.h"
 #include <vector>
@@ -34,10 +34,24 @@ struct AirAuxHost {
     std::vector<AirAuxColumnHost> cols;
 };
 
-// The rules of a straight-line program (op 0 LOAD, 1 CONST, 2 ADD, 3 SUB, 4 MUL, 5 OUT): a LOAD has a < load_a_end and
+// Host form of sp_air_periodic_desc: column k repeats cols[k] (a power-of-two number of values, at most the trace length).
+constexpr uint32_t AIR_MAX_PERIODIC = 64;
+struct AirPeriodicHost { std::vector<std::vector<fe>> cols; };
+// sp_air_periodic_desc -> AirPeriodicHost for a trace of n rows; false - before anything is allocated or copied - for more than 64
+// columns, a count without its array, null values, a period that is no power of two or exceeds n.  capi_host.cpp
+bool air_periodic_from_c(const sp_air_periodic_desc* d, uint64_t n, AirPeriodicHost& out);
+bool air_periodic_fits(const AirPeriodicHost& p, uint64_t n);
+// P(point) of one periodic column on a trace of n rows: q interpolated from the values (a size-period inverse transform),
+// evaluated at point^(n / period).  What the verifier uses for P_k(z g^offset) and what sp_air_periodic_eval returns.  verifier.cpp
+std::vector<fe> air_periodic_interpolate(const std::vector<fe>& values);
+fe air_periodic_eval(const std::vector<fe>& coeffs, uint64_t n, const fe& point);
+
+// The rules of a straight-line program (op 0 LOAD, 1 CONST, 2 ADD, 3 SUB, 4 MUL, 5 OUT, 6 PERIODIC): a LOAD has a < load_a_end and
 // b < load_b_end, a CONST names one of n_values constants or RAP challenges, ADD / SUB / MUL take two earlier ops that are not
-// OUTs, an OUT one of n_out targets and such an op (n_out 0: no OUT at all).  Returns the index of the first op that breaks
-// them, ops.size() when none does.  verifier.cpp
-size_t air_program_first_bad_op(const std::vector<AirOpHost>& ops, uint32_t load_a_end, uint32_t load_b_end, size_t n_values, uint32_t n_out);
+// OUTs, an OUT one of n_out targets and such an op (n_out 0: no OUT at all), a PERIODIC a < load_a_end and one of n_periodic
+// periodic columns (0: the program cannot read any).  Returns the index of the first op that breaks them, ops.size() when none
+// does.  verifier.cpp
+size_t air_program_first_bad_op(const std::vector<AirOpHost>& ops, uint32_t load_a_end, uint32_t load_b_end, size_t n_values, uint32_t n_out,
+                                uint32_t n_periodic);
 
 }  // namespace sp

@@ -9,6 +9,8 @@
 #include <cstring>
 #include <vector>
 
+// prover.cpp: the periodic-column tables of a program AIR (sp_air_periodic_lde hands one out)
+namespace sp { int air_periodic_tables(hipStream_t st, NttEngine& ntt, fe* vals, fe* ws, fe* tab, uint32_t cnt, uint32_t logp, uint32_t logn, uint32_t logb, const fe& h); }
 using namespace sp;
 
 namespace {
@@ -636,6 +638,32 @@ int sp_lde(sp_ctx* c, const uint8_t* coeffs, uint64_t n, uint32_t cols, uint32_t
     SP_TRY(e.scale_by_powers(b.as<fe>(), n, cols, n, fe_one(), &ninv));
     SP_TRY(e.lde_from_bitrev(b.as<fe>(), d.as<fe>(), k, lb, cols, n, N));
     SP_TRY(encode_download(c, d.as<fe>(), N * cols, out));
+    return SP_OK;
+}
+
+// The periodic-column table of the prover (prover.cpp air_periodic_tables: the routine composition_air calls), for one column,
+// handed back in natural order: out[j b + c] = table entry (c, j).  Canonical big-endian whatever the context's encoding.
+int sp_air_periodic_lde(sp_ctx* c, const sp_air_periodic_column* col, uint64_t n, uint32_t blowup, const uint8_t coset[32], uint8_t* out) {
+    if (!c || !col || !coset || !out) return SP_E_INVALID_ARG;
+    SP_HIP_CHECK(hipSetDevice(c->device));
+    const int k = sp_log2_exact(n), lb = sp_log2_exact(blowup), lp = col->period ? sp_log2_exact(col->period) : -1;
+    if (k < 0 || lb < 1 || k + lb > 30 || lp < 0 || lp > k || !col->values) {
+        sp_set_error("sp_air_periodic_lde: n, blowup (>= 2) and the period must be powers of two, 1 <= period <= n");
+        return SP_E_INVALID_ARG;
+    }
+    const uint64_t p = col->period, M = p << lb;
+    std::vector<fe> hv(p), ht(M);
+    for (uint64_t j = 0; j < p; ++j) hv[j] = fe_from_bytes_be(col->values + 32 * j);
+    DevBuf vals, ws, tab;
+    SP_TRY(vals.alloc(p * sizeof(fe)));
+    SP_TRY(ws.alloc(p * sizeof(fe)));
+    SP_TRY(tab.alloc(M * sizeof(fe)));
+    SP_HIP_CHECK(hipMemcpyAsync(vals.p, hv.data(), p * sizeof(fe), hipMemcpyHostToDevice, c->stream));
+    SP_TRY(air_periodic_tables(c->stream, *c->ntt, vals.as<fe>(), ws.as<fe>(), tab.as<fe>(), 1, (uint32_t)lp, (uint32_t)k, (uint32_t)lb, fe_from_bytes_be(coset)));
+    SP_HIP_CHECK(hipMemcpyAsync(ht.data(), tab.p, M * sizeof(fe), hipMemcpyDeviceToHost, c->stream));
+    SP_HIP_CHECK(hipStreamSynchronize(c->stream));
+    for (uint64_t cc = 0; cc < blowup; ++cc)
+        for (uint64_t j = 0; j < p; ++j) fe_to_bytes_be(ht[cc * p + j], out + 32 * (j * blowup + cc));
     return SP_OK;
 }
 

@@ -55,7 +55,7 @@ bool cairo_run_device_inputs(const sp_cairo_run* run, const TracePlan** plan, Tr
 }
 static thread_local std::string g_last_error;
 void sp_set_error(const std::string& s) { g_last_error = s; }
-namespace sp { int air_verify_host(const uint8_t* proof_bytes, size_t len, const AirDescHost& air, const ProofOptionsHost& opt); }
+namespace sp { int air_verify_host(const uint8_t* proof_bytes, size_t len, const AirDescHost& air, const ProofOptionsHost& opt, const AirPeriodicHost* periodic); }
 namespace sp { void set_verify_merkle_backend(int backend); int host_bind_calling_thread_to_device_node(int device, int* node_out); }
 namespace sp { int cairo_verify_host(const uint8_t* proof_bytes, size_t len, const PublicInputs& pub, uint8_t blowup, uint64_t queries, uint64_t coset_offset, uint8_t grinding); }
 
@@ -94,6 +94,25 @@ bool air_desc_from_c(const sp_air_desc* d, AirDescHost& a) {
         a.boundary.push_back(BoundaryConstraint{d->boundary[i].col, d->boundary[i].step, fe_from_bytes_be(d->boundary[i].value)});
     return true;
 }
+
+bool air_periodic_from_c(const sp_air_periodic_desc* d, uint64_t n, AirPeriodicHost& out) {
+    if (d->n_cols > AIR_MAX_PERIODIC || (d->n_cols && !d->cols)) return false;
+    for (uint32_t k = 0; k < d->n_cols; ++k) {   // every column first: nothing is allocated for a descriptor that is refused
+        const sp_air_periodic_column& c = d->cols[k];
+        if (c.period == 0 || (c.period & (c.period - 1)) || c.period > n || !c.values) return false;
+    }
+    for (uint32_t k = 0; k < d->n_cols; ++k) {
+        const sp_air_periodic_column& c = d->cols[k];
+        std::vector<fe> v(c.period);
+        for (uint32_t j = 0; j < c.period; ++j) v[j] = fe_from_bytes_be(c.values + 32 * (size_t)j);
+        out.cols.push_back(std::move(v));
+    }
+    return true;
+}
+bool air_periodic_fits(const AirPeriodicHost& p, uint64_t n) {
+    for (const auto& c : p.cols) if (c.size() > n) return false;
+    return true;
+}
 }  // namespace sp
 
 extern "C" {
@@ -102,6 +121,12 @@ const char* sp_version(void) { return "stark252-hip 0.3 (gfx950)"; }
 int sp_abi_version(void) { return SP_ABI_VERSION; }
 uint64_t sp_air_desc_size(void) { return sizeof(sp_air_desc); }
 uint64_t sp_air_aux_desc_size(void) { return sizeof(sp_air_aux_desc); }
+uint64_t sp_air_periodic_desc_size(void) { return sizeof(sp_air_periodic_desc); }
+int sp_air_periodic_limits(uint32_t out[4]) {
+    if (!out) return SP_E_INVALID_ARG;
+    out[0] = sp::AIR_MAX_PERIODIC; out[1] = out[2] = out[3] = 0u;
+    return SP_OK;
+}
 int sp_air_limits(uint32_t out[8]) {
     if (!out) return SP_E_INVALID_ARG;
     const uint32_t lim[8] = {(uint32_t)sp::AIR_MAX_COLS, (uint32_t)sp::AIR_MAX_TRANSITIONS, (uint32_t)sp::AIR_MAX_OFFSETS, (uint32_t)sp::AIR_MAX_BOUNDARY,
@@ -433,7 +458,7 @@ int sp_air_verify(const uint8_t* proof, uint64_t proof_len, const sp_air_desc* d
     try {
         sp::AirDescHost air;
         if (!sp::air_desc_from_c(d, air)) { sp_set_error("malformed: AIR descriptor"); return 0; }
-        const int ok = sp::air_verify_host(proof, proof_len, air, sp::proof_options_from_c(opt));
+        const int ok = sp::air_verify_host(proof, proof_len, air, sp::proof_options_from_c(opt), nullptr);
         sp_set_error(ok == 1 ? "" : "rejected: a verification step failed");
         return ok;
     } catch (const std::exception& e) { sp_set_error(e.what()); return 0; }
@@ -479,6 +504,43 @@ int sp_air_verify_backend(const uint8_t* proof, uint64_t proof_len, const sp_air
     if (merkle_backend != SP_MERKLE_KECCAK256 && merkle_backend != SP_MERKLE_POSEIDON) return SP_E_INVALID_ARG;
     VerifyBackendScope scope(merkle_backend);
     return sp_air_verify(proof, proof_len, d, opt);
+}
+
+// sp_air_verify_backend for an AIR whose constraint program reads periodic columns (op 6): the verifier evaluates them at the
+// out-of-domain frame's points itself; nothing about them is in the proof.
+int sp_air_verify_periodic(const uint8_t* proof, uint64_t proof_len, const sp_air_desc* d, const sp_air_periodic_desc* pd, const sp_proof_options* opt,
+                           int merkle_backend) {
+    if (!proof || !d || !pd || !opt) return SP_E_INVALID_ARG;
+    if (merkle_backend != SP_MERKLE_KECCAK256 && merkle_backend != SP_MERKLE_POSEIDON) return SP_E_INVALID_ARG;
+    VerifyBackendScope scope(merkle_backend);
+    try {
+        sp::AirDescHost air;
+        sp::AirPeriodicHost periodic;
+        if (!sp::air_desc_from_c(d, air)) { sp_set_error("malformed: AIR descriptor"); return 0; }
+        // the trace length is only known from the proof (its first eight bytes): the periods are held against it before anything is
+        // copied or interpolated
+        if (proof_len < 8) throw std::runtime_error("malformed: InvalidAmountOfBytes");
+        uint64_t n = 0;
+        for (int i = 0; i < 8; ++i) n = (n << 8) | proof[i];
+        if (!sp::air_periodic_from_c(pd, n, periodic)) { sp_set_error("malformed: periodic columns (at most 64, each a power-of-two number of values, at most the trace length)"); return 0; }
+        const int ok = sp::air_verify_host(proof, proof_len, air, sp::proof_options_from_c(opt), &periodic);
+        sp_set_error(ok == 1 ? "" : "rejected: a verification step failed");
+        return ok;
+    } catch (const std::exception& e) { sp_set_error(e.what()); return 0; }
+}
+
+int sp_air_periodic_eval(const sp_air_periodic_column* col, uint64_t n, const uint8_t point[32], uint8_t out[32]) {
+    if (!col || !point || !out) return SP_E_INVALID_ARG;
+    try {
+        const sp_air_periodic_desc one{1, 0, col};
+        sp::AirPeriodicHost p;
+        if (sp_log2_exact(n) < 0 || !sp::air_periodic_from_c(&one, n, p)) {
+            sp_set_error("sp_air_periodic_eval: n and the period must be powers of two, 1 <= period <= n");
+            return SP_E_INVALID_ARG;
+        }
+        fe_to_bytes_be(sp::air_periodic_eval(sp::air_periodic_interpolate(p.cols[0]), n, fe_from_bytes_be(point)), out);
+        return SP_OK;
+    } catch (const std::exception& e) { sp_set_error(e.what()); return SP_E_INVALID_ARG; }
 }
 
 // Host-side Poseidon (csrc/poseidon.h) for known-answer tests of the optional Merkle backend.

@@ -369,13 +369,13 @@ int sp_last_round_ms(sp_ctx* c, float out[5]) {
 }
 
 static int air_prove_common(sp_ctx* c, const sp_air_desc* d, const sp::AirAuxHost* aux, const uint8_t* main_trace, uint64_t n,
-                            const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len) {
+                            const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len, const sp::AirPeriodicHost* periodic = nullptr) {
     c->prewarm_cancel.store(0, std::memory_order_release);
     sp::AirDescHost a;
     if (!air_desc_from_c(d, a)) { sp_set_error("sp_air_prove: malformed descriptor"); return SP_E_INVALID_ARG; }
     std::vector<uint8_t> proof;
     float ms[5] = {0, 0, 0, 0, 0};
-    SP_TRY(sp::air_prove(c, a, main_trace, n, proof_options_from_c(opt), proof, ms, aux));
+    SP_TRY(sp::air_prove(c, a, main_trace, n, proof_options_from_c(opt), proof, ms, aux, periodic));
     return publish_proof(c, ms, proof, proof_out, proof_len);
 }
 
@@ -385,9 +385,8 @@ int sp_air_prove(sp_ctx* c, const sp_air_desc* d, const uint8_t* main_trace, uin
     return air_prove_common(c, d, nullptr, main_trace, n, opt, proof_out, proof_len);
 }
 
-int sp_air_prove_aux(sp_ctx* c, const sp_air_desc* d, const sp_air_aux_desc* x, const uint8_t* main_trace, uint64_t n,
-                     const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len) {
-    if (!c || !d || !x || !main_trace || !opt || !proof_out || !proof_len) return SP_E_INVALID_ARG;
+// sp_air_aux_desc -> AirAuxHost, checked against its AIR as far as the C view goes (the program itself: validate_aux_program)
+static int aux_from_c(const sp_air_desc* d, const sp_air_aux_desc* x, sp::AirAuxHost& aux) {
     if (d->aux_kind != SP_AIR_AUX_PROGRAM || d->aux_cols == 0 || x->n_cols != d->aux_cols) {
         sp_set_error("sp_air_prove_aux: needs aux_kind SP_AIR_AUX_PROGRAM and aux->n_cols == air->aux_cols >= 1");
         return SP_E_INVALID_ARG;
@@ -397,11 +396,33 @@ int sp_air_prove_aux(sp_ctx* c, const sp_air_desc* d, const sp_air_aux_desc* x, 
         sp_set_error("sp_air_prove_aux: the auxiliary program exceeds 65535 ops or 4096 constants");
         return SP_E_INVALID_ARG;
     }
-    sp::AirAuxHost aux;
     for (uint32_t i = 0; i < x->n_ops; ++i) aux.ops.push_back(sp::AirOpHost{x->ops[i].op, x->ops[i].a, x->ops[i].b});
     for (uint32_t i = 0; i < x->n_consts; ++i) aux.consts.push_back(fe_from_bytes_be(x->consts + 32 * (size_t)i));
     for (uint32_t k = 0; k < x->n_cols; ++k) aux.cols.push_back(sp::AirAuxColumnHost{x->cols[k].kind, x->cols[k].num_op, x->cols[k].den_op});
+    return SP_OK;
+}
+
+int sp_air_prove_aux(sp_ctx* c, const sp_air_desc* d, const sp_air_aux_desc* x, const uint8_t* main_trace, uint64_t n,
+                     const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len) {
+    if (!c || !d || !x || !main_trace || !opt || !proof_out || !proof_len) return SP_E_INVALID_ARG;
+    sp::AirAuxHost aux;
+    SP_TRY(aux_from_c(d, x, aux));
     return air_prove_common(c, d, &aux, main_trace, n, opt, proof_out, proof_len);
+}
+
+int sp_air_prove_periodic(sp_ctx* c, const sp_air_desc* d, const sp_air_aux_desc* x, const sp_air_periodic_desc* pd, const uint8_t* main_trace,
+                          uint64_t n, const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len) {
+    if (!c || !d || !pd || !main_trace || !opt || !proof_out || !proof_len) return SP_E_INVALID_ARG;
+    try {
+        sp::AirPeriodicHost periodic;
+        if (!sp::air_periodic_from_c(pd, n, periodic)) {
+            sp_set_error("sp_air_prove_periodic: malformed periodic columns (at most 64, each a power-of-two number of values, at most the trace length)");
+            return SP_E_INVALID_ARG;
+        }
+        sp::AirAuxHost aux;
+        if (x) SP_TRY(aux_from_c(d, x, aux));
+        return air_prove_common(c, d, x ? &aux : nullptr, main_trace, n, opt, proof_out, proof_len, &periodic);
+    } catch (const std::exception& e) { sp_set_error(e.what()); return SP_E_INVALID_ARG; }
 }
 
 }  // extern "C"

@@ -429,7 +429,7 @@ int validate_aux_program(const AirAuxHost& aux, uint32_t main_cols, uint32_t n_r
     if (aux.consts.size() > (size_t)AIR_MAX_CONSTS) { sp_set_error("aux program: more than 4096 constants"); return SP_E_INVALID_ARG; }
     if (aux.consts.size() + n_rap > 65535) { sp_set_error("aux program: constants and RAP challenges exceed the 16-bit operand range"); return SP_E_INVALID_ARG; }
     if (aux.cols.empty() || aux.cols.size() > (size_t)AIR_MAX_COLS) { sp_set_error("aux program: 1 .. 1024 auxiliary columns"); return SP_E_INVALID_ARG; }
-    const size_t bad = air_program_first_bad_op(aux.ops, AIR_AUX_MAX_SHIFT + 1, main_cols, aux.consts.size() + n_rap, 0);   // (no OUT: the columns name their ops)
+    const size_t bad = air_program_first_bad_op(aux.ops, AIR_AUX_MAX_SHIFT + 1, main_cols, aux.consts.size() + n_rap, 0, 0);   // (no OUT: the columns name their ops; no periodic columns)
     if (bad < n_ops) {
         sp_set_error("aux program: malformed op " + std::to_string(bad) + " (LOAD needs a shift of 0 .. 7 and a main column, CONST a constant or a RAP "
                      "challenge, ADD / SUB / MUL earlier ops; there is no OUT)");
@@ -673,8 +673,23 @@ int air_assign_slots(const std::vector<AirOpHost>& ops, std::vector<AirOpDev>& d
     return SP_OK;
 }
 
+int air_periodic_tables(hipStream_t st, NttEngine& ntt, fe* vals, fe* ws, fe* tab, uint32_t cnt, uint32_t logp, uint32_t logn, uint32_t logb, const fe& h) {
+    if (logp > logn || cnt == 0) return SP_E_INVALID_ARG;
+    const uint64_t p = 1ull << logp;
+    const fe hq = fe_pow_u64(h, (1ull << logn) >> logp);   // x -> x^(n/p) takes the coset h <w_N> to hq <w_(p b)>
+    if (p <= AIR_PERIODIC_DIRECT_MAX) {
+        const fe* roots_pb = nullptr;
+        SP_TRY(ntt.roots((int)(logp + logb), &roots_pb));
+        return air_periodic_table_direct(st, vals, ws, tab, cnt, logp, logb, hq, roots_pb);
+    }
+    // as a trace column: unscaled bit-reversed inverse transform with the post factors p^-1 hq^rev(position), then the coset-major LDE
+    SP_TRY(gen_power_table(st, ws, p, logp, hq, fe_inv(fe_from_u64(p))));
+    SP_TRY(ntt.dif_natural_to_bitrev_inverse(vals, (int)logp, cnt, p, ws));
+    return ntt.lde_coset_major(vals, tab, (int)logp, (int)logb, cnt, p, p << logb);
+}
+
 int StarkProver::composition_air(const AirDescHost& air, const std::vector<fe>& rap, const std::vector<fe>& b_alpha, const std::vector<fe>& b_beta,
-                                 const std::vector<fe>& t_alpha, const std::vector<fe>& t_beta, uint8_t root_out[32]) {
+                                 const std::vector<fe>& t_alpha, const std::vector<fe>& t_beta, uint8_t root_out[32], const AirPeriodicHost* periodic) {
     if (stage_ != 3 && !(stage_ == 2 && Ca_ == 0)) { sp_set_error("composition: trace segments not committed"); return SP_E_STATE; }
     const uint32_t T = (uint32_t)air.degrees.size(), B = (uint32_t)air.boundary.size(), R = (uint32_t)air.offsets.size();
     if (T == 0 || T > AIR_MAX_TRANSITIONS || B > AIR_MAX_BOUNDARY || R == 0 || R > AIR_MAX_OFFSETS || air.exemptions.size() != T ||
@@ -694,7 +709,19 @@ int StarkProver::composition_air(const AirDescHost& air, const std::vector<fe>& 
     prog.n_ops = (uint32_t)air.ops.size();
     prog.n_offsets = R;
     for (uint32_t k = 0; k < R; ++k) prog.offsets[k] = air.offsets[k];
-    if (air_program_first_bad_op(air.ops, R, C_, air.consts.size() + rap.size(), T) < air.ops.size()) { sp_set_error("composition_air: malformed constraint program"); return SP_E_INVALID_ARG; }
+    // --- periodic columns: column k's values at pvals + off_k (off_k = the periods before it, summed), its table at ptab + off_k b
+    const uint32_t Kp = periodic ? (uint32_t)periodic->cols.size() : 0u;
+    if (Kp > AIR_MAX_PERIODIC) { sp_set_error("composition_air: more than 64 periodic columns"); return SP_E_INVALID_ARG; }
+    std::vector<AirPeriodicCol> pcols(Kp);
+    uint64_t S = 0;
+    for (uint32_t k = 0; k < Kp; ++k) {
+        const uint64_t p = periodic->cols[k].size();
+        const int lp = sp_log2_exact(p);
+        if (lp < 0 || p > n_) { sp_set_error("composition_air: a period must be a power of two, 1 <= period <= n"); return SP_E_INVALID_ARG; }
+        pcols[k] = AirPeriodicCol{(uint32_t)lp, 0u, S};
+        S += p;
+    }
+    if (air_program_first_bad_op(air.ops, R, C_, air.consts.size() + rap.size(), T, Kp) < air.ops.size()) { sp_set_error("composition_air: malformed constraint program"); return SP_E_INVALID_ARG; }
     SP_TRY(air_assign_slots(air.ops, dops, "composition_air: more than 64 values alive at once in the constraint program"));
     prog.n_ops = (uint32_t)dops.size();
     // --- transition exemptions (traits.rs:49-79, evaluator.rs:299-323): distinct non-zero counts; with
@@ -750,7 +777,8 @@ int StarkProver::composition_air(const AirDescHost& air, const std::vector<fe>& 
     const size_t o_prog = place(sizeof(AirProgram)), o_ops = place(sizeof(AirOpDev) * dops.size()),
                  o_consts = place(sizeof(fe) * (air.consts.size() + rap.size())), o_zf = place(sizeof(fe) * b),
                  o_coef = place(sizeof(fe) * b * nterm), o_bval = place(sizeof(fe) * B), o_gpt = place(sizeof(fe) * nd),
-                 o_bstep = place(sizeof(uint64_t) * B), o_bcol = place(sizeof(uint32_t) * B), o_gend = place(sizeof(uint32_t) * nd);
+                 o_bstep = place(sizeof(uint64_t) * B), o_bcol = place(sizeof(uint32_t) * B), o_gend = place(sizeof(uint32_t) * nd),
+                 o_pcols = place(sizeof(AirPeriodicCol) * Kp), o_pvals = place(sizeof(fe) * S);
     SP_TRY(grow(od_.air_buf, at));
     std::vector<uint8_t>& up = h_air_up_;
     up.assign(at, 0);
@@ -774,6 +802,8 @@ int StarkProver::composition_air(const AirDescHost& air, const std::vector<fe>& 
         const BoundaryConstraint& bc = air.boundary[order[jp]];
         hbval[jp] = bc.value; hbstep[jp] = bc.step; hbcol[jp] = bc.col;
     }
+    if (Kp) std::memcpy(host_at(o_pcols), pcols.data(), sizeof(AirPeriodicCol) * Kp);
+    for (uint32_t k = 0; k < Kp; ++k) std::memcpy(host_at(o_pvals) + sizeof(fe) * pcols[k].off, periodic->cols[k].data(), sizeof(fe) * periodic->cols[k].size());
     std::vector<fe> points(nd);
     for (uint32_t g = 0; g < nd; ++g) hgpt[g] = points[g] = fe_pow_u64(g_, steps[g]);
     {
@@ -803,6 +833,25 @@ int StarkProver::composition_air(const AirDescHost& air, const std::vector<fe>& 
     tabs.bstep = reinterpret_cast<const uint64_t*>(dev_at(o_bstep));
     tabs.gpoint = reinterpret_cast<const fe*>(dev_at(o_gpt));
     tabs.gend = reinterpret_cast<const uint32_t*>(dev_at(o_gend));
+    tabs.pcols = nullptr; tabs.pvals = nullptr; tabs.ptab = nullptr;
+    if (Kp) {
+        // [b S] tables, [S] working copy of the values (the transforms run in place), [S] scratch.  Every rank builds all b cosets:
+        // the kernel indexes by the global LDE index.
+        SP_TRY(grow(od_.periodic, S * (b + 2)));
+        fe* tab = od_.periodic.p;
+        fe* work = tab + S * b;
+        fe* ws = work + S;
+        SP_HIP_CHECK(hipMemcpyAsync(work, dev_at(o_pvals), sizeof(fe) * S, hipMemcpyDeviceToDevice, c_->stream));
+        for (uint32_t k = 0; k < Kp;) {   // neighbours of one period in one batch
+            uint32_t cnt = 1;
+            while (k + cnt < Kp && pcols[k + cnt].logp == pcols[k].logp) ++cnt;
+            SP_TRY(air_periodic_tables(c_->stream, *c_->ntt, work + pcols[k].off, ws, tab + pcols[k].off * b, cnt, pcols[k].logp, logn_, logb_, h_));
+            k += cnt;
+        }
+        tabs.pcols = reinterpret_cast<const AirPeriodicCol*>(dev_at(o_pcols));
+        tabs.pvals = reinterpret_cast<const fe*>(dev_at(o_pvals));
+        tabs.ptab = tab;
+    }
     offsets_ = air.offsets;
     return composition_core(nullptr, points, reinterpret_cast<const AirProgram*>(dev_at(o_prog)), &tabs, od_.ex_roots.p, allow_sub, root_out);
 }

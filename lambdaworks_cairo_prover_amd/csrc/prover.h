@@ -22,6 +22,11 @@ int validate_aux_program(const AirAuxHost& aux, uint32_t main_cols, uint32_t n_r
 // or through other values, are dropped; every other value gets one of AIR_MAX_LIVE slots, released after its last use.  The ops
 // must already be validated.  SP_E_UNSUPPORTED with `live_error` as sp_last_error() when more than AIR_MAX_LIVE are alive at once.
 int air_assign_slots(const std::vector<AirOpHost>& ops, std::vector<AirOpDev>& out, const char* live_error);
+// Tables of `cnt` periodic columns of one period p = 2^logp on a trace of 2^logn rows: vals = [cnt][p] values (overwritten),
+// tab = [cnt][b][p] coset-major evaluations, entry (c, j) = P(h w_N^(j b + c)) = q(h^(n/p) w_(p b)^(j b + c)); ws: cnt * p elements.
+// Periods up to AIR_PERIODIC_DIRECT_MAX by the direct kernels, longer ones by the transform plans (an inverse transform whose post
+// factors scale by h^(n/p) and 1/p, then the coset-major LDE every trace column goes through).
+int air_periodic_tables(hipStream_t st, NttEngine& ntt, fe* vals, fe* ws, fe* tab, uint32_t cnt, uint32_t logp, uint32_t logn, uint32_t logb, const fe& h);
 
 struct Openings {
     uint32_t n_queries = 0, n_layers = 0, n_cols = 0, depth0 = 0;
@@ -96,8 +101,9 @@ class StarkProver : public sp_deletable {
     int composition_precheck(const fe rap[3], const std::vector<BoundaryConstraint>& bcs, uint32_t n_transitions);
     // round 2 for an AIR given as a constraint program (reference traits.rs:15-119 + evaluator.rs:38-260); rap = its RAP
     // challenges (appended to the program's constants); also sets the frame offsets used by rounds 3 and 4.
+    // periodic (nullable): the periodic columns the program reads with op 6; their tables are built here (od_.periodic)
     int composition_air(const AirDescHost& air, const std::vector<fe>& rap, const std::vector<fe>& b_alpha, const std::vector<fe>& b_beta,
-                        const std::vector<fe>& t_alpha, const std::vector<fe>& t_beta, uint8_t root_out[32]);
+                        const std::vector<fe>& t_alpha, const std::vector<fe>& t_beta, uint8_t root_out[32], const AirPeriodicHost* periodic = nullptr);
     // round 3: H1(z^2), H2(z^2), t_j(z g^ofs_k) for every frame row k (row-major [k][j])
     int ood(const fe& z, fe* h1_z2, fe* h2_z2, std::vector<fe>& trace_ood);
     // round 4
@@ -250,6 +256,7 @@ class StarkProver : public sp_deletable {
         // auxiliary programs (commit_aux_program): ops, constants and column tables of every chunk in one buffer, and the N / D
         // workspace (denominators, batch-inversion scratch, scan block totals); kept across proofs of a shape
         DevBuf<uint8_t> auxp_buf; DevBuf<fe> auxp_ws;
+        DevBuf<fe> periodic;                     // periodic columns of a program AIR: [b S] tables, [S] values being transformed, [S] scratch (S = sum of the periods)
         DevBuf<uint8_t> fri_chain;               // [state 32 B][L x constants][L x zeta constants][L x roots]
         DevBuf<int> side_flags;                  // [SIDE_FLAGS]
         DevBuf<fe> bpre;                         // [3][2n] boundary inverses + [3][2n] scratch
@@ -382,7 +389,8 @@ int cairo_prove(sp_ctx* ctx, const uint8_t* main_trace, uint64_t n, uint32_t col
 // main_trace: row-major n x air.main_cols in the context encoding (host memory).
 // round_ms: device time of rounds 1 - 4 in [1..4], as cairo_prove.
 // aux (nullable): the auxiliary program of an AIR with aux_kind SP_AIR_AUX_PROGRAM (sp_air_prove_aux).
+// periodic (nullable): the periodic columns its constraint program reads (sp_air_prove_periodic); without them op 6 is malformed.
 int air_prove(sp_ctx* ctx, const AirDescHost& air, const uint8_t* main_trace, uint64_t n, const ProofOptionsHost& opt,
-              std::vector<uint8_t>& proof_out, float round_ms[5], const AirAuxHost* aux = nullptr);
+              std::vector<uint8_t>& proof_out, float round_ms[5], const AirAuxHost* aux = nullptr, const AirPeriodicHost* periodic = nullptr);
 
 }  // namespace sp

@@ -257,7 +257,7 @@ int cairo_prove(sp_ctx* ctx, const uint8_t* main_trace, uint64_t n, uint32_t col
 // the descriptor - RAP challenges (n_rap field samples), auxiliary trace (by kind: the fibonacci_rap column and the caller's
 // callback on the host - the example AIRs are tiny -, an auxiliary program on the device), boundary constraints, transition program.
 int air_prove(sp_ctx* ctx, const AirDescHost& air, const uint8_t* main_trace, uint64_t n, const ProofOptionsHost& opt,
-              std::vector<uint8_t>& proof_out, float round_ms[5], const AirAuxHost* aux) {
+              std::vector<uint8_t>& proof_out, float round_ms[5], const AirAuxHost* aux, const AirPeriodicHost* periodic) {
     try {
         if (air.main_cols == 0 || (uint64_t)air.main_cols + air.aux_cols > (uint64_t)AIR_MAX_COLS) {
             sp_set_error("air_prove: column count out of range (1 .. 1024 columns, main + aux)");
@@ -267,6 +267,10 @@ int air_prove(sp_ctx* ctx, const AirDescHost& air, const uint8_t* main_trace, ui
         if (air.consts.size() > (size_t)AIR_MAX_CONSTS) { sp_set_error("air_prove: more than 4096 constants"); return SP_E_INVALID_ARG; }
         if (air.consts.size() + air.n_rap > 65535) { sp_set_error("air_prove: constants and RAP challenges exceed the 16-bit operand range"); return SP_E_INVALID_ARG; }
         if (air.ops.size() > (size_t)AIR_MAX_OPS) { sp_set_error("air_prove: more than 65535 ops"); return SP_E_INVALID_ARG; }
+        if (periodic) {
+            if (periodic->cols.size() > (size_t)AIR_MAX_PERIODIC) { sp_set_error("air_prove: more than 64 periodic columns"); return SP_E_INVALID_ARG; }
+            if (!air_periodic_fits(*periodic, n)) { sp_set_error("air_prove: a periodic column's period exceeds the trace length"); return SP_E_INVALID_ARG; }
+        }
         if (aux) {
             if (air.aux_kind != SP_AIR_AUX_PROGRAM || air.aux_cols == 0 || aux->cols.size() != air.aux_cols) {
                 sp_set_error("air_prove: an auxiliary program needs aux_kind SP_AIR_AUX_PROGRAM and one column per auxiliary column");
@@ -324,7 +328,7 @@ int air_prove(sp_ctx* ctx, const AirDescHost& air, const uint8_t* main_trace, ui
         }
         SP_HIP_CHECK(hipEventRecord(run.H->round_ev[1], ctx->stream));
         auto composition = [&](const std::vector<fe>& b_alpha, const std::vector<fe>& b_beta, const std::vector<fe>& t_alpha, const std::vector<fe>& t_beta, uint8_t* root_out) {
-            return P->composition_air(air, rap, b_alpha, b_beta, t_alpha, t_beta, root_out);
+            return P->composition_air(air, rap, b_alpha, b_beta, t_alpha, t_beta, root_out, periodic);
         };
         return finish_proof(ctx, run, air.boundary.size(), air.degrees.size(), opt, composition, proof_out, round_ms);
     } catch (const std::exception& e) {

@@ -72,6 +72,7 @@ constexpr int AIR_MAX_COLS = 1024, AIR_MAX_TRANSITIONS = 64, AIR_MAX_OFFSETS = 8
 // Device form of one op: the host assigns every value a slot of a small per-point value file (liveness analysis in
 // composition_air), so a long straight-line program needs AIR_MAX_LIVE values per point, not one per op.
 //   0 LOAD(a = row, b = col) -> dst   1 CONST(a = idx) -> dst   2 ADD / 3 SUB / 4 MUL (a, b = slots) -> dst   5 OUT(a = constraint, b = slot)
+//   6 PERIODIC(a = row, b = periodic column) -> dst
 struct AirOpDev { uint8_t op, pad; uint16_t a, b, dst; };
 struct AirProgram {
     uint32_t n_ops, n_offsets, offsets[AIR_MAX_OFFSETS];
@@ -81,6 +82,7 @@ struct AirProgram {
     const AirOpDev* ops;                      // [n_ops]   (device arrays sized by the program, beside this header)
     const fe* consts;                         // constants followed by the RAP challenges
 };
+struct AirPeriodicCol { uint32_t logp, pad; uint64_t off; };   // off: the periods of the columns before this one, summed
 // Per-proof composition data of a program AIR, in device memory sized by the proof (every lane of a launch reads the same
 // entry: uniform loads).  Boundary constraints are grouped by row: group g holds constraints [gend[g-1], gend[g]) on the row
 // whose point is gpoint[g] = g^step.
@@ -94,6 +96,14 @@ struct AirCompTables {
     const uint64_t* bstep;     // [B]  (trace check)
     const fe* gpoint;          // [ndist]
     const uint32_t* gend;      // [ndist]
+    // periodic columns (null without any): column k has 2^logp values at pvals + off and its table at ptab + off * b, coset-major
+    // [b][2^logp]: entry (c, j) = P_k(h w_N^(j b + c)) - the order of the LDE columns themselves.  Lane i stands on the natural-order
+    // index i << stride_log, so on the whole domain a wave covers b_loc cosets of 64 / b_loc adjacent j (b_loc runs of adjacent
+    // elements, 32 p bytes apart) and on the 2n-point path two cosets of 32 adjacent j - the pattern of its LDE loads.  A [p][b]
+    // layout would make the whole-domain reads contiguous; the two have not been measured against each other.
+    const AirPeriodicCol* pcols;
+    const fe* pvals;
+    const fe* ptab;
 };
 // zb[i] = prod_g (x_i - point[g]) over the ndist boundary points (device array), x_i = h w_N^i as coset_minus_points maps
 // i (shard included); the caller inverts it with batch_inverse.  Reference evaluator.rs:56-116 divides every boundary
@@ -107,9 +117,17 @@ int boundary_vanishing(hipStream_t st, fe* zb, uint64_t N, uint32_t logN, const 
 int air_composition(hipStream_t st, const fe* lde, uint64_t count, uint64_t col_len, uint32_t stride_log, uint32_t logN, uint32_t logb,
                     const fe* roots_N, AirCompTables tabs, const AirProgram* prog_dev, const fe* ex_roots,
                     const fe* zbinv, fe* out, uint32_t shard_log = 0, uint32_t shard_rank = 0);
+// (both: tabs.pcols != null selects the instantiation that knows op 6, so a program without periodic columns runs the code it always ran)
 // validate_trace (debug.rs:13-104): the transition constraints on every row (one thread per row), then the boundary
-// values (one thread per constraint); *flag_dev |= 1 on any violation.
+// values (one thread per constraint); *flag_dev |= 1 on any violation.  Op 6 reads the periodic VALUES, not the table.
 int air_trace_check(hipStream_t st, const fe* trace, uint64_t n, AirCompTables tabs, const AirProgram* prog_dev, int* flag_dev);
+
+// Table of `cnt` periodic columns of period p = 2^logp <= AIR_PERIODIC_DIRECT_MAX without the transform plans: coef[v][m] = q_v's
+// coefficients from vals[v][.] (one thread per coefficient, p terms each), then tab[v][c][j] = q_v(hq w_(p b)^(j b + c)) by Horner (one
+// thread per entry, p steps).  hq = h^(n/p); roots_pb = NttEngine::roots(logp + logb).  p^2 (1 + b) products per column: 4352 at p = 16, b = 16.
+constexpr uint32_t AIR_PERIODIC_DIRECT_MAX = 16;
+int air_periodic_table_direct(hipStream_t st, const fe* vals, fe* coef, fe* tab, uint32_t cnt, uint32_t logp, uint32_t logb, const fe& hq,
+                              const fe* roots_pb);
 
 // Split of the composition polynomial (reference src/starks/prover.rs:250-252, evaluation_table.rs:27-33):
 // X = unscaled bit-reversed size-N inverse transform of the N evaluations; writes the h-scaled bit-reversed coefficient

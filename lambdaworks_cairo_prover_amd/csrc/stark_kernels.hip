@@ -1,6 +1,7 @@
 // Device kernels of the STARK rounds (see stark_kernels.h).
 #include "stark_kernels.h"
 #include "keccak.h"
+#include "ntt.h"
 
 namespace sp {
 
@@ -616,7 +617,10 @@ int boundary_vanishing(hipStream_t st, fe* zb, uint64_t N, uint32_t logN, const 
 // CHECK = false: composition evaluations, point i = element e = i << stride_log of every LDE column (as cairo_composition);
 // CHECK = true: the transition constraints on the trace itself (natural-order columns of n rows): *flag |= 1 if one is non-zero on a
 // row it is enforced on (the boundary values: air_boundary_check_kernel).
-template <bool CHECK>
+// PER: the program may read periodic columns (op 6): the exact check takes v[(i + offset) mod p] from the values, the composition
+// entry (coset c, (j + offset) mod p) of the column's table, j = iglob / b the trace row of the point - the GLOBAL index, so a
+// sharded context and the strided 2n-point evaluation read the entry of the point they stand on.
+template <bool CHECK, bool PER>
 __global__ void __launch_bounds__(256) air_composition_kernel(const fe* __restrict__ cols, uint64_t count, uint64_t col_len, uint32_t stride_log,
                                                               uint32_t logN, uint32_t logb, const fe* __restrict__ roots,
                                                               const AirCompTables K, const AirProgram* __restrict__ Pg,
@@ -640,6 +644,16 @@ __global__ void __launch_bounds__(256) air_composition_kernel(const fe* __restri
     for (uint32_t t = 0; t < n_ops; ++t) {
         const AirOpDev o = ops[t];
         fe r = fe_zero();
+        if constexpr (PER) {
+            if (o.op == 6) {
+                const AirPeriodicCol pc = K.pcols[o.b];
+                const uint32_t pm = (1u << pc.logp) - 1u, ofs = Pg->offsets[o.a];
+                if (CHECK) r = sk_ld(K.pvals + pc.off + (((uint32_t)i + ofs) & pm));
+                else r = sk_ld(K.ptab + (pc.off << logb) + ((uint64_t)c << pc.logp) + (((iglob >> logb) + ofs) & pm));
+                v[o.dst] = r;
+                continue;
+            }
+        }
         switch (o.op) {
             case 0: {   // frame row = trace row + offset: LDE index + offset * blowup (frame.rs:40-59), same coset
                 const uint64_t row = (e + (uint64_t)Pg->offsets[o.a] * (CHECK ? 1u : b_loc)) & (col_len - 1);
@@ -699,8 +713,10 @@ int air_composition(hipStream_t st, const fe* lde, uint64_t count, uint64_t col_
                     const fe* roots_N, AirCompTables tabs, const AirProgram* prog_dev, const fe* ex_roots,
                     const fe* zbinv, fe* out, uint32_t shard_log, uint32_t shard_rank) {
     if ((1u << logb) > CAIRO_MAX_BLOWUP) { sp_set_error("composition: blowup factor > 128 unsupported"); return SP_E_UNSUPPORTED; }
-    hipLaunchKernelGGL(air_composition_kernel<false>, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, lde, count, col_len, stride_log,
-                       logN, logb, roots_N, tabs, prog_dev, ex_roots, zbinv, out, (int*)nullptr, shard_log, shard_rank);
+    if (tabs.pcols) hipLaunchKernelGGL((air_composition_kernel<false, true>), dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, lde, count, col_len, stride_log,
+                                       logN, logb, roots_N, tabs, prog_dev, ex_roots, zbinv, out, (int*)nullptr, shard_log, shard_rank);
+    else hipLaunchKernelGGL((air_composition_kernel<false, false>), dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, lde, count, col_len, stride_log,
+                            logN, logb, roots_N, tabs, prog_dev, ex_roots, zbinv, out, (int*)nullptr, shard_log, shard_rank);
     SP_HIP_CHECK(hipGetLastError());
     return SP_OK;
 }
@@ -713,13 +729,57 @@ __global__ void __launch_bounds__(256) air_boundary_check_kernel(const fe* __res
 }
 
 int air_trace_check(hipStream_t st, const fe* trace, uint64_t n, AirCompTables tabs, const AirProgram* prog_dev, int* flag_dev) {
-    hipLaunchKernelGGL(air_composition_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, trace, n, n, 0u, 0u, 0u,
-                       (const fe*)nullptr, tabs, prog_dev, (const fe*)nullptr, (const fe*)nullptr, (fe*)nullptr, flag_dev, 0u, 0u);
+    if (tabs.pcols) hipLaunchKernelGGL((air_composition_kernel<true, true>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, trace, n, n, 0u, 0u, 0u,
+                                       (const fe*)nullptr, tabs, prog_dev, (const fe*)nullptr, (const fe*)nullptr, (fe*)nullptr, flag_dev, 0u, 0u);
+    else hipLaunchKernelGGL((air_composition_kernel<true, false>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, trace, n, n, 0u, 0u, 0u,
+                            (const fe*)nullptr, tabs, prog_dev, (const fe*)nullptr, (const fe*)nullptr, (fe*)nullptr, flag_dev, 0u, 0u);
     SP_HIP_CHECK(hipGetLastError());
     if (tabs.B) {
         hipLaunchKernelGGL(air_boundary_check_kernel, dim3((tabs.B + 255) / 256), dim3(256), 0, st, trace, n, tabs, flag_dev);
         SP_HIP_CHECK(hipGetLastError());
     }
+    return SP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- periodic columns, small periods
+// q_m = p^-1 sum_j v_j w_p^(-j m): winv[e] = w_p^(-e), e < p <= AIR_PERIODIC_DIRECT_MAX, by value
+struct PeriodicDirectArgs { fe winv[AIR_PERIODIC_DIRECT_MAX]; fe pinv; };
+__global__ void __launch_bounds__(256) periodic_coeffs_kernel(const fe* __restrict__ vals, fe* __restrict__ coef, uint32_t total, uint32_t logp,
+                                                              const PeriodicDirectArgs a) {
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= total) return;
+    const uint32_t p = 1u << logp, m = t & (p - 1);
+    const fe* __restrict__ v = vals + (t - m);
+    fe acc = fe_zero();
+    for (uint32_t j = 0; j < p; ++j) acc = acc + sk_ld(v + j) * a.winv[(j * m) & (p - 1)];
+    sk_st(coef + t, acc * a.pinv);
+}
+// tab[v][c][j] = q_v(hq w_(p b)^(j b + c))
+__global__ void __launch_bounds__(256) periodic_horner_kernel(const fe* __restrict__ coef, fe* __restrict__ tab, uint32_t total, uint32_t logp, uint32_t logb,
+                                                              const fe* __restrict__ roots_pb, const fe hq) {
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= total) return;
+    const uint32_t p = 1u << logp, j = t & (p - 1), c = (t >> logp) & ((1u << logb) - 1), col = t >> (logp + logb);
+    const fe x = root_pow(roots_pb, (j << logb) + c, logp + logb) * hq;
+    const fe* __restrict__ q = coef + ((uint64_t)col << logp);
+    fe acc = sk_ld(q + p - 1);
+    for (uint32_t m = p - 1; m-- > 0;) acc = acc * x + sk_ld(q + m);
+    sk_st(tab + t, acc);
+}
+int air_periodic_table_direct(hipStream_t st, const fe* vals, fe* coef, fe* tab, uint32_t cnt, uint32_t logp, uint32_t logb, const fe& hq,
+                              const fe* roots_pb) {
+    const uint32_t p = 1u << logp;
+    if (p > AIR_PERIODIC_DIRECT_MAX || logb < 1 || cnt == 0) return SP_E_INVALID_ARG;
+    PeriodicDirectArgs a;
+    const fe winv = logp ? fe_inv(host_primitive_root((int)logp)) : fe_one();
+    a.winv[0] = fe_one();
+    for (uint32_t e = 1; e < AIR_PERIODIC_DIRECT_MAX; ++e) a.winv[e] = fe_mul(a.winv[e - 1], winv);
+    a.pinv = fe_inv(fe_from_u64(p));
+    const uint32_t nc = cnt << logp, nt = nc << logb;
+    hipLaunchKernelGGL(periodic_coeffs_kernel, dim3((nc + 255) / 256), dim3(256), 0, st, vals, coef, nc, logp, a);
+    SP_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(periodic_horner_kernel, dim3((nt + 255) / 256), dim3(256), 0, st, coef, tab, nt, logp, logb, roots_pb, hq);
+    SP_HIP_CHECK(hipGetLastError());
     return SP_OK;
 }
 

@@ -213,8 +213,17 @@ struct VerifySpec {
     uint32_t bound_factor = 2;   // composition_poly_degree_bound / trace_length
     uint32_t n_rap = 0;
     std::function<std::vector<BoundaryConstraint>(const std::vector<fe>& rap)> boundary;
-    std::function<void(const fe* frame /*[rows][C]*/, const std::vector<fe>& rap, fe* out)> transition;
+    // periodic: for every frame row r the values P_k(z g^offsets[r]) of the AIR's periodic columns, [rows][periodic_coeffs.size()]
+    std::function<void(const fe* frame /*[rows][C]*/, const fe* periodic, const std::vector<fe>& rap, fe* out)> transition;
+    std::vector<std::vector<fe>> periodic_coeffs;   // q of every periodic column (air_periodic_interpolate)
 };
+
+// the primitive root of unity of order 2^order (lambdaworks get_primitive_root_of_unity): the field's 2^192-th root, squared down
+static fe root_of(int order) {
+    fe w = fe_from_bytes_be((const uint8_t*)"\x00\x52\x82\xdb\x87\x52\x9c\xfa\x3f\x04\x64\x51\x9c\x8b\x0f\xa5\xad\x18\x71\x48\xe1\x1a\x61\x61\x60\x70\x02\x4f\x42\xf8\xef\x94");
+    for (int i = order; i < 192; ++i) w = fe_sqr(w);
+    return w;
+}
 
 // returns 1 accept, 0 reject; throws on malformed input
 static int verify_host(const uint8_t* proof_bytes, size_t len, const VerifySpec& air, uint8_t blowup, uint64_t queries, uint64_t coset_offset, uint8_t grinding) {
@@ -232,7 +241,6 @@ static int verify_host(const uint8_t* proof_bytes, size_t len, const VerifySpec&
     if (pr.ood.size() != (size_t)R * C || pr.row_width != C || pr.trace_roots.size() != n_roots || pr.fri_roots.size() != (size_t)k) return 0;
     for (uint32_t c = 0; c < T; ++c) if (air.degrees[c] < 1 || air.degrees[c] > f + 1 || air.exemptions[c] >= n) return 0;
     const fe h = fe_from_u64(coset_offset), hinv = fe_inv(h);
-    auto root_of = [&](int order) { fe w = fe_from_bytes_be((const uint8_t*)"\x00\x52\x82\xdb\x87\x52\x9c\xfa\x3f\x04\x64\x51\x9c\x8b\x0f\xa5\xad\x18\x71\x48\xe1\x1a\x61\x61\x60\x70\x02\x4f\x42\xf8\xef\x94"); for (int i = order; i < 192; ++i) w = fe_sqr(w); return w; };
     const fe g = root_of(k), w = root_of(k + lb);
     // ---- step 1: replay the transcript (verifier.rs:59-206)
     Transcript t;
@@ -284,7 +292,16 @@ static int verify_host(const uint8_t* proof_bytes, size_t len, const VerifySpec&
             bq = fe_add(bq, fe_mul(fe_mul(num, fe_inv(den)), fe_add(fe_mul(ba[j], bdz), bb[j])));
         }
         std::vector<fe> cons(T);
-        air.transition(pr.ood.data(), rap, cons.data());
+        const size_t Kp = air.periodic_coeffs.size();
+        std::vector<fe> per((size_t)R * Kp);
+        for (uint32_t r = 0; r < R && Kp; ++r) {
+            const fe zr = fe_mul(z, fe_pow_u64(g, air.offsets[r]));
+            for (size_t kp = 0; kp < Kp; ++kp) {
+                if (air.periodic_coeffs[kp].size() > n) return 0;
+                per[(size_t)r * Kp + kp] = air_periodic_eval(air.periodic_coeffs[kp], n, zr);
+            }
+        }
+        air.transition(pr.ood.data(), per.data(), rap, cons.data());
         fe zden = fe_sub(zn, fe_one());
         if (fe_is_zero(zden)) return 0;
         fe zf = fe_inv(zden);
@@ -384,22 +401,24 @@ int cairo_verify_host(const uint8_t* proof_bytes, size_t len, const PublicInputs
     const bool has_rc = info.has_rc_builtin;
     const uint32_t C = info.trace_columns;
     spec.boundary = [&pub, n, has_rc](const std::vector<fe>& rap) { fe r[3] = {rap[0], rap[1], rap[2]}; return boundary_constraints(pub, r, n, has_rc); };
-    spec.transition = [C, has_rc](const fe* frame, const std::vector<fe>& rap, fe* out) { fe r[3] = {rap[0], rap[1], rap[2]}; cairo_transition_host(frame, C, has_rc, r, out); };
+    spec.transition = [C, has_rc](const fe* frame, const fe*, const std::vector<fe>& rap, fe* out) { fe r[3] = {rap[0], rap[1], rap[2]}; cairo_transition_host(frame, C, has_rc, r, out); };
     return verify_host(proof_bytes, len, spec, blowup, queries, coset_offset, grinding);
 }
 
 // `verify::<F, A>` for a program AIR (include/stark252_hip.h sp_air_desc); ops as in AirOpDev of stark_kernels.h.
-int air_verify_host(const uint8_t* proof_bytes, size_t len, const AirDescHost& air, const ProofOptionsHost& opt) {
+int air_verify_host(const uint8_t* proof_bytes, size_t len, const AirDescHost& air, const ProofOptionsHost& opt, const AirPeriodicHost* periodic) {
     const uint32_t C = air.main_cols + air.aux_cols, T = (uint32_t)air.degrees.size(), R = (uint32_t)air.offsets.size();
     if (T == 0 || R == 0 || air.exemptions.size() != T || air.degree_bound_factor < 1 || C < air.main_cols) return 0;   // (C < main_cols: the sum wrapped)
     const std::vector<AirOpHost>& ops = air.ops;
     const std::vector<fe>& consts = air.consts;
-    if (air_program_first_bad_op(ops, R, C, consts.size() + air.n_rap, T) < ops.size()) throw std::runtime_error("malformed: constraint program");
+    const uint32_t Kp = periodic ? (uint32_t)periodic->cols.size() : 0u;
+    if (air_program_first_bad_op(ops, R, C, consts.size() + air.n_rap, T, Kp) < ops.size()) throw std::runtime_error("malformed: constraint program");
     VerifySpec spec;
+    for (uint32_t k = 0; k < Kp; ++k) spec.periodic_coeffs.push_back(air_periodic_interpolate(periodic->cols[k]));
     spec.main_cols = air.main_cols; spec.aux_cols = air.aux_cols; spec.offsets = air.offsets; spec.degrees = air.degrees; spec.exemptions = air.exemptions;
     spec.bound_factor = air.degree_bound_factor; spec.n_rap = air.n_rap;
     spec.boundary = [&air](const std::vector<fe>&) { return air.boundary; };
-    spec.transition = [&ops, &consts, C, T](const fe* frame, const std::vector<fe>& rap, fe* out) {
+    spec.transition = [&ops, &consts, C, T, Kp](const fe* frame, const fe* per, const std::vector<fe>& rap, fe* out) {
         std::vector<fe> v(ops.size(), fe_zero());
         for (uint32_t k = 0; k < T; ++k) out[k] = fe_zero();
         for (size_t t = 0; t < ops.size(); ++t) {
@@ -410,6 +429,7 @@ int air_verify_host(const uint8_t* proof_bytes, size_t len, const AirDescHost& a
                 case 2: v[t] = fe_add(v[a], v[b]); break;
                 case 3: v[t] = fe_sub(v[a], v[b]); break;
                 case 4: v[t] = fe_mul(v[a], v[b]); break;
+                case 6: v[t] = per[(size_t)a * Kp + b]; break;
                 default: out[a] = v[b]; break;
             }
         }
@@ -417,7 +437,45 @@ int air_verify_host(const uint8_t* proof_bytes, size_t len, const AirDescHost& a
     return verify_host(proof_bytes, len, spec, opt.blowup_factor, opt.fri_number_of_queries, opt.coset_offset, opt.grinding_factor);
 }
 
-size_t air_program_first_bad_op(const std::vector<AirOpHost>& ops, uint32_t load_a_end, uint32_t load_b_end, size_t n_values, uint32_t n_out) {
+// q from its values on <w_p>: an in-place radix-2 inverse transform (bit-reversal, then butterflies with w_p^-1), times 1/p
+std::vector<fe> air_periodic_interpolate(const std::vector<fe>& values) {
+    const size_t p = values.size();
+    const int lp = sp_log2_exact(p);
+    if (lp < 0) throw std::runtime_error("malformed: periodic column period");
+    std::vector<fe> a(p);
+    for (size_t i = 0; i < p; ++i) {
+        size_t r = 0;
+        for (int bit = 0; bit < lp; ++bit) r |= ((i >> bit) & 1) << (lp - 1 - bit);
+        a[r] = values[i];
+    }
+    const fe winv = lp ? fe_inv(root_of(lp)) : fe_one();
+    for (int s = 1; s <= lp; ++s) {
+        const size_t m = size_t(1) << s, half = m >> 1;
+        const fe wm = fe_pow_u64(winv, p / m);
+        std::vector<fe> tw(half);
+        tw[0] = fe_one();
+        for (size_t j = 1; j < half; ++j) tw[j] = fe_mul(tw[j - 1], wm);
+        for (size_t k = 0; k < p; k += m)
+            for (size_t j = 0; j < half; ++j) {
+                const fe t = fe_mul(tw[j], a[k + j + half]), u = a[k + j];
+                a[k + j] = fe_add(u, t);
+                a[k + j + half] = fe_sub(u, t);
+            }
+    }
+    const fe pinv = fe_inv(fe_from_u64(p));
+    for (auto& x : a) x = fe_mul(x, pinv);
+    return a;
+}
+
+fe air_periodic_eval(const std::vector<fe>& coeffs, uint64_t n, const fe& point) {
+    const fe y = fe_pow_u64(point, n / coeffs.size());
+    fe acc = fe_zero();
+    for (size_t m = coeffs.size(); m-- > 0;) acc = fe_add(fe_mul(acc, y), coeffs[m]);
+    return acc;
+}
+
+size_t air_program_first_bad_op(const std::vector<AirOpHost>& ops, uint32_t load_a_end, uint32_t load_b_end, size_t n_values, uint32_t n_out,
+                                uint32_t n_periodic) {
     auto value = [&](uint32_t i, size_t t) { return i < t && ops[i].op != 5; };   // an earlier op that produces a value
     for (size_t t = 0; t < ops.size(); ++t) {
         const AirOpHost& o = ops[t];
@@ -427,6 +485,7 @@ size_t air_program_first_bad_op(const std::vector<AirOpHost>& ops, uint32_t load
             case 1: ok = o.a < n_values; break;
             case 2: case 3: case 4: ok = value(o.a, t) && value(o.b, t); break;
             case 5: ok = o.a < n_out && value(o.b, t); break;
+            case 6: ok = o.a < load_a_end && o.b < n_periodic; break;
             default: ok = false;
         }
         if (!ok) return t;

@@ -2,8 +2,10 @@
 grinding 20, 64 transition constraints each tying together 4 column recurrences, 512 boundary constraints on 64 distinct rows
 (--boundary-rows 3: the same 512 folded onto 3 rows, which prices the many-row boundary path).  One warm-up proof, then --reps
 timed proofs on one GPU; prints one JSON line: the median and sp_last_round_ms of the last proof (rounds 1 - 4, device time).
+--periodic K --period P: the same shape with K periodic columns of period P (sp_air_prove_periodic): column j < K counts up by
+k_j + Q_j(i mod P), so its recurrence reads periodic column j, and the boundary values follow the changed trace.
 
-    python tools/air_wide_bench.py [--boundary-rows 64] [--reps 5] [--log-n 18]
+    python tools/air_wide_bench.py [--boundary-rows 64] [--reps 5] [--log-n 18] [--periodic 8 --period 64]
 """
 import argparse
 import json
@@ -16,8 +18,39 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+import numpy as np  # noqa: E402
+
 import many_column_air as M  # noqa: E402
-from lambdaworks_cairo_prover_amd import api  # noqa: E402
+from lambdaworks_cairo_prover_amd import air, api  # noqa: E402
+
+
+def build_periodic(n, cols, n_transitions, boundary_rows, boundary_total, k_periodic, period):
+    """The shape of M.build with x_j(i + 1) = x_j(i) + k_j + Q_j(i mod period) for the first k_periodic columns; (builder, trace)."""
+    q = [[(5 * j + 3 * t * t + 1) % 1000 for t in range(period)] for j in range(k_periodic)]
+    b = air.AirBuilder(cols, [0, 1], 1, periodic=q)
+    groups = [[] for _ in range(n_transitions)]
+    for j in range(cols):
+        groups[j % n_transitions].append(j)
+    for g in groups:
+        acc = None
+        for j in g:
+            rec = b.load(1, j) - b.load(0, j) - M.column_step(j)
+            if j < k_periodic:
+                rec = rec - b.periodic(0, j)
+            w = j % 5 + 1
+            term = rec if w == 1 else rec * w
+            acc = term if acc is None else acc + term
+        b.constraint(acc, 1, 1)
+    trace = M.main_trace(n, cols)
+    values = {}
+    for j in range(k_periodic):
+        bump = np.concatenate(([0], np.cumsum(np.tile(np.array(q[j], dtype=np.uint64), n // period))[:-1])).astype(np.uint64)
+        col = np.uint64(M.column_start(j)) + np.arange(n, dtype=np.uint64) * np.uint64(M.column_step(j)) + bump
+        trace[:, j, 24:] = col.astype(">u8").view(np.uint8).reshape(n, 8)
+        values[j] = col
+    for col, step in M.boundary_list(n, cols, boundary_rows, boundary_total):
+        b.boundary(col, step, int(values[col][step]) if col in values else M.cell(step, col))
+    return b, trace
 
 
 def main():
@@ -25,14 +58,20 @@ def main():
     ap.add_argument("--boundary-rows", type=int, default=64)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--log-n", type=int, default=18)
+    ap.add_argument("--periodic", type=int, default=0, help="periodic columns read by the first recurrences (0: the plain shape)")
+    ap.add_argument("--period", type=int, default=64)
     args = ap.parse_args()
     n, cols, options = 1 << args.log_n, 256, (4, 80, 3, 20)
-    b = M.build(n, cols, n_transitions=64, boundary_row_count=args.boundary_rows, boundary_total=512)
+    if args.periodic:
+        b, trace = build_periodic(n, cols, 64, args.boundary_rows, 512, args.periodic, args.period)
+    else:
+        b = M.build(n, cols, n_transitions=64, boundary_row_count=args.boundary_rows, boundary_total=512)
+        trace = M.main_trace(n, cols)
     desc, keep = b.build()
-    trace = M.main_trace(n, cols)
     opt = api.ProofOptions(*options)
     with api.Context(device=0) as ctx:
         proof = ctx.air_prove(desc, trace, opt)            # warm-up: set-up of the shape, first launches
+        assert ctx.last_proof_info()["composition_path"] == 1, "the trace does not satisfy its constraints"
         times = []
         for _ in range(args.reps):
             t0 = time.perf_counter()
@@ -42,6 +81,7 @@ def main():
         rounds = ctx.last_round_ms()
     print(json.dumps({"tool": "air_wide_bench", "rows": n, "main_cols": cols, "transitions": len(b.degrees), "ops": len(b.ops),
                       "constants": len(b.consts), "boundary_constraints": len(b.bcs), "boundary_rows": args.boundary_rows,
+                      "periodic_columns": args.periodic, "period": args.period if args.periodic else 0,
                       "options": options, "proof_bytes": len(proof), "median_ms": round(statistics.median(times), 2),
                       "min_ms": round(min(times), 2), "max_ms": round(max(times), 2), "last_round_ms": [round(x, 2) for x in rounds[1:]]}))
 
