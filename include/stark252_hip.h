@@ -75,7 +75,8 @@ const char* sp_version(void);
  * sp_proof_options_* / sp_proof_file_verify / SP_OPT_HOST_RANKS family and sp_set_collective keeping the prover across re-installs
  * of the same world; 5: sp_fe_mul; 6: sp_air_limits, sp_air_prove beyond 64 columns and 3 boundary rows; 7: sp_air_prove_aux, sp_air_aux_desc,
  * sp_air_aux_desc_size, sp_air_prove_periodic, sp_air_verify_periodic, sp_air_periodic_desc_size, sp_air_periodic_limits,
- * sp_air_periodic_eval, sp_air_periodic_lde).  A binding compares it (and sp_air_desc_size against its own idea of the struct) when it loads the library, so
+ * sp_air_periodic_eval, sp_air_periodic_lde; sp_air_check_trace and sp_air_violation_size joined under 7 - they change no structure
+ * and no call, and a binding finds a build without them by probing the symbols).  A binding compares it (and sp_air_desc_size against its own idea of the struct) when it loads the library, so
  * a stale build fails at load time with "rebuild the library" instead of with a missing symbol or shifted fields later. */
 #define SP_ABI_VERSION 7
 int sp_abi_version(void);
@@ -491,6 +492,34 @@ int sp_air_verify_periodic(const uint8_t* proof, uint64_t proof_len, const sp_ai
  * the period are powers of two with blowup >= 2, n x blowup <= 2^30 and 1 <= period <= n (SP_E_INVALID_ARG otherwise), as a proof's are. */
 int sp_air_periodic_eval(const sp_air_periodic_column* col, uint64_t n, const uint8_t point[32], uint8_t out[32]);
 int sp_air_periodic_lde(sp_ctx* ctx, const sp_air_periodic_column* col, uint64_t n, uint32_t blowup, const uint8_t coset[32], uint8_t* out);
+
+/* Which constraints of a program AIR a trace breaks, and where (reference validate_trace, src/starks/debug.rs:13-104, which logs the
+ * constraint, the step and the value).  sp_air_prove proves a constraint-violating trace anyway, as the reference does; the only
+ * signal there is the 3 in sp_last_proof_info and a proof the verifier rejects.  This call produces no proof.
+ *   air, aux (nullable), periodic (nullable), main_trace, n: what sp_air_prove_periodic takes, with its argument checks and error codes.
+ *   rap: air->n_rap x 32 bytes in the context encoding - the auxiliary columns (aux_kind 1, 2 or 3) are built from these challenges -
+ *        or NULL: the challenges a proof under `opt` would sample (round 1's main commitment, then n_rap transcript samples).
+ *   opt: required when rap == NULL (SP_E_INVALID_ARG without both); with rap it only sizes the commitments, and may be NULL.
+ * The trace checked is main || aux as the prover holds it before round 2, reached through the prover's own ingest and auxiliary
+ * builders (round 1 runs, commitments included).  Constraint k is enforced on rows 0 .. n - 1 - e_k, frame rows wrapping modulo n;
+ * e_k is the exemption count the composition uses for it: exemptions[k], or - with num_transition_exemptions == 1 - the first
+ * non-zero entry of exemptions[] for every constraint that has one.
+ * out receives the violated constraints, transitions first by index, then boundary constraints by index - at most `cap` records;
+ * *n_out is their total number and may exceed cap (0: the trace satisfies the AIR).  out may be NULL with cap == 0.  SP_OK whether
+ * or not anything is violated; a zero denominator in an aux program stays SP_E_ZERO_INVERSE; SP_E_UNSUPPORTED on a context with
+ * world > 1.  A later proof on the context is not affected. */
+typedef struct {
+    uint32_t kind;        /* 0 transition constraint, 1 boundary constraint */
+    uint32_t index;       /* transition: constraint index (OUT's a); boundary: index into air->boundary */
+    uint64_t rows;        /* enforced rows on which it is non-zero (boundary: 1) */
+    uint64_t first_row;   /* lowest such row (boundary: its step) */
+    uint64_t last_row;    /* highest such row (boundary: its step) */
+    uint8_t  value[32];   /* canonical BE.  transition: the evaluation on first_row; boundary: the cell found */
+} sp_air_violation;
+uint64_t sp_air_violation_size(void);
+int sp_air_check_trace(sp_ctx* ctx, const sp_air_desc* air, const sp_air_aux_desc* aux, const sp_air_periodic_desc* periodic,
+                       const uint8_t* main_trace, uint64_t n, const sp_proof_options* opt, const uint8_t* rap,
+                       sp_air_violation* out, uint32_t cap, uint32_t* n_out);
 
 /* verify::<Stark252PrimeField, A> (reference src/starks/verifier.rs:559-657) on the host CPU: 1 accept, 0 reject (also for
  * malformed proofs or descriptors). */

@@ -13,6 +13,7 @@ Periodic columns (an extension beyond the reference's trait): AirBuilder(..., pe
 sequences that repeat down the trace (each a power-of-two number of values, at most the trace length); b.periodic(row, k) reads
 column k at frame row `row`.  In a constraint's declared degree such a value counts as a trace cell.  See mimc_chain below.
 """
+import collections
 import ctypes
 
 P = 2**251 + 17 * 2**192 + 1
@@ -88,6 +89,25 @@ def _check_periodic_layout():
     want = _lib.load().sp_air_periodic_desc_size()
     if ctypes.sizeof(AirPeriodicDescC) != want:
         raise ImportError(f"AirPeriodicDescC is {ctypes.sizeof(AirPeriodicDescC)} bytes, the library's sp_air_periodic_desc {want}: the binding is out of date")
+
+
+class AirViolationC(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_uint32), ("index", ctypes.c_uint32), ("rows", ctypes.c_uint64), ("first_row", ctypes.c_uint64),
+                ("last_row", ctypes.c_uint64), ("value", ctypes.c_uint8 * 32)]
+
+
+def _check_violation_layout():
+    from . import _lib
+    want = _lib.load().sp_air_violation_size()
+    if ctypes.sizeof(AirViolationC) != want:
+        raise ImportError(f"AirViolationC is {ctypes.sizeof(AirViolationC)} bytes, the library's sp_air_violation {want}: the binding is out of date")
+
+
+# One violated constraint, as sp_air_check_trace reports it (sp_air_violation): kind 0 a transition constraint (index = its number;
+# rows = enforced rows on which it is non-zero, first_row / last_row the lowest / highest of them, value its evaluation on first_row),
+# kind 1 a boundary constraint (index into the builder's list; rows 1, first_row = last_row = its step, value the cell found).
+Violation = collections.namedtuple("Violation", "kind index rows first_row last_row value")
+TRANSITION, BOUNDARY = 0, 1
 
 
 def periodic_desc(columns):
@@ -305,6 +325,67 @@ class AirBuilder:
 
     def boundary(self, col, step, value):
         self.bcs.append((col, step, value % P))
+
+    def enforced_exemptions(self):
+        """Per constraint, the number of last rows it is not enforced on - what the composition uses: its own exemption count, or,
+        with num_transition_exemptions == 1, the first non-zero count of the AIR for every constraint that has one."""
+        nonzero = [e for e in self.exemptions if e > 0]
+        if self.num_transition_exemptions == 1 and nonzero:
+            return [nonzero[0] if e > 0 else 0 for e in self.exemptions]
+        return list(self.exemptions)
+
+    def check_trace(self, rows, rap=()):
+        """Which constraints the trace breaks, and where, in Python integers: the model of sp_air_check_trace (the reference's
+        validate_trace, src/starks/debug.rs:13-104).  rows: (n, main_cols + aux_cols) ints, main||aux; with an aux program also
+        (n, main_cols), to which self.aux.evaluate(rows, rap) is appended.  rap: the RAP challenges.  Constraint k is enforced on rows
+        0 .. n - 1 - enforced_exemptions()[k]; frame rows wrap modulo n.  Returns [Violation, ...]: the transition constraints by
+        index, then the boundary constraints by index; [] for a trace that satisfies the AIR."""
+        import numpy as np
+        m = np.empty((len(rows), len(rows[0])), dtype=object)
+        m[:, :] = rows if not isinstance(rows, np.ndarray) else rows.astype(object)
+        m %= P
+        n = m.shape[0]
+        rap = [int(r) % P for r in rap]
+        if len(rap) != self.n_rap:
+            raise ValueError(f"check_trace: {len(rap)} RAP challenges for an AIR with n_rap = {self.n_rap}")
+        if self.aux is not None and m.shape[1] == self.main_cols and self.aux_cols:
+            m = np.concatenate([m, self.aux.evaluate(m, rap)], axis=1)
+        if m.shape[1] != self.main_cols + self.aux_cols:
+            raise ValueError(f"check_trace: {m.shape[1]} columns, the AIR has {self.main_cols} + {self.aux_cols}")
+        consts = list(self.consts) + rap
+        index = np.arange(n)
+        vals, outs = [], {}
+        for op, a, b in self.ops:
+            v = None
+            if op == OP_LOAD:
+                v = np.roll(m[:, b], -self.offsets[a])
+            elif op == OP_CONST:
+                v = np.full(n, consts[len(self.consts) + (a & ~_RAP_TAG) if a & _RAP_TAG else a], dtype=object)
+            elif op == OP_ADD:
+                v = (vals[a] + vals[b]) % P
+            elif op == OP_SUB:
+                v = (vals[a] - vals[b]) % P
+            elif op == OP_MUL:
+                v = (vals[a] * vals[b]) % P
+            elif op == OP_PERIODIC:
+                values = self.periodic_cols[b]
+                v = np.array(values, dtype=object)[(index + self.offsets[a]) % len(values)]
+            elif op == OP_OUT:
+                outs[a] = vals[b]
+            else:
+                raise ValueError(f"check_trace: op {op}")
+            vals.append(v)
+        found = []
+        for k, ex in enumerate(self.enforced_exemptions()):
+            if k not in outs:
+                continue
+            bad = [i for i in range(max(0, n - ex)) if outs[k][i] != 0]
+            if bad:
+                found.append(Violation(TRANSITION, k, len(bad), bad[0], bad[-1], int(outs[k][bad[0]])))
+        for j, (col, step, value) in enumerate(self.bcs):
+            if int(m[step, col]) != value:
+                found.append(Violation(BOUNDARY, j, 1, step, step, int(m[step, col])))
+        return found
 
     def check_limits(self):
         """Raises ValueError naming the first bound of sp_air_limits (api.air_limits) this AIR exceeds."""

@@ -243,6 +243,38 @@ class Context:
         self._lib.sp_free(out)
         return proof
 
+    def air_check_trace(self, desc, main_trace, options=None, rap=None, cap=4160):
+        """sp_air_check_trace: which constraints of the AIR the trace breaks, and where - [air.Violation, ...] as AirBuilder.check_trace
+        gives them (transition constraints by index, then boundary constraints by index; [] for a satisfying trace), at most `cap` of
+        them.  desc and main_trace as for air_prove (the same dispatch on desc.aux_desc / desc.periodic_desc).  rap: the RAP challenges
+        (ints) the auxiliary columns are built from; None: those a proof under `options` would sample.  No proof is produced."""
+        from . import air
+        if rap is None and options is None:
+            raise ValueError("air_check_trace: without rap, the options of the proof whose challenges are wanted are needed")
+        air._check_violation_layout()
+        a = np.ascontiguousarray(main_trace, dtype=np.uint8)
+        n, cols = a.shape[0], a.shape[1]
+        assert cols == desc.main_cols
+        opt = None if options is None else options.to_c()
+        rap_bytes = None
+        if rap is not None:
+            if len(rap) != desc.n_rap:
+                raise ValueError(f"air_check_trace: {len(rap)} RAP challenges for an AIR with n_rap = {desc.n_rap}")
+            rap_bytes = np.zeros((max(1, len(rap)), 32), dtype=np.uint8)
+            if len(rap):
+                be = felts_to_bytes([int(r) % P for r in rap])
+                rap_bytes[:] = be if self.fe_encoding == SP_FE_CANON_BE else fe_from_device(fe_to_device(be, SP_FE_CANON_BE), self.fe_encoding)
+        out = (air.AirViolationC * max(1, cap))()
+        total = ctypes.c_uint32(0)
+        aux = getattr(desc, "aux_desc", None)
+        per = getattr(desc, "periodic_desc", None)
+        check(self._lib.sp_air_check_trace(self._h, ctypes.byref(desc), None if aux is None else ctypes.byref(aux), None if per is None else ctypes.byref(per),
+                                           _u8p(a), ctypes.c_uint64(n), None if opt is None else ctypes.byref(opt), None if rap_bytes is None else _u8p(rap_bytes),
+                                           out if cap else None, ctypes.c_uint32(cap), ctypes.byref(total)))
+        self.last_check_total = total.value     # the number of violated constraints, which may exceed cap
+        return [air.Violation(int(v.kind), int(v.index), int(v.rows), int(v.first_row), int(v.last_row), int.from_bytes(bytes(v.value), "big"))
+                for v in out[:min(cap, total.value)]]
+
     def air_periodic_lde(self, values, n, blowup, coset):
         """sp_air_periodic_lde: the table the composition kernel reads for one periodic column (`values`: ints, a power-of-two number
         of them) on a trace of n rows, in natural order: (period * blowup, 32) canonical big-endian, row k = P(coset w_N^k)."""

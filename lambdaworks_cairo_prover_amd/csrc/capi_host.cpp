@@ -122,6 +122,7 @@ int sp_abi_version(void) { return SP_ABI_VERSION; }
 uint64_t sp_air_desc_size(void) { return sizeof(sp_air_desc); }
 uint64_t sp_air_aux_desc_size(void) { return sizeof(sp_air_aux_desc); }
 uint64_t sp_air_periodic_desc_size(void) { return sizeof(sp_air_periodic_desc); }
+uint64_t sp_air_violation_size(void) { return sizeof(sp_air_violation); }
 int sp_air_periodic_limits(uint32_t out[4]) {
     if (!out) return SP_E_INVALID_ARG;
     out[0] = sp::AIR_MAX_PERIODIC; out[1] = out[2] = out[3] = 0u;

@@ -425,4 +425,33 @@ int sp_air_prove_periodic(sp_ctx* c, const sp_air_desc* d, const sp_air_aux_desc
     } catch (const std::exception& e) { sp_set_error(e.what()); return SP_E_INVALID_ARG; }
 }
 
+int sp_air_check_trace(sp_ctx* c, const sp_air_desc* d, const sp_air_aux_desc* x, const sp_air_periodic_desc* pd, const uint8_t* main_trace,
+                       uint64_t n, const sp_proof_options* opt, const uint8_t* rap, sp_air_violation* out, uint32_t cap, uint32_t* n_out) {
+    if (!c || !d || !main_trace || !n_out || (!opt && !rap) || (!out && cap)) return SP_E_INVALID_ARG;
+    try {
+        sp::AirDescHost a;
+        if (!air_desc_from_c(d, a)) { sp_set_error("sp_air_check_trace: malformed descriptor"); return SP_E_INVALID_ARG; }
+        sp::AirPeriodicHost periodic;
+        if (pd && !sp::air_periodic_from_c(pd, n, periodic)) {
+            sp_set_error("sp_air_check_trace: malformed periodic columns (at most 64, each a power-of-two number of values, at most the trace length)");
+            return SP_E_INVALID_ARG;
+        }
+        sp::AirAuxHost aux;
+        if (x) SP_TRY(aux_from_c(d, x, aux));
+        c->prewarm_cancel.store(0, std::memory_order_release);   // (the context is first touched here: the descriptors are judged without it)
+        std::vector<fe> rap_fe(a.n_rap);
+        if (rap && a.n_rap) SP_TRY(dec(c, rap, a.n_rap, rap_fe.data()));
+        const sp::ProofOptionsHost oh = opt ? proof_options_from_c(opt) : sp::ProofOptionsHost{};
+        std::vector<sp::AirViolationHost> found;
+        SP_TRY(sp::air_check_trace(c, a, main_trace, n, opt ? &oh : nullptr, rap ? &rap_fe : nullptr, found, x ? &aux : nullptr, pd ? &periodic : nullptr));
+        *n_out = (uint32_t)found.size();
+        for (size_t i = 0; i < found.size() && i < cap; ++i) {
+            const sp::AirViolationHost& v = found[i];
+            out[i].kind = v.kind; out[i].index = v.index; out[i].rows = v.rows; out[i].first_row = v.first_row; out[i].last_row = v.last_row;
+            fe_to_bytes_be(v.value, out[i].value);
+        }
+        return SP_OK;
+    } catch (const std::exception& e) { sp_set_error(e.what()); return SP_E_INVALID_ARG; }
+}
+
 }  // extern "C"

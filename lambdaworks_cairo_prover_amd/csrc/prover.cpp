@@ -14,8 +14,8 @@ int StarkProver::wait_stream() {
 }
 
 int StarkProver::readback(void* dst_host, const void* src_dev, size_t bytes) {
-    if (bytes > 4096) { sp_set_error("readback: more than the 4 KB pinned slot"); return SP_E_INVALID_ARG; }
     SP_TRY(ensure_pin());
+    if (bytes > h_pin_.bytes) SP_TRY(h_pin_.ensure(bytes, "pinned read-back slot"));   // (nothing is in flight into the slot between two calls)
     SP_HIP_CHECK(hipMemcpyAsync(h_pin_.p, src_dev, bytes, hipMemcpyDeviceToHost, c_->stream));
     SP_TRY(wait_stream());
     memcpy(dst_host, h_pin_.p, bytes);
@@ -688,31 +688,30 @@ int air_periodic_tables(hipStream_t st, NttEngine& ntt, fe* vals, fe* ws, fe* ta
     return ntt.lde_coset_major(vals, tab, (int)logp, (int)logb, cnt, p, p << logb);
 }
 
-int StarkProver::composition_air(const AirDescHost& air, const std::vector<fe>& rap, const std::vector<fe>& b_alpha, const std::vector<fe>& b_beta,
-                                 const std::vector<fe>& t_alpha, const std::vector<fe>& t_beta, uint8_t root_out[32], const AirPeriodicHost* periodic) {
-    if (stage_ != 3 && !(stage_ == 2 && Ca_ == 0)) { sp_set_error("composition: trace segments not committed"); return SP_E_STATE; }
+// The device form of an AIR's constraint program, and what of the descriptor goes with it: checked against the committed trace, values
+// in slots, the periodic columns' places, the exemptions as both the composition and the trace check use them.
+int StarkProver::build_air_program(const AirDescHost& air, size_t n_rap, const AirPeriodicHost* periodic, AirProgramHost& out) {
     const uint32_t T = (uint32_t)air.degrees.size(), B = (uint32_t)air.boundary.size(), R = (uint32_t)air.offsets.size();
     if (T == 0 || T > AIR_MAX_TRANSITIONS || B > AIR_MAX_BOUNDARY || R == 0 || R > AIR_MAX_OFFSETS || air.exemptions.size() != T ||
-        t_alpha.size() != T || t_beta.size() != T || b_alpha.size() != B || b_beta.size() != B || air.ops.size() > AIR_MAX_OPS ||
-        air.consts.size() > AIR_MAX_CONSTS || air.consts.size() + rap.size() > 65535 || rap.size() != air.n_rap || air.main_cols != Cm_ || air.aux_cols != Ca_ ||
-        air.degree_bound_factor < 1) {
+        air.ops.size() > AIR_MAX_OPS || air.consts.size() > AIR_MAX_CONSTS || air.consts.size() + n_rap > 65535 || n_rap != air.n_rap ||
+        air.main_cols != Cm_ || air.aux_cols != Ca_ || air.degree_bound_factor < 1) {
         sp_set_error("composition_air: descriptor out of range or inconsistent with the committed trace");
         return SP_E_INVALID_ARG;
     }
-    SP_HIP_CHECK(hipSetDevice(c_->device));
-    const uint32_t b = 1u << logb_, f = air.degree_bound_factor;
+    const uint32_t f = air.degree_bound_factor;
     // --- validate the program (every operand refers to an earlier value, cells exist) and build the device copy: every
     //     value gets a slot of the per-point value file, released after its last use (the program is straight-line)
-    AirProgram prog;
+    AirProgram& prog = out.prog;
     std::memset(&prog, 0, sizeof(prog));
-    std::vector<AirOpDev> dops;
+    std::vector<AirOpDev>& dops = out.dops;
     prog.n_ops = (uint32_t)air.ops.size();
     prog.n_offsets = R;
     for (uint32_t k = 0; k < R; ++k) prog.offsets[k] = air.offsets[k];
     // --- periodic columns: column k's values at pvals + off_k (off_k = the periods before it, summed), its table at ptab + off_k b
     const uint32_t Kp = periodic ? (uint32_t)periodic->cols.size() : 0u;
     if (Kp > AIR_MAX_PERIODIC) { sp_set_error("composition_air: more than 64 periodic columns"); return SP_E_INVALID_ARG; }
-    std::vector<AirPeriodicCol> pcols(Kp);
+    std::vector<AirPeriodicCol>& pcols = out.pcols;
+    pcols.assign(Kp, AirPeriodicCol{});
     uint64_t S = 0;
     for (uint32_t k = 0; k < Kp; ++k) {
         const uint64_t p = periodic->cols[k].size();
@@ -721,7 +720,8 @@ int StarkProver::composition_air(const AirDescHost& air, const std::vector<fe>& 
         pcols[k] = AirPeriodicCol{(uint32_t)lp, 0u, S};
         S += p;
     }
-    if (air_program_first_bad_op(air.ops, R, C_, air.consts.size() + rap.size(), T, Kp) < air.ops.size()) { sp_set_error("composition_air: malformed constraint program"); return SP_E_INVALID_ARG; }
+    out.S = S;
+    if (air_program_first_bad_op(air.ops, R, C_, air.consts.size() + n_rap, T, Kp) < air.ops.size()) { sp_set_error("composition_air: malformed constraint program"); return SP_E_INVALID_ARG; }
     SP_TRY(air_assign_slots(air.ops, dops, "composition_air: more than 64 values alive at once in the constraint program"));
     prog.n_ops = (uint32_t)dops.size();
     // --- transition exemptions (traits.rs:49-79, evaluator.rs:299-323): distinct non-zero counts; with
@@ -732,7 +732,7 @@ int StarkProver::composition_air(const AirDescHost& air, const std::vector<fe>& 
     uint32_t max_ex = 0;
     for (size_t q = 0; q < uniq.size(); ++q) { prog.ex_count[q] = uniq[q]; max_ex = std::max(max_ex, uniq[q]); }
     if (max_ex >= n_) { sp_set_error("composition_air: exemptions exceed the trace length"); return SP_E_INVALID_ARG; }
-    uint64_t deg_bound = 0;   // of H for a constraint-satisfying trace
+    out.max_ex = max_ex;
     for (uint32_t k = 0; k < T; ++k) {
         const uint32_t e = air.exemptions[k], d = air.degrees[k];
         if (d < 1 || d > f + 1) { sp_set_error("composition_air: transition degree above the composition degree bound"); return SP_E_INVALID_ARG; }
@@ -740,10 +740,33 @@ int StarkProver::composition_air(const AirDescHost& air, const std::vector<fe>& 
             size_t idx = air.num_transition_exemptions == 1 ? 0 : (size_t)(std::find(uniq.begin(), uniq.end(), e) - uniq.begin());
             prog.ex_kind[k] = 1 + (uint32_t)idx;
         }
+        prog.ex_rows[k] = prog.ex_kind[k] ? prog.ex_count[prog.ex_kind[k] - 1] : 0;   // rows the composition really exempts for this constraint (what the trace check must mirror)
+    }
+    return SP_OK;
+}
+
+int StarkProver::composition_air(const AirDescHost& air, const std::vector<fe>& rap, const std::vector<fe>& b_alpha, const std::vector<fe>& b_beta,
+                                 const std::vector<fe>& t_alpha, const std::vector<fe>& t_beta, uint8_t root_out[32], const AirPeriodicHost* periodic) {
+    if (stage_ != 3 && !(stage_ == 2 && Ca_ == 0)) { sp_set_error("composition: trace segments not committed"); return SP_E_STATE; }
+    const uint32_t T = (uint32_t)air.degrees.size(), B = (uint32_t)air.boundary.size();
+    if (t_alpha.size() != T || t_beta.size() != T || b_alpha.size() != B || b_beta.size() != B) {
+        sp_set_error("composition_air: descriptor out of range or inconsistent with the committed trace");
+        return SP_E_INVALID_ARG;
+    }
+    SP_HIP_CHECK(hipSetDevice(c_->device));
+    AirProgramHost ph;
+    SP_TRY(build_air_program(air, rap.size(), periodic, ph));
+    const uint32_t b = 1u << logb_, f = air.degree_bound_factor;
+    AirProgram& prog = ph.prog;
+    const std::vector<AirOpDev>& dops = ph.dops;
+    const std::vector<AirPeriodicCol>& pcols = ph.pcols;
+    const uint32_t Kp = (uint32_t)pcols.size(), max_ex = ph.max_ex;
+    const uint64_t S = ph.S;
+    uint64_t deg_bound = 0;   // of H for a constraint-satisfying trace
+    for (uint32_t k = 0; k < T; ++k) {
         // deg C_k <= d (n - 1); times x^(n (f - d + 1)); times the exemption product; over x^n - 1
-        const uint32_t ex_used = prog.ex_kind[k] ? prog.ex_count[prog.ex_kind[k] - 1] : 0;
-        prog.ex_rows[k] = ex_used;   // rows the composition really exempts for this constraint (what the trace check must mirror)
-        deg_bound = std::max<uint64_t>(deg_bound, (uint64_t)d * (n_ - 1) + n_ * (f - d + 1) + ex_used - n_ + 1);
+        const uint32_t d = air.degrees[k];
+        deg_bound = std::max<uint64_t>(deg_bound, (uint64_t)d * (n_ - 1) + n_ * (f - d + 1) + prog.ex_rows[k] - n_ + 1);
     }
     deg_bound = std::max<uint64_t>(deg_bound, (n_ - 1) + n_ * (f - 1));   // boundary terms
     const bool allow_sub = deg_bound <= 2 * n_;                            // deg H < 2n: 2n evaluations fix it
@@ -854,6 +877,79 @@ int StarkProver::composition_air(const AirDescHost& air, const std::vector<fe>& 
     }
     offsets_ = air.offsets;
     return composition_core(nullptr, points, reinterpret_cast<const AirProgram*>(dev_at(o_prog)), &tabs, od_.ex_roots.p, allow_sub, root_out);
+}
+
+// validate_trace (reference debug.rs:13-104) for a program AIR, on the device: the program and the descriptor's boundary constraints
+// (in the descriptor's order - the report names them by index) go up in one block, the report comes back in one.
+int StarkProver::check_trace_air(const AirDescHost& air, const std::vector<fe>& rap, const AirPeriodicHost* periodic, std::vector<AirViolationHost>& out) {
+    out.clear();
+    if (stage_ != 3 && !(stage_ == 2 && Ca_ == 0)) { sp_set_error("check_trace_air: trace segments not committed"); return SP_E_STATE; }
+    if (world_ > 1) { sp_set_error("check_trace_air: a report from a sharded context is not supported"); return SP_E_UNSUPPORTED; }
+    SP_HIP_CHECK(hipSetDevice(c_->device));
+    AirProgramHost ph;
+    SP_TRY(build_air_program(air, rap.size(), periodic, ph));
+    const uint32_t T = (uint32_t)air.degrees.size(), B = (uint32_t)air.boundary.size(), Kp = (uint32_t)ph.pcols.size();
+    for (const BoundaryConstraint& bc : air.boundary)
+        if (bc.col >= C_ || bc.step >= n_) { sp_set_error("composition_air: boundary constraint outside the trace"); return SP_E_INVALID_ARG; }
+    size_t at = 0;
+    auto place = [&at](size_t bytes) { const size_t o = at; at = (at + bytes + 255) & ~size_t(255); return o; };
+    const size_t o_prog = place(sizeof(AirProgram)), o_ops = place(sizeof(AirOpDev) * ph.dops.size()),
+                 o_consts = place(sizeof(fe) * (air.consts.size() + rap.size())), o_bval = place(sizeof(fe) * B),
+                 o_bstep = place(sizeof(uint64_t) * B), o_bcol = place(sizeof(uint32_t) * B),
+                 o_pcols = place(sizeof(AirPeriodicCol) * Kp), o_pvals = place(sizeof(fe) * ph.S);
+    SP_TRY(grow(od_.air_buf, at));
+    std::vector<uint8_t>& up = h_air_up_;
+    up.assign(at, 0);
+    auto dev_at = [&](size_t off) { return od_.air_buf.p + off; };
+    ph.prog.ops = reinterpret_cast<const AirOpDev*>(dev_at(o_ops));
+    ph.prog.consts = reinterpret_cast<const fe*>(dev_at(o_consts));
+    std::memcpy(up.data() + o_prog, &ph.prog, sizeof(AirProgram));
+    if (!ph.dops.empty()) std::memcpy(up.data() + o_ops, ph.dops.data(), sizeof(AirOpDev) * ph.dops.size());
+    fe* hconst = reinterpret_cast<fe*>(up.data() + o_consts);
+    for (size_t i = 0; i < air.consts.size(); ++i) hconst[i] = air.consts[i];
+    for (size_t i = 0; i < rap.size(); ++i) hconst[air.consts.size() + i] = rap[i];
+    fe* hbval = reinterpret_cast<fe*>(up.data() + o_bval);
+    uint64_t* hbstep = reinterpret_cast<uint64_t*>(up.data() + o_bstep);
+    uint32_t* hbcol = reinterpret_cast<uint32_t*>(up.data() + o_bcol);
+    for (uint32_t j = 0; j < B; ++j) { hbval[j] = air.boundary[j].value; hbstep[j] = air.boundary[j].step; hbcol[j] = air.boundary[j].col; }
+    if (Kp) std::memcpy(up.data() + o_pcols, ph.pcols.data(), sizeof(AirPeriodicCol) * Kp);
+    for (uint32_t k = 0; k < Kp; ++k) std::memcpy(up.data() + o_pvals + sizeof(fe) * ph.pcols[k].off, periodic->cols[k].data(), sizeof(fe) * periodic->cols[k].size());
+    SP_HIP_CHECK(hipMemcpyAsync(od_.air_buf.p, up.data(), at, hipMemcpyHostToDevice, c_->stream));
+    AirCompTables tabs;
+    std::memset(&tabs, 0, sizeof(tabs));
+    tabs.T = T; tabs.B = B;
+    tabs.bvalue = reinterpret_cast<const fe*>(dev_at(o_bval));
+    tabs.bstep = reinterpret_cast<const uint64_t*>(dev_at(o_bstep));
+    tabs.bcol = reinterpret_cast<const uint32_t*>(dev_at(o_bcol));
+    if (Kp) {
+        tabs.pcols = reinterpret_cast<const AirPeriodicCol*>(dev_at(o_pcols));
+        tabs.pvals = reinterpret_cast<const fe*>(dev_at(o_pvals));
+    }
+    // the report block, in 8-byte words: value [4 T] | bcell [4 B] | count [T] | first [T] | last [T] | bbad [B / 2]
+    const uint64_t w_value = 0, w_bcell = w_value + 4ull * T, w_count = w_bcell + 4ull * B, w_first = w_count + T, w_last = w_first + T,
+                   w_bbad = w_last + T, words = w_bbad + (B + 1) / 2;
+    SP_TRY(grow(od_.air_report, words));
+    uint64_t* rp = od_.air_report.p;
+    SP_HIP_CHECK(hipMemsetAsync(rp, 0, words * sizeof(uint64_t), c_->stream));
+    SP_HIP_CHECK(hipMemsetAsync(rp + w_first, 0xFF, (size_t)T * sizeof(uint64_t), c_->stream));
+    AirReport rep;
+    rep.value = reinterpret_cast<fe*>(rp + w_value);
+    rep.bcell = reinterpret_cast<fe*>(rp + w_bcell);
+    rep.count = reinterpret_cast<unsigned long long*>(rp + w_count);
+    rep.first = reinterpret_cast<unsigned long long*>(rp + w_first);
+    rep.last = reinterpret_cast<unsigned long long*>(rp + w_last);
+    rep.bbad = reinterpret_cast<uint32_t*>(rp + w_bbad);
+    SP_TRY(air_trace_report(c_->stream, d_trace_, n_, tabs, reinterpret_cast<const AirProgram*>(dev_at(o_prog)), rep));
+    h_report_.resize(words * sizeof(uint64_t));
+    SP_TRY(readback(h_report_.data(), rp, h_report_.size()));   // (waits for the stream: the upload above is done with h_air_up_)
+    const uint64_t* h = reinterpret_cast<const uint64_t*>(h_report_.data());
+    auto fe_at = [&](uint64_t word) { fe x; std::memcpy(&x, h + word, sizeof(fe)); return x; };
+    for (uint32_t k = 0; k < T; ++k)
+        if (h[w_count + k]) out.push_back(AirViolationHost{0u, k, h[w_count + k], h[w_first + k], h[w_last + k], fe_at(w_value + 4ull * k)});
+    const uint32_t* bbad = reinterpret_cast<const uint32_t*>(h + w_bbad);
+    for (uint32_t j = 0; j < B; ++j)
+        if (bbad[j]) out.push_back(AirViolationHost{1u, j, 1, air.boundary[j].step, air.boundary[j].step, fe_at(w_bcell + 4ull * j)});
+    return SP_OK;
 }
 
 // Shared second half of round 2.  Cairo (prog_dev == nullptr): K (per-coset coefficients, zerofier, boundary data) is complete and

@@ -37,6 +37,10 @@ struct Openings {
     std::vector<digest32> fri_paths, fri_paths_sym;              // [q][sum_k (depth0-k)]
 };
 
+// One violated constraint of a program AIR (sp_air_violation): kind 0 a transition constraint (index = OUT's a), 1 a boundary
+// constraint (index into the descriptor's list; rows = 1, first_row = last_row = its step, value = the cell found).
+struct AirViolationHost { uint32_t kind, index; uint64_t rows, first_row, last_row; fe value; };
+
 class HostPool;   // prover.cpp: parked host threads for the upload pipeline
 
 // Device memory that setup() does not carve: allocated on first use or grown on demand by StarkProver::grow, `cap` elements of T.
@@ -104,6 +108,10 @@ class StarkProver : public sp_deletable {
     // periodic (nullable): the periodic columns the program reads with op 6; their tables are built here (od_.periodic)
     int composition_air(const AirDescHost& air, const std::vector<fe>& rap, const std::vector<fe>& b_alpha, const std::vector<fe>& b_beta,
                         const std::vector<fe>& t_alpha, const std::vector<fe>& t_beta, uint8_t root_out[32], const AirPeriodicHost* periodic = nullptr);
+    // Instead of round 2, for an AIR given as a constraint program: which constraints the trace held since round 1 (d_trace_,
+    // main || aux) breaks, and where - the transition constraints by index, then the boundary constraints by index (sp_air_check_trace).
+    // Leaves the stage where it was: composition_air may follow.
+    int check_trace_air(const AirDescHost& air, const std::vector<fe>& rap, const AirPeriodicHost* periodic, std::vector<AirViolationHost>& out);
     // round 3: H1(z^2), H2(z^2), t_j(z g^ofs_k) for every frame row k (row-major [k][j])
     int ood(const fe& z, fe* h1_z2, fe* h2_z2, std::vector<fe>& trace_ood);
     // round 4
@@ -226,6 +234,8 @@ class StarkProver : public sp_deletable {
         const uint64_t ood = C_ <= 64 ? 0 : 2ull * C_ * AIR_MAX_OFFSETS * std::max<uint64_t>(1, n_ >> 8) + 8ull * AIR_MAX_OFFSETS * 256;
         return std::max<uint64_t>(std::max<uint64_t>(std::max<uint64_t>(Nl_ * 7, 4 * n_), 8192), ood);
     }
+    struct AirProgramHost { AirProgram prog; std::vector<AirOpDev> dops; std::vector<AirPeriodicCol> pcols; uint64_t S = 0; uint32_t max_ex = 0; };   // S: the periods, summed
+    int build_air_program(const AirDescHost& air, size_t n_rap, const AirPeriodicHost* periodic, AirProgramHost& out);
     int composition_core(const CompositionConsts* K, const std::vector<fe>& points, const AirProgram* prog_dev, const AirCompTables* air_tabs,
                          const fe* ex_roots_dev, bool allow_sub_coset, uint8_t root_out[32]);
 
@@ -256,6 +266,7 @@ class StarkProver : public sp_deletable {
         // auxiliary programs (commit_aux_program): ops, constants and column tables of every chunk in one buffer, and the N / D
         // workspace (denominators, batch-inversion scratch, scan block totals); kept across proofs of a shape
         DevBuf<uint8_t> auxp_buf; DevBuf<fe> auxp_ws;
+        DevBuf<uint64_t> air_report;             // check_trace_air: per-constraint counters, values and boundary results, one block (AirReport)
         DevBuf<fe> periodic;                     // periodic columns of a program AIR: [b S] tables, [S] values being transformed, [S] scratch (S = sum of the periods)
         DevBuf<uint8_t> fri_chain;               // [state 32 B][L x constants][L x zeta constants][L x roots]
         DevBuf<int> side_flags;                  // [SIDE_FLAGS]
@@ -318,11 +329,12 @@ class StarkProver : public sp_deletable {
     std::unique_ptr<CompositionConsts> h_comp_chk_;    // host copy of od_.comp_consts_chk (stays put until the upload has happened)
     bool check_pending_ = false;
     std::vector<uint8_t> h_air_up_, h_auxp_up_;        // host sides of the uploads into od_.air_buf and od_.auxp_buf
+    std::vector<uint8_t> h_report_;                    // host copy of od_.air_report
     DeepConsts* d_deep_consts_ = nullptr;
     fe* d_deep_gammas_ = nullptr;                      // [AIR_MAX_OFFSETS][C], behind the DeepConsts in the same allocation
     static size_t deep_gammas_at() { return (sizeof(DeepConsts) + 255) & ~size_t(255); }
     unsigned long long* d_nonce_ = nullptr;
-    PinnedBuf h_pin_;         // 4 KB for readback()
+    PinnedBuf h_pin_;         // for readback(): 4 KB, more when a report asks for it
     PinnedBuf h_open_pin_;    // landing zone of the openings' download (kept across proofs)
     PinnedBuf h_flags_;       // HostFlags
     int ensure_pin() { return h_pin_.ensure(4096, "pinned read-back slot"); }
@@ -392,5 +404,11 @@ int cairo_prove(sp_ctx* ctx, const uint8_t* main_trace, uint64_t n, uint32_t col
 // periodic (nullable): the periodic columns its constraint program reads (sp_air_prove_periodic); without them op 6 is malformed.
 int air_prove(sp_ctx* ctx, const AirDescHost& air, const uint8_t* main_trace, uint64_t n, const ProofOptionsHost& opt,
               std::vector<uint8_t>& proof_out, float round_ms[5], const AirAuxHost* aux = nullptr, const AirPeriodicHost* periodic = nullptr);
+// Which constraints of a program AIR a trace breaks, and where (sp_air_check_trace): round 1 as air_prove runs it - the same ingest and
+// auxiliary builders -, then StarkProver::check_trace_air; no proof.  rap_given (nullable): the RAP challenges, instead of the ones a
+// proof under *opt would sample; opt may be null only with them.  One GPU (SP_E_UNSUPPORTED on a context with world > 1).
+int air_check_trace(sp_ctx* ctx, const AirDescHost& air, const uint8_t* main_trace, uint64_t n, const ProofOptionsHost* opt,
+                    const std::vector<fe>* rap_given, std::vector<AirViolationHost>& out, const AirAuxHost* aux = nullptr,
+                    const AirPeriodicHost* periodic = nullptr);
 
 }  // namespace sp

@@ -253,79 +253,120 @@ int cairo_prove(sp_ctx* ctx, const uint8_t* main_trace, uint64_t n, uint32_t col
     }
 }
 
+// The argument checks of air_prove and air_check_trace.
+static int air_check_args(const AirDescHost& air, uint64_t n, const AirAuxHost* aux, const AirPeriodicHost* periodic) {
+    if (air.main_cols == 0 || (uint64_t)air.main_cols + air.aux_cols > (uint64_t)AIR_MAX_COLS) {
+        sp_set_error("air_prove: column count out of range (1 .. 1024 columns, main + aux)");
+        return SP_E_INVALID_ARG;
+    }
+    if (air.boundary.size() > (size_t)AIR_MAX_BOUNDARY) { sp_set_error("air_prove: more than 4096 boundary constraints"); return SP_E_INVALID_ARG; }
+    if (air.consts.size() > (size_t)AIR_MAX_CONSTS) { sp_set_error("air_prove: more than 4096 constants"); return SP_E_INVALID_ARG; }
+    if (air.consts.size() + air.n_rap > 65535) { sp_set_error("air_prove: constants and RAP challenges exceed the 16-bit operand range"); return SP_E_INVALID_ARG; }
+    if (air.ops.size() > (size_t)AIR_MAX_OPS) { sp_set_error("air_prove: more than 65535 ops"); return SP_E_INVALID_ARG; }
+    if (periodic) {
+        if (periodic->cols.size() > (size_t)AIR_MAX_PERIODIC) { sp_set_error("air_prove: more than 64 periodic columns"); return SP_E_INVALID_ARG; }
+        if (!air_periodic_fits(*periodic, n)) { sp_set_error("air_prove: a periodic column's period exceeds the trace length"); return SP_E_INVALID_ARG; }
+    }
+    if (aux) {
+        if (air.aux_kind != SP_AIR_AUX_PROGRAM || air.aux_cols == 0 || aux->cols.size() != air.aux_cols) {
+            sp_set_error("air_prove: an auxiliary program needs aux_kind SP_AIR_AUX_PROGRAM and one column per auxiliary column");
+            return SP_E_INVALID_ARG;
+        }
+        SP_TRY(validate_aux_program(*aux, air.main_cols, air.n_rap));
+    }
+    return SP_OK;
+}
+
+// Round 1 of a program AIR (reference prover.rs:187-224) on a prover that begin_proof has set up: the main segment, the RAP
+// challenges - sampled from the transcript, or rap_given (air_check_trace with the caller's challenges) -, the auxiliary segment by
+// its kind.  Leaves main || aux on the device as round 2 reads it.
+static int air_round1(sp_ctx* ctx, ProofRun& run, const AirDescHost& air, const uint8_t* main_trace, uint64_t n, const AirAuxHost* aux,
+                      std::vector<fe>& rap, const std::vector<fe>* rap_given = nullptr) {
+    StarkProver* P = &run.H->prover;
+    Transcript& tr = run.tr;
+    uint8_t root[32];
+    SP_TRY(P->commit_trace(0, main_trace, air.main_cols, root));
+    run.trace_committed(root);
+    rap.assign(air.n_rap, fe_zero());
+    for (auto& x : rap) x = tr.to_field();
+    if (rap_given) rap = *rap_given;
+    if (air.aux_cols && air.aux_kind == 2) {
+        // build_auxiliary_trace of the caller's AIR (traits.rs:25-29): row-major n x aux_cols from the RAP challenges
+        if (!air.aux_fn) { sp_set_error("air_prove: aux_kind 2 needs aux_fn"); return SP_E_INVALID_ARG; }
+        std::vector<uint8_t> rap_bytes(std::max<size_t>(1, rap.size()) * 32), aux_rows((size_t)n * air.aux_cols * 32);
+        if (!rap.empty()) SP_TRY(sp_fe_from_device(ctx->enc, reinterpret_cast<const uint8_t*>(rap.data()), rap.size(), rap_bytes.data()));
+        if (air.aux_fn(air.aux_user, rap_bytes.data(), (uint32_t)rap.size(), aux_rows.data()) != 0) { sp_set_error("air_prove: the auxiliary-trace callback failed"); return SP_E_INVALID_ARG; }
+        SP_TRY(P->commit_trace(1, aux_rows.data(), air.aux_cols, root));
+        run.trace_committed(root);
+    } else if (air.aux_cols && air.aux_kind == SP_AIR_AUX_PROGRAM && aux) {
+        // the auxiliary program on the device, from the resident main trace (every rank holds all of it: no exchange)
+        SP_TRY(P->commit_aux_program(*aux, rap, root));
+        run.trace_committed(root);
+    } else if (air.aux_cols) {
+        if (air.aux_kind != 1 || air.aux_cols != 1 || air.main_cols < 2 || air.n_rap < 1) {
+            sp_set_error("air_prove: unknown auxiliary-trace kind (1 = fibonacci_rap permutation column, 2 = caller-supplied)");
+            return SP_E_UNSUPPORTED;
+        }
+        // fibonacci_rap.rs:69-93: z_0 = 1, z_i = z_(i-1) (a_(i-1) + gamma) / (b_(i-1) + gamma)
+        std::vector<fe> den(n), num(n);
+        for (uint64_t i = 0; i < n; ++i) {
+            fe a, b;
+            const uint8_t* row = main_trace + (size_t)i * air.main_cols * 32;
+            if (ctx->enc == SP_FE_CANON_BE) { a = fe_from_bytes_be(row); b = fe_from_bytes_be(row + 32); }
+            else { uint64_t l[4]; std::memcpy(l, row, 32); a = fe_from_lw_limbs(l); std::memcpy(l, row + 32, 32); b = fe_from_lw_limbs(l); }
+            num[i] = fe_add(a, rap[0]); den[i] = fe_add(b, rap[0]);
+        }
+        for (auto& d : den) if (fe_is_zero(d)) { sp_set_error("air_prove: zero denominator in the permutation column"); return SP_E_ZERO_INVERSE; }
+        host_batch_inverse(den);
+        std::vector<uint8_t> aux_rows((size_t)n * 32);
+        fe zacc = fe_one();
+        for (uint64_t i = 0; i < n; ++i) {
+            if (i > 0) zacc = fe_mul(zacc, fe_mul(num[i - 1], den[i - 1]));
+            if (ctx->enc == SP_FE_CANON_BE) fe_to_bytes_be(zacc, &aux_rows[(size_t)i * 32]);
+            else { uint64_t l[4]; fe_to_lw_limbs(zacc, l); std::memcpy(&aux_rows[(size_t)i * 32], l, 32); }
+        }
+        SP_TRY(P->commit_trace(1, aux_rows.data(), 1, root));
+        run.trace_committed(root);
+    }
+    return SP_OK;
+}
+
+// Which constraints of a program AIR the trace breaks (sp_air_check_trace; reference validate_trace, debug.rs:13-104): round 1 as
+// air_prove runs it, then the report instead of rounds 2 - 4.  opt (nullable when rap is given): the options of the proof whose
+// challenges are wanted; with the caller's challenges the commitments still run (under the smallest options when none are given),
+// since they are how the prover takes a trace in.
+int air_check_trace(sp_ctx* ctx, const AirDescHost& air, const uint8_t* main_trace, uint64_t n, const ProofOptionsHost* opt,
+                    const std::vector<fe>* rap_given, std::vector<AirViolationHost>& out, const AirAuxHost* aux, const AirPeriodicHost* periodic) {
+    try {
+        if (!opt && !rap_given) { sp_set_error("air_check_trace: proof options are needed to sample the RAP challenges"); return SP_E_INVALID_ARG; }
+        if (rap_given && rap_given->size() != air.n_rap) { sp_set_error("air_check_trace: one RAP challenge per n_rap"); return SP_E_INVALID_ARG; }
+        SP_TRY(air_check_args(air, n, aux, periodic));
+        if (ctx->world > 1) { sp_set_error("air_check_trace: a report from a sharded context (world > 1) is not supported"); return SP_E_UNSUPPORTED; }
+        const ProofOptionsHost smallest{2, 1, 3, 0};
+        ProofRun run;
+        SP_TRY(begin_proof(ctx, n, air.main_cols, air.aux_cols, false, opt ? *opt : smallest, run));
+        std::vector<fe> rap;
+        SP_TRY(air_round1(ctx, run, air, main_trace, n, aux, rap, rap_given));
+        return run.H->prover.check_trace_air(air, rap, periodic, out);
+    } catch (const std::exception& e) {
+        sp_set_error(std::string("air_check_trace: ") + e.what());
+        return SP_E_INVALID_ARG;
+    }
+}
+
 // prove::<F, A> for a program AIR (reference src/starks/prover.rs:532-766): same rounds, the AIR-specific parts come from
 // the descriptor - RAP challenges (n_rap field samples), auxiliary trace (by kind: the fibonacci_rap column and the caller's
 // callback on the host - the example AIRs are tiny -, an auxiliary program on the device), boundary constraints, transition program.
 int air_prove(sp_ctx* ctx, const AirDescHost& air, const uint8_t* main_trace, uint64_t n, const ProofOptionsHost& opt,
               std::vector<uint8_t>& proof_out, float round_ms[5], const AirAuxHost* aux, const AirPeriodicHost* periodic) {
     try {
-        if (air.main_cols == 0 || (uint64_t)air.main_cols + air.aux_cols > (uint64_t)AIR_MAX_COLS) {
-            sp_set_error("air_prove: column count out of range (1 .. 1024 columns, main + aux)");
-            return SP_E_INVALID_ARG;
-        }
-        if (air.boundary.size() > (size_t)AIR_MAX_BOUNDARY) { sp_set_error("air_prove: more than 4096 boundary constraints"); return SP_E_INVALID_ARG; }
-        if (air.consts.size() > (size_t)AIR_MAX_CONSTS) { sp_set_error("air_prove: more than 4096 constants"); return SP_E_INVALID_ARG; }
-        if (air.consts.size() + air.n_rap > 65535) { sp_set_error("air_prove: constants and RAP challenges exceed the 16-bit operand range"); return SP_E_INVALID_ARG; }
-        if (air.ops.size() > (size_t)AIR_MAX_OPS) { sp_set_error("air_prove: more than 65535 ops"); return SP_E_INVALID_ARG; }
-        if (periodic) {
-            if (periodic->cols.size() > (size_t)AIR_MAX_PERIODIC) { sp_set_error("air_prove: more than 64 periodic columns"); return SP_E_INVALID_ARG; }
-            if (!air_periodic_fits(*periodic, n)) { sp_set_error("air_prove: a periodic column's period exceeds the trace length"); return SP_E_INVALID_ARG; }
-        }
-        if (aux) {
-            if (air.aux_kind != SP_AIR_AUX_PROGRAM || air.aux_cols == 0 || aux->cols.size() != air.aux_cols) {
-                sp_set_error("air_prove: an auxiliary program needs aux_kind SP_AIR_AUX_PROGRAM and one column per auxiliary column");
-                return SP_E_INVALID_ARG;
-            }
-            SP_TRY(validate_aux_program(*aux, air.main_cols, air.n_rap));
-        }
+        SP_TRY(air_check_args(air, n, aux, periodic));
         ProofRun run;
         SP_TRY(begin_proof(ctx, n, air.main_cols, air.aux_cols, false, opt, run));
         StarkProver* P = &run.H->prover;
-        Transcript& tr = run.tr;
-        uint8_t root[32];
+        std::vector<fe> rap;
         // ---- round 1 (reference prover.rs:187-224)
-        SP_TRY(P->commit_trace(0, main_trace, air.main_cols, root));
-        run.trace_committed(root);
-        std::vector<fe> rap(air.n_rap);
-        for (auto& x : rap) x = tr.to_field();
-        if (air.aux_cols && air.aux_kind == 2) {
-            // build_auxiliary_trace of the caller's AIR (traits.rs:25-29): row-major n x aux_cols from the RAP challenges
-            if (!air.aux_fn) { sp_set_error("air_prove: aux_kind 2 needs aux_fn"); return SP_E_INVALID_ARG; }
-            std::vector<uint8_t> rap_bytes(std::max<size_t>(1, rap.size()) * 32), aux_rows((size_t)n * air.aux_cols * 32);
-            if (!rap.empty()) SP_TRY(sp_fe_from_device(ctx->enc, reinterpret_cast<const uint8_t*>(rap.data()), rap.size(), rap_bytes.data()));
-            if (air.aux_fn(air.aux_user, rap_bytes.data(), (uint32_t)rap.size(), aux_rows.data()) != 0) { sp_set_error("air_prove: the auxiliary-trace callback failed"); return SP_E_INVALID_ARG; }
-            SP_TRY(P->commit_trace(1, aux_rows.data(), air.aux_cols, root));
-            run.trace_committed(root);
-        } else if (air.aux_cols && air.aux_kind == SP_AIR_AUX_PROGRAM && aux) {
-            // the auxiliary program on the device, from the resident main trace (every rank holds all of it: no exchange)
-            SP_TRY(P->commit_aux_program(*aux, rap, root));
-            run.trace_committed(root);
-        } else if (air.aux_cols) {
-            if (air.aux_kind != 1 || air.aux_cols != 1 || air.main_cols < 2 || air.n_rap < 1) {
-                sp_set_error("air_prove: unknown auxiliary-trace kind (1 = fibonacci_rap permutation column, 2 = caller-supplied)");
-                return SP_E_UNSUPPORTED;
-            }
-            // fibonacci_rap.rs:69-93: z_0 = 1, z_i = z_(i-1) (a_(i-1) + gamma) / (b_(i-1) + gamma)
-            std::vector<fe> den(n), num(n);
-            for (uint64_t i = 0; i < n; ++i) {
-                fe a, b;
-                const uint8_t* row = main_trace + (size_t)i * air.main_cols * 32;
-                if (ctx->enc == SP_FE_CANON_BE) { a = fe_from_bytes_be(row); b = fe_from_bytes_be(row + 32); }
-                else { uint64_t l[4]; std::memcpy(l, row, 32); a = fe_from_lw_limbs(l); std::memcpy(l, row + 32, 32); b = fe_from_lw_limbs(l); }
-                num[i] = fe_add(a, rap[0]); den[i] = fe_add(b, rap[0]);
-            }
-            for (auto& d : den) if (fe_is_zero(d)) { sp_set_error("air_prove: zero denominator in the permutation column"); return SP_E_ZERO_INVERSE; }
-            host_batch_inverse(den);
-            std::vector<uint8_t> aux_rows((size_t)n * 32);
-            fe zacc = fe_one();
-            for (uint64_t i = 0; i < n; ++i) {
-                if (i > 0) zacc = fe_mul(zacc, fe_mul(num[i - 1], den[i - 1]));
-                if (ctx->enc == SP_FE_CANON_BE) fe_to_bytes_be(zacc, &aux_rows[(size_t)i * 32]);
-                else { uint64_t l[4]; fe_to_lw_limbs(zacc, l); std::memcpy(&aux_rows[(size_t)i * 32], l, 32); }
-            }
-            SP_TRY(P->commit_trace(1, aux_rows.data(), 1, root));
-            run.trace_committed(root);
-        }
+        SP_TRY(air_round1(ctx, run, air, main_trace, n, aux, rap));
         SP_HIP_CHECK(hipEventRecord(run.H->round_ev[1], ctx->stream));
         auto composition = [&](const std::vector<fe>& b_alpha, const std::vector<fe>& b_beta, const std::vector<fe>& t_alpha, const std::vector<fe>& t_beta, uint8_t* root_out) {
             return P->composition_air(air, rap, b_alpha, b_beta, t_alpha, t_beta, root_out, periodic);

@@ -121,6 +121,21 @@ int air_composition(hipStream_t st, const fe* lde, uint64_t count, uint64_t col_
 // validate_trace (debug.rs:13-104): the transition constraints on every row (one thread per row), then the boundary
 // values (one thread per constraint); *flag_dev |= 1 on any violation.  Op 6 reads the periodic VALUES, not the table.
 int air_trace_check(hipStream_t st, const fe* trace, uint64_t n, AirCompTables tabs, const AirProgram* prog_dev, int* flag_dev);
+// The same check with a report instead of a flag (sp_air_check_trace; validate_trace prints what it finds, debug.rs:52-104).
+// Per transition constraint k: count[k] = enforced rows on which it is non-zero, first[k] / last[k] = the lowest / highest of them,
+// value[k] = its evaluation on first[k] (Montgomery form; untouched when count[k] is 0).  Per boundary constraint j, in the order of
+// tabs.bcol / bstep / bvalue: bcell[j] = the cell found, bbad[j] = 1 when it differs from the value.
+// The caller zeroes the block and sets first[] to all ones before the launch.  tabs: T, B, bvalue, bcol, bstep, pcols, pvals are read.
+struct AirReport {
+    unsigned long long *count, *first, *last;   // [T] each
+    fe* value;                                   // [T]
+    fe* bcell;                                   // [B]
+    uint32_t* bbad;                              // [B]
+};
+// Three launches: one lane per row (a wave votes per constraint and one of its lanes adds the vote's population count and offers the
+// rows of its lowest and highest set lane: at most three atomics per wave and constraint, none for a wave without a violation), one
+// lane per transition constraint for the values, one lane per boundary constraint.
+int air_trace_report(hipStream_t st, const fe* trace, uint64_t n, AirCompTables tabs, const AirProgram* prog_dev, AirReport report);
 
 // Table of `cnt` periodic columns of period p = 2^logp <= AIR_PERIODIC_DIRECT_MAX without the transform plans: coef[v][m] = q_v's
 // coefficients from vals[v][.] (one thread per coefficient, p terms each), then tab[v][c][j] = q_v(hq w_(p b)^(j b + c)) by Horner (one

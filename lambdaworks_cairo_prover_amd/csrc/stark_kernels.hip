@@ -741,6 +741,102 @@ int air_trace_check(hipStream_t st, const fe* trace, uint64_t n, AirCompTables t
     return SP_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- program AIRs: the report
+// The constraint program on trace row i, as air_composition_kernel<true, PER> runs it: natural-order columns of n rows, frame rows wrap
+// modulo n, op 6 reads the periodic VALUES.  cons[k], k < K.T, receives the evaluations.
+template <bool PER>
+__device__ __forceinline__ void air_eval_row(const fe* __restrict__ cols, uint64_t n, uint64_t i, const AirCompTables& K,
+                                             const AirProgram* __restrict__ Pg, fe* cons) {
+    const AirOpDev* __restrict__ ops = Pg->ops;
+    const fe* __restrict__ consts = Pg->consts;
+    fe v[AIR_MAX_LIVE];
+    for (uint32_t k = 0; k < K.T; ++k) cons[k] = fe_zero();
+    const uint32_t n_ops = Pg->n_ops;
+    for (uint32_t t = 0; t < n_ops; ++t) {
+        const AirOpDev o = ops[t];
+        fe r = fe_zero();
+        if constexpr (PER) {
+            if (o.op == 6) {
+                const AirPeriodicCol pc = K.pcols[o.b];
+                const uint32_t pm = (1u << pc.logp) - 1u;
+                v[o.dst] = sk_ld(K.pvals + pc.off + (((uint32_t)i + Pg->offsets[o.a]) & pm));
+                continue;
+            }
+        }
+        switch (o.op) {
+            case 0: r = sk_ld(cols + (uint64_t)o.b * n + ((i + Pg->offsets[o.a]) & (n - 1))); break;
+            case 1: r = sk_ld(consts + o.a); break;
+            case 2: r = v[o.a] + v[o.b]; break;
+            case 3: r = v[o.a] - v[o.b]; break;
+            case 4: r = v[o.a] * v[o.b]; break;
+            default: cons[o.a] = v[o.b]; continue;
+        }
+        v[o.dst] = r;
+    }
+}
+
+// One lane per trace row.  The lanes of the last block beyond row n - 1 run no program and never vote, but stay for the ballots.
+template <bool PER>
+__global__ void __launch_bounds__(256) air_report_kernel(const fe* __restrict__ cols, uint64_t n, const AirCompTables K,
+                                                         const AirProgram* __restrict__ Pg, const AirReport R) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    const bool live = i < n;
+    fe cons[AIR_MAX_TRANSITIONS];
+    if (live) air_eval_row<PER>(cols, n, i, K, Pg, cons);
+    const uint32_t lane = threadIdx.x & 63u;   // (blocks of 256 in one dimension: wave w holds threads 64 w .. 64 w + 63)
+    const uint64_t row0 = i - lane;
+    for (uint32_t k = 0; k < K.T; ++k) {
+        const bool bad = live && i + Pg->ex_rows[k] < n && !fe_is_zero(cons[k]);   // enforced on rows 0 .. n - 1 - exemptions
+        const unsigned long long m = __ballot(bad);
+        const uint32_t lo = m ? (uint32_t)__ffsll(m) - 1u : 64u;
+        if (lane == lo) {                      // the lowest voter speaks for the wave; no voter, no atomic
+            atomicAdd(R.count + k, (unsigned long long)__popcll(m));
+            atomicMin(R.first + k, (unsigned long long)(row0 + lo));
+            atomicMax(R.last + k, (unsigned long long)(row0 + 63u - (uint32_t)__clzll((long long)m)));
+        }
+    }
+}
+
+// One lane per transition constraint: the evaluation on the first row that breaks it.
+template <bool PER>
+__global__ void __launch_bounds__(64) air_report_value_kernel(const fe* __restrict__ cols, uint64_t n, const AirCompTables K,
+                                                              const AirProgram* __restrict__ Pg, const AirReport R) {
+    const uint32_t k = threadIdx.x;
+    if (k >= K.T || R.count[k] == 0) return;
+    const uint64_t row = R.first[k];
+    if (row >= n) return;
+    fe cons[AIR_MAX_TRANSITIONS];
+    air_eval_row<PER>(cols, n, row, K, Pg, cons);
+    sk_st(R.value + k, cons[k]);
+}
+
+// One lane per boundary constraint, as air_boundary_check_kernel: the cell, and whether it is the value.
+__global__ void __launch_bounds__(256) air_boundary_report_kernel(const fe* __restrict__ trace, uint64_t n, const AirCompTables K, const AirReport R) {
+    const uint32_t j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= K.B) return;
+    const fe cell = sk_ld(trace + (uint64_t)K.bcol[j] * n + K.bstep[j]);
+    sk_st(R.bcell + j, cell);
+    R.bbad[j] = fe_eq(cell, sk_ld(K.bvalue + j)) ? 0u : 1u;
+}
+
+int air_trace_report(hipStream_t st, const fe* trace, uint64_t n, AirCompTables tabs, const AirProgram* prog_dev, AirReport report) {
+    if (n == 0 || (n & (n - 1)) || tabs.T == 0 || tabs.T > (uint32_t)AIR_MAX_TRANSITIONS) return SP_E_INVALID_ARG;
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (tabs.pcols) {
+        hipLaunchKernelGGL((air_report_kernel<true>), grid, dim3(256), 0, st, trace, n, tabs, prog_dev, report);
+        hipLaunchKernelGGL((air_report_value_kernel<true>), dim3(1), dim3(64), 0, st, trace, n, tabs, prog_dev, report);
+    } else {
+        hipLaunchKernelGGL((air_report_kernel<false>), grid, dim3(256), 0, st, trace, n, tabs, prog_dev, report);
+        hipLaunchKernelGGL((air_report_value_kernel<false>), dim3(1), dim3(64), 0, st, trace, n, tabs, prog_dev, report);
+    }
+    SP_HIP_CHECK(hipGetLastError());
+    if (tabs.B) {
+        hipLaunchKernelGGL(air_boundary_report_kernel, dim3((tabs.B + 255) / 256), dim3(256), 0, st, trace, n, tabs, report);
+        SP_HIP_CHECK(hipGetLastError());
+    }
+    return SP_OK;
+}
+
 // ---------------------------------------------------------------------------------------------- periodic columns, small periods
 // q_m = p^-1 sum_j v_j w_p^(-j m): winv[e] = w_p^(-e), e < p <= AIR_PERIODIC_DIRECT_MAX, by value
 struct PeriodicDirectArgs { fe winv[AIR_PERIODIC_DIRECT_MAX]; fe pinv; };
