@@ -1,46 +1,24 @@
 // Auxiliary columns of a program AIR on gfx950 (see air_aux_kernels.h).
 #include "air_aux_kernels.h"
+#include "air_interp.h"
 
 namespace sp {
 
-__device__ __forceinline__ fe aa_ld(const fe* p) {
-    const uint4* q = reinterpret_cast<const uint4*>(p);
-    uint4 lo = q[0], hi = q[1];
-    fe r;
-    r.v[0] = lo.x; r.v[1] = lo.y; r.v[2] = lo.z; r.v[3] = lo.w;
-    r.v[4] = hi.x; r.v[5] = hi.y; r.v[6] = hi.z; r.v[7] = hi.w;
-    return r;
-}
-__device__ __forceinline__ void aa_st(fe* p, const fe& a) {
-    uint4* q = reinterpret_cast<uint4*>(p);
-    q[0] = make_uint4(a.v[0], a.v[1], a.v[2], a.v[3]);
-    q[1] = make_uint4(a.v[4], a.v[5], a.v[6], a.v[7]);
-}
-
 // ---- per-row terms ------------------------------------------------------------------------------------------
-// The value file is a per-thread array (scratch), as in air_composition_kernel; every lane reads the same op and constant.
+// The program runs in the shared interpreter (air_interp.h): LOAD takes the row shift itself, there are no periodic columns, and an
+// OUT stores into the num / den column it names.
 __global__ void __launch_bounds__(256) air_aux_terms_kernel(const fe* __restrict__ trace, uint64_t n, const AirOpDev* __restrict__ ops, uint32_t n_ops,
                                                             const fe* __restrict__ consts, fe* __restrict__ num, fe* __restrict__ den) {
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    fe v[AIR_MAX_LIVE];
-    for (uint32_t t = 0; t < n_ops; ++t) {
-        const AirOpDev o = ops[t];
-        fe r = fe_zero();
-        switch (o.op) {
-            case 0: r = aa_ld(trace + (uint64_t)o.b * n + ((i + o.a) & (n - 1))); break;   // n is a power of two
-            case 1: r = aa_ld(consts + o.a); break;
-            case 2: r = fe_add(v[o.a], v[o.b]); break;
-            case 3: r = fe_sub(v[o.a], v[o.b]); break;
-            case 4: r = fe_mul(v[o.a], v[o.b]); break;
-            default: {
-                fe* dst = o.a < AIR_AUX_DEN_TAG ? num + (uint64_t)o.a * n : den + (uint64_t)(o.a - AIR_AUX_DEN_TAG) * n;
-                aa_st(dst + i, v[o.b]);
-                continue;
-            }
-        }
-        v[o.dst] = r;
-    }
+    air_run_program<false>(
+        ops, n_ops, consts,
+        [&](uint32_t shift, uint32_t col) { return fe_ld(trace + (uint64_t)col * n + ((i + shift) & (n - 1))); },   // n is a power of two
+        AirNoPeriodic{},
+        [&](uint32_t a, const fe& val) {
+            fe* dst = a < AIR_AUX_DEN_TAG ? num + (uint64_t)a * n : den + (uint64_t)(a - AIR_AUX_DEN_TAG) * n;
+            fe_st(dst + i, val);
+        });
 }
 
 int air_aux_terms(hipStream_t st, const fe* trace, uint64_t n, const AirOpDev* ops, uint32_t n_ops, const fe* consts, fe* num, fe* den) {
@@ -55,7 +33,7 @@ __global__ void __launch_bounds__(256) air_aux_apply_den_kernel(fe* __restrict__
     if (i >= n) return;
     const uint32_t d = blockIdx.y;
     fe* p = num + (uint64_t)col_of[d] * n + i;
-    aa_st(p, fe_mul(aa_ld(p), aa_ld(dinv + (uint64_t)d * n + i)));
+    fe_st(p, fe_mul(fe_ld(p), fe_ld(dinv + (uint64_t)d * n + i)));
 }
 
 int air_aux_apply_den(hipStream_t st, fe* num, const fe* dinv, const uint32_t* col_of, uint32_t n_den, uint64_t n) {
@@ -97,10 +75,10 @@ __global__ void __launch_bounds__(256) as_block_totals_kernel(const fe* __restri
     const uint64_t base = (uint64_t)blockIdx.x * AS_BLOCK + (uint64_t)threadIdx.x * AS_PER_THREAD;
     fe acc = as_id(kind);
     for (int j = 0; j < AS_PER_THREAD; ++j)
-        if (base + j < n) acc = as_op(kind, acc, aa_ld(col + base + j));
+        if (base + j < n) acc = as_op(kind, acc, fe_ld(col + base + j));
     fe tot;
     (void)as_block_exclusive(kind, acc, sh, &tot);
-    if (threadIdx.x == 0) aa_st(block_tot + (uint64_t)k * gridDim.x + blockIdx.x, tot);
+    if (threadIdx.x == 0) fe_st(block_tot + (uint64_t)k * gridDim.x + blockIdx.x, tot);
 }
 
 // one block per column: the `count` block totals of column blockIdx.x -> their exclusive prefixes, in place
@@ -111,12 +89,12 @@ __global__ void __launch_bounds__(256) as_scan_totals_kernel(fe* __restrict__ bl
     const uint64_t per = (count + 255) / 256, base = (uint64_t)threadIdx.x * per;
     fe acc = as_id(kind);
     for (uint64_t j = 0; j < per; ++j)
-        if (base + j < count) acc = as_op(kind, acc, aa_ld(tot + base + j));
+        if (base + j < count) acc = as_op(kind, acc, fe_ld(tot + base + j));
     fe run = as_block_exclusive(kind, acc, sh, nullptr);
     for (uint64_t j = 0; j < per; ++j)
         if (base + j < count) {
-            const fe cur = aa_ld(tot + base + j);
-            aa_st(tot + base + j, run);
+            const fe cur = fe_ld(tot + base + j);
+            fe_st(tot + base + j, run);
             run = as_op(kind, run, cur);
         }
 }
@@ -130,13 +108,13 @@ __global__ void __launch_bounds__(256) as_apply_kernel(fe* __restrict__ data, ui
     fe acc = as_id(kind);
 #pragma unroll
     for (int j = 0; j < AS_PER_THREAD; ++j) {
-        vals[j] = (base + j < n) ? aa_ld(col + base + j) : as_id(kind);
+        vals[j] = (base + j < n) ? fe_ld(col + base + j) : as_id(kind);
         acc = as_op(kind, acc, vals[j]);
     }
-    fe run = as_op(kind, aa_ld(block_prefix + (uint64_t)k * gridDim.x + blockIdx.x), as_block_exclusive(kind, acc, sh, nullptr));
+    fe run = as_op(kind, fe_ld(block_prefix + (uint64_t)k * gridDim.x + blockIdx.x), as_block_exclusive(kind, acc, sh, nullptr));
 #pragma unroll
     for (int j = 0; j < AS_PER_THREAD; ++j) {
-        if (base + j < n) aa_st(col + base + j, run);   // exclusive: row i gets the elements before it
+        if (base + j < n) fe_st(col + base + j, run);   // exclusive: row i gets the elements before it
         run = as_op(kind, run, vals[j]);
     }
 }

@@ -1,0 +1,41 @@
+// The device interpreter of a straight-line AIR program (AirOpDev with slots, as air_assign_slots produces it): one lane runs the
+// whole program with its values in a per-thread array (scratch); every lane of a launch reads the same op and the same constant.
+// What differs between the consumers - the composition on LDE points, the exact row evaluation of the trace check and the report, the
+// auxiliary columns' terms - comes in as three functors, inlined with the loop:
+//   load(a, b)      -> fe   op 0: a = frame row (or, for an auxiliary program, the row shift itself), b = column
+//   periodic(a, b)  -> fe   op 6: a = frame row, b = periodic column; called only when PER
+//   out(a, value)           op 5: a = constraint (or the num / den column of an auxiliary program)
+// PER = false leaves no test for op 6 in the generated code: a program without periodic columns runs the code it always ran.
+#pragma once
+#include "stark_kernels.h"
+
+namespace sp {
+
+struct AirNoPeriodic { __device__ fe operator()(uint32_t, uint32_t) const { return fe_zero(); } };
+
+template <bool PER, class Load, class Periodic, class Out>
+__device__ __forceinline__ void air_run_program(const AirOpDev* __restrict__ ops, uint32_t n_ops, const fe* __restrict__ consts, Load load,
+                                                Periodic periodic, Out out) {
+    fe v[AIR_MAX_LIVE];
+    for (uint32_t t = 0; t < n_ops; ++t) {
+        const AirOpDev o = ops[t];
+        fe r = fe_zero();
+        if constexpr (PER) {
+            if (o.op == 6) {
+                v[o.dst] = periodic(o.a, o.b);
+                continue;
+            }
+        }
+        switch (o.op) {
+            case 0: r = load(o.a, o.b); break;
+            case 1: r = fe_ld(consts + o.a); break;
+            case 2: r = fe_add(v[o.a], v[o.b]); break;
+            case 3: r = fe_sub(v[o.a], v[o.b]); break;
+            case 4: r = fe_mul(v[o.a], v[o.b]); break;
+            default: out(o.a, v[o.b]); continue;
+        }
+        v[o.dst] = r;
+    }
+}
+
+}  // namespace sp

@@ -6,20 +6,6 @@
 
 namespace sp {
 
-__device__ __forceinline__ fe ax_ld(const fe* p) {
-    const uint4* q = reinterpret_cast<const uint4*>(p);
-    uint4 lo = q[0], hi = q[1];
-    fe r;
-    r.v[0] = lo.x; r.v[1] = lo.y; r.v[2] = lo.z; r.v[3] = lo.w;
-    r.v[4] = hi.x; r.v[5] = hi.y; r.v[6] = hi.z; r.v[7] = hi.w;
-    return r;
-}
-__device__ __forceinline__ void ax_st(fe* p, const fe& a) {
-    uint4* q = reinterpret_cast<uint4*>(p);
-    q[0] = make_uint4(a.v[0], a.v[1], a.v[2], a.v[3]);
-    q[1] = make_uint4(a.v[4], a.v[5], a.v[6], a.v[7]);
-}
-
 struct AuxConsts { fe z, alpha, zrc; };
 
 // ---- memory part -------------------------------------------------------------------------------------------
@@ -32,12 +18,12 @@ __global__ void __launch_bounds__(256) aux_keys_kernel(const fe* mem_cols, uint6
     fe a, v;
     if (e >= 4 * n - pm) {  // last |pm| accesses are replaced by the public memory (air.rs:475-494)
         uint64_t j = e - (4 * n - pm);
-        a = ax_ld(pm_addr + j); v = ax_ld(pm_val + j);
+        a = fe_ld(pm_addr + j); v = fe_ld(pm_val + j);
     } else {
-        a = ax_ld(mem_cols + (uint64_t)k * n + i);
-        v = ax_ld(mem_cols + (uint64_t)(4 + k) * n + i);
+        a = fe_ld(mem_cols + (uint64_t)k * n + i);
+        v = fe_ld(mem_cols + (uint64_t)(4 + k) * n + i);
     }
-    ax_st(a_aux + e, a); ax_st(v_aux + e, v);
+    fe_st(a_aux + e, a); fe_st(v_aux + e, v);
     fe raw = fe_from_mont(a);
     // an address beyond 2^64 (no Cairo VM produces one; the reference sorts whatever the table holds by its 256-bit value,
     // air.rs:519-523): flag 2 sends the caller to the four-limb sort below, which passes all_limbs = 1
@@ -52,7 +38,7 @@ __global__ void __launch_bounds__(256) aux_limb_keys_kernel(const fe* a_aux, con
     uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= M) return;
     const uint32_t s = order[e];
-    const fe raw = fe_from_mont(ax_ld(a_aux + s));
+    const fe raw = fe_from_mont(fe_ld(a_aux + s));
     keys[e] = (uint64_t)raw.v[2 * limb] | ((uint64_t)raw.v[2 * limb + 1] << 32);
     idx[e] = s;
 }
@@ -60,22 +46,22 @@ __global__ void __launch_bounds__(256) aux_gather_pairs_kernel(const fe* a_aux, 
     uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= M) return;
     uint32_t s = idx[e];
-    ax_st(a_s + e, ax_ld(a_aux + s)); ax_st(v_s + e, ax_ld(v_aux + s));
+    fe_st(a_s + e, fe_ld(a_aux + s)); fe_st(v_s + e, fe_ld(v_aux + s));
 }
 // num[e] = z - (a + alpha v) of the ORIGINAL access e (air.rs:543-550), den[e] = the same of the sorted pair e
 __global__ void __launch_bounds__(256) aux_num_den_kernel(const fe* mem_cols, uint64_t n, const fe* a_s, const fe* v_s, AuxConsts K, fe* num, fe* den) {
     uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= 4 * n) return;
     uint64_t i = e >> 2; uint32_t k = (uint32_t)e & 3;
-    const fe a = ax_ld(mem_cols + (uint64_t)k * n + i), v = ax_ld(mem_cols + (uint64_t)(4 + k) * n + i);
-    ax_st(num + e, fe_sub(K.z, fe_add(a, fe_mul(K.alpha, v))));
-    ax_st(den + e, fe_sub(K.z, fe_add(ax_ld(a_s + e), fe_mul(K.alpha, ax_ld(v_s + e)))));
+    const fe a = fe_ld(mem_cols + (uint64_t)k * n + i), v = fe_ld(mem_cols + (uint64_t)(4 + k) * n + i);
+    fe_st(num + e, fe_sub(K.z, fe_add(a, fe_mul(K.alpha, v))));
+    fe_st(den + e, fe_sub(K.z, fe_add(fe_ld(a_s + e), fe_mul(K.alpha, fe_ld(v_s + e)))));
 }
 
 __global__ void __launch_bounds__(256) mul_inplace_kernel(fe* x, const fe* y, uint64_t M) {
     uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= M) return;
-    ax_st(x + e, fe_mul(ax_ld(x + e), ax_ld(y + e)));
+    fe_st(x + e, fe_mul(fe_ld(x + e), fe_ld(y + e)));
 }
 
 // ---- prefix product ----------------------------------------------------------------------------------------
@@ -103,10 +89,10 @@ __global__ void __launch_bounds__(256) pp_block_totals_kernel(const fe* data, ui
     uint64_t base = (uint64_t)blockIdx.x * PP_BLOCK + (uint64_t)threadIdx.x * PP_PER_THREAD;
     fe acc = fe_one();
     for (int k = 0; k < PP_PER_THREAD; ++k)
-        if (base + k < M) acc = fe_mul(acc, ax_ld(data + base + k));
+        if (base + k < M) acc = fe_mul(acc, fe_ld(data + base + k));
     fe tot;
     (void)block_exclusive_scan(acc, sh, &tot);
-    if (threadIdx.x == 0) ax_st(block_tot + blockIdx.x, tot);
+    if (threadIdx.x == 0) fe_st(block_tot + blockIdx.x, tot);
 }
 
 // single block: in-place inclusive scan of `count` block totals, converted to EXCLUSIVE prefixes
@@ -116,12 +102,12 @@ __global__ void __launch_bounds__(256) pp_scan_totals_kernel(fe* block_tot, uint
     uint64_t base = (uint64_t)threadIdx.x * per;
     fe acc = fe_one();
     for (uint64_t k = 0; k < per; ++k)
-        if (base + k < count) acc = fe_mul(acc, ax_ld(block_tot + base + k));
+        if (base + k < count) acc = fe_mul(acc, fe_ld(block_tot + base + k));
     fe run = block_exclusive_scan(acc, sh, nullptr);
     for (uint64_t k = 0; k < per; ++k)
         if (base + k < count) {
-            fe cur = ax_ld(block_tot + base + k);
-            ax_st(block_tot + base + k, run);  // exclusive prefix of block (base + k)
+            fe cur = fe_ld(block_tot + base + k);
+            fe_st(block_tot + base + k, run);  // exclusive prefix of block (base + k)
             run = fe_mul(run, cur);
         }
 }
@@ -133,14 +119,14 @@ __global__ void __launch_bounds__(256) pp_apply_kernel(fe* data, uint64_t M, con
     fe acc = fe_one();
 #pragma unroll
     for (int k = 0; k < PP_PER_THREAD; ++k) {
-        vals[k] = (base + k < M) ? ax_ld(data + base + k) : fe_one();
+        vals[k] = (base + k < M) ? fe_ld(data + base + k) : fe_one();
         acc = fe_mul(acc, vals[k]);
     }
-    fe run = fe_mul(ax_ld(block_prefix + blockIdx.x), block_exclusive_scan(acc, sh, nullptr));
+    fe run = fe_mul(fe_ld(block_prefix + blockIdx.x), block_exclusive_scan(acc, sh, nullptr));
 #pragma unroll
     for (int k = 0; k < PP_PER_THREAD; ++k) {
         run = fe_mul(run, vals[k]);
-        if (base + k < M) ax_st(data + base + k, run);
+        if (base + k < M) fe_st(data + base + k, run);
     }
 }
 
@@ -161,7 +147,7 @@ __global__ void __launch_bounds__(256) rc_keys_kernel(const fe* off_cols, uint64
     uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= 3 * n) return;
     uint64_t i = e / 3; uint32_t k = (uint32_t)(e % 3);
-    fe raw = fe_from_mont(ax_ld(off_cols + (uint64_t)k * n + i));
+    fe raw = fe_from_mont(fe_ld(off_cols + (uint64_t)k * n + i));
     keys[e] = (uint16_t)raw.v[0];     // the low 16 bits whatever the cell holds, like the reference (air.rs:689-692: `representative().into()` to u16)
     (void)flag;
 }
@@ -169,14 +155,14 @@ __global__ void __launch_bounds__(256) rc_den_kernel(fe* den, AuxConsts K) {
     uint32_t v = blockIdx.x * 256 + threadIdx.x;
     if (v >= 65536) return;
     fe raw = fe_zero(); raw.v[0] = v;
-    ax_st(den + v, fe_sub(K.zrc, fe_to_mont(raw)));
+    fe_st(den + v, fe_sub(K.zrc, fe_to_mont(raw)));
 }
 __global__ void __launch_bounds__(256) rc_terms_kernel(const fe* off_cols, uint64_t n, const uint16_t* sorted, const fe* dinv, AuxConsts K, fe* terms) {
     uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= 3 * n) return;
     uint64_t i = e / 3; uint32_t k = (uint32_t)(e % 3);
-    fe o = ax_ld(off_cols + (uint64_t)k * n + i);
-    ax_st(terms + e, fe_mul(fe_sub(K.zrc, o), ax_ld(dinv + sorted[e])));
+    fe o = fe_ld(off_cols + (uint64_t)k * n + i);
+    fe_st(terms + e, fe_mul(fe_sub(K.zrc, o), fe_ld(dinv + sorted[e])));
 }
 
 // ---- wide format (air.rs:705-728), straight into natural-order columns -------------------------------------
@@ -186,19 +172,19 @@ __global__ void __launch_bounds__(256) aux_sorted_columns_kernel(uint64_t n, con
     if (i >= n) return;
     for (uint32_t k = 0; k < 3; ++k) {
         fe raw = fe_zero(); raw.v[0] = rc_sorted[3 * i + k];
-        ax_st(out + (uint64_t)k * n + i, fe_to_mont(raw));
+        fe_st(out + (uint64_t)k * n + i, fe_to_mont(raw));
     }
     for (uint32_t k = 0; k < 4; ++k) {
-        ax_st(out + (uint64_t)(3 + k) * n + i, ax_ld(a_s + 4 * i + k));
-        ax_st(out + (uint64_t)(7 + k) * n + i, ax_ld(v_s + 4 * i + k));
+        fe_st(out + (uint64_t)(3 + k) * n + i, fe_ld(a_s + 4 * i + k));
+        fe_st(out + (uint64_t)(7 + k) * n + i, fe_ld(v_s + 4 * i + k));
     }
 }
 // columns 11-14 memory permutation, 15-17 range-check permutation (the two prefix products)
 __global__ void __launch_bounds__(256) aux_permutation_columns_kernel(uint64_t n, const fe* perm, const fe* rperm, fe* out) {
     uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    for (uint32_t k = 0; k < 4; ++k) ax_st(out + (uint64_t)(11 + k) * n + i, ax_ld(perm + 4 * i + k));
-    for (uint32_t k = 0; k < 3; ++k) ax_st(out + (uint64_t)(15 + k) * n + i, ax_ld(rperm + 3 * i + k));
+    for (uint32_t k = 0; k < 4; ++k) fe_st(out + (uint64_t)(11 + k) * n + i, fe_ld(perm + 4 * i + k));
+    for (uint32_t k = 0; k < 3; ++k) fe_st(out + (uint64_t)(15 + k) * n + i, fe_ld(rperm + 3 * i + k));
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------

@@ -4,20 +4,6 @@
 
 namespace sp {
 
-__device__ __forceinline__ fe fk_ld(const fe* p) {
-    const uint4* q = reinterpret_cast<const uint4*>(p);
-    uint4 lo = q[0], hi = q[1];
-    fe r;
-    r.v[0] = lo.x; r.v[1] = lo.y; r.v[2] = lo.z; r.v[3] = lo.w;
-    r.v[4] = hi.x; r.v[5] = hi.y; r.v[6] = hi.z; r.v[7] = hi.w;
-    return r;
-}
-__device__ __forceinline__ void fk_st(fe* p, const fe& a) {
-    uint4* q = reinterpret_cast<uint4*>(p);
-    q[0] = make_uint4(a.v[0], a.v[1], a.v[2], a.v[3]);
-    q[1] = make_uint4(a.v[4], a.v[5], a.v[6], a.v[7]);
-}
-
 // FieldElement::inplace_batch_inverse (reference src/starks/constraints/evaluator.rs:69,171; lambdaworks-math):
 // Montgomery's trick per thread over the strided chunk {t, t+T, t+2T, ...} (T = total threads), so that every
 // global access of a wave is contiguous. scratch holds the running prefix products (n elements).
@@ -27,16 +13,16 @@ __global__ void __launch_bounds__(256) batch_inverse_kernel(fe* data, fe* scratc
     if (t >= n) return;
     fe acc = fe_one();
     for (uint64_t i = t; i < n; i += T) {
-        fk_st(scratch + i, acc);
-        acc = fe_mul(acc, fk_ld(data + i));
+        fe_st(scratch + i, acc);
+        acc = fe_mul(acc, fe_ld(data + i));
     }
     if (fe_is_zero(acc)) { atomicExch(zero_flag, 1); return; }
     fe inv = fe_inv(acc);
     uint64_t cnt = (n - t + T - 1) / T;
     for (uint64_t m = cnt; m-- > 0;) {
         uint64_t i = t + m * T;
-        fe a = fk_ld(data + i);
-        fk_st(data + i, fe_mul(inv, fk_ld(scratch + i)));
+        fe a = fe_ld(data + i);
+        fe_st(data + i, fe_mul(inv, fe_ld(scratch + i)));
         inv = fe_mul(inv, a);
     }
 }
@@ -52,28 +38,28 @@ constexpr uint32_t BI_TOP = 8;
 __global__ void __launch_bounds__(256) batch_inverse_prefix_kernel(const fe* data, fe* scratch, uint64_t T) {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= T) return;
-    fe acc = fk_ld(data + t);
+    fe acc = fe_ld(data + t);
 #pragma unroll 1
     for (uint32_t k = 1; k < BI_CHUNK; ++k) {
-        if (k >= 2) fk_st(scratch + t + k * T, acc);
-        acc = fe_mul(acc, fk_ld(data + t + k * T));
+        if (k >= 2) fe_st(scratch + t + k * T, acc);
+        acc = fe_mul(acc, fe_ld(data + t + k * T));
     }
-    fk_st(scratch + t, acc);   // chunk product
+    fe_st(scratch + t, acc);   // chunk product
 }
 __global__ void __launch_bounds__(256) batch_inverse_unwind_kernel(fe* data, const fe* scratch, uint64_t T) {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= T) return;
-    fe inv = fk_ld(scratch + t);   // inverse of the chunk product
+    fe inv = fe_ld(scratch + t);   // inverse of the chunk product
 #pragma unroll 1
     for (uint32_t k = BI_CHUNK; k-- > 2;) {
         const uint64_t i = t + k * T;
-        fe a = fk_ld(data + i);
-        fk_st(data + i, fe_mul(inv, fk_ld(scratch + i)));
+        fe a = fe_ld(data + i);
+        fe_st(data + i, fe_mul(inv, fe_ld(scratch + i)));
         inv = fe_mul(inv, a);
     }
-    fe a1 = fk_ld(data + t + T), a0 = fk_ld(data + t);
-    fk_st(data + t + T, fe_mul(inv, a0));
-    fk_st(data + t, fe_mul(inv, a1));
+    fe a1 = fe_ld(data + t + T), a0 = fe_ld(data + t);
+    fe_st(data + t + T, fe_mul(inv, a0));
+    fe_st(data + t, fe_mul(inv, a1));
 }
 
 int batch_inverse(hipStream_t st, fe* data, fe* scratch, uint64_t n, int* zero_flag_dev) {
@@ -136,7 +122,7 @@ __global__ void __launch_bounds__(256) rows_to_columns_kernel(const uint8_t* row
     {
         uint32_t ry = threadIdx.x & 31, cx = threadIdx.x >> 5;
         uint64_t rr = row0 + ry; uint32_t cc = col0 + cx;
-        if (rr < n_rows && cc < n_cols) fk_st(cols + (uint64_t)cc * col_stride + rr, tile[ry][cx]);
+        if (rr < n_rows && cc < n_cols) fe_st(cols + (uint64_t)cc * col_stride + rr, tile[ry][cx]);
     }
 }
 
@@ -155,8 +141,8 @@ int rows_to_columns(hipStream_t st, int enc, const uint8_t* rows_dev, uint64_t n
 __global__ void __launch_bounds__(256) mul_elements_kernel(const fe* a, const fe* b, uint64_t n, fe* out) {
     uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const fe x = fk_ld(a + i);
-    fk_st(out + i, b ? fe_mul(x, fk_ld(b + i)) : fe_sqr(x));
+    const fe x = fe_ld(a + i);
+    fe_st(out + i, b ? fe_mul(x, fe_ld(b + i)) : fe_sqr(x));
 }
 int mul_elements(hipStream_t st, const fe* a, const fe* b, uint64_t n, fe* out) {
     if (n == 0) return SP_OK;
@@ -170,7 +156,7 @@ template <int ENC>
 __global__ void __launch_bounds__(256) encode_kernel(const fe* in, uint64_t n, uint8_t* out) {
     uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    fe x = fk_ld(in + i);
+    fe x = fe_ld(in + i);
     if (ENC == SP_FE_MONT_LIMBS) {
         uint64_t l[4];
         fe_to_lw_limbs(x, l);
@@ -199,7 +185,7 @@ __global__ void __launch_bounds__(256) decode_kernel(const uint8_t* in, uint64_t
         for (int k = 0; k < 8; ++k) raw.v[k] = sp_bswap32(p[7 - k]);
         x = fe_to_mont(raw);
     }
-    fk_st(out + i, x);
+    fe_st(out + i, x);
 }
 
 // Host-to-device copy by a kernel that reads page-locked host memory over PCIe itself (52 - 54 GB/s against 56 for the DMA engine,
@@ -247,7 +233,7 @@ __global__ void __launch_bounds__(256) expand_bit_columns_kernel(const uint64_t*
     if (e >= total) return;
     const uint64_t c = e / n, i = e - c * n;
     const uint64_t w = bits[c * (n >> 6) + (i >> 6)];
-    fk_st(out + e, ((w >> (i & 63)) & 1ULL) ? fe_one() : fe_zero());
+    fe_st(out + e, ((w >> (i & 63)) & 1ULL) ? fe_one() : fe_zero());
 }
 int expand_bit_columns(hipStream_t st, const uint64_t* bits_dev, uint64_t n, uint32_t cols, fe* out) {
     if (!bits_dev || !out || n < 64 || (n & 63)) return SP_E_INVALID_ARG;

@@ -56,6 +56,21 @@ SP_HD bool fe_eq(const fe& a, const fe& b) {
     return o == 0;
 }
 
+// One element to or from device memory as two 16-byte accesses (device only).
+__device__ __forceinline__ fe fe_ld(const fe* p) {
+    const uint4* q = reinterpret_cast<const uint4*>(p);
+    uint4 lo = q[0], hi = q[1];
+    fe r;
+    r.v[0] = lo.x; r.v[1] = lo.y; r.v[2] = lo.z; r.v[3] = lo.w;
+    r.v[4] = hi.x; r.v[5] = hi.y; r.v[6] = hi.z; r.v[7] = hi.w;
+    return r;
+}
+__device__ __forceinline__ void fe_st(fe* p, const fe& a) {
+    uint4* q = reinterpret_cast<uint4*>(p);
+    q[0] = make_uint4(a.v[0], a.v[1], a.v[2], a.v[3]);
+    q[1] = make_uint4(a.v[4], a.v[5], a.v[6], a.v[7]);
+}
+
 // 32-bit add/sub with carry: clang lowers these to v_addc_co_u32 / v_subb_co_u32 chains on gfx950
 #define SP_ADDC(x, y, cin, cout) __builtin_addc((uint32_t)(x), (uint32_t)(y), (unsigned)(cin), &(cout))
 #define SP_SUBC(x, y, bin, bout) __builtin_subc((uint32_t)(x), (uint32_t)(y), (unsigned)(bin), &(bout))

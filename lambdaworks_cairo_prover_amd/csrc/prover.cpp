@@ -5,6 +5,7 @@
 #include <cstring>
 #include <cmath>
 #include <functional>
+#include <numeric>
 
 namespace sp {
 
@@ -445,6 +446,18 @@ int validate_aux_program(const AirAuxHost& aux, uint32_t main_cols, uint32_t n_r
     return SP_OK;
 }
 
+// One upload block: regions in the order they are placed, each at a multiple of 256 bytes.
+struct UploadLayout {
+    size_t bytes = 0;
+    size_t place(size_t b) { const size_t o = bytes; bytes = (bytes + b + 255) & ~size_t(255); return o; }
+};
+// The value table of a program (op 1 indexes it): its constants, then the RAP challenges.
+static void fill_consts_then_rap(uint8_t* at, const std::vector<fe>& consts, const std::vector<fe>& rap) {
+    fe* h = reinterpret_cast<fe*>(at);
+    std::copy(consts.begin(), consts.end(), h);
+    std::copy(rap.begin(), rap.end(), h + consts.size());
+}
+
 // Chunks of columns bound the workspace: a chunk holds at most max(1, AUXP_CHUNK_ELEMS / n) columns, so its denominators take
 // at most max(2^22, n) elements (128 MB up to 2^22 rows, 32 bytes a row beyond) and the batch inversion as much scratch again,
 // whatever the number of auxiliary columns.  The numerators are written straight into the trace columns they become.
@@ -488,20 +501,18 @@ int StarkProver::commit_aux_program(const AirAuxHost& aux, const std::vector<fe>
         chunks.push_back(std::move(ch));
     }
     // --- one upload: constants (then the RAP challenges), and per chunk its ops, column kinds and denominator -> column table
-    size_t bytes = 0;
-    auto place = [&bytes](size_t b) { const size_t o = bytes; bytes = (bytes + b + 255) & ~size_t(255); return o; };
-    const size_t o_consts = place(sizeof(fe) * std::max<size_t>(1, aux.consts.size() + rap.size()));
+    UploadLayout lay;
+    const size_t o_consts = lay.place(sizeof(fe) * std::max<size_t>(1, aux.consts.size() + rap.size()));
     for (Chunk& ch : chunks) {
-        ch.o_ops = place(sizeof(AirOpDev) * ch.ops.size());
-        ch.o_kinds = place(sizeof(uint32_t) * ch.kc);
-        ch.o_col = place(sizeof(uint32_t) * std::max<uint32_t>(1, ch.n_den));
+        ch.o_ops = lay.place(sizeof(AirOpDev) * ch.ops.size());
+        ch.o_kinds = lay.place(sizeof(uint32_t) * ch.kc);
+        ch.o_col = lay.place(sizeof(uint32_t) * std::max<uint32_t>(1, ch.n_den));
     }
+    const size_t bytes = lay.bytes;
     SP_TRY(grow(od_.auxp_buf, bytes));
     std::vector<uint8_t>& up = h_auxp_up_;
     up.assign(bytes, 0);
-    fe* hconst = reinterpret_cast<fe*>(up.data() + o_consts);
-    for (size_t i = 0; i < aux.consts.size(); ++i) hconst[i] = aux.consts[i];
-    for (size_t i = 0; i < rap.size(); ++i) hconst[aux.consts.size() + i] = rap[i];
+    fill_consts_then_rap(up.data() + o_consts, aux.consts, rap);
     for (const Chunk& ch : chunks) {
         std::memcpy(up.data() + ch.o_ops, ch.ops.data(), sizeof(AirOpDev) * ch.ops.size());
         std::memcpy(up.data() + ch.o_kinds, ch.kinds.data(), sizeof(uint32_t) * ch.kc);
@@ -745,6 +756,54 @@ int StarkProver::build_air_program(const AirDescHost& air, size_t n_rap, const A
     return SP_OK;
 }
 
+// The part of od_.air_buf that the composition and the trace check share, laid out and filled in h_air_up_ (every region 256-byte
+// aligned): the AirProgram header with its ops / consts pointers set, the slotted ops, the constants followed by the RAP challenges,
+// bvalue / bstep / bcol with constraint order[j] at position j, the periodic descriptors and values; behind them one region per entry
+// of `extra` (its bytes, and where its offset goes), which the caller fills.  od_.air_buf is grown to the whole block; the caller
+// uploads it in one copy.  tabs: T, B, bvalue, bstep, bcol, pcols, pvals set, the rest zero.
+int StarkProver::build_air_block(const AirDescHost& air, const std::vector<fe>& rap, const AirPeriodicHost* periodic, AirProgramHost& ph,
+                                 const std::vector<uint32_t>& order, std::initializer_list<std::pair<size_t, size_t*>> extra,
+                                 AirCompTables& tabs, const AirProgram*& prog_dev) {
+    const uint32_t B = (uint32_t)air.boundary.size(), Kp = (uint32_t)ph.pcols.size();
+    for (const BoundaryConstraint& bc : air.boundary)
+        if (bc.col >= C_ || bc.step >= n_) { sp_set_error("composition_air: boundary constraint outside the trace"); return SP_E_INVALID_ARG; }
+    UploadLayout lay;
+    const size_t o_prog = lay.place(sizeof(AirProgram)), o_ops = lay.place(sizeof(AirOpDev) * ph.dops.size()),
+                 o_consts = lay.place(sizeof(fe) * (air.consts.size() + rap.size())), o_bval = lay.place(sizeof(fe) * B),
+                 o_bstep = lay.place(sizeof(uint64_t) * B), o_bcol = lay.place(sizeof(uint32_t) * B),
+                 o_pcols = lay.place(sizeof(AirPeriodicCol) * Kp), o_pvals = lay.place(sizeof(fe) * ph.S);
+    for (const auto& x : extra) *x.second = lay.place(x.first);
+    SP_TRY(grow(od_.air_buf, lay.bytes));
+    std::vector<uint8_t>& up = h_air_up_;
+    up.assign(lay.bytes, 0);
+    auto dev_at = [&](size_t off) { return od_.air_buf.p + off; };
+    ph.prog.ops = reinterpret_cast<const AirOpDev*>(dev_at(o_ops));
+    ph.prog.consts = reinterpret_cast<const fe*>(dev_at(o_consts));
+    std::memcpy(up.data() + o_prog, &ph.prog, sizeof(AirProgram));
+    if (!ph.dops.empty()) std::memcpy(up.data() + o_ops, ph.dops.data(), sizeof(AirOpDev) * ph.dops.size());
+    fill_consts_then_rap(up.data() + o_consts, air.consts, rap);
+    fe* hbval = reinterpret_cast<fe*>(up.data() + o_bval);
+    uint64_t* hbstep = reinterpret_cast<uint64_t*>(up.data() + o_bstep);
+    uint32_t* hbcol = reinterpret_cast<uint32_t*>(up.data() + o_bcol);
+    for (uint32_t jp = 0; jp < B; ++jp) {
+        const BoundaryConstraint& bc = air.boundary[order[jp]];
+        hbval[jp] = bc.value; hbstep[jp] = bc.step; hbcol[jp] = bc.col;
+    }
+    if (Kp) std::memcpy(up.data() + o_pcols, ph.pcols.data(), sizeof(AirPeriodicCol) * Kp);
+    for (uint32_t k = 0; k < Kp; ++k) std::memcpy(up.data() + o_pvals + sizeof(fe) * ph.pcols[k].off, periodic->cols[k].data(), sizeof(fe) * periodic->cols[k].size());
+    std::memset(&tabs, 0, sizeof(tabs));
+    tabs.T = (uint32_t)air.degrees.size(); tabs.B = B;
+    tabs.bvalue = reinterpret_cast<const fe*>(dev_at(o_bval));
+    tabs.bstep = reinterpret_cast<const uint64_t*>(dev_at(o_bstep));
+    tabs.bcol = reinterpret_cast<const uint32_t*>(dev_at(o_bcol));
+    if (Kp) {
+        tabs.pcols = reinterpret_cast<const AirPeriodicCol*>(dev_at(o_pcols));
+        tabs.pvals = reinterpret_cast<const fe*>(dev_at(o_pvals));
+    }
+    prog_dev = reinterpret_cast<const AirProgram*>(dev_at(o_prog));
+    return SP_OK;
+}
+
 int StarkProver::composition_air(const AirDescHost& air, const std::vector<fe>& rap, const std::vector<fe>& b_alpha, const std::vector<fe>& b_beta,
                                  const std::vector<fe>& t_alpha, const std::vector<fe>& t_beta, uint8_t root_out[32], const AirPeriodicHost* periodic) {
     if (stage_ != 3 && !(stage_ == 2 && Ca_ == 0)) { sp_set_error("composition: trace segments not committed"); return SP_E_STATE; }
@@ -758,7 +817,6 @@ int StarkProver::composition_air(const AirDescHost& air, const std::vector<fe>& 
     SP_TRY(build_air_program(air, rap.size(), periodic, ph));
     const uint32_t b = 1u << logb_, f = air.degree_bound_factor;
     AirProgram& prog = ph.prog;
-    const std::vector<AirOpDev>& dops = ph.dops;
     const std::vector<AirPeriodicCol>& pcols = ph.pcols;
     const uint32_t Kp = (uint32_t)pcols.size(), max_ex = ph.max_ex;
     const uint64_t S = ph.S;
@@ -783,7 +841,6 @@ int StarkProver::composition_air(const AirDescHost& air, const std::vector<fe>& 
     std::unordered_map<uint64_t, uint32_t> group_of;
     for (uint32_t j = 0; j < B; ++j) {
         const BoundaryConstraint& bc = air.boundary[j];
-        if (bc.col >= C_ || bc.step >= n_) { sp_set_error("composition_air: boundary constraint outside the trace"); return SP_E_INVALID_ARG; }
         auto ins = group_of.emplace(bc.step, (uint32_t)steps.size());
         if (ins.second) { steps.push_back(bc.step); by_row.emplace_back(); }
         by_row[ins.first->second].push_back(j);
@@ -792,41 +849,19 @@ int StarkProver::composition_air(const AirDescHost& air, const std::vector<fe>& 
     std::vector<uint32_t> order;                       // constraint at grouped position j'
     std::vector<uint32_t> gend(nd);
     for (uint32_t g = 0; g < nd; ++g) { order.insert(order.end(), by_row[g].begin(), by_row[g].end()); gend[g] = (uint32_t)order.size(); }
-    // --- the device copy: program header, ops, constants (then the RAP challenges) and the per-proof tables in one buffer sized by
-    //     this proof (grown on demand, kept across proofs), one upload
+    // --- the device copy: the shared block (build_air_block) and behind it this proof's tables, one upload
     const uint32_t nterm = T + B;
-    size_t at = 0;
-    auto place = [&at](size_t bytes) { const size_t o = at; at = (at + bytes + 255) & ~size_t(255); return o; };
-    const size_t o_prog = place(sizeof(AirProgram)), o_ops = place(sizeof(AirOpDev) * dops.size()),
-                 o_consts = place(sizeof(fe) * (air.consts.size() + rap.size())), o_zf = place(sizeof(fe) * b),
-                 o_coef = place(sizeof(fe) * b * nterm), o_bval = place(sizeof(fe) * B), o_gpt = place(sizeof(fe) * nd),
-                 o_bstep = place(sizeof(uint64_t) * B), o_bcol = place(sizeof(uint32_t) * B), o_gend = place(sizeof(uint32_t) * nd),
-                 o_pcols = place(sizeof(AirPeriodicCol) * Kp), o_pvals = place(sizeof(fe) * S);
-    SP_TRY(grow(od_.air_buf, at));
+    size_t o_zf, o_coef, o_gpt, o_gend;
+    AirCompTables tabs;
+    const AirProgram* prog_dev = nullptr;
+    SP_TRY(build_air_block(air, rap, periodic, ph, order,
+                           {{sizeof(fe) * b, &o_zf}, {sizeof(fe) * b * nterm, &o_coef}, {sizeof(fe) * nd, &o_gpt}, {sizeof(uint32_t) * nd, &o_gend}}, tabs, prog_dev));
     std::vector<uint8_t>& up = h_air_up_;
-    up.assign(at, 0);
-    auto host_at = [&](size_t off) { return up.data() + off; };
     auto dev_at = [&](size_t off) { return od_.air_buf.p + off; };
-    prog.ops = reinterpret_cast<const AirOpDev*>(dev_at(o_ops));
-    prog.consts = reinterpret_cast<const fe*>(dev_at(o_consts));
-    std::memcpy(host_at(o_prog), &prog, sizeof(prog));
-    if (!dops.empty()) std::memcpy(host_at(o_ops), dops.data(), sizeof(AirOpDev) * dops.size());
-    fe* hconst = reinterpret_cast<fe*>(host_at(o_consts));
-    for (size_t i = 0; i < air.consts.size(); ++i) hconst[i] = air.consts[i];
-    for (size_t i = 0; i < rap.size(); ++i) hconst[air.consts.size() + i] = rap[i];
-    fe* hzf = reinterpret_cast<fe*>(host_at(o_zf));
-    fe* hcoef = reinterpret_cast<fe*>(host_at(o_coef));
-    fe* hbval = reinterpret_cast<fe*>(host_at(o_bval));
-    fe* hgpt = reinterpret_cast<fe*>(host_at(o_gpt));
-    uint64_t* hbstep = reinterpret_cast<uint64_t*>(host_at(o_bstep));
-    uint32_t* hbcol = reinterpret_cast<uint32_t*>(host_at(o_bcol));
-    std::memcpy(host_at(o_gend), gend.data(), sizeof(uint32_t) * nd);
-    for (uint32_t jp = 0; jp < B; ++jp) {
-        const BoundaryConstraint& bc = air.boundary[order[jp]];
-        hbval[jp] = bc.value; hbstep[jp] = bc.step; hbcol[jp] = bc.col;
-    }
-    if (Kp) std::memcpy(host_at(o_pcols), pcols.data(), sizeof(AirPeriodicCol) * Kp);
-    for (uint32_t k = 0; k < Kp; ++k) std::memcpy(host_at(o_pvals) + sizeof(fe) * pcols[k].off, periodic->cols[k].data(), sizeof(fe) * periodic->cols[k].size());
+    fe* hzf = reinterpret_cast<fe*>(up.data() + o_zf);
+    fe* hcoef = reinterpret_cast<fe*>(up.data() + o_coef);
+    fe* hgpt = reinterpret_cast<fe*>(up.data() + o_gpt);
+    std::memcpy(up.data() + o_gend, gend.data(), sizeof(uint32_t) * nd);
     std::vector<fe> points(nd);
     for (uint32_t g = 0; g < nd; ++g) hgpt[g] = points[g] = fe_pow_u64(g_, steps[g]);
     {
@@ -846,17 +881,12 @@ int StarkProver::composition_air(const AirDescHost& air, const std::vector<fe>& 
         host_batch_inverse(zf);
         for (uint32_t c = 0; c < b; ++c) hzf[c] = zf[c];
     }
-    SP_HIP_CHECK(hipMemcpyAsync(od_.air_buf.p, up.data(), at, hipMemcpyHostToDevice, c_->stream));
-    AirCompTables tabs;
-    tabs.h = h_; tabs.T = T; tabs.B = B; tabs.ndist = nd;
+    SP_HIP_CHECK(hipMemcpyAsync(od_.air_buf.p, up.data(), up.size(), hipMemcpyHostToDevice, c_->stream));
+    tabs.h = h_; tabs.ndist = nd;
     tabs.zerofier = reinterpret_cast<const fe*>(dev_at(o_zf));
     tabs.coef = reinterpret_cast<const fe*>(dev_at(o_coef));
-    tabs.bvalue = reinterpret_cast<const fe*>(dev_at(o_bval));
-    tabs.bcol = reinterpret_cast<const uint32_t*>(dev_at(o_bcol));
-    tabs.bstep = reinterpret_cast<const uint64_t*>(dev_at(o_bstep));
     tabs.gpoint = reinterpret_cast<const fe*>(dev_at(o_gpt));
     tabs.gend = reinterpret_cast<const uint32_t*>(dev_at(o_gend));
-    tabs.pcols = nullptr; tabs.pvals = nullptr; tabs.ptab = nullptr;
     if (Kp) {
         // [b S] tables, [S] working copy of the values (the transforms run in place), [S] scratch.  Every rank builds all b cosets:
         // the kernel indexes by the global LDE index.
@@ -864,19 +894,17 @@ int StarkProver::composition_air(const AirDescHost& air, const std::vector<fe>& 
         fe* tab = od_.periodic.p;
         fe* work = tab + S * b;
         fe* ws = work + S;
-        SP_HIP_CHECK(hipMemcpyAsync(work, dev_at(o_pvals), sizeof(fe) * S, hipMemcpyDeviceToDevice, c_->stream));
+        SP_HIP_CHECK(hipMemcpyAsync(work, tabs.pvals, sizeof(fe) * S, hipMemcpyDeviceToDevice, c_->stream));
         for (uint32_t k = 0; k < Kp;) {   // neighbours of one period in one batch
             uint32_t cnt = 1;
             while (k + cnt < Kp && pcols[k + cnt].logp == pcols[k].logp) ++cnt;
             SP_TRY(air_periodic_tables(c_->stream, *c_->ntt, work + pcols[k].off, ws, tab + pcols[k].off * b, cnt, pcols[k].logp, logn_, logb_, h_));
             k += cnt;
         }
-        tabs.pcols = reinterpret_cast<const AirPeriodicCol*>(dev_at(o_pcols));
-        tabs.pvals = reinterpret_cast<const fe*>(dev_at(o_pvals));
         tabs.ptab = tab;
     }
     offsets_ = air.offsets;
-    return composition_core(nullptr, points, reinterpret_cast<const AirProgram*>(dev_at(o_prog)), &tabs, od_.ex_roots.p, allow_sub, root_out);
+    return composition_core(nullptr, points, prog_dev, &tabs, od_.ex_roots.p, allow_sub, root_out);
 }
 
 // validate_trace (reference debug.rs:13-104) for a program AIR, on the device: the program and the descriptor's boundary constraints
@@ -888,43 +916,13 @@ int StarkProver::check_trace_air(const AirDescHost& air, const std::vector<fe>& 
     SP_HIP_CHECK(hipSetDevice(c_->device));
     AirProgramHost ph;
     SP_TRY(build_air_program(air, rap.size(), periodic, ph));
-    const uint32_t T = (uint32_t)air.degrees.size(), B = (uint32_t)air.boundary.size(), Kp = (uint32_t)ph.pcols.size();
-    for (const BoundaryConstraint& bc : air.boundary)
-        if (bc.col >= C_ || bc.step >= n_) { sp_set_error("composition_air: boundary constraint outside the trace"); return SP_E_INVALID_ARG; }
-    size_t at = 0;
-    auto place = [&at](size_t bytes) { const size_t o = at; at = (at + bytes + 255) & ~size_t(255); return o; };
-    const size_t o_prog = place(sizeof(AirProgram)), o_ops = place(sizeof(AirOpDev) * ph.dops.size()),
-                 o_consts = place(sizeof(fe) * (air.consts.size() + rap.size())), o_bval = place(sizeof(fe) * B),
-                 o_bstep = place(sizeof(uint64_t) * B), o_bcol = place(sizeof(uint32_t) * B),
-                 o_pcols = place(sizeof(AirPeriodicCol) * Kp), o_pvals = place(sizeof(fe) * ph.S);
-    SP_TRY(grow(od_.air_buf, at));
-    std::vector<uint8_t>& up = h_air_up_;
-    up.assign(at, 0);
-    auto dev_at = [&](size_t off) { return od_.air_buf.p + off; };
-    ph.prog.ops = reinterpret_cast<const AirOpDev*>(dev_at(o_ops));
-    ph.prog.consts = reinterpret_cast<const fe*>(dev_at(o_consts));
-    std::memcpy(up.data() + o_prog, &ph.prog, sizeof(AirProgram));
-    if (!ph.dops.empty()) std::memcpy(up.data() + o_ops, ph.dops.data(), sizeof(AirOpDev) * ph.dops.size());
-    fe* hconst = reinterpret_cast<fe*>(up.data() + o_consts);
-    for (size_t i = 0; i < air.consts.size(); ++i) hconst[i] = air.consts[i];
-    for (size_t i = 0; i < rap.size(); ++i) hconst[air.consts.size() + i] = rap[i];
-    fe* hbval = reinterpret_cast<fe*>(up.data() + o_bval);
-    uint64_t* hbstep = reinterpret_cast<uint64_t*>(up.data() + o_bstep);
-    uint32_t* hbcol = reinterpret_cast<uint32_t*>(up.data() + o_bcol);
-    for (uint32_t j = 0; j < B; ++j) { hbval[j] = air.boundary[j].value; hbstep[j] = air.boundary[j].step; hbcol[j] = air.boundary[j].col; }
-    if (Kp) std::memcpy(up.data() + o_pcols, ph.pcols.data(), sizeof(AirPeriodicCol) * Kp);
-    for (uint32_t k = 0; k < Kp; ++k) std::memcpy(up.data() + o_pvals + sizeof(fe) * ph.pcols[k].off, periodic->cols[k].data(), sizeof(fe) * periodic->cols[k].size());
-    SP_HIP_CHECK(hipMemcpyAsync(od_.air_buf.p, up.data(), at, hipMemcpyHostToDevice, c_->stream));
+    const uint32_t T = (uint32_t)air.degrees.size(), B = (uint32_t)air.boundary.size();
+    std::vector<uint32_t> order(B);
+    std::iota(order.begin(), order.end(), 0u);
     AirCompTables tabs;
-    std::memset(&tabs, 0, sizeof(tabs));
-    tabs.T = T; tabs.B = B;
-    tabs.bvalue = reinterpret_cast<const fe*>(dev_at(o_bval));
-    tabs.bstep = reinterpret_cast<const uint64_t*>(dev_at(o_bstep));
-    tabs.bcol = reinterpret_cast<const uint32_t*>(dev_at(o_bcol));
-    if (Kp) {
-        tabs.pcols = reinterpret_cast<const AirPeriodicCol*>(dev_at(o_pcols));
-        tabs.pvals = reinterpret_cast<const fe*>(dev_at(o_pvals));
-    }
+    const AirProgram* prog_dev = nullptr;
+    SP_TRY(build_air_block(air, rap, periodic, ph, order, {}, tabs, prog_dev));
+    SP_HIP_CHECK(hipMemcpyAsync(od_.air_buf.p, h_air_up_.data(), h_air_up_.size(), hipMemcpyHostToDevice, c_->stream));
     // the report block, in 8-byte words: value [4 T] | bcell [4 B] | count [T] | first [T] | last [T] | bbad [B / 2]
     const uint64_t w_value = 0, w_bcell = w_value + 4ull * T, w_count = w_bcell + 4ull * B, w_first = w_count + T, w_last = w_first + T,
                    w_bbad = w_last + T, words = w_bbad + (B + 1) / 2;
@@ -939,7 +937,7 @@ int StarkProver::check_trace_air(const AirDescHost& air, const std::vector<fe>& 
     rep.first = reinterpret_cast<unsigned long long*>(rp + w_first);
     rep.last = reinterpret_cast<unsigned long long*>(rp + w_last);
     rep.bbad = reinterpret_cast<uint32_t*>(rp + w_bbad);
-    SP_TRY(air_trace_report(c_->stream, d_trace_, n_, tabs, reinterpret_cast<const AirProgram*>(dev_at(o_prog)), rep));
+    SP_TRY(air_trace_report(c_->stream, d_trace_, n_, tabs, prog_dev, rep));
     h_report_.resize(words * sizeof(uint64_t));
     SP_TRY(readback(h_report_.data(), rp, h_report_.size()));   // (waits for the stream: the upload above is done with h_air_up_)
     const uint64_t* h = reinterpret_cast<const uint64_t*>(h_report_.data());

@@ -11,6 +11,8 @@
 #include <vector>
 #include <memory>
 #include <array>
+#include <initializer_list>
+#include <utility>
 #include <algorithm>
 
 namespace sp {
@@ -236,6 +238,9 @@ class StarkProver : public sp_deletable {
     }
     struct AirProgramHost { AirProgram prog; std::vector<AirOpDev> dops; std::vector<AirPeriodicCol> pcols; uint64_t S = 0; uint32_t max_ex = 0; };   // S: the periods, summed
     int build_air_program(const AirDescHost& air, size_t n_rap, const AirPeriodicHost* periodic, AirProgramHost& out);
+    int build_air_block(const AirDescHost& air, const std::vector<fe>& rap, const AirPeriodicHost* periodic, AirProgramHost& ph,
+                        const std::vector<uint32_t>& order, std::initializer_list<std::pair<size_t, size_t*>> extra, AirCompTables& tabs,
+                        const AirProgram*& prog_dev);
     int composition_core(const CompositionConsts* K, const std::vector<fe>& points, const AirProgram* prog_dev, const AirCompTables* air_tabs,
                          const fe* ex_roots_dev, bool allow_sub_coset, uint8_t root_out[32]);
 

@@ -70,7 +70,7 @@ int cairo_trace_check(hipStream_t st, const fe* trace, uint64_t n, const Composi
 constexpr int AIR_MAX_COLS = 1024, AIR_MAX_TRANSITIONS = 64, AIR_MAX_OFFSETS = 8, AIR_MAX_BOUNDARY = 4096, AIR_MAX_CONSTS = 4096,
               AIR_MAX_OPS = 65535, AIR_MAX_LIVE = 64, AIR_MAX_EXEMPT_KINDS = 4;
 // Device form of one op: the host assigns every value a slot of a small per-point value file (liveness analysis in
-// composition_air), so a long straight-line program needs AIR_MAX_LIVE values per point, not one per op.
+// air_assign_slots), so a long straight-line program needs AIR_MAX_LIVE values per point, not one per op.
 //   0 LOAD(a = row, b = col) -> dst   1 CONST(a = idx) -> dst   2 ADD / 3 SUB / 4 MUL (a, b = slots) -> dst   5 OUT(a = constraint, b = slot)
 //   6 PERIODIC(a = row, b = periodic column) -> dst
 struct AirOpDev { uint8_t op, pad; uint16_t a, b, dst; };
@@ -113,15 +113,18 @@ int boundary_vanishing(hipStream_t st, fe* zb, uint64_t N, uint32_t logN, const 
 // ConstraintEvaluator::evaluate (evaluator.rs:38-260) for a program AIR.  Transition terms as for Cairo; the boundary terms
 // sum_j coef_j (t_col_j(x) - v_j) / (x - g^step_j) accumulate row group by row group as one fraction A / Z_B(x)
 // (A <- A (x - g^s) + S_s P, P <- P (x - g^s)), finished with zbinv[i] = 1 / Z_B(x_i) (boundary_vanishing + batch_inverse).
-// ex_roots[j] = g^(n-1-j).
+// ex_roots[j] = g^(n-1-j).  The constraint program runs in the shared interpreter (air_interp.h): LOAD reads the LDE point, op 6 the
+// periodic TABLE.
 int air_composition(hipStream_t st, const fe* lde, uint64_t count, uint64_t col_len, uint32_t stride_log, uint32_t logN, uint32_t logb,
                     const fe* roots_N, AirCompTables tabs, const AirProgram* prog_dev, const fe* ex_roots,
                     const fe* zbinv, fe* out, uint32_t shard_log = 0, uint32_t shard_rank = 0);
-// (both: tabs.pcols != null selects the instantiation that knows op 6, so a program without periodic columns runs the code it always ran)
-// validate_trace (debug.rs:13-104): the transition constraints on every row (one thread per row), then the boundary
-// values (one thread per constraint); *flag_dev |= 1 on any violation.  Op 6 reads the periodic VALUES, not the table.
+// (here and below: tabs.pcols != null selects the instantiation that knows op 6, so a program without periodic columns runs the code it always ran)
+// validate_trace (debug.rs:13-104): the transition constraints on every row (a kernel of its own, one thread per row: the exact row
+// evaluation - natural-order columns, frame rows modulo n, op 6 from the periodic VALUES, not the table - then one atomicOr), then the
+// boundary values (one thread per constraint); *flag_dev |= 1 on any violation.  tabs: T, B, bvalue, bcol, bstep, pcols, pvals are read.
 int air_trace_check(hipStream_t st, const fe* trace, uint64_t n, AirCompTables tabs, const AirProgram* prog_dev, int* flag_dev);
-// The same check with a report instead of a flag (sp_air_check_trace; validate_trace prints what it finds, debug.rs:52-104).
+// The same check, on the same row evaluation, with a report instead of a flag (sp_air_check_trace; validate_trace prints what it
+// finds, debug.rs:52-104).
 // Per transition constraint k: count[k] = enforced rows on which it is non-zero, first[k] / last[k] = the lowest / highest of them,
 // value[k] = its evaluation on first[k] (Montgomery form; untouched when count[k] is 0).  Per boundary constraint j, in the order of
 // tabs.bcol / bstep / bvalue: bcell[j] = the cell found, bbad[j] = 1 when it differs from the value.

@@ -1,23 +1,11 @@
 // Device kernels of the STARK rounds (see stark_kernels.h).
 #include "stark_kernels.h"
+#include "air_interp.h"
 #include "keccak.h"
 #include "ntt.h"
 
 namespace sp {
 
-__device__ __forceinline__ fe sk_ld(const fe* p) {
-    const uint4* q = reinterpret_cast<const uint4*>(p);
-    uint4 lo = q[0], hi = q[1];
-    fe r;
-    r.v[0] = lo.x; r.v[1] = lo.y; r.v[2] = lo.z; r.v[3] = lo.w;
-    r.v[4] = hi.x; r.v[5] = hi.y; r.v[6] = hi.z; r.v[7] = hi.w;
-    return r;
-}
-__device__ __forceinline__ void sk_st(fe* p, const fe& a) {
-    uint4* q = reinterpret_cast<uint4*>(p);
-    q[0] = make_uint4(a.v[0], a.v[1], a.v[2], a.v[3]);
-    q[1] = make_uint4(a.v[4], a.v[5], a.v[6], a.v[7]);
-}
 __device__ __forceinline__ fe operator+(const fe& a, const fe& b) { return fe_add(a, b); }
 __device__ __forceinline__ fe operator-(const fe& a, const fe& b) { return fe_sub(a, b); }
 __device__ __forceinline__ fe operator*(const fe& a, const fe& b) { return fe_mul(a, b); }
@@ -25,7 +13,7 @@ __device__ __forceinline__ fe operator*(const fe& a, const fe& b) { return fe_mu
 // w_N^e (e in [0, N)) from the half table
 __device__ __forceinline__ fe root_pow(const fe* tw, uint32_t e, uint32_t logN) {
     uint32_t half = 1u << (logN - 1);
-    fe w = sk_ld(tw + (e & (half - 1)));
+    fe w = fe_ld(tw + (e & (half - 1)));
     return (e & half) ? fe_neg(w) : w;
 }
 
@@ -38,7 +26,7 @@ __global__ void __launch_bounds__(256) power_table_kernel(fe* out, uint64_t coun
     fe acc = a.c;
     for (uint32_t i = 0; i < 32; ++i)
         if ((e >> i) & 1) acc = fe_mul(acc, a.pw[i]);
-    sk_st(out + q, acc);
+    fe_st(out + q, acc);
 }
 int gen_power_table(hipStream_t st, fe* out, uint64_t count, uint32_t bitrev_bits, const fe& base, const fe& c) {
     PowTableArgs a;
@@ -61,7 +49,7 @@ __global__ void __launch_bounds__(256) coset_minus_points_kernel(fe* den, uint64
     uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= N) return;
     fe x = fe_mul(root_pow(roots, shard_global_index((uint32_t)i, sm), logN), a.h);
-    for (uint32_t d = 0; d < ndist; ++d) sk_st(den + (uint64_t)d * N + i, fe_sub(x, a.pt[d]));
+    for (uint32_t d = 0; d < ndist; ++d) fe_st(den + (uint64_t)d * N + i, fe_sub(x, a.pt[d]));
 }
 int coset_minus_points(hipStream_t st, fe* den, uint64_t N, uint32_t logN, const fe* roots_N, const fe& h, const fe* points_host, uint32_t ndist, ShardMap sm) {
     if (ndist > AIR_MAX_OFFSETS + 1) return SP_E_INVALID_ARG;
@@ -152,8 +140,8 @@ cairo_composition_kernel(const fe* __restrict__ cols, uint64_t count, uint64_t c
     auto coef_at = [&](uint32_t k) -> fe { if (STAGED) return sh_coef[c * W + k]; else return K->coef[c][k]; };
     const uint32_t A = K->main_cols;
     uint32_t gate = 0;  // see phase_gate
-    auto cur = [&](uint32_t col) { return sk_ld(cols + (uint64_t)col * col_len + e + gate); };
-    auto nxt = [&](uint32_t col) { return sk_ld(cols + (uint64_t)col * col_len + enext + gate); };
+    auto cur = [&](uint32_t col) { return fe_ld(cols + (uint64_t)col * col_len + e + gate); };
+    auto nxt = [&](uint32_t col) { return fe_ld(cols + (uint64_t)col * col_len + enext + gate); };
 
     const fe one = fe_one();
     fe S0 = fe_zero(), S1 = fe_zero(), S2 = fe_zero(), S3 = fe_zero();
@@ -237,15 +225,15 @@ cairo_composition_kernel(const fe* __restrict__ cols, uint64_t count, uint64_t c
             // k = 1..3: next sorted cell of this row; k = 4: first sorted cell of the next row
             const uint64_t row = ((k < 4) ? e : enext) + gate;
             const uint32_t kk = (k < 4) ? k : 0;
-            fe a_k = sk_ld(cols + (uint64_t)(A + 3 + kk) * col_len + row);
-            fe v_k = sk_ld(cols + (uint64_t)(A + 7 + kk) * col_len + row);
-            fe p_k = sk_ld(cols + (uint64_t)(A + 11 + kk) * col_len + row);
+            fe a_k = fe_ld(cols + (uint64_t)(A + 3 + kk) * col_len + row);
+            fe v_k = fe_ld(cols + (uint64_t)(A + 7 + kk) * col_len + row);
+            fe p_k = fe_ld(cols + (uint64_t)(A + 11 + kk) * col_len + row);
             fe step = a_k - a_prev - one;
             fe inc = (a_prev - a_k) * step;           // MEMORY_INCREASING_{k-1}
             fe cons = (v_prev - v_k) * step;          // MEMORY_CONSISTENCY_{k-1}
             // original (unsorted) access k: (dst_addr,dst), (op0_addr,op0), (op1_addr,op1), then next row's (pc,inst)
-            fe a_o = sk_ld(cols + (uint64_t)(K_PC + kk) * col_len + row);
-            fe v_o = sk_ld(cols + (uint64_t)(K_INST + kk) * col_len + row);
+            fe a_o = fe_ld(cols + (uint64_t)(K_PC + kk) * col_len + row);
+            fe v_o = fe_ld(cols + (uint64_t)(K_INST + kk) * col_len + row);
             fe perm = (z - (a_k + alpha * v_k)) * p_k - (z - (a_o + alpha * v_o)) * p_prev;  // PERMUTATION_ARGUMENT_{k-1}
             if (k < 4) {
                 acc(S0, 31 + k - 1, inc); acc(S0, 35 + k - 1, cons); acc(S0, 39 + k - 1, perm);
@@ -295,9 +283,9 @@ cairo_composition_kernel(const fe* __restrict__ cols, uint64_t count, uint64_t c
 #pragma unroll 1
     for (uint32_t j = 0; j < B; ++j) {
         fe num = cur(K->bcol[j]) - K->bvalue[j];
-        total = total + coef_at(T + j) * num * sk_ld(binv + (uint64_t)K->bden[j] * count + i);
+        total = total + coef_at(T + j) * num * fe_ld(binv + (uint64_t)K->bden[j] * count + i);
     }
-    sk_st(out + i, total);
+    fe_st(out + i, total);
 }
 
 int cairo_composition(hipStream_t st, const fe* lde, uint64_t count, uint64_t col_len, uint32_t stride_log, uint32_t logN, uint32_t logb,
@@ -331,13 +319,13 @@ __global__ void __launch_bounds__(256) split_composition_kernel(const fe* X, uin
     if (q >= n) return;
     uint64_t N = n << logb;
     uint64_t pos = logb ? (q << (logb - 1)) : 0;
-    fe t = sk_ld(t2 + q);
+    fe t = fe_ld(t2 + q);
     if (logb == 0) {
         // blowup 1: X has n entries in bit-reversed order of k; even k -> first half. Not used by the prover (b >= 2).
         return;
     }
-    sk_st(H1s + q, fe_mul(sk_ld(X + pos), t));
-    sk_st(H2s + q, fe_mul(fe_mul(sk_ld(X + (N >> 1) + pos), t), a.hinv));
+    fe_st(H1s + q, fe_mul(fe_ld(X + pos), t));
+    fe_st(H2s + q, fe_mul(fe_mul(fe_ld(X + (N >> 1) + pos), t), a.hinv));
 }
 int split_composition(hipStream_t st, const fe* X, uint64_t n, uint32_t logb, const fe* t2, const fe& hinv, fe* H1s, fe* H2s) {
     if (logb == 0) { sp_set_error("split_composition: blowup factor must be >= 2"); return SP_E_UNSUPPORTED; }
@@ -356,7 +344,7 @@ __global__ void __launch_bounds__(256) high_coeff_check_kernel(const fe* X, uint
     if (logb < 2) return;  // b = 2: every coefficient index below N is < 2n
     uint64_t low = q & ((1ULL << (logb - 1)) - 1ULL);
     if (low == 0) return;
-    if (!fe_is_zero(sk_ld(X + q))) atomicOr(flag, 1);
+    if (!fe_is_zero(fe_ld(X + q))) atomicOr(flag, 1);
 }
 int high_coeff_check(hipStream_t st, const fe* X, uint64_t N, uint32_t logb, int* flag_dev) {
     hipLaunchKernelGGL(high_coeff_check_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, X, N, logb, flag_dev);
@@ -368,9 +356,9 @@ int high_coeff_check(hipStream_t st, const fe* X, uint64_t N, uint32_t logb, int
 __global__ void __launch_bounds__(256) split_full_kernel(const fe* X, uint64_t half, const fe* t, SplitArgs a, fe* H1f, fe* H2f) {
     uint64_t q = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (q >= half) return;
-    fe tq = sk_ld(t + q);
-    sk_st(H1f + q, fe_mul(sk_ld(X + q), tq));
-    sk_st(H2f + q, fe_mul(fe_mul(sk_ld(X + half + q), tq), a.hinv));
+    fe tq = fe_ld(t + q);
+    fe_st(H1f + q, fe_mul(fe_ld(X + q), tq));
+    fe_st(H2f + q, fe_mul(fe_mul(fe_ld(X + half + q), tq), a.hinv));
 }
 int split_composition_full(hipStream_t st, const fe* X, uint64_t N, const fe* t_half, const fe& hinv, fe* H1f, fe* H2f) {
     SplitArgs a; a.hinv = hinv;
@@ -390,10 +378,10 @@ __global__ void __launch_bounds__(256) fold_eval_kernel(const fe* in, uint64_t i
     // lazily reduced sum: products in [0, 2p), eight of them on top of an accumulator below 2p stay below 18p < 2^256
     fe acc = fe_zero();
     for (uint32_t t = 0; t < T; ++t) {
-        acc = fe_add_raw(acc, fe_mul_lazy(sk_ld(src + (uint64_t)t * Mq + q), yp[p * T + t]));
+        acc = fe_add_raw(acc, fe_mul_lazy(fe_ld(src + (uint64_t)t * Mq + q), yp[p * T + t]));
         if ((t & 7u) == 7u) acc = fe_reduce_lazy_2p(acc);
     }
-    sk_st(out + ((uint64_t)v * points + p) * Mq + q, fe_canonical_lazy(acc));
+    fe_st(out + ((uint64_t)v * points + p) * Mq + q, fe_canonical_lazy(acc));
 }
 int fold_eval_level(hipStream_t st, const fe* in, uint64_t in_vec_stride, uint32_t in_points, uint64_t M, uint32_t l,
                     const fe* yp, uint32_t points, uint32_t vectors, fe* out) {
@@ -420,7 +408,7 @@ __global__ void __launch_bounds__(256) deep_kernel(const fe* __restrict__ lde, c
     for (int k = 0; k < MAXR; ++k) a[k] = fe_zero();
     // lazily reduced sums over the columns: products in [0, 2p), eight of them on top of an accumulator below 2p stay below 18p < 2^256
     for (uint32_t j = 0; j < C; ++j) {
-        fe t = sk_ld(lde + (uint64_t)j * col_stride + i);
+        fe t = fe_ld(lde + (uint64_t)j * col_stride + i);
 #pragma unroll
         for (int k = 0; k < MAXR; ++k)
             if ((uint32_t)k < R) {
@@ -430,12 +418,12 @@ __global__ void __launch_bounds__(256) deep_kernel(const fe* __restrict__ lde, c
     }
 #pragma unroll
     for (int k = 0; k < MAXR; ++k) a[k] = fe_canonical_lazy(a[k]);
-    fe hh = K->gamma_h1 * sk_ld(h1 + i) + K->gamma_h2 * sk_ld(h2 + i) - K->c_h;
-    fe r = hh * sk_ld(inv + (uint64_t)R * count + q);
+    fe hh = K->gamma_h1 * fe_ld(h1 + i) + K->gamma_h2 * fe_ld(h2 + i) - K->c_h;
+    fe r = hh * fe_ld(inv + (uint64_t)R * count + q);
 #pragma unroll
     for (int k = 0; k < MAXR; ++k)
-        if ((uint32_t)k < R) r = r + (a[k] - K->c_t[k]) * sk_ld(inv + (uint64_t)k * count + q);
-    sk_st(out + q, r);
+        if ((uint32_t)k < R) r = r + (a[k] - K->c_t[k]) * fe_ld(inv + (uint64_t)k * count + q);
+    fe_st(out + q, r);
 }
 int deep_composition(hipStream_t st, const fe* lde, const fe* h1, const fe* h2, uint64_t count, uint64_t col_stride, uint32_t shift,
                      const DeepConsts* consts_dev, const fe* gammas, const fe* inv, fe* out, LdeOrder order, uint32_t frame_rows) {
@@ -454,13 +442,13 @@ __global__ void __launch_bounds__(256) fri_fold_kernel(const fe* cur, fe* next, 
                                                        uint32_t shard_log, uint32_t shard_rank, const fe* c_dev) {
     uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= Mh) return;
-    if (c_dev) a.c = sk_ld(c_dev);   // zeta * half / offset left in device memory by the previous layer's root launch (merkle.h, FriChallenge)
-    fe x = sk_ld(cur + i), y = sk_ld(cur + Mh + i);
+    if (c_dev) a.c = fe_ld(c_dev);   // zeta * half / offset left in device memory by the previous layer's root launch (merkle.h, FriChallenge)
+    fe x = fe_ld(cur + i), y = fe_ld(cur + Mh + i);
     uint32_t Nm = (1u << logN) - 1;
     const uint32_t ig = ((uint32_t)i << shard_log) | shard_rank;
     uint32_t e = (0u - (ig << layer)) & Nm;  // w_M^-i = w_N^(-i 2^layer)
     fe w = root_pow(roots, e, logN);
-    sk_st(next + i, a.half * (x + y) + a.c * (w * (x - y)));
+    fe_st(next + i, a.half * (x + y) + a.c * (w * (x - y)));
 }
 // The fold and the leaf hash of the layer it produces in one launch (FriLayer::new, fri_commitment.rs:30-47: the leaf of a FRI tree
 // is Keccak256 of the element's canonical 32-byte big-endian encoding): the folded element never travels to HBM and back before it is
@@ -469,13 +457,13 @@ __global__ void __launch_bounds__(256) fri_fold_hash_kernel(const fe* cur, fe* n
                                                             const fe* c_dev, digest32* leaves_out) {
     uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= Mh) return;
-    if (c_dev) a.c = sk_ld(c_dev);
-    fe x = sk_ld(cur + i), y = sk_ld(cur + Mh + i);
+    if (c_dev) a.c = fe_ld(c_dev);
+    fe x = fe_ld(cur + i), y = fe_ld(cur + Mh + i);
     uint32_t Nm = (1u << logN) - 1;
     uint32_t e = (0u - ((uint32_t)i << layer)) & Nm;
     fe w = root_pow(roots, e, logN);
     const fe v = a.half * (x + y) + a.c * (w * (x - y));
-    sk_st(next + i, v);
+    fe_st(next + i, v);
     const fe raw = fe_from_mont(v);
     uint64_t s[25];
 #pragma unroll
@@ -544,12 +532,12 @@ __global__ void __launch_bounds__(128) gather_jobs_kernel(const GatherJob* jobs,
     const uint32_t r = t / jb.width, j = t % jb.width;
     const uint64_t at = idx[jb.idx_off + r];
     if (jb.kind == 0) {
-        sk_st(out + jb.out_off + t, sk_ld(static_cast<const fe*>(jb.base) + (uint64_t)j * jb.stride_or_leaves + at));
+        fe_st(out + jb.out_off + t, fe_ld(static_cast<const fe*>(jb.base) + (uint64_t)j * jb.stride_or_leaves + at));
     } else {
         uint64_t p = at + jb.stride_or_leaves - 1;
         for (uint32_t k = 0; k < j; ++k) p = (p - 1) >> 1;
         const uint64_t sib = (p & 1) ? p + 1 : p - 1;
-        sk_st(out + jb.out_off + t, sk_ld(static_cast<const fe*>(jb.base) + sib));
+        fe_st(out + jb.out_off + t, fe_ld(static_cast<const fe*>(jb.base) + sib));
     }
 }
 int gather_jobs(hipStream_t st, const GatherJob* jobs_dev, uint32_t njobs, uint32_t max_items, const uint64_t* idx_dev, fe* out) {
@@ -565,7 +553,7 @@ __global__ void __launch_bounds__(256) natural_to_coset_major_kernel(const fe* s
                                                                      uint32_t shard_log, uint32_t shard_rank) {
     uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= len) return;
-    sk_st(dst + (uint64_t)blockIdx.y * len + ord.at(i), sk_ld(src + (uint64_t)blockIdx.y * src_stride + ((i << shard_log) | shard_rank)));
+    fe_st(dst + (uint64_t)blockIdx.y * len + ord.at(i), fe_ld(src + (uint64_t)blockIdx.y * src_stride + ((i << shard_log) | shard_rank)));
 }
 int natural_to_coset_major(hipStream_t st, const fe* src, uint64_t src_stride, fe* dst, uint64_t len, uint32_t ncols, LdeOrder order,
                            uint32_t shard_log, uint32_t shard_rank) {
@@ -603,9 +591,9 @@ __global__ void __launch_bounds__(256) boundary_vanishing_kernel(fe* zb, uint64_
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= N) return;
     const fe x = fe_mul(root_pow(roots, shard_global_index((uint32_t)i, sm), logN), h);
-    fe p = fe_sub(x, sk_ld(points));
-    for (uint32_t g = 1; g < ndist; ++g) p = p * (x - sk_ld(points + g));
-    sk_st(zb + i, p);
+    fe p = fe_sub(x, fe_ld(points));
+    for (uint32_t g = 1; g < ndist; ++g) p = p * (x - fe_ld(points + g));
+    fe_st(zb + i, p);
 }
 int boundary_vanishing(hipStream_t st, fe* zb, uint64_t N, uint32_t logN, const fe* roots_N, const fe& h, const fe* points_dev, uint32_t ndist, ShardMap sm) {
     if (ndist == 0) return SP_E_INVALID_ARG;
@@ -614,83 +602,55 @@ int boundary_vanishing(hipStream_t st, fe* zb, uint64_t N, uint32_t logN, const 
     return SP_OK;
 }
 
-// CHECK = false: composition evaluations, point i = element e = i << stride_log of every LDE column (as cairo_composition);
-// CHECK = true: the transition constraints on the trace itself (natural-order columns of n rows): *flag |= 1 if one is non-zero on a
-// row it is enforced on (the boundary values: air_boundary_check_kernel).
-// PER: the program may read periodic columns (op 6): the exact check takes v[(i + offset) mod p] from the values, the composition
-// entry (coset c, (j + offset) mod p) of the column's table, j = iglob / b the trace row of the point - the GLOBAL index, so a
-// sharded context and the strided 2n-point evaluation read the entry of the point they stand on.
-template <bool CHECK, bool PER>
+// Composition evaluations of a program AIR: point i = element e = i << stride_log of every LDE column (as cairo_composition).
+// PER: the program may read periodic columns (op 6): entry (coset c, (j + offset) mod p) of the column's table, j = iglob / b the
+// trace row of the point - the GLOBAL index, so a sharded context and the strided 2n-point evaluation read the entry of the point
+// they stand on.
+template <bool PER>
 __global__ void __launch_bounds__(256) air_composition_kernel(const fe* __restrict__ cols, uint64_t count, uint64_t col_len, uint32_t stride_log,
                                                               uint32_t logN, uint32_t logb, const fe* __restrict__ roots,
                                                               const AirCompTables K, const AirProgram* __restrict__ Pg,
                                                               const fe* __restrict__ ex_roots, const fe* __restrict__ zbinv,
-                                                              fe* __restrict__ out, int* __restrict__ flag, uint32_t shard_log, uint32_t shard_rank) {
+                                                              fe* __restrict__ out, uint32_t shard_log, uint32_t shard_rank) {
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= count) return;
     const uint32_t b = 1u << logb, b_loc = b >> shard_log;
     const ShardMap sm{logb, shard_log, shard_rank};
-    const uint64_t e = CHECK ? i : (i << stride_log);   // local natural-order index; storage index = ord.at(.)
-    const LdeOrder ord{CHECK ? 0u : 1u, logb - shard_log, logN - logb};
-    const uint32_t iglob = CHECK ? 0u : shard_global_index((uint32_t)e, sm);
+    const uint64_t e = i << stride_log;   // local natural-order index; storage index = ord.at(.)
+    const LdeOrder ord{1u, logb - shard_log, logN - logb};
+    const uint32_t iglob = shard_global_index((uint32_t)e, sm);
     const uint32_t c = iglob & (b - 1);
     const uint32_t T = K.T, B = K.B;
-    const AirOpDev* __restrict__ ops = Pg->ops;
-    const fe* __restrict__ consts = Pg->consts;
-    fe v[AIR_MAX_LIVE];
     fe cons[AIR_MAX_TRANSITIONS];
     for (uint32_t k = 0; k < T; ++k) cons[k] = fe_zero();
-    const uint32_t n_ops = Pg->n_ops;
-    for (uint32_t t = 0; t < n_ops; ++t) {
-        const AirOpDev o = ops[t];
-        fe r = fe_zero();
-        if constexpr (PER) {
-            if (o.op == 6) {
-                const AirPeriodicCol pc = K.pcols[o.b];
-                const uint32_t pm = (1u << pc.logp) - 1u, ofs = Pg->offsets[o.a];
-                if (CHECK) r = sk_ld(K.pvals + pc.off + (((uint32_t)i + ofs) & pm));
-                else r = sk_ld(K.ptab + (pc.off << logb) + ((uint64_t)c << pc.logp) + (((iglob >> logb) + ofs) & pm));
-                v[o.dst] = r;
-                continue;
-            }
-        }
-        switch (o.op) {
-            case 0: {   // frame row = trace row + offset: LDE index + offset * blowup (frame.rs:40-59), same coset
-                const uint64_t row = (e + (uint64_t)Pg->offsets[o.a] * (CHECK ? 1u : b_loc)) & (col_len - 1);
-                r = sk_ld(cols + (uint64_t)o.b * col_len + ord.at(row));
-                break;
-            }
-            case 1: r = sk_ld(consts + o.a); break;
-            case 2: r = v[o.a] + v[o.b]; break;
-            case 3: r = v[o.a] - v[o.b]; break;
-            case 4: r = v[o.a] * v[o.b]; break;
-            default: cons[o.a] = v[o.b]; continue;
-        }
-        v[o.dst] = r;
-    }
-    if (CHECK) {
-        bool bad = false;
-        for (uint32_t k = 0; k < T; ++k)
-            if (i + Pg->ex_rows[k] < count && !fe_is_zero(cons[k])) bad = true;   // enforced on rows 0 .. n - 1 - exemptions
-        if (bad) atomicOr(flag, 1);
-        return;
-    }
+    air_run_program<PER>(
+        Pg->ops, Pg->n_ops, Pg->consts,
+        [&](uint32_t a, uint32_t col) {   // frame row = trace row + offset: LDE index + offset * blowup (frame.rs:40-59), same coset
+            const uint64_t row = (e + (uint64_t)Pg->offsets[a] * b_loc) & (col_len - 1);
+            return fe_ld(cols + (uint64_t)col * col_len + ord.at(row));
+        },
+        [&](uint32_t a, uint32_t col) {
+            const AirPeriodicCol pc = K.pcols[col];
+            const uint32_t pm = (1u << pc.logp) - 1u, ofs = Pg->offsets[a];
+            return fe_ld(K.ptab + (pc.off << logb) + ((uint64_t)c << pc.logp) + (((iglob >> logb) + ofs) & pm));
+        },
+        [&](uint32_t k, const fe& val) { cons[k] = val; });
     const fe x = root_pow(roots, iglob, logN) * K.h;
     fe exv[AIR_MAX_EXEMPT_KINDS];
     for (int q = 0; q < AIR_MAX_EXEMPT_KINDS; ++q) {
         fe p = fe_one();
-        for (uint32_t j = 0; j < Pg->ex_count[q]; ++j) p = p * (x - sk_ld(ex_roots + j));
+        for (uint32_t j = 0; j < Pg->ex_count[q]; ++j) p = p * (x - fe_ld(ex_roots + j));
         exv[q] = p;
     }
     const fe* __restrict__ coef = K.coef + (uint64_t)c * (T + B);
     fe acc = fe_zero();
     for (uint32_t k = 0; k < T; ++k) {
-        fe term = sk_ld(coef + k) * cons[k];
+        fe term = fe_ld(coef + k) * cons[k];
         const uint32_t ek = Pg->ex_kind[k];
         if (ek) term = term * exv[ek - 1];
         acc = acc + term;
     }
-    fe total = sk_ld(K.zerofier + c) * acc;
+    fe total = fe_ld(K.zerofier + c) * acc;
     if (K.ndist) {
         // sum_s S_s / (x - g^s) as A / P over the rows s seen so far: three products per row, one inverse (zbinv) per point
         const uint64_t at = ord.at(e);
@@ -699,40 +659,70 @@ __global__ void __launch_bounds__(256) air_composition_kernel(const fe* __restri
         for (uint32_t g = 0; g < K.ndist; ++g) {
             fe S = fe_zero();
             for (const uint32_t end = K.gend[g]; j < end; ++j)
-                S = S + sk_ld(coef + T + j) * (sk_ld(cols + (uint64_t)K.bcol[j] * col_len + at) - sk_ld(K.bvalue + j));
-            const fe d = x - sk_ld(K.gpoint + g);
+                S = S + fe_ld(coef + T + j) * (fe_ld(cols + (uint64_t)K.bcol[j] * col_len + at) - fe_ld(K.bvalue + j));
+            const fe d = x - fe_ld(K.gpoint + g);
             A = A * d + S * P;
             P = P * d;
         }
-        total = total + A * sk_ld(zbinv + i);
+        total = total + A * fe_ld(zbinv + i);
     }
-    sk_st(out + i, total);
+    fe_st(out + i, total);
 }
 
 int air_composition(hipStream_t st, const fe* lde, uint64_t count, uint64_t col_len, uint32_t stride_log, uint32_t logN, uint32_t logb,
                     const fe* roots_N, AirCompTables tabs, const AirProgram* prog_dev, const fe* ex_roots,
                     const fe* zbinv, fe* out, uint32_t shard_log, uint32_t shard_rank) {
     if ((1u << logb) > CAIRO_MAX_BLOWUP) { sp_set_error("composition: blowup factor > 128 unsupported"); return SP_E_UNSUPPORTED; }
-    if (tabs.pcols) hipLaunchKernelGGL((air_composition_kernel<false, true>), dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, lde, count, col_len, stride_log,
-                                       logN, logb, roots_N, tabs, prog_dev, ex_roots, zbinv, out, (int*)nullptr, shard_log, shard_rank);
-    else hipLaunchKernelGGL((air_composition_kernel<false, false>), dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, lde, count, col_len, stride_log,
-                            logN, logb, roots_N, tabs, prog_dev, ex_roots, zbinv, out, (int*)nullptr, shard_log, shard_rank);
+    const dim3 grid((unsigned)((count + 255) / 256));
+    if (tabs.pcols) hipLaunchKernelGGL((air_composition_kernel<true>), grid, dim3(256), 0, st, lde, count, col_len, stride_log, logN, logb, roots_N, tabs, prog_dev,
+                                       ex_roots, zbinv, out, shard_log, shard_rank);
+    else hipLaunchKernelGGL((air_composition_kernel<false>), grid, dim3(256), 0, st, lde, count, col_len, stride_log, logN, logb, roots_N, tabs, prog_dev,
+                            ex_roots, zbinv, out, shard_log, shard_rank);
     SP_HIP_CHECK(hipGetLastError());
     return SP_OK;
 }
 
+// The constraint program on trace row i, exactly: natural-order columns of n rows, frame rows wrap modulo n, op 6 reads the periodic
+// VALUES.  cons[k], k < K.T, receives the evaluations.  The trace check and the report share it.
+template <bool PER>
+__device__ __forceinline__ void air_eval_row(const fe* __restrict__ cols, uint64_t n, uint64_t i, const AirCompTables& K,
+                                             const AirProgram* __restrict__ Pg, fe* cons) {
+    for (uint32_t k = 0; k < K.T; ++k) cons[k] = fe_zero();
+    air_run_program<PER>(
+        Pg->ops, Pg->n_ops, Pg->consts,
+        [&](uint32_t a, uint32_t col) { return fe_ld(cols + (uint64_t)col * n + ((i + Pg->offsets[a]) & (n - 1))); },
+        [&](uint32_t a, uint32_t col) {
+            const AirPeriodicCol pc = K.pcols[col];
+            const uint32_t pm = (1u << pc.logp) - 1u;
+            return fe_ld(K.pvals + pc.off + (((uint32_t)i + Pg->offsets[a]) & pm));
+        },
+        [&](uint32_t k, const fe& val) { cons[k] = val; });
+}
+
+// one thread per trace row: *flag |= 1 if a transition constraint is non-zero on a row it is enforced on
+template <bool PER>
+__global__ void __launch_bounds__(256) air_check_kernel(const fe* __restrict__ trace, uint64_t n, const AirCompTables K, const AirProgram* __restrict__ Pg,
+                                                        int* __restrict__ flag) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    fe cons[AIR_MAX_TRANSITIONS];
+    air_eval_row<PER>(trace, n, i, K, Pg, cons);
+    bool bad = false;
+    for (uint32_t k = 0; k < K.T; ++k)
+        if (i + Pg->ex_rows[k] < n && !fe_is_zero(cons[k])) bad = true;   // enforced on rows 0 .. n - 1 - exemptions
+    if (bad) atomicOr(flag, 1);
+}
 // one thread per boundary constraint: trace[col][step] == value (validate_trace, debug.rs:88-104)
 __global__ void __launch_bounds__(256) air_boundary_check_kernel(const fe* __restrict__ trace, uint64_t n, const AirCompTables K, int* __restrict__ flag) {
     const uint32_t j = blockIdx.x * 256 + threadIdx.x;
     if (j >= K.B) return;
-    if (!fe_eq(sk_ld(trace + (uint64_t)K.bcol[j] * n + K.bstep[j]), sk_ld(K.bvalue + j))) atomicOr(flag, 1);
+    if (!fe_eq(fe_ld(trace + (uint64_t)K.bcol[j] * n + K.bstep[j]), fe_ld(K.bvalue + j))) atomicOr(flag, 1);
 }
 
 int air_trace_check(hipStream_t st, const fe* trace, uint64_t n, AirCompTables tabs, const AirProgram* prog_dev, int* flag_dev) {
-    if (tabs.pcols) hipLaunchKernelGGL((air_composition_kernel<true, true>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, trace, n, n, 0u, 0u, 0u,
-                                       (const fe*)nullptr, tabs, prog_dev, (const fe*)nullptr, (const fe*)nullptr, (fe*)nullptr, flag_dev, 0u, 0u);
-    else hipLaunchKernelGGL((air_composition_kernel<true, false>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, trace, n, n, 0u, 0u, 0u,
-                            (const fe*)nullptr, tabs, prog_dev, (const fe*)nullptr, (const fe*)nullptr, (fe*)nullptr, flag_dev, 0u, 0u);
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (tabs.pcols) hipLaunchKernelGGL((air_check_kernel<true>), grid, dim3(256), 0, st, trace, n, tabs, prog_dev, flag_dev);
+    else hipLaunchKernelGGL((air_check_kernel<false>), grid, dim3(256), 0, st, trace, n, tabs, prog_dev, flag_dev);
     SP_HIP_CHECK(hipGetLastError());
     if (tabs.B) {
         hipLaunchKernelGGL(air_boundary_check_kernel, dim3((tabs.B + 255) / 256), dim3(256), 0, st, trace, n, tabs, flag_dev);
@@ -742,39 +732,6 @@ int air_trace_check(hipStream_t st, const fe* trace, uint64_t n, AirCompTables t
 }
 
 // ---------------------------------------------------------------------------------------------- program AIRs: the report
-// The constraint program on trace row i, as air_composition_kernel<true, PER> runs it: natural-order columns of n rows, frame rows wrap
-// modulo n, op 6 reads the periodic VALUES.  cons[k], k < K.T, receives the evaluations.
-template <bool PER>
-__device__ __forceinline__ void air_eval_row(const fe* __restrict__ cols, uint64_t n, uint64_t i, const AirCompTables& K,
-                                             const AirProgram* __restrict__ Pg, fe* cons) {
-    const AirOpDev* __restrict__ ops = Pg->ops;
-    const fe* __restrict__ consts = Pg->consts;
-    fe v[AIR_MAX_LIVE];
-    for (uint32_t k = 0; k < K.T; ++k) cons[k] = fe_zero();
-    const uint32_t n_ops = Pg->n_ops;
-    for (uint32_t t = 0; t < n_ops; ++t) {
-        const AirOpDev o = ops[t];
-        fe r = fe_zero();
-        if constexpr (PER) {
-            if (o.op == 6) {
-                const AirPeriodicCol pc = K.pcols[o.b];
-                const uint32_t pm = (1u << pc.logp) - 1u;
-                v[o.dst] = sk_ld(K.pvals + pc.off + (((uint32_t)i + Pg->offsets[o.a]) & pm));
-                continue;
-            }
-        }
-        switch (o.op) {
-            case 0: r = sk_ld(cols + (uint64_t)o.b * n + ((i + Pg->offsets[o.a]) & (n - 1))); break;
-            case 1: r = sk_ld(consts + o.a); break;
-            case 2: r = v[o.a] + v[o.b]; break;
-            case 3: r = v[o.a] - v[o.b]; break;
-            case 4: r = v[o.a] * v[o.b]; break;
-            default: cons[o.a] = v[o.b]; continue;
-        }
-        v[o.dst] = r;
-    }
-}
-
 // One lane per trace row.  The lanes of the last block beyond row n - 1 run no program and never vote, but stay for the ballots.
 template <bool PER>
 __global__ void __launch_bounds__(256) air_report_kernel(const fe* __restrict__ cols, uint64_t n, const AirCompTables K,
@@ -807,16 +764,16 @@ __global__ void __launch_bounds__(64) air_report_value_kernel(const fe* __restri
     if (row >= n) return;
     fe cons[AIR_MAX_TRANSITIONS];
     air_eval_row<PER>(cols, n, row, K, Pg, cons);
-    sk_st(R.value + k, cons[k]);
+    fe_st(R.value + k, cons[k]);
 }
 
 // One lane per boundary constraint, as air_boundary_check_kernel: the cell, and whether it is the value.
 __global__ void __launch_bounds__(256) air_boundary_report_kernel(const fe* __restrict__ trace, uint64_t n, const AirCompTables K, const AirReport R) {
     const uint32_t j = blockIdx.x * 256 + threadIdx.x;
     if (j >= K.B) return;
-    const fe cell = sk_ld(trace + (uint64_t)K.bcol[j] * n + K.bstep[j]);
-    sk_st(R.bcell + j, cell);
-    R.bbad[j] = fe_eq(cell, sk_ld(K.bvalue + j)) ? 0u : 1u;
+    const fe cell = fe_ld(trace + (uint64_t)K.bcol[j] * n + K.bstep[j]);
+    fe_st(R.bcell + j, cell);
+    R.bbad[j] = fe_eq(cell, fe_ld(K.bvalue + j)) ? 0u : 1u;
 }
 
 int air_trace_report(hipStream_t st, const fe* trace, uint64_t n, AirCompTables tabs, const AirProgram* prog_dev, AirReport report) {
@@ -847,8 +804,8 @@ __global__ void __launch_bounds__(256) periodic_coeffs_kernel(const fe* __restri
     const uint32_t p = 1u << logp, m = t & (p - 1);
     const fe* __restrict__ v = vals + (t - m);
     fe acc = fe_zero();
-    for (uint32_t j = 0; j < p; ++j) acc = acc + sk_ld(v + j) * a.winv[(j * m) & (p - 1)];
-    sk_st(coef + t, acc * a.pinv);
+    for (uint32_t j = 0; j < p; ++j) acc = acc + fe_ld(v + j) * a.winv[(j * m) & (p - 1)];
+    fe_st(coef + t, acc * a.pinv);
 }
 // tab[v][c][j] = q_v(hq w_(p b)^(j b + c))
 __global__ void __launch_bounds__(256) periodic_horner_kernel(const fe* __restrict__ coef, fe* __restrict__ tab, uint32_t total, uint32_t logp, uint32_t logb,
@@ -858,9 +815,9 @@ __global__ void __launch_bounds__(256) periodic_horner_kernel(const fe* __restri
     const uint32_t p = 1u << logp, j = t & (p - 1), c = (t >> logp) & ((1u << logb) - 1), col = t >> (logp + logb);
     const fe x = root_pow(roots_pb, (j << logb) + c, logp + logb) * hq;
     const fe* __restrict__ q = coef + ((uint64_t)col << logp);
-    fe acc = sk_ld(q + p - 1);
-    for (uint32_t m = p - 1; m-- > 0;) acc = acc * x + sk_ld(q + m);
-    sk_st(tab + t, acc);
+    fe acc = fe_ld(q + p - 1);
+    for (uint32_t m = p - 1; m-- > 0;) acc = acc * x + fe_ld(q + m);
+    fe_st(tab + t, acc);
 }
 int air_periodic_table_direct(hipStream_t st, const fe* vals, fe* coef, fe* tab, uint32_t cnt, uint32_t logp, uint32_t logb, const fe& hq,
                               const fe* roots_pb) {

@@ -6,26 +6,13 @@ namespace sp {
 
 namespace {
 
-__device__ __forceinline__ fe tk_ld(const fe* p) {
-    const uint4* q = reinterpret_cast<const uint4*>(p);
-    uint4 lo = q[0], hi = q[1];
-    fe r;
-    r.v[0] = lo.x; r.v[1] = lo.y; r.v[2] = lo.z; r.v[3] = lo.w;
-    r.v[4] = hi.x; r.v[5] = hi.y; r.v[6] = hi.z; r.v[7] = hi.w;
-    return r;
-}
-__device__ __forceinline__ void tk_st(fe* p, const fe& a) {
-    uint4* q = reinterpret_cast<uint4*>(p);
-    q[0] = make_uint4(a.v[0], a.v[1], a.v[2], a.v[3]);
-    q[1] = make_uint4(a.v[4], a.v[5], a.v[6], a.v[7]);
-}
 __device__ __forceinline__ uint64_t tk_low64(const fe& mont) {
     const fe r = fe_from_mont(mont);
     return (uint64_t)r.v[0] | ((uint64_t)r.v[1] << 32);
 }
 __device__ __forceinline__ fe tk_cell(const MainTraceArgs& a, uint64_t addr, int* flag) {
     if (addr >= a.cells) { atomicExch(flag, 2); return fe_zero(); }
-    return tk_ld(a.mem + addr);
+    return fe_ld(a.mem + addr);
 }
 
 constexpr int TK_THREADS = 256;
@@ -53,8 +40,8 @@ __global__ void __launch_bounds__(TK_THREADS) step_rows_kernel(MainTraceArgs a, 
     fe* T = a.trace + i;
     const uint64_t n = a.n;
 #pragma unroll
-    for (int k = 0; k < 15; ++k) tk_st(T + (uint64_t)k * n, ((f >> k) & 1) ? one : zero);
-    tk_st(T + 15 * n, zero);
+    for (int k = 0; k < 15; ++k) fe_st(T + (uint64_t)k * n, ((f >> k) & 1) ? one : zero);
+    fe_st(T + 15 * n, zero);
     fe res;
     bool deferred = false;
     if (pc_update == 4) {
@@ -63,29 +50,29 @@ __global__ void __launch_bounds__(TK_THREADS) step_rows_kernel(MainTraceArgs a, 
     } else {
         res = res_logic == 0 ? op1 : res_logic == 1 ? fe_add(op0, op1) : fe_mul(op0, op1);
     }
-    tk_st(inv + i, deferred ? dst : one);
+    fe_st(inv + i, deferred ? dst : one);
     deferred_mask[i] = deferred ? 1 : 0;
     if (opcode == 1) { op0 = fe_from_u64(pc + (op1_src == 1 ? 2 : 1)); dst = fe_from_u64(fp); }
     else if (opcode == 4) res = dst;
-    tk_st(T + 16 * n, res);
-    tk_st(T + 17 * n, fe_from_u64(ap)); tk_st(T + 18 * n, fe_from_u64(fp)); tk_st(T + 19 * n, fe_from_u64(pc));
-    tk_st(T + 20 * n, fe_from_u64(dst_addr)); tk_st(T + 21 * n, fe_from_u64(op0_addr)); tk_st(T + 22 * n, fe_from_u64(op1_addr));
-    tk_st(T + 23 * n, inst); tk_st(T + 24 * n, dst); tk_st(T + 25 * n, op0); tk_st(T + 26 * n, op1);
-    tk_st(T + 27 * n, fe_from_u64(off_dst)); tk_st(T + 28 * n, fe_from_u64(off_op0)); tk_st(T + 29 * n, fe_from_u64(off_op1));
+    fe_st(T + 16 * n, res);
+    fe_st(T + 17 * n, fe_from_u64(ap)); fe_st(T + 18 * n, fe_from_u64(fp)); fe_st(T + 19 * n, fe_from_u64(pc));
+    fe_st(T + 20 * n, fe_from_u64(dst_addr)); fe_st(T + 21 * n, fe_from_u64(op0_addr)); fe_st(T + 22 * n, fe_from_u64(op1_addr));
+    fe_st(T + 23 * n, inst); fe_st(T + 24 * n, dst); fe_st(T + 25 * n, op0); fe_st(T + 26 * n, op1);
+    fe_st(T + 27 * n, fe_from_u64(off_dst)); fe_st(T + 28 * n, fe_from_u64(off_op0)); fe_st(T + 29 * n, fe_from_u64(off_op1));
     const fe t0 = ((f >> 9) & 1) ? dst : zero;
-    tk_st(T + 30 * n, t0);
-    tk_st(T + 31 * n, deferred ? zero : fe_mul(t0, res));
-    tk_st(T + 32 * n, fe_mul(op0, op1));
-    tk_st(T + 33 * n, (i + 1 == a.steps) ? zero : one);
-    for (uint32_t c = 34; c < a.cols; ++c) tk_st(T + (uint64_t)c * n, zero);
+    fe_st(T + 30 * n, t0);
+    fe_st(T + 31 * n, deferred ? zero : fe_mul(t0, res));
+    fe_st(T + 32 * n, fe_mul(op0, op1));
+    fe_st(T + 33 * n, (i + 1 == a.steps) ? zero : one);
+    for (uint32_t c = 34; c < a.cols; ++c) fe_st(T + (uint64_t)c * n, zero);
 }
 
 __global__ void __launch_bounds__(TK_THREADS) jnz_fix_kernel(MainTraceArgs a, const fe* inv, const uint8_t* deferred_mask) {
     const uint64_t i = (uint64_t)blockIdx.x * TK_THREADS + threadIdx.x;
     if (i >= a.steps || !deferred_mask[i]) return;
-    const fe r = tk_ld(inv + i);
-    tk_st(a.trace + 16 * a.n + i, r);
-    tk_st(a.trace + 31 * a.n + i, fe_mul(tk_ld(a.trace + 30 * a.n + i), r));
+    const fe r = fe_ld(inv + i);
+    fe_st(a.trace + 16 * a.n + i, r);
+    fe_st(a.trace + 31 * a.n + i, fe_mul(fe_ld(a.trace + 30 * a.n + i), r));
 }
 
 // add_rc_builtin_columns (execution_trace.rs:358-379, :604-624): the eight 16-bit limbs of the value, least significant first, and the value
@@ -95,8 +82,8 @@ __global__ void __launch_bounds__(TK_THREADS) rc_builtin_kernel(MainTraceArgs a,
     const fe v = tk_cell(a, a.rc_start + k, flag);
     const fe raw = fe_from_mont(v);
 #pragma unroll
-    for (int c = 0; c < 8; ++c) tk_st(a.trace + (uint64_t)(34 + c) * a.n + k, fe_from_u64((raw.v[c / 2] >> (16 * (c & 1))) & 0xffff));
-    tk_st(a.trace + 42ull * a.n + k, v);
+    for (int c = 0; c < 8; ++c) fe_st(a.trace + (uint64_t)(34 + c) * a.n + k, fe_from_u64((raw.v[c / 2] >> (16 * (c & 1))) & 0xffff));
+    fe_st(a.trace + 42ull * a.n + k, v);
 }
 
 // The rows behind the steps: fill_rc_holes, fill_memory_holes, add_pub_memory_dummy_accesses + pad_with_last_row.  Every row is a
@@ -114,7 +101,7 @@ __global__ void __launch_bounds__(TK_THREADS) tail_rows_kernel(MainTraceArgs a) 
         } else {
             // row A, column c
             if (rc_rows) v = (c >= 27 && c <= 29) ? fe_from_u64(a.missing[3 * (a.r_holes - 1 - a.r_rc) + (c - 27)]) : zero;
-            else v = tk_ld(a.trace + (uint64_t)c * a.n + (a.steps - 1));
+            else v = fe_ld(a.trace + (uint64_t)c * a.n + (a.steps - 1));
             // a memory-hole row: A with four unused addresses; beyond them: row r_dummy - 1 with the memory columns zeroed
             const uint64_t hr = r < a.r_dummy ? r : (a.r_dummy > a.r_holes ? a.r_dummy - 1 : ~0ull);
             if (hr != ~0ull && c >= 19 && c <= 22) {
@@ -123,7 +110,7 @@ __global__ void __launch_bounds__(TK_THREADS) tail_rows_kernel(MainTraceArgs a) 
             }
             if (r >= a.r_dummy && c >= 19 && c <= 26) v = zero;
         }
-        tk_st(a.trace + (uint64_t)c * a.n + r, v);
+        fe_st(a.trace + (uint64_t)c * a.n + r, v);
     }
 }
 

@@ -239,3 +239,23 @@ def test_agreement_with_prover_and_verifier(hip_ctx, oracle):
         found2 = hip_ctx.air_check_trace(desc, trace, None, [])  # without options: the smallest commitments, the same report
         assert found2 == found
         assert hip_ctx.air_prove(desc, trace, opt) == before
+
+
+# ---- 8. the flag-only check and the report share one row evaluation: the edges of the launch -------------------------------------
+@pytest.mark.parametrize("n,cell_rows", [(8, (6, 0)), (512, (510, 0, 256))], ids=["less than one wave", "two blocks"])
+def test_flag_and_report_agree_at_the_edges_of_the_launch(hip_ctx, n, cell_rows):
+    """periodic_airs.linear (periods 2 and 8: at n = 8 every period wraps inside the one partial wave): a clean trace takes the 2n-point
+    path and reports nothing; one cell of column 0 changed on the last enforced row, on row 0, on the first row of the second block
+    makes the prover's flag leave that path and the report name constraint 0 on the rows the model names."""
+    b, rows = periodic_airs.linear(n, periodic_airs.keys(51, 2), periodic_airs.keys(52, 8))
+    desc, keep = b.build()
+    hip_ctx.air_prove(desc, air.ints_to_bytes(rows), OPT)
+    assert hip_ctx.last_proof_info()["composition_path"] == 1
+    assert same(hip_ctx, b, rows) == []
+    for row in cell_rows:
+        bad = X.changed(rows, (row, 0, 1))
+        hip_ctx.air_prove(desc, air.ints_to_bytes(bad), OPT)
+        assert hip_ctx.last_proof_info()["composition_path"] != 1, row
+        got = same(hip_ctx, b, bad)                                  # rows, first_row, last_row (and value) equal to the model's
+        hit = [v for v in got if v.kind == 0 and v.index == 0]      # a' - a - K0 breaks on the row of the cell and on the one before it
+        assert [(v.first_row, v.last_row) for v in hit] == [(max(row - 1, 0), row)], row

@@ -2,11 +2,11 @@
 (256 main columns, 2^18 rows, 64 transition constraints, 512 boundary constraints on 64 rows).  --trace clean: the satisfying trace;
 --trace wrong: every column counts up by one too much, so every constraint is non-zero on every enforced row and every wave of the
 report kernel issues its three atomics for each of the 64 constraints.  One proof (whose round 2 runs the flag-only check
-air_composition_kernel<true, false> on the same trace), then --reps reports.  Meant to run under the profiler:
+air_check_kernel<false> on the same trace), then --reps reports.  Meant to run under the profiler:
 
     rocprofv3 --kernel-trace --stats -d OUT -o p -- python tools/air_check_trace_bench.py --trace clean
     rocprofv3 --kernel-trace --stats -d OUT2 -o p -- python tools/air_check_trace_bench.py --trace wrong
-    python tools/rocprof_summary.py OUT/*/p_results.db        (the air_report_kernel and air_composition_kernel<true, ..> rows)
+    python tools/rocprof_summary.py OUT/*/p_results.db        (the air_report_kernel and air_check_kernel rows)
 """
 import argparse
 import json
