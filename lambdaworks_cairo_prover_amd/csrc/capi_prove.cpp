@@ -307,13 +307,7 @@ int sp_cairo_run_main_trace_dev(sp_ctx* c, const sp_cairo_run* run, int enc, uin
     uint8_t* stage = static_cast<uint8_t*>(img.p);
     SP_HIP_CHECK(hipMemcpyAsync(stage, image->current(), image->bytes, hipMemcpyHostToDevice, c->stream));
     SP_HIP_CHECK(hipMemsetAsync(flag.p, 0, sizeof(int), c->stream));
-    MainTraceArgs a{};
-    a.regs = reinterpret_cast<const uint64_t*>(stage + image->off_regs);
-    a.mem = reinterpret_cast<const fe*>(stage + image->off_mem);
-    a.missing = reinterpret_cast<const uint16_t*>(stage + image->off_missing);
-    a.holes = reinterpret_cast<const uint64_t*>(stage + image->off_holes);
-    a.steps = P.steps; a.cells = P.mem_cells; a.n = P.n; a.r_rc = P.r_rc; a.r_holes = P.r_holes; a.r_dummy = P.r_dummy; a.n_holes = P.holes.size();
-    a.rc_start = P.rc_start; a.rc_count = P.rc_count; a.cols = (uint32_t)P.cols; a.trace = static_cast<fe*>(table.p);
+    const MainTraceArgs a = main_trace_args(P, *image, stage, static_cast<fe*>(table.p));
     SP_TRY(cairo_main_trace_device(c->stream, a, stage + image->bytes, static_cast<int*>(flag.p)));
     SP_TRY(encode_elements(c->stream, enc, static_cast<const fe*>(table.p), (uint64_t)P.n * P.cols, static_cast<uint8_t*>(enc_dev.p)));
     std::vector<uint8_t> cols_host(table_bytes);

@@ -127,7 +127,7 @@ class StarkProver : public sp_deletable {
     // Several ranks: with a stream-ordered transport the sharded layers are part of the chain (their digest exchange and root
     // all-gather sit on the compute stream); with blocking hooks it is available from the first layer every rank holds whole (the
     // sharded layers in front of it go through fri_fold_commit, one exchange each).  The caller passes the zeta of the layer to fold next.
-    bool fri_chain_available() const { return stage_ == 6 && logn_ >= 2 && fri_layer_ >= 1 && (!fri_sharded(fri_layer_ - 1) || comm_async()); }
+    bool fri_chain_available() const { return stage_ == Stage::FriRunning && logn_ >= 2 && fri_layer_ >= 1 && (!fri_sharded(fri_layer_ - 1) || comm_async()); }
     int fri_commit_chain(const fe& zeta0, const uint8_t state32[32], std::vector<std::array<uint8_t, 32>>& roots_out, fe* last_value);
     int grind(const uint8_t challenge[32], uint8_t factor, uint64_t* nonce_out);
     // values_canonical_be: the opened field elements come back as their canonical 32-byte big-endian encodings (the proof's wire format,
@@ -236,13 +236,33 @@ class StarkProver : public sp_deletable {
         const uint64_t ood = C_ <= 64 ? 0 : 2ull * C_ * AIR_MAX_OFFSETS * std::max<uint64_t>(1, n_ >> 8) + 8ull * AIR_MAX_OFFSETS * 256;
         return std::max<uint64_t>(std::max<uint64_t>(std::max<uint64_t>(Nl_ * 7, 4 * n_), 8192), ood);
     }
+    // ---- round 2 (prover_round2.cpp)
+    // the 2n-point paths of round 2 by shape: this rank holds the cosets c0 = rank and c0 + b/2 (always on one GPU), or one coset per rank (G = b)
+    bool sub_coset_shape() const { return logb_ >= logG_ + 1; }
+    bool pair_shape() const { return G_ > 1 && logb_ == logG_ && d_post_comp0_; }
+    int fill_cairo_consts(CompositionConsts& K, const fe rap[3], const std::vector<BoundaryConstraint>& bcs, uint32_t n_transitions);
     struct AirProgramHost { AirProgram prog; std::vector<AirOpDev> dops; std::vector<AirPeriodicCol> pcols; uint64_t S = 0; uint32_t max_ex = 0; };   // S: the periods, summed
     int build_air_program(const AirDescHost& air, size_t n_rap, const AirPeriodicHost* periodic, AirProgramHost& out);
     int build_air_block(const AirDescHost& air, const std::vector<fe>& rap, const AirPeriodicHost* periodic, AirProgramHost& ph,
                         const std::vector<uint32_t>& order, std::initializer_list<std::pair<size_t, size_t*>> extra, AirCompTables& tabs,
                         const AirProgram*& prog_dev);
-    int composition_core(const CompositionConsts* K, const std::vector<fe>& points, const AirProgram* prog_dev, const AirCompTables* air_tabs,
-                         const fe* ex_roots_dev, bool allow_sub_coset, uint8_t root_out[32]);
+    struct Round2Air;   // what composition_core is given; the two members below it are where Cairo and a program AIR differ
+    int round2_evaluate(const Round2Air& air, uint64_t count, uint32_t stride_log, const fe* binv, fe* out);
+    int round2_boundary_inverses(const Round2Air& air, fe* binv, fe* inv_scratch, uint64_t count, uint32_t logM, const fe* roots_m, const fe& hp, ShardMap sm);
+    int composition_core(Round2Air air, uint8_t root_out[32]);
+    int composition_sub_coset(const Round2Air& air, int* flag, int* flag_pref);
+    int composition_pair(const Round2Air& air, int* flag);
+    int composition_whole_domain(const Round2Air& air);
+    int split_2n_and_extend(const fe* post);
+    CompositionConsts* d_comp_consts_ = nullptr;
+    std::unique_ptr<CompositionConsts> h_comp_chk_;    // host copy of od_.comp_consts_chk (stays put until the upload has happened)
+    bool check_pending_ = false;
+    std::vector<uint8_t> h_air_up_;                    // host side of the upload into od_.air_buf
+    std::vector<uint8_t> h_report_;                    // host copy of od_.air_report
+    bool h_full_ = false;     // the composition polynomial of this proof has degree >= 2n: its halves are in od_.hfull
+    fe* d_post_comp_ = nullptr;                        // shape-only post-factor table of the 2n-point inverse transform (setup)
+    fe* d_post_comp0_ = nullptr;                       // the same for c0 = 0 (one coset per rank)
+    std::vector<fe> bpre_points_; bool bpre_valid_ = false;   // od_.bpre holds the boundary inverses for these points (prefetch_boundary_inverses)
 
     sp_ctx* c_;
     ProofOptionsHost opt_{};
@@ -306,6 +326,7 @@ class StarkProver : public sp_deletable {
     // recv[s] = the block rank s addressed to this role: send = [G][bytes], recv = [G][bytes]
     int exchange_blocks(const void* send_dev, void* recv_dev, uint64_t bytes_per_block, bool stream_ordered = false);
     ShardMap shard_map() const { return ShardMap{logb_, logG_, rank_}; }
+    fe rank_coset_offset() const { return fe_mul(h_, fe_pow_u64(host_primitive_root((int)logN_), rank_)); }   // h w_N^rank: offset of this rank's first coset
     bool has_rc_ = false;
     fe h_, hinv_, g_;                       // coset offset, its inverse, trace generator
     std::vector<void*> allocs_;             // buffers outside the arena (grown on demand, or when the arena could not be had)
@@ -330,11 +351,7 @@ class StarkProver : public sp_deletable {
     uint32_t fri_layer_ = 0;                // number of committed layers so far
     fe fri_offset_, fri_offset_inv_;        // h^(2^layer) and its inverse
     fe half_, binv_;                        // 1/2, 1/blowup
-    CompositionConsts* d_comp_consts_ = nullptr;
-    std::unique_ptr<CompositionConsts> h_comp_chk_;    // host copy of od_.comp_consts_chk (stays put until the upload has happened)
-    bool check_pending_ = false;
-    std::vector<uint8_t> h_air_up_, h_auxp_up_;        // host sides of the uploads into od_.air_buf and od_.auxp_buf
-    std::vector<uint8_t> h_report_;                    // host copy of od_.air_report
+    std::vector<uint8_t> h_auxp_up_;                   // host side of the upload into od_.auxp_buf
     DeepConsts* d_deep_consts_ = nullptr;
     fe* d_deep_gammas_ = nullptr;                      // [AIR_MAX_OFFSETS][C], behind the DeepConsts in the same allocation
     static size_t deep_gammas_at() { return (sizeof(DeepConsts) + 255) & ~size_t(255); }
@@ -357,7 +374,6 @@ class StarkProver : public sp_deletable {
     int* side_flag(SideFlag f) { return od_.side_flags.p + f; }
     int prefetch_deep_inverses();           // from ood(): z_ is set
     bool deep_pref_ = false;
-    std::vector<fe> bpre_points_; bool bpre_valid_ = false;   // od_.bpre holds the inverses for these points
     // the challenge-free part of the Cairo auxiliary trace (sorts) beside round 1's transforms and hashing
     const PublicInputs* presort_pub_ = nullptr; bool presorted_ = false;
     hipEvent_t ev_side_presort_ = nullptr;
@@ -375,13 +391,15 @@ class StarkProver : public sp_deletable {
   private:
     fe* d_memcols_ = nullptr;               // natural-order main-trace columns 19..29 kept for the auxiliary trace
     AuxWorkspace auxws_{}; uint64_t auxws_pm_ = 0;
-    bool h_full_ = false;     // the composition polynomial of this proof has degree >= 2n: its halves are in od_.hfull
-    fe* d_post_comp_ = nullptr; fe* d_post_deep_ = nullptr;   // shape-only post-factor tables (setup)
-    fe* d_post_comp0_ = nullptr;                               // the same for c0 = 0 (one coset per rank)
+    fe* d_post_deep_ = nullptr;             // shape-only post-factor table of round 4 (setup)
     fe z_; fe h1_z2_, h2_z2_;
     std::vector<fe> trace_ood_;
     std::vector<uint32_t> offsets_{0, 1};   // transition offsets of the AIR (frame rows); Cairo: {0, 1}
-    int stage_ = 0;  // 0 new, 1 setup, 2 main committed, 3 aux committed, 4 composition, 5 ood, 6 fri running, 7 fri done
+    enum class Stage { New, Setup, MainCommitted, AuxCommitted, Composed, OodDone, FriRunning, FriDone };
+    Stage stage_ = Stage::New;
+    // round 1 is over: both segments, or the main segment of an AIR without auxiliary columns
+    bool segments_committed() const { return stage_ == Stage::AuxCommitted || (stage_ == Stage::MainCommitted && Ca_ == 0); }
+    void segment_committed(int segment) { stage_ = segment == 0 ? Stage::MainCommitted : Stage::AuxCommitted; }
 };
 
 // The prover of a context with the host-side buffers of the round-level ABI: one object whichever entry point created it, so a

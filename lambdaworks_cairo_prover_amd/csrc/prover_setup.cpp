@@ -71,7 +71,7 @@ int StarkProver::setup(uint64_t n, uint32_t main_cols, uint32_t aux_cols, bool h
     const int rc = setup_impl(n, main_cols, aux_cols, has_rc, opt);
     if (rc != SP_OK) {   // a failed (re)shaping leaves nothing behind: the next setup() of the same shape starts from scratch
         free_all();
-        n_ = 0; ready_ = false; stage_ = 0;
+        n_ = 0; ready_ = false; stage_ = Stage::New;
     }
     return rc;
 }
@@ -90,12 +90,12 @@ int StarkProver::setup_impl(uint64_t n, uint32_t main_cols, uint32_t aux_cols, b
     if (ready_ && (arena_ || !allocs_.empty()) && n == n_ && main_cols == Cm_ && aux_cols == Ca_ && has_rc == has_rc_ && opt.blowup_factor == opt_.blowup_factor &&
         opt.coset_offset == opt_.coset_offset && (uint32_t)c_->world == world_ && (uint32_t)c_->rank == wrank_ && c_->opt_shard_interpolation == shard_mode_) {
         // same shape as the previous proof on this context: keep every device buffer and table
-        opt_ = opt; stage_ = 1; fri_layer_ = 0;
+        opt_ = opt; stage_ = Stage::Setup; fri_layer_ = 0;
         reset_proof_flags();
         return SP_OK;
     }
     free_all();
-    ready_ = false; stage_ = 0;
+    ready_ = false; stage_ = Stage::New;
     opt_ = opt; n_ = n; logn_ = (uint32_t)k; logb_ = (uint32_t)lb; logN_ = logn_ + logb_; N_ = n << lb;
     Cm_ = main_cols; Ca_ = aux_cols; C_ = main_cols + aux_cols; has_rc_ = has_rc;
     world_ = (uint32_t)c_->world; wrank_ = (uint32_t)c_->rank; shard_mode_ = c_->opt_shard_interpolation;
@@ -226,7 +226,7 @@ int StarkProver::setup_impl(uint64_t n, uint32_t main_cols, uint32_t aux_cols, b
     }
     SP_TIMEPOINT("  setup: tables");
     ready_ = true;
-    stage_ = 1;
+    stage_ = Stage::Setup;
     return SP_OK;
 }
 
@@ -246,7 +246,7 @@ int StarkProver::warm_plumbing(bool host_rows) {
 // data-dependent control flow and accept any 256-bit operand; the hash kernels convert and absorb whatever they read) - the
 // size-specific kernel variants take their first launch here, and the device reaches its clocks before the trace exists.
 int StarkProver::warm_round1() {
-    if (!ready_ || stage_ != 1) return SP_E_STATE;
+    if (!ready_ || stage_ != Stage::Setup) return SP_E_STATE;
     SP_HIP_CHECK(hipSetDevice(c_->device));
     SP_HIP_CHECK(hipMemsetAsync(d_trace_, 0, sizeof(fe) * n_ * C_, c_->stream));
     // Column slice by column slice, with a look at sp_prewarm_cancel's flag between slices: a caller whose trace is ready does not wait

@@ -145,7 +145,7 @@ int StarkProver::commit_trace_columns(int segment, const uint8_t* cols_host, uin
     if (sharded_interp) rc = commit_segment_resident(segment, cols, root_out);
     else {
         rc = commit_columns(lde, Nl_, cols, segment == 0 ? tree_main_ : tree_aux_, root_out);
-        if (rc == SP_OK) stage_ = segment == 0 ? 2 : 3;
+        if (rc == SP_OK) segment_committed(segment);
     }
     if (rc == SP_OK) {
         SP_TRY(finish_upload_stats(groups, (uint64_t)cols * n_ * 32, 0.0, host_ms, pinned ? 2 : 3));
@@ -636,7 +636,7 @@ int StarkProver::commit_trace_pipelined(int segment, const uint8_t* rows_host, u
     SP_TIMEPOINT("  aux presort queued (+ its workspace)");
     SP_TRY(commit_columns(lde, Nl_, cols, segment == 0 ? tree_main_ : tree_aux_, root_out));
     SP_TIMEPOINT("  leaf hashing + tree");
-    stage_ = segment == 0 ? 2 : 3;
+    segment_committed(segment);
     return finish_upload_stats(groups, dma_bytes, gather_ms, host_ms, 1);
 }
 

@@ -106,6 +106,28 @@ def test_degree_one_constraints_with_degree_bound_factor_one(hip_ctx, options):
     assert not api.air_verify(proof, desc, opt)
 
 
+def test_valid_trace_on_the_whole_domain_gives_the_oracle_bytes(hip_ctx, oracle):
+    """composition_path 2, without periodic columns: x' = x^2 + k DECLARED cubic under the degree bound 2n, the last three rows exempt.
+    By the declared degree deg H may reach 3 (n - 1) + 3 - n = 2n, so 2n points do not fix it and the 2n-point path is refused before
+    the trace is looked at; the trace satisfies the constraint and its H, of degree 2 (n - 1) + 3 - n = n + 1, passes the
+    high-coefficient check.  16 rows, blowup 4."""
+    n, k = 16, X.keys(61, 1)[0]
+    b = air.AirBuilder(1, [0, 1], 2)
+    x = b.load(0, 0)
+    b.constraint(b.load(1, 0) - x * x - b.const(k), degree=3, exemptions=3)
+    b.boundary(0, 0, 3)
+    rows = [[3]]
+    while len(rows) < n:
+        rows.append([(rows[-1][0] ** 2 + k) % P])
+    assert b.check_trace(rows) == []
+    desc, keep = b.build()
+    trace, options = X.to_bytes(rows), (4, 3, 3, 1)
+    want = O.program_air_prove(desc, trace, options)
+    assert O.program_air_verify(desc, want, options)
+    assert hip_ctx.air_prove(desc, trace, api.ProofOptions(*options)) == want
+    assert hip_ctx.last_proof_info()["composition_path"] == 2
+
+
 # ---- 5. Poseidon trees -----------------------------------------------------------------------------------------------------------
 def test_poseidon_backend(hip_ctx):
     b, rows = X.mimc(64, 8, seed=41)
