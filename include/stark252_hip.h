@@ -76,7 +76,8 @@ const char* sp_version(void);
  * of the same world; 5: sp_fe_mul; 6: sp_air_limits, sp_air_prove beyond 64 columns and 3 boundary rows; 7: sp_air_prove_aux, sp_air_aux_desc,
  * sp_air_aux_desc_size, sp_air_prove_periodic, sp_air_verify_periodic, sp_air_periodic_desc_size, sp_air_periodic_limits,
  * sp_air_periodic_eval, sp_air_periodic_lde; sp_air_check_trace and sp_air_violation_size joined under 7 - they change no structure
- * and no call, and a binding finds a build without them by probing the symbols).  A binding compares it (and sp_air_desc_size against its own idea of the struct) when it loads the library, so
+ * and no call, and a binding finds a build without them by probing the symbols; so did sp_air_prove_ext, sp_air_verify_ext, sp_air_check_trace_ext,
+ * sp_air_stride_size, sp_air_stride_desc_size, sp_air_ext_size, sp_air_stride_limits, sp_air_stride_eval and sp_air_stride_table).  A binding compares it (and sp_air_desc_size against its own idea of the struct) when it loads the library, so
  * a stale build fails at load time with "rebuild the library" instead of with a missing symbol or shifted fields later. */
 #define SP_ABI_VERSION 7
 int sp_abi_version(void);
@@ -520,6 +521,56 @@ uint64_t sp_air_violation_size(void);
 int sp_air_check_trace(sp_ctx* ctx, const sp_air_desc* air, const sp_air_aux_desc* aux, const sp_air_periodic_desc* periodic,
                        const uint8_t* main_trace, uint64_t n, const sp_proof_options* opt, const uint8_t* rap,
                        sp_air_violation* out, uint32_t cap, uint32_t* n_out);
+
+/* Strided transition constraints (NO reference counterpart, like periodic columns): constraint k is enforced on the rows
+ * i = offset_k (mod period_k) only - "every 8th row starts a hash invocation", "rows = 3 (mod 4) carry the range-check cell".  period
+ * is a power of two with 1 <= period <= n and 0 <= offset < period; (1, 0) is sp_air_prove's behaviour.  With s = period, o = offset,
+ * e = exemptions[k], g the trace-domain generator, f = degree_bound_factor and d = degrees[k]:
+ *   enforced rows   i = o (mod s) except the last e rows OF THAT PROGRESSION, o + s (n/s - 1 - t) for t < e; a stride with s > 1
+ *                   needs e < n/s and always uses its own e (the num_transition_exemptions == 1 rule stays with the (1, 0) constraints)
+ *   zerofier        Z(x) = x^(n/s) - g^(o n/s)
+ *   exemptions      E(x) = prod_{t < e} (x - g^(o + s (n/s - 1 - t)))
+ *   composition     (alpha_k x^adj + beta_k) C_k(x) E(x) / Z(x),  adj = n (f - d) + n/s   (s = 1: sp_air_prove's n (f - d + 1))
+ * The term has f n - d + e + 1 coefficients whatever the stride.  A stride with s > 1 needs d <= f: the quotient C_k / Z divides by n/s
+ * roots only and has degree d n - n/s, so adj would be negative for d = f + 1 (which a (1, 0) constraint may have).  Constraints with
+ * the same (s, o), s > 1, form a stride class: at most 4 classes per AIR, at most 4 distinct (class, e > 0) exemption products
+ * (sp_air_stride_limits).  Nothing of this enters the transcript or the proof format. */
+typedef struct { uint32_t period, offset; } sp_air_stride;
+typedef struct { uint32_t n; uint32_t pad; const sp_air_stride* strides; /* n == air->n_transitions */ } sp_air_stride_desc;
+/* The extensions of a program AIR in one block, each nullable: size = sizeof(sp_air_ext) as the caller compiled it. */
+typedef struct {
+    uint32_t size, pad;
+    const sp_air_aux_desc* aux;              /* as sp_air_prove_aux takes it */
+    const sp_air_periodic_desc* periodic;    /* as sp_air_prove_periodic takes it */
+    const sp_air_stride_desc* strides;
+} sp_air_ext;
+uint64_t sp_air_stride_size(void);
+uint64_t sp_air_stride_desc_size(void);
+uint64_t sp_air_ext_size(void);
+/* out = {stride classes at most (4), distinct (class, e > 0) exemption products at most (4), 0, 0 (reserved)} */
+int sp_air_stride_limits(uint32_t out[4]);
+/* sp_air_prove / _aux / _periodic, sp_air_verify_periodic and sp_air_check_trace with the extensions of `ext` (NULL, or all members
+ * NULL: sp_air_prove, sp_air_verify_backend, sp_air_check_trace without extensions - the same bytes, verdicts and error codes).  A
+ * malformed stride descriptor - n != air->n_transitions, null strides, a period that is zero, no power of two or above the trace
+ * length, offset >= period, exemptions[k] >= n/period or degrees[k] > degree_bound_factor for a period > 1, more classes or exemption products than
+ * sp_air_stride_limits, ext->size other than sizeof(sp_air_ext) - is SP_E_INVALID_ARG from the prover and the trace check and 0 from
+ * the verifier, before anything is sized from it.  sp_air_check_trace_ext follows the enforced-row rule above: rows outside a
+ * constraint's progression are neither flagged nor counted. */
+int sp_air_prove_ext(sp_ctx* ctx, const sp_air_desc* air, const sp_air_ext* ext, const uint8_t* main_trace, uint64_t n,
+                     const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len);
+int sp_air_verify_ext(const uint8_t* proof, uint64_t proof_len, const sp_air_desc* air, const sp_air_ext* ext,
+                      const sp_proof_options* opt, int merkle_backend);
+int sp_air_check_trace_ext(sp_ctx* ctx, const sp_air_desc* air, const sp_air_ext* ext, const uint8_t* main_trace, uint64_t n,
+                           const sp_proof_options* opt, const uint8_t* rap, sp_air_violation* out, uint32_t cap, uint32_t* n_out);
+/* Test seams.  sp_air_stride_eval (host, the verifier's routine): out_z = Z(point), out_e = E(point) for a stride (period, offset)
+ * with `exemptions` exempted rows on a trace of n rows, canonical BE in and out; period 1 gives x^n - 1 and the last rows of the
+ * trace.  sp_air_stride_table (device): one period of 1 / Z as the composition kernel reads it, in natural order: out[k] =
+ * 1 / Z(coset w_N^k) for k < period x blowup (N = n x blowup), canonical BE.  n, blowup, period powers of two, blowup >= 2,
+ * n x blowup <= 2^30, 1 <= period <= n, offset < period, exemptions <= n / period and <= 65536 (one host product each) (SP_E_INVALID_ARG otherwise); SP_E_ZERO_INVERSE when
+ * Z vanishes on the coset. */
+int sp_air_stride_eval(uint32_t period, uint32_t offset, uint32_t exemptions, uint64_t n, const uint8_t point[32], uint8_t out_z[32],
+                       uint8_t out_e[32]);
+int sp_air_stride_table(sp_ctx* ctx, uint32_t period, uint32_t offset, uint64_t n, uint32_t blowup, const uint8_t coset[32], uint8_t* out);
 
 /* verify::<Stark252PrimeField, A> (reference src/starks/verifier.rs:559-657) on the host CPU: 1 accept, 0 reject (also for
  * malformed proofs or descriptors). */

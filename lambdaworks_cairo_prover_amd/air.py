@@ -12,6 +12,10 @@ context (columns, transition offsets / degrees / exemptions), `compute_transitio
 Periodic columns (an extension beyond the reference's trait): AirBuilder(..., periodic=[values0, values1, ...]) declares public
 sequences that repeat down the trace (each a power-of-two number of values, at most the trace length); b.periodic(row, k) reads
 column k at frame row `row`.  In a constraint's declared degree such a value counts as a trace cell.  See mimc_chain below.
+
+Strided constraints (another extension): b.constraint(value, degree, exemptions, period=4, offset=1) enforces the constraint on the rows
+= 1 (mod 4) only, dividing by that progression's own zerofier instead of multiplying by a selector column: the declared degree stays
+the constraint's own.  `exemptions` then counts the last rows of the progression.  See strided_mimc_chain below.
 """
 import collections
 import ctypes
@@ -89,6 +93,51 @@ def _check_periodic_layout():
     want = _lib.load().sp_air_periodic_desc_size()
     if ctypes.sizeof(AirPeriodicDescC) != want:
         raise ImportError(f"AirPeriodicDescC is {ctypes.sizeof(AirPeriodicDescC)} bytes, the library's sp_air_periodic_desc {want}: the binding is out of date")
+
+
+class AirStrideC(ctypes.Structure):
+    _fields_ = [("period", ctypes.c_uint32), ("offset", ctypes.c_uint32)]
+
+
+class AirStrideDescC(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_uint32), ("pad", ctypes.c_uint32), ("strides", ctypes.POINTER(AirStrideC))]
+
+
+class AirExtC(ctypes.Structure):
+    _fields_ = [("size", ctypes.c_uint32), ("pad", ctypes.c_uint32), ("aux", ctypes.POINTER(AirAuxDescC)),
+                ("periodic", ctypes.POINTER(AirPeriodicDescC)), ("strides", ctypes.POINTER(AirStrideDescC))]
+
+
+def _check_stride_layout():
+    from . import _lib
+    lib = _lib.load()
+    for name, mirror in (("sp_air_stride_size", AirStrideC), ("sp_air_stride_desc_size", AirStrideDescC), ("sp_air_ext_size", AirExtC)):
+        want = getattr(lib, name)()
+        if ctypes.sizeof(mirror) != want:
+            raise ImportError(f"{mirror.__name__} is {ctypes.sizeof(mirror)} bytes, the library's struct ({name}) {want}: the binding is out of date")
+
+
+def stride_desc(strides):
+    """[(period, offset), ...], one per transition constraint -> (AirStrideDescC, keepalive): sp_air_stride_desc."""
+    _check_stride_layout()
+    arr = (AirStrideC * max(1, len(strides)))()
+    for k, (period, offset) in enumerate(strides):
+        arr[k].period, arr[k].offset = period, offset
+    d = AirStrideDescC()
+    d.n, d.strides = len(strides), ctypes.cast(arr, ctypes.POINTER(AirStrideC))
+    return d, arr
+
+
+def ext_of(desc):
+    """The sp_air_ext of a built descriptor: what it carries of desc.aux_desc, desc.periodic_desc and desc.stride_desc."""
+    _check_stride_layout()
+    x = AirExtC()
+    x.size = ctypes.sizeof(AirExtC)
+    for field, attr in (("aux", "aux_desc"), ("periodic", "periodic_desc"), ("strides", "stride_desc")):
+        part = getattr(desc, attr, None)
+        if part is not None:
+            setattr(x, field, ctypes.pointer(part))
+    return x
 
 
 class AirViolationC(ctypes.Structure):
@@ -287,6 +336,7 @@ class AirBuilder:
         self.degree_bound_factor, self.n_rap, self.aux_kind = degree_bound_factor, n_rap, aux_kind
         self.num_transition_exemptions = num_transition_exemptions
         self.ops, self.consts, self.degrees, self.exemptions, self.bcs = [], [], [], [], []
+        self.strides = []   # per constraint (period, offset): enforced on the rows = offset (mod period)
         # aux_kind AUX_PROGRAM: the auxiliary columns as a program over the main-trace row (sp_air_prove_aux)
         self.aux = AuxProgram(main_cols, n_rap) if aux_kind == AUX_PROGRAM else None
 
@@ -317,11 +367,18 @@ class AirBuilder:
         assert i < self.n_rap
         return self._emit(OP_CONST, _RAP_TAG | i, 0)
 
-    def constraint(self, value, degree, exemptions):
+    def constraint(self, value, degree, exemptions, period=1, offset=0):
+        """period, offset: enforce the constraint on the rows = offset (mod period) only (a power of two; 1, 0: every row).  With a
+        period > 1 `exemptions` counts the last rows of that progression, and must leave one: exemptions < n / period."""
         assert len(self.degrees) < MAX_TRANSITIONS
+        if period < 1 or period & (period - 1):
+            raise ValueError(f"constraint {len(self.degrees)}: its period {period} is not a power of two")
+        if not 0 <= offset < period:
+            raise ValueError(f"constraint {len(self.degrees)}: offset {offset} outside 0 .. period - 1 = {period - 1}")
         self._emit(OP_OUT, len(self.degrees), value.i)
         self.degrees.append(degree)
         self.exemptions.append(exemptions)
+        self.strides.append((period, offset))
 
     def boundary(self, col, step, value):
         self.bcs.append((col, step, value % P))
@@ -329,16 +386,28 @@ class AirBuilder:
     def enforced_exemptions(self):
         """Per constraint, the number of last rows it is not enforced on - what the composition uses: its own exemption count, or,
         with num_transition_exemptions == 1, the first non-zero count of the AIR for every constraint that has one."""
-        nonzero = [e for e in self.exemptions if e > 0]
+        strided = [period > 1 for period, _ in self._strides()]   # (a strided constraint always uses its own count)
+        nonzero = [e for e, s in zip(self.exemptions, strided) if e > 0 and not s]
         if self.num_transition_exemptions == 1 and nonzero:
-            return [nonzero[0] if e > 0 else 0 for e in self.exemptions]
+            return [e if s else (nonzero[0] if e > 0 else 0) for e, s in zip(self.exemptions, strided)]
         return list(self.exemptions)
+
+    def _strides(self):
+        """One (period, offset) per constraint, also for a builder whose lists were filled by hand."""
+        return list(self.strides) + [(1, 0)] * (len(self.degrees) - len(self.strides))
+
+    def enforced_rows(self, k, n):
+        """The rows constraint k is enforced on in a trace of n rows: its progression without its last enforced_exemptions()[k] rows."""
+        period, offset = self._strides()[k]
+        rows = list(range(offset, n, period))
+        return rows[:max(0, len(rows) - self.enforced_exemptions()[k])]
 
     def check_trace(self, rows, rap=()):
         """Which constraints the trace breaks, and where, in Python integers: the model of sp_air_check_trace (the reference's
         validate_trace, src/starks/debug.rs:13-104).  rows: (n, main_cols + aux_cols) ints, main||aux; with an aux program also
         (n, main_cols), to which self.aux.evaluate(rows, rap) is appended.  rap: the RAP challenges.  Constraint k is enforced on rows
-        0 .. n - 1 - enforced_exemptions()[k]; frame rows wrap modulo n.  Returns [Violation, ...]: the transition constraints by
+        0 .. n - 1 - enforced_exemptions()[k] - with a period > 1 on enforced_rows(k, n), its progression without that many of its last
+        rows; frame rows wrap modulo n.  Returns [Violation, ...]: the transition constraints by
         index, then the boundary constraints by index; [] for a trace that satisfies the AIR."""
         import numpy as np
         m = np.empty((len(rows), len(rows[0])), dtype=object)
@@ -379,7 +448,7 @@ class AirBuilder:
         for k, ex in enumerate(self.enforced_exemptions()):
             if k not in outs:
                 continue
-            bad = [i for i in range(max(0, n - ex)) if outs[k][i] != 0]
+            bad = [i for i in self.enforced_rows(k, n) if outs[k][i] != 0]
             if bad:
                 found.append(Violation(TRANSITION, k, len(bad), bad[0], bad[-1], int(outs[k][bad[0]])))
         for j, (col, step, value) in enumerate(self.bcs):
@@ -401,6 +470,19 @@ class AirBuilder:
             most = air_periodic_limits()["periodic_columns"]
             if len(self.periodic_cols) > most:
                 raise ValueError(f"AIR exceeds the periodic_columns limit of sp_air_prove_periodic: {len(self.periodic_cols)} > {most}")
+        classes = sorted({s for s in self._strides() if s[0] > 1})
+        for k, (period, _) in enumerate(self._strides()):
+            if period > 1 and self.degrees[k] > self.degree_bound_factor:
+                raise ValueError(f"constraint {k}: degree {self.degrees[k]} on a stride needs degree_bound_factor >= {self.degrees[k]} (the quotient by "
+                                 f"the progression's zerofier has degree d n - n / period; only a constraint on every row may have d = f + 1)")
+        if classes:
+            from .api import air_stride_limits
+            slim = air_stride_limits()
+            kinds = {(s, e) for s, e in zip(self._strides(), self.exemptions) if s[0] > 1 and e > 0}
+            if len(classes) > slim["stride_classes"]:
+                raise ValueError(f"AIR exceeds the stride_classes limit of sp_air_prove_ext: {len(classes)} > {slim['stride_classes']}")
+            if len(kinds) > slim["stride_exemption_products"]:
+                raise ValueError(f"AIR exceeds the stride_exemption_products limit of sp_air_prove_ext: {len(kinds)} > {slim['stride_exemption_products']}")
         if self.aux is not None:
             if len(self.aux.cols) != self.aux_cols:
                 raise ValueError(f"aux program declares {len(self.aux.cols)} auxiliary columns, the AIR has aux_cols = {self.aux_cols}")
@@ -413,6 +495,9 @@ class AirBuilder:
     def build(self, aux_as_callback=False, main_trace=None):
         """Returns (AirDescC, keepalive).  Raises ValueError if the AIR exceeds a bound of sp_air_limits.
 
+        With a constraint of period > 1 the returned desc carries the AirStrideDescC of all constraints (desc.stride_desc):
+        api.Context.air_prove, air_check_trace and api.air_verify then go through the _ext entry points (sp_air_prove_ext ...) with
+        whatever else the desc carries.  A builder that never passes `period` produces the descriptor it always produced.
         With periodic columns the returned desc carries their AirPeriodicDescC (desc.periodic_desc): api.Context.air_prove proves it with
         sp_air_prove_periodic, api.air_verify checks it with sp_air_verify_periodic.
         With an aux program (aux_kind AUX_PROGRAM) the returned desc carries its AirAuxDescC (desc.aux_desc), and
@@ -472,6 +557,10 @@ class AirBuilder:
             per_desc, per_keep = periodic_desc(self.periodic_cols)
             d.periodic_desc = per_desc
             keep = keep + (per_desc, per_keep)
+        if any(period > 1 for period, _ in self._strides()):
+            s_desc, s_keep = stride_desc(self._strides())
+            d.stride_desc = s_desc
+            keep = keep + (s_desc, s_keep)
         if self.aux is not None:
             aux_desc, aux_keep = self._aux_desc()
             d.aux_desc = aux_desc
@@ -598,4 +687,48 @@ def mimc_chain_trace(n, x0, keys):
     for i in range(n):
         rows.append([x])
         x = pow((x + keys[i % len(keys)]) % P, 3, P)
+    return rows
+
+
+# ---- strided constraints: a worked example ------------------------------------------------------------------------------
+STRIDED_CHAIN_PERIOD = 4
+
+
+def strided_mimc_chain(n, x0, keys, selector=False):
+    """mimc_chain's shape with a SQUARING round on the rows = 0 (mod 4) only: x_(i+1) = (x_i + K_(i mod period))^2 for i = 0, 4, 8,
+    ..., n - 8, the three rows between free (a real layout would put other cells there) and the last row of the progression, n - 4,
+    exempt as the last row of mimc_chain is.  One statement, two ways to say it, both under degree_bound_factor 2:
+
+    selector=False  the constraint x' - (x + K)^2 with period=4, offset=0, exemptions=1: declared degree 2.  Its quotient by
+                    x^(n/4) - 1 has degree 2 (n - 1) + 1 - n/4, the term of the composition 2n - 2 + 1 + 1 = 2n coefficients.
+    selector=True   the same constraint times the periodic column [1, 0, 0, 0] on every row but the last four: declared degree 3 =
+                    degree_bound_factor + 1, 2n - 3 + 4 + 1 = 2n + 2 coefficients by the declared degrees: above 2n, so the 2n-point
+                    path is refused before the trace is looked at and the whole LDE domain is evaluated (blowup / 2 times the
+                    composition points), and every lane reads and multiplies the selector.
+
+    The cube of mimc_chain cannot be put on a stride under degree_bound_factor 2: a strided constraint needs degree <= the factor
+    (AirBuilder.check_limits), and a factor of 3 is beyond the two halves H1, H2 of the proof format.
+
+    keys: a power-of-two number of round constants, at most n; n >= 8."""
+    if n < 2 * STRIDED_CHAIN_PERIOD or len(keys) > n:
+        raise ValueError(f"strided_mimc_chain: {n} rows, {len(keys)} keys (at least 8 rows, at most n keys)")
+    if selector:
+        b = AirBuilder(1, [0, 1], 2, periodic=[keys, [1, 0, 0, 0]])
+        t = b.load(0, 0) + b.periodic(0, 0)
+        b.constraint(b.periodic(0, 1) * (b.load(1, 0) - t * t), degree=3, exemptions=4)
+    else:
+        b = AirBuilder(1, [0, 1], 2, periodic=[keys])
+        t = b.load(0, 0) + b.periodic(0, 0)
+        b.constraint(b.load(1, 0) - t * t, degree=2, exemptions=1, period=STRIDED_CHAIN_PERIOD, offset=0)
+    b.boundary(0, 0, x0)
+    return b
+
+
+def strided_mimc_chain_trace(n, x0, keys, free):
+    """A trace of strided_mimc_chain as (n, 1) Python ints: row i + 1 = (x_i + K_(i mod period))^2 for i = 0 (mod 4), the other rows
+    from `free` (a callable giving the next free value)."""
+    rows, x = [], x0 % P
+    for i in range(n):
+        rows.append([x])
+        x = pow((x + keys[i % len(keys)]) % P, 2, P) if i % STRIDED_CHAIN_PERIOD == 0 else free() % P
     return rows

@@ -222,7 +222,8 @@ class Context:
     def air_prove(self, desc, main_trace, options):
         """sp_air_prove: desc = lambdaworks_cairo_prover_amd.air.AirDescC (AirBuilder.build()[0]); main_trace (n, cols, 32).
         A desc that carries an auxiliary program (AirBuilder with aux_kind=air.AUX_PROGRAM) goes to sp_air_prove_aux, one that
-        carries periodic columns (AirBuilder(..., periodic=[...])) to sp_air_prove_periodic - with its auxiliary program, if any."""
+        carries periodic columns (AirBuilder(..., periodic=[...])) to sp_air_prove_periodic - with its auxiliary program, if any; one
+        that carries strides (a constraint with period > 1) to sp_air_prove_ext with all of these."""
         a = np.ascontiguousarray(main_trace, dtype=np.uint8)
         n, cols = a.shape[0], a.shape[1]
         assert cols == desc.main_cols
@@ -231,7 +232,12 @@ class Context:
         ln = ctypes.c_uint64()
         aux = getattr(desc, "aux_desc", None)
         per = getattr(desc, "periodic_desc", None)
-        if per is not None:
+        if getattr(desc, "stride_desc", None) is not None:
+            from . import air
+            ext = air.ext_of(desc)
+            check(self._lib.sp_air_prove_ext(self._h, ctypes.byref(desc), ctypes.byref(ext), _u8p(a), ctypes.c_uint64(n), ctypes.byref(opt),
+                                             ctypes.byref(out), ctypes.byref(ln)))
+        elif per is not None:
             check(self._lib.sp_air_prove_periodic(self._h, ctypes.byref(desc), None if aux is None else ctypes.byref(aux), ctypes.byref(per), _u8p(a),
                                                   ctypes.c_uint64(n), ctypes.byref(opt), ctypes.byref(out), ctypes.byref(ln)))
         elif aux is not None:
@@ -268,9 +274,13 @@ class Context:
         total = ctypes.c_uint32(0)
         aux = getattr(desc, "aux_desc", None)
         per = getattr(desc, "periodic_desc", None)
-        check(self._lib.sp_air_check_trace(self._h, ctypes.byref(desc), None if aux is None else ctypes.byref(aux), None if per is None else ctypes.byref(per),
-                                           _u8p(a), ctypes.c_uint64(n), None if opt is None else ctypes.byref(opt), None if rap_bytes is None else _u8p(rap_bytes),
-                                           out if cap else None, ctypes.c_uint32(cap), ctypes.byref(total)))
+        tail = (_u8p(a), ctypes.c_uint64(n), None if opt is None else ctypes.byref(opt), None if rap_bytes is None else _u8p(rap_bytes),
+                out if cap else None, ctypes.c_uint32(cap), ctypes.byref(total))
+        if getattr(desc, "stride_desc", None) is not None:
+            ext = air.ext_of(desc)
+            check(self._lib.sp_air_check_trace_ext(self._h, ctypes.byref(desc), ctypes.byref(ext), *tail))
+        else:
+            check(self._lib.sp_air_check_trace(self._h, ctypes.byref(desc), None if aux is None else ctypes.byref(aux), None if per is None else ctypes.byref(per), *tail))
         self.last_check_total = total.value     # the number of violated constraints, which may exceed cap
         return [air.Violation(int(v.kind), int(v.index), int(v.rows), int(v.first_row), int(v.last_row), int.from_bytes(bytes(v.value), "big"))
                 for v in out[:min(cap, total.value)]]
@@ -282,6 +292,14 @@ class Context:
         d, keep = air.periodic_desc([list(values)])
         out = np.empty((len(values) * blowup, 32), dtype=np.uint8)
         check(self._lib.sp_air_periodic_lde(self._h, d.cols, ctypes.c_uint64(n), ctypes.c_uint32(blowup), int(coset).to_bytes(32, "big"), _u8p(out)))
+        return out
+
+    def air_stride_table(self, period, offset, n, blowup, coset):
+        """sp_air_stride_table: one period of 1 / Z, Z = x^(n/period) - g^(offset n/period), as the composition kernel reads it for the
+        constraints on the rows = offset (mod period), in natural order: (period * blowup, 32) canonical big-endian, row k at coset w_N^k."""
+        out = np.empty((period * blowup, 32), dtype=np.uint8)
+        check(self._lib.sp_air_stride_table(self._h, ctypes.c_uint32(period), ctypes.c_uint32(offset), ctypes.c_uint64(n), ctypes.c_uint32(blowup),
+                                            int(coset).to_bytes(32, "big"), _u8p(out)))
         return out
 
     def last_proof_info(self):
@@ -509,6 +527,23 @@ def air_periodic_limits():
     return {"periodic_columns": int(out[0])}
 
 
+def air_stride_limits():
+    """sp_air_stride_limits: {"stride_classes": 4, "stride_exemption_products": 4} - distinct (period, offset) with period > 1, and distinct
+    (class, exemptions > 0), per AIR."""
+    out = (ctypes.c_uint32 * 4)()
+    check(_lib.load().sp_air_stride_limits(out))
+    return {"stride_classes": int(out[0]), "stride_exemption_products": int(out[1])}
+
+
+def air_stride_eval(period, offset, exemptions, n, point):
+    """sp_air_stride_eval (host, the verifier's routine): (Z(point), E(point)) as ints - the zerofier x^(n/period) - g^(offset n/period) of
+    the rows = offset (mod period) and the product of (x - g^row) over the last `exemptions` rows of that progression."""
+    z, e = ctypes.create_string_buffer(32), ctypes.create_string_buffer(32)
+    check(_lib.load().sp_air_stride_eval(ctypes.c_uint32(period), ctypes.c_uint32(offset), ctypes.c_uint32(exemptions), ctypes.c_uint64(n),
+                                         (int(point) % P).to_bytes(32, "big"), z, e))
+    return int.from_bytes(z.raw, "big"), int.from_bytes(e.raw, "big")
+
+
 def air_periodic_eval(values, n, point):
     """sp_air_periodic_eval (host): P(point) of the periodic column `values` (ints) on a trace of n rows, as an int."""
     from . import air
@@ -520,10 +555,14 @@ def air_periodic_eval(values, n, point):
 
 def air_verify(proof, desc, options, merkle_backend=0):
     """sp_air_verify(_backend): the library's CPU verifier for an AIR given as a constraint program (sp_air_verify_periodic for a
-    desc that carries periodic columns)."""
+    desc that carries periodic columns, sp_air_verify_ext for one that carries strides)."""
     lib = _lib.load()
     opt = options.to_c()
     per = getattr(desc, "periodic_desc", None)
+    if getattr(desc, "stride_desc", None) is not None:
+        from . import air
+        ext = air.ext_of(desc)
+        return lib.sp_air_verify_ext(proof, ctypes.c_uint64(len(proof)), ctypes.byref(desc), ctypes.byref(ext), ctypes.byref(opt), int(merkle_backend)) == 1
     if per is not None:
         return lib.sp_air_verify_periodic(proof, ctypes.c_uint64(len(proof)), ctypes.byref(desc), ctypes.byref(per), ctypes.byref(opt), int(merkle_backend)) == 1
     return lib.sp_air_verify_backend(proof, ctypes.c_uint64(len(proof)), ctypes.byref(desc), ctypes.byref(opt), int(merkle_backend)) == 1

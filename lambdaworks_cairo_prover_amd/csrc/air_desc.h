@@ -1,7 +1,8 @@
 // Host forms of the C views of include/stark252_hip.h that the prover and the verifier share: proof options, sp_air_desc,
-// sp_air_aux_desc, sp_air_periodic_desc, and the well-formedness rules of their straight-line programs.  Host only (no device headers).
+// sp_air_aux_desc, sp_air_periodic_desc, sp_air_stride_desc, and the well-formedness rules of their straight-line programs.  Host only (no device headers).
 #pragma once
 #include "cairo_air_host.h"
+#include <utility>
 #include <vector>
 
 namespace sp {
@@ -10,6 +11,11 @@ struct ProofOptionsHost { uint8_t blowup_factor; uint64_t fri_number_of_queries;
 inline ProofOptionsHost proof_options_from_c(const sp_proof_options* o) {
     return ProofOptionsHost{o->blowup_factor, o->fri_number_of_queries, o->coset_offset, o->grinding_factor};
 }
+
+// Host form of sp_air_stride: constraint k is enforced on the rows i = offset (mod period), period a power of two.
+struct AirStrideHost { uint32_t period = 1, offset = 0; };
+// Constraints with one (period, offset), period > 1, share a zerofier: a stride class.  An exemption product belongs to a (class, e > 0).
+constexpr uint32_t AIR_MAX_STRIDE_CLASSES = 4, AIR_MAX_STRIDE_EXEMPT_KINDS = 4;
 
 // Host form of sp_air_desc.
 struct AirOpHost { uint8_t op; uint32_t a, b; };   // as the caller wrote it: operands are indices of earlier ops
@@ -22,6 +28,7 @@ struct AirDescHost {
     uint32_t n_rap = 0, aux_kind = 0;
     sp_aux_trace_fn aux_fn = nullptr; void* aux_user = nullptr;   // aux_kind 2: build_auxiliary_trace supplied by the caller
     std::vector<BoundaryConstraint> boundary;
+    std::vector<AirStrideHost> strides;   // per transition constraint (sp_air_stride_desc); empty: every constraint on every row
 };
 // sp_air_desc -> AirDescHost; false for a malformed descriptor (counts out of range, a count without its array).  capi_host.cpp
 bool air_desc_from_c(const sp_air_desc* d, AirDescHost& out);
@@ -45,6 +52,25 @@ bool air_periodic_fits(const AirPeriodicHost& p, uint64_t n);
 // evaluated at point^(n / period).  What the verifier uses for P_k(z g^offset) and what sp_air_periodic_eval returns.  verifier.cpp
 std::vector<fe> air_periodic_interpolate(const std::vector<fe>& values);
 fe air_periodic_eval(const std::vector<fe>& coeffs, uint64_t n, const fe& point);
+
+// The strides of an AIR sorted into classes and exemption products, for a trace of n rows.  cls[k]: -1 for a (1, 0) constraint, else
+// its class; kind[k]: -1 without exempted rows (or for a (1, 0) constraint), else its entry of `kinds` = (class, e).
+struct AirStridePlan {
+    std::vector<AirStrideHost> classes;
+    std::vector<std::pair<uint32_t, uint32_t>> kinds;
+    std::vector<int> cls, kind;
+};
+// false for strides that break a rule of sp_air_stride_desc: not one per transition, a period that is zero, no power of two or above
+// n, offset >= period, exemptions[k] >= n / period or degrees[k] > degree_bound_factor for a period > 1 (the quotient by the smaller
+// zerofier has degree d n - n/s, which fits under f n for d <= f only), more classes or exemption products than the limits.  Reads
+// air.strides / exemptions / degrees / degree_bound_factor only; empty strides give a plan without classes.  verifier.cpp
+bool air_stride_plan(const AirDescHost& air, uint64_t n, AirStridePlan& out);
+// sp_air_stride_desc -> air.strides for a trace of n rows (a power of two): the one place where a descriptor's strides are checked
+// (air_stride_plan) - prover, trace check and verifier all read them through it; on false air.strides stays empty.  capi_host.cpp
+bool air_strides_from_c(const sp_air_stride_desc* d, uint64_t n, AirDescHost& air);
+// Z(x) = x^(n/s) - g^(o n/s) and E(x) = prod_{t<e} (x - g^(o + s (n/s - 1 - t))) of a stride (s, o) with e exempted rows on a trace of
+// n rows (all already checked: s | n, o < s, e <= n/s).  What the verifier's step 2 uses and sp_air_stride_eval returns.  verifier.cpp
+void air_stride_eval(uint32_t s, uint32_t o, uint32_t e, uint64_t n, const fe& x, fe& Z, fe& E);
 
 // The rules of a straight-line program (op 0 LOAD, 1 CONST, 2 ADD, 3 SUB, 4 MUL, 5 OUT, 6 PERIODIC): a LOAD has a < load_a_end and
 // b < load_b_end, a CONST names one of n_values constants or RAP challenges, ADD / SUB / MUL take two earlier ops that are not

@@ -11,6 +11,8 @@
 
 // prover.cpp: the periodic-column tables of a program AIR (sp_air_periodic_lde hands one out)
 namespace sp { int air_periodic_tables(hipStream_t st, NttEngine& ntt, fe* vals, fe* ws, fe* tab, uint32_t cnt, uint32_t logp, uint32_t logn, uint32_t logb, const fe& h); }
+// prover_round2.cpp: the tables of one stride class (sp_air_stride_table hands out their inverse half)
+namespace sp { int air_stride_class_tables(hipStream_t st, NttEngine& ntt, fe* u, fe* z, uint32_t logs, uint32_t offset, uint32_t logn, uint32_t logb, const fe& h); }
 using namespace sp;
 
 namespace {
@@ -664,6 +666,34 @@ int sp_air_periodic_lde(sp_ctx* c, const sp_air_periodic_column* col, uint64_t n
     SP_HIP_CHECK(hipStreamSynchronize(c->stream));
     for (uint64_t cc = 0; cc < blowup; ++cc)
         for (uint64_t j = 0; j < p; ++j) fe_to_bytes_be(ht[cc * p + j], out + 32 * (j * blowup + cc));
+    return SP_OK;
+}
+
+// One stride class's 1 / Z table as composition_air builds it (air_stride_tables + batch_inverse), handed back in natural order:
+// out[j b + c] = table entry (c, j).  Canonical big-endian whatever the context's encoding.
+int sp_air_stride_table(sp_ctx* c, uint32_t period, uint32_t offset, uint64_t n, uint32_t blowup, const uint8_t coset[32], uint8_t* out) {
+    if (!c || !coset || !out) return SP_E_INVALID_ARG;
+    SP_HIP_CHECK(hipSetDevice(c->device));
+    const int k = sp_log2_exact(n), lb = sp_log2_exact(blowup), ls = period ? sp_log2_exact(period) : -1;
+    if (k < 0 || lb < 1 || k + lb > 30 || ls < 0 || ls > k || offset >= period) {
+        sp_set_error("sp_air_stride_table: n, blowup (>= 2) and the period must be powers of two, 1 <= period <= n, offset < period");
+        return SP_E_INVALID_ARG;
+    }
+    const uint64_t M = (uint64_t)period << lb;
+    DevBuf tab;   // [M] U, [M] U - g^(o n/s) -> 1 / Z, [M] scratch
+    SP_TRY(tab.alloc(3 * M * sizeof(fe)));
+    fe* u = tab.as<fe>();
+    SP_HIP_CHECK(hipMemsetAsync(c->d_flag, 0, sizeof(int), c->stream));
+    SP_TRY(air_stride_class_tables(c->stream, *c->ntt, u, u + M, (uint32_t)ls, offset, (uint32_t)k, (uint32_t)lb, fe_from_bytes_be(coset)));
+    SP_TRY(batch_inverse(c->stream, u + M, u + 2 * M, M, c->d_flag));
+    std::vector<fe> ht(M);
+    int flag = 0;
+    SP_HIP_CHECK(hipMemcpyAsync(ht.data(), u + M, M * sizeof(fe), hipMemcpyDeviceToHost, c->stream));
+    SP_HIP_CHECK(hipMemcpyAsync(&flag, c->d_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    SP_HIP_CHECK(hipStreamSynchronize(c->stream));
+    if (flag) { sp_set_error("sp_air_stride_table: the zerofier vanishes on the coset"); return SP_E_ZERO_INVERSE; }
+    for (uint64_t cc = 0; cc < blowup; ++cc)
+        for (uint64_t j = 0; j < period; ++j) fe_to_bytes_be(ht[cc * period + j], out + 32 * (j * blowup + cc));
     return SP_OK;
 }
 

@@ -109,6 +109,14 @@ bool air_periodic_from_c(const sp_air_periodic_desc* d, uint64_t n, AirPeriodicH
     }
     return true;
 }
+bool air_strides_from_c(const sp_air_stride_desc* d, uint64_t n, AirDescHost& air) {
+    if (d->n != air.exemptions.size() || !d->strides || sp_log2_exact(n) < 0) return false;
+    for (uint32_t k = 0; k < d->n; ++k) air.strides.push_back(AirStrideHost{d->strides[k].period, d->strides[k].offset});
+    AirStridePlan plan;
+    if (air_stride_plan(air, n, plan)) return true;
+    air.strides.clear();
+    return false;
+}
 bool air_periodic_fits(const AirPeriodicHost& p, uint64_t n) {
     for (const auto& c : p.cols) if (c.size() > n) return false;
     return true;
@@ -123,6 +131,14 @@ uint64_t sp_air_desc_size(void) { return sizeof(sp_air_desc); }
 uint64_t sp_air_aux_desc_size(void) { return sizeof(sp_air_aux_desc); }
 uint64_t sp_air_periodic_desc_size(void) { return sizeof(sp_air_periodic_desc); }
 uint64_t sp_air_violation_size(void) { return sizeof(sp_air_violation); }
+uint64_t sp_air_stride_size(void) { return sizeof(sp_air_stride); }
+uint64_t sp_air_stride_desc_size(void) { return sizeof(sp_air_stride_desc); }
+uint64_t sp_air_ext_size(void) { return sizeof(sp_air_ext); }
+int sp_air_stride_limits(uint32_t out[4]) {
+    if (!out) return SP_E_INVALID_ARG;
+    out[0] = sp::AIR_MAX_STRIDE_CLASSES; out[1] = sp::AIR_MAX_STRIDE_EXEMPT_KINDS; out[2] = out[3] = 0u;
+    return SP_OK;
+}
 int sp_air_periodic_limits(uint32_t out[4]) {
     if (!out) return SP_E_INVALID_ARG;
     out[0] = sp::AIR_MAX_PERIODIC; out[1] = out[2] = out[3] = 0u;
@@ -528,6 +544,47 @@ int sp_air_verify_periodic(const uint8_t* proof, uint64_t proof_len, const sp_ai
         sp_set_error(ok == 1 ? "" : "rejected: a verification step failed");
         return ok;
     } catch (const std::exception& e) { sp_set_error(e.what()); return 0; }
+}
+
+// sp_air_verify_backend / sp_air_verify_periodic with the extensions in one block: the strides of the transition constraints too.  The
+// auxiliary program of `ext` is the prover's business (the verifier sees the committed columns) and is not looked at.
+int sp_air_verify_ext(const uint8_t* proof, uint64_t proof_len, const sp_air_desc* d, const sp_air_ext* ext, const sp_proof_options* opt,
+                      int merkle_backend) {
+    if (!proof || !d || !opt) return SP_E_INVALID_ARG;
+    if (merkle_backend != SP_MERKLE_KECCAK256 && merkle_backend != SP_MERKLE_POSEIDON) return SP_E_INVALID_ARG;
+    if (ext && ext->size != sizeof(sp_air_ext)) { sp_set_error("malformed: sp_air_ext.size is not sizeof(sp_air_ext)"); return 0; }
+    VerifyBackendScope scope(merkle_backend);
+    try {
+        sp::AirDescHost air;
+        sp::AirPeriodicHost periodic;
+        if (!sp::air_desc_from_c(d, air)) { sp_set_error("malformed: AIR descriptor"); return 0; }
+        if (proof_len < 8) throw std::runtime_error("malformed: InvalidAmountOfBytes");
+        uint64_t n = 0;   // the trace length is only known from the proof: periods and strides are held against it before anything is copied
+        for (int i = 0; i < 8; ++i) n = (n << 8) | proof[i];
+        const sp_air_periodic_desc* pd = ext ? ext->periodic : nullptr;
+        if (pd && !sp::air_periodic_from_c(pd, n, periodic)) { sp_set_error("malformed: periodic columns (at most 64, each a power-of-two number of values, at most the trace length)"); return 0; }
+        if (ext && ext->strides && !sp::air_strides_from_c(ext->strides, n, air)) {
+            sp_set_error("malformed: strides (one per transition, a power-of-two period <= the trace length, offset < period, exemptions < n / period and degree <= degree_bound_factor for a period > 1, at most 4 classes)");
+            return 0;
+        }
+        const int ok = sp::air_verify_host(proof, proof_len, air, sp::proof_options_from_c(opt), pd ? &periodic : nullptr);
+        sp_set_error(ok == 1 ? "" : "rejected: a verification step failed");
+        return ok;
+    } catch (const std::exception& e) { sp_set_error(e.what()); return 0; }
+}
+
+int sp_air_stride_eval(uint32_t period, uint32_t offset, uint32_t exemptions, uint64_t n, const uint8_t point[32], uint8_t out_z[32], uint8_t out_e[32]) {
+    if (!point || !out_z || !out_e) return SP_E_INVALID_ARG;
+    // E is a host loop of one product per exempted row: bounded here so that the seam cannot be made to spin for 2^40 products
+    if (sp_log2_exact(n) < 0 || n > (1ull << 40) || period == 0 || (period & (period - 1)) || period > n || offset >= period || exemptions > n / period ||
+        exemptions > (1u << 16)) {
+        sp_set_error("sp_air_stride_eval: n and the period must be powers of two, 1 <= period <= n, offset < period, exemptions <= min(n / period, 65536)");
+        return SP_E_INVALID_ARG;
+    }
+    fe Z, E;
+    sp::air_stride_eval(period, offset, exemptions, n, fe_from_bytes_be(point), Z, E);
+    fe_to_bytes_be(Z, out_z); fe_to_bytes_be(E, out_e);
+    return SP_OK;
 }
 
 int sp_air_periodic_eval(const sp_air_periodic_column* col, uint64_t n, const uint8_t point[32], uint8_t out[32]) {

@@ -362,11 +362,15 @@ int sp_last_round_ms(sp_ctx* c, float out[5]) {
     return SP_OK;
 }
 
+static const char* const STRIDES_MALFORMED = "malformed strides (one per transition, a power-of-two period <= the trace length, offset < period, "
+                                             "exemptions < n / period and degree <= degree_bound_factor for a period > 1, at most 4 classes and 4 exemption products)";
 static int air_prove_common(sp_ctx* c, const sp_air_desc* d, const sp::AirAuxHost* aux, const uint8_t* main_trace, uint64_t n,
-                            const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len, const sp::AirPeriodicHost* periodic = nullptr) {
+                            const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len, const sp::AirPeriodicHost* periodic = nullptr,
+                            const sp_air_stride_desc* strides = nullptr) {
     c->prewarm_cancel.store(0, std::memory_order_release);
     sp::AirDescHost a;
     if (!air_desc_from_c(d, a)) { sp_set_error("sp_air_prove: malformed descriptor"); return SP_E_INVALID_ARG; }
+    if (strides && !sp::air_strides_from_c(strides, n, a)) { sp_set_error(STRIDES_MALFORMED); return SP_E_INVALID_ARG; }
     std::vector<uint8_t> proof;
     float ms[5] = {0, 0, 0, 0, 0};
     SP_TRY(sp::air_prove(c, a, main_trace, n, proof_options_from_c(opt), proof, ms, aux, periodic));
@@ -419,8 +423,9 @@ int sp_air_prove_periodic(sp_ctx* c, const sp_air_desc* d, const sp_air_aux_desc
     } catch (const std::exception& e) { sp_set_error(e.what()); return SP_E_INVALID_ARG; }
 }
 
-int sp_air_check_trace(sp_ctx* c, const sp_air_desc* d, const sp_air_aux_desc* x, const sp_air_periodic_desc* pd, const uint8_t* main_trace,
-                       uint64_t n, const sp_proof_options* opt, const uint8_t* rap, sp_air_violation* out, uint32_t cap, uint32_t* n_out) {
+static int air_check_trace_common(sp_ctx* c, const sp_air_desc* d, const sp_air_aux_desc* x, const sp_air_periodic_desc* pd, const sp_air_stride_desc* sd,
+                                  const uint8_t* main_trace, uint64_t n, const sp_proof_options* opt, const uint8_t* rap, sp_air_violation* out, uint32_t cap,
+                                  uint32_t* n_out) {
     if (!c || !d || !main_trace || !n_out || (!opt && !rap) || (!out && cap)) return SP_E_INVALID_ARG;
     try {
         sp::AirDescHost a;
@@ -430,6 +435,7 @@ int sp_air_check_trace(sp_ctx* c, const sp_air_desc* d, const sp_air_aux_desc* x
             sp_set_error("sp_air_check_trace: malformed periodic columns (at most 64, each a power-of-two number of values, at most the trace length)");
             return SP_E_INVALID_ARG;
         }
+        if (sd && !sp::air_strides_from_c(sd, n, a)) { sp_set_error(STRIDES_MALFORMED); return SP_E_INVALID_ARG; }
         sp::AirAuxHost aux;
         if (x) SP_TRY(aux_from_c(d, x, aux));
         c->prewarm_cancel.store(0, std::memory_order_release);   // (the context is first touched here: the descriptors are judged without it)
@@ -446,6 +452,41 @@ int sp_air_check_trace(sp_ctx* c, const sp_air_desc* d, const sp_air_aux_desc* x
         }
         return SP_OK;
     } catch (const std::exception& e) { sp_set_error(e.what()); return SP_E_INVALID_ARG; }
+}
+
+int sp_air_check_trace(sp_ctx* c, const sp_air_desc* d, const sp_air_aux_desc* x, const sp_air_periodic_desc* pd, const uint8_t* main_trace,
+                       uint64_t n, const sp_proof_options* opt, const uint8_t* rap, sp_air_violation* out, uint32_t cap, uint32_t* n_out) {
+    return air_check_trace_common(c, d, x, pd, nullptr, main_trace, n, opt, rap, out, cap, n_out);
+}
+
+// The extensions in one block (sp_air_ext): what sp_air_prove, _aux, _periodic and sp_air_check_trace take one by one, and the strides.
+static bool ext_ok(const sp_air_ext* ext) {
+    if (ext && ext->size != sizeof(sp_air_ext)) { sp_set_error("sp_air_ext.size is not sizeof(sp_air_ext)"); return false; }
+    return true;
+}
+
+int sp_air_prove_ext(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const uint8_t* main_trace, uint64_t n, const sp_proof_options* opt,
+                     uint8_t** proof_out, uint64_t* proof_len) {
+    if (!c || !d || !main_trace || !opt || !proof_out || !proof_len || !ext_ok(ext)) return SP_E_INVALID_ARG;
+    try {
+        sp::AirPeriodicHost periodic;
+        const sp_air_periodic_desc* pd = ext ? ext->periodic : nullptr;
+        if (pd && !sp::air_periodic_from_c(pd, n, periodic)) {
+            sp_set_error("sp_air_prove_ext: malformed periodic columns (at most 64, each a power-of-two number of values, at most the trace length)");
+            return SP_E_INVALID_ARG;
+        }
+        sp::AirAuxHost aux;
+        const sp_air_aux_desc* x = ext ? ext->aux : nullptr;
+        if (x) SP_TRY(aux_from_c(d, x, aux));
+        return air_prove_common(c, d, x ? &aux : nullptr, main_trace, n, opt, proof_out, proof_len, pd ? &periodic : nullptr, ext ? ext->strides : nullptr);
+    } catch (const std::exception& e) { sp_set_error(e.what()); return SP_E_INVALID_ARG; }
+}
+
+int sp_air_check_trace_ext(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const uint8_t* main_trace, uint64_t n, const sp_proof_options* opt,
+                           const uint8_t* rap, sp_air_violation* out, uint32_t cap, uint32_t* n_out) {
+    if (!ext_ok(ext)) return SP_E_INVALID_ARG;
+    return air_check_trace_common(c, d, ext ? ext->aux : nullptr, ext ? ext->periodic : nullptr, ext ? ext->strides : nullptr, main_trace, n, opt, rap,
+                                  out, cap, n_out);
 }
 
 }  // extern "C"

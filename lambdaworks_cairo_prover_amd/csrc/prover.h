@@ -29,6 +29,10 @@ int air_assign_slots(const std::vector<AirOpHost>& ops, std::vector<AirOpDev>& o
 // Periods up to AIR_PERIODIC_DIRECT_MAX by the direct kernels, longer ones by the transform plans (an inverse transform whose post
 // factors scale by h^(n/p) and 1/p, then the coset-major LDE every trace column goes through).
 int air_periodic_tables(hipStream_t st, NttEngine& ntt, fe* vals, fe* ws, fe* tab, uint32_t cnt, uint32_t logp, uint32_t logn, uint32_t logb, const fe& h);
+// The tables of the stride class (s = 2^logs, offset) on a trace of 2^logn rows, coset-major [b][s]: u = U = x^(n/s), z = U - g^(offset n/s)
+// at x = h w_N^(j b + c) (air_stride_tables with its constants).  The caller inverts z.  What composition_air calls per class and what
+// sp_air_stride_table hands out.
+int air_stride_class_tables(hipStream_t st, NttEngine& ntt, fe* u, fe* z, uint32_t logs, uint32_t offset, uint32_t logn, uint32_t logb, const fe& h);
 
 struct Openings {
     uint32_t n_queries = 0, n_layers = 0, n_cols = 0, depth0 = 0;
@@ -241,7 +245,15 @@ class StarkProver : public sp_deletable {
     bool sub_coset_shape() const { return logb_ >= logG_ + 1; }
     bool pair_shape() const { return G_ > 1 && logb_ == logG_ && d_post_comp0_; }
     int fill_cairo_consts(CompositionConsts& K, const fe rap[3], const std::vector<BoundaryConstraint>& bcs, uint32_t n_transitions);
-    struct AirProgramHost { AirProgram prog; std::vector<AirOpDev> dops; std::vector<AirPeriodicCol> pcols; uint64_t S = 0; uint32_t max_ex = 0; };   // S: the periods, summed
+    // S: the periods, summed.  Strided constraints (air.strides): their classes and exemption products (plan), the device descriptor
+    // with its pointers still unset (sdev), the exemption products' roots in the order sdev.kind_root0 names (sroots), the entries of
+    // all classes' [b][s] tables (stab), where build_air_block put the descriptor in the upload (o_sdev), and per constraint the
+    // exempted rows the composition really uses (ex_eff: ex_rows, or a strided constraint's own count).
+    struct AirProgramHost {
+        AirProgram prog; std::vector<AirOpDev> dops; std::vector<AirPeriodicCol> pcols; uint64_t S = 0; uint32_t max_ex = 0;
+        AirStridePlan plan; AirStrideDev sdev; std::vector<fe> sroots; uint64_t stab = 0; size_t o_sdev = 0; std::vector<uint32_t> ex_eff;
+        bool strided() const { return !plan.classes.empty(); }
+    };
     int build_air_program(const AirDescHost& air, size_t n_rap, const AirPeriodicHost* periodic, AirProgramHost& out);
     int build_air_block(const AirDescHost& air, const std::vector<fe>& rap, const AirPeriodicHost* periodic, AirProgramHost& ph,
                         const std::vector<uint32_t>& order, std::initializer_list<std::pair<size_t, size_t*>> extra, AirCompTables& tabs,
@@ -292,6 +304,7 @@ class StarkProver : public sp_deletable {
         // workspace (denominators, batch-inversion scratch, scan block totals); kept across proofs of a shape
         DevBuf<uint8_t> auxp_buf; DevBuf<fe> auxp_ws;
         DevBuf<uint64_t> air_report;             // check_trace_air: per-constraint counters, values and boundary results, one block (AirReport)
+        DevBuf<fe> stride;                       // strided constraints of a program AIR: [E] U, [E] 1 / Z, [E] scratch (E = b x the classes' periods, summed)
         DevBuf<fe> periodic;                     // periodic columns of a program AIR: [b S] tables, [S] values being transformed, [S] scratch (S = sum of the periods)
         DevBuf<uint8_t> fri_chain;               // [state 32 B][L x constants][L x zeta constants][L x roots]
         DevBuf<int> side_flags;                  // [SIDE_FLAGS]

@@ -179,6 +179,14 @@ int air_periodic_tables(hipStream_t st, NttEngine& ntt, fe* vals, fe* ws, fe* ta
     return ntt.lde_coset_major(vals, tab, (int)logp, (int)logb, cnt, p, p << logb);
 }
 
+int air_stride_class_tables(hipStream_t st, NttEngine& ntt, fe* u, fe* z, uint32_t logs, uint32_t offset, uint32_t logn, uint32_t logb, const fe& h) {
+    if (logs > logn || (offset >> logs)) return SP_E_INVALID_ARG;
+    const uint64_t m = (1ull << logn) >> logs;   // n / s: x -> x^m takes the coset h <w_N> to h^m <w_(s b)>, row o to g^(o m)
+    const fe* roots_sb = nullptr;
+    SP_TRY(ntt.roots((int)(logs + logb), &roots_sb));
+    return air_stride_tables(st, u, z, logs, logb, fe_pow_u64(h, m), fe_pow_u64(host_primitive_root((int)logn), offset * m), roots_sb);
+}
+
 // The device form of an AIR's constraint program, and what of the descriptor goes with it: checked against the committed trace, values
 // in slots, the periodic columns' places, the exemptions as both the composition and the trace check use them.
 int StarkProver::build_air_program(const AirDescHost& air, size_t n_rap, const AirPeriodicHost* periodic, AirProgramHost& out) {
@@ -217,8 +225,14 @@ int StarkProver::build_air_program(const AirDescHost& air, size_t n_rap, const A
     prog.n_ops = (uint32_t)dops.size();
     // --- transition exemptions (traits.rs:49-79, evaluator.rs:299-323): distinct non-zero counts; with
     //     num_transition_exemptions == 1 every exempted constraint uses the first of them
+    //     (constraints of a stride class keep their own count and their own roots, below)
+    if (!air_stride_plan(air, n_, out.plan)) { sp_set_error("composition_air: malformed strides of the transition constraints"); return SP_E_INVALID_ARG; }
+    const AirStridePlan& plan = out.plan;
     std::vector<uint32_t> uniq;
-    for (uint32_t e : air.exemptions) if (e > 0 && std::find(uniq.begin(), uniq.end(), e) == uniq.end()) uniq.push_back(e);
+    for (uint32_t k = 0; k < T; ++k) {
+        const uint32_t e = air.exemptions[k];
+        if (plan.cls[k] < 0 && e > 0 && std::find(uniq.begin(), uniq.end(), e) == uniq.end()) uniq.push_back(e);
+    }
     if (uniq.size() > AIR_MAX_EXEMPT_KINDS) { sp_set_error("composition_air: too many distinct exemption counts"); return SP_E_UNSUPPORTED; }
     uint32_t max_ex = 0;
     for (size_t q = 0; q < uniq.size(); ++q) { prog.ex_count[q] = uniq[q]; max_ex = std::max(max_ex, uniq[q]); }
@@ -227,20 +241,48 @@ int StarkProver::build_air_program(const AirDescHost& air, size_t n_rap, const A
     for (uint32_t k = 0; k < T; ++k) {
         const uint32_t e = air.exemptions[k], d = air.degrees[k];
         if (d < 1 || d > f + 1) { sp_set_error("composition_air: transition degree above the composition degree bound"); return SP_E_INVALID_ARG; }
-        if (e) {
+        if (e && plan.cls[k] < 0) {
             size_t idx = air.num_transition_exemptions == 1 ? 0 : (size_t)(std::find(uniq.begin(), uniq.end(), e) - uniq.begin());
             prog.ex_kind[k] = 1 + (uint32_t)idx;
         }
         prog.ex_rows[k] = prog.ex_kind[k] ? prog.ex_count[prog.ex_kind[k] - 1] : 0;   // rows the composition really exempts for this constraint (what the trace check must mirror)
+    }
+    out.ex_eff.assign(prog.ex_rows, prog.ex_rows + T);
+    // --- stride classes: the rows = o (mod s), zerofier x^(n/s) - g^(o n/s); an exemption product per (class, e) over the LAST e rows
+    //     of the progression, o + s (n/s - 1 - t)
+    AirStrideDev& sd = out.sdev;
+    std::memset(&sd, 0, sizeof(sd));
+    out.sroots.clear();
+    out.stab = 0;
+    if (!out.strided()) return SP_OK;
+    sd.n_classes = (uint32_t)plan.classes.size(); sd.n_kinds = (uint32_t)plan.kinds.size();
+    for (uint32_t q = 0; q < sd.n_classes; ++q) {
+        sd.logs[q] = (uint32_t)sp_log2_exact(plan.classes[q].period); sd.off[q] = plan.classes[q].offset;
+        sd.tab_off[q] = out.stab;
+        out.stab += (uint64_t)plan.classes[q].period << logb_;
+    }
+    for (uint32_t j = 0; j < sd.n_kinds; ++j) {
+        const AirStrideHost& c = plan.classes[plan.kinds[j].first];
+        const uint32_t e = plan.kinds[j].second;
+        sd.kind_count[j] = e; sd.kind_root0[j] = (uint32_t)out.sroots.size();
+        for (uint32_t t = 0; t < e; ++t) out.sroots.push_back(fe_pow_u64(g_, c.offset + (uint64_t)c.period * (n_ / c.period - 1 - t)));
+    }
+    for (uint32_t k = 0; k < T; ++k) {
+        if (plan.cls[k] < 0) continue;
+        const AirStrideHost& c = plan.classes[plan.cls[k]];
+        sd.cls[k] = (uint8_t)(1 + plan.cls[k]); sd.kind[k] = (uint8_t)(1 + plan.kind[k]);
+        sd.last[k] = c.offset + (uint64_t)c.period * (n_ / c.period - 1 - air.exemptions[k]);
+        out.ex_eff[k] = air.exemptions[k];
     }
     return SP_OK;
 }
 
 // The part of od_.air_buf that the composition and the trace check share, laid out and filled in h_air_up_ (every region 256-byte
 // aligned): the AirProgram header with its ops / consts pointers set, the slotted ops, the constants followed by the RAP challenges,
-// bvalue / bstep / bcol with constraint order[j] at position j, the periodic descriptors and values; behind them one region per entry
+// bvalue / bstep / bcol with constraint order[j] at position j, the periodic descriptors and values, the stride classes' descriptor
+// (AirStrideDev) and exemption roots; behind them one region per entry
 // of `extra` (its bytes, and where its offset goes), which the caller fills.  od_.air_buf is grown to the whole block; the caller
-// uploads it in one copy.  tabs: T, B, bvalue, bstep, bcol, pcols, pvals set, the rest zero.
+// uploads it in one copy.  tabs: T, B, bvalue, bstep, bcol, pcols, pvals, strides set, the rest zero.
 int StarkProver::build_air_block(const AirDescHost& air, const std::vector<fe>& rap, const AirPeriodicHost* periodic, AirProgramHost& ph,
                                  const std::vector<uint32_t>& order, std::initializer_list<std::pair<size_t, size_t*>> extra,
                                  AirCompTables& tabs, const AirProgram*& prog_dev) {
@@ -252,6 +294,7 @@ int StarkProver::build_air_block(const AirDescHost& air, const std::vector<fe>& 
                  o_consts = lay.place(sizeof(fe) * (air.consts.size() + rap.size())), o_bval = lay.place(sizeof(fe) * B),
                  o_bstep = lay.place(sizeof(uint64_t) * B), o_bcol = lay.place(sizeof(uint32_t) * B),
                  o_pcols = lay.place(sizeof(AirPeriodicCol) * Kp), o_pvals = lay.place(sizeof(fe) * ph.S);
+    const size_t o_sdev = ph.strided() ? lay.place(sizeof(AirStrideDev)) : 0, o_sroots = ph.strided() ? lay.place(sizeof(fe) * ph.sroots.size()) : 0;
     for (const auto& x : extra) *x.second = lay.place(x.first);
     SP_TRY(grow(od_.air_buf, lay.bytes));
     std::vector<uint8_t>& up = h_air_up_;
@@ -280,6 +323,13 @@ int StarkProver::build_air_block(const AirDescHost& air, const std::vector<fe>& 
         tabs.pcols = reinterpret_cast<const AirPeriodicCol*>(dev_at(o_pcols));
         tabs.pvals = reinterpret_cast<const fe*>(dev_at(o_pvals));
     }
+    if (ph.strided()) {   // the class descriptors and the exemption roots (sdev.u / zinv / beta: composition_air, in the upload at ph.o_sdev)
+        ph.o_sdev = o_sdev;
+        ph.sdev.roots = reinterpret_cast<const fe*>(dev_at(o_sroots));
+        std::memcpy(up.data() + o_sdev, &ph.sdev, sizeof(AirStrideDev));
+        if (!ph.sroots.empty()) std::memcpy(up.data() + o_sroots, ph.sroots.data(), sizeof(fe) * ph.sroots.size());
+        tabs.strides = reinterpret_cast<const AirStrideDev*>(dev_at(o_sdev));
+    }
     prog_dev = reinterpret_cast<const AirProgram*>(dev_at(o_prog));
     return SP_OK;
 }
@@ -302,7 +352,8 @@ int StarkProver::composition_air(const AirDescHost& air, const std::vector<fe>& 
     for (uint32_t k = 0; k < T; ++k) {
         // deg C_k <= d (n - 1); times x^(n (f - d + 1)); times the exemption product; over x^n - 1
         const uint32_t d = air.degrees[k];
-        deg_bound = std::max<uint64_t>(deg_bound, (uint64_t)d * (n_ - 1) + n_ * (f - d + 1) + ph.prog.ex_rows[k] - n_ + 1);
+        //   (a strided constraint: times x^(n (f - d) + n/s), over x^(n/s) - g^(o n/s) - the same f n - d + e + 1 coefficients)
+        deg_bound = std::max<uint64_t>(deg_bound, (uint64_t)d * (n_ - 1) + n_ * (f - d + 1) + ph.ex_eff[k] - n_ + 1);
     }
     deg_bound = std::max<uint64_t>(deg_bound, (n_ - 1) + n_ * (f - 1));   // boundary terms
     const bool allow_sub = deg_bound <= 2 * n_;                            // deg H < 2n: 2n evaluations fix it
@@ -339,6 +390,18 @@ int StarkProver::composition_air(const AirDescHost& air, const std::vector<fe>& 
     std::vector<fe> ga(B), gb(B);                              // the boundary coefficients in grouped order
     for (uint32_t jp = 0; jp < B; ++jp) { ga[jp] = b_alpha[order[jp]]; gb[jp] = b_beta[order[jp]]; }
     coset_tables(fe_pow_u64(h_, n_), logb_, f, air.degrees, t_alpha, t_beta, ga, gb, hcoef, nterm, hzf);
+    if (ph.strided()) {
+        // a strided constraint's slot of coef holds alpha_k (x^n)^(f - d_k) per coset - U = x^(n/s) and beta_k join it in the kernel
+        AirStrideDev* hsd = reinterpret_cast<AirStrideDev*>(up.data() + ph.o_sdev);
+        SP_TRY(grow(od_.stride, 3 * ph.stab));
+        hsd->u = od_.stride.p; hsd->zinv = od_.stride.p + ph.stab;
+        const fe wb = host_primitive_root((int)logb_);
+        fe xn = fe_pow_u64(h_, n_);
+        for (uint32_t c = 0; c < b; ++c, xn = fe_mul(xn, wb))
+            for (uint32_t k = 0; k < T; ++k)
+                if (ph.plan.cls[k] >= 0) hcoef[(size_t)c * nterm + k] = fe_mul(t_alpha[k], fe_pow_u64(xn, f - air.degrees[k]));
+        for (uint32_t k = 0; k < T; ++k) if (ph.plan.cls[k] >= 0) hsd->beta[k] = t_beta[k];
+    }
     SP_HIP_CHECK(hipMemcpyAsync(od_.air_buf.p, up.data(), up.size(), hipMemcpyHostToDevice, c_->stream));
     tabs.h = h_; tabs.ndist = nd;
     tabs.zerofier = reinterpret_cast<const fe*>(dev_at(o_zf));
@@ -361,6 +424,21 @@ int StarkProver::composition_air(const AirDescHost& air, const std::vector<fe>& 
             k += cnt;
         }
         tabs.ptab = tab;
+    }
+    if (ph.strided()) {
+        // per class [b][s] U and U - g^(o n/s), all b cosets on every rank (the kernel indexes by the global LDE index); one batch
+        // inversion over all classes, its zero flag looked at before composition_core takes the flag over
+        fe* u = od_.stride.p;
+        fe* z = u + ph.stab;
+        SP_HIP_CHECK(hipMemsetAsync(c_->d_flag, 0, sizeof(int), c_->stream));
+        for (uint32_t q = 0; q < ph.sdev.n_classes; ++q) {
+            SP_TRY(air_stride_class_tables(c_->stream, *c_->ntt, u + ph.sdev.tab_off[q], z + ph.sdev.tab_off[q], ph.sdev.logs[q], ph.sdev.off[q], logn_, logb_, h_));
+        }
+        SP_TRY(batch_inverse(c_->stream, z, z + ph.stab, ph.stab, c_->d_flag));
+        int zero = 0;
+        SP_HIP_CHECK(hipMemcpyAsync(&zero, c_->d_flag, sizeof(int), hipMemcpyDeviceToHost, c_->stream));
+        SP_HIP_CHECK(sp_stream_wait_polling(c_->stream));
+        if (zero) { sp_set_error("composition_air: a stride class's zerofier vanishes on the LDE domain"); return SP_E_ZERO_INVERSE; }
     }
     offsets_ = air.offsets;
     return composition_core(Round2Air{points, nullptr, prog_dev, &tabs, od_.ex_roots.p, allow_sub}, root_out);

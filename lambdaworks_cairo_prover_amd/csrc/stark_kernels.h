@@ -82,6 +82,26 @@ struct AirProgram {
     const AirOpDev* ops;                      // [n_ops]   (device arrays sized by the program, beside this header)
     const fe* consts;                         // constants followed by the RAP challenges
 };
+// Strided transition constraints (sp_air_stride_desc), device form; in device memory beside the program.  Class q: the constraints
+// enforced on the rows = off[q] (mod 2^logs[q]), zerofier x^(n/s) - g^(o n/s).  Its tables are coset-major [b][s] like every LDE
+// column, at u + tab_off[q] and zinv + tab_off[q]: entry (c, j) = U = x^(n/s) resp. 1 / (U - g^(o n/s)) at x = h w_N^(j b + c) - they
+// depend on c and j mod s only.  Exemption product j belongs to class kind_class[j] and is prod_t (x - roots[kind_root0[j] + t]),
+// t < kind_count[j].  Constraint k: cls[k] = 0 for one enforced on every row (it goes through coef / zerofier / ex_kind as without
+// strides), else 1 + its class; kind[k] = 0 or 1 + its exemption product; last[k] = the last row it is enforced on (trace check);
+// beta[k] its beta, its alpha (x^n)^(f - d_k) per coset sits in AirCompTables::coef[c][k].
+constexpr int AIR_MAX_STRIDE_CLASSES_DEV = 4, AIR_MAX_STRIDE_KINDS_DEV = 4;
+struct AirStrideDev {
+    uint32_t n_classes, n_kinds;
+    uint32_t logs[AIR_MAX_STRIDE_CLASSES_DEV], off[AIR_MAX_STRIDE_CLASSES_DEV];
+    uint64_t tab_off[AIR_MAX_STRIDE_CLASSES_DEV];
+    uint32_t kind_count[AIR_MAX_STRIDE_KINDS_DEV], kind_root0[AIR_MAX_STRIDE_KINDS_DEV];
+    uint8_t cls[AIR_MAX_TRANSITIONS], kind[AIR_MAX_TRANSITIONS];
+    uint64_t last[AIR_MAX_TRANSITIONS];
+    fe beta[AIR_MAX_TRANSITIONS];
+    const fe* u;
+    const fe* zinv;
+    const fe* roots;
+};
 struct AirPeriodicCol { uint32_t logp, pad; uint64_t off; };   // off: the periods of the columns before this one, summed
 // Per-proof composition data of a program AIR, in device memory sized by the proof (every lane of a launch reads the same
 // entry: uniform loads).  Boundary constraints are grouped by row: group g holds constraints [gend[g-1], gend[g]) on the row
@@ -104,6 +124,7 @@ struct AirCompTables {
     const AirPeriodicCol* pcols;
     const fe* pvals;
     const fe* ptab;
+    const AirStrideDev* strides;   // null unless some constraint has a period > 1
 };
 // zb[i] = prod_g (x_i - point[g]) over the ndist boundary points (device array), x_i = h w_N^i as coset_minus_points maps
 // i (shard included); the caller inverts it with batch_inverse.  Reference evaluator.rs:56-116 divides every boundary
@@ -119,6 +140,9 @@ int air_composition(hipStream_t st, const fe* lde, uint64_t count, uint64_t col_
                     const fe* roots_N, AirCompTables tabs, const AirProgram* prog_dev, const fe* ex_roots,
                     const fe* zbinv, fe* out, uint32_t shard_log = 0, uint32_t shard_rank = 0);
 // (here and below: tabs.pcols != null selects the instantiation that knows op 6, so a program without periodic columns runs the code it always ran)
+// (likewise tabs.strides != null selects the instantiation that knows strided constraints: per class q, acc_q = sum_{k in q}
+// (coef[c][k] U_q + beta_k) cons[k] E, total += zinv_q acc_q; the trace check and the report then take a constraint's enforced rows
+// from cls / logs / off / last instead of ex_rows)
 // validate_trace (debug.rs:13-104): the transition constraints on every row (a kernel of its own, one thread per row: the exact row
 // evaluation - natural-order columns, frame rows modulo n, op 6 from the periodic VALUES, not the table - then one atomicOr), then the
 // boundary values (one thread per constraint); *flag_dev |= 1 on any violation.  tabs: T, B, bvalue, bcol, bstep, pcols, pvals are read.
@@ -143,6 +167,10 @@ int air_trace_report(hipStream_t st, const fe* trace, uint64_t n, AirCompTables 
 // Table of `cnt` periodic columns of period p = 2^logp <= AIR_PERIODIC_DIRECT_MAX without the transform plans: coef[v][m] = q_v's
 // coefficients from vals[v][.] (one thread per coefficient, p terms each), then tab[v][c][j] = q_v(hq w_(p b)^(j b + c)) by Horner (one
 // thread per entry, p steps).  hq = h^(n/p); roots_pb = NttEngine::roots(logp + logb).  p^2 (1 + b) products per column: 4352 at p = 16, b = 16.
+// The tables of one stride class (AirStrideDev): u[t] = U = hq w_(s b)^(j b + c) and z[t] = U - gpow for t = c s + j < s b, one lane per
+// entry; hq = h^(n/s), gpow = g^(o n/s), roots_sb = NttEngine::roots(logs + logb).  The caller inverts z (batch_inverse, zero flag).
+int air_stride_tables(hipStream_t st, fe* u, fe* z, uint32_t logs, uint32_t logb, const fe& hq, const fe& gpow, const fe* roots_sb);
+
 constexpr uint32_t AIR_PERIODIC_DIRECT_MAX = 16;
 int air_periodic_table_direct(hipStream_t st, const fe* vals, fe* coef, fe* tab, uint32_t cnt, uint32_t logp, uint32_t logb, const fe& hq,
                               const fe* roots_pb);

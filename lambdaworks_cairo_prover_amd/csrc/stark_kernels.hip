@@ -606,7 +606,9 @@ int boundary_vanishing(hipStream_t st, fe* zb, uint64_t N, uint32_t logN, const 
 // PER: the program may read periodic columns (op 6): entry (coset c, (j + offset) mod p) of the column's table, j = iglob / b the
 // trace row of the point - the GLOBAL index, so a sharded context and the strided 2n-point evaluation read the entry of the point
 // they stand on.
-template <bool PER>
+// STR: some constraints are enforced on a row progression only (AirStrideDev): their terms are summed per class and divided by the
+// class's own zerofier, read like a periodic table at (coset c, j mod s).
+template <bool PER, bool STR>
 __global__ void __launch_bounds__(256) air_composition_kernel(const fe* __restrict__ cols, uint64_t count, uint64_t col_len, uint32_t stride_log,
                                                               uint32_t logN, uint32_t logb, const fe* __restrict__ roots,
                                                               const AirCompTables K, const AirProgram* __restrict__ Pg,
@@ -643,14 +645,41 @@ __global__ void __launch_bounds__(256) air_composition_kernel(const fe* __restri
         exv[q] = p;
     }
     const fe* __restrict__ coef = K.coef + (uint64_t)c * (T + B);
+    fe strided = fe_zero();
+    if (STR) {
+        const AirStrideDev* __restrict__ S = K.strides;
+        fe sexv[AIR_MAX_STRIDE_KINDS_DEV];
+        for (uint32_t q = 0; q < S->n_kinds; ++q) {
+            fe p = fe_one();
+            const fe* __restrict__ r = S->roots + S->kind_root0[q];
+            for (uint32_t j = 0; j < S->kind_count[q]; ++j) p = p * (x - fe_ld(r + j));
+            sexv[q] = p;
+        }
+        for (uint32_t q = 0; q < S->n_classes; ++q) {   // one class at a time: a pass over the constraints, no per-class accumulators
+            const uint32_t ls = S->logs[q];
+            const uint64_t at = S->tab_off[q] + ((uint64_t)c << ls) + ((iglob >> logb) & ((1u << ls) - 1u));
+            const fe U = fe_ld(S->u + at);
+            fe a = fe_zero();
+            for (uint32_t k = 0; k < T; ++k) {
+                if (S->cls[k] != q + 1) continue;
+                fe term = (fe_ld(coef + k) * U + fe_ld(S->beta + k)) * cons[k];
+                const uint32_t ek = S->kind[k];
+                if (ek) term = term * sexv[ek - 1];
+                a = a + term;
+            }
+            strided = strided + fe_ld(S->zinv + at) * a;
+        }
+    }
     fe acc = fe_zero();
     for (uint32_t k = 0; k < T; ++k) {
+        if (STR && K.strides->cls[k]) continue;
         fe term = fe_ld(coef + k) * cons[k];
         const uint32_t ek = Pg->ex_kind[k];
         if (ek) term = term * exv[ek - 1];
         acc = acc + term;
     }
     fe total = fe_ld(K.zerofier + c) * acc;
+    if (STR) total = total + strided;
     if (K.ndist) {
         // sum_s S_s / (x - g^s) as A / P over the rows s seen so far: three products per row, one inverse (zbinv) per point
         const uint64_t at = ord.at(e);
@@ -674,10 +703,13 @@ int air_composition(hipStream_t st, const fe* lde, uint64_t count, uint64_t col_
                     const fe* zbinv, fe* out, uint32_t shard_log, uint32_t shard_rank) {
     if ((1u << logb) > CAIRO_MAX_BLOWUP) { sp_set_error("composition: blowup factor > 128 unsupported"); return SP_E_UNSUPPORTED; }
     const dim3 grid((unsigned)((count + 255) / 256));
-    if (tabs.pcols) hipLaunchKernelGGL((air_composition_kernel<true>), grid, dim3(256), 0, st, lde, count, col_len, stride_log, logN, logb, roots_N, tabs, prog_dev,
-                                       ex_roots, zbinv, out, shard_log, shard_rank);
-    else hipLaunchKernelGGL((air_composition_kernel<false>), grid, dim3(256), 0, st, lde, count, col_len, stride_log, logN, logb, roots_N, tabs, prog_dev,
-                            ex_roots, zbinv, out, shard_log, shard_rank);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, lde, count, col_len, stride_log, logN, logb, roots_N, tabs, prog_dev, ex_roots, zbinv, out,
+                           shard_log, shard_rank);
+    };
+    if (tabs.strides) { if (tabs.pcols) launch(air_composition_kernel<true, true>); else launch(air_composition_kernel<false, true>); }
+    else if (tabs.pcols) launch(air_composition_kernel<true, false>);
+    else launch(air_composition_kernel<false, false>);
     SP_HIP_CHECK(hipGetLastError());
     return SP_OK;
 }
@@ -700,7 +732,19 @@ __device__ __forceinline__ void air_eval_row(const fe* __restrict__ cols, uint64
 }
 
 // one thread per trace row: *flag |= 1 if a transition constraint is non-zero on a row it is enforced on
-template <bool PER>
+// Whether constraint k is enforced on row i: rows 0 .. n - 1 - exemptions, or - STR, a constraint of a stride class - the rows of its
+// progression up to its last enforced one.
+template <bool STR>
+__device__ __forceinline__ bool air_row_enforced(const AirCompTables& K, const AirProgram* __restrict__ Pg, uint32_t k, uint64_t i, uint64_t n) {
+    if (STR) {
+        const AirStrideDev* __restrict__ S = K.strides;
+        const uint32_t q = S->cls[k];
+        if (q) return (i & ((1u << S->logs[q - 1]) - 1u)) == S->off[q - 1] && i <= S->last[k];
+    }
+    return i + Pg->ex_rows[k] < n;
+}
+
+template <bool PER, bool STR>
 __global__ void __launch_bounds__(256) air_check_kernel(const fe* __restrict__ trace, uint64_t n, const AirCompTables K, const AirProgram* __restrict__ Pg,
                                                         int* __restrict__ flag) {
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
@@ -709,7 +753,7 @@ __global__ void __launch_bounds__(256) air_check_kernel(const fe* __restrict__ t
     air_eval_row<PER>(trace, n, i, K, Pg, cons);
     bool bad = false;
     for (uint32_t k = 0; k < K.T; ++k)
-        if (i + Pg->ex_rows[k] < n && !fe_is_zero(cons[k])) bad = true;   // enforced on rows 0 .. n - 1 - exemptions
+        if (air_row_enforced<STR>(K, Pg, k, i, n) && !fe_is_zero(cons[k])) bad = true;
     if (bad) atomicOr(flag, 1);
 }
 // one thread per boundary constraint: trace[col][step] == value (validate_trace, debug.rs:88-104)
@@ -721,8 +765,10 @@ __global__ void __launch_bounds__(256) air_boundary_check_kernel(const fe* __res
 
 int air_trace_check(hipStream_t st, const fe* trace, uint64_t n, AirCompTables tabs, const AirProgram* prog_dev, int* flag_dev) {
     const dim3 grid((unsigned)((n + 255) / 256));
-    if (tabs.pcols) hipLaunchKernelGGL((air_check_kernel<true>), grid, dim3(256), 0, st, trace, n, tabs, prog_dev, flag_dev);
-    else hipLaunchKernelGGL((air_check_kernel<false>), grid, dim3(256), 0, st, trace, n, tabs, prog_dev, flag_dev);
+    auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, trace, n, tabs, prog_dev, flag_dev); };
+    if (tabs.strides) { if (tabs.pcols) launch(air_check_kernel<true, true>); else launch(air_check_kernel<false, true>); }
+    else if (tabs.pcols) launch(air_check_kernel<true, false>);
+    else launch(air_check_kernel<false, false>);
     SP_HIP_CHECK(hipGetLastError());
     if (tabs.B) {
         hipLaunchKernelGGL(air_boundary_check_kernel, dim3((tabs.B + 255) / 256), dim3(256), 0, st, trace, n, tabs, flag_dev);
@@ -733,7 +779,7 @@ int air_trace_check(hipStream_t st, const fe* trace, uint64_t n, AirCompTables t
 
 // ---------------------------------------------------------------------------------------------- program AIRs: the report
 // One lane per trace row.  The lanes of the last block beyond row n - 1 run no program and never vote, but stay for the ballots.
-template <bool PER>
+template <bool PER, bool STR>
 __global__ void __launch_bounds__(256) air_report_kernel(const fe* __restrict__ cols, uint64_t n, const AirCompTables K,
                                                          const AirProgram* __restrict__ Pg, const AirReport R) {
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
@@ -743,7 +789,7 @@ __global__ void __launch_bounds__(256) air_report_kernel(const fe* __restrict__ 
     const uint32_t lane = threadIdx.x & 63u;   // (blocks of 256 in one dimension: wave w holds threads 64 w .. 64 w + 63)
     const uint64_t row0 = i - lane;
     for (uint32_t k = 0; k < K.T; ++k) {
-        const bool bad = live && i + Pg->ex_rows[k] < n && !fe_is_zero(cons[k]);   // enforced on rows 0 .. n - 1 - exemptions
+        const bool bad = live && air_row_enforced<STR>(K, Pg, k, i, n) && !fe_is_zero(cons[k]);
         const unsigned long long m = __ballot(bad);
         const uint32_t lo = m ? (uint32_t)__ffsll(m) - 1u : 64u;
         if (lane == lo) {                      // the lowest voter speaks for the wave; no voter, no atomic
@@ -779,18 +825,39 @@ __global__ void __launch_bounds__(256) air_boundary_report_kernel(const fe* __re
 int air_trace_report(hipStream_t st, const fe* trace, uint64_t n, AirCompTables tabs, const AirProgram* prog_dev, AirReport report) {
     if (n == 0 || (n & (n - 1)) || tabs.T == 0 || tabs.T > (uint32_t)AIR_MAX_TRANSITIONS) return SP_E_INVALID_ARG;
     const dim3 grid((unsigned)((n + 255) / 256));
-    if (tabs.pcols) {
-        hipLaunchKernelGGL((air_report_kernel<true>), grid, dim3(256), 0, st, trace, n, tabs, prog_dev, report);
-        hipLaunchKernelGGL((air_report_value_kernel<true>), dim3(1), dim3(64), 0, st, trace, n, tabs, prog_dev, report);
-    } else {
-        hipLaunchKernelGGL((air_report_kernel<false>), grid, dim3(256), 0, st, trace, n, tabs, prog_dev, report);
-        hipLaunchKernelGGL((air_report_value_kernel<false>), dim3(1), dim3(64), 0, st, trace, n, tabs, prog_dev, report);
-    }
+    auto launch = [&](auto rows, auto values) {   // (the value kernel evaluates the row the row kernel found: it needs no rule of its own)
+        hipLaunchKernelGGL(rows, grid, dim3(256), 0, st, trace, n, tabs, prog_dev, report);
+        hipLaunchKernelGGL(values, dim3(1), dim3(64), 0, st, trace, n, tabs, prog_dev, report);
+    };
+    if (tabs.strides) {
+        if (tabs.pcols) launch(air_report_kernel<true, true>, air_report_value_kernel<true>);
+        else launch(air_report_kernel<false, true>, air_report_value_kernel<false>);
+    } else if (tabs.pcols) launch(air_report_kernel<true, false>, air_report_value_kernel<true>);
+    else launch(air_report_kernel<false, false>, air_report_value_kernel<false>);
     SP_HIP_CHECK(hipGetLastError());
     if (tabs.B) {
         hipLaunchKernelGGL(air_boundary_report_kernel, dim3((tabs.B + 255) / 256), dim3(256), 0, st, trace, n, tabs, report);
         SP_HIP_CHECK(hipGetLastError());
     }
+    return SP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- strided constraints: a class's tables
+// one lane per entry t = c s + j of the coset-major [b][s] tables
+__global__ void __launch_bounds__(256) air_stride_table_kernel(fe* __restrict__ u, fe* __restrict__ z, uint32_t total, uint32_t logs, uint32_t logb,
+                                                               const fe* __restrict__ roots_sb, const fe hq, const fe gpow) {
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= total) return;
+    const uint32_t j = t & ((1u << logs) - 1u), c = t >> logs;
+    const fe U = root_pow(roots_sb, (j << logb) + c, logs + logb) * hq;
+    fe_st(u + t, U);
+    fe_st(z + t, U - gpow);
+}
+int air_stride_tables(hipStream_t st, fe* u, fe* z, uint32_t logs, uint32_t logb, const fe& hq, const fe& gpow, const fe* roots_sb) {
+    if (logb < 1 || logs + logb > 31) return SP_E_INVALID_ARG;
+    const uint32_t total = 1u << (logs + logb);
+    hipLaunchKernelGGL(air_stride_table_kernel, dim3((total + 255) / 256), dim3(256), 0, st, u, z, total, logs, logb, roots_sb, hq, gpow);
+    SP_HIP_CHECK(hipGetLastError());
     return SP_OK;
 }
 

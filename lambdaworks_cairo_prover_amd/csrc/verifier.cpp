@@ -216,6 +216,7 @@ struct VerifySpec {
     // periodic: for every frame row r the values P_k(z g^offsets[r]) of the AIR's periodic columns, [rows][periodic_coeffs.size()]
     std::function<void(const fe* frame /*[rows][C]*/, const fe* periodic, const std::vector<fe>& rap, fe* out)> transition;
     std::vector<std::vector<fe>> periodic_coeffs;   // q of every periodic column (air_periodic_interpolate)
+    std::vector<AirStrideHost> strides;             // per transition constraint; empty: every constraint on every row
 };
 
 // the primitive root of unity of order 2^order (lambdaworks get_primitive_root_of_unity): the field's 2^192-th root, squared down
@@ -307,11 +308,22 @@ static int verify_host(const uint8_t* proof_bytes, size_t len, const VerifySpec&
         fe zf = fe_inv(zden);
         // transition_exemptions_verifier (traits.rs:97-118): ex_e(z) = prod_{i=1..e} (z - g^(n-i))
         uint32_t max_ex = 0;
-        for (uint32_t e : air.exemptions) max_ex = std::max(max_ex, e);
+        for (uint32_t c = 0; c < T; ++c)
+            if (air.strides.empty() || air.strides[c].period == 1) max_ex = std::max(max_ex, air.exemptions[c]);
         std::vector<fe> ex(max_ex + 1, fe_one());
         for (uint32_t e = 1; e <= max_ex; ++e) ex[e] = fe_mul(ex[e - 1], fe_sub(z, fe_pow_u64(g, n - e)));
         fe sum = fe_zero();
         for (uint32_t c = 0; c < T; ++c) {
+            if (!air.strides.empty() && air.strides[c].period > 1) {
+                // enforced on the rows = offset (mod period) only: its own zerofier, exemption product and z^(n (f - deg) + n / period)
+                const uint32_t s = air.strides[c].period;
+                fe Z, E;
+                air_stride_eval(s, air.strides[c].offset, air.exemptions[c], n, z, Z, E);
+                if (fe_is_zero(Z)) return 0;
+                const fe adj = fe_mul(fe_pow_u64(zn, f - air.degrees[c]), fe_pow_u64(z, n / s));
+                sum = fe_add(sum, fe_mul(fe_mul(fe_mul(fe_inv(Z), cons[c]), fe_add(fe_mul(ta[c], adj), tb[c])), E));
+                continue;
+            }
             fe adj = fe_pow_u64(zn, f - air.degrees[c] + 1);   // z^(D - n (deg - 1))
             fe term = fe_mul(fe_mul(zf, cons[c]), fe_add(fe_mul(ta[c], adj), tb[c]));
             term = fe_mul(term, ex[air.exemptions[c]]);
@@ -417,6 +429,7 @@ int air_verify_host(const uint8_t* proof_bytes, size_t len, const AirDescHost& a
     for (uint32_t k = 0; k < Kp; ++k) spec.periodic_coeffs.push_back(air_periodic_interpolate(periodic->cols[k]));
     spec.main_cols = air.main_cols; spec.aux_cols = air.aux_cols; spec.offsets = air.offsets; spec.degrees = air.degrees; spec.exemptions = air.exemptions;
     spec.bound_factor = air.degree_bound_factor; spec.n_rap = air.n_rap;
+    spec.strides = air.strides;   // checked against the proof's trace length where they were read (air_strides_from_c)
     spec.boundary = [&air](const std::vector<fe>&) { return air.boundary; };
     spec.transition = [&ops, &consts, C, T, Kp](const fe* frame, const fe* per, const std::vector<fe>& rap, fe* out) {
         std::vector<fe> v(ops.size(), fe_zero());
@@ -472,6 +485,51 @@ fe air_periodic_eval(const std::vector<fe>& coeffs, uint64_t n, const fe& point)
     fe acc = fe_zero();
     for (size_t m = coeffs.size(); m-- > 0;) acc = fe_add(fe_mul(acc, y), coeffs[m]);
     return acc;
+}
+
+bool air_stride_plan(const AirDescHost& air, uint64_t n, AirStridePlan& out) {
+    const size_t T = air.exemptions.size();
+    out = AirStridePlan{};
+    out.cls.assign(T, -1); out.kind.assign(T, -1);
+    if (air.strides.empty()) return true;
+    if (air.strides.size() != T) return false;
+    for (size_t k = 0; k < T; ++k) {
+        const uint32_t s = air.strides[k].period, o = air.strides[k].offset, e = air.exemptions[k];
+        if (s == 0 || (s & (s - 1)) || s > n || o >= s) return false;
+        if (s == 1) continue;
+        // C_k / Z_k has degree d n - n/s: the adjustment x^(n (f - d) + n/s) exists for d <= f only (a (1, 0) constraint may have d = f + 1)
+        if (e >= n / s || k >= air.degrees.size() || air.degrees[k] > air.degree_bound_factor) return false;
+        size_t q = 0;
+        while (q < out.classes.size() && (out.classes[q].period != s || out.classes[q].offset != o)) ++q;
+        if (q == out.classes.size()) {
+            if (q == AIR_MAX_STRIDE_CLASSES) return false;
+            out.classes.push_back(air.strides[k]);
+        }
+        out.cls[k] = (int)q;
+        if (!e) continue;
+        const std::pair<uint32_t, uint32_t> want((uint32_t)q, e);
+        size_t j = 0;
+        while (j < out.kinds.size() && out.kinds[j] != want) ++j;
+        if (j == out.kinds.size()) {
+            if (j == AIR_MAX_STRIDE_EXEMPT_KINDS) return false;
+            out.kinds.push_back(want);
+        }
+        out.kind[k] = (int)j;
+    }
+    return true;
+}
+
+void air_stride_eval(uint32_t s, uint32_t o, uint32_t e, uint64_t n, const fe& x, fe& Z, fe& E) {
+    const uint64_t m = n / s;                       // rows of the progression
+    const fe g = root_of(sp_log2_exact(n));
+    Z = fe_sub(fe_pow_u64(x, m), fe_pow_u64(g, (uint64_t)o * m));
+    E = fe_one();
+    const fe gs_inv = fe_inv(fe_pow_u64(g, s));
+    fe root = fe_pow_u64(g, o + (uint64_t)s * (m - 1));   // the last row of the progression, then s rows down at a time
+    for (uint32_t t = 0; t < e; ++t) {
+        E = fe_mul(E, fe_sub(x, root));
+        root = fe_mul(root, gs_inv);
+    }
 }
 
 size_t air_program_first_bad_op(const std::vector<AirOpHost>& ops, uint32_t load_a_end, uint32_t load_b_end, size_t n_values, uint32_t n_out,

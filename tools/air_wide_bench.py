@@ -4,10 +4,14 @@ grinding 20, 64 transition constraints each tying together 4 column recurrences,
 timed proofs on one GPU; prints one JSON line: the median and sp_last_round_ms of the last proof (rounds 1 - 4, device time).
 --periodic K --period P: the same shape with K periodic columns of period P (sp_air_prove_periodic): column j < K counts up by
 k_j + Q_j(i mod P), so its recurrence reads periodic column j, and the boundary values follow the changed trace.
+--stride K: every second constraint (1, 3, ...) enforced on the rows = 0 (mod K) only (sp_air_prove_ext; one stride class).  The trace
+is the same - it satisfies them on every row -, so the figure prices the class's tables and the strided terms of the composition.
+proof_sha256 lets two builds be held against each other byte for byte.
 
-    python tools/air_wide_bench.py [--boundary-rows 64] [--reps 5] [--log-n 18] [--periodic 8 --period 64]
+    python tools/air_wide_bench.py [--boundary-rows 64] [--reps 5] [--log-n 18] [--periodic 8 --period 64] [--stride 8]
 """
 import argparse
+import hashlib
 import json
 import os
 import statistics
@@ -60,6 +64,7 @@ def main():
     ap.add_argument("--log-n", type=int, default=18)
     ap.add_argument("--periodic", type=int, default=0, help="periodic columns read by the first recurrences (0: the plain shape)")
     ap.add_argument("--period", type=int, default=64)
+    ap.add_argument("--stride", type=int, default=0, help="put every second constraint on the rows = 0 (mod K) (0: none)")
     args = ap.parse_args()
     n, cols, options = 1 << args.log_n, 256, (4, 80, 3, 20)
     if args.periodic:
@@ -67,6 +72,8 @@ def main():
     else:
         b = M.build(n, cols, n_transitions=64, boundary_row_count=args.boundary_rows, boundary_total=512)
         trace = M.main_trace(n, cols)
+    if args.stride:
+        b.strides = [(args.stride, 0) if k % 2 else (1, 0) for k in range(len(b.degrees))]
     desc, keep = b.build()
     opt = api.ProofOptions(*options)
     with api.Context(device=0) as ctx:
@@ -81,8 +88,8 @@ def main():
         rounds = ctx.last_round_ms()
     print(json.dumps({"tool": "air_wide_bench", "rows": n, "main_cols": cols, "transitions": len(b.degrees), "ops": len(b.ops),
                       "constants": len(b.consts), "boundary_constraints": len(b.bcs), "boundary_rows": args.boundary_rows,
-                      "periodic_columns": args.periodic, "period": args.period if args.periodic else 0,
-                      "options": options, "proof_bytes": len(proof), "median_ms": round(statistics.median(times), 2),
+                      "periodic_columns": args.periodic, "period": args.period if args.periodic else 0, "stride": args.stride,
+                      "options": options, "proof_bytes": len(proof), "proof_sha256": hashlib.sha256(proof).hexdigest(), "median_ms": round(statistics.median(times), 2),
                       "min_ms": round(min(times), 2), "max_ms": round(max(times), 2), "last_round_ms": [round(x, 2) for x in rounds[1:]]}))
 
 
