@@ -77,7 +77,8 @@ const char* sp_version(void);
  * sp_air_aux_desc_size, sp_air_prove_periodic, sp_air_verify_periodic, sp_air_periodic_desc_size, sp_air_periodic_limits,
  * sp_air_periodic_eval, sp_air_periodic_lde; sp_air_check_trace and sp_air_violation_size joined under 7 - they change no structure
  * and no call, and a binding finds a build without them by probing the symbols; so did sp_air_prove_ext, sp_air_verify_ext, sp_air_check_trace_ext,
- * sp_air_stride_size, sp_air_stride_desc_size, sp_air_ext_size, sp_air_stride_limits, sp_air_stride_eval and sp_air_stride_table).  A binding compares it (and sp_air_desc_size against its own idea of the struct) when it loads the library, so
+ * sp_air_stride_size, sp_air_stride_desc_size, sp_air_ext_size, sp_air_stride_limits, sp_air_stride_eval and sp_air_stride_table, and after them sp_air_prove_pub, sp_air_verify_pub,
+ * sp_air_check_trace_pub, sp_air_boundary_desc_size and sp_air_boundary_resolve).  A binding compares it (and sp_air_desc_size against its own idea of the struct) when it loads the library, so
  * a stale build fails at load time with "rebuild the library" instead of with a missing symbol or shifted fields later. */
 #define SP_ABI_VERSION 7
 int sp_abi_version(void);
@@ -470,7 +471,8 @@ uint64_t sp_air_aux_desc_size(void);
  * the composition polynomial do not change.  The columns are NOT committed and do not enter the transcript, the proof format is
  * unchanged: like the program's constants they are part of the statement prover and verifier both hold.  sp_air_prove,
  * sp_air_prove_aux, sp_air_verify and sp_air_verify_backend answer a program that contains op 6 as they answer any unknown op
- * (SP_E_INVALID_ARG / 0); an auxiliary program (sp_air_aux_desc) cannot read periodic columns and is refused the same way. */
+ * (SP_E_INVALID_ARG / 0); an auxiliary program (sp_air_aux_desc) cannot read periodic columns and is refused the same way (only
+ * sp_air_prove_pub and its siblings below let it). */
 #define SP_AIR_OP_PERIODIC 6
 typedef struct { uint32_t period, pad; const uint8_t* values; /* period x 32, canonical BE */ } sp_air_periodic_column;
 typedef struct { uint32_t n_cols, pad; const sp_air_periodic_column* cols; } sp_air_periodic_desc;
@@ -571,6 +573,42 @@ int sp_air_check_trace_ext(sp_ctx* ctx, const sp_air_desc* air, const sp_air_ext
 int sp_air_stride_eval(uint32_t period, uint32_t offset, uint32_t exemptions, uint64_t n, const uint8_t point[32], uint8_t out_z[32],
                        uint8_t out_e[32]);
 int sp_air_stride_table(sp_ctx* ctx, uint32_t period, uint32_t offset, uint64_t n, uint32_t blowup, const uint8_t coset[32], uint8_t* out);
+
+/* Public data inside a randomized (RAP) argument, through the three _pub calls below only.
+ *
+ * (1) The auxiliary program of ext->aux may read the periodic columns of ext->periodic - a LogUp lookup against a public table, an
+ *     S-box, an opcode table:
+ *   op 6 PERIODIC  a = row shift s (0 .. 7), b = periodic column of ext->periodic: values[(i + s) mod period] on row i
+ * An op 6 with b >= ext->periodic->n_cols, or without ext->periodic, is malformed.  sp_air_prove_aux / _periodic / _ext keep refusing
+ * op 6 in an auxiliary program.
+ *
+ * (2) Boundary values computed from the RAP challenges (reference traits.rs:44-47, `boundary_constraints(&self, rap_challenges)`).  A
+ *     straight-line program in the sp_air_op encoding: CONST (indices >= n_consts are the RAP challenges), ADD, SUB, MUL only.  Entry j
+ *     replaces air->boundary[values[j].boundary].value by N / D (D = 1 for SP_AIR_AUX_NO_DEN) once the challenges exist.
+ * Bounds: those of sp_air_limits (65535 ops, 4096 constants, constants + RAP challenges <= 65535).  Malformed - null members, an op
+ * other than 1 .. 4, an operand that is not an earlier op, boundary >= air->n_boundary, the same boundary named twice, num_op / den_op
+ * beyond the program - is SP_E_INVALID_ARG from the prover and the trace check and 0 from the verifier, before anything is sized from
+ * it.  A D that evaluates to zero is SP_E_ZERO_INVERSE from the prover and the trace check and 0 from the verifier.  Nothing of this
+ * enters the transcript; the proof format is unchanged.
+ *
+ * With bvals == NULL and an auxiliary program without op 6 the three calls are sp_air_prove_ext / _verify_ext / _check_trace_ext: the
+ * same bytes, verdicts and error codes. */
+typedef struct { uint32_t boundary, num_op, den_op, pad; } sp_air_boundary_value;
+typedef struct {
+    uint32_t n_ops; const sp_air_op* ops;
+    uint32_t n_consts; const uint8_t* consts;   /* canonical BE */
+    uint32_t n_values; const sp_air_boundary_value* values;
+} sp_air_boundary_desc;
+uint64_t sp_air_boundary_desc_size(void);
+int sp_air_prove_pub(sp_ctx* ctx, const sp_air_desc* air, const sp_air_ext* ext, const sp_air_boundary_desc* bvals, const uint8_t* main_trace,
+                     uint64_t n, const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len);
+int sp_air_verify_pub(const uint8_t* proof, uint64_t proof_len, const sp_air_desc* air, const sp_air_ext* ext, const sp_air_boundary_desc* bvals,
+                      const sp_proof_options* opt, int merkle_backend);
+int sp_air_check_trace_pub(sp_ctx* ctx, const sp_air_desc* air, const sp_air_ext* ext, const sp_air_boundary_desc* bvals, const uint8_t* main_trace,
+                           uint64_t n, const sp_proof_options* opt, const uint8_t* rap, sp_air_violation* out, uint32_t cap, uint32_t* n_out);
+/* Test seam (host): out[j] = the resolved value of values[j], canonical BE; rap = n_rap x 32 bytes, canonical BE.  The `boundary` members
+ * are only held against each other here (no AIR to hold them against). */
+int sp_air_boundary_resolve(const sp_air_boundary_desc* bvals, const uint8_t* rap, uint32_t n_rap, uint8_t* out);
 
 /* verify::<Stark252PrimeField, A> (reference src/starks/verifier.rs:559-657) on the host CPU: 1 accept, 0 reject (also for
  * malformed proofs or descriptors). */

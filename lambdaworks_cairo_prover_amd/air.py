@@ -16,6 +16,11 @@ column k at frame row `row`.  In a constraint's declared degree such a value cou
 Strided constraints (another extension): b.constraint(value, degree, exemptions, period=4, offset=1) enforces the constraint on the rows
 = 1 (mod 4) only, dividing by that progression's own zerofier instead of multiplying by a selector column: the declared degree stays
 the constraint's own.  `exemptions` then counts the last rows of the progression.  See strided_mimc_chain below.
+
+Public data inside a randomized (RAP) argument (sp_air_prove_pub): b.aux.table(shift, k) reads periodic column k from the auxiliary
+program - the public table of a LogUp lookup -, and b.boundary_from(col, step, num, den) declares a boundary constraint whose value is
+N / D of b.public, a small program over constants and the RAP challenges: the reference's boundary_constraints(rap_challenges).  See
+table_lookup and public_permutation below.
 """
 import collections
 import ctypes
@@ -140,6 +145,55 @@ def ext_of(desc):
     return x
 
 
+class AirBoundaryValueC(ctypes.Structure):
+    _fields_ = [("boundary", ctypes.c_uint32), ("num_op", ctypes.c_uint32), ("den_op", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
+
+
+class AirBoundaryDescC(ctypes.Structure):
+    _fields_ = [("n_ops", ctypes.c_uint32), ("ops", ctypes.POINTER(AirOpC)),
+                ("n_consts", ctypes.c_uint32), ("consts", ctypes.c_void_p),
+                ("n_values", ctypes.c_uint32), ("values", ctypes.POINTER(AirBoundaryValueC))]
+
+
+def _check_boundary_layout():
+    from . import _lib
+    lib = _lib.load()
+    lib.sp_air_boundary_desc_size.restype = ctypes.c_uint64
+    want = lib.sp_air_boundary_desc_size()
+    if ctypes.sizeof(AirBoundaryDescC) != want:
+        raise ImportError(f"AirBoundaryDescC is {ctypes.sizeof(AirBoundaryDescC)} bytes, the library's sp_air_boundary_desc {want}: the binding is out of date")
+
+
+def boundary_desc(ops, consts, values):
+    """ops [(op, a, b), ...] as the library reads them, consts [int, ...], values [(boundary, num_op, den_op), ...] ->
+    (AirBoundaryDescC, keepalive): sp_air_boundary_desc."""
+    _check_boundary_layout()
+    c_ops = (AirOpC * max(1, len(ops)))()
+    for i, (op, a, b) in enumerate(ops):
+        c_ops[i].op, c_ops[i].a, c_ops[i].b = op, a, b
+    c_consts = ctypes.create_string_buffer(b"".join((int(c) % P).to_bytes(32, "big") for c in consts), max(1, 32 * len(consts)))
+    c_values = (AirBoundaryValueC * max(1, len(values)))()
+    for j, (boundary, num_op, den_op) in enumerate(values):
+        c_values[j].boundary, c_values[j].num_op, c_values[j].den_op = boundary, num_op, den_op
+    d = AirBoundaryDescC()
+    d.n_ops, d.ops = len(ops), ctypes.cast(c_ops, ctypes.POINTER(AirOpC))
+    d.n_consts, d.consts = len(consts), ctypes.cast(c_consts, ctypes.c_void_p)
+    d.n_values, d.values = len(values), ctypes.cast(c_values, ctypes.POINTER(AirBoundaryValueC))
+    return d, (c_ops, c_consts, c_values)
+
+
+def needs_pub(desc):
+    """Whether a built descriptor needs the _pub entry points: it carries boundary values computed from the challenges
+    (desc.boundary_desc), or its auxiliary program reads a periodic column (op 6)."""
+    if getattr(desc, "boundary_desc", None) is not None:
+        return True
+    aux = getattr(desc, "aux_desc", None)
+    if aux is None:
+        return False
+    known = getattr(desc, "aux_reads_table", None)   # (AirBuilder.build() says so; a descriptor put together by hand is looked through)
+    return any(aux.ops[i].op == OP_PERIODIC for i in range(aux.n_ops)) if known is None else known
+
+
 class AirViolationC(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_uint32), ("index", ctypes.c_uint32), ("rows", ctypes.c_uint64), ("first_row", ctypes.c_uint64),
                 ("last_row", ctypes.c_uint64), ("value", ctypes.c_uint8 * 32)]
@@ -196,8 +250,9 @@ class AuxProgram:
     device.  load(shift, col) reads main column `col` of row (i + shift) mod n; product(N, D) and running_sum(N, D) each declare the
     next auxiliary column: z_0 = 1, z_i = z_(i-1) N(i-1) / D(i-1), or z_0 = 0, z_i = z_(i-1) + N(i-1) / D(i-1) (D = 1 when None)."""
 
-    def __init__(self, main_cols, n_rap):
+    def __init__(self, main_cols, n_rap, periodic_cols=()):
         self.main_cols, self.n_rap = main_cols, n_rap
+        self.periodic_cols = periodic_cols   # the owning AirBuilder's periodic columns: what table() may read
         self.ops, self.consts, self.cols = [], [], []
         self._const_at = {}
 
@@ -228,6 +283,18 @@ class AuxProgram:
         raise ValueError("aux program: an auxiliary program cannot read periodic columns (sp_air_prove_periodic refuses op 6 there); "
                          "only the constraint program can")
 
+    def table(self, shift, k):
+        """Periodic column k of the owning AirBuilder on row (i + shift): values[(i + shift) mod period] - the public table of a lookup.
+        Op 6 in an auxiliary program, which only sp_air_prove_pub and its siblings take."""
+        if not 0 <= shift <= AUX_MAX_SHIFT:
+            raise ValueError(f"aux program: row shift {shift} outside 0 .. {AUX_MAX_SHIFT}")
+        if not 0 <= k < len(self.periodic_cols):
+            raise ValueError(f"aux program: column {k} is not one of the AIR's {len(self.periodic_cols)} periodic columns")
+        return self._emit(OP_PERIODIC, shift, k)
+
+    def reads_table(self):
+        return any(op == OP_PERIODIC for op, _, _ in self.ops)
+
     def _column(self, kind, num, den):
         num = num if isinstance(num, Value) else self.const(num)
         if den is not None and not isinstance(den, Value):
@@ -244,10 +311,11 @@ class AuxProgram:
         """The ops as the library reads them: RAP challenges follow the constants."""
         return [(op, len(self.consts) + (a & ~_RAP_TAG) if op == OP_CONST and a & _RAP_TAG else a, b) for op, a, b in self.ops]
 
-    def evaluate(self, rows, rap):
+    def evaluate(self, rows, rap, periodic=None):
         """The auxiliary columns in Python integers (the semantics of sp_air_prove_aux): rows = n x main_cols field elements (any
         sequence of rows, or a numpy array of Python ints); returns an (n, len(cols)) numpy object array.  Each op is one vectorised
-        numpy operation over all rows; the inverses are one batch inversion; the scans run row by row."""
+        numpy operation over all rows; the inverses are one batch inversion; the scans run row by row.  periodic: the columns table()
+        reads, one list of values each (None: those of the owning AirBuilder)."""
         import numpy as np
         m = np.empty((len(rows), self.main_cols), dtype=object)
         m[:, :] = rows if not isinstance(rows, np.ndarray) else rows.astype(object)
@@ -265,6 +333,9 @@ class AuxProgram:
                 v = (vals[a] - vals[b]) % P
             elif op == OP_MUL:
                 v = (vals[a] * vals[b]) % P
+            elif op == OP_PERIODIC:
+                values = (self.periodic_cols if periodic is None else periodic)[b]
+                v = np.array([int(x) % P for x in values], dtype=object)[(np.arange(n) + a) % len(values)]
             else:
                 raise ValueError(f"aux program: op {op}")
             vals.append(v)
@@ -304,6 +375,53 @@ def _batch_inverse(xs):
     return out
 
 
+class PublicProgram:
+    """Values computed from constants and the RAP challenges alone (sp_air_boundary_desc): const(v), rap(i) and + - * through Value.
+    AirBuilder.boundary_from names two of them as the N and D of a boundary value."""
+
+    def __init__(self, n_rap):
+        self.n_rap = n_rap
+        self.ops, self.consts = [], []
+        self._const_at = {}
+
+    def _emit(self, op, a, b):
+        self.ops.append((op, a, b))
+        return Value(self, len(self.ops) - 1)
+
+    def const(self, v):
+        v %= P
+        if v not in self._const_at:
+            self._const_at[v] = len(self.consts)
+            self.consts.append(v)
+        return self._emit(OP_CONST, self._const_at[v], 0)
+
+    def rap(self, i):
+        if not 0 <= i < self.n_rap:
+            raise ValueError(f"public values: RAP challenge {i} of {self.n_rap}")
+        return self._emit(OP_CONST, _RAP_TAG | i, 0)
+
+    def resolved_ops(self):
+        """The ops as the library reads them: RAP challenges follow the constants."""
+        return [(op, len(self.consts) + (a & ~_RAP_TAG) if op == OP_CONST and a & _RAP_TAG else a, b) for op, a, b in self.ops]
+
+    def evaluate(self, rap):
+        """Every op's value in Python integers."""
+        values = list(self.consts) + [int(r) % P for r in rap]
+        vals = []
+        for op, a, b in self.resolved_ops():
+            if op == OP_CONST:
+                vals.append(values[a])
+            elif op == OP_ADD:
+                vals.append((vals[a] + vals[b]) % P)
+            elif op == OP_SUB:
+                vals.append((vals[a] - vals[b]) % P)
+            elif op == OP_MUL:
+                vals.append((vals[a] * vals[b]) % P)
+            else:
+                raise ValueError(f"public values: op {op}")
+        return vals
+
+
 def trace_to_ints(trace):
     """(n, cols, 32) canonical big-endian bytes -> (n, cols) numpy object array of Python ints."""
     import numpy as np
@@ -338,7 +456,10 @@ class AirBuilder:
         self.ops, self.consts, self.degrees, self.exemptions, self.bcs = [], [], [], [], []
         self.strides = []   # per constraint (period, offset): enforced on the rows = offset (mod period)
         # aux_kind AUX_PROGRAM: the auxiliary columns as a program over the main-trace row (sp_air_prove_aux)
-        self.aux = AuxProgram(main_cols, n_rap) if aux_kind == AUX_PROGRAM else None
+        self.aux = AuxProgram(main_cols, n_rap, self.periodic_cols) if aux_kind == AUX_PROGRAM else None
+        # boundary values computed from the RAP challenges (sp_air_boundary_desc): the program, and per value (index into bcs, N, D)
+        self.public = PublicProgram(n_rap)
+        self.bvalues = []
 
     def _emit(self, op, a, b):
         self.ops.append((op, a, b))
@@ -383,6 +504,41 @@ class AirBuilder:
     def boundary(self, col, step, value):
         self.bcs.append((col, step, value % P))
 
+    def boundary_from(self, col, step, num, den=None):
+        """A boundary constraint whose value is N / D of b.public (D = 1 when None): known once the RAP challenges are - the reference's
+        boundary_constraints(rap_challenges).  The descriptor holds 0 in its place; sp_air_prove_pub and its siblings put the value in."""
+        num = num if isinstance(num, Value) else self.public.const(num)
+        if den is not None and not isinstance(den, Value):
+            den = self.public.const(den)
+        if num.b is not self.public or (den is not None and den.b is not self.public):
+            raise ValueError("boundary_from: N and D must be values of b.public")
+        self.bvalues.append((len(self.bcs), num.i, AUX_NO_DEN if den is None else den.i))
+        self.bcs.append((col, step, 0))
+
+    def resolve_boundary(self, rap):
+        """The values of the boundary_from constraints under these challenges, in the order they were declared (Python integers: the
+        model of sp_air_boundary_resolve).  ValueError when a D is zero (SP_E_ZERO_INVERSE there)."""
+        rap = [int(r) % P for r in rap]
+        if len(rap) != self.n_rap:
+            raise ValueError(f"resolve_boundary: {len(rap)} RAP challenges for an AIR with n_rap = {self.n_rap}")
+        vals = self.public.evaluate(rap)
+        out = []
+        for _, num_op, den_op in self.bvalues:
+            if den_op == AUX_NO_DEN:
+                out.append(vals[num_op])
+                continue
+            if vals[den_op] == 0:
+                raise ValueError("resolve_boundary: a denominator is zero")
+            out.append(vals[num_op] * pow(vals[den_op], P - 2, P) % P)
+        return out
+
+    def resolved_bcs(self, rap):
+        """bcs with the boundary_from values put in."""
+        bcs = list(self.bcs)
+        for (j, _, _), value in zip(self.bvalues, self.resolve_boundary(rap) if self.bvalues else []):
+            bcs[j] = (bcs[j][0], bcs[j][1], value)
+        return bcs
+
     def enforced_exemptions(self):
         """Per constraint, the number of last rows it is not enforced on - what the composition uses: its own exemption count, or,
         with num_transition_exemptions == 1, the first non-zero count of the AIR for every constraint that has one."""
@@ -407,8 +563,8 @@ class AirBuilder:
         validate_trace, src/starks/debug.rs:13-104).  rows: (n, main_cols + aux_cols) ints, main||aux; with an aux program also
         (n, main_cols), to which self.aux.evaluate(rows, rap) is appended.  rap: the RAP challenges.  Constraint k is enforced on rows
         0 .. n - 1 - enforced_exemptions()[k] - with a period > 1 on enforced_rows(k, n), its progression without that many of its last
-        rows; frame rows wrap modulo n.  Returns [Violation, ...]: the transition constraints by
-        index, then the boundary constraints by index; [] for a trace that satisfies the AIR."""
+        rows; frame rows wrap modulo n.  Boundary values declared with boundary_from are resolved under `rap` first.  Returns
+        [Violation, ...]: the transition constraints by index, then the boundary constraints by index; [] for a trace that satisfies the AIR."""
         import numpy as np
         m = np.empty((len(rows), len(rows[0])), dtype=object)
         m[:, :] = rows if not isinstance(rows, np.ndarray) else rows.astype(object)
@@ -451,7 +607,7 @@ class AirBuilder:
             bad = [i for i in self.enforced_rows(k, n) if outs[k][i] != 0]
             if bad:
                 found.append(Violation(TRANSITION, k, len(bad), bad[0], bad[-1], int(outs[k][bad[0]])))
-        for j, (col, step, value) in enumerate(self.bcs):
+        for j, (col, step, value) in enumerate(self.resolved_bcs(rap)):
             if int(m[step, col]) != value:
                 found.append(Violation(BOUNDARY, j, 1, step, step, int(m[step, col])))
         return found
@@ -491,6 +647,12 @@ class AirBuilder:
                     raise ValueError(f"aux program exceeds the {name} limit of sp_air_prove_aux: {value} > {lim[name]}")
             if len(self.aux.consts) + self.n_rap > 65535:
                 raise ValueError("aux program: constants and RAP challenges exceed the 16-bit operand range")
+        if self.bvalues:
+            for name, value in (("constants", len(self.public.consts)), ("ops", len(self.public.ops))):
+                if value > lim[name]:
+                    raise ValueError(f"boundary values exceed the {name} limit of sp_air_prove_pub: {value} > {lim[name]}")
+            if len(self.public.consts) + self.n_rap > 65535:
+                raise ValueError("boundary values: constants and RAP challenges exceed the 16-bit operand range")
 
     def build(self, aux_as_callback=False, main_trace=None):
         """Returns (AirDescC, keepalive).  Raises ValueError if the AIR exceeds a bound of sp_air_limits.
@@ -503,7 +665,9 @@ class AirBuilder:
         With an aux program (aux_kind AUX_PROGRAM) the returned desc carries its AirAuxDescC (desc.aux_desc), and
         api.Context.air_prove proves it with sp_air_prove_aux.  aux_as_callback=True returns the same AIR as aux_kind AUX_CALLBACK
         instead, its callback evaluating the aux program in Python over `main_trace` ((n, main_cols, 32) canonical big-endian
-        bytes, or n rows of ints): what the CPU oracle and sp_air_prove accept."""
+        bytes, or n rows of ints): what the CPU oracle and sp_air_prove accept.
+        With boundary_from constraints the returned desc carries their AirBoundaryDescC (desc.boundary_desc); with that, or an aux program
+        that reads a table, api.Context.air_prove, air_check_trace and api.air_verify go through sp_air_prove_pub and its siblings."""
         _check_layout()
         self.check_limits()
         if self.aux is not None and aux_as_callback:
@@ -564,8 +728,17 @@ class AirBuilder:
         if self.aux is not None:
             aux_desc, aux_keep = self._aux_desc()
             d.aux_desc = aux_desc
+            d.aux_reads_table = self.aux.reads_table()
             keep = keep + (aux_desc, aux_keep)
+        if self.bvalues:
+            b_desc, b_keep = self.build_boundary_desc()
+            d.boundary_desc = b_desc
+            keep = keep + (b_desc, b_keep)
         return d, keep
+
+    def build_boundary_desc(self):
+        """(AirBoundaryDescC, keepalive) of the boundary_from constraints: what build() attaches as desc.boundary_desc."""
+        return boundary_desc(self.public.resolved_ops(), self.public.consts, self.bvalues)
 
     def _aux_desc(self):
         _check_aux_layout()
@@ -594,12 +767,12 @@ class AirBuilder:
             d, keep = self.build()
         finally:
             self.aux_kind, self.aux = aux_kind, program
-        aux_cols = self.aux_cols
+        aux_cols, periodic = self.aux_cols, self.periodic_cols
 
         def _aux(user, rap_ptr, n_rap, out_ptr):   # canonical big-endian contexts (the default encoding)
             try:
                 raw = ctypes.string_at(rap_ptr, 32 * n_rap)
-                flat = ints_to_bytes(program.evaluate(rows, [int.from_bytes(raw[32 * i:32 * i + 32], "big") for i in range(n_rap)]))
+                flat = ints_to_bytes(program.evaluate(rows, [int.from_bytes(raw[32 * i:32 * i + 32], "big") for i in range(n_rap)], periodic=periodic))
                 assert flat.shape[1] == aux_cols
                 ctypes.memmove(out_ptr, flat.ctypes.data, flat.nbytes)
                 return 0
@@ -732,3 +905,72 @@ def strided_mimc_chain_trace(n, x0, keys, free):
         rows.append([x])
         x = pow((x + keys[i % len(keys)]) % P, 2, P) if i % STRIDED_CHAIN_PERIOD == 0 else free() % P
     return rows
+
+
+# ---- public data inside a RAP argument: two worked examples -------------------------------------------------------------------
+def table_lookup(n, table):
+    """Every a_i is an entry of the public `table` (a power-of-two number of values, at most n): a LogUp lookup.  Main columns a and m
+    (m_i: how often the table entry of row i, T_i = table[i mod len(table)], is looked up - a prover's choice that sums right), T periodic
+    column 0, one challenge gamma.  The auxiliary column is the running sum s_0 = 0, s' = s + m / (gamma - T) - 1 / (gamma - a), built on
+    the device by an auxiliary program that reads T with table().  The constraint (s' - s)(gamma - T)(gamma - a) - m (gamma - a) +
+    (gamma - T) has degree 3 under degree_bound_factor 2 and NO exempted row: on row n - 1 it wraps to s_0 = 0 and closes the sum."""
+    if len(table) > n:
+        raise ValueError(f"table_lookup: {len(table)} table entries on {n} rows")
+    b = AirBuilder(2, [0, 1], 2, aux_cols=1, n_rap=1, aux_kind=AUX_PROGRAM, periodic=[table])
+    gamma = b.rap(0)
+    ga, gt = gamma - b.load(0, 0), gamma - b.periodic(0, 0)
+    b.constraint((b.load(1, 2) - b.load(0, 2)) * gt * ga - b.load(0, 1) * ga + gt, degree=3, exemptions=0)
+    b.boundary(2, 0, 0)
+    g = b.aux.rap(0)
+    xa, xt = g - b.aux.load(0, 0), g - b.aux.table(0, 0)
+    b.aux.running_sum(b.aux.load(0, 1) * xa - xt, xt * xa)
+    return b
+
+
+def table_lookup_trace(n, table, looked_up):
+    """(n, 2) Python ints [a_i, m_i] for the n values `looked_up` (each an entry of the table): each distinct table value's multiplicity
+    sits on the first row that holds it, every other m is 0."""
+    first = {}
+    for j, v in enumerate(table):
+        first.setdefault(int(v) % P, j)
+    a = [int(v) % P for v in looked_up]
+    if len(a) != n or any(v not in first for v in a):
+        raise ValueError("table_lookup_trace: n looked-up values, each an entry of the table")
+    m = [0] * n
+    for v in a:
+        m[first[v]] += 1
+    return [[a[i], m[i]] for i in range(n)]
+
+
+def public_permutation(n, public):
+    """Column a is column b with L of its zeros replaced by the public list (L = len(public) < n), in any order: main columns a and b,
+    one challenge gamma, the grand product z_0 = 1, z' (gamma - b) = z (gamma - a) with the last row exempt.  a_(n-1) = b_(n-1) = 0 and
+    z_0 = 1 are constants; z_(n-1) = prod_j (gamma - v_j) / gamma^L depends on the challenge and goes through boundary_from - the short
+    public list never becomes a column of n values."""
+    if len(public) >= n:
+        raise ValueError(f"public_permutation: {len(public)} public values on {n} rows")
+    b = AirBuilder(2, [0, 1], 1, aux_cols=1, n_rap=1, aux_kind=AUX_PROGRAM)
+    gamma = b.rap(0)
+    b.constraint(b.load(1, 2) * (gamma - b.load(0, 1)) - b.load(0, 2) * (gamma - b.load(0, 0)), degree=2, exemptions=1)
+    b.boundary(0, n - 1, 0); b.boundary(1, n - 1, 0); b.boundary(2, 0, 1)
+    g = b.aux.rap(0)
+    b.aux.product(g - b.aux.load(0, 0), g - b.aux.load(0, 1))
+    pg = b.public.rap(0)
+    num, den = b.public.const(1), None
+    for v in public:
+        num = num * (pg - v)
+        den = pg if den is None else den * pg
+    b.boundary_from(2, n - 1, num, den)
+    return b
+
+
+def public_permutation_trace(n, public, fill, order):
+    """(n, 2) Python ints [a_i, b_i]: b holds the non-zero values `fill` (n - 1 - len(public) of them) and len(public) zeros on its rows
+    0 .. n - 2 in the order `order` (a permutation of range(n - 1)), a holds `fill` and the public list there in their given order;
+    the last row is [0, 0]."""
+    L = len(public)
+    if len(fill) != n - 1 - L or sorted(order) != list(range(n - 1)):
+        raise ValueError("public_permutation_trace: n - 1 - len(public) fill values and a permutation of range(n - 1)")
+    a = [int(v) % P for v in list(public) + list(fill)]
+    src = [0] * L + [int(v) % P for v in fill]
+    return [[a[i], src[order[i]]] for i in range(n - 1)] + [[0, 0]]

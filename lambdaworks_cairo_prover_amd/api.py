@@ -223,7 +223,9 @@ class Context:
         """sp_air_prove: desc = lambdaworks_cairo_prover_amd.air.AirDescC (AirBuilder.build()[0]); main_trace (n, cols, 32).
         A desc that carries an auxiliary program (AirBuilder with aux_kind=air.AUX_PROGRAM) goes to sp_air_prove_aux, one that
         carries periodic columns (AirBuilder(..., periodic=[...])) to sp_air_prove_periodic - with its auxiliary program, if any; one
-        that carries strides (a constraint with period > 1) to sp_air_prove_ext with all of these."""
+        that carries strides (a constraint with period > 1) to sp_air_prove_ext with all of these; one that carries boundary values
+        computed from the challenges (AirBuilder.boundary_from) or whose auxiliary program reads a table (AuxProgram.table) to
+        sp_air_prove_pub."""
         a = np.ascontiguousarray(main_trace, dtype=np.uint8)
         n, cols = a.shape[0], a.shape[1]
         assert cols == desc.main_cols
@@ -232,8 +234,12 @@ class Context:
         ln = ctypes.c_uint64()
         aux = getattr(desc, "aux_desc", None)
         per = getattr(desc, "periodic_desc", None)
-        if getattr(desc, "stride_desc", None) is not None:
-            from . import air
+        from . import air
+        if air.needs_pub(desc):
+            ext, bvals = air.ext_of(desc), getattr(desc, "boundary_desc", None)
+            check(self._lib.sp_air_prove_pub(self._h, ctypes.byref(desc), ctypes.byref(ext), None if bvals is None else ctypes.byref(bvals), _u8p(a),
+                                             ctypes.c_uint64(n), ctypes.byref(opt), ctypes.byref(out), ctypes.byref(ln)))
+        elif getattr(desc, "stride_desc", None) is not None:
             ext = air.ext_of(desc)
             check(self._lib.sp_air_prove_ext(self._h, ctypes.byref(desc), ctypes.byref(ext), _u8p(a), ctypes.c_uint64(n), ctypes.byref(opt),
                                              ctypes.byref(out), ctypes.byref(ln)))
@@ -276,7 +282,10 @@ class Context:
         per = getattr(desc, "periodic_desc", None)
         tail = (_u8p(a), ctypes.c_uint64(n), None if opt is None else ctypes.byref(opt), None if rap_bytes is None else _u8p(rap_bytes),
                 out if cap else None, ctypes.c_uint32(cap), ctypes.byref(total))
-        if getattr(desc, "stride_desc", None) is not None:
+        if air.needs_pub(desc):
+            ext, bvals = air.ext_of(desc), getattr(desc, "boundary_desc", None)
+            check(self._lib.sp_air_check_trace_pub(self._h, ctypes.byref(desc), ctypes.byref(ext), None if bvals is None else ctypes.byref(bvals), *tail))
+        elif getattr(desc, "stride_desc", None) is not None:
             ext = air.ext_of(desc)
             check(self._lib.sp_air_check_trace_ext(self._h, ctypes.byref(desc), ctypes.byref(ext), *tail))
         else:
@@ -535,6 +544,15 @@ def air_stride_limits():
     return {"stride_classes": int(out[0]), "stride_exemption_products": int(out[1])}
 
 
+def air_boundary_resolve(bvals, rap):
+    """sp_air_boundary_resolve (host): the values of an air.AirBoundaryDescC (desc.boundary_desc) under the RAP challenges `rap` (ints),
+    as ints in the order of its entries - what the prover, the trace check and the verifier put into the boundary constraints."""
+    rap_bytes = b"".join((int(r) % P).to_bytes(32, "big") for r in rap)
+    out = ctypes.create_string_buffer(max(1, 32 * bvals.n_values))
+    check(_lib.load().sp_air_boundary_resolve(ctypes.byref(bvals), rap_bytes if rap else None, ctypes.c_uint32(len(rap)), out))
+    return [int.from_bytes(out.raw[32 * j:32 * j + 32], "big") for j in range(bvals.n_values)]
+
+
 def air_stride_eval(period, offset, exemptions, n, point):
     """sp_air_stride_eval (host, the verifier's routine): (Z(point), E(point)) as ints - the zerofier x^(n/period) - g^(offset n/period) of
     the rows = offset (mod period) and the product of (x - g^row) over the last `exemptions` rows of that progression."""
@@ -555,12 +573,17 @@ def air_periodic_eval(values, n, point):
 
 def air_verify(proof, desc, options, merkle_backend=0):
     """sp_air_verify(_backend): the library's CPU verifier for an AIR given as a constraint program (sp_air_verify_periodic for a
-    desc that carries periodic columns, sp_air_verify_ext for one that carries strides)."""
+    desc that carries periodic columns, sp_air_verify_ext for one that carries strides, sp_air_verify_pub for one that carries boundary
+    values computed from the challenges or an auxiliary program that reads a table)."""
+    from . import air
     lib = _lib.load()
     opt = options.to_c()
     per = getattr(desc, "periodic_desc", None)
+    if air.needs_pub(desc):
+        ext, bvals = air.ext_of(desc), getattr(desc, "boundary_desc", None)
+        return lib.sp_air_verify_pub(proof, ctypes.c_uint64(len(proof)), ctypes.byref(desc), ctypes.byref(ext), None if bvals is None else ctypes.byref(bvals),
+                                     ctypes.byref(opt), int(merkle_backend)) == 1
     if getattr(desc, "stride_desc", None) is not None:
-        from . import air
         ext = air.ext_of(desc)
         return lib.sp_air_verify_ext(proof, ctypes.c_uint64(len(proof)), ctypes.byref(desc), ctypes.byref(ext), ctypes.byref(opt), int(merkle_backend)) == 1
     if per is not None:

@@ -15,7 +15,10 @@ constexpr uint32_t AIR_AUX_MAX_SHIFT = 7;
 
 // One thread per row: evaluates the program once and writes every N and D it names (column-major, coalesced across rows).
 // trace: [main_cols][n] natural order; consts: the aux constants followed by the RAP challenges.
-int air_aux_terms(hipStream_t st, const fe* trace, uint64_t n, const AirOpDev* ops, uint32_t n_ops, const fe* consts, fe* num, fe* den);
+// pcols / pvals (both null for a program without op 6, which then launches the kernel without them): the periodic columns an op 6
+// reads, a = row shift, b = column k: pvals[off_k + ((i + a) mod period_k)] - the raw values, as the exact trace check reads them.
+int air_aux_terms(hipStream_t st, const fe* trace, uint64_t n, const AirOpDev* ops, uint32_t n_ops, const fe* consts, fe* num, fe* den,
+                  const AirPeriodicCol* pcols = nullptr, const fe* pvals = nullptr);
 // num[col_of[d] * n + i] *= dinv[d * n + i]  for d < n_den, i < n
 int air_aux_apply_den(hipStream_t st, fe* num, const fe* dinv, const uint32_t* col_of, uint32_t n_den, uint64_t n);
 // In-place EXCLUSIVE scan of K columns of n elements (column k at data + k * n), shifted by one row: out[0] = identity,

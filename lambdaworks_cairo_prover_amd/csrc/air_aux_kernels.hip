@@ -5,25 +5,48 @@
 namespace sp {
 
 // ---- per-row terms ------------------------------------------------------------------------------------------
-// The program runs in the shared interpreter (air_interp.h): LOAD takes the row shift itself, there are no periodic columns, and an
-// OUT stores into the num / den column it names.
-__global__ void __launch_bounds__(256) air_aux_terms_kernel(const fe* __restrict__ trace, uint64_t n, const AirOpDev* __restrict__ ops, uint32_t n_ops,
-                                                            const fe* __restrict__ consts, fe* __restrict__ num, fe* __restrict__ den) {
-    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    air_run_program<false>(
+// The program runs in the shared interpreter (air_interp.h): LOAD takes the row shift itself, and an OUT stores into the num / den
+// column it names.  Two kernels share the body: a program without op 6 runs the one without periodic columns (PER = false leaves no
+// test for op 6 in it); one with table reads gets the columns' descriptors and raw values.
+template <bool PER, class Periodic>
+__device__ __forceinline__ void air_aux_terms_row(const fe* __restrict__ trace, uint64_t n, uint64_t i, const AirOpDev* __restrict__ ops, uint32_t n_ops,
+                                                  const fe* __restrict__ consts, fe* __restrict__ num, fe* __restrict__ den, Periodic periodic) {
+    air_run_program<PER>(
         ops, n_ops, consts,
         [&](uint32_t shift, uint32_t col) { return fe_ld(trace + (uint64_t)col * n + ((i + shift) & (n - 1))); },   // n is a power of two
-        AirNoPeriodic{},
+        periodic,
         [&](uint32_t a, const fe& val) {
             fe* dst = a < AIR_AUX_DEN_TAG ? num + (uint64_t)a * n : den + (uint64_t)(a - AIR_AUX_DEN_TAG) * n;
             fe_st(dst + i, val);
         });
 }
 
-int air_aux_terms(hipStream_t st, const fe* trace, uint64_t n, const AirOpDev* ops, uint32_t n_ops, const fe* consts, fe* num, fe* den) {
-    if (n == 0 || (n & (n - 1))) return SP_E_INVALID_ARG;
-    hipLaunchKernelGGL(air_aux_terms_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, trace, n, ops, n_ops, consts, num, den);
+__global__ void __launch_bounds__(256) air_aux_terms_kernel(const fe* __restrict__ trace, uint64_t n, const AirOpDev* __restrict__ ops, uint32_t n_ops,
+                                                            const fe* __restrict__ consts, fe* __restrict__ num, fe* __restrict__ den) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    air_aux_terms_row<false>(trace, n, i, ops, n_ops, consts, num, den, AirNoPeriodic{});
+}
+
+// op 6: a = row shift, b = periodic column.  A period is a power of two <= n, so (i + shift) mod period is a mask and stays inside the
+// column's own values.
+__global__ void __launch_bounds__(256) air_aux_terms_periodic_kernel(const fe* __restrict__ trace, uint64_t n, const AirOpDev* __restrict__ ops, uint32_t n_ops,
+                                                                     const fe* __restrict__ consts, fe* __restrict__ num, fe* __restrict__ den,
+                                                                     const AirPeriodicCol* __restrict__ pcols, const fe* __restrict__ pvals) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    air_aux_terms_row<true>(trace, n, i, ops, n_ops, consts, num, den, [&](uint32_t shift, uint32_t col) {
+        const AirPeriodicCol pc = pcols[col];
+        return fe_ld(pvals + pc.off + ((i + shift) & ((1ull << pc.logp) - 1ull)));
+    });
+}
+
+int air_aux_terms(hipStream_t st, const fe* trace, uint64_t n, const AirOpDev* ops, uint32_t n_ops, const fe* consts, fe* num, fe* den,
+                  const AirPeriodicCol* pcols, const fe* pvals) {
+    if (n == 0 || (n & (n - 1)) || (pcols == nullptr) != (pvals == nullptr)) return SP_E_INVALID_ARG;
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (pcols) hipLaunchKernelGGL(air_aux_terms_periodic_kernel, grid, dim3(256), 0, st, trace, n, ops, n_ops, consts, num, den, pcols, pvals);
+    else hipLaunchKernelGGL(air_aux_terms_kernel, grid, dim3(256), 0, st, trace, n, ops, n_ops, consts, num, den);
     SP_HIP_CHECK(hipGetLastError());
     return SP_OK;
 }

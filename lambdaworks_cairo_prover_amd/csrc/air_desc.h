@@ -72,6 +72,23 @@ bool air_strides_from_c(const sp_air_stride_desc* d, uint64_t n, AirDescHost& ai
 // n rows (all already checked: s | n, o < s, e <= n/s).  What the verifier's step 2 uses and sp_air_stride_eval returns.  verifier.cpp
 void air_stride_eval(uint32_t s, uint32_t o, uint32_t e, uint64_t n, const fe& x, fe& Z, fe& E);
 
+// Host form of sp_air_boundary_desc: boundary values that are N / D of a program over constants and the RAP challenges (ops 1 - 4).
+struct AirBoundaryValueHost { uint32_t boundary, num_op, den_op; };
+struct AirBoundaryHost {
+    std::vector<AirOpHost> ops;
+    std::vector<fe> consts;
+    std::vector<AirBoundaryValueHost> values;
+};
+// sp_air_boundary_desc -> AirBoundaryHost for an AIR with n_boundary boundary constraints and n_rap challenges; false - before anything
+// is allocated or copied - for null members, counts beyond sp_air_limits, an op other than 1 - 4, an operand that is no earlier op,
+// boundary >= n_boundary, a boundary named twice, num_op / den_op beyond the program.  capi_host.cpp
+bool air_boundary_from_c(const sp_air_boundary_desc* d, uint32_t n_boundary, uint32_t n_rap, AirBoundaryHost& out);
+// The one resolver: values[j] = N_j / D_j under these challenges (one batch inversion).  false when a D is zero.  Prover, trace check,
+// verifier and sp_air_boundary_resolve all go through it.  verifier.cpp
+bool air_resolve_boundary(const AirBoundaryHost& bvals, const std::vector<fe>& rap, std::vector<fe>& values);
+// air.boundary with the resolved values put in: what everything behind round 1's challenges sees as constants.
+bool air_resolve_boundary_into(const AirBoundaryHost& bvals, const std::vector<fe>& rap, std::vector<BoundaryConstraint>& boundary);
+
 // The rules of a straight-line program (op 0 LOAD, 1 CONST, 2 ADD, 3 SUB, 4 MUL, 5 OUT, 6 PERIODIC): a LOAD has a < load_a_end and
 // b < load_b_end, a CONST names one of n_values constants or RAP challenges, ADD / SUB / MUL take two earlier ops that are not
 // OUTs, an OUT one of n_out targets and such an op (n_out 0: no OUT at all), a PERIODIC a < load_a_end and one of n_periodic

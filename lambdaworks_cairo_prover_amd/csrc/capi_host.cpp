@@ -55,7 +55,8 @@ bool cairo_run_device_inputs(const sp_cairo_run* run, const TracePlan** plan, Tr
 }
 static thread_local std::string g_last_error;
 void sp_set_error(const std::string& s) { g_last_error = s; }
-namespace sp { int air_verify_host(const uint8_t* proof_bytes, size_t len, const AirDescHost& air, const ProofOptionsHost& opt, const AirPeriodicHost* periodic); }
+namespace sp { int air_verify_host(const uint8_t* proof_bytes, size_t len, const AirDescHost& air, const ProofOptionsHost& opt, const AirPeriodicHost* periodic,
+                                   const AirBoundaryHost* bvals = nullptr); }
 namespace sp { void set_verify_merkle_backend(int backend); int host_bind_calling_thread_to_device_node(int device, int* node_out); }
 namespace sp { int cairo_verify_host(const uint8_t* proof_bytes, size_t len, const PublicInputs& pub, uint8_t blowup, uint64_t queries, uint64_t coset_offset, uint8_t grinding); }
 
@@ -117,6 +118,26 @@ bool air_strides_from_c(const sp_air_stride_desc* d, uint64_t n, AirDescHost& ai
     air.strides.clear();
     return false;
 }
+bool air_boundary_from_c(const sp_air_boundary_desc* d, uint32_t n_boundary, uint32_t n_rap, AirBoundaryHost& out) {
+    if (!d->ops || !d->consts || !d->values || d->n_ops == 0 || d->n_ops > (uint32_t)AIR_MAX_OPS || d->n_consts > (uint32_t)AIR_MAX_CONSTS ||
+        (uint64_t)d->n_consts + n_rap > 65535 || d->n_values > (uint32_t)AIR_MAX_BOUNDARY) return false;
+    std::vector<AirOpHost> ops;
+    for (uint32_t i = 0; i < d->n_ops; ++i) ops.push_back(AirOpHost{d->ops[i].op, d->ops[i].a, d->ops[i].b});
+    // (no cell to LOAD, no OUT target, no periodic column: ops 1 - 4 are all that is left)
+    if (air_program_first_bad_op(ops, 0, 0, (size_t)d->n_consts + n_rap, 0, 0) < ops.size()) return false;
+    std::vector<uint32_t> named;
+    for (uint32_t j = 0; j < d->n_values; ++j) {
+        const sp_air_boundary_value& e = d->values[j];
+        if (e.boundary >= n_boundary || e.num_op >= d->n_ops || (e.den_op != SP_AIR_AUX_NO_DEN && e.den_op >= d->n_ops)) return false;
+        named.push_back(e.boundary);
+    }
+    std::sort(named.begin(), named.end());
+    if (std::adjacent_find(named.begin(), named.end()) != named.end()) return false;
+    out.ops.swap(ops);
+    for (uint32_t i = 0; i < d->n_consts; ++i) out.consts.push_back(fe_from_bytes_be(d->consts + 32 * (size_t)i));
+    for (uint32_t j = 0; j < d->n_values; ++j) out.values.push_back(AirBoundaryValueHost{d->values[j].boundary, d->values[j].num_op, d->values[j].den_op});
+    return true;
+}
 bool air_periodic_fits(const AirPeriodicHost& p, uint64_t n) {
     for (const auto& c : p.cols) if (c.size() > n) return false;
     return true;
@@ -134,6 +155,7 @@ uint64_t sp_air_violation_size(void) { return sizeof(sp_air_violation); }
 uint64_t sp_air_stride_size(void) { return sizeof(sp_air_stride); }
 uint64_t sp_air_stride_desc_size(void) { return sizeof(sp_air_stride_desc); }
 uint64_t sp_air_ext_size(void) { return sizeof(sp_air_ext); }
+uint64_t sp_air_boundary_desc_size(void) { return sizeof(sp_air_boundary_desc); }
 int sp_air_stride_limits(uint32_t out[4]) {
     if (!out) return SP_E_INVALID_ARG;
     out[0] = sp::AIR_MAX_STRIDE_CLASSES; out[1] = sp::AIR_MAX_STRIDE_EXEMPT_KINDS; out[2] = out[3] = 0u;
@@ -546,10 +568,12 @@ int sp_air_verify_periodic(const uint8_t* proof, uint64_t proof_len, const sp_ai
     } catch (const std::exception& e) { sp_set_error(e.what()); return 0; }
 }
 
+static const char* const BOUNDARY_VALUES_MALFORMED = "malformed: boundary values (ops 1 - 4 over earlier ops, each boundary < n_boundary and named once, "
+                                                     "num_op / den_op inside the program, the bounds of sp_air_limits)";
 // sp_air_verify_backend / sp_air_verify_periodic with the extensions in one block: the strides of the transition constraints too.  The
 // auxiliary program of `ext` is the prover's business (the verifier sees the committed columns) and is not looked at.
-int sp_air_verify_ext(const uint8_t* proof, uint64_t proof_len, const sp_air_desc* d, const sp_air_ext* ext, const sp_proof_options* opt,
-                      int merkle_backend) {
+static int air_verify_ext_common(const uint8_t* proof, uint64_t proof_len, const sp_air_desc* d, const sp_air_ext* ext, const sp_air_boundary_desc* bv,
+                                 const sp_proof_options* opt, int merkle_backend) {
     if (!proof || !d || !opt) return SP_E_INVALID_ARG;
     if (merkle_backend != SP_MERKLE_KECCAK256 && merkle_backend != SP_MERKLE_POSEIDON) return SP_E_INVALID_ARG;
     if (ext && ext->size != sizeof(sp_air_ext)) { sp_set_error("malformed: sp_air_ext.size is not sizeof(sp_air_ext)"); return 0; }
@@ -567,10 +591,37 @@ int sp_air_verify_ext(const uint8_t* proof, uint64_t proof_len, const sp_air_des
             sp_set_error("malformed: strides (one per transition, a power-of-two period <= the trace length, offset < period, exemptions < n / period and degree <= degree_bound_factor for a period > 1, at most 4 classes)");
             return 0;
         }
-        const int ok = sp::air_verify_host(proof, proof_len, air, sp::proof_options_from_c(opt), pd ? &periodic : nullptr);
+        sp::AirBoundaryHost bvals;
+        if (bv && !sp::air_boundary_from_c(bv, d->n_boundary, d->n_rap, bvals)) { sp_set_error(BOUNDARY_VALUES_MALFORMED); return 0; }
+        const int ok = sp::air_verify_host(proof, proof_len, air, sp::proof_options_from_c(opt), pd ? &periodic : nullptr, bv ? &bvals : nullptr);
         sp_set_error(ok == 1 ? "" : "rejected: a verification step failed");
         return ok;
     } catch (const std::exception& e) { sp_set_error(e.what()); return 0; }
+}
+
+int sp_air_verify_ext(const uint8_t* proof, uint64_t proof_len, const sp_air_desc* d, const sp_air_ext* ext, const sp_proof_options* opt,
+                      int merkle_backend) {
+    return air_verify_ext_common(proof, proof_len, d, ext, nullptr, opt, merkle_backend);
+}
+
+// sp_air_verify_ext with boundary values computed from the proof's own RAP challenges (the auxiliary program, and so whether it reads
+// periodic columns, stays the prover's business).
+int sp_air_verify_pub(const uint8_t* proof, uint64_t proof_len, const sp_air_desc* d, const sp_air_ext* ext, const sp_air_boundary_desc* bv,
+                      const sp_proof_options* opt, int merkle_backend) {
+    return air_verify_ext_common(proof, proof_len, d, ext, bv, opt, merkle_backend);
+}
+
+int sp_air_boundary_resolve(const sp_air_boundary_desc* bv, const uint8_t* rap, uint32_t n_rap, uint8_t* out) {
+    if (!bv || (n_rap && !rap) || !out) return SP_E_INVALID_ARG;
+    try {
+        sp::AirBoundaryHost bvals;
+        if (!sp::air_boundary_from_c(bv, 0xFFFFFFFFu, n_rap, bvals)) { sp_set_error(BOUNDARY_VALUES_MALFORMED); return SP_E_INVALID_ARG; }
+        std::vector<fe> r(n_rap), values;
+        for (uint32_t i = 0; i < n_rap; ++i) r[i] = fe_from_bytes_be(rap + 32 * (size_t)i);
+        if (!sp::air_resolve_boundary(bvals, r, values)) { sp_set_error("sp_air_boundary_resolve: a boundary value's denominator is zero"); return SP_E_ZERO_INVERSE; }
+        for (size_t j = 0; j < values.size(); ++j) fe_to_bytes_be(values[j], out + 32 * j);
+        return SP_OK;
+    } catch (const std::exception& e) { sp_set_error(e.what()); return SP_E_INVALID_ARG; }
 }
 
 int sp_air_stride_eval(uint32_t period, uint32_t offset, uint32_t exemptions, uint64_t n, const uint8_t point[32], uint8_t out_z[32], uint8_t out_e[32]) {

@@ -364,16 +364,20 @@ int sp_last_round_ms(sp_ctx* c, float out[5]) {
 
 static const char* const STRIDES_MALFORMED = "malformed strides (one per transition, a power-of-two period <= the trace length, offset < period, "
                                              "exemptions < n / period and degree <= degree_bound_factor for a period > 1, at most 4 classes and 4 exemption products)";
+static const char* const BOUNDARY_VALUES_MALFORMED = "malformed boundary values (ops 1 - 4 over earlier ops, each boundary < n_boundary and named once, num_op / den_op "
+                                                     "inside the program, the bounds of sp_air_limits)";
 static int air_prove_common(sp_ctx* c, const sp_air_desc* d, const sp::AirAuxHost* aux, const uint8_t* main_trace, uint64_t n,
                             const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len, const sp::AirPeriodicHost* periodic = nullptr,
-                            const sp_air_stride_desc* strides = nullptr) {
+                            const sp_air_stride_desc* strides = nullptr, const sp_air_boundary_desc* bv = nullptr, bool aux_reads_periodic = false) {
     c->prewarm_cancel.store(0, std::memory_order_release);
     sp::AirDescHost a;
     if (!air_desc_from_c(d, a)) { sp_set_error("sp_air_prove: malformed descriptor"); return SP_E_INVALID_ARG; }
     if (strides && !sp::air_strides_from_c(strides, n, a)) { sp_set_error(STRIDES_MALFORMED); return SP_E_INVALID_ARG; }
+    sp::AirBoundaryHost bvals;
+    if (bv && !sp::air_boundary_from_c(bv, d->n_boundary, d->n_rap, bvals)) { sp_set_error(BOUNDARY_VALUES_MALFORMED); return SP_E_INVALID_ARG; }
     std::vector<uint8_t> proof;
     float ms[5] = {0, 0, 0, 0, 0};
-    SP_TRY(sp::air_prove(c, a, main_trace, n, proof_options_from_c(opt), proof, ms, aux, periodic));
+    SP_TRY(sp::air_prove(c, a, main_trace, n, proof_options_from_c(opt), proof, ms, aux, periodic, sp::AirPublicHost{bv ? &bvals : nullptr, aux_reads_periodic}));
     return publish_proof(c, ms, proof, proof_out, proof_len);
 }
 
@@ -425,7 +429,7 @@ int sp_air_prove_periodic(sp_ctx* c, const sp_air_desc* d, const sp_air_aux_desc
 
 static int air_check_trace_common(sp_ctx* c, const sp_air_desc* d, const sp_air_aux_desc* x, const sp_air_periodic_desc* pd, const sp_air_stride_desc* sd,
                                   const uint8_t* main_trace, uint64_t n, const sp_proof_options* opt, const uint8_t* rap, sp_air_violation* out, uint32_t cap,
-                                  uint32_t* n_out) {
+                                  uint32_t* n_out, const sp_air_boundary_desc* bv = nullptr, bool aux_reads_periodic = false) {
     if (!c || !d || !main_trace || !n_out || (!opt && !rap) || (!out && cap)) return SP_E_INVALID_ARG;
     try {
         sp::AirDescHost a;
@@ -438,12 +442,15 @@ static int air_check_trace_common(sp_ctx* c, const sp_air_desc* d, const sp_air_
         if (sd && !sp::air_strides_from_c(sd, n, a)) { sp_set_error(STRIDES_MALFORMED); return SP_E_INVALID_ARG; }
         sp::AirAuxHost aux;
         if (x) SP_TRY(aux_from_c(d, x, aux));
+        sp::AirBoundaryHost bvals;
+        if (bv && !sp::air_boundary_from_c(bv, d->n_boundary, d->n_rap, bvals)) { sp_set_error(BOUNDARY_VALUES_MALFORMED); return SP_E_INVALID_ARG; }
         c->prewarm_cancel.store(0, std::memory_order_release);   // (the context is first touched here: the descriptors are judged without it)
         std::vector<fe> rap_fe(a.n_rap);
         if (rap && a.n_rap) SP_TRY(dec(c, rap, a.n_rap, rap_fe.data()));
         const sp::ProofOptionsHost oh = opt ? proof_options_from_c(opt) : sp::ProofOptionsHost{};
         std::vector<sp::AirViolationHost> found;
-        SP_TRY(sp::air_check_trace(c, a, main_trace, n, opt ? &oh : nullptr, rap ? &rap_fe : nullptr, found, x ? &aux : nullptr, pd ? &periodic : nullptr));
+        SP_TRY(sp::air_check_trace(c, a, main_trace, n, opt ? &oh : nullptr, rap ? &rap_fe : nullptr, found, x ? &aux : nullptr, pd ? &periodic : nullptr,
+                                   sp::AirPublicHost{bv ? &bvals : nullptr, aux_reads_periodic}));
         *n_out = (uint32_t)found.size();
         for (size_t i = 0; i < found.size() && i < cap; ++i) {
             const sp::AirViolationHost& v = found[i];
@@ -465,8 +472,8 @@ static bool ext_ok(const sp_air_ext* ext) {
     return true;
 }
 
-int sp_air_prove_ext(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const uint8_t* main_trace, uint64_t n, const sp_proof_options* opt,
-                     uint8_t** proof_out, uint64_t* proof_len) {
+static int air_prove_ext_common(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const sp_air_boundary_desc* bv, bool aux_reads_periodic,
+                               const uint8_t* main_trace, uint64_t n, const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len) {
     if (!c || !d || !main_trace || !opt || !proof_out || !proof_len || !ext_ok(ext)) return SP_E_INVALID_ARG;
     try {
         sp::AirPeriodicHost periodic;
@@ -478,8 +485,28 @@ int sp_air_prove_ext(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, con
         sp::AirAuxHost aux;
         const sp_air_aux_desc* x = ext ? ext->aux : nullptr;
         if (x) SP_TRY(aux_from_c(d, x, aux));
-        return air_prove_common(c, d, x ? &aux : nullptr, main_trace, n, opt, proof_out, proof_len, pd ? &periodic : nullptr, ext ? ext->strides : nullptr);
+        return air_prove_common(c, d, x ? &aux : nullptr, main_trace, n, opt, proof_out, proof_len, pd ? &periodic : nullptr, ext ? ext->strides : nullptr, bv,
+                                aux_reads_periodic);
     } catch (const std::exception& e) { sp_set_error(e.what()); return SP_E_INVALID_ARG; }
+}
+
+int sp_air_prove_ext(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const uint8_t* main_trace, uint64_t n, const sp_proof_options* opt,
+                     uint8_t** proof_out, uint64_t* proof_len) {
+    return air_prove_ext_common(c, d, ext, nullptr, false, main_trace, n, opt, proof_out, proof_len);
+}
+
+// sp_air_prove_ext with public data inside the RAP argument: boundary values computed from the challenges (bv, nullable), and an
+// auxiliary program that may read ext->periodic with op 6.
+int sp_air_prove_pub(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const sp_air_boundary_desc* bv, const uint8_t* main_trace, uint64_t n,
+                     const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len) {
+    return air_prove_ext_common(c, d, ext, bv, true, main_trace, n, opt, proof_out, proof_len);
+}
+
+int sp_air_check_trace_pub(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const sp_air_boundary_desc* bv, const uint8_t* main_trace, uint64_t n,
+                           const sp_proof_options* opt, const uint8_t* rap, sp_air_violation* out, uint32_t cap, uint32_t* n_out) {
+    if (!ext_ok(ext)) return SP_E_INVALID_ARG;
+    return air_check_trace_common(c, d, ext ? ext->aux : nullptr, ext ? ext->periodic : nullptr, ext ? ext->strides : nullptr, main_trace, n, opt, rap,
+                                  out, cap, n_out, bv, true);
 }
 
 int sp_air_check_trace_ext(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const uint8_t* main_trace, uint64_t n, const sp_proof_options* opt,

@@ -416,16 +416,16 @@ int StarkProver::commit_aux_cairo(const PublicInputs& pub, const fe rap[3], uint
     return commit_segment_resident(1, Ca_, root_out);
 }
 
-int validate_aux_program(const AirAuxHost& aux, uint32_t main_cols, uint32_t n_rap) {
+int validate_aux_program(const AirAuxHost& aux, uint32_t main_cols, uint32_t n_rap, uint32_t n_periodic) {
     const size_t n_ops = aux.ops.size();
     if (n_ops == 0 || n_ops > (size_t)AIR_MAX_OPS) { sp_set_error("aux program: 1 .. 65535 ops"); return SP_E_INVALID_ARG; }
     if (aux.consts.size() > (size_t)AIR_MAX_CONSTS) { sp_set_error("aux program: more than 4096 constants"); return SP_E_INVALID_ARG; }
     if (aux.consts.size() + n_rap > 65535) { sp_set_error("aux program: constants and RAP challenges exceed the 16-bit operand range"); return SP_E_INVALID_ARG; }
     if (aux.cols.empty() || aux.cols.size() > (size_t)AIR_MAX_COLS) { sp_set_error("aux program: 1 .. 1024 auxiliary columns"); return SP_E_INVALID_ARG; }
-    const size_t bad = air_program_first_bad_op(aux.ops, AIR_AUX_MAX_SHIFT + 1, main_cols, aux.consts.size() + n_rap, 0, 0);   // (no OUT: the columns name their ops; no periodic columns)
+    const size_t bad = air_program_first_bad_op(aux.ops, AIR_AUX_MAX_SHIFT + 1, main_cols, aux.consts.size() + n_rap, 0, n_periodic);   // (no OUT: the columns name their ops)
     if (bad < n_ops) {
         sp_set_error("aux program: malformed op " + std::to_string(bad) + " (LOAD needs a shift of 0 .. 7 and a main column, CONST a constant or a RAP "
-                     "challenge, ADD / SUB / MUL earlier ops; there is no OUT)");
+                     "challenge, ADD / SUB / MUL earlier ops; there is no OUT, and PERIODIC only through sp_air_prove_pub: a shift of 0 .. 7 and a periodic column)");
         return SP_E_INVALID_ARG;
     }
     for (size_t k = 0; k < aux.cols.size(); ++k) {
@@ -443,18 +443,23 @@ int validate_aux_program(const AirAuxHost& aux, uint32_t main_cols, uint32_t n_r
 // whatever the number of auxiliary columns.  The numerators are written straight into the trace columns they become.
 static constexpr uint64_t AUXP_CHUNK_ELEMS = 1ull << 22;
 
-int StarkProver::commit_aux_program(const AirAuxHost& aux, const std::vector<fe>& rap, uint8_t root_out[32]) {
+int StarkProver::commit_aux_program(const AirAuxHost& aux, const std::vector<fe>& rap, uint8_t root_out[32], const AirPeriodicHost* periodic) {
     const uint32_t K = (uint32_t)aux.cols.size();
     if (stage_ != Stage::MainCommitted || K == 0 || K != Ca_) { sp_set_error("commit_aux_program: main segment not committed or auxiliary column count differs"); return SP_E_STATE; }
-    SP_TRY(validate_aux_program(aux, Cm_, (uint32_t)rap.size()));
+    const uint32_t Kp = periodic ? (uint32_t)periodic->cols.size() : 0u;
+    bool periods_ok = Kp <= AIR_MAX_PERIODIC && (!periodic || air_periodic_fits(*periodic, n_));
+    for (uint32_t k = 0; k < Kp && periods_ok; ++k) periods_ok = sp_log2_exact(periodic->cols[k].size()) >= 0;
+    if (!periods_ok) { sp_set_error("commit_aux_program: more than 64 periodic columns, or a period that is no power of two or exceeds the trace length"); return SP_E_INVALID_ARG; }
+    SP_TRY(validate_aux_program(aux, Cm_, (uint32_t)rap.size(), Kp));
     SP_HIP_CHECK(hipSetDevice(c_->device));
     const uint32_t chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(K, AUXP_CHUNK_ELEMS / n_));
     const uint64_t nb = air_aux_scan_blocks(n_);
     // --- per chunk: the program with an OUT behind every op whose value is an N or a D of the chunk's columns (a value then lives
     //     only until it is stored), slots by air_assign_slots (which drops what the chunk does not need)
-    struct Chunk { uint32_t k0, kc, n_den; std::vector<AirOpDev> ops; std::vector<uint32_t> kinds, col_of; size_t o_ops, o_kinds, o_col; };
+    struct Chunk { uint32_t k0, kc, n_den; bool periodic; std::vector<AirOpDev> ops; std::vector<uint32_t> kinds, col_of; size_t o_ops, o_kinds, o_col; };
     std::vector<Chunk> chunks;
     uint32_t max_den = 0;
+    bool any_periodic = false;
     const uint32_t n_src = (uint32_t)aux.ops.size();
     for (uint32_t k0 = 0; k0 < K; k0 += chunk) {
         Chunk ch{};
@@ -471,12 +476,14 @@ int StarkProver::commit_aux_program(const AirAuxHost& aux, const std::vector<fe>
         ext.reserve(n_src + 2 * ch.kc);
         for (uint32_t t = 0; t < n_src; ++t) {
             AirOpHost o = aux.ops[t];
-            if (o.op >= 2) { o.a = at[o.a]; o.b = at[o.b]; }
+            if (o.op >= 2 && o.op <= 4) { o.a = at[o.a]; o.b = at[o.b]; }   // (LOAD, CONST and PERIODIC name cells, not values)
             at[t] = (uint32_t)ext.size();
             ext.push_back(o);
             for (uint32_t code : outs[t]) ext.push_back(AirOpHost{5, code, at[t]});
         }
         SP_TRY(air_assign_slots(ext, ch.ops, "aux program: more than 64 values alive at once"));
+        for (const AirOpDev& o : ch.ops) ch.periodic |= o.op == 6;   // (of what air_assign_slots kept: a table read that feeds an N or a D of this chunk)
+        any_periodic |= ch.periodic;
         max_den = std::max(max_den, ch.n_den);
         chunks.push_back(std::move(ch));
     }
@@ -488,6 +495,15 @@ int StarkProver::commit_aux_program(const AirAuxHost& aux, const std::vector<fe>
         ch.o_kinds = lay.place(sizeof(uint32_t) * ch.kc);
         ch.o_col = lay.place(sizeof(uint32_t) * std::max<uint32_t>(1, ch.n_den));
     }
+    // the periodic columns a chunk reads, as round 2's block holds them: AirPeriodicCol[] and the raw values, column k at pvals + off_k
+    std::vector<AirPeriodicCol> pcols;
+    uint64_t S = 0;
+    if (any_periodic)
+        for (uint32_t k = 0; k < Kp; ++k) {
+            pcols.push_back(AirPeriodicCol{(uint32_t)sp_log2_exact(periodic->cols[k].size()), 0u, S});
+            S += periodic->cols[k].size();
+        }
+    const size_t o_pcols = any_periodic ? lay.place(sizeof(AirPeriodicCol) * Kp) : 0, o_pvals = any_periodic ? lay.place(sizeof(fe) * S) : 0;
     const size_t bytes = lay.bytes;
     SP_TRY(grow(od_.auxp_buf, bytes));
     std::vector<uint8_t>& up = h_auxp_up_;
@@ -497,6 +513,10 @@ int StarkProver::commit_aux_program(const AirAuxHost& aux, const std::vector<fe>
         std::memcpy(up.data() + ch.o_ops, ch.ops.data(), sizeof(AirOpDev) * ch.ops.size());
         std::memcpy(up.data() + ch.o_kinds, ch.kinds.data(), sizeof(uint32_t) * ch.kc);
         if (ch.n_den) std::memcpy(up.data() + ch.o_col, ch.col_of.data(), sizeof(uint32_t) * ch.n_den);
+    }
+    if (any_periodic) {
+        std::memcpy(up.data() + o_pcols, pcols.data(), sizeof(AirPeriodicCol) * Kp);
+        for (uint32_t k = 0; k < Kp; ++k) std::memcpy(up.data() + o_pvals + sizeof(fe) * pcols[k].off, periodic->cols[k].data(), sizeof(fe) * periodic->cols[k].size());
     }
     SP_HIP_CHECK(hipMemcpyAsync(od_.auxp_buf.p, up.data(), bytes, hipMemcpyHostToDevice, c_->stream));
     // --- workspace: [max_den][n] denominators, as much batch-inversion scratch, [chunk][nb] scan block totals
@@ -510,7 +530,9 @@ int StarkProver::commit_aux_program(const AirAuxHost& aux, const std::vector<fe>
     for (const Chunk& ch : chunks) {
         fe* cols = d_trace_ + (uint64_t)(Cm_ + ch.k0) * n_;
         const uint32_t* kinds = reinterpret_cast<const uint32_t*>(od_.auxp_buf.p + ch.o_kinds);
-        SP_TRY(air_aux_terms(c_->stream, d_trace_, n_, reinterpret_cast<const AirOpDev*>(od_.auxp_buf.p + ch.o_ops), (uint32_t)ch.ops.size(), consts_dev, cols, den));
+        SP_TRY(air_aux_terms(c_->stream, d_trace_, n_, reinterpret_cast<const AirOpDev*>(od_.auxp_buf.p + ch.o_ops), (uint32_t)ch.ops.size(), consts_dev, cols, den,
+                             ch.periodic ? reinterpret_cast<const AirPeriodicCol*>(od_.auxp_buf.p + o_pcols) : nullptr,
+                             ch.periodic ? reinterpret_cast<const fe*>(od_.auxp_buf.p + o_pvals) : nullptr));
         if (ch.n_den) {
             SP_TRY(batch_inverse(c_->stream, den, scratch, (uint64_t)ch.n_den * n_, c_->d_flag));
             SP_TRY(air_aux_apply_den(c_->stream, cols, den, reinterpret_cast<const uint32_t*>(od_.auxp_buf.p + ch.o_col), ch.n_den, n_));

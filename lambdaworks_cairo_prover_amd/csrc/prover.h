@@ -19,7 +19,7 @@ namespace sp {
 
 // Checks an auxiliary program against its AIR (operands refer to earlier ops, LOADs to main columns at shifts 0 .. 7, CONSTs to
 // the constants or the n_rap challenges, every column's ops exist).  SP_E_INVALID_ARG with sp_last_error() set otherwise.
-int validate_aux_program(const AirAuxHost& aux, uint32_t main_cols, uint32_t n_rap);
+int validate_aux_program(const AirAuxHost& aux, uint32_t main_cols, uint32_t n_rap, uint32_t n_periodic = 0);   // n_periodic: the periodic columns op 6 may name (0: none, the old entry points)
 // Value slots of a straight-line program (ops 0 - 4 produce a value, op 5 OUT consumes op b): values that no OUT reads, directly
 // or through other values, are dropped; every other value gets one of AIR_MAX_LIVE slots, released after its last use.  The ops
 // must already be validated.  SP_E_UNSUPPORTED with `live_error` as sp_last_error() when more than AIR_MAX_LIVE are alive at once.
@@ -100,7 +100,8 @@ class StarkProver : public sp_deletable {
     int commit_aux_cairo(const PublicInputs& pub, const fe rap[3], uint8_t root_out[32]);
     // round 1, auxiliary segment of a program AIR built on the device from an auxiliary program (validate_aux_program first) and
     // the RAP challenges: per-row N and D, one batch inversion, an exclusive product / sum scan per column, commit_segment_resident
-    int commit_aux_program(const AirAuxHost& aux, const std::vector<fe>& rap, uint8_t root_out[32]);
+    // periodic (nullable): the columns the program may read with op 6 (a = row shift, b = column: values[(i + a) mod period]).
+    int commit_aux_program(const AirAuxHost& aux, const std::vector<fe>& rap, uint8_t root_out[32], const AirPeriodicHost* periodic = nullptr);
     // round 2: constraint composition, H1/H2 split, LDE and commitment
     int composition(const fe rap[3], const std::vector<BoundaryConstraint>& bcs, const std::vector<fe>& b_alpha,
                     const std::vector<fe>& b_beta, const std::vector<fe>& t_alpha, const std::vector<fe>& t_beta,
@@ -438,13 +439,17 @@ int cairo_prove(sp_ctx* ctx, const uint8_t* main_trace, uint64_t n, uint32_t col
 // round_ms: device time of rounds 1 - 4 in [1..4], as cairo_prove.
 // aux (nullable): the auxiliary program of an AIR with aux_kind SP_AIR_AUX_PROGRAM (sp_air_prove_aux).
 // periodic (nullable): the periodic columns its constraint program reads (sp_air_prove_periodic); without them op 6 is malformed.
+// pub: public data inside the RAP argument (sp_air_prove_pub) - boundary values resolved from the challenges after round 1, and whether the
+// auxiliary program may read the periodic columns.
+struct AirPublicHost { const AirBoundaryHost* bvals = nullptr; bool aux_reads_periodic = false; };
 int air_prove(sp_ctx* ctx, const AirDescHost& air, const uint8_t* main_trace, uint64_t n, const ProofOptionsHost& opt,
-              std::vector<uint8_t>& proof_out, float round_ms[5], const AirAuxHost* aux = nullptr, const AirPeriodicHost* periodic = nullptr);
+              std::vector<uint8_t>& proof_out, float round_ms[5], const AirAuxHost* aux = nullptr, const AirPeriodicHost* periodic = nullptr,
+              const AirPublicHost& pub = AirPublicHost());
 // Which constraints of a program AIR a trace breaks, and where (sp_air_check_trace): round 1 as air_prove runs it - the same ingest and
 // auxiliary builders -, then StarkProver::check_trace_air; no proof.  rap_given (nullable): the RAP challenges, instead of the ones a
 // proof under *opt would sample; opt may be null only with them.  One GPU (SP_E_UNSUPPORTED on a context with world > 1).
 int air_check_trace(sp_ctx* ctx, const AirDescHost& air, const uint8_t* main_trace, uint64_t n, const ProofOptionsHost* opt,
                     const std::vector<fe>* rap_given, std::vector<AirViolationHost>& out, const AirAuxHost* aux = nullptr,
-                    const AirPeriodicHost* periodic = nullptr);
+                    const AirPeriodicHost* periodic = nullptr, const AirPublicHost& pub = AirPublicHost());
 
 }  // namespace sp

@@ -418,7 +418,8 @@ int cairo_verify_host(const uint8_t* proof_bytes, size_t len, const PublicInputs
 }
 
 // `verify::<F, A>` for a program AIR (include/stark252_hip.h sp_air_desc); ops as in AirOpDev of stark_kernels.h.
-int air_verify_host(const uint8_t* proof_bytes, size_t len, const AirDescHost& air, const ProofOptionsHost& opt, const AirPeriodicHost* periodic) {
+int air_verify_host(const uint8_t* proof_bytes, size_t len, const AirDescHost& air, const ProofOptionsHost& opt, const AirPeriodicHost* periodic,
+                    const AirBoundaryHost* bvals) {
     const uint32_t C = air.main_cols + air.aux_cols, T = (uint32_t)air.degrees.size(), R = (uint32_t)air.offsets.size();
     if (T == 0 || R == 0 || air.exemptions.size() != T || air.degree_bound_factor < 1 || C < air.main_cols) return 0;   // (C < main_cols: the sum wrapped)
     const std::vector<AirOpHost>& ops = air.ops;
@@ -430,7 +431,12 @@ int air_verify_host(const uint8_t* proof_bytes, size_t len, const AirDescHost& a
     spec.main_cols = air.main_cols; spec.aux_cols = air.aux_cols; spec.offsets = air.offsets; spec.degrees = air.degrees; spec.exemptions = air.exemptions;
     spec.bound_factor = air.degree_bound_factor; spec.n_rap = air.n_rap;
     spec.strides = air.strides;   // checked against the proof's trace length where they were read (air_strides_from_c)
-    spec.boundary = [&air](const std::vector<fe>&) { return air.boundary; };
+    // boundary_constraints(rap_challenges) (traits.rs:44-47): the descriptor's constants, those of bvals computed from the challenges
+    spec.boundary = [&air, bvals](const std::vector<fe>& rap) {
+        std::vector<BoundaryConstraint> bcs = air.boundary;
+        if (bvals && !air_resolve_boundary_into(*bvals, rap, bcs)) throw std::runtime_error("rejected: a boundary value's denominator is zero under the proof's challenges");
+        return bcs;
+    };
     spec.transition = [&ops, &consts, C, T, Kp](const fe* frame, const fe* per, const std::vector<fe>& rap, fe* out) {
         std::vector<fe> v(ops.size(), fe_zero());
         for (uint32_t k = 0; k < T; ++k) out[k] = fe_zero();
@@ -448,6 +454,39 @@ int air_verify_host(const uint8_t* proof_bytes, size_t len, const AirDescHost& a
         }
     };
     return verify_host(proof_bytes, len, spec, opt.blowup_factor, opt.fri_number_of_queries, opt.coset_offset, opt.grinding_factor);
+}
+
+bool air_resolve_boundary(const AirBoundaryHost& bvals, const std::vector<fe>& rap, std::vector<fe>& values) {
+    const size_t nc = bvals.consts.size();
+    std::vector<fe> v(bvals.ops.size());
+    for (size_t t = 0; t < bvals.ops.size(); ++t) {
+        const AirOpHost& o = bvals.ops[t];
+        switch (o.op) {
+            case 1: v[t] = o.a < nc ? bvals.consts[o.a] : rap[o.a - nc]; break;
+            case 2: v[t] = fe_add(v[o.a], v[o.b]); break;
+            case 3: v[t] = fe_sub(v[o.a], v[o.b]); break;
+            default: v[t] = fe_mul(v[o.a], v[o.b]); break;
+        }
+    }
+    std::vector<fe> dens;
+    for (const AirBoundaryValueHost& e : bvals.values)
+        if (e.den_op != SP_AIR_AUX_NO_DEN) {
+            if (fe_is_zero(v[e.den_op])) return false;
+            dens.push_back(v[e.den_op]);
+        }
+    if (!dens.empty()) host_batch_inverse(dens);
+    values.clear();
+    size_t d = 0;
+    for (const AirBoundaryValueHost& e : bvals.values)
+        values.push_back(e.den_op != SP_AIR_AUX_NO_DEN ? fe_mul(v[e.num_op], dens[d++]) : v[e.num_op]);
+    return true;
+}
+
+bool air_resolve_boundary_into(const AirBoundaryHost& bvals, const std::vector<fe>& rap, std::vector<BoundaryConstraint>& boundary) {
+    std::vector<fe> values;
+    if (!air_resolve_boundary(bvals, rap, values)) return false;
+    for (size_t j = 0; j < values.size(); ++j) boundary[bvals.values[j].boundary].value = values[j];
+    return true;
 }
 
 // q from its values on <w_p>: an in-place radix-2 inverse transform (bit-reversal, then butterflies with w_p^-1), times 1/p

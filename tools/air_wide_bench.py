@@ -6,9 +6,11 @@ timed proofs on one GPU; prints one JSON line: the median and sp_last_round_ms o
 k_j + Q_j(i mod P), so its recurrence reads periodic column j, and the boundary values follow the changed trace.
 --stride K: every second constraint (1, 3, ...) enforced on the rows = 0 (mod K) only (sp_air_prove_ext; one stride class).  The trace
 is the same - it satisfies them on every row -, so the figure prices the class's tables and the strided terms of the composition.
+--lookup P: another shape altogether - air.table_lookup (two main columns, one auxiliary column, a public table of P values as periodic
+column 0) on 2^log-n rows through sp_air_prove_pub: round 1 (last_round_ms[0]) then holds the auxiliary program that reads the table.
 proof_sha256 lets two builds be held against each other byte for byte.
 
-    python tools/air_wide_bench.py [--boundary-rows 64] [--reps 5] [--log-n 18] [--periodic 8 --period 64] [--stride 8]
+    python tools/air_wide_bench.py [--boundary-rows 64] [--reps 5] [--log-n 18] [--periodic 8 --period 64] [--stride 8] [--lookup 64]
 """
 import argparse
 import hashlib
@@ -57,6 +59,16 @@ def build_periodic(n, cols, n_transitions, boundary_rows, boundary_total, k_peri
     return b, trace
 
 
+def build_lookup(n, period):
+    """air.table_lookup over the table 7, 10, 13, ... with row i looking up entry (5 i + 3) mod period; (builder, trace)."""
+    table = [7 + 3 * j for j in range(period)]
+    pick = (5 * np.arange(n, dtype=np.uint64) + 3) % np.uint64(period)
+    cells = np.stack([np.uint64(7) + np.uint64(3) * pick, np.bincount(pick.astype(np.int64), minlength=n).astype(np.uint64)], axis=1)
+    trace = np.zeros((n, 2, 32), dtype=np.uint8)
+    trace[:, :, 24:] = cells.astype(">u8").view(np.uint8).reshape(n, 2, 8)
+    return air.table_lookup(n, table), trace
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--boundary-rows", type=int, default=64)
@@ -65,9 +77,13 @@ def main():
     ap.add_argument("--periodic", type=int, default=0, help="periodic columns read by the first recurrences (0: the plain shape)")
     ap.add_argument("--period", type=int, default=64)
     ap.add_argument("--stride", type=int, default=0, help="put every second constraint on the rows = 0 (mod K) (0: none)")
+    ap.add_argument("--lookup", type=int, default=0, help="air.table_lookup against a table of this many values instead of the wide shape (0: the wide shape)")
     args = ap.parse_args()
     n, cols, options = 1 << args.log_n, 256, (4, 80, 3, 20)
-    if args.periodic:
+    if args.lookup:
+        b, trace = build_lookup(n, args.lookup)
+        cols = b.main_cols
+    elif args.periodic:
         b, trace = build_periodic(n, cols, 64, args.boundary_rows, 512, args.periodic, args.period)
     else:
         b = M.build(n, cols, n_transitions=64, boundary_row_count=args.boundary_rows, boundary_total=512)
@@ -88,7 +104,7 @@ def main():
         rounds = ctx.last_round_ms()
     print(json.dumps({"tool": "air_wide_bench", "rows": n, "main_cols": cols, "transitions": len(b.degrees), "ops": len(b.ops),
                       "constants": len(b.consts), "boundary_constraints": len(b.bcs), "boundary_rows": args.boundary_rows,
-                      "periodic_columns": args.periodic, "period": args.period if args.periodic else 0, "stride": args.stride,
+                      "periodic_columns": args.periodic, "period": args.period if args.periodic else 0, "stride": args.stride, "lookup": args.lookup,
                       "options": options, "proof_bytes": len(proof), "proof_sha256": hashlib.sha256(proof).hexdigest(), "median_ms": round(statistics.median(times), 2),
                       "min_ms": round(min(times), 2), "max_ms": round(max(times), 2), "last_round_ms": [round(x, 2) for x in rounds[1:]]}))
 
