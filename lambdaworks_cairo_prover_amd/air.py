@@ -194,6 +194,29 @@ def needs_pub(desc):
     return any(aux.ops[i].op == OP_PERIODIC for i in range(aux.n_ops)) if known is None else known
 
 
+def route(desc, call):
+    """Where a built descriptor goes for call = "prove", "check_trace" or "verify" - new entry points only when the descriptor needs
+    them: (the entry point's name, its arguments between `air` and the trace / the options, keepalive).  _pub for boundary values
+    computed from the challenges or an auxiliary program that reads a table, _ext for strides, else the parts one by one (the
+    verifier takes no auxiliary program)."""
+    def ref(part):
+        return None if part is None else ctypes.byref(part)
+    aux, per = getattr(desc, "aux_desc", None), getattr(desc, "periodic_desc", None)
+    if needs_pub(desc):
+        ext = ext_of(desc)
+        return f"sp_air_{call}_pub", (ctypes.byref(ext), ref(getattr(desc, "boundary_desc", None))), ext
+    if getattr(desc, "stride_desc", None) is not None:
+        ext = ext_of(desc)
+        return f"sp_air_{call}_ext", (ctypes.byref(ext),), ext
+    if call == "check_trace":
+        return "sp_air_check_trace", (ref(aux), ref(per)), None
+    if call == "verify":
+        return ("sp_air_verify_periodic", (ref(per),), None) if per is not None else ("sp_air_verify_backend", (), None)
+    if per is not None:
+        return "sp_air_prove_periodic", (ref(aux), ref(per)), None
+    return ("sp_air_prove_aux", (ref(aux),), None) if aux is not None else ("sp_air_prove", (), None)
+
+
 class AirViolationC(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_uint32), ("index", ctypes.c_uint32), ("rows", ctypes.c_uint64), ("first_row", ctypes.c_uint64),
                 ("last_row", ctypes.c_uint64), ("value", ctypes.c_uint8 * 32)]

@@ -232,25 +232,9 @@ class Context:
         opt = options.to_c()
         out = ctypes.POINTER(ctypes.c_uint8)()
         ln = ctypes.c_uint64()
-        aux = getattr(desc, "aux_desc", None)
-        per = getattr(desc, "periodic_desc", None)
         from . import air
-        if air.needs_pub(desc):
-            ext, bvals = air.ext_of(desc), getattr(desc, "boundary_desc", None)
-            check(self._lib.sp_air_prove_pub(self._h, ctypes.byref(desc), ctypes.byref(ext), None if bvals is None else ctypes.byref(bvals), _u8p(a),
-                                             ctypes.c_uint64(n), ctypes.byref(opt), ctypes.byref(out), ctypes.byref(ln)))
-        elif getattr(desc, "stride_desc", None) is not None:
-            ext = air.ext_of(desc)
-            check(self._lib.sp_air_prove_ext(self._h, ctypes.byref(desc), ctypes.byref(ext), _u8p(a), ctypes.c_uint64(n), ctypes.byref(opt),
-                                             ctypes.byref(out), ctypes.byref(ln)))
-        elif per is not None:
-            check(self._lib.sp_air_prove_periodic(self._h, ctypes.byref(desc), None if aux is None else ctypes.byref(aux), ctypes.byref(per), _u8p(a),
-                                                  ctypes.c_uint64(n), ctypes.byref(opt), ctypes.byref(out), ctypes.byref(ln)))
-        elif aux is not None:
-            check(self._lib.sp_air_prove_aux(self._h, ctypes.byref(desc), ctypes.byref(aux), _u8p(a), ctypes.c_uint64(n), ctypes.byref(opt),
-                                             ctypes.byref(out), ctypes.byref(ln)))
-        else:
-            check(self._lib.sp_air_prove(self._h, ctypes.byref(desc), _u8p(a), ctypes.c_uint64(n), ctypes.byref(opt), ctypes.byref(out), ctypes.byref(ln)))
+        name, parts, keep = air.route(desc, "prove")
+        check(getattr(self._lib, name)(self._h, ctypes.byref(desc), *parts, _u8p(a), ctypes.c_uint64(n), ctypes.byref(opt), ctypes.byref(out), ctypes.byref(ln)))
         proof = ctypes.string_at(out, ln.value)
         self._lib.sp_free(out)
         return proof
@@ -278,18 +262,9 @@ class Context:
                 rap_bytes[:] = be if self.fe_encoding == SP_FE_CANON_BE else fe_from_device(fe_to_device(be, SP_FE_CANON_BE), self.fe_encoding)
         out = (air.AirViolationC * max(1, cap))()
         total = ctypes.c_uint32(0)
-        aux = getattr(desc, "aux_desc", None)
-        per = getattr(desc, "periodic_desc", None)
-        tail = (_u8p(a), ctypes.c_uint64(n), None if opt is None else ctypes.byref(opt), None if rap_bytes is None else _u8p(rap_bytes),
-                out if cap else None, ctypes.c_uint32(cap), ctypes.byref(total))
-        if air.needs_pub(desc):
-            ext, bvals = air.ext_of(desc), getattr(desc, "boundary_desc", None)
-            check(self._lib.sp_air_check_trace_pub(self._h, ctypes.byref(desc), ctypes.byref(ext), None if bvals is None else ctypes.byref(bvals), *tail))
-        elif getattr(desc, "stride_desc", None) is not None:
-            ext = air.ext_of(desc)
-            check(self._lib.sp_air_check_trace_ext(self._h, ctypes.byref(desc), ctypes.byref(ext), *tail))
-        else:
-            check(self._lib.sp_air_check_trace(self._h, ctypes.byref(desc), None if aux is None else ctypes.byref(aux), None if per is None else ctypes.byref(per), *tail))
+        name, parts, keep = air.route(desc, "check_trace")
+        check(getattr(self._lib, name)(self._h, ctypes.byref(desc), *parts, _u8p(a), ctypes.c_uint64(n), None if opt is None else ctypes.byref(opt),
+                                       None if rap_bytes is None else _u8p(rap_bytes), out if cap else None, ctypes.c_uint32(cap), ctypes.byref(total)))
         self.last_check_total = total.value     # the number of violated constraints, which may exceed cap
         return [air.Violation(int(v.kind), int(v.index), int(v.rows), int(v.first_row), int(v.last_row), int.from_bytes(bytes(v.value), "big"))
                 for v in out[:min(cap, total.value)]]
@@ -578,17 +553,8 @@ def air_verify(proof, desc, options, merkle_backend=0):
     from . import air
     lib = _lib.load()
     opt = options.to_c()
-    per = getattr(desc, "periodic_desc", None)
-    if air.needs_pub(desc):
-        ext, bvals = air.ext_of(desc), getattr(desc, "boundary_desc", None)
-        return lib.sp_air_verify_pub(proof, ctypes.c_uint64(len(proof)), ctypes.byref(desc), ctypes.byref(ext), None if bvals is None else ctypes.byref(bvals),
-                                     ctypes.byref(opt), int(merkle_backend)) == 1
-    if getattr(desc, "stride_desc", None) is not None:
-        ext = air.ext_of(desc)
-        return lib.sp_air_verify_ext(proof, ctypes.c_uint64(len(proof)), ctypes.byref(desc), ctypes.byref(ext), ctypes.byref(opt), int(merkle_backend)) == 1
-    if per is not None:
-        return lib.sp_air_verify_periodic(proof, ctypes.c_uint64(len(proof)), ctypes.byref(desc), ctypes.byref(per), ctypes.byref(opt), int(merkle_backend)) == 1
-    return lib.sp_air_verify_backend(proof, ctypes.c_uint64(len(proof)), ctypes.byref(desc), ctypes.byref(opt), int(merkle_backend)) == 1
+    name, parts, keep = air.route(desc, "verify")
+    return getattr(lib, name)(proof, ctypes.c_uint64(len(proof)), ctypes.byref(desc), *parts, ctypes.byref(opt), int(merkle_backend)) == 1
 
 
 def poseidon_host(mode, values):

@@ -1,0 +1,280 @@
+// The statement of a program AIR on the host (air_desc.h): its one decoder and validator, and the model of its parts that the
+// prover, the trace check, the verifier and the test seams share - program rules, stride plans and zerofiers, boundary values from
+// the challenges, periodic columns as polynomials.
+#include "air_desc.h"
+#include "common.h"
+#include <algorithm>
+#include <stdexcept>
+
+namespace sp {
+
+fe air_root_of_unity(int order) {   // the field's 2^192-th root, squared down
+    fe w = fe_from_bytes_be((const uint8_t*)"\x00\x52\x82\xdb\x87\x52\x9c\xfa\x3f\x04\x64\x51\x9c\x8b\x0f\xa5\xad\x18\x71\x48\xe1\x1a\x61\x61\x60\x70\x02\x4f\x42\xf8\xef\x94");
+    for (int i = order; i < 192; ++i) w = fe_sqr(w);
+    return w;
+}
+
+size_t air_program_first_bad_op(const std::vector<AirOpHost>& ops, uint32_t load_a_end, uint32_t load_b_end, size_t n_values, uint32_t n_out,
+                                uint32_t n_periodic) {
+    auto value = [&](uint32_t i, size_t t) { return i < t && ops[i].op != 5; };   // an earlier op that produces a value
+    for (size_t t = 0; t < ops.size(); ++t) {
+        const AirOpHost& o = ops[t];
+        bool ok;
+        switch (o.op) {
+            case 0: ok = o.a < load_a_end && o.b < load_b_end; break;
+            case 1: ok = o.a < n_values; break;
+            case 2: case 3: case 4: ok = value(o.a, t) && value(o.b, t); break;
+            case 5: ok = o.a < n_out && value(o.b, t); break;
+            case 6: ok = o.a < load_a_end && o.b < n_periodic; break;
+            default: ok = false;
+        }
+        if (!ok) return t;
+    }
+    return ops.size();
+}
+
+// ---- the decoder: one function per part, each with one caller (air_boundary_from_c: sp_air_boundary_resolve too)
+namespace {
+template <class Op> void ops_from_c(const Op* ops, uint32_t n, std::vector<AirOpHost>& out) {
+    out.reserve(n);
+    for (uint32_t i = 0; i < n; ++i) out.push_back(AirOpHost{ops[i].op, ops[i].a, ops[i].b});
+}
+void consts_from_c(const uint8_t* consts, uint32_t n, std::vector<fe>& out) {
+    out.reserve(n);
+    for (uint32_t i = 0; i < n; ++i) out.push_back(fe_from_bytes_be(consts + 32 * (size_t)i));
+}
+
+// sp_air_desc -> AirDescHost; false for counts out of range or a count without its array
+bool air_desc_from_c(const sp_air_desc* d, AirDescHost& a) {
+    if (d->n_offsets == 0 || d->n_offsets > 8 || d->n_transitions == 0 || d->n_transitions > 64 || (d->n_ops && !d->ops) ||
+        (d->n_consts && !d->consts) || (d->n_boundary && !d->boundary)) return false;
+    a.main_cols = d->main_cols; a.aux_cols = d->aux_cols;
+    a.offsets.assign(d->offsets, d->offsets + d->n_offsets);
+    a.degrees.assign(d->degrees, d->degrees + d->n_transitions);
+    a.exemptions.assign(d->exemptions, d->exemptions + d->n_transitions);
+    a.num_transition_exemptions = d->num_transition_exemptions;
+    a.degree_bound_factor = d->degree_bound_factor;
+    ops_from_c(d->ops, d->n_ops, a.ops);
+    consts_from_c(d->consts, d->n_consts, a.consts);
+    a.n_rap = d->n_rap; a.aux_kind = d->aux_kind; a.aux_fn = d->aux_fn; a.aux_user = d->aux_user;
+    for (uint32_t i = 0; i < d->n_boundary; ++i)
+        a.boundary.push_back(BoundaryConstraint{d->boundary[i].col, d->boundary[i].step, fe_from_bytes_be(d->boundary[i].value)});
+    return true;
+}
+
+// sp_air_periodic_desc -> AirPeriodicHost for a trace of n rows; false for more than 64 columns, a count without its array, null
+// values, a period that is no power of two or exceeds n
+bool air_periodic_from_c(const sp_air_periodic_desc* d, uint64_t n, AirPeriodicHost& out) {
+    if (d->n_cols > AIR_MAX_PERIODIC || (d->n_cols && !d->cols)) return false;
+    for (uint32_t k = 0; k < d->n_cols; ++k) {   // every column first: nothing is allocated for a descriptor that is refused
+        const sp_air_periodic_column& c = d->cols[k];
+        if (c.period == 0 || (c.period & (c.period - 1)) || c.period > n || !c.values) return false;
+    }
+    for (uint32_t k = 0; k < d->n_cols; ++k) {
+        out.cols.emplace_back();
+        consts_from_c(d->cols[k].values, d->cols[k].period, out.cols.back());
+    }
+    return true;
+}
+
+// sp_air_stride_desc -> air.strides for a trace of n rows (a power of two), checked by air_stride_plan: prover, trace check and
+// verifier all read a descriptor's strides through here
+bool air_strides_from_c(const sp_air_stride_desc* d, uint64_t n, AirDescHost& air) {
+    if (d->n != air.exemptions.size() || !d->strides || sp_log2_exact(n) < 0) return false;
+    for (uint32_t k = 0; k < d->n; ++k) air.strides.push_back(AirStrideHost{d->strides[k].period, d->strides[k].offset});
+    AirStridePlan plan;
+    return air_stride_plan(air, n, plan);
+}
+
+// sp_air_aux_desc -> AirAuxHost, as far as the C view goes: its AIR wants one, counts have their arrays and stay within the bounds
+bool aux_from_c(const AirDescHost& air, const sp_air_aux_desc* x, AirAuxHost& aux) {
+    if (air.aux_kind != SP_AIR_AUX_PROGRAM || air.aux_cols == 0 || x->n_cols != air.aux_cols || (x->n_ops && !x->ops) || (x->n_consts && !x->consts) ||
+        !x->cols || x->n_ops > AIR_LIMIT_OPS || x->n_consts > AIR_LIMIT_CONSTS) return false;
+    ops_from_c(x->ops, x->n_ops, aux.ops);
+    consts_from_c(x->consts, x->n_consts, aux.consts);
+    for (uint32_t k = 0; k < x->n_cols; ++k) aux.cols.push_back(AirAuxColumnHost{x->cols[k].kind, x->cols[k].num_op, x->cols[k].den_op});
+    return true;
+}
+
+// The auxiliary program against its AIR: operands refer to earlier ops, LOADs to main columns at shifts 0 .. 7, CONSTs to the constants
+// or the n_rap challenges, PERIODICs to one of n_periodic columns (0: none), every column's ops exist.  "" or what is wrong.
+std::string validate_aux_program(const AirAuxHost& aux, uint32_t main_cols, uint32_t n_rap, uint32_t n_periodic) {
+    const size_t n_ops = aux.ops.size();
+    if (n_ops == 0) return "auxiliary program: no ops";
+    if (aux.consts.size() + n_rap > 65535) return "auxiliary program: constants and RAP challenges exceed the 16-bit operand range";
+    const size_t bad = air_program_first_bad_op(aux.ops, AIR_LIMIT_AUX_SHIFT + 1, main_cols, aux.consts.size() + n_rap, 0, n_periodic);   // (no OUT: the columns name their ops)
+    if (bad < n_ops)
+        return "auxiliary program: malformed op " + std::to_string(bad) + " (LOAD needs a shift of 0 .. 7 and a main column, CONST a constant or a RAP "
+               "challenge, ADD / SUB / MUL earlier ops; there is no OUT, and PERIODIC only through sp_air_prove_pub: a shift of 0 .. 7 and a periodic column)";
+    for (size_t k = 0; k < aux.cols.size(); ++k) {
+        const AirAuxColumnHost& c = aux.cols[k];
+        if (c.kind > SP_AIR_AUX_SUM || c.num_op >= n_ops || (c.den_op != SP_AIR_AUX_NO_DEN && c.den_op >= n_ops))
+            return "auxiliary program: column " + std::to_string(k) + " has an unknown kind or names an op beyond the program";
+    }
+    return "";
+}
+}  // namespace
+
+const char* const AIR_BOUNDARY_VALUES_MALFORMED = "malformed boundary values (ops 1 - 4 over earlier ops, each boundary < n_boundary and named once, num_op / den_op "
+                                                  "inside the program, the bounds of sp_air_limits)";
+bool air_boundary_from_c(const sp_air_boundary_desc* d, uint32_t n_boundary, uint32_t n_rap, AirBoundaryHost& out) {
+    if (!d->ops || !d->consts || !d->values || d->n_ops == 0 || d->n_ops > AIR_LIMIT_OPS || d->n_consts > AIR_LIMIT_CONSTS ||
+        (uint64_t)d->n_consts + n_rap > 65535 || d->n_values > AIR_LIMIT_BOUNDARY) return false;   // (all counts first: nothing is allocated for a descriptor that is refused)
+    std::vector<AirOpHost> ops;
+    ops_from_c(d->ops, d->n_ops, ops);
+    // (no cell to LOAD, no OUT target, no periodic column: ops 1 - 4 are all that is left)
+    if (air_program_first_bad_op(ops, 0, 0, (size_t)d->n_consts + n_rap, 0, 0) < ops.size()) return false;
+    std::vector<uint32_t> named;
+    for (uint32_t j = 0; j < d->n_values; ++j) {
+        const sp_air_boundary_value& e = d->values[j];
+        if (e.boundary >= n_boundary || e.num_op >= d->n_ops || (e.den_op != SP_AIR_AUX_NO_DEN && e.den_op >= d->n_ops)) return false;
+        named.push_back(e.boundary);
+    }
+    std::sort(named.begin(), named.end());
+    if (std::adjacent_find(named.begin(), named.end()) != named.end()) return false;
+    out.ops.swap(ops);
+    consts_from_c(d->consts, d->n_consts, out.consts);
+    for (uint32_t j = 0; j < d->n_values; ++j) out.values.push_back(AirBoundaryValueHost{d->values[j].boundary, d->values[j].num_op, d->values[j].den_op});
+    return true;
+}
+
+std::string air_statement_from_c(const sp_air_desc* d, const sp_air_aux_desc* aux, const sp_air_periodic_desc* periodic, const sp_air_stride_desc* strides,
+                                 const sp_air_boundary_desc* bvals, bool aux_reads_periodic, uint64_t n, AirStatement& st) {
+    AirDescHost& air = st.air;
+    st.aux_reads_periodic = aux_reads_periodic;
+    if (!air_desc_from_c(d, air)) return "malformed AIR descriptor (1 .. 8 frame rows, 1 .. 64 transition constraints, every count with its array)";
+    if (periodic && !air_periodic_from_c(periodic, n, st.periodic.emplace()))
+        return "malformed periodic columns (at most 64, each a power-of-two number of values, at most the trace length)";
+    if (strides && !air_strides_from_c(strides, n, air))
+        return "malformed strides (one per transition, a power-of-two period <= the trace length, offset < period, exemptions < n / period and degree <= "
+               "degree_bound_factor for a period > 1, at most 4 classes and 4 exemption products)";
+    if (aux && !aux_from_c(air, aux, st.aux.emplace()))
+        return "malformed auxiliary program (needs aux_kind SP_AIR_AUX_PROGRAM and aux->n_cols == air->aux_cols >= 1, every count with its array, at most "
+               "65535 ops and 4096 constants)";
+    if (bvals && !air_boundary_from_c(bvals, d->n_boundary, d->n_rap, st.bvals.emplace())) return AIR_BOUNDARY_VALUES_MALFORMED;
+    if (air.main_cols == 0 || (uint64_t)air.main_cols + air.aux_cols > AIR_LIMIT_COLS) return "column count out of range (1 .. 1024 columns, main + aux)";
+    if (air.boundary.size() > AIR_LIMIT_BOUNDARY) return "more than 4096 boundary constraints";
+    if (air.consts.size() > AIR_LIMIT_CONSTS) return "more than 4096 constants";
+    if (air.consts.size() + air.n_rap > 65535) return "constants and RAP challenges exceed the 16-bit operand range";
+    if (air.ops.size() > AIR_LIMIT_OPS) return "more than 65535 ops";
+    // (only the _pub entry points let an auxiliary program read the periodic columns: 0 of them from everywhere else)
+    if (st.aux) return validate_aux_program(*st.aux, air.main_cols, air.n_rap, st.aux_periodic() ? st.n_periodic() : 0u);
+    return "";
+}
+
+bool air_resolve_boundary(const AirBoundaryHost& bvals, const std::vector<fe>& rap, std::vector<fe>& values) {
+    const size_t nc = bvals.consts.size();
+    std::vector<fe> v(bvals.ops.size());
+    for (size_t t = 0; t < bvals.ops.size(); ++t) {
+        const AirOpHost& o = bvals.ops[t];
+        switch (o.op) {
+            case 1: v[t] = o.a < nc ? bvals.consts[o.a] : rap[o.a - nc]; break;
+            case 2: v[t] = fe_add(v[o.a], v[o.b]); break;
+            case 3: v[t] = fe_sub(v[o.a], v[o.b]); break;
+            default: v[t] = fe_mul(v[o.a], v[o.b]); break;
+        }
+    }
+    std::vector<fe> dens;
+    for (const AirBoundaryValueHost& e : bvals.values)
+        if (e.den_op != SP_AIR_AUX_NO_DEN) {
+            if (fe_is_zero(v[e.den_op])) return false;
+            dens.push_back(v[e.den_op]);
+        }
+    if (!dens.empty()) host_batch_inverse(dens);
+    values.clear();
+    size_t d = 0;
+    for (const AirBoundaryValueHost& e : bvals.values)
+        values.push_back(e.den_op != SP_AIR_AUX_NO_DEN ? fe_mul(v[e.num_op], dens[d++]) : v[e.num_op]);
+    return true;
+}
+
+bool air_resolve_boundary_into(const AirBoundaryHost& bvals, const std::vector<fe>& rap, std::vector<BoundaryConstraint>& boundary) {
+    std::vector<fe> values;
+    if (!air_resolve_boundary(bvals, rap, values)) return false;
+    for (size_t j = 0; j < values.size(); ++j) boundary[bvals.values[j].boundary].value = values[j];
+    return true;
+}
+
+// q from its values on <w_p>: an in-place radix-2 inverse transform (bit-reversal, then butterflies with w_p^-1), times 1/p
+std::vector<fe> air_periodic_interpolate(const std::vector<fe>& values) {
+    const size_t p = values.size();
+    const int lp = sp_log2_exact(p);
+    if (lp < 0) throw std::runtime_error("malformed: periodic column period");
+    std::vector<fe> a(p);
+    for (size_t i = 0; i < p; ++i) {
+        size_t r = 0;
+        for (int bit = 0; bit < lp; ++bit) r |= ((i >> bit) & 1) << (lp - 1 - bit);
+        a[r] = values[i];
+    }
+    const fe winv = lp ? fe_inv(air_root_of_unity(lp)) : fe_one();
+    for (int s = 1; s <= lp; ++s) {
+        const size_t m = size_t(1) << s, half = m >> 1;
+        const fe wm = fe_pow_u64(winv, p / m);
+        std::vector<fe> tw(half);
+        tw[0] = fe_one();
+        for (size_t j = 1; j < half; ++j) tw[j] = fe_mul(tw[j - 1], wm);
+        for (size_t k = 0; k < p; k += m)
+            for (size_t j = 0; j < half; ++j) {
+                const fe t = fe_mul(tw[j], a[k + j + half]), u = a[k + j];
+                a[k + j] = fe_add(u, t);
+                a[k + j + half] = fe_sub(u, t);
+            }
+    }
+    const fe pinv = fe_inv(fe_from_u64(p));
+    for (auto& x : a) x = fe_mul(x, pinv);
+    return a;
+}
+
+fe air_periodic_eval(const std::vector<fe>& coeffs, uint64_t n, const fe& point) {
+    const fe y = fe_pow_u64(point, n / coeffs.size());
+    fe acc = fe_zero();
+    for (size_t m = coeffs.size(); m-- > 0;) acc = fe_add(fe_mul(acc, y), coeffs[m]);
+    return acc;
+}
+
+bool air_stride_plan(const AirDescHost& air, uint64_t n, AirStridePlan& out) {
+    const size_t T = air.exemptions.size();
+    out = AirStridePlan{};
+    out.cls.assign(T, -1); out.kind.assign(T, -1);
+    if (air.strides.empty()) return true;
+    if (air.strides.size() != T) return false;
+    for (size_t k = 0; k < T; ++k) {
+        const uint32_t s = air.strides[k].period, o = air.strides[k].offset, e = air.exemptions[k];
+        if (s == 0 || (s & (s - 1)) || s > n || o >= s) return false;
+        if (s == 1) continue;
+        // C_k / Z_k has degree d n - n/s: the adjustment x^(n (f - d) + n/s) exists for d <= f only (a (1, 0) constraint may have d = f + 1)
+        if (e >= n / s || k >= air.degrees.size() || air.degrees[k] > air.degree_bound_factor) return false;
+        size_t q = 0;
+        while (q < out.classes.size() && (out.classes[q].period != s || out.classes[q].offset != o)) ++q;
+        if (q == out.classes.size()) {
+            if (q == AIR_MAX_STRIDE_CLASSES) return false;
+            out.classes.push_back(air.strides[k]);
+        }
+        out.cls[k] = (int)q;
+        if (!e) continue;
+        const std::pair<uint32_t, uint32_t> want((uint32_t)q, e);
+        size_t j = 0;
+        while (j < out.kinds.size() && out.kinds[j] != want) ++j;
+        if (j == out.kinds.size()) {
+            if (j == AIR_MAX_STRIDE_EXEMPT_KINDS) return false;
+            out.kinds.push_back(want);
+        }
+        out.kind[k] = (int)j;
+    }
+    return true;
+}
+
+void air_stride_eval(uint32_t s, uint32_t o, uint32_t e, uint64_t n, const fe& x, fe& Z, fe& E) {
+    const uint64_t m = n / s;                       // rows of the progression
+    const fe g = air_root_of_unity(sp_log2_exact(n));
+    Z = fe_sub(fe_pow_u64(x, m), fe_pow_u64(g, (uint64_t)o * m));
+    E = fe_one();
+    const fe gs_inv = fe_inv(fe_pow_u64(g, s));
+    fe root = fe_pow_u64(g, o + (uint64_t)s * (m - 1));   // the last row of the progression, then s rows down at a time
+    for (uint32_t t = 0; t < e; ++t) {
+        E = fe_mul(E, fe_sub(x, root));
+        root = fe_mul(root, gs_inv);
+    }
+}
+
+}  // namespace sp

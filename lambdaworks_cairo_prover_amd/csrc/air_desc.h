@@ -1,7 +1,10 @@
-// Host forms of the C views of include/stark252_hip.h that the prover and the verifier share: proof options, sp_air_desc,
-// sp_air_aux_desc, sp_air_periodic_desc, sp_air_stride_desc, and the well-formedness rules of their straight-line programs.  Host only (no device headers).
+// Host forms of the C views of include/stark252_hip.h that the prover and the verifier share: proof options, and the statement of a
+// program AIR - sp_air_desc with its optional parts sp_air_aux_desc, sp_air_periodic_desc, sp_air_stride_desc and sp_air_boundary_desc -
+// as one AirStatement, its one decoder and validator, and the host model of its parts.  Host only (no device headers); air_desc.cpp.
 #pragma once
 #include "cairo_air_host.h"
+#include <optional>
+#include <string>
 #include <utility>
 #include <vector>
 
@@ -30,8 +33,9 @@ struct AirDescHost {
     std::vector<BoundaryConstraint> boundary;
     std::vector<AirStrideHost> strides;   // per transition constraint (sp_air_stride_desc); empty: every constraint on every row
 };
-// sp_air_desc -> AirDescHost; false for a malformed descriptor (counts out of range, a count without its array).  capi_host.cpp
-bool air_desc_from_c(const sp_air_desc* d, AirDescHost& out);
+// The bounds of a statement (sp_air_limits reports them; prover.h holds them against the kernels' AIR_MAX_*), and the row shifts an
+// auxiliary program's LOAD and PERIODIC may name.
+constexpr uint32_t AIR_LIMIT_COLS = 1024, AIR_LIMIT_BOUNDARY = 4096, AIR_LIMIT_CONSTS = 4096, AIR_LIMIT_OPS = 65535, AIR_LIMIT_AUX_SHIFT = 7;
 
 // Host form of sp_air_aux_desc: the auxiliary program of an AIR with aux_kind SP_AIR_AUX_PROGRAM.
 struct AirAuxColumnHost { uint32_t kind, num_op, den_op; };
@@ -44,12 +48,8 @@ struct AirAuxHost {
 // Host form of sp_air_periodic_desc: column k repeats cols[k] (a power-of-two number of values, at most the trace length).
 constexpr uint32_t AIR_MAX_PERIODIC = 64;
 struct AirPeriodicHost { std::vector<std::vector<fe>> cols; };
-// sp_air_periodic_desc -> AirPeriodicHost for a trace of n rows; false - before anything is allocated or copied - for more than 64
-// columns, a count without its array, null values, a period that is no power of two or exceeds n.  capi_host.cpp
-bool air_periodic_from_c(const sp_air_periodic_desc* d, uint64_t n, AirPeriodicHost& out);
-bool air_periodic_fits(const AirPeriodicHost& p, uint64_t n);
 // P(point) of one periodic column on a trace of n rows: q interpolated from the values (a size-period inverse transform),
-// evaluated at point^(n / period).  What the verifier uses for P_k(z g^offset) and what sp_air_periodic_eval returns.  verifier.cpp
+// evaluated at point^(n / period).  What the verifier uses for P_k(z g^offset) and what sp_air_periodic_eval returns.
 std::vector<fe> air_periodic_interpolate(const std::vector<fe>& values);
 fe air_periodic_eval(const std::vector<fe>& coeffs, uint64_t n, const fe& point);
 
@@ -63,13 +63,10 @@ struct AirStridePlan {
 // false for strides that break a rule of sp_air_stride_desc: not one per transition, a period that is zero, no power of two or above
 // n, offset >= period, exemptions[k] >= n / period or degrees[k] > degree_bound_factor for a period > 1 (the quotient by the smaller
 // zerofier has degree d n - n/s, which fits under f n for d <= f only), more classes or exemption products than the limits.  Reads
-// air.strides / exemptions / degrees / degree_bound_factor only; empty strides give a plan without classes.  verifier.cpp
+// air.strides / exemptions / degrees / degree_bound_factor only; empty strides give a plan without classes.
 bool air_stride_plan(const AirDescHost& air, uint64_t n, AirStridePlan& out);
-// sp_air_stride_desc -> air.strides for a trace of n rows (a power of two): the one place where a descriptor's strides are checked
-// (air_stride_plan) - prover, trace check and verifier all read them through it; on false air.strides stays empty.  capi_host.cpp
-bool air_strides_from_c(const sp_air_stride_desc* d, uint64_t n, AirDescHost& air);
 // Z(x) = x^(n/s) - g^(o n/s) and E(x) = prod_{t<e} (x - g^(o + s (n/s - 1 - t))) of a stride (s, o) with e exempted rows on a trace of
-// n rows (all already checked: s | n, o < s, e <= n/s).  What the verifier's step 2 uses and sp_air_stride_eval returns.  verifier.cpp
+// n rows (all already checked: s | n, o < s, e <= n/s).  What the verifier's step 2 uses and sp_air_stride_eval returns.
 void air_stride_eval(uint32_t s, uint32_t o, uint32_t e, uint64_t n, const fe& x, fe& Z, fe& E);
 
 // Host form of sp_air_boundary_desc: boundary values that are N / D of a program over constants and the RAP challenges (ops 1 - 4).
@@ -81,10 +78,12 @@ struct AirBoundaryHost {
 };
 // sp_air_boundary_desc -> AirBoundaryHost for an AIR with n_boundary boundary constraints and n_rap challenges; false - before anything
 // is allocated or copied - for null members, counts beyond sp_air_limits, an op other than 1 - 4, an operand that is no earlier op,
-// boundary >= n_boundary, a boundary named twice, num_op / den_op beyond the program.  capi_host.cpp
+// boundary >= n_boundary, a boundary named twice, num_op / den_op beyond the program.  Called by air_statement_from_c, and by
+// sp_air_boundary_resolve with an unbounded n_boundary.
 bool air_boundary_from_c(const sp_air_boundary_desc* d, uint32_t n_boundary, uint32_t n_rap, AirBoundaryHost& out);
+extern const char* const AIR_BOUNDARY_VALUES_MALFORMED;   // what both callers say on false
 // The one resolver: values[j] = N_j / D_j under these challenges (one batch inversion).  false when a D is zero.  Prover, trace check,
-// verifier and sp_air_boundary_resolve all go through it.  verifier.cpp
+// verifier and sp_air_boundary_resolve all go through it.
 bool air_resolve_boundary(const AirBoundaryHost& bvals, const std::vector<fe>& rap, std::vector<fe>& values);
 // air.boundary with the resolved values put in: what everything behind round 1's challenges sees as constants.
 bool air_resolve_boundary_into(const AirBoundaryHost& bvals, const std::vector<fe>& rap, std::vector<BoundaryConstraint>& boundary);
@@ -93,8 +92,41 @@ bool air_resolve_boundary_into(const AirBoundaryHost& bvals, const std::vector<f
 // b < load_b_end, a CONST names one of n_values constants or RAP challenges, ADD / SUB / MUL take two earlier ops that are not
 // OUTs, an OUT one of n_out targets and such an op (n_out 0: no OUT at all), a PERIODIC a < load_a_end and one of n_periodic
 // periodic columns (0: the program cannot read any).  Returns the index of the first op that breaks them, ops.size() when none
-// does.  verifier.cpp
+// does.
 size_t air_program_first_bad_op(const std::vector<AirOpHost>& ops, uint32_t load_a_end, uint32_t load_b_end, size_t n_values, uint32_t n_out,
                                 uint32_t n_periodic);
+// the primitive root of unity of order 2^order (lambdaworks get_primitive_root_of_unity)
+fe air_root_of_unity(int order);
+
+// Everything a prover, a trace check or a verifier is told about a program AIR: the descriptor (its strides inside) and its optional
+// parts, each present or not.  aux_reads_periodic: whether the auxiliary program may read the periodic columns with op 6 (the _pub
+// entry points; everywhere else such an op is malformed).
+struct AirStatement {
+    AirDescHost air;
+    std::optional<AirAuxHost> aux;            // the auxiliary program of an AIR with aux_kind SP_AIR_AUX_PROGRAM
+    std::optional<AirPeriodicHost> periodic;  // the periodic columns the constraint program reads with op 6
+    std::optional<AirBoundaryHost> bvals;     // boundary values computed from the RAP challenges (air_resolve_boundary_into after round 1)
+    bool aux_reads_periodic = false;
+    // the periodic columns the auxiliary program may read: null when it may read none
+    const AirPeriodicHost* aux_periodic() const { return aux_reads_periodic && periodic ? &*periodic : nullptr; }
+    uint32_t n_periodic() const { return periodic ? (uint32_t)periodic->cols.size() : 0u; }
+};
+// The one decoder and validator of a statement for a trace of n rows: d and whichever of aux, periodic, strides (what sp_air_ext
+// carries) and bvals are non-null.  Returns "" and fills `out`, or the cause of the refusal (the entry point puts its own name in
+// front).  Every count and pointer of a part is judged before anything is allocated or copied for it.  The rules: those of
+// sp_air_desc's counts; <= 64 periodic columns, each a power-of-two number of values <= n; strides as air_stride_plan wants them;
+// an auxiliary program that fits its AIR (aux_kind, one column per auxiliary column, ops over earlier ops, LOADs of main columns at
+// shifts 0 .. 7, op 6 only with aux_reads_periodic); boundary values as air_boundary_from_c wants them; the bounds of sp_air_limits.
+// The constraint program itself is checked where it is turned into what runs it (build_air_program, air_verify_host).
+// An sp_air_ext is taken apart by the entry point that receives it; this is the one thing it checks first: null, or what is wrong.
+inline const char* air_ext_refusal(const sp_air_ext* ext) { return ext && ext->size != sizeof(sp_air_ext) ? "sp_air_ext.size is not sizeof(sp_air_ext)" : nullptr; }
+std::string air_statement_from_c(const sp_air_desc* d, const sp_air_aux_desc* aux, const sp_air_periodic_desc* periodic, const sp_air_stride_desc* strides,
+                                 const sp_air_boundary_desc* bvals, bool aux_reads_periodic, uint64_t n, AirStatement& out);
+// `verify::<F, A>` for a program AIR (verifier.cpp): 1 accept, 0 reject; throws std::runtime_error on a malformed proof or constraint
+// program.  st.aux is the prover's business and is not looked at.
+int air_verify_host(const uint8_t* proof_bytes, size_t len, const AirStatement& st, const ProofOptionsHost& opt);
+// The trace length a proof states (its first eight bytes): what a verifier holds a statement's periods and strides against before it
+// parses the rest.  Throws std::runtime_error for a shorter proof.  verifier.cpp
+uint64_t proof_trace_length(const uint8_t* proof_bytes, size_t len);
 
 }  // namespace sp

@@ -55,8 +55,6 @@ bool cairo_run_device_inputs(const sp_cairo_run* run, const TracePlan** plan, Tr
 }
 static thread_local std::string g_last_error;
 void sp_set_error(const std::string& s) { g_last_error = s; }
-namespace sp { int air_verify_host(const uint8_t* proof_bytes, size_t len, const AirDescHost& air, const ProofOptionsHost& opt, const AirPeriodicHost* periodic,
-                                   const AirBoundaryHost* bvals = nullptr); }
 namespace sp { void set_verify_merkle_backend(int backend); int host_bind_calling_thread_to_device_node(int device, int* node_out); }
 namespace sp { int cairo_verify_host(const uint8_t* proof_bytes, size_t len, const PublicInputs& pub, uint8_t blowup, uint64_t queries, uint64_t coset_offset, uint8_t grinding); }
 
@@ -77,70 +75,6 @@ PublicInputs public_inputs_from_c(const sp_cairo_public_inputs* p) {
     }
     r.num_steps = p->num_steps;
     return r;
-}
-
-bool air_desc_from_c(const sp_air_desc* d, AirDescHost& a) {
-    if (d->n_offsets == 0 || d->n_offsets > 8 || d->n_transitions == 0 || d->n_transitions > 64 || (d->n_ops && !d->ops) ||
-        (d->n_consts && !d->consts) || (d->n_boundary && !d->boundary)) return false;
-    a.main_cols = d->main_cols; a.aux_cols = d->aux_cols;
-    a.offsets.assign(d->offsets, d->offsets + d->n_offsets);
-    a.degrees.assign(d->degrees, d->degrees + d->n_transitions);
-    a.exemptions.assign(d->exemptions, d->exemptions + d->n_transitions);
-    a.num_transition_exemptions = d->num_transition_exemptions;
-    a.degree_bound_factor = d->degree_bound_factor;
-    for (uint32_t i = 0; i < d->n_ops; ++i) a.ops.push_back(AirOpHost{d->ops[i].op, d->ops[i].a, d->ops[i].b});
-    for (uint32_t i = 0; i < d->n_consts; ++i) a.consts.push_back(fe_from_bytes_be(d->consts + 32 * (size_t)i));
-    a.n_rap = d->n_rap; a.aux_kind = d->aux_kind; a.aux_fn = d->aux_fn; a.aux_user = d->aux_user;
-    for (uint32_t i = 0; i < d->n_boundary; ++i)
-        a.boundary.push_back(BoundaryConstraint{d->boundary[i].col, d->boundary[i].step, fe_from_bytes_be(d->boundary[i].value)});
-    return true;
-}
-
-bool air_periodic_from_c(const sp_air_periodic_desc* d, uint64_t n, AirPeriodicHost& out) {
-    if (d->n_cols > AIR_MAX_PERIODIC || (d->n_cols && !d->cols)) return false;
-    for (uint32_t k = 0; k < d->n_cols; ++k) {   // every column first: nothing is allocated for a descriptor that is refused
-        const sp_air_periodic_column& c = d->cols[k];
-        if (c.period == 0 || (c.period & (c.period - 1)) || c.period > n || !c.values) return false;
-    }
-    for (uint32_t k = 0; k < d->n_cols; ++k) {
-        const sp_air_periodic_column& c = d->cols[k];
-        std::vector<fe> v(c.period);
-        for (uint32_t j = 0; j < c.period; ++j) v[j] = fe_from_bytes_be(c.values + 32 * (size_t)j);
-        out.cols.push_back(std::move(v));
-    }
-    return true;
-}
-bool air_strides_from_c(const sp_air_stride_desc* d, uint64_t n, AirDescHost& air) {
-    if (d->n != air.exemptions.size() || !d->strides || sp_log2_exact(n) < 0) return false;
-    for (uint32_t k = 0; k < d->n; ++k) air.strides.push_back(AirStrideHost{d->strides[k].period, d->strides[k].offset});
-    AirStridePlan plan;
-    if (air_stride_plan(air, n, plan)) return true;
-    air.strides.clear();
-    return false;
-}
-bool air_boundary_from_c(const sp_air_boundary_desc* d, uint32_t n_boundary, uint32_t n_rap, AirBoundaryHost& out) {
-    if (!d->ops || !d->consts || !d->values || d->n_ops == 0 || d->n_ops > (uint32_t)AIR_MAX_OPS || d->n_consts > (uint32_t)AIR_MAX_CONSTS ||
-        (uint64_t)d->n_consts + n_rap > 65535 || d->n_values > (uint32_t)AIR_MAX_BOUNDARY) return false;
-    std::vector<AirOpHost> ops;
-    for (uint32_t i = 0; i < d->n_ops; ++i) ops.push_back(AirOpHost{d->ops[i].op, d->ops[i].a, d->ops[i].b});
-    // (no cell to LOAD, no OUT target, no periodic column: ops 1 - 4 are all that is left)
-    if (air_program_first_bad_op(ops, 0, 0, (size_t)d->n_consts + n_rap, 0, 0) < ops.size()) return false;
-    std::vector<uint32_t> named;
-    for (uint32_t j = 0; j < d->n_values; ++j) {
-        const sp_air_boundary_value& e = d->values[j];
-        if (e.boundary >= n_boundary || e.num_op >= d->n_ops || (e.den_op != SP_AIR_AUX_NO_DEN && e.den_op >= d->n_ops)) return false;
-        named.push_back(e.boundary);
-    }
-    std::sort(named.begin(), named.end());
-    if (std::adjacent_find(named.begin(), named.end()) != named.end()) return false;
-    out.ops.swap(ops);
-    for (uint32_t i = 0; i < d->n_consts; ++i) out.consts.push_back(fe_from_bytes_be(d->consts + 32 * (size_t)i));
-    for (uint32_t j = 0; j < d->n_values; ++j) out.values.push_back(AirBoundaryValueHost{d->values[j].boundary, d->values[j].num_op, d->values[j].den_op});
-    return true;
-}
-bool air_periodic_fits(const AirPeriodicHost& p, uint64_t n) {
-    for (const auto& c : p.cols) if (c.size() > n) return false;
-    return true;
 }
 }  // namespace sp
 
@@ -490,19 +424,6 @@ int sp_cairo_verify_backend(const uint8_t* proof, uint64_t proof_len, const sp_c
     return sp_cairo_verify(proof, proof_len, p, opt);
 }
 
-// verify::<Stark252PrimeField, A> (reference src/starks/verifier.rs:559-657) for a program AIR: 1 = accept, 0 = reject
-// (also for malformed proofs or descriptors).
-int sp_air_verify(const uint8_t* proof, uint64_t proof_len, const sp_air_desc* d, const sp_proof_options* opt) {
-    if (!proof || !d || !opt) return SP_E_INVALID_ARG;
-    try {
-        sp::AirDescHost air;
-        if (!sp::air_desc_from_c(d, air)) { sp_set_error("malformed: AIR descriptor"); return 0; }
-        const int ok = sp::air_verify_host(proof, proof_len, air, sp::proof_options_from_c(opt), nullptr);
-        sp_set_error(ok == 1 ? "" : "rejected: a verification step failed");
-        return ok;
-    } catch (const std::exception& e) { sp_set_error(e.what()); return 0; }
-}
-
 // The `verify` command of the reference CLI (src/main.rs:113-143): u64_be(len(proof)) || proof || PublicInputs::serialize, parsed and
 // handed to verify_cairo_proof.  1 = accepted; 0 otherwise, sp_last_error() as for sp_cairo_verify.
 int sp_proof_file_verify_backend(const uint8_t* file, uint64_t file_len, const sp_proof_options* opt, int merkle_backend) {
@@ -539,83 +460,54 @@ int sp_proof_file_encode(const uint8_t* proof, uint64_t proof_len, const sp_cair
     return SP_OK;
 }
 
-int sp_air_verify_backend(const uint8_t* proof, uint64_t proof_len, const sp_air_desc* d, const sp_proof_options* opt, int merkle_backend) {
-    if (merkle_backend != SP_MERKLE_KECCAK256 && merkle_backend != SP_MERKLE_POSEIDON) return SP_E_INVALID_ARG;
-    VerifyBackendScope scope(merkle_backend);
-    return sp_air_verify(proof, proof_len, d, opt);
-}
-
-// sp_air_verify_backend for an AIR whose constraint program reads periodic columns (op 6): the verifier evaluates them at the
-// out-of-domain frame's points itself; nothing about them is in the proof.
-int sp_air_verify_periodic(const uint8_t* proof, uint64_t proof_len, const sp_air_desc* d, const sp_air_periodic_desc* pd, const sp_proof_options* opt,
-                           int merkle_backend) {
-    if (!proof || !d || !pd || !opt) return SP_E_INVALID_ARG;
-    if (merkle_backend != SP_MERKLE_KECCAK256 && merkle_backend != SP_MERKLE_POSEIDON) return SP_E_INVALID_ARG;
-    VerifyBackendScope scope(merkle_backend);
-    try {
-        sp::AirDescHost air;
-        sp::AirPeriodicHost periodic;
-        if (!sp::air_desc_from_c(d, air)) { sp_set_error("malformed: AIR descriptor"); return 0; }
-        // the trace length is only known from the proof (its first eight bytes): the periods are held against it before anything is
-        // copied or interpolated
-        if (proof_len < 8) throw std::runtime_error("malformed: InvalidAmountOfBytes");
-        uint64_t n = 0;
-        for (int i = 0; i < 8; ++i) n = (n << 8) | proof[i];
-        if (!sp::air_periodic_from_c(pd, n, periodic)) { sp_set_error("malformed: periodic columns (at most 64, each a power-of-two number of values, at most the trace length)"); return 0; }
-        const int ok = sp::air_verify_host(proof, proof_len, air, sp::proof_options_from_c(opt), &periodic);
-        sp_set_error(ok == 1 ? "" : "rejected: a verification step failed");
-        return ok;
-    } catch (const std::exception& e) { sp_set_error(e.what()); return 0; }
-}
-
-static const char* const BOUNDARY_VALUES_MALFORMED = "malformed: boundary values (ops 1 - 4 over earlier ops, each boundary < n_boundary and named once, "
-                                                     "num_op / den_op inside the program, the bounds of sp_air_limits)";
-// sp_air_verify_backend / sp_air_verify_periodic with the extensions in one block: the strides of the transition constraints too.  The
-// auxiliary program of `ext` is the prover's business (the verifier sees the committed columns) and is not looked at.
-static int air_verify_ext_common(const uint8_t* proof, uint64_t proof_len, const sp_air_desc* d, const sp_air_ext* ext, const sp_air_boundary_desc* bv,
-                                 const sp_proof_options* opt, int merkle_backend) {
+// verify::<Stark252PrimeField, A> (reference src/starks/verifier.rs:559-657) for a program AIR: 1 = accept, 0 = reject (also for
+// malformed proofs or statements).  The one body of the sp_air_verify* entry points: the periodic columns come from pd or from ext,
+// the strides from ext; ext's auxiliary program is the prover's business (the verifier sees the committed columns) and is not looked
+// at.  The verifier evaluates periodic columns at the out-of-domain frame's points itself; nothing about them is in the proof.
+static int air_verify_body(const uint8_t* proof, uint64_t proof_len, const sp_air_desc* d, const sp_air_periodic_desc* pd, const sp_air_ext* ext,
+                           const sp_air_boundary_desc* bv, const sp_proof_options* opt, int merkle_backend) {
     if (!proof || !d || !opt) return SP_E_INVALID_ARG;
     if (merkle_backend != SP_MERKLE_KECCAK256 && merkle_backend != SP_MERKLE_POSEIDON) return SP_E_INVALID_ARG;
-    if (ext && ext->size != sizeof(sp_air_ext)) { sp_set_error("malformed: sp_air_ext.size is not sizeof(sp_air_ext)"); return 0; }
+    if (const char* bad = sp::air_ext_refusal(ext)) { sp_set_error(std::string("malformed: ") + bad); return 0; }
     VerifyBackendScope scope(merkle_backend);
     try {
-        sp::AirDescHost air;
-        sp::AirPeriodicHost periodic;
-        if (!sp::air_desc_from_c(d, air)) { sp_set_error("malformed: AIR descriptor"); return 0; }
-        if (proof_len < 8) throw std::runtime_error("malformed: InvalidAmountOfBytes");
-        uint64_t n = 0;   // the trace length is only known from the proof: periods and strides are held against it before anything is copied
-        for (int i = 0; i < 8; ++i) n = (n << 8) | proof[i];
-        const sp_air_periodic_desc* pd = ext ? ext->periodic : nullptr;
-        if (pd && !sp::air_periodic_from_c(pd, n, periodic)) { sp_set_error("malformed: periodic columns (at most 64, each a power-of-two number of values, at most the trace length)"); return 0; }
-        if (ext && ext->strides && !sp::air_strides_from_c(ext->strides, n, air)) {
-            sp_set_error("malformed: strides (one per transition, a power-of-two period <= the trace length, offset < period, exemptions < n / period and degree <= degree_bound_factor for a period > 1, at most 4 classes)");
-            return 0;
-        }
-        sp::AirBoundaryHost bvals;
-        if (bv && !sp::air_boundary_from_c(bv, d->n_boundary, d->n_rap, bvals)) { sp_set_error(BOUNDARY_VALUES_MALFORMED); return 0; }
-        const int ok = sp::air_verify_host(proof, proof_len, air, sp::proof_options_from_c(opt), pd ? &periodic : nullptr, bv ? &bvals : nullptr);
+        // the trace length is only known from the proof: periods and strides are held against it before anything is copied or interpolated
+        sp::AirStatement st;
+        const std::string refused = sp::air_statement_from_c(d, nullptr, ext ? ext->periodic : pd, ext ? ext->strides : nullptr, bv, false,
+                                                             sp::proof_trace_length(proof, proof_len), st);
+        if (!refused.empty()) { sp_set_error("malformed: " + refused); return 0; }
+        const int ok = sp::air_verify_host(proof, proof_len, st, sp::proof_options_from_c(opt));
         sp_set_error(ok == 1 ? "" : "rejected: a verification step failed");
         return ok;
     } catch (const std::exception& e) { sp_set_error(e.what()); return 0; }
 }
 
+int sp_air_verify(const uint8_t* proof, uint64_t proof_len, const sp_air_desc* d, const sp_proof_options* opt) {
+    return air_verify_body(proof, proof_len, d, nullptr, nullptr, nullptr, opt, SP_MERKLE_KECCAK256);
+}
+int sp_air_verify_backend(const uint8_t* proof, uint64_t proof_len, const sp_air_desc* d, const sp_proof_options* opt, int merkle_backend) {
+    return air_verify_body(proof, proof_len, d, nullptr, nullptr, nullptr, opt, merkle_backend);
+}
+int sp_air_verify_periodic(const uint8_t* proof, uint64_t proof_len, const sp_air_desc* d, const sp_air_periodic_desc* pd, const sp_proof_options* opt,
+                           int merkle_backend) {
+    if (!pd) return SP_E_INVALID_ARG;
+    return air_verify_body(proof, proof_len, d, pd, nullptr, nullptr, opt, merkle_backend);
+}
 int sp_air_verify_ext(const uint8_t* proof, uint64_t proof_len, const sp_air_desc* d, const sp_air_ext* ext, const sp_proof_options* opt,
                       int merkle_backend) {
-    return air_verify_ext_common(proof, proof_len, d, ext, nullptr, opt, merkle_backend);
+    return air_verify_body(proof, proof_len, d, nullptr, ext, nullptr, opt, merkle_backend);
 }
-
-// sp_air_verify_ext with boundary values computed from the proof's own RAP challenges (the auxiliary program, and so whether it reads
-// periodic columns, stays the prover's business).
+// sp_air_verify_ext with boundary values computed from the proof's own RAP challenges
 int sp_air_verify_pub(const uint8_t* proof, uint64_t proof_len, const sp_air_desc* d, const sp_air_ext* ext, const sp_air_boundary_desc* bv,
                       const sp_proof_options* opt, int merkle_backend) {
-    return air_verify_ext_common(proof, proof_len, d, ext, bv, opt, merkle_backend);
+    return air_verify_body(proof, proof_len, d, nullptr, ext, bv, opt, merkle_backend);
 }
 
 int sp_air_boundary_resolve(const sp_air_boundary_desc* bv, const uint8_t* rap, uint32_t n_rap, uint8_t* out) {
     if (!bv || (n_rap && !rap) || !out) return SP_E_INVALID_ARG;
     try {
         sp::AirBoundaryHost bvals;
-        if (!sp::air_boundary_from_c(bv, 0xFFFFFFFFu, n_rap, bvals)) { sp_set_error(BOUNDARY_VALUES_MALFORMED); return SP_E_INVALID_ARG; }
+        if (!sp::air_boundary_from_c(bv, 0xFFFFFFFFu, n_rap, bvals)) { sp_set_error(std::string("sp_air_boundary_resolve: ") + sp::AIR_BOUNDARY_VALUES_MALFORMED); return SP_E_INVALID_ARG; }
         std::vector<fe> r(n_rap), values;
         for (uint32_t i = 0; i < n_rap; ++i) r[i] = fe_from_bytes_be(rap + 32 * (size_t)i);
         if (!sp::air_resolve_boundary(bvals, r, values)) { sp_set_error("sp_air_boundary_resolve: a boundary value's denominator is zero"); return SP_E_ZERO_INVERSE; }
@@ -641,13 +533,13 @@ int sp_air_stride_eval(uint32_t period, uint32_t offset, uint32_t exemptions, ui
 int sp_air_periodic_eval(const sp_air_periodic_column* col, uint64_t n, const uint8_t point[32], uint8_t out[32]) {
     if (!col || !point || !out) return SP_E_INVALID_ARG;
     try {
-        const sp_air_periodic_desc one{1, 0, col};
-        sp::AirPeriodicHost p;
-        if (sp_log2_exact(n) < 0 || !sp::air_periodic_from_c(&one, n, p)) {
+        if (sp_log2_exact(n) < 0 || sp_log2_exact(col->period) < 0 || col->period > n || !col->values) {
             sp_set_error("sp_air_periodic_eval: n and the period must be powers of two, 1 <= period <= n");
             return SP_E_INVALID_ARG;
         }
-        fe_to_bytes_be(sp::air_periodic_eval(sp::air_periodic_interpolate(p.cols[0]), n, fe_from_bytes_be(point)), out);
+        std::vector<fe> values(col->period);
+        for (uint32_t j = 0; j < col->period; ++j) values[j] = fe_from_bytes_be(col->values + 32 * (size_t)j);
+        fe_to_bytes_be(sp::air_periodic_eval(sp::air_periodic_interpolate(values), n, fe_from_bytes_be(point)), out);
         return SP_OK;
     } catch (const std::exception& e) { sp_set_error(e.what()); return SP_E_INVALID_ARG; }
 }

@@ -362,95 +362,55 @@ int sp_last_round_ms(sp_ctx* c, float out[5]) {
     return SP_OK;
 }
 
-static const char* const STRIDES_MALFORMED = "malformed strides (one per transition, a power-of-two period <= the trace length, offset < period, "
-                                             "exemptions < n / period and degree <= degree_bound_factor for a period > 1, at most 4 classes and 4 exemption products)";
-static const char* const BOUNDARY_VALUES_MALFORMED = "malformed boundary values (ops 1 - 4 over earlier ops, each boundary < n_boundary and named once, num_op / den_op "
-                                                     "inside the program, the bounds of sp_air_limits)";
-static int air_prove_common(sp_ctx* c, const sp_air_desc* d, const sp::AirAuxHost* aux, const uint8_t* main_trace, uint64_t n,
-                            const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len, const sp::AirPeriodicHost* periodic = nullptr,
-                            const sp_air_stride_desc* strides = nullptr, const sp_air_boundary_desc* bv = nullptr, bool aux_reads_periodic = false) {
-    c->prewarm_cancel.store(0, std::memory_order_release);
-    sp::AirDescHost a;
-    if (!air_desc_from_c(d, a)) { sp_set_error("sp_air_prove: malformed descriptor"); return SP_E_INVALID_ARG; }
-    if (strides && !sp::air_strides_from_c(strides, n, a)) { sp_set_error(STRIDES_MALFORMED); return SP_E_INVALID_ARG; }
-    sp::AirBoundaryHost bvals;
-    if (bv && !sp::air_boundary_from_c(bv, d->n_boundary, d->n_rap, bvals)) { sp_set_error(BOUNDARY_VALUES_MALFORMED); return SP_E_INVALID_ARG; }
-    std::vector<uint8_t> proof;
-    float ms[5] = {0, 0, 0, 0, 0};
-    SP_TRY(sp::air_prove(c, a, main_trace, n, proof_options_from_c(opt), proof, ms, aux, periodic, sp::AirPublicHost{bv ? &bvals : nullptr, aux_reads_periodic}));
-    return publish_proof(c, ms, proof, proof_out, proof_len);
+// ---- program AIRs.  Every entry point is a null check of what it insists on, the statement decoded from its own subset of the parts
+// (sp::air_statement_from_c: the one place where they are judged), and one of the two bodies below (the verifiers' is in capi_host.cpp).
+namespace {
+// The parts of a statement as an entry point received them; with `ext` given, its members (the entry points that take an sp_air_ext
+// take no single parts beside it).
+struct AirParts {
+    const sp_air_aux_desc* aux; const sp_air_periodic_desc* periodic; const sp_air_stride_desc* strides; const sp_air_boundary_desc* bvals; bool aux_reads_periodic;
+    static AirParts of_ext(const sp_air_ext* ext, const sp_air_boundary_desc* bvals, bool aux_reads_periodic) {
+        return AirParts{ext ? ext->aux : nullptr, ext ? ext->periodic : nullptr, ext ? ext->strides : nullptr, bvals, aux_reads_periodic};
+    }
+};
+bool ext_ok(const sp_air_ext* ext) {
+    const char* bad = sp::air_ext_refusal(ext);
+    if (bad) sp_set_error(bad);
+    return !bad;
+}
+int decode(const char* who, const sp_air_desc* d, const AirParts& p, uint64_t n, sp::AirStatement& st) {
+    const std::string refused = sp::air_statement_from_c(d, p.aux, p.periodic, p.strides, p.bvals, p.aux_reads_periodic, n, st);
+    if (refused.empty()) return SP_OK;
+    sp_set_error(std::string(who) + ": " + refused);
+    return SP_E_INVALID_ARG;
 }
 
-int sp_air_prove(sp_ctx* c, const sp_air_desc* d, const uint8_t* main_trace, uint64_t n, const sp_proof_options* opt,
-                 uint8_t** proof_out, uint64_t* proof_len) {
+int air_prove_body(sp_ctx* c, const sp_air_desc* d, const AirParts& p, const uint8_t* main_trace, uint64_t n, const sp_proof_options* opt, uint8_t** proof_out,
+                   uint64_t* proof_len) {
     if (!c || !d || !main_trace || !opt || !proof_out || !proof_len) return SP_E_INVALID_ARG;
-    return air_prove_common(c, d, nullptr, main_trace, n, opt, proof_out, proof_len);
-}
-
-// sp_air_aux_desc -> AirAuxHost, checked against its AIR as far as the C view goes (the program itself: validate_aux_program)
-static int aux_from_c(const sp_air_desc* d, const sp_air_aux_desc* x, sp::AirAuxHost& aux) {
-    if (d->aux_kind != SP_AIR_AUX_PROGRAM || d->aux_cols == 0 || x->n_cols != d->aux_cols) {
-        sp_set_error("sp_air_prove_aux: needs aux_kind SP_AIR_AUX_PROGRAM and aux->n_cols == air->aux_cols >= 1");
-        return SP_E_INVALID_ARG;
-    }
-    if ((x->n_ops && !x->ops) || (x->n_consts && !x->consts) || !x->cols) { sp_set_error("sp_air_prove_aux: malformed auxiliary program"); return SP_E_INVALID_ARG; }
-    if (x->n_ops > (uint32_t)sp::AIR_MAX_OPS || x->n_consts > (uint32_t)sp::AIR_MAX_CONSTS) {
-        sp_set_error("sp_air_prove_aux: the auxiliary program exceeds 65535 ops or 4096 constants");
-        return SP_E_INVALID_ARG;
-    }
-    for (uint32_t i = 0; i < x->n_ops; ++i) aux.ops.push_back(sp::AirOpHost{x->ops[i].op, x->ops[i].a, x->ops[i].b});
-    for (uint32_t i = 0; i < x->n_consts; ++i) aux.consts.push_back(fe_from_bytes_be(x->consts + 32 * (size_t)i));
-    for (uint32_t k = 0; k < x->n_cols; ++k) aux.cols.push_back(sp::AirAuxColumnHost{x->cols[k].kind, x->cols[k].num_op, x->cols[k].den_op});
-    return SP_OK;
-}
-
-int sp_air_prove_aux(sp_ctx* c, const sp_air_desc* d, const sp_air_aux_desc* x, const uint8_t* main_trace, uint64_t n,
-                     const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len) {
-    if (!c || !d || !x || !main_trace || !opt || !proof_out || !proof_len) return SP_E_INVALID_ARG;
-    sp::AirAuxHost aux;
-    SP_TRY(aux_from_c(d, x, aux));
-    return air_prove_common(c, d, &aux, main_trace, n, opt, proof_out, proof_len);
-}
-
-int sp_air_prove_periodic(sp_ctx* c, const sp_air_desc* d, const sp_air_aux_desc* x, const sp_air_periodic_desc* pd, const uint8_t* main_trace,
-                          uint64_t n, const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len) {
-    if (!c || !d || !pd || !main_trace || !opt || !proof_out || !proof_len) return SP_E_INVALID_ARG;
     try {
-        sp::AirPeriodicHost periodic;
-        if (!sp::air_periodic_from_c(pd, n, periodic)) {
-            sp_set_error("sp_air_prove_periodic: malformed periodic columns (at most 64, each a power-of-two number of values, at most the trace length)");
-            return SP_E_INVALID_ARG;
-        }
-        sp::AirAuxHost aux;
-        if (x) SP_TRY(aux_from_c(d, x, aux));
-        return air_prove_common(c, d, x ? &aux : nullptr, main_trace, n, opt, proof_out, proof_len, &periodic);
+        sp::AirStatement st;
+        SP_TRY(decode("sp_air_prove", d, p, n, st));
+        c->prewarm_cancel.store(0, std::memory_order_release);
+        std::vector<uint8_t> proof;
+        float ms[5] = {0, 0, 0, 0, 0};
+        SP_TRY(sp::air_prove(c, st, main_trace, n, proof_options_from_c(opt), proof, ms));
+        return publish_proof(c, ms, proof, proof_out, proof_len);
     } catch (const std::exception& e) { sp_set_error(e.what()); return SP_E_INVALID_ARG; }
 }
 
-static int air_check_trace_common(sp_ctx* c, const sp_air_desc* d, const sp_air_aux_desc* x, const sp_air_periodic_desc* pd, const sp_air_stride_desc* sd,
-                                  const uint8_t* main_trace, uint64_t n, const sp_proof_options* opt, const uint8_t* rap, sp_air_violation* out, uint32_t cap,
-                                  uint32_t* n_out, const sp_air_boundary_desc* bv = nullptr, bool aux_reads_periodic = false) {
+int air_check_trace_body(sp_ctx* c, const sp_air_desc* d, const AirParts& p, const uint8_t* main_trace, uint64_t n, const sp_proof_options* opt,
+                         const uint8_t* rap, sp_air_violation* out, uint32_t cap, uint32_t* n_out) {
     if (!c || !d || !main_trace || !n_out || (!opt && !rap) || (!out && cap)) return SP_E_INVALID_ARG;
     try {
-        sp::AirDescHost a;
-        if (!air_desc_from_c(d, a)) { sp_set_error("sp_air_check_trace: malformed descriptor"); return SP_E_INVALID_ARG; }
-        sp::AirPeriodicHost periodic;
-        if (pd && !sp::air_periodic_from_c(pd, n, periodic)) {
-            sp_set_error("sp_air_check_trace: malformed periodic columns (at most 64, each a power-of-two number of values, at most the trace length)");
-            return SP_E_INVALID_ARG;
-        }
-        if (sd && !sp::air_strides_from_c(sd, n, a)) { sp_set_error(STRIDES_MALFORMED); return SP_E_INVALID_ARG; }
-        sp::AirAuxHost aux;
-        if (x) SP_TRY(aux_from_c(d, x, aux));
-        sp::AirBoundaryHost bvals;
-        if (bv && !sp::air_boundary_from_c(bv, d->n_boundary, d->n_rap, bvals)) { sp_set_error(BOUNDARY_VALUES_MALFORMED); return SP_E_INVALID_ARG; }
-        c->prewarm_cancel.store(0, std::memory_order_release);   // (the context is first touched here: the descriptors are judged without it)
-        std::vector<fe> rap_fe(a.n_rap);
-        if (rap && a.n_rap) SP_TRY(dec(c, rap, a.n_rap, rap_fe.data()));
+        sp::AirStatement st;
+        SP_TRY(decode("sp_air_check_trace", d, p, n, st));
+        c->prewarm_cancel.store(0, std::memory_order_release);   // (the context is first touched here: the statement is judged without it)
+        std::vector<fe> rap_fe(st.air.n_rap);
+        if (rap && st.air.n_rap) SP_TRY(dec(c, rap, st.air.n_rap, rap_fe.data()));
         const sp::ProofOptionsHost oh = opt ? proof_options_from_c(opt) : sp::ProofOptionsHost{};
         std::vector<sp::AirViolationHost> found;
-        SP_TRY(sp::air_check_trace(c, a, main_trace, n, opt ? &oh : nullptr, rap ? &rap_fe : nullptr, found, x ? &aux : nullptr, pd ? &periodic : nullptr,
-                                   sp::AirPublicHost{bv ? &bvals : nullptr, aux_reads_periodic}));
+        SP_TRY(sp::air_check_trace(c, st, main_trace, n, opt ? &oh : nullptr, rap ? &rap_fe : nullptr, found));
         *n_out = (uint32_t)found.size();
         for (size_t i = 0; i < found.size() && i < cap; ++i) {
             const sp::AirViolationHost& v = found[i];
@@ -460,60 +420,49 @@ static int air_check_trace_common(sp_ctx* c, const sp_air_desc* d, const sp_air_
         return SP_OK;
     } catch (const std::exception& e) { sp_set_error(e.what()); return SP_E_INVALID_ARG; }
 }
+}  // namespace
 
-int sp_air_check_trace(sp_ctx* c, const sp_air_desc* d, const sp_air_aux_desc* x, const sp_air_periodic_desc* pd, const uint8_t* main_trace,
-                       uint64_t n, const sp_proof_options* opt, const uint8_t* rap, sp_air_violation* out, uint32_t cap, uint32_t* n_out) {
-    return air_check_trace_common(c, d, x, pd, nullptr, main_trace, n, opt, rap, out, cap, n_out);
+int sp_air_prove(sp_ctx* c, const sp_air_desc* d, const uint8_t* main_trace, uint64_t n, const sp_proof_options* opt,
+                 uint8_t** proof_out, uint64_t* proof_len) {
+    return air_prove_body(c, d, AirParts{}, main_trace, n, opt, proof_out, proof_len);
 }
-
+int sp_air_prove_aux(sp_ctx* c, const sp_air_desc* d, const sp_air_aux_desc* x, const uint8_t* main_trace, uint64_t n,
+                     const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len) {
+    if (!x) return SP_E_INVALID_ARG;
+    return air_prove_body(c, d, AirParts{x}, main_trace, n, opt, proof_out, proof_len);
+}
+int sp_air_prove_periodic(sp_ctx* c, const sp_air_desc* d, const sp_air_aux_desc* x, const sp_air_periodic_desc* pd, const uint8_t* main_trace,
+                          uint64_t n, const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len) {
+    if (!pd) return SP_E_INVALID_ARG;
+    return air_prove_body(c, d, AirParts{x, pd}, main_trace, n, opt, proof_out, proof_len);
+}
 // The extensions in one block (sp_air_ext): what sp_air_prove, _aux, _periodic and sp_air_check_trace take one by one, and the strides.
-static bool ext_ok(const sp_air_ext* ext) {
-    if (ext && ext->size != sizeof(sp_air_ext)) { sp_set_error("sp_air_ext.size is not sizeof(sp_air_ext)"); return false; }
-    return true;
-}
-
-static int air_prove_ext_common(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const sp_air_boundary_desc* bv, bool aux_reads_periodic,
-                               const uint8_t* main_trace, uint64_t n, const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len) {
-    if (!c || !d || !main_trace || !opt || !proof_out || !proof_len || !ext_ok(ext)) return SP_E_INVALID_ARG;
-    try {
-        sp::AirPeriodicHost periodic;
-        const sp_air_periodic_desc* pd = ext ? ext->periodic : nullptr;
-        if (pd && !sp::air_periodic_from_c(pd, n, periodic)) {
-            sp_set_error("sp_air_prove_ext: malformed periodic columns (at most 64, each a power-of-two number of values, at most the trace length)");
-            return SP_E_INVALID_ARG;
-        }
-        sp::AirAuxHost aux;
-        const sp_air_aux_desc* x = ext ? ext->aux : nullptr;
-        if (x) SP_TRY(aux_from_c(d, x, aux));
-        return air_prove_common(c, d, x ? &aux : nullptr, main_trace, n, opt, proof_out, proof_len, pd ? &periodic : nullptr, ext ? ext->strides : nullptr, bv,
-                                aux_reads_periodic);
-    } catch (const std::exception& e) { sp_set_error(e.what()); return SP_E_INVALID_ARG; }
-}
-
 int sp_air_prove_ext(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const uint8_t* main_trace, uint64_t n, const sp_proof_options* opt,
                      uint8_t** proof_out, uint64_t* proof_len) {
-    return air_prove_ext_common(c, d, ext, nullptr, false, main_trace, n, opt, proof_out, proof_len);
+    if (!ext_ok(ext)) return SP_E_INVALID_ARG;
+    return air_prove_body(c, d, AirParts::of_ext(ext, nullptr, false), main_trace, n, opt, proof_out, proof_len);
 }
-
 // sp_air_prove_ext with public data inside the RAP argument: boundary values computed from the challenges (bv, nullable), and an
 // auxiliary program that may read ext->periodic with op 6.
 int sp_air_prove_pub(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const sp_air_boundary_desc* bv, const uint8_t* main_trace, uint64_t n,
                      const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len) {
-    return air_prove_ext_common(c, d, ext, bv, true, main_trace, n, opt, proof_out, proof_len);
-}
-
-int sp_air_check_trace_pub(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const sp_air_boundary_desc* bv, const uint8_t* main_trace, uint64_t n,
-                           const sp_proof_options* opt, const uint8_t* rap, sp_air_violation* out, uint32_t cap, uint32_t* n_out) {
     if (!ext_ok(ext)) return SP_E_INVALID_ARG;
-    return air_check_trace_common(c, d, ext ? ext->aux : nullptr, ext ? ext->periodic : nullptr, ext ? ext->strides : nullptr, main_trace, n, opt, rap,
-                                  out, cap, n_out, bv, true);
+    return air_prove_body(c, d, AirParts::of_ext(ext, bv, true), main_trace, n, opt, proof_out, proof_len);
 }
 
+int sp_air_check_trace(sp_ctx* c, const sp_air_desc* d, const sp_air_aux_desc* x, const sp_air_periodic_desc* pd, const uint8_t* main_trace,
+                       uint64_t n, const sp_proof_options* opt, const uint8_t* rap, sp_air_violation* out, uint32_t cap, uint32_t* n_out) {
+    return air_check_trace_body(c, d, AirParts{x, pd}, main_trace, n, opt, rap, out, cap, n_out);
+}
 int sp_air_check_trace_ext(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const uint8_t* main_trace, uint64_t n, const sp_proof_options* opt,
                            const uint8_t* rap, sp_air_violation* out, uint32_t cap, uint32_t* n_out) {
     if (!ext_ok(ext)) return SP_E_INVALID_ARG;
-    return air_check_trace_common(c, d, ext ? ext->aux : nullptr, ext ? ext->periodic : nullptr, ext ? ext->strides : nullptr, main_trace, n, opt, rap,
-                                  out, cap, n_out);
+    return air_check_trace_body(c, d, AirParts::of_ext(ext, nullptr, false), main_trace, n, opt, rap, out, cap, n_out);
+}
+int sp_air_check_trace_pub(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const sp_air_boundary_desc* bv, const uint8_t* main_trace, uint64_t n,
+                           const sp_proof_options* opt, const uint8_t* rap, sp_air_violation* out, uint32_t cap, uint32_t* n_out) {
+    if (!ext_ok(ext)) return SP_E_INVALID_ARG;
+    return air_check_trace_body(c, d, AirParts::of_ext(ext, bv, true), main_trace, n, opt, rap, out, cap, n_out);
 }
 
 }  // extern "C"

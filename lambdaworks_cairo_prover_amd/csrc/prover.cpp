@@ -416,41 +416,17 @@ int StarkProver::commit_aux_cairo(const PublicInputs& pub, const fe rap[3], uint
     return commit_segment_resident(1, Ca_, root_out);
 }
 
-int validate_aux_program(const AirAuxHost& aux, uint32_t main_cols, uint32_t n_rap, uint32_t n_periodic) {
-    const size_t n_ops = aux.ops.size();
-    if (n_ops == 0 || n_ops > (size_t)AIR_MAX_OPS) { sp_set_error("aux program: 1 .. 65535 ops"); return SP_E_INVALID_ARG; }
-    if (aux.consts.size() > (size_t)AIR_MAX_CONSTS) { sp_set_error("aux program: more than 4096 constants"); return SP_E_INVALID_ARG; }
-    if (aux.consts.size() + n_rap > 65535) { sp_set_error("aux program: constants and RAP challenges exceed the 16-bit operand range"); return SP_E_INVALID_ARG; }
-    if (aux.cols.empty() || aux.cols.size() > (size_t)AIR_MAX_COLS) { sp_set_error("aux program: 1 .. 1024 auxiliary columns"); return SP_E_INVALID_ARG; }
-    const size_t bad = air_program_first_bad_op(aux.ops, AIR_AUX_MAX_SHIFT + 1, main_cols, aux.consts.size() + n_rap, 0, n_periodic);   // (no OUT: the columns name their ops)
-    if (bad < n_ops) {
-        sp_set_error("aux program: malformed op " + std::to_string(bad) + " (LOAD needs a shift of 0 .. 7 and a main column, CONST a constant or a RAP "
-                     "challenge, ADD / SUB / MUL earlier ops; there is no OUT, and PERIODIC only through sp_air_prove_pub: a shift of 0 .. 7 and a periodic column)");
-        return SP_E_INVALID_ARG;
-    }
-    for (size_t k = 0; k < aux.cols.size(); ++k) {
-        const AirAuxColumnHost& c = aux.cols[k];
-        if (c.kind > SP_AIR_AUX_SUM || c.num_op >= n_ops || (c.den_op != SP_AIR_AUX_NO_DEN && c.den_op >= n_ops)) {
-            sp_set_error("aux program: column " + std::to_string(k) + " has an unknown kind or names an op beyond the program");
-            return SP_E_INVALID_ARG;
-        }
-    }
-    return SP_OK;
-}
-
 // Chunks of columns bound the workspace: a chunk holds at most max(1, AUXP_CHUNK_ELEMS / n) columns, so its denominators take
 // at most max(2^22, n) elements (128 MB up to 2^22 rows, 32 bytes a row beyond) and the batch inversion as much scratch again,
 // whatever the number of auxiliary columns.  The numerators are written straight into the trace columns they become.
 static constexpr uint64_t AUXP_CHUNK_ELEMS = 1ull << 22;
 
-int StarkProver::commit_aux_program(const AirAuxHost& aux, const std::vector<fe>& rap, uint8_t root_out[32], const AirPeriodicHost* periodic) {
+int StarkProver::commit_aux_program(const AirStatement& st, const std::vector<fe>& rap, uint8_t root_out[32]) {
+    const AirAuxHost& aux = *st.aux;
+    const AirPeriodicHost* periodic = st.aux_periodic();
     const uint32_t K = (uint32_t)aux.cols.size();
     if (stage_ != Stage::MainCommitted || K == 0 || K != Ca_) { sp_set_error("commit_aux_program: main segment not committed or auxiliary column count differs"); return SP_E_STATE; }
     const uint32_t Kp = periodic ? (uint32_t)periodic->cols.size() : 0u;
-    bool periods_ok = Kp <= AIR_MAX_PERIODIC && (!periodic || air_periodic_fits(*periodic, n_));
-    for (uint32_t k = 0; k < Kp && periods_ok; ++k) periods_ok = sp_log2_exact(periodic->cols[k].size()) >= 0;
-    if (!periods_ok) { sp_set_error("commit_aux_program: more than 64 periodic columns, or a period that is no power of two or exceeds the trace length"); return SP_E_INVALID_ARG; }
-    SP_TRY(validate_aux_program(aux, Cm_, (uint32_t)rap.size(), Kp));
     SP_HIP_CHECK(hipSetDevice(c_->device));
     const uint32_t chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(K, AUXP_CHUNK_ELEMS / n_));
     const uint64_t nb = air_aux_scan_blocks(n_);

@@ -17,9 +17,10 @@
 
 namespace sp {
 
-// Checks an auxiliary program against its AIR (operands refer to earlier ops, LOADs to main columns at shifts 0 .. 7, CONSTs to
-// the constants or the n_rap challenges, every column's ops exist).  SP_E_INVALID_ARG with sp_last_error() set otherwise.
-int validate_aux_program(const AirAuxHost& aux, uint32_t main_cols, uint32_t n_rap, uint32_t n_periodic = 0);   // n_periodic: the periodic columns op 6 may name (0: none, the old entry points)
+// the bounds a statement is decoded under (air_desc.h) are the kernels'
+static_assert(AIR_LIMIT_COLS == AIR_MAX_COLS && AIR_LIMIT_BOUNDARY == AIR_MAX_BOUNDARY && AIR_LIMIT_CONSTS == AIR_MAX_CONSTS && AIR_LIMIT_OPS == AIR_MAX_OPS &&
+              AIR_LIMIT_AUX_SHIFT == AIR_AUX_MAX_SHIFT && AIR_MAX_STRIDE_CLASSES == AIR_MAX_STRIDE_CLASSES_DEV && AIR_MAX_STRIDE_EXEMPT_KINDS == AIR_MAX_STRIDE_KINDS_DEV,
+              "air_desc.h and the kernel headers disagree about a bound");
 // Value slots of a straight-line program (ops 0 - 4 produce a value, op 5 OUT consumes op b): values that no OUT reads, directly
 // or through other values, are dropped; every other value gets one of AIR_MAX_LIVE slots, released after its last use.  The ops
 // must already be validated.  SP_E_UNSUPPORTED with `live_error` as sp_last_error() when more than AIR_MAX_LIVE are alive at once.
@@ -98,10 +99,11 @@ class StarkProver : public sp_deletable {
                      int col_enc = -1, uint64_t col_stride = 0);
     // round 1, Cairo auxiliary segment built on the device from the resident main trace (reference cairo/air.rs:660-729)
     int commit_aux_cairo(const PublicInputs& pub, const fe rap[3], uint8_t root_out[32]);
-    // round 1, auxiliary segment of a program AIR built on the device from an auxiliary program (validate_aux_program first) and
-    // the RAP challenges: per-row N and D, one batch inversion, an exclusive product / sum scan per column, commit_segment_resident
-    // periodic (nullable): the columns the program may read with op 6 (a = row shift, b = column: values[(i + a) mod period]).
-    int commit_aux_program(const AirAuxHost& aux, const std::vector<fe>& rap, uint8_t root_out[32], const AirPeriodicHost* periodic = nullptr);
+    // round 1, auxiliary segment of a program AIR built on the device from the statement's auxiliary program (st.aux, present and
+    // validated: air_statement_from_c) and the RAP challenges: per-row N and D, one batch inversion, an exclusive product / sum scan
+    // per column, commit_segment_resident.  The columns the program may read with op 6 (a = row shift, b = column:
+    // values[(i + a) mod period]) are st.aux_periodic().
+    int commit_aux_program(const AirStatement& st, const std::vector<fe>& rap, uint8_t root_out[32]);
     // round 2: constraint composition, H1/H2 split, LDE and commitment
     int composition(const fe rap[3], const std::vector<BoundaryConstraint>& bcs, const std::vector<fe>& b_alpha,
                     const std::vector<fe>& b_beta, const std::vector<fe>& t_alpha, const std::vector<fe>& t_beta,
@@ -112,13 +114,14 @@ class StarkProver : public sp_deletable {
     int composition_precheck(const fe rap[3], const std::vector<BoundaryConstraint>& bcs, uint32_t n_transitions);
     // round 2 for an AIR given as a constraint program (reference traits.rs:15-119 + evaluator.rs:38-260); rap = its RAP
     // challenges (appended to the program's constants); also sets the frame offsets used by rounds 3 and 4.
-    // periodic (nullable): the periodic columns the program reads with op 6; their tables are built here (od_.periodic)
-    int composition_air(const AirDescHost& air, const std::vector<fe>& rap, const std::vector<fe>& b_alpha, const std::vector<fe>& b_beta,
-                        const std::vector<fe>& t_alpha, const std::vector<fe>& t_beta, uint8_t root_out[32], const AirPeriodicHost* periodic = nullptr);
+    // air: st.air as everything behind round 1 sees it (its boundary values resolved); the tables of st.periodic, the columns the
+    // program reads with op 6, are built here (od_.periodic)
+    int composition_air(const AirStatement& st, const AirDescHost& air, const std::vector<fe>& rap, const std::vector<fe>& b_alpha, const std::vector<fe>& b_beta,
+                        const std::vector<fe>& t_alpha, const std::vector<fe>& t_beta, uint8_t root_out[32]);
     // Instead of round 2, for an AIR given as a constraint program: which constraints the trace held since round 1 (d_trace_,
     // main || aux) breaks, and where - the transition constraints by index, then the boundary constraints by index (sp_air_check_trace).
     // Leaves the stage where it was: composition_air may follow.
-    int check_trace_air(const AirDescHost& air, const std::vector<fe>& rap, const AirPeriodicHost* periodic, std::vector<AirViolationHost>& out);
+    int check_trace_air(const AirStatement& st, const AirDescHost& air, const std::vector<fe>& rap, std::vector<AirViolationHost>& out);
     // round 3: H1(z^2), H2(z^2), t_j(z g^ofs_k) for every frame row k (row-major [k][j])
     int ood(const fe& z, fe* h1_z2, fe* h2_z2, std::vector<fe>& trace_ood);
     // round 4
@@ -255,8 +258,8 @@ class StarkProver : public sp_deletable {
         AirStridePlan plan; AirStrideDev sdev; std::vector<fe> sroots; uint64_t stab = 0; size_t o_sdev = 0; std::vector<uint32_t> ex_eff;
         bool strided() const { return !plan.classes.empty(); }
     };
-    int build_air_program(const AirDescHost& air, size_t n_rap, const AirPeriodicHost* periodic, AirProgramHost& out);
-    int build_air_block(const AirDescHost& air, const std::vector<fe>& rap, const AirPeriodicHost* periodic, AirProgramHost& ph,
+    int build_air_program(const AirStatement& st, const AirDescHost& air, size_t n_rap, AirProgramHost& out);
+    int build_air_block(const AirStatement& st, const AirDescHost& air, const std::vector<fe>& rap, AirProgramHost& ph,
                         const std::vector<uint32_t>& order, std::initializer_list<std::pair<size_t, size_t*>> extra, AirCompTables& tabs,
                         const AirProgram*& prog_dev);
     struct Round2Air;   // what composition_core is given; the two members below it are where Cairo and a program AIR differ
@@ -435,21 +438,14 @@ int cairo_prove(sp_ctx* ctx, const uint8_t* main_trace, uint64_t n, uint32_t col
                 const ProofOptionsHost& opt, std::vector<uint8_t>& proof_out, float round_ms[5],
                 StarkProver::TraceSource src = StarkProver::TRACE_HOST_ROWS, int col_enc = -1, uint64_t col_stride = 0);
 // Whole proof for an AIR given as a constraint program: `prove::<F, A>` (reference src/starks/prover.rs:532-766) + serialize.
-// main_trace: row-major n x air.main_cols in the context encoding (host memory).
-// round_ms: device time of rounds 1 - 4 in [1..4], as cairo_prove.
-// aux (nullable): the auxiliary program of an AIR with aux_kind SP_AIR_AUX_PROGRAM (sp_air_prove_aux).
-// periodic (nullable): the periodic columns its constraint program reads (sp_air_prove_periodic); without them op 6 is malformed.
-// pub: public data inside the RAP argument (sp_air_prove_pub) - boundary values resolved from the challenges after round 1, and whether the
-// auxiliary program may read the periodic columns.
-struct AirPublicHost { const AirBoundaryHost* bvals = nullptr; bool aux_reads_periodic = false; };
-int air_prove(sp_ctx* ctx, const AirDescHost& air, const uint8_t* main_trace, uint64_t n, const ProofOptionsHost& opt,
-              std::vector<uint8_t>& proof_out, float round_ms[5], const AirAuxHost* aux = nullptr, const AirPeriodicHost* periodic = nullptr,
-              const AirPublicHost& pub = AirPublicHost());
+// st: the statement as air_statement_from_c accepted it for n rows.  main_trace: row-major n x st.air.main_cols in the context
+// encoding (host memory).  round_ms: device time of rounds 1 - 4 in [1..4], as cairo_prove.
+int air_prove(sp_ctx* ctx, const AirStatement& st, const uint8_t* main_trace, uint64_t n, const ProofOptionsHost& opt, std::vector<uint8_t>& proof_out,
+              float round_ms[5]);
 // Which constraints of a program AIR a trace breaks, and where (sp_air_check_trace): round 1 as air_prove runs it - the same ingest and
 // auxiliary builders -, then StarkProver::check_trace_air; no proof.  rap_given (nullable): the RAP challenges, instead of the ones a
 // proof under *opt would sample; opt may be null only with them.  One GPU (SP_E_UNSUPPORTED on a context with world > 1).
-int air_check_trace(sp_ctx* ctx, const AirDescHost& air, const uint8_t* main_trace, uint64_t n, const ProofOptionsHost* opt,
-                    const std::vector<fe>* rap_given, std::vector<AirViolationHost>& out, const AirAuxHost* aux = nullptr,
-                    const AirPeriodicHost* periodic = nullptr, const AirPublicHost& pub = AirPublicHost());
+int air_check_trace(sp_ctx* ctx, const AirStatement& st, const uint8_t* main_trace, uint64_t n, const ProofOptionsHost* opt,
+                    const std::vector<fe>* rap_given, std::vector<AirViolationHost>& out);
 
 }  // namespace sp

@@ -253,42 +253,12 @@ int cairo_prove(sp_ctx* ctx, const uint8_t* main_trace, uint64_t n, uint32_t col
     }
 }
 
-// The argument checks of air_prove and air_check_trace.
-static int air_check_args(const AirDescHost& air, uint64_t n, const AirAuxHost* aux, const AirPeriodicHost* periodic, const AirPublicHost& pub) {
-    if (air.main_cols == 0 || (uint64_t)air.main_cols + air.aux_cols > (uint64_t)AIR_MAX_COLS) {
-        sp_set_error("air_prove: column count out of range (1 .. 1024 columns, main + aux)");
-        return SP_E_INVALID_ARG;
-    }
-    if (air.boundary.size() > (size_t)AIR_MAX_BOUNDARY) { sp_set_error("air_prove: more than 4096 boundary constraints"); return SP_E_INVALID_ARG; }
-    if (air.consts.size() > (size_t)AIR_MAX_CONSTS) { sp_set_error("air_prove: more than 4096 constants"); return SP_E_INVALID_ARG; }
-    if (air.consts.size() + air.n_rap > 65535) { sp_set_error("air_prove: constants and RAP challenges exceed the 16-bit operand range"); return SP_E_INVALID_ARG; }
-    if (air.ops.size() > (size_t)AIR_MAX_OPS) { sp_set_error("air_prove: more than 65535 ops"); return SP_E_INVALID_ARG; }
-    if (periodic) {
-        if (periodic->cols.size() > (size_t)AIR_MAX_PERIODIC) { sp_set_error("air_prove: more than 64 periodic columns"); return SP_E_INVALID_ARG; }
-        if (!air_periodic_fits(*periodic, n)) { sp_set_error("air_prove: a periodic column's period exceeds the trace length"); return SP_E_INVALID_ARG; }
-    }
-    if (aux) {
-        if (air.aux_kind != SP_AIR_AUX_PROGRAM || air.aux_cols == 0 || aux->cols.size() != air.aux_cols) {
-            sp_set_error("air_prove: an auxiliary program needs aux_kind SP_AIR_AUX_PROGRAM and one column per auxiliary column");
-            return SP_E_INVALID_ARG;
-        }
-        // (only the _pub entry points let an auxiliary program read the periodic columns: 0 of them from everywhere else)
-        SP_TRY(validate_aux_program(*aux, air.main_cols, air.n_rap, pub.aux_reads_periodic && periodic ? (uint32_t)periodic->cols.size() : 0u));
-    }
-    if (pub.bvals) {   // (checked where the descriptor was read, air_boundary_from_c; held against this AIR once more)
-        for (const AirBoundaryValueHost& e : pub.bvals->values)
-            if (e.boundary >= air.boundary.size()) { sp_set_error("air_prove: a boundary value names a boundary constraint the AIR does not have"); return SP_E_INVALID_ARG; }
-        if (pub.bvals->consts.size() + air.n_rap > 65535) { sp_set_error("air_prove: boundary values: constants and RAP challenges exceed the 16-bit operand range"); return SP_E_INVALID_ARG; }
-    }
-    return SP_OK;
-}
-
 // Round 1 of a program AIR (reference prover.rs:187-224) on a prover that begin_proof has set up: the main segment, the RAP
 // challenges - sampled from the transcript, or rap_given (air_check_trace with the caller's challenges) -, the auxiliary segment by
 // its kind.  Leaves main || aux on the device as round 2 reads it.
-// aux_periodic (nullable): the periodic columns the auxiliary program may read (sp_air_prove_pub).
-static int air_round1(sp_ctx* ctx, ProofRun& run, const AirDescHost& air, const uint8_t* main_trace, uint64_t n, const AirAuxHost* aux,
-                      std::vector<fe>& rap, const std::vector<fe>* rap_given = nullptr, const AirPeriodicHost* aux_periodic = nullptr) {
+static int air_round1(sp_ctx* ctx, ProofRun& run, const AirStatement& st, const uint8_t* main_trace, uint64_t n, std::vector<fe>& rap,
+                      const std::vector<fe>* rap_given = nullptr) {
+    const AirDescHost& air = st.air;
     StarkProver* P = &run.H->prover;
     Transcript& tr = run.tr;
     uint8_t root[32];
@@ -305,9 +275,9 @@ static int air_round1(sp_ctx* ctx, ProofRun& run, const AirDescHost& air, const 
         if (air.aux_fn(air.aux_user, rap_bytes.data(), (uint32_t)rap.size(), aux_rows.data()) != 0) { sp_set_error("air_prove: the auxiliary-trace callback failed"); return SP_E_INVALID_ARG; }
         SP_TRY(P->commit_trace(1, aux_rows.data(), air.aux_cols, root));
         run.trace_committed(root);
-    } else if (air.aux_cols && air.aux_kind == SP_AIR_AUX_PROGRAM && aux) {
+    } else if (air.aux_cols && air.aux_kind == SP_AIR_AUX_PROGRAM && st.aux) {
         // the auxiliary program on the device, from the resident main trace (every rank holds all of it: no exchange)
-        SP_TRY(P->commit_aux_program(*aux, rap, root, aux_periodic));
+        SP_TRY(P->commit_aux_program(st, rap, root));
         run.trace_committed(root);
     } else if (air.aux_cols) {
         if (air.aux_kind != 1 || air.aux_cols != 1 || air.main_cols < 2 || air.n_rap < 1) {
@@ -340,11 +310,11 @@ static int air_round1(sp_ctx* ctx, ProofRun& run, const AirDescHost& air, const 
 
 // boundary_constraints(rap_challenges) (traits.rs:44-47): the AIR as everything behind round 1 sees it - the descriptor itself, or, with
 // boundary values computed from the challenges, a copy (`resolved`) whose boundary constraints carry them as constants.
-static int air_with_boundary(const AirDescHost& air, const AirPublicHost& pub, const std::vector<fe>& rap, AirDescHost& resolved, const AirDescHost*& use) {
-    use = &air;
-    if (!pub.bvals) return SP_OK;
-    resolved = air;
-    if (!air_resolve_boundary_into(*pub.bvals, rap, resolved.boundary)) { sp_set_error("air_prove: a boundary value's denominator is zero under these challenges"); return SP_E_ZERO_INVERSE; }
+static int air_with_boundary(const AirStatement& st, const std::vector<fe>& rap, AirDescHost& resolved, const AirDescHost*& use) {
+    use = &st.air;
+    if (!st.bvals) return SP_OK;
+    resolved = st.air;
+    if (!air_resolve_boundary_into(*st.bvals, rap, resolved.boundary)) { sp_set_error("air_prove: a boundary value's denominator is zero under these challenges"); return SP_E_ZERO_INVERSE; }
     use = &resolved;
     return SP_OK;
 }
@@ -353,23 +323,22 @@ static int air_with_boundary(const AirDescHost& air, const AirPublicHost& pub, c
 // air_prove runs it, then the report instead of rounds 2 - 4.  opt (nullable when rap is given): the options of the proof whose
 // challenges are wanted; with the caller's challenges the commitments still run (under the smallest options when none are given),
 // since they are how the prover takes a trace in.
-int air_check_trace(sp_ctx* ctx, const AirDescHost& air, const uint8_t* main_trace, uint64_t n, const ProofOptionsHost* opt,
-                    const std::vector<fe>* rap_given, std::vector<AirViolationHost>& out, const AirAuxHost* aux, const AirPeriodicHost* periodic,
-                    const AirPublicHost& pub) {
+int air_check_trace(sp_ctx* ctx, const AirStatement& st, const uint8_t* main_trace, uint64_t n, const ProofOptionsHost* opt,
+                    const std::vector<fe>* rap_given, std::vector<AirViolationHost>& out) {
+    const AirDescHost& air = st.air;
     try {
         if (!opt && !rap_given) { sp_set_error("air_check_trace: proof options are needed to sample the RAP challenges"); return SP_E_INVALID_ARG; }
         if (rap_given && rap_given->size() != air.n_rap) { sp_set_error("air_check_trace: one RAP challenge per n_rap"); return SP_E_INVALID_ARG; }
-        SP_TRY(air_check_args(air, n, aux, periodic, pub));
         if (ctx->world > 1) { sp_set_error("air_check_trace: a report from a sharded context (world > 1) is not supported"); return SP_E_UNSUPPORTED; }
         const ProofOptionsHost smallest{2, 1, 3, 0};
         ProofRun run;
         SP_TRY(begin_proof(ctx, n, air.main_cols, air.aux_cols, false, opt ? *opt : smallest, run));
         std::vector<fe> rap;
-        SP_TRY(air_round1(ctx, run, air, main_trace, n, aux, rap, rap_given, pub.aux_reads_periodic ? periodic : nullptr));
+        SP_TRY(air_round1(ctx, run, st, main_trace, n, rap, rap_given));
         AirDescHost resolved;
         const AirDescHost* use = nullptr;
-        SP_TRY(air_with_boundary(air, pub, rap, resolved, use));
-        return run.H->prover.check_trace_air(*use, rap, periodic, out);
+        SP_TRY(air_with_boundary(st, rap, resolved, use));
+        return run.H->prover.check_trace_air(st, *use, rap, out);
     } catch (const std::exception& e) {
         sp_set_error(std::string("air_check_trace: ") + e.what());
         return SP_E_INVALID_ARG;
@@ -379,22 +348,22 @@ int air_check_trace(sp_ctx* ctx, const AirDescHost& air, const uint8_t* main_tra
 // prove::<F, A> for a program AIR (reference src/starks/prover.rs:532-766): same rounds, the AIR-specific parts come from
 // the descriptor - RAP challenges (n_rap field samples), auxiliary trace (by kind: the fibonacci_rap column and the caller's
 // callback on the host - the example AIRs are tiny -, an auxiliary program on the device), boundary constraints, transition program.
-int air_prove(sp_ctx* ctx, const AirDescHost& air, const uint8_t* main_trace, uint64_t n, const ProofOptionsHost& opt,
-              std::vector<uint8_t>& proof_out, float round_ms[5], const AirAuxHost* aux, const AirPeriodicHost* periodic, const AirPublicHost& pub) {
+int air_prove(sp_ctx* ctx, const AirStatement& st, const uint8_t* main_trace, uint64_t n, const ProofOptionsHost& opt, std::vector<uint8_t>& proof_out,
+              float round_ms[5]) {
+    const AirDescHost& air = st.air;
     try {
-        SP_TRY(air_check_args(air, n, aux, periodic, pub));
         ProofRun run;
         SP_TRY(begin_proof(ctx, n, air.main_cols, air.aux_cols, false, opt, run));
         StarkProver* P = &run.H->prover;
         std::vector<fe> rap;
         // ---- round 1 (reference prover.rs:187-224)
-        SP_TRY(air_round1(ctx, run, air, main_trace, n, aux, rap, nullptr, pub.aux_reads_periodic ? periodic : nullptr));
+        SP_TRY(air_round1(ctx, run, st, main_trace, n, rap));
         SP_HIP_CHECK(hipEventRecord(run.H->round_ev[1], ctx->stream));
         AirDescHost resolved;
         const AirDescHost* use = nullptr;
-        SP_TRY(air_with_boundary(air, pub, rap, resolved, use));
+        SP_TRY(air_with_boundary(st, rap, resolved, use));
         auto composition = [&](const std::vector<fe>& b_alpha, const std::vector<fe>& b_beta, const std::vector<fe>& t_alpha, const std::vector<fe>& t_beta, uint8_t* root_out) {
-            return P->composition_air(*use, rap, b_alpha, b_beta, t_alpha, t_beta, root_out, periodic);
+            return P->composition_air(st, *use, rap, b_alpha, b_beta, t_alpha, t_beta, root_out);
         };
         return finish_proof(ctx, run, air.boundary.size(), air.degrees.size(), opt, composition, proof_out, round_ms);
     } catch (const std::exception& e) {

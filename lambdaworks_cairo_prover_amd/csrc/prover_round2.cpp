@@ -189,7 +189,7 @@ int air_stride_class_tables(hipStream_t st, NttEngine& ntt, fe* u, fe* z, uint32
 
 // The device form of an AIR's constraint program, and what of the descriptor goes with it: checked against the committed trace, values
 // in slots, the periodic columns' places, the exemptions as both the composition and the trace check use them.
-int StarkProver::build_air_program(const AirDescHost& air, size_t n_rap, const AirPeriodicHost* periodic, AirProgramHost& out) {
+int StarkProver::build_air_program(const AirStatement& st, const AirDescHost& air, size_t n_rap, AirProgramHost& out) {
     const uint32_t T = (uint32_t)air.degrees.size(), B = (uint32_t)air.boundary.size(), R = (uint32_t)air.offsets.size();
     if (T == 0 || T > AIR_MAX_TRANSITIONS || B > AIR_MAX_BOUNDARY || R == 0 || R > AIR_MAX_OFFSETS || air.exemptions.size() != T ||
         air.ops.size() > AIR_MAX_OPS || air.consts.size() > AIR_MAX_CONSTS || air.consts.size() + n_rap > 65535 || n_rap != air.n_rap ||
@@ -207,16 +207,14 @@ int StarkProver::build_air_program(const AirDescHost& air, size_t n_rap, const A
     prog.n_offsets = R;
     for (uint32_t k = 0; k < R; ++k) prog.offsets[k] = air.offsets[k];
     // --- periodic columns: column k's values at pvals + off_k (off_k = the periods before it, summed), its table at ptab + off_k b
-    const uint32_t Kp = periodic ? (uint32_t)periodic->cols.size() : 0u;
-    if (Kp > AIR_MAX_PERIODIC) { sp_set_error("composition_air: more than 64 periodic columns"); return SP_E_INVALID_ARG; }
+    //     (at most 64 of them, each a power of two <= n: the statement's decoder has seen to that)
+    const uint32_t Kp = st.n_periodic();
     std::vector<AirPeriodicCol>& pcols = out.pcols;
     pcols.assign(Kp, AirPeriodicCol{});
     uint64_t S = 0;
     for (uint32_t k = 0; k < Kp; ++k) {
-        const uint64_t p = periodic->cols[k].size();
-        const int lp = sp_log2_exact(p);
-        if (lp < 0 || p > n_) { sp_set_error("composition_air: a period must be a power of two, 1 <= period <= n"); return SP_E_INVALID_ARG; }
-        pcols[k] = AirPeriodicCol{(uint32_t)lp, 0u, S};
+        const uint64_t p = st.periodic->cols[k].size();
+        pcols[k] = AirPeriodicCol{(uint32_t)sp_log2_exact(p), 0u, S};
         S += p;
     }
     out.S = S;
@@ -283,7 +281,7 @@ int StarkProver::build_air_program(const AirDescHost& air, size_t n_rap, const A
 // (AirStrideDev) and exemption roots; behind them one region per entry
 // of `extra` (its bytes, and where its offset goes), which the caller fills.  od_.air_buf is grown to the whole block; the caller
 // uploads it in one copy.  tabs: T, B, bvalue, bstep, bcol, pcols, pvals, strides set, the rest zero.
-int StarkProver::build_air_block(const AirDescHost& air, const std::vector<fe>& rap, const AirPeriodicHost* periodic, AirProgramHost& ph,
+int StarkProver::build_air_block(const AirStatement& st, const AirDescHost& air, const std::vector<fe>& rap, AirProgramHost& ph,
                                  const std::vector<uint32_t>& order, std::initializer_list<std::pair<size_t, size_t*>> extra,
                                  AirCompTables& tabs, const AirProgram*& prog_dev) {
     const uint32_t B = (uint32_t)air.boundary.size(), Kp = (uint32_t)ph.pcols.size();
@@ -313,7 +311,7 @@ int StarkProver::build_air_block(const AirDescHost& air, const std::vector<fe>& 
         hbval[jp] = bc.value; hbstep[jp] = bc.step; hbcol[jp] = bc.col;
     }
     if (Kp) std::memcpy(up.data() + o_pcols, ph.pcols.data(), sizeof(AirPeriodicCol) * Kp);
-    for (uint32_t k = 0; k < Kp; ++k) std::memcpy(up.data() + o_pvals + sizeof(fe) * ph.pcols[k].off, periodic->cols[k].data(), sizeof(fe) * periodic->cols[k].size());
+    for (uint32_t k = 0; k < Kp; ++k) std::memcpy(up.data() + o_pvals + sizeof(fe) * ph.pcols[k].off, st.periodic->cols[k].data(), sizeof(fe) * st.periodic->cols[k].size());
     std::memset(&tabs, 0, sizeof(tabs));
     tabs.T = (uint32_t)air.degrees.size(); tabs.B = B;
     tabs.bvalue = reinterpret_cast<const fe*>(dev_at(o_bval));
@@ -334,8 +332,8 @@ int StarkProver::build_air_block(const AirDescHost& air, const std::vector<fe>& 
     return SP_OK;
 }
 
-int StarkProver::composition_air(const AirDescHost& air, const std::vector<fe>& rap, const std::vector<fe>& b_alpha, const std::vector<fe>& b_beta,
-                                 const std::vector<fe>& t_alpha, const std::vector<fe>& t_beta, uint8_t root_out[32], const AirPeriodicHost* periodic) {
+int StarkProver::composition_air(const AirStatement& st, const AirDescHost& air, const std::vector<fe>& rap, const std::vector<fe>& b_alpha,
+                                 const std::vector<fe>& b_beta, const std::vector<fe>& t_alpha, const std::vector<fe>& t_beta, uint8_t root_out[32]) {
     if (!segments_committed()) { sp_set_error("composition: trace segments not committed"); return SP_E_STATE; }
     const uint32_t T = (uint32_t)air.degrees.size(), B = (uint32_t)air.boundary.size();
     if (t_alpha.size() != T || t_beta.size() != T || b_alpha.size() != B || b_beta.size() != B) {
@@ -344,7 +342,7 @@ int StarkProver::composition_air(const AirDescHost& air, const std::vector<fe>& 
     }
     SP_HIP_CHECK(hipSetDevice(c_->device));
     AirProgramHost ph;
-    SP_TRY(build_air_program(air, rap.size(), periodic, ph));
+    SP_TRY(build_air_program(st, air, rap.size(), ph));
     const uint32_t b = 1u << logb_, f = air.degree_bound_factor;
     const std::vector<AirPeriodicCol>& pcols = ph.pcols;
     const uint32_t Kp = (uint32_t)pcols.size(), max_ex = ph.max_ex;
@@ -377,7 +375,7 @@ int StarkProver::composition_air(const AirDescHost& air, const std::vector<fe>& 
     size_t o_zf, o_coef, o_gpt, o_gend;
     AirCompTables tabs;
     const AirProgram* prog_dev = nullptr;
-    SP_TRY(build_air_block(air, rap, periodic, ph, order,
+    SP_TRY(build_air_block(st, air, rap, ph, order,
                            {{sizeof(fe) * b, &o_zf}, {sizeof(fe) * b * nterm, &o_coef}, {sizeof(fe) * nd, &o_gpt}, {sizeof(uint32_t) * nd, &o_gend}}, tabs, prog_dev));
     std::vector<uint8_t>& up = h_air_up_;
     auto dev_at = [&](size_t off) { return od_.air_buf.p + off; };
@@ -446,19 +444,19 @@ int StarkProver::composition_air(const AirDescHost& air, const std::vector<fe>& 
 
 // validate_trace (reference debug.rs:13-104) for a program AIR, on the device: the program and the descriptor's boundary constraints
 // (in the descriptor's order - the report names them by index) go up in one block, the report comes back in one.
-int StarkProver::check_trace_air(const AirDescHost& air, const std::vector<fe>& rap, const AirPeriodicHost* periodic, std::vector<AirViolationHost>& out) {
+int StarkProver::check_trace_air(const AirStatement& st, const AirDescHost& air, const std::vector<fe>& rap, std::vector<AirViolationHost>& out) {
     out.clear();
     if (!segments_committed()) { sp_set_error("check_trace_air: trace segments not committed"); return SP_E_STATE; }
     if (world_ > 1) { sp_set_error("check_trace_air: a report from a sharded context is not supported"); return SP_E_UNSUPPORTED; }
     SP_HIP_CHECK(hipSetDevice(c_->device));
     AirProgramHost ph;
-    SP_TRY(build_air_program(air, rap.size(), periodic, ph));
+    SP_TRY(build_air_program(st, air, rap.size(), ph));
     const uint32_t T = (uint32_t)air.degrees.size(), B = (uint32_t)air.boundary.size();
     std::vector<uint32_t> order(B);
     std::iota(order.begin(), order.end(), 0u);
     AirCompTables tabs;
     const AirProgram* prog_dev = nullptr;
-    SP_TRY(build_air_block(air, rap, periodic, ph, order, {}, tabs, prog_dev));
+    SP_TRY(build_air_block(st, air, rap, ph, order, {}, tabs, prog_dev));
     SP_HIP_CHECK(hipMemcpyAsync(od_.air_buf.p, h_air_up_.data(), h_air_up_.size(), hipMemcpyHostToDevice, c_->stream));
     // the report block, in 8-byte words: value [4 T] | bcell [4 B] | count [T] | first [T] | last [T] | bbad [B / 2]
     const uint64_t w_value = 0, w_bcell = w_value + 4ull * T, w_count = w_bcell + 4ull * B, w_first = w_count + T, w_last = w_first + T,

@@ -219,13 +219,6 @@ struct VerifySpec {
     std::vector<AirStrideHost> strides;             // per transition constraint; empty: every constraint on every row
 };
 
-// the primitive root of unity of order 2^order (lambdaworks get_primitive_root_of_unity): the field's 2^192-th root, squared down
-static fe root_of(int order) {
-    fe w = fe_from_bytes_be((const uint8_t*)"\x00\x52\x82\xdb\x87\x52\x9c\xfa\x3f\x04\x64\x51\x9c\x8b\x0f\xa5\xad\x18\x71\x48\xe1\x1a\x61\x61\x60\x70\x02\x4f\x42\xf8\xef\x94");
-    for (int i = order; i < 192; ++i) w = fe_sqr(w);
-    return w;
-}
-
 // returns 1 accept, 0 reject; throws on malformed input
 static int verify_host(const uint8_t* proof_bytes, size_t len, const VerifySpec& air, uint8_t blowup, uint64_t queries, uint64_t coset_offset, uint8_t grinding) {
     Proof pr = parse(proof_bytes, len);
@@ -242,7 +235,7 @@ static int verify_host(const uint8_t* proof_bytes, size_t len, const VerifySpec&
     if (pr.ood.size() != (size_t)R * C || pr.row_width != C || pr.trace_roots.size() != n_roots || pr.fri_roots.size() != (size_t)k) return 0;
     for (uint32_t c = 0; c < T; ++c) if (air.degrees[c] < 1 || air.degrees[c] > f + 1 || air.exemptions[c] >= n) return 0;
     const fe h = fe_from_u64(coset_offset), hinv = fe_inv(h);
-    const fe g = root_of(k), w = root_of(k + lb);
+    const fe g = air_root_of_unity(k), w = air_root_of_unity(k + lb);
     // ---- step 1: replay the transcript (verifier.rs:59-206)
     Transcript t;
     t.append(pr.trace_roots[0].data(), 32);
@@ -399,6 +392,8 @@ static int verify_host(const uint8_t* proof_bytes, size_t len, const VerifySpec&
     return 1;
 }
 
+uint64_t proof_trace_length(const uint8_t* proof_bytes, size_t len) { return Reader(proof_bytes, len).u64(); }
+
 int cairo_verify_host(const uint8_t* proof_bytes, size_t len, const PublicInputs& pub, uint8_t blowup, uint64_t queries, uint64_t coset_offset, uint8_t grinding) {
     CairoAirInfo info = cairo_air_info(pub);
     VerifySpec spec;
@@ -406,10 +401,7 @@ int cairo_verify_host(const uint8_t* proof_bytes, size_t len, const PublicInputs
     spec.offsets = {0, 1};
     spec.degrees = info.transition_degrees; spec.exemptions = info.transition_exemptions;
     spec.bound_factor = 2; spec.n_rap = 3;
-    // the trace length is only known from the proof: read it first (boundary steps depend on it)
-    if (len < 8) throw std::runtime_error("malformed: InvalidAmountOfBytes");
-    uint64_t n = 0;
-    for (int i = 0; i < 8; ++i) n = (n << 8) | proof_bytes[i];
+    const uint64_t n = proof_trace_length(proof_bytes, len);   // (boundary steps depend on it)
     const bool has_rc = info.has_rc_builtin;
     const uint32_t C = info.trace_columns;
     spec.boundary = [&pub, n, has_rc](const std::vector<fe>& rap) { fe r[3] = {rap[0], rap[1], rap[2]}; return boundary_constraints(pub, r, n, has_rc); };
@@ -418,23 +410,23 @@ int cairo_verify_host(const uint8_t* proof_bytes, size_t len, const PublicInputs
 }
 
 // `verify::<F, A>` for a program AIR (include/stark252_hip.h sp_air_desc); ops as in AirOpDev of stark_kernels.h.
-int air_verify_host(const uint8_t* proof_bytes, size_t len, const AirDescHost& air, const ProofOptionsHost& opt, const AirPeriodicHost* periodic,
-                    const AirBoundaryHost* bvals) {
+int air_verify_host(const uint8_t* proof_bytes, size_t len, const AirStatement& st, const ProofOptionsHost& opt) {
+    const AirDescHost& air = st.air;
     const uint32_t C = air.main_cols + air.aux_cols, T = (uint32_t)air.degrees.size(), R = (uint32_t)air.offsets.size();
     if (T == 0 || R == 0 || air.exemptions.size() != T || air.degree_bound_factor < 1 || C < air.main_cols) return 0;   // (C < main_cols: the sum wrapped)
     const std::vector<AirOpHost>& ops = air.ops;
     const std::vector<fe>& consts = air.consts;
-    const uint32_t Kp = periodic ? (uint32_t)periodic->cols.size() : 0u;
+    const uint32_t Kp = st.n_periodic();
     if (air_program_first_bad_op(ops, R, C, consts.size() + air.n_rap, T, Kp) < ops.size()) throw std::runtime_error("malformed: constraint program");
     VerifySpec spec;
-    for (uint32_t k = 0; k < Kp; ++k) spec.periodic_coeffs.push_back(air_periodic_interpolate(periodic->cols[k]));
+    for (uint32_t k = 0; k < Kp; ++k) spec.periodic_coeffs.push_back(air_periodic_interpolate(st.periodic->cols[k]));
     spec.main_cols = air.main_cols; spec.aux_cols = air.aux_cols; spec.offsets = air.offsets; spec.degrees = air.degrees; spec.exemptions = air.exemptions;
     spec.bound_factor = air.degree_bound_factor; spec.n_rap = air.n_rap;
-    spec.strides = air.strides;   // checked against the proof's trace length where they were read (air_strides_from_c)
+    spec.strides = air.strides;   // checked against the proof's trace length where they were read (air_statement_from_c)
     // boundary_constraints(rap_challenges) (traits.rs:44-47): the descriptor's constants, those of bvals computed from the challenges
-    spec.boundary = [&air, bvals](const std::vector<fe>& rap) {
-        std::vector<BoundaryConstraint> bcs = air.boundary;
-        if (bvals && !air_resolve_boundary_into(*bvals, rap, bcs)) throw std::runtime_error("rejected: a boundary value's denominator is zero under the proof's challenges");
+    spec.boundary = [&st](const std::vector<fe>& rap) {
+        std::vector<BoundaryConstraint> bcs = st.air.boundary;
+        if (st.bvals && !air_resolve_boundary_into(*st.bvals, rap, bcs)) throw std::runtime_error("rejected: a boundary value's denominator is zero under the proof's challenges");
         return bcs;
     };
     spec.transition = [&ops, &consts, C, T, Kp](const fe* frame, const fe* per, const std::vector<fe>& rap, fe* out) {
@@ -454,140 +446,6 @@ int air_verify_host(const uint8_t* proof_bytes, size_t len, const AirDescHost& a
         }
     };
     return verify_host(proof_bytes, len, spec, opt.blowup_factor, opt.fri_number_of_queries, opt.coset_offset, opt.grinding_factor);
-}
-
-bool air_resolve_boundary(const AirBoundaryHost& bvals, const std::vector<fe>& rap, std::vector<fe>& values) {
-    const size_t nc = bvals.consts.size();
-    std::vector<fe> v(bvals.ops.size());
-    for (size_t t = 0; t < bvals.ops.size(); ++t) {
-        const AirOpHost& o = bvals.ops[t];
-        switch (o.op) {
-            case 1: v[t] = o.a < nc ? bvals.consts[o.a] : rap[o.a - nc]; break;
-            case 2: v[t] = fe_add(v[o.a], v[o.b]); break;
-            case 3: v[t] = fe_sub(v[o.a], v[o.b]); break;
-            default: v[t] = fe_mul(v[o.a], v[o.b]); break;
-        }
-    }
-    std::vector<fe> dens;
-    for (const AirBoundaryValueHost& e : bvals.values)
-        if (e.den_op != SP_AIR_AUX_NO_DEN) {
-            if (fe_is_zero(v[e.den_op])) return false;
-            dens.push_back(v[e.den_op]);
-        }
-    if (!dens.empty()) host_batch_inverse(dens);
-    values.clear();
-    size_t d = 0;
-    for (const AirBoundaryValueHost& e : bvals.values)
-        values.push_back(e.den_op != SP_AIR_AUX_NO_DEN ? fe_mul(v[e.num_op], dens[d++]) : v[e.num_op]);
-    return true;
-}
-
-bool air_resolve_boundary_into(const AirBoundaryHost& bvals, const std::vector<fe>& rap, std::vector<BoundaryConstraint>& boundary) {
-    std::vector<fe> values;
-    if (!air_resolve_boundary(bvals, rap, values)) return false;
-    for (size_t j = 0; j < values.size(); ++j) boundary[bvals.values[j].boundary].value = values[j];
-    return true;
-}
-
-// q from its values on <w_p>: an in-place radix-2 inverse transform (bit-reversal, then butterflies with w_p^-1), times 1/p
-std::vector<fe> air_periodic_interpolate(const std::vector<fe>& values) {
-    const size_t p = values.size();
-    const int lp = sp_log2_exact(p);
-    if (lp < 0) throw std::runtime_error("malformed: periodic column period");
-    std::vector<fe> a(p);
-    for (size_t i = 0; i < p; ++i) {
-        size_t r = 0;
-        for (int bit = 0; bit < lp; ++bit) r |= ((i >> bit) & 1) << (lp - 1 - bit);
-        a[r] = values[i];
-    }
-    const fe winv = lp ? fe_inv(root_of(lp)) : fe_one();
-    for (int s = 1; s <= lp; ++s) {
-        const size_t m = size_t(1) << s, half = m >> 1;
-        const fe wm = fe_pow_u64(winv, p / m);
-        std::vector<fe> tw(half);
-        tw[0] = fe_one();
-        for (size_t j = 1; j < half; ++j) tw[j] = fe_mul(tw[j - 1], wm);
-        for (size_t k = 0; k < p; k += m)
-            for (size_t j = 0; j < half; ++j) {
-                const fe t = fe_mul(tw[j], a[k + j + half]), u = a[k + j];
-                a[k + j] = fe_add(u, t);
-                a[k + j + half] = fe_sub(u, t);
-            }
-    }
-    const fe pinv = fe_inv(fe_from_u64(p));
-    for (auto& x : a) x = fe_mul(x, pinv);
-    return a;
-}
-
-fe air_periodic_eval(const std::vector<fe>& coeffs, uint64_t n, const fe& point) {
-    const fe y = fe_pow_u64(point, n / coeffs.size());
-    fe acc = fe_zero();
-    for (size_t m = coeffs.size(); m-- > 0;) acc = fe_add(fe_mul(acc, y), coeffs[m]);
-    return acc;
-}
-
-bool air_stride_plan(const AirDescHost& air, uint64_t n, AirStridePlan& out) {
-    const size_t T = air.exemptions.size();
-    out = AirStridePlan{};
-    out.cls.assign(T, -1); out.kind.assign(T, -1);
-    if (air.strides.empty()) return true;
-    if (air.strides.size() != T) return false;
-    for (size_t k = 0; k < T; ++k) {
-        const uint32_t s = air.strides[k].period, o = air.strides[k].offset, e = air.exemptions[k];
-        if (s == 0 || (s & (s - 1)) || s > n || o >= s) return false;
-        if (s == 1) continue;
-        // C_k / Z_k has degree d n - n/s: the adjustment x^(n (f - d) + n/s) exists for d <= f only (a (1, 0) constraint may have d = f + 1)
-        if (e >= n / s || k >= air.degrees.size() || air.degrees[k] > air.degree_bound_factor) return false;
-        size_t q = 0;
-        while (q < out.classes.size() && (out.classes[q].period != s || out.classes[q].offset != o)) ++q;
-        if (q == out.classes.size()) {
-            if (q == AIR_MAX_STRIDE_CLASSES) return false;
-            out.classes.push_back(air.strides[k]);
-        }
-        out.cls[k] = (int)q;
-        if (!e) continue;
-        const std::pair<uint32_t, uint32_t> want((uint32_t)q, e);
-        size_t j = 0;
-        while (j < out.kinds.size() && out.kinds[j] != want) ++j;
-        if (j == out.kinds.size()) {
-            if (j == AIR_MAX_STRIDE_EXEMPT_KINDS) return false;
-            out.kinds.push_back(want);
-        }
-        out.kind[k] = (int)j;
-    }
-    return true;
-}
-
-void air_stride_eval(uint32_t s, uint32_t o, uint32_t e, uint64_t n, const fe& x, fe& Z, fe& E) {
-    const uint64_t m = n / s;                       // rows of the progression
-    const fe g = root_of(sp_log2_exact(n));
-    Z = fe_sub(fe_pow_u64(x, m), fe_pow_u64(g, (uint64_t)o * m));
-    E = fe_one();
-    const fe gs_inv = fe_inv(fe_pow_u64(g, s));
-    fe root = fe_pow_u64(g, o + (uint64_t)s * (m - 1));   // the last row of the progression, then s rows down at a time
-    for (uint32_t t = 0; t < e; ++t) {
-        E = fe_mul(E, fe_sub(x, root));
-        root = fe_mul(root, gs_inv);
-    }
-}
-
-size_t air_program_first_bad_op(const std::vector<AirOpHost>& ops, uint32_t load_a_end, uint32_t load_b_end, size_t n_values, uint32_t n_out,
-                                uint32_t n_periodic) {
-    auto value = [&](uint32_t i, size_t t) { return i < t && ops[i].op != 5; };   // an earlier op that produces a value
-    for (size_t t = 0; t < ops.size(); ++t) {
-        const AirOpHost& o = ops[t];
-        bool ok;
-        switch (o.op) {
-            case 0: ok = o.a < load_a_end && o.b < load_b_end; break;
-            case 1: ok = o.a < n_values; break;
-            case 2: case 3: case 4: ok = value(o.a, t) && value(o.b, t); break;
-            case 5: ok = o.a < n_out && value(o.b, t); break;
-            case 6: ok = o.a < load_a_end && o.b < n_periodic; break;
-            default: ok = false;
-        }
-        if (!ok) return t;
-    }
-    return ops.size();
 }
 
 }  // namespace sp

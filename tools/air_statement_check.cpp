@@ -1,0 +1,132 @@
+// Stand-alone check of the statement decoder (csrc/air_desc.cpp) for sanitizer builds: malformed and well-formed C structs of every
+// part through sp::air_statement_from_c, each with the verdict it must get, and the host model on what was accepted.  No GPU, no
+// library: build and run on the CPU, from the repository root:
+//   hipcc -x hip --offload-arch=gfx950 -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=all \
+//     tools/air_statement_check.cpp lambdaworks_cairo_prover_amd/csrc/air_desc.cpp lambdaworks_cairo_prover_amd/csrc/cairo_air_host.cpp \
+//     lambdaworks_cairo_prover_amd/csrc/cairo_host.cpp -o /tmp/air_statement_check && /tmp/air_statement_check
+#include "../lambdaworks_cairo_prover_amd/csrc/air_desc.h"
+#include <cstdio>
+#include <cstring>
+#include <functional>
+
+namespace {
+int failures = 0;
+struct Felt { uint8_t b[32]; };
+Felt felt(uint64_t v) { Felt f{}; for (int i = 0; i < 8; ++i) f.b[31 - i] = (uint8_t)(v >> (8 * i)); return f; }
+
+// x' = x + K on one main column, one auxiliary column (a running product of gamma - x, over gamma - x), x_0 = 3 and z_0 from the
+// challenge; every part in its well-formed form, for a trace of 16 rows
+struct Parts {
+    sp_air_op ops[5] = {{0, 0, 1, 0, 0}, {0, 0, 0, 0, 0}, {6, 0, 0, 0, 0}, {2, 0, 1, 2, 0}, {5, 0, 0, 3, 0}};   // (LOAD next, LOAD cur, PERIODIC, ADD - never run here)
+    sp_air_boundary boundary[2] = {};
+    sp_air_desc d{};
+    sp_air_op aux_ops[4] = {{1, 0, 0, 0, 0}, {0, 0, 0, 0, 0}, {3, 0, 0, 1, 0}, {6, 0, 7, 0, 0}};   // gamma, x, gamma - x, table read at shift 7
+    sp_air_aux_column aux_cols[1] = {{SP_AIR_AUX_PRODUCT, 2, 2, 0}};
+    sp_air_aux_desc aux{};
+    Felt keys[8];
+    sp_air_periodic_column pcols[65];
+    sp_air_periodic_desc per{};
+    sp_air_stride strides[2] = {{4, 1}, {1, 0}};
+    sp_air_stride_desc sd{};
+    Felt bconsts[1] = {felt(77)};
+    sp_air_op bops[3] = {{1, 0, 1, 0, 0}, {1, 0, 0, 0, 0}, {3, 0, 0, 1, 0}};   // gamma, 77, gamma - 77
+    sp_air_boundary_value bvalues[2] = {{1, 2, 2, 0}, {0, 2, SP_AIR_AUX_NO_DEN, 0}};
+    sp_air_boundary_desc bv{};
+    Parts() {
+        for (int j = 0; j < 8; ++j) keys[j] = felt(100 + j);
+        for (auto& c : pcols) c = sp_air_periodic_column{8, 0, keys[0].b};
+        boundary[0].col = 0; boundary[1].col = 1;
+        d.main_cols = 1; d.aux_cols = 1; d.n_offsets = 2; d.offsets[1] = 1; d.n_transitions = 1; d.degrees[0] = 1; d.exemptions[0] = 1;
+        d.num_transition_exemptions = 1; d.degree_bound_factor = 2; d.n_ops = 5; d.ops = ops; d.n_rap = 1; d.aux_kind = SP_AIR_AUX_PROGRAM;
+        d.n_boundary = 2; d.boundary = boundary;
+        aux.n_ops = 3; aux.ops = aux_ops; aux.n_cols = 1; aux.cols = aux_cols;
+        per.n_cols = 1; per.cols = pcols;
+        sd.n = 1; sd.strides = strides;
+        bv.n_ops = 3; bv.ops = bops; bv.n_consts = 1; bv.consts = bconsts[0].b; bv.n_values = 2; bv.values = bvalues;
+    }
+};
+
+// use: which parts go to the decoder (a x p s b, upper case P: the auxiliary program may read the periodic columns)
+void run(const char* label, const char* use, bool want_ok, const std::function<void(Parts&)>& patch) {
+    Parts p;
+    patch(p);
+    auto has = [&](char c) { return std::strchr(use, c) != nullptr; };
+    sp::AirStatement st;
+    const std::string refused = sp::air_statement_from_c(&p.d, has('x') ? &p.aux : nullptr, has('p') ? &p.per : nullptr, has('s') ? &p.sd : nullptr,
+                                                         has('b') ? &p.bv : nullptr, has('P'), 16, st);
+    const bool ok = refused.empty();
+    if (ok != want_ok) { ++failures; std::printf("FAIL %-44s wanted %s, got %s\n", label, want_ok ? "accepted" : "refused", ok ? "accepted" : refused.c_str()); return; }
+    std::printf("ok   %-44s %s\n", label, ok ? "accepted" : refused.substr(0, 60).c_str());
+    if (!ok) return;
+    // the model on what was accepted: stride plan and zerofier, periodic columns as polynomials, boundary values under a challenge
+    sp::AirStridePlan plan;
+    bool fine = sp::air_stride_plan(st.air, 16, plan) && st.aux.has_value() == has('x') && st.periodic.has_value() == has('p') && st.bvals.has_value() == has('b') &&
+                (st.aux_periodic() != nullptr) == (has('P') && has('p'));
+    const fe x = fe_from_u64(5);
+    for (const sp::AirStrideHost& c : plan.classes) { fe Z, E; sp::air_stride_eval(c.period, c.offset, 1, 16, x, Z, E); fine = fine && !fe_is_zero(Z); }
+    if (st.periodic)
+        for (const auto& col : st.periodic->cols) {   // P(g^i) = values[i mod period]
+            const fe at = sp::air_periodic_eval(sp::air_periodic_interpolate(col), 16, fe_pow_u64(sp::air_root_of_unity(4), 11));
+            fine = fine && fe_eq(fe_reduce_once(at), fe_reduce_once(col[11 % col.size()]));
+        }
+    if (st.bvals) {
+        std::vector<sp::BoundaryConstraint> bcs = st.air.boundary;
+        fine = fine && sp::air_resolve_boundary_into(*st.bvals, {fe_from_u64(80)}, bcs) && fe_eq(fe_reduce_once(bcs[1].value), fe_one()) &&
+               fe_eq(fe_reduce_once(bcs[0].value), fe_from_u64(3)) && !sp::air_resolve_boundary_into(*st.bvals, {fe_from_u64(77)}, bcs);
+    }
+    if (!fine) { ++failures; std::printf("FAIL %-44s the host model disagrees\n", label); }
+}
+}  // namespace
+
+int main() {
+    const auto none = [](Parts&) {};
+    // ---- well-formed, one of each kind
+    run("plain", "", true, [](Parts& p) { p.ops[2] = sp_air_op{1, 0, 0, 0, 0}; });
+    run("auxiliary program", "x", true, none);
+    run("periodic columns", "p", true, none);
+    run("periodic columns beside an auxiliary program", "xp", true, none);
+    run("64 periodic columns", "p", true, [](Parts& p) { p.per.n_cols = 64; });
+    run("strides", "ps", true, none);
+    run("boundary values", "xb", true, none);
+    run("auxiliary program reading a table (_pub)", "xpP", true, [](Parts& p) { p.aux.n_ops = 4; });
+    run("everything", "xpsbP", true, [](Parts& p) { p.aux.n_ops = 4; });
+    // ---- malformed: the table of tests/test_air_statement.py
+    run("n_offsets = 9", "xp", false, [](Parts& p) { p.d.n_offsets = 9; });
+    run("a count without its array", "", false, [](Parts& p) { p.d.ops = nullptr; });
+    run("period no power of two", "p", false, [](Parts& p) { p.pcols[0].period = 6; });
+    run("period longer than the trace", "p", false, [](Parts& p) { p.pcols[0].period = 32; });
+    run("period 2^31", "p", false, [](Parts& p) { p.pcols[0].period = 1u << 31; });
+    run("65 periodic columns", "p", false, [](Parts& p) { p.per.n_cols = 65; });
+    run("null values", "p", false, [](Parts& p) { p.pcols[0].values = nullptr; });
+    run("strides: not one per transition", "ps", false, [](Parts& p) { p.sd.n = 2; });
+    run("strides: offset >= period", "ps", false, [](Parts& p) { p.strides[0].offset = 4; });
+    run("strides: null", "ps", false, [](Parts& p) { p.sd.strides = nullptr; });
+    run("aux: op 6 outside _pub", "xp", false, [](Parts& p) { p.aux.n_ops = 4; });
+    run("aux: op 6 beyond the columns", "xpP", false, [](Parts& p) { p.aux.n_ops = 4; p.aux_ops[3].b = 1; });
+    run("aux: n_cols != aux_cols", "x", false, [](Parts& p) { p.aux.n_cols = 2; });
+    run("aux: aux_kind is not a program", "x", false, [](Parts& p) { p.d.aux_kind = 1; });
+    run("aux: no ops", "x", false, [](Parts& p) { p.aux.n_ops = 0; });
+    run("aux: 65536 ops", "x", false, [](Parts& p) { p.aux.n_ops = 65536; });
+    run("aux: operand is a later op", "x", false, [](Parts& p) { p.aux_ops[2].b = 3; });
+    run("aux: column names an op beyond the program", "x", false, [](Parts& p) { p.aux_cols[0].den_op = 3; });
+    run("bvals: null ops", "xb", false, [](Parts& p) { p.bv.ops = nullptr; });
+    run("bvals: null consts", "xb", false, [](Parts& p) { p.bv.consts = nullptr; });
+    run("bvals: null values", "xb", false, [](Parts& p) { p.bv.values = nullptr; });
+    run("bvals: no ops", "xb", false, [](Parts& p) { p.bv.n_ops = 0; });
+    run("bvals: 2^32 - 1 ops", "xb", false, [](Parts& p) { p.bv.n_ops = 0xFFFFFFFFu; });
+    run("bvals: LOAD", "xb", false, [](Parts& p) { p.bops[0].op = 0; });
+    run("bvals: OUT", "xb", false, [](Parts& p) { p.bops[2].op = 5; });
+    run("bvals: PERIODIC", "xb", false, [](Parts& p) { p.bops[0].op = 6; });
+    run("bvals: op 7", "xb", false, [](Parts& p) { p.bops[2].op = 7; });
+    run("bvals: operand is itself", "xb", false, [](Parts& p) { p.bops[2].a = 2; });
+    run("bvals: operand is later", "xb", false, [](Parts& p) { p.bops[2].b = 3; });
+    run("bvals: constant beyond consts + rap", "xb", false, [](Parts& p) { p.bops[1].a = 2; });
+    run("bvals: num_op beyond the program", "xb", false, [](Parts& p) { p.bvalues[0].num_op = 3; });
+    run("bvals: den_op beyond the program", "xb", false, [](Parts& p) { p.bvalues[0].den_op = 3; });
+    run("bvals: boundary >= n_boundary", "xb", false, [](Parts& p) { p.bvalues[0].boundary = 2; });
+    run("bvals: a boundary named twice", "xb", false, [](Parts& p) { p.bvalues[1].boundary = 1; });
+    run("no main column", "", false, [](Parts& p) { p.d.main_cols = 0; p.ops[2] = sp_air_op{1, 0, 0, 0, 0}; });
+    run("1025 columns", "", false, [](Parts& p) { p.d.main_cols = 1024; p.ops[2] = sp_air_op{1, 0, 0, 0, 0}; });
+    std::printf("%s\n", failures ? "FAILED" : "all verdicts as expected");
+    return failures ? 1 : 0;
+}
