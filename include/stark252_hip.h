@@ -444,11 +444,23 @@ int sp_air_limits(uint32_t out[8]);
  *   SP_AIR_AUX_PRODUCT  z_0 = 1, z_i = z_(i-1) N(i-1) / D(i-1)
  *   SP_AIR_AUX_SUM      z_0 = 0, z_i = z_(i-1) + N(i-1) / D(i-1)
  * A zero D on any row is SP_E_ZERO_INVERSE.  Bounds: those of the constraint program (sp_air_limits: 65535 ops, 4096 constants,
- * 64 values alive at once). */
+ * 64 values alive at once).
+ *   SP_AIR_AUX_SORTED   a sorted copy of values of the main-trace row (Cairo's memory and range-check arguments).  num_op is the op whose
+ *                       value the column carries, den_op the op that is the KEY of its sort group (SP_AIR_AUX_NO_DEN is refused), pad
+ *                       the key's bits (1 .. 64; 0 means 64, above 64 is refused; kinds 0 and 1 ignore pad).  Columns with one den_op
+ *                       form a group and must agree on pad; at most SP_AIR_AUX_MAX_SORT_GROUPS groups.  With key_i the canonical
+ *                       integer of the key on row i and pi the stable ascending order of the rows by key_i (ties stay in row order),
+ *                       row i of the column holds the value of num_op on row pi(i).  A key >= 2^bits on any row - every "negative"
+ *                       element such as p - 1 included - is SP_E_INVALID_ARG ("a sort key is out of range").
+ * A LOAD with b = main_cols + k reads auxiliary column k of row (i + s) mod n; k must be a SORTED column.  The ops behind a sorted
+ * column's key or value must not contain such a LOAD, directly or through earlier ops (SP_E_INVALID_ARG).  All sort groups are built
+ * before any product or sum, whatever the order of the columns. */
 #define SP_AIR_AUX_PROGRAM 3
 #define SP_AIR_AUX_PRODUCT 0
 #define SP_AIR_AUX_SUM 1
+#define SP_AIR_AUX_SORTED 2
 #define SP_AIR_AUX_NO_DEN 0xFFFFFFFFu
+#define SP_AIR_AUX_MAX_SORT_GROUPS 16
 typedef struct { uint32_t kind, num_op, den_op, pad; } sp_air_aux_column;
 typedef struct {
     uint32_t n_ops; const sp_air_op* ops;

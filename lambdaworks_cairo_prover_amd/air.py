@@ -62,7 +62,8 @@ def _check_layout():
 
 
 AUX_NONE, AUX_FIBONACCI_RAP, AUX_CALLBACK, AUX_PROGRAM = 0, 1, 2, 3
-AUX_PRODUCT, AUX_SUM = 0, 1          # sp_air_aux_column.kind
+AUX_PRODUCT, AUX_SUM, AUX_SORTED = 0, 1, 2   # sp_air_aux_column.kind
+AUX_MAX_SORT_GROUPS = 16             # SP_AIR_AUX_MAX_SORT_GROUPS: sorted columns with one key op form a group
 AUX_NO_DEN = 0xFFFFFFFF              # sp_air_aux_column.den_op: D = 1
 AUX_MAX_SHIFT = 7
 _RAP_TAG = 0x8000
@@ -271,12 +272,16 @@ class Value:
 class AuxProgram:
     """The auxiliary program of an AIR built with aux_kind=AUX_PROGRAM (sp_air_aux_desc): evaluated once per trace row i on the
     device.  load(shift, col) reads main column `col` of row (i + shift) mod n; product(N, D) and running_sum(N, D) each declare the
-    next auxiliary column: z_0 = 1, z_i = z_(i-1) N(i-1) / D(i-1), or z_0 = 0, z_i = z_(i-1) + N(i-1) / D(i-1) (D = 1 when None)."""
+    next auxiliary column: z_0 = 1, z_i = z_(i-1) N(i-1) / D(i-1), or z_0 = 0, z_i = z_(i-1) + N(i-1) / D(i-1) (D = 1 when None).
+    sorted(key, carry) declares 1 + len(carry) columns: the key and the carried values, each evaluated on the main-trace row alone, in
+    the stable ascending order of the rows by the key's canonical integer; sorted_load(shift, k) reads such a column from a product
+    or a running sum."""
 
     def __init__(self, main_cols, n_rap, periodic_cols=()):
         self.main_cols, self.n_rap = main_cols, n_rap
         self.periodic_cols = periodic_cols   # the owning AirBuilder's periodic columns: what table() may read
         self.ops, self.consts, self.cols = [], [], []
+        self.key_bits = {}                   # sorted column -> the bits of its group's key (sp_air_aux_column.pad)
         self._const_at = {}
 
     def _emit(self, op, a, b):
@@ -330,6 +335,51 @@ class AuxProgram:
     def running_sum(self, num, den=None):
         self._column(AUX_SUM, num, den)
 
+    def sorted(self, key, carry=(), key_bits=64):
+        """Declares 1 + len(carry) auxiliary columns and returns their indices: the key first, then the carried values, row i of each
+        holding its expression on row pi(i), pi the stable ascending order of the rows by the key's canonical integer (ties stay in row
+        order).  The key must be < 2^key_bits on every row (1 <= key_bits <= 64: the device sorts ceil(key_bits / 8) digits); key and
+        carried values depend on the main-trace row only - none may read a sorted column.  Columns declared with the same key Value
+        form one group: one sort serves them all."""
+        if not 1 <= key_bits <= 64:
+            raise ValueError(f"aux program: key_bits {key_bits} outside 1 .. 64")
+        values = [v if isinstance(v, Value) else self.const(v) for v in (key, *carry)]
+        tainted = self._reads_sorted()
+        for v in values:
+            if v.b is not self or tainted[v.i]:
+                raise ValueError("aux program: the key and the carried values of a sorted column are values of this program that read no sorted column")
+        first = len(self.cols)
+        for v in values:
+            self.key_bits[len(self.cols)] = key_bits
+            self.cols.append((AUX_SORTED, v.i, values[0].i))
+        return list(range(first, len(self.cols)))
+
+    def sorted_load(self, shift, k):
+        """Sorted auxiliary column k (an index sorted() returned) on row (i + shift) mod n: OP_LOAD(shift, main_cols + k)."""
+        if not 0 <= shift <= AUX_MAX_SHIFT:
+            raise ValueError(f"aux program: row shift {shift} outside 0 .. {AUX_MAX_SHIFT}")
+        if not 0 <= k < len(self.cols) or self.cols[k][0] != AUX_SORTED:
+            raise ValueError(f"aux program: auxiliary column {k} is not a sorted column declared so far")
+        return self._emit(OP_LOAD, shift, self.main_cols + k)
+
+    def _reads_sorted(self):
+        """Per op: whether its value depends on a sorted column."""
+        tainted = []
+        for op, a, b in self.ops:
+            if op == OP_LOAD:
+                tainted.append(b >= self.main_cols)
+            else:
+                tainted.append(op in (OP_ADD, OP_SUB, OP_MUL) and (tainted[a] or tainted[b]))
+        return tainted
+
+    def sort_groups(self):
+        """{key op: [sorted column, ...]} in declaration order."""
+        groups = {}
+        for k, (kind, _, den_op) in enumerate(self.cols):
+            if kind == AUX_SORTED:
+                groups.setdefault(den_op, []).append(k)
+        return groups
+
     def resolved_ops(self):
         """The ops as the library reads them: RAP challenges follow the constants."""
         return [(op, len(self.consts) + (a & ~_RAP_TAG) if op == OP_CONST and a & _RAP_TAG else a, b) for op, a, b in self.ops]
@@ -338,35 +388,39 @@ class AuxProgram:
         """The auxiliary columns in Python integers (the semantics of sp_air_prove_aux): rows = n x main_cols field elements (any
         sequence of rows, or a numpy array of Python ints); returns an (n, len(cols)) numpy object array.  Each op is one vectorised
         numpy operation over all rows; the inverses are one batch inversion; the scans run row by row.  periodic: the columns table()
-        reads, one list of values each (None: those of the owning AirBuilder)."""
+        reads, one list of values each (None: those of the owning AirBuilder).  Two phases: the ops that read no sorted column, from
+        which the sorted columns are built (Python's stable sort by the key's integer; ValueError on a key >= 2^key_bits), then the ops
+        that read them."""
         import numpy as np
         m = np.empty((len(rows), self.main_cols), dtype=object)
         m[:, :] = rows if not isinstance(rows, np.ndarray) else rows.astype(object)
         n = m.shape[0]
         consts = list(self.consts) + [int(r) % P for r in rap]
-        vals = []
-        for op, a, b in self.resolved_ops():
-            if op == OP_LOAD:
-                v = np.roll(m[:, b], -a)
-            elif op == OP_CONST:
-                v = np.full(n, consts[a], dtype=object)
-            elif op == OP_ADD:
-                v = (vals[a] + vals[b]) % P
-            elif op == OP_SUB:
-                v = (vals[a] - vals[b]) % P
-            elif op == OP_MUL:
-                v = (vals[a] * vals[b]) % P
-            elif op == OP_PERIODIC:
-                values = (self.periodic_cols if periodic is None else periodic)[b]
-                v = np.array([int(x) % P for x in values], dtype=object)[(np.arange(n) + a) % len(values)]
-            else:
-                raise ValueError(f"aux program: op {op}")
-            vals.append(v)
-        dens = [k for k, (_, _, d) in enumerate(self.cols) if d != AUX_NO_DEN]
+        out = np.empty((n, len(self.cols)), dtype=object)
+        tainted = self._reads_sorted()
+        vals = [None] * len(self.ops)
+        for phase in (False, True):
+            self._evaluate_ops(vals, [t for t, late in enumerate(tainted) if late == phase], m, out, consts, periodic)
+            if phase:
+                break
+            for key_op, members in self.sort_groups().items():
+                for k in members:
+                    if tainted[key_op] or tainted[self.cols[k][1]]:
+                        raise ValueError(f"aux program: the key or the value of sorted column {k} reads a sorted column")
+                keys = [int(x) for x in vals[key_op]]
+                worst = max(range(n), key=keys.__getitem__)
+                for k in members:
+                    if keys[worst] >> self.key_bits.get(k, 64):
+                        raise ValueError(f"aux program: a sort key is out of range (row {worst} has {keys[worst]} >= 2^{self.key_bits.get(k, 64)}, column {k})")
+                order = sorted(range(n), key=keys.__getitem__)
+                for k in members:
+                    out[:, k] = vals[self.cols[k][1]][order]
+        dens = [k for k, (kind, _, d) in enumerate(self.cols) if d != AUX_NO_DEN and kind != AUX_SORTED]
         flat = [int(x) for k in dens for x in vals[self.cols[k][2]]]
         inv = _batch_inverse(flat)
-        out = np.empty((n, len(self.cols)), dtype=object)
         for k, (kind, num_op, den_op) in enumerate(self.cols):
+            if kind == AUX_SORTED:
+                continue
             t = vals[num_op]
             if den_op != AUX_NO_DEN:
                 j = dens.index(k)
@@ -380,6 +434,31 @@ class AuxProgram:
                 col[i] = z
                 z = z * int(t[i]) % P
         return out
+
+    def _evaluate_ops(self, vals, which, m, out, consts, periodic):
+        """vals[t] for the ops `which` (ascending), each one vectorised operation over all rows; a LOAD beyond the main columns reads
+        the sorted column of `out`."""
+        import numpy as np
+        n = m.shape[0]
+        ops = self.resolved_ops()
+        for t in which:
+            op, a, b = ops[t]
+            if op == OP_LOAD:
+                v = np.roll(m[:, b] if b < self.main_cols else out[:, b - self.main_cols], -a)
+            elif op == OP_CONST:
+                v = np.full(n, consts[a], dtype=object)
+            elif op == OP_ADD:
+                v = (vals[a] + vals[b]) % P
+            elif op == OP_SUB:
+                v = (vals[a] - vals[b]) % P
+            elif op == OP_MUL:
+                v = (vals[a] * vals[b]) % P
+            elif op == OP_PERIODIC:
+                values = (self.periodic_cols if periodic is None else periodic)[b]
+                v = np.array([int(x) % P for x in values], dtype=object)[(np.arange(n) + a) % len(values)]
+            else:
+                raise ValueError(f"aux program: op {op}")
+            vals[t] = v
 
 
 def _batch_inverse(xs):
@@ -670,6 +749,13 @@ class AirBuilder:
                     raise ValueError(f"aux program exceeds the {name} limit of sp_air_prove_aux: {value} > {lim[name]}")
             if len(self.aux.consts) + self.n_rap > 65535:
                 raise ValueError("aux program: constants and RAP challenges exceed the 16-bit operand range")
+            groups = self.aux.sort_groups()
+            if len(groups) > AUX_MAX_SORT_GROUPS:
+                raise ValueError(f"aux program exceeds the limit of {AUX_MAX_SORT_GROUPS} sort groups: {len(groups)}")
+            for members in groups.values():
+                bits = {self.aux.key_bits.get(k, 64) for k in members}
+                if len(bits) > 1 or not 1 <= min(bits) <= 64:
+                    raise ValueError(f"aux program: the sorted columns {members} share a key and must agree on key_bits in 1 .. 64, not {sorted(bits)}")
         if self.bvalues:
             for name, value in (("constants", len(self.public.consts)), ("ops", len(self.public.ops))):
                 if value > lim[name]:
@@ -773,6 +859,7 @@ class AirBuilder:
         cols = (AirAuxColumnC * max(1, len(p.cols)))()
         for k, (kind, num_op, den_op) in enumerate(p.cols):
             cols[k].kind, cols[k].num_op, cols[k].den_op = kind, num_op, den_op
+            cols[k].pad = p.key_bits.get(k, 64) if kind == AUX_SORTED else 0   # (key_bits; the library reads 0 as 64)
         x = AirAuxDescC()
         x.n_ops, x.ops = len(p.ops), ctypes.cast(ops, ctypes.POINTER(AirOpC))
         x.n_consts, x.consts = len(p.consts), ctypes.cast(consts, ctypes.c_void_p)
@@ -997,3 +1084,63 @@ def public_permutation_trace(n, public, fill, order):
     a = [int(v) % P for v in list(public) + list(fill)]
     src = [0] * L + [int(v) % P for v in fill]
     return [[a[i], src[order[i]]] for i in range(n - 1)] + [[0, 0]]
+
+
+# ---- sorted auxiliary columns: two worked examples ------------------------------------------------------------------------------
+def sorted_range_check(n, lo, hi, key_bits=16):
+    """Every a_i lies in lo .. hi, and every value of that range occurs: range check by sorting.  Main column a; auxiliary columns a'
+    (a sorted, trace column 1) and the grand product z (trace column 2), one challenge gamma.  z_0 = 1 and z' (gamma - a') = z (gamma - a) on every
+    row - no exemption: the last row wraps to z_0 = 1 and closes the product, so a' is a permutation of a.  Continuity: (a'_(i+1) - a'_i)
+    (a'_(i+1) - a'_i - 1) = 0 with the last row exempt; a'_0 = lo and a'_(n-1) = hi.  degree_bound_factor 1."""
+    if not 0 <= lo <= hi < 1 << key_bits or hi - lo >= n:
+        raise ValueError(f"sorted_range_check: the range {lo} .. {hi} on {n} rows with keys of {key_bits} bits")
+    b = AirBuilder(1, [0, 1], 1, aux_cols=2, n_rap=1, aux_kind=AUX_PROGRAM)
+    gamma = b.rap(0)
+    b.constraint(b.load(1, 2) * (gamma - b.load(0, 1)) - b.load(0, 2) * (gamma - b.load(0, 0)), degree=2, exemptions=0)
+    step = b.load(1, 1) - b.load(0, 1)
+    b.constraint(step * (step - 1), degree=2, exemptions=1)
+    b.boundary(2, 0, 1); b.boundary(1, 0, lo); b.boundary(1, n - 1, hi)
+    g = b.aux.rap(0)
+    a = b.aux.load(0, 0)
+    s, = b.aux.sorted(a, key_bits=key_bits)
+    b.aux.product(g - a, g - b.aux.sorted_load(0, s))
+    return b
+
+
+def sorted_range_check_trace(n, lo, hi, extra, order):
+    """(n, 1) Python ints: every value of lo .. hi once and the n - (hi - lo + 1) values `extra` (each in the range), row i holding
+    entry order[i] of that list (`order` a permutation of range(n))."""
+    values = list(range(lo, hi + 1)) + [int(v) for v in extra]
+    if len(values) != n or any(not lo <= v <= hi for v in values) or sorted(order) != list(range(n)):
+        raise ValueError("sorted_range_check_trace: n - (hi - lo + 1) extra values inside the range and a permutation of range(n)")
+    return [[values[order[i]]] for i in range(n)]
+
+
+def memory_consistency(n, key_bits=64):
+    """A read-only memory: every access (addr, val) of the main trace agrees with every other access of its address, and the addresses
+    used are contiguous - Cairo's memory argument (src/cairo/air.rs in the reference) in program form.  Main columns addr and val;
+    the sorted group (addr'; val') = the accesses by address (trace columns 2 and 3) and the grand product z (trace column 4); challenges alpha and
+    gamma.  z_0 = 1 and z' (gamma - (addr' + alpha val')) = z (gamma - (addr + alpha val)) on every row, the last wrapping to z_0;
+    (addr'_(i+1) - addr'_i)(addr'_(i+1) - addr'_i - 1) = 0 and (val'_(i+1) - val'_i)(addr'_(i+1) - addr'_i - 1) = 0 with the last row
+    exempt.  degree_bound_factor 1; the addresses must be < 2^key_bits."""
+    b = AirBuilder(2, [0, 1], 1, aux_cols=3, n_rap=2, aux_kind=AUX_PROGRAM)
+    alpha, gamma = b.rap(0), b.rap(1)
+    b.constraint(b.load(1, 4) * (gamma - (b.load(0, 2) + alpha * b.load(0, 3))) - b.load(0, 4) * (gamma - (b.load(0, 0) + alpha * b.load(0, 1))),
+                 degree=2, exemptions=0)
+    step = b.load(1, 2) - b.load(0, 2)
+    b.constraint(step * (step - 1), degree=2, exemptions=1)
+    b.constraint((b.load(1, 3) - b.load(0, 3)) * (step - 1), degree=2, exemptions=1)
+    b.boundary(4, 0, 1)
+    al, g = b.aux.rap(0), b.aux.rap(1)
+    addr, val = b.aux.load(0, 0), b.aux.load(0, 1)
+    sa, sv = b.aux.sorted(addr, carry=[val], key_bits=key_bits)
+    b.aux.product(g - (addr + al * val), g - (b.aux.sorted_load(0, sa) + al * b.aux.sorted_load(0, sv)))
+    return b
+
+
+def memory_consistency_trace(n, first, cells, accesses):
+    """(n, 2) Python ints [addr_i, val_i]: the memory holds `cells` at the addresses first, first + 1, ...; row i reads cell accesses[i]
+    (an index into `cells`; every cell at least once, or the addresses are not contiguous)."""
+    if len(accesses) != n or set(accesses) != set(range(len(cells))):
+        raise ValueError("memory_consistency_trace: n accesses that reach every cell")
+    return [[first + j, int(cells[j]) % P] for j in accesses]

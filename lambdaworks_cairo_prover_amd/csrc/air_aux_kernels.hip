@@ -8,17 +8,21 @@ namespace sp {
 // The program runs in the shared interpreter (air_interp.h): LOAD takes the row shift itself, and an OUT stores into the num / den
 // column it names.  Two kernels share the body: a program without op 6 runs the one without periodic columns (PER = false leaves no
 // test for op 6 in it); one with table reads gets the columns' descriptors and raw values.
-template <bool PER, class Periodic>
-__device__ __forceinline__ void air_aux_terms_row(const fe* __restrict__ trace, uint64_t n, uint64_t i, const AirOpDev* __restrict__ ops, uint32_t n_ops,
-                                                  const fe* __restrict__ consts, fe* __restrict__ num, fe* __restrict__ den, Periodic periodic) {
+template <bool PER, class Periodic, class Out>
+__device__ __forceinline__ void air_aux_run_row(const fe* __restrict__ trace, uint64_t n, uint64_t i, const AirOpDev* __restrict__ ops, uint32_t n_ops,
+                                                const fe* __restrict__ consts, Periodic periodic, Out out) {
     air_run_program<PER>(
         ops, n_ops, consts,
         [&](uint32_t shift, uint32_t col) { return fe_ld(trace + (uint64_t)col * n + ((i + shift) & (n - 1))); },   // n is a power of two
-        periodic,
-        [&](uint32_t a, const fe& val) {
-            fe* dst = a < AIR_AUX_DEN_TAG ? num + (uint64_t)a * n : den + (uint64_t)(a - AIR_AUX_DEN_TAG) * n;
-            fe_st(dst + i, val);
-        });
+        periodic, out);
+}
+template <bool PER, class Periodic>
+__device__ __forceinline__ void air_aux_terms_row(const fe* __restrict__ trace, uint64_t n, uint64_t i, const AirOpDev* __restrict__ ops, uint32_t n_ops,
+                                                  const fe* __restrict__ consts, fe* __restrict__ num, fe* __restrict__ den, Periodic periodic) {
+    air_aux_run_row<PER>(trace, n, i, ops, n_ops, consts, periodic, [&](uint32_t a, const fe& val) {
+        fe* dst = a < AIR_AUX_DEN_TAG ? num + (uint64_t)a * n : den + (uint64_t)(a - AIR_AUX_DEN_TAG) * n;
+        fe_st(dst + i, val);
+    });
 }
 
 __global__ void __launch_bounds__(256) air_aux_terms_kernel(const fe* __restrict__ trace, uint64_t n, const AirOpDev* __restrict__ ops, uint32_t n_ops,
@@ -47,6 +51,83 @@ int air_aux_terms(hipStream_t st, const fe* trace, uint64_t n, const AirOpDev* o
     const dim3 grid((unsigned)((n + 255) / 256));
     if (pcols) hipLaunchKernelGGL(air_aux_terms_periodic_kernel, grid, dim3(256), 0, st, trace, n, ops, n_ops, consts, num, den, pcols, pvals);
     else hipLaunchKernelGGL(air_aux_terms_kernel, grid, dim3(256), 0, st, trace, n, ops, n_ops, consts, num, den);
+    SP_HIP_CHECK(hipGetLastError());
+    return SP_OK;
+}
+
+// ---- sorted columns -------------------------------------------------------------------------------------------------
+// Key pass: the same program shape, OUT a < AIR_AUX_DEN_TAG storing carried value a at vals[a * n + i] and OUT AIR_AUX_DEN_TAG the
+// group's key: out of Montgomery form, its low 64 bits and the row become the pair the radix sort takes; anything above key_bits
+// raises the flag (the sort then orders the low bits, all in bounds, and the host refuses the proof).
+template <bool PER, class Periodic>
+__device__ __forceinline__ void air_aux_sort_terms_row(const fe* __restrict__ trace, uint64_t n, uint64_t i, const AirOpDev* __restrict__ ops, uint32_t n_ops,
+                                                       const fe* __restrict__ consts, fe* __restrict__ vals, uint64_t* __restrict__ keys, uint32_t* __restrict__ idx,
+                                                       uint32_t key_bits, int* __restrict__ flag, Periodic periodic) {
+    air_aux_run_row<PER>(trace, n, i, ops, n_ops, consts, periodic, [&](uint32_t a, const fe& val) {
+        if (a < AIR_AUX_DEN_TAG) { fe_st(vals + (uint64_t)a * n + i, val); return; }
+        const fe raw = fe_from_mont(val);
+        const uint64_t key = (uint64_t)raw.v[0] | ((uint64_t)raw.v[1] << 32);
+        const uint32_t high = raw.v[2] | raw.v[3] | raw.v[4] | raw.v[5] | raw.v[6] | raw.v[7];
+        if (high || (key_bits < 64 && (key >> key_bits))) atomicExch(flag, AIR_AUX_FLAG_KEY_RANGE);
+        keys[i] = key;
+        idx[i] = (uint32_t)i;
+    });
+}
+__global__ void __launch_bounds__(256) air_aux_sort_terms_kernel(const fe* __restrict__ trace, uint64_t n, const AirOpDev* __restrict__ ops, uint32_t n_ops,
+                                                                 const fe* __restrict__ consts, fe* __restrict__ vals, uint64_t* __restrict__ keys,
+                                                                 uint32_t* __restrict__ idx, uint32_t key_bits, int* __restrict__ flag) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    air_aux_sort_terms_row<false>(trace, n, i, ops, n_ops, consts, vals, keys, idx, key_bits, flag, AirNoPeriodic{});
+}
+__global__ void __launch_bounds__(256) air_aux_sort_terms_periodic_kernel(const fe* __restrict__ trace, uint64_t n, const AirOpDev* __restrict__ ops, uint32_t n_ops,
+                                                                          const fe* __restrict__ consts, fe* __restrict__ vals, uint64_t* __restrict__ keys,
+                                                                          uint32_t* __restrict__ idx, uint32_t key_bits, int* __restrict__ flag,
+                                                                          const AirPeriodicCol* __restrict__ pcols, const fe* __restrict__ pvals) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    air_aux_sort_terms_row<true>(trace, n, i, ops, n_ops, consts, vals, keys, idx, key_bits, flag, [&](uint32_t shift, uint32_t col) {
+        const AirPeriodicCol pc = pcols[col];
+        return fe_ld(pvals + pc.off + ((i + shift) & ((1ull << pc.logp) - 1ull)));
+    });
+}
+
+int air_aux_sort_terms(hipStream_t st, const fe* trace, uint64_t n, const AirOpDev* ops, uint32_t n_ops, const fe* consts, fe* vals, uint64_t* keys,
+                       uint32_t* idx, uint32_t key_bits, int* flag, const AirPeriodicCol* pcols, const fe* pvals) {
+    if (n == 0 || (n & (n - 1)) || n >= (1ull << 32) || key_bits == 0 || key_bits > 64 || (pcols == nullptr) != (pvals == nullptr)) return SP_E_INVALID_ARG;
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (pcols) hipLaunchKernelGGL(air_aux_sort_terms_periodic_kernel, grid, dim3(256), 0, st, trace, n, ops, n_ops, consts, vals, keys, idx, key_bits, flag, pcols, pvals);
+    else hipLaunchKernelGGL(air_aux_sort_terms_kernel, grid, dim3(256), 0, st, trace, n, ops, n_ops, consts, vals, keys, idx, key_bits, flag);
+    SP_HIP_CHECK(hipGetLastError());
+    return SP_OK;
+}
+
+// Gather: one lane per output element, a block's 256 outputs of one column contiguous.  The 32-byte read at vals[idx[i]] is a whole
+// sector of its own wherever it lands (nothing of a neighbour's is fetched in vain, and nothing can be coalesced: the order is the
+// data's); the writes are the coalesced side.  idx[i] < n: the sort permutes the rows the key pass wrote.
+__global__ void __launch_bounds__(256) air_aux_gather_kernel(const fe* __restrict__ vals, const uint32_t* __restrict__ idx, uint64_t n, fe* __restrict__ aux,
+                                                             const uint32_t* __restrict__ col_of) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t k = blockIdx.y;
+    fe_st(aux + (uint64_t)col_of[k] * n + i, fe_ld(vals + (uint64_t)k * n + idx[i]));
+}
+int air_aux_gather(hipStream_t st, const fe* vals, const uint32_t* idx, uint64_t n, fe* aux, const uint32_t* col_of, uint32_t n_cols) {
+    if (n_cols == 0) return SP_OK;
+    hipLaunchKernelGGL(air_aux_gather_kernel, dim3((unsigned)((n + 255) / 256), n_cols), dim3(256), 0, st, vals, idx, n, aux, col_of);
+    SP_HIP_CHECK(hipGetLastError());
+    return SP_OK;
+}
+
+// The key column is the sorted keys back in Montgomery form: no gather.
+__global__ void __launch_bounds__(256) air_aux_key_columns_kernel(const uint64_t* __restrict__ keys, uint64_t n, fe* __restrict__ aux, const uint32_t* __restrict__ col_of) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    fe_st(aux + (uint64_t)col_of[blockIdx.y] * n + i, fe_from_u64(keys[i]));
+}
+int air_aux_key_columns(hipStream_t st, const uint64_t* keys, uint64_t n, fe* aux, const uint32_t* col_of, uint32_t n_cols) {
+    if (n_cols == 0) return SP_OK;
+    hipLaunchKernelGGL(air_aux_key_columns_kernel, dim3((unsigned)((n + 255) / 256), n_cols), dim3(256), 0, st, keys, n, aux, col_of);
     SP_HIP_CHECK(hipGetLastError());
     return SP_OK;
 }

@@ -92,24 +92,57 @@ bool aux_from_c(const AirDescHost& air, const sp_air_aux_desc* x, AirAuxHost& au
         !x->cols || x->n_ops > AIR_LIMIT_OPS || x->n_consts > AIR_LIMIT_CONSTS) return false;
     ops_from_c(x->ops, x->n_ops, aux.ops);
     consts_from_c(x->consts, x->n_consts, aux.consts);
-    for (uint32_t k = 0; k < x->n_cols; ++k) aux.cols.push_back(AirAuxColumnHost{x->cols[k].kind, x->cols[k].num_op, x->cols[k].den_op});
+    for (uint32_t k = 0; k < x->n_cols; ++k) aux.cols.push_back(AirAuxColumnHost{x->cols[k].kind, x->cols[k].num_op, x->cols[k].den_op,
+                                                                                 x->cols[k].kind == SP_AIR_AUX_SORTED ? (x->cols[k].pad ? x->cols[k].pad : 64u) : 0u});   // (pad 0: 64 bits; kinds 0 and 1 ignore it)
     return true;
 }
 
-// The auxiliary program against its AIR: operands refer to earlier ops, LOADs to main columns at shifts 0 .. 7, CONSTs to the constants
-// or the n_rap challenges, PERIODICs to one of n_periodic columns (0: none), every column's ops exist.  "" or what is wrong.
+// The auxiliary program against its AIR: operands refer to earlier ops, LOADs to main columns - or to SORTED auxiliary columns - at
+// shifts 0 .. 7, CONSTs to the constants or the n_rap challenges, PERIODICs to one of n_periodic columns (0: none), every column's ops
+// exist; a sorted column has a key op and 1 .. 64 key bits, its group agrees on them, there are at most SP_AIR_AUX_MAX_SORT_GROUPS
+// groups, and nothing behind its key or its value reads a sorted column.  "" or what is wrong.
 std::string validate_aux_program(const AirAuxHost& aux, uint32_t main_cols, uint32_t n_rap, uint32_t n_periodic) {
     const size_t n_ops = aux.ops.size();
     if (n_ops == 0) return "auxiliary program: no ops";
     if (aux.consts.size() + n_rap > 65535) return "auxiliary program: constants and RAP challenges exceed the 16-bit operand range";
-    const size_t bad = air_program_first_bad_op(aux.ops, AIR_LIMIT_AUX_SHIFT + 1, main_cols, aux.consts.size() + n_rap, 0, n_periodic);   // (no OUT: the columns name their ops)
+    bool any_sorted = false;
+    for (const AirAuxColumnHost& c : aux.cols) any_sorted |= c.kind == SP_AIR_AUX_SORTED;
+    // (a program without sorted columns is held to the main columns, as it always was)
+    const uint32_t load_b_end = main_cols + (any_sorted ? (uint32_t)aux.cols.size() : 0u);
+    const size_t bad = air_program_first_bad_op(aux.ops, AIR_LIMIT_AUX_SHIFT + 1, load_b_end, aux.consts.size() + n_rap, 0, n_periodic);   // (no OUT: the columns name their ops)
     if (bad < n_ops)
         return "auxiliary program: malformed op " + std::to_string(bad) + " (LOAD needs a shift of 0 .. 7 and a main column, CONST a constant or a RAP "
                "challenge, ADD / SUB / MUL earlier ops; there is no OUT, and PERIODIC only through sp_air_prove_pub: a shift of 0 .. 7 and a periodic column)";
     for (size_t k = 0; k < aux.cols.size(); ++k) {
         const AirAuxColumnHost& c = aux.cols[k];
-        if (c.kind > SP_AIR_AUX_SUM || c.num_op >= n_ops || (c.den_op != SP_AIR_AUX_NO_DEN && c.den_op >= n_ops))
+        if (c.kind > SP_AIR_AUX_SORTED || c.num_op >= n_ops || (c.den_op != SP_AIR_AUX_NO_DEN && c.den_op >= n_ops))
             return "auxiliary program: column " + std::to_string(k) + " has an unknown kind or names an op beyond the program";
+    }
+    if (!any_sorted) return "";
+    // reads[t]: the value of op t depends on a sorted column
+    std::vector<uint8_t> reads(n_ops, 0);
+    for (size_t t = 0; t < n_ops; ++t) {
+        const AirOpHost& o = aux.ops[t];
+        if (o.op == 0 && o.b >= main_cols) {   // a LOAD of an auxiliary column
+            if (aux.cols[o.b - main_cols].kind != SP_AIR_AUX_SORTED)
+                return "auxiliary program: op " + std::to_string(t) + " loads auxiliary column " + std::to_string(o.b - main_cols) + ", which is not a sorted column";
+            reads[t] = 1;
+        } else if (o.op >= 2 && o.op <= 4) reads[t] = reads[o.a] | reads[o.b];
+    }
+    std::vector<std::pair<uint32_t, uint32_t>> groups;   // (key op, key bits)
+    for (size_t k = 0; k < aux.cols.size(); ++k) {
+        const AirAuxColumnHost& c = aux.cols[k];
+        if (c.kind != SP_AIR_AUX_SORTED) continue;
+        const std::string who = "auxiliary program: sorted column " + std::to_string(k);
+        if (c.den_op == SP_AIR_AUX_NO_DEN) return who + " names no key op (den_op)";
+        if (c.key_bits == 0 || c.key_bits > 64) return who + " has " + std::to_string(c.key_bits) + " key bits (pad: 1 .. 64, or 0 for 64)";
+        if (reads[c.num_op] || reads[c.den_op]) return who + " reads a sorted column through its key or its value";
+        size_t g = 0;
+        while (g < groups.size() && groups[g].first != c.den_op) ++g;
+        if (g == groups.size()) {
+            if (g == SP_AIR_AUX_MAX_SORT_GROUPS) return who + " opens more than " + std::to_string(SP_AIR_AUX_MAX_SORT_GROUPS) + " sort groups";
+            groups.emplace_back(c.den_op, c.key_bits);
+        } else if (groups[g].second != c.key_bits) return who + " disagrees with its group (key op " + std::to_string(c.den_op) + ") on the key bits";
     }
     return "";
 }

@@ -38,7 +38,7 @@ struct AirDescHost {
 constexpr uint32_t AIR_LIMIT_COLS = 1024, AIR_LIMIT_BOUNDARY = 4096, AIR_LIMIT_CONSTS = 4096, AIR_LIMIT_OPS = 65535, AIR_LIMIT_AUX_SHIFT = 7;
 
 // Host form of sp_air_aux_desc: the auxiliary program of an AIR with aux_kind SP_AIR_AUX_PROGRAM.
-struct AirAuxColumnHost { uint32_t kind, num_op, den_op; };
+struct AirAuxColumnHost { uint32_t kind, num_op, den_op, key_bits = 0; };   // key_bits: 1 .. 64 for a SORTED column (den_op is its group's key), else 0
 struct AirAuxHost {
     std::vector<AirOpHost> ops;
     std::vector<fe> consts;
@@ -115,8 +115,9 @@ struct AirStatement {
 // carries) and bvals are non-null.  Returns "" and fills `out`, or the cause of the refusal (the entry point puts its own name in
 // front).  Every count and pointer of a part is judged before anything is allocated or copied for it.  The rules: those of
 // sp_air_desc's counts; <= 64 periodic columns, each a power-of-two number of values <= n; strides as air_stride_plan wants them;
-// an auxiliary program that fits its AIR (aux_kind, one column per auxiliary column, ops over earlier ops, LOADs of main columns at
-// shifts 0 .. 7, op 6 only with aux_reads_periodic); boundary values as air_boundary_from_c wants them; the bounds of sp_air_limits.
+// an auxiliary program that fits its AIR (aux_kind, one column per auxiliary column, ops over earlier ops, LOADs of main columns - or
+// of SORTED auxiliary columns, but not from the ops behind a sorted column - at shifts 0 .. 7, op 6 only with aux_reads_periodic, at
+// most SP_AIR_AUX_MAX_SORT_GROUPS sort groups, each with one key_bits in 1 .. 64); boundary values as air_boundary_from_c wants them; the bounds of sp_air_limits.
 // The constraint program itself is checked where it is turned into what runs it (build_air_program, air_verify_host).
 // An sp_air_ext is taken apart by the entry point that receives it; this is the one thing it checks first: null, or what is wrong.
 inline const char* air_ext_refusal(const sp_air_ext* ext) { return ext && ext->size != sizeof(sp_air_ext) ? "sp_air_ext.size is not sizeof(sp_air_ext)" : nullptr; }

@@ -1,6 +1,7 @@
 // Round-by-round STARK prover on the device (see prover.h). Host code only: it sequences kernels on the context
 // stream, keeps every polynomial / evaluation / tree resident in HBM and moves only roots, challenges and openings.
 #include "prover_internal.h"
+#include "sort_kernels.h"
 #include <unordered_map>
 #include <cstring>
 #include <cmath>
@@ -419,6 +420,9 @@ int StarkProver::commit_aux_cairo(const PublicInputs& pub, const fe rap[3], uint
 // Chunks of columns bound the workspace: a chunk holds at most max(1, AUXP_CHUNK_ELEMS / n) columns, so its denominators take
 // at most max(2^22, n) elements (128 MB up to 2^22 rows, 32 bytes a row beyond) and the batch inversion as much scratch again,
 // whatever the number of auxiliary columns.  The numerators are written straight into the trace columns they become.
+// Sorted columns (SP_AIR_AUX_SORTED) come first, one sort group at a time in the same workspace: the carried values of a group go
+// through it at most a chunk's worth of columns per pass, beside the (key, row) pairs and the radix sort's histograms (24 bytes a row).
+// A chunk of products and sums is a run of such columns: a sorted column ends it.
 static constexpr uint64_t AUXP_CHUNK_ELEMS = 1ull << 22;
 
 int StarkProver::commit_aux_program(const AirStatement& st, const std::vector<fe>& rap, uint8_t root_out[32]) {
@@ -430,26 +434,13 @@ int StarkProver::commit_aux_program(const AirStatement& st, const std::vector<fe
     SP_HIP_CHECK(hipSetDevice(c_->device));
     const uint32_t chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(K, AUXP_CHUNK_ELEMS / n_));
     const uint64_t nb = air_aux_scan_blocks(n_);
-    // --- per chunk: the program with an OUT behind every op whose value is an N or a D of the chunk's columns (a value then lives
-    //     only until it is stored), slots by air_assign_slots (which drops what the chunk does not need)
-    struct Chunk { uint32_t k0, kc, n_den; bool periodic; std::vector<AirOpDev> ops; std::vector<uint32_t> kinds, col_of; size_t o_ops, o_kinds, o_col; };
-    std::vector<Chunk> chunks;
-    uint32_t max_den = 0;
-    bool any_periodic = false;
     const uint32_t n_src = (uint32_t)aux.ops.size();
-    for (uint32_t k0 = 0; k0 < K; k0 += chunk) {
-        Chunk ch{};
-        ch.k0 = k0; ch.kc = std::min(chunk, K - k0);
-        std::vector<std::vector<uint32_t>> outs(n_src);
-        for (uint32_t k = 0; k < ch.kc; ++k) {
-            const AirAuxColumnHost& c = aux.cols[k0 + k];
-            ch.kinds.push_back(c.kind);
-            outs[c.num_op].push_back(k);
-            if (c.den_op != SP_AIR_AUX_NO_DEN) { outs[c.den_op].push_back(AIR_AUX_DEN_TAG + ch.n_den); ch.col_of.push_back(k); ++ch.n_den; }
-        }
+    bool any_periodic = false;
+    // the program with an OUT behind every op whose value is wanted - outs[t]: the codes op t is stored under - (a value then lives only
+    // until it is stored), slots by air_assign_slots (which drops what these OUTs do not need)
+    auto program_with_outs = [&](const std::vector<std::vector<uint32_t>>& outs, std::vector<AirOpDev>& dev, bool& reads_periodic) -> int {
         std::vector<AirOpHost> ext;
         std::vector<uint32_t> at(n_src);
-        ext.reserve(n_src + 2 * ch.kc);
         for (uint32_t t = 0; t < n_src; ++t) {
             AirOpHost o = aux.ops[t];
             if (o.op >= 2 && o.op <= 4) { o.a = at[o.a]; o.b = at[o.b]; }   // (LOAD, CONST and PERIODIC name cells, not values)
@@ -457,15 +448,72 @@ int StarkProver::commit_aux_program(const AirStatement& st, const std::vector<fe
             ext.push_back(o);
             for (uint32_t code : outs[t]) ext.push_back(AirOpHost{5, code, at[t]});
         }
-        SP_TRY(air_assign_slots(ext, ch.ops, "aux program: more than 64 values alive at once"));
-        for (const AirOpDev& o : ch.ops) ch.periodic |= o.op == 6;   // (of what air_assign_slots kept: a table read that feeds an N or a D of this chunk)
-        any_periodic |= ch.periodic;
+        SP_TRY(air_assign_slots(ext, dev, "aux program: more than 64 values alive at once"));
+        reads_periodic = false;
+        for (const AirOpDev& o : dev) reads_periodic |= o.op == 6;   // (of what air_assign_slots kept: a table read that feeds one of these OUTs)
+        any_periodic |= reads_periodic;
+        return SP_OK;
+    };
+    // --- per sort group: its key columns (rebuilt from the sorted keys) and its carried columns in passes of at most `chunk`; the
+    //     first pass also stores the key (OUT AIR_AUX_DEN_TAG)
+    struct SortPass { bool periodic; std::vector<AirOpDev> ops; std::vector<uint32_t> col_of; size_t o_ops, o_col; };
+    struct SortGroup { uint32_t key_op, key_bits; std::vector<uint32_t> key_cols, carried; std::vector<SortPass> passes; size_t o_keycol; };
+    std::vector<SortGroup> groups;
+    for (uint32_t k = 0; k < K; ++k) {
+        const AirAuxColumnHost& c = aux.cols[k];
+        if (c.kind != SP_AIR_AUX_SORTED) continue;
+        size_t g = 0;
+        while (g < groups.size() && groups[g].key_op != c.den_op) ++g;
+        if (g == groups.size()) { groups.emplace_back(); groups[g].key_op = c.den_op; groups[g].key_bits = c.key_bits; }
+        (c.num_op == c.den_op ? groups[g].key_cols : groups[g].carried).push_back(k);
+    }
+    uint32_t max_carried = 0;
+    for (SortGroup& g : groups) {
+        for (size_t j0 = 0; j0 == 0 || j0 < g.carried.size(); j0 += chunk) {
+            SortPass ps{};
+            std::vector<std::vector<uint32_t>> outs(n_src);
+            for (size_t j = j0; j < std::min<size_t>(g.carried.size(), j0 + chunk); ++j) {
+                outs[aux.cols[g.carried[j]].num_op].push_back((uint32_t)ps.col_of.size());
+                ps.col_of.push_back(g.carried[j]);
+            }
+            if (j0 == 0) outs[g.key_op].push_back(AIR_AUX_DEN_TAG);
+            SP_TRY(program_with_outs(outs, ps.ops, ps.periodic));
+            max_carried = std::max(max_carried, (uint32_t)ps.col_of.size());
+            g.passes.push_back(std::move(ps));
+        }
+    }
+    if (!groups.empty() && n_ >= (1ull << 32)) { sp_set_error("commit_aux_program: sorted columns need a trace of fewer than 2^32 rows"); return SP_E_INVALID_ARG; }
+    // --- per chunk of products and sums: its N and D
+    struct Chunk { uint32_t k0, kc, n_den; bool periodic; std::vector<AirOpDev> ops; std::vector<uint32_t> kinds, col_of; size_t o_ops, o_kinds, o_col; };
+    std::vector<Chunk> chunks;
+    uint32_t max_den = 0;
+    for (uint32_t k0 = 0; k0 < K;) {
+        if (aux.cols[k0].kind == SP_AIR_AUX_SORTED) { ++k0; continue; }
+        Chunk ch{};
+        ch.k0 = k0;
+        std::vector<std::vector<uint32_t>> outs(n_src);
+        for (; ch.kc < chunk && k0 + ch.kc < K && aux.cols[k0 + ch.kc].kind != SP_AIR_AUX_SORTED; ++ch.kc) {
+            const AirAuxColumnHost& c = aux.cols[k0 + ch.kc];
+            ch.kinds.push_back(c.kind);
+            outs[c.num_op].push_back(ch.kc);
+            if (c.den_op != SP_AIR_AUX_NO_DEN) { outs[c.den_op].push_back(AIR_AUX_DEN_TAG + ch.n_den); ch.col_of.push_back(ch.kc); ++ch.n_den; }
+        }
+        SP_TRY(program_with_outs(outs, ch.ops, ch.periodic));
         max_den = std::max(max_den, ch.n_den);
+        k0 += ch.kc;
         chunks.push_back(std::move(ch));
     }
-    // --- one upload: constants (then the RAP challenges), and per chunk its ops, column kinds and denominator -> column table
+    // --- one upload: constants (then the RAP challenges), per sort pass its ops and value -> column table, per chunk its ops, column
+    //     kinds and denominator -> column table
     UploadLayout lay;
     const size_t o_consts = lay.place(sizeof(fe) * std::max<size_t>(1, aux.consts.size() + rap.size()));
+    for (SortGroup& g : groups) {
+        g.o_keycol = lay.place(sizeof(uint32_t) * std::max<size_t>(1, g.key_cols.size()));
+        for (SortPass& ps : g.passes) {
+            ps.o_ops = lay.place(sizeof(AirOpDev) * ps.ops.size());
+            ps.o_col = lay.place(sizeof(uint32_t) * std::max<size_t>(1, ps.col_of.size()));
+        }
+    }
     for (Chunk& ch : chunks) {
         ch.o_ops = lay.place(sizeof(AirOpDev) * ch.ops.size());
         ch.o_kinds = lay.place(sizeof(uint32_t) * ch.kc);
@@ -485,6 +533,13 @@ int StarkProver::commit_aux_program(const AirStatement& st, const std::vector<fe
     std::vector<uint8_t>& up = h_auxp_up_;
     up.assign(bytes, 0);
     fill_consts_then_rap(up.data() + o_consts, aux.consts, rap);
+    for (const SortGroup& g : groups) {
+        if (!g.key_cols.empty()) std::memcpy(up.data() + g.o_keycol, g.key_cols.data(), sizeof(uint32_t) * g.key_cols.size());
+        for (const SortPass& ps : g.passes) {
+            std::memcpy(up.data() + ps.o_ops, ps.ops.data(), sizeof(AirOpDev) * ps.ops.size());
+            if (!ps.col_of.empty()) std::memcpy(up.data() + ps.o_col, ps.col_of.data(), sizeof(uint32_t) * ps.col_of.size());
+        }
+    }
     for (const Chunk& ch : chunks) {
         std::memcpy(up.data() + ch.o_ops, ch.ops.data(), sizeof(AirOpDev) * ch.ops.size());
         std::memcpy(up.data() + ch.o_kinds, ch.kinds.data(), sizeof(uint32_t) * ch.kc);
@@ -495,30 +550,63 @@ int StarkProver::commit_aux_program(const AirStatement& st, const std::vector<fe
         for (uint32_t k = 0; k < Kp; ++k) std::memcpy(up.data() + o_pvals + sizeof(fe) * pcols[k].off, periodic->cols[k].data(), sizeof(fe) * periodic->cols[k].size());
     }
     SP_HIP_CHECK(hipMemcpyAsync(od_.auxp_buf.p, up.data(), bytes, hipMemcpyHostToDevice, c_->stream));
-    // --- workspace: [max_den][n] denominators, as much batch-inversion scratch, [chunk][nb] scan block totals
-    const uint64_t ws = 2 * (uint64_t)max_den * n_ + (uint64_t)chunk * nb;
+    // --- workspace, whichever of the two uses is larger (the sorts are over before the first chunk starts):
+    //     chunks: [max_den][n] denominators, as much batch-inversion scratch, [chunk][nb] scan block totals
+    //     sorts:  [max_carried][n] carried values, 2 x [n] keys, 2 x [n] rows, the radix sort's histograms (all in units of 32 bytes)
+    const uint64_t keys_el = (n_ + 3) / 4, idx_el = (n_ + 7) / 8;
+    const uint64_t ws_sort = groups.empty() ? 0 : (uint64_t)max_carried * n_ + 2 * keys_el + 2 * idx_el + (radix_sort_workspace_bytes(n_) + sizeof(fe) - 1) / sizeof(fe);
+    const uint64_t ws = std::max(2 * (uint64_t)max_den * n_ + (uint64_t)chunk * nb, ws_sort);
     SP_TRY(grow(od_.auxp_ws, ws));
+    const fe* consts_dev = reinterpret_cast<const fe*>(od_.auxp_buf.p + o_consts);
+    const AirPeriodicCol* pcols_dev = any_periodic ? reinterpret_cast<const AirPeriodicCol*>(od_.auxp_buf.p + o_pcols) : nullptr;
+    const fe* pvals_dev = any_periodic ? reinterpret_cast<const fe*>(od_.auxp_buf.p + o_pvals) : nullptr;
+    fe* aux_cols = d_trace_ + (uint64_t)Cm_ * n_;
+    SP_TRY(ensure_host_flags());
+    host_flags().auxp_bad_key = 0;
+    SP_HIP_CHECK(hipMemsetAsync(c_->d_flag, 0, sizeof(int), c_->stream));
+    if (!groups.empty()) {
+        fe* vals = od_.auxp_ws.p;
+        uint64_t* keys_a = reinterpret_cast<uint64_t*>(vals + (uint64_t)max_carried * n_);
+        uint64_t* keys_b = reinterpret_cast<uint64_t*>(vals + (uint64_t)max_carried * n_ + keys_el);
+        uint32_t* idx_a = reinterpret_cast<uint32_t*>(vals + (uint64_t)max_carried * n_ + 2 * keys_el);
+        uint32_t* idx_b = reinterpret_cast<uint32_t*>(vals + (uint64_t)max_carried * n_ + 2 * keys_el + idx_el);
+        void* radix_ws = vals + (uint64_t)max_carried * n_ + 2 * keys_el + 2 * idx_el;
+        for (const SortGroup& g : groups)
+            for (size_t p = 0; p < g.passes.size(); ++p) {
+                const SortPass& ps = g.passes[p];
+                SP_TRY(air_aux_sort_terms(c_->stream, d_trace_, n_, reinterpret_cast<const AirOpDev*>(od_.auxp_buf.p + ps.o_ops), (uint32_t)ps.ops.size(), consts_dev, vals,
+                                          p == 0 ? keys_a : nullptr, p == 0 ? idx_a : nullptr, g.key_bits, c_->d_flag, ps.periodic ? pcols_dev : nullptr,
+                                          ps.periodic ? pvals_dev : nullptr));
+                if (p == 0) {   // ceil(key_bits / 8) passes; the sorted pairs end up in keys_b / idx_b
+                    SP_TRY(radix_sort_pairs_u64(c_->stream, keys_a, keys_b, idx_a, idx_b, n_, g.key_bits, radix_ws));
+                    SP_TRY(air_aux_key_columns(c_->stream, keys_b, n_, aux_cols, reinterpret_cast<const uint32_t*>(od_.auxp_buf.p + g.o_keycol), (uint32_t)g.key_cols.size()));
+                }
+                SP_TRY(air_aux_gather(c_->stream, vals, idx_b, n_, aux_cols, reinterpret_cast<const uint32_t*>(od_.auxp_buf.p + ps.o_col), (uint32_t)ps.col_of.size()));
+            }
+        // the key-range flag rides to the host from here: a zero denominator behind it overwrites the word on the device
+        SP_HIP_CHECK(hipMemcpyAsync(&host_flags().auxp_bad_key, c_->d_flag, sizeof(int), hipMemcpyDeviceToHost, c_->stream));
+    }
     fe* den = od_.auxp_ws.p;
     fe* scratch = den + (uint64_t)max_den * n_;
     fe* block_tot = scratch + (uint64_t)max_den * n_;
-    const fe* consts_dev = reinterpret_cast<const fe*>(od_.auxp_buf.p + o_consts);
-    SP_HIP_CHECK(hipMemsetAsync(c_->d_flag, 0, sizeof(int), c_->stream));
     for (const Chunk& ch : chunks) {
-        fe* cols = d_trace_ + (uint64_t)(Cm_ + ch.k0) * n_;
+        fe* cols = aux_cols + (uint64_t)ch.k0 * n_;
         const uint32_t* kinds = reinterpret_cast<const uint32_t*>(od_.auxp_buf.p + ch.o_kinds);
         SP_TRY(air_aux_terms(c_->stream, d_trace_, n_, reinterpret_cast<const AirOpDev*>(od_.auxp_buf.p + ch.o_ops), (uint32_t)ch.ops.size(), consts_dev, cols, den,
-                             ch.periodic ? reinterpret_cast<const AirPeriodicCol*>(od_.auxp_buf.p + o_pcols) : nullptr,
-                             ch.periodic ? reinterpret_cast<const fe*>(od_.auxp_buf.p + o_pvals) : nullptr));
+                             ch.periodic ? pcols_dev : nullptr, ch.periodic ? pvals_dev : nullptr));
         if (ch.n_den) {
             SP_TRY(batch_inverse(c_->stream, den, scratch, (uint64_t)ch.n_den * n_, c_->d_flag));
             SP_TRY(air_aux_apply_den(c_->stream, cols, den, reinterpret_cast<const uint32_t*>(od_.auxp_buf.p + ch.o_col), ch.n_den, n_));
         }
         SP_TRY(air_aux_scan(c_->stream, cols, n_, ch.kc, kinds, block_tot));
     }
-    // the zero-denominator flag rides behind the columns; the read-back of the root below waits for it
-    SP_TRY(ensure_host_flags());
+    // the zero-denominator flag rides behind the columns; the read-back of the root below waits for it (and for the key-range flag)
     SP_HIP_CHECK(hipMemcpyAsync(&host_flags().auxp_zero_den, c_->d_flag, sizeof(int), hipMemcpyDeviceToHost, c_->stream));
     SP_TRY(commit_segment_resident(1, K, root_out));
+    if (host_flags().auxp_bad_key == AIR_AUX_FLAG_KEY_RANGE) {
+        sp_set_error("commit_aux_program: a sort key is out of range on some row (the key of a sorted column must be below 2^key_bits as a canonical integer)");
+        return SP_E_INVALID_ARG;
+    }
     if (host_flags().auxp_zero_den) { sp_set_error("commit_aux_program: an auxiliary column's denominator is zero on some row"); return SP_E_ZERO_INVERSE; }
     return SP_OK;
 }

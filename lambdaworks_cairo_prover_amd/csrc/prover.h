@@ -77,7 +77,7 @@ struct ScopedDevAlloc {
 };
 // The pinned flag slot (64 bytes): flags that ride to the host behind the work they belong to.  presort_malformed and presort_wide_key
 // stay adjacent and in the order of SIDE_PRESORT_MALFORMED, SIDE_PRESORT_WIDE_KEY: launch_aux_presort fills both with one copy.
-struct HostFlags { int presort_malformed, presort_wide_key, _pad[2], trace_build_oob, auxp_zero_den; };
+struct HostFlags { int presort_malformed, presort_wide_key, _pad[2], trace_build_oob, auxp_zero_den, auxp_bad_key; };
 // flags of the side-stream work (device): DEEP inverses, boundary inverses, the presort's malformed input / key beyond its bits
 enum SideFlag { SIDE_DEEP_INV = 0, SIDE_BND_INV, SIDE_PRESORT_MALFORMED, SIDE_PRESORT_WIDE_KEY, SIDE_FLAGS };
 
@@ -100,8 +100,9 @@ class StarkProver : public sp_deletable {
     // round 1, Cairo auxiliary segment built on the device from the resident main trace (reference cairo/air.rs:660-729)
     int commit_aux_cairo(const PublicInputs& pub, const fe rap[3], uint8_t root_out[32]);
     // round 1, auxiliary segment of a program AIR built on the device from the statement's auxiliary program (st.aux, present and
-    // validated: air_statement_from_c) and the RAP challenges: per-row N and D, one batch inversion, an exclusive product / sum scan
-    // per column, commit_segment_resident.  The columns the program may read with op 6 (a = row shift, b = column:
+    // validated: air_statement_from_c) and the RAP challenges: the sorted columns first (key pass, radix sort, gather; a key beyond its
+    // bits is SP_E_INVALID_ARG), then per-row N and D, one batch inversion, an exclusive product / sum scan per column,
+    // commit_segment_resident.  The columns the program may read with op 6 (a = row shift, b = column:
     // values[(i + a) mod period]) are st.aux_periodic().
     int commit_aux_program(const AirStatement& st, const std::vector<fe>& rap, uint8_t root_out[32]);
     // round 2: constraint composition, H1/H2 split, LDE and commitment
@@ -305,7 +306,8 @@ class StarkProver : public sp_deletable {
         DevBuf<CompositionConsts> comp_consts_chk;   // the constants of an early constraint check (composition_precheck)
         DevBuf<uint8_t> air_buf; DevBuf<fe> ex_roots;   // program AIRs (composition_air): header, ops, constants and per-proof tables in one buffer; exempted rows' roots
         // auxiliary programs (commit_aux_program): ops, constants and column tables of every chunk in one buffer, and the N / D
-        // workspace (denominators, batch-inversion scratch, scan block totals); kept across proofs of a shape
+        // workspace (denominators, batch-inversion scratch, scan block totals - or, before those, one sort group's carried values,
+        // (key, row) pairs and radix histograms); kept across proofs of a shape
         DevBuf<uint8_t> auxp_buf; DevBuf<fe> auxp_ws;
         DevBuf<uint64_t> air_report;             // check_trace_air: per-constraint counters, values and boundary results, one block (AirReport)
         DevBuf<fe> stride;                       // strided constraints of a program AIR: [E] U, [E] 1 / Z, [E] scratch (E = b x the classes' periods, summed)

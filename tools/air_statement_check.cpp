@@ -23,6 +23,11 @@ struct Parts {
     sp_air_op aux_ops[4] = {{1, 0, 0, 0, 0}, {0, 0, 0, 0, 0}, {3, 0, 0, 1, 0}, {6, 0, 7, 0, 0}};   // gamma, x, gamma - x, table read at shift 7
     sp_air_aux_column aux_cols[1] = {{SP_AIR_AUX_PRODUCT, 2, 2, 0}};
     sp_air_aux_desc aux{};
+    // sorted(): x sorted by itself (16 key bits) with gamma - x carried, and a product that reads the sorted x one row ahead
+    sp_air_op sort_ops[6] = {{1, 0, 0, 0, 0}, {0, 0, 0, 0, 0}, {3, 0, 0, 1, 0}, {0, 0, 1, 1, 0}, {3, 0, 0, 3, 0}, {6, 0, 7, 0, 0}};
+    sp_air_aux_column sort_cols[3] = {{SP_AIR_AUX_SORTED, 1, 1, 16}, {SP_AIR_AUX_SORTED, 2, 1, 16}, {SP_AIR_AUX_PRODUCT, 2, 4, 0}};
+    sp_air_op many_ops[17] = {};                 // 17 LOADs of x, each the key of a group of its own
+    sp_air_aux_column many_cols[17];
     Felt keys[8];
     sp_air_periodic_column pcols[65];
     sp_air_periodic_desc per{};
@@ -33,6 +38,7 @@ struct Parts {
     sp_air_boundary_value bvalues[2] = {{1, 2, 2, 0}, {0, 2, SP_AIR_AUX_NO_DEN, 0}};
     sp_air_boundary_desc bv{};
     Parts() {
+        for (uint32_t j = 0; j < 17; ++j) many_cols[j] = sp_air_aux_column{SP_AIR_AUX_SORTED, j, j, 16};
         for (int j = 0; j < 8; ++j) keys[j] = felt(100 + j);
         for (auto& c : pcols) c = sp_air_periodic_column{8, 0, keys[0].b};
         boundary[0].col = 0; boundary[1].col = 1;
@@ -44,6 +50,8 @@ struct Parts {
         sd.n = 1; sd.strides = strides;
         bv.n_ops = 3; bv.ops = bops; bv.n_consts = 1; bv.consts = bconsts[0].b; bv.n_values = 2; bv.values = bvalues;
     }
+    void sorted() { d.aux_cols = 3; aux.n_ops = 5; aux.ops = sort_ops; aux.n_cols = 3; aux.cols = sort_cols; }
+    void many(uint32_t groups) { d.aux_cols = groups; aux.n_ops = 17; aux.ops = many_ops; aux.n_cols = groups; aux.cols = many_cols; }
 };
 
 // use: which parts go to the decoder (a x p s b, upper case P: the auxiliary program may read the periodic columns)
@@ -90,6 +98,24 @@ int main() {
     run("boundary values", "xb", true, none);
     run("auxiliary program reading a table (_pub)", "xpP", true, [](Parts& p) { p.aux.n_ops = 4; });
     run("everything", "xpsbP", true, [](Parts& p) { p.aux.n_ops = 4; });
+    run("sorted columns and a product that reads one", "x", true, [](Parts& p) { p.sorted(); });
+    run("sorted: pad 0 is 64 bits", "x", true, [](Parts& p) { p.sorted(); p.sort_cols[0].pad = p.sort_cols[1].pad = 0; });
+    run("sorted: 64 key bits", "x", true, [](Parts& p) { p.sorted(); p.sort_cols[0].pad = 64; p.sort_cols[1].pad = 0; });
+    run("sorted: a carried value reads a table (_pub)", "xpP", true, [](Parts& p) { p.sorted(); p.aux.n_ops = 6; p.sort_cols[1].num_op = 5; });
+    run("sorted: 16 groups", "x", true, [](Parts& p) { p.many(16); });
+    run("pad is ignored for products and sums", "x", true, [](Parts& p) { p.aux_cols[0].pad = 65; });
+    // ---- malformed sorted columns
+    run("sorted: kind 3", "x", false, [](Parts& p) { p.sorted(); p.sort_cols[1].kind = 3; });
+    run("sorted: no key op", "x", false, [](Parts& p) { p.sorted(); p.sort_cols[1].den_op = SP_AIR_AUX_NO_DEN; });
+    run("sorted: key op beyond the program", "x", false, [](Parts& p) { p.sorted(); p.sort_cols[1].den_op = 5; });
+    run("sorted: pad 65", "x", false, [](Parts& p) { p.sorted(); p.sort_cols[0].pad = p.sort_cols[1].pad = 65; });
+    run("sorted: a group that disagrees on the key bits", "x", false, [](Parts& p) { p.sorted(); p.sort_cols[1].pad = 8; });
+    run("sorted: LOAD of a product column", "x", false, [](Parts& p) { p.sorted(); p.sort_ops[3].b = 3; });
+    run("sorted: LOAD beyond main + aux", "x", false, [](Parts& p) { p.sorted(); p.sort_ops[3].b = 4; });
+    run("sorted: a key that reads a sorted column", "x", false, [](Parts& p) { p.sorted(); p.sort_cols[1].den_op = 4; });
+    run("sorted: a value that reads a sorted column", "x", false, [](Parts& p) { p.sorted(); p.sort_cols[1].num_op = 4; });
+    run("sorted: 17 groups", "x", false, [](Parts& p) { p.many(17); });
+    run("LOAD of an auxiliary column without sorted columns", "x", false, [](Parts& p) { p.sorted(); p.sort_cols[0].kind = p.sort_cols[1].kind = SP_AIR_AUX_SUM; });
     // ---- malformed: the table of tests/test_air_statement.py
     run("n_offsets = 9", "xp", false, [](Parts& p) { p.d.n_offsets = 9; });
     run("a count without its array", "", false, [](Parts& p) { p.d.ops = nullptr; });
