@@ -2,15 +2,13 @@
 fibonacci_rap example, the callback-built test AIRs, a permutation argument and a LogUp lookup - on one GPU and on sharded
 contexts; the same bytes as the host callback path at 2^16 rows; and the errors."""
 import ctypes
-import os
-import socket
 
 import pytest
-import torch.multiprocessing as mp
 
 import aux_program_airs as X
 import oracle_lib as O
 from lambdaworks_cairo_prover_amd import _lib, air, api
+from rank_procs import run_ranks
 
 pytestmark = pytest.mark.gpu
 
@@ -90,37 +88,14 @@ def test_device_program_equals_the_device_callback_at_2_16_rows(hip_ctx):
     assert api.air_verify(got, desc, options)
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
-
-
-def _aux_worker(rank, world, port, n, options, q):
-    import sys
-    import torch.distributed as dist
-    here = os.path.dirname(os.path.abspath(__file__))
-    sys.path.insert(0, os.path.dirname(here))
-    sys.path.insert(0, here)
-    import aux_program_airs as X
-    from lambdaworks_cairo_prover_amd import api
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        ctx = api.Context(device=0)
-        ctx.set_collective(world, rank, api.StagedAllGather())
-        ctx.set_option(api.SP_OPT_FRI_SHARD_MIN_LOG, 5)
-        desc, keep = X.rap_air(n, perm_shifts=(0, 3), logup_shifts=(1, 6)).build()
-        proof = ctx.air_prove(desc, X.main_trace(n), api.ProofOptions(*options))
-        q.put((rank, proof))
-        ctx.close()
-    except Exception:
-        import traceback
-        q.put((rank, ("fail: " + traceback.format_exc()).encode()))
-    finally:
-        dist.destroy_process_group()
+def _aux_body(rank, world, n, options):
+    ctx = api.Context(device=0)
+    ctx.set_collective(world, rank, api.StagedAllGather())
+    ctx.set_option(api.SP_OPT_FRI_SHARD_MIN_LOG, 5)
+    desc, keep = X.rap_air(n, perm_shifts=(0, 3), logup_shifts=(1, 6)).build()
+    proof = ctx.air_prove(desc, X.main_trace(n), api.ProofOptions(*options))
+    ctx.close()
+    return proof
 
 
 @pytest.mark.parametrize("world,n,options", [(2, 64, (4, 3, 3, 1)), (4, 256, (4, 4, 3, 2))])
@@ -128,15 +103,7 @@ def test_sharded_contexts_give_the_one_gpu_bytes(hip_ctx, world, n, options):
     """Every rank holds the whole main trace and builds the same columns: no exchange, the one-GPU bytes on every rank."""
     desc, keep = X.rap_air(n, perm_shifts=(0, 3), logup_shifts=(1, 6)).build()
     want = hip_ctx.air_prove(desc, X.main_trace(n), api.ProofOptions(*options))
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_aux_worker, args=(r, world, port, n, options, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    got = dict(q.get(timeout=600) for _ in procs)
-    for p in procs:
-        p.join(timeout=60)
+    got = run_ranks(world, _aux_body, (n, options), timeout=600)
     for r in range(world):
         assert got[r] == want, (r, got[r][:400])
 

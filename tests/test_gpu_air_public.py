@@ -3,16 +3,14 @@ periodic column against the same AIR with the column built by the Python model o
 for a table of equal values, against the CPU oracle; boundary values computed from the challenges against the AIR frozen under the
 recorded challenges (the existing sp_air_prove_aux, and the oracle); the trace report against the model; the refusals; a sharded context."""
 import ctypes
-import os
-import socket
 
 import pytest
-import torch.multiprocessing as mp
 
 import oracle_lib as O
 import public_airs as X
 import strided_airs
 from lambdaworks_cairo_prover_amd import _lib, air, api
+from rank_procs import run_child, run_ranks
 
 pytestmark = pytest.mark.gpu
 
@@ -190,83 +188,40 @@ def test_old_entry_points_refuse_and_pub_without_public_data_is_ext(hip_lib, hip
 
 
 # ---- 5. a sharded context ----------------------------------------------------------------------------------------------------------------
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
-
-
 def _cases(n):
     return [X.table_lookup(n, 8, seed=71), X.public_permutation(n, 5, seed=72)]
 
 
-def _worker(rank, world, port, n, q):
-    import sys
-    import torch.distributed as dist
-    here = os.path.dirname(os.path.abspath(__file__))
-    sys.path.insert(0, os.path.dirname(here))
-    sys.path.insert(0, here)
-    from lambdaworks_cairo_prover_amd import api
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        ctx = api.Context(device=0)
-        ctx.set_collective(world, rank, api.StagedAllGather())
-        ctx.set_option(api.SP_OPT_FRI_SHARD_MIN_LOG, 5)
-        proofs = []
+def _body(rank, world, n):
+    ctx = api.Context(device=0)
+    ctx.set_collective(world, rank, api.StagedAllGather())
+    ctx.set_option(api.SP_OPT_FRI_SHARD_MIN_LOG, 5)
+    proofs = []
+    for b, rows in _cases(n):
+        desc, keep = b.build()
+        proofs.append(ctx.air_prove(desc, X.to_bytes(rows), api.ProofOptions(*X.OPTIONS)))
+    ctx.close()
+    return proofs
+
+
+def _single_body(n):
+    proofs = []
+    with api.Context(device=0) as ctx:
         for b, rows in _cases(n):
             desc, keep = b.build()
             proofs.append(ctx.air_prove(desc, X.to_bytes(rows), api.ProofOptions(*X.OPTIONS)))
-        q.put((rank, proofs))
-        ctx.close()
-    except Exception:
-        import traceback
-        q.put((rank, ("fail: " + traceback.format_exc()).encode()))
-    finally:
-        dist.destroy_process_group()
-
-
-def _single_worker(n, q):
-    import sys
-    here = os.path.dirname(os.path.abspath(__file__))
-    sys.path.insert(0, os.path.dirname(here))
-    sys.path.insert(0, here)
-    from lambdaworks_cairo_prover_amd import api
-    try:
-        proofs = []
-        with api.Context(device=0) as ctx:
-            for b, rows in _cases(n):
-                desc, keep = b.build()
-                proofs.append(ctx.air_prove(desc, X.to_bytes(rows), api.ProofOptions(*X.OPTIONS)))
-                assert ctx.last_proof_info()["composition_path"] == 1
-        q.put(proofs)
-    except Exception:
-        import traceback
-        q.put(("fail: " + traceback.format_exc()).encode())
+            assert ctx.last_proof_info()["composition_path"] == 1
+    return proofs
 
 
 def test_sharded_context_gives_the_one_gpu_bytes():
     """Every rank builds the whole auxiliary column from its whole copy of the main trace and resolves the boundary values itself: both
     ranks return the one-GPU bytes of both worked examples.  The one-GPU child has ended before the ranks start."""
     world, n = 2, 64
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    one = ctx.Process(target=_single_worker, args=(n, q))
-    one.start()
-    want = q.get(timeout=600)
-    one.join(timeout=60)
-    assert isinstance(want, list), want[:2000]
+    want = run_child(_single_body, (n,), timeout=600)
     for (b, rows), proof in zip(_cases(n), want):
         desc, keep = b.build()
         assert api.air_verify(proof, desc, OPT)
-    port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, n, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    got = dict(q.get(timeout=600) for _ in procs)
-    for p in procs:
-        p.join(timeout=60)
+    got = run_ranks(world, _body, (n,), timeout=600)
     for r in range(world):
-        assert got[r] == want, (r, got[r][:400] if isinstance(got[r], bytes) else "proof bytes differ")
+        assert got[r] == want, (r, "proof bytes differ")

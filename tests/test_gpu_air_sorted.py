@@ -2,15 +2,13 @@
 for the two worked examples and a mixed AIR; past one sort tile and one scan segment against the host callback path; a violating trace;
 the trace report against the model; the key-range error and the decoder's refusals, with recovery; a sharded context."""
 import ctypes
-import os
-import socket
 
 import pytest
-import torch.multiprocessing as mp
 
 import oracle_lib as O
 import sorted_airs as X
 from lambdaworks_cairo_prover_amd import _lib, air, api
+from rank_procs import run_ranks
 
 pytestmark = pytest.mark.gpu
 
@@ -148,40 +146,17 @@ def test_hand_edited_descriptors_are_refused(hip_ctx, oracle):
     assert hip_ctx.air_prove(good, trace, options) == want
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
-
-
-def _worker(rank, world, port, n, options, q):
-    import sys
-    import torch.distributed as dist
-    here = os.path.dirname(os.path.abspath(__file__))
-    sys.path.insert(0, os.path.dirname(here))
-    sys.path.insert(0, here)
-    import sorted_airs as X
-    from lambdaworks_cairo_prover_amd import api
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        ctx = api.Context(device=0)
-        ctx.set_collective(world, rank, api.StagedAllGather())
-        ctx.set_option(api.SP_OPT_FRI_SHARD_MIN_LOG, 5)
-        proofs = []
-        for make in (X.range_check, X.memory, X.mixed):
-            b, rows = make(n)
-            desc, keep = b.build()
-            proofs.append(ctx.air_prove(desc, X.to_bytes(rows), api.ProofOptions(*options)))
-        q.put((rank, proofs))
-        ctx.close()
-    except Exception:
-        import traceback
-        q.put((rank, ("fail: " + traceback.format_exc()).encode()))
-    finally:
-        dist.destroy_process_group()
+def _body(rank, world, n, options):
+    ctx = api.Context(device=0)
+    ctx.set_collective(world, rank, api.StagedAllGather())
+    ctx.set_option(api.SP_OPT_FRI_SHARD_MIN_LOG, 5)
+    proofs = []
+    for make in (X.range_check, X.memory, X.mixed):
+        b, rows = make(n)
+        desc, keep = b.build()
+        proofs.append(ctx.air_prove(desc, X.to_bytes(rows), api.ProofOptions(*options)))
+    ctx.close()
+    return proofs
 
 
 def test_sharded_contexts_give_the_one_gpu_bytes(hip_ctx):
@@ -192,14 +167,6 @@ def test_sharded_contexts_give_the_one_gpu_bytes(hip_ctx):
         b, rows = make(n)
         desc, keep = b.build()
         want.append(hip_ctx.air_prove(desc, X.to_bytes(rows), api.ProofOptions(*options)))
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, n, options, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    got = dict(q.get(timeout=600) for _ in procs)
-    for p in procs:
-        p.join(timeout=60)
+    got = run_ranks(world, _body, (n, options), timeout=600)
     for r in range(world):
-        assert got[r] == want, (r, got[r][:400] if isinstance(got[r], bytes) else "proof bytes differ")
+        assert got[r] == want, (r, "proof bytes differ")

@@ -3,8 +3,6 @@ strides, so the checks are: the oracle's bytes where every stride is (1, 0), the
 the 2n-point path and soundness through the library's verifier - whose zerofier and exemption product the CPU tests pin
 (tests/test_air_stride.py) -, and the trace report against the Python-integer model."""
 import ctypes
-import os
-import socket
 
 import numpy as np
 import pytest
@@ -14,6 +12,7 @@ import oracle_lib as O
 import periodic_airs as XP
 import strided_airs as X
 from lambdaworks_cairo_prover_amd import _lib, air, api
+from rank_procs import run_child, run_ranks
 
 pytestmark = pytest.mark.gpu
 
@@ -241,85 +240,38 @@ def test_prover_refuses_malformed_stride_descriptors(hip_ctx):
 
 
 # ---- 9. sharded contexts -------------------------------------------------------------------------------------------------------------------
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
-
-
-def _paths():
-    import sys
-    here = os.path.dirname(os.path.abspath(__file__))
-    sys.path.insert(0, os.path.dirname(here))
-    sys.path.insert(0, here)
-
-
-def _worker(rank, world, port, n, options, q):
-    import torch.distributed as dist
-    _paths()
-    import strided_airs as X
-    from lambdaworks_cairo_prover_amd import _lib, api
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+def _body(rank, world, n, options):
+    ctx = api.Context(device=0)
+    ctx.set_collective(world, rank, api.StagedAllGather())
+    ctx.set_option(api.SP_OPT_FRI_SHARD_MIN_LOG, 5)
+    c = X.two_class(n)
+    desc, keep = c.builder.build()
+    proof = ctx.air_prove(desc, X.to_bytes(c.rows), api.ProofOptions(*options))
     try:
-        ctx = api.Context(device=0)
-        ctx.set_collective(world, rank, api.StagedAllGather())
-        ctx.set_option(api.SP_OPT_FRI_SHARD_MIN_LOG, 5)
+        ctx.air_check_trace(desc, X.to_bytes(c.rows), api.ProofOptions(*options))
+        report = 0
+    except api.SpError as e:
+        report = e.code
+    ctx.close()
+    return proof, report
+
+
+def _single_body(n, options):
+    with api.Context(device=0) as ctx:
         c = X.two_class(n)
         desc, keep = c.builder.build()
         proof = ctx.air_prove(desc, X.to_bytes(c.rows), api.ProofOptions(*options))
-        try:
-            ctx.air_check_trace(desc, X.to_bytes(c.rows), api.ProofOptions(*options))
-            report = 0
-        except api.SpError as e:
-            report = e.code
-        q.put((rank, (proof, report)))
-        ctx.close()
-    except Exception:
-        import traceback
-        q.put((rank, ("fail: " + traceback.format_exc()).encode()))
-    finally:
-        dist.destroy_process_group()
-
-
-def _single_worker(n, options, q):
-    _paths()
-    import strided_airs as X
-    from lambdaworks_cairo_prover_amd import api
-    try:
-        with api.Context(device=0) as ctx:
-            c = X.two_class(n)
-            desc, keep = c.builder.build()
-            proof = ctx.air_prove(desc, X.to_bytes(c.rows), api.ProofOptions(*options))
-            assert ctx.last_proof_info()["composition_path"] == 1
-        q.put([proof])
-    except Exception:
-        import traceback
-        q.put(("fail: " + traceback.format_exc()).encode())
+        assert ctx.last_proof_info()["composition_path"] == 1
+    return proof
 
 
 def test_sharded_contexts_give_the_one_gpu_bytes():
     """World 2 over the gloo-staged all-gather, ranks sharing the GPU: every rank builds all b cosets of the classes' tables and indexes
     them by the global LDE index.  The one-GPU proof comes from a child that has ended before the ranks start."""
-    import torch.multiprocessing as mp
     world, n, options = 2, 64, (4, 3, 3, 1)
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    one = ctx.Process(target=_single_worker, args=(n, options, q))
-    one.start()
-    want = q.get(timeout=600)
-    one.join(timeout=60)
-    assert isinstance(want, list), want[:2000]
+    want = run_child(_single_body, (n, options), timeout=600)
     desc, keep = X.two_class(n).builder.build()
-    assert api.air_verify(want[0], desc, api.ProofOptions(*options))
-    port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, n, options, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    got = dict(q.get(timeout=600) for _ in procs)
-    for p in procs:
-        p.join(timeout=60)
+    assert api.air_verify(want, desc, api.ProofOptions(*options))
+    got = run_ranks(world, _body, (n, options), timeout=600)
     for r in range(world):
-        assert got[r] == (want[0], _lib.SP_E_UNSUPPORTED), (r, got[r][:400] if isinstance(got[r], bytes) else "proof bytes or report code differ")
+        assert got[r] == (want, _lib.SP_E_UNSUPPORTED), (r, "proof bytes or report code differ")

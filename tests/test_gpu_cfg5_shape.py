@@ -5,11 +5,10 @@ holds is measured and extrapolated to n = 2^24 (it is linear in n) against the 2
 
 About 40 s (every collective is staged through host memory and gloo here); needs ~200 GB of free device memory."""
 import hashlib
-import os
-import socket
 
 import pytest
-import torch.multiprocessing as mp
+
+from rank_procs import run_ranks
 
 pytestmark = pytest.mark.gpu
 
@@ -19,35 +18,16 @@ WORLD = 8
 HBM_BYTES = 288e9
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
-def _worker(rank, world, port, backend, q):
-    import sys
-    import torch.distributed as dist
-    here = os.path.dirname(os.path.abspath(__file__))
-    sys.path.insert(0, os.path.dirname(here))
+def _body(rank, world, backend):
     from lambdaworks_cairo_prover_amd import api
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        run = api.CairoRun.fibonacci(FIB_INDEX)
-        ctx = api.Context(device=0)
-        ctx.set_collective(world, rank, api.StagedAllGather())
-        ctx.set_option(api.SP_OPT_MERKLE_BACKEND, backend)
-        proof = ctx.cairo_prove(run.main_trace(), run.public_inputs_c, api.ProofOptions(*OPTIONS))
-        q.put((rank, hashlib.sha256(proof).hexdigest(), ctx.prover_device_bytes(), ctx.last_proof_info(), ctx.comm_stats()))
-        ctx.close()
-    except Exception:
-        import traceback
-        q.put((rank, "fail: " + traceback.format_exc(), 0, None, None))
-    finally:
-        dist.destroy_process_group()
+    run = api.CairoRun.fibonacci(FIB_INDEX)
+    ctx = api.Context(device=0)
+    ctx.set_collective(world, rank, api.StagedAllGather())
+    ctx.set_option(api.SP_OPT_MERKLE_BACKEND, backend)
+    proof = ctx.cairo_prove(run.main_trace(), run.public_inputs_c, api.ProofOptions(*OPTIONS))
+    result = hashlib.sha256(proof).hexdigest(), ctx.prover_device_bytes(), ctx.last_proof_info(), ctx.comm_stats()
+    ctx.close()
+    return result
 
 
 @pytest.mark.parametrize("backend", [0, 1], ids=["keccak256", "poseidon"])
@@ -71,17 +51,10 @@ def test_cfg5_shape_eight_ranks_two_cosets_each(hip_lib, backend):
     assert api.cairo_verify(single, run.public_inputs_c, api.ProofOptions(*OPTIONS), backend)
     assert not api.cairo_verify(single, run.public_inputs_c, api.ProofOptions(*OPTIONS), 1 - backend)
     want = hashlib.sha256(single).hexdigest()
-    mpc = mp.get_context("spawn")
-    q = mpc.Queue()
-    port = _free_port()
-    procs = [mpc.Process(target=_worker, args=(r, WORLD, port, backend, q)) for r in range(WORLD)]
-    for p in procs:
-        p.start()
-    got = [q.get(timeout=3000) for _ in procs]
-    for p in procs:
-        p.join(timeout=120)
+    got = run_ranks(WORLD, _body, (backend,), timeout=3000)
     per_rank = []
-    for rank, digest, dev_bytes, info, stats in sorted(got):
+    for rank in range(WORLD):
+        digest, dev_bytes, info, stats = got[rank]
         assert digest == want, (rank, digest[:400])
         # (interpolation: the link model's choice - on every rank at 46 GB/s per link; by column is pinned in test_gpu_multirank*.py)
         assert info["groups"] == WORLD and info["interpolation_sharded"] == 0 and info["composition_path"] == 1

@@ -1,15 +1,12 @@
 """sp_air_prove beyond 64 columns and 3 boundary rows on the device (many_column_air.py): the oracle's proof bytes, and both
 verifiers accept - up to 1024 columns, 300 boundary constraints on 64 rows, violating traces, several shapes on one context,
 2^16 rows x 256 columns, and two ranks."""
-import os
-import socket
-
 import pytest
-import torch.multiprocessing as mp
 
 import many_column_air as M
 import oracle_lib as O
 from lambdaworks_cairo_prover_amd import air, api
+from rank_procs import run_ranks
 
 pytestmark = pytest.mark.gpu
 
@@ -85,49 +82,21 @@ def test_2p16_rows_256_columns(hip_ctx):
         assert fresh.air_prove(desc, trace, api.ProofOptions(*options)) == got
 
 
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
-def _air_worker(rank, world, port, q):
-    import sys
-    import torch.distributed as dist
-    here = os.path.dirname(os.path.abspath(__file__))
-    sys.path.insert(0, os.path.dirname(here))
-    sys.path.insert(0, here)
-    import many_column_air as MM
-    from lambdaworks_cairo_prover_amd import api as A
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        n, m, a, r, rows, total, options = SHAPES["200_plus_8_aux"]
-        desc, keep = MM.build(n, m, aux_cols=a, frame_rows=r, boundary_row_count=rows, boundary_total=total).build()
-        ctx = A.Context(device=0)
-        ctx.set_collective(world, rank, A.StagedAllGather())
-        ctx.set_option(A.SP_OPT_FRI_SHARD_MIN_LOG, 5)
-        q.put((rank, ctx.air_prove(desc, MM.main_trace(n, m), A.ProofOptions(*options))))
-        ctx.close()
-    except Exception:
-        import traceback
-        q.put((rank, ("fail: " + traceback.format_exc()).encode()))
-    finally:
-        dist.destroy_process_group()
+def _air_body(rank, world):
+    n, m, a, r, rows, total, options = SHAPES["200_plus_8_aux"]
+    desc, keep = M.build(n, m, aux_cols=a, frame_rows=r, boundary_row_count=rows, boundary_total=total).build()
+    ctx = api.Context(device=0)
+    ctx.set_collective(world, rank, api.StagedAllGather())
+    ctx.set_option(api.SP_OPT_FRI_SHARD_MIN_LOG, 5)
+    proof = ctx.air_prove(desc, M.main_trace(n, m), api.ProofOptions(*options))
+    ctx.close()
+    return proof
 
 
 def test_sharded_200_columns_world_2(hip_ctx):
     n, m, b, options = _shape("200_plus_8_aux")
     desc, keep = b.build()
     want = hip_ctx.air_prove(desc, M.main_trace(n, m), api.ProofOptions(*options))
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_air_worker, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    got = dict(q.get(timeout=300) for _ in procs)
-    for p in procs:
-        p.join(timeout=60)
+    got = run_ranks(2, _air_body, timeout=300)
     for r in range(2):
         assert got[r] == want, (r, got[r][:400])

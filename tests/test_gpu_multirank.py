@@ -5,20 +5,12 @@ with more ranks than cosets.  On the one-GPU test box the ranks share device 0 a
 (`test_rccl_on_distinct_devices` runs the library's own RCCL communicator when the box has two GPUs or more)."""
 import os
 import random
-import socket
 
 import pytest
-import torch.multiprocessing as mp
+
+from rank_procs import run_ranks
 
 pytestmark = pytest.mark.gpu
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _inputs(case):
@@ -59,70 +51,48 @@ def _inputs(case):
     return trace, pub, keep
 
 
-def _worker(rank, world, port, case, options, knobs, q):
-    import sys
-    import torch.distributed as dist
-    here = os.path.dirname(os.path.abspath(__file__))
-    sys.path.insert(0, os.path.dirname(here))
-    sys.path.insert(0, here)
+def _body(rank, world, case, options, knobs):
     from lambdaworks_cairo_prover_amd import api
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
     if knobs.get("rows_window"):
         os.environ["SP_UPLOAD_MIN_MB"] = "0"      # (read once per process by the library)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        trace, pub, keep = _inputs(case)
-        ctx = api.Context(device=0)
-        ctx.set_collective(world, rank, api.StagedAllGather(), alltoall=knobs.get("alltoall", True))
-        if knobs.get("async"):   # stream-ordered all-gather: the coefficient exchange of a segment goes in column blocks beside the transforms
-            ctx.set_collective_async(api.StagedAsyncAllGather(alltoall=knobs.get("async_a2a", True)))
-        ctx.comm_selftest(4096)  # rank-stamped blocks through every installed primitive (blocking and stream-ordered)
-        link = ctx.comm_measure(1 << 16) if knobs.get("measure") else None   # sp_comm_measure through a transport that really exchanges
-        if "measure_fault" in knobs:     # one rank cannot prepare its payload buffers (the library's fault injection): what do the OTHERS do?
-            os.environ["SP_COMM_MEASURE_FAULT_RANK"] = str(knobs["measure_fault"])
-            try:
-                ctx.comm_measure(1 << 16)
-                raised = None
-            except api.SpError as e:
-                raised = (e.code, str(e))
-            os.environ.pop("SP_COMM_MEASURE_FAULT_RANK")
-            link = dict(ctx.comm_measure(0), raised=raised)
-        if "fri_min_log" in knobs:
-            ctx.set_option(api.SP_OPT_FRI_SHARD_MIN_LOG, knobs["fri_min_log"])
-        if "shard_interp" in knobs:
-            ctx.set_option(api.SP_OPT_SHARD_INTERPOLATION, knobs["shard_interp"])
-        if knobs.get("poseidon"):
-            ctx.set_option(api.SP_OPT_MERKLE_BACKEND, api.SP_MERKLE_POSEIDON)
-        if knobs.get("prewarm"):   # every rank pre-warms (its small proofs are sharded proofs over the same transport)
-            ctx.prewarm(trace.shape[0], trace.shape[1], 18, trace.shape[1] == 43, api.ProofOptions(*options))
-        proof = ctx.cairo_prove(trace, pub, api.ProofOptions(*options))
-        proof2 = ctx.cairo_prove(trace, pub, api.ProofOptions(*options))  # buffer reuse path
-        stats = ctx.comm_stats()
-        stats["composition_path"] = ctx.last_proof_info()["composition_path"]
-        stats["interpolation_sharded"] = ctx.last_proof_info()["interpolation_sharded"]
-        stats["upload_kind"] = ctx.last_upload_stats()["kind"]
-        stats["link"] = link
-        stats["comm_ms"] = ctx.comm_time_ms()
-        q.put((rank, proof if proof == proof2 else b"MISMATCH-ON-REUSE", stats))
-        ctx.close()
-    except Exception:
-        import traceback
-        q.put((rank, ("fail: " + traceback.format_exc()).encode(), None))
-    finally:
-        dist.destroy_process_group()
+    trace, pub, keep = _inputs(case)
+    ctx = api.Context(device=0)
+    ctx.set_collective(world, rank, api.StagedAllGather(), alltoall=knobs.get("alltoall", True))
+    if knobs.get("async"):   # stream-ordered all-gather: the coefficient exchange of a segment goes in column blocks beside the transforms
+        ctx.set_collective_async(api.StagedAsyncAllGather(alltoall=knobs.get("async_a2a", True)))
+    ctx.comm_selftest(4096)  # rank-stamped blocks through every installed primitive (blocking and stream-ordered)
+    link = ctx.comm_measure(1 << 16) if knobs.get("measure") else None   # sp_comm_measure through a transport that really exchanges
+    if "measure_fault" in knobs:     # one rank cannot prepare its payload buffers (the library's fault injection): what do the OTHERS do?
+        os.environ["SP_COMM_MEASURE_FAULT_RANK"] = str(knobs["measure_fault"])
+        try:
+            ctx.comm_measure(1 << 16)
+            raised = None
+        except api.SpError as e:
+            raised = (e.code, str(e))
+        os.environ.pop("SP_COMM_MEASURE_FAULT_RANK")
+        link = dict(ctx.comm_measure(0), raised=raised)
+    if "fri_min_log" in knobs:
+        ctx.set_option(api.SP_OPT_FRI_SHARD_MIN_LOG, knobs["fri_min_log"])
+    if "shard_interp" in knobs:
+        ctx.set_option(api.SP_OPT_SHARD_INTERPOLATION, knobs["shard_interp"])
+    if knobs.get("poseidon"):
+        ctx.set_option(api.SP_OPT_MERKLE_BACKEND, api.SP_MERKLE_POSEIDON)
+    if knobs.get("prewarm"):   # every rank pre-warms (its small proofs are sharded proofs over the same transport)
+        ctx.prewarm(trace.shape[0], trace.shape[1], 18, trace.shape[1] == 43, api.ProofOptions(*options))
+    proof = ctx.cairo_prove(trace, pub, api.ProofOptions(*options))
+    proof2 = ctx.cairo_prove(trace, pub, api.ProofOptions(*options))  # buffer reuse path
+    stats = ctx.comm_stats()
+    stats["composition_path"] = ctx.last_proof_info()["composition_path"]
+    stats["interpolation_sharded"] = ctx.last_proof_info()["interpolation_sharded"]
+    stats["upload_kind"] = ctx.last_upload_stats()["kind"]
+    stats["link"] = link
+    stats["comm_ms"] = ctx.comm_time_ms()
+    ctx.close()
+    return proof if proof == proof2 else b"MISMATCH-ON-REUSE", stats
 
 
 def _run_world(world, case, options, knobs):
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, case, options, knobs, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    got = [q.get(timeout=600) for _ in procs]
-    for p in procs:
-        p.join(timeout=60)
-    return {r: (proof, stats) for r, proof, stats in got}
+    return run_ranks(world, _body, (case, options, knobs), timeout=600)
 
 
 FIB = lambda i: {"kind": "fib", "fib": i}          # noqa: E731
@@ -227,30 +197,17 @@ def test_sharded_random_programs(world, case, options, knobs, oracle, hip_ctx):
         assert "cell" not in case or stats["composition_path"] != 1
 
 
-def _rccl_worker(rank, world, port, fib_index, options, q):
-    import sys
-    import torch
-    import torch.distributed as dist
-    here = os.path.dirname(os.path.abspath(__file__))
-    sys.path.insert(0, os.path.dirname(here))
+def _rccl_body(rank, world, fib_index, options):
     from lambdaworks_cairo_prover_amd import api
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    torch.cuda.set_device(rank)
-    dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device(f"cuda:{rank}"))
-    try:
-        run = api.CairoRun.fibonacci(fib_index)
-        ctx = api.Context(device=rank)
-        ctx.set_option(api.SP_OPT_FRI_SHARD_MIN_LOG, 8)
-        ctx.init_rccl()                       # ncclAllGather / grouped ncclSend+ncclRecv on the context stream
-        ctx.comm_selftest(1 << 20)
-        proof = ctx.cairo_prove(run.main_trace(), run.public_inputs_c, api.ProofOptions(*options))
-        q.put((rank, proof, ctx.comm_stats()))
-        ctx.close()
-    except Exception:
-        import traceback
-        q.put((rank, ("fail: " + traceback.format_exc()).encode(), None))
-    finally:
-        dist.destroy_process_group()
+    run = api.CairoRun.fibonacci(fib_index)
+    ctx = api.Context(device=rank)
+    ctx.set_option(api.SP_OPT_FRI_SHARD_MIN_LOG, 8)
+    ctx.init_rccl()                       # ncclAllGather / grouped ncclSend+ncclRecv on the context stream
+    ctx.comm_selftest(1 << 20)
+    proof = ctx.cairo_prove(run.main_trace(), run.public_inputs_c, api.ProofOptions(*options))
+    stats = ctx.comm_stats()
+    ctx.close()
+    return proof, stats
 
 
 def test_rccl_on_distinct_devices(oracle, hip_ctx, hip_lib):
@@ -266,91 +223,45 @@ def test_rccl_on_distinct_devices(oracle, hip_ctx, hip_lib):
     run = api.CairoRun.fibonacci(fib_index)
     want = hip_ctx.cairo_prove(run.main_trace(), run.public_inputs_c, api.ProofOptions(*options))
     assert want == oracle.cairo_prove(run.main_trace(), run.public_inputs_c, options)
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_rccl_worker, args=(r, world, port, fib_index, options, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    try:
-        got = [q.get(timeout=300) for _ in procs]
-        for p in procs:
-            p.join(timeout=60)
-    finally:
-        for p in procs:
-            if p.is_alive():
-                p.terminate()               # exactly the processes started above
-                p.join(timeout=30)
-    for r, proof, stats in got:
+    got = run_ranks(world, _rccl_body, (fib_index, options), backend="nccl", devices=range(world), timeout=300)
+    for r in range(world):
+        proof, stats = got[r]
         assert proof == want, (r, proof[:300])
         assert stats["world"] == world and stats["alltoall_calls"] >= 3
 
 
-def _rccl_single_worker(port, q):
-    import sys
-    import torch
-    import torch.distributed as dist
-    here = os.path.dirname(os.path.abspath(__file__))
-    sys.path.insert(0, os.path.dirname(here))
+def _rccl_single_body(rank, world):
     from lambdaworks_cairo_prover_amd import api
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    torch.cuda.set_device(0)
-    dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda:0"))
-    try:
-        ctx = api.Context(device=0)
-        ctx.init_rccl()
-        ctx.comm_selftest(1 << 20)
-        ctx.comm_selftest(8)
-        run = api.CairoRun.fibonacci(100)
-        proof = ctx.cairo_prove(run.main_trace(), run.public_inputs_c, api.ProofOptions(4, 3, 3, 1))
-        q.put(("ok", proof))
-        ctx.close()
-    except Exception:
-        import traceback
-        q.put(("fail", traceback.format_exc().encode()))
-    finally:
-        dist.destroy_process_group()
+    ctx = api.Context(device=0)
+    ctx.init_rccl()
+    ctx.comm_selftest(1 << 20)
+    ctx.comm_selftest(8)
+    run = api.CairoRun.fibonacci(100)
+    proof = ctx.cairo_prove(run.main_trace(), run.public_inputs_c, api.ProofOptions(4, 3, 3, 1))
+    ctx.close()
+    return proof
 
 
 def test_rccl_transport_single_rank(oracle):
     """The library's RCCL communicator on the one GPU of the test box (world 1): communicator set-up, ncclAllGather and the
     grouped ncclSend / ncclRecv all-to-all run and deliver the documented layout (sp_comm_selftest)."""
     from lambdaworks_cairo_prover_amd import api
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    p = ctx.Process(target=_rccl_single_worker, args=(_free_port(), q))
-    p.start()
-    status, proof = q.get(timeout=600)
-    p.join(timeout=60)
-    assert status == "ok", proof[:2000]
+    proof = run_ranks(1, _rccl_single_body, backend="nccl", devices=[0], timeout=600)[0]
     run = api.CairoRun.fibonacci(100)
     assert proof == oracle.cairo_prove(run.main_trace(), run.public_inputs_c, (4, 3, 3, 1))
 
 
-def _air_worker(rank, world, port, n, options, q):
-    import sys
-    import torch.distributed as dist
-    here = os.path.dirname(os.path.abspath(__file__))
-    sys.path.insert(0, os.path.dirname(here))
-    sys.path.insert(0, here)
+def _air_body(rank, world, n, options):
     import wide_air
     from lambdaworks_cairo_prover_amd import api
     from test_wide_air import to_bytes
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        ctx = api.Context(device=0)
-        ctx.set_collective(world, rank, api.StagedAllGather())
-        ctx.set_option(api.SP_OPT_FRI_SHARD_MIN_LOG, 5)
-        desc, keep = wide_air.build(n).build()
-        proof = ctx.air_prove(desc, to_bytes(wide_air.main_trace(n)), api.ProofOptions(*options))
-        q.put((rank, proof))
-        ctx.close()
-    except Exception:
-        import traceback
-        q.put((rank, ("fail: " + traceback.format_exc()).encode()))
-    finally:
-        dist.destroy_process_group()
+    ctx = api.Context(device=0)
+    ctx.set_collective(world, rank, api.StagedAllGather())
+    ctx.set_option(api.SP_OPT_FRI_SHARD_MIN_LOG, 5)
+    desc, keep = wide_air.build(n).build()
+    proof = ctx.air_prove(desc, to_bytes(wide_air.main_trace(n)), api.ProofOptions(*options))
+    ctx.close()
+    return proof
 
 
 @pytest.mark.parametrize("world,n,options", [(2, 64, (4, 3, 3, 1)), (4, 256, (4, 4, 3, 2)), (2, 128, (8, 3, 3, 1))])
@@ -361,15 +272,7 @@ def test_sharded_program_air(world, n, options, oracle):
     from test_wide_air import to_bytes
     desc, keep = wide_air.build(n).build()
     want = O.program_air_prove(desc, to_bytes(wide_air.main_trace(n)), options)
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_air_worker, args=(r, world, port, n, options, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    got = dict(q.get(timeout=600) for _ in procs)
-    for p in procs:
-        p.join(timeout=60)
+    got = run_ranks(world, _air_body, (n, options), timeout=600)
     for r in range(world):
         assert got[r] == want, (r, got[r][:400])
 

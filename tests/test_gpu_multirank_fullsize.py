@@ -15,26 +15,17 @@ exchange at 34 / 18 columns of 2^19 and 2^20 rows, digest blocks of 2^18 ... 2^2
 at the default knobs, the row-sharded trace check on real slices."""
 import hashlib
 import os
-import socket
 
 import pytest
-import torch.multiprocessing as mp
 
 from lambdaworks_cairo_prover_amd import api
+from rank_procs import run_ranks
 
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 SHA_70K = "da962bd4513d991c39a0e0cc11cc76d25b9ec405cebcdaaf1449184d4b54cd6b"      # tests/golden/fibonacci_70000.proof, proof section
 SHA_CFG3 = "3b115b1ab0a2d9e2710d2d8a2f4f4a85938bbe574fe7e5ace903c47040ebaa88"     # tests/golden/README_config3.md
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _run_of(case):
@@ -49,73 +40,42 @@ def _run_of(case):
     return api.CairoRun.fibonacci(int(case))
 
 
-def _worker(rank, world, port, case, options, knobs, q):
-    import sys
-    import torch.distributed as dist
-    here = os.path.dirname(os.path.abspath(__file__))
-    sys.path.insert(0, os.path.dirname(here))
-    sys.path.insert(0, here)
-    from lambdaworks_cairo_prover_amd import api
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)      # control plane only (the 128-byte RCCL id, or the staged hooks)
-    try:
-        rccl = knobs.get("transport") == "rccl"
-        device = rank if rccl else 0
-        ctx = api.Context(device=device)
-        if rccl:                           # one GPU per rank: ncclAllGather + grouped ncclSend / ncclRecv, blocking and stream-ordered forms
-            ctx.init_rccl()
-            ctx.comm_selftest(64 << 20)    # rank-stamped 64 MB blocks through every installed primitive
-        else:
-            ctx.set_collective(world, rank, api.StagedAllGather(), alltoall=knobs.get("alltoall", True))
-            if knobs.get("async"):
-                ctx.set_collective_async(api.StagedAsyncAllGather())
-        if "shard_interp" in knobs:
-            ctx.set_option(api.SP_OPT_SHARD_INTERPOLATION, knobs["shard_interp"])
-        run = _run_of(case)
-        opt = api.ProofOptions(*options)
-        entry = knobs.get("entry", "rows")
-        if entry == "rows":            # the reference's row-major TraceTable in pageable host memory (sp_cairo_prove)
-            proof = ctx.cairo_prove(run.main_trace(), run.public_inputs_c, opt)
-        elif entry == "run":           # the front-end's own column-major store (sp_cairo_prove_run)
-            proof = ctx.cairo_prove_run(run, opt)
-        else:                          # already in HBM (sp_cairo_prove_dev)
-            import torch
-            dev_trace = torch.from_numpy(run.main_trace()).to(f"cuda:{device}")
-            torch.cuda.synchronize()
-            proof = ctx.cairo_prove_dev(dev_trace.data_ptr(), run.n_rows, run.n_cols, run.public_inputs_c, opt)
-        stats = ctx.comm_stats()
-        stats.update(ctx.last_proof_info())
-        stats["device_bytes"] = ctx.prover_device_bytes()
-        stats["link"] = ctx.comm_measure(0)          # what sp_comm_init_rccl measured (zeros under the staged hooks)
-        q.put((rank, hashlib.sha256(proof).hexdigest(), len(proof), proof if knobs.get("want_bytes") and rank == 0 else None, stats))
-        ctx.close()
-    except Exception:
-        import traceback
-        q.put((rank, "fail: " + traceback.format_exc(), 0, None, None))
-    finally:
-        dist.destroy_process_group()
+def _body(rank, world, case, options, knobs):      # (the gloo group is the control plane only: the 128-byte RCCL id, or the staged hooks)
+    rccl = knobs.get("transport") == "rccl"
+    device = rank if rccl else 0
+    ctx = api.Context(device=device)
+    if rccl:                           # one GPU per rank: ncclAllGather + grouped ncclSend / ncclRecv, blocking and stream-ordered forms
+        ctx.init_rccl()
+        ctx.comm_selftest(64 << 20)    # rank-stamped 64 MB blocks through every installed primitive
+    else:
+        ctx.set_collective(world, rank, api.StagedAllGather(), alltoall=knobs.get("alltoall", True))
+        if knobs.get("async"):
+            ctx.set_collective_async(api.StagedAsyncAllGather())
+    if "shard_interp" in knobs:
+        ctx.set_option(api.SP_OPT_SHARD_INTERPOLATION, knobs["shard_interp"])
+    run = _run_of(case)
+    opt = api.ProofOptions(*options)
+    entry = knobs.get("entry", "rows")
+    if entry == "rows":            # the reference's row-major TraceTable in pageable host memory (sp_cairo_prove)
+        proof = ctx.cairo_prove(run.main_trace(), run.public_inputs_c, opt)
+    elif entry == "run":           # the front-end's own column-major store (sp_cairo_prove_run)
+        proof = ctx.cairo_prove_run(run, opt)
+    else:                          # already in HBM (sp_cairo_prove_dev)
+        import torch
+        dev_trace = torch.from_numpy(run.main_trace()).to(f"cuda:{device}")
+        torch.cuda.synchronize()
+        proof = ctx.cairo_prove_dev(dev_trace.data_ptr(), run.n_rows, run.n_cols, run.public_inputs_c, opt)
+    stats = ctx.comm_stats()
+    stats.update(ctx.last_proof_info())
+    stats["device_bytes"] = ctx.prover_device_bytes()
+    stats["link"] = ctx.comm_measure(0)          # what sp_comm_init_rccl measured (zeros under the staged hooks)
+    ctx.close()
+    return hashlib.sha256(proof).hexdigest(), len(proof), proof if knobs.get("want_bytes") and rank == 0 else None, stats
 
 
 def _run_world(world, case, options, knobs):
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, case, options, knobs, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    try:
-        # (a collective that never completes on hardware nobody has run yet must not eat the wall-clock limit of the whole suite)
-        got = [q.get(timeout=300 if knobs.get("transport") == "rccl" else 900) for _ in procs]
-        for p in procs:
-            p.join(timeout=120)
-    finally:                                # a rank that hangs (a collective that never completes) must not outlive the test
-        for p in procs:
-            if p.is_alive():
-                p.terminate()               # exactly the processes started above
-                p.join(timeout=30)
-                if p.is_alive():
-                    p.kill()
-    return {g[0]: g[1:] for g in got}
+    # (a collective that never completes on hardware nobody has run yet must not eat the wall-clock limit of the whole suite)
+    return run_ranks(world, _body, (case, options, knobs), timeout=300 if knobs.get("transport") == "rccl" else 900)
 
 
 def _need_devices(world, knobs):
