@@ -78,7 +78,8 @@ const char* sp_version(void);
  * sp_air_periodic_eval, sp_air_periodic_lde; sp_air_check_trace and sp_air_violation_size joined under 7 - they change no structure
  * and no call, and a binding finds a build without them by probing the symbols; so did sp_air_prove_ext, sp_air_verify_ext, sp_air_check_trace_ext,
  * sp_air_stride_size, sp_air_stride_desc_size, sp_air_ext_size, sp_air_stride_limits, sp_air_stride_eval and sp_air_stride_table, and after them sp_air_prove_pub, sp_air_verify_pub,
- * sp_air_check_trace_pub, sp_air_boundary_desc_size and sp_air_boundary_resolve).  A binding compares it (and sp_air_desc_size against its own idea of the struct) when it loads the library, so
+ * sp_air_check_trace_pub, sp_air_boundary_desc_size and sp_air_boundary_resolve, and then sp_air_prove_main, sp_air_check_trace_main,
+ * sp_air_main_trace, sp_air_main_check and sp_air_main_desc_size).  A binding compares it (and sp_air_desc_size against its own idea of the struct) when it loads the library, so
  * a stale build fails at load time with "rebuild the library" instead of with a missing symbol or shifted fields later. */
 #define SP_ABI_VERSION 7
 int sp_abi_version(void);
@@ -621,6 +622,48 @@ int sp_air_check_trace_pub(sp_ctx* ctx, const sp_air_desc* air, const sp_air_ext
 /* Test seam (host): out[j] = the resolved value of values[j], canonical BE; rap = n_rap x 32 bytes, canonical BE.  The `boundary` members
  * are only held against each other here (no AIR to hold them against). */
 int sp_air_boundary_resolve(const sp_air_boundary_desc* bvals, const uint8_t* rap, uint32_t n_rap, uint8_t* out);
+
+/* ---- A program for the MAIN segment: the caller supplies the first input_cols main columns, the device derives the other n_cols as
+ * row-local functions of columns that exist already (bit decompositions, is-zero inverses, intermediate products, counters), then
+ * commits the main segment as ever.  The proof is that of sp_air_prove_pub given the whole table: same bytes, same verifier calls
+ * (there is no verifier entry point for it - how a trace was made is no part of the statement).
+ *
+ * The program runs once per row i (the sp_air_op encoding): LOAD a = row shift 0 .. 7 (row (i + a) mod n), b = main column; CONST
+ * a = constant; ADD, SUB, MUL over earlier ops.  No OUT, no op 6, no RAP challenges (there are none yet).  Derived column k (main
+ * column input_cols + k) names its ops N = num_op and D = den_op (SP_AIR_AUX_NO_DEN: D = 1) and a kind: */
+#define SP_AIR_MAIN_VALUE       0  /* z_i = N(i) / D(i)   (D = 1 for SP_AIR_AUX_NO_DEN); a zero D on any row: SP_E_ZERO_INVERSE */
+#define SP_AIR_MAIN_INV_OR_ZERO 1  /* z_i = 0 where N(i) = 0, else 1 / N(i); den_op must be SP_AIR_AUX_NO_DEN; never an error    */
+#define SP_AIR_MAIN_BIT         2  /* z_i = bit `pad` (0 .. 251) of the canonical integer of N(i); den_op must be NO_DEN          */
+#define SP_AIR_MAIN_SUM         3  /* z_0 = 0, z_i = z_(i-1) + N(i-1) / D(i-1)   (as SP_AIR_AUX_SUM, without challenges)           */
+#define SP_AIR_MAIN_PRODUCT     4  /* z_0 = 1, z_i = z_(i-1) N(i-1) / D(i-1)                                                       */
+/* A LOAD of b < input_cols reads an input; a LOAD of input_cols + k reads derived column k and may stand only behind (the N or D of)
+ * a derived column j > k: columns are built in index order, and a column is complete before anything reads it (shifts wrap).  A column
+ * whose evolution is a true recurrence - z_(i+1) a non-linear function of z_i, such as the state of a hash chain - cannot be written
+ * this way and stays an input.  With a main program air->aux_kind must be 0 or SP_AIR_AUX_PROGRAM (kinds 1 and 2 read a host table of
+ * the main segment, which no longer exists: SP_E_UNSUPPORTED).  Bounds: those of sp_air_limits (65535 ops, 4096 constants, 64 live
+ * values).  Malformed - size other than sizeof(sp_air_main_desc), null members, input_cols == 0 or input_cols + n_cols !=
+ * air->main_cols, input_location above 1, an unknown kind, pad > 251 on a BIT, a denominator on INV_OR_ZERO or BIT, an op outside
+ * 0 .. 4, an operand that is no earlier op, a LOAD of a derived column that is not earlier, num_op / den_op beyond the program - is
+ * SP_E_INVALID_ARG before anything is sized from it. */
+typedef struct { uint32_t kind, num_op, den_op, pad; } sp_air_main_column;
+typedef struct {
+    uint32_t size, input_cols;          /* size = sizeof as compiled; the first input_cols main columns come from the caller */
+    uint32_t input_location, pad;       /* 0: host memory, 1: device memory of the context's device; both row-major n x input_cols, context encoding */
+    uint32_t n_ops;    const sp_air_op* ops;
+    uint32_t n_consts; const uint8_t* consts;     /* canonical BE */
+    uint32_t n_cols;   const sp_air_main_column* cols;   /* input_cols + n_cols == air->main_cols, input_cols >= 1 */
+} sp_air_main_desc;
+uint64_t sp_air_main_desc_size(void);
+/* sp_air_prove_pub / sp_air_check_trace_pub (ext and bvals nullable, as there) with `inputs` in place of the main trace. */
+int sp_air_prove_main(sp_ctx* ctx, const sp_air_desc* air, const sp_air_ext* ext, const sp_air_boundary_desc* bvals, const sp_air_main_desc* main,
+                      const void* inputs, uint64_t n, const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len);
+int sp_air_check_trace_main(sp_ctx* ctx, const sp_air_desc* air, const sp_air_ext* ext, const sp_air_boundary_desc* bvals, const sp_air_main_desc* main,
+                            const void* inputs, uint64_t n, const sp_proof_options* opt, const uint8_t* rap, sp_air_violation* out, uint32_t cap,
+                            uint32_t* n_out);
+/* Test seam (device): rows_out = the whole n x air->main_cols table the prover would commit, row-major, context encoding, host memory;
+ * nothing is committed.  sp_air_main_check (host only): SP_OK, or the decoder's refusal of this program for this AIR and n rows. */
+int sp_air_main_trace(sp_ctx* ctx, const sp_air_desc* air, const sp_air_main_desc* main, const void* inputs, uint64_t n, uint8_t* rows_out);
+int sp_air_main_check(const sp_air_desc* air, const sp_air_main_desc* main, uint64_t n);
 
 /* verify::<Stark252PrimeField, A> (reference src/starks/verifier.rs:559-657) on the host CPU: 1 accept, 0 reject (also for
  * malformed proofs or descriptors). */

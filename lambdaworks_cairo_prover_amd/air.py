@@ -21,6 +21,11 @@ Public data inside a randomized (RAP) argument (sp_air_prove_pub): b.aux.table(s
 program - the public table of a LogUp lookup -, and b.boundary_from(col, step, num, den) declares a boundary constraint whose value is
 N / D of b.public, a small program over constants and the RAP challenges: the reference's boundary_constraints(rap_challenges).  See
 table_lookup and public_permutation below.
+
+Derived main columns (sp_air_prove_main): AirBuilder(..., main_inputs=I) says that the caller supplies main columns 0 .. I - 1 only;
+b.main (MainProgram) declares the others as row-local functions of columns that exist already - b.main.value, inv_or_zero, bit / bits,
+running_sum, product -, which the device builds before it commits the main segment.  The proof is the one of the whole table.  See
+bit_range_check and zero_count below.
 """
 import collections
 import ctypes
@@ -183,6 +188,49 @@ def boundary_desc(ops, consts, values):
     return d, (c_ops, c_consts, c_values)
 
 
+MAIN_VALUE, MAIN_INV_OR_ZERO, MAIN_BIT, MAIN_SUM, MAIN_PRODUCT = range(5)   # sp_air_main_column.kind
+MAIN_MAX_BIT = 251
+INPUTS_HOST, INPUTS_DEVICE = 0, 1    # sp_air_main_desc.input_location
+
+
+class AirMainColumnC(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_uint32), ("num_op", ctypes.c_uint32), ("den_op", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
+
+
+class AirMainDescC(ctypes.Structure):
+    _fields_ = [("size", ctypes.c_uint32), ("input_cols", ctypes.c_uint32), ("input_location", ctypes.c_uint32), ("pad", ctypes.c_uint32),
+                ("n_ops", ctypes.c_uint32), ("ops", ctypes.POINTER(AirOpC)),
+                ("n_consts", ctypes.c_uint32), ("consts", ctypes.c_void_p),
+                ("n_cols", ctypes.c_uint32), ("cols", ctypes.POINTER(AirMainColumnC))]
+
+
+def _check_main_layout():
+    from . import _lib
+    lib = _lib.load()
+    lib.sp_air_main_desc_size.restype = ctypes.c_uint64
+    want = lib.sp_air_main_desc_size()
+    if ctypes.sizeof(AirMainDescC) != want:
+        raise ImportError(f"AirMainDescC is {ctypes.sizeof(AirMainDescC)} bytes, the library's sp_air_main_desc {want}: the binding is out of date")
+
+
+def main_desc(input_cols, ops, consts, cols, input_location=INPUTS_HOST):
+    """ops [(op, a, b), ...], consts [int, ...], cols [(kind, num_op, den_op, pad), ...] -> (AirMainDescC, keepalive): sp_air_main_desc."""
+    _check_main_layout()
+    c_ops = (AirOpC * max(1, len(ops)))()
+    for i, (op, a, b) in enumerate(ops):
+        c_ops[i].op, c_ops[i].a, c_ops[i].b = op, a, b
+    c_consts = ctypes.create_string_buffer(b"".join((int(c) % P).to_bytes(32, "big") for c in consts), max(1, 32 * len(consts)))
+    c_cols = (AirMainColumnC * max(1, len(cols)))()
+    for k, (kind, num_op, den_op, pad) in enumerate(cols):
+        c_cols[k].kind, c_cols[k].num_op, c_cols[k].den_op, c_cols[k].pad = kind, num_op, den_op, pad
+    d = AirMainDescC()
+    d.size, d.input_cols, d.input_location = ctypes.sizeof(AirMainDescC), input_cols, input_location
+    d.n_ops, d.ops = len(ops), ctypes.cast(c_ops, ctypes.POINTER(AirOpC))
+    d.n_consts, d.consts = len(consts), ctypes.cast(c_consts, ctypes.c_void_p)
+    d.n_cols, d.cols = len(cols), ctypes.cast(c_cols, ctypes.POINTER(AirMainColumnC))
+    return d, (c_ops, c_consts, c_cols)
+
+
 def needs_pub(desc):
     """Whether a built descriptor needs the _pub entry points: it carries boundary values computed from the challenges
     (desc.boundary_desc), or its auxiliary program reads a periodic column (op 6)."""
@@ -199,10 +247,16 @@ def route(desc, call):
     """Where a built descriptor goes for call = "prove", "check_trace" or "verify" - new entry points only when the descriptor needs
     them: (the entry point's name, its arguments between `air` and the trace / the options, keepalive).  _pub for boundary values
     computed from the challenges or an auxiliary program that reads a table, _ext for strides, else the parts one by one (the
-    verifier takes no auxiliary program)."""
+    verifier takes no auxiliary program).  A descriptor with a main-trace program (desc.main_desc) is proved and checked through the
+    _main entry points, which take everything the _pub ones do; it is verified as if it had none."""
     def ref(part):
         return None if part is None else ctypes.byref(part)
     aux, per = getattr(desc, "aux_desc", None), getattr(desc, "periodic_desc", None)
+    main = getattr(desc, "main_desc", None)
+    if main is not None and call != "verify":
+        # a main-trace program: the trace argument holds its input columns (a verifier never learns how the trace was made)
+        ext = ext_of(desc)
+        return f"sp_air_{call}_main", (ctypes.byref(ext), ref(getattr(desc, "boundary_desc", None)), ctypes.byref(main)), ext
     if needs_pub(desc):
         ext = ext_of(desc)
         return f"sp_air_{call}_pub", (ctypes.byref(ext), ref(getattr(desc, "boundary_desc", None))), ext
@@ -477,6 +531,174 @@ def _batch_inverse(xs):
     return out
 
 
+class MainProgram:
+    """The main-trace program of an AIR built with main_inputs=I (sp_air_main_desc): the caller supplies main columns 0 .. I - 1, the
+    device derives the others, each a row-local function of columns that exist already.  load(shift, col) reads main column `col` - an
+    input, or a derived column declared so far - on row (i + shift) mod n; every declaration below adds the next main column and returns
+    its index:
+
+        value(N, D)          z_i = N(i) / D(i)   (D = 1 when None): intermediate products, selectors, anything row-local
+        inv_or_zero(x)       z_i = 0 where x(i) = 0, else 1 / x(i): the witness of an is-zero gadget
+        bit(x, j)            z_i = bit j (0 .. 251) of the canonical integer of x(i); bits(x, count): bits 0 .. count - 1
+        running_sum(N, D)    z_0 = 0, z_i = z_(i-1) + N(i-1) / D(i-1): counters and running totals
+        product(N, D)        z_0 = 1, z_i = z_(i-1) N(i-1) / D(i-1)
+
+    A column that reads a derived column must come after it.  A column whose next value is a non-linear function of its own - the
+    state of a hash chain - is a true recurrence and stays an input."""
+
+    def __init__(self, input_cols, main_cols):
+        if not 1 <= input_cols < main_cols:
+            raise ValueError(f"main program: {input_cols} input columns of {main_cols} main columns (at least one input, at least one derived)")
+        self.input_cols, self.main_cols = input_cols, main_cols
+        self.ops, self.consts, self.cols = [], [], []    # cols: (kind, num_op, den_op, pad)
+        self._const_at = {}
+
+    def _emit(self, op, a, b):
+        self.ops.append((op, a, b))
+        return Value(self, len(self.ops) - 1)
+
+    def load(self, shift, col):
+        if not 0 <= shift <= AUX_MAX_SHIFT:
+            raise ValueError(f"main program: row shift {shift} outside 0 .. {AUX_MAX_SHIFT}")
+        if not 0 <= col < self.input_cols + len(self.cols):
+            raise ValueError(f"main program: column {col} is neither an input nor a derived column declared so far")
+        return self._emit(OP_LOAD, shift, col)
+
+    def const(self, v):
+        v %= P
+        if v not in self._const_at:
+            self._const_at[v] = len(self.consts)
+            self.consts.append(v)
+        return self._emit(OP_CONST, self._const_at[v], 0)
+
+    def _column(self, kind, num, den=None, pad=0):
+        num = num if isinstance(num, Value) else self.const(num)
+        if den is not None and not isinstance(den, Value):
+            den = self.const(den)
+        if num.b is not self or (den is not None and den.b is not self):
+            raise ValueError("main program: N and D must be values of this program")
+        if self.input_cols + len(self.cols) >= self.main_cols:
+            raise ValueError(f"main program: more derived columns than main_cols - main_inputs = {self.main_cols - self.input_cols}")
+        self.cols.append((kind, num.i, AUX_NO_DEN if den is None else den.i, pad))
+        return self.input_cols + len(self.cols) - 1
+
+    def value(self, num, den=None):
+        return self._column(MAIN_VALUE, num, den)
+
+    def inv_or_zero(self, x):
+        return self._column(MAIN_INV_OR_ZERO, x)
+
+    def bit(self, x, j):
+        if not 0 <= j <= MAIN_MAX_BIT:
+            raise ValueError(f"main program: bit {j} outside 0 .. {MAIN_MAX_BIT}")
+        return self._column(MAIN_BIT, x, None, j)
+
+    def bits(self, x, count):
+        """Bits 0 .. count - 1 of x, one column each (they share x: the device takes it out of Montgomery form once per row)."""
+        x = x if isinstance(x, Value) else self.const(x)
+        return [self.bit(x, j) for j in range(count)]
+
+    def running_sum(self, num, den=None):
+        return self._column(MAIN_SUM, num, den)
+
+    def product(self, num, den=None):
+        return self._column(MAIN_PRODUCT, num, den)
+
+    def reads(self):
+        """Per op: one more than the highest derived column its value depends on (0: inputs only) - what the decoder follows."""
+        reads = []
+        for op, a, b in self.ops:
+            if op == OP_LOAD:
+                reads.append(max(0, b - self.input_cols + 1))
+            else:
+                reads.append(max(reads[a], reads[b]) if op in (OP_ADD, OP_SUB, OP_MUL) else 0)
+        return reads
+
+    def check(self):
+        """The decoder's rules (air_statement_from_c), for a program whose lists were filled by hand too: ValueError naming the first one broken."""
+        if self.input_cols < 1 or not self.cols or self.input_cols + len(self.cols) != self.main_cols:
+            raise ValueError(f"main program: {self.input_cols} input + {len(self.cols)} derived columns, the AIR has main_cols = {self.main_cols}")
+        for t, (op, a, b) in enumerate(self.ops):
+            ok = ((op == OP_LOAD and 0 <= a <= AUX_MAX_SHIFT and 0 <= b < self.main_cols) or (op == OP_CONST and 0 <= a < len(self.consts)) or
+                  (op in (OP_ADD, OP_SUB, OP_MUL) and 0 <= a < t and 0 <= b < t))
+            if not ok:
+                raise ValueError(f"main program: malformed op {t} (LOAD, CONST, ADD, SUB, MUL over earlier ops only)")
+        reads = self.reads()
+        for k, (kind, num_op, den_op, pad) in enumerate(self.cols):
+            den = den_op != AUX_NO_DEN
+            if not MAIN_VALUE <= kind <= MAIN_PRODUCT:
+                raise ValueError(f"main program: derived column {k} has an unknown kind")
+            if not 0 <= num_op < len(self.ops) or (den and not 0 <= den_op < len(self.ops)):
+                raise ValueError(f"main program: derived column {k} names an op beyond the program")
+            if den and kind in (MAIN_INV_OR_ZERO, MAIN_BIT):
+                raise ValueError(f"main program: derived column {k} is an INV_OR_ZERO or a BIT and takes no denominator")
+            if kind == MAIN_BIT and not 0 <= pad <= MAIN_MAX_BIT:
+                raise ValueError(f"main program: derived column {k} names bit {pad} (0 .. {MAIN_MAX_BIT})")
+            r = max(reads[num_op], reads[den_op] if den else 0)
+            if r > k:
+                raise ValueError(f"main program: derived column {k} reads derived column {r - 1}, which is not an earlier one")
+
+    def evaluate(self, input_rows):
+        """The whole main segment in Python integers (the semantics of sp_air_prove_main): input_rows = n x input_cols field elements;
+        returns an (n, main_cols) numpy object array.  Columns in index order, each op one vectorised numpy operation, evaluated when the
+        first column that needs it is built (the columns it loads are complete by then).  ValueError on a zero denominator."""
+        import numpy as np
+        self.check()
+        rows = input_rows if not isinstance(input_rows, np.ndarray) else input_rows.astype(object)
+        n = len(rows)
+        m = np.empty((n, self.main_cols), dtype=object)
+        m[:, :self.input_cols] = rows
+        m[:, :self.input_cols] %= P
+        vals = [None] * len(self.ops)
+
+        def need(t):
+            todo, stack = set(), [t]
+            while stack:
+                u = stack.pop()
+                if u in todo or vals[u] is not None:
+                    continue
+                todo.add(u)
+                if self.ops[u][0] in (OP_ADD, OP_SUB, OP_MUL):
+                    stack += [self.ops[u][1], self.ops[u][2]]
+            for u in sorted(todo):
+                op, a, b = self.ops[u]
+                if op == OP_LOAD:
+                    vals[u] = np.roll(m[:, b], -a)
+                elif op == OP_CONST:
+                    vals[u] = np.full(n, self.consts[a], dtype=object)
+                elif op == OP_ADD:
+                    vals[u] = (vals[a] + vals[b]) % P
+                elif op == OP_SUB:
+                    vals[u] = (vals[a] - vals[b]) % P
+                else:
+                    vals[u] = (vals[a] * vals[b]) % P
+            return vals[t]
+
+        for k, (kind, num_op, den_op, pad) in enumerate(self.cols):
+            t = need(num_op)
+            if den_op != AUX_NO_DEN:
+                t = (t * np.array(_batch_inverse([int(x) for x in need(den_op)]), dtype=object)) % P
+            col = m[:, self.input_cols + k]
+            if kind == MAIN_VALUE:
+                col[:] = t
+            elif kind == MAIN_INV_OR_ZERO:
+                where = [i for i in range(n) if int(t[i]) != 0]
+                col[:] = 0
+                for i, inv in zip(where, _batch_inverse([int(t[i]) for i in where])):
+                    col[i] = inv
+            elif kind == MAIN_BIT:
+                col[:] = [(int(x) >> pad) & 1 for x in t]
+            elif kind == MAIN_SUM:
+                col[0] = 0
+                col[1:] = np.cumsum(t[:-1]) % P
+            else:
+                z = 1
+                for i in range(n):
+                    col[i] = z
+                    z = z * int(t[i]) % P
+        return m
+
+
 class PublicProgram:
     """Values computed from constants and the RAP challenges alone (sp_air_boundary_desc): const(v), rap(i) and + - * through Value.
     AirBuilder.boundary_from names two of them as the N and D of a boundary value."""
@@ -543,9 +765,11 @@ def ints_to_bytes(values):
 
 class AirBuilder:
     def __init__(self, main_cols, offsets, degree_bound_factor, aux_cols=0, n_rap=0, aux_kind=AUX_NONE, num_transition_exemptions=1,
-                 aux_builder=None, periodic=None):
+                 aux_builder=None, periodic=None, main_inputs=None):
         """aux_builder(rap: list[int]) -> (n, aux_cols) nested list of ints: the AIR's build_auxiliary_trace (aux_kind AUX_CALLBACK).
-        periodic: the periodic columns, one list of values each (a power-of-two number of them; the trace must be at least as long)."""
+        periodic: the periodic columns, one list of values each (a power-of-two number of them; the trace must be at least as long).
+        main_inputs: the number of main columns the caller supplies; the others are declared through b.main (MainProgram) and derived
+        on the device (sp_air_prove_main).  None: the caller supplies the whole main segment."""
         assert 1 <= len(offsets) <= MAX_OFFSETS
         self.periodic_cols = [[int(v) % P for v in values] for values in (periodic or [])]
         for k, values in enumerate(self.periodic_cols):
@@ -562,6 +786,8 @@ class AirBuilder:
         # boundary values computed from the RAP challenges (sp_air_boundary_desc): the program, and per value (index into bcs, N, D)
         self.public = PublicProgram(n_rap)
         self.bvalues = []
+        # main_inputs: the derived main columns as a program over the main columns before them (sp_air_prove_main)
+        self.main = MainProgram(main_inputs, main_cols) if main_inputs is not None else None
 
     def _emit(self, op, a, b):
         self.ops.append((op, a, b))
@@ -663,7 +889,8 @@ class AirBuilder:
     def check_trace(self, rows, rap=()):
         """Which constraints the trace breaks, and where, in Python integers: the model of sp_air_check_trace (the reference's
         validate_trace, src/starks/debug.rs:13-104).  rows: (n, main_cols + aux_cols) ints, main||aux; with an aux program also
-        (n, main_cols), to which self.aux.evaluate(rows, rap) is appended.  rap: the RAP challenges.  Constraint k is enforced on rows
+        (n, main_cols), to which self.aux.evaluate(rows, rap) is appended; with a main program also (n, main_inputs), the input columns
+        alone, which self.main.evaluate completes first.  rap: the RAP challenges.  Constraint k is enforced on rows
         0 .. n - 1 - enforced_exemptions()[k] - with a period > 1 on enforced_rows(k, n), its progression without that many of its last
         rows; frame rows wrap modulo n.  Boundary values declared with boundary_from are resolved under `rap` first.  Returns
         [Violation, ...]: the transition constraints by index, then the boundary constraints by index; [] for a trace that satisfies the AIR."""
@@ -675,6 +902,8 @@ class AirBuilder:
         rap = [int(r) % P for r in rap]
         if len(rap) != self.n_rap:
             raise ValueError(f"check_trace: {len(rap)} RAP challenges for an AIR with n_rap = {self.n_rap}")
+        if self.main is not None and m.shape[1] == self.main.input_cols:
+            m = self.main.evaluate(m)
         if self.aux is not None and m.shape[1] == self.main_cols and self.aux_cols:
             m = np.concatenate([m, self.aux.evaluate(m, rap)], axis=1)
         if m.shape[1] != self.main_cols + self.aux_cols:
@@ -756,6 +985,14 @@ class AirBuilder:
                 bits = {self.aux.key_bits.get(k, 64) for k in members}
                 if len(bits) > 1 or not 1 <= min(bits) <= 64:
                     raise ValueError(f"aux program: the sorted columns {members} share a key and must agree on key_bits in 1 .. 64, not {sorted(bits)}")
+        if self.main is not None:
+            for name, value in (("constants", len(self.main.consts)), ("ops", len(self.main.ops))):
+                if value > lim[name]:
+                    raise ValueError(f"main program exceeds the {name} limit of sp_air_prove_main: {value} > {lim[name]}")
+            self.main.check()
+            if self.aux_kind not in (AUX_NONE, AUX_PROGRAM):
+                raise ValueError("main program: aux_kind must be AUX_NONE or AUX_PROGRAM (the other kinds build the auxiliary segment from a host "
+                                 "table of the main segment)")
         if self.bvalues:
             for name, value in (("constants", len(self.public.consts)), ("ops", len(self.public.ops))):
                 if value > lim[name]:
@@ -776,7 +1013,9 @@ class AirBuilder:
         instead, its callback evaluating the aux program in Python over `main_trace` ((n, main_cols, 32) canonical big-endian
         bytes, or n rows of ints): what the CPU oracle and sp_air_prove accept.
         With boundary_from constraints the returned desc carries their AirBoundaryDescC (desc.boundary_desc); with that, or an aux program
-        that reads a table, api.Context.air_prove, air_check_trace and api.air_verify go through sp_air_prove_pub and its siblings."""
+        that reads a table, api.Context.air_prove, air_check_trace and api.air_verify go through sp_air_prove_pub and its siblings.
+        With a main program (main_inputs) the returned desc carries its AirMainDescC (desc.main_desc): api.Context.air_prove and
+        air_check_trace then take the input columns only and go through sp_air_prove_main / sp_air_check_trace_main."""
         _check_layout()
         self.check_limits()
         if self.aux is not None and aux_as_callback:
@@ -843,6 +1082,10 @@ class AirBuilder:
             b_desc, b_keep = self.build_boundary_desc()
             d.boundary_desc = b_desc
             keep = keep + (b_desc, b_keep)
+        if self.main is not None:
+            m_desc, m_keep = main_desc(self.main.input_cols, self.main.ops, self.main.consts, self.main.cols)
+            d.main_desc = m_desc
+            keep = keep + (m_desc, m_keep)
         return d, keep
 
     def build_boundary_desc(self):
@@ -871,12 +1114,12 @@ class AirBuilder:
         rows = main_trace
         if isinstance(rows, np.ndarray) and rows.dtype == np.uint8:
             rows = trace_to_ints(rows)
-        program, aux_kind = self.aux, self.aux_kind
-        self.aux_kind, self.aux = AUX_CALLBACK, None
+        program, aux_kind, main = self.aux, self.aux_kind, self.main
+        self.aux_kind, self.aux, self.main = AUX_CALLBACK, None, None   # (the callback's AIR takes the whole main segment: no main program)
         try:
             d, keep = self.build()
         finally:
-            self.aux_kind, self.aux = aux_kind, program
+            self.aux_kind, self.aux, self.main = aux_kind, program, main
         aux_cols, periodic = self.aux_cols, self.periodic_cols
 
         def _aux(user, rap_ptr, n_rap, out_ptr):   # canonical big-endian contexts (the default encoding)
@@ -1144,3 +1387,57 @@ def memory_consistency_trace(n, first, cells, accesses):
     if len(accesses) != n or set(accesses) != set(range(len(cells))):
         raise ValueError("memory_consistency_trace: n accesses that reach every cell")
     return [[first + j, int(cells[j]) % P] for j in accesses]
+
+
+# ---- derived main columns: two worked examples ----------------------------------------------------------------------------------
+def bit_range_check(n, bits):
+    """Every v_i is below 2^bits: one input column v and `bits` derived columns b_0 .. b_(bits-1), the bits of v (MainProgram.bits), so
+    the caller uploads n values where the table has n x (1 + bits).  Two constraints on every row, no exemption: sum_j gamma^j b_j
+    (b_j - 1) = 0 - every b_j (b_j - 1) = 0, folded with the powers of one challenge gamma sampled behind the main commitment, since a
+    descriptor takes at most 64 transition constraints and there may be up to 251 bits - and sum_j 2^j b_j = v.  degree_bound_factor 1
+    (the products have degree 2 = factor + 1, as in `dummy`); no auxiliary column."""
+    if not 1 <= bits <= MAIN_MAX_BIT:
+        raise ValueError(f"bit_range_check: {bits} bits (1 .. {MAIN_MAX_BIT}: the canonical integers of the field have 252)")
+    b = AirBuilder(1 + bits, [0], 1, n_rap=1, main_inputs=1)
+    cols = b.main.bits(b.main.load(0, 0), bits)
+    gamma = b.rap(0)
+    power, boolean, total = None, None, None
+    for j, c in enumerate(cols):
+        x = b.load(0, c)
+        power = b.const(1) if power is None else power * gamma
+        term, weighted = power * (x * (x - 1)), x * (1 << j)
+        boolean = term if boolean is None else boolean + term
+        total = weighted if total is None else total + weighted
+    b.constraint(boolean, degree=2, exemptions=0)
+    b.constraint(total - b.load(0, 0), degree=1, exemptions=0)
+    return b
+
+
+def bit_range_check_inputs(n, bits, rng):
+    """(n, 1) Python ints below 2^bits from rng.randrange: the input column of bit_range_check."""
+    return [[rng.randrange(1 << bits)] for _ in range(n)]
+
+
+def zero_count(n, count):
+    """The public `count` is the number of zeros among x_0 .. x_(n-2): one input column x; derived columns inv = INV_OR_ZERO(x) (column
+    1), f = VALUE(1 - x inv), the is-zero flag, which reads inv (column 2), and c = SUM(f), the zeros before each row, which reads f
+    (column 3).  Constraints x f = 0 and f = 1 - x inv on every row, c' = c + f with the last row exempt; boundaries c_0 = 0 and
+    c_(n-1) = count.  degree_bound_factor 1."""
+    b = AirBuilder(4, [0, 1], 1, main_inputs=1)
+    m = b.main
+    inv = m.inv_or_zero(m.load(0, 0))
+    f = m.value(1 - m.load(0, 0) * m.load(0, inv))
+    c = m.running_sum(m.load(0, f))
+    x = b.load(0, 0)
+    b.constraint(x * b.load(0, f), degree=2, exemptions=0)
+    b.constraint(b.load(0, f) - (1 - x * b.load(0, inv)), degree=2, exemptions=0)
+    b.constraint(b.load(1, c) - b.load(0, c) - b.load(0, f), degree=1, exemptions=1)
+    b.boundary(c, 0, 0); b.boundary(c, n - 1, count)
+    return b
+
+
+def zero_count_inputs(n, zeros, rng):
+    """(n, 1) Python ints: zero on the rows `zeros`, a non-zero value from rng.randrange elsewhere; the statement's count is the number
+    of those rows below n - 1."""
+    zeros = set(zeros)
+    return [[0 if i in zeros else 1 + rng.randrange(P - 1)] for i in range(n)]

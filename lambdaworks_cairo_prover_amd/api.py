@@ -219,22 +219,51 @@ class Context:
         return {"kind": kinds.get(int(v[0]), "?"), "groups": int(v[1]), "bytes": int(v[2]), "gather_ms": round(v[3], 3), "gather_gbs": round(v[4], 1),
                 "dma_ms": round(v[5], 3), "dma_gbs": round(v[6], 1), "exposed_ms": round(v[7], 3), "max_stall_ms": round(v[8], 3), "host_ms": round(v[9], 3)}
 
+    def _air_rows(self, desc, rows):
+        """The trace argument of air_prove / air_check_trace / air_main_trace as (pointer, n, keepalive): (n, cols, 32) bytes in host
+        memory - cols = desc.main_cols, or, for a desc with a main-trace program, its input columns -, or, with such a program, a CUDA
+        torch.uint8 tensor of the same shape on the context's device, passed by data_ptr() (desc.main_desc.input_location says which)."""
+        main = getattr(desc, "main_desc", None)
+        cols = desc.main_cols if main is None else main.input_cols
+        if main is not None and hasattr(rows, "data_ptr") and getattr(rows, "is_cuda", False):
+            import torch
+            t = rows.contiguous()
+            assert t.dtype == torch.uint8 and t.dim() == 3 and t.shape[1] == cols and t.shape[2] == 32
+            torch.cuda.current_stream(t.device).synchronize()   # (the library runs on its own stream)
+            main.input_location = 1
+            return ctypes.c_void_p(t.data_ptr()), t.shape[0], t
+        a = np.ascontiguousarray(rows, dtype=np.uint8)
+        assert a.ndim == 3 and a.shape[1] == cols and a.shape[2] == 32
+        if main is not None:
+            main.input_location = 0
+        return _u8p(a), a.shape[0], a
+
+    def air_main_trace(self, desc, inputs):
+        """sp_air_main_trace: the whole main segment the prover would commit for a desc with a main-trace program (AirBuilder(...,
+        main_inputs=I)), built on the device from the input columns: (n, main_cols, 32) uint8 in the context encoding.  No commitment."""
+        main = getattr(desc, "main_desc", None)
+        if main is None:
+            raise ValueError("air_main_trace: the descriptor carries no main program (AirBuilder(..., main_inputs=...))")
+        ptr, n, keep = self._air_rows(desc, inputs)
+        out = np.empty((n, desc.main_cols, 32), dtype=np.uint8)
+        check(self._lib.sp_air_main_trace(self._h, ctypes.byref(desc), ctypes.byref(main), ptr, ctypes.c_uint64(n), _u8p(out)))
+        return out
+
     def air_prove(self, desc, main_trace, options):
         """sp_air_prove: desc = lambdaworks_cairo_prover_amd.air.AirDescC (AirBuilder.build()[0]); main_trace (n, cols, 32).
         A desc that carries an auxiliary program (AirBuilder with aux_kind=air.AUX_PROGRAM) goes to sp_air_prove_aux, one that
         carries periodic columns (AirBuilder(..., periodic=[...])) to sp_air_prove_periodic - with its auxiliary program, if any; one
         that carries strides (a constraint with period > 1) to sp_air_prove_ext with all of these; one that carries boundary values
         computed from the challenges (AirBuilder.boundary_from) or whose auxiliary program reads a table (AuxProgram.table) to
-        sp_air_prove_pub."""
-        a = np.ascontiguousarray(main_trace, dtype=np.uint8)
-        n, cols = a.shape[0], a.shape[1]
-        assert cols == desc.main_cols
+        sp_air_prove_pub.  One that carries a main-trace program (AirBuilder(..., main_inputs=I)) goes to sp_air_prove_main with all of
+        these: main_trace then holds the I input columns only, (n, I, 32) bytes or a CUDA torch.uint8 tensor of that shape."""
+        a, n, keep_rows = self._air_rows(desc, main_trace)
         opt = options.to_c()
         out = ctypes.POINTER(ctypes.c_uint8)()
         ln = ctypes.c_uint64()
         from . import air
         name, parts, keep = air.route(desc, "prove")
-        check(getattr(self._lib, name)(self._h, ctypes.byref(desc), *parts, _u8p(a), ctypes.c_uint64(n), ctypes.byref(opt), ctypes.byref(out), ctypes.byref(ln)))
+        check(getattr(self._lib, name)(self._h, ctypes.byref(desc), *parts, a, ctypes.c_uint64(n), ctypes.byref(opt), ctypes.byref(out), ctypes.byref(ln)))
         proof = ctypes.string_at(out, ln.value)
         self._lib.sp_free(out)
         return proof
@@ -242,15 +271,13 @@ class Context:
     def air_check_trace(self, desc, main_trace, options=None, rap=None, cap=4160):
         """sp_air_check_trace: which constraints of the AIR the trace breaks, and where - [air.Violation, ...] as AirBuilder.check_trace
         gives them (transition constraints by index, then boundary constraints by index; [] for a satisfying trace), at most `cap` of
-        them.  desc and main_trace as for air_prove (the same dispatch on desc.aux_desc / desc.periodic_desc).  rap: the RAP challenges
+        them.  desc and main_trace as for air_prove (the same dispatch on desc.aux_desc / desc.periodic_desc / desc.main_desc).  rap: the RAP challenges
         (ints) the auxiliary columns are built from; None: those a proof under `options` would sample.  No proof is produced."""
         from . import air
         if rap is None and options is None:
             raise ValueError("air_check_trace: without rap, the options of the proof whose challenges are wanted are needed")
         air._check_violation_layout()
-        a = np.ascontiguousarray(main_trace, dtype=np.uint8)
-        n, cols = a.shape[0], a.shape[1]
-        assert cols == desc.main_cols
+        a, n, keep_rows = self._air_rows(desc, main_trace)
         opt = None if options is None else options.to_c()
         rap_bytes = None
         if rap is not None:
@@ -263,7 +290,7 @@ class Context:
         out = (air.AirViolationC * max(1, cap))()
         total = ctypes.c_uint32(0)
         name, parts, keep = air.route(desc, "check_trace")
-        check(getattr(self._lib, name)(self._h, ctypes.byref(desc), *parts, _u8p(a), ctypes.c_uint64(n), None if opt is None else ctypes.byref(opt),
+        check(getattr(self._lib, name)(self._h, ctypes.byref(desc), *parts, a, ctypes.c_uint64(n), None if opt is None else ctypes.byref(opt),
                                        None if rap_bytes is None else _u8p(rap_bytes), out if cap else None, ctypes.c_uint32(cap), ctypes.byref(total)))
         self.last_check_total = total.value     # the number of violated constraints, which may exceed cap
         return [air.Violation(int(v.kind), int(v.index), int(v.rows), int(v.first_row), int(v.last_row), int.from_bytes(bytes(v.value), "big"))
@@ -526,6 +553,13 @@ def air_boundary_resolve(bvals, rap):
     out = ctypes.create_string_buffer(max(1, 32 * bvals.n_values))
     check(_lib.load().sp_air_boundary_resolve(ctypes.byref(bvals), rap_bytes if rap else None, ctypes.c_uint32(len(rap)), out))
     return [int.from_bytes(out.raw[32 * j:32 * j + 32], "big") for j in range(bvals.n_values)]
+
+
+def air_main_check(desc, n, main=None):
+    """sp_air_main_check (host): the decoder's verdict on a main-trace program (main, or desc.main_desc) for this AIR and n rows; raises
+    SpError with its refusal (SP_E_INVALID_ARG, or SP_E_UNSUPPORTED beside aux_kind 1 or 2)."""
+    main = desc.main_desc if main is None else main
+    check(_lib.load().sp_air_main_check(ctypes.byref(desc), ctypes.byref(main), ctypes.c_uint64(n)))
 
 
 def air_stride_eval(period, offset, exemptions, n, point):

@@ -146,6 +146,52 @@ std::string validate_aux_program(const AirAuxHost& aux, uint32_t main_cols, uint
     }
     return "";
 }
+
+// sp_air_main_desc -> AirMainHost against its AIR: "" or what is wrong.  Every count and pointer first; then the ops (0 .. 4 over
+// earlier ops, LOADs of main columns at shifts 0 .. 7), the columns' kinds, and - following the operands - which derived columns
+// the ops behind each column load: only earlier ones.
+std::string main_from_c(const AirDescHost& air, const sp_air_main_desc* m, AirMainHost& out) {
+    if (m->size != sizeof(sp_air_main_desc)) return "main program: sp_air_main_desc.size is not sizeof(sp_air_main_desc)";
+    if (!m->ops || !m->consts || !m->cols) return "main program: null ops, consts or cols";
+    if (m->input_cols == 0 || m->n_cols == 0 || (uint64_t)m->input_cols + m->n_cols != air.main_cols)
+        return "main program: input_cols (>= 1) + n_cols (>= 1) must be air->main_cols";
+    if (m->input_location > 1) return "main program: input_location is 0 (host memory) or 1 (device memory)";
+    if (m->n_ops == 0 || m->n_ops > AIR_LIMIT_OPS || m->n_consts > AIR_LIMIT_CONSTS) return "main program: 1 .. 65535 ops and at most 4096 constants";
+    std::vector<AirOpHost> ops;
+    ops_from_c(m->ops, m->n_ops, ops);
+    const size_t n_ops = ops.size();
+    // (no OUT target, no periodic column: ops 0 .. 4 are all that is left)
+    const size_t bad = air_program_first_bad_op(ops, AIR_LIMIT_AUX_SHIFT + 1, air.main_cols, m->n_consts, 0, 0);
+    if (bad < n_ops)
+        return "main program: malformed op " + std::to_string(bad) + " (LOAD needs a shift of 0 .. 7 and a main column, CONST a constant, ADD / SUB / MUL earlier "
+               "ops; there is no OUT, no op 6 and no RAP challenge)";
+    // reads[t]: one more than the highest derived column the value of op t depends on (0: inputs only)
+    std::vector<uint32_t> reads(n_ops, 0);
+    for (size_t t = 0; t < n_ops; ++t) {
+        const AirOpHost& o = ops[t];
+        if (o.op == 0 && o.b >= m->input_cols) reads[t] = o.b - m->input_cols + 1;
+        else if (o.op >= 2 && o.op <= 4) reads[t] = std::max(reads[o.a], reads[o.b]);
+    }
+    std::vector<AirMainColumnHost> cols;
+    cols.reserve(m->n_cols);
+    for (uint32_t k = 0; k < m->n_cols; ++k) {
+        const sp_air_main_column& c = m->cols[k];
+        const std::string who = "main program: derived column " + std::to_string(k);
+        const bool den = c.den_op != SP_AIR_AUX_NO_DEN;
+        if (c.kind > SP_AIR_MAIN_PRODUCT) return who + " has an unknown kind";
+        if (c.num_op >= n_ops || (den && c.den_op >= n_ops)) return who + " names an op beyond the program";
+        if (den && (c.kind == SP_AIR_MAIN_INV_OR_ZERO || c.kind == SP_AIR_MAIN_BIT)) return who + " is an INV_OR_ZERO or a BIT and takes no denominator";
+        if (c.kind == SP_AIR_MAIN_BIT && c.pad > 251) return who + " names bit " + std::to_string(c.pad) + " (0 .. 251)";
+        const uint32_t r = std::max(reads[c.num_op], den ? reads[c.den_op] : 0u);
+        if (r > k) return who + " reads derived column " + std::to_string(r - 1) + ", which is not an earlier one";
+        cols.push_back(AirMainColumnHost{c.kind, c.num_op, c.den_op, c.kind == SP_AIR_MAIN_BIT ? c.pad : 0u, r});
+    }
+    out.input_cols = m->input_cols; out.input_location = m->input_location;
+    out.ops.swap(ops);
+    consts_from_c(m->consts, m->n_consts, out.consts);
+    out.cols.swap(cols);
+    return "";
+}
 }  // namespace
 
 const char* const AIR_BOUNDARY_VALUES_MALFORMED = "malformed boundary values (ops 1 - 4 over earlier ops, each boundary < n_boundary and named once, num_op / den_op "
@@ -172,7 +218,7 @@ bool air_boundary_from_c(const sp_air_boundary_desc* d, uint32_t n_boundary, uin
 }
 
 std::string air_statement_from_c(const sp_air_desc* d, const sp_air_aux_desc* aux, const sp_air_periodic_desc* periodic, const sp_air_stride_desc* strides,
-                                 const sp_air_boundary_desc* bvals, bool aux_reads_periodic, uint64_t n, AirStatement& st) {
+                                 const sp_air_boundary_desc* bvals, bool aux_reads_periodic, uint64_t n, AirStatement& st, const sp_air_main_desc* main) {
     AirDescHost& air = st.air;
     st.aux_reads_periodic = aux_reads_periodic;
     if (!air_desc_from_c(d, air)) return "malformed AIR descriptor (1 .. 8 frame rows, 1 .. 64 transition constraints, every count with its array)";
@@ -190,8 +236,19 @@ std::string air_statement_from_c(const sp_air_desc* d, const sp_air_aux_desc* au
     if (air.consts.size() > AIR_LIMIT_CONSTS) return "more than 4096 constants";
     if (air.consts.size() + air.n_rap > 65535) return "constants and RAP challenges exceed the 16-bit operand range";
     if (air.ops.size() > AIR_LIMIT_OPS) return "more than 65535 ops";
+    if (main) {
+        const std::string refused = main_from_c(air, main, st.main.emplace());
+        if (!refused.empty()) return refused;
+    }
     // (only the _pub entry points let an auxiliary program read the periodic columns: 0 of them from everywhere else)
-    if (st.aux) return validate_aux_program(*st.aux, air.main_cols, air.n_rap, st.aux_periodic() ? st.n_periodic() : 0u);
+    if (st.aux) {
+        const std::string refused = validate_aux_program(*st.aux, air.main_cols, air.n_rap, st.aux_periodic() ? st.n_periodic() : 0u);
+        if (!refused.empty()) return refused;
+    }
+    if (st.main && air.aux_kind != 0 && air.aux_kind != SP_AIR_AUX_PROGRAM) {
+        st.unsupported = true;
+        return "a main program needs aux_kind 0 or SP_AIR_AUX_PROGRAM (kinds 1 and 2 build the auxiliary segment from a host table of the main segment)";
+    }
     return "";
 }
 

@@ -45,6 +45,16 @@ struct AirAuxHost {
     std::vector<AirAuxColumnHost> cols;
 };
 
+// Host form of sp_air_main_desc: the program that derives main columns input_cols .. main_cols - 1 from the caller's input columns.
+// reads: derived columns [0, reads) are what the ops behind this column load (0: inputs only); the decoder holds reads <= its index.
+struct AirMainColumnHost { uint32_t kind, num_op, den_op, bit, reads; };
+struct AirMainHost {
+    uint32_t input_cols = 0, input_location = 0;   // 0: the inputs are host memory, 1: device memory
+    std::vector<AirOpHost> ops;
+    std::vector<fe> consts;
+    std::vector<AirMainColumnHost> cols;
+};
+
 // Host form of sp_air_periodic_desc: column k repeats cols[k] (a power-of-two number of values, at most the trace length).
 constexpr uint32_t AIR_MAX_PERIODIC = 64;
 struct AirPeriodicHost { std::vector<std::vector<fe>> cols; };
@@ -106,7 +116,9 @@ struct AirStatement {
     std::optional<AirAuxHost> aux;            // the auxiliary program of an AIR with aux_kind SP_AIR_AUX_PROGRAM
     std::optional<AirPeriodicHost> periodic;  // the periodic columns the constraint program reads with op 6
     std::optional<AirBoundaryHost> bvals;     // boundary values computed from the RAP challenges (air_resolve_boundary_into after round 1)
+    std::optional<AirMainHost> main;          // the main-trace program: the caller hands over its input columns only (sp_air_prove_main)
     bool aux_reads_periodic = false;
+    bool unsupported = false;                 // set with a refusal that is SP_E_UNSUPPORTED, not SP_E_INVALID_ARG (a main program beside aux_kind 1 or 2)
     // the periodic columns the auxiliary program may read: null when it may read none
     const AirPeriodicHost* aux_periodic() const { return aux_reads_periodic && periodic ? &*periodic : nullptr; }
     uint32_t n_periodic() const { return periodic ? (uint32_t)periodic->cols.size() : 0u; }
@@ -118,11 +130,15 @@ struct AirStatement {
 // an auxiliary program that fits its AIR (aux_kind, one column per auxiliary column, ops over earlier ops, LOADs of main columns - or
 // of SORTED auxiliary columns, but not from the ops behind a sorted column - at shifts 0 .. 7, op 6 only with aux_reads_periodic, at
 // most SP_AIR_AUX_MAX_SORT_GROUPS sort groups, each with one key_bits in 1 .. 64); boundary values as air_boundary_from_c wants them; the bounds of sp_air_limits.
+// main (nullable, the prover and the trace check only): a main-trace program whose columns add up to air.main_cols, ops 0 .. 4 over
+// earlier ops, LOADs at shifts 0 .. 7 of inputs or - from the ops behind derived column j - of derived columns k < j, the kinds' own
+// rules (sp_air_main_desc); beside it aux_kind is 0 or SP_AIR_AUX_PROGRAM, else the refusal comes with out.unsupported set.
 // The constraint program itself is checked where it is turned into what runs it (build_air_program, air_verify_host).
 // An sp_air_ext is taken apart by the entry point that receives it; this is the one thing it checks first: null, or what is wrong.
 inline const char* air_ext_refusal(const sp_air_ext* ext) { return ext && ext->size != sizeof(sp_air_ext) ? "sp_air_ext.size is not sizeof(sp_air_ext)" : nullptr; }
 std::string air_statement_from_c(const sp_air_desc* d, const sp_air_aux_desc* aux, const sp_air_periodic_desc* periodic, const sp_air_stride_desc* strides,
-                                 const sp_air_boundary_desc* bvals, bool aux_reads_periodic, uint64_t n, AirStatement& out);
+                                 const sp_air_boundary_desc* bvals, bool aux_reads_periodic, uint64_t n, AirStatement& out,
+                                 const sp_air_main_desc* main = nullptr);
 // `verify::<F, A>` for a program AIR (verifier.cpp): 1 accept, 0 reject; throws std::runtime_error on a malformed proof or constraint
 // program.  st.aux is the prover's business and is not looked at.
 int air_verify_host(const uint8_t* proof_bytes, size_t len, const AirStatement& st, const ProofOptionsHost& opt);

@@ -1,0 +1,24 @@
+// Derived main-trace columns of a program AIR on the device (include/stark252_hip.h sp_air_main_desc): per-row terms from a
+// straight-line program over the main columns that exist already, then what each kind needs on top - a zero guard in front of the
+// chunk's one batch inversion (INV_OR_ZERO), the bits of a value (BIT).  VALUE, SUM and PRODUCT columns go on through
+// air_aux_apply_den and air_aux_scan (air_aux_kernels.h).  One lane per row, 256-lane blocks, every store coalesced into a column.
+#pragma once
+#include "air_aux_kernels.h"
+
+namespace sp {
+
+// One thread per row: the program once (an AirOpDev list with slots, the OUT codes of air_aux_kernels.h): OUT a < AIR_AUX_DEN_TAG
+// stores N of chunk column a at cols[a * n + i], OUT AIR_AUX_DEN_TAG + s stores into workspace slot s at ws[s * n + i] - a
+// denominator, the N of an INV_OR_ZERO column or the N of a BIT group.  trace: [main_cols][n] natural order, of which the inputs and
+// the derived columns of earlier chunks exist; LOAD a = row shift, b = column: row (i + a) mod n.
+int air_main_terms(hipStream_t st, const fe* trace, uint64_t n, const AirOpDev* ops, uint32_t n_ops, const fe* consts, fe* cols, fe* ws);
+// INV_OR_ZERO, before the batch inversion: for k < n_inv, with (slot, col) = tab[2 k], tab[2 k + 1]: where ws[slot * n + i] is zero it
+// becomes one and cols[col * n + i] = 0, elsewhere cols[col * n + i] = 1.  The inversion then meets no zero of these, and
+// air_aux_apply_den leaves 0 or 1 / N in the column.
+int air_main_zero_guard(hipStream_t st, fe* ws, fe* cols, const uint32_t* tab, uint32_t n_inv, uint64_t n);
+// BIT: group g < n_groups is gtab[3 g .. 3 g + 2] = (slot, first, count): the value ws[slot * n + i] leaves Montgomery form once, and for
+// e in [first, first + count), with (col, bit) = etab[2 e], etab[2 e + 1] (bit <= 251): cols[col * n + i] = that bit of its canonical
+// integer, as the field element 0 or 1.
+int air_main_bits(hipStream_t st, const fe* ws, fe* cols, const uint32_t* gtab, const uint32_t* etab, uint32_t n_groups, uint64_t n);
+
+}  // namespace sp

@@ -90,6 +90,18 @@ uint64_t sp_air_stride_size(void) { return sizeof(sp_air_stride); }
 uint64_t sp_air_stride_desc_size(void) { return sizeof(sp_air_stride_desc); }
 uint64_t sp_air_ext_size(void) { return sizeof(sp_air_ext); }
 uint64_t sp_air_boundary_desc_size(void) { return sizeof(sp_air_boundary_desc); }
+uint64_t sp_air_main_desc_size(void) { return sizeof(sp_air_main_desc); }
+// The decoder's verdict on a main-trace program for this AIR and n rows (sp::air_statement_from_c), without a context.
+int sp_air_main_check(const sp_air_desc* d, const sp_air_main_desc* mp, uint64_t n) {
+    if (!d || !mp) return SP_E_INVALID_ARG;
+    try {
+        sp::AirStatement st;
+        const std::string refused = sp::air_statement_from_c(d, nullptr, nullptr, nullptr, nullptr, false, n, st, mp);
+        if (refused.empty()) return SP_OK;
+        sp_set_error("sp_air_main_check: " + refused);
+        return st.unsupported ? SP_E_UNSUPPORTED : SP_E_INVALID_ARG;
+    } catch (const std::exception& e) { sp_set_error(e.what()); return SP_E_INVALID_ARG; }
+}
 int sp_air_stride_limits(uint32_t out[4]) {
     if (!out) return SP_E_INVALID_ARG;
     out[0] = sp::AIR_MAX_STRIDE_CLASSES; out[1] = sp::AIR_MAX_STRIDE_EXEMPT_KINDS; out[2] = out[3] = 0u;

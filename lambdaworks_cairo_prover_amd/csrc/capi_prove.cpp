@@ -369,8 +369,9 @@ namespace {
 // take no single parts beside it).
 struct AirParts {
     const sp_air_aux_desc* aux; const sp_air_periodic_desc* periodic; const sp_air_stride_desc* strides; const sp_air_boundary_desc* bvals; bool aux_reads_periodic;
-    static AirParts of_ext(const sp_air_ext* ext, const sp_air_boundary_desc* bvals, bool aux_reads_periodic) {
-        return AirParts{ext ? ext->aux : nullptr, ext ? ext->periodic : nullptr, ext ? ext->strides : nullptr, bvals, aux_reads_periodic};
+    const sp_air_main_desc* main;   // (the _main entry points: the trace argument then holds the input columns only)
+    static AirParts of_ext(const sp_air_ext* ext, const sp_air_boundary_desc* bvals, bool aux_reads_periodic, const sp_air_main_desc* main = nullptr) {
+        return AirParts{ext ? ext->aux : nullptr, ext ? ext->periodic : nullptr, ext ? ext->strides : nullptr, bvals, aux_reads_periodic, main};
     }
 };
 bool ext_ok(const sp_air_ext* ext) {
@@ -379,10 +380,10 @@ bool ext_ok(const sp_air_ext* ext) {
     return !bad;
 }
 int decode(const char* who, const sp_air_desc* d, const AirParts& p, uint64_t n, sp::AirStatement& st) {
-    const std::string refused = sp::air_statement_from_c(d, p.aux, p.periodic, p.strides, p.bvals, p.aux_reads_periodic, n, st);
+    const std::string refused = sp::air_statement_from_c(d, p.aux, p.periodic, p.strides, p.bvals, p.aux_reads_periodic, n, st, p.main);
     if (refused.empty()) return SP_OK;
     sp_set_error(std::string(who) + ": " + refused);
-    return SP_E_INVALID_ARG;
+    return st.unsupported ? SP_E_UNSUPPORTED : SP_E_INVALID_ARG;
 }
 
 int air_prove_body(sp_ctx* c, const sp_air_desc* d, const AirParts& p, const uint8_t* main_trace, uint64_t n, const sp_proof_options* opt, uint8_t** proof_out,
@@ -463,6 +464,31 @@ int sp_air_check_trace_pub(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ex
                            const sp_proof_options* opt, const uint8_t* rap, sp_air_violation* out, uint32_t cap, uint32_t* n_out) {
     if (!ext_ok(ext)) return SP_E_INVALID_ARG;
     return air_check_trace_body(c, d, AirParts::of_ext(ext, bv, true), main_trace, n, opt, rap, out, cap, n_out);
+}
+
+// sp_air_prove_pub / sp_air_check_trace_pub from the input columns of a main-trace program: the device derives the other main columns.
+int sp_air_prove_main(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const sp_air_boundary_desc* bv, const sp_air_main_desc* mp, const void* inputs,
+                      uint64_t n, const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len) {
+    if (!mp || !ext_ok(ext)) return SP_E_INVALID_ARG;
+    return air_prove_body(c, d, AirParts::of_ext(ext, bv, true, mp), static_cast<const uint8_t*>(inputs), n, opt, proof_out, proof_len);
+}
+int sp_air_check_trace_main(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const sp_air_boundary_desc* bv, const sp_air_main_desc* mp, const void* inputs,
+                            uint64_t n, const sp_proof_options* opt, const uint8_t* rap, sp_air_violation* out, uint32_t cap, uint32_t* n_out) {
+    if (!mp || !ext_ok(ext)) return SP_E_INVALID_ARG;
+    return air_check_trace_body(c, d, AirParts::of_ext(ext, bv, true, mp), static_cast<const uint8_t*>(inputs), n, opt, rap, out, cap, n_out);
+}
+int sp_air_main_trace(sp_ctx* c, const sp_air_desc* d, const sp_air_main_desc* mp, const void* inputs, uint64_t n, uint8_t* rows_out) {
+    if (!c || !d || !mp || !inputs || !rows_out) return SP_E_INVALID_ARG;
+    try {
+        sp::AirStatement st;
+        // (the table does not depend on the auxiliary segment: the statement is judged as one without, whatever the AIR's aux_kind)
+        sp_air_desc main_only = *d;
+        main_only.aux_cols = 0; main_only.aux_kind = 0;
+        SP_TRY(decode("sp_air_main_trace", &main_only, AirParts::of_ext(nullptr, nullptr, false, mp), n, st));
+        if (sp_log2_exact(n) < 0) { sp_set_error("sp_air_main_trace: n must be a power of two"); return SP_E_INVALID_ARG; }
+        c->prewarm_cancel.store(0, std::memory_order_release);
+        return sp::air_main_trace(c, st, static_cast<const uint8_t*>(inputs), n, rows_out);
+    } catch (const std::exception& e) { sp_set_error(e.what()); return SP_E_INVALID_ARG; }
 }
 
 }  // extern "C"

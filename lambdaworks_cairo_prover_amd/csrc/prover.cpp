@@ -611,6 +611,177 @@ int StarkProver::commit_aux_program(const AirStatement& st, const std::vector<fe
     return SP_OK;
 }
 
+// The main-trace program.  Chunks as above (at most max(1, AUXP_CHUNK_ELEMS / n) columns), and a chunk also ends before a column
+// that reads a derived column of the chunk itself: LOADs wrap around the trace, so a column must be complete - its scan included -
+// before anything reads it, and the stream orders one chunk behind the other.  Workspace slots of a chunk, n elements each: first
+// the ones the batch inversion takes (the D of VALUE / SUM / PRODUCT columns, the guarded N of INV_OR_ZERO columns), then one per
+// group of BIT columns that share their N.  od_.auxp_buf / od_.auxp_ws: the auxiliary program runs later on the same stream.
+int StarkProver::build_main_program(const AirStatement& st, const uint8_t* inputs) {
+    const AirMainHost& mp = *st.main;
+    const uint32_t I = mp.input_cols, K = (uint32_t)mp.cols.size();
+    if (!inputs) return SP_E_INVALID_ARG;
+    if (stage_ != Stage::Setup || I + K != Cm_) { sp_set_error("commit_main_program: wrong segment order, or input and derived columns are not the main segment"); return SP_E_STATE; }
+    SP_HIP_CHECK(hipSetDevice(c_->device));
+    binary_cols_hint_ = 0;
+    for (double& x : c_->upload_stats) x = 0.0;
+    leaf_head_done_ = false;
+    const uint32_t chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(K, AUXP_CHUNK_ELEMS / n_));
+    const uint64_t nb = air_aux_scan_blocks(n_);
+    const uint32_t n_src = (uint32_t)mp.ops.size();
+    struct Chunk {
+        uint32_t k0 = 0, kc = 0, n_inv = 0, n_slots = 0;            // n_inv: slots the batch inversion takes; n_slots: those and the BIT groups'
+        std::vector<AirOpDev> ops;
+        std::vector<uint32_t> kinds, den_col, guard, gtab, etab;     // kinds: 0 product / 1 sum per column (read for scanned columns only)
+        std::vector<std::pair<uint32_t, uint32_t>> scans;            // runs of SUM / PRODUCT columns: (first, count)
+        size_t o_ops = 0, o_kinds = 0, o_den = 0, o_guard = 0, o_gtab = 0, o_etab = 0;
+    };
+    std::vector<Chunk> chunks;
+    uint32_t max_slots = 0, max_inv = 0;
+    for (uint32_t k0 = 0; k0 < K;) {
+        Chunk ch;
+        ch.k0 = k0;
+        std::vector<std::vector<uint32_t>> outs(n_src);
+        struct BitGroup { uint32_t num_op; std::vector<uint32_t> entries; };
+        std::vector<BitGroup> groups;
+        for (; ch.kc < chunk && k0 + ch.kc < K && mp.cols[k0 + ch.kc].reads <= k0; ++ch.kc) {
+            const AirMainColumnHost& c = mp.cols[k0 + ch.kc];
+            const bool scanned = c.kind == SP_AIR_MAIN_SUM || c.kind == SP_AIR_MAIN_PRODUCT;
+            ch.kinds.push_back(c.kind == SP_AIR_MAIN_SUM ? 1u : 0u);
+            if (scanned) {
+                if (!ch.scans.empty() && ch.scans.back().first + ch.scans.back().second == ch.kc) ++ch.scans.back().second;
+                else ch.scans.emplace_back(ch.kc, 1u);
+            }
+            if (c.kind == SP_AIR_MAIN_BIT) {
+                size_t g = 0;
+                while (g < groups.size() && groups[g].num_op != c.num_op) ++g;
+                if (g == groups.size()) groups.push_back(BitGroup{c.num_op, {}});
+                groups[g].entries.push_back(ch.kc);
+                groups[g].entries.push_back(c.bit);
+                continue;
+            }
+            if (c.kind == SP_AIR_MAIN_INV_OR_ZERO) {
+                outs[c.num_op].push_back(AIR_AUX_DEN_TAG + ch.n_inv);
+                ch.guard.push_back(ch.n_inv); ch.guard.push_back(ch.kc);
+                ch.den_col.push_back(ch.kc);
+                ++ch.n_inv;
+                continue;
+            }
+            outs[c.num_op].push_back(ch.kc);
+            if (c.den_op != SP_AIR_AUX_NO_DEN) { outs[c.den_op].push_back(AIR_AUX_DEN_TAG + ch.n_inv); ch.den_col.push_back(ch.kc); ++ch.n_inv; }
+        }
+        ch.n_slots = ch.n_inv;
+        for (const BitGroup& g : groups) {
+            outs[g.num_op].push_back(AIR_AUX_DEN_TAG + ch.n_slots);
+            ch.gtab.push_back(ch.n_slots++); ch.gtab.push_back((uint32_t)ch.etab.size() / 2); ch.gtab.push_back((uint32_t)g.entries.size() / 2);
+            ch.etab.insert(ch.etab.end(), g.entries.begin(), g.entries.end());
+        }
+        // the program with an OUT behind every op whose value is wanted, slots by air_assign_slots (as commit_aux_program)
+        std::vector<AirOpHost> ext;
+        std::vector<uint32_t> at(n_src);
+        for (uint32_t t = 0; t < n_src; ++t) {
+            AirOpHost o = mp.ops[t];
+            if (o.op >= 2 && o.op <= 4) { o.a = at[o.a]; o.b = at[o.b]; }
+            at[t] = (uint32_t)ext.size();
+            ext.push_back(o);
+            for (uint32_t code : outs[t]) ext.push_back(AirOpHost{5, code, at[t]});
+        }
+        SP_TRY(air_assign_slots(ext, ch.ops, "main program: more than 64 values alive at once"));
+        max_slots = std::max(max_slots, ch.n_slots);
+        max_inv = std::max(max_inv, ch.n_inv);
+        k0 += ch.kc;
+        chunks.push_back(std::move(ch));
+    }
+    // --- one upload: the constants, per chunk its ops and tables
+    UploadLayout lay;
+    auto words = [&](const std::vector<uint32_t>& v) { return lay.place(sizeof(uint32_t) * std::max<size_t>(1, v.size())); };
+    const size_t o_consts = lay.place(sizeof(fe) * std::max<size_t>(1, mp.consts.size()));
+    for (Chunk& ch : chunks) {
+        ch.o_ops = lay.place(sizeof(AirOpDev) * std::max<size_t>(1, ch.ops.size()));
+        ch.o_kinds = words(ch.kinds); ch.o_den = words(ch.den_col); ch.o_guard = words(ch.guard); ch.o_gtab = words(ch.gtab); ch.o_etab = words(ch.etab);
+    }
+    const size_t bytes = lay.bytes;
+    SP_TRY(grow(od_.auxp_buf, bytes));
+    std::vector<uint8_t>& up = h_auxp_up_;
+    up.assign(bytes, 0);
+    fill_consts_then_rap(up.data() + o_consts, mp.consts, {});
+    auto put = [&](size_t at, const std::vector<uint32_t>& v) { if (!v.empty()) std::memcpy(up.data() + at, v.data(), sizeof(uint32_t) * v.size()); };
+    for (const Chunk& ch : chunks) {
+        if (!ch.ops.empty()) std::memcpy(up.data() + ch.o_ops, ch.ops.data(), sizeof(AirOpDev) * ch.ops.size());
+        put(ch.o_kinds, ch.kinds); put(ch.o_den, ch.den_col); put(ch.o_guard, ch.guard); put(ch.o_gtab, ch.gtab); put(ch.o_etab, ch.etab);
+    }
+    // --- workspace: [max_slots][n] slots, [max_inv][n] batch-inversion scratch, [chunk][nb] scan block totals
+    SP_TRY(grow(od_.auxp_ws, ((uint64_t)max_slots + max_inv) * n_ + (uint64_t)chunk * nb));
+    SP_TRY(ensure_host_flags());
+    // --- ingest: the plain staged copy (the inputs are a small part of the table; their raw rows sit in the segment's LDE area,
+    //     which is written only by the transforms behind the last chunk), then rows -> columns [0, I)
+    if (mp.input_location == 1) {
+        SP_TRY(rows_to_columns(c_->stream, c_->enc, inputs, n_, I, d_trace_, n_));
+    } else {
+        uint8_t* raw = reinterpret_cast<uint8_t*>(d_lde_);
+        SP_HIP_CHECK(hipMemcpyAsync(raw, inputs, (size_t)n_ * I * 32, hipMemcpyHostToDevice, c_->stream));
+        SP_TRY(rows_to_columns(c_->stream, c_->enc, raw, n_, I, d_trace_, n_));
+    }
+    SP_HIP_CHECK(hipMemcpyAsync(od_.auxp_buf.p, up.data(), bytes, hipMemcpyHostToDevice, c_->stream));
+    SP_HIP_CHECK(hipMemsetAsync(c_->d_flag, 0, sizeof(int), c_->stream));
+    const fe* consts_dev = reinterpret_cast<const fe*>(od_.auxp_buf.p + o_consts);
+    fe* ws = od_.auxp_ws.p;
+    fe* scratch = ws + (uint64_t)max_slots * n_;
+    fe* block_tot = scratch + (uint64_t)max_inv * n_;
+    auto tab = [&](size_t at) { return reinterpret_cast<const uint32_t*>(od_.auxp_buf.p + at); };
+    for (const Chunk& ch : chunks) {
+        fe* cols = d_trace_ + (uint64_t)(I + ch.k0) * n_;
+        SP_TRY(air_main_terms(c_->stream, d_trace_, n_, reinterpret_cast<const AirOpDev*>(od_.auxp_buf.p + ch.o_ops), (uint32_t)ch.ops.size(), consts_dev, cols, ws));
+        SP_TRY(air_main_zero_guard(c_->stream, ws, cols, tab(ch.o_guard), (uint32_t)ch.guard.size() / 2, n_));
+        if (ch.n_inv) {
+            SP_TRY(batch_inverse(c_->stream, ws, scratch, (uint64_t)ch.n_inv * n_, c_->d_flag));
+            SP_TRY(air_aux_apply_den(c_->stream, cols, ws, tab(ch.o_den), ch.n_inv, n_));
+        }
+        SP_TRY(air_main_bits(c_->stream, ws, cols, tab(ch.o_gtab), tab(ch.o_etab), (uint32_t)ch.gtab.size() / 3, n_));
+        for (const auto& run : ch.scans)
+            SP_TRY(air_aux_scan(c_->stream, cols + (uint64_t)run.first * n_, n_, run.second, tab(ch.o_kinds) + run.first, block_tot));
+    }
+    // the zero-denominator flag rides behind the columns; whoever reads the root (or the table) back waits for it
+    SP_HIP_CHECK(hipMemcpyAsync(&host_flags().auxp_zero_den, c_->d_flag, sizeof(int), hipMemcpyDeviceToHost, c_->stream));
+    return SP_OK;
+}
+
+static const char* const MAIN_PROGRAM_ZERO_DEN = "commit_main_program: a derived main column's denominator is zero on some row";
+
+int StarkProver::commit_main_program(const AirStatement& st, const uint8_t* inputs, uint8_t root_out[32]) {
+    if (!root_out) return SP_E_INVALID_ARG;
+    const double t0 = wall_ms();
+    int rc = build_main_program(st, inputs);
+    const double host_ms = wall_ms() - t0;
+    if (rc == SP_OK) rc = launch_aux_presort();
+    if (rc == SP_OK) rc = commit_segment_resident(0, Cm_, root_out);
+    if (rc != SP_OK) {   // (nothing returns while a copy from the caller's inputs may still be in flight)
+        (void)hipStreamSynchronize(c_->stream);
+        (void)hipGetLastError();
+        return rc;
+    }
+    if (host_flags().auxp_zero_den) { sp_set_error(MAIN_PROGRAM_ZERO_DEN); return SP_E_ZERO_INVERSE; }
+    return finish_upload_stats(0, st.main->input_location == 1 ? 0 : (uint64_t)n_ * st.main->input_cols * 32, 0.0, host_ms, 0);
+}
+
+int StarkProver::main_program_table(const AirStatement& st, const uint8_t* inputs, uint8_t* rows_out) {
+    if (!rows_out) return SP_E_INVALID_ARG;
+    int rc = build_main_program(st, inputs);
+    // the columns in the context encoding, through the (unused) LDE area, then transposed on the host
+    uint8_t* enc_dev = reinterpret_cast<uint8_t*>(d_lde_);
+    std::vector<uint8_t> by_col;
+    if (rc == SP_OK) rc = encode_elements(c_->stream, c_->enc, d_trace_, (uint64_t)Cm_ * n_, enc_dev);
+    if (rc == SP_OK) { by_col.resize((size_t)Cm_ * n_ * 32); rc = readback(by_col.data(), enc_dev, by_col.size()); }
+    if (rc != SP_OK) {
+        (void)hipStreamSynchronize(c_->stream);
+        (void)hipGetLastError();
+        return rc;
+    }
+    if (host_flags().auxp_zero_den) { sp_set_error(MAIN_PROGRAM_ZERO_DEN); return SP_E_ZERO_INVERSE; }
+    for (uint32_t c = 0; c < Cm_; ++c)
+        for (uint64_t i = 0; i < n_; ++i) std::memcpy(rows_out + ((size_t)i * Cm_ + c) * 32, by_col.data() + ((size_t)c * n_ + i) * 32, 32);
+    return SP_OK;
+}
+
 // sum_q A[q] y^rev(q) for `vectors` arrays of 2^k elements and `points` points, by repeated folding
 // (DESIGN.md "Out-of-domain evaluation"): one level maps M elements to M >> l.
 // scratch: at least 3 * 2^k elements (two ping-pong buffers and the per-level power tables).

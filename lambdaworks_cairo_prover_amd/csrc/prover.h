@@ -6,6 +6,7 @@
 #include "air_desc.h"
 #include "aux_kernels.h"
 #include "air_aux_kernels.h"
+#include "air_main_kernels.h"
 #include "trace_kernels.h"
 #include "cairo_host.h"
 #include <vector>
@@ -105,6 +106,15 @@ class StarkProver : public sp_deletable {
     // commit_segment_resident.  The columns the program may read with op 6 (a = row shift, b = column:
     // values[(i + a) mod period]) are st.aux_periodic().
     int commit_aux_program(const AirStatement& st, const std::vector<fe>& rap, uint8_t root_out[32]);
+    // round 1, main segment of a program AIR with a main-trace program (st.main, present and validated: air_statement_from_c) in place
+    // of commit_trace(0, ..): `inputs` - row-major n x input_cols in the context encoding, host or device memory by
+    // st.main->input_location - become columns [0, input_cols); the derived columns follow in index order, in chunks that end where
+    // the workspace does or before a column that reads one of the chunk's own (a shifted read needs the whole column): per chunk one
+    // pass of the interpreter, one batch inversion (behind the zero guard of the INV_OR_ZERO columns), the bits, the scans; then
+    // commit_segment_resident.  A zero denominator is SP_E_ZERO_INVERSE once the root is back.  Every rank builds every column.
+    int commit_main_program(const AirStatement& st, const uint8_t* inputs, uint8_t root_out[32]);
+    // the same table without the commitment, to host memory: row-major n x main_cols, context encoding (sp_air_main_trace)
+    int main_program_table(const AirStatement& st, const uint8_t* inputs, uint8_t* rows_out);
     // round 2: constraint composition, H1/H2 split, LDE and commitment
     int composition(const fe rap[3], const std::vector<BoundaryConstraint>& bcs, const std::vector<fe>& b_alpha,
                     const std::vector<fe>& b_beta, const std::vector<fe>& t_alpha, const std::vector<fe>& t_beta,
@@ -202,6 +212,9 @@ class StarkProver : public sp_deletable {
         return commit_local(cols_dev, stride, ncols, Nl_, lde_order(), tree, root_out);
     }
     int commit_segment_resident(int segment, uint32_t cols, uint8_t root_out[32]);
+    // the ingest and the derived columns of commit_main_program, queued on the compute stream; the zero-denominator flag is on its way
+    // to host_flags().auxp_zero_den behind them
+    int build_main_program(const AirStatement& st, const uint8_t* inputs);
     int commit_trace_pipelined(int segment, const uint8_t* rows_host, uint32_t table_cols, uint8_t root_out[32], uint32_t c_begin = 0, uint32_t c_count = 0,
                                bool window_only = false, uint32_t binary_cols = 0);
     // The first `binary_cols` columns of the main segment hold only 0 and 1 (the sixteen instruction flags of a Cairo trace, reference
@@ -444,6 +457,10 @@ int cairo_prove(sp_ctx* ctx, const uint8_t* main_trace, uint64_t n, uint32_t col
 // encoding (host memory).  round_ms: device time of rounds 1 - 4 in [1..4], as cairo_prove.
 int air_prove(sp_ctx* ctx, const AirStatement& st, const uint8_t* main_trace, uint64_t n, const ProofOptionsHost& opt, std::vector<uint8_t>& proof_out,
               float round_ms[5]);
+// With st.main (a main-trace program) main_trace holds the input columns only - row-major n x st.main->input_cols, host or device memory
+// by st.main->input_location - here and in air_check_trace.  air_main_trace: the table that program builds, row-major n x main_cols in
+// the context encoding, to host memory; no commitment.
+int air_main_trace(sp_ctx* ctx, const AirStatement& st, const uint8_t* inputs, uint64_t n, uint8_t* rows_out);
 // Which constraints of a program AIR a trace breaks, and where (sp_air_check_trace): round 1 as air_prove runs it - the same ingest and
 // auxiliary builders -, then StarkProver::check_trace_air; no proof.  rap_given (nullable): the RAP challenges, instead of the ones a
 // proof under *opt would sample; opt may be null only with them.  One GPU (SP_E_UNSUPPORTED on a context with world > 1).

@@ -262,7 +262,9 @@ static int air_round1(sp_ctx* ctx, ProofRun& run, const AirStatement& st, const 
     StarkProver* P = &run.H->prover;
     Transcript& tr = run.tr;
     uint8_t root[32];
-    SP_TRY(P->commit_trace(0, main_trace, air.main_cols, root));
+    // (with a main-trace program `main_trace` holds the input columns only, in host or device memory, and the device derives the rest)
+    if (st.main) SP_TRY(P->commit_main_program(st, main_trace, root));
+    else SP_TRY(P->commit_trace(0, main_trace, air.main_cols, root));
     run.trace_committed(root);
     rap.assign(air.n_rap, fe_zero());
     for (auto& x : rap) x = tr.to_field();
@@ -306,6 +308,20 @@ static int air_round1(sp_ctx* ctx, ProofRun& run, const AirStatement& st, const 
         run.trace_committed(root);
     }
     return SP_OK;
+}
+
+// The main segment a statement's main-trace program builds from `inputs`, without a commitment (sp_air_main_trace): the prover at
+// this shape under the smallest options, the builder of commit_main_program, the table back on the host.
+int air_main_trace(sp_ctx* ctx, const AirStatement& st, const uint8_t* inputs, uint64_t n, uint8_t* rows_out) {
+    try {
+        if (!st.main) { sp_set_error("air_main_trace: the statement has no main program"); return SP_E_INVALID_ARG; }
+        ProofRun run;
+        SP_TRY(begin_proof(ctx, n, st.air.main_cols, st.air.aux_cols, false, ProofOptionsHost{2, 1, 3, 0}, run));
+        return run.H->prover.main_program_table(st, inputs, rows_out);
+    } catch (const std::exception& e) {
+        sp_set_error(std::string("air_main_trace: ") + e.what());
+        return SP_E_INVALID_ARG;
+    }
 }
 
 // boundary_constraints(rap_challenges) (traits.rs:44-47): the AIR as everything behind round 1 sees it - the descriptor itself, or, with

@@ -37,6 +37,12 @@ struct Parts {
     sp_air_op bops[3] = {{1, 0, 1, 0, 0}, {1, 0, 0, 0, 0}, {3, 0, 0, 1, 0}};   // gamma, 77, gamma - 77
     sp_air_boundary_value bvalues[2] = {{1, 2, 2, 0}, {0, 2, SP_AIR_AUX_NO_DEN, 0}};
     sp_air_boundary_desc bv{};
+    // a main program (use 'm'): x the one input; inv = INV_OR_ZERO(x), f = (1 - x inv) / 1, bit 3 of x, the running sum of f, a product of x over x
+    Felt mconsts[1] = {felt(1)};
+    sp_air_op mops[7] = {{0, 0, 0, 0, 0}, {0, 0, 0, 1, 0}, {4, 0, 0, 1, 0}, {1, 0, 0, 0, 0}, {3, 0, 3, 2, 0}, {0, 0, 7, 2, 0}, {0, 0, 0, 0, 0}};
+    sp_air_main_column mcols[5] = {{SP_AIR_MAIN_INV_OR_ZERO, 0, SP_AIR_AUX_NO_DEN, 0}, {SP_AIR_MAIN_VALUE, 4, 3, 0}, {SP_AIR_MAIN_BIT, 0, SP_AIR_AUX_NO_DEN, 3},
+                                   {SP_AIR_MAIN_SUM, 5, SP_AIR_AUX_NO_DEN, 0}, {SP_AIR_MAIN_PRODUCT, 0, 6, 0}};
+    sp_air_main_desc mp{};
     Parts() {
         for (uint32_t j = 0; j < 17; ++j) many_cols[j] = sp_air_aux_column{SP_AIR_AUX_SORTED, j, j, 16};
         for (int j = 0; j < 8; ++j) keys[j] = felt(100 + j);
@@ -49,19 +55,23 @@ struct Parts {
         per.n_cols = 1; per.cols = pcols;
         sd.n = 1; sd.strides = strides;
         bv.n_ops = 3; bv.ops = bops; bv.n_consts = 1; bv.consts = bconsts[0].b; bv.n_values = 2; bv.values = bvalues;
+        mp.size = sizeof(sp_air_main_desc); mp.input_cols = 1; mp.n_ops = 7; mp.ops = mops; mp.n_consts = 1; mp.consts = mconsts[0].b; mp.n_cols = 5; mp.cols = mcols;
     }
+    void with_main() { d.main_cols = 6; }
     void sorted() { d.aux_cols = 3; aux.n_ops = 5; aux.ops = sort_ops; aux.n_cols = 3; aux.cols = sort_cols; }
     void many(uint32_t groups) { d.aux_cols = groups; aux.n_ops = 17; aux.ops = many_ops; aux.n_cols = groups; aux.cols = many_cols; }
 };
 
-// use: which parts go to the decoder (a x p s b, upper case P: the auxiliary program may read the periodic columns)
+// use: which parts go to the decoder (x p s b m, upper case P: the auxiliary program may read the periodic columns; m: the main
+// program, for which the AIR gets its six main columns first)
 void run(const char* label, const char* use, bool want_ok, const std::function<void(Parts&)>& patch) {
     Parts p;
+    if (std::strchr(use, 'm')) p.with_main();
     patch(p);
     auto has = [&](char c) { return std::strchr(use, c) != nullptr; };
     sp::AirStatement st;
     const std::string refused = sp::air_statement_from_c(&p.d, has('x') ? &p.aux : nullptr, has('p') ? &p.per : nullptr, has('s') ? &p.sd : nullptr,
-                                                         has('b') ? &p.bv : nullptr, has('P'), 16, st);
+                                                         has('b') ? &p.bv : nullptr, has('P'), 16, st, has('m') ? &p.mp : nullptr);
     const bool ok = refused.empty();
     if (ok != want_ok) { ++failures; std::printf("FAIL %-44s wanted %s, got %s\n", label, want_ok ? "accepted" : "refused", ok ? "accepted" : refused.c_str()); return; }
     std::printf("ok   %-44s %s\n", label, ok ? "accepted" : refused.substr(0, 60).c_str());
@@ -69,7 +79,12 @@ void run(const char* label, const char* use, bool want_ok, const std::function<v
     // the model on what was accepted: stride plan and zerofier, periodic columns as polynomials, boundary values under a challenge
     sp::AirStridePlan plan;
     bool fine = sp::air_stride_plan(st.air, 16, plan) && st.aux.has_value() == has('x') && st.periodic.has_value() == has('p') && st.bvals.has_value() == has('b') &&
-                (st.aux_periodic() != nullptr) == (has('P') && has('p'));
+                (st.aux_periodic() != nullptr) == (has('P') && has('p')) && st.main.has_value() == has('m') && !st.unsupported;
+    if (st.main) {   // what the prover's chunking reads: which derived columns each column needs, and the bit
+        const auto& c = st.main->cols;
+        fine = fine && c.size() == 5 && c[0].reads == 0 && c[1].reads == 1 && c[2].reads == 0 && c[2].bit == p.mcols[2].pad && c[3].reads == 2 && c[4].reads == 0 &&
+               st.main->input_cols == 1 && st.main->ops.size() == 7 && st.main->consts.size() == 1;
+    }
     const fe x = fe_from_u64(5);
     for (const sp::AirStrideHost& c : plan.classes) { fe Z, E; sp::air_stride_eval(c.period, c.offset, 1, 16, x, Z, E); fine = fine && !fe_is_zero(Z); }
     if (st.periodic)
@@ -151,6 +166,40 @@ int main() {
     run("bvals: den_op beyond the program", "xb", false, [](Parts& p) { p.bvalues[0].den_op = 3; });
     run("bvals: boundary >= n_boundary", "xb", false, [](Parts& p) { p.bvalues[0].boundary = 2; });
     run("bvals: a boundary named twice", "xb", false, [](Parts& p) { p.bvalues[1].boundary = 1; });
+    // ---- main programs
+    run("main program", "m", true, none);
+    run("main program beside everything", "xpsbPm", true, [](Parts& p) { p.aux.n_ops = 4; });
+    run("main program: inputs on the device", "m", true, [](Parts& p) { p.mp.input_location = 1; });
+    run("main program: bit 251", "m", true, [](Parts& p) { p.mcols[2].pad = 251; });
+    run("main: size", "m", false, [](Parts& p) { p.mp.size -= 4; });
+    run("main: null ops", "m", false, [](Parts& p) { p.mp.ops = nullptr; });
+    run("main: null consts", "m", false, [](Parts& p) { p.mp.consts = nullptr; });
+    run("main: null cols", "m", false, [](Parts& p) { p.mp.cols = nullptr; });
+    run("main: no input column", "m", false, [](Parts& p) { p.mp.input_cols = 0; p.mp.n_cols = 6; });
+    run("main: columns do not add up", "m", false, [](Parts& p) { p.mp.n_cols = 4; });
+    run("main: input_cols 2^32 - 1", "m", false, [](Parts& p) { p.mp.input_cols = 0xFFFFFFFFu; p.mp.n_cols = 7; });
+    run("main: input_location 2", "m", false, [](Parts& p) { p.mp.input_location = 2; });
+    run("main: no ops", "m", false, [](Parts& p) { p.mp.n_ops = 0; });
+    run("main: 2^32 - 1 ops", "m", false, [](Parts& p) { p.mp.n_ops = 0xFFFFFFFFu; });
+    run("main: 4097 constants", "m", false, [](Parts& p) { p.mp.n_consts = 4097; });
+    run("main: unknown kind", "m", false, [](Parts& p) { p.mcols[1].kind = 5; });
+    run("main: bit 252", "m", false, [](Parts& p) { p.mcols[2].pad = 252; });
+    run("main: a denominator on INV_OR_ZERO", "m", false, [](Parts& p) { p.mcols[0].den_op = 3; });
+    run("main: a denominator on BIT", "m", false, [](Parts& p) { p.mcols[2].den_op = 3; });
+    run("main: OUT", "m", false, [](Parts& p) { p.mops[4].op = 5; });
+    run("main: PERIODIC", "m", false, [](Parts& p) { p.mops[1].op = 6; });
+    run("main: op 7", "m", false, [](Parts& p) { p.mops[4].op = 7; });
+    run("main: operand is itself", "m", false, [](Parts& p) { p.mops[2].a = 2; });
+    run("main: operand is later", "m", false, [](Parts& p) { p.mops[2].b = 6; });
+    run("main: shift 8", "m", false, [](Parts& p) { p.mops[5].a = 8; });
+    run("main: LOAD beyond the main columns", "m", false, [](Parts& p) { p.mops[5].b = 6; });
+    run("main: constant beyond consts", "m", false, [](Parts& p) { p.mops[3].a = 1; });
+    run("main: a column loads itself", "m", false, [](Parts& p) { p.mops[0].b = 1; });
+    run("main: a column loads a later one", "m", false, [](Parts& p) { p.mops[1].b = 4; });
+    run("main: num_op beyond the program", "m", false, [](Parts& p) { p.mcols[3].num_op = 7; });
+    run("main: den_op beyond the program", "m", false, [](Parts& p) { p.mcols[1].den_op = 7; });
+    run("main: aux_kind 1", "m", false, [](Parts& p) { p.d.aux_kind = 1; });
+    run("main: aux_kind 2", "m", false, [](Parts& p) { p.d.aux_kind = 2; });
     run("no main column", "", false, [](Parts& p) { p.d.main_cols = 0; p.ops[2] = sp_air_op{1, 0, 0, 0, 0}; });
     run("1025 columns", "", false, [](Parts& p) { p.d.main_cols = 1024; p.ops[2] = sp_air_op{1, 0, 0, 0, 0}; });
     std::printf("%s\n", failures ? "FAILED" : "all verdicts as expected");
