@@ -79,7 +79,8 @@ const char* sp_version(void);
  * and no call, and a binding finds a build without them by probing the symbols; so did sp_air_prove_ext, sp_air_verify_ext, sp_air_check_trace_ext,
  * sp_air_stride_size, sp_air_stride_desc_size, sp_air_ext_size, sp_air_stride_limits, sp_air_stride_eval and sp_air_stride_table, and after them sp_air_prove_pub, sp_air_verify_pub,
  * sp_air_check_trace_pub, sp_air_boundary_desc_size and sp_air_boundary_resolve, and then sp_air_prove_main, sp_air_check_trace_main,
- * sp_air_main_trace, sp_air_main_check and sp_air_main_desc_size).  A binding compares it (and sp_air_desc_size against its own idea of the struct) when it loads the library, so
+ * sp_air_main_trace, sp_air_main_check and sp_air_main_desc_size, and last sp_air_prove_rec, sp_air_check_trace_rec, sp_air_main_trace_rec,
+ * sp_air_main_check_rec and sp_air_main_chain_limits).  A binding compares it (and sp_air_desc_size against its own idea of the struct) when it loads the library, so
  * a stale build fails at load time with "rebuild the library" instead of with a missing symbol or shifted fields later. */
 #define SP_ABI_VERSION 7
 int sp_abi_version(void);
@@ -639,7 +640,7 @@ int sp_air_boundary_resolve(const sp_air_boundary_desc* bvals, const uint8_t* ra
 /* A LOAD of b < input_cols reads an input; a LOAD of input_cols + k reads derived column k and may stand only behind (the N or D of)
  * a derived column j > k: columns are built in index order, and a column is complete before anything reads it (shifts wrap).  A column
  * whose evolution is a true recurrence - z_(i+1) a non-linear function of z_i, such as the state of a hash chain - cannot be written
- * this way and stays an input.  With a main program air->aux_kind must be 0 or SP_AIR_AUX_PROGRAM (kinds 1 and 2 read a host table of
+ * with these five kinds; it is an SP_AIR_MAIN_CHAIN column of the _rec entry points below.  With a main program air->aux_kind must be 0 or SP_AIR_AUX_PROGRAM (kinds 1 and 2 read a host table of
  * the main segment, which no longer exists: SP_E_UNSUPPORTED).  Bounds: those of sp_air_limits (65535 ops, 4096 constants, 64 live
  * values).  Malformed - size other than sizeof(sp_air_main_desc), null members, input_cols == 0 or input_cols + n_cols !=
  * air->main_cols, input_location above 1, an unknown kind, pad > 251 on a BIT, a denominator on INV_OR_ZERO or BIT, an op outside
@@ -664,6 +665,37 @@ int sp_air_check_trace_main(sp_ctx* ctx, const sp_air_desc* air, const sp_air_ex
  * nothing is committed.  sp_air_main_check (host only): SP_OK, or the decoder's refusal of this program for this AIR and n rows. */
 int sp_air_main_trace(sp_ctx* ctx, const sp_air_desc* air, const sp_air_main_desc* main, const void* inputs, uint64_t n, uint8_t* rows_out);
 int sp_air_main_check(const sp_air_desc* air, const sp_air_main_desc* main, uint64_t n);
+
+/* ---- Block recurrences in a main program: the states of many independent permutations (MiMC, Poseidon, Rescue rounds; Merkle paths;
+ * hash-based signatures), each a block of s = 2^l consecutive rows seeded on its first row.  Through the _rec entry points - and only
+ * through them: everywhere else kind 5 stays an unknown kind and op 6 a malformed op - a main program may hold columns of kind */
+#define SP_AIR_MAIN_CHAIN       5  /* z(B s) = Seed(B s);  z(i + 1) = Step(i) for (i + 1) mod s != 0   (rows i = B s + t)                  */
+/* and read the periodic columns of ext->periodic with op 6: a = row shift 0 .. 7, b = periodic column k, the value values[(i + a) mod
+ * period_k] - the raw values, as the auxiliary program's table read; behind columns of every kind.
+ * A chain group is a run of w consecutive CHAIN columns, 1 <= w <= 16: pad = l + 256 j with s = 2^l the block length (1 <= l <= log2 n)
+ * and j the column's position in its group - j = 0 opens a group, the columns after it carry j = 1, 2, .. and the same l.  den_op names
+ * the column's SEED op (SP_AIR_AUX_NO_DEN is refused: a chain needs a seed), num_op its STEP op.  The seeds are evaluated on the block's
+ * first row and may read inputs, derived columns before the group and periodic columns - nothing of the group.  The steps are evaluated
+ * on the row they leave from: a LOAD of a column of the group must have shift 0 and is the state on row i; inputs and derived columns
+ * before the group at shifts 0 .. 7, wrapping modulo n; periodic columns.  The w next values are assigned together, after the whole
+ * step program has run.  Columns after the group read its columns as any earlier derived column.  No denominators: seeds and steps are
+ * polynomial (CONST, ADD, SUB, MUL) - an inverse S-box (x^(1/d)) or a division inside a step is out of scope, and so is a block seeded
+ * from the block before it (a multi-block sponge is serial across blocks).  Refused with SP_E_INVALID_ARG and a message that names the
+ * column, before anything is sized: j out of sequence or a group longer than 16, l = 0 or 2^l > n, members of a group that differ in l,
+ * a step that loads its group at a shift other than 0, a seed that loads its group, any load of a later column, a chain without a seed,
+ * op 6 naming a periodic column the statement does not have (or without ext->periodic).  Argument lists as sp_air_prove_main /
+ * sp_air_check_trace_main / sp_air_main_trace / sp_air_main_check; the last two also take the sp_air_ext (nullable) that carries the
+ * periodic columns. */
+int sp_air_prove_rec(sp_ctx* ctx, const sp_air_desc* air, const sp_air_ext* ext, const sp_air_boundary_desc* bvals, const sp_air_main_desc* main,
+                     const void* inputs, uint64_t n, const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len);
+int sp_air_check_trace_rec(sp_ctx* ctx, const sp_air_desc* air, const sp_air_ext* ext, const sp_air_boundary_desc* bvals, const sp_air_main_desc* main,
+                           const void* inputs, uint64_t n, const sp_proof_options* opt, const uint8_t* rap, sp_air_violation* out, uint32_t cap,
+                           uint32_t* n_out);
+int sp_air_main_trace_rec(sp_ctx* ctx, const sp_air_desc* air, const sp_air_ext* ext, const sp_air_main_desc* main, const void* inputs, uint64_t n,
+                          uint8_t* rows_out);
+int sp_air_main_check_rec(const sp_air_desc* air, const sp_air_ext* ext, const sp_air_main_desc* main, uint64_t n);
+/* out[0] = the most columns of a chain group (16), out[1] = the highest row shift of a LOAD or an op 6 (7) */
+int sp_air_main_chain_limits(uint32_t out[2]);
 
 /* verify::<Stark252PrimeField, A> (reference src/starks/verifier.rs:559-657) on the host CPU: 1 accept, 0 reject (also for
  * malformed proofs or descriptors). */

@@ -26,6 +26,11 @@ Derived main columns (sp_air_prove_main): AirBuilder(..., main_inputs=I) says th
 b.main (MainProgram) declares the others as row-local functions of columns that exist already - b.main.value, inv_or_zero, bit / bits,
 running_sum, product -, which the device builds before it commits the main segment.  The proof is the one of the whole table.  See
 bit_range_check and zero_count below.
+
+Block recurrences (sp_air_prove_rec): g = b.main.chain(period, seeds) declares a group of columns that hold the states of independent
+permutations, one per block of `period` rows - seeded on the block's first row, every later cell a polynomial of the row before it
+(g.state(j), g.step([...])) -, and b.main.periodic(shift, k) reads a periodic column (round constants) from the main program.  See
+mimc_blocks below.
 """
 import collections
 import ctypes
@@ -188,8 +193,9 @@ def boundary_desc(ops, consts, values):
     return d, (c_ops, c_consts, c_values)
 
 
-MAIN_VALUE, MAIN_INV_OR_ZERO, MAIN_BIT, MAIN_SUM, MAIN_PRODUCT = range(5)   # sp_air_main_column.kind
+MAIN_VALUE, MAIN_INV_OR_ZERO, MAIN_BIT, MAIN_SUM, MAIN_PRODUCT, MAIN_CHAIN = range(6)   # sp_air_main_column.kind
 MAIN_MAX_BIT = 251
+MAIN_CHAIN_MAX_WIDTH = 16            # sp_air_main_chain_limits
 INPUTS_HOST, INPUTS_DEVICE = 0, 1    # sp_air_main_desc.input_location
 
 
@@ -243,12 +249,26 @@ def needs_pub(desc):
     return any(aux.ops[i].op == OP_PERIODIC for i in range(aux.n_ops)) if known is None else known
 
 
+def needs_rec(desc):
+    """Whether a built descriptor's main program needs the _rec entry points: it has a chain column (kind 5) or reads a periodic
+    column (op 6)."""
+    main = getattr(desc, "main_desc", None)
+    if main is None:
+        return False
+    known = getattr(desc, "main_needs_rec", None)   # (AirBuilder.build() says so; a descriptor put together by hand is looked through)
+    if known is not None:
+        return known
+    return ((bool(main.cols) and any(main.cols[k].kind == MAIN_CHAIN for k in range(main.n_cols))) or
+            (bool(main.ops) and any(main.ops[i].op == OP_PERIODIC for i in range(main.n_ops))))
+
+
 def route(desc, call):
     """Where a built descriptor goes for call = "prove", "check_trace" or "verify" - new entry points only when the descriptor needs
     them: (the entry point's name, its arguments between `air` and the trace / the options, keepalive).  _pub for boundary values
     computed from the challenges or an auxiliary program that reads a table, _ext for strides, else the parts one by one (the
     verifier takes no auxiliary program).  A descriptor with a main-trace program (desc.main_desc) is proved and checked through the
-    _main entry points, which take everything the _pub ones do; it is verified as if it had none."""
+    _main entry points, which take everything the _pub ones do - through the _rec ones when it holds a chain column or reads a
+    periodic column (needs_rec) -; it is verified as if it had none."""
     def ref(part):
         return None if part is None else ctypes.byref(part)
     aux, per = getattr(desc, "aux_desc", None), getattr(desc, "periodic_desc", None)
@@ -256,7 +276,7 @@ def route(desc, call):
     if main is not None and call != "verify":
         # a main-trace program: the trace argument holds its input columns (a verifier never learns how the trace was made)
         ext = ext_of(desc)
-        return f"sp_air_{call}_main", (ctypes.byref(ext), ref(getattr(desc, "boundary_desc", None)), ctypes.byref(main)), ext
+        return f"sp_air_{call}_{'rec' if needs_rec(desc) else 'main'}", (ctypes.byref(ext), ref(getattr(desc, "boundary_desc", None)), ctypes.byref(main)), ext
     if needs_pub(desc):
         ext = ext_of(desc)
         return f"sp_air_{call}_pub", (ctypes.byref(ext), ref(getattr(desc, "boundary_desc", None))), ext
@@ -544,14 +564,25 @@ class MainProgram:
         product(N, D)        z_0 = 1, z_i = z_(i-1) N(i-1) / D(i-1)
 
     A column that reads a derived column must come after it.  A column whose next value is a non-linear function of its own - the
-    state of a hash chain - is a true recurrence and stays an input."""
+    state of a hash chain - is a true recurrence: a chain group (sp_air_prove_rec).
 
-    def __init__(self, input_cols, main_cols):
+        g = chain(period, seeds)   len(seeds) columns g.cols (at most 16) in blocks of `period` = 2^l rows, 2 <= period <= n: on the
+                                   first row of a block column j is seeds[j] - values that read inputs, earlier columns and periodic
+                                   columns -, on every other row what g.step gave on the row before
+        g.state(j)                 the group's column j on the current row (a LOAD at shift 0: the only way a step reads its group)
+        g.step([next_0, ...])      the value of each column on the NEXT row, all computed from the current one; closes the group
+        periodic(shift, k)         periodic column k of the AirBuilder on row (i + shift): values[(i + shift) mod period_k] (op 6)
+
+    Between chain() and step() no other column can be declared.  Seeds and steps are polynomial: no denominators."""
+
+    def __init__(self, input_cols, main_cols, periodic_cols=()):
         if not 1 <= input_cols < main_cols:
             raise ValueError(f"main program: {input_cols} input columns of {main_cols} main columns (at least one input, at least one derived)")
         self.input_cols, self.main_cols = input_cols, main_cols
+        self.periodic_cols = periodic_cols   # the owning AirBuilder's periodic columns: what periodic() may read
         self.ops, self.consts, self.cols = [], [], []    # cols: (kind, num_op, den_op, pad)
         self._const_at = {}
+        self._open = None                    # the chain group between chain() and step()
 
     def _emit(self, op, a, b):
         self.ops.append((op, a, b))
@@ -562,7 +593,33 @@ class MainProgram:
             raise ValueError(f"main program: row shift {shift} outside 0 .. {AUX_MAX_SHIFT}")
         if not 0 <= col < self.input_cols + len(self.cols):
             raise ValueError(f"main program: column {col} is neither an input nor a derived column declared so far")
+        if self._open is not None and col in self._open.cols and shift != 0:
+            raise ValueError(f"main program: a step reads its own chain group at shift 0 only (column {col} at shift {shift})")
         return self._emit(OP_LOAD, shift, col)
+
+    def periodic(self, shift, k):
+        """Periodic column k of the owning AirBuilder on row (i + shift): op 6, which only sp_air_prove_rec and its siblings take."""
+        if not 0 <= shift <= AUX_MAX_SHIFT:
+            raise ValueError(f"main program: row shift {shift} outside 0 .. {AUX_MAX_SHIFT}")
+        if not 0 <= k < len(self.periodic_cols):
+            raise ValueError(f"main program: column {k} is not one of the AIR's {len(self.periodic_cols)} periodic columns")
+        return self._emit(OP_PERIODIC, shift, k)
+
+    def chain(self, period, seeds):
+        """Opens a chain group of len(seeds) columns in blocks of `period` rows (see the class); returns its ChainGroup."""
+        if self._open is not None:
+            raise ValueError("main program: a chain group is open (g.step closes it)")
+        if period < 2 or period & (period - 1):
+            raise ValueError(f"main program: the block length {period} of a chain group is not a power of two >= 2")
+        if not 1 <= len(seeds) <= MAIN_CHAIN_MAX_WIDTH:
+            raise ValueError(f"main program: a chain group of {len(seeds)} columns (1 .. {MAIN_CHAIN_MAX_WIDTH})")
+        seeds = [x if isinstance(x, Value) else self.const(x) for x in seeds]
+        log = period.bit_length() - 1
+        first = self.input_cols + len(self.cols)
+        for j, seed in enumerate(seeds):   # (num_op, the step, is filled in by g.step)
+            self._column(MAIN_CHAIN, seed, seed, log + 256 * j)
+        self._open = ChainGroup(self, list(range(first, first + len(seeds))), period)
+        return self._open
 
     def const(self, v):
         v %= P
@@ -577,6 +634,8 @@ class MainProgram:
             den = self.const(den)
         if num.b is not self or (den is not None and den.b is not self):
             raise ValueError("main program: N and D must be values of this program")
+        if self._open is not None:
+            raise ValueError("main program: a chain group is open: g.step([...]) closes it before another column is declared")
         if self.input_cols + len(self.cols) >= self.main_cols:
             raise ValueError(f"main program: more derived columns than main_cols - main_inputs = {self.main_cols - self.input_cols}")
         self.cols.append((kind, num.i, AUX_NO_DEN if den is None else den.i, pad))
@@ -606,28 +665,67 @@ class MainProgram:
 
     def reads(self):
         """Per op: one more than the highest derived column its value depends on (0: inputs only) - what the decoder follows."""
+        return self._reads(False)
+
+    def _reads(self, shifted_only):
         reads = []
         for op, a, b in self.ops:
             if op == OP_LOAD:
-                reads.append(max(0, b - self.input_cols + 1))
+                reads.append(max(0, b - self.input_cols + 1) if a or not shifted_only else 0)
             else:
                 reads.append(max(reads[a], reads[b]) if op in (OP_ADD, OP_SUB, OP_MUL) else 0)
         return reads
 
-    def check(self):
-        """The decoder's rules (air_statement_from_c), for a program whose lists were filled by hand too: ValueError naming the first one broken."""
+    def check(self, n=None):
+        """The decoder's rules (air_statement_from_c), for a program whose lists were filled by hand too: ValueError naming the first one
+        broken.  n: the trace length a chain group's block length is held against (None: not yet known)."""
+        if self._open is not None:
+            raise ValueError("main program: a chain group is open: g.step([...]) closes it")
         if self.input_cols < 1 or not self.cols or self.input_cols + len(self.cols) != self.main_cols:
             raise ValueError(f"main program: {self.input_cols} input + {len(self.cols)} derived columns, the AIR has main_cols = {self.main_cols}")
         for t, (op, a, b) in enumerate(self.ops):
+            if op == OP_PERIODIC and 0 <= a <= AUX_MAX_SHIFT and not 0 <= b < len(self.periodic_cols):
+                raise ValueError(f"main program: op {t} reads periodic column {b}, and the AIR has {len(self.periodic_cols)}")
             ok = ((op == OP_LOAD and 0 <= a <= AUX_MAX_SHIFT and 0 <= b < self.main_cols) or (op == OP_CONST and 0 <= a < len(self.consts)) or
-                  (op in (OP_ADD, OP_SUB, OP_MUL) and 0 <= a < t and 0 <= b < t))
+                  (op in (OP_ADD, OP_SUB, OP_MUL) and 0 <= a < t and 0 <= b < t) or (op == OP_PERIODIC and 0 <= a <= AUX_MAX_SHIFT))
             if not ok:
-                raise ValueError(f"main program: malformed op {t} (LOAD, CONST, ADD, SUB, MUL over earlier ops only)")
-        reads = self.reads()
+                raise ValueError(f"main program: malformed op {t} (LOAD, CONST, ADD, SUB, MUL over earlier ops, PERIODIC only)")
+        reads, shifted = self.reads(), self._reads(True)
+        g0 = g_end = 0      # the chain group that column k belongs to is [g0, g_end), when k < g_end
         for k, (kind, num_op, den_op, pad) in enumerate(self.cols):
             den = den_op != AUX_NO_DEN
-            if not MAIN_VALUE <= kind <= MAIN_PRODUCT:
+            if not MAIN_VALUE <= kind <= MAIN_CHAIN:
                 raise ValueError(f"main program: derived column {k} has an unknown kind")
+            if kind == MAIN_CHAIN:
+                log, j = pad & 255, pad >> 8
+                if k >= g_end:
+                    if j != 0:
+                        raise ValueError(f"main program: derived column {k} is a CHAIN column with j = {j} out of sequence (no group is open)")
+                    g0, g_end = k, k + 1
+                    while g_end < len(self.cols) and self.cols[g_end][0] == MAIN_CHAIN and self.cols[g_end][3] >> 8:
+                        jj = self.cols[g_end][3] >> 8
+                        if jj != g_end - g0:
+                            raise ValueError(f"main program: derived column {g_end} is a CHAIN column with j = {jj} out of sequence (the next of its group is {g_end - g0})")
+                        if jj >= MAIN_CHAIN_MAX_WIDTH:
+                            raise ValueError(f"main program: derived column {g_end} makes its chain group longer than {MAIN_CHAIN_MAX_WIDTH} columns")
+                        g_end += 1
+                if log == 0 or log >= 64 or (n is not None and (1 << log) > n):
+                    raise ValueError(f"main program: derived column {k} is a CHAIN column with l = {log} (block length 2^l: 1 <= l and 2^l <= n)")
+                if log != self.cols[g0][3] & 255:
+                    raise ValueError(f"main program: derived column {k} differs from its chain group in l")
+                if not den:
+                    raise ValueError(f"main program: derived column {k} is a CHAIN column without a seed")
+                if not (0 <= num_op < len(self.ops) and 0 <= den_op < len(self.ops)):
+                    raise ValueError(f"main program: derived column {k} names an op beyond the program")
+                r = max(reads[num_op], reads[den_op])
+                if r > g_end:
+                    raise ValueError(f"main program: derived column {k} reads derived column {r - 1}, which is not an earlier one")
+                if reads[den_op] > g0:
+                    raise ValueError(f"main program: derived column {k} has a seed that loads derived column {reads[den_op] - 1} of its own chain group")
+                if shifted[num_op] > g0:
+                    raise ValueError(f"main program: derived column {k} has a step that loads derived column {shifted[num_op] - 1} of its own chain group "
+                                     "at a shift other than 0")
+                continue
             if not 0 <= num_op < len(self.ops) or (den and not 0 <= den_op < len(self.ops)):
                 raise ValueError(f"main program: derived column {k} names an op beyond the program")
             if den and kind in (MAIN_INV_OR_ZERO, MAIN_BIT):
@@ -641,9 +739,10 @@ class MainProgram:
     def evaluate(self, input_rows):
         """The whole main segment in Python integers (the semantics of sp_air_prove_main): input_rows = n x input_cols field elements;
         returns an (n, main_cols) numpy object array.  Columns in index order, each op one vectorised numpy operation, evaluated when the
-        first column that needs it is built (the columns it loads are complete by then).  ValueError on a zero denominator."""
+        first column that needs it is built (the columns it loads are complete by then).  ValueError on a zero denominator.  A chain
+        group is a loop over the rows t of a block, each step vectorised over the n / period blocks."""
         import numpy as np
-        self.check()
+        self.check(len(input_rows))
         rows = input_rows if not isinstance(input_rows, np.ndarray) else input_rows.astype(object)
         n = len(rows)
         m = np.empty((n, self.main_cols), dtype=object)
@@ -664,6 +763,8 @@ class MainProgram:
                 op, a, b = self.ops[u]
                 if op == OP_LOAD:
                     vals[u] = np.roll(m[:, b], -a)
+                elif op == OP_PERIODIC:
+                    vals[u] = periodic[b][(np.arange(n) + a) % len(periodic[b])]
                 elif op == OP_CONST:
                     vals[u] = np.full(n, self.consts[a], dtype=object)
                 elif op == OP_ADD:
@@ -674,7 +775,49 @@ class MainProgram:
                     vals[u] = (vals[a] * vals[b]) % P
             return vals[t]
 
+        def run(targets, rows, first, state):
+            """The values of the ops `targets` on the rows `rows` alone, a LOAD of group column first + j being state[j]."""
+            got, stack = {}, list(targets)
+            todo = set()
+            while stack:
+                u = stack.pop()
+                if u in todo:
+                    continue
+                todo.add(u)
+                if self.ops[u][0] in (OP_ADD, OP_SUB, OP_MUL):
+                    stack += [self.ops[u][1], self.ops[u][2]]
+            for u in sorted(todo):
+                op, a, b = self.ops[u]
+                if op == OP_LOAD:
+                    got[u] = state[b - first] if first <= b < first + len(state) else m[(rows + a) % n, b]
+                elif op == OP_PERIODIC:
+                    got[u] = periodic[b][(rows + a) % len(periodic[b])]
+                elif op == OP_CONST:
+                    got[u] = np.full(len(rows), self.consts[a], dtype=object)
+                elif op == OP_ADD:
+                    got[u] = (got[a] + got[b]) % P
+                elif op == OP_SUB:
+                    got[u] = (got[a] - got[b]) % P
+                else:
+                    got[u] = (got[a] * got[b]) % P
+            return [got[u] for u in targets]
+
+        periodic = [np.array(values, dtype=object) for values in self.periodic_cols]
         for k, (kind, num_op, den_op, pad) in enumerate(self.cols):
+            if kind == MAIN_CHAIN:
+                if pad >> 8:
+                    continue            # (built with its group, at the column that opens it)
+                period, w = 1 << (pad & 255), 1
+                while k + w < len(self.cols) and self.cols[k + w][0] == MAIN_CHAIN and self.cols[k + w][3] >> 8:
+                    w += 1
+                first, rows = self.input_cols + k, np.arange(0, n, period)
+                state = run([self.cols[k + j][2] for j in range(w)], rows, first, [])
+                for t in range(period):
+                    for j in range(w):
+                        m[rows + t, first + j] = state[j]
+                    if t + 1 < period:   # all w next values from the state of row t, assigned together
+                        state = run([self.cols[k + j][1] for j in range(w)], rows + t, first, state)
+                continue
             t = need(num_op)
             if den_op != AUX_NO_DEN:
                 t = (t * np.array(_batch_inverse([int(x) for x in need(den_op)]), dtype=object)) % P
@@ -697,6 +840,31 @@ class MainProgram:
                     col[i] = z
                     z = z * int(t[i]) % P
         return m
+
+
+class ChainGroup:
+    """A chain group of a MainProgram between chain() and step(): cols = its main columns, state(j) = column j on the current row."""
+
+    def __init__(self, program, cols, period):
+        self.program, self.cols, self.period = program, cols, period
+
+    def state(self, j):
+        return self.program.load(0, self.cols[j])
+
+    def step(self, nexts):
+        """nexts[j]: the value of column j on the next row, from the current one; the group is complete with it."""
+        m = self.program
+        if m._open is not self:
+            raise ValueError("main program: this chain group is closed already")
+        if len(nexts) != len(self.cols):
+            raise ValueError(f"main program: {len(nexts)} next values for a chain group of {len(self.cols)} columns")
+        nexts = [x if isinstance(x, Value) else m.const(x) for x in nexts]
+        if any(x.b is not m for x in nexts):
+            raise ValueError("main program: the next values must be values of this program")
+        for col, x in zip(self.cols, nexts):
+            kind, _, seed, pad = m.cols[col - m.input_cols]
+            m.cols[col - m.input_cols] = (kind, x.i, seed, pad)
+        m._open = None
 
 
 class PublicProgram:
@@ -787,7 +955,7 @@ class AirBuilder:
         self.public = PublicProgram(n_rap)
         self.bvalues = []
         # main_inputs: the derived main columns as a program over the main columns before them (sp_air_prove_main)
-        self.main = MainProgram(main_inputs, main_cols) if main_inputs is not None else None
+        self.main = MainProgram(main_inputs, main_cols, self.periodic_cols) if main_inputs is not None else None
 
     def _emit(self, op, a, b):
         self.ops.append((op, a, b))
@@ -989,7 +1157,7 @@ class AirBuilder:
             for name, value in (("constants", len(self.main.consts)), ("ops", len(self.main.ops))):
                 if value > lim[name]:
                     raise ValueError(f"main program exceeds the {name} limit of sp_air_prove_main: {value} > {lim[name]}")
-            self.main.check()
+            self.main.check()   # (a chain group's block length is held against n by evaluate and by the decoder)
             if self.aux_kind not in (AUX_NONE, AUX_PROGRAM):
                 raise ValueError("main program: aux_kind must be AUX_NONE or AUX_PROGRAM (the other kinds build the auxiliary segment from a host "
                                  "table of the main segment)")
@@ -1085,6 +1253,7 @@ class AirBuilder:
         if self.main is not None:
             m_desc, m_keep = main_desc(self.main.input_cols, self.main.ops, self.main.consts, self.main.cols)
             d.main_desc = m_desc
+            d.main_needs_rec = any(c[0] == MAIN_CHAIN for c in self.main.cols) or any(op == OP_PERIODIC for op, _, _ in self.main.ops)
             keep = keep + (m_desc, m_keep)
         return d, keep
 
@@ -1441,3 +1610,55 @@ def zero_count_inputs(n, zeros, rng):
     of those rows below n - 1."""
     zeros = set(zeros)
     return [[0 if i in zeros else 1 + rng.randrange(P - 1)] for i in range(n)]
+
+
+# ---- block recurrences: a worked example ----------------------------------------------------------------------------------------
+def mimc_blocks(n, s, keys, digest, width=1):
+    """n / s independent MiMC permutations of s rounds each, one per block of s rows: the caller uploads the messages m (column 0, of
+    which only the rows = 0 (mod s) matter) and the device builds the rest (sp_air_prove_rec).  Column 1 is the state x, a chain group
+    with seed m and step (x + K_t)^3; column 2 the row-local q = (x + K)^2, a VALUE that reads x and the periodic column K.  Periodic
+    columns K = keys (period s) and sel = [1] (s - 1) + [0].  Constraints under degree_bound_factor 2, no exemption: q - (x + K)^2
+    (degree 2) on every row; sel (x' - q (x + K)) (degree 3) on every row - sel switches it off where a block ends, the trace's last
+    row among them; x - m (degree 1) on the rows = 0 (mod s).  The boundary constraint x_(s-1) = digest is block 0's public digest
+    (mimc_blocks_digest).
+
+    width > 1 widens the group: states x_0 .. x_(w-1) in columns 1 .. w with seeds m + j and steps (x_j + x_((j+1) mod w) + K)^3, their
+    squares q_j in columns w + 1 .. 2 w, every constraint once per j; the digest is that of x_0."""
+    if s < 2 or s & (s - 1) or s > n or len(keys) != s:
+        raise ValueError(f"mimc_blocks: blocks of {s} rows with {len(keys)} keys on {n} rows (a power of two in 2 .. n, one key per row of a block)")
+    w = width
+    b = AirBuilder(1 + 2 * w, [0, 1], 2, periodic=[keys, [1] * (s - 1) + [0]], main_inputs=1)
+    m = b.main
+    g = m.chain(s, [m.load(0, 0) + j for j in range(w)] if w > 1 else [m.load(0, 0)])
+
+    def round_input(load, key, j):
+        return load(j) + key if w == 1 else load(j) + load((j + 1) % w) + key
+
+    t = [round_input(g.state, m.periodic(0, 0), j) for j in range(w)]
+    g.step([t[j] * t[j] * t[j] for j in range(w)])
+    x = g.cols
+    q = []
+    for j in range(w):
+        u = round_input(lambda j: m.load(0, x[j]), m.periodic(0, 0), j)
+        q.append(m.value(u * u))
+    for j in range(w):
+        u = round_input(lambda j: b.load(0, x[j]), b.periodic(0, 0), j)
+        b.constraint(b.load(0, q[j]) - u * u, degree=2, exemptions=0)
+        b.constraint(b.periodic(0, 1) * (b.load(1, x[j]) - b.load(0, q[j]) * u), degree=3, exemptions=0)
+        b.constraint(b.load(0, x[j]) - (b.load(0, 0) + j if j else b.load(0, 0)), degree=1, exemptions=0, period=s, offset=0)
+    b.boundary(x[0], s - 1, digest)
+    return b
+
+
+def mimc_blocks_digest(messages, s, keys, width=1):
+    """x_0 on the last row of the block seeded from messages[0]: the public digest of mimc_blocks (rounds 0 .. s - 2; the last key is
+    read by q alone)."""
+    x = [(int(messages[0]) + j) % P for j in range(width)]
+    for t in range(s - 1):
+        x = [pow((x[j] + (x[(j + 1) % width] if width > 1 else 0) + keys[t]) % P, 3, P) for j in range(width)]
+    return x[0]
+
+
+def mimc_blocks_inputs(n, s, rng):
+    """(n, 1) Python ints from rng.randrange: a message on every row = 0 (mod s), the caller's filler on the others."""
+    return [[rng.randrange(P)] for _ in range(n)]

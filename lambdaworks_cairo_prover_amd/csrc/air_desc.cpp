@@ -149,8 +149,10 @@ std::string validate_aux_program(const AirAuxHost& aux, uint32_t main_cols, uint
 
 // sp_air_main_desc -> AirMainHost against its AIR: "" or what is wrong.  Every count and pointer first; then the ops (0 .. 4 over
 // earlier ops, LOADs of main columns at shifts 0 .. 7), the columns' kinds, and - following the operands - which derived columns
-// the ops behind each column load: only earlier ones.
-std::string main_from_c(const AirDescHost& air, const sp_air_main_desc* m, AirMainHost& out) {
+// the ops behind each column load: only earlier ones.  rec (the _rec entry points): op 6 over the statement's n_periodic periodic
+// columns and SP_AIR_MAIN_CHAIN columns too - groups with j = 0, 1, .. and one l, seeds that read nothing of their group, steps that
+// read it at shift 0 only; without rec kind 5 is an unknown kind and op 6 a malformed op.
+std::string main_from_c(const AirDescHost& air, const sp_air_main_desc* m, uint64_t n, uint32_t n_periodic, bool rec, AirMainHost& out) {
     if (m->size != sizeof(sp_air_main_desc)) return "main program: sp_air_main_desc.size is not sizeof(sp_air_main_desc)";
     if (!m->ops || !m->consts || !m->cols) return "main program: null ops, consts or cols";
     if (m->input_cols == 0 || m->n_cols == 0 || (uint64_t)m->input_cols + m->n_cols != air.main_cols)
@@ -160,25 +162,57 @@ std::string main_from_c(const AirDescHost& air, const sp_air_main_desc* m, AirMa
     std::vector<AirOpHost> ops;
     ops_from_c(m->ops, m->n_ops, ops);
     const size_t n_ops = ops.size();
-    // (no OUT target, no periodic column: ops 0 .. 4 are all that is left)
-    const size_t bad = air_program_first_bad_op(ops, AIR_LIMIT_AUX_SHIFT + 1, air.main_cols, m->n_consts, 0, 0);
+    if (rec)
+        for (size_t t = 0; t < n_ops; ++t)
+            if (ops[t].op == 6 && ops[t].b >= n_periodic)
+                return "main program: op " + std::to_string(t) + " reads periodic column " + std::to_string(ops[t].b) + ", and the statement has " +
+                       std::to_string(n_periodic) + " (ext->periodic)";
+    // (no OUT target; a periodic column only through the _rec entry points: elsewhere ops 0 .. 4 are all that is left)
+    const size_t bad = air_program_first_bad_op(ops, AIR_LIMIT_AUX_SHIFT + 1, air.main_cols, m->n_consts, 0, rec ? n_periodic : 0u);
     if (bad < n_ops)
         return "main program: malformed op " + std::to_string(bad) + " (LOAD needs a shift of 0 .. 7 and a main column, CONST a constant, ADD / SUB / MUL earlier "
-               "ops; there is no OUT, no op 6 and no RAP challenge)";
-    // reads[t]: one more than the highest derived column the value of op t depends on (0: inputs only)
-    std::vector<uint32_t> reads(n_ops, 0);
+               "ops; there is no OUT and no RAP challenge, and op 6 - a shift of 0 .. 7 and a periodic column - only through the _rec entry points)";
+    // reads[t]: one more than the highest derived column the value of op t depends on (0: inputs only); shifted[t]: the same over the
+    // LOADs at a shift other than 0 alone (what a chain's step may not do to its own group)
+    std::vector<uint32_t> reads(n_ops, 0), shifted(n_ops, 0);
     for (size_t t = 0; t < n_ops; ++t) {
         const AirOpHost& o = ops[t];
-        if (o.op == 0 && o.b >= m->input_cols) reads[t] = o.b - m->input_cols + 1;
-        else if (o.op >= 2 && o.op <= 4) reads[t] = std::max(reads[o.a], reads[o.b]);
+        if (o.op == 0 && o.b >= m->input_cols) { reads[t] = o.b - m->input_cols + 1; shifted[t] = o.a ? reads[t] : 0u; }
+        else if (o.op >= 2 && o.op <= 4) { reads[t] = std::max(reads[o.a], reads[o.b]); shifted[t] = std::max(shifted[o.a], shifted[o.b]); }
     }
     std::vector<AirMainColumnHost> cols;
     cols.reserve(m->n_cols);
+    uint32_t g0 = 0, g_end = 0;   // the chain group that column k belongs to is [g0, g_end), when k < g_end
     for (uint32_t k = 0; k < m->n_cols; ++k) {
         const sp_air_main_column& c = m->cols[k];
         const std::string who = "main program: derived column " + std::to_string(k);
         const bool den = c.den_op != SP_AIR_AUX_NO_DEN;
-        if (c.kind > SP_AIR_MAIN_PRODUCT) return who + " has an unknown kind";
+        if (c.kind > (rec ? SP_AIR_MAIN_CHAIN : SP_AIR_MAIN_PRODUCT)) return who + " has an unknown kind";
+        if (c.kind == SP_AIR_MAIN_CHAIN) {
+            const uint32_t l = c.pad & 255u, j = c.pad >> 8;
+            if (k >= g_end) {   // it must open a group: the run of CHAIN columns with j = 1, 2, .. behind it
+                if (j != 0) return who + " is a CHAIN column with j = " + std::to_string(j) + " out of sequence (no group is open: j = 0 opens one)";
+                g0 = k; g_end = k + 1;
+                while (g_end < m->n_cols && m->cols[g_end].kind == SP_AIR_MAIN_CHAIN && (m->cols[g_end].pad >> 8) != 0) {
+                    const uint32_t jj = m->cols[g_end].pad >> 8;
+                    const std::string member = "main program: derived column " + std::to_string(g_end);
+                    if (jj != g_end - g0) return member + " is a CHAIN column with j = " + std::to_string(jj) + " out of sequence (the next of its group is " + std::to_string(g_end - g0) + ")";
+                    if (jj >= AIR_MAIN_CHAIN_MAX_WIDTH) return member + " makes its chain group longer than 16 columns";
+                    ++g_end;
+                }
+            }
+            if (l == 0 || l >= 64 || (1ull << l) > n) return who + " is a CHAIN column with l = " + std::to_string(l) + " (block length 2^l: 1 <= l and 2^l <= n)";
+            if (l != (m->cols[g0].pad & 255u)) return who + " differs from its chain group in l (" + std::to_string(l) + " against " + std::to_string(m->cols[g0].pad & 255u) + ")";
+            if (!den) return who + " is a CHAIN column without a seed (den_op names the seed op)";
+            if (c.num_op >= n_ops || c.den_op >= n_ops) return who + " names an op beyond the program";
+            const uint32_t r = std::max(reads[c.num_op], reads[c.den_op]);
+            if (r > g_end) return who + " reads derived column " + std::to_string(r - 1) + ", which is not an earlier one";
+            if (reads[c.den_op] > g0) return who + " has a seed that loads derived column " + std::to_string(reads[c.den_op] - 1) + " of its own chain group";
+            if (shifted[c.num_op] > g0)
+                return who + " has a step that loads derived column " + std::to_string(shifted[c.num_op] - 1) + " of its own chain group at a shift other than 0";
+            cols.push_back(AirMainColumnHost{c.kind, c.num_op, c.den_op, 0u, r, l, j});
+            continue;
+        }
         if (c.num_op >= n_ops || (den && c.den_op >= n_ops)) return who + " names an op beyond the program";
         if (den && (c.kind == SP_AIR_MAIN_INV_OR_ZERO || c.kind == SP_AIR_MAIN_BIT)) return who + " is an INV_OR_ZERO or a BIT and takes no denominator";
         if (c.kind == SP_AIR_MAIN_BIT && c.pad > 251) return who + " names bit " + std::to_string(c.pad) + " (0 .. 251)";
@@ -218,9 +252,11 @@ bool air_boundary_from_c(const sp_air_boundary_desc* d, uint32_t n_boundary, uin
 }
 
 std::string air_statement_from_c(const sp_air_desc* d, const sp_air_aux_desc* aux, const sp_air_periodic_desc* periodic, const sp_air_stride_desc* strides,
-                                 const sp_air_boundary_desc* bvals, bool aux_reads_periodic, uint64_t n, AirStatement& st, const sp_air_main_desc* main) {
+                                 const sp_air_boundary_desc* bvals, bool aux_reads_periodic, uint64_t n, AirStatement& st, const sp_air_main_desc* main,
+                                 bool main_rec) {
     AirDescHost& air = st.air;
     st.aux_reads_periodic = aux_reads_periodic;
+    st.main_rec = main_rec;
     if (!air_desc_from_c(d, air)) return "malformed AIR descriptor (1 .. 8 frame rows, 1 .. 64 transition constraints, every count with its array)";
     if (periodic && !air_periodic_from_c(periodic, n, st.periodic.emplace()))
         return "malformed periodic columns (at most 64, each a power-of-two number of values, at most the trace length)";
@@ -237,7 +273,8 @@ std::string air_statement_from_c(const sp_air_desc* d, const sp_air_aux_desc* au
     if (air.consts.size() + air.n_rap > 65535) return "constants and RAP challenges exceed the 16-bit operand range";
     if (air.ops.size() > AIR_LIMIT_OPS) return "more than 65535 ops";
     if (main) {
-        const std::string refused = main_from_c(air, main, st.main.emplace());
+        // (only the _rec entry points let a main program hold chain columns and read the periodic columns)
+        const std::string refused = main_from_c(air, main, n, st.n_periodic(), st.main_rec, st.main.emplace());
         if (!refused.empty()) return refused;
     }
     // (only the _pub entry points let an auxiliary program read the periodic columns: 0 of them from everywhere else)

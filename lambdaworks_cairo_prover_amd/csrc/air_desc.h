@@ -46,8 +46,11 @@ struct AirAuxHost {
 };
 
 // Host form of sp_air_main_desc: the program that derives main columns input_cols .. main_cols - 1 from the caller's input columns.
-// reads: derived columns [0, reads) are what the ops behind this column load (0: inputs only); the decoder holds reads <= its index.
-struct AirMainColumnHost { uint32_t kind, num_op, den_op, bit, reads; };
+// reads: derived columns [0, reads) are what the ops behind this column load (0: inputs only); the decoder holds reads <= its index
+// (for a CHAIN column: <= the end of its group for the step, <= the group's first column for the seed).  chain_log / chain_pos: the
+// l and j of a CHAIN column's pad (block length 2^l, position in its group), 0 for the other kinds.
+constexpr uint32_t AIR_MAIN_CHAIN_MAX_WIDTH = 16;
+struct AirMainColumnHost { uint32_t kind, num_op, den_op, bit, reads, chain_log = 0, chain_pos = 0; };
 struct AirMainHost {
     uint32_t input_cols = 0, input_location = 0;   // 0: the inputs are host memory, 1: device memory
     std::vector<AirOpHost> ops;
@@ -118,6 +121,7 @@ struct AirStatement {
     std::optional<AirBoundaryHost> bvals;     // boundary values computed from the RAP challenges (air_resolve_boundary_into after round 1)
     std::optional<AirMainHost> main;          // the main-trace program: the caller hands over its input columns only (sp_air_prove_main)
     bool aux_reads_periodic = false;
+    bool main_rec = false;                    // the main program may hold CHAIN columns and read the periodic columns with op 6 (the _rec entry points)
     bool unsupported = false;                 // set with a refusal that is SP_E_UNSUPPORTED, not SP_E_INVALID_ARG (a main program beside aux_kind 1 or 2)
     // the periodic columns the auxiliary program may read: null when it may read none
     const AirPeriodicHost* aux_periodic() const { return aux_reads_periodic && periodic ? &*periodic : nullptr; }
@@ -133,12 +137,15 @@ struct AirStatement {
 // main (nullable, the prover and the trace check only): a main-trace program whose columns add up to air.main_cols, ops 0 .. 4 over
 // earlier ops, LOADs at shifts 0 .. 7 of inputs or - from the ops behind derived column j - of derived columns k < j, the kinds' own
 // rules (sp_air_main_desc); beside it aux_kind is 0 or SP_AIR_AUX_PROGRAM, else the refusal comes with out.unsupported set.
+// main_rec (the _rec entry points only): the main program may also hold SP_AIR_MAIN_CHAIN columns - groups of 1 .. 16 with j = 0, 1, ..
+// and one block length 2^l in 2 .. n, a seed that reads nothing of its group, a step that reads its group at shift 0 only - and read
+// the periodic columns with op 6; without it kind 5 is an unknown kind and op 6 a malformed op, as ever.
 // The constraint program itself is checked where it is turned into what runs it (build_air_program, air_verify_host).
 // An sp_air_ext is taken apart by the entry point that receives it; this is the one thing it checks first: null, or what is wrong.
 inline const char* air_ext_refusal(const sp_air_ext* ext) { return ext && ext->size != sizeof(sp_air_ext) ? "sp_air_ext.size is not sizeof(sp_air_ext)" : nullptr; }
 std::string air_statement_from_c(const sp_air_desc* d, const sp_air_aux_desc* aux, const sp_air_periodic_desc* periodic, const sp_air_stride_desc* strides,
                                  const sp_air_boundary_desc* bvals, bool aux_reads_periodic, uint64_t n, AirStatement& out,
-                                 const sp_air_main_desc* main = nullptr);
+                                 const sp_air_main_desc* main = nullptr, bool main_rec = false);
 // `verify::<F, A>` for a program AIR (verifier.cpp): 1 accept, 0 reject; throws std::runtime_error on a malformed proof or constraint
 // program.  st.aux is the prover's business and is not looked at.
 int air_verify_host(const uint8_t* proof_bytes, size_t len, const AirStatement& st, const ProofOptionsHost& opt);

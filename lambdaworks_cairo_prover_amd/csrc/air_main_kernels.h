@@ -2,6 +2,7 @@
 // straight-line program over the main columns that exist already, then what each kind needs on top - a zero guard in front of the
 // chunk's one batch inversion (INV_OR_ZERO), the bits of a value (BIT).  VALUE, SUM and PRODUCT columns go on through
 // air_aux_apply_den and air_aux_scan (air_aux_kernels.h).  One lane per row, 256-lane blocks, every store coalesced into a column.
+// CHAIN columns (block recurrences) are the exception: one lane per block of rows, which walks its block (air_main_chain).
 #pragma once
 #include "air_aux_kernels.h"
 
@@ -10,8 +11,18 @@ namespace sp {
 // One thread per row: the program once (an AirOpDev list with slots, the OUT codes of air_aux_kernels.h): OUT a < AIR_AUX_DEN_TAG
 // stores N of chunk column a at cols[a * n + i], OUT AIR_AUX_DEN_TAG + s stores into workspace slot s at ws[s * n + i] - a
 // denominator, the N of an INV_OR_ZERO column or the N of a BIT group.  trace: [main_cols][n] natural order, of which the inputs and
-// the derived columns of earlier chunks exist; LOAD a = row shift, b = column: row (i + a) mod n.
-int air_main_terms(hipStream_t st, const fe* trace, uint64_t n, const AirOpDev* ops, uint32_t n_ops, const fe* consts, fe* cols, fe* ws);
+// the derived columns of earlier chunks exist; LOAD a = row shift, b = column: row (i + a) mod n.  pcols / pvals (both null for a
+// program without op 6, which then launches the kernel without them): the periodic columns, as air_aux_terms takes them.
+int air_main_terms(hipStream_t st, const fe* trace, uint64_t n, const AirOpDev* ops, uint32_t n_ops, const fe* consts, fe* cols, fe* ws,
+                   const AirPeriodicCol* pcols = nullptr, const fe* pvals = nullptr);
+// One chain group: columns [first_col, first_col + w) of trace, w <= AIR_MAIN_CHAIN_WIDTH, in blocks of 2^log_s rows (2^log_s <= n).
+// One lane per block B < n >> log_s, 64-lane work-groups: the seed program once on row B s - OUT j stores column j's seed -, then for
+// t = 0 .. s - 2 the step program on row i = B s + t - a LOAD of a group column is the lane's state (the decoder allows shift 0 only),
+// every other LOAD row (i + shift) mod n of trace, OUT j the next value of column j - after which the state becomes the next values
+// and goes to row i + 1.  Neither program reads the group's columns from memory: what the kernel reads and what it writes are apart.
+constexpr uint32_t AIR_MAIN_CHAIN_WIDTH = 16;
+int air_main_chain(hipStream_t st, fe* trace, uint64_t n, uint32_t log_s, uint32_t first_col, uint32_t w, const AirOpDev* seed_ops, uint32_t n_seed,
+                   const AirOpDev* step_ops, uint32_t n_step, const fe* consts, const AirPeriodicCol* pcols = nullptr, const fe* pvals = nullptr);
 // INV_OR_ZERO, before the batch inversion: for k < n_inv, with (slot, col) = tab[2 k], tab[2 k + 1]: where ws[slot * n + i] is zero it
 // becomes one and cols[col * n + i] = 0, elsewhere cols[col * n + i] = 1.  The inversion then meets no zero of these, and
 // air_aux_apply_den leaves 0 or 1 / N in the column.

@@ -616,6 +616,10 @@ int StarkProver::commit_aux_program(const AirStatement& st, const std::vector<fe
 // before anything reads it, and the stream orders one chunk behind the other.  Workspace slots of a chunk, n elements each: first
 // the ones the batch inversion takes (the D of VALUE / SUM / PRODUCT columns, the guarded N of INV_OR_ZERO columns), then one per
 // group of BIT columns that share their N.  od_.auxp_buf / od_.auxp_ws: the auxiliary program runs later on the same stream.
+// A chain group (SP_AIR_MAIN_CHAIN, st.main_rec) is a chunk of its own and ends the chunk before it: two programs, the seeds' and the
+// steps', each with an OUT per group column, and one launch of air_main_chain; nothing of the group is read before that launch is
+// over, which the stream's order guarantees.  It takes no workspace.  The periodic columns an op 6 reads (st.periodic) ride in this
+// upload block as they do in the auxiliary program's: round 2's block comes too late.
 int StarkProver::build_main_program(const AirStatement& st, const uint8_t* inputs) {
     const AirMainHost& mp = *st.main;
     const uint32_t I = mp.input_cols, K = (uint32_t)mp.cols.size();
@@ -634,16 +638,53 @@ int StarkProver::build_main_program(const AirStatement& st, const uint8_t* input
         std::vector<uint32_t> kinds, den_col, guard, gtab, etab;     // kinds: 0 product / 1 sum per column (read for scanned columns only)
         std::vector<std::pair<uint32_t, uint32_t>> scans;            // runs of SUM / PRODUCT columns: (first, count)
         size_t o_ops = 0, o_kinds = 0, o_den = 0, o_guard = 0, o_gtab = 0, o_etab = 0;
+        bool periodic = false;                                       // the program (of a chain group: either program) reads a periodic column
+        uint32_t chain_log = 0;                                      // a chain group (kc columns, blocks of 2^chain_log rows): ops is the step program,
+        std::vector<AirOpDev> seed_ops;                              //   seed_ops the seeds'
+        size_t o_seed = 0;
     };
     std::vector<Chunk> chunks;
     uint32_t max_slots = 0, max_inv = 0;
+    bool any_periodic = false;
+    // the program with an OUT behind every op whose value is wanted, slots by air_assign_slots (as commit_aux_program)
+    auto program_with_outs = [&](const std::vector<std::vector<uint32_t>>& outs, std::vector<AirOpDev>& dev, bool& reads_periodic) -> int {
+        std::vector<AirOpHost> ext;
+        std::vector<uint32_t> at(n_src);
+        for (uint32_t t = 0; t < n_src; ++t) {
+            AirOpHost o = mp.ops[t];
+            if (o.op >= 2 && o.op <= 4) { o.a = at[o.a]; o.b = at[o.b]; }
+            at[t] = (uint32_t)ext.size();
+            ext.push_back(o);
+            for (uint32_t code : outs[t]) ext.push_back(AirOpHost{5, code, at[t]});
+        }
+        SP_TRY(air_assign_slots(ext, dev, "main program: more than 64 values alive at once"));
+        for (const AirOpDev& o : dev) reads_periodic |= o.op == 6;   // (of what air_assign_slots kept)
+        any_periodic |= reads_periodic;
+        return SP_OK;
+    };
     for (uint32_t k0 = 0; k0 < K;) {
         Chunk ch;
         ch.k0 = k0;
         std::vector<std::vector<uint32_t>> outs(n_src);
+        if (mp.cols[k0].kind == SP_AIR_MAIN_CHAIN) {   // the whole group (the decoder saw to j = 0, 1, .. and one l)
+            std::vector<std::vector<uint32_t>> seeds(n_src);
+            ch.chain_log = mp.cols[k0].chain_log;
+            do {
+                const AirMainColumnHost& c = mp.cols[k0 + ch.kc];
+                seeds[c.den_op].push_back(ch.kc);
+                outs[c.num_op].push_back(ch.kc);
+                ++ch.kc;
+            } while (k0 + ch.kc < K && mp.cols[k0 + ch.kc].kind == SP_AIR_MAIN_CHAIN && mp.cols[k0 + ch.kc].chain_pos != 0);
+            if (ch.kc > AIR_MAIN_CHAIN_WIDTH || n_ >> ch.chain_log == 0) { sp_set_error("commit_main_program: a chain group the decoder should have refused"); return SP_E_INVALID_ARG; }
+            SP_TRY(program_with_outs(seeds, ch.seed_ops, ch.periodic));
+            SP_TRY(program_with_outs(outs, ch.ops, ch.periodic));
+            k0 += ch.kc;
+            chunks.push_back(std::move(ch));
+            continue;
+        }
         struct BitGroup { uint32_t num_op; std::vector<uint32_t> entries; };
         std::vector<BitGroup> groups;
-        for (; ch.kc < chunk && k0 + ch.kc < K && mp.cols[k0 + ch.kc].reads <= k0; ++ch.kc) {
+        for (; ch.kc < chunk && k0 + ch.kc < K && mp.cols[k0 + ch.kc].reads <= k0 && mp.cols[k0 + ch.kc].kind != SP_AIR_MAIN_CHAIN; ++ch.kc) {
             const AirMainColumnHost& c = mp.cols[k0 + ch.kc];
             const bool scanned = c.kind == SP_AIR_MAIN_SUM || c.kind == SP_AIR_MAIN_PRODUCT;
             ch.kinds.push_back(c.kind == SP_AIR_MAIN_SUM ? 1u : 0u);
@@ -675,17 +716,7 @@ int StarkProver::build_main_program(const AirStatement& st, const uint8_t* input
             ch.gtab.push_back(ch.n_slots++); ch.gtab.push_back((uint32_t)ch.etab.size() / 2); ch.gtab.push_back((uint32_t)g.entries.size() / 2);
             ch.etab.insert(ch.etab.end(), g.entries.begin(), g.entries.end());
         }
-        // the program with an OUT behind every op whose value is wanted, slots by air_assign_slots (as commit_aux_program)
-        std::vector<AirOpHost> ext;
-        std::vector<uint32_t> at(n_src);
-        for (uint32_t t = 0; t < n_src; ++t) {
-            AirOpHost o = mp.ops[t];
-            if (o.op >= 2 && o.op <= 4) { o.a = at[o.a]; o.b = at[o.b]; }
-            at[t] = (uint32_t)ext.size();
-            ext.push_back(o);
-            for (uint32_t code : outs[t]) ext.push_back(AirOpHost{5, code, at[t]});
-        }
-        SP_TRY(air_assign_slots(ext, ch.ops, "main program: more than 64 values alive at once"));
+        SP_TRY(program_with_outs(outs, ch.ops, ch.periodic));
         max_slots = std::max(max_slots, ch.n_slots);
         max_inv = std::max(max_inv, ch.n_inv);
         k0 += ch.kc;
@@ -697,8 +728,20 @@ int StarkProver::build_main_program(const AirStatement& st, const uint8_t* input
     const size_t o_consts = lay.place(sizeof(fe) * std::max<size_t>(1, mp.consts.size()));
     for (Chunk& ch : chunks) {
         ch.o_ops = lay.place(sizeof(AirOpDev) * std::max<size_t>(1, ch.ops.size()));
+        ch.o_seed = lay.place(sizeof(AirOpDev) * std::max<size_t>(1, ch.seed_ops.size()));
         ch.o_kinds = words(ch.kinds); ch.o_den = words(ch.den_col); ch.o_guard = words(ch.guard); ch.o_gtab = words(ch.gtab); ch.o_etab = words(ch.etab);
     }
+    // the periodic columns, as commit_aux_program lays them out: AirPeriodicCol[] and the raw values, column k at pvals + off_k
+    const AirPeriodicHost* periodic = st.main_rec && st.periodic ? &*st.periodic : nullptr;
+    if (any_periodic && !periodic) { sp_set_error("commit_main_program: op 6 without periodic columns (the decoder should have refused it)"); return SP_E_INVALID_ARG; }
+    const uint32_t Kp = any_periodic ? (uint32_t)periodic->cols.size() : 0u;
+    std::vector<AirPeriodicCol> pcols;
+    uint64_t S = 0;
+    for (uint32_t k = 0; k < Kp; ++k) {
+        pcols.push_back(AirPeriodicCol{(uint32_t)sp_log2_exact(periodic->cols[k].size()), 0u, S});
+        S += periodic->cols[k].size();
+    }
+    const size_t o_pcols = any_periodic ? lay.place(sizeof(AirPeriodicCol) * Kp) : 0, o_pvals = any_periodic ? lay.place(sizeof(fe) * S) : 0;
     const size_t bytes = lay.bytes;
     SP_TRY(grow(od_.auxp_buf, bytes));
     std::vector<uint8_t>& up = h_auxp_up_;
@@ -707,7 +750,12 @@ int StarkProver::build_main_program(const AirStatement& st, const uint8_t* input
     auto put = [&](size_t at, const std::vector<uint32_t>& v) { if (!v.empty()) std::memcpy(up.data() + at, v.data(), sizeof(uint32_t) * v.size()); };
     for (const Chunk& ch : chunks) {
         if (!ch.ops.empty()) std::memcpy(up.data() + ch.o_ops, ch.ops.data(), sizeof(AirOpDev) * ch.ops.size());
+        if (!ch.seed_ops.empty()) std::memcpy(up.data() + ch.o_seed, ch.seed_ops.data(), sizeof(AirOpDev) * ch.seed_ops.size());
         put(ch.o_kinds, ch.kinds); put(ch.o_den, ch.den_col); put(ch.o_guard, ch.guard); put(ch.o_gtab, ch.gtab); put(ch.o_etab, ch.etab);
+    }
+    if (any_periodic) {
+        std::memcpy(up.data() + o_pcols, pcols.data(), sizeof(AirPeriodicCol) * Kp);
+        for (uint32_t k = 0; k < Kp; ++k) std::memcpy(up.data() + o_pvals + sizeof(fe) * pcols[k].off, periodic->cols[k].data(), sizeof(fe) * periodic->cols[k].size());
     }
     // --- workspace: [max_slots][n] slots, [max_inv][n] batch-inversion scratch, [chunk][nb] scan block totals
     SP_TRY(grow(od_.auxp_ws, ((uint64_t)max_slots + max_inv) * n_ + (uint64_t)chunk * nb));
@@ -728,9 +776,19 @@ int StarkProver::build_main_program(const AirStatement& st, const uint8_t* input
     fe* scratch = ws + (uint64_t)max_slots * n_;
     fe* block_tot = scratch + (uint64_t)max_inv * n_;
     auto tab = [&](size_t at) { return reinterpret_cast<const uint32_t*>(od_.auxp_buf.p + at); };
+    const AirPeriodicCol* pcols_dev = any_periodic ? reinterpret_cast<const AirPeriodicCol*>(od_.auxp_buf.p + o_pcols) : nullptr;
+    const fe* pvals_dev = any_periodic ? reinterpret_cast<const fe*>(od_.auxp_buf.p + o_pvals) : nullptr;
     for (const Chunk& ch : chunks) {
         fe* cols = d_trace_ + (uint64_t)(I + ch.k0) * n_;
-        SP_TRY(air_main_terms(c_->stream, d_trace_, n_, reinterpret_cast<const AirOpDev*>(od_.auxp_buf.p + ch.o_ops), (uint32_t)ch.ops.size(), consts_dev, cols, ws));
+        const AirOpDev* ops_dev = reinterpret_cast<const AirOpDev*>(od_.auxp_buf.p + ch.o_ops);
+        if (ch.chain_log) {
+            SP_TRY(air_main_chain(c_->stream, d_trace_, n_, ch.chain_log, I + ch.k0, ch.kc, reinterpret_cast<const AirOpDev*>(od_.auxp_buf.p + ch.o_seed),
+                                  (uint32_t)ch.seed_ops.size(), ops_dev, (uint32_t)ch.ops.size(), consts_dev, ch.periodic ? pcols_dev : nullptr,
+                                  ch.periodic ? pvals_dev : nullptr));
+            continue;
+        }
+        SP_TRY(air_main_terms(c_->stream, d_trace_, n_, ops_dev, (uint32_t)ch.ops.size(), consts_dev, cols, ws, ch.periodic ? pcols_dev : nullptr,
+                              ch.periodic ? pvals_dev : nullptr));
         SP_TRY(air_main_zero_guard(c_->stream, ws, cols, tab(ch.o_guard), (uint32_t)ch.guard.size() / 2, n_));
         if (ch.n_inv) {
             SP_TRY(batch_inverse(c_->stream, ws, scratch, (uint64_t)ch.n_inv * n_, c_->d_flag));

@@ -20,7 +20,8 @@ namespace sp {
 
 // the bounds a statement is decoded under (air_desc.h) are the kernels'
 static_assert(AIR_LIMIT_COLS == AIR_MAX_COLS && AIR_LIMIT_BOUNDARY == AIR_MAX_BOUNDARY && AIR_LIMIT_CONSTS == AIR_MAX_CONSTS && AIR_LIMIT_OPS == AIR_MAX_OPS &&
-              AIR_LIMIT_AUX_SHIFT == AIR_AUX_MAX_SHIFT && AIR_MAX_STRIDE_CLASSES == AIR_MAX_STRIDE_CLASSES_DEV && AIR_MAX_STRIDE_EXEMPT_KINDS == AIR_MAX_STRIDE_KINDS_DEV,
+              AIR_LIMIT_AUX_SHIFT == AIR_AUX_MAX_SHIFT && AIR_MAX_STRIDE_CLASSES == AIR_MAX_STRIDE_CLASSES_DEV && AIR_MAX_STRIDE_EXEMPT_KINDS == AIR_MAX_STRIDE_KINDS_DEV &&
+              AIR_MAIN_CHAIN_MAX_WIDTH == AIR_MAIN_CHAIN_WIDTH,
               "air_desc.h and the kernel headers disagree about a bound");
 // Value slots of a straight-line program (ops 0 - 4 produce a value, op 5 OUT consumes op b): values that no OUT reads, directly
 // or through other values, are dropped; every other value gets one of AIR_MAX_LIVE slots, released after its last use.  The ops
@@ -112,6 +113,8 @@ class StarkProver : public sp_deletable {
     // the workspace does or before a column that reads one of the chunk's own (a shifted read needs the whole column): per chunk one
     // pass of the interpreter, one batch inversion (behind the zero guard of the INV_OR_ZERO columns), the bits, the scans; then
     // commit_segment_resident.  A zero denominator is SP_E_ZERO_INVERSE once the root is back.  Every rank builds every column.
+    // With st.main_rec a chain group (SP_AIR_MAIN_CHAIN) is a chunk of its own, built by one launch of air_main_chain, and op 6 reads
+    // st.periodic, whose raw values go up with the program.
     int commit_main_program(const AirStatement& st, const uint8_t* inputs, uint8_t root_out[32]);
     // the same table without the commitment, to host memory: row-major n x main_cols, context encoding (sp_air_main_trace)
     int main_program_table(const AirStatement& st, const uint8_t* inputs, uint8_t* rows_out);

@@ -43,6 +43,11 @@ struct Parts {
     sp_air_main_column mcols[5] = {{SP_AIR_MAIN_INV_OR_ZERO, 0, SP_AIR_AUX_NO_DEN, 0}, {SP_AIR_MAIN_VALUE, 4, 3, 0}, {SP_AIR_MAIN_BIT, 0, SP_AIR_AUX_NO_DEN, 3},
                                    {SP_AIR_MAIN_SUM, 5, SP_AIR_AUX_NO_DEN, 0}, {SP_AIR_MAIN_PRODUCT, 0, 6, 0}};
     sp_air_main_desc mp{};
+    // a main program with a chain group (use 'r': through the _rec policy, 'R': without it): x the one input; a group of two in blocks of
+    // four rows, seeds x and K (op 6), steps x0 x1 and x0 + K; then x0 one row ahead as a VALUE
+    sp_air_op rops[7] = {{0, 0, 0, 0, 0}, {6, 0, 0, 0, 0}, {0, 0, 0, 1, 0}, {0, 0, 0, 2, 0}, {4, 0, 2, 3, 0}, {2, 0, 2, 1, 0}, {0, 0, 1, 1, 0}};
+    sp_air_main_column rcols[3] = {{SP_AIR_MAIN_CHAIN, 4, 0, 2}, {SP_AIR_MAIN_CHAIN, 5, 1, 2 + 256}, {SP_AIR_MAIN_VALUE, 6, SP_AIR_AUX_NO_DEN, 0}};
+    sp_air_main_desc rp{};
     Parts() {
         for (uint32_t j = 0; j < 17; ++j) many_cols[j] = sp_air_aux_column{SP_AIR_AUX_SORTED, j, j, 16};
         for (int j = 0; j < 8; ++j) keys[j] = felt(100 + j);
@@ -56,22 +61,26 @@ struct Parts {
         sd.n = 1; sd.strides = strides;
         bv.n_ops = 3; bv.ops = bops; bv.n_consts = 1; bv.consts = bconsts[0].b; bv.n_values = 2; bv.values = bvalues;
         mp.size = sizeof(sp_air_main_desc); mp.input_cols = 1; mp.n_ops = 7; mp.ops = mops; mp.n_consts = 1; mp.consts = mconsts[0].b; mp.n_cols = 5; mp.cols = mcols;
+        rp.size = sizeof(sp_air_main_desc); rp.input_cols = 1; rp.n_ops = 7; rp.ops = rops; rp.n_consts = 1; rp.consts = mconsts[0].b; rp.n_cols = 3; rp.cols = rcols;
     }
+    void with_chain() { d.main_cols = 4; }
     void with_main() { d.main_cols = 6; }
     void sorted() { d.aux_cols = 3; aux.n_ops = 5; aux.ops = sort_ops; aux.n_cols = 3; aux.cols = sort_cols; }
     void many(uint32_t groups) { d.aux_cols = groups; aux.n_ops = 17; aux.ops = many_ops; aux.n_cols = groups; aux.cols = many_cols; }
 };
 
-// use: which parts go to the decoder (x p s b m, upper case P: the auxiliary program may read the periodic columns; m: the main
+// use: which parts go to the decoder (x p s b m r R, upper case P: the auxiliary program may read the periodic columns; m: the main
 // program, for which the AIR gets its six main columns first)
 void run(const char* label, const char* use, bool want_ok, const std::function<void(Parts&)>& patch) {
     Parts p;
     if (std::strchr(use, 'm')) p.with_main();
+    if (std::strchr(use, 'r') || std::strchr(use, 'R')) p.with_chain();
     patch(p);
     auto has = [&](char c) { return std::strchr(use, c) != nullptr; };
     sp::AirStatement st;
     const std::string refused = sp::air_statement_from_c(&p.d, has('x') ? &p.aux : nullptr, has('p') ? &p.per : nullptr, has('s') ? &p.sd : nullptr,
-                                                         has('b') ? &p.bv : nullptr, has('P'), 16, st, has('m') ? &p.mp : nullptr);
+                                                         has('b') ? &p.bv : nullptr, has('P'), 16, st,
+                                                         has('m') ? &p.mp : has('r') || has('R') ? &p.rp : nullptr, has('r'));
     const bool ok = refused.empty();
     if (ok != want_ok) { ++failures; std::printf("FAIL %-44s wanted %s, got %s\n", label, want_ok ? "accepted" : "refused", ok ? "accepted" : refused.c_str()); return; }
     std::printf("ok   %-44s %s\n", label, ok ? "accepted" : refused.substr(0, 60).c_str());
@@ -79,8 +88,13 @@ void run(const char* label, const char* use, bool want_ok, const std::function<v
     // the model on what was accepted: stride plan and zerofier, periodic columns as polynomials, boundary values under a challenge
     sp::AirStridePlan plan;
     bool fine = sp::air_stride_plan(st.air, 16, plan) && st.aux.has_value() == has('x') && st.periodic.has_value() == has('p') && st.bvals.has_value() == has('b') &&
-                (st.aux_periodic() != nullptr) == (has('P') && has('p')) && st.main.has_value() == has('m') && !st.unsupported;
-    if (st.main) {   // what the prover's chunking reads: which derived columns each column needs, and the bit
+                (st.aux_periodic() != nullptr) == (has('P') && has('p')) && st.main.has_value() == (has('m') || has('r')) && st.main_rec == has('r') && !st.unsupported;
+    if (st.main && has('r')) {   // what the prover's chunking reads of a chain group
+        const auto& c = st.main->cols;
+        fine = fine && c.size() == 3 && c[0].kind == SP_AIR_MAIN_CHAIN && c[0].chain_log == (p.rcols[0].pad & 255u) && c[0].chain_pos == 0 && c[1].chain_log == c[0].chain_log && c[1].chain_pos == 1 &&
+               c[2].chain_log == 0 && c[2].reads == 1;
+    }
+    if (st.main && has('m')) {   // what the prover's chunking reads: which derived columns each column needs, and the bit
         const auto& c = st.main->cols;
         fine = fine && c.size() == 5 && c[0].reads == 0 && c[1].reads == 1 && c[2].reads == 0 && c[2].bit == p.mcols[2].pad && c[3].reads == 2 && c[4].reads == 0 &&
                st.main->input_cols == 1 && st.main->ops.size() == 7 && st.main->consts.size() == 1;
@@ -200,6 +214,30 @@ int main() {
     run("main: den_op beyond the program", "m", false, [](Parts& p) { p.mcols[1].den_op = 7; });
     run("main: aux_kind 1", "m", false, [](Parts& p) { p.d.aux_kind = 1; });
     run("main: aux_kind 2", "m", false, [](Parts& p) { p.d.aux_kind = 2; });
+    // ---- chain groups and op 6 in a main program (the _rec policy)
+    run("chain group and op 6", "pr", true, none);
+    run("chain group beside everything", "xpsbPr", true, [](Parts& p) { p.aux.n_ops = 4; });
+    run("chain: the whole trace one block", "pr", true, [](Parts& p) { p.rcols[0].pad = 4; p.rcols[1].pad = 4 + 256; });
+    run("chain: without the policy bit", "pR", false, none);
+    run("chain: op 6 without the policy bit", "pR", false, [](Parts& p) { p.rcols[0].kind = p.rcols[1].kind = SP_AIR_MAIN_VALUE; p.rcols[0].pad = p.rcols[1].pad = 0; p.rops[2].b = p.rops[3].b = p.rops[6].b = 0; });
+    run("chain: op 6 without periodic columns", "r", false, none);
+    run("chain: periodic column 1 of 1", "pr", false, [](Parts& p) { p.rops[1].b = 1; });
+    run("chain: op 6 at shift 8", "pr", false, [](Parts& p) { p.rops[1].a = 8; });
+    run("chain: j = 1 opens", "pr", false, [](Parts& p) { p.rcols[0].pad = 2 + 256; });
+    run("chain: j skips", "pr", false, [](Parts& p) { p.rcols[1].pad = 2 + 512; });
+    run("chain: j = 2^24 - 1", "pr", false, [](Parts& p) { p.rcols[1].pad = 0xFFFFFF02u; });
+    run("chain: l = 0", "pr", false, [](Parts& p) { p.rcols[0].pad = 0; p.rcols[1].pad = 256; });
+    run("chain: blocks longer than the trace", "pr", false, [](Parts& p) { p.rcols[0].pad = 5; p.rcols[1].pad = 5 + 256; });
+    run("chain: l = 255", "pr", false, [](Parts& p) { p.rcols[0].pad = 255; p.rcols[1].pad = 255 + 256; });
+    run("chain: members differ in l", "pr", false, [](Parts& p) { p.rcols[1].pad = 3 + 256; });
+    run("chain: a step reads its group at shift 1", "pr", false, [](Parts& p) { p.rops[2].a = 1; });
+    run("chain: a seed reads its group", "pr", false, [](Parts& p) { p.rcols[1].den_op = 2; });
+    run("chain: a step reads a later column", "pr", false, [](Parts& p) { p.rops[3].b = 3; });
+    run("chain: no seed", "pr", false, [](Parts& p) { p.rcols[0].den_op = SP_AIR_AUX_NO_DEN; });
+    run("chain: step beyond the program", "pr", false, [](Parts& p) { p.rcols[1].num_op = 7; });
+    run("chain: seed beyond the program", "pr", false, [](Parts& p) { p.rcols[1].den_op = 7; });
+    run("chain: kind 6", "pr", false, [](Parts& p) { p.rcols[2].kind = 6; });
+    run("chain: aux_kind 2", "pr", false, [](Parts& p) { p.d.aux_kind = 2; });
     run("no main column", "", false, [](Parts& p) { p.d.main_cols = 0; p.ops[2] = sp_air_op{1, 0, 0, 0, 0}; });
     run("1025 columns", "", false, [](Parts& p) { p.d.main_cols = 1024; p.ops[2] = sp_air_op{1, 0, 0, 0, 0}; });
     std::printf("%s\n", failures ? "FAILED" : "all verdicts as expected");
