@@ -79,8 +79,9 @@ const char* sp_version(void);
  * and no call, and a binding finds a build without them by probing the symbols; so did sp_air_prove_ext, sp_air_verify_ext, sp_air_check_trace_ext,
  * sp_air_stride_size, sp_air_stride_desc_size, sp_air_ext_size, sp_air_stride_limits, sp_air_stride_eval and sp_air_stride_table, and after them sp_air_prove_pub, sp_air_verify_pub,
  * sp_air_check_trace_pub, sp_air_boundary_desc_size and sp_air_boundary_resolve, and then sp_air_prove_main, sp_air_check_trace_main,
- * sp_air_main_trace, sp_air_main_check and sp_air_main_desc_size, and last sp_air_prove_rec, sp_air_check_trace_rec, sp_air_main_trace_rec,
- * sp_air_main_check_rec and sp_air_main_chain_limits).  A binding compares it (and sp_air_desc_size against its own idea of the struct) when it loads the library, so
+ * sp_air_main_trace, sp_air_main_check and sp_air_main_desc_size, then sp_air_prove_rec, sp_air_check_trace_rec, sp_air_main_trace_rec,
+ * sp_air_main_check_rec and sp_air_main_chain_limits, and last sp_air_prove_lk, sp_air_check_trace_lk, sp_air_main_trace_lk, sp_air_main_check_lk
+ * and sp_air_main_count_limits).  A binding compares it (and sp_air_desc_size against its own idea of the struct) when it loads the library, so
  * a stale build fails at load time with "rebuild the library" instead of with a missing symbol or shifted fields later. */
 #define SP_ABI_VERSION 7
 int sp_abi_version(void);
@@ -696,6 +697,31 @@ int sp_air_main_trace_rec(sp_ctx* ctx, const sp_air_desc* air, const sp_air_ext*
 int sp_air_main_check_rec(const sp_air_desc* air, const sp_air_ext* ext, const sp_air_main_desc* main, uint64_t n);
 /* out[0] = the most columns of a chain group (16), out[1] = the highest row shift of a LOAD or an op 6 (7) */
 int sp_air_main_chain_limits(uint32_t out[2]);
+
+/* ---- Lookup multiplicities in a main program: the column m of a LogUp lookup into a table ("how often is the table entry of row i
+ * looked up"), which is a join of the looked-up column against the table and so no row-local kind.  Through the _lk entry points - and
+ * only through them: everywhere else kind 6 stays an unknown kind - a main program may hold columns of kind */
+#define SP_AIR_MAIN_COUNT       6  /* z_i = #{ j in [0, n) : X(j) = T(i) } if no row i' < i has T(i') = T(i), else 0                         */
+/* num_op names the looked-up value X, den_op the table value T (SP_AIR_AUX_NO_DEN is refused: a COUNT needs a table), pad = key_bits,
+ * 1 .. 64.  X and T are ordinary values of the program, evaluated on every row: inputs, earlier derived columns at shifts 0 .. 7 and
+ * periodic columns (op 6).  Each distinct table value's multiplicity sits on the first row that holds it; values of X that no T holds
+ * are counted nowhere, which is no error (the LogUp sum then does not close and the proof is rejected as for any violating trace).
+ * The canonical integers of X(j) and T(i) must be below 2^key_bits on every row: otherwise SP_E_INVALID_ARG with "a lookup key is out
+ * of range on some row", which is reported before a zero denominator of the same program when both occur.  A tuple is looked up by
+ * packing it on both sides (a + 2^w b + 2^(2w) c): X and T are expressions.  n < 2^32.  The _lk entry points accept everything the
+ * _rec ones do; they refuse, with SP_E_INVALID_ARG and a message that names the column, before anything is sized: a COUNT column
+ * without a table, key_bits 0 or above 64, X or T reading a column that is not an earlier one, ops beyond the program, more than 16
+ * COUNT columns in one program.  Argument lists as the _rec entry points. */
+int sp_air_prove_lk(sp_ctx* ctx, const sp_air_desc* air, const sp_air_ext* ext, const sp_air_boundary_desc* bvals, const sp_air_main_desc* main,
+                    const void* inputs, uint64_t n, const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len);
+int sp_air_check_trace_lk(sp_ctx* ctx, const sp_air_desc* air, const sp_air_ext* ext, const sp_air_boundary_desc* bvals, const sp_air_main_desc* main,
+                          const void* inputs, uint64_t n, const sp_proof_options* opt, const uint8_t* rap, sp_air_violation* out, uint32_t cap,
+                          uint32_t* n_out);
+int sp_air_main_trace_lk(sp_ctx* ctx, const sp_air_desc* air, const sp_air_ext* ext, const sp_air_main_desc* main, const void* inputs, uint64_t n,
+                         uint8_t* rows_out);
+int sp_air_main_check_lk(const sp_air_desc* air, const sp_air_ext* ext, const sp_air_main_desc* main, uint64_t n);
+/* out[0] = the most key bits of a COUNT column (64), out[1] = the most COUNT columns of one main program (16) */
+int sp_air_main_count_limits(uint32_t out[2]);
 
 /* verify::<Stark252PrimeField, A> (reference src/starks/verifier.rs:559-657) on the host CPU: 1 accept, 0 reject (also for
  * malformed proofs or descriptors). */

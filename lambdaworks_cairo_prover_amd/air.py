@@ -31,6 +31,10 @@ Block recurrences (sp_air_prove_rec): g = b.main.chain(period, seeds) declares a
 permutations, one per block of `period` rows - seeded on the block's first row, every later cell a polynomial of the row before it
 (g.state(j), g.step([...])) -, and b.main.periodic(shift, k) reads a periodic column (round constants) from the main program.  See
 mimc_blocks below.
+
+Lookup multiplicities (sp_air_prove_lk): b.main.multiplicity(x, table, key_bits) declares the column m of a LogUp lookup - how often
+the table value of row i occurs among the looked-up values of all rows, on the first row that holds it -, which the device builds by
+sorting both sides.  With it a lookup's whole witness comes from the inputs.  See table_lookup_main and xor_lookup below.
 """
 import collections
 import ctypes
@@ -193,9 +197,10 @@ def boundary_desc(ops, consts, values):
     return d, (c_ops, c_consts, c_values)
 
 
-MAIN_VALUE, MAIN_INV_OR_ZERO, MAIN_BIT, MAIN_SUM, MAIN_PRODUCT, MAIN_CHAIN = range(6)   # sp_air_main_column.kind
+MAIN_VALUE, MAIN_INV_OR_ZERO, MAIN_BIT, MAIN_SUM, MAIN_PRODUCT, MAIN_CHAIN, MAIN_COUNT = range(7)   # sp_air_main_column.kind
 MAIN_MAX_BIT = 251
 MAIN_CHAIN_MAX_WIDTH = 16            # sp_air_main_chain_limits
+MAIN_COUNT_MAX_KEY_BITS, MAIN_COUNT_MAX_COLS = 64, 16   # sp_air_main_count_limits
 INPUTS_HOST, INPUTS_DEVICE = 0, 1    # sp_air_main_desc.input_location
 
 
@@ -262,13 +267,30 @@ def needs_rec(desc):
             (bool(main.ops) and any(main.ops[i].op == OP_PERIODIC for i in range(main.n_ops))))
 
 
+def needs_lk(desc):
+    """Whether a built descriptor's main program needs the _lk entry points: it has a COUNT column (kind 6), a lookup multiplicity."""
+    main = getattr(desc, "main_desc", None)
+    if main is None:
+        return False
+    known = getattr(desc, "main_needs_lk", None)   # (AirBuilder.build() says so; a descriptor put together by hand is looked through)
+    if known is not None:
+        return known
+    return bool(main.cols) and any(main.cols[k].kind == MAIN_COUNT for k in range(main.n_cols))
+
+
+def main_suffix(desc):
+    """The entry points a descriptor's main program goes through: "lk", "rec" or "main" - the newer ones only where it needs them."""
+    return "lk" if needs_lk(desc) else "rec" if needs_rec(desc) else "main"
+
+
 def route(desc, call):
     """Where a built descriptor goes for call = "prove", "check_trace" or "verify" - new entry points only when the descriptor needs
     them: (the entry point's name, its arguments between `air` and the trace / the options, keepalive).  _pub for boundary values
     computed from the challenges or an auxiliary program that reads a table, _ext for strides, else the parts one by one (the
     verifier takes no auxiliary program).  A descriptor with a main-trace program (desc.main_desc) is proved and checked through the
     _main entry points, which take everything the _pub ones do - through the _rec ones when it holds a chain column or reads a
-    periodic column (needs_rec) -; it is verified as if it had none."""
+    periodic column (needs_rec), through the _lk ones when it holds a lookup multiplicity (needs_lk) -; it is verified as if it had
+    none."""
     def ref(part):
         return None if part is None else ctypes.byref(part)
     aux, per = getattr(desc, "aux_desc", None), getattr(desc, "periodic_desc", None)
@@ -276,7 +298,7 @@ def route(desc, call):
     if main is not None and call != "verify":
         # a main-trace program: the trace argument holds its input columns (a verifier never learns how the trace was made)
         ext = ext_of(desc)
-        return f"sp_air_{call}_{'rec' if needs_rec(desc) else 'main'}", (ctypes.byref(ext), ref(getattr(desc, "boundary_desc", None)), ctypes.byref(main)), ext
+        return f"sp_air_{call}_{main_suffix(desc)}", (ctypes.byref(ext), ref(getattr(desc, "boundary_desc", None)), ctypes.byref(main)), ext
     if needs_pub(desc):
         ext = ext_of(desc)
         return f"sp_air_{call}_pub", (ctypes.byref(ext), ref(getattr(desc, "boundary_desc", None))), ext
@@ -573,7 +595,14 @@ class MainProgram:
         g.step([next_0, ...])      the value of each column on the NEXT row, all computed from the current one; closes the group
         periodic(shift, k)         periodic column k of the AirBuilder on row (i + shift): values[(i + shift) mod period_k] (op 6)
 
-    Between chain() and step() no other column can be declared.  Seeds and steps are polynomial: no denominators."""
+    Between chain() and step() no other column can be declared.  Seeds and steps are polynomial: no denominators.
+
+    A lookup multiplicity (sp_air_prove_lk) is no row-local column either: it joins one value against another over all rows.
+
+        multiplicity(X, T, key_bits)   z_i = #{ j : X(j) = T(i) } on the first row i that holds the table value T(i), 0 on its later
+                                       rows: the column m of a LogUp lookup of X into the table T.  X and T are values of this
+                                       program whose canonical integers stay below 2^key_bits (1 .. 64) on every row; a tuple is
+                                       packed on both sides.  At most 16 such columns."""
 
     def __init__(self, input_cols, main_cols, periodic_cols=()):
         if not 1 <= input_cols < main_cols:
@@ -583,6 +612,7 @@ class MainProgram:
         self.ops, self.consts, self.cols = [], [], []    # cols: (kind, num_op, den_op, pad)
         self._const_at = {}
         self._open = None                    # the chain group between chain() and step()
+        self.lookups = False                 # multiplicity() was called: check() mirrors the decoder of the _lk entry points
 
     def _emit(self, op, a, b):
         self.ops.append((op, a, b))
@@ -663,6 +693,17 @@ class MainProgram:
     def product(self, num, den=None):
         return self._column(MAIN_PRODUCT, num, den)
 
+    def multiplicity(self, x, table, key_bits=64):
+        """The lookup multiplicity of x in table (see the class): a COUNT column; returns its index."""
+        if table is None:
+            raise ValueError("main program: a multiplicity column needs a table value")
+        if not 1 <= key_bits <= MAIN_COUNT_MAX_KEY_BITS:
+            raise ValueError(f"main program: key_bits {key_bits} outside 1 .. {MAIN_COUNT_MAX_KEY_BITS}")
+        if sum(1 for c in self.cols if c[0] == MAIN_COUNT) >= MAIN_COUNT_MAX_COLS:
+            raise ValueError(f"main program: more than {MAIN_COUNT_MAX_COLS} multiplicity columns")
+        self.lookups = True
+        return self._column(MAIN_COUNT, x, table, key_bits)
+
     def reads(self):
         """Per op: one more than the highest derived column its value depends on (0: inputs only) - what the decoder follows."""
         return self._reads(False)
@@ -676,9 +717,13 @@ class MainProgram:
                 reads.append(max(reads[a], reads[b]) if op in (OP_ADD, OP_SUB, OP_MUL) else 0)
         return reads
 
-    def check(self, n=None):
+    def check(self, n=None, lookups=None):
         """The decoder's rules (air_statement_from_c), for a program whose lists were filled by hand too: ValueError naming the first one
-        broken.  n: the trace length a chain group's block length is held against (None: not yet known)."""
+        broken.  n: the trace length a chain group's block length is held against (None: not yet known).  lookups: whether COUNT
+        columns are known - the decoder of the _lk entry points, where the program would be routed after multiplicity() declared one
+        (None: self.lookups); otherwise kind 6 is an unknown kind, as for the _rec entry points."""
+        lookups = self.lookups if lookups is None else lookups
+        n_count = 0
         if self._open is not None:
             raise ValueError("main program: a chain group is open: g.step([...]) closes it")
         if self.input_cols < 1 or not self.cols or self.input_cols + len(self.cols) != self.main_cols:
@@ -694,8 +739,22 @@ class MainProgram:
         g0 = g_end = 0      # the chain group that column k belongs to is [g0, g_end), when k < g_end
         for k, (kind, num_op, den_op, pad) in enumerate(self.cols):
             den = den_op != AUX_NO_DEN
-            if not MAIN_VALUE <= kind <= MAIN_CHAIN:
+            if not MAIN_VALUE <= kind <= (MAIN_COUNT if lookups else MAIN_CHAIN):
                 raise ValueError(f"main program: derived column {k} has an unknown kind")
+            if kind == MAIN_COUNT:
+                if not den:
+                    raise ValueError(f"main program: derived column {k} is a COUNT column without a table (den_op names the table value)")
+                if not 1 <= pad <= MAIN_COUNT_MAX_KEY_BITS:
+                    raise ValueError(f"main program: derived column {k} is a COUNT column with key_bits = {pad} (1 .. {MAIN_COUNT_MAX_KEY_BITS})")
+                if not (0 <= num_op < len(self.ops) and 0 <= den_op < len(self.ops)):
+                    raise ValueError(f"main program: derived column {k} names an op beyond the program")
+                r = max(reads[num_op], reads[den_op])
+                if r > k:
+                    raise ValueError(f"main program: derived column {k} reads derived column {r - 1}, which is not an earlier one")
+                n_count += 1
+                if n_count > MAIN_COUNT_MAX_COLS:
+                    raise ValueError(f"main program: derived column {k} is the program's COUNT column number {n_count} (at most {MAIN_COUNT_MAX_COLS})")
+                continue
             if kind == MAIN_CHAIN:
                 log, j = pad & 255, pad >> 8
                 if k >= g_end:
@@ -740,7 +799,8 @@ class MainProgram:
         """The whole main segment in Python integers (the semantics of sp_air_prove_main): input_rows = n x input_cols field elements;
         returns an (n, main_cols) numpy object array.  Columns in index order, each op one vectorised numpy operation, evaluated when the
         first column that needs it is built (the columns it loads are complete by then).  ValueError on a zero denominator.  A chain
-        group is a loop over the rows t of a block, each step vectorised over the n / period blocks."""
+        group is a loop over the rows t of a block, each step vectorised over the n / period blocks.  A COUNT column is a dictionary
+        count of X, read on the first row of each table value; ValueError on a key at or above 2^key_bits."""
         import numpy as np
         self.check(len(input_rows))
         rows = input_rows if not isinstance(input_rows, np.ndarray) else input_rows.astype(object)
@@ -817,6 +877,18 @@ class MainProgram:
                         m[rows + t, first + j] = state[j]
                     if t + 1 < period:   # all w next values from the state of row t, assigned together
                         state = run([self.cols[k + j][1] for j in range(w)], rows + t, first, state)
+                continue
+            if kind == MAIN_COUNT:
+                xs, ts = [int(v) for v in need(num_op)], [int(v) for v in need(den_op)]
+                if any(v >> pad for v in xs) or any(v >> pad for v in ts):
+                    raise ValueError("main program: a lookup key is out of range on some row")
+                counts, seen = {}, set()
+                for v in xs:
+                    counts[v] = counts.get(v, 0) + 1
+                col = m[:, self.input_cols + k]
+                for i, v in enumerate(ts):
+                    col[i] = 0 if v in seen else counts.get(v, 0)
+                    seen.add(v)
                 continue
             t = need(num_op)
             if den_op != AUX_NO_DEN:
@@ -1254,6 +1326,7 @@ class AirBuilder:
             m_desc, m_keep = main_desc(self.main.input_cols, self.main.ops, self.main.consts, self.main.cols)
             d.main_desc = m_desc
             d.main_needs_rec = any(c[0] == MAIN_CHAIN for c in self.main.cols) or any(op == OP_PERIODIC for op, _, _ in self.main.ops)
+            d.main_needs_lk = any(c[0] == MAIN_COUNT for c in self.main.cols)
             keep = keep + (m_desc, m_keep)
         return d, keep
 
@@ -1662,3 +1735,66 @@ def mimc_blocks_digest(messages, s, keys, width=1):
 def mimc_blocks_inputs(n, s, rng):
     """(n, 1) Python ints from rng.randrange: a message on every row = 0 (mod s), the caller's filler on the others."""
     return [[rng.randrange(P)] for _ in range(n)]
+
+
+# ---- lookup multiplicities: two worked examples -----------------------------------------------------------------------------------
+def _logup_sum(b, looked_up, aux_looked_up, m_col, s_col):
+    """The LogUp running sum of table_lookup for a looked-up value given as an expression: column s_col, s_0 = 0, s' = s + m / (gamma -
+    T) - 1 / (gamma - X) with T periodic column 0, its constraint (degree 3, no exempted row) and its boundary."""
+    gamma = b.rap(0)
+    ga, gt = gamma - looked_up, gamma - b.periodic(0, 0)
+    b.constraint((b.load(1, s_col) - b.load(0, s_col)) * gt * ga - b.load(0, m_col) * ga + gt, degree=3, exemptions=0)
+    b.boundary(s_col, 0, 0)
+    g = b.aux.rap(0)
+    xa, xt = g - aux_looked_up, g - b.aux.table(0, 0)
+    b.aux.running_sum(b.aux.load(0, m_col) * xa - xt, xt * xa)
+
+
+def table_lookup_main(n, table, key_bits=64):
+    """table_lookup with main_inputs=1 (sp_air_prove_lk): the caller uploads the looked-up column a alone, and the device builds m =
+    multiplicity(a, T, key_bits) - every a_i and every table entry below 2^key_bits - and, as before, the running sum.  The same
+    statement, the same trace (table_lookup_trace) and the same proof as table_lookup from the whole table."""
+    if len(table) > n:
+        raise ValueError(f"table_lookup_main: {len(table)} table entries on {n} rows")
+    b = AirBuilder(2, [0, 1], 2, aux_cols=1, n_rap=1, aux_kind=AUX_PROGRAM, periodic=[table], main_inputs=1)
+    b.main.multiplicity(b.main.load(0, 0), b.main.periodic(0, 0), key_bits)
+    _logup_sum(b, b.load(0, 0), b.aux.load(0, 0), 1, 2)
+    return b
+
+
+def table_lookup_main_inputs(n, table, rng):
+    """(n, 1) Python ints: n entries of the table, drawn with rng.randrange."""
+    return [[int(table[rng.randrange(len(table))]) % P] for _ in range(n)]
+
+
+def xor_lookup_table(bits):
+    """The 2^(2 bits) packed triples a + 2^bits b + 2^(2 bits) (a xor b), in the order of a + 2^bits b."""
+    return [a + (b << bits) + ((a ^ b) << (2 * bits)) for b in range(1 << bits) for a in range(1 << bits)]
+
+
+def xor_lookup(n, bits=4):
+    """c_i = a_i xor b_i on every row, for `bits`-bit a and b, by one lookup of the packed triple a + 2^bits b + 2^(2 bits) c into the
+    table of all 2^(2 bits) such triples (periodic column 0; at most n of them).  Inputs a, b, c (columns 0 - 2); column 3 is m =
+    multiplicity(a + 2^bits b + 2^(2 bits) c, T, 3 bits), built on the device; the auxiliary column 4 is the LogUp running sum of
+    table_lookup over the packed value.  A row whose c is not a xor b - or whose a or b has more than `bits` bits, while the packed
+    value stays below 2^(3 bits) - packs to no table entry, is counted nowhere, and the sum does not close."""
+    table = xor_lookup_table(bits)
+    if len(table) > n:
+        raise ValueError(f"xor_lookup: {len(table)} table entries on {n} rows")
+    b = AirBuilder(4, [0, 1], 2, aux_cols=1, n_rap=1, aux_kind=AUX_PROGRAM, periodic=[table], main_inputs=3)
+
+    def packed(load):
+        return load(0, 0) + load(0, 1) * (1 << bits) + load(0, 2) * (1 << (2 * bits))
+
+    b.main.multiplicity(packed(b.main.load), b.main.periodic(0, 0), 3 * bits)
+    _logup_sum(b, packed(b.load), packed(b.aux.load), 3, 4)
+    return b
+
+
+def xor_lookup_inputs(n, bits, rng):
+    """(n, 3) Python ints [a, b, a xor b] with a, b from rng.randrange(2^bits)."""
+    rows = []
+    for _ in range(n):
+        a, b = rng.randrange(1 << bits), rng.randrange(1 << bits)
+        rows.append([a, b, a ^ b])
+    return rows

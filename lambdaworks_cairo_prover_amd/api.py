@@ -242,16 +242,18 @@ class Context:
         """sp_air_main_trace: the whole main segment the prover would commit for a desc with a main-trace program (AirBuilder(...,
         main_inputs=I)), built on the device from the input columns: (n, main_cols, 32) uint8 in the context encoding.  No commitment.
         A program with a chain column or a read of a periodic column (air.needs_rec) goes to sp_air_main_trace_rec with the
-        descriptor's sp_air_ext, which carries the periodic columns."""
+        descriptor's sp_air_ext, which carries the periodic columns; one with a lookup multiplicity (air.needs_lk) to
+        sp_air_main_trace_lk, with the same arguments."""
         main = getattr(desc, "main_desc", None)
         if main is None:
             raise ValueError("air_main_trace: the descriptor carries no main program (AirBuilder(..., main_inputs=...))")
         ptr, n, keep = self._air_rows(desc, inputs)
         out = np.empty((n, desc.main_cols, 32), dtype=np.uint8)
         from . import air
-        if air.needs_rec(desc):
+        suffix = air.main_suffix(desc)
+        if suffix != "main":
             ext = air.ext_of(desc)
-            check(self._lib.sp_air_main_trace_rec(self._h, ctypes.byref(desc), ctypes.byref(ext), ctypes.byref(main), ptr, ctypes.c_uint64(n), _u8p(out)))
+            check(getattr(self._lib, f"sp_air_main_trace_{suffix}")(self._h, ctypes.byref(desc), ctypes.byref(ext), ctypes.byref(main), ptr, ctypes.c_uint64(n), _u8p(out)))
         else:
             check(self._lib.sp_air_main_trace(self._h, ctypes.byref(desc), ctypes.byref(main), ptr, ctypes.c_uint64(n), _u8p(out)))
         return out
@@ -565,13 +567,15 @@ def air_boundary_resolve(bvals, rap):
 def air_main_check(desc, n, main=None):
     """sp_air_main_check (host): the decoder's verdict on a main-trace program (main, or desc.main_desc) for this AIR and n rows; raises
     SpError with its refusal (SP_E_INVALID_ARG, or SP_E_UNSUPPORTED beside aux_kind 1 or 2).  A program with a chain column or a read of
-    a periodic column (air.needs_rec) is judged by sp_air_main_check_rec, beside the descriptor's periodic columns."""
+    a periodic column (air.needs_rec) is judged by sp_air_main_check_rec, beside the descriptor's periodic columns; one with a lookup
+    multiplicity (air.needs_lk) by sp_air_main_check_lk."""
     from . import air
     own = getattr(desc, "main_desc", None)
     main = own if main is None else main
-    if main is own and air.needs_rec(desc):
+    suffix = air.main_suffix(desc) if main is own else "main"
+    if suffix != "main":
         ext = air.ext_of(desc)
-        check(_lib.load().sp_air_main_check_rec(ctypes.byref(desc), ctypes.byref(ext), ctypes.byref(main), ctypes.c_uint64(n)))
+        check(getattr(_lib.load(), f"sp_air_main_check_{suffix}")(ctypes.byref(desc), ctypes.byref(ext), ctypes.byref(main), ctypes.c_uint64(n)))
         return
     check(_lib.load().sp_air_main_check(ctypes.byref(desc), ctypes.byref(main), ctypes.c_uint64(n)))
 
@@ -581,6 +585,13 @@ def air_main_chain_limits():
     out = (ctypes.c_uint32 * 2)()
     check(_lib.load().sp_air_main_chain_limits(out))
     return {"width": int(out[0]), "shift": int(out[1])}
+
+
+def air_main_count_limits():
+    """sp_air_main_count_limits: {"key_bits": the most key bits of a COUNT column, "columns": the most COUNT columns of one main program}."""
+    out = (ctypes.c_uint32 * 2)()
+    check(_lib.load().sp_air_main_count_limits(out))
+    return {"key_bits": int(out[0]), "columns": int(out[1])}
 
 
 def air_stride_eval(period, offset, exemptions, n, point):

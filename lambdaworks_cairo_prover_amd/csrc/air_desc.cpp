@@ -151,8 +151,9 @@ std::string validate_aux_program(const AirAuxHost& aux, uint32_t main_cols, uint
 // earlier ops, LOADs of main columns at shifts 0 .. 7), the columns' kinds, and - following the operands - which derived columns
 // the ops behind each column load: only earlier ones.  rec (the _rec entry points): op 6 over the statement's n_periodic periodic
 // columns and SP_AIR_MAIN_CHAIN columns too - groups with j = 0, 1, .. and one l, seeds that read nothing of their group, steps that
-// read it at shift 0 only; without rec kind 5 is an unknown kind and op 6 a malformed op.
-std::string main_from_c(const AirDescHost& air, const sp_air_main_desc* m, uint64_t n, uint32_t n_periodic, bool rec, AirMainHost& out) {
+// read it at shift 0 only; without rec kind 5 is an unknown kind and op 6 a malformed op.  lk (the _lk entry points, with rec):
+// SP_AIR_MAIN_COUNT columns too - a table, key_bits in 1 .. 64, at most 16 of them; without lk kind 6 is an unknown kind.
+std::string main_from_c(const AirDescHost& air, const sp_air_main_desc* m, uint64_t n, uint32_t n_periodic, bool rec, bool lk, AirMainHost& out) {
     if (m->size != sizeof(sp_air_main_desc)) return "main program: sp_air_main_desc.size is not sizeof(sp_air_main_desc)";
     if (!m->ops || !m->consts || !m->cols) return "main program: null ops, consts or cols";
     if (m->input_cols == 0 || m->n_cols == 0 || (uint64_t)m->input_cols + m->n_cols != air.main_cols)
@@ -183,11 +184,22 @@ std::string main_from_c(const AirDescHost& air, const sp_air_main_desc* m, uint6
     std::vector<AirMainColumnHost> cols;
     cols.reserve(m->n_cols);
     uint32_t g0 = 0, g_end = 0;   // the chain group that column k belongs to is [g0, g_end), when k < g_end
+    uint32_t n_count = 0;
     for (uint32_t k = 0; k < m->n_cols; ++k) {
         const sp_air_main_column& c = m->cols[k];
         const std::string who = "main program: derived column " + std::to_string(k);
         const bool den = c.den_op != SP_AIR_AUX_NO_DEN;
-        if (c.kind > (rec ? SP_AIR_MAIN_CHAIN : SP_AIR_MAIN_PRODUCT)) return who + " has an unknown kind";
+        if (c.kind > (lk ? SP_AIR_MAIN_COUNT : rec ? SP_AIR_MAIN_CHAIN : SP_AIR_MAIN_PRODUCT)) return who + " has an unknown kind";
+        if (c.kind == SP_AIR_MAIN_COUNT) {
+            if (!den) return who + " is a COUNT column without a table (den_op names the table value)";
+            if (c.pad == 0 || c.pad > AIR_MAIN_COUNT_MAX_KEY_BITS) return who + " is a COUNT column with key_bits = " + std::to_string(c.pad) + " (1 .. 64)";
+            if (c.num_op >= n_ops || c.den_op >= n_ops) return who + " names an op beyond the program";
+            const uint32_t r = std::max(reads[c.num_op], reads[c.den_op]);
+            if (r > k) return who + " reads derived column " + std::to_string(r - 1) + ", which is not an earlier one";
+            if (++n_count > AIR_MAIN_COUNT_MAX_COLS) return who + " is the program's COUNT column number " + std::to_string(n_count) + " (at most 16)";
+            cols.push_back(AirMainColumnHost{c.kind, c.num_op, c.den_op, 0u, r, 0u, 0u, c.pad});
+            continue;
+        }
         if (c.kind == SP_AIR_MAIN_CHAIN) {
             const uint32_t l = c.pad & 255u, j = c.pad >> 8;
             if (k >= g_end) {   // it must open a group: the run of CHAIN columns with j = 1, 2, .. behind it
@@ -253,10 +265,11 @@ bool air_boundary_from_c(const sp_air_boundary_desc* d, uint32_t n_boundary, uin
 
 std::string air_statement_from_c(const sp_air_desc* d, const sp_air_aux_desc* aux, const sp_air_periodic_desc* periodic, const sp_air_stride_desc* strides,
                                  const sp_air_boundary_desc* bvals, bool aux_reads_periodic, uint64_t n, AirStatement& st, const sp_air_main_desc* main,
-                                 bool main_rec) {
+                                 bool main_rec, bool main_lk) {
     AirDescHost& air = st.air;
     st.aux_reads_periodic = aux_reads_periodic;
-    st.main_rec = main_rec;
+    st.main_rec = main_rec || main_lk;
+    st.main_lk = main_lk;
     if (!air_desc_from_c(d, air)) return "malformed AIR descriptor (1 .. 8 frame rows, 1 .. 64 transition constraints, every count with its array)";
     if (periodic && !air_periodic_from_c(periodic, n, st.periodic.emplace()))
         return "malformed periodic columns (at most 64, each a power-of-two number of values, at most the trace length)";
@@ -273,8 +286,8 @@ std::string air_statement_from_c(const sp_air_desc* d, const sp_air_aux_desc* au
     if (air.consts.size() + air.n_rap > 65535) return "constants and RAP challenges exceed the 16-bit operand range";
     if (air.ops.size() > AIR_LIMIT_OPS) return "more than 65535 ops";
     if (main) {
-        // (only the _rec entry points let a main program hold chain columns and read the periodic columns)
-        const std::string refused = main_from_c(air, main, n, st.n_periodic(), st.main_rec, st.main.emplace());
+        // (only the _rec and _lk entry points let a main program hold chain columns and read the periodic columns, only _lk COUNT columns)
+        const std::string refused = main_from_c(air, main, n, st.n_periodic(), st.main_rec, st.main_lk, st.main.emplace());
         if (!refused.empty()) return refused;
     }
     // (only the _pub entry points let an auxiliary program read the periodic columns: 0 of them from everywhere else)

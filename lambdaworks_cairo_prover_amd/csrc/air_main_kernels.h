@@ -23,6 +23,11 @@ int air_main_terms(hipStream_t st, const fe* trace, uint64_t n, const AirOpDev* 
 constexpr uint32_t AIR_MAIN_CHAIN_WIDTH = 16;
 int air_main_chain(hipStream_t st, fe* trace, uint64_t n, uint32_t log_s, uint32_t first_col, uint32_t w, const AirOpDev* seed_ops, uint32_t n_seed,
                    const AirOpDev* step_ops, uint32_t n_step, const fe* consts, const AirPeriodicCol* pcols = nullptr, const fe* pvals = nullptr);
+// One COUNT column (a lookup multiplicity): kx the n looked-up keys in ascending order, kt the n table keys in ascending order - sorted
+// stably, rows[p] the row that table key p came from - all from air_aux_sort_terms and radix_sort_pairs_u64.  One lane per p: on the
+// head of a run of equal table keys (p == 0 or kt[p] != kt[p - 1]) z = upper_bound(kx, kt[p]) - lower_bound(kx, kt[p]), elsewhere
+// z = 0; col[rows[p]] = z as a field element.  rows is a permutation of 0 .. n - 1: every cell of col is written once.  n < 2^32.
+int air_main_count(hipStream_t st, const uint64_t* kx, const uint64_t* kt, const uint32_t* rows, uint64_t n, fe* col);
 // INV_OR_ZERO, before the batch inversion: for k < n_inv, with (slot, col) = tab[2 k], tab[2 k + 1]: where ws[slot * n + i] is zero it
 // becomes one and cols[col * n + i] = 0, elsewhere cols[col * n + i] = 1.  The inversion then meets no zero of these, and
 // air_aux_apply_den leaves 0 or 1 / N in the column.

@@ -105,6 +105,42 @@ int air_main_chain(hipStream_t st, fe* trace, uint64_t n, uint32_t log_s, uint32
     return SP_OK;
 }
 
+// ---- lookup multiplicities: the join of the sorted looked-up keys against the sorted table keys ---------------------------------
+// One lane per sorted table position p.  The head of a run of equal table keys - the stable sort put the run's lowest row there -
+// counts its key in the sorted looked-up keys with two binary searches, interleaved in one loop: each step of either is a dependent
+// load of 8 bytes out of an array that the sort has just left in the L2, and the two chains overlap.  The lanes of a run behind its
+// head store zero; a table of period L keeps n / L - 1 of every n / L lanes out of the loop, which costs nothing but their idle issue
+// slots.  Every lane stores one cell, 32 bytes - a sector of its own - at the row the sort carried along: rows is a permutation of
+// 0 .. n - 1 (the sort permutes what the key pass wrote, whatever the keys), so every cell is written exactly once and nothing needs
+// a memset.  lo and hi stay in [0, n] and mid in [0, n) whatever the arrays hold - keys that were out of range leave kx ordered by
+// its low bits only, the searches then end somewhere inside the array and the call is an error already.
+__global__ void __launch_bounds__(256) air_main_count_kernel(const uint64_t* __restrict__ kx, const uint64_t* __restrict__ kt, const uint32_t* __restrict__ rows,
+                                                             uint64_t n, fe* __restrict__ col) {
+    const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    const uint64_t key = kt[p];
+    const uint32_t row = rows[p];
+    uint64_t z = 0;
+    if (p == 0 || kt[p - 1] != key) {
+        uint64_t lo0 = 0, hi0 = n, lo1 = 0, hi1 = n;   // lower bound: first kx >= key; upper bound: first kx > key
+        while (lo0 < hi0 || lo1 < hi1) {
+            const uint64_t m0 = lo0 < hi0 ? lo0 + ((hi0 - lo0) >> 1) : 0, m1 = lo1 < hi1 ? lo1 + ((hi1 - lo1) >> 1) : 0;
+            const uint64_t a = kx[m0], b = kx[m1];
+            if (lo0 < hi0) { if (a < key) lo0 = m0 + 1; else hi0 = m0; }
+            if (lo1 < hi1) { if (b <= key) lo1 = m1 + 1; else hi1 = m1; }
+        }
+        z = lo1 >= lo0 ? lo1 - lo0 : 0;
+    }
+    if (row < n) fe_st(col + row, fe_from_u64(z));
+}
+
+int air_main_count(hipStream_t st, const uint64_t* kx, const uint64_t* kt, const uint32_t* rows, uint64_t n, fe* col) {
+    if (n == 0 || n >= (1ull << 32) || !kx || !kt || !rows || !col) return SP_E_INVALID_ARG;
+    hipLaunchKernelGGL(air_main_count_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, kx, kt, rows, n, col);
+    SP_HIP_CHECK(hipGetLastError());
+    return SP_OK;
+}
+
 // Both stores happen on every row, with values chosen by mask: no lane takes a path of its own.
 __global__ void __launch_bounds__(256) air_main_zero_guard_kernel(fe* __restrict__ ws, fe* __restrict__ cols, const uint32_t* __restrict__ tab, uint64_t n) {
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;

@@ -620,6 +620,11 @@ int StarkProver::commit_aux_program(const AirStatement& st, const std::vector<fe
 // steps', each with an OUT per group column, and one launch of air_main_chain; nothing of the group is read before that launch is
 // over, which the stream's order guarantees.  It takes no workspace.  The periodic columns an op 6 reads (st.periodic) ride in this
 // upload block as they do in the auxiliary program's: round 2's block comes too late.
+// A COUNT column (SP_AIR_MAIN_COUNT, st.main_lk) is a chunk of its own too: two programs, X's and T's, each with the one OUT of a key
+// pass; two launches of air_aux_sort_terms (keys out of Montgomery form, the row beside each), two radix sorts - the table's carries
+// its rows - and one launch of air_main_count, which writes every cell of the column.  Its arrays (4 x [n] keys, 4 x [n] rows, the
+// radix histograms) lie at the start of the same workspace: the chunk before it is over, the chunk behind it starts after the count.
+// The key-range flag is a word of its own at the end of the workspace, so that no batch inversion before or behind overwrites it.
 int StarkProver::build_main_program(const AirStatement& st, const uint8_t* inputs) {
     const AirMainHost& mp = *st.main;
     const uint32_t I = mp.input_cols, K = (uint32_t)mp.cols.size();
@@ -642,9 +647,11 @@ int StarkProver::build_main_program(const AirStatement& st, const uint8_t* input
         uint32_t chain_log = 0;                                      // a chain group (kc columns, blocks of 2^chain_log rows): ops is the step program,
         std::vector<AirOpDev> seed_ops;                              //   seed_ops the seeds'
         size_t o_seed = 0;
+        uint32_t count_bits = 0;                                     // a COUNT column (kc = 1) with this key_bits: ops is X's program, seed_ops T's
     };
     std::vector<Chunk> chunks;
     uint32_t max_slots = 0, max_inv = 0;
+    bool any_count = false;
     bool any_periodic = false;
     // the program with an OUT behind every op whose value is wanted, slots by air_assign_slots (as commit_aux_program)
     auto program_with_outs = [&](const std::vector<std::vector<uint32_t>>& outs, std::vector<AirOpDev>& dev, bool& reads_periodic) -> int {
@@ -682,9 +689,25 @@ int StarkProver::build_main_program(const AirStatement& st, const uint8_t* input
             chunks.push_back(std::move(ch));
             continue;
         }
+        if (mp.cols[k0].kind == SP_AIR_MAIN_COUNT) {
+            const AirMainColumnHost& c = mp.cols[k0];
+            std::vector<std::vector<uint32_t>> table(n_src);
+            if (c.key_bits == 0 || c.key_bits > 64 || c.den_op >= n_src) { sp_set_error("commit_main_program: a COUNT column the decoder should have refused"); return SP_E_INVALID_ARG; }
+            outs[c.num_op].push_back(AIR_AUX_DEN_TAG);
+            table[c.den_op].push_back(AIR_AUX_DEN_TAG);
+            ch.kc = 1;
+            ch.count_bits = c.key_bits;
+            SP_TRY(program_with_outs(outs, ch.ops, ch.periodic));
+            SP_TRY(program_with_outs(table, ch.seed_ops, ch.periodic));
+            any_count = true;
+            k0 += 1;
+            chunks.push_back(std::move(ch));
+            continue;
+        }
         struct BitGroup { uint32_t num_op; std::vector<uint32_t> entries; };
         std::vector<BitGroup> groups;
-        for (; ch.kc < chunk && k0 + ch.kc < K && mp.cols[k0 + ch.kc].reads <= k0 && mp.cols[k0 + ch.kc].kind != SP_AIR_MAIN_CHAIN; ++ch.kc) {
+        for (; ch.kc < chunk && k0 + ch.kc < K && mp.cols[k0 + ch.kc].reads <= k0 && mp.cols[k0 + ch.kc].kind != SP_AIR_MAIN_CHAIN &&
+               mp.cols[k0 + ch.kc].kind != SP_AIR_MAIN_COUNT; ++ch.kc) {
             const AirMainColumnHost& c = mp.cols[k0 + ch.kc];
             const bool scanned = c.kind == SP_AIR_MAIN_SUM || c.kind == SP_AIR_MAIN_PRODUCT;
             ch.kinds.push_back(c.kind == SP_AIR_MAIN_SUM ? 1u : 0u);
@@ -757,9 +780,16 @@ int StarkProver::build_main_program(const AirStatement& st, const uint8_t* input
         std::memcpy(up.data() + o_pcols, pcols.data(), sizeof(AirPeriodicCol) * Kp);
         for (uint32_t k = 0; k < Kp; ++k) std::memcpy(up.data() + o_pvals + sizeof(fe) * pcols[k].off, periodic->cols[k].data(), sizeof(fe) * periodic->cols[k].size());
     }
-    // --- workspace: [max_slots][n] slots, [max_inv][n] batch-inversion scratch, [chunk][nb] scan block totals
-    SP_TRY(grow(od_.auxp_ws, ((uint64_t)max_slots + max_inv) * n_ + (uint64_t)chunk * nb));
+    // --- workspace, the larger of what a row-local chunk and what a COUNT column takes, and behind it the word of the key-range flag:
+    //     chunks: [max_slots][n] slots, [max_inv][n] batch-inversion scratch, [chunk][nb] scan block totals
+    //     counts: 4 x [n] keys, 4 x [n] rows, the radix sort's histograms (all in units of 32 bytes)
+    if (any_count && n_ >= (1ull << 32)) { sp_set_error("commit_main_program: COUNT columns need a trace of fewer than 2^32 rows"); return SP_E_INVALID_ARG; }
+    const uint64_t keys_el = (n_ + 3) / 4, idx_el = (n_ + 7) / 8;
+    const uint64_t ws_count = any_count ? 4 * keys_el + 4 * idx_el + (radix_sort_workspace_bytes(n_) + sizeof(fe) - 1) / sizeof(fe) : 0;
+    const uint64_t ws_elems = std::max(((uint64_t)max_slots + max_inv) * n_ + (uint64_t)chunk * nb, ws_count);
+    SP_TRY(grow(od_.auxp_ws, ws_elems + 1));
     SP_TRY(ensure_host_flags());
+    host_flags().auxp_bad_key = 0;
     // --- ingest: the plain staged copy (the inputs are a small part of the table; their raw rows sit in the segment's LDE area,
     //     which is written only by the transforms behind the last chunk), then rows -> columns [0, I)
     if (mp.input_location == 1) {
@@ -773,6 +803,17 @@ int StarkProver::build_main_program(const AirStatement& st, const uint8_t* input
     SP_HIP_CHECK(hipMemsetAsync(c_->d_flag, 0, sizeof(int), c_->stream));
     const fe* consts_dev = reinterpret_cast<const fe*>(od_.auxp_buf.p + o_consts);
     fe* ws = od_.auxp_ws.p;
+    int* key_flag = reinterpret_cast<int*>(ws + ws_elems);
+    if (any_count) SP_HIP_CHECK(hipMemsetAsync(key_flag, 0, sizeof(int), c_->stream));
+    uint64_t* kx_a = reinterpret_cast<uint64_t*>(ws);
+    uint64_t* kx_b = reinterpret_cast<uint64_t*>(ws + keys_el);
+    uint64_t* kt_a = reinterpret_cast<uint64_t*>(ws + 2 * keys_el);
+    uint64_t* kt_b = reinterpret_cast<uint64_t*>(ws + 3 * keys_el);
+    uint32_t* ix_a = reinterpret_cast<uint32_t*>(ws + 4 * keys_el);
+    uint32_t* ix_b = reinterpret_cast<uint32_t*>(ws + 4 * keys_el + idx_el);
+    uint32_t* it_a = reinterpret_cast<uint32_t*>(ws + 4 * keys_el + 2 * idx_el);
+    uint32_t* it_b = reinterpret_cast<uint32_t*>(ws + 4 * keys_el + 3 * idx_el);
+    void* radix_ws = ws + 4 * keys_el + 4 * idx_el;
     fe* scratch = ws + (uint64_t)max_slots * n_;
     fe* block_tot = scratch + (uint64_t)max_inv * n_;
     auto tab = [&](size_t at) { return reinterpret_cast<const uint32_t*>(od_.auxp_buf.p + at); };
@@ -785,6 +826,17 @@ int StarkProver::build_main_program(const AirStatement& st, const uint8_t* input
             SP_TRY(air_main_chain(c_->stream, d_trace_, n_, ch.chain_log, I + ch.k0, ch.kc, reinterpret_cast<const AirOpDev*>(od_.auxp_buf.p + ch.o_seed),
                                   (uint32_t)ch.seed_ops.size(), ops_dev, (uint32_t)ch.ops.size(), consts_dev, ch.periodic ? pcols_dev : nullptr,
                                   ch.periodic ? pvals_dev : nullptr));
+            continue;
+        }
+        if (ch.count_bits) {   // key passes, sorts (the sorted pairs end up in kx_b / ix_b and kt_b / it_b), the join
+            const AirPeriodicCol* pc = ch.periodic ? pcols_dev : nullptr;
+            const fe* pv = ch.periodic ? pvals_dev : nullptr;
+            SP_TRY(air_aux_sort_terms(c_->stream, d_trace_, n_, ops_dev, (uint32_t)ch.ops.size(), consts_dev, nullptr, kx_a, ix_a, ch.count_bits, key_flag, pc, pv));
+            SP_TRY(air_aux_sort_terms(c_->stream, d_trace_, n_, reinterpret_cast<const AirOpDev*>(od_.auxp_buf.p + ch.o_seed), (uint32_t)ch.seed_ops.size(), consts_dev,
+                                      nullptr, kt_a, it_a, ch.count_bits, key_flag, pc, pv));
+            SP_TRY(radix_sort_pairs_u64(c_->stream, kx_a, kx_b, ix_a, ix_b, n_, ch.count_bits, radix_ws));
+            SP_TRY(radix_sort_pairs_u64(c_->stream, kt_a, kt_b, it_a, it_b, n_, ch.count_bits, radix_ws));
+            SP_TRY(air_main_count(c_->stream, kx_b, kt_b, it_b, n_, cols));
             continue;
         }
         SP_TRY(air_main_terms(c_->stream, d_trace_, n_, ops_dev, (uint32_t)ch.ops.size(), consts_dev, cols, ws, ch.periodic ? pcols_dev : nullptr,
@@ -800,10 +852,13 @@ int StarkProver::build_main_program(const AirStatement& st, const uint8_t* input
     }
     // the zero-denominator flag rides behind the columns; whoever reads the root (or the table) back waits for it
     SP_HIP_CHECK(hipMemcpyAsync(&host_flags().auxp_zero_den, c_->d_flag, sizeof(int), hipMemcpyDeviceToHost, c_->stream));
+    if (any_count) SP_HIP_CHECK(hipMemcpyAsync(&host_flags().auxp_bad_key, key_flag, sizeof(int), hipMemcpyDeviceToHost, c_->stream));
     return SP_OK;
 }
 
 static const char* const MAIN_PROGRAM_ZERO_DEN = "commit_main_program: a derived main column's denominator is zero on some row";
+static const char* const MAIN_PROGRAM_KEY_RANGE =
+    "commit_main_program: a lookup key is out of range on some row (X and T of a COUNT column must be below 2^key_bits as canonical integers)";
 
 int StarkProver::commit_main_program(const AirStatement& st, const uint8_t* inputs, uint8_t root_out[32]) {
     if (!root_out) return SP_E_INVALID_ARG;
@@ -817,6 +872,7 @@ int StarkProver::commit_main_program(const AirStatement& st, const uint8_t* inpu
         (void)hipGetLastError();
         return rc;
     }
+    if (host_flags().auxp_bad_key == AIR_AUX_FLAG_KEY_RANGE) { sp_set_error(MAIN_PROGRAM_KEY_RANGE); return SP_E_INVALID_ARG; }   // (first, as commit_aux_program)
     if (host_flags().auxp_zero_den) { sp_set_error(MAIN_PROGRAM_ZERO_DEN); return SP_E_ZERO_INVERSE; }
     return finish_upload_stats(0, st.main->input_location == 1 ? 0 : (uint64_t)n_ * st.main->input_cols * 32, 0.0, host_ms, 0);
 }
@@ -834,6 +890,7 @@ int StarkProver::main_program_table(const AirStatement& st, const uint8_t* input
         (void)hipGetLastError();
         return rc;
     }
+    if (host_flags().auxp_bad_key == AIR_AUX_FLAG_KEY_RANGE) { sp_set_error(MAIN_PROGRAM_KEY_RANGE); return SP_E_INVALID_ARG; }   // (first, as commit_aux_program)
     if (host_flags().auxp_zero_den) { sp_set_error(MAIN_PROGRAM_ZERO_DEN); return SP_E_ZERO_INVERSE; }
     for (uint32_t c = 0; c < Cm_; ++c)
         for (uint64_t i = 0; i < n_; ++i) std::memcpy(rows_out + ((size_t)i * Cm_ + c) * 32, by_col.data() + ((size_t)c * n_ + i) * 32, 32);

@@ -48,7 +48,15 @@ struct Parts {
     sp_air_op rops[7] = {{0, 0, 0, 0, 0}, {6, 0, 0, 0, 0}, {0, 0, 0, 1, 0}, {0, 0, 0, 2, 0}, {4, 0, 2, 3, 0}, {2, 0, 2, 1, 0}, {0, 0, 1, 1, 0}};
     sp_air_main_column rcols[3] = {{SP_AIR_MAIN_CHAIN, 4, 0, 2}, {SP_AIR_MAIN_CHAIN, 5, 1, 2 + 256}, {SP_AIR_MAIN_VALUE, 6, SP_AIR_AUX_NO_DEN, 0}};
     sp_air_main_desc rp{};
+    // a main program with a lookup multiplicity (use 'l': through the _lk policy, 'L': through the _rec policy alone): x the one input;
+    // v = x + K (VALUE, op 6), m = COUNT of X = v in T = K with 16 key bits, the running sum of m one row ahead; and one of 17 COUNT columns
+    sp_air_op lops[5] = {{0, 0, 0, 0, 0}, {6, 0, 0, 0, 0}, {2, 0, 0, 1, 0}, {0, 0, 0, 1, 0}, {0, 0, 1, 2, 0}};
+    sp_air_main_column lcols[3] = {{SP_AIR_MAIN_VALUE, 2, SP_AIR_AUX_NO_DEN, 0}, {SP_AIR_MAIN_COUNT, 3, 1, 16}, {SP_AIR_MAIN_SUM, 4, SP_AIR_AUX_NO_DEN, 0}};
+    sp_air_main_column many_lcols[17];
+    sp_air_main_desc lp{};
     Parts() {
+        for (auto& c : many_lcols) c = sp_air_main_column{SP_AIR_MAIN_COUNT, 0, 1, 64};
+        lp.size = sizeof(sp_air_main_desc); lp.input_cols = 1; lp.n_ops = 5; lp.ops = lops; lp.n_consts = 1; lp.consts = mconsts[0].b; lp.n_cols = 3; lp.cols = lcols;
         for (uint32_t j = 0; j < 17; ++j) many_cols[j] = sp_air_aux_column{SP_AIR_AUX_SORTED, j, j, 16};
         for (int j = 0; j < 8; ++j) keys[j] = felt(100 + j);
         for (auto& c : pcols) c = sp_air_periodic_column{8, 0, keys[0].b};
@@ -64,23 +72,26 @@ struct Parts {
         rp.size = sizeof(sp_air_main_desc); rp.input_cols = 1; rp.n_ops = 7; rp.ops = rops; rp.n_consts = 1; rp.consts = mconsts[0].b; rp.n_cols = 3; rp.cols = rcols;
     }
     void with_chain() { d.main_cols = 4; }
+    void many_counts(uint32_t count) { d.main_cols = 1 + count; lp.n_ops = 2; lp.n_cols = count; lp.cols = many_lcols; }
     void with_main() { d.main_cols = 6; }
     void sorted() { d.aux_cols = 3; aux.n_ops = 5; aux.ops = sort_ops; aux.n_cols = 3; aux.cols = sort_cols; }
     void many(uint32_t groups) { d.aux_cols = groups; aux.n_ops = 17; aux.ops = many_ops; aux.n_cols = groups; aux.cols = many_cols; }
 };
 
-// use: which parts go to the decoder (x p s b m r R, upper case P: the auxiliary program may read the periodic columns; m: the main
-// program, for which the AIR gets its six main columns first)
+// use: which parts go to the decoder (x p s b m r R l L, upper case P: the auxiliary program may read the periodic columns; m: the main
+// program, for which the AIR gets its six main columns first; r / R the chain program with and without the _rec policy; l / L the
+// lookup program under the _lk policy and under the _rec policy alone)
 void run(const char* label, const char* use, bool want_ok, const std::function<void(Parts&)>& patch) {
     Parts p;
     if (std::strchr(use, 'm')) p.with_main();
-    if (std::strchr(use, 'r') || std::strchr(use, 'R')) p.with_chain();
+    if (std::strchr(use, 'r') || std::strchr(use, 'R') || std::strchr(use, 'l') || std::strchr(use, 'L')) p.with_chain();
     patch(p);
     auto has = [&](char c) { return std::strchr(use, c) != nullptr; };
     sp::AirStatement st;
     const std::string refused = sp::air_statement_from_c(&p.d, has('x') ? &p.aux : nullptr, has('p') ? &p.per : nullptr, has('s') ? &p.sd : nullptr,
                                                          has('b') ? &p.bv : nullptr, has('P'), 16, st,
-                                                         has('m') ? &p.mp : has('r') || has('R') ? &p.rp : nullptr, has('r'));
+                                                         has('m') ? &p.mp : has('r') || has('R') ? &p.rp : has('l') || has('L') ? &p.lp : nullptr,
+                                                         has('r') || has('L'), has('l'));
     const bool ok = refused.empty();
     if (ok != want_ok) { ++failures; std::printf("FAIL %-44s wanted %s, got %s\n", label, want_ok ? "accepted" : "refused", ok ? "accepted" : refused.c_str()); return; }
     std::printf("ok   %-44s %s\n", label, ok ? "accepted" : refused.substr(0, 60).c_str());
@@ -88,7 +99,13 @@ void run(const char* label, const char* use, bool want_ok, const std::function<v
     // the model on what was accepted: stride plan and zerofier, periodic columns as polynomials, boundary values under a challenge
     sp::AirStridePlan plan;
     bool fine = sp::air_stride_plan(st.air, 16, plan) && st.aux.has_value() == has('x') && st.periodic.has_value() == has('p') && st.bvals.has_value() == has('b') &&
-                (st.aux_periodic() != nullptr) == (has('P') && has('p')) && st.main.has_value() == (has('m') || has('r')) && st.main_rec == has('r') && !st.unsupported;
+                (st.aux_periodic() != nullptr) == (has('P') && has('p')) && st.main.has_value() == (has('m') || has('r') || has('l')) && st.main_rec == (has('r') || has('l')) && st.main_lk == has('l') &&
+                !st.unsupported;
+    if (st.main && has('l') && !has('r') && st.main->cols.size() == 3) {   // what the prover's chunking reads of a COUNT column
+        const auto& c = st.main->cols;
+        fine = fine && c[1].kind == SP_AIR_MAIN_COUNT && c[1].key_bits == p.lcols[1].pad && c[1].num_op == 3 && c[1].den_op == 1 && c[1].reads == 1 && c[0].key_bits == 0 &&
+               c[2].key_bits == 0 && c[2].reads == 2;
+    }
     if (st.main && has('r')) {   // what the prover's chunking reads of a chain group
         const auto& c = st.main->cols;
         fine = fine && c.size() == 3 && c[0].kind == SP_AIR_MAIN_CHAIN && c[0].chain_log == (p.rcols[0].pad & 255u) && c[0].chain_pos == 0 && c[1].chain_log == c[0].chain_log && c[1].chain_pos == 1 &&
@@ -238,6 +255,26 @@ int main() {
     run("chain: seed beyond the program", "pr", false, [](Parts& p) { p.rcols[1].den_op = 7; });
     run("chain: kind 6", "pr", false, [](Parts& p) { p.rcols[2].kind = 6; });
     run("chain: aux_kind 2", "pr", false, [](Parts& p) { p.d.aux_kind = 2; });
+    // ---- lookup multiplicities in a main program (the _lk policy)
+    run("count column", "pl", true, none);
+    run("count beside everything", "xpsbPl", true, [](Parts& p) { p.aux.n_ops = 4; });
+    run("count: 1 key bit", "pl", true, [](Parts& p) { p.lcols[1].pad = 1; });
+    run("count: 64 key bits", "pl", true, [](Parts& p) { p.lcols[1].pad = 64; });
+    run("count: 16 columns", "pl", true, [](Parts& p) { p.many_counts(16); });
+    run("count: a chain program under the _lk policy", "prl", true, none);
+    run("count: under the _rec policy alone", "pL", false, none);
+    run("count: no table", "pl", false, [](Parts& p) { p.lcols[1].den_op = SP_AIR_AUX_NO_DEN; });
+    run("count: 0 key bits", "pl", false, [](Parts& p) { p.lcols[1].pad = 0; });
+    run("count: 65 key bits", "pl", false, [](Parts& p) { p.lcols[1].pad = 65; });
+    run("count: 2^32 - 1 key bits", "pl", false, [](Parts& p) { p.lcols[1].pad = 0xFFFFFFFFu; });
+    run("count: X reads a later column", "pl", false, [](Parts& p) { p.lops[3].b = 3; });
+    run("count: T reads the column itself", "pl", false, [](Parts& p) { p.lcols[1].den_op = 4; });
+    run("count: X beyond the program", "pl", false, [](Parts& p) { p.lcols[1].num_op = 5; });
+    run("count: T beyond the program", "pl", false, [](Parts& p) { p.lcols[1].den_op = 5; });
+    run("count: 17 columns", "pl", false, [](Parts& p) { p.many_counts(17); });
+    run("count: kind 7", "pl", false, [](Parts& p) { p.lcols[2].kind = 7; });
+    run("count: op 6 without periodic columns", "l", false, none);
+    run("count: aux_kind 2", "pl", false, [](Parts& p) { p.d.aux_kind = 2; });
     run("no main column", "", false, [](Parts& p) { p.d.main_cols = 0; p.ops[2] = sp_air_op{1, 0, 0, 0, 0}; });
     run("1025 columns", "", false, [](Parts& p) { p.d.main_cols = 1024; p.ops[2] = sp_air_op{1, 0, 0, 0, 0}; });
     std::printf("%s\n", failures ? "FAILED" : "all verdicts as expected");
