@@ -80,8 +80,9 @@ const char* sp_version(void);
  * sp_air_stride_size, sp_air_stride_desc_size, sp_air_ext_size, sp_air_stride_limits, sp_air_stride_eval and sp_air_stride_table, and after them sp_air_prove_pub, sp_air_verify_pub,
  * sp_air_check_trace_pub, sp_air_boundary_desc_size and sp_air_boundary_resolve, and then sp_air_prove_main, sp_air_check_trace_main,
  * sp_air_main_trace, sp_air_main_check and sp_air_main_desc_size, then sp_air_prove_rec, sp_air_check_trace_rec, sp_air_main_trace_rec,
- * sp_air_main_check_rec and sp_air_main_chain_limits, and last sp_air_prove_lk, sp_air_check_trace_lk, sp_air_main_trace_lk, sp_air_main_check_lk
- * and sp_air_main_count_limits).  A binding compares it (and sp_air_desc_size against its own idea of the struct) when it loads the library, so
+ * sp_air_main_check_rec and sp_air_main_chain_limits, then sp_air_prove_lk, sp_air_check_trace_lk, sp_air_main_trace_lk, sp_air_main_check_lk
+ * and sp_air_main_count_limits, and last sp_air_prove_link, sp_air_check_trace_link, sp_air_main_trace_link, sp_air_main_check_link and
+ * sp_air_main_link_limits).  A binding compares it (and sp_air_desc_size against its own idea of the struct) when it loads the library, so
  * a stale build fails at load time with "rebuild the library" instead of with a missing symbol or shifted fields later. */
 #define SP_ABI_VERSION 7
 int sp_abi_version(void);
@@ -680,8 +681,9 @@ int sp_air_main_check(const sp_air_desc* air, const sp_air_main_desc* main, uint
  * on the row they leave from: a LOAD of a column of the group must have shift 0 and is the state on row i; inputs and derived columns
  * before the group at shifts 0 .. 7, wrapping modulo n; periodic columns.  The w next values are assigned together, after the whole
  * step program has run.  Columns after the group read its columns as any earlier derived column.  No denominators: seeds and steps are
- * polynomial (CONST, ADD, SUB, MUL) - an inverse S-box (x^(1/d)) or a division inside a step is out of scope, and so is a block seeded
- * from the block before it (a multi-block sponge is serial across blocks).  Refused with SP_E_INVALID_ARG and a message that names the
+ * polynomial (CONST, ADD, SUB, MUL) - an inverse S-box (x^(1/d)) or a division inside a step is out of scope.  A block seeded from the
+ * block before it (a multi-block sponge, a Merkle path) is a linked group of the _link entry points below; through these every block
+ * stands alone, and bits of pad at or above 16 count as part of j.  Refused with SP_E_INVALID_ARG and a message that names the
  * column, before anything is sized: j out of sequence or a group longer than 16, l = 0 or 2^l > n, members of a group that differ in l,
  * a step that loads its group at a shift other than 0, a seed that loads its group, any load of a later column, a chain without a seed,
  * op 6 naming a periodic column the statement does not have (or without ext->periodic).  Argument lists as sp_air_prove_main /
@@ -722,6 +724,30 @@ int sp_air_main_trace_lk(sp_ctx* ctx, const sp_air_desc* air, const sp_air_ext* 
 int sp_air_main_check_lk(const sp_air_desc* air, const sp_air_ext* ext, const sp_air_main_desc* main, uint64_t n);
 /* out[0] = the most key bits of a COUNT column (64), out[1] = the most COUNT columns of one main program (16) */
 int sp_air_main_count_limits(uint32_t out[2]);
+
+/* ---- Linked chain groups: blocks seeded from the block before (a sponge that absorbs several blocks, a Merkle path whose level
+ * k + 1 hashes level k's digest with a sibling).  Through the _link entry points - and only through them - the pad of a CHAIN column
+ * is l + 256 j + 65536 k: l = pad & 255 and j = (pad >> 8) & 255 as above, and k = pad >> 16 links 2^k consecutive blocks into a RUN of
+ * 2^(l + k) rows, aligned.  k = 0 is the group of the _rec entry points, bit for bit.  For k >= 1: l + k <= log2 n, all columns of a
+ * group carry the same k, and the seed programs may LOAD columns of their own group at shift 0.  Such a LOAD reads the CARRY: for a
+ * block whose first row is i, the state of that group column on row i - 1 (the last row of the block before) when the block is not the
+ * first of its run, and zero when it is.  A seed may read the carry of any column of its group; every other LOAD and every op 6 of a
+ * seed is evaluated on row i, as ever; the w seeds are assigned together after the whole seed program has run.  Steps are unchanged,
+ * and so is the proof: the same table gives the same bytes, and sp_air_verify* take these proofs as they are.  One lane builds one run,
+ * so a program wants n / 2^(l + k) runs in the thousands to fill the device.  The _link entry points accept everything the _lk ones do;
+ * they refuse, with SP_E_INVALID_ARG and a message that names the column, before anything is sized: k above the limit, l + k > log2 n,
+ * members of a group that differ in k, a seed that loads its group at a shift other than 0, and - with k = 0 - a seed that loads its
+ * group at all.  Argument lists as the _lk entry points. */
+int sp_air_prove_link(sp_ctx* ctx, const sp_air_desc* air, const sp_air_ext* ext, const sp_air_boundary_desc* bvals, const sp_air_main_desc* main,
+                      const void* inputs, uint64_t n, const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len);
+int sp_air_check_trace_link(sp_ctx* ctx, const sp_air_desc* air, const sp_air_ext* ext, const sp_air_boundary_desc* bvals, const sp_air_main_desc* main,
+                            const void* inputs, uint64_t n, const sp_proof_options* opt, const uint8_t* rap, sp_air_violation* out, uint32_t cap,
+                            uint32_t* n_out);
+int sp_air_main_trace_link(sp_ctx* ctx, const sp_air_desc* air, const sp_air_ext* ext, const sp_air_main_desc* main, const void* inputs, uint64_t n,
+                           uint8_t* rows_out);
+int sp_air_main_check_link(const sp_air_desc* air, const sp_air_ext* ext, const sp_air_main_desc* main, uint64_t n);
+/* out[0] = the highest k of a linked group (62), out[1] = the most columns of a linked group (16) */
+int sp_air_main_link_limits(uint32_t out[2]);
 
 /* verify::<Stark252PrimeField, A> (reference src/starks/verifier.rs:559-657) on the host CPU: 1 accept, 0 reject (also for
  * malformed proofs or descriptors). */

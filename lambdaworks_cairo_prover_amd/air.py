@@ -32,6 +32,10 @@ permutations, one per block of `period` rows - seeded on the block's first row, 
 (g.state(j), g.step([...])) -, and b.main.periodic(shift, k) reads a periodic column (round constants) from the main program.  See
 mimc_blocks below.
 
+Linked chain groups (sp_air_prove_link): g = b.main.chain(period, None, width=w, link=L) links L consecutive blocks into a run; until
+g.seed([...]) gives the seeds, g.carry(j) reads column j on the last row of the block before (zero on a run's first block).  A sponge
+over several blocks, a Merkle path.  See mimc_sponge and merkle_paths below.
+
 Lookup multiplicities (sp_air_prove_lk): b.main.multiplicity(x, table, key_bits) declares the column m of a LogUp lookup - how often
 the table value of row i occurs among the looked-up values of all rows, on the first row that holds it -, which the device builds by
 sorting both sides.  With it a lookup's whole witness comes from the inputs.  See table_lookup_main and xor_lookup below.
@@ -201,6 +205,7 @@ MAIN_VALUE, MAIN_INV_OR_ZERO, MAIN_BIT, MAIN_SUM, MAIN_PRODUCT, MAIN_CHAIN, MAIN
 MAIN_MAX_BIT = 251
 MAIN_CHAIN_MAX_WIDTH = 16            # sp_air_main_chain_limits
 MAIN_COUNT_MAX_KEY_BITS, MAIN_COUNT_MAX_COLS = 64, 16   # sp_air_main_count_limits
+MAIN_LINK_MAX_LOG, MAIN_LINK_MAX_WIDTH = 62, 16         # sp_air_main_link_limits
 INPUTS_HOST, INPUTS_DEVICE = 0, 1    # sp_air_main_desc.input_location
 
 
@@ -278,9 +283,22 @@ def needs_lk(desc):
     return bool(main.cols) and any(main.cols[k].kind == MAIN_COUNT for k in range(main.n_cols))
 
 
+def needs_link(desc):
+    """Whether a built descriptor's main program needs the _link entry points: a chain column (kind 5) whose pad carries k >= 1, runs
+    of 2^k blocks seeded from the block before."""
+    main = getattr(desc, "main_desc", None)
+    if main is None:
+        return False
+    known = getattr(desc, "main_needs_link", None)   # (AirBuilder.build() says so; a descriptor put together by hand is looked through)
+    if known is not None:
+        return known
+    return bool(main.cols) and any(main.cols[k].kind == MAIN_CHAIN and main.cols[k].pad >> 16 for k in range(main.n_cols))
+
+
 def main_suffix(desc):
-    """The entry points a descriptor's main program goes through: "lk", "rec" or "main" - the newer ones only where it needs them."""
-    return "lk" if needs_lk(desc) else "rec" if needs_rec(desc) else "main"
+    """The entry points a descriptor's main program goes through: "link", "lk", "rec" or "main" - the newer ones only where it needs
+    them."""
+    return "link" if needs_link(desc) else "lk" if needs_lk(desc) else "rec" if needs_rec(desc) else "main"
 
 
 def route(desc, call):
@@ -289,8 +307,8 @@ def route(desc, call):
     computed from the challenges or an auxiliary program that reads a table, _ext for strides, else the parts one by one (the
     verifier takes no auxiliary program).  A descriptor with a main-trace program (desc.main_desc) is proved and checked through the
     _main entry points, which take everything the _pub ones do - through the _rec ones when it holds a chain column or reads a
-    periodic column (needs_rec), through the _lk ones when it holds a lookup multiplicity (needs_lk) -; it is verified as if it had
-    none."""
+    periodic column (needs_rec), through the _lk ones when it holds a lookup multiplicity (needs_lk), through the _link ones when a
+    chain group links its blocks into runs (needs_link) -; it is verified as if it had none."""
     def ref(part):
         return None if part is None else ctypes.byref(part)
     aux, per = getattr(desc, "aux_desc", None), getattr(desc, "periodic_desc", None)
@@ -597,6 +615,13 @@ class MainProgram:
 
     Between chain() and step() no other column can be declared.  Seeds and steps are polynomial: no denominators.
 
+    Blocks seeded from the block before - a sponge that absorbs several blocks, a Merkle path - are a linked group (sp_air_prove_link):
+
+        g = chain(period, None, width=w, link=L)   L = 2^k consecutive blocks form a run of L * period rows, L * period <= n
+        g.carry(j)                 while the seeds are declared: the group's column j on the last row of the block before, and zero on
+                                   the first block of a run (a LOAD of the group at shift 0 inside a seed)
+        g.seed([seed_0, ...])      the seeds, which may read any column's carry; then g.state / g.step as above
+
     A lookup multiplicity (sp_air_prove_lk) is no row-local column either: it joins one value against another over all rows.
 
         multiplicity(X, T, key_bits)   z_i = #{ j : X(j) = T(i) } on the first row i that holds the table value T(i), 0 on its later
@@ -613,6 +638,7 @@ class MainProgram:
         self._const_at = {}
         self._open = None                    # the chain group between chain() and step()
         self.lookups = False                 # multiplicity() was called: check() mirrors the decoder of the _lk entry points
+        self.links = False                   # chain(link > 1) was called: check() mirrors the decoder of the _link entry points
 
     def _emit(self, op, a, b):
         self.ops.append((op, a, b))
@@ -623,8 +649,11 @@ class MainProgram:
             raise ValueError(f"main program: row shift {shift} outside 0 .. {AUX_MAX_SHIFT}")
         if not 0 <= col < self.input_cols + len(self.cols):
             raise ValueError(f"main program: column {col} is neither an input nor a derived column declared so far")
-        if self._open is not None and col in self._open.cols and shift != 0:
-            raise ValueError(f"main program: a step reads its own chain group at shift 0 only (column {col} at shift {shift})")
+        if self._open is not None and col in self._open.cols:
+            if self._open.seeding and self._open.link == 1:
+                raise ValueError(f"main program: a seed reads its own chain group only in a linked group (column {col}; chain(..., link=L))")
+            if shift != 0:
+                raise ValueError(f"main program: a {'seed' if self._open.seeding else 'step'} reads its own chain group at shift 0 only (column {col} at shift {shift})")
         return self._emit(OP_LOAD, shift, col)
 
     def periodic(self, shift, k):
@@ -635,20 +664,34 @@ class MainProgram:
             raise ValueError(f"main program: column {k} is not one of the AIR's {len(self.periodic_cols)} periodic columns")
         return self._emit(OP_PERIODIC, shift, k)
 
-    def chain(self, period, seeds):
-        """Opens a chain group of len(seeds) columns in blocks of `period` rows (see the class); returns its ChainGroup."""
+    def chain(self, period, seeds, width=None, link=1):
+        """Opens a chain group of len(seeds) columns in blocks of `period` rows (see the class); returns its ChainGroup.  link = L > 1
+        (a power of two) links L consecutive blocks into a run.  seeds=None with width=w declares the columns first and takes the
+        seeds through g.seed([...]), which may then read g.carry(j)."""
         if self._open is not None:
             raise ValueError("main program: a chain group is open (g.step closes it)")
         if period < 2 or period & (period - 1):
             raise ValueError(f"main program: the block length {period} of a chain group is not a power of two >= 2")
-        if not 1 <= len(seeds) <= MAIN_CHAIN_MAX_WIDTH:
-            raise ValueError(f"main program: a chain group of {len(seeds)} columns (1 .. {MAIN_CHAIN_MAX_WIDTH})")
-        seeds = [x if isinstance(x, Value) else self.const(x) for x in seeds]
+        if link < 1 or link & (link - 1) or link.bit_length() - 1 > MAIN_LINK_MAX_LOG:
+            raise ValueError(f"main program: a run of {link} blocks is not a power of two (1 .. 2^{MAIN_LINK_MAX_LOG})")
+        if seeds is None and width is None:
+            raise ValueError("main program: chain(period, None) needs width=w, the number of columns whose seeds g.seed will give")
+        w = len(seeds) if seeds is not None else width
+        if width is not None and width != w:
+            raise ValueError(f"main program: {w} seeds for a chain group of width {width}")
+        if not 1 <= w <= MAIN_CHAIN_MAX_WIDTH:
+            raise ValueError(f"main program: a chain group of {w} columns (1 .. {MAIN_CHAIN_MAX_WIDTH})")
         log = period.bit_length() - 1
         first = self.input_cols + len(self.cols)
+        deferred = seeds is None
+        if deferred:
+            seeds = [self.const(0)] * w    # (den_op, the seed, is filled in by g.seed)
+        else:
+            seeds = [x if isinstance(x, Value) else self.const(x) for x in seeds]
         for j, seed in enumerate(seeds):   # (num_op, the step, is filled in by g.step)
-            self._column(MAIN_CHAIN, seed, seed, log + 256 * j)
-        self._open = ChainGroup(self, list(range(first, first + len(seeds))), period)
+            self._column(MAIN_CHAIN, seed, seed, log + 256 * j + 65536 * (link.bit_length() - 1))
+        self.links |= link > 1
+        self._open = ChainGroup(self, list(range(first, first + w)), period, link, seeding=deferred)
         return self._open
 
     def const(self, v):
@@ -717,12 +760,16 @@ class MainProgram:
                 reads.append(max(reads[a], reads[b]) if op in (OP_ADD, OP_SUB, OP_MUL) else 0)
         return reads
 
-    def check(self, n=None, lookups=None):
+    def check(self, n=None, lookups=None, links=None):
         """The decoder's rules (air_statement_from_c), for a program whose lists were filled by hand too: ValueError naming the first one
         broken.  n: the trace length a chain group's block length is held against (None: not yet known).  lookups: whether COUNT
         columns are known - the decoder of the _lk entry points, where the program would be routed after multiplicity() declared one
-        (None: self.lookups); otherwise kind 6 is an unknown kind, as for the _rec entry points."""
-        lookups = self.lookups if lookups is None else lookups
+        (None: self.lookups); otherwise kind 6 is an unknown kind, as for the _rec entry points.  links: whether the k of a CHAIN
+        column's pad is known - the decoder of the _link entry points, where the program would be routed after chain(link > 1) declared
+        a linked group (None: self.links), which knows COUNT columns too; otherwise the bits at and above 16 belong to j."""
+        links = self.links if links is None else links
+        lookups = (self.lookups if lookups is None else lookups) or links
+        pos = (lambda pad: (pad >> 8) & 255) if links else (lambda pad: pad >> 8)
         n_count = 0
         if self._open is not None:
             raise ValueError("main program: a chain group is open: g.step([...]) closes it")
@@ -756,13 +803,13 @@ class MainProgram:
                     raise ValueError(f"main program: derived column {k} is the program's COUNT column number {n_count} (at most {MAIN_COUNT_MAX_COLS})")
                 continue
             if kind == MAIN_CHAIN:
-                log, j = pad & 255, pad >> 8
+                log, j, kr = pad & 255, pos(pad), pad >> 16 if links else 0     # kr: the k of a run of 2^k blocks
                 if k >= g_end:
                     if j != 0:
                         raise ValueError(f"main program: derived column {k} is a CHAIN column with j = {j} out of sequence (no group is open)")
                     g0, g_end = k, k + 1
-                    while g_end < len(self.cols) and self.cols[g_end][0] == MAIN_CHAIN and self.cols[g_end][3] >> 8:
-                        jj = self.cols[g_end][3] >> 8
+                    while g_end < len(self.cols) and self.cols[g_end][0] == MAIN_CHAIN and pos(self.cols[g_end][3]):
+                        jj = pos(self.cols[g_end][3])
                         if jj != g_end - g0:
                             raise ValueError(f"main program: derived column {g_end} is a CHAIN column with j = {jj} out of sequence (the next of its group is {g_end - g0})")
                         if jj >= MAIN_CHAIN_MAX_WIDTH:
@@ -772,6 +819,12 @@ class MainProgram:
                     raise ValueError(f"main program: derived column {k} is a CHAIN column with l = {log} (block length 2^l: 1 <= l and 2^l <= n)")
                 if log != self.cols[g0][3] & 255:
                     raise ValueError(f"main program: derived column {k} differs from its chain group in l")
+                if kr > MAIN_LINK_MAX_LOG:
+                    raise ValueError(f"main program: derived column {k} is a CHAIN column with k = {kr} (runs of 2^k blocks: k <= {MAIN_LINK_MAX_LOG})")
+                if kr and (log + kr >= 64 or (n is not None and (1 << (log + kr)) > n)):
+                    raise ValueError(f"main program: derived column {k} is a CHAIN column with l + k = {log + kr} (a run is 2^(l + k) rows: 2^(l + k) <= n)")
+                if links and kr != self.cols[g0][3] >> 16:
+                    raise ValueError(f"main program: derived column {k} differs from its chain group in k")
                 if not den:
                     raise ValueError(f"main program: derived column {k} is a CHAIN column without a seed")
                 if not (0 <= num_op < len(self.ops) and 0 <= den_op < len(self.ops)):
@@ -779,8 +832,11 @@ class MainProgram:
                 r = max(reads[num_op], reads[den_op])
                 if r > g_end:
                     raise ValueError(f"main program: derived column {k} reads derived column {r - 1}, which is not an earlier one")
-                if reads[den_op] > g0:
+                if kr == 0 and reads[den_op] > g0:
                     raise ValueError(f"main program: derived column {k} has a seed that loads derived column {reads[den_op] - 1} of its own chain group")
+                if shifted[den_op] > g0:    # (k >= 1: a load of the group at shift 0 is the carry)
+                    raise ValueError(f"main program: derived column {k} has a seed that loads derived column {shifted[den_op] - 1} of its own chain group "
+                                     "at a shift other than 0")
                 if shifted[num_op] > g0:
                     raise ValueError(f"main program: derived column {k} has a step that loads derived column {shifted[num_op] - 1} of its own chain group "
                                      "at a shift other than 0")
@@ -799,7 +855,8 @@ class MainProgram:
         """The whole main segment in Python integers (the semantics of sp_air_prove_main): input_rows = n x input_cols field elements;
         returns an (n, main_cols) numpy object array.  Columns in index order, each op one vectorised numpy operation, evaluated when the
         first column that needs it is built (the columns it loads are complete by then).  ValueError on a zero denominator.  A chain
-        group is a loop over the rows t of a block, each step vectorised over the n / period blocks.  A COUNT column is a dictionary
+        group is a loop over the rows t of a block, each step vectorised over the n / period blocks; a linked group a loop over the
+        blocks of a run and the rows of each, vectorised over the runs, the carry zero in front of each run.  A COUNT column is a dictionary
         count of X, read on the first row of each table value; ValueError on a key at or above 2^key_bits."""
         import numpy as np
         self.check(len(input_rows))
@@ -865,18 +922,23 @@ class MainProgram:
         periodic = [np.array(values, dtype=object) for values in self.periodic_cols]
         for k, (kind, num_op, den_op, pad) in enumerate(self.cols):
             if kind == MAIN_CHAIN:
-                if pad >> 8:
+                pos = (lambda pad: (pad >> 8) & 255) if self.links else (lambda pad: pad >> 8)
+                if pos(pad):
                     continue            # (built with its group, at the column that opens it)
                 period, w = 1 << (pad & 255), 1
-                while k + w < len(self.cols) and self.cols[k + w][0] == MAIN_CHAIN and self.cols[k + w][3] >> 8:
+                while k + w < len(self.cols) and self.cols[k + w][0] == MAIN_CHAIN and pos(self.cols[k + w][3]):
                     w += 1
-                first, rows = self.input_cols + k, np.arange(0, n, period)
-                state = run([self.cols[k + j][2] for j in range(w)], rows, first, [])
-                for t in range(period):
-                    for j in range(w):
-                        m[rows + t, first + j] = state[j]
-                    if t + 1 < period:   # all w next values from the state of row t, assigned together
-                        state = run([self.cols[k + j][1] for j in range(w)], rows + t, first, state)
+                link = 1 << (pad >> 16) if self.links else 1
+                first = self.input_cols + k
+                state = [np.zeros(n // (period * link), dtype=object) for _ in range(w)] if link > 1 else []   # the carry in front of a run
+                for block in range(link):
+                    rows = np.arange(block * period, n, period * link)
+                    state = run([self.cols[k + j][2] for j in range(w)], rows, first, state)   # all w seeds together, from the carry
+                    for t in range(period):
+                        for j in range(w):
+                            m[rows + t, first + j] = state[j]
+                        if t + 1 < period:   # all w next values from the state of row t, assigned together
+                            state = run([self.cols[k + j][1] for j in range(w)], rows + t, first, state)
                 continue
             if kind == MAIN_COUNT:
                 xs, ts = [int(v) for v in need(num_op)], [int(v) for v in need(den_op)]
@@ -917,17 +979,44 @@ class MainProgram:
 class ChainGroup:
     """A chain group of a MainProgram between chain() and step(): cols = its main columns, state(j) = column j on the current row."""
 
-    def __init__(self, program, cols, period):
+    def __init__(self, program, cols, period, link=1, seeding=False):
         self.program, self.cols, self.period = program, cols, period
+        self.link = link            # blocks in a run (1: every block stands alone)
+        self.seeding = seeding      # opened without seeds: g.seed([...]) gives them, and until then g.carry(j) may be read
 
     def state(self, j):
+        if self.seeding:
+            raise ValueError("main program: this chain group has no seeds yet: g.seed([...]) comes before the step reads the state")
         return self.program.load(0, self.cols[j])
+
+    def carry(self, j):
+        """Column j on the last row of the block before, zero on a run's first block: legal only while the seeds are being declared."""
+        if self.program._open is not self or not self.seeding:
+            raise ValueError("main program: g.carry(j) is read only while the seeds of an open group are declared (chain(period, None, width=w, link=L))")
+        return self.program.load(0, self.cols[j])
+
+    def seed(self, seeds):
+        """seeds[j]: the value of column j on a block's first row, from that row's inputs and - in a linked group - the carry."""
+        m = self.program
+        if m._open is not self or not self.seeding:
+            raise ValueError("main program: this chain group has its seeds already")
+        if len(seeds) != len(self.cols):
+            raise ValueError(f"main program: {len(seeds)} seeds for a chain group of {len(self.cols)} columns")
+        seeds = [x if isinstance(x, Value) else m.const(x) for x in seeds]
+        if any(x.b is not m for x in seeds):
+            raise ValueError("main program: the seeds must be values of this program")
+        for col, x in zip(self.cols, seeds):
+            kind, _, _, pad = m.cols[col - m.input_cols]
+            m.cols[col - m.input_cols] = (kind, x.i, x.i, pad)
+        self.seeding = False
 
     def step(self, nexts):
         """nexts[j]: the value of column j on the next row, from the current one; the group is complete with it."""
         m = self.program
         if m._open is not self:
             raise ValueError("main program: this chain group is closed already")
+        if self.seeding:
+            raise ValueError("main program: this chain group has no seeds yet: g.seed([...]) comes before g.step([...])")
         if len(nexts) != len(self.cols):
             raise ValueError(f"main program: {len(nexts)} next values for a chain group of {len(self.cols)} columns")
         nexts = [x if isinstance(x, Value) else m.const(x) for x in nexts]
@@ -1327,6 +1416,7 @@ class AirBuilder:
             d.main_desc = m_desc
             d.main_needs_rec = any(c[0] == MAIN_CHAIN for c in self.main.cols) or any(op == OP_PERIODIC for op, _, _ in self.main.ops)
             d.main_needs_lk = any(c[0] == MAIN_COUNT for c in self.main.cols)
+            d.main_needs_link = self.main.links and any(c[0] == MAIN_CHAIN and c[3] >> 16 for c in self.main.cols)
             keep = keep + (m_desc, m_keep)
         return d, keep
 
@@ -1735,6 +1825,124 @@ def mimc_blocks_digest(messages, s, keys, width=1):
 def mimc_blocks_inputs(n, s, rng):
     """(n, 1) Python ints from rng.randrange: a message on every row = 0 (mod s), the caller's filler on the others."""
     return [[rng.randrange(P)] for _ in range(n)]
+
+
+# ---- linked chain groups: two worked examples --------------------------------------------------------------------------------------
+def _run_selector(s, link):
+    """Period s * link: 1 on the last row of every block of a run but the run's last - the rows whose next row absorbs."""
+    return [1 if t % s == s - 1 and t != s * link - 1 else 0 for t in range(s * link)]
+
+
+def mimc_sponge(n, s, link, keys, digest):
+    """n / (s link) MiMC sponges, each absorbing `link` message blocks: the caller uploads the messages m (column 0, of which only the
+    rows = 0 (mod s) matter) and the device builds the rest (sp_air_prove_link).  Column 1 is the state x, a one-column linked group in
+    runs of `link` blocks with seed carry + m - the state the block before ended on, zero in front of a run - and step (x + K_t)^3;
+    column 2 the row-local q = (x + K)^2 as in mimc_blocks.  Periodic columns K = keys (period s), sel = [1] (s - 1) + [0] and ab
+    (period s link), 1 on the block ends that are no run ends.  Constraints under degree_bound_factor 2, no exemption: q - (x + K)^2
+    (degree 2) and sel (x' - q (x + K)) (degree 3) on every row, which tie the steps inside a block; ab (x' - x - m') (degree 2) on
+    every row, which ties a block's seed to the block before; x - m (degree 1) on the rows = 0 (mod s link), the run starts.  The
+    boundary constraint x_(s link - 1) = digest is run 0's public digest (mimc_sponge_digest)."""
+    if s < 2 or s & (s - 1) or link < 2 or link & (link - 1) or s * link > n or len(keys) != s:
+        raise ValueError(f"mimc_sponge: runs of {link} blocks of {s} rows with {len(keys)} keys on {n} rows (powers of two, link >= 2, s link <= n, one key "
+                         "per row of a block)")
+    b = AirBuilder(3, [0, 1], 2, periodic=[keys, [1] * (s - 1) + [0], _run_selector(s, link)], main_inputs=1)
+    m = b.main
+    g = m.chain(s, None, width=1, link=link)
+    g.seed([g.carry(0) + m.load(0, 0)])
+    t = g.state(0) + m.periodic(0, 0)
+    g.step([t * t * t])
+    x = g.cols[0]
+    u = m.load(0, x) + m.periodic(0, 0)
+    q = m.value(u * u)
+    u = b.load(0, x) + b.periodic(0, 0)
+    b.constraint(b.load(0, q) - u * u, degree=2, exemptions=0)
+    b.constraint(b.periodic(0, 1) * (b.load(1, x) - b.load(0, q) * u), degree=3, exemptions=0)
+    b.constraint(b.periodic(0, 2) * (b.load(1, x) - b.load(0, x) - b.load(1, 0)), degree=2, exemptions=0)
+    b.constraint(b.load(0, x) - b.load(0, 0), degree=1, exemptions=0, period=s * link, offset=0)
+    b.boundary(x, s * link - 1, digest)
+    return b
+
+
+def mimc_sponge_digest(messages, s, keys):
+    """The state after absorbing `messages`, one per block (rounds 0 .. s - 2 of each block; the last key is read by q alone): the
+    public digest of mimc_sponge for the `link` messages of run 0."""
+    x = 0
+    for msg in messages:
+        x = (x + int(msg)) % P
+        for t in range(s - 1):
+            x = pow((x + keys[t]) % P, 3, P)
+    return x
+
+
+def mimc_sponge_inputs(n, s, link, rng):
+    """(n, 1) Python ints from rng.randrange: a message on every row = 0 (mod s), the caller's filler on the others."""
+    return [[rng.randrange(P)] for _ in range(n)]
+
+
+def merkle_paths(n, s, depth, keys, root):
+    """n / (s depth) Merkle paths of `depth` levels against one public root, each level a Feistel-MiMC compression of (left, right) in
+    a block of s rows: (L, R) -> (R + (L + K_t)^3, L), the digest the L of the block's last row (merkle_paths_digest).  Inputs: the
+    value v (column 0: the leaf on a run's first row, 0 on the other block starts), the sibling (column 1) and the direction bit d
+    (column 2: 1 where the path's node is the right child); all three matter on the rows = 0 (mod s) only.  Columns 3 and 4 are (L, R),
+    a two-column linked group in runs of `depth` blocks whose seeds read cur = carry_0 + v - the digest of the level below, or the leaf
+    where the carry is zero - and place it by the bit: L = cur + d (sib - cur), R = sib + d (cur - sib).  Column 5 is q = (L + K)^2.
+    Constraints under degree_bound_factor 2 (sel and ab as in mimc_sponge): q - (L + K)^2; sel (L' - R - q (L + K)) and sel (R' - L);
+    ab (L' - L - d' (sib' - L)) and ab (R' - sib' - d' (L - sib')), degree 3 - a value other than 0 on a later block start breaks
+    them -; L - v - d (sib - v) and R - sib - d (v - sib) on the run starts; d (d - 1) on the rows = 0 (mod s); L - root on every run's
+    last row."""
+    if s < 2 or s & (s - 1) or depth < 2 or depth & (depth - 1) or s * depth > n or len(keys) != s:
+        raise ValueError(f"merkle_paths: paths of {depth} levels in blocks of {s} rows with {len(keys)} keys on {n} rows (powers of two, depth >= 2, "
+                         "s depth <= n, one key per row of a block)")
+    b = AirBuilder(6, [0, 1], 2, periodic=[keys, [1] * (s - 1) + [0], _run_selector(s, depth)], main_inputs=3)
+    m = b.main
+    g = m.chain(s, None, width=2, link=depth)
+    cur, sib, d = g.carry(0) + m.load(0, 0), m.load(0, 1), m.load(0, 2)
+    g.seed([cur + d * (sib - cur), sib + d * (cur - sib)])
+    t = g.state(0) + m.periodic(0, 0)
+    g.step([g.state(1) + t * t * t, g.state(0)])
+    left, right = g.cols
+    u = m.load(0, left) + m.periodic(0, 0)
+    q = m.value(u * u)
+    run = s * depth
+    u = b.load(0, left) + b.periodic(0, 0)
+    sel, ab = b.periodic(0, 1), b.periodic(0, 2)
+    b.constraint(b.load(0, q) - u * u, degree=2, exemptions=0)
+    b.constraint(sel * (b.load(1, left) - b.load(0, right) - b.load(0, q) * u), degree=3, exemptions=0)
+    b.constraint(sel * (b.load(1, right) - b.load(0, left)), degree=2, exemptions=0)
+    cur, sib, d = b.load(0, left), b.load(1, 1), b.load(1, 2)
+    b.constraint(ab * (b.load(1, left) - cur - d * (sib - cur)), degree=3, exemptions=0)
+    b.constraint(ab * (b.load(1, right) - sib - d * (cur - sib)), degree=3, exemptions=0)
+    cur, sib, d = b.load(0, 0), b.load(0, 1), b.load(0, 2)
+    b.constraint(b.load(0, left) - cur - d * (sib - cur), degree=2, exemptions=0, period=run, offset=0)
+    b.constraint(b.load(0, right) - sib - d * (cur - sib), degree=2, exemptions=0, period=run, offset=0)
+    b.constraint(d * (d - 1), degree=2, exemptions=0, period=s, offset=0)
+    b.constraint(b.load(0, left) - root, degree=1, exemptions=0, period=run, offset=run - 1)
+    return b
+
+
+def merkle_paths_digest(left, right, s, keys):
+    """The compression of merkle_paths: s - 1 Feistel-MiMC rounds on (left, right), the digest the left half."""
+    lo, hi = int(left) % P, int(right) % P
+    for t in range(s - 1):
+        lo, hi = (hi + pow((lo + keys[t]) % P, 3, P)) % P, lo
+    return lo
+
+
+def merkle_paths_inputs(n, s, depth, keys, rng):
+    """(rows, root): a tree of 2^depth leaves from rng.randrange under merkle_paths_digest, and for each of the n / (s depth) runs the
+    path of a leaf rng picks - (n, 3) Python ints: leaf, sibling and direction bit on the block starts, filler on the other rows (the
+    bit column's filler is free as well: d (d - 1) is enforced on the block starts alone)."""
+    levels = [[rng.randrange(P) for _ in range(1 << depth)]]
+    while len(levels[-1]) > 1:
+        below = levels[-1]
+        levels.append([merkle_paths_digest(below[2 * i], below[2 * i + 1], s, keys) for i in range(len(below) // 2)])
+    rows = [[rng.randrange(P), rng.randrange(P), rng.randrange(P)] for _ in range(n)]
+    for first in range(0, n, s * depth):
+        index = rng.randrange(1 << depth)
+        for level in range(depth):
+            rows[first + level * s] = [levels[0][index] if level == 0 else 0, levels[level][index ^ 1], index & 1]
+            index >>= 1
+    return rows, levels[-1][0]
 
 
 # ---- lookup multiplicities: two worked examples -----------------------------------------------------------------------------------

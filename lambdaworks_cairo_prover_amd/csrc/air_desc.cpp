@@ -152,8 +152,10 @@ std::string validate_aux_program(const AirAuxHost& aux, uint32_t main_cols, uint
 // the ops behind each column load: only earlier ones.  rec (the _rec entry points): op 6 over the statement's n_periodic periodic
 // columns and SP_AIR_MAIN_CHAIN columns too - groups with j = 0, 1, .. and one l, seeds that read nothing of their group, steps that
 // read it at shift 0 only; without rec kind 5 is an unknown kind and op 6 a malformed op.  lk (the _lk entry points, with rec):
-// SP_AIR_MAIN_COUNT columns too - a table, key_bits in 1 .. 64, at most 16 of them; without lk kind 6 is an unknown kind.
-std::string main_from_c(const AirDescHost& air, const sp_air_main_desc* m, uint64_t n, uint32_t n_periodic, bool rec, bool lk, AirMainHost& out) {
+// SP_AIR_MAIN_COUNT columns too - a table, key_bits in 1 .. 64, at most 16 of them; without lk kind 6 is an unknown kind.  link (the
+// _link entry points, with lk): a CHAIN column's pad is l + 256 j + 65536 k, runs of 2^k blocks; with k >= 1 a seed may load its own
+// group at shift 0; without link j = pad >> 8, so a pad with bits at or above 16 is a j out of sequence.
+std::string main_from_c(const AirDescHost& air, const sp_air_main_desc* m, uint64_t n, uint32_t n_periodic, bool rec, bool lk, bool link, AirMainHost& out) {
     if (m->size != sizeof(sp_air_main_desc)) return "main program: sp_air_main_desc.size is not sizeof(sp_air_main_desc)";
     if (!m->ops || !m->consts || !m->cols) return "main program: null ops, consts or cols";
     if (m->input_cols == 0 || m->n_cols == 0 || (uint64_t)m->input_cols + m->n_cols != air.main_cols)
@@ -201,12 +203,13 @@ std::string main_from_c(const AirDescHost& air, const sp_air_main_desc* m, uint6
             continue;
         }
         if (c.kind == SP_AIR_MAIN_CHAIN) {
-            const uint32_t l = c.pad & 255u, j = c.pad >> 8;
+            const auto pos = [link](uint32_t pad) { return link ? (pad >> 8) & 255u : pad >> 8; };
+            const uint32_t l = c.pad & 255u, j = pos(c.pad), kr = link ? c.pad >> 16 : 0u;   // kr: the k of a run of 2^k blocks
             if (k >= g_end) {   // it must open a group: the run of CHAIN columns with j = 1, 2, .. behind it
                 if (j != 0) return who + " is a CHAIN column with j = " + std::to_string(j) + " out of sequence (no group is open: j = 0 opens one)";
                 g0 = k; g_end = k + 1;
-                while (g_end < m->n_cols && m->cols[g_end].kind == SP_AIR_MAIN_CHAIN && (m->cols[g_end].pad >> 8) != 0) {
-                    const uint32_t jj = m->cols[g_end].pad >> 8;
+                while (g_end < m->n_cols && m->cols[g_end].kind == SP_AIR_MAIN_CHAIN && pos(m->cols[g_end].pad) != 0) {
+                    const uint32_t jj = pos(m->cols[g_end].pad);
                     const std::string member = "main program: derived column " + std::to_string(g_end);
                     if (jj != g_end - g0) return member + " is a CHAIN column with j = " + std::to_string(jj) + " out of sequence (the next of its group is " + std::to_string(g_end - g0) + ")";
                     if (jj >= AIR_MAIN_CHAIN_MAX_WIDTH) return member + " makes its chain group longer than 16 columns";
@@ -215,14 +218,20 @@ std::string main_from_c(const AirDescHost& air, const sp_air_main_desc* m, uint6
             }
             if (l == 0 || l >= 64 || (1ull << l) > n) return who + " is a CHAIN column with l = " + std::to_string(l) + " (block length 2^l: 1 <= l and 2^l <= n)";
             if (l != (m->cols[g0].pad & 255u)) return who + " differs from its chain group in l (" + std::to_string(l) + " against " + std::to_string(m->cols[g0].pad & 255u) + ")";
+            if (kr > AIR_MAIN_LINK_MAX_LOG) return who + " is a CHAIN column with k = " + std::to_string(kr) + " (runs of 2^k blocks: k <= " + std::to_string(AIR_MAIN_LINK_MAX_LOG) + ")";
+            if (kr && (l + kr >= 64 || (1ull << (l + kr)) > n))
+                return who + " is a CHAIN column with l + k = " + std::to_string(l + kr) + " (a run is 2^(l + k) rows: 2^(l + k) <= n)";
+            if (link && kr != (m->cols[g0].pad >> 16)) return who + " differs from its chain group in k (" + std::to_string(kr) + " against " + std::to_string(m->cols[g0].pad >> 16) + ")";
             if (!den) return who + " is a CHAIN column without a seed (den_op names the seed op)";
             if (c.num_op >= n_ops || c.den_op >= n_ops) return who + " names an op beyond the program";
             const uint32_t r = std::max(reads[c.num_op], reads[c.den_op]);
             if (r > g_end) return who + " reads derived column " + std::to_string(r - 1) + ", which is not an earlier one";
-            if (reads[c.den_op] > g0) return who + " has a seed that loads derived column " + std::to_string(reads[c.den_op] - 1) + " of its own chain group";
+            if (kr == 0 && reads[c.den_op] > g0) return who + " has a seed that loads derived column " + std::to_string(reads[c.den_op] - 1) + " of its own chain group";
+            if (shifted[c.den_op] > g0)   // (k >= 1: a load of the group at shift 0 is the carry)
+                return who + " has a seed that loads derived column " + std::to_string(shifted[c.den_op] - 1) + " of its own chain group at a shift other than 0";
             if (shifted[c.num_op] > g0)
                 return who + " has a step that loads derived column " + std::to_string(shifted[c.num_op] - 1) + " of its own chain group at a shift other than 0";
-            cols.push_back(AirMainColumnHost{c.kind, c.num_op, c.den_op, 0u, r, l, j});
+            cols.push_back(AirMainColumnHost{c.kind, c.num_op, c.den_op, 0u, r, l, j, 0u, kr});
             continue;
         }
         if (c.num_op >= n_ops || (den && c.den_op >= n_ops)) return who + " names an op beyond the program";
@@ -265,11 +274,12 @@ bool air_boundary_from_c(const sp_air_boundary_desc* d, uint32_t n_boundary, uin
 
 std::string air_statement_from_c(const sp_air_desc* d, const sp_air_aux_desc* aux, const sp_air_periodic_desc* periodic, const sp_air_stride_desc* strides,
                                  const sp_air_boundary_desc* bvals, bool aux_reads_periodic, uint64_t n, AirStatement& st, const sp_air_main_desc* main,
-                                 bool main_rec, bool main_lk) {
+                                 bool main_rec, bool main_lk, bool main_link) {
     AirDescHost& air = st.air;
     st.aux_reads_periodic = aux_reads_periodic;
-    st.main_rec = main_rec || main_lk;
-    st.main_lk = main_lk;
+    st.main_rec = main_rec || main_lk || main_link;
+    st.main_lk = main_lk || main_link;
+    st.main_link = main_link;
     if (!air_desc_from_c(d, air)) return "malformed AIR descriptor (1 .. 8 frame rows, 1 .. 64 transition constraints, every count with its array)";
     if (periodic && !air_periodic_from_c(periodic, n, st.periodic.emplace()))
         return "malformed periodic columns (at most 64, each a power-of-two number of values, at most the trace length)";
@@ -286,8 +296,9 @@ std::string air_statement_from_c(const sp_air_desc* d, const sp_air_aux_desc* au
     if (air.consts.size() + air.n_rap > 65535) return "constants and RAP challenges exceed the 16-bit operand range";
     if (air.ops.size() > AIR_LIMIT_OPS) return "more than 65535 ops";
     if (main) {
-        // (only the _rec and _lk entry points let a main program hold chain columns and read the periodic columns, only _lk COUNT columns)
-        const std::string refused = main_from_c(air, main, n, st.n_periodic(), st.main_rec, st.main_lk, st.main.emplace());
+        // (only the _rec, _lk and _link entry points let a main program hold chain columns and read the periodic columns, only _lk and
+        // _link COUNT columns, only _link runs of blocks)
+        const std::string refused = main_from_c(air, main, n, st.n_periodic(), st.main_rec, st.main_lk, st.main_link, st.main.emplace());
         if (!refused.empty()) return refused;
     }
     // (only the _pub entry points let an auxiliary program read the periodic columns: 0 of them from everywhere else)

@@ -50,9 +50,12 @@ struct AirAuxHost {
 // (for a CHAIN column: <= the end of its group for the step, <= the group's first column for the seed).  chain_log / chain_pos: the
 // l and j of a CHAIN column's pad (block length 2^l, position in its group), 0 for the other kinds.
 // key_bits: the pad of a COUNT column (its X is num_op, its T den_op), 0 for the other kinds.
+// chain_link: the k of a CHAIN column's pad through the _link entry points - runs of 2^k blocks, a seed inside a run reads the last
+// state of the block before it (0: every block on its own, and always 0 through every other entry point).
 constexpr uint32_t AIR_MAIN_CHAIN_MAX_WIDTH = 16;
+constexpr uint32_t AIR_MAIN_LINK_MAX_LOG = 62;   // (l >= 1 and l + k <= log2 n <= 63)
 constexpr uint32_t AIR_MAIN_COUNT_MAX_KEY_BITS = 64, AIR_MAIN_COUNT_MAX_COLS = 16;
-struct AirMainColumnHost { uint32_t kind, num_op, den_op, bit, reads, chain_log = 0, chain_pos = 0, key_bits = 0; };
+struct AirMainColumnHost { uint32_t kind, num_op, den_op, bit, reads, chain_log = 0, chain_pos = 0, key_bits = 0, chain_link = 0; };
 struct AirMainHost {
     uint32_t input_cols = 0, input_location = 0;   // 0: the inputs are host memory, 1: device memory
     std::vector<AirOpHost> ops;
@@ -125,6 +128,7 @@ struct AirStatement {
     bool aux_reads_periodic = false;
     bool main_rec = false;                    // the main program may hold CHAIN columns and read the periodic columns with op 6 (the _rec entry points)
     bool main_lk = false;                     // all of main_rec, and the main program may hold COUNT columns, lookup multiplicities (the _lk entry points)
+    bool main_link = false;                   // all of main_lk, and a chain group's blocks may form runs seeded from the block before (the _link entry points)
     bool unsupported = false;                 // set with a refusal that is SP_E_UNSUPPORTED, not SP_E_INVALID_ARG (a main program beside aux_kind 1 or 2)
     // the periodic columns the auxiliary program may read: null when it may read none
     const AirPeriodicHost* aux_periodic() const { return aux_reads_periodic && periodic ? &*periodic : nullptr; }
@@ -145,12 +149,15 @@ struct AirStatement {
 // the periodic columns with op 6; without it kind 5 is an unknown kind and op 6 a malformed op, as ever.
 // main_lk (the _lk entry points only; it brings main_rec with it): the main program may also hold SP_AIR_MAIN_COUNT columns - at most
 // 16, each with a table (den_op), key_bits (pad) in 1 .. 64, X and T over earlier columns; without it kind 6 is an unknown kind.
+// main_link (the _link entry points only; it brings main_lk with it): a CHAIN column's pad also carries k = pad >> 16 - runs of 2^k
+// blocks, l + k <= log2 n, one k per group - and with k >= 1 a seed may load its own group at shift 0 (the carry); without it the
+// bits at and above 16 belong to j, as ever.
 // The constraint program itself is checked where it is turned into what runs it (build_air_program, air_verify_host).
 // An sp_air_ext is taken apart by the entry point that receives it; this is the one thing it checks first: null, or what is wrong.
 inline const char* air_ext_refusal(const sp_air_ext* ext) { return ext && ext->size != sizeof(sp_air_ext) ? "sp_air_ext.size is not sizeof(sp_air_ext)" : nullptr; }
 std::string air_statement_from_c(const sp_air_desc* d, const sp_air_aux_desc* aux, const sp_air_periodic_desc* periodic, const sp_air_stride_desc* strides,
                                  const sp_air_boundary_desc* bvals, bool aux_reads_periodic, uint64_t n, AirStatement& out,
-                                 const sp_air_main_desc* main = nullptr, bool main_rec = false, bool main_lk = false);
+                                 const sp_air_main_desc* main = nullptr, bool main_rec = false, bool main_lk = false, bool main_link = false);
 // `verify::<F, A>` for a program AIR (verifier.cpp): 1 accept, 0 reject; throws std::runtime_error on a malformed proof or constraint
 // program.  st.aux is the prover's business and is not looked at.
 int air_verify_host(const uint8_t* proof_bytes, size_t len, const AirStatement& st, const ProofOptionsHost& opt);

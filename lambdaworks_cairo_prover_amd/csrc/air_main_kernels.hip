@@ -105,6 +105,68 @@ int air_main_chain(hipStream_t st, fe* trace, uint64_t n, uint32_t log_s, uint32
     return SP_OK;
 }
 
+// ---- linked chain groups: one lane per run of 2^log_k blocks ------------------------------------------------------------------
+// The blocks of a run are serial too - a seed reads the last state of the block before -, so the lane walks the whole run, 2^(log_s +
+// log_k) rows, and the n >> (log_s + log_k) runs are the parallel dimension.  The state starts as zero, the carry of a run's first
+// block; after a block's last advance() it holds that block's last row, which is what the next seed program's LOADs of the group read.
+// The body is the unlinked kernel's, the seeds' loader apart (from_state, not from_trace), in a loop over the blocks; a kernel of its
+// own, so that a group without runs launches the code it always launched.
+template <bool PER>
+__global__ void __launch_bounds__(64) air_main_chain_linked_kernel(fe* __restrict__ group, const fe* __restrict__ trace, uint64_t n, uint32_t log_s, uint32_t log_k,
+                                                                   uint32_t first_col, uint32_t w, const AirOpDev* __restrict__ seed_ops, uint32_t n_seed,
+                                                                   const AirOpDev* __restrict__ step_ops, uint32_t n_step, const fe* __restrict__ consts,
+                                                                   const AirPeriodicCol* __restrict__ pcols, const fe* __restrict__ pvals) {
+    const uint64_t R = (uint64_t)blockIdx.x * 64 + threadIdx.x;
+    if (R >= (n >> (log_s + log_k))) return;   // (with fewer than 64 runs the only wave is partly empty)
+    fe state[AIR_MAIN_CHAIN_WIDTH], next[AIR_MAIN_CHAIN_WIDTH];
+    for (uint32_t j = 0; j < AIR_MAIN_CHAIN_WIDTH; ++j) state[j] = fe_zero();
+    uint64_t i = R << (log_s + log_k);
+    auto periodic = [&](uint32_t shift, uint32_t col) {
+        const AirPeriodicCol pc = pcols[col];
+        return fe_ld(pvals + pc.off + ((i + shift) & ((1ull << pc.logp) - 1ull)));
+    };
+    auto from_trace = [&](uint32_t shift, uint32_t col) { return fe_ld(trace + (uint64_t)col * n + ((i + shift) & (n - 1))); };
+    auto from_state = [&](uint32_t shift, uint32_t col) {   // (col - first_col wraps to a large value for a column before the group)
+        return col - first_col < w ? state[col - first_col] : from_trace(shift, col);
+    };
+    auto to_next = [&](uint32_t j, const fe& val) { next[j] = val; };
+    auto advance = [&]() {
+        for (uint32_t j = 0; j < w; ++j) {
+            state[j] = next[j];
+            fe_st(group + (uint64_t)j * n + i, next[j]);
+        }
+    };
+    const uint64_t run_end = i + (1ull << (log_s + log_k));
+    while (i < run_end) {
+        // the seeds on the block's first row: a LOAD of the group is the carry, the state the block before left (zero in front of a run)
+        if constexpr (PER) air_run_program<true>(seed_ops, n_seed, consts, from_state, periodic, to_next);
+        else air_run_program<false>(seed_ops, n_seed, consts, from_state, AirNoPeriodic{}, to_next);
+        advance();
+        const uint64_t last = i + (1ull << log_s) - 1;
+        while (i < last) {
+            if constexpr (PER) air_run_program<true>(step_ops, n_step, consts, from_state, periodic, to_next);
+            else air_run_program<false>(step_ops, n_step, consts, from_state, AirNoPeriodic{}, to_next);
+            ++i;
+            advance();
+        }
+        ++i;
+    }
+}
+
+int air_main_chain_linked(hipStream_t st, fe* trace, uint64_t n, uint32_t log_s, uint32_t log_k, uint32_t first_col, uint32_t w, const AirOpDev* seed_ops,
+                          uint32_t n_seed, const AirOpDev* step_ops, uint32_t n_step, const fe* consts, const AirPeriodicCol* pcols, const fe* pvals) {
+    if (n == 0 || (n & (n - 1)) || log_s == 0 || log_k == 0 || log_s + log_k >= 64 || (1ull << (log_s + log_k)) > n || w == 0 || w > AIR_MAIN_CHAIN_WIDTH ||
+        (pcols == nullptr) != (pvals == nullptr))
+        return SP_E_INVALID_ARG;
+    const uint64_t lanes = n >> (log_s + log_k);
+    const dim3 grid((unsigned)((lanes + 63) / 64));
+    fe* group = trace + (uint64_t)first_col * n;
+    if (pcols) hipLaunchKernelGGL(air_main_chain_linked_kernel<true>, grid, dim3(64), 0, st, group, trace, n, log_s, log_k, first_col, w, seed_ops, n_seed, step_ops, n_step, consts, pcols, pvals);
+    else hipLaunchKernelGGL(air_main_chain_linked_kernel<false>, grid, dim3(64), 0, st, group, trace, n, log_s, log_k, first_col, w, seed_ops, n_seed, step_ops, n_step, consts, pcols, pvals);
+    SP_HIP_CHECK(hipGetLastError());
+    return SP_OK;
+}
+
 // ---- lookup multiplicities: the join of the sorted looked-up keys against the sorted table keys ---------------------------------
 // One lane per sorted table position p.  The head of a run of equal table keys - the stable sort put the run's lowest row there -
 // counts its key in the sorted looked-up keys with two binary searches, interleaved in one loop: each step of either is a dependent

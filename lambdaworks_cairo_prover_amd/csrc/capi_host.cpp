@@ -124,6 +124,22 @@ int sp_air_main_check_lk(const sp_air_desc* d, const sp_air_ext* ext, const sp_a
         return st.unsupported ? SP_E_UNSUPPORTED : SP_E_INVALID_ARG;
     } catch (const std::exception& e) { sp_set_error(e.what()); return SP_E_INVALID_ARG; }
 }
+int sp_air_main_check_link(const sp_air_desc* d, const sp_air_ext* ext, const sp_air_main_desc* mp, uint64_t n) {
+    if (!d || !mp) return SP_E_INVALID_ARG;
+    if (const char* bad = sp::air_ext_refusal(ext)) { sp_set_error(bad); return SP_E_INVALID_ARG; }
+    try {
+        sp::AirStatement st;
+        const std::string refused = sp::air_statement_from_c(d, nullptr, ext ? ext->periodic : nullptr, nullptr, nullptr, false, n, st, mp, true, true, true);
+        if (refused.empty()) return SP_OK;
+        sp_set_error("sp_air_main_check_link: " + refused);
+        return st.unsupported ? SP_E_UNSUPPORTED : SP_E_INVALID_ARG;
+    } catch (const std::exception& e) { sp_set_error(e.what()); return SP_E_INVALID_ARG; }
+}
+int sp_air_main_link_limits(uint32_t out[2]) {
+    if (!out) return SP_E_INVALID_ARG;
+    out[0] = sp::AIR_MAIN_LINK_MAX_LOG; out[1] = sp::AIR_MAIN_CHAIN_MAX_WIDTH;
+    return SP_OK;
+}
 int sp_air_main_count_limits(uint32_t out[2]) {
     if (!out) return SP_E_INVALID_ARG;
     out[0] = sp::AIR_MAIN_COUNT_MAX_KEY_BITS; out[1] = sp::AIR_MAIN_COUNT_MAX_COLS;

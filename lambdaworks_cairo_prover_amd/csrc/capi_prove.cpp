@@ -372,9 +372,10 @@ struct AirParts {
     const sp_air_main_desc* main;   // (the _main entry points: the trace argument then holds the input columns only)
     bool main_rec;                  // (the _rec entry points: the main program may hold chain columns and read the periodic columns)
     bool main_lk;                   // (the _lk entry points: all of that, and lookup multiplicities - SP_AIR_MAIN_COUNT columns)
+    bool main_link;                 // (the _link entry points: all of that, and chain groups whose blocks form runs seeded from the block before)
     static AirParts of_ext(const sp_air_ext* ext, const sp_air_boundary_desc* bvals, bool aux_reads_periodic, const sp_air_main_desc* main = nullptr,
-                           bool main_rec = false, bool main_lk = false) {
-        return AirParts{ext ? ext->aux : nullptr, ext ? ext->periodic : nullptr, ext ? ext->strides : nullptr, bvals, aux_reads_periodic, main, main_rec, main_lk};
+                           bool main_rec = false, bool main_lk = false, bool main_link = false) {
+        return AirParts{ext ? ext->aux : nullptr, ext ? ext->periodic : nullptr, ext ? ext->strides : nullptr, bvals, aux_reads_periodic, main, main_rec, main_lk, main_link};
     }
 };
 bool ext_ok(const sp_air_ext* ext) {
@@ -383,7 +384,7 @@ bool ext_ok(const sp_air_ext* ext) {
     return !bad;
 }
 int decode(const char* who, const sp_air_desc* d, const AirParts& p, uint64_t n, sp::AirStatement& st) {
-    const std::string refused = sp::air_statement_from_c(d, p.aux, p.periodic, p.strides, p.bvals, p.aux_reads_periodic, n, st, p.main, p.main_rec, p.main_lk);
+    const std::string refused = sp::air_statement_from_c(d, p.aux, p.periodic, p.strides, p.bvals, p.aux_reads_periodic, n, st, p.main, p.main_rec, p.main_lk, p.main_link);
     if (refused.empty()) return SP_OK;
     sp_set_error(std::string(who) + ": " + refused);
     return st.unsupported ? SP_E_UNSUPPORTED : SP_E_INVALID_ARG;
@@ -483,14 +484,14 @@ int sp_air_check_trace_main(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* e
 namespace {
 // sp_air_main_trace and its _rec form (periodic: the columns an op 6 of the main program reads)
 int air_main_trace_body(const char* who, sp_ctx* c, const sp_air_desc* d, const sp_air_periodic_desc* periodic, bool main_rec, const sp_air_main_desc* mp,
-                        const void* inputs, uint64_t n, uint8_t* rows_out, bool main_lk = false) {
+                        const void* inputs, uint64_t n, uint8_t* rows_out, bool main_lk = false, bool main_link = false) {
     if (!c || !d || !mp || !inputs || !rows_out) return SP_E_INVALID_ARG;
     try {
         sp::AirStatement st;
         // (the table does not depend on the auxiliary segment: the statement is judged as one without, whatever the AIR's aux_kind)
         sp_air_desc main_only = *d;
         main_only.aux_cols = 0; main_only.aux_kind = 0;
-        SP_TRY(decode(who, &main_only, AirParts{nullptr, periodic, nullptr, nullptr, false, mp, main_rec, main_lk}, n, st));
+        SP_TRY(decode(who, &main_only, AirParts{nullptr, periodic, nullptr, nullptr, false, mp, main_rec, main_lk, main_link}, n, st));
         if (sp_log2_exact(n) < 0) { sp_set_error(std::string(who) + ": n must be a power of two"); return SP_E_INVALID_ARG; }
         c->prewarm_cancel.store(0, std::memory_order_release);
         return sp::air_main_trace(c, st, static_cast<const uint8_t*>(inputs), n, rows_out);
@@ -531,6 +532,22 @@ int sp_air_check_trace_lk(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext
 int sp_air_main_trace_lk(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const sp_air_main_desc* mp, const void* inputs, uint64_t n, uint8_t* rows_out) {
     if (!ext_ok(ext)) return SP_E_INVALID_ARG;
     return air_main_trace_body("sp_air_main_trace_lk", c, d, ext ? ext->periodic : nullptr, true, mp, inputs, n, rows_out, true);
+}
+
+// The _lk entry points for a main program whose chain groups link their blocks into runs (the k of a CHAIN column's pad).
+int sp_air_prove_link(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const sp_air_boundary_desc* bv, const sp_air_main_desc* mp, const void* inputs,
+                      uint64_t n, const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len) {
+    if (!mp || !ext_ok(ext)) return SP_E_INVALID_ARG;
+    return air_prove_body(c, d, AirParts::of_ext(ext, bv, true, mp, true, true, true), static_cast<const uint8_t*>(inputs), n, opt, proof_out, proof_len);
+}
+int sp_air_check_trace_link(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const sp_air_boundary_desc* bv, const sp_air_main_desc* mp, const void* inputs,
+                            uint64_t n, const sp_proof_options* opt, const uint8_t* rap, sp_air_violation* out, uint32_t cap, uint32_t* n_out) {
+    if (!mp || !ext_ok(ext)) return SP_E_INVALID_ARG;
+    return air_check_trace_body(c, d, AirParts::of_ext(ext, bv, true, mp, true, true, true), static_cast<const uint8_t*>(inputs), n, opt, rap, out, cap, n_out);
+}
+int sp_air_main_trace_link(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const sp_air_main_desc* mp, const void* inputs, uint64_t n, uint8_t* rows_out) {
+    if (!ext_ok(ext)) return SP_E_INVALID_ARG;
+    return air_main_trace_body("sp_air_main_trace_link", c, d, ext ? ext->periodic : nullptr, true, mp, inputs, n, rows_out, true, true);
 }
 
 }  // extern "C"

@@ -619,7 +619,8 @@ int StarkProver::commit_aux_program(const AirStatement& st, const std::vector<fe
 // A chain group (SP_AIR_MAIN_CHAIN, st.main_rec) is a chunk of its own and ends the chunk before it: two programs, the seeds' and the
 // steps', each with an OUT per group column, and one launch of air_main_chain; nothing of the group is read before that launch is
 // over, which the stream's order guarantees.  It takes no workspace.  The periodic columns an op 6 reads (st.periodic) ride in this
-// upload block as they do in the auxiliary program's: round 2's block comes too late.
+// upload block as they do in the auxiliary program's: round 2's block comes too late.  A linked group (st.main_link, k >= 1 in its
+// columns' pad) is the same chunk with the same two programs and one launch of air_main_chain_linked, a lane per run of 2^k blocks.
 // A COUNT column (SP_AIR_MAIN_COUNT, st.main_lk) is a chunk of its own too: two programs, X's and T's, each with the one OUT of a key
 // pass; two launches of air_aux_sort_terms (keys out of Montgomery form, the row beside each), two radix sorts - the table's carries
 // its rows - and one launch of air_main_count, which writes every cell of the column.  Its arrays (4 x [n] keys, 4 x [n] rows, the
@@ -647,6 +648,7 @@ int StarkProver::build_main_program(const AirStatement& st, const uint8_t* input
         uint32_t chain_log = 0;                                      // a chain group (kc columns, blocks of 2^chain_log rows): ops is the step program,
         std::vector<AirOpDev> seed_ops;                              //   seed_ops the seeds'
         size_t o_seed = 0;
+        uint32_t link_log = 0;                                       // a linked chain group: runs of 2^link_log blocks, one lane per run (st.main_link)
         uint32_t count_bits = 0;                                     // a COUNT column (kc = 1) with this key_bits: ops is X's program, seed_ops T's
     };
     std::vector<Chunk> chunks;
@@ -676,13 +678,14 @@ int StarkProver::build_main_program(const AirStatement& st, const uint8_t* input
         if (mp.cols[k0].kind == SP_AIR_MAIN_CHAIN) {   // the whole group (the decoder saw to j = 0, 1, .. and one l)
             std::vector<std::vector<uint32_t>> seeds(n_src);
             ch.chain_log = mp.cols[k0].chain_log;
+            ch.link_log = mp.cols[k0].chain_link;
             do {
                 const AirMainColumnHost& c = mp.cols[k0 + ch.kc];
                 seeds[c.den_op].push_back(ch.kc);
                 outs[c.num_op].push_back(ch.kc);
                 ++ch.kc;
             } while (k0 + ch.kc < K && mp.cols[k0 + ch.kc].kind == SP_AIR_MAIN_CHAIN && mp.cols[k0 + ch.kc].chain_pos != 0);
-            if (ch.kc > AIR_MAIN_CHAIN_WIDTH || n_ >> ch.chain_log == 0) { sp_set_error("commit_main_program: a chain group the decoder should have refused"); return SP_E_INVALID_ARG; }
+            if (ch.kc > AIR_MAIN_CHAIN_WIDTH || ch.chain_log + ch.link_log >= 64 || n_ >> (ch.chain_log + ch.link_log) == 0) { sp_set_error("commit_main_program: a chain group the decoder should have refused"); return SP_E_INVALID_ARG; }
             SP_TRY(program_with_outs(seeds, ch.seed_ops, ch.periodic));
             SP_TRY(program_with_outs(outs, ch.ops, ch.periodic));
             k0 += ch.kc;
@@ -822,6 +825,12 @@ int StarkProver::build_main_program(const AirStatement& st, const uint8_t* input
     for (const Chunk& ch : chunks) {
         fe* cols = d_trace_ + (uint64_t)(I + ch.k0) * n_;
         const AirOpDev* ops_dev = reinterpret_cast<const AirOpDev*>(od_.auxp_buf.p + ch.o_ops);
+        if (ch.chain_log && ch.link_log) {   // the same two programs; a seed's LOAD of its group is the carry
+            SP_TRY(air_main_chain_linked(c_->stream, d_trace_, n_, ch.chain_log, ch.link_log, I + ch.k0, ch.kc, reinterpret_cast<const AirOpDev*>(od_.auxp_buf.p + ch.o_seed),
+                                         (uint32_t)ch.seed_ops.size(), ops_dev, (uint32_t)ch.ops.size(), consts_dev, ch.periodic ? pcols_dev : nullptr,
+                                         ch.periodic ? pvals_dev : nullptr));
+            continue;
+        }
         if (ch.chain_log) {
             SP_TRY(air_main_chain(c_->stream, d_trace_, n_, ch.chain_log, I + ch.k0, ch.kc, reinterpret_cast<const AirOpDev*>(od_.auxp_buf.p + ch.o_seed),
                                   (uint32_t)ch.seed_ops.size(), ops_dev, (uint32_t)ch.ops.size(), consts_dev, ch.periodic ? pcols_dev : nullptr,

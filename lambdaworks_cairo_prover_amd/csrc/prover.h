@@ -115,6 +115,7 @@ class StarkProver : public sp_deletable {
     // commit_segment_resident.  A zero denominator is SP_E_ZERO_INVERSE once the root is back.  Every rank builds every column.
     // With st.main_rec a chain group (SP_AIR_MAIN_CHAIN) is a chunk of its own, built by one launch of air_main_chain, and op 6 reads
     // st.periodic, whose raw values go up with the program.
+    // With st.main_link a chain group whose columns carry k >= 1 is built by one launch of air_main_chain_linked, a lane per run.
     // With st.main_lk a COUNT column (SP_AIR_MAIN_COUNT) is a chunk of its own as well: two key passes, two radix sorts and
     // air_main_count; a key out of range is SP_E_INVALID_ARG once the root is back, ahead of a zero denominator.
     int commit_main_program(const AirStatement& st, const uint8_t* inputs, uint8_t root_out[32]);

@@ -1,0 +1,205 @@
+"""Linked chain groups on the device (sp_air_prove_link, sp_air_check_trace_link, sp_air_main_trace_link): the columns equal the
+Python-integer model cell for cell, and a proof from the input columns has the bytes of the proof from the model's whole table through
+the entry points that existed before.  Every comparison is exact."""
+import ctypes
+import random
+
+import numpy as np
+import pytest
+
+import link_airs as L
+import oracle_lib as O
+from lambdaworks_cairo_prover_amd import _lib, air, api
+from rank_procs import run_ranks
+from test_gpu_air_main import OPTIONS, model_ints, prove_full, table_ints, to_bytes
+
+pytestmark = pytest.mark.gpu
+P = air.P
+
+
+# ---- cell equality ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n,s,link", [(64, 2, 2), (64, 8, 8), (64, 32, 2), (4096, 4, 4), (8192, 2, 2)])
+def test_table_equals_the_model_cell_for_cell(hip_ctx, n, s, link):
+    """(64, 2, 2): 16 lanes, one step a block.  (64, 8, 8): one lane, the whole trace one run, the input read at shift 3 wraps on its
+    last rows.  (64, 32, 2): a single run of two blocks.  (4096, 4, 4): 256 lanes, four work-groups.  (8192, 2, 2): 2048 lanes.
+    The program (link_airs.mixed): a linked group of three whose seeds read each other's carries - an OUT of column 0 ahead of a later
+    carry LOAD of column 0 -, a k = 0 group beside it, a linked group of sixteen, a VALUE and a SUM that read them, op 6 in seeds and
+    steps (periods 4 and 64), and the seed carry + 1, which is 1 on every run's first block only if the carry there is zero."""
+    rng = random.Random(n + s + link)
+    periodic = L.periodic_columns(rng)
+    b, cols = L.mixed(s, link, periodic)
+    rows = L.mixed_inputs(n, rng)
+    desc, keep = b.build()
+    assert air.main_suffix(desc) == "link"
+    got = hip_ctx.air_main_trace(desc, to_bytes(rows))
+    assert got.shape == (n, b.main_cols, 32)
+    got, want = table_ints(got), model_ints(b, rows)
+    if n == 64:
+        assert want == L.hand_table(rows, s, link, periodic)
+    for i in range(n):
+        assert got[i] == want[i], i
+    for first in range(0, n, s * link):
+        assert got[first][cols["x2"]] == 1, first
+
+
+def test_worked_examples_tables(hip_ctx):
+    n, s, link = 256, 8, 4
+    b, rows, keys = L.sponge_case(n, s, link, random.Random(40))
+    desc, keep = b.build()
+    got = table_ints(hip_ctx.air_main_trace(desc, to_bytes(rows)))
+    assert got == model_ints(b, rows) == L.sponge_table(rows, s, link, keys)
+    b, rows, keys, root = L.merkle_case(n, s, link, random.Random(41))
+    desc, keep = b.build()
+    got = table_ints(hip_ctx.air_main_trace(desc, to_bytes(rows)))
+    assert got == model_ints(b, rows)
+    assert all(got[last][3] == root for last in range(s * link - 1, n, s * link))
+
+
+# ---- proof bytes ------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("options", OPTIONS)
+def test_sponge_proof_bytes_equal_those_from_the_whole_table(hip_ctx, options):
+    """air.mimc_sponge reads periodic columns and puts one constraint on a stride; the CPU oracle's entry point takes the descriptor
+    alone and has no argument for either, so it is not asked here (test_plain_link_proof_bytes_equal_the_oracles asks it)."""
+    n, s, link = 64, 4, 4
+    b, rows, keys = L.sponge_case(n, s, link, random.Random(7))
+    assert b.check_trace(rows) == []
+    desc, keep = b.build()
+    full = to_bytes(model_ints(b, rows))
+    got = hip_ctx.air_prove(desc, to_bytes(rows), api.ProofOptions(*options))
+    assert got == prove_full(hip_ctx, desc, full, options, "pub")
+    assert got == prove_full(hip_ctx, desc, full, options, "ext")
+    assert hip_ctx.air_prove(desc, to_bytes(rows), api.ProofOptions(*options)) == got   # the kept workspace, a second time
+    assert api.air_verify(got, desc, api.ProofOptions(*options))
+
+
+@pytest.mark.parametrize("options", OPTIONS)
+def test_plain_link_proof_bytes_equal_the_oracles(hip_ctx, oracle, options):
+    """plain_link has no periodic column and no stride: the CPU oracle, which takes the descriptor alone, proves the same table."""
+    n, s, link = 64, 4, 4
+    b = L.plain_link(s, link)
+    rng = random.Random(8)
+    rows = [[rng.randrange(P)] for _ in range(n)]
+    assert b.check_trace(rows) == []
+    desc, keep = b.build()
+    full = to_bytes(model_ints(b, rows))
+    got = hip_ctx.air_prove(desc, to_bytes(rows), api.ProofOptions(*options))
+    assert got == prove_full(hip_ctx, desc, full, options, "pub") == prove_full(hip_ctx, desc, full, options, "ext")
+    assert got == O.program_air_prove(desc, full, options)
+    assert api.air_verify(got, desc, api.ProofOptions(*options))
+
+
+LINK_OPTIONS = (4, 4, 3, 2)      # (degree_bound_factor 2: the composition has 2n coefficients)
+
+
+def test_merkle_paths_proves_verifies_and_checks_clean(hip_ctx):
+    n, s, depth = 256, 8, 4
+    b, rows, keys, root = L.merkle_case(n, s, depth, random.Random(11))
+    assert b.check_trace(rows) == []
+    desc, keep = b.build()
+    options = api.ProofOptions(*LINK_OPTIONS)
+    proof = hip_ctx.air_prove(desc, to_bytes(rows), options)
+    assert api.air_verify(proof, desc, options)
+    full = to_bytes(model_ints(b, rows))
+    assert proof == prove_full(hip_ctx, desc, full, LINK_OPTIONS, "ext") == prove_full(hip_ctx, desc, full, LINK_OPTIONS, "pub")
+    assert hip_ctx.air_check_trace(desc, to_bytes(rows), options) == []
+
+
+def test_wrong_root_is_proved_rejected_and_reported(hip_ctx):
+    n, s, depth = 256, 8, 4
+    b, rows, keys, root = L.merkle_case(n, s, depth, random.Random(12))
+    wrong = air.merkle_paths(n, s, depth, keys, root + 1)
+    desc, keep = wrong.build()
+    options = api.ProofOptions(*LINK_OPTIONS)
+    proof = hip_ctx.air_prove(desc, to_bytes(rows), options)           # as the reference: a proof all the same ...
+    assert not api.air_verify(proof, desc, options)                    # ... which no verifier accepts
+    want = wrong.check_trace(rows)
+    run = s * depth
+    assert want == [air.Violation(air.TRANSITION, 8, n // run, run - 1, n - 1, P - 1)]
+    assert hip_ctx.air_check_trace(desc, to_bytes(rows), options) == want
+
+
+def test_linked_group_beside_an_auxiliary_program(hip_ctx, oracle):
+    """A grand product over the linked column: the auxiliary program reads what the main program built."""
+    n, s, link, options = 128, 4, 8, (4, 3, 3, 1)
+    rng = random.Random(9)
+    b = L.link_permutation(s, link)
+    rows = [[rng.randrange(P)] for _ in range(n)]
+    assert b.check_trace(rows, rap=[12345]) == []
+    desc, keep = b.build()
+    full = to_bytes(model_ints(b, rows))
+    got = hip_ctx.air_prove(desc, to_bytes(rows), api.ProofOptions(*options))
+    assert got == prove_full(hip_ctx, desc, full, options, "pub") == prove_full(hip_ctx, desc, full, options, "ext")
+    cb_desc, cb_keep = b.build(aux_as_callback=True, main_trace=full)
+    assert got == O.program_air_prove(cb_desc, full, options)
+    assert api.air_verify(got, desc, api.ProofOptions(*options))
+    assert hip_ctx.air_check_trace(desc, to_bytes(rows), rap=[12345]) == []
+
+
+def test_inputs_in_device_memory_give_the_same_bytes(hip_ctx):
+    import torch
+    n, s, link = 256, 8, 4
+    options = api.ProofOptions(*LINK_OPTIONS)
+    b, rows, keys = L.sponge_case(n, s, link, random.Random(13))
+    desc, keep = b.build()
+    host = to_bytes(rows)
+    want = hip_ctx.air_prove(desc, host, options)
+    assert api.air_verify(want, desc, options)
+    dev = torch.from_numpy(host).to("cuda:0")
+    assert hip_ctx.air_prove(desc, dev, options) == want
+    assert desc.main_desc.input_location == air.INPUTS_DEVICE
+    assert np.array_equal(hip_ctx.air_main_trace(desc, dev), hip_ctx.air_main_trace(desc, host))
+    assert hip_ctx.air_prove(desc, host, options) == want and desc.main_desc.input_location == air.INPUTS_HOST
+
+
+def test_malformed_linked_program_is_refused_and_the_context_goes_on(hip_ctx):
+    n, s, link, options = 64, 4, 4, api.ProofOptions(4, 3, 3, 1)
+    rng = random.Random(29)
+    rows = [[rng.randrange(P)] for _ in range(n)]
+    desc, keep = L.plain_link(s, link).build()
+    want = hip_ctx.air_prove(desc, to_bytes(rows), options)
+    pad = desc.main_desc.cols[1].pad
+    desc.main_desc.cols[1].pad = 2 + 256 + 65536    # the second column of the group in runs of 2 blocks, the first in runs of 4
+    for call in (lambda: hip_ctx.air_prove(desc, to_bytes(rows), options), lambda: hip_ctx.air_main_trace(desc, to_bytes(rows)),
+                 lambda: hip_ctx.air_check_trace(desc, to_bytes(rows), options)):
+        with pytest.raises(api.SpError) as e:
+            call()
+        assert e.value.code == _lib.SP_E_INVALID_ARG and "differs from its chain group in k" in str(e.value)
+    desc.main_desc.cols[1].pad = pad
+    assert hip_ctx.air_prove(desc, to_bytes(rows), options) == want
+    # and through the entry points that were there before the same program is a j out of sequence
+    lib, opt = _lib.load(), options.to_c()
+    out, ln = ctypes.POINTER(ctypes.c_uint8)(), ctypes.c_uint64()
+    a = to_bytes(rows)
+    for name in ("sp_air_prove_rec", "sp_air_prove_lk"):
+        rc = getattr(lib, name)(hip_ctx._h, ctypes.byref(desc), None, None, ctypes.byref(desc.main_desc), a.ctypes.data_as(ctypes.c_void_p), ctypes.c_uint64(n),
+                                ctypes.byref(opt), ctypes.byref(out), ctypes.byref(ln))
+        assert rc == _lib.SP_E_INVALID_ARG and "out of sequence" in lib.sp_last_error().decode(), name
+    assert hip_ctx.air_prove(desc, to_bytes(rows), options) == want
+
+
+# ---- two ranks ------------------------------------------------------------------------------------------------------------------
+def _rank_case(n, s, link):
+    return L.sponge_case(n, s, link, random.Random(31))
+
+
+def _link_body(rank, world, n, s, link, options):
+    ctx = api.Context(device=0)
+    ctx.set_collective(world, rank, api.StagedAllGather())
+    ctx.set_option(api.SP_OPT_FRI_SHARD_MIN_LOG, 5)
+    b, rows, keys = _rank_case(n, s, link)
+    desc, keep = b.build()
+    proof = ctx.air_prove(desc, to_bytes(rows), api.ProofOptions(*options))
+    ctx.close()
+    return proof
+
+
+def test_two_ranks_give_the_one_rank_bytes(hip_ctx):
+    """Every rank ingests the inputs and builds every linked column itself: no exchange before the commitment."""
+    n, s, link, options = 4096, 8, 4, LINK_OPTIONS
+    b, rows, keys = _rank_case(n, s, link)
+    desc, keep = b.build()
+    want = hip_ctx.air_prove(desc, to_bytes(rows), api.ProofOptions(*options))
+    assert api.air_verify(want, desc, api.ProofOptions(*options))
+    got = run_ranks(2, _link_body, (n, s, link, options), timeout=600)
+    for r in range(2):
+        assert got[r] == want, (r, got[r][:400])

@@ -80,18 +80,18 @@ struct Parts {
 
 // use: which parts go to the decoder (x p s b m r R l L, upper case P: the auxiliary program may read the periodic columns; m: the main
 // program, for which the AIR gets its six main columns first; r / R the chain program with and without the _rec policy; l / L the
-// lookup program under the _lk policy and under the _rec policy alone)
+// lookup program under the _lk policy and under the _rec policy alone; k the chain program under the _link policy)
 void run(const char* label, const char* use, bool want_ok, const std::function<void(Parts&)>& patch) {
     Parts p;
     if (std::strchr(use, 'm')) p.with_main();
-    if (std::strchr(use, 'r') || std::strchr(use, 'R') || std::strchr(use, 'l') || std::strchr(use, 'L')) p.with_chain();
+    if (std::strchr(use, 'r') || std::strchr(use, 'R') || std::strchr(use, 'l') || std::strchr(use, 'L') || std::strchr(use, 'k')) p.with_chain();
     patch(p);
     auto has = [&](char c) { return std::strchr(use, c) != nullptr; };
     sp::AirStatement st;
     const std::string refused = sp::air_statement_from_c(&p.d, has('x') ? &p.aux : nullptr, has('p') ? &p.per : nullptr, has('s') ? &p.sd : nullptr,
                                                          has('b') ? &p.bv : nullptr, has('P'), 16, st,
-                                                         has('m') ? &p.mp : has('r') || has('R') ? &p.rp : has('l') || has('L') ? &p.lp : nullptr,
-                                                         has('r') || has('L'), has('l'));
+                                                         has('m') ? &p.mp : has('r') || has('R') || has('k') ? &p.rp : has('l') || has('L') ? &p.lp : nullptr,
+                                                         has('r') || has('L'), has('l'), has('k'));
     const bool ok = refused.empty();
     if (ok != want_ok) { ++failures; std::printf("FAIL %-44s wanted %s, got %s\n", label, want_ok ? "accepted" : "refused", ok ? "accepted" : refused.c_str()); return; }
     std::printf("ok   %-44s %s\n", label, ok ? "accepted" : refused.substr(0, 60).c_str());
@@ -99,16 +99,21 @@ void run(const char* label, const char* use, bool want_ok, const std::function<v
     // the model on what was accepted: stride plan and zerofier, periodic columns as polynomials, boundary values under a challenge
     sp::AirStridePlan plan;
     bool fine = sp::air_stride_plan(st.air, 16, plan) && st.aux.has_value() == has('x') && st.periodic.has_value() == has('p') && st.bvals.has_value() == has('b') &&
-                (st.aux_periodic() != nullptr) == (has('P') && has('p')) && st.main.has_value() == (has('m') || has('r') || has('l')) && st.main_rec == (has('r') || has('l')) && st.main_lk == has('l') &&
-                !st.unsupported;
+                (st.aux_periodic() != nullptr) == (has('P') && has('p')) && st.main.has_value() == (has('m') || has('r') || has('l') || has('k')) && st.main_rec == (has('r') || has('l') || has('k')) &&
+                st.main_lk == (has('l') || has('k')) && st.main_link == has('k') && !st.unsupported;
     if (st.main && has('l') && !has('r') && st.main->cols.size() == 3) {   // what the prover's chunking reads of a COUNT column
         const auto& c = st.main->cols;
         fine = fine && c[1].kind == SP_AIR_MAIN_COUNT && c[1].key_bits == p.lcols[1].pad && c[1].num_op == 3 && c[1].den_op == 1 && c[1].reads == 1 && c[0].key_bits == 0 &&
                c[2].key_bits == 0 && c[2].reads == 2;
     }
+    if (st.main && has('k')) {   // what the prover's chunking reads of a linked group: l, j and k apart
+        const auto& c = st.main->cols;
+        fine = fine && c.size() == 3 && c[0].chain_log == (p.rcols[0].pad & 255u) && c[0].chain_link == (p.rcols[0].pad >> 16) && c[0].chain_pos == 0 &&
+               c[1].chain_pos == 1 && c[1].chain_link == c[0].chain_link && c[2].chain_link == 0;
+    }
     if (st.main && has('r')) {   // what the prover's chunking reads of a chain group
         const auto& c = st.main->cols;
-        fine = fine && c.size() == 3 && c[0].kind == SP_AIR_MAIN_CHAIN && c[0].chain_log == (p.rcols[0].pad & 255u) && c[0].chain_pos == 0 && c[1].chain_log == c[0].chain_log && c[1].chain_pos == 1 &&
+        fine = fine && c.size() == 3 && c[0].chain_link == 0 && c[0].kind == SP_AIR_MAIN_CHAIN && c[0].chain_log == (p.rcols[0].pad & 255u) && c[0].chain_pos == 0 && c[1].chain_log == c[0].chain_log && c[1].chain_pos == 1 &&
                c[2].chain_log == 0 && c[2].reads == 1;
     }
     if (st.main && has('m')) {   // what the prover's chunking reads: which derived columns each column needs, and the bit
@@ -275,6 +280,27 @@ int main() {
     run("count: kind 7", "pl", false, [](Parts& p) { p.lcols[2].kind = 7; });
     run("count: op 6 without periodic columns", "l", false, none);
     run("count: aux_kind 2", "pl", false, [](Parts& p) { p.d.aux_kind = 2; });
+    // ---- linked chain groups (the _link policy): l = 2 throughout, k in bits 16 and up of pad
+    const auto linked = [](uint32_t k, uint32_t k1) { return [k, k1](Parts& p) { p.rcols[0].pad = 2 + (k << 16); p.rcols[1].pad = 2 + 256 + (k1 << 16); }; };
+    const auto carried = [](uint32_t k) { return [k](Parts& p) { p.rcols[0].pad = 2 + (k << 16); p.rcols[1].pad = 2 + 256 + (k << 16); p.rcols[1].den_op = 2; }; };
+    run("link: a chain program with k = 0", "pk", true, none);
+    run("link: a lookup program", "pl", true, none);
+    run("link: runs of two blocks", "pk", true, linked(1, 1));
+    run("link: the whole trace one run", "pk", true, linked(2, 2));
+    run("link: a seed reads the carry", "pk", true, carried(1));
+    run("link: beside everything", "xpsbPk", true, [&](Parts& p) { p.aux.n_ops = 4; carried(2)(p); });
+    run("link: a run longer than the trace", "pk", false, linked(3, 3));
+    run("link: k = 63", "pk", false, linked(63, 63));
+    run("link: k = 65535", "pk", false, linked(65535, 65535));
+    run("link: members differ in k", "pk", false, linked(2, 1));
+    run("link: k on the second column alone", "pk", false, linked(0, 1));
+    run("link: a seed reads its group, k = 0", "pk", false, carried(0));
+    run("link: a seed reads its group at shift 1", "pk", false, [&](Parts& p) { carried(1)(p); p.rcols[1].den_op = 6; });
+    run("link: j = 1 opens", "pk", false, [](Parts& p) { p.rcols[0].pad = 2 + 256 + (1u << 16); });
+    run("link: l = 0", "pk", false, [](Parts& p) { p.rcols[0].pad = 1u << 16; p.rcols[1].pad = 256 + (1u << 16); });
+    run("link: k through the _rec policy", "pr", false, linked(1, 1));
+    run("link: k through the _lk policy", "prl", false, linked(1, 1));
+    run("link: op 6 without periodic columns", "k", false, none);
     run("no main column", "", false, [](Parts& p) { p.d.main_cols = 0; p.ops[2] = sp_air_op{1, 0, 0, 0, 0}; });
     run("1025 columns", "", false, [](Parts& p) { p.d.main_cols = 1024; p.ops[2] = sp_air_op{1, 0, 0, 0, 0}; });
     std::printf("%s\n", failures ? "FAILED" : "all verdicts as expected");
