@@ -17,6 +17,9 @@ constexpr uint32_t AIR_AUX_MAX_SHIFT = 7;
 // trace: [main_cols][n] natural order; consts: the aux constants followed by the RAP challenges.
 // pcols / pvals (both null for a program without op 6, which then launches the kernel without them): the periodic columns an op 6
 // reads, a = row shift, b = column k: pvals[off_k + ((i + a) mod period_k)] - the raw values, as the exact trace check reads them.
+// A row-local chunk of the main program (build_main_program) runs through the same call: trace then holds the inputs and the derived
+// columns of earlier chunks, num is the chunk's first column and den the workspace - OUT AIR_AUX_DEN_TAG + s stores into slot s at
+// den[s * n + i]: a denominator, the N of an INV_OR_ZERO column or the N of a BIT group.
 int air_aux_terms(hipStream_t st, const fe* trace, uint64_t n, const AirOpDev* ops, uint32_t n_ops, const fe* consts, fe* num, fe* den,
                   const AirPeriodicCol* pcols = nullptr, const fe* pvals = nullptr);
 // Sorted columns (SP_AIR_AUX_SORTED), one sort group at a time.  Key pass, one thread per row: the group's program, OUT a <

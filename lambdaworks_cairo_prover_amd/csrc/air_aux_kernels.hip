@@ -32,17 +32,13 @@ __global__ void __launch_bounds__(256) air_aux_terms_kernel(const fe* __restrict
     air_aux_terms_row<false>(trace, n, i, ops, n_ops, consts, num, den, AirNoPeriodic{});
 }
 
-// op 6: a = row shift, b = periodic column.  A period is a power of two <= n, so (i + shift) mod period is a mask and stays inside the
-// column's own values.
+// op 6 through AirRowPeriodic (air_interp.h)
 __global__ void __launch_bounds__(256) air_aux_terms_periodic_kernel(const fe* __restrict__ trace, uint64_t n, const AirOpDev* __restrict__ ops, uint32_t n_ops,
                                                                      const fe* __restrict__ consts, fe* __restrict__ num, fe* __restrict__ den,
                                                                      const AirPeriodicCol* __restrict__ pcols, const fe* __restrict__ pvals) {
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    air_aux_terms_row<true>(trace, n, i, ops, n_ops, consts, num, den, [&](uint32_t shift, uint32_t col) {
-        const AirPeriodicCol pc = pcols[col];
-        return fe_ld(pvals + pc.off + ((i + shift) & ((1ull << pc.logp) - 1ull)));
-    });
+    air_aux_terms_row<true>(trace, n, i, ops, n_ops, consts, num, den, AirRowPeriodic{pcols, pvals, i});
 }
 
 int air_aux_terms(hipStream_t st, const fe* trace, uint64_t n, const AirOpDev* ops, uint32_t n_ops, const fe* consts, fe* num, fe* den,
@@ -86,10 +82,7 @@ __global__ void __launch_bounds__(256) air_aux_sort_terms_periodic_kernel(const 
                                                                           const AirPeriodicCol* __restrict__ pcols, const fe* __restrict__ pvals) {
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    air_aux_sort_terms_row<true>(trace, n, i, ops, n_ops, consts, vals, keys, idx, key_bits, flag, [&](uint32_t shift, uint32_t col) {
-        const AirPeriodicCol pc = pcols[col];
-        return fe_ld(pvals + pc.off + ((i + shift) & ((1ull << pc.logp) - 1ull)));
-    });
+    air_aux_sort_terms_row<true>(trace, n, i, ops, n_ops, consts, vals, keys, idx, key_bits, flag, AirRowPeriodic{pcols, pvals, i});
 }
 
 int air_aux_sort_terms(hipStream_t st, const fe* trace, uint64_t n, const AirOpDev* ops, uint32_t n_ops, const fe* consts, fe* vals, uint64_t* keys,

@@ -155,7 +155,8 @@ std::string validate_aux_program(const AirAuxHost& aux, uint32_t main_cols, uint
 // SP_AIR_MAIN_COUNT columns too - a table, key_bits in 1 .. 64, at most 16 of them; without lk kind 6 is an unknown kind.  link (the
 // _link entry points, with lk): a CHAIN column's pad is l + 256 j + 65536 k, runs of 2^k blocks; with k >= 1 a seed may load its own
 // group at shift 0; without link j = pad >> 8, so a pad with bits at or above 16 is a j out of sequence.
-std::string main_from_c(const AirDescHost& air, const sp_air_main_desc* m, uint64_t n, uint32_t n_periodic, bool rec, bool lk, bool link, AirMainHost& out) {
+std::string main_from_c(const AirDescHost& air, const sp_air_main_desc* m, uint64_t n, uint32_t n_periodic, AirMainLevel level, AirMainHost& out) {
+    const bool rec = air_main_allows_chains(level), lk = air_main_allows_counts(level), link = air_main_allows_runs(level);
     if (m->size != sizeof(sp_air_main_desc)) return "main program: sp_air_main_desc.size is not sizeof(sp_air_main_desc)";
     if (!m->ops || !m->consts || !m->cols) return "main program: null ops, consts or cols";
     if (m->input_cols == 0 || m->n_cols == 0 || (uint64_t)m->input_cols + m->n_cols != air.main_cols)
@@ -274,12 +275,10 @@ bool air_boundary_from_c(const sp_air_boundary_desc* d, uint32_t n_boundary, uin
 
 std::string air_statement_from_c(const sp_air_desc* d, const sp_air_aux_desc* aux, const sp_air_periodic_desc* periodic, const sp_air_stride_desc* strides,
                                  const sp_air_boundary_desc* bvals, bool aux_reads_periodic, uint64_t n, AirStatement& st, const sp_air_main_desc* main,
-                                 bool main_rec, bool main_lk, bool main_link) {
+                                 AirMainLevel main_level) {
     AirDescHost& air = st.air;
     st.aux_reads_periodic = aux_reads_periodic;
-    st.main_rec = main_rec || main_lk || main_link;
-    st.main_lk = main_lk || main_link;
-    st.main_link = main_link;
+    st.main_level = main_level;
     if (!air_desc_from_c(d, air)) return "malformed AIR descriptor (1 .. 8 frame rows, 1 .. 64 transition constraints, every count with its array)";
     if (periodic && !air_periodic_from_c(periodic, n, st.periodic.emplace()))
         return "malformed periodic columns (at most 64, each a power-of-two number of values, at most the trace length)";
@@ -298,7 +297,7 @@ std::string air_statement_from_c(const sp_air_desc* d, const sp_air_aux_desc* au
     if (main) {
         // (only the _rec, _lk and _link entry points let a main program hold chain columns and read the periodic columns, only _lk and
         // _link COUNT columns, only _link runs of blocks)
-        const std::string refused = main_from_c(air, main, n, st.n_periodic(), st.main_rec, st.main_lk, st.main_link, st.main.emplace());
+        const std::string refused = main_from_c(air, main, n, st.n_periodic(), st.main_level, st.main.emplace());
         if (!refused.empty()) return refused;
     }
     // (only the _pub entry points let an auxiliary program read the periodic columns: 0 of them from everywhere else)

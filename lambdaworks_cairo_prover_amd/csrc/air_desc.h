@@ -116,6 +116,16 @@ size_t air_program_first_bad_op(const std::vector<AirOpHost>& ops, uint32_t load
 // the primitive root of unity of order 2^order (lambdaworks get_primitive_root_of_unity)
 fe air_root_of_unity(int order);
 
+// What a main-trace program may hold, one ordered level - each brings the ones before it with it:
+//   Main   VALUE, INV_OR_ZERO, BIT, SUM and PRODUCT columns over ops 0 .. 4
+//   Rec    (the _rec entry points) CHAIN columns too, and op 6 reads the periodic columns
+//   Lk     (the _lk entry points) COUNT columns too, lookup multiplicities
+//   Link   (the _link entry points) a chain group's blocks may form runs seeded from the block before
+enum class AirMainLevel : uint8_t { Main, Rec, Lk, Link };
+inline bool air_main_allows_chains(AirMainLevel l) { return l >= AirMainLevel::Rec; }   // (and op 6)
+inline bool air_main_allows_counts(AirMainLevel l) { return l >= AirMainLevel::Lk; }
+inline bool air_main_allows_runs(AirMainLevel l) { return l >= AirMainLevel::Link; }
+
 // Everything a prover, a trace check or a verifier is told about a program AIR: the descriptor (its strides inside) and its optional
 // parts, each present or not.  aux_reads_periodic: whether the auxiliary program may read the periodic columns with op 6 (the _pub
 // entry points; everywhere else such an op is malformed).
@@ -126,9 +136,7 @@ struct AirStatement {
     std::optional<AirBoundaryHost> bvals;     // boundary values computed from the RAP challenges (air_resolve_boundary_into after round 1)
     std::optional<AirMainHost> main;          // the main-trace program: the caller hands over its input columns only (sp_air_prove_main)
     bool aux_reads_periodic = false;
-    bool main_rec = false;                    // the main program may hold CHAIN columns and read the periodic columns with op 6 (the _rec entry points)
-    bool main_lk = false;                     // all of main_rec, and the main program may hold COUNT columns, lookup multiplicities (the _lk entry points)
-    bool main_link = false;                   // all of main_lk, and a chain group's blocks may form runs seeded from the block before (the _link entry points)
+    AirMainLevel main_level = AirMainLevel::Main;   // what the main program may hold: the entry point's suffix decides
     bool unsupported = false;                 // set with a refusal that is SP_E_UNSUPPORTED, not SP_E_INVALID_ARG (a main program beside aux_kind 1 or 2)
     // the periodic columns the auxiliary program may read: null when it may read none
     const AirPeriodicHost* aux_periodic() const { return aux_reads_periodic && periodic ? &*periodic : nullptr; }
@@ -144,12 +152,12 @@ struct AirStatement {
 // main (nullable, the prover and the trace check only): a main-trace program whose columns add up to air.main_cols, ops 0 .. 4 over
 // earlier ops, LOADs at shifts 0 .. 7 of inputs or - from the ops behind derived column j - of derived columns k < j, the kinds' own
 // rules (sp_air_main_desc); beside it aux_kind is 0 or SP_AIR_AUX_PROGRAM, else the refusal comes with out.unsupported set.
-// main_rec (the _rec entry points only): the main program may also hold SP_AIR_MAIN_CHAIN columns - groups of 1 .. 16 with j = 0, 1, ..
+// main_level Rec (the _rec entry points only): the main program may also hold SP_AIR_MAIN_CHAIN columns - groups of 1 .. 16 with j = 0, 1, ..
 // and one block length 2^l in 2 .. n, a seed that reads nothing of its group, a step that reads its group at shift 0 only - and read
 // the periodic columns with op 6; without it kind 5 is an unknown kind and op 6 a malformed op, as ever.
-// main_lk (the _lk entry points only; it brings main_rec with it): the main program may also hold SP_AIR_MAIN_COUNT columns - at most
+// main_level Lk (the _lk entry points only; it brings Rec with it): the main program may also hold SP_AIR_MAIN_COUNT columns - at most
 // 16, each with a table (den_op), key_bits (pad) in 1 .. 64, X and T over earlier columns; without it kind 6 is an unknown kind.
-// main_link (the _link entry points only; it brings main_lk with it): a CHAIN column's pad also carries k = pad >> 16 - runs of 2^k
+// main_level Link (the _link entry points only; it brings Lk with it): a CHAIN column's pad also carries k = pad >> 16 - runs of 2^k
 // blocks, l + k <= log2 n, one k per group - and with k >= 1 a seed may load its own group at shift 0 (the carry); without it the
 // bits at and above 16 belong to j, as ever.
 // The constraint program itself is checked where it is turned into what runs it (build_air_program, air_verify_host).
@@ -157,7 +165,7 @@ struct AirStatement {
 inline const char* air_ext_refusal(const sp_air_ext* ext) { return ext && ext->size != sizeof(sp_air_ext) ? "sp_air_ext.size is not sizeof(sp_air_ext)" : nullptr; }
 std::string air_statement_from_c(const sp_air_desc* d, const sp_air_aux_desc* aux, const sp_air_periodic_desc* periodic, const sp_air_stride_desc* strides,
                                  const sp_air_boundary_desc* bvals, bool aux_reads_periodic, uint64_t n, AirStatement& out,
-                                 const sp_air_main_desc* main = nullptr, bool main_rec = false, bool main_lk = false, bool main_link = false);
+                                 const sp_air_main_desc* main = nullptr, AirMainLevel main_level = AirMainLevel::Main);
 // `verify::<F, A>` for a program AIR (verifier.cpp): 1 accept, 0 reject; throws std::runtime_error on a malformed proof or constraint
 // program.  st.aux is the prover's business and is not looked at.
 int air_verify_host(const uint8_t* proof_bytes, size_t len, const AirStatement& st, const ProofOptionsHost& opt);

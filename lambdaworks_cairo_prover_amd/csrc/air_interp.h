@@ -13,6 +13,19 @@ namespace sp {
 
 struct AirNoPeriodic { __device__ fe operator()(uint32_t, uint32_t) const { return fe_zero(); } };
 
+// op 6 of a row program (the auxiliary terms, the sort keys, the main terms and chains): a = row shift, b = periodic column, read
+// relative to the lane's row i - held by reference, since a chain's lane moves it.  A period is a power of two <= n, so (i + shift)
+// mod period is a mask and stays inside the column's own values.
+struct AirRowPeriodic {
+    const AirPeriodicCol* __restrict__ pcols;
+    const fe* __restrict__ pvals;
+    const uint64_t& i;
+    __device__ fe operator()(uint32_t shift, uint32_t col) const {
+        const AirPeriodicCol pc = pcols[col];
+        return fe_ld(pvals + pc.off + ((i + shift) & ((1ull << pc.logp) - 1ull)));
+    }
+};
+
 template <bool PER, class Load, class Periodic, class Out>
 __device__ __forceinline__ void air_run_program(const AirOpDev* __restrict__ ops, uint32_t n_ops, const fe* __restrict__ consts, Load load,
                                                 Periodic periodic, Out out) {

@@ -8,28 +8,21 @@
 
 namespace sp {
 
-// One thread per row: the program once (an AirOpDev list with slots, the OUT codes of air_aux_kernels.h): OUT a < AIR_AUX_DEN_TAG
-// stores N of chunk column a at cols[a * n + i], OUT AIR_AUX_DEN_TAG + s stores into workspace slot s at ws[s * n + i] - a
-// denominator, the N of an INV_OR_ZERO column or the N of a BIT group.  trace: [main_cols][n] natural order, of which the inputs and
-// the derived columns of earlier chunks exist; LOAD a = row shift, b = column: row (i + a) mod n.  pcols / pvals (both null for a
-// program without op 6, which then launches the kernel without them): the periodic columns, as air_aux_terms takes them.
-int air_main_terms(hipStream_t st, const fe* trace, uint64_t n, const AirOpDev* ops, uint32_t n_ops, const fe* consts, fe* cols, fe* ws,
-                   const AirPeriodicCol* pcols = nullptr, const fe* pvals = nullptr);
-// One chain group: columns [first_col, first_col + w) of trace, w <= AIR_MAIN_CHAIN_WIDTH, in blocks of 2^log_s rows (2^log_s <= n).
-// One lane per block B < n >> log_s, 64-lane work-groups: the seed program once on row B s - OUT j stores column j's seed -, then for
-// t = 0 .. s - 2 the step program on row i = B s + t - a LOAD of a group column is the lane's state (the decoder allows shift 0 only),
-// every other LOAD row (i + shift) mod n of trace, OUT j the next value of column j - after which the state becomes the next values
-// and goes to row i + 1.  Neither program reads the group's columns from memory: what the kernel reads and what it writes are apart.
+// The per-row terms of a chunk come from air_aux_terms (air_aux_kernels.h), which documents what a main chunk's OUT codes mean.
+// One chain group: columns [first_col, first_col + w) of trace, w <= AIR_MAIN_CHAIN_WIDTH, in blocks of 2^log_s rows.
+// log_k = 0 (2^log_s <= n): one lane per block B < n >> log_s, 64-lane work-groups: the seed program once on row B s - OUT j stores
+// column j's seed -, then for t = 0 .. s - 2 the step program on row i = B s + t - a LOAD of a group column is the lane's state (the
+// decoder allows shift 0 only), every other LOAD row (i + shift) mod n of trace, OUT j the next value of column j - after which the
+// state becomes the next values and goes to row i + 1.  Neither program reads the group's columns from memory: what the kernel reads
+// and what it writes are apart.
+// log_k >= 1, a linked group (runs of 2^log_k blocks, 2^(log_s + log_k) <= n): one lane per run R < n >> (log_s + log_k).  The lane's
+// state starts as zero; for each block of its run it runs the seed program on the block's first row - a LOAD of a group column is the
+// lane's state, the last row of the block before (the carry; zero on the run's first block), every other LOAD and op 6 as in the step
+// program - assigns the w seeds together, and then walks the block as above.  The two cases are instantiations of one kernel body.
 constexpr uint32_t AIR_MAIN_CHAIN_WIDTH = 16;
-int air_main_chain(hipStream_t st, fe* trace, uint64_t n, uint32_t log_s, uint32_t first_col, uint32_t w, const AirOpDev* seed_ops, uint32_t n_seed,
-                   const AirOpDev* step_ops, uint32_t n_step, const fe* consts, const AirPeriodicCol* pcols = nullptr, const fe* pvals = nullptr);
-// One linked chain group (runs of 2^log_k blocks, log_k >= 1, 2^(log_s + log_k) <= n): one lane per run R < n >> (log_s + log_k),
-// 64-lane work-groups.  The lane's state starts as zero; for each block of its run it runs the seed program on the block's first row -
-// a LOAD of a group column is the lane's state, the last row of the block before (the carry; zero on the run's first block), every
-// other LOAD and op 6 as in the step program - assigns the w seeds together, and then walks the block as air_main_chain does.
-int air_main_chain_linked(hipStream_t st, fe* trace, uint64_t n, uint32_t log_s, uint32_t log_k, uint32_t first_col, uint32_t w, const AirOpDev* seed_ops,
-                          uint32_t n_seed, const AirOpDev* step_ops, uint32_t n_step, const fe* consts, const AirPeriodicCol* pcols = nullptr,
-                          const fe* pvals = nullptr);
+int air_main_chain(hipStream_t st, fe* trace, uint64_t n, uint32_t log_s, uint32_t log_k, uint32_t first_col, uint32_t w, const AirOpDev* seed_ops,
+                   uint32_t n_seed, const AirOpDev* step_ops, uint32_t n_step, const fe* consts, const AirPeriodicCol* pcols = nullptr,
+                   const fe* pvals = nullptr);
 // One COUNT column (a lookup multiplicity): kx the n looked-up keys in ascending order, kt the n table keys in ascending order - sorted
 // stably, rows[p] the row that table key p came from - all from air_aux_sort_terms and radix_sort_pairs_u64.  One lane per p: on the
 // head of a run of equal table keys (p == 0 or kt[p] != kt[p - 1]) z = upper_bound(kx, kt[p]) - lower_bound(kx, kt[p]), elsewhere

@@ -4,71 +4,34 @@
 
 namespace sp {
 
-// The third user of the shared interpreter (beside the composition and air_aux_terms_kernel): LOAD takes the row shift itself, an OUT
-// stores into the chunk column or the workspace slot it names.  Two kernels share the body, as the auxiliary terms do: a program without
-// op 6 runs the one without periodic columns.
-template <bool PER, class Periodic>
-__device__ __forceinline__ void air_main_terms_row(const fe* __restrict__ trace, uint64_t n, uint64_t i, const AirOpDev* __restrict__ ops, uint32_t n_ops,
-                                                   const fe* __restrict__ consts, fe* __restrict__ cols, fe* __restrict__ ws, Periodic periodic) {
-    air_run_program<PER>(
-        ops, n_ops, consts,
-        [&](uint32_t shift, uint32_t col) { return fe_ld(trace + (uint64_t)col * n + ((i + shift) & (n - 1))); },   // n is a power of two
-        periodic,
-        [&](uint32_t a, const fe& val) {
-            fe* dst = a < AIR_AUX_DEN_TAG ? cols + (uint64_t)a * n : ws + (uint64_t)(a - AIR_AUX_DEN_TAG) * n;
-            fe_st(dst + i, val);
-        });
-}
+// The per-row terms of a chunk are the auxiliary programs' kernel, air_aux_terms (air_aux_kernels.h): the same program shape, the
+// same two destinations of an OUT.
 
-__global__ void __launch_bounds__(256) air_main_terms_kernel(const fe* __restrict__ trace, uint64_t n, const AirOpDev* __restrict__ ops, uint32_t n_ops,
-                                                             const fe* __restrict__ consts, fe* __restrict__ cols, fe* __restrict__ ws) {
-    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    air_main_terms_row<false>(trace, n, i, ops, n_ops, consts, cols, ws, AirNoPeriodic{});
-}
-
-// op 6: a = row shift, b = periodic column; a period is a power of two <= n, so the mask stays inside the column's own values
-__global__ void __launch_bounds__(256) air_main_terms_periodic_kernel(const fe* __restrict__ trace, uint64_t n, const AirOpDev* __restrict__ ops, uint32_t n_ops,
-                                                                      const fe* __restrict__ consts, fe* __restrict__ cols, fe* __restrict__ ws,
-                                                                      const AirPeriodicCol* __restrict__ pcols, const fe* __restrict__ pvals) {
-    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    air_main_terms_row<true>(trace, n, i, ops, n_ops, consts, cols, ws, [&](uint32_t shift, uint32_t col) {
-        const AirPeriodicCol pc = pcols[col];
-        return fe_ld(pvals + pc.off + ((i + shift) & ((1ull << pc.logp) - 1ull)));
-    });
-}
-
-int air_main_terms(hipStream_t st, const fe* trace, uint64_t n, const AirOpDev* ops, uint32_t n_ops, const fe* consts, fe* cols, fe* ws,
-                   const AirPeriodicCol* pcols, const fe* pvals) {
-    if (n == 0 || (n & (n - 1)) || (pcols == nullptr) != (pvals == nullptr)) return SP_E_INVALID_ARG;
-    const dim3 grid((unsigned)((n + 255) / 256));
-    if (pcols) hipLaunchKernelGGL(air_main_terms_periodic_kernel, grid, dim3(256), 0, st, trace, n, ops, n_ops, consts, cols, ws, pcols, pvals);
-    else hipLaunchKernelGGL(air_main_terms_kernel, grid, dim3(256), 0, st, trace, n, ops, n_ops, consts, cols, ws);
-    SP_HIP_CHECK(hipGetLastError());
-    return SP_OK;
-}
-
-// ---- chain groups: one lane per block of s rows -------------------------------------------------------------------------------
+// ---- chain groups: one lane per block of s rows, or per run of 2^log_k blocks ---------------------------------------------------
 // The serial dimension is the block, s - 1 dependent steps; the n / s blocks are the parallel one.  Work-groups of one wave: the
 // waves are few (n / (64 s)) and spread over the CUs this way instead of stacking four to a CU.  The state lives in a per-lane array
 // beside the interpreter's values; `next` holds the step's OUTs until the program is through, since an OUT of column j may come before
 // a later LOAD of the state of column j.  A lane's stores are 32 s bytes from its neighbour's and stay direct: the kernel is bound by
 // its s - 1 dependent steps of several field products each, not by the n w 32 bytes it writes, and a lane fills the other quarters of
 // each 128-byte line within its next three steps.
-template <bool PER>
+// LINKED (runs of 2^log_k blocks): the blocks of a run are serial too - a seed reads the last state of the block before -, so the lane
+// walks the whole run, 2^(log_s + log_k) rows, and the n >> (log_s + log_k) runs are the parallel dimension.  The state starts as zero,
+// the carry of a run's first block; after a block's last advance() it holds that block's last row, which is what the next seed
+// program's LOADs of the group read (from_state, not from_trace).  An instantiation of its own, not a run-time flag: a group without
+// runs (log_k = 0, which the unlinked instantiations do not read) launches the code it always launched.
+template <bool PER, bool LINKED>
 __global__ void __launch_bounds__(64) air_main_chain_kernel(fe* __restrict__ group, const fe* __restrict__ trace, uint64_t n, uint32_t log_s, uint32_t first_col,
                                                             uint32_t w, const AirOpDev* __restrict__ seed_ops, uint32_t n_seed,
                                                             const AirOpDev* __restrict__ step_ops, uint32_t n_step, const fe* __restrict__ consts,
-                                                            const AirPeriodicCol* __restrict__ pcols, const fe* __restrict__ pvals) {
-    const uint64_t B = (uint64_t)blockIdx.x * 64 + threadIdx.x;
-    if (B >= (n >> log_s)) return;   // (with fewer than 64 blocks the only wave is partly empty)
+                                                            const AirPeriodicCol* __restrict__ pcols, const fe* __restrict__ pvals, uint32_t log_k) {
+    const uint32_t log_run = LINKED ? log_s + log_k : log_s;
+    const uint64_t L = (uint64_t)blockIdx.x * 64 + threadIdx.x;
+    if (L >= (n >> log_run)) return;   // (with fewer than 64 blocks or runs the only wave is partly empty)
     fe state[AIR_MAIN_CHAIN_WIDTH], next[AIR_MAIN_CHAIN_WIDTH];
-    uint64_t i = B << log_s;
-    auto periodic = [&](uint32_t shift, uint32_t col) {
-        const AirPeriodicCol pc = pcols[col];
-        return fe_ld(pvals + pc.off + ((i + shift) & ((1ull << pc.logp) - 1ull)));
-    };
+    if constexpr (LINKED)
+        for (uint32_t j = 0; j < AIR_MAIN_CHAIN_WIDTH; ++j) state[j] = fe_zero();
+    uint64_t i = L << log_run;
+    const AirRowPeriodic periodic{pcols, pvals, i};
     auto from_trace = [&](uint32_t shift, uint32_t col) { return fe_ld(trace + (uint64_t)col * n + ((i + shift) & (n - 1))); };
     auto from_state = [&](uint32_t shift, uint32_t col) {   // (col - first_col wraps to a large value for a column before the group)
         return col - first_col < w ? state[col - first_col] : from_trace(shift, col);
@@ -80,89 +43,42 @@ __global__ void __launch_bounds__(64) air_main_chain_kernel(fe* __restrict__ gro
             fe_st(group + (uint64_t)j * n + i, next[j]);
         }
     };
-    if constexpr (PER) air_run_program<true>(seed_ops, n_seed, consts, from_trace, periodic, to_next);
-    else air_run_program<false>(seed_ops, n_seed, consts, from_trace, AirNoPeriodic{}, to_next);
-    advance();
-    const uint64_t last = i + (1ull << log_s) - 1;
-    while (i < last) {
-        if constexpr (PER) air_run_program<true>(step_ops, n_step, consts, from_state, periodic, to_next);
-        else air_run_program<false>(step_ops, n_step, consts, from_state, AirNoPeriodic{}, to_next);
-        ++i;
-        advance();
-    }
-}
-
-int air_main_chain(hipStream_t st, fe* trace, uint64_t n, uint32_t log_s, uint32_t first_col, uint32_t w, const AirOpDev* seed_ops, uint32_t n_seed,
-                   const AirOpDev* step_ops, uint32_t n_step, const fe* consts, const AirPeriodicCol* pcols, const fe* pvals) {
-    if (n == 0 || (n & (n - 1)) || log_s == 0 || log_s >= 64 || (1ull << log_s) > n || w == 0 || w > AIR_MAIN_CHAIN_WIDTH || (pcols == nullptr) != (pvals == nullptr))
-        return SP_E_INVALID_ARG;
-    const uint64_t lanes = n >> log_s;
-    const dim3 grid((unsigned)((lanes + 63) / 64));
-    fe* group = trace + (uint64_t)first_col * n;
-    if (pcols) hipLaunchKernelGGL(air_main_chain_kernel<true>, grid, dim3(64), 0, st, group, trace, n, log_s, first_col, w, seed_ops, n_seed, step_ops, n_step, consts, pcols, pvals);
-    else hipLaunchKernelGGL(air_main_chain_kernel<false>, grid, dim3(64), 0, st, group, trace, n, log_s, first_col, w, seed_ops, n_seed, step_ops, n_step, consts, pcols, pvals);
-    SP_HIP_CHECK(hipGetLastError());
-    return SP_OK;
-}
-
-// ---- linked chain groups: one lane per run of 2^log_k blocks ------------------------------------------------------------------
-// The blocks of a run are serial too - a seed reads the last state of the block before -, so the lane walks the whole run, 2^(log_s +
-// log_k) rows, and the n >> (log_s + log_k) runs are the parallel dimension.  The state starts as zero, the carry of a run's first
-// block; after a block's last advance() it holds that block's last row, which is what the next seed program's LOADs of the group read.
-// The body is the unlinked kernel's, the seeds' loader apart (from_state, not from_trace), in a loop over the blocks; a kernel of its
-// own, so that a group without runs launches the code it always launched.
-template <bool PER>
-__global__ void __launch_bounds__(64) air_main_chain_linked_kernel(fe* __restrict__ group, const fe* __restrict__ trace, uint64_t n, uint32_t log_s, uint32_t log_k,
-                                                                   uint32_t first_col, uint32_t w, const AirOpDev* __restrict__ seed_ops, uint32_t n_seed,
-                                                                   const AirOpDev* __restrict__ step_ops, uint32_t n_step, const fe* __restrict__ consts,
-                                                                   const AirPeriodicCol* __restrict__ pcols, const fe* __restrict__ pvals) {
-    const uint64_t R = (uint64_t)blockIdx.x * 64 + threadIdx.x;
-    if (R >= (n >> (log_s + log_k))) return;   // (with fewer than 64 runs the only wave is partly empty)
-    fe state[AIR_MAIN_CHAIN_WIDTH], next[AIR_MAIN_CHAIN_WIDTH];
-    for (uint32_t j = 0; j < AIR_MAIN_CHAIN_WIDTH; ++j) state[j] = fe_zero();
-    uint64_t i = R << (log_s + log_k);
-    auto periodic = [&](uint32_t shift, uint32_t col) {
-        const AirPeriodicCol pc = pcols[col];
-        return fe_ld(pvals + pc.off + ((i + shift) & ((1ull << pc.logp) - 1ull)));
+    auto run = [&](const AirOpDev* ops, uint32_t n_ops, auto load) {
+        if constexpr (PER) air_run_program<true>(ops, n_ops, consts, load, periodic, to_next);
+        else air_run_program<false>(ops, n_ops, consts, load, AirNoPeriodic{}, to_next);
     };
-    auto from_trace = [&](uint32_t shift, uint32_t col) { return fe_ld(trace + (uint64_t)col * n + ((i + shift) & (n - 1))); };
-    auto from_state = [&](uint32_t shift, uint32_t col) {   // (col - first_col wraps to a large value for a column before the group)
-        return col - first_col < w ? state[col - first_col] : from_trace(shift, col);
-    };
-    auto to_next = [&](uint32_t j, const fe& val) { next[j] = val; };
-    auto advance = [&]() {
-        for (uint32_t j = 0; j < w; ++j) {
-            state[j] = next[j];
-            fe_st(group + (uint64_t)j * n + i, next[j]);
-        }
-    };
-    const uint64_t run_end = i + (1ull << (log_s + log_k));
-    while (i < run_end) {
-        // the seeds on the block's first row: a LOAD of the group is the carry, the state the block before left (zero in front of a run)
-        if constexpr (PER) air_run_program<true>(seed_ops, n_seed, consts, from_state, periodic, to_next);
-        else air_run_program<false>(seed_ops, n_seed, consts, from_state, AirNoPeriodic{}, to_next);
+    auto block = [&](auto seed_load) {   // the seeds on the block's first row, then its s - 1 steps; leaves i on the block's last row
+        run(seed_ops, n_seed, seed_load);
         advance();
         const uint64_t last = i + (1ull << log_s) - 1;
         while (i < last) {
-            if constexpr (PER) air_run_program<true>(step_ops, n_step, consts, from_state, periodic, to_next);
-            else air_run_program<false>(step_ops, n_step, consts, from_state, AirNoPeriodic{}, to_next);
+            run(step_ops, n_step, from_state);
             ++i;
             advance();
         }
-        ++i;
+    };
+    if constexpr (LINKED) {
+        // a seed's LOAD of the group is the carry, the state the block before left (zero in front of a run)
+        for (const uint64_t run_end = i + (1ull << log_run); i < run_end; ++i) block(from_state);
+    } else {
+        block(from_trace);
     }
 }
 
-int air_main_chain_linked(hipStream_t st, fe* trace, uint64_t n, uint32_t log_s, uint32_t log_k, uint32_t first_col, uint32_t w, const AirOpDev* seed_ops,
-                          uint32_t n_seed, const AirOpDev* step_ops, uint32_t n_step, const fe* consts, const AirPeriodicCol* pcols, const fe* pvals) {
-    if (n == 0 || (n & (n - 1)) || log_s == 0 || log_k == 0 || log_s + log_k >= 64 || (1ull << (log_s + log_k)) > n || w == 0 || w > AIR_MAIN_CHAIN_WIDTH ||
+// log_k = 0: an unlinked group, one lane per block; log_k >= 1: runs of 2^log_k blocks, one lane per run.
+int air_main_chain(hipStream_t st, fe* trace, uint64_t n, uint32_t log_s, uint32_t log_k, uint32_t first_col, uint32_t w, const AirOpDev* seed_ops,
+                   uint32_t n_seed, const AirOpDev* step_ops, uint32_t n_step, const fe* consts, const AirPeriodicCol* pcols, const fe* pvals) {
+    if (n == 0 || (n & (n - 1)) || log_s == 0 || log_s + log_k >= 64 || (1ull << (log_s + log_k)) > n || w == 0 || w > AIR_MAIN_CHAIN_WIDTH ||
         (pcols == nullptr) != (pvals == nullptr))
         return SP_E_INVALID_ARG;
     const uint64_t lanes = n >> (log_s + log_k);
     const dim3 grid((unsigned)((lanes + 63) / 64));
     fe* group = trace + (uint64_t)first_col * n;
-    if (pcols) hipLaunchKernelGGL(air_main_chain_linked_kernel<true>, grid, dim3(64), 0, st, group, trace, n, log_s, log_k, first_col, w, seed_ops, n_seed, step_ops, n_step, consts, pcols, pvals);
-    else hipLaunchKernelGGL(air_main_chain_linked_kernel<false>, grid, dim3(64), 0, st, group, trace, n, log_s, log_k, first_col, w, seed_ops, n_seed, step_ops, n_step, consts, pcols, pvals);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(64), 0, st, group, trace, n, log_s, first_col, w, seed_ops, n_seed, step_ops, n_step, consts, pcols, pvals, log_k);
+    };
+    if (log_k == 0) pcols ? launch(air_main_chain_kernel<true, false>) : launch(air_main_chain_kernel<false, false>);
+    else pcols ? launch(air_main_chain_kernel<true, true>) : launch(air_main_chain_kernel<false, true>);
     SP_HIP_CHECK(hipGetLastError());
     return SP_OK;
 }

@@ -91,49 +91,28 @@ uint64_t sp_air_stride_desc_size(void) { return sizeof(sp_air_stride_desc); }
 uint64_t sp_air_ext_size(void) { return sizeof(sp_air_ext); }
 uint64_t sp_air_boundary_desc_size(void) { return sizeof(sp_air_boundary_desc); }
 uint64_t sp_air_main_desc_size(void) { return sizeof(sp_air_main_desc); }
-// The decoder's verdict on a main-trace program for this AIR and n rows (sp::air_statement_from_c), without a context.
-int sp_air_main_check(const sp_air_desc* d, const sp_air_main_desc* mp, uint64_t n) {
-    if (!d || !mp) return SP_E_INVALID_ARG;
-    try {
-        sp::AirStatement st;
-        const std::string refused = sp::air_statement_from_c(d, nullptr, nullptr, nullptr, nullptr, false, n, st, mp);
-        if (refused.empty()) return SP_OK;
-        sp_set_error("sp_air_main_check: " + refused);
-        return st.unsupported ? SP_E_UNSUPPORTED : SP_E_INVALID_ARG;
-    } catch (const std::exception& e) { sp_set_error(e.what()); return SP_E_INVALID_ARG; }
-}
-int sp_air_main_check_rec(const sp_air_desc* d, const sp_air_ext* ext, const sp_air_main_desc* mp, uint64_t n) {
+// The decoder's verdict on a main-trace program for this AIR and n rows (sp::air_statement_from_c), without a context.  ext: null for
+// sp_air_main_check, which has none and passes no periodic columns.
+static int air_main_check(const char* who, const sp_air_desc* d, const sp_air_ext* ext, sp::AirMainLevel level, const sp_air_main_desc* mp, uint64_t n) {
     if (!d || !mp) return SP_E_INVALID_ARG;
     if (const char* bad = sp::air_ext_refusal(ext)) { sp_set_error(bad); return SP_E_INVALID_ARG; }
     try {
         sp::AirStatement st;
-        const std::string refused = sp::air_statement_from_c(d, nullptr, ext ? ext->periodic : nullptr, nullptr, nullptr, false, n, st, mp, true);
+        const std::string refused = sp::air_statement_from_c(d, nullptr, ext ? ext->periodic : nullptr, nullptr, nullptr, false, n, st, mp, level);
         if (refused.empty()) return SP_OK;
-        sp_set_error("sp_air_main_check_rec: " + refused);
+        sp_set_error(std::string(who) + ": " + refused);
         return st.unsupported ? SP_E_UNSUPPORTED : SP_E_INVALID_ARG;
     } catch (const std::exception& e) { sp_set_error(e.what()); return SP_E_INVALID_ARG; }
+}
+int sp_air_main_check(const sp_air_desc* d, const sp_air_main_desc* mp, uint64_t n) { return air_main_check("sp_air_main_check", d, nullptr, sp::AirMainLevel::Main, mp, n); }
+int sp_air_main_check_rec(const sp_air_desc* d, const sp_air_ext* ext, const sp_air_main_desc* mp, uint64_t n) {
+    return air_main_check("sp_air_main_check_rec", d, ext, sp::AirMainLevel::Rec, mp, n);
 }
 int sp_air_main_check_lk(const sp_air_desc* d, const sp_air_ext* ext, const sp_air_main_desc* mp, uint64_t n) {
-    if (!d || !mp) return SP_E_INVALID_ARG;
-    if (const char* bad = sp::air_ext_refusal(ext)) { sp_set_error(bad); return SP_E_INVALID_ARG; }
-    try {
-        sp::AirStatement st;
-        const std::string refused = sp::air_statement_from_c(d, nullptr, ext ? ext->periodic : nullptr, nullptr, nullptr, false, n, st, mp, true, true);
-        if (refused.empty()) return SP_OK;
-        sp_set_error("sp_air_main_check_lk: " + refused);
-        return st.unsupported ? SP_E_UNSUPPORTED : SP_E_INVALID_ARG;
-    } catch (const std::exception& e) { sp_set_error(e.what()); return SP_E_INVALID_ARG; }
+    return air_main_check("sp_air_main_check_lk", d, ext, sp::AirMainLevel::Lk, mp, n);
 }
 int sp_air_main_check_link(const sp_air_desc* d, const sp_air_ext* ext, const sp_air_main_desc* mp, uint64_t n) {
-    if (!d || !mp) return SP_E_INVALID_ARG;
-    if (const char* bad = sp::air_ext_refusal(ext)) { sp_set_error(bad); return SP_E_INVALID_ARG; }
-    try {
-        sp::AirStatement st;
-        const std::string refused = sp::air_statement_from_c(d, nullptr, ext ? ext->periodic : nullptr, nullptr, nullptr, false, n, st, mp, true, true, true);
-        if (refused.empty()) return SP_OK;
-        sp_set_error("sp_air_main_check_link: " + refused);
-        return st.unsupported ? SP_E_UNSUPPORTED : SP_E_INVALID_ARG;
-    } catch (const std::exception& e) { sp_set_error(e.what()); return SP_E_INVALID_ARG; }
+    return air_main_check("sp_air_main_check_link", d, ext, sp::AirMainLevel::Link, mp, n);
 }
 int sp_air_main_link_limits(uint32_t out[2]) {
     if (!out) return SP_E_INVALID_ARG;

@@ -370,12 +370,10 @@ namespace {
 struct AirParts {
     const sp_air_aux_desc* aux; const sp_air_periodic_desc* periodic; const sp_air_stride_desc* strides; const sp_air_boundary_desc* bvals; bool aux_reads_periodic;
     const sp_air_main_desc* main;   // (the _main entry points: the trace argument then holds the input columns only)
-    bool main_rec;                  // (the _rec entry points: the main program may hold chain columns and read the periodic columns)
-    bool main_lk;                   // (the _lk entry points: all of that, and lookup multiplicities - SP_AIR_MAIN_COUNT columns)
-    bool main_link;                 // (the _link entry points: all of that, and chain groups whose blocks form runs seeded from the block before)
+    sp::AirMainLevel main_level;    // (what the main program may hold: the _rec, _lk and _link entry points raise it)
     static AirParts of_ext(const sp_air_ext* ext, const sp_air_boundary_desc* bvals, bool aux_reads_periodic, const sp_air_main_desc* main = nullptr,
-                           bool main_rec = false, bool main_lk = false, bool main_link = false) {
-        return AirParts{ext ? ext->aux : nullptr, ext ? ext->periodic : nullptr, ext ? ext->strides : nullptr, bvals, aux_reads_periodic, main, main_rec, main_lk, main_link};
+                           sp::AirMainLevel main_level = sp::AirMainLevel::Main) {
+        return AirParts{ext ? ext->aux : nullptr, ext ? ext->periodic : nullptr, ext ? ext->strides : nullptr, bvals, aux_reads_periodic, main, main_level};
     }
 };
 bool ext_ok(const sp_air_ext* ext) {
@@ -384,7 +382,7 @@ bool ext_ok(const sp_air_ext* ext) {
     return !bad;
 }
 int decode(const char* who, const sp_air_desc* d, const AirParts& p, uint64_t n, sp::AirStatement& st) {
-    const std::string refused = sp::air_statement_from_c(d, p.aux, p.periodic, p.strides, p.bvals, p.aux_reads_periodic, n, st, p.main, p.main_rec, p.main_lk, p.main_link);
+    const std::string refused = sp::air_statement_from_c(d, p.aux, p.periodic, p.strides, p.bvals, p.aux_reads_periodic, n, st, p.main, p.main_level);
     if (refused.empty()) return SP_OK;
     sp_set_error(std::string(who) + ": " + refused);
     return st.unsupported ? SP_E_UNSUPPORTED : SP_E_INVALID_ARG;
@@ -471,83 +469,88 @@ int sp_air_check_trace_pub(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ex
 }
 
 // sp_air_prove_pub / sp_air_check_trace_pub from the input columns of a main-trace program: the device derives the other main columns.
-int sp_air_prove_main(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const sp_air_boundary_desc* bv, const sp_air_main_desc* mp, const void* inputs,
-                      uint64_t n, const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len) {
-    if (!mp || !ext_ok(ext)) return SP_E_INVALID_ARG;
-    return air_prove_body(c, d, AirParts::of_ext(ext, bv, true, mp), static_cast<const uint8_t*>(inputs), n, opt, proof_out, proof_len);
-}
-int sp_air_check_trace_main(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const sp_air_boundary_desc* bv, const sp_air_main_desc* mp, const void* inputs,
-                            uint64_t n, const sp_proof_options* opt, const uint8_t* rap, sp_air_violation* out, uint32_t cap, uint32_t* n_out) {
-    if (!mp || !ext_ok(ext)) return SP_E_INVALID_ARG;
-    return air_check_trace_body(c, d, AirParts::of_ext(ext, bv, true, mp), static_cast<const uint8_t*>(inputs), n, opt, rap, out, cap, n_out);
-}
+// One body per family over the level of the main program (sp::AirMainLevel): _main, then _rec for block recurrences
+// (SP_AIR_MAIN_CHAIN) and reads of the periodic columns (op 6), _lk for lookup multiplicities (SP_AIR_MAIN_COUNT) too, _link for chain
+// groups that link their blocks into runs (the k of a CHAIN column's pad).
 namespace {
-// sp_air_main_trace and its _rec form (periodic: the columns an op 6 of the main program reads)
-int air_main_trace_body(const char* who, sp_ctx* c, const sp_air_desc* d, const sp_air_periodic_desc* periodic, bool main_rec, const sp_air_main_desc* mp,
-                        const void* inputs, uint64_t n, uint8_t* rows_out, bool main_lk = false, bool main_link = false) {
+using sp::AirMainLevel;
+int air_prove_main(AirMainLevel level, sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const sp_air_boundary_desc* bv, const sp_air_main_desc* mp,
+                   const void* inputs, uint64_t n, const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len) {
+    if (!mp || !ext_ok(ext)) return SP_E_INVALID_ARG;
+    return air_prove_body(c, d, AirParts::of_ext(ext, bv, true, mp, level), static_cast<const uint8_t*>(inputs), n, opt, proof_out, proof_len);
+}
+int air_check_trace_main(AirMainLevel level, sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const sp_air_boundary_desc* bv, const sp_air_main_desc* mp,
+                         const void* inputs, uint64_t n, const sp_proof_options* opt, const uint8_t* rap, sp_air_violation* out, uint32_t cap, uint32_t* n_out) {
+    if (!mp || !ext_ok(ext)) return SP_E_INVALID_ARG;
+    return air_check_trace_body(c, d, AirParts::of_ext(ext, bv, true, mp, level), static_cast<const uint8_t*>(inputs), n, opt, rap, out, cap, n_out);
+}
+// sp_air_main_trace and its forms with an ext (periodic: the columns an op 6 of the main program reads)
+int air_main_trace_body(const char* who, AirMainLevel level, sp_ctx* c, const sp_air_desc* d, const sp_air_periodic_desc* periodic, const sp_air_main_desc* mp,
+                        const void* inputs, uint64_t n, uint8_t* rows_out) {
     if (!c || !d || !mp || !inputs || !rows_out) return SP_E_INVALID_ARG;
     try {
         sp::AirStatement st;
         // (the table does not depend on the auxiliary segment: the statement is judged as one without, whatever the AIR's aux_kind)
         sp_air_desc main_only = *d;
         main_only.aux_cols = 0; main_only.aux_kind = 0;
-        SP_TRY(decode(who, &main_only, AirParts{nullptr, periodic, nullptr, nullptr, false, mp, main_rec, main_lk, main_link}, n, st));
+        SP_TRY(decode(who, &main_only, AirParts{nullptr, periodic, nullptr, nullptr, false, mp, level}, n, st));
         if (sp_log2_exact(n) < 0) { sp_set_error(std::string(who) + ": n must be a power of two"); return SP_E_INVALID_ARG; }
         c->prewarm_cancel.store(0, std::memory_order_release);
         return sp::air_main_trace(c, st, static_cast<const uint8_t*>(inputs), n, rows_out);
     } catch (const std::exception& e) { sp_set_error(e.what()); return SP_E_INVALID_ARG; }
 }
+int air_main_trace_ext(const char* who, AirMainLevel level, sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const sp_air_main_desc* mp, const void* inputs,
+                       uint64_t n, uint8_t* rows_out) {
+    if (!ext_ok(ext)) return SP_E_INVALID_ARG;
+    return air_main_trace_body(who, level, c, d, ext ? ext->periodic : nullptr, mp, inputs, n, rows_out);
+}
 }  // namespace
+int sp_air_prove_main(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const sp_air_boundary_desc* bv, const sp_air_main_desc* mp, const void* inputs,
+                      uint64_t n, const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len) {
+    return air_prove_main(AirMainLevel::Main, c, d, ext, bv, mp, inputs, n, opt, proof_out, proof_len);
+}
+int sp_air_check_trace_main(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const sp_air_boundary_desc* bv, const sp_air_main_desc* mp, const void* inputs,
+                            uint64_t n, const sp_proof_options* opt, const uint8_t* rap, sp_air_violation* out, uint32_t cap, uint32_t* n_out) {
+    return air_check_trace_main(AirMainLevel::Main, c, d, ext, bv, mp, inputs, n, opt, rap, out, cap, n_out);
+}
 int sp_air_main_trace(sp_ctx* c, const sp_air_desc* d, const sp_air_main_desc* mp, const void* inputs, uint64_t n, uint8_t* rows_out) {
-    return air_main_trace_body("sp_air_main_trace", c, d, nullptr, false, mp, inputs, n, rows_out);
+    return air_main_trace_body("sp_air_main_trace", AirMainLevel::Main, c, d, nullptr, mp, inputs, n, rows_out);
 }
 
-// The _main entry points for a main program with block recurrences (SP_AIR_MAIN_CHAIN) or reads of the periodic columns (op 6).
 int sp_air_prove_rec(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const sp_air_boundary_desc* bv, const sp_air_main_desc* mp, const void* inputs,
                      uint64_t n, const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len) {
-    if (!mp || !ext_ok(ext)) return SP_E_INVALID_ARG;
-    return air_prove_body(c, d, AirParts::of_ext(ext, bv, true, mp, true), static_cast<const uint8_t*>(inputs), n, opt, proof_out, proof_len);
+    return air_prove_main(AirMainLevel::Rec, c, d, ext, bv, mp, inputs, n, opt, proof_out, proof_len);
 }
 int sp_air_check_trace_rec(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const sp_air_boundary_desc* bv, const sp_air_main_desc* mp, const void* inputs,
                            uint64_t n, const sp_proof_options* opt, const uint8_t* rap, sp_air_violation* out, uint32_t cap, uint32_t* n_out) {
-    if (!mp || !ext_ok(ext)) return SP_E_INVALID_ARG;
-    return air_check_trace_body(c, d, AirParts::of_ext(ext, bv, true, mp, true), static_cast<const uint8_t*>(inputs), n, opt, rap, out, cap, n_out);
+    return air_check_trace_main(AirMainLevel::Rec, c, d, ext, bv, mp, inputs, n, opt, rap, out, cap, n_out);
 }
 int sp_air_main_trace_rec(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const sp_air_main_desc* mp, const void* inputs, uint64_t n, uint8_t* rows_out) {
-    if (!ext_ok(ext)) return SP_E_INVALID_ARG;
-    return air_main_trace_body("sp_air_main_trace_rec", c, d, ext ? ext->periodic : nullptr, true, mp, inputs, n, rows_out);
+    return air_main_trace_ext("sp_air_main_trace_rec", AirMainLevel::Rec, c, d, ext, mp, inputs, n, rows_out);
 }
 
-// The _rec entry points for a main program that also holds lookup multiplicities (SP_AIR_MAIN_COUNT).
 int sp_air_prove_lk(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const sp_air_boundary_desc* bv, const sp_air_main_desc* mp, const void* inputs,
                     uint64_t n, const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len) {
-    if (!mp || !ext_ok(ext)) return SP_E_INVALID_ARG;
-    return air_prove_body(c, d, AirParts::of_ext(ext, bv, true, mp, true, true), static_cast<const uint8_t*>(inputs), n, opt, proof_out, proof_len);
+    return air_prove_main(AirMainLevel::Lk, c, d, ext, bv, mp, inputs, n, opt, proof_out, proof_len);
 }
 int sp_air_check_trace_lk(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const sp_air_boundary_desc* bv, const sp_air_main_desc* mp, const void* inputs,
                           uint64_t n, const sp_proof_options* opt, const uint8_t* rap, sp_air_violation* out, uint32_t cap, uint32_t* n_out) {
-    if (!mp || !ext_ok(ext)) return SP_E_INVALID_ARG;
-    return air_check_trace_body(c, d, AirParts::of_ext(ext, bv, true, mp, true, true), static_cast<const uint8_t*>(inputs), n, opt, rap, out, cap, n_out);
+    return air_check_trace_main(AirMainLevel::Lk, c, d, ext, bv, mp, inputs, n, opt, rap, out, cap, n_out);
 }
 int sp_air_main_trace_lk(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const sp_air_main_desc* mp, const void* inputs, uint64_t n, uint8_t* rows_out) {
-    if (!ext_ok(ext)) return SP_E_INVALID_ARG;
-    return air_main_trace_body("sp_air_main_trace_lk", c, d, ext ? ext->periodic : nullptr, true, mp, inputs, n, rows_out, true);
+    return air_main_trace_ext("sp_air_main_trace_lk", AirMainLevel::Lk, c, d, ext, mp, inputs, n, rows_out);
 }
 
-// The _lk entry points for a main program whose chain groups link their blocks into runs (the k of a CHAIN column's pad).
 int sp_air_prove_link(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const sp_air_boundary_desc* bv, const sp_air_main_desc* mp, const void* inputs,
                       uint64_t n, const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len) {
-    if (!mp || !ext_ok(ext)) return SP_E_INVALID_ARG;
-    return air_prove_body(c, d, AirParts::of_ext(ext, bv, true, mp, true, true, true), static_cast<const uint8_t*>(inputs), n, opt, proof_out, proof_len);
+    return air_prove_main(AirMainLevel::Link, c, d, ext, bv, mp, inputs, n, opt, proof_out, proof_len);
 }
 int sp_air_check_trace_link(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const sp_air_boundary_desc* bv, const sp_air_main_desc* mp, const void* inputs,
                             uint64_t n, const sp_proof_options* opt, const uint8_t* rap, sp_air_violation* out, uint32_t cap, uint32_t* n_out) {
-    if (!mp || !ext_ok(ext)) return SP_E_INVALID_ARG;
-    return air_check_trace_body(c, d, AirParts::of_ext(ext, bv, true, mp, true, true, true), static_cast<const uint8_t*>(inputs), n, opt, rap, out, cap, n_out);
+    return air_check_trace_main(AirMainLevel::Link, c, d, ext, bv, mp, inputs, n, opt, rap, out, cap, n_out);
 }
 int sp_air_main_trace_link(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const sp_air_main_desc* mp, const void* inputs, uint64_t n, uint8_t* rows_out) {
-    if (!ext_ok(ext)) return SP_E_INVALID_ARG;
-    return air_main_trace_body("sp_air_main_trace_link", c, d, ext ? ext->periodic : nullptr, true, mp, inputs, n, rows_out, true, true);
+    return air_main_trace_ext("sp_air_main_trace_link", AirMainLevel::Link, c, d, ext, mp, inputs, n, rows_out);
 }
 
 }  // extern "C"

@@ -1,7 +1,6 @@
 // Round-by-round STARK prover on the device (see prover.h). Host code only: it sequences kernels on the context
 // stream, keeps every polynomial / evaluation / tree resident in HBM and moves only roots, challenges and openings.
 #include "prover_internal.h"
-#include "sort_kernels.h"
 #include <unordered_map>
 #include <cstring>
 #include <cmath>
@@ -415,495 +414,6 @@ int StarkProver::commit_aux_cairo(const PublicInputs& pub, const fe rap[3], uint
     }
     if (flag) { sp_set_error("commit_aux_cairo: a permutation denominator of the auxiliary trace is zero (the reference's batch inversion fails on this trace and these challenges too)"); return flag == 1 ? SP_E_ZERO_INVERSE : SP_E_INVALID_ARG; }
     return commit_segment_resident(1, Ca_, root_out);
-}
-
-// Chunks of columns bound the workspace: a chunk holds at most max(1, AUXP_CHUNK_ELEMS / n) columns, so its denominators take
-// at most max(2^22, n) elements (128 MB up to 2^22 rows, 32 bytes a row beyond) and the batch inversion as much scratch again,
-// whatever the number of auxiliary columns.  The numerators are written straight into the trace columns they become.
-// Sorted columns (SP_AIR_AUX_SORTED) come first, one sort group at a time in the same workspace: the carried values of a group go
-// through it at most a chunk's worth of columns per pass, beside the (key, row) pairs and the radix sort's histograms (24 bytes a row).
-// A chunk of products and sums is a run of such columns: a sorted column ends it.
-static constexpr uint64_t AUXP_CHUNK_ELEMS = 1ull << 22;
-
-int StarkProver::commit_aux_program(const AirStatement& st, const std::vector<fe>& rap, uint8_t root_out[32]) {
-    const AirAuxHost& aux = *st.aux;
-    const AirPeriodicHost* periodic = st.aux_periodic();
-    const uint32_t K = (uint32_t)aux.cols.size();
-    if (stage_ != Stage::MainCommitted || K == 0 || K != Ca_) { sp_set_error("commit_aux_program: main segment not committed or auxiliary column count differs"); return SP_E_STATE; }
-    const uint32_t Kp = periodic ? (uint32_t)periodic->cols.size() : 0u;
-    SP_HIP_CHECK(hipSetDevice(c_->device));
-    const uint32_t chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(K, AUXP_CHUNK_ELEMS / n_));
-    const uint64_t nb = air_aux_scan_blocks(n_);
-    const uint32_t n_src = (uint32_t)aux.ops.size();
-    bool any_periodic = false;
-    // the program with an OUT behind every op whose value is wanted - outs[t]: the codes op t is stored under - (a value then lives only
-    // until it is stored), slots by air_assign_slots (which drops what these OUTs do not need)
-    auto program_with_outs = [&](const std::vector<std::vector<uint32_t>>& outs, std::vector<AirOpDev>& dev, bool& reads_periodic) -> int {
-        std::vector<AirOpHost> ext;
-        std::vector<uint32_t> at(n_src);
-        for (uint32_t t = 0; t < n_src; ++t) {
-            AirOpHost o = aux.ops[t];
-            if (o.op >= 2 && o.op <= 4) { o.a = at[o.a]; o.b = at[o.b]; }   // (LOAD, CONST and PERIODIC name cells, not values)
-            at[t] = (uint32_t)ext.size();
-            ext.push_back(o);
-            for (uint32_t code : outs[t]) ext.push_back(AirOpHost{5, code, at[t]});
-        }
-        SP_TRY(air_assign_slots(ext, dev, "aux program: more than 64 values alive at once"));
-        reads_periodic = false;
-        for (const AirOpDev& o : dev) reads_periodic |= o.op == 6;   // (of what air_assign_slots kept: a table read that feeds one of these OUTs)
-        any_periodic |= reads_periodic;
-        return SP_OK;
-    };
-    // --- per sort group: its key columns (rebuilt from the sorted keys) and its carried columns in passes of at most `chunk`; the
-    //     first pass also stores the key (OUT AIR_AUX_DEN_TAG)
-    struct SortPass { bool periodic; std::vector<AirOpDev> ops; std::vector<uint32_t> col_of; size_t o_ops, o_col; };
-    struct SortGroup { uint32_t key_op, key_bits; std::vector<uint32_t> key_cols, carried; std::vector<SortPass> passes; size_t o_keycol; };
-    std::vector<SortGroup> groups;
-    for (uint32_t k = 0; k < K; ++k) {
-        const AirAuxColumnHost& c = aux.cols[k];
-        if (c.kind != SP_AIR_AUX_SORTED) continue;
-        size_t g = 0;
-        while (g < groups.size() && groups[g].key_op != c.den_op) ++g;
-        if (g == groups.size()) { groups.emplace_back(); groups[g].key_op = c.den_op; groups[g].key_bits = c.key_bits; }
-        (c.num_op == c.den_op ? groups[g].key_cols : groups[g].carried).push_back(k);
-    }
-    uint32_t max_carried = 0;
-    for (SortGroup& g : groups) {
-        for (size_t j0 = 0; j0 == 0 || j0 < g.carried.size(); j0 += chunk) {
-            SortPass ps{};
-            std::vector<std::vector<uint32_t>> outs(n_src);
-            for (size_t j = j0; j < std::min<size_t>(g.carried.size(), j0 + chunk); ++j) {
-                outs[aux.cols[g.carried[j]].num_op].push_back((uint32_t)ps.col_of.size());
-                ps.col_of.push_back(g.carried[j]);
-            }
-            if (j0 == 0) outs[g.key_op].push_back(AIR_AUX_DEN_TAG);
-            SP_TRY(program_with_outs(outs, ps.ops, ps.periodic));
-            max_carried = std::max(max_carried, (uint32_t)ps.col_of.size());
-            g.passes.push_back(std::move(ps));
-        }
-    }
-    if (!groups.empty() && n_ >= (1ull << 32)) { sp_set_error("commit_aux_program: sorted columns need a trace of fewer than 2^32 rows"); return SP_E_INVALID_ARG; }
-    // --- per chunk of products and sums: its N and D
-    struct Chunk { uint32_t k0, kc, n_den; bool periodic; std::vector<AirOpDev> ops; std::vector<uint32_t> kinds, col_of; size_t o_ops, o_kinds, o_col; };
-    std::vector<Chunk> chunks;
-    uint32_t max_den = 0;
-    for (uint32_t k0 = 0; k0 < K;) {
-        if (aux.cols[k0].kind == SP_AIR_AUX_SORTED) { ++k0; continue; }
-        Chunk ch{};
-        ch.k0 = k0;
-        std::vector<std::vector<uint32_t>> outs(n_src);
-        for (; ch.kc < chunk && k0 + ch.kc < K && aux.cols[k0 + ch.kc].kind != SP_AIR_AUX_SORTED; ++ch.kc) {
-            const AirAuxColumnHost& c = aux.cols[k0 + ch.kc];
-            ch.kinds.push_back(c.kind);
-            outs[c.num_op].push_back(ch.kc);
-            if (c.den_op != SP_AIR_AUX_NO_DEN) { outs[c.den_op].push_back(AIR_AUX_DEN_TAG + ch.n_den); ch.col_of.push_back(ch.kc); ++ch.n_den; }
-        }
-        SP_TRY(program_with_outs(outs, ch.ops, ch.periodic));
-        max_den = std::max(max_den, ch.n_den);
-        k0 += ch.kc;
-        chunks.push_back(std::move(ch));
-    }
-    // --- one upload: constants (then the RAP challenges), per sort pass its ops and value -> column table, per chunk its ops, column
-    //     kinds and denominator -> column table
-    UploadLayout lay;
-    const size_t o_consts = lay.place(sizeof(fe) * std::max<size_t>(1, aux.consts.size() + rap.size()));
-    for (SortGroup& g : groups) {
-        g.o_keycol = lay.place(sizeof(uint32_t) * std::max<size_t>(1, g.key_cols.size()));
-        for (SortPass& ps : g.passes) {
-            ps.o_ops = lay.place(sizeof(AirOpDev) * ps.ops.size());
-            ps.o_col = lay.place(sizeof(uint32_t) * std::max<size_t>(1, ps.col_of.size()));
-        }
-    }
-    for (Chunk& ch : chunks) {
-        ch.o_ops = lay.place(sizeof(AirOpDev) * ch.ops.size());
-        ch.o_kinds = lay.place(sizeof(uint32_t) * ch.kc);
-        ch.o_col = lay.place(sizeof(uint32_t) * std::max<uint32_t>(1, ch.n_den));
-    }
-    // the periodic columns a chunk reads, as round 2's block holds them: AirPeriodicCol[] and the raw values, column k at pvals + off_k
-    std::vector<AirPeriodicCol> pcols;
-    uint64_t S = 0;
-    if (any_periodic)
-        for (uint32_t k = 0; k < Kp; ++k) {
-            pcols.push_back(AirPeriodicCol{(uint32_t)sp_log2_exact(periodic->cols[k].size()), 0u, S});
-            S += periodic->cols[k].size();
-        }
-    const size_t o_pcols = any_periodic ? lay.place(sizeof(AirPeriodicCol) * Kp) : 0, o_pvals = any_periodic ? lay.place(sizeof(fe) * S) : 0;
-    const size_t bytes = lay.bytes;
-    SP_TRY(grow(od_.auxp_buf, bytes));
-    std::vector<uint8_t>& up = h_auxp_up_;
-    up.assign(bytes, 0);
-    fill_consts_then_rap(up.data() + o_consts, aux.consts, rap);
-    for (const SortGroup& g : groups) {
-        if (!g.key_cols.empty()) std::memcpy(up.data() + g.o_keycol, g.key_cols.data(), sizeof(uint32_t) * g.key_cols.size());
-        for (const SortPass& ps : g.passes) {
-            std::memcpy(up.data() + ps.o_ops, ps.ops.data(), sizeof(AirOpDev) * ps.ops.size());
-            if (!ps.col_of.empty()) std::memcpy(up.data() + ps.o_col, ps.col_of.data(), sizeof(uint32_t) * ps.col_of.size());
-        }
-    }
-    for (const Chunk& ch : chunks) {
-        std::memcpy(up.data() + ch.o_ops, ch.ops.data(), sizeof(AirOpDev) * ch.ops.size());
-        std::memcpy(up.data() + ch.o_kinds, ch.kinds.data(), sizeof(uint32_t) * ch.kc);
-        if (ch.n_den) std::memcpy(up.data() + ch.o_col, ch.col_of.data(), sizeof(uint32_t) * ch.n_den);
-    }
-    if (any_periodic) {
-        std::memcpy(up.data() + o_pcols, pcols.data(), sizeof(AirPeriodicCol) * Kp);
-        for (uint32_t k = 0; k < Kp; ++k) std::memcpy(up.data() + o_pvals + sizeof(fe) * pcols[k].off, periodic->cols[k].data(), sizeof(fe) * periodic->cols[k].size());
-    }
-    SP_HIP_CHECK(hipMemcpyAsync(od_.auxp_buf.p, up.data(), bytes, hipMemcpyHostToDevice, c_->stream));
-    // --- workspace, whichever of the two uses is larger (the sorts are over before the first chunk starts):
-    //     chunks: [max_den][n] denominators, as much batch-inversion scratch, [chunk][nb] scan block totals
-    //     sorts:  [max_carried][n] carried values, 2 x [n] keys, 2 x [n] rows, the radix sort's histograms (all in units of 32 bytes)
-    const uint64_t keys_el = (n_ + 3) / 4, idx_el = (n_ + 7) / 8;
-    const uint64_t ws_sort = groups.empty() ? 0 : (uint64_t)max_carried * n_ + 2 * keys_el + 2 * idx_el + (radix_sort_workspace_bytes(n_) + sizeof(fe) - 1) / sizeof(fe);
-    const uint64_t ws = std::max(2 * (uint64_t)max_den * n_ + (uint64_t)chunk * nb, ws_sort);
-    SP_TRY(grow(od_.auxp_ws, ws));
-    const fe* consts_dev = reinterpret_cast<const fe*>(od_.auxp_buf.p + o_consts);
-    const AirPeriodicCol* pcols_dev = any_periodic ? reinterpret_cast<const AirPeriodicCol*>(od_.auxp_buf.p + o_pcols) : nullptr;
-    const fe* pvals_dev = any_periodic ? reinterpret_cast<const fe*>(od_.auxp_buf.p + o_pvals) : nullptr;
-    fe* aux_cols = d_trace_ + (uint64_t)Cm_ * n_;
-    SP_TRY(ensure_host_flags());
-    host_flags().auxp_bad_key = 0;
-    SP_HIP_CHECK(hipMemsetAsync(c_->d_flag, 0, sizeof(int), c_->stream));
-    if (!groups.empty()) {
-        fe* vals = od_.auxp_ws.p;
-        uint64_t* keys_a = reinterpret_cast<uint64_t*>(vals + (uint64_t)max_carried * n_);
-        uint64_t* keys_b = reinterpret_cast<uint64_t*>(vals + (uint64_t)max_carried * n_ + keys_el);
-        uint32_t* idx_a = reinterpret_cast<uint32_t*>(vals + (uint64_t)max_carried * n_ + 2 * keys_el);
-        uint32_t* idx_b = reinterpret_cast<uint32_t*>(vals + (uint64_t)max_carried * n_ + 2 * keys_el + idx_el);
-        void* radix_ws = vals + (uint64_t)max_carried * n_ + 2 * keys_el + 2 * idx_el;
-        for (const SortGroup& g : groups)
-            for (size_t p = 0; p < g.passes.size(); ++p) {
-                const SortPass& ps = g.passes[p];
-                SP_TRY(air_aux_sort_terms(c_->stream, d_trace_, n_, reinterpret_cast<const AirOpDev*>(od_.auxp_buf.p + ps.o_ops), (uint32_t)ps.ops.size(), consts_dev, vals,
-                                          p == 0 ? keys_a : nullptr, p == 0 ? idx_a : nullptr, g.key_bits, c_->d_flag, ps.periodic ? pcols_dev : nullptr,
-                                          ps.periodic ? pvals_dev : nullptr));
-                if (p == 0) {   // ceil(key_bits / 8) passes; the sorted pairs end up in keys_b / idx_b
-                    SP_TRY(radix_sort_pairs_u64(c_->stream, keys_a, keys_b, idx_a, idx_b, n_, g.key_bits, radix_ws));
-                    SP_TRY(air_aux_key_columns(c_->stream, keys_b, n_, aux_cols, reinterpret_cast<const uint32_t*>(od_.auxp_buf.p + g.o_keycol), (uint32_t)g.key_cols.size()));
-                }
-                SP_TRY(air_aux_gather(c_->stream, vals, idx_b, n_, aux_cols, reinterpret_cast<const uint32_t*>(od_.auxp_buf.p + ps.o_col), (uint32_t)ps.col_of.size()));
-            }
-        // the key-range flag rides to the host from here: a zero denominator behind it overwrites the word on the device
-        SP_HIP_CHECK(hipMemcpyAsync(&host_flags().auxp_bad_key, c_->d_flag, sizeof(int), hipMemcpyDeviceToHost, c_->stream));
-    }
-    fe* den = od_.auxp_ws.p;
-    fe* scratch = den + (uint64_t)max_den * n_;
-    fe* block_tot = scratch + (uint64_t)max_den * n_;
-    for (const Chunk& ch : chunks) {
-        fe* cols = aux_cols + (uint64_t)ch.k0 * n_;
-        const uint32_t* kinds = reinterpret_cast<const uint32_t*>(od_.auxp_buf.p + ch.o_kinds);
-        SP_TRY(air_aux_terms(c_->stream, d_trace_, n_, reinterpret_cast<const AirOpDev*>(od_.auxp_buf.p + ch.o_ops), (uint32_t)ch.ops.size(), consts_dev, cols, den,
-                             ch.periodic ? pcols_dev : nullptr, ch.periodic ? pvals_dev : nullptr));
-        if (ch.n_den) {
-            SP_TRY(batch_inverse(c_->stream, den, scratch, (uint64_t)ch.n_den * n_, c_->d_flag));
-            SP_TRY(air_aux_apply_den(c_->stream, cols, den, reinterpret_cast<const uint32_t*>(od_.auxp_buf.p + ch.o_col), ch.n_den, n_));
-        }
-        SP_TRY(air_aux_scan(c_->stream, cols, n_, ch.kc, kinds, block_tot));
-    }
-    // the zero-denominator flag rides behind the columns; the read-back of the root below waits for it (and for the key-range flag)
-    SP_HIP_CHECK(hipMemcpyAsync(&host_flags().auxp_zero_den, c_->d_flag, sizeof(int), hipMemcpyDeviceToHost, c_->stream));
-    SP_TRY(commit_segment_resident(1, K, root_out));
-    if (host_flags().auxp_bad_key == AIR_AUX_FLAG_KEY_RANGE) {
-        sp_set_error("commit_aux_program: a sort key is out of range on some row (the key of a sorted column must be below 2^key_bits as a canonical integer)");
-        return SP_E_INVALID_ARG;
-    }
-    if (host_flags().auxp_zero_den) { sp_set_error("commit_aux_program: an auxiliary column's denominator is zero on some row"); return SP_E_ZERO_INVERSE; }
-    return SP_OK;
-}
-
-// The main-trace program.  Chunks as above (at most max(1, AUXP_CHUNK_ELEMS / n) columns), and a chunk also ends before a column
-// that reads a derived column of the chunk itself: LOADs wrap around the trace, so a column must be complete - its scan included -
-// before anything reads it, and the stream orders one chunk behind the other.  Workspace slots of a chunk, n elements each: first
-// the ones the batch inversion takes (the D of VALUE / SUM / PRODUCT columns, the guarded N of INV_OR_ZERO columns), then one per
-// group of BIT columns that share their N.  od_.auxp_buf / od_.auxp_ws: the auxiliary program runs later on the same stream.
-// A chain group (SP_AIR_MAIN_CHAIN, st.main_rec) is a chunk of its own and ends the chunk before it: two programs, the seeds' and the
-// steps', each with an OUT per group column, and one launch of air_main_chain; nothing of the group is read before that launch is
-// over, which the stream's order guarantees.  It takes no workspace.  The periodic columns an op 6 reads (st.periodic) ride in this
-// upload block as they do in the auxiliary program's: round 2's block comes too late.  A linked group (st.main_link, k >= 1 in its
-// columns' pad) is the same chunk with the same two programs and one launch of air_main_chain_linked, a lane per run of 2^k blocks.
-// A COUNT column (SP_AIR_MAIN_COUNT, st.main_lk) is a chunk of its own too: two programs, X's and T's, each with the one OUT of a key
-// pass; two launches of air_aux_sort_terms (keys out of Montgomery form, the row beside each), two radix sorts - the table's carries
-// its rows - and one launch of air_main_count, which writes every cell of the column.  Its arrays (4 x [n] keys, 4 x [n] rows, the
-// radix histograms) lie at the start of the same workspace: the chunk before it is over, the chunk behind it starts after the count.
-// The key-range flag is a word of its own at the end of the workspace, so that no batch inversion before or behind overwrites it.
-int StarkProver::build_main_program(const AirStatement& st, const uint8_t* inputs) {
-    const AirMainHost& mp = *st.main;
-    const uint32_t I = mp.input_cols, K = (uint32_t)mp.cols.size();
-    if (!inputs) return SP_E_INVALID_ARG;
-    if (stage_ != Stage::Setup || I + K != Cm_) { sp_set_error("commit_main_program: wrong segment order, or input and derived columns are not the main segment"); return SP_E_STATE; }
-    SP_HIP_CHECK(hipSetDevice(c_->device));
-    binary_cols_hint_ = 0;
-    for (double& x : c_->upload_stats) x = 0.0;
-    leaf_head_done_ = false;
-    const uint32_t chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(K, AUXP_CHUNK_ELEMS / n_));
-    const uint64_t nb = air_aux_scan_blocks(n_);
-    const uint32_t n_src = (uint32_t)mp.ops.size();
-    struct Chunk {
-        uint32_t k0 = 0, kc = 0, n_inv = 0, n_slots = 0;            // n_inv: slots the batch inversion takes; n_slots: those and the BIT groups'
-        std::vector<AirOpDev> ops;
-        std::vector<uint32_t> kinds, den_col, guard, gtab, etab;     // kinds: 0 product / 1 sum per column (read for scanned columns only)
-        std::vector<std::pair<uint32_t, uint32_t>> scans;            // runs of SUM / PRODUCT columns: (first, count)
-        size_t o_ops = 0, o_kinds = 0, o_den = 0, o_guard = 0, o_gtab = 0, o_etab = 0;
-        bool periodic = false;                                       // the program (of a chain group: either program) reads a periodic column
-        uint32_t chain_log = 0;                                      // a chain group (kc columns, blocks of 2^chain_log rows): ops is the step program,
-        std::vector<AirOpDev> seed_ops;                              //   seed_ops the seeds'
-        size_t o_seed = 0;
-        uint32_t link_log = 0;                                       // a linked chain group: runs of 2^link_log blocks, one lane per run (st.main_link)
-        uint32_t count_bits = 0;                                     // a COUNT column (kc = 1) with this key_bits: ops is X's program, seed_ops T's
-    };
-    std::vector<Chunk> chunks;
-    uint32_t max_slots = 0, max_inv = 0;
-    bool any_count = false;
-    bool any_periodic = false;
-    // the program with an OUT behind every op whose value is wanted, slots by air_assign_slots (as commit_aux_program)
-    auto program_with_outs = [&](const std::vector<std::vector<uint32_t>>& outs, std::vector<AirOpDev>& dev, bool& reads_periodic) -> int {
-        std::vector<AirOpHost> ext;
-        std::vector<uint32_t> at(n_src);
-        for (uint32_t t = 0; t < n_src; ++t) {
-            AirOpHost o = mp.ops[t];
-            if (o.op >= 2 && o.op <= 4) { o.a = at[o.a]; o.b = at[o.b]; }
-            at[t] = (uint32_t)ext.size();
-            ext.push_back(o);
-            for (uint32_t code : outs[t]) ext.push_back(AirOpHost{5, code, at[t]});
-        }
-        SP_TRY(air_assign_slots(ext, dev, "main program: more than 64 values alive at once"));
-        for (const AirOpDev& o : dev) reads_periodic |= o.op == 6;   // (of what air_assign_slots kept)
-        any_periodic |= reads_periodic;
-        return SP_OK;
-    };
-    for (uint32_t k0 = 0; k0 < K;) {
-        Chunk ch;
-        ch.k0 = k0;
-        std::vector<std::vector<uint32_t>> outs(n_src);
-        if (mp.cols[k0].kind == SP_AIR_MAIN_CHAIN) {   // the whole group (the decoder saw to j = 0, 1, .. and one l)
-            std::vector<std::vector<uint32_t>> seeds(n_src);
-            ch.chain_log = mp.cols[k0].chain_log;
-            ch.link_log = mp.cols[k0].chain_link;
-            do {
-                const AirMainColumnHost& c = mp.cols[k0 + ch.kc];
-                seeds[c.den_op].push_back(ch.kc);
-                outs[c.num_op].push_back(ch.kc);
-                ++ch.kc;
-            } while (k0 + ch.kc < K && mp.cols[k0 + ch.kc].kind == SP_AIR_MAIN_CHAIN && mp.cols[k0 + ch.kc].chain_pos != 0);
-            if (ch.kc > AIR_MAIN_CHAIN_WIDTH || ch.chain_log + ch.link_log >= 64 || n_ >> (ch.chain_log + ch.link_log) == 0) { sp_set_error("commit_main_program: a chain group the decoder should have refused"); return SP_E_INVALID_ARG; }
-            SP_TRY(program_with_outs(seeds, ch.seed_ops, ch.periodic));
-            SP_TRY(program_with_outs(outs, ch.ops, ch.periodic));
-            k0 += ch.kc;
-            chunks.push_back(std::move(ch));
-            continue;
-        }
-        if (mp.cols[k0].kind == SP_AIR_MAIN_COUNT) {
-            const AirMainColumnHost& c = mp.cols[k0];
-            std::vector<std::vector<uint32_t>> table(n_src);
-            if (c.key_bits == 0 || c.key_bits > 64 || c.den_op >= n_src) { sp_set_error("commit_main_program: a COUNT column the decoder should have refused"); return SP_E_INVALID_ARG; }
-            outs[c.num_op].push_back(AIR_AUX_DEN_TAG);
-            table[c.den_op].push_back(AIR_AUX_DEN_TAG);
-            ch.kc = 1;
-            ch.count_bits = c.key_bits;
-            SP_TRY(program_with_outs(outs, ch.ops, ch.periodic));
-            SP_TRY(program_with_outs(table, ch.seed_ops, ch.periodic));
-            any_count = true;
-            k0 += 1;
-            chunks.push_back(std::move(ch));
-            continue;
-        }
-        struct BitGroup { uint32_t num_op; std::vector<uint32_t> entries; };
-        std::vector<BitGroup> groups;
-        for (; ch.kc < chunk && k0 + ch.kc < K && mp.cols[k0 + ch.kc].reads <= k0 && mp.cols[k0 + ch.kc].kind != SP_AIR_MAIN_CHAIN &&
-               mp.cols[k0 + ch.kc].kind != SP_AIR_MAIN_COUNT; ++ch.kc) {
-            const AirMainColumnHost& c = mp.cols[k0 + ch.kc];
-            const bool scanned = c.kind == SP_AIR_MAIN_SUM || c.kind == SP_AIR_MAIN_PRODUCT;
-            ch.kinds.push_back(c.kind == SP_AIR_MAIN_SUM ? 1u : 0u);
-            if (scanned) {
-                if (!ch.scans.empty() && ch.scans.back().first + ch.scans.back().second == ch.kc) ++ch.scans.back().second;
-                else ch.scans.emplace_back(ch.kc, 1u);
-            }
-            if (c.kind == SP_AIR_MAIN_BIT) {
-                size_t g = 0;
-                while (g < groups.size() && groups[g].num_op != c.num_op) ++g;
-                if (g == groups.size()) groups.push_back(BitGroup{c.num_op, {}});
-                groups[g].entries.push_back(ch.kc);
-                groups[g].entries.push_back(c.bit);
-                continue;
-            }
-            if (c.kind == SP_AIR_MAIN_INV_OR_ZERO) {
-                outs[c.num_op].push_back(AIR_AUX_DEN_TAG + ch.n_inv);
-                ch.guard.push_back(ch.n_inv); ch.guard.push_back(ch.kc);
-                ch.den_col.push_back(ch.kc);
-                ++ch.n_inv;
-                continue;
-            }
-            outs[c.num_op].push_back(ch.kc);
-            if (c.den_op != SP_AIR_AUX_NO_DEN) { outs[c.den_op].push_back(AIR_AUX_DEN_TAG + ch.n_inv); ch.den_col.push_back(ch.kc); ++ch.n_inv; }
-        }
-        ch.n_slots = ch.n_inv;
-        for (const BitGroup& g : groups) {
-            outs[g.num_op].push_back(AIR_AUX_DEN_TAG + ch.n_slots);
-            ch.gtab.push_back(ch.n_slots++); ch.gtab.push_back((uint32_t)ch.etab.size() / 2); ch.gtab.push_back((uint32_t)g.entries.size() / 2);
-            ch.etab.insert(ch.etab.end(), g.entries.begin(), g.entries.end());
-        }
-        SP_TRY(program_with_outs(outs, ch.ops, ch.periodic));
-        max_slots = std::max(max_slots, ch.n_slots);
-        max_inv = std::max(max_inv, ch.n_inv);
-        k0 += ch.kc;
-        chunks.push_back(std::move(ch));
-    }
-    // --- one upload: the constants, per chunk its ops and tables
-    UploadLayout lay;
-    auto words = [&](const std::vector<uint32_t>& v) { return lay.place(sizeof(uint32_t) * std::max<size_t>(1, v.size())); };
-    const size_t o_consts = lay.place(sizeof(fe) * std::max<size_t>(1, mp.consts.size()));
-    for (Chunk& ch : chunks) {
-        ch.o_ops = lay.place(sizeof(AirOpDev) * std::max<size_t>(1, ch.ops.size()));
-        ch.o_seed = lay.place(sizeof(AirOpDev) * std::max<size_t>(1, ch.seed_ops.size()));
-        ch.o_kinds = words(ch.kinds); ch.o_den = words(ch.den_col); ch.o_guard = words(ch.guard); ch.o_gtab = words(ch.gtab); ch.o_etab = words(ch.etab);
-    }
-    // the periodic columns, as commit_aux_program lays them out: AirPeriodicCol[] and the raw values, column k at pvals + off_k
-    const AirPeriodicHost* periodic = st.main_rec && st.periodic ? &*st.periodic : nullptr;
-    if (any_periodic && !periodic) { sp_set_error("commit_main_program: op 6 without periodic columns (the decoder should have refused it)"); return SP_E_INVALID_ARG; }
-    const uint32_t Kp = any_periodic ? (uint32_t)periodic->cols.size() : 0u;
-    std::vector<AirPeriodicCol> pcols;
-    uint64_t S = 0;
-    for (uint32_t k = 0; k < Kp; ++k) {
-        pcols.push_back(AirPeriodicCol{(uint32_t)sp_log2_exact(periodic->cols[k].size()), 0u, S});
-        S += periodic->cols[k].size();
-    }
-    const size_t o_pcols = any_periodic ? lay.place(sizeof(AirPeriodicCol) * Kp) : 0, o_pvals = any_periodic ? lay.place(sizeof(fe) * S) : 0;
-    const size_t bytes = lay.bytes;
-    SP_TRY(grow(od_.auxp_buf, bytes));
-    std::vector<uint8_t>& up = h_auxp_up_;
-    up.assign(bytes, 0);
-    fill_consts_then_rap(up.data() + o_consts, mp.consts, {});
-    auto put = [&](size_t at, const std::vector<uint32_t>& v) { if (!v.empty()) std::memcpy(up.data() + at, v.data(), sizeof(uint32_t) * v.size()); };
-    for (const Chunk& ch : chunks) {
-        if (!ch.ops.empty()) std::memcpy(up.data() + ch.o_ops, ch.ops.data(), sizeof(AirOpDev) * ch.ops.size());
-        if (!ch.seed_ops.empty()) std::memcpy(up.data() + ch.o_seed, ch.seed_ops.data(), sizeof(AirOpDev) * ch.seed_ops.size());
-        put(ch.o_kinds, ch.kinds); put(ch.o_den, ch.den_col); put(ch.o_guard, ch.guard); put(ch.o_gtab, ch.gtab); put(ch.o_etab, ch.etab);
-    }
-    if (any_periodic) {
-        std::memcpy(up.data() + o_pcols, pcols.data(), sizeof(AirPeriodicCol) * Kp);
-        for (uint32_t k = 0; k < Kp; ++k) std::memcpy(up.data() + o_pvals + sizeof(fe) * pcols[k].off, periodic->cols[k].data(), sizeof(fe) * periodic->cols[k].size());
-    }
-    // --- workspace, the larger of what a row-local chunk and what a COUNT column takes, and behind it the word of the key-range flag:
-    //     chunks: [max_slots][n] slots, [max_inv][n] batch-inversion scratch, [chunk][nb] scan block totals
-    //     counts: 4 x [n] keys, 4 x [n] rows, the radix sort's histograms (all in units of 32 bytes)
-    if (any_count && n_ >= (1ull << 32)) { sp_set_error("commit_main_program: COUNT columns need a trace of fewer than 2^32 rows"); return SP_E_INVALID_ARG; }
-    const uint64_t keys_el = (n_ + 3) / 4, idx_el = (n_ + 7) / 8;
-    const uint64_t ws_count = any_count ? 4 * keys_el + 4 * idx_el + (radix_sort_workspace_bytes(n_) + sizeof(fe) - 1) / sizeof(fe) : 0;
-    const uint64_t ws_elems = std::max(((uint64_t)max_slots + max_inv) * n_ + (uint64_t)chunk * nb, ws_count);
-    SP_TRY(grow(od_.auxp_ws, ws_elems + 1));
-    SP_TRY(ensure_host_flags());
-    host_flags().auxp_bad_key = 0;
-    // --- ingest: the plain staged copy (the inputs are a small part of the table; their raw rows sit in the segment's LDE area,
-    //     which is written only by the transforms behind the last chunk), then rows -> columns [0, I)
-    if (mp.input_location == 1) {
-        SP_TRY(rows_to_columns(c_->stream, c_->enc, inputs, n_, I, d_trace_, n_));
-    } else {
-        uint8_t* raw = reinterpret_cast<uint8_t*>(d_lde_);
-        SP_HIP_CHECK(hipMemcpyAsync(raw, inputs, (size_t)n_ * I * 32, hipMemcpyHostToDevice, c_->stream));
-        SP_TRY(rows_to_columns(c_->stream, c_->enc, raw, n_, I, d_trace_, n_));
-    }
-    SP_HIP_CHECK(hipMemcpyAsync(od_.auxp_buf.p, up.data(), bytes, hipMemcpyHostToDevice, c_->stream));
-    SP_HIP_CHECK(hipMemsetAsync(c_->d_flag, 0, sizeof(int), c_->stream));
-    const fe* consts_dev = reinterpret_cast<const fe*>(od_.auxp_buf.p + o_consts);
-    fe* ws = od_.auxp_ws.p;
-    int* key_flag = reinterpret_cast<int*>(ws + ws_elems);
-    if (any_count) SP_HIP_CHECK(hipMemsetAsync(key_flag, 0, sizeof(int), c_->stream));
-    uint64_t* kx_a = reinterpret_cast<uint64_t*>(ws);
-    uint64_t* kx_b = reinterpret_cast<uint64_t*>(ws + keys_el);
-    uint64_t* kt_a = reinterpret_cast<uint64_t*>(ws + 2 * keys_el);
-    uint64_t* kt_b = reinterpret_cast<uint64_t*>(ws + 3 * keys_el);
-    uint32_t* ix_a = reinterpret_cast<uint32_t*>(ws + 4 * keys_el);
-    uint32_t* ix_b = reinterpret_cast<uint32_t*>(ws + 4 * keys_el + idx_el);
-    uint32_t* it_a = reinterpret_cast<uint32_t*>(ws + 4 * keys_el + 2 * idx_el);
-    uint32_t* it_b = reinterpret_cast<uint32_t*>(ws + 4 * keys_el + 3 * idx_el);
-    void* radix_ws = ws + 4 * keys_el + 4 * idx_el;
-    fe* scratch = ws + (uint64_t)max_slots * n_;
-    fe* block_tot = scratch + (uint64_t)max_inv * n_;
-    auto tab = [&](size_t at) { return reinterpret_cast<const uint32_t*>(od_.auxp_buf.p + at); };
-    const AirPeriodicCol* pcols_dev = any_periodic ? reinterpret_cast<const AirPeriodicCol*>(od_.auxp_buf.p + o_pcols) : nullptr;
-    const fe* pvals_dev = any_periodic ? reinterpret_cast<const fe*>(od_.auxp_buf.p + o_pvals) : nullptr;
-    for (const Chunk& ch : chunks) {
-        fe* cols = d_trace_ + (uint64_t)(I + ch.k0) * n_;
-        const AirOpDev* ops_dev = reinterpret_cast<const AirOpDev*>(od_.auxp_buf.p + ch.o_ops);
-        if (ch.chain_log && ch.link_log) {   // the same two programs; a seed's LOAD of its group is the carry
-            SP_TRY(air_main_chain_linked(c_->stream, d_trace_, n_, ch.chain_log, ch.link_log, I + ch.k0, ch.kc, reinterpret_cast<const AirOpDev*>(od_.auxp_buf.p + ch.o_seed),
-                                         (uint32_t)ch.seed_ops.size(), ops_dev, (uint32_t)ch.ops.size(), consts_dev, ch.periodic ? pcols_dev : nullptr,
-                                         ch.periodic ? pvals_dev : nullptr));
-            continue;
-        }
-        if (ch.chain_log) {
-            SP_TRY(air_main_chain(c_->stream, d_trace_, n_, ch.chain_log, I + ch.k0, ch.kc, reinterpret_cast<const AirOpDev*>(od_.auxp_buf.p + ch.o_seed),
-                                  (uint32_t)ch.seed_ops.size(), ops_dev, (uint32_t)ch.ops.size(), consts_dev, ch.periodic ? pcols_dev : nullptr,
-                                  ch.periodic ? pvals_dev : nullptr));
-            continue;
-        }
-        if (ch.count_bits) {   // key passes, sorts (the sorted pairs end up in kx_b / ix_b and kt_b / it_b), the join
-            const AirPeriodicCol* pc = ch.periodic ? pcols_dev : nullptr;
-            const fe* pv = ch.periodic ? pvals_dev : nullptr;
-            SP_TRY(air_aux_sort_terms(c_->stream, d_trace_, n_, ops_dev, (uint32_t)ch.ops.size(), consts_dev, nullptr, kx_a, ix_a, ch.count_bits, key_flag, pc, pv));
-            SP_TRY(air_aux_sort_terms(c_->stream, d_trace_, n_, reinterpret_cast<const AirOpDev*>(od_.auxp_buf.p + ch.o_seed), (uint32_t)ch.seed_ops.size(), consts_dev,
-                                      nullptr, kt_a, it_a, ch.count_bits, key_flag, pc, pv));
-            SP_TRY(radix_sort_pairs_u64(c_->stream, kx_a, kx_b, ix_a, ix_b, n_, ch.count_bits, radix_ws));
-            SP_TRY(radix_sort_pairs_u64(c_->stream, kt_a, kt_b, it_a, it_b, n_, ch.count_bits, radix_ws));
-            SP_TRY(air_main_count(c_->stream, kx_b, kt_b, it_b, n_, cols));
-            continue;
-        }
-        SP_TRY(air_main_terms(c_->stream, d_trace_, n_, ops_dev, (uint32_t)ch.ops.size(), consts_dev, cols, ws, ch.periodic ? pcols_dev : nullptr,
-                              ch.periodic ? pvals_dev : nullptr));
-        SP_TRY(air_main_zero_guard(c_->stream, ws, cols, tab(ch.o_guard), (uint32_t)ch.guard.size() / 2, n_));
-        if (ch.n_inv) {
-            SP_TRY(batch_inverse(c_->stream, ws, scratch, (uint64_t)ch.n_inv * n_, c_->d_flag));
-            SP_TRY(air_aux_apply_den(c_->stream, cols, ws, tab(ch.o_den), ch.n_inv, n_));
-        }
-        SP_TRY(air_main_bits(c_->stream, ws, cols, tab(ch.o_gtab), tab(ch.o_etab), (uint32_t)ch.gtab.size() / 3, n_));
-        for (const auto& run : ch.scans)
-            SP_TRY(air_aux_scan(c_->stream, cols + (uint64_t)run.first * n_, n_, run.second, tab(ch.o_kinds) + run.first, block_tot));
-    }
-    // the zero-denominator flag rides behind the columns; whoever reads the root (or the table) back waits for it
-    SP_HIP_CHECK(hipMemcpyAsync(&host_flags().auxp_zero_den, c_->d_flag, sizeof(int), hipMemcpyDeviceToHost, c_->stream));
-    if (any_count) SP_HIP_CHECK(hipMemcpyAsync(&host_flags().auxp_bad_key, key_flag, sizeof(int), hipMemcpyDeviceToHost, c_->stream));
-    return SP_OK;
-}
-
-static const char* const MAIN_PROGRAM_ZERO_DEN = "commit_main_program: a derived main column's denominator is zero on some row";
-static const char* const MAIN_PROGRAM_KEY_RANGE =
-    "commit_main_program: a lookup key is out of range on some row (X and T of a COUNT column must be below 2^key_bits as canonical integers)";
-
-int StarkProver::commit_main_program(const AirStatement& st, const uint8_t* inputs, uint8_t root_out[32]) {
-    if (!root_out) return SP_E_INVALID_ARG;
-    const double t0 = wall_ms();
-    int rc = build_main_program(st, inputs);
-    const double host_ms = wall_ms() - t0;
-    if (rc == SP_OK) rc = launch_aux_presort();
-    if (rc == SP_OK) rc = commit_segment_resident(0, Cm_, root_out);
-    if (rc != SP_OK) {   // (nothing returns while a copy from the caller's inputs may still be in flight)
-        (void)hipStreamSynchronize(c_->stream);
-        (void)hipGetLastError();
-        return rc;
-    }
-    if (host_flags().auxp_bad_key == AIR_AUX_FLAG_KEY_RANGE) { sp_set_error(MAIN_PROGRAM_KEY_RANGE); return SP_E_INVALID_ARG; }   // (first, as commit_aux_program)
-    if (host_flags().auxp_zero_den) { sp_set_error(MAIN_PROGRAM_ZERO_DEN); return SP_E_ZERO_INVERSE; }
-    return finish_upload_stats(0, st.main->input_location == 1 ? 0 : (uint64_t)n_ * st.main->input_cols * 32, 0.0, host_ms, 0);
-}
-
-int StarkProver::main_program_table(const AirStatement& st, const uint8_t* inputs, uint8_t* rows_out) {
-    if (!rows_out) return SP_E_INVALID_ARG;
-    int rc = build_main_program(st, inputs);
-    // the columns in the context encoding, through the (unused) LDE area, then transposed on the host
-    uint8_t* enc_dev = reinterpret_cast<uint8_t*>(d_lde_);
-    std::vector<uint8_t> by_col;
-    if (rc == SP_OK) rc = encode_elements(c_->stream, c_->enc, d_trace_, (uint64_t)Cm_ * n_, enc_dev);
-    if (rc == SP_OK) { by_col.resize((size_t)Cm_ * n_ * 32); rc = readback(by_col.data(), enc_dev, by_col.size()); }
-    if (rc != SP_OK) {
-        (void)hipStreamSynchronize(c_->stream);
-        (void)hipGetLastError();
-        return rc;
-    }
-    if (host_flags().auxp_bad_key == AIR_AUX_FLAG_KEY_RANGE) { sp_set_error(MAIN_PROGRAM_KEY_RANGE); return SP_E_INVALID_ARG; }   // (first, as commit_aux_program)
-    if (host_flags().auxp_zero_den) { sp_set_error(MAIN_PROGRAM_ZERO_DEN); return SP_E_ZERO_INVERSE; }
-    for (uint32_t c = 0; c < Cm_; ++c)
-        for (uint64_t i = 0; i < n_; ++i) std::memcpy(rows_out + ((size_t)i * Cm_ + c) * 32, by_col.data() + ((size_t)c * n_ + i) * 32, 32);
-    return SP_OK;
 }
 
 // sum_q A[q] y^rev(q) for `vectors` arrays of 2^k elements and `points` points, by repeated folding

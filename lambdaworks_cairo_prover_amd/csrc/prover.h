@@ -101,6 +101,7 @@ class StarkProver : public sp_deletable {
                      int col_enc = -1, uint64_t col_stride = 0);
     // round 1, Cairo auxiliary segment built on the device from the resident main trace (reference cairo/air.rs:660-729)
     int commit_aux_cairo(const PublicInputs& pub, const fe rap[3], uint8_t root_out[32]);
+    // (the column builders of a program AIR, commit_aux_program to main_program_table, are in prover_programs.cpp)
     // round 1, auxiliary segment of a program AIR built on the device from the statement's auxiliary program (st.aux, present and
     // validated: air_statement_from_c) and the RAP challenges: the sorted columns first (key pass, radix sort, gather; a key beyond its
     // bits is SP_E_INVALID_ARG), then per-row N and D, one batch inversion, an exclusive product / sum scan per column,
@@ -113,10 +114,9 @@ class StarkProver : public sp_deletable {
     // the workspace does or before a column that reads one of the chunk's own (a shifted read needs the whole column): per chunk one
     // pass of the interpreter, one batch inversion (behind the zero guard of the INV_OR_ZERO columns), the bits, the scans; then
     // commit_segment_resident.  A zero denominator is SP_E_ZERO_INVERSE once the root is back.  Every rank builds every column.
-    // With st.main_rec a chain group (SP_AIR_MAIN_CHAIN) is a chunk of its own, built by one launch of air_main_chain, and op 6 reads
-    // st.periodic, whose raw values go up with the program.
-    // With st.main_link a chain group whose columns carry k >= 1 is built by one launch of air_main_chain_linked, a lane per run.
-    // With st.main_lk a COUNT column (SP_AIR_MAIN_COUNT) is a chunk of its own as well: two key passes, two radix sorts and
+    // From st.main_level Rec on a chain group (SP_AIR_MAIN_CHAIN) is a chunk of its own, built by one launch of air_main_chain, and op 6
+    // reads st.periodic, whose raw values go up with the program; at Link a group whose columns carry k >= 1 is that launch with a lane
+    // per run.  From Lk on a COUNT column (SP_AIR_MAIN_COUNT) is a chunk of its own as well: two key passes, two radix sorts and
     // air_main_count; a key out of range is SP_E_INVALID_ARG once the root is back, ahead of a zero denominator.
     int commit_main_program(const AirStatement& st, const uint8_t* inputs, uint8_t root_out[32]);
     // the same table without the commitment, to host memory: row-major n x main_cols, context encoding (sp_air_main_trace)
@@ -219,7 +219,7 @@ class StarkProver : public sp_deletable {
     }
     int commit_segment_resident(int segment, uint32_t cols, uint8_t root_out[32]);
     // the ingest and the derived columns of commit_main_program, queued on the compute stream; the zero-denominator flag is on its way
-    // to host_flags().auxp_zero_den behind them
+    // to host_flags().auxp_zero_den behind them (prover_programs.cpp: a plan made without a HIP call, then the launches)
     int build_main_program(const AirStatement& st, const uint8_t* inputs);
     int commit_trace_pipelined(int segment, const uint8_t* rows_host, uint32_t table_cols, uint8_t root_out[32], uint32_t c_begin = 0, uint32_t c_count = 0,
                                bool window_only = false, uint32_t binary_cols = 0);

@@ -1,5 +1,5 @@
-// Helpers shared by the translation units of the prover (prover.cpp, prover_round2.cpp, prover_setup.cpp, prover_upload.cpp,
-// prover_driver.cpp) and its C entry points.
+// Helpers shared by the translation units of the prover (prover.cpp, prover_programs.cpp, prover_round2.cpp, prover_setup.cpp,
+// prover_upload.cpp, prover_driver.cpp) and its C entry points.
 #pragma once
 #include "prover.h"
 #include <chrono>

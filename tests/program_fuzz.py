@@ -1,6 +1,6 @@
 """Seeded generators of valid main and auxiliary programs (air.MainProgram, air.AuxProgram), built through the public builder API only,
 with inputs under which the plain reference (program_ref) meets no error, and - computed from the program alone - the set of features a
-program contains: the combinations of the host scheduler's paths (csrc/prover.cpp: build_main_program, commit_aux_program) that no
+program contains: the combinations of the host scheduler's paths (csrc/prover_programs.cpp: build_main_program, commit_aux_program) that no
 hand-written AIR holds.
 
     random_main(seed, n) -> (AirBuilder with main_inputs=I, input rows, features)

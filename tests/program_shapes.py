@@ -1,5 +1,5 @@
 """The deterministic shape cases of test_gpu_air_program_fuzz.py: the smallest programs that reach the seams of the host scheduler
-(csrc/prover.cpp: commit_aux_program, build_main_program) which no size of the fuzzed programs reaches.  Builders and inputs only; what
+(csrc/prover_programs.cpp: commit_aux_program, build_main_program) which no size of the fuzzed programs reaches.  Builders and inputs only; what
 each is held against stands in the test.  test_air_program_fuzz.py checks on the CPU that each shape cuts the way it is meant to."""
 import numpy as np
 

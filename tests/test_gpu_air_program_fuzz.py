@@ -1,5 +1,5 @@
 """Randomized main and auxiliary programs on the device against the plain reference of program_ref.py, and the deterministic shape cases
-of program_shapes.py, which reach the seams of the host scheduler (csrc/prover.cpp: build_main_program, commit_aux_program) that no
+of program_shapes.py, which reach the seams of the host scheduler (csrc/prover_programs.cpp: build_main_program, commit_aux_program) that no
 fuzzed size does.  Every comparison is exact; a refusal of a generated program (SP_E_UNSUPPORTED, anything) is a failure.
 
 Main programs: sp_air_main_trace* equals the reference cell for cell.  Auxiliary programs: the reference's columns under fixed

@@ -6,7 +6,7 @@ median wall time of a proof, sp_last_round_ms of the last one (rounds 1 - 4, dev
 (its bytes uploaded); and the estimate the linked kernel's own time is to be held against, as tools/air_chain_bench.py has it for the
 chain kernel: products per step x steps of a run x the time of one product of a wave that has its SIMD to itself
 (profiles/r06_mul3_v2_ubench.txt: 211.34 G products/s over 1024 SIMDs of 64 lanes).  The kernel's own time is the
-air_main_chain_linked_kernel row of a kernel trace of this script, in a run of its own:
+air_main_chain_kernel<PER, true> row of a kernel trace of this script, in a run of its own:
 
     python tools/air_link_bench.py [--log-n 18] [--block 64] [--link 8] [--alternations 5]
     rocprofv3 --kernel-trace --stats -d OUT -o p -- python tools/air_link_bench.py --alternations 1

@@ -2,11 +2,12 @@
 (eight and two passes of the radix sort), next to air.table_lookup (one LogUp sum, no sort) and air.fibonacci_2_columns (two main
 columns, no auxiliary segment at all) at the same size.  All four have two main columns, so round 1 differs by the auxiliary segment
 alone: its columns (3, 3, 1, 0), their transform and commitment, and what builds them.  One warm-up proof each, then --reps timed
-proofs; prints one JSON line: per shape the median wall time and the median of sp_last_round_ms[1] (round 1, device time).
+proofs; prints one JSON line: per shape the median wall time, the median of sp_last_round_ms[1] (round 1, device time) and the proof's sha256.
 
     python tools/air_sorted_bench.py [--reps 7] [--log-n 18]
 """
 import argparse
+import hashlib
 import json
 import os
 import random
@@ -69,7 +70,7 @@ def main():
                 wall.append((time.perf_counter() - t0) * 1e3)
                 round1.append(ctx.last_round_ms()[1])
             out[name] = {"aux_cols": b.aux_cols, "wall_median_ms": round(statistics.median(wall), 2), "round1_median_ms": round(statistics.median(round1), 3),
-                         "round1_min_ms": round(min(round1), 3), "round1_max_ms": round(max(round1), 3)}
+                         "round1_min_ms": round(min(round1), 3), "round1_max_ms": round(max(round1), 3), "proof_sha256": hashlib.sha256(proof).hexdigest()}
     print(json.dumps(out))
 
 

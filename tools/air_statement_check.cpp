@@ -87,11 +87,13 @@ void run(const char* label, const char* use, bool want_ok, const std::function<v
     if (std::strchr(use, 'r') || std::strchr(use, 'R') || std::strchr(use, 'l') || std::strchr(use, 'L') || std::strchr(use, 'k')) p.with_chain();
     patch(p);
     auto has = [&](char c) { return std::strchr(use, c) != nullptr; };
+    using sp::AirMainLevel;   // the highest level a use-letter implies wins
+    const AirMainLevel level = has('k') ? AirMainLevel::Link : has('l') ? AirMainLevel::Lk : has('r') || has('L') ? AirMainLevel::Rec : AirMainLevel::Main;
     sp::AirStatement st;
     const std::string refused = sp::air_statement_from_c(&p.d, has('x') ? &p.aux : nullptr, has('p') ? &p.per : nullptr, has('s') ? &p.sd : nullptr,
                                                          has('b') ? &p.bv : nullptr, has('P'), 16, st,
                                                          has('m') ? &p.mp : has('r') || has('R') || has('k') ? &p.rp : has('l') || has('L') ? &p.lp : nullptr,
-                                                         has('r') || has('L'), has('l'), has('k'));
+                                                         level);
     const bool ok = refused.empty();
     if (ok != want_ok) { ++failures; std::printf("FAIL %-44s wanted %s, got %s\n", label, want_ok ? "accepted" : "refused", ok ? "accepted" : refused.c_str()); return; }
     std::printf("ok   %-44s %s\n", label, ok ? "accepted" : refused.substr(0, 60).c_str());
@@ -99,8 +101,8 @@ void run(const char* label, const char* use, bool want_ok, const std::function<v
     // the model on what was accepted: stride plan and zerofier, periodic columns as polynomials, boundary values under a challenge
     sp::AirStridePlan plan;
     bool fine = sp::air_stride_plan(st.air, 16, plan) && st.aux.has_value() == has('x') && st.periodic.has_value() == has('p') && st.bvals.has_value() == has('b') &&
-                (st.aux_periodic() != nullptr) == (has('P') && has('p')) && st.main.has_value() == (has('m') || has('r') || has('l') || has('k')) && st.main_rec == (has('r') || has('l') || has('k')) &&
-                st.main_lk == (has('l') || has('k')) && st.main_link == has('k') && !st.unsupported;
+                (st.aux_periodic() != nullptr) == (has('P') && has('p')) && st.main.has_value() == (has('m') || has('r') || has('l') || has('k')) &&
+                st.main_level == (has('k') ? AirMainLevel::Link : has('l') ? AirMainLevel::Lk : has('r') ? AirMainLevel::Rec : AirMainLevel::Main) && !st.unsupported;
     if (st.main && has('l') && !has('r') && st.main->cols.size() == 3) {   // what the prover's chunking reads of a COUNT column
         const auto& c = st.main->cols;
         fine = fine && c[1].kind == SP_AIR_MAIN_COUNT && c[1].key_bits == p.lcols[1].pad && c[1].num_op == 3 && c[1].den_op == 1 && c[1].reads == 1 && c[0].key_bits == 0 &&
