@@ -81,8 +81,8 @@ const char* sp_version(void);
  * sp_air_check_trace_pub, sp_air_boundary_desc_size and sp_air_boundary_resolve, and then sp_air_prove_main, sp_air_check_trace_main,
  * sp_air_main_trace, sp_air_main_check and sp_air_main_desc_size, then sp_air_prove_rec, sp_air_check_trace_rec, sp_air_main_trace_rec,
  * sp_air_main_check_rec and sp_air_main_chain_limits, then sp_air_prove_lk, sp_air_check_trace_lk, sp_air_main_trace_lk, sp_air_main_check_lk
- * and sp_air_main_count_limits, and last sp_air_prove_link, sp_air_check_trace_link, sp_air_main_trace_link, sp_air_main_check_link and
- * sp_air_main_link_limits).  A binding compares it (and sp_air_desc_size against its own idea of the struct) when it loads the library, so
+ * and sp_air_main_count_limits, then sp_air_prove_link, sp_air_check_trace_link, sp_air_main_trace_link, sp_air_main_check_link and
+ * sp_air_main_link_limits, and last sp_air_prove_div, sp_air_check_trace_div, sp_air_main_trace_div and sp_air_main_check_div).  A binding compares it (and sp_air_desc_size against its own idea of the struct) when it loads the library, so
  * a stale build fails at load time with "rebuild the library" instead of with a missing symbol or shifted fields later. */
 #define SP_ABI_VERSION 7
 int sp_abi_version(void);
@@ -681,7 +681,8 @@ int sp_air_main_check(const sp_air_desc* air, const sp_air_main_desc* main, uint
  * on the row they leave from: a LOAD of a column of the group must have shift 0 and is the state on row i; inputs and derived columns
  * before the group at shifts 0 .. 7, wrapping modulo n; periodic columns.  The w next values are assigned together, after the whole
  * step program has run.  Columns after the group read its columns as any earlier derived column.  No denominators: seeds and steps are
- * polynomial (CONST, ADD, SUB, MUL) - an inverse S-box (x^(1/d)) or a division inside a step is out of scope.  A block seeded from the
+ * polynomial (CONST, ADD, SUB, MUL) - an inverse S-box (x^(1/d)) is out of scope, a division inside a seed or a step is op 7 of the
+ * _div entry points below.  A block seeded from the
  * block before it (a multi-block sponge, a Merkle path) is a linked group of the _link entry points below; through these every block
  * stands alone, and bits of pad at or above 16 count as part of j.  Refused with SP_E_INVALID_ARG and a message that names the
  * column, before anything is sized: j out of sequence or a group longer than 16, l = 0 or 2^l > n, members of a group that differ in l,
@@ -748,6 +749,31 @@ int sp_air_main_trace_link(sp_ctx* ctx, const sp_air_desc* air, const sp_air_ext
 int sp_air_main_check_link(const sp_air_desc* air, const sp_air_ext* ext, const sp_air_main_desc* main, uint64_t n);
 /* out[0] = the highest k of a linked group (62), out[1] = the most columns of a linked group (16) */
 int sp_air_main_link_limits(uint32_t out[2]);
+
+/* ---- Quotients in chain steps: a recurrence whose next state needs a division by something the state decides - the slope
+ * lambda = (y - y_P) / (x - x_P) of an elliptic-curve addition chain (Pedersen, EC-op, ECDSA), itself a trace column because the AIR
+ * constrains lambda (x - x_P) = y - y_P.  Through the _div entry points - and only through them: everywhere else op 7 stays the malformed
+ * op it was - a main program may hold */
+#define SP_AIR_OP_DIV 7            /* op 7 DIV  a, b = earlier ops  -> value(a) / value(b)                                        */
+/* behind the SEED or the STEP op of an SP_AIR_MAIN_CHAIN column, that is: reachable through operands from a CHAIN column's den_op or
+ * num_op.  A quotient is an ordinary intermediate value: it may feed further arithmetic and another DIV, and several next values may
+ * share it.  Only the ops a group's seeds or steps reach are evaluated, so a zero under a DIV that nothing reaches is no error.  A
+ * reachable denominator that is zero on any row its group evaluates fails the call with SP_E_ZERO_INVERSE - the verdict of a zero D
+ * of a VALUE column, at the same moment: once the root (or the table) is back; nothing is returned and the context goes on.  Every
+ * other kind stays as it is: a VALUE, INV_OR_ZERO, BIT, SUM, PRODUCT or COUNT column whose N, D, X or T depends on an op 7 is refused
+ * with SP_E_INVALID_ARG and a message that names the column - a row-local quotient is a VALUE column's N / D, which shares one batched
+ * inversion with its whole chunk, where a DIV costs one inversion per lane (tens of microseconds: a DIV step is dominated by them, and
+ * a group's time is about rows-per-block x DIVs-per-step x that, whatever the number of blocks up to the device's width).  Constraint
+ * programs, auxiliary programs and boundary programs know no op 7.  The _div entry points accept everything the _link ones do; the
+ * proof is unchanged: the same table gives the same bytes.  Argument lists as the _link entry points. */
+int sp_air_prove_div(sp_ctx* ctx, const sp_air_desc* air, const sp_air_ext* ext, const sp_air_boundary_desc* bvals, const sp_air_main_desc* main,
+                     const void* inputs, uint64_t n, const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len);
+int sp_air_check_trace_div(sp_ctx* ctx, const sp_air_desc* air, const sp_air_ext* ext, const sp_air_boundary_desc* bvals, const sp_air_main_desc* main,
+                           const void* inputs, uint64_t n, const sp_proof_options* opt, const uint8_t* rap, sp_air_violation* out, uint32_t cap,
+                           uint32_t* n_out);
+int sp_air_main_trace_div(sp_ctx* ctx, const sp_air_desc* air, const sp_air_ext* ext, const sp_air_main_desc* main, const void* inputs, uint64_t n,
+                          uint8_t* rows_out);
+int sp_air_main_check_div(const sp_air_desc* air, const sp_air_ext* ext, const sp_air_main_desc* main, uint64_t n);
 
 /* verify::<Stark252PrimeField, A> (reference src/starks/verifier.rs:559-657) on the host CPU: 1 accept, 0 reject (also for
  * malformed proofs or descriptors). */

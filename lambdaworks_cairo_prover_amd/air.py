@@ -39,6 +39,10 @@ over several blocks, a Merkle path.  See mimc_sponge and merkle_paths below.
 Lookup multiplicities (sp_air_prove_lk): b.main.multiplicity(x, table, key_bits) declares the column m of a LogUp lookup - how often
 the table value of row i occurs among the looked-up values of all rows, on the first row that holds it -, which the device builds by
 sorting both sides.  With it a lookup's whole witness comes from the inputs.  See table_lookup_main and xor_lookup below.
+
+Quotients in chain steps (sp_air_prove_div): inside the seeds and steps of a chain group b.main.div(num, den) - or num / den - is a
+value like any other: the slope of an elliptic-curve addition, which the next state needs and the AIR constrains as a column.  See
+ec_subset_sum below.
 """
 import collections
 import ctypes
@@ -46,6 +50,8 @@ import ctypes
 P = 2**251 + 17 * 2**192 + 1
 
 OP_LOAD, OP_CONST, OP_ADD, OP_SUB, OP_MUL, OP_OUT, OP_PERIODIC = range(7)
+OP_DIV = 7      # a main-trace program only, behind the seed or step of a CHAIN column (sp_air_prove_div)
+_TWO_VALUES = (OP_ADD, OP_SUB, OP_MUL, OP_DIV)   # the ops whose a and b name earlier values
 MAX_OFFSETS, MAX_TRANSITIONS = 8, 64
 AUX_TRACE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint8))
 
@@ -295,10 +301,21 @@ def needs_link(desc):
     return bool(main.cols) and any(main.cols[k].kind == MAIN_CHAIN and main.cols[k].pad >> 16 for k in range(main.n_cols))
 
 
+def needs_div(desc):
+    """Whether a built descriptor's main program needs the _div entry points: it holds an op 7, a quotient behind a chain group."""
+    main = getattr(desc, "main_desc", None)
+    if main is None:
+        return False
+    known = getattr(desc, "main_needs_div", None)   # (AirBuilder.build() says so; a descriptor put together by hand is looked through)
+    if known is not None:
+        return known
+    return bool(main.ops) and any(main.ops[i].op == OP_DIV for i in range(main.n_ops))
+
+
 def main_suffix(desc):
-    """The entry points a descriptor's main program goes through: "link", "lk", "rec" or "main" - the newer ones only where it needs
-    them."""
-    return "link" if needs_link(desc) else "lk" if needs_lk(desc) else "rec" if needs_rec(desc) else "main"
+    """The entry points a descriptor's main program goes through: "div", "link", "lk", "rec" or "main" - the newer ones only where it
+    needs them."""
+    return "div" if needs_div(desc) else "link" if needs_link(desc) else "lk" if needs_lk(desc) else "rec" if needs_rec(desc) else "main"
 
 
 def route(desc, call):
@@ -308,7 +325,8 @@ def route(desc, call):
     verifier takes no auxiliary program).  A descriptor with a main-trace program (desc.main_desc) is proved and checked through the
     _main entry points, which take everything the _pub ones do - through the _rec ones when it holds a chain column or reads a
     periodic column (needs_rec), through the _lk ones when it holds a lookup multiplicity (needs_lk), through the _link ones when a
-    chain group links its blocks into runs (needs_link) -; it is verified as if it had none."""
+    chain group links its blocks into runs (needs_link), through the _div ones when a seed or a step divides (needs_div) -; it is
+    verified as if it had none."""
     def ref(part):
         return None if part is None else ctypes.byref(part)
     aux, per = getattr(desc, "aux_desc", None), getattr(desc, "periodic_desc", None)
@@ -381,6 +399,15 @@ class Value:
     __rmul__ = __mul__
 
     def __rsub__(self, o): return self._lift(o) - self
+
+    def _div(self, num, den):
+        if not hasattr(self.b, "div"):
+            raise ValueError("a quotient (/) lives in a main-trace program only, behind the seed or step of a chain group (b.main.div); a constraint, "
+                             "auxiliary or boundary program has N / D of a column or a boundary value instead")
+        return self.b.div(num, den)
+
+    def __truediv__(self, o): return self._div(self, self._lift(o))
+    def __rtruediv__(self, o): return self._div(self._lift(o), self)
 
 
 class AuxProgram:
@@ -613,7 +640,12 @@ class MainProgram:
         g.step([next_0, ...])      the value of each column on the NEXT row, all computed from the current one; closes the group
         periodic(shift, k)         periodic column k of the AirBuilder on row (i + shift): values[(i + shift) mod period_k] (op 6)
 
-    Between chain() and step() no other column can be declared.  Seeds and steps are polynomial: no denominators.
+    Between chain() and step() no other column can be declared.  Seeds and steps are polynomial, unless they divide (sp_air_prove_div):
+
+        div(num, den)              num / den, also written num / den: a value like any other - it may feed further arithmetic and
+                                   another quotient, and several next values may share it - but only the seed or the step of a chain
+                                   group may depend on it.  A zero den on a row the group evaluates fails the call (SP_E_ZERO_INVERSE;
+                                   ValueError in evaluate).  A row-local quotient is value(N, D), which is far cheaper.
 
     Blocks seeded from the block before - a sponge that absorbs several blocks, a Merkle path - are a linked group (sp_air_prove_link):
 
@@ -639,6 +671,7 @@ class MainProgram:
         self._open = None                    # the chain group between chain() and step()
         self.lookups = False                 # multiplicity() was called: check() mirrors the decoder of the _lk entry points
         self.links = False                   # chain(link > 1) was called: check() mirrors the decoder of the _link entry points
+        self.divs = False                    # div() was called: check() mirrors the decoder of the _div entry points
 
     def _emit(self, op, a, b):
         self.ops.append((op, a, b))
@@ -663,6 +696,15 @@ class MainProgram:
         if not 0 <= k < len(self.periodic_cols):
             raise ValueError(f"main program: column {k} is not one of the AIR's {len(self.periodic_cols)} periodic columns")
         return self._emit(OP_PERIODIC, shift, k)
+
+    def div(self, num, den):
+        """num / den (op 7): see the class.  Legal behind the seed or step of a chain group only, which check() holds the columns to."""
+        num = num if isinstance(num, Value) else self.const(num)
+        den = den if isinstance(den, Value) else self.const(den)
+        if num.b is not self or den.b is not self:
+            raise ValueError("main program: the operands of a quotient must be values of this program")
+        self.divs = True
+        return self._emit(OP_DIV, num.i, den.i)
 
     def chain(self, period, seeds, width=None, link=1):
         """Opens a chain group of len(seeds) columns in blocks of `period` rows (see the class); returns its ChainGroup.  link = L > 1
@@ -757,17 +799,27 @@ class MainProgram:
             if op == OP_LOAD:
                 reads.append(max(0, b - self.input_cols + 1) if a or not shifted_only else 0)
             else:
-                reads.append(max(reads[a], reads[b]) if op in (OP_ADD, OP_SUB, OP_MUL) else 0)
+                reads.append(max(reads[a], reads[b]) if op in _TWO_VALUES else 0)
         return reads
 
-    def check(self, n=None, lookups=None, links=None):
+    def _quotients(self):
+        """Per op: whether its value depends on a quotient (op 7) - the decoder's mark of the same name."""
+        quot = []
+        for op, a, b in self.ops:
+            quot.append(op == OP_DIV or (op in _TWO_VALUES and (quot[a] or quot[b])))
+        return quot
+
+    def check(self, n=None, lookups=None, links=None, divs=None):
         """The decoder's rules (air_statement_from_c), for a program whose lists were filled by hand too: ValueError naming the first one
         broken.  n: the trace length a chain group's block length is held against (None: not yet known).  lookups: whether COUNT
         columns are known - the decoder of the _lk entry points, where the program would be routed after multiplicity() declared one
         (None: self.lookups); otherwise kind 6 is an unknown kind, as for the _rec entry points.  links: whether the k of a CHAIN
         column's pad is known - the decoder of the _link entry points, where the program would be routed after chain(link > 1) declared
-        a linked group (None: self.links), which knows COUNT columns too; otherwise the bits at and above 16 belong to j."""
-        links = self.links if links is None else links
+        a linked group (None: self.links), which knows COUNT columns too; otherwise the bits at and above 16 belong to j.  divs:
+        whether op 7 is known - the decoder of the _div entry points, where the program would be routed after div() emitted one (None:
+        self.divs), which knows linked groups too; otherwise op 7 is a malformed op."""
+        divs = self.divs if divs is None else divs
+        links = (self.links if links is None else links) or divs
         lookups = (self.lookups if lookups is None else lookups) or links
         pos = (lambda pad: (pad >> 8) & 255) if links else (lambda pad: pad >> 8)
         n_count = 0
@@ -779,10 +831,15 @@ class MainProgram:
             if op == OP_PERIODIC and 0 <= a <= AUX_MAX_SHIFT and not 0 <= b < len(self.periodic_cols):
                 raise ValueError(f"main program: op {t} reads periodic column {b}, and the AIR has {len(self.periodic_cols)}")
             ok = ((op == OP_LOAD and 0 <= a <= AUX_MAX_SHIFT and 0 <= b < self.main_cols) or (op == OP_CONST and 0 <= a < len(self.consts)) or
-                  (op in (OP_ADD, OP_SUB, OP_MUL) and 0 <= a < t and 0 <= b < t) or (op == OP_PERIODIC and 0 <= a <= AUX_MAX_SHIFT))
+                  (op in (OP_ADD, OP_SUB, OP_MUL) and 0 <= a < t and 0 <= b < t) or (op == OP_PERIODIC and 0 <= a <= AUX_MAX_SHIFT) or
+                  (divs and op == OP_DIV and 0 <= a < t and 0 <= b < t))
+            if not ok and divs:
+                raise ValueError(f"main program: malformed op {t} (LOAD, CONST, ADD, SUB, MUL, DIV over earlier ops, PERIODIC only)")
             if not ok:
                 raise ValueError(f"main program: malformed op {t} (LOAD, CONST, ADD, SUB, MUL over earlier ops, PERIODIC only)")
-        reads, shifted = self.reads(), self._reads(True)
+        reads, shifted, quot = self.reads(), self._reads(True), self._quotients()
+        refused = ("depends on a quotient (op 7), which only the seed or the step of a CHAIN column may: a row-local quotient is a VALUE "
+                   "column's N / D")
         g0 = g_end = 0      # the chain group that column k belongs to is [g0, g_end), when k < g_end
         for k, (kind, num_op, den_op, pad) in enumerate(self.cols):
             den = den_op != AUX_NO_DEN
@@ -795,6 +852,8 @@ class MainProgram:
                     raise ValueError(f"main program: derived column {k} is a COUNT column with key_bits = {pad} (1 .. {MAIN_COUNT_MAX_KEY_BITS})")
                 if not (0 <= num_op < len(self.ops) and 0 <= den_op < len(self.ops)):
                     raise ValueError(f"main program: derived column {k} names an op beyond the program")
+                if quot[num_op] or quot[den_op]:
+                    raise ValueError(f"main program: derived column {k} {refused}")
                 r = max(reads[num_op], reads[den_op])
                 if r > k:
                     raise ValueError(f"main program: derived column {k} reads derived column {r - 1}, which is not an earlier one")
@@ -843,6 +902,8 @@ class MainProgram:
                 continue
             if not 0 <= num_op < len(self.ops) or (den and not 0 <= den_op < len(self.ops)):
                 raise ValueError(f"main program: derived column {k} names an op beyond the program")
+            if quot[num_op] or (den and quot[den_op]):
+                raise ValueError(f"main program: derived column {k} {refused}")
             if den and kind in (MAIN_INV_OR_ZERO, MAIN_BIT):
                 raise ValueError(f"main program: derived column {k} is an INV_OR_ZERO or a BIT and takes no denominator")
             if kind == MAIN_BIT and not 0 <= pad <= MAIN_MAX_BIT:
@@ -856,8 +917,9 @@ class MainProgram:
         returns an (n, main_cols) numpy object array.  Columns in index order, each op one vectorised numpy operation, evaluated when the
         first column that needs it is built (the columns it loads are complete by then).  ValueError on a zero denominator.  A chain
         group is a loop over the rows t of a block, each step vectorised over the n / period blocks; a linked group a loop over the
-        blocks of a run and the rows of each, vectorised over the runs, the carry zero in front of each run.  A COUNT column is a dictionary
-        count of X, read on the first row of each table value; ValueError on a key at or above 2^key_bits."""
+        blocks of a run and the rows of each, vectorised over the runs, the carry zero in front of each run.  A quotient (op 7) is one
+        batch inversion per op and step, over the blocks or runs; ValueError on a zero under one that a seed or a step reaches.  A COUNT
+        column is a dictionary count of X, read on the first row of each table value; ValueError on a key at or above 2^key_bits."""
         import numpy as np
         self.check(len(input_rows))
         rows = input_rows if not isinstance(input_rows, np.ndarray) else input_rows.astype(object)
@@ -874,7 +936,7 @@ class MainProgram:
                 if u in todo or vals[u] is not None:
                     continue
                 todo.add(u)
-                if self.ops[u][0] in (OP_ADD, OP_SUB, OP_MUL):
+                if self.ops[u][0] in _TWO_VALUES:
                     stack += [self.ops[u][1], self.ops[u][2]]
             for u in sorted(todo):
                 op, a, b = self.ops[u]
@@ -888,9 +950,19 @@ class MainProgram:
                     vals[u] = (vals[a] + vals[b]) % P
                 elif op == OP_SUB:
                     vals[u] = (vals[a] - vals[b]) % P
-                else:
+                elif op == OP_MUL:
                     vals[u] = (vals[a] * vals[b]) % P
+                elif op == OP_DIV:    # (check() lets no row-local column reach here: kept for a program it was not asked about)
+                    vals[u] = (vals[a] * np.array(quotient_inverses(vals[b]), dtype=object)) % P
+                else:
+                    raise ValueError(f"main program: op {u} has the unknown code {op}")
             return vals[t]
+
+        def quotient_inverses(dens):
+            try:
+                return _batch_inverse([int(x) for x in dens])
+            except ValueError:
+                raise ValueError("main program: a denominator of a quotient (op 7) is zero on some row") from None
 
         def run(targets, rows, first, state):
             """The values of the ops `targets` on the rows `rows` alone, a LOAD of group column first + j being state[j]."""
@@ -901,7 +973,7 @@ class MainProgram:
                 if u in todo:
                     continue
                 todo.add(u)
-                if self.ops[u][0] in (OP_ADD, OP_SUB, OP_MUL):
+                if self.ops[u][0] in _TWO_VALUES:
                     stack += [self.ops[u][1], self.ops[u][2]]
             for u in sorted(todo):
                 op, a, b = self.ops[u]
@@ -915,20 +987,25 @@ class MainProgram:
                     got[u] = (got[a] + got[b]) % P
                 elif op == OP_SUB:
                     got[u] = (got[a] - got[b]) % P
-                else:
+                elif op == OP_MUL:
                     got[u] = (got[a] * got[b]) % P
+                elif op == OP_DIV:    # one batch inversion per op and step, over the blocks (or runs)
+                    got[u] = (got[a] * np.array(quotient_inverses(got[b]), dtype=object)) % P
+                else:
+                    raise ValueError(f"main program: op {u} has the unknown code {op}")
             return [got[u] for u in targets]
 
         periodic = [np.array(values, dtype=object) for values in self.periodic_cols]
         for k, (kind, num_op, den_op, pad) in enumerate(self.cols):
             if kind == MAIN_CHAIN:
-                pos = (lambda pad: (pad >> 8) & 255) if self.links else (lambda pad: pad >> 8)
+                linked = self.links or self.divs    # (the _div entry points read the k of a pad as the _link ones do)
+                pos = (lambda pad: (pad >> 8) & 255) if linked else (lambda pad: pad >> 8)
                 if pos(pad):
                     continue            # (built with its group, at the column that opens it)
                 period, w = 1 << (pad & 255), 1
                 while k + w < len(self.cols) and self.cols[k + w][0] == MAIN_CHAIN and pos(self.cols[k + w][3]):
                     w += 1
-                link = 1 << (pad >> 16) if self.links else 1
+                link = 1 << (pad >> 16) if linked else 1
                 first = self.input_cols + k
                 state = [np.zeros(n // (period * link), dtype=object) for _ in range(w)] if link > 1 else []   # the carry in front of a run
                 for block in range(link):
@@ -1417,6 +1494,7 @@ class AirBuilder:
             d.main_needs_rec = any(c[0] == MAIN_CHAIN for c in self.main.cols) or any(op == OP_PERIODIC for op, _, _ in self.main.ops)
             d.main_needs_lk = any(c[0] == MAIN_COUNT for c in self.main.cols)
             d.main_needs_link = self.main.links and any(c[0] == MAIN_CHAIN and c[3] >> 16 for c in self.main.cols)
+            d.main_needs_div = any(op == OP_DIV for op, _, _ in self.main.ops)
             keep = keep + (m_desc, m_keep)
         return d, keep
 
@@ -2006,3 +2084,73 @@ def xor_lookup_inputs(n, bits, rng):
         a, b = rng.randrange(1 << bits), rng.randrange(1 << bits)
         rows.append([a, b, a ^ b])
     return rows
+
+
+# ---- quotients in chain steps: a worked example -----------------------------------------------------------------------------------
+def ec_subset_sum(n, s, points, shift, result):
+    """n / s fixed-base accumulations on a curve y^2 = x^3 + a x + beta, one per block of s rows (the shape of Cairo's Pedersen, EC-op
+    and ECDSA builtins): the caller uploads the bits b (column 0) and the device builds the rest (sp_air_prove_div).  Columns 1 - 3 are
+    the chain group (x, y, lambda): the accumulator and the slope of the chord to the row's public point P_t = `points`[t] (periodic
+    columns 0 and 1, period s).  Seeds: (x, y) = `shift`, a public point, and lambda = (y - y_P) / (x - x_P) - a quotient in a seed.
+    Step: the row adds P_t when b = 1 and keeps the accumulator when b = 0,
+
+        x' = b (lambda^2 - x - x_P) + (1 - b) x,    y' = b (lambda (x - x_add) - y) + (1 - b) y    (x_add the added point's x),
+        lambda' = (y' - y_P(i + 1)) / (x' - x_P(i + 1))
+
+    - a quotient over the step's own new values, with the periodic columns read at shift 1.  Columns 4 and 5 are the row-local q =
+    lambda^2 and u = b lambda (VALUE), which keep every constraint at degree 3 under degree_bound_factor 2.  Periodic column 2 is
+    sel = [1] (s - 1) + [0].  Constraints, no exemption: b (b - 1); lambda (x - x_P) - (y - y_P); q - lambda^2; u - b lambda;
+    sel (b (q - x - x_P - x') + (1 - b) (x' - x)); sel (u (x - x') - b (y + y') + (1 - b) (y' - y)) on every row - sel switches the
+    last two off where a block ends -; x - shift_x and y - shift_y on the rows = 0 (mod s).  The boundary constraints (x, y) = `result`
+    on row s - 1 are block 0's public sum (ec_subset_sum_result): shift + the sum of b_t P_t over t < s - 1; the last point of a block
+    is met by the slope alone.  An accumulator that meets +-P_t has no chord: the device answers SP_E_ZERO_INVERSE, evaluate ValueError
+    - `shift` is there to keep the sums off the points."""
+    if s < 2 or s & (s - 1) or s > n or len(points) != s:
+        raise ValueError(f"ec_subset_sum: blocks of {s} rows with {len(points)} points on {n} rows (a power of two in 2 .. n, one point per row of a block)")
+    b = AirBuilder(6, [0, 1], 2, periodic=[[p[0] for p in points], [p[1] for p in points], [1] * (s - 1) + [0]], main_inputs=1)
+    m = b.main
+    sx, sy = m.const(shift[0]), m.const(shift[1])
+    g = m.chain(s, [sx, sy, (sy - m.periodic(0, 1)) / (sx - m.periodic(0, 0))])
+    bit, x, y, lam = m.load(0, 0), g.state(0), g.state(1), g.state(2)
+    x_add = lam * lam - x - m.periodic(0, 0)
+    x2 = bit * x_add + (1 - bit) * x
+    y2 = bit * (lam * (x - x_add) - y) + (1 - bit) * y
+    g.step([x2, y2, (y2 - m.periodic(1, 1)) / (x2 - m.periodic(1, 0))])
+    cx, cy, cl = g.cols
+    q = m.value(m.load(0, cl) * m.load(0, cl))
+    u = m.value(m.load(0, 0) * m.load(0, cl))
+    B, X, Y, L, Q, U = b.load(0, 0), b.load(0, cx), b.load(0, cy), b.load(0, cl), b.load(0, q), b.load(0, u)
+    X1, Y1 = b.load(1, cx), b.load(1, cy)
+    XP, YP, SEL = b.periodic(0, 0), b.periodic(0, 1), b.periodic(0, 2)
+    b.constraint(B * (B - 1), degree=2, exemptions=0)
+    b.constraint(L * (X - XP) - (Y - YP), degree=2, exemptions=0)
+    b.constraint(Q - L * L, degree=2, exemptions=0)
+    b.constraint(U - B * L, degree=2, exemptions=0)
+    b.constraint(SEL * (B * (Q - X - XP - X1) + (1 - B) * (X1 - X)), degree=3, exemptions=0)
+    b.constraint(SEL * (U * (X - X1) - B * (Y + Y1) + (1 - B) * (Y1 - Y)), degree=3, exemptions=0)
+    b.constraint(X - shift[0], degree=1, exemptions=0, period=s, offset=0)
+    b.constraint(Y - shift[1], degree=1, exemptions=0, period=s, offset=0)
+    b.boundary(cx, s - 1, result[0])
+    b.boundary(cy, s - 1, result[1])
+    return b
+
+
+def _ec_add(p, q):
+    """The chord addition of two affine points with different x (the only case ec_subset_sum meets)."""
+    lam = (p[1] - q[1]) * pow(p[0] - q[0], P - 2, P) % P
+    x = (lam * lam - p[0] - q[0]) % P
+    return x, (lam * (p[0] - x) - p[1]) % P
+
+
+def ec_subset_sum_result(bits, points, shift):
+    """(x, y) on the last row of the block whose bits are `bits` (its first s - 1 count): the public sum of ec_subset_sum."""
+    acc = (shift[0] % P, shift[1] % P)
+    for bit, point in zip(bits[:len(points) - 1], points):
+        if int(bit):
+            acc = _ec_add(acc, point)
+    return acc
+
+
+def ec_subset_sum_inputs(n, rng):
+    """(n, 1) Python ints: a random bit on every row."""
+    return [[rng.randrange(2)] for _ in range(n)]

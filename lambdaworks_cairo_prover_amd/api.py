@@ -243,7 +243,8 @@ class Context:
         main_inputs=I)), built on the device from the input columns: (n, main_cols, 32) uint8 in the context encoding.  No commitment.
         A program with a chain column or a read of a periodic column (air.needs_rec) goes to sp_air_main_trace_rec with the
         descriptor's sp_air_ext, which carries the periodic columns; one with a lookup multiplicity (air.needs_lk) to
-        sp_air_main_trace_lk, one with a linked chain group (air.needs_link) to sp_air_main_trace_link, with the same arguments."""
+        sp_air_main_trace_lk, one with a linked chain group (air.needs_link) to sp_air_main_trace_link, one with a quotient (op 7) behind
+        a chain group (air.needs_div) to sp_air_main_trace_div, with the same arguments."""
         main = getattr(desc, "main_desc", None)
         if main is None:
             raise ValueError("air_main_trace: the descriptor carries no main program (AirBuilder(..., main_inputs=...))")
@@ -568,7 +569,8 @@ def air_main_check(desc, n, main=None):
     """sp_air_main_check (host): the decoder's verdict on a main-trace program (main, or desc.main_desc) for this AIR and n rows; raises
     SpError with its refusal (SP_E_INVALID_ARG, or SP_E_UNSUPPORTED beside aux_kind 1 or 2).  A program with a chain column or a read of
     a periodic column (air.needs_rec) is judged by sp_air_main_check_rec, beside the descriptor's periodic columns; one with a lookup
-    multiplicity (air.needs_lk) by sp_air_main_check_lk, one with a linked chain group (air.needs_link) by sp_air_main_check_link."""
+    multiplicity (air.needs_lk) by sp_air_main_check_lk, one with a linked chain group (air.needs_link) by sp_air_main_check_link, one
+    with a quotient (air.needs_div) by sp_air_main_check_div."""
     from . import air
     own = getattr(desc, "main_desc", None)
     main = own if main is None else main

@@ -15,7 +15,7 @@ fe air_root_of_unity(int order) {   // the field's 2^192-th root, squared down
 }
 
 size_t air_program_first_bad_op(const std::vector<AirOpHost>& ops, uint32_t load_a_end, uint32_t load_b_end, size_t n_values, uint32_t n_out,
-                                uint32_t n_periodic) {
+                                uint32_t n_periodic, bool div) {
     auto value = [&](uint32_t i, size_t t) { return i < t && ops[i].op != 5; };   // an earlier op that produces a value
     for (size_t t = 0; t < ops.size(); ++t) {
         const AirOpHost& o = ops[t];
@@ -26,6 +26,7 @@ size_t air_program_first_bad_op(const std::vector<AirOpHost>& ops, uint32_t load
             case 2: case 3: case 4: ok = value(o.a, t) && value(o.b, t); break;
             case 5: ok = o.a < n_out && value(o.b, t); break;
             case 6: ok = o.a < load_a_end && o.b < n_periodic; break;
+            case 7: ok = div && value(o.a, t) && value(o.b, t); break;
             default: ok = false;
         }
         if (!ok) return t;
@@ -154,9 +155,12 @@ std::string validate_aux_program(const AirAuxHost& aux, uint32_t main_cols, uint
 // read it at shift 0 only; without rec kind 5 is an unknown kind and op 6 a malformed op.  lk (the _lk entry points, with rec):
 // SP_AIR_MAIN_COUNT columns too - a table, key_bits in 1 .. 64, at most 16 of them; without lk kind 6 is an unknown kind.  link (the
 // _link entry points, with lk): a CHAIN column's pad is l + 256 j + 65536 k, runs of 2^k blocks; with k >= 1 a seed may load its own
-// group at shift 0; without link j = pad >> 8, so a pad with bits at or above 16 is a j out of sequence.
+// group at shift 0; without link j = pad >> 8, so a pad with bits at or above 16 is a j out of sequence.  div (the _div entry points,
+// with link): op 7 DIV over earlier ops, behind the seeds and steps of CHAIN columns only; a column of any other kind that depends on
+// one is refused, and without div op 7 is a malformed op.
 std::string main_from_c(const AirDescHost& air, const sp_air_main_desc* m, uint64_t n, uint32_t n_periodic, AirMainLevel level, AirMainHost& out) {
     const bool rec = air_main_allows_chains(level), lk = air_main_allows_counts(level), link = air_main_allows_runs(level);
+    const bool div = air_main_allows_quotients(level);
     if (m->size != sizeof(sp_air_main_desc)) return "main program: sp_air_main_desc.size is not sizeof(sp_air_main_desc)";
     if (!m->ops || !m->consts || !m->cols) return "main program: null ops, consts or cols";
     if (m->input_cols == 0 || m->n_cols == 0 || (uint64_t)m->input_cols + m->n_cols != air.main_cols)
@@ -172,17 +176,28 @@ std::string main_from_c(const AirDescHost& air, const sp_air_main_desc* m, uint6
                 return "main program: op " + std::to_string(t) + " reads periodic column " + std::to_string(ops[t].b) + ", and the statement has " +
                        std::to_string(n_periodic) + " (ext->periodic)";
     // (no OUT target; a periodic column only through the _rec entry points: elsewhere ops 0 .. 4 are all that is left)
-    const size_t bad = air_program_first_bad_op(ops, AIR_LIMIT_AUX_SHIFT + 1, air.main_cols, m->n_consts, 0, rec ? n_periodic : 0u);
+    const size_t bad = air_program_first_bad_op(ops, AIR_LIMIT_AUX_SHIFT + 1, air.main_cols, m->n_consts, 0, rec ? n_periodic : 0u, div);
+    if (bad < n_ops && div)
+        return "main program: malformed op " + std::to_string(bad) + " (LOAD needs a shift of 0 .. 7 and a main column, CONST a constant, ADD / SUB / MUL / DIV "
+               "earlier ops, op 6 a shift of 0 .. 7 and a periodic column; there is no OUT and no RAP challenge)";
     if (bad < n_ops)
         return "main program: malformed op " + std::to_string(bad) + " (LOAD needs a shift of 0 .. 7 and a main column, CONST a constant, ADD / SUB / MUL earlier "
                "ops; there is no OUT and no RAP challenge, and op 6 - a shift of 0 .. 7 and a periodic column - only through the _rec entry points)";
     // reads[t]: one more than the highest derived column the value of op t depends on (0: inputs only); shifted[t]: the same over the
-    // LOADs at a shift other than 0 alone (what a chain's step may not do to its own group)
+    // LOADs at a shift other than 0 alone (what a chain's step may not do to its own group); quot[t]: the value of op t depends on a
+    // quotient (an op 7 is op t or stands behind it), which only the seed and the step of a CHAIN column may
     std::vector<uint32_t> reads(n_ops, 0), shifted(n_ops, 0);
+    std::vector<uint8_t> quot(n_ops, 0);
+    const auto quotient_refused = [](const std::string& who) {
+        return who + " depends on a quotient (op 7), which only the seed or the step of a CHAIN column may: a row-local quotient is a VALUE column's N / D";
+    };
     for (size_t t = 0; t < n_ops; ++t) {
         const AirOpHost& o = ops[t];
         if (o.op == 0 && o.b >= m->input_cols) { reads[t] = o.b - m->input_cols + 1; shifted[t] = o.a ? reads[t] : 0u; }
-        else if (o.op >= 2 && o.op <= 4) { reads[t] = std::max(reads[o.a], reads[o.b]); shifted[t] = std::max(shifted[o.a], shifted[o.b]); }
+        else if (air_op_takes_two_values(o.op)) {
+            reads[t] = std::max(reads[o.a], reads[o.b]); shifted[t] = std::max(shifted[o.a], shifted[o.b]);
+            quot[t] = o.op == 7 || quot[o.a] || quot[o.b];
+        }
     }
     std::vector<AirMainColumnHost> cols;
     cols.reserve(m->n_cols);
@@ -197,6 +212,7 @@ std::string main_from_c(const AirDescHost& air, const sp_air_main_desc* m, uint6
             if (!den) return who + " is a COUNT column without a table (den_op names the table value)";
             if (c.pad == 0 || c.pad > AIR_MAIN_COUNT_MAX_KEY_BITS) return who + " is a COUNT column with key_bits = " + std::to_string(c.pad) + " (1 .. 64)";
             if (c.num_op >= n_ops || c.den_op >= n_ops) return who + " names an op beyond the program";
+            if (quot[c.num_op] || quot[c.den_op]) return quotient_refused(who);
             const uint32_t r = std::max(reads[c.num_op], reads[c.den_op]);
             if (r > k) return who + " reads derived column " + std::to_string(r - 1) + ", which is not an earlier one";
             if (++n_count > AIR_MAIN_COUNT_MAX_COLS) return who + " is the program's COUNT column number " + std::to_string(n_count) + " (at most 16)";
@@ -236,6 +252,7 @@ std::string main_from_c(const AirDescHost& air, const sp_air_main_desc* m, uint6
             continue;
         }
         if (c.num_op >= n_ops || (den && c.den_op >= n_ops)) return who + " names an op beyond the program";
+        if (quot[c.num_op] || (den && quot[c.den_op])) return quotient_refused(who);
         if (den && (c.kind == SP_AIR_MAIN_INV_OR_ZERO || c.kind == SP_AIR_MAIN_BIT)) return who + " is an INV_OR_ZERO or a BIT and takes no denominator";
         if (c.kind == SP_AIR_MAIN_BIT && c.pad > 251) return who + " names bit " + std::to_string(c.pad) + " (0 .. 251)";
         const uint32_t r = std::max(reads[c.num_op], den ? reads[c.den_op] : 0u);
@@ -295,8 +312,8 @@ std::string air_statement_from_c(const sp_air_desc* d, const sp_air_aux_desc* au
     if (air.consts.size() + air.n_rap > 65535) return "constants and RAP challenges exceed the 16-bit operand range";
     if (air.ops.size() > AIR_LIMIT_OPS) return "more than 65535 ops";
     if (main) {
-        // (only the _rec, _lk and _link entry points let a main program hold chain columns and read the periodic columns, only _lk and
-        // _link COUNT columns, only _link runs of blocks)
+        // (only the _rec, _lk, _link and _div entry points let a main program hold chain columns and read the periodic columns, only
+        // _lk, _link and _div COUNT columns, only _link and _div runs of blocks, only _div quotients behind chain seeds and steps)
         const std::string refused = main_from_c(air, main, n, st.n_periodic(), st.main_level, st.main.emplace());
         if (!refused.empty()) return refused;
     }

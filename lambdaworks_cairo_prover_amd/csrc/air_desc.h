@@ -110,9 +110,12 @@ bool air_resolve_boundary_into(const AirBoundaryHost& bvals, const std::vector<f
 // b < load_b_end, a CONST names one of n_values constants or RAP challenges, ADD / SUB / MUL take two earlier ops that are not
 // OUTs, an OUT one of n_out targets and such an op (n_out 0: no OUT at all), a PERIODIC a < load_a_end and one of n_periodic
 // periodic columns (0: the program cannot read any).  Returns the index of the first op that breaks them, ops.size() when none
-// does.
+// does.  div (a main-trace program through the _div entry points, and nothing else): op 7 DIV takes two earlier ops that are not OUTs
+// too; without it op 7 is the unknown op it always was.
 size_t air_program_first_bad_op(const std::vector<AirOpHost>& ops, uint32_t load_a_end, uint32_t load_b_end, size_t n_values, uint32_t n_out,
-                                uint32_t n_periodic);
+                                uint32_t n_periodic, bool div = false);
+// ADD, SUB, MUL and DIV: the ops whose a and b name earlier values (what the slot assignment and the operand walks follow)
+inline bool air_op_takes_two_values(uint8_t op) { return (op >= 2 && op <= 4) || op == 7; }
 // the primitive root of unity of order 2^order (lambdaworks get_primitive_root_of_unity)
 fe air_root_of_unity(int order);
 
@@ -121,10 +124,12 @@ fe air_root_of_unity(int order);
 //   Rec    (the _rec entry points) CHAIN columns too, and op 6 reads the periodic columns
 //   Lk     (the _lk entry points) COUNT columns too, lookup multiplicities
 //   Link   (the _link entry points) a chain group's blocks may form runs seeded from the block before
-enum class AirMainLevel : uint8_t { Main, Rec, Lk, Link };
+//   Div    (the _div entry points) op 7 DIV behind the seeds and steps of CHAIN columns: quotients inside a recurrence
+enum class AirMainLevel : uint8_t { Main, Rec, Lk, Link, Div };
 inline bool air_main_allows_chains(AirMainLevel l) { return l >= AirMainLevel::Rec; }   // (and op 6)
 inline bool air_main_allows_counts(AirMainLevel l) { return l >= AirMainLevel::Lk; }
 inline bool air_main_allows_runs(AirMainLevel l) { return l >= AirMainLevel::Link; }
+inline bool air_main_allows_quotients(AirMainLevel l) { return l >= AirMainLevel::Div; }
 
 // Everything a prover, a trace check or a verifier is told about a program AIR: the descriptor (its strides inside) and its optional
 // parts, each present or not.  aux_reads_periodic: whether the auxiliary program may read the periodic columns with op 6 (the _pub
@@ -160,6 +165,10 @@ struct AirStatement {
 // main_level Link (the _link entry points only; it brings Lk with it): a CHAIN column's pad also carries k = pad >> 16 - runs of 2^k
 // blocks, l + k <= log2 n, one k per group - and with k >= 1 a seed may load its own group at shift 0 (the carry); without it the
 // bits at and above 16 belong to j, as ever.
+// main_level Div (the _div entry points only; it brings Link with it): op 7 DIV a b = value(a) / value(b) over earlier ops, behind the
+// seed or step op of a CHAIN column only - a VALUE, INV_OR_ZERO, BIT, SUM, PRODUCT or COUNT column whose N, D, X or T depends on an
+// op 7 is refused (a row-local quotient is a VALUE column's N / D, which keeps the batched inversion); without it op 7 is a malformed
+// op, as ever.  A zero under a DIV is a matter of the rows, not of the statement: SP_E_ZERO_INVERSE from the call that meets it.
 // The constraint program itself is checked where it is turned into what runs it (build_air_program, air_verify_host).
 // An sp_air_ext is taken apart by the entry point that receives it; this is the one thing it checks first: null, or what is wrong.
 inline const char* air_ext_refusal(const sp_air_ext* ext) { return ext && ext->size != sizeof(sp_air_ext) ? "sp_air_ext.size is not sizeof(sp_air_ext)" : nullptr; }

@@ -26,9 +26,20 @@ struct AirRowPeriodic {
     }
 };
 
-template <bool PER, class Load, class Periodic, class Out>
+// op 7 of a chain group's seed and step programs (DIV): num / den by one safegcd inversion of the lane's own.  fe_inv runs the same
+// instructions whatever the value, so the lanes of a wave stay together; it maps zero to zero.  Out of line: about 12 000 instructions,
+// one copy per code object instead of one per program loop that can meet an op 7.  A zero denominator is a compare of the canonical
+// value and a plain store of 1 to the flag word.
+__device__ __noinline__ inline fe air_quotient(fe num, fe den, int* __restrict__ zero_flag) {   // (by value: in registers, not through scratch)
+    if (fe_is_zero(den)) *zero_flag = 1;
+    return fe_mul(num, fe_inv(den));
+}
+
+// DIV = false leaves no test for op 7 either: every consumer but the chain kernel's DIV instantiations compiles the code it compiled
+// before, and zero_flag is not looked at.
+template <bool PER, bool DIV = false, class Load, class Periodic, class Out>
 __device__ __forceinline__ void air_run_program(const AirOpDev* __restrict__ ops, uint32_t n_ops, const fe* __restrict__ consts, Load load,
-                                                Periodic periodic, Out out) {
+                                                Periodic periodic, Out out, int* __restrict__ zero_flag = nullptr) {
     fe v[AIR_MAX_LIVE];
     for (uint32_t t = 0; t < n_ops; ++t) {
         const AirOpDev o = ops[t];
@@ -45,7 +56,12 @@ __device__ __forceinline__ void air_run_program(const AirOpDev* __restrict__ ops
             case 2: r = fe_add(v[o.a], v[o.b]); break;
             case 3: r = fe_sub(v[o.a], v[o.b]); break;
             case 4: r = fe_mul(v[o.a], v[o.b]); break;
-            default: out(o.a, v[o.b]); continue;
+            default:
+                if constexpr (DIV) {
+                    if (o.op == 7) { r = air_quotient(v[o.a], v[o.b], zero_flag); break; }
+                }
+                out(o.a, v[o.b]);
+                continue;
         }
         v[o.dst] = r;
     }

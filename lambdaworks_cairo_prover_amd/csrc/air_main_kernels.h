@@ -19,10 +19,14 @@ namespace sp {
 // state starts as zero; for each block of its run it runs the seed program on the block's first row - a LOAD of a group column is the
 // lane's state, the last row of the block before (the carry; zero on the run's first block), every other LOAD and op 6 as in the step
 // program - assigns the w seeds together, and then walks the block as above.  The two cases are instantiations of one kernel body.
+// zero_flag: null for a group whose programs hold no op 7 - it launches the instantiation it always launched.  Non-null (a word of
+// device memory, zeroed by the caller): the programs may hold op 7 DIV a b = v[a] / v[b], one fe_inv per lane and op; a lane that meets
+// a zero denominator stores 1 there (a plain store; every such lane stores the same word) and goes on with a quotient of zero, so all
+// its stores stay where they belong and the caller refuses the table once the stream has drained.
 constexpr uint32_t AIR_MAIN_CHAIN_WIDTH = 16;
 int air_main_chain(hipStream_t st, fe* trace, uint64_t n, uint32_t log_s, uint32_t log_k, uint32_t first_col, uint32_t w, const AirOpDev* seed_ops,
                    uint32_t n_seed, const AirOpDev* step_ops, uint32_t n_step, const fe* consts, const AirPeriodicCol* pcols = nullptr,
-                   const fe* pvals = nullptr);
+                   const fe* pvals = nullptr, int* zero_flag = nullptr);
 // One COUNT column (a lookup multiplicity): kx the n looked-up keys in ascending order, kt the n table keys in ascending order - sorted
 // stably, rows[p] the row that table key p came from - all from air_aux_sort_terms and radix_sort_pairs_u64.  One lane per p: on the
 // head of a run of equal table keys (p == 0 or kt[p] != kt[p - 1]) z = upper_bound(kx, kt[p]) - lower_bound(kx, kt[p]), elsewhere

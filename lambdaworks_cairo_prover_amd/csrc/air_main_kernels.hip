@@ -19,11 +19,16 @@ namespace sp {
 // the carry of a run's first block; after a block's last advance() it holds that block's last row, which is what the next seed
 // program's LOADs of the group read (from_state, not from_trace).  An instantiation of its own, not a run-time flag: a group without
 // runs (log_k = 0, which the unlinked instantiations do not read) launches the code it always launched.
-template <bool PER, bool LINKED>
+// DIV (a group whose seed or step program holds an op 7): the interpreter knows DIV, one fe_inv per lane and op - a step is then
+// dominated by its inversions, tens of microseconds each against well under one for a polynomial op -, and zero_flag is the word a
+// lane that meets a zero denominator stores 1 to.  An instantiation of its own too: zero_flag is not read without it, and a group
+// without an op 7 launches the code it always launched, whatever entry point its program came through.
+template <bool PER, bool LINKED, bool DIV>
 __global__ void __launch_bounds__(64) air_main_chain_kernel(fe* __restrict__ group, const fe* __restrict__ trace, uint64_t n, uint32_t log_s, uint32_t first_col,
                                                             uint32_t w, const AirOpDev* __restrict__ seed_ops, uint32_t n_seed,
                                                             const AirOpDev* __restrict__ step_ops, uint32_t n_step, const fe* __restrict__ consts,
-                                                            const AirPeriodicCol* __restrict__ pcols, const fe* __restrict__ pvals, uint32_t log_k) {
+                                                            const AirPeriodicCol* __restrict__ pcols, const fe* __restrict__ pvals, uint32_t log_k,
+                                                            int* __restrict__ zero_flag) {
     const uint32_t log_run = LINKED ? log_s + log_k : log_s;
     const uint64_t L = (uint64_t)blockIdx.x * 64 + threadIdx.x;
     if (L >= (n >> log_run)) return;   // (with fewer than 64 blocks or runs the only wave is partly empty)
@@ -44,8 +49,8 @@ __global__ void __launch_bounds__(64) air_main_chain_kernel(fe* __restrict__ gro
         }
     };
     auto run = [&](const AirOpDev* ops, uint32_t n_ops, auto load) {
-        if constexpr (PER) air_run_program<true>(ops, n_ops, consts, load, periodic, to_next);
-        else air_run_program<false>(ops, n_ops, consts, load, AirNoPeriodic{}, to_next);
+        if constexpr (PER) air_run_program<true, DIV>(ops, n_ops, consts, load, periodic, to_next, zero_flag);
+        else air_run_program<false, DIV>(ops, n_ops, consts, load, AirNoPeriodic{}, to_next, zero_flag);
     };
     auto block = [&](auto seed_load) {   // the seeds on the block's first row, then its s - 1 steps; leaves i on the block's last row
         run(seed_ops, n_seed, seed_load);
@@ -65,9 +70,11 @@ __global__ void __launch_bounds__(64) air_main_chain_kernel(fe* __restrict__ gro
     }
 }
 
-// log_k = 0: an unlinked group, one lane per block; log_k >= 1: runs of 2^log_k blocks, one lane per run.
+// log_k = 0: an unlinked group, one lane per block; log_k >= 1: runs of 2^log_k blocks, one lane per run.  zero_flag non-null: the
+// programs hold an op 7.
 int air_main_chain(hipStream_t st, fe* trace, uint64_t n, uint32_t log_s, uint32_t log_k, uint32_t first_col, uint32_t w, const AirOpDev* seed_ops,
-                   uint32_t n_seed, const AirOpDev* step_ops, uint32_t n_step, const fe* consts, const AirPeriodicCol* pcols, const fe* pvals) {
+                   uint32_t n_seed, const AirOpDev* step_ops, uint32_t n_step, const fe* consts, const AirPeriodicCol* pcols, const fe* pvals,
+                   int* zero_flag) {
     if (n == 0 || (n & (n - 1)) || log_s == 0 || log_s + log_k >= 64 || (1ull << (log_s + log_k)) > n || w == 0 || w > AIR_MAIN_CHAIN_WIDTH ||
         (pcols == nullptr) != (pvals == nullptr))
         return SP_E_INVALID_ARG;
@@ -75,10 +82,14 @@ int air_main_chain(hipStream_t st, fe* trace, uint64_t n, uint32_t log_s, uint32
     const dim3 grid((unsigned)((lanes + 63) / 64));
     fe* group = trace + (uint64_t)first_col * n;
     auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, grid, dim3(64), 0, st, group, trace, n, log_s, first_col, w, seed_ops, n_seed, step_ops, n_step, consts, pcols, pvals, log_k);
+        hipLaunchKernelGGL(kernel, grid, dim3(64), 0, st, group, trace, n, log_s, first_col, w, seed_ops, n_seed, step_ops, n_step, consts, pcols, pvals, log_k,
+                           zero_flag);
     };
-    if (log_k == 0) pcols ? launch(air_main_chain_kernel<true, false>) : launch(air_main_chain_kernel<false, false>);
-    else pcols ? launch(air_main_chain_kernel<true, true>) : launch(air_main_chain_kernel<false, true>);
+    if (zero_flag) {
+        if (log_k == 0) pcols ? launch(air_main_chain_kernel<true, false, true>) : launch(air_main_chain_kernel<false, false, true>);
+        else pcols ? launch(air_main_chain_kernel<true, true, true>) : launch(air_main_chain_kernel<false, true, true>);
+    } else if (log_k == 0) pcols ? launch(air_main_chain_kernel<true, false, false>) : launch(air_main_chain_kernel<false, false, false>);
+    else pcols ? launch(air_main_chain_kernel<true, true, false>) : launch(air_main_chain_kernel<false, true, false>);
     SP_HIP_CHECK(hipGetLastError());
     return SP_OK;
 }

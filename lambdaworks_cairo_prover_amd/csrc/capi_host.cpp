@@ -114,6 +114,9 @@ int sp_air_main_check_lk(const sp_air_desc* d, const sp_air_ext* ext, const sp_a
 int sp_air_main_check_link(const sp_air_desc* d, const sp_air_ext* ext, const sp_air_main_desc* mp, uint64_t n) {
     return air_main_check("sp_air_main_check_link", d, ext, sp::AirMainLevel::Link, mp, n);
 }
+int sp_air_main_check_div(const sp_air_desc* d, const sp_air_ext* ext, const sp_air_main_desc* mp, uint64_t n) {
+    return air_main_check("sp_air_main_check_div", d, ext, sp::AirMainLevel::Div, mp, n);
+}
 int sp_air_main_link_limits(uint32_t out[2]) {
     if (!out) return SP_E_INVALID_ARG;
     out[0] = sp::AIR_MAIN_LINK_MAX_LOG; out[1] = sp::AIR_MAIN_CHAIN_MAX_WIDTH;

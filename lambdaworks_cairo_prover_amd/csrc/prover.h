@@ -117,7 +117,9 @@ class StarkProver : public sp_deletable {
     // From st.main_level Rec on a chain group (SP_AIR_MAIN_CHAIN) is a chunk of its own, built by one launch of air_main_chain, and op 6
     // reads st.periodic, whose raw values go up with the program; at Link a group whose columns carry k >= 1 is that launch with a lane
     // per run.  From Lk on a COUNT column (SP_AIR_MAIN_COUNT) is a chunk of its own as well: two key passes, two radix sorts and
-    // air_main_count; a key out of range is SP_E_INVALID_ARG once the root is back, ahead of a zero denominator.
+    // air_main_count; a key out of range is SP_E_INVALID_ARG once the root is back, ahead of a zero denominator.  At Div a chain group
+    // whose slotted seed or step program still holds an op 7 launches the kernel's DIV instantiation with the context's flag word - a
+    // zero under a quotient is the same SP_E_ZERO_INVERSE -, every other group the instantiation it always launched.
     int commit_main_program(const AirStatement& st, const uint8_t* inputs, uint8_t root_out[32]);
     // the same table without the commitment, to host memory: row-major n x main_cols, context encoding (sp_air_main_trace)
     int main_program_table(const AirStatement& st, const uint8_t* inputs, uint8_t* rows_out);

@@ -17,21 +17,21 @@ static constexpr uint64_t AUXP_CHUNK_ELEMS = 1ull << 22;
 
 // The program `src` with an OUT behind every op whose value is wanted - outs[t]: the codes op t is stored under - (a value then lives
 // only until it is stored), slots by air_assign_slots (which drops what these OUTs do not need).  reads_periodic: an op 6 is among
-// what air_assign_slots kept, a table read that feeds one of these OUTs.
+// what air_assign_slots kept, a table read that feeds one of these OUTs; divides: an op 7 is among them, a quotient that does.
 static int program_with_outs(const std::vector<AirOpHost>& src, const std::vector<std::vector<uint32_t>>& outs, const char* live_error,
-                             std::vector<AirOpDev>& dev, bool& reads_periodic) {
+                             std::vector<AirOpDev>& dev, bool& reads_periodic, bool& divides) {
     std::vector<AirOpHost> ext;
     std::vector<uint32_t> at(src.size());
     for (size_t t = 0; t < src.size(); ++t) {
         AirOpHost o = src[t];
-        if (o.op >= 2 && o.op <= 4) { o.a = at[o.a]; o.b = at[o.b]; }   // (LOAD, CONST and PERIODIC name cells, not values)
+        if (air_op_takes_two_values(o.op)) { o.a = at[o.a]; o.b = at[o.b]; }   // (LOAD, CONST and PERIODIC name cells, not values)
         at[t] = (uint32_t)ext.size();
         ext.push_back(o);
         for (uint32_t code : outs[t]) ext.push_back(AirOpHost{5, code, at[t]});
     }
     SP_TRY(air_assign_slots(ext, dev, live_error));
-    reads_periodic = false;
-    for (const AirOpDev& o : dev) reads_periodic |= o.op == 6;
+    reads_periodic = divides = false;
+    for (const AirOpDev& o : dev) { reads_periodic |= o.op == 6; divides |= o.op == 7; }
     return SP_OK;
 }
 
@@ -90,7 +90,8 @@ int StarkProver::commit_aux_program(const AirStatement& st, const std::vector<fe
     const uint32_t n_src = (uint32_t)aux.ops.size();
     bool any_periodic = false;
     auto program = [&](const std::vector<std::vector<uint32_t>>& outs, std::vector<AirOpDev>& dev, bool& reads_periodic) -> int {
-        SP_TRY(program_with_outs(aux.ops, outs, "aux program: more than 64 values alive at once", dev, reads_periodic));
+        bool divides = false;   // (never: validate_aux_program knows no op 7)
+        SP_TRY(program_with_outs(aux.ops, outs, "aux program: more than 64 values alive at once", dev, reads_periodic, divides));
         any_periodic |= reads_periodic;
         return SP_OK;
     };
@@ -248,6 +249,7 @@ struct MainChunk {
     // Chain: a chain group (SP_AIR_MAIN_CHAIN), a chunk of its own that ends the chunk before it: the seeds' program and the steps',
     //   each with an OUT per group column, and one launch of air_main_chain - a lane per block, or per run of 2^log_k blocks of a
     //   linked group; nothing of the group is read before that launch is over, which the stream's order guarantees.  No workspace.
+    //   A group whose programs hold an op 7 (divides) hands the launch the zero-denominator flag the batch inversions share.
     // Count: a COUNT column (SP_AIR_MAIN_COUNT), a chunk of its own too: X's program and T's, each with the one OUT of a key pass; two
     //   launches of air_aux_sort_terms (keys out of Montgomery form, the row beside each), two radix sorts - the table's carries its
     //   rows - and one launch of air_main_count, which writes every cell of the column.  Its arrays (4 x [n] keys, 4 x [n] rows, the
@@ -266,6 +268,7 @@ struct MainChunk {
     size_t o_kinds = 0, o_den = 0, o_guard = 0, o_gtab = 0, o_etab = 0;
     // Chain
     uint32_t log_s = 0, log_k = 0;           // blocks of 2^log_s rows; log_k >= 1: runs of 2^log_k blocks
+    bool divides = false;                    // the slotted seed or step program holds an op 7: the launch takes the zero flag
     // Count
     uint32_t key_bits = 0;
 };
@@ -287,10 +290,16 @@ static int plan_main_program(const AirStatement& st, uint64_t n, MainPlan& P) {
     bool any_periodic = false;
     // (a chunk's programs share one flag)
     auto program = [&](const std::vector<std::vector<uint32_t>>& outs, MainChunk& ch, int which) -> int {
-        bool reads_periodic = false;
-        SP_TRY(program_with_outs(mp.ops, outs, "main program: more than 64 values alive at once", ch.prog[which], reads_periodic));
+        bool reads_periodic = false, divides = false;
+        SP_TRY(program_with_outs(mp.ops, outs, "main program: more than 64 values alive at once", ch.prog[which], reads_periodic, divides));
         ch.periodic |= reads_periodic;
         any_periodic |= reads_periodic;
+        // (only the chain kernel's DIV instantiations know op 7, and only the statement's level lets it in)
+        if (divides && (ch.kind != MainChunk::Kind::Chain || !air_main_allows_quotients(st.main_level))) {
+            sp_set_error("commit_main_program: op 7 outside a chain group's programs (the decoder should have refused it)");
+            return SP_E_INVALID_ARG;
+        }
+        ch.divides |= divides;
         return SP_OK;
     };
     for (uint32_t k0 = 0; k0 < K;) {
@@ -441,7 +450,7 @@ int StarkProver::build_main_program(const AirStatement& st, const uint8_t* input
         switch (ch.kind) {
         case MainChunk::Kind::Chain:
             SP_TRY(air_main_chain(c_->stream, d_trace_, n_, ch.log_s, ch.log_k, I + ch.k0, ch.kc, prog[MainChunk::SEED], n_prog[MainChunk::SEED], prog[MainChunk::STEP],
-                                  n_prog[MainChunk::STEP], consts_dev, pc, pv));
+                                  n_prog[MainChunk::STEP], consts_dev, pc, pv, ch.divides ? c_->d_flag : nullptr));
             break;
         case MainChunk::Kind::Count:   // key passes, sorts (the sorted pairs end up in keys / rows [1] and [3]), the join
             SP_TRY(air_aux_sort_terms(c_->stream, d_trace_, n_, prog[MainChunk::KEY_X], n_prog[MainChunk::KEY_X], consts_dev, nullptr, s.keys[0], s.rows[0], ch.key_bits, key_flag, pc, pv));

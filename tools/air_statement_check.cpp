@@ -45,7 +45,8 @@ struct Parts {
     sp_air_main_desc mp{};
     // a main program with a chain group (use 'r': through the _rec policy, 'R': without it): x the one input; a group of two in blocks of
     // four rows, seeds x and K (op 6), steps x0 x1 and x0 + K; then x0 one row ahead as a VALUE
-    sp_air_op rops[7] = {{0, 0, 0, 0, 0}, {6, 0, 0, 0, 0}, {0, 0, 0, 1, 0}, {0, 0, 0, 2, 0}, {4, 0, 2, 3, 0}, {2, 0, 2, 1, 0}, {0, 0, 1, 1, 0}};
+    // (ops 7 and 8, beyond n_ops until a case of the _div policy - use 'd' - asks for them: x / K, and a sum behind that quotient)
+    sp_air_op rops[9] = {{0, 0, 0, 0, 0}, {6, 0, 0, 0, 0}, {0, 0, 0, 1, 0}, {0, 0, 0, 2, 0}, {4, 0, 2, 3, 0}, {2, 0, 2, 1, 0}, {0, 0, 1, 1, 0}, {7, 0, 0, 1, 0}, {2, 0, 7, 7, 0}};
     sp_air_main_column rcols[3] = {{SP_AIR_MAIN_CHAIN, 4, 0, 2}, {SP_AIR_MAIN_CHAIN, 5, 1, 2 + 256}, {SP_AIR_MAIN_VALUE, 6, SP_AIR_AUX_NO_DEN, 0}};
     sp_air_main_desc rp{};
     // a main program with a lookup multiplicity (use 'l': through the _lk policy, 'L': through the _rec policy alone): x the one input;
@@ -80,19 +81,20 @@ struct Parts {
 
 // use: which parts go to the decoder (x p s b m r R l L, upper case P: the auxiliary program may read the periodic columns; m: the main
 // program, for which the AIR gets its six main columns first; r / R the chain program with and without the _rec policy; l / L the
-// lookup program under the _lk policy and under the _rec policy alone; k the chain program under the _link policy)
+// lookup program under the _lk policy and under the _rec policy alone; k the chain program under the _link policy; d the chain program
+// under the _div policy)
 void run(const char* label, const char* use, bool want_ok, const std::function<void(Parts&)>& patch) {
     Parts p;
     if (std::strchr(use, 'm')) p.with_main();
-    if (std::strchr(use, 'r') || std::strchr(use, 'R') || std::strchr(use, 'l') || std::strchr(use, 'L') || std::strchr(use, 'k')) p.with_chain();
+    if (std::strchr(use, 'r') || std::strchr(use, 'R') || std::strchr(use, 'l') || std::strchr(use, 'L') || std::strchr(use, 'k') || std::strchr(use, 'd')) p.with_chain();
     patch(p);
     auto has = [&](char c) { return std::strchr(use, c) != nullptr; };
     using sp::AirMainLevel;   // the highest level a use-letter implies wins
-    const AirMainLevel level = has('k') ? AirMainLevel::Link : has('l') ? AirMainLevel::Lk : has('r') || has('L') ? AirMainLevel::Rec : AirMainLevel::Main;
+    const AirMainLevel level = has('d') ? AirMainLevel::Div : has('k') ? AirMainLevel::Link : has('l') ? AirMainLevel::Lk : has('r') || has('L') ? AirMainLevel::Rec : AirMainLevel::Main;
     sp::AirStatement st;
     const std::string refused = sp::air_statement_from_c(&p.d, has('x') ? &p.aux : nullptr, has('p') ? &p.per : nullptr, has('s') ? &p.sd : nullptr,
                                                          has('b') ? &p.bv : nullptr, has('P'), 16, st,
-                                                         has('m') ? &p.mp : has('r') || has('R') || has('k') ? &p.rp : has('l') || has('L') ? &p.lp : nullptr,
+                                                         has('m') ? &p.mp : has('r') || has('R') || has('k') || has('d') ? &p.rp : has('l') || has('L') ? &p.lp : nullptr,
                                                          level);
     const bool ok = refused.empty();
     if (ok != want_ok) { ++failures; std::printf("FAIL %-44s wanted %s, got %s\n", label, want_ok ? "accepted" : "refused", ok ? "accepted" : refused.c_str()); return; }
@@ -101,12 +103,17 @@ void run(const char* label, const char* use, bool want_ok, const std::function<v
     // the model on what was accepted: stride plan and zerofier, periodic columns as polynomials, boundary values under a challenge
     sp::AirStridePlan plan;
     bool fine = sp::air_stride_plan(st.air, 16, plan) && st.aux.has_value() == has('x') && st.periodic.has_value() == has('p') && st.bvals.has_value() == has('b') &&
-                (st.aux_periodic() != nullptr) == (has('P') && has('p')) && st.main.has_value() == (has('m') || has('r') || has('l') || has('k')) &&
-                st.main_level == (has('k') ? AirMainLevel::Link : has('l') ? AirMainLevel::Lk : has('r') ? AirMainLevel::Rec : AirMainLevel::Main) && !st.unsupported;
+                (st.aux_periodic() != nullptr) == (has('P') && has('p')) && st.main.has_value() == (has('m') || has('r') || has('l') || has('k') || has('d')) &&
+                st.main_level == (has('d') ? AirMainLevel::Div : has('k') ? AirMainLevel::Link : has('l') ? AirMainLevel::Lk : has('r') ? AirMainLevel::Rec : AirMainLevel::Main) && !st.unsupported;
     if (st.main && has('l') && !has('r') && st.main->cols.size() == 3) {   // what the prover's chunking reads of a COUNT column
         const auto& c = st.main->cols;
         fine = fine && c[1].kind == SP_AIR_MAIN_COUNT && c[1].key_bits == p.lcols[1].pad && c[1].num_op == 3 && c[1].den_op == 1 && c[1].reads == 1 && c[0].key_bits == 0 &&
                c[2].key_bits == 0 && c[2].reads == 2;
+    }
+    if (st.main && has('d')) {   // what the prover's chunking reads behind a quotient: the ops as they came, reads through op 7
+        const auto& c = st.main->cols;
+        fine = fine && c.size() == 3 && st.main->ops.size() == p.rp.n_ops && c[0].kind == SP_AIR_MAIN_CHAIN && c[2].reads == 1;
+        for (uint32_t t = 0; t < p.rp.n_ops; ++t) fine = fine && st.main->ops[t].op == p.rops[t].op;
     }
     if (st.main && has('k')) {   // what the prover's chunking reads of a linked group: l, j and k apart
         const auto& c = st.main->cols;
@@ -303,6 +310,45 @@ int main() {
     run("link: k through the _rec policy", "pr", false, linked(1, 1));
     run("link: k through the _lk policy", "prl", false, linked(1, 1));
     run("link: op 6 without periodic columns", "k", false, none);
+    // ---- quotients behind chain seeds and steps (the _div policy): op 7 over earlier ops, and nowhere else
+    const auto step_divides = [](Parts& p) { p.rops[4].op = 7; };                                   // x0' = x0 / x1
+    const auto with_quotient = [](Parts& p) { p.rp.n_ops = 9; };                                    // ops 7 (x / K) and 8 (behind it) join
+    const auto third_is = [](uint32_t kind, uint32_t num_op, uint32_t den_op, uint32_t pad) {
+        return [=](Parts& p) { p.rp.n_ops = 9; p.rcols[2] = sp_air_main_column{kind, num_op, den_op, pad}; };
+    };
+    run("div: a chain program without op 7", "pd", true, none);
+    run("div: a chain program under the _lk letters too", "prld", true, none);
+    run("div: DIV in a step", "pd", true, step_divides);
+    run("div: DIV in a seed", "pd", true, [&](Parts& p) { with_quotient(p); p.rcols[0].den_op = 7; });
+    run("div: a quotient of a quotient", "pd", true, [&](Parts& p) { step_divides(p); p.rops[5] = sp_air_op{7, 0, 4, 1, 0}; });
+    run("div: one quotient behind two next values", "pd", true, [&](Parts& p) { step_divides(p); p.rops[5] = sp_air_op{2, 0, 4, 1, 0}; });
+    run("div: a DIV that nothing reaches", "pd", true, with_quotient);
+    run("div: a step behind a quotient", "pd", true, [&](Parts& p) { with_quotient(p); p.rcols[1].num_op = 8; });
+    run("div: DIV in a linked seed beside a carry", "pd", true, [&](Parts& p) { carried(1)(p); with_quotient(p); p.rcols[0].den_op = 7; });
+    run("div: beside everything", "xpsbPd", true, [&](Parts& p) { p.aux.n_ops = 4; step_divides(p); });
+    run("div: a VALUE that is a quotient", "pd", false, third_is(SP_AIR_MAIN_VALUE, 7, SP_AIR_AUX_NO_DEN, 0));
+    run("div: a VALUE behind a quotient", "pd", false, third_is(SP_AIR_MAIN_VALUE, 8, SP_AIR_AUX_NO_DEN, 0));
+    run("div: a VALUE whose D is a quotient", "pd", false, third_is(SP_AIR_MAIN_VALUE, 0, 7, 0));
+    run("div: an INV_OR_ZERO behind a quotient", "pd", false, third_is(SP_AIR_MAIN_INV_OR_ZERO, 8, SP_AIR_AUX_NO_DEN, 0));
+    run("div: a BIT behind a quotient", "pd", false, third_is(SP_AIR_MAIN_BIT, 8, SP_AIR_AUX_NO_DEN, 3));
+    run("div: a SUM behind a quotient", "pd", false, third_is(SP_AIR_MAIN_SUM, 8, SP_AIR_AUX_NO_DEN, 0));
+    run("div: a PRODUCT whose D is a quotient", "pd", false, third_is(SP_AIR_MAIN_PRODUCT, 0, 8, 0));
+    run("div: a COUNT whose X is behind a quotient", "pd", false, third_is(SP_AIR_MAIN_COUNT, 8, 0, 16));
+    run("div: a COUNT whose T is behind a quotient", "pd", false, third_is(SP_AIR_MAIN_COUNT, 0, 8, 16));
+    run("div: operand is itself", "pd", false, [](Parts& p) { p.rops[4] = sp_air_op{7, 0, 4, 3, 0}; });
+    run("div: operand is later", "pd", false, [](Parts& p) { p.rops[4] = sp_air_op{7, 0, 2, 5, 0}; });
+    run("div: operand beyond the program", "pd", false, [](Parts& p) { p.rops[4] = sp_air_op{7, 0, 2, 9, 0}; });
+    run("div: op 8", "pd", false, [](Parts& p) { p.rops[4].op = 8; });
+    run("div: OUT", "pd", false, [](Parts& p) { p.rops[4].op = 5; });
+    run("div: op 6 without periodic columns", "d", false, none);
+    run("div: DIV in a step through the _link policy", "pk", false, step_divides);
+    run("div: DIV in a step through the _lk policy", "prl", false, step_divides);
+    run("div: DIV in a step through the _rec policy", "pr", false, step_divides);
+    run("div: DIV in a step without any policy", "pR", false, step_divides);
+    run("div: a DIV that nothing reaches through the _link policy", "pk", false, with_quotient);
+    run("div: a DIV that nothing reaches through the _rec policy", "pr", false, with_quotient);
+    run("aux: op 7", "x", false, [](Parts& p) { p.aux_ops[2].op = 7; });
+    run("aux: op 7 through the _div policy", "xpd", false, [](Parts& p) { p.aux_ops[2].op = 7; });
     run("no main column", "", false, [](Parts& p) { p.d.main_cols = 0; p.ops[2] = sp_air_op{1, 0, 0, 0, 0}; });
     run("1025 columns", "", false, [](Parts& p) { p.d.main_cols = 1024; p.ops[2] = sp_air_op{1, 0, 0, 0, 0}; });
     std::printf("%s\n", failures ? "FAILED" : "all verdicts as expected");
