@@ -82,7 +82,8 @@ const char* sp_version(void);
  * sp_air_main_trace, sp_air_main_check and sp_air_main_desc_size, then sp_air_prove_rec, sp_air_check_trace_rec, sp_air_main_trace_rec,
  * sp_air_main_check_rec and sp_air_main_chain_limits, then sp_air_prove_lk, sp_air_check_trace_lk, sp_air_main_trace_lk, sp_air_main_check_lk
  * and sp_air_main_count_limits, then sp_air_prove_link, sp_air_check_trace_link, sp_air_main_trace_link, sp_air_main_check_link and
- * sp_air_main_link_limits, and last sp_air_prove_div, sp_air_check_trace_div, sp_air_main_trace_div and sp_air_main_check_div).  A binding compares it (and sp_air_desc_size against its own idea of the struct) when it loads the library, so
+ * sp_air_main_link_limits, then sp_air_prove_div, sp_air_check_trace_div, sp_air_main_trace_div and sp_air_main_check_div, and last
+ * sp_air_prove_fetch, sp_air_check_trace_fetch, sp_air_main_trace_fetch, sp_air_main_check_fetch and sp_air_main_fetch_limits).  A binding compares it (and sp_air_desc_size against its own idea of the struct) when it loads the library, so
  * a stale build fails at load time with "rebuild the library" instead of with a missing symbol or shifted fields later. */
 #define SP_ABI_VERSION 7
 int sp_abi_version(void);
@@ -774,6 +775,39 @@ int sp_air_check_trace_div(sp_ctx* ctx, const sp_air_desc* air, const sp_air_ext
 int sp_air_main_trace_div(sp_ctx* ctx, const sp_air_desc* air, const sp_air_ext* ext, const sp_air_main_desc* main, const void* inputs, uint64_t n,
                           uint8_t* rows_out);
 int sp_air_main_check_div(const sp_air_desc* air, const sp_air_ext* ext, const sp_air_main_desc* main, uint64_t n);
+
+/* ---- Looked-up values in a main program: the result of a lookup - c = a xor b as "the third field of the table row whose first two
+ * are a, b", the word at a program counter, a read from read-only memory - is a join of the looked-up key against the table, as the
+ * multiplicity of the same lookup is, and so no row-local kind.  Through the _fetch entry points - and only through them: everywhere
+ * else kind 7 stays an unknown kind - a main program may hold columns of kind */
+#define SP_AIR_MAIN_FETCH       7  /* z_i = V(j*), j* the lowest row j with T(j) = X(i)                                                     */
+/* num_op names the looked-up key X, den_op the table key T (SP_AIR_AUX_NO_DEN is refused: a FETCH needs a table key), and pad =
+ * key_bits + 256 v_op: key_bits (bits 0 - 7) in 1 .. 64, v_op (bits 8 - 23) the op whose value is the table value V; a bit at or above
+ * 24 is refused.  X, T and V are ordinary values of the program, evaluated on every row: inputs, earlier derived columns at shifts
+ * 0 .. 7 (wrapping) and periodic columns (op 6).  The canonical integers of X(i) and T(j) must be below 2^key_bits on every row -
+ * otherwise SP_E_INVALID_ARG with the COUNT columns' "a lookup key is out of range on some row", reported first -; V is a full field
+ * element.  Equal table keys: the lowest row wins, the row a COUNT column puts the key's multiplicity on.  A key X(i) that no row of T
+ * holds fails the call with SP_E_INVALID_ARG, "a fetched key is in no table row" (a COUNT column lets such a value pass and the proof
+ * fail; a FETCH has no value to write): nothing is returned and the context goes on, and a caller with idle rows points them at a key
+ * the table holds.  It is reported behind the key range and before a zero denominator of the same program.  n < 2^32.  Consecutive
+ * FETCH columns with one X, one T and one key_bits that read nothing of each other - the fields of an instruction word, several
+ * outputs of one table - share one sort of the table and one search (at most 16 columns at a time); the values are those of the
+ * columns taken one by one.  A tuple key is packed on both sides.  The _fetch entry points accept everything the _div ones do; they
+ * refuse, with SP_E_INVALID_ARG and a message that names the column, before anything is sized: a pad with a bit at or above 24, a
+ * FETCH column without a table key, key_bits 0 or above 64, X, T or v_op beyond the program, X, T or V behind an op 7 or reading a
+ * column that is not an earlier one, more than 64 FETCH columns in one program.  The proof is unchanged: the same table gives the same
+ * bytes.  Argument lists as the _div entry points. */
+int sp_air_prove_fetch(sp_ctx* ctx, const sp_air_desc* air, const sp_air_ext* ext, const sp_air_boundary_desc* bvals, const sp_air_main_desc* main,
+                       const void* inputs, uint64_t n, const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len);
+int sp_air_check_trace_fetch(sp_ctx* ctx, const sp_air_desc* air, const sp_air_ext* ext, const sp_air_boundary_desc* bvals, const sp_air_main_desc* main,
+                             const void* inputs, uint64_t n, const sp_proof_options* opt, const uint8_t* rap, sp_air_violation* out, uint32_t cap,
+                             uint32_t* n_out);
+int sp_air_main_trace_fetch(sp_ctx* ctx, const sp_air_desc* air, const sp_air_ext* ext, const sp_air_main_desc* main, const void* inputs, uint64_t n,
+                            uint8_t* rows_out);
+int sp_air_main_check_fetch(const sp_air_desc* air, const sp_air_ext* ext, const sp_air_main_desc* main, uint64_t n);
+/* out[0] = the most key bits of a FETCH column (64), out[1] = the most FETCH columns that share one sort and one search (16), out[2] =
+ * the most FETCH columns of one main program (64) */
+int sp_air_main_fetch_limits(uint32_t out[3]);
 
 /* verify::<Stark252PrimeField, A> (reference src/starks/verifier.rs:559-657) on the host CPU: 1 accept, 0 reject (also for
  * malformed proofs or descriptors). */

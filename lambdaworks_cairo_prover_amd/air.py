@@ -212,6 +212,8 @@ MAIN_MAX_BIT = 251
 MAIN_CHAIN_MAX_WIDTH = 16            # sp_air_main_chain_limits
 MAIN_COUNT_MAX_KEY_BITS, MAIN_COUNT_MAX_COLS = 64, 16   # sp_air_main_count_limits
 MAIN_LINK_MAX_LOG, MAIN_LINK_MAX_WIDTH = 62, 16         # sp_air_main_link_limits
+MAIN_FETCH = SP_AIR_MAIN_FETCH = 7                      # sp_air_main_column.kind of a looked-up value (the _fetch entry points)
+MAIN_FETCH_MAX_KEY_BITS, MAIN_FETCH_MAX_GROUP, MAIN_FETCH_MAX_COLS = 64, 16, 64   # sp_air_main_fetch_limits
 INPUTS_HOST, INPUTS_DEVICE = 0, 1    # sp_air_main_desc.input_location
 
 
@@ -312,10 +314,21 @@ def needs_div(desc):
     return bool(main.ops) and any(main.ops[i].op == OP_DIV for i in range(main.n_ops))
 
 
+def needs_fetch(desc):
+    """Whether a built descriptor's main program needs the _fetch entry points: it has a FETCH column (kind 7), a looked-up value."""
+    main = getattr(desc, "main_desc", None)
+    if main is None:
+        return False
+    known = getattr(desc, "main_needs_fetch", None)   # (AirBuilder.build() says so; a descriptor put together by hand is looked through)
+    if known is not None:
+        return known
+    return bool(main.cols) and any(main.cols[k].kind == MAIN_FETCH for k in range(main.n_cols))
+
+
 def main_suffix(desc):
-    """The entry points a descriptor's main program goes through: "div", "link", "lk", "rec" or "main" - the newer ones only where it
-    needs them."""
-    return "div" if needs_div(desc) else "link" if needs_link(desc) else "lk" if needs_lk(desc) else "rec" if needs_rec(desc) else "main"
+    """The entry points a descriptor's main program goes through: "fetch", "div", "link", "lk", "rec" or "main" - the newer ones only
+    where it needs them."""
+    return "fetch" if needs_fetch(desc) else "div" if needs_div(desc) else "link" if needs_link(desc) else "lk" if needs_lk(desc) else "rec" if needs_rec(desc) else "main"
 
 
 def route(desc, call):
@@ -325,8 +338,8 @@ def route(desc, call):
     verifier takes no auxiliary program).  A descriptor with a main-trace program (desc.main_desc) is proved and checked through the
     _main entry points, which take everything the _pub ones do - through the _rec ones when it holds a chain column or reads a
     periodic column (needs_rec), through the _lk ones when it holds a lookup multiplicity (needs_lk), through the _link ones when a
-    chain group links its blocks into runs (needs_link), through the _div ones when a seed or a step divides (needs_div) -; it is
-    verified as if it had none."""
+    chain group links its blocks into runs (needs_link), through the _div ones when a seed or a step divides (needs_div), through the
+    _fetch ones when it holds a looked-up value (needs_fetch) -; it is verified as if it had none."""
     def ref(part):
         return None if part is None else ctypes.byref(part)
     aux, per = getattr(desc, "aux_desc", None), getattr(desc, "periodic_desc", None)
@@ -659,7 +672,17 @@ class MainProgram:
         multiplicity(X, T, key_bits)   z_i = #{ j : X(j) = T(i) } on the first row i that holds the table value T(i), 0 on its later
                                        rows: the column m of a LogUp lookup of X into the table T.  X and T are values of this
                                        program whose canonical integers stay below 2^key_bits (1 .. 64) on every row; a tuple is
-                                       packed on both sides.  At most 16 such columns."""
+                                       packed on both sides.  At most 16 such columns.
+
+    The looked-up result itself (sp_air_prove_fetch) is the same join read the other way:
+
+        fetch(X, T, V, key_bits)       a column z_i = V(j*), j* the lowest row j with T(j) = X(i): the result of a lookup of the key X
+                                       into the table whose row j holds the key T(j) and the value V(j) - c = a xor b, the word at a
+                                       program counter, a read from read-only memory.  X and T as for multiplicity; V is any value.
+                                       Returns the column as a Value (a load at shift 0).  A key that no table row holds fails the
+                                       call (SP_E_INVALID_ARG; ValueError in evaluate): idle rows point at a key the table holds.
+        fetch_many(X, T, [V...], key_bits)   one column per V, declared as one run: the device sorts the table and searches once for
+                                       up to 16 of them - the fields of an instruction word.  At most 64 FETCH columns."""
 
     def __init__(self, input_cols, main_cols, periodic_cols=()):
         if not 1 <= input_cols < main_cols:
@@ -672,6 +695,7 @@ class MainProgram:
         self.lookups = False                 # multiplicity() was called: check() mirrors the decoder of the _lk entry points
         self.links = False                   # chain(link > 1) was called: check() mirrors the decoder of the _link entry points
         self.divs = False                    # div() was called: check() mirrors the decoder of the _div entry points
+        self.fetches = False                 # fetch() was called: check() mirrors the decoder of the _fetch entry points
 
     def _emit(self, op, a, b):
         self.ops.append((op, a, b))
@@ -789,6 +813,32 @@ class MainProgram:
         self.lookups = True
         return self._column(MAIN_COUNT, x, table, key_bits)
 
+    def fetch(self, x, table_key, table_value, key_bits=64):
+        """The value of the table row whose key is x (see the class): a FETCH column; returns it as a Value."""
+        return self.fetch_many(x, table_key, [table_value], key_bits)[0]
+
+    def fetch_many(self, x, table_key, table_values, key_bits=64):
+        """One FETCH column per table value, as one run that shares x, table_key and key_bits; returns the columns as Values."""
+        if table_key is None:
+            raise ValueError("main program: a fetch needs a table key")
+        if not 1 <= key_bits <= MAIN_FETCH_MAX_KEY_BITS:
+            raise ValueError(f"main program: key_bits {key_bits} outside 1 .. {MAIN_FETCH_MAX_KEY_BITS}")
+        table_values = list(table_values)
+        if not table_values:
+            raise ValueError("main program: a fetch needs at least one table value")
+        if sum(1 for c in self.cols if c[0] == MAIN_FETCH) + len(table_values) > MAIN_FETCH_MAX_COLS:
+            raise ValueError(f"main program: more than {MAIN_FETCH_MAX_COLS} fetched columns")
+        x = x if isinstance(x, Value) else self.const(x)
+        table_key = table_key if isinstance(table_key, Value) else self.const(table_key)
+        values = [v if isinstance(v, Value) else self.const(v) for v in table_values]
+        if any(v.b is not self for v in values):
+            raise ValueError("main program: the table values of a fetch must be values of this program")
+        if max(v.i for v in values) >= 1 << 16:
+            raise ValueError("main program: the table value of a fetch must be one of the program's first 65536 ops (v_op rides in 16 bits of the pad)")
+        self.fetches = True
+        cols = [self._column(MAIN_FETCH, x, table_key, key_bits + 256 * v.i) for v in values]
+        return [self.load(0, c) for c in cols]
+
     def reads(self):
         """Per op: one more than the highest derived column its value depends on (0: inputs only) - what the decoder follows."""
         return self._reads(False)
@@ -809,7 +859,7 @@ class MainProgram:
             quot.append(op == OP_DIV or (op in _TWO_VALUES and (quot[a] or quot[b])))
         return quot
 
-    def check(self, n=None, lookups=None, links=None, divs=None):
+    def check(self, n=None, lookups=None, links=None, divs=None, fetches=None):
         """The decoder's rules (air_statement_from_c), for a program whose lists were filled by hand too: ValueError naming the first one
         broken.  n: the trace length a chain group's block length is held against (None: not yet known).  lookups: whether COUNT
         columns are known - the decoder of the _lk entry points, where the program would be routed after multiplicity() declared one
@@ -817,12 +867,15 @@ class MainProgram:
         column's pad is known - the decoder of the _link entry points, where the program would be routed after chain(link > 1) declared
         a linked group (None: self.links), which knows COUNT columns too; otherwise the bits at and above 16 belong to j.  divs:
         whether op 7 is known - the decoder of the _div entry points, where the program would be routed after div() emitted one (None:
-        self.divs), which knows linked groups too; otherwise op 7 is a malformed op."""
-        divs = self.divs if divs is None else divs
+        self.divs), which knows linked groups too; otherwise op 7 is a malformed op.  fetches: whether FETCH columns are known - the
+        decoder of the _fetch entry points, where the program would be routed after fetch() declared one (None: self.fetches), which
+        knows quotients too; otherwise kind 7 is an unknown kind."""
+        fetches = self.fetches if fetches is None else fetches
+        divs = (self.divs if divs is None else divs) or fetches
         links = (self.links if links is None else links) or divs
         lookups = (self.lookups if lookups is None else lookups) or links
         pos = (lambda pad: (pad >> 8) & 255) if links else (lambda pad: pad >> 8)
-        n_count = 0
+        n_count = n_fetch = 0
         if self._open is not None:
             raise ValueError("main program: a chain group is open: g.step([...]) closes it")
         if self.input_cols < 1 or not self.cols or self.input_cols + len(self.cols) != self.main_cols:
@@ -843,8 +896,29 @@ class MainProgram:
         g0 = g_end = 0      # the chain group that column k belongs to is [g0, g_end), when k < g_end
         for k, (kind, num_op, den_op, pad) in enumerate(self.cols):
             den = den_op != AUX_NO_DEN
-            if not MAIN_VALUE <= kind <= (MAIN_COUNT if lookups else MAIN_CHAIN):
+            if not MAIN_VALUE <= kind <= (MAIN_FETCH if fetches else MAIN_COUNT if lookups else MAIN_CHAIN):
                 raise ValueError(f"main program: derived column {k} has an unknown kind")
+            if kind == MAIN_FETCH:
+                key_bits, v_op = pad & 255, (pad >> 8) & 65535
+                if pad >> 24:
+                    raise ValueError(f"main program: derived column {k} is a FETCH column whose pad has a bit at or above 24 (pad = key_bits + 256 v_op)")
+                if not den:
+                    raise ValueError(f"main program: derived column {k} is a FETCH column without a table key (den_op names the table key)")
+                if not 1 <= key_bits <= MAIN_FETCH_MAX_KEY_BITS:
+                    raise ValueError(f"main program: derived column {k} is a FETCH column with key_bits = {key_bits} (1 .. {MAIN_FETCH_MAX_KEY_BITS})")
+                if not (0 <= num_op < len(self.ops) and 0 <= den_op < len(self.ops)):
+                    raise ValueError(f"main program: derived column {k} names an op beyond the program")
+                if v_op >= len(self.ops) or self.ops[v_op][0] == OP_OUT:
+                    raise ValueError(f"main program: derived column {k} is a FETCH column with v_op = {v_op}, which is beyond the program or an OUT")
+                if quot[num_op] or quot[den_op] or quot[v_op]:
+                    raise ValueError(f"main program: derived column {k} {refused}")
+                r = max(reads[num_op], reads[den_op], reads[v_op])
+                if r > k:
+                    raise ValueError(f"main program: derived column {k} reads derived column {r - 1}, which is not an earlier one")
+                n_fetch += 1
+                if n_fetch > MAIN_FETCH_MAX_COLS:
+                    raise ValueError(f"main program: derived column {k} is the program's FETCH column number {n_fetch} (at most {MAIN_FETCH_MAX_COLS})")
+                continue
             if kind == MAIN_COUNT:
                 if not den:
                     raise ValueError(f"main program: derived column {k} is a COUNT column without a table (den_op names the table value)")
@@ -919,7 +993,9 @@ class MainProgram:
         group is a loop over the rows t of a block, each step vectorised over the n / period blocks; a linked group a loop over the
         blocks of a run and the rows of each, vectorised over the runs, the carry zero in front of each run.  A quotient (op 7) is one
         batch inversion per op and step, over the blocks or runs; ValueError on a zero under one that a seed or a step reaches.  A COUNT
-        column is a dictionary count of X, read on the first row of each table value; ValueError on a key at or above 2^key_bits."""
+        column is a dictionary count of X, read on the first row of each table value; ValueError on a key at or above 2^key_bits.  A
+        FETCH column is a dictionary from each table key to the first row that holds it; ValueError on a key out of range (the COUNT
+        columns' words) or on a looked-up key that no row holds."""
         import numpy as np
         self.check(len(input_rows))
         rows = input_rows if not isinstance(input_rows, np.ndarray) else input_rows.astype(object)
@@ -998,7 +1074,7 @@ class MainProgram:
         periodic = [np.array(values, dtype=object) for values in self.periodic_cols]
         for k, (kind, num_op, den_op, pad) in enumerate(self.cols):
             if kind == MAIN_CHAIN:
-                linked = self.links or self.divs    # (the _div entry points read the k of a pad as the _link ones do)
+                linked = self.links or self.divs or self.fetches    # (the _div and _fetch entry points read the k of a pad as the _link ones do)
                 pos = (lambda pad: (pad >> 8) & 255) if linked else (lambda pad: pad >> 8)
                 if pos(pad):
                     continue            # (built with its group, at the column that opens it)
@@ -1028,6 +1104,18 @@ class MainProgram:
                 for i, v in enumerate(ts):
                     col[i] = 0 if v in seen else counts.get(v, 0)
                     seen.add(v)
+                continue
+            if kind == MAIN_FETCH:
+                key_bits = pad & 255
+                xs, ts, vs = [int(v) for v in need(num_op)], [int(v) for v in need(den_op)], need((pad >> 8) & 65535)
+                if any(v >> key_bits for v in xs) or any(v >> key_bits for v in ts):
+                    raise ValueError("main program: a lookup key is out of range on some row")
+                first = {}
+                for j, v in enumerate(ts):
+                    first.setdefault(v, j)
+                if any(v not in first for v in xs):
+                    raise ValueError("main program: a fetched key is in no table row")
+                m[:, self.input_cols + k] = [vs[first[v]] for v in xs]
                 continue
             t = need(num_op)
             if den_op != AUX_NO_DEN:
@@ -1495,6 +1583,7 @@ class AirBuilder:
             d.main_needs_lk = any(c[0] == MAIN_COUNT for c in self.main.cols)
             d.main_needs_link = self.main.links and any(c[0] == MAIN_CHAIN and c[3] >> 16 for c in self.main.cols)
             d.main_needs_div = any(op == OP_DIV for op, _, _ in self.main.ops)
+            d.main_needs_fetch = self.main.fetches and any(c[0] == MAIN_FETCH for c in self.main.cols)
             keep = keep + (m_desc, m_keep)
         return d, keep
 
@@ -2084,6 +2173,86 @@ def xor_lookup_inputs(n, bits, rng):
         a, b = rng.randrange(1 << bits), rng.randrange(1 << bits)
         rows.append([a, b, a ^ b])
     return rows
+
+
+# ---- looked-up values: two worked examples ----------------------------------------------------------------------------------------
+def xor_fetch(n, bits=4):
+    """xor_lookup with main_inputs=2 (sp_air_prove_fetch): the caller uploads a and b alone, and the device fetches c = a xor b as the
+    value of the table row whose key is a + 2^bits b - periodic column 1 holds the keys, periodic column 2 the values, both in the order
+    of xor_lookup_table (periodic column 0, which the statement reads as before).  Behind it the statement of xor_lookup unchanged: m =
+    multiplicity over the packed triple and the LogUp sum.  The same trace and the same proof as xor_lookup from [a, b, a xor b].  An a
+    or b of more than `bits` bits packs to a key of more than 2 bits bits or to no table row, and the call is refused."""
+    table = xor_lookup_table(bits)
+    if len(table) > n:
+        raise ValueError(f"xor_fetch: {len(table)} table entries on {n} rows")
+    keys = [a + (b << bits) for b in range(1 << bits) for a in range(1 << bits)]
+    values = [a ^ b for b in range(1 << bits) for a in range(1 << bits)]
+    b = AirBuilder(4, [0, 1], 2, aux_cols=1, n_rap=1, aux_kind=AUX_PROGRAM, periodic=[table, keys, values], main_inputs=2)
+    m = b.main
+    m.fetch(m.load(0, 0) + m.load(0, 1) * (1 << bits), m.periodic(0, 1), m.periodic(0, 2), 2 * bits)
+
+    def packed(load):
+        return load(0, 0) + load(0, 1) * (1 << bits) + load(0, 2) * (1 << (2 * bits))
+
+    m.multiplicity(packed(m.load), m.periodic(0, 0), 3 * bits)
+    _logup_sum(b, packed(b.load), packed(b.aux.load), 3, 4)
+    return b
+
+
+def xor_fetch_inputs(n, bits, rng):
+    """(n, 2) Python ints [a, b]: the first two columns of xor_lookup_inputs under the same rng."""
+    return [r[:2] for r in xor_lookup_inputs(n, bits, rng)]
+
+
+def rom_reads(n, key_bits=64):
+    """n reads from a read-only memory of n cells, one write and one read a row (Cairo's access pattern for its program segment and
+    its public memory).  Inputs: the written address addr_w (column 0), the written value val_w (column 1) and the read address addr_r
+    (column 2), addresses below 2^key_bits.  The device builds val_r = fetch(addr_r, addr_w, val_w) (column 3) and m =
+    multiplicity(addr_r, addr_w) (column 4); the auxiliary column 5 is one LogUp sum over (address, value) pairs compressed with a
+    second challenge: s_0 = 0, s' = s + m / (gamma - addr_w - alpha val_w) - 1 / (gamma - addr_r - alpha val_r), degree 3 with no
+    exempted row, so that row n - 1 wraps to s_0 = 0 and closes the sum.  The written addresses must be DISTINCT for the statement to
+    mean a memory: of two rows that write one address the lowest is the one every read fetches and the one that carries the
+    multiplicity, and the sum says nothing about the other."""
+    b = AirBuilder(5, [0, 1], 2, aux_cols=1, n_rap=2, aux_kind=AUX_PROGRAM, main_inputs=3)
+    m = b.main
+    m.fetch(m.load(0, 2), m.load(0, 0), m.load(0, 1), key_bits)
+    m.multiplicity(m.load(0, 2), m.load(0, 0), key_bits)
+    gamma, alpha = b.rap(0), b.rap(1)
+    dw, dr = gamma - b.load(0, 0) - alpha * b.load(0, 1), gamma - b.load(0, 2) - alpha * b.load(0, 3)
+    b.constraint((b.load(1, 5) - b.load(0, 5)) * dw * dr - b.load(0, 4) * dr + dw, degree=3, exemptions=0)
+    b.boundary(5, 0, 0)
+    g, a = b.aux.rap(0), b.aux.rap(1)
+    xw, xr = g - b.aux.load(0, 0) - a * b.aux.load(0, 1), g - b.aux.load(0, 2) - a * b.aux.load(0, 3)
+    b.aux.running_sum(b.aux.load(0, 4) * xr - xw, xw * xr)
+    return b
+
+
+def rom_reads_inputs(n, key_bits, rng):
+    """(n, 3) Python ints [addr_w, val_w, addr_r]: n distinct addresses below 2^key_bits in a shuffled order, values from the whole
+    field, and reads of addresses that were written - some of them several times, some never."""
+    if key_bits < 64 and (1 << key_bits) < n:
+        raise ValueError(f"rom_reads_inputs: {n} distinct addresses need more than {key_bits} key bits")
+    if (1 << key_bits) <= 4 * n:
+        addrs = list(range(1 << key_bits))
+        rng.shuffle(addrs)
+        addrs = addrs[:n]
+    else:
+        seen = set()
+        while len(seen) < n:
+            seen.add(rng.randrange(1 << key_bits))
+        addrs = sorted(seen)
+        rng.shuffle(addrs)
+    return [[addrs[i], rng.randrange(P), addrs[rng.randrange(max(1, n // 2))]] for i in range(n)]
+
+
+def rom_reads_trace(inputs):
+    """The whole main table of rom_reads as (n, 5) Python ints, from rom_reads_inputs' rows: a dictionary read and a count."""
+    first, counts = {}, {}
+    for j, (addr_w, val_w, addr_r) in enumerate(inputs):
+        first.setdefault(addr_w, j)
+        counts[addr_r] = counts.get(addr_r, 0) + 1
+    return [[addr_w, val_w, addr_r, inputs[first[addr_r]][1], counts.get(addr_w, 0) if first[addr_w] == j else 0]
+            for j, (addr_w, val_w, addr_r) in enumerate(inputs)]
 
 
 # ---- quotients in chain steps: a worked example -----------------------------------------------------------------------------------

@@ -244,7 +244,8 @@ class Context:
         A program with a chain column or a read of a periodic column (air.needs_rec) goes to sp_air_main_trace_rec with the
         descriptor's sp_air_ext, which carries the periodic columns; one with a lookup multiplicity (air.needs_lk) to
         sp_air_main_trace_lk, one with a linked chain group (air.needs_link) to sp_air_main_trace_link, one with a quotient (op 7) behind
-        a chain group (air.needs_div) to sp_air_main_trace_div, with the same arguments."""
+        a chain group (air.needs_div) to sp_air_main_trace_div, one with a looked-up value (air.needs_fetch) to sp_air_main_trace_fetch,
+        with the same arguments."""
         main = getattr(desc, "main_desc", None)
         if main is None:
             raise ValueError("air_main_trace: the descriptor carries no main program (AirBuilder(..., main_inputs=...))")
@@ -570,7 +571,7 @@ def air_main_check(desc, n, main=None):
     SpError with its refusal (SP_E_INVALID_ARG, or SP_E_UNSUPPORTED beside aux_kind 1 or 2).  A program with a chain column or a read of
     a periodic column (air.needs_rec) is judged by sp_air_main_check_rec, beside the descriptor's periodic columns; one with a lookup
     multiplicity (air.needs_lk) by sp_air_main_check_lk, one with a linked chain group (air.needs_link) by sp_air_main_check_link, one
-    with a quotient (air.needs_div) by sp_air_main_check_div."""
+    with a quotient (air.needs_div) by sp_air_main_check_div, one with a looked-up value (air.needs_fetch) by sp_air_main_check_fetch."""
     from . import air
     own = getattr(desc, "main_desc", None)
     main = own if main is None else main
@@ -594,6 +595,14 @@ def air_main_link_limits():
     out = (ctypes.c_uint32 * 2)()
     check(_lib.load().sp_air_main_link_limits(out))
     return {"link_log": int(out[0]), "width": int(out[1])}
+
+
+def air_main_fetch_limits():
+    """sp_air_main_fetch_limits: {"key_bits": the most key bits of a FETCH column, "group": the most FETCH columns that share one sort and
+    one search, "columns": the most FETCH columns of one main program}."""
+    out = (ctypes.c_uint32 * 3)()
+    check(_lib.load().sp_air_main_fetch_limits(out))
+    return {"key_bits": int(out[0]), "group": int(out[1]), "columns": int(out[2])}
 
 
 def air_main_count_limits():

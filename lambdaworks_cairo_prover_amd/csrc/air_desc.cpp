@@ -157,10 +157,12 @@ std::string validate_aux_program(const AirAuxHost& aux, uint32_t main_cols, uint
 // _link entry points, with lk): a CHAIN column's pad is l + 256 j + 65536 k, runs of 2^k blocks; with k >= 1 a seed may load its own
 // group at shift 0; without link j = pad >> 8, so a pad with bits at or above 16 is a j out of sequence.  div (the _div entry points,
 // with link): op 7 DIV over earlier ops, behind the seeds and steps of CHAIN columns only; a column of any other kind that depends on
-// one is refused, and without div op 7 is a malformed op.
+// one is refused, and without div op 7 is a malformed op.  fetch (the _fetch entry points, with div): SP_AIR_MAIN_FETCH columns too - a
+// table key, pad = key_bits (1 .. 64) + 256 v_op below 2^24, X, T and V over earlier columns and behind no op 7, at most 64 of them;
+// without fetch kind 7 is an unknown kind.
 std::string main_from_c(const AirDescHost& air, const sp_air_main_desc* m, uint64_t n, uint32_t n_periodic, AirMainLevel level, AirMainHost& out) {
     const bool rec = air_main_allows_chains(level), lk = air_main_allows_counts(level), link = air_main_allows_runs(level);
-    const bool div = air_main_allows_quotients(level);
+    const bool div = air_main_allows_quotients(level), fetch = air_main_allows_fetches(level);
     if (m->size != sizeof(sp_air_main_desc)) return "main program: sp_air_main_desc.size is not sizeof(sp_air_main_desc)";
     if (!m->ops || !m->consts || !m->cols) return "main program: null ops, consts or cols";
     if (m->input_cols == 0 || m->n_cols == 0 || (uint64_t)m->input_cols + m->n_cols != air.main_cols)
@@ -202,12 +204,26 @@ std::string main_from_c(const AirDescHost& air, const sp_air_main_desc* m, uint6
     std::vector<AirMainColumnHost> cols;
     cols.reserve(m->n_cols);
     uint32_t g0 = 0, g_end = 0;   // the chain group that column k belongs to is [g0, g_end), when k < g_end
-    uint32_t n_count = 0;
+    uint32_t n_count = 0, n_fetch = 0;
     for (uint32_t k = 0; k < m->n_cols; ++k) {
         const sp_air_main_column& c = m->cols[k];
         const std::string who = "main program: derived column " + std::to_string(k);
         const bool den = c.den_op != SP_AIR_AUX_NO_DEN;
-        if (c.kind > (lk ? SP_AIR_MAIN_COUNT : rec ? SP_AIR_MAIN_CHAIN : SP_AIR_MAIN_PRODUCT)) return who + " has an unknown kind";
+        if (c.kind > (fetch ? SP_AIR_MAIN_FETCH : lk ? SP_AIR_MAIN_COUNT : rec ? SP_AIR_MAIN_CHAIN : SP_AIR_MAIN_PRODUCT)) return who + " has an unknown kind";
+        if (c.kind == SP_AIR_MAIN_FETCH) {
+            const uint32_t key_bits = c.pad & 255u, v_op = (c.pad >> 8) & 65535u;
+            if (c.pad >> 24) return who + " is a FETCH column whose pad has a bit at or above 24 (pad = key_bits + 256 v_op)";
+            if (!den) return who + " is a FETCH column without a table key (den_op names the table key)";
+            if (key_bits == 0 || key_bits > AIR_MAIN_FETCH_MAX_KEY_BITS) return who + " is a FETCH column with key_bits = " + std::to_string(key_bits) + " (1 .. 64)";
+            if (c.num_op >= n_ops || c.den_op >= n_ops) return who + " names an op beyond the program";
+            if (v_op >= n_ops || ops[v_op].op == 5) return who + " is a FETCH column with v_op = " + std::to_string(v_op) + ", which is beyond the program or an OUT";
+            if (quot[c.num_op] || quot[c.den_op] || quot[v_op]) return quotient_refused(who);
+            const uint32_t r = std::max(std::max(reads[c.num_op], reads[c.den_op]), reads[v_op]);
+            if (r > k) return who + " reads derived column " + std::to_string(r - 1) + ", which is not an earlier one";
+            if (++n_fetch > AIR_MAIN_FETCH_MAX_COLS) return who + " is the program's FETCH column number " + std::to_string(n_fetch) + " (at most 64)";
+            cols.push_back(AirMainColumnHost{c.kind, c.num_op, c.den_op, 0u, r, 0u, 0u, key_bits, 0u, v_op});
+            continue;
+        }
         if (c.kind == SP_AIR_MAIN_COUNT) {
             if (!den) return who + " is a COUNT column without a table (den_op names the table value)";
             if (c.pad == 0 || c.pad > AIR_MAIN_COUNT_MAX_KEY_BITS) return who + " is a COUNT column with key_bits = " + std::to_string(c.pad) + " (1 .. 64)";
@@ -313,7 +329,8 @@ std::string air_statement_from_c(const sp_air_desc* d, const sp_air_aux_desc* au
     if (air.ops.size() > AIR_LIMIT_OPS) return "more than 65535 ops";
     if (main) {
         // (only the _rec, _lk, _link and _div entry points let a main program hold chain columns and read the periodic columns, only
-        // _lk, _link and _div COUNT columns, only _link and _div runs of blocks, only _div quotients behind chain seeds and steps)
+        // _lk, _link and _div COUNT columns, only _link and _div runs of blocks, only _div quotients behind chain seeds and steps; the
+        // _fetch entry points all of that and FETCH columns)
         const std::string refused = main_from_c(air, main, n, st.n_periodic(), st.main_level, st.main.emplace());
         if (!refused.empty()) return refused;
     }

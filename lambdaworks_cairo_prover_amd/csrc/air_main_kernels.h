@@ -32,6 +32,15 @@ int air_main_chain(hipStream_t st, fe* trace, uint64_t n, uint32_t log_s, uint32
 // head of a run of equal table keys (p == 0 or kt[p] != kt[p - 1]) z = upper_bound(kx, kt[p]) - lower_bound(kx, kt[p]), elsewhere
 // z = 0; col[rows[p]] = z as a field element.  rows is a permutation of 0 .. n - 1: every cell of col is written once.  n < 2^32.
 int air_main_count(hipStream_t st, const uint64_t* kx, const uint64_t* kt, const uint32_t* rows, uint64_t n, fe* col);
+// A group of w FETCH columns (looked-up values) that share their keys: kx the n looked-up keys in ROW order, kt the n table keys in
+// ascending order - sorted stably, rows[p] the row that table key p came from -, vals[j * n + r] the table value of group column j on
+// row r.  One lane per row i: p = lower_bound(kt, kx[i]) over [0, n) - the head of the run of equal table keys, its lowest row -, found
+// = p < n and kt[p] == kx[i], and cols[j * n + i] = vals[j * n + (found ? rows[p] : 0)] for j < w.  A lane that does not find its key
+// stores AIR_MAIN_FLAG_MISSING_KEY to *miss_flag (a plain store; every such lane stores the same word) and writes V of row 0, so all
+// its stores stay where they belong and every cell is written once.  1 <= w, n < 2^32.
+constexpr int AIR_MAIN_FLAG_MISSING_KEY = 1;
+int air_main_fetch(hipStream_t st, const uint64_t* kx, const uint64_t* kt, const uint32_t* rows, const fe* vals, uint64_t n, fe* cols, uint32_t w,
+                   int* miss_flag);
 // INV_OR_ZERO, before the batch inversion: for k < n_inv, with (slot, col) = tab[2 k], tab[2 k + 1]: where ws[slot * n + i] is zero it
 // becomes one and cols[col * n + i] = 0, elsewhere cols[col * n + i] = 1.  The inversion then meets no zero of these, and
 // air_aux_apply_den leaves 0 or 1 / N in the column.

@@ -130,6 +130,42 @@ int air_main_count(hipStream_t st, const uint64_t* kx, const uint64_t* kt, const
     return SP_OK;
 }
 
+// ---- looked-up values: the join of the looked-up keys, in row order, against the sorted table keys -----------------------------
+// One lane per row i, so the w stores of a lane are coalesced with its neighbours' into the group's columns.  The search is one
+// chain of dependent 8-byte loads out of kt, which the sort has just left in the L2 (log2 n + 1 of them); neighbouring rows look up
+// unrelated keys, so nothing of it can be shared or staged.  The lower bound of a key is the head of its run of equal table keys, and
+// the stable sort put the run's lowest row there.  Each of the w gathers is a 32-byte read - a sector of its own wherever it lands, as
+// in air_aux_gather - and they are independent of one another.  lo, hi and every probe stay in [0, n) whatever the arrays hold: keys
+// that were out of range leave kt ordered by its low bits only, the search then ends somewhere inside the array and the call is an
+// error already; kt[n] is never read, and a row that the arrays do not bound (rows is a permutation of 0 .. n - 1) reads row 0.
+// No LDS, no scratch: the lane's state is a key, two bounds and one value in flight.
+__global__ void __launch_bounds__(256) air_main_fetch_kernel(const uint64_t* __restrict__ kx, const uint64_t* __restrict__ kt, const uint32_t* __restrict__ rows,
+                                                             const fe* __restrict__ vals, uint64_t n, fe* __restrict__ cols, uint32_t w,
+                                                             int* __restrict__ miss_flag) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t key = kx[i];
+    uint64_t lo = 0, hi = n;   // lower bound: first kt >= key
+    while (lo < hi) {
+        const uint64_t mid = lo + ((hi - lo) >> 1);
+        if (kt[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    const uint64_t p = lo < n ? lo : n - 1;
+    const bool found = lo < n && kt[p] == key;
+    uint64_t src = found ? rows[p] : 0;
+    if (src >= n) src = 0;
+    if (!found) *miss_flag = AIR_MAIN_FLAG_MISSING_KEY;
+    for (uint32_t j = 0; j < w; ++j) fe_st(cols + (uint64_t)j * n + i, fe_ld(vals + (uint64_t)j * n + src));
+}
+
+int air_main_fetch(hipStream_t st, const uint64_t* kx, const uint64_t* kt, const uint32_t* rows, const fe* vals, uint64_t n, fe* cols, uint32_t w,
+                   int* miss_flag) {
+    if (n == 0 || n >= (1ull << 32) || w == 0 || !kx || !kt || !rows || !vals || !cols || !miss_flag) return SP_E_INVALID_ARG;
+    hipLaunchKernelGGL(air_main_fetch_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, kx, kt, rows, vals, n, cols, w, miss_flag);
+    SP_HIP_CHECK(hipGetLastError());
+    return SP_OK;
+}
+
 // Both stores happen on every row, with values chosen by mask: no lane takes a path of its own.
 __global__ void __launch_bounds__(256) air_main_zero_guard_kernel(fe* __restrict__ ws, fe* __restrict__ cols, const uint32_t* __restrict__ tab, uint64_t n) {
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;

@@ -370,7 +370,7 @@ namespace {
 struct AirParts {
     const sp_air_aux_desc* aux; const sp_air_periodic_desc* periodic; const sp_air_stride_desc* strides; const sp_air_boundary_desc* bvals; bool aux_reads_periodic;
     const sp_air_main_desc* main;   // (the _main entry points: the trace argument then holds the input columns only)
-    sp::AirMainLevel main_level;    // (what the main program may hold: the _rec, _lk, _link and _div entry points raise it)
+    sp::AirMainLevel main_level;    // (what the main program may hold: the _rec, _lk, _link, _div and _fetch entry points raise it)
     static AirParts of_ext(const sp_air_ext* ext, const sp_air_boundary_desc* bvals, bool aux_reads_periodic, const sp_air_main_desc* main = nullptr,
                            sp::AirMainLevel main_level = sp::AirMainLevel::Main) {
         return AirParts{ext ? ext->aux : nullptr, ext ? ext->periodic : nullptr, ext ? ext->strides : nullptr, bvals, aux_reads_periodic, main, main_level};
@@ -471,7 +471,8 @@ int sp_air_check_trace_pub(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ex
 // sp_air_prove_pub / sp_air_check_trace_pub from the input columns of a main-trace program: the device derives the other main columns.
 // One body per family over the level of the main program (sp::AirMainLevel): _main, then _rec for block recurrences
 // (SP_AIR_MAIN_CHAIN) and reads of the periodic columns (op 6), _lk for lookup multiplicities (SP_AIR_MAIN_COUNT) too, _link for chain
-// groups that link their blocks into runs (the k of a CHAIN column's pad), _div for quotients (op 7) behind chain seeds and steps.
+// groups that link their blocks into runs (the k of a CHAIN column's pad), _div for quotients (op 7) behind chain seeds and steps,
+// _fetch for looked-up values (SP_AIR_MAIN_FETCH).
 namespace {
 using sp::AirMainLevel;
 int air_prove_main(AirMainLevel level, sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const sp_air_boundary_desc* bv, const sp_air_main_desc* mp,
@@ -563,6 +564,18 @@ int sp_air_check_trace_div(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ex
 }
 int sp_air_main_trace_div(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const sp_air_main_desc* mp, const void* inputs, uint64_t n, uint8_t* rows_out) {
     return air_main_trace_ext("sp_air_main_trace_div", AirMainLevel::Div, c, d, ext, mp, inputs, n, rows_out);
+}
+
+int sp_air_prove_fetch(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const sp_air_boundary_desc* bv, const sp_air_main_desc* mp, const void* inputs,
+                       uint64_t n, const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len) {
+    return air_prove_main(AirMainLevel::Fetch, c, d, ext, bv, mp, inputs, n, opt, proof_out, proof_len);
+}
+int sp_air_check_trace_fetch(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const sp_air_boundary_desc* bv, const sp_air_main_desc* mp, const void* inputs,
+                             uint64_t n, const sp_proof_options* opt, const uint8_t* rap, sp_air_violation* out, uint32_t cap, uint32_t* n_out) {
+    return air_check_trace_main(AirMainLevel::Fetch, c, d, ext, bv, mp, inputs, n, opt, rap, out, cap, n_out);
+}
+int sp_air_main_trace_fetch(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const sp_air_main_desc* mp, const void* inputs, uint64_t n, uint8_t* rows_out) {
+    return air_main_trace_ext("sp_air_main_trace_fetch", AirMainLevel::Fetch, c, d, ext, mp, inputs, n, rows_out);
 }
 
 }  // extern "C"

@@ -241,7 +241,7 @@ int StarkProver::commit_aux_program(const AirStatement& st, const std::vector<fe
 // Chunks as above (at most max(1, AUXP_CHUNK_ELEMS / n) columns), and a chunk also ends before a column that reads a derived column
 // of the chunk itself: LOADs wrap around the trace, so a column must be complete - its scan included - before anything reads it, and
 // the stream orders one chunk behind the other.  od_.auxp_buf / od_.auxp_ws: the auxiliary program runs later on the same stream.
-// Every chunk places two programs and five word tables in the upload block, whatever its kind uses of them.
+// Every chunk places three programs and five word tables in the upload block, whatever its kind uses of them.
 struct MainChunk {
     // RowLocal: one pass of the interpreter (air_aux_terms), then what each column kind needs on top.  Workspace slots, n elements
     //   each: first the ones the batch inversion takes (the D of VALUE / SUM / PRODUCT columns, the guarded N of INV_OR_ZERO columns),
@@ -254,12 +254,19 @@ struct MainChunk {
     //   launches of air_aux_sort_terms (keys out of Montgomery form, the row beside each), two radix sorts - the table's carries its
     //   rows - and one launch of air_main_count, which writes every cell of the column.  Its arrays (4 x [n] keys, 4 x [n] rows, the
     //   radix histograms) lie at the start of the workspace: the chunk before it is over, the chunk behind it starts after the count.
-    enum class Kind { RowLocal, Chain, Count };
-    static constexpr int TERMS = 0, STEP = 0, SEED = 1, KEY_X = 0, KEY_T = 1;   // which of prog[] a kind's programs are
+    // Fetch: a run of at most AIR_MAIN_FETCH_MAX_GROUP consecutive FETCH columns (SP_AIR_MAIN_FETCH) with one X, one T and one key_bits,
+    //   none of which reads a derived column of the run; a chunk of its own that ends the chunk before it.  X's program and T's, each
+    //   with the one OUT of a key pass, and V's with an OUT per group column: two launches of air_aux_sort_terms - X's pairs stay in row
+    //   order -, one of air_aux_terms into kc workspace slots, one radix sort of the table's pairs and one launch of air_main_fetch,
+    //   which writes every cell of the group.  Its arrays (3 x [n] keys, 3 x [n] rows, the radix histograms) lie at the start of the
+    //   workspace, the kc slots behind them.
+    enum class Kind { RowLocal, Chain, Count, Fetch };
+    static constexpr int N_PROG = 3;
+    static constexpr int TERMS = 0, STEP = 0, SEED = 1, KEY_X = 0, KEY_T = 1, TABLE_V = 2;   // which of prog[] a kind's programs are
     Kind kind = Kind::RowLocal;
     uint32_t k0 = 0, kc = 0;                 // derived columns [k0, k0 + kc)
-    std::vector<AirOpDev> prog[2];           // in upload order: RowLocal TERMS (and none); Chain STEP, SEED; Count KEY_X, KEY_T
-    size_t o_prog[2] = {0, 0};
+    std::vector<AirOpDev> prog[N_PROG];      // in upload order: RowLocal TERMS (and none); Chain STEP, SEED; Count KEY_X, KEY_T; Fetch those and TABLE_V
+    size_t o_prog[N_PROG] = {0, 0, 0};
     bool periodic = false;                   // one of the chunk's programs reads a periodic column
     // RowLocal
     uint32_t n_inv = 0, n_slots = 0;                              // n_inv: slots the batch inversion takes; n_slots: those and the BIT groups'
@@ -269,17 +276,18 @@ struct MainChunk {
     // Chain
     uint32_t log_s = 0, log_k = 0;           // blocks of 2^log_s rows; log_k >= 1: runs of 2^log_k blocks
     bool divides = false;                    // the slotted seed or step program holds an op 7: the launch takes the zero flag
-    // Count
+    // Count, Fetch
     uint32_t key_bits = 0;
 };
 
 struct MainPlan {
     std::vector<MainChunk> chunks;
     uint32_t chunk = 0, max_slots = 0, max_inv = 0;
-    bool any_count = false;
+    bool any_count = false, any_fetch = false;
+    uint32_t max_fetch = 0;                  // the widest FETCH group
     size_t o_consts = 0, bytes = 0;          // the upload block: the constants, per chunk its programs and tables, the periodic columns
     PeriodicUpload per;
-    uint64_t ws_elems = 0;                   // the workspace; the word of the key-range flag lies behind it
+    uint64_t ws_elems = 0;                   // the workspace; the words of the key-range flag and the missing-key flag lie behind it
 };
 
 // Planning: the chunks and their programs, the upload block's layout and the workspace's size.  No HIP call.
@@ -332,11 +340,31 @@ static int plan_main_program(const AirStatement& st, uint64_t n, MainPlan& P) {
             SP_TRY(program(outs, ch, MainChunk::KEY_X));
             SP_TRY(program(table, ch, MainChunk::KEY_T));
             P.any_count = true;
+        } else if (mp.cols[k0].kind == SP_AIR_MAIN_FETCH) {
+            const AirMainColumnHost& c = mp.cols[k0];
+            std::vector<std::vector<uint32_t>> table(n_src), values(n_src);
+            if (c.key_bits == 0 || c.key_bits > 64 || c.num_op >= n_src || c.den_op >= n_src) { sp_set_error("commit_main_program: a FETCH column the decoder should have refused"); return SP_E_INVALID_ARG; }
+            outs[c.num_op].push_back(AIR_AUX_DEN_TAG);
+            table[c.den_op].push_back(AIR_AUX_DEN_TAG);
+            ch.kind = MainChunk::Kind::Fetch;
+            ch.key_bits = c.key_bits;
+            for (; ch.kc < AIR_MAIN_FETCH_MAX_GROUP && k0 + ch.kc < K; ++ch.kc) {
+                const AirMainColumnHost& g = mp.cols[k0 + ch.kc];
+                if (g.kind != SP_AIR_MAIN_FETCH || g.num_op != c.num_op || g.den_op != c.den_op || g.key_bits != c.key_bits || g.reads > k0) break;
+                if (g.value_op >= n_src) { sp_set_error("commit_main_program: a FETCH column the decoder should have refused"); return SP_E_INVALID_ARG; }
+                values[g.value_op].push_back(ch.kc);
+            }
+            if (ch.kc == 0) { sp_set_error("commit_main_program: a FETCH column that reads itself (the decoder should have refused it)"); return SP_E_INVALID_ARG; }
+            SP_TRY(program(outs, ch, MainChunk::KEY_X));
+            SP_TRY(program(table, ch, MainChunk::KEY_T));
+            SP_TRY(program(values, ch, MainChunk::TABLE_V));
+            P.any_fetch = true;
+            P.max_fetch = std::max(P.max_fetch, ch.kc);
         } else {
             struct BitGroup { uint32_t num_op; std::vector<uint32_t> entries; };
             std::vector<BitGroup> groups;
             for (; ch.kc < P.chunk && k0 + ch.kc < K && mp.cols[k0 + ch.kc].reads <= k0 && mp.cols[k0 + ch.kc].kind != SP_AIR_MAIN_CHAIN &&
-                   mp.cols[k0 + ch.kc].kind != SP_AIR_MAIN_COUNT; ++ch.kc) {
+                   mp.cols[k0 + ch.kc].kind != SP_AIR_MAIN_COUNT && mp.cols[k0 + ch.kc].kind != SP_AIR_MAIN_FETCH; ++ch.kc) {
                 const AirMainColumnHost& c = mp.cols[k0 + ch.kc];
                 const bool scanned = c.kind == SP_AIR_MAIN_SUM || c.kind == SP_AIR_MAIN_PRODUCT;
                 ch.kinds.push_back(c.kind == SP_AIR_MAIN_SUM ? 1u : 0u);
@@ -380,23 +408,26 @@ static int plan_main_program(const AirStatement& st, uint64_t n, MainPlan& P) {
     auto words = [&](const std::vector<uint32_t>& v) { return lay.place(sizeof(uint32_t) * std::max<size_t>(1, v.size())); };
     P.o_consts = lay.place(sizeof(fe) * std::max<size_t>(1, mp.consts.size()));
     for (MainChunk& ch : P.chunks) {
-        for (int w = 0; w < 2; ++w) ch.o_prog[w] = lay.place(sizeof(AirOpDev) * std::max<size_t>(1, ch.prog[w].size()));
+        for (int w = 0; w < MainChunk::N_PROG; ++w) ch.o_prog[w] = lay.place(sizeof(AirOpDev) * std::max<size_t>(1, ch.prog[w].size()));
         ch.o_kinds = words(ch.kinds); ch.o_den = words(ch.den_col); ch.o_guard = words(ch.guard); ch.o_gtab = words(ch.gtab); ch.o_etab = words(ch.etab);
     }
     const AirPeriodicHost* periodic = air_main_allows_chains(st.main_level) && st.periodic ? &*st.periodic : nullptr;
     if (any_periodic && !periodic) { sp_set_error("commit_main_program: op 6 without periodic columns (the decoder should have refused it)"); return SP_E_INVALID_ARG; }
     P.per.place(lay, any_periodic ? periodic : nullptr);
     P.bytes = lay.bytes;
-    // --- workspace, the larger of what a row-local chunk and what a COUNT column takes:
-    //     chunks: [max_slots][n] slots, [max_inv][n] batch-inversion scratch, [chunk][nb] scan block totals
-    //     counts: 4 x [n] keys, 4 x [n] rows, the radix sort's histograms (all in units of 32 bytes)
-    if (P.any_count && n >= (1ull << 32)) { sp_set_error("commit_main_program: COUNT columns need a trace of fewer than 2^32 rows"); return SP_E_INVALID_ARG; }
+    // --- workspace, the largest of what a row-local chunk, a COUNT column and a FETCH group take:
+    //     chunks:  [max_slots][n] slots, [max_inv][n] batch-inversion scratch, [chunk][nb] scan block totals
+    //     counts:  4 x [n] keys, 4 x [n] rows, the radix sort's histograms (all in units of 32 bytes)
+    //     fetches: 3 x [n] keys, 3 x [n] rows, the radix sort's histograms, [max_fetch][n] table values
+    if ((P.any_count || P.any_fetch) && n >= (1ull << 32)) { sp_set_error("commit_main_program: COUNT and FETCH columns need a trace of fewer than 2^32 rows"); return SP_E_INVALID_ARG; }
     P.ws_elems = std::max(((uint64_t)P.max_slots + P.max_inv) * n + (uint64_t)P.chunk * air_aux_scan_blocks(n), P.any_count ? SortScratch::elems(n, 4) : 0);
+    if (P.any_fetch) P.ws_elems = std::max(P.ws_elems, SortScratch::elems(n, 3) + (uint64_t)P.max_fetch * n);
     return SP_OK;
 }
 
-// Launching: the ingest, the upload and the chunks one behind the other.  The key-range flag of the COUNT columns is a word of its own
-// behind the workspace, so that no batch inversion before or behind overwrites it.
+// Launching: the ingest, the upload and the chunks one behind the other.  The key-range flag of the COUNT and FETCH columns is a word of
+// its own behind the workspace, so that no batch inversion before or behind overwrites it; the missing-key flag of the FETCH columns is
+// the word behind that one, so that neither a key pass nor a batch inversion does (both lie inside the one element behind ws_elems).
 int StarkProver::build_main_program(const AirStatement& st, const uint8_t* inputs) {
     const AirMainHost& mp = *st.main;
     const uint32_t I = mp.input_cols, K = (uint32_t)mp.cols.size();
@@ -414,7 +445,7 @@ int StarkProver::build_main_program(const AirStatement& st, const uint8_t* input
     fill_consts_then_rap(up.data() + P.o_consts, mp.consts, {});
     auto put = [&](size_t at, const std::vector<uint32_t>& v) { if (!v.empty()) std::memcpy(up.data() + at, v.data(), sizeof(uint32_t) * v.size()); };
     for (const MainChunk& ch : P.chunks) {
-        for (int w = 0; w < 2; ++w)
+        for (int w = 0; w < MainChunk::N_PROG; ++w)
             if (!ch.prog[w].empty()) std::memcpy(up.data() + ch.o_prog[w], ch.prog[w].data(), sizeof(AirOpDev) * ch.prog[w].size());
         put(ch.o_kinds, ch.kinds); put(ch.o_den, ch.den_col); put(ch.o_guard, ch.guard); put(ch.o_gtab, ch.gtab); put(ch.o_etab, ch.etab);
     }
@@ -422,6 +453,7 @@ int StarkProver::build_main_program(const AirStatement& st, const uint8_t* input
     SP_TRY(grow(od_.auxp_ws, P.ws_elems + 1));
     SP_TRY(ensure_host_flags());
     host_flags().auxp_bad_key = 0;
+    host_flags().auxp_missing_key = 0;
     // --- ingest: the plain staged copy (the inputs are a small part of the table; their raw rows sit in the segment's LDE area,
     //     which is written only by the transforms behind the last chunk), then rows -> columns [0, I)
     if (mp.input_location == 1) {
@@ -436,15 +468,19 @@ int StarkProver::build_main_program(const AirStatement& st, const uint8_t* input
     const fe* consts_dev = reinterpret_cast<const fe*>(od_.auxp_buf.p + P.o_consts);
     fe* ws = od_.auxp_ws.p;
     int* key_flag = reinterpret_cast<int*>(ws + P.ws_elems);
-    if (P.any_count) SP_HIP_CHECK(hipMemsetAsync(key_flag, 0, sizeof(int), c_->stream));
-    const SortScratch s(ws, n_, 4);   // X's pairs in keys / rows [0] and [1], T's in [2] and [3]
+    int* miss_flag = key_flag + 1;
+    if (P.any_count || P.any_fetch) SP_HIP_CHECK(hipMemsetAsync(key_flag, 0, (P.any_fetch ? 2 : 1) * sizeof(int), c_->stream));
+    const SortScratch s(ws, n_, 4);   // a COUNT column: X's pairs in keys / rows [0] and [1], T's in [2] and [3]
+    const SortScratch f(ws, n_, 3);   // a FETCH group: T's pairs in keys / rows [0] and [1], X's in [2]; the table values behind
+    fe* fetch_vals = ws + SortScratch::elems(n_, 3);
     fe* scratch = ws + (uint64_t)P.max_slots * n_;
     fe* block_tot = scratch + (uint64_t)P.max_inv * n_;
     auto tab = [&](size_t at) { return reinterpret_cast<const uint32_t*>(od_.auxp_buf.p + at); };
     for (const MainChunk& ch : P.chunks) {
         fe* cols = d_trace_ + (uint64_t)(I + ch.k0) * n_;
-        const AirOpDev* const prog[2] = {reinterpret_cast<const AirOpDev*>(od_.auxp_buf.p + ch.o_prog[0]), reinterpret_cast<const AirOpDev*>(od_.auxp_buf.p + ch.o_prog[1])};
-        const uint32_t n_prog[2] = {(uint32_t)ch.prog[0].size(), (uint32_t)ch.prog[1].size()};
+        const AirOpDev* const prog[MainChunk::N_PROG] = {reinterpret_cast<const AirOpDev*>(od_.auxp_buf.p + ch.o_prog[0]), reinterpret_cast<const AirOpDev*>(od_.auxp_buf.p + ch.o_prog[1]),
+                                                         reinterpret_cast<const AirOpDev*>(od_.auxp_buf.p + ch.o_prog[2])};
+        const uint32_t n_prog[MainChunk::N_PROG] = {(uint32_t)ch.prog[0].size(), (uint32_t)ch.prog[1].size(), (uint32_t)ch.prog[2].size()};
         const AirPeriodicCol* pc = ch.periodic ? P.per.cols_dev(od_.auxp_buf.p) : nullptr;
         const fe* pv = ch.periodic ? P.per.vals_dev(od_.auxp_buf.p) : nullptr;
         switch (ch.kind) {
@@ -458,6 +494,13 @@ int StarkProver::build_main_program(const AirStatement& st, const uint8_t* input
             SP_TRY(radix_sort_pairs_u64(c_->stream, s.keys[0], s.keys[1], s.rows[0], s.rows[1], n_, ch.key_bits, s.radix));
             SP_TRY(radix_sort_pairs_u64(c_->stream, s.keys[2], s.keys[3], s.rows[2], s.rows[3], n_, ch.key_bits, s.radix));
             SP_TRY(air_main_count(c_->stream, s.keys[1], s.keys[3], s.rows[3], n_, cols));
+            break;
+        case MainChunk::Kind::Fetch:   // key passes (X's pairs stay in row order), V's terms, the table's sort (into keys / rows [1]), the join
+            SP_TRY(air_aux_sort_terms(c_->stream, d_trace_, n_, prog[MainChunk::KEY_T], n_prog[MainChunk::KEY_T], consts_dev, nullptr, f.keys[0], f.rows[0], ch.key_bits, key_flag, pc, pv));
+            SP_TRY(air_aux_sort_terms(c_->stream, d_trace_, n_, prog[MainChunk::KEY_X], n_prog[MainChunk::KEY_X], consts_dev, nullptr, f.keys[2], f.rows[2], ch.key_bits, key_flag, pc, pv));
+            SP_TRY(air_aux_terms(c_->stream, d_trace_, n_, prog[MainChunk::TABLE_V], n_prog[MainChunk::TABLE_V], consts_dev, fetch_vals, nullptr, pc, pv));
+            SP_TRY(radix_sort_pairs_u64(c_->stream, f.keys[0], f.keys[1], f.rows[0], f.rows[1], n_, ch.key_bits, f.radix));
+            SP_TRY(air_main_fetch(c_->stream, f.keys[2], f.keys[1], f.rows[1], fetch_vals, n_, cols, ch.kc, miss_flag));
             break;
         case MainChunk::Kind::RowLocal:
             // OUT a < AIR_AUX_DEN_TAG stores N of chunk column a, OUT AIR_AUX_DEN_TAG + s stores into workspace slot s
@@ -475,14 +518,20 @@ int StarkProver::build_main_program(const AirStatement& st, const uint8_t* input
     }
     // the zero-denominator flag rides behind the columns; whoever reads the root (or the table) back waits for it
     SP_HIP_CHECK(hipMemcpyAsync(&host_flags().auxp_zero_den, c_->d_flag, sizeof(int), hipMemcpyDeviceToHost, c_->stream));
-    if (P.any_count) SP_HIP_CHECK(hipMemcpyAsync(&host_flags().auxp_bad_key, key_flag, sizeof(int), hipMemcpyDeviceToHost, c_->stream));
+    if (P.any_count || P.any_fetch) SP_HIP_CHECK(hipMemcpyAsync(&host_flags().auxp_bad_key, key_flag, sizeof(int), hipMemcpyDeviceToHost, c_->stream));
+    if (P.any_fetch) SP_HIP_CHECK(hipMemcpyAsync(&host_flags().auxp_missing_key, miss_flag, sizeof(int), hipMemcpyDeviceToHost, c_->stream));
     return SP_OK;
 }
 
-// What the flags say once the stream has drained: the key range first (as commit_aux_program), then a zero denominator.
+// What the flags say once the stream has drained: the key range first (as commit_aux_program), then a missing key, then a zero
+// denominator.
 static int main_program_verdict(const HostFlags& f) {
     if (f.auxp_bad_key == AIR_AUX_FLAG_KEY_RANGE) {
         sp_set_error("commit_main_program: a lookup key is out of range on some row (X and T of a COUNT column must be below 2^key_bits as canonical integers)");
+        return SP_E_INVALID_ARG;
+    }
+    if (f.auxp_missing_key == AIR_MAIN_FLAG_MISSING_KEY) {
+        sp_set_error("commit_main_program: a fetched key is in no table row (every X of a FETCH column must equal the T of some row)");
         return SP_E_INVALID_ARG;
     }
     if (f.auxp_zero_den) { sp_set_error("commit_main_program: a derived main column's denominator is zero on some row"); return SP_E_ZERO_INVERSE; }
