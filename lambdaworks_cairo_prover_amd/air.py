@@ -46,6 +46,7 @@ ec_subset_sum below.
 """
 import collections
 import ctypes
+import enum
 
 P = 2**251 + 17 * 2**192 + 1
 
@@ -267,68 +268,63 @@ def needs_pub(desc):
     return any(aux.ops[i].op == OP_PERIODIC for i in range(aux.n_ops)) if known is None else known
 
 
-def needs_rec(desc):
-    """Whether a built descriptor's main program needs the _rec entry points: it has a chain column (kind 5) or reads a periodic
-    column (op 6)."""
+class MainLevel(enum.IntEnum):
+    """The entry points a main-trace program goes through, in the order of sp::AirMainLevel (air_desc.h): each level's decoder knows what
+    the levels below it know, and the entry points carry its suffix (sp_air_prove_rec, sp_air_main_check_rec, ...; sp_air_main_trace and
+    sp_air_main_check at MAIN)."""
+    MAIN, REC, LK, LINK, DIV, FETCH = range(6)
+
+    @property
+    def suffix(self):
+        return self.name.lower()
+
+
+# What in a main program demands each level above MAIN: a test of a column's (kind, pad) and a test of an op code (None: no such thing).
+_MAIN_DEMANDS = {
+    MainLevel.REC: (lambda kind, pad: kind == MAIN_CHAIN, lambda op: op == OP_PERIODIC),      # a chain column, a read of a periodic column
+    MainLevel.LK: (lambda kind, pad: kind == MAIN_COUNT, None),                               # a lookup multiplicity
+    MainLevel.LINK: (lambda kind, pad: kind == MAIN_CHAIN and pad >> 16 != 0, None),          # a pad that carries k >= 1: runs of 2^k blocks
+    MainLevel.DIV: (None, lambda op: op == OP_DIV),                                           # a quotient behind a chain group
+    MainLevel.FETCH: (lambda kind, pad: kind == MAIN_FETCH, None),                            # a looked-up value
+}
+
+
+def _demanded(cols, ops):
+    """The levels that the columns (kind, pad) and the op codes of a main program demand, one pass over each."""
+    found = {level for kind, pad in cols for level, (col, _) in _MAIN_DEMANDS.items() if col is not None and col(kind, pad)}
+    found |= {level for code in ops for level, (_, op) in _MAIN_DEMANDS.items() if op is not None and op(code)}
+    return frozenset(found)
+
+
+def main_features(desc):
+    """The levels a built descriptor's main program demands (none without one): what AirBuilder.build() recorded as desc.main_features,
+    or, for a descriptor put together by hand, what its C arrays show."""
     main = getattr(desc, "main_desc", None)
     if main is None:
-        return False
-    known = getattr(desc, "main_needs_rec", None)   # (AirBuilder.build() says so; a descriptor put together by hand is looked through)
+        return frozenset()
+    known = getattr(desc, "main_features", None)
     if known is not None:
         return known
-    return ((bool(main.cols) and any(main.cols[k].kind == MAIN_CHAIN for k in range(main.n_cols))) or
-            (bool(main.ops) and any(main.ops[i].op == OP_PERIODIC for i in range(main.n_ops))))
+    return _demanded([(main.cols[k].kind, main.cols[k].pad) for k in range(main.n_cols)] if main.cols else [],
+                     [main.ops[i].op for i in range(main.n_ops)] if main.ops else [])
 
 
-def needs_lk(desc):
-    """Whether a built descriptor's main program needs the _lk entry points: it has a COUNT column (kind 6), a lookup multiplicity."""
-    main = getattr(desc, "main_desc", None)
-    if main is None:
-        return False
-    known = getattr(desc, "main_needs_lk", None)   # (AirBuilder.build() says so; a descriptor put together by hand is looked through)
-    if known is not None:
-        return known
-    return bool(main.cols) and any(main.cols[k].kind == MAIN_COUNT for k in range(main.n_cols))
-
-
-def needs_link(desc):
-    """Whether a built descriptor's main program needs the _link entry points: a chain column (kind 5) whose pad carries k >= 1, runs
-    of 2^k blocks seeded from the block before."""
-    main = getattr(desc, "main_desc", None)
-    if main is None:
-        return False
-    known = getattr(desc, "main_needs_link", None)   # (AirBuilder.build() says so; a descriptor put together by hand is looked through)
-    if known is not None:
-        return known
-    return bool(main.cols) and any(main.cols[k].kind == MAIN_CHAIN and main.cols[k].pad >> 16 for k in range(main.n_cols))
-
-
-def needs_div(desc):
-    """Whether a built descriptor's main program needs the _div entry points: it holds an op 7, a quotient behind a chain group."""
-    main = getattr(desc, "main_desc", None)
-    if main is None:
-        return False
-    known = getattr(desc, "main_needs_div", None)   # (AirBuilder.build() says so; a descriptor put together by hand is looked through)
-    if known is not None:
-        return known
-    return bool(main.ops) and any(main.ops[i].op == OP_DIV for i in range(main.n_ops))
-
-
-def needs_fetch(desc):
-    """Whether a built descriptor's main program needs the _fetch entry points: it has a FETCH column (kind 7), a looked-up value."""
-    main = getattr(desc, "main_desc", None)
-    if main is None:
-        return False
-    known = getattr(desc, "main_needs_fetch", None)   # (AirBuilder.build() says so; a descriptor put together by hand is looked through)
-    if known is not None:
-        return known
-    return bool(main.cols) and any(main.cols[k].kind == MAIN_FETCH for k in range(main.n_cols))
+def main_level(desc):
+    """The level a descriptor's main program is routed to: the highest it demands, or MAIN."""
+    return max(main_features(desc), default=MainLevel.MAIN)
 
 
 def main_suffix(desc):
-    """The entry points a descriptor's main program goes through: "fetch", "div", "link", "lk", "rec" or "main" - the newer ones only
-    where it needs them."""
-    return "fetch" if needs_fetch(desc) else "div" if needs_div(desc) else "link" if needs_link(desc) else "lk" if needs_lk(desc) else "rec" if needs_rec(desc) else "main"
+    """The suffix of the entry points of main_level(desc): the newer ones only where the program needs them."""
+    return main_level(desc).suffix
+
+
+# Whether a descriptor's main program holds what demands a level - a fact about the program, not about where it is routed.
+def needs_rec(desc): return MainLevel.REC in main_features(desc)
+def needs_lk(desc): return MainLevel.LK in main_features(desc)
+def needs_link(desc): return MainLevel.LINK in main_features(desc)
+def needs_div(desc): return MainLevel.DIV in main_features(desc)
+def needs_fetch(desc): return MainLevel.FETCH in main_features(desc)
 
 
 def route(desc, call):
@@ -336,10 +332,7 @@ def route(desc, call):
     them: (the entry point's name, its arguments between `air` and the trace / the options, keepalive).  _pub for boundary values
     computed from the challenges or an auxiliary program that reads a table, _ext for strides, else the parts one by one (the
     verifier takes no auxiliary program).  A descriptor with a main-trace program (desc.main_desc) is proved and checked through the
-    _main entry points, which take everything the _pub ones do - through the _rec ones when it holds a chain column or reads a
-    periodic column (needs_rec), through the _lk ones when it holds a lookup multiplicity (needs_lk), through the _link ones when a
-    chain group links its blocks into runs (needs_link), through the _div ones when a seed or a step divides (needs_div), through the
-    _fetch ones when it holds a looked-up value (needs_fetch) -; it is verified as if it had none."""
+    entry points of its MainLevel (main_level), which take everything the _pub ones do; it is verified as if it had none."""
     def ref(part):
         return None if part is None else ctypes.byref(part)
     aux, per = getattr(desc, "aux_desc", None), getattr(desc, "periodic_desc", None)
@@ -403,7 +396,7 @@ class Value:
         self.b, self.i = builder, index
 
     def _lift(self, other):
-        return other if isinstance(other, Value) else self.b.const(other)
+        return self.b._lift(other)
 
     def __add__(self, o): return self.b._emit(OP_ADD, self.i, self._lift(o).i)
     def __sub__(self, o): return self.b._emit(OP_SUB, self.i, self._lift(o).i)
@@ -423,31 +416,17 @@ class Value:
     def __rtruediv__(self, o): return self._div(self._lift(o), self)
 
 
-class AuxProgram:
-    """The auxiliary program of an AIR built with aux_kind=AUX_PROGRAM (sp_air_aux_desc): evaluated once per trace row i on the
-    device.  load(shift, col) reads main column `col` of row (i + shift) mod n; product(N, D) and running_sum(N, D) each declare the
-    next auxiliary column: z_0 = 1, z_i = z_(i-1) N(i-1) / D(i-1), or z_0 = 0, z_i = z_(i-1) + N(i-1) / D(i-1) (D = 1 when None).
-    sorted(key, carry) declares 1 + len(carry) columns: the key and the carried values, each evaluated on the main-trace row alone, in
-    the stable ascending order of the rows by the key's canonical integer; sorted_load(shift, k) reads such a column from a product
-    or a running sum."""
+class _Program:
+    """What every builder of a straight-line program shares: ops [(op, a, b)], the constants - interned, so that the first sight of a
+    value appends it - and the emitter that Value's operators go through."""
 
-    def __init__(self, main_cols, n_rap, periodic_cols=()):
-        self.main_cols, self.n_rap = main_cols, n_rap
-        self.periodic_cols = periodic_cols   # the owning AirBuilder's periodic columns: what table() may read
-        self.ops, self.consts, self.cols = [], [], []
-        self.key_bits = {}                   # sorted column -> the bits of its group's key (sp_air_aux_column.pad)
+    def __init__(self):
+        self.ops, self.consts = [], []
         self._const_at = {}
 
     def _emit(self, op, a, b):
         self.ops.append((op, a, b))
         return Value(self, len(self.ops) - 1)
-
-    def load(self, shift, col):
-        if not 0 <= shift <= AUX_MAX_SHIFT:
-            raise ValueError(f"aux program: row shift {shift} outside 0 .. {AUX_MAX_SHIFT}")
-        if not 0 <= col < self.main_cols:
-            raise ValueError(f"aux program: column {col} is not a main column (main_cols = {self.main_cols})")
-        return self._emit(OP_LOAD, shift, col)
 
     def const(self, v):
         v %= P
@@ -456,10 +435,89 @@ class AuxProgram:
             self.consts.append(v)
         return self._emit(OP_CONST, self._const_at[v], 0)
 
+    def _lift(self, x):
+        return x if isinstance(x, Value) else self.const(x)
+
+
+class _ChallengeProgram(_Program):
+    """A program that reads the RAP challenges (n_rap of them): a CONST whose index carries _RAP_TAG until resolved_ops() resolves it."""
+    _what = None    # the prefix of the refusal: "aux program", "public values"
+
     def rap(self, i):
         if not 0 <= i < self.n_rap:
-            raise ValueError(f"aux program: RAP challenge {i} of {self.n_rap}")
+            raise ValueError(f"{self._what}: RAP challenge {i} of {self.n_rap}")
         return self._emit(OP_CONST, _RAP_TAG | i, 0)
+
+    def resolved_ops(self):
+        """The ops as the library reads them: RAP challenges follow the constants."""
+        return [(op, len(self.consts) + (a & ~_RAP_TAG) if op == OP_CONST and a & _RAP_TAG else a, b) for op, a, b in self.ops]
+
+
+def _reachable(ops, targets, done=lambda u: False):
+    """The ops that the values `targets` depend on, ascending, without those that are `done` and what only they need."""
+    todo, stack = set(), list(targets)
+    while stack:
+        u = stack.pop()
+        if u in todo or done(u):
+            continue
+        todo.add(u)
+        if ops[u][0] in _TWO_VALUES:
+            stack += [ops[u][1], ops[u][2]]
+    return sorted(todo)
+
+
+def _interpret(ops, which, vals, unknown, const, load=None, periodic=None, div=None, out=None):
+    """vals[t] for the ops `which` (ascending) of `ops`: the one place the op codes are dispatched.  The values are whatever supports
+    + - * % - Python integers, or numpy object arrays, one vectorised operation per op.  What differs between the callers comes as
+    callables, and an op whose callable is None is unknown to the caller, as is any other code: ValueError(unknown(t, op)).
+    const(a) fetches a constant (or a challenge), load(a, b) reads a cell, periodic(a, b) reads op 6, div(num, den) is op 7's quotient and
+    out(a, value) takes an OUT (whose own value is what it returns)."""
+    for t in which:
+        op, a, b = ops[t]
+        if op == OP_ADD:
+            v = (vals[a] + vals[b]) % P
+        elif op == OP_SUB:
+            v = (vals[a] - vals[b]) % P
+        elif op == OP_MUL:
+            v = (vals[a] * vals[b]) % P
+        elif op == OP_LOAD and load is not None:
+            v = load(a, b)
+        elif op == OP_CONST:
+            v = const(a)
+        elif op == OP_PERIODIC and periodic is not None:
+            v = periodic(a, b)
+        elif op == OP_DIV and div is not None:
+            v = div(vals[a], vals[b])
+        elif op == OP_OUT and out is not None:
+            v = out(a, vals[b])
+        else:
+            raise ValueError(unknown(t, op))
+        vals[t] = v
+
+
+class AuxProgram(_ChallengeProgram):
+    """The auxiliary program of an AIR built with aux_kind=AUX_PROGRAM (sp_air_aux_desc): evaluated once per trace row i on the
+    device.  load(shift, col) reads main column `col` of row (i + shift) mod n; product(N, D) and running_sum(N, D) each declare the
+    next auxiliary column: z_0 = 1, z_i = z_(i-1) N(i-1) / D(i-1), or z_0 = 0, z_i = z_(i-1) + N(i-1) / D(i-1) (D = 1 when None).
+    sorted(key, carry) declares 1 + len(carry) columns: the key and the carried values, each evaluated on the main-trace row alone, in
+    the stable ascending order of the rows by the key's canonical integer; sorted_load(shift, k) reads such a column from a product
+    or a running sum."""
+
+    _what = "aux program"
+
+    def __init__(self, main_cols, n_rap, periodic_cols=()):
+        super().__init__()
+        self.main_cols, self.n_rap = main_cols, n_rap
+        self.periodic_cols = periodic_cols   # the owning AirBuilder's periodic columns: what table() may read
+        self.cols = []
+        self.key_bits = {}                   # sorted column -> the bits of its group's key (sp_air_aux_column.pad)
+
+    def load(self, shift, col):
+        if not 0 <= shift <= AUX_MAX_SHIFT:
+            raise ValueError(f"aux program: row shift {shift} outside 0 .. {AUX_MAX_SHIFT}")
+        if not 0 <= col < self.main_cols:
+            raise ValueError(f"aux program: column {col} is not a main column (main_cols = {self.main_cols})")
+        return self._emit(OP_LOAD, shift, col)
 
     def periodic(self, row, k):
         raise ValueError("aux program: an auxiliary program cannot read periodic columns (sp_air_prove_periodic refuses op 6 there); "
@@ -478,9 +536,7 @@ class AuxProgram:
         return any(op == OP_PERIODIC for op, _, _ in self.ops)
 
     def _column(self, kind, num, den):
-        num = num if isinstance(num, Value) else self.const(num)
-        if den is not None and not isinstance(den, Value):
-            den = self.const(den)
+        num, den = self._lift(num), None if den is None else self._lift(den)
         self.cols.append((kind, num.i, AUX_NO_DEN if den is None else den.i))
 
     def product(self, num, den=None):
@@ -497,7 +553,7 @@ class AuxProgram:
         form one group: one sort serves them all."""
         if not 1 <= key_bits <= 64:
             raise ValueError(f"aux program: key_bits {key_bits} outside 1 .. 64")
-        values = [v if isinstance(v, Value) else self.const(v) for v in (key, *carry)]
+        values = [self._lift(v) for v in (key, *carry)]
         tainted = self._reads_sorted()
         for v in values:
             if v.b is not self or tainted[v.i]:
@@ -533,10 +589,6 @@ class AuxProgram:
             if kind == AUX_SORTED:
                 groups.setdefault(den_op, []).append(k)
         return groups
-
-    def resolved_ops(self):
-        """The ops as the library reads them: RAP challenges follow the constants."""
-        return [(op, len(self.consts) + (a & ~_RAP_TAG) if op == OP_CONST and a & _RAP_TAG else a, b) for op, a, b in self.ops]
 
     def evaluate(self, rows, rap, periodic=None):
         """The auxiliary columns in Python integers (the semantics of sp_air_prove_aux): rows = n x main_cols field elements (any
@@ -594,25 +646,13 @@ class AuxProgram:
         the sorted column of `out`."""
         import numpy as np
         n = m.shape[0]
-        ops = self.resolved_ops()
-        for t in which:
-            op, a, b = ops[t]
-            if op == OP_LOAD:
-                v = np.roll(m[:, b] if b < self.main_cols else out[:, b - self.main_cols], -a)
-            elif op == OP_CONST:
-                v = np.full(n, consts[a], dtype=object)
-            elif op == OP_ADD:
-                v = (vals[a] + vals[b]) % P
-            elif op == OP_SUB:
-                v = (vals[a] - vals[b]) % P
-            elif op == OP_MUL:
-                v = (vals[a] * vals[b]) % P
-            elif op == OP_PERIODIC:
-                values = (self.periodic_cols if periodic is None else periodic)[b]
-                v = np.array([int(x) % P for x in values], dtype=object)[(np.arange(n) + a) % len(values)]
-            else:
-                raise ValueError(f"aux program: op {op}")
-            vals[t] = v
+
+        def table(a, b):
+            values = (self.periodic_cols if periodic is None else periodic)[b]
+            return np.array([int(x) % P for x in values], dtype=object)[(np.arange(n) + a) % len(values)]
+
+        _interpret(self.resolved_ops(), which, vals, lambda t, op: f"aux program: op {op}", lambda a: np.full(n, consts[a], dtype=object),
+                   load=lambda a, b: np.roll(m[:, b] if b < self.main_cols else out[:, b - self.main_cols], -a), periodic=table)
 
 
 def _batch_inverse(xs):
@@ -631,7 +671,7 @@ def _batch_inverse(xs):
     return out
 
 
-class MainProgram:
+class MainProgram(_Program):
     """The main-trace program of an AIR built with main_inputs=I (sp_air_main_desc): the caller supplies main columns 0 .. I - 1, the
     device derives the others, each a row-local function of columns that exist already.  load(shift, col) reads main column `col` - an
     input, or a derived column declared so far - on row (i + shift) mod n; every declaration below adds the next main column and returns
@@ -687,19 +727,18 @@ class MainProgram:
     def __init__(self, input_cols, main_cols, periodic_cols=()):
         if not 1 <= input_cols < main_cols:
             raise ValueError(f"main program: {input_cols} input columns of {main_cols} main columns (at least one input, at least one derived)")
+        super().__init__()
         self.input_cols, self.main_cols = input_cols, main_cols
         self.periodic_cols = periodic_cols   # the owning AirBuilder's periodic columns: what periodic() may read
-        self.ops, self.consts, self.cols = [], [], []    # cols: (kind, num_op, den_op, pad)
-        self._const_at = {}
+        self.cols = []                       # (kind, num_op, den_op, pad)
         self._open = None                    # the chain group between chain() and step()
-        self.lookups = False                 # multiplicity() was called: check() mirrors the decoder of the _lk entry points
-        self.links = False                   # chain(link > 1) was called: check() mirrors the decoder of the _link entry points
-        self.divs = False                    # div() was called: check() mirrors the decoder of the _div entry points
-        self.fetches = False                 # fetch() was called: check() mirrors the decoder of the _fetch entry points
+        # the entry points whose decoder check() mirrors: multiplicity(), chain(link > 1), div() and fetch_many() raise it
+        self.level = MainLevel.REC
 
-    def _emit(self, op, a, b):
-        self.ops.append((op, a, b))
-        return Value(self, len(self.ops) - 1)
+    lookups = property(lambda self: self.level >= MainLevel.LK)     # what was declared, as the level says it
+    links = property(lambda self: self.level >= MainLevel.LINK)
+    divs = property(lambda self: self.level >= MainLevel.DIV)
+    fetches = property(lambda self: self.level >= MainLevel.FETCH)
 
     def load(self, shift, col):
         if not 0 <= shift <= AUX_MAX_SHIFT:
@@ -723,11 +762,10 @@ class MainProgram:
 
     def div(self, num, den):
         """num / den (op 7): see the class.  Legal behind the seed or step of a chain group only, which check() holds the columns to."""
-        num = num if isinstance(num, Value) else self.const(num)
-        den = den if isinstance(den, Value) else self.const(den)
+        num, den = self._lift(num), self._lift(den)
         if num.b is not self or den.b is not self:
             raise ValueError("main program: the operands of a quotient must be values of this program")
-        self.divs = True
+        self.level = max(self.level, MainLevel.DIV)
         return self._emit(OP_DIV, num.i, den.i)
 
     def chain(self, period, seeds, width=None, link=1):
@@ -753,24 +791,16 @@ class MainProgram:
         if deferred:
             seeds = [self.const(0)] * w    # (den_op, the seed, is filled in by g.seed)
         else:
-            seeds = [x if isinstance(x, Value) else self.const(x) for x in seeds]
+            seeds = [self._lift(x) for x in seeds]
         for j, seed in enumerate(seeds):   # (num_op, the step, is filled in by g.step)
             self._column(MAIN_CHAIN, seed, seed, log + 256 * j + 65536 * (link.bit_length() - 1))
-        self.links |= link > 1
+        if link > 1:
+            self.level = max(self.level, MainLevel.LINK)
         self._open = ChainGroup(self, list(range(first, first + w)), period, link, seeding=deferred)
         return self._open
 
-    def const(self, v):
-        v %= P
-        if v not in self._const_at:
-            self._const_at[v] = len(self.consts)
-            self.consts.append(v)
-        return self._emit(OP_CONST, self._const_at[v], 0)
-
     def _column(self, kind, num, den=None, pad=0):
-        num = num if isinstance(num, Value) else self.const(num)
-        if den is not None and not isinstance(den, Value):
-            den = self.const(den)
+        num, den = self._lift(num), None if den is None else self._lift(den)
         if num.b is not self or (den is not None and den.b is not self):
             raise ValueError("main program: N and D must be values of this program")
         if self._open is not None:
@@ -793,7 +823,7 @@ class MainProgram:
 
     def bits(self, x, count):
         """Bits 0 .. count - 1 of x, one column each (they share x: the device takes it out of Montgomery form once per row)."""
-        x = x if isinstance(x, Value) else self.const(x)
+        x = self._lift(x)
         return [self.bit(x, j) for j in range(count)]
 
     def running_sum(self, num, den=None):
@@ -810,7 +840,7 @@ class MainProgram:
             raise ValueError(f"main program: key_bits {key_bits} outside 1 .. {MAIN_COUNT_MAX_KEY_BITS}")
         if sum(1 for c in self.cols if c[0] == MAIN_COUNT) >= MAIN_COUNT_MAX_COLS:
             raise ValueError(f"main program: more than {MAIN_COUNT_MAX_COLS} multiplicity columns")
-        self.lookups = True
+        self.level = max(self.level, MainLevel.LK)
         return self._column(MAIN_COUNT, x, table, key_bits)
 
     def fetch(self, x, table_key, table_value, key_bits=64):
@@ -828,14 +858,13 @@ class MainProgram:
             raise ValueError("main program: a fetch needs at least one table value")
         if sum(1 for c in self.cols if c[0] == MAIN_FETCH) + len(table_values) > MAIN_FETCH_MAX_COLS:
             raise ValueError(f"main program: more than {MAIN_FETCH_MAX_COLS} fetched columns")
-        x = x if isinstance(x, Value) else self.const(x)
-        table_key = table_key if isinstance(table_key, Value) else self.const(table_key)
-        values = [v if isinstance(v, Value) else self.const(v) for v in table_values]
+        x, table_key = self._lift(x), self._lift(table_key)
+        values = [self._lift(v) for v in table_values]
         if any(v.b is not self for v in values):
             raise ValueError("main program: the table values of a fetch must be values of this program")
         if max(v.i for v in values) >= 1 << 16:
             raise ValueError("main program: the table value of a fetch must be one of the program's first 65536 ops (v_op rides in 16 bits of the pad)")
-        self.fetches = True
+        self.level = max(self.level, MainLevel.FETCH)
         cols = [self._column(MAIN_FETCH, x, table_key, key_bits + 256 * v.i) for v in values]
         return [self.load(0, c) for c in cols]
 
@@ -859,21 +888,15 @@ class MainProgram:
             quot.append(op == OP_DIV or (op in _TWO_VALUES and (quot[a] or quot[b])))
         return quot
 
-    def check(self, n=None, lookups=None, links=None, divs=None, fetches=None):
+    def check(self, n=None, level=None):
         """The decoder's rules (air_statement_from_c), for a program whose lists were filled by hand too: ValueError naming the first one
-        broken.  n: the trace length a chain group's block length is held against (None: not yet known).  lookups: whether COUNT
-        columns are known - the decoder of the _lk entry points, where the program would be routed after multiplicity() declared one
-        (None: self.lookups); otherwise kind 6 is an unknown kind, as for the _rec entry points.  links: whether the k of a CHAIN
-        column's pad is known - the decoder of the _link entry points, where the program would be routed after chain(link > 1) declared
-        a linked group (None: self.links), which knows COUNT columns too; otherwise the bits at and above 16 belong to j.  divs:
-        whether op 7 is known - the decoder of the _div entry points, where the program would be routed after div() emitted one (None:
-        self.divs), which knows linked groups too; otherwise op 7 is a malformed op.  fetches: whether FETCH columns are known - the
-        decoder of the _fetch entry points, where the program would be routed after fetch() declared one (None: self.fetches), which
-        knows quotients too; otherwise kind 7 is an unknown kind."""
-        fetches = self.fetches if fetches is None else fetches
-        divs = (self.divs if divs is None else divs) or fetches
-        links = (self.links if links is None else links) or divs
-        lookups = (self.lookups if lookups is None else lookups) or links
+        broken.  n: the trace length a chain group's block length is held against (None: not yet known).  level: the MainLevel whose
+        decoder is mirrored (None: self.level, where the program would be routed after what was declared).  Below LK kind 6 is an
+        unknown kind; below LINK the bits of a CHAIN column's pad at and above 16 belong to j; below DIV op 7 is a malformed op; below
+        FETCH kind 7 is an unknown kind.  The _main entry points' refusal of chain columns and op 6 was never modelled here, and is not:
+        MAIN is judged as REC."""
+        level = self.level if level is None else level
+        lookups, links, divs, fetches = (level >= at for at in (MainLevel.LK, MainLevel.LINK, MainLevel.DIV, MainLevel.FETCH))
         pos = (lambda pad: (pad >> 8) & 255) if links else (lambda pad: pad >> 8)
         n_count = n_fetch = 0
         if self._open is not None:
@@ -1005,76 +1028,33 @@ class MainProgram:
         m[:, :self.input_cols] %= P
         vals = [None] * len(self.ops)
 
-        def need(t):
-            todo, stack = set(), [t]
-            while stack:
-                u = stack.pop()
-                if u in todo or vals[u] is not None:
-                    continue
-                todo.add(u)
-                if self.ops[u][0] in _TWO_VALUES:
-                    stack += [self.ops[u][1], self.ops[u][2]]
-            for u in sorted(todo):
-                op, a, b = self.ops[u]
-                if op == OP_LOAD:
-                    vals[u] = np.roll(m[:, b], -a)
-                elif op == OP_PERIODIC:
-                    vals[u] = periodic[b][(np.arange(n) + a) % len(periodic[b])]
-                elif op == OP_CONST:
-                    vals[u] = np.full(n, self.consts[a], dtype=object)
-                elif op == OP_ADD:
-                    vals[u] = (vals[a] + vals[b]) % P
-                elif op == OP_SUB:
-                    vals[u] = (vals[a] - vals[b]) % P
-                elif op == OP_MUL:
-                    vals[u] = (vals[a] * vals[b]) % P
-                elif op == OP_DIV:    # (check() lets no row-local column reach here: kept for a program it was not asked about)
-                    vals[u] = (vals[a] * np.array(quotient_inverses(vals[b]), dtype=object)) % P
-                else:
-                    raise ValueError(f"main program: op {u} has the unknown code {op}")
-            return vals[t]
+        def unknown(u, op):
+            return f"main program: op {u} has the unknown code {op}"
 
-        def quotient_inverses(dens):
+        def quotient(num, dens):    # one batch inversion per op 7 (and step, over the blocks or runs)
             try:
-                return _batch_inverse([int(x) for x in dens])
+                return (num * np.array(_batch_inverse([int(x) for x in dens]), dtype=object)) % P
             except ValueError:
                 raise ValueError("main program: a denominator of a quotient (op 7) is zero on some row") from None
 
+        def need(t):
+            """The value of op t on all rows.  (check() lets no row-local column reach an op 7: kept for a program it was not asked about.)"""
+            _interpret(self.ops, _reachable(self.ops, [t], lambda u: vals[u] is not None), vals, unknown, lambda a: np.full(n, self.consts[a], dtype=object),
+                       load=lambda a, b: np.roll(m[:, b], -a), periodic=lambda a, b: periodic[b][(np.arange(n) + a) % len(periodic[b])], div=quotient)
+            return vals[t]
+
         def run(targets, rows, first, state):
             """The values of the ops `targets` on the rows `rows` alone, a LOAD of group column first + j being state[j]."""
-            got, stack = {}, list(targets)
-            todo = set()
-            while stack:
-                u = stack.pop()
-                if u in todo:
-                    continue
-                todo.add(u)
-                if self.ops[u][0] in _TWO_VALUES:
-                    stack += [self.ops[u][1], self.ops[u][2]]
-            for u in sorted(todo):
-                op, a, b = self.ops[u]
-                if op == OP_LOAD:
-                    got[u] = state[b - first] if first <= b < first + len(state) else m[(rows + a) % n, b]
-                elif op == OP_PERIODIC:
-                    got[u] = periodic[b][(rows + a) % len(periodic[b])]
-                elif op == OP_CONST:
-                    got[u] = np.full(len(rows), self.consts[a], dtype=object)
-                elif op == OP_ADD:
-                    got[u] = (got[a] + got[b]) % P
-                elif op == OP_SUB:
-                    got[u] = (got[a] - got[b]) % P
-                elif op == OP_MUL:
-                    got[u] = (got[a] * got[b]) % P
-                elif op == OP_DIV:    # one batch inversion per op and step, over the blocks (or runs)
-                    got[u] = (got[a] * np.array(quotient_inverses(got[b]), dtype=object)) % P
-                else:
-                    raise ValueError(f"main program: op {u} has the unknown code {op}")
+            got = {}
+            _interpret(self.ops, _reachable(self.ops, targets), got, unknown, lambda a: np.full(len(rows), self.consts[a], dtype=object),
+                       load=lambda a, b: state[b - first] if first <= b < first + len(state) else m[(rows + a) % n, b],
+                       periodic=lambda a, b: periodic[b][(rows + a) % len(periodic[b])], div=quotient)
             return [got[u] for u in targets]
 
         periodic = [np.array(values, dtype=object) for values in self.periodic_cols]
         for k, (kind, num_op, den_op, pad) in enumerate(self.cols):
             if kind == MAIN_CHAIN:
-                linked = self.links or self.divs or self.fetches    # (the _div and _fetch entry points read the k of a pad as the _link ones do)
+                linked = self.level >= MainLevel.LINK    # (the _div and _fetch entry points read the k of a pad as the _link ones do)
                 pos = (lambda pad: (pad >> 8) & 255) if linked else (lambda pad: pad >> 8)
                 if pos(pad):
                     continue            # (built with its group, at the column that opens it)
@@ -1167,7 +1147,7 @@ class ChainGroup:
             raise ValueError("main program: this chain group has its seeds already")
         if len(seeds) != len(self.cols):
             raise ValueError(f"main program: {len(seeds)} seeds for a chain group of {len(self.cols)} columns")
-        seeds = [x if isinstance(x, Value) else m.const(x) for x in seeds]
+        seeds = [m._lift(x) for x in seeds]
         if any(x.b is not m for x in seeds):
             raise ValueError("main program: the seeds must be values of this program")
         for col, x in zip(self.cols, seeds):
@@ -1184,7 +1164,7 @@ class ChainGroup:
             raise ValueError("main program: this chain group has no seeds yet: g.seed([...]) comes before g.step([...])")
         if len(nexts) != len(self.cols):
             raise ValueError(f"main program: {len(nexts)} next values for a chain group of {len(self.cols)} columns")
-        nexts = [x if isinstance(x, Value) else m.const(x) for x in nexts]
+        nexts = [m._lift(x) for x in nexts]
         if any(x.b is not m for x in nexts):
             raise ValueError("main program: the next values must be values of this program")
         for col, x in zip(self.cols, nexts):
@@ -1193,50 +1173,20 @@ class ChainGroup:
         m._open = None
 
 
-class PublicProgram:
+class PublicProgram(_ChallengeProgram):
     """Values computed from constants and the RAP challenges alone (sp_air_boundary_desc): const(v), rap(i) and + - * through Value.
     AirBuilder.boundary_from names two of them as the N and D of a boundary value."""
+    _what = "public values"
 
     def __init__(self, n_rap):
+        super().__init__()
         self.n_rap = n_rap
-        self.ops, self.consts = [], []
-        self._const_at = {}
-
-    def _emit(self, op, a, b):
-        self.ops.append((op, a, b))
-        return Value(self, len(self.ops) - 1)
-
-    def const(self, v):
-        v %= P
-        if v not in self._const_at:
-            self._const_at[v] = len(self.consts)
-            self.consts.append(v)
-        return self._emit(OP_CONST, self._const_at[v], 0)
-
-    def rap(self, i):
-        if not 0 <= i < self.n_rap:
-            raise ValueError(f"public values: RAP challenge {i} of {self.n_rap}")
-        return self._emit(OP_CONST, _RAP_TAG | i, 0)
-
-    def resolved_ops(self):
-        """The ops as the library reads them: RAP challenges follow the constants."""
-        return [(op, len(self.consts) + (a & ~_RAP_TAG) if op == OP_CONST and a & _RAP_TAG else a, b) for op, a, b in self.ops]
 
     def evaluate(self, rap):
         """Every op's value in Python integers."""
         values = list(self.consts) + [int(r) % P for r in rap]
-        vals = []
-        for op, a, b in self.resolved_ops():
-            if op == OP_CONST:
-                vals.append(values[a])
-            elif op == OP_ADD:
-                vals.append((vals[a] + vals[b]) % P)
-            elif op == OP_SUB:
-                vals.append((vals[a] - vals[b]) % P)
-            elif op == OP_MUL:
-                vals.append((vals[a] * vals[b]) % P)
-            else:
-                raise ValueError(f"public values: op {op}")
+        vals = [None] * len(self.ops)
+        _interpret(self.resolved_ops(), range(len(vals)), vals, lambda t, op: f"public values: op {op}", values.__getitem__)
         return vals
 
 
@@ -1257,7 +1207,7 @@ def ints_to_bytes(values):
     return np.ascontiguousarray(limbs.astype(">u8")).view(np.uint8).reshape(v.shape[0], v.shape[1], 32)
 
 
-class AirBuilder:
+class AirBuilder(_ChallengeProgram):
     def __init__(self, main_cols, offsets, degree_bound_factor, aux_cols=0, n_rap=0, aux_kind=AUX_NONE, num_transition_exemptions=1,
                  aux_builder=None, periodic=None, main_inputs=None):
         """aux_builder(rap: list[int]) -> (n, aux_cols) nested list of ints: the AIR's build_auxiliary_trace (aux_kind AUX_CALLBACK).
@@ -1265,6 +1215,7 @@ class AirBuilder:
         main_inputs: the number of main columns the caller supplies; the others are declared through b.main (MainProgram) and derived
         on the device (sp_air_prove_main).  None: the caller supplies the whole main segment."""
         assert 1 <= len(offsets) <= MAX_OFFSETS
+        super().__init__()
         self.periodic_cols = [[int(v) % P for v in values] for values in (periodic or [])]
         for k, values in enumerate(self.periodic_cols):
             if len(values) == 0 or len(values) & (len(values) - 1):
@@ -1273,7 +1224,7 @@ class AirBuilder:
         self.main_cols, self.aux_cols, self.offsets = main_cols, aux_cols, list(offsets)
         self.degree_bound_factor, self.n_rap, self.aux_kind = degree_bound_factor, n_rap, aux_kind
         self.num_transition_exemptions = num_transition_exemptions
-        self.ops, self.consts, self.degrees, self.exemptions, self.bcs = [], [], [], [], []
+        self.degrees, self.exemptions, self.bcs = [], [], []
         self.strides = []   # per constraint (period, offset): enforced on the rows = offset (mod period)
         # aux_kind AUX_PROGRAM: the auxiliary columns as a program over the main-trace row (sp_air_prove_aux)
         self.aux = AuxProgram(main_cols, n_rap, self.periodic_cols) if aux_kind == AUX_PROGRAM else None
@@ -1282,10 +1233,6 @@ class AirBuilder:
         self.bvalues = []
         # main_inputs: the derived main columns as a program over the main columns before them (sp_air_prove_main)
         self.main = MainProgram(main_inputs, main_cols, self.periodic_cols) if main_inputs is not None else None
-
-    def _emit(self, op, a, b):
-        self.ops.append((op, a, b))
-        return Value(self, len(self.ops) - 1)
 
     def load(self, row, col):
         """Cell (frame row `row` = index into the transition offsets, column `col` of main||aux)."""
@@ -1299,12 +1246,6 @@ class AirBuilder:
         if not 0 <= k < len(self.periodic_cols):
             raise ValueError(f"periodic: column {k} is not one of the AIR's {len(self.periodic_cols)} periodic columns")
         return self._emit(OP_PERIODIC, row, k)
-
-    def const(self, v):
-        v %= P
-        if v not in self.consts:
-            self.consts.append(v)
-        return self._emit(OP_CONST, self.consts.index(v), 0)
 
     def rap(self, i):
         assert i < self.n_rap
@@ -1329,9 +1270,7 @@ class AirBuilder:
     def boundary_from(self, col, step, num, den=None):
         """A boundary constraint whose value is N / D of b.public (D = 1 when None): known once the RAP challenges are - the reference's
         boundary_constraints(rap_challenges).  The descriptor holds 0 in its place; sp_air_prove_pub and its siblings put the value in."""
-        num = num if isinstance(num, Value) else self.public.const(num)
-        if den is not None and not isinstance(den, Value):
-            den = self.public.const(den)
+        num, den = self.public._lift(num), None if den is None else self.public._lift(den)
         if num.b is not self.public or (den is not None and den.b is not self.public):
             raise ValueError("boundary_from: N and D must be values of b.public")
         self.bvalues.append((len(self.bcs), num.i, AUX_NO_DEN if den is None else den.i))
@@ -1404,27 +1343,14 @@ class AirBuilder:
             raise ValueError(f"check_trace: {m.shape[1]} columns, the AIR has {self.main_cols} + {self.aux_cols}")
         consts = list(self.consts) + rap
         index = np.arange(n)
-        vals, outs = [], {}
-        for op, a, b in self.ops:
-            v = None
-            if op == OP_LOAD:
-                v = np.roll(m[:, b], -self.offsets[a])
-            elif op == OP_CONST:
-                v = np.full(n, consts[len(self.consts) + (a & ~_RAP_TAG) if a & _RAP_TAG else a], dtype=object)
-            elif op == OP_ADD:
-                v = (vals[a] + vals[b]) % P
-            elif op == OP_SUB:
-                v = (vals[a] - vals[b]) % P
-            elif op == OP_MUL:
-                v = (vals[a] * vals[b]) % P
-            elif op == OP_PERIODIC:
-                values = self.periodic_cols[b]
-                v = np.array(values, dtype=object)[(index + self.offsets[a]) % len(values)]
-            elif op == OP_OUT:
-                outs[a] = vals[b]
-            else:
-                raise ValueError(f"check_trace: op {op}")
-            vals.append(v)
+        vals, outs = [None] * len(self.ops), {}
+
+        def periodic(a, b):
+            values = self.periodic_cols[b]
+            return np.array(values, dtype=object)[(index + self.offsets[a]) % len(values)]
+
+        _interpret(self.resolved_ops(), range(len(vals)), vals, lambda t, op: f"check_trace: op {op}", lambda a: np.full(n, consts[a], dtype=object),
+                   load=lambda a, b: np.roll(m[:, b], -self.offsets[a]), periodic=periodic, out=outs.__setitem__)
         found = []
         for k, ex in enumerate(self.enforced_exemptions()):
             if k not in outs:
@@ -1527,9 +1453,7 @@ class AirBuilder:
         d.num_transition_exemptions = self.num_transition_exemptions
         d.degree_bound_factor = self.degree_bound_factor
         ops = (AirOpC * len(self.ops))()
-        for i, (op, a, b) in enumerate(self.ops):
-            if op == OP_CONST and (a & _RAP_TAG):
-                a = len(self.consts) + (a & ~_RAP_TAG)   # RAP challenges follow the constants
+        for i, (op, a, b) in enumerate(self.resolved_ops()):
             ops[i].op, ops[i].a, ops[i].b = op, a, b
         consts = ctypes.create_string_buffer(b"".join(c.to_bytes(32, "big") for c in self.consts), max(1, 32 * len(self.consts)))
         bcs = (AirBoundaryC * max(1, len(self.bcs)))()
@@ -1579,11 +1503,9 @@ class AirBuilder:
         if self.main is not None:
             m_desc, m_keep = main_desc(self.main.input_cols, self.main.ops, self.main.consts, self.main.cols)
             d.main_desc = m_desc
-            d.main_needs_rec = any(c[0] == MAIN_CHAIN for c in self.main.cols) or any(op == OP_PERIODIC for op, _, _ in self.main.ops)
-            d.main_needs_lk = any(c[0] == MAIN_COUNT for c in self.main.cols)
-            d.main_needs_link = self.main.links and any(c[0] == MAIN_CHAIN and c[3] >> 16 for c in self.main.cols)
-            d.main_needs_div = any(op == OP_DIV for op, _, _ in self.main.ops)
-            d.main_needs_fetch = self.main.fetches and any(c[0] == MAIN_FETCH for c in self.main.cols)
+            # (LINK and FETCH only where the program declared them: below its level check() has read those pad bits as a j)
+            d.main_features = _demanded([(c[0], c[3]) for c in self.main.cols], [op for op, _, _ in self.main.ops]) - {
+                level for level in (MainLevel.LINK, MainLevel.FETCH) if self.main.level < level}
             keep = keep + (m_desc, m_keep)
         return d, keep
 

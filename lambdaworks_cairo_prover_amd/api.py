@@ -241,21 +241,17 @@ class Context:
     def air_main_trace(self, desc, inputs):
         """sp_air_main_trace: the whole main segment the prover would commit for a desc with a main-trace program (AirBuilder(...,
         main_inputs=I)), built on the device from the input columns: (n, main_cols, 32) uint8 in the context encoding.  No commitment.
-        A program with a chain column or a read of a periodic column (air.needs_rec) goes to sp_air_main_trace_rec with the
-        descriptor's sp_air_ext, which carries the periodic columns; one with a lookup multiplicity (air.needs_lk) to
-        sp_air_main_trace_lk, one with a linked chain group (air.needs_link) to sp_air_main_trace_link, one with a quotient (op 7) behind
-        a chain group (air.needs_div) to sp_air_main_trace_div, one with a looked-up value (air.needs_fetch) to sp_air_main_trace_fetch,
-        with the same arguments."""
+        Above air.MainLevel.MAIN the program goes to the entry point of its level (air.main_level), with the descriptor's sp_air_ext."""
         main = getattr(desc, "main_desc", None)
         if main is None:
             raise ValueError("air_main_trace: the descriptor carries no main program (AirBuilder(..., main_inputs=...))")
         ptr, n, keep = self._air_rows(desc, inputs)
         out = np.empty((n, desc.main_cols, 32), dtype=np.uint8)
         from . import air
-        suffix = air.main_suffix(desc)
-        if suffix != "main":
+        level = air.main_level(desc)
+        if level != air.MainLevel.MAIN:
             ext = air.ext_of(desc)
-            check(getattr(self._lib, f"sp_air_main_trace_{suffix}")(self._h, ctypes.byref(desc), ctypes.byref(ext), ctypes.byref(main), ptr, ctypes.c_uint64(n), _u8p(out)))
+            check(getattr(self._lib, f"sp_air_main_trace_{level.suffix}")(self._h, ctypes.byref(desc), ctypes.byref(ext), ctypes.byref(main), ptr, ctypes.c_uint64(n), _u8p(out)))
         else:
             check(self._lib.sp_air_main_trace(self._h, ctypes.byref(desc), ctypes.byref(main), ptr, ctypes.c_uint64(n), _u8p(out)))
         return out
@@ -568,17 +564,15 @@ def air_boundary_resolve(bvals, rap):
 
 def air_main_check(desc, n, main=None):
     """sp_air_main_check (host): the decoder's verdict on a main-trace program (main, or desc.main_desc) for this AIR and n rows; raises
-    SpError with its refusal (SP_E_INVALID_ARG, or SP_E_UNSUPPORTED beside aux_kind 1 or 2).  A program with a chain column or a read of
-    a periodic column (air.needs_rec) is judged by sp_air_main_check_rec, beside the descriptor's periodic columns; one with a lookup
-    multiplicity (air.needs_lk) by sp_air_main_check_lk, one with a linked chain group (air.needs_link) by sp_air_main_check_link, one
-    with a quotient (air.needs_div) by sp_air_main_check_div, one with a looked-up value (air.needs_fetch) by sp_air_main_check_fetch."""
+    SpError with its refusal (SP_E_INVALID_ARG, or SP_E_UNSUPPORTED beside aux_kind 1 or 2).  Above air.MainLevel.MAIN the descriptor's
+    own program is judged by the entry point of its level (air.main_level), beside the descriptor's sp_air_ext."""
     from . import air
     own = getattr(desc, "main_desc", None)
     main = own if main is None else main
-    suffix = air.main_suffix(desc) if main is own else "main"
-    if suffix != "main":
+    level = air.main_level(desc) if main is own else air.MainLevel.MAIN
+    if level != air.MainLevel.MAIN:
         ext = air.ext_of(desc)
-        check(getattr(_lib.load(), f"sp_air_main_check_{suffix}")(ctypes.byref(desc), ctypes.byref(ext), ctypes.byref(main), ctypes.c_uint64(n)))
+        check(getattr(_lib.load(), f"sp_air_main_check_{level.suffix}")(ctypes.byref(desc), ctypes.byref(ext), ctypes.byref(main), ctypes.c_uint64(n)))
         return
     check(_lib.load().sp_air_main_check(ctypes.byref(desc), ctypes.byref(main), ctypes.c_uint64(n)))
 

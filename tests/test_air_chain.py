@@ -10,6 +10,7 @@ import re
 import pytest
 
 import chain_airs as C
+from air_main_checks import _col, _first, _op, check_with, decoder_refuses_and_the_builder_raises
 from lambdaworks_cairo_prover_amd import _lib, air, api
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -36,15 +37,6 @@ def test_symbols_are_declared_everywhere_and_the_abi_is_7(hip_lib):
     assert hip_lib.sp_air_main_chain_limits(None) == INVALID
 
 
-def check_rec(lib, desc, n=N, ext=True):
-    x = air.ext_of(desc) if ext else None
-    return lib.sp_air_main_check_rec(ctypes.byref(desc), None if x is None else ctypes.byref(x), ctypes.byref(desc.main_desc), ctypes.c_uint64(n))
-
-
-def check_old(lib, desc, n=N):
-    return lib.sp_air_main_check(ctypes.byref(desc), ctypes.byref(desc.main_desc), ctypes.c_uint64(n))
-
-
 def mixed_builder():
     return C.mixed(S, C.periodic_columns(random.Random(3)))[0]
 
@@ -69,10 +61,10 @@ def test_the_helpers_and_the_example_pass_the_decoder(hip_lib):
     for b in (mixed_builder(), wide_builder(), C.plain_pair(S), C.chain_permutation(S), mimc_builder(), C.mimc_case(N, S, random.Random(5), 3)[0]):
         desc, keep = b.build()
         assert air.needs_rec(desc)
-        assert check_rec(hip_lib, desc) == _lib.SP_OK, hip_lib.sp_last_error()
+        assert check_with(hip_lib, "rec", desc, N) == _lib.SP_OK, hip_lib.sp_last_error()
         api.air_main_check(desc, N)
     desc, keep = air.zero_count(N, 3).build()          # a program without either goes where it went
-    assert not air.needs_rec(desc) and air.route(desc, "prove")[0] == "sp_air_prove_main" and check_rec(hip_lib, desc) == _lib.SP_OK
+    assert not air.needs_rec(desc) and air.route(desc, "prove")[0] == "sp_air_prove_main" and check_with(hip_lib, "rec", desc, N) == _lib.SP_OK
     desc, keep = mimc_builder().build()
     assert [air.route(desc, c)[0] for c in ("prove", "check_trace")] == ["sp_air_prove_rec", "sp_air_check_trace_rec"]
     assert not air.route(desc, "verify")[0].endswith("_rec")
@@ -80,27 +72,6 @@ def test_the_helpers_and_the_example_pass_the_decoder(hip_lib):
 
 # ---- the refusal table: the same mutation on the builder's lists (ops [(op, a, b)], cols [(kind, num_op, den_op, pad)]) and, through
 # build(), on the C structs.  mixed: derived columns 0 .. 2 are group A (main columns 2 .. 4), 3 and 4 group B, 5 the VALUE, 6 the SUM.
-def _col(k, **fields):
-    def mutate(m):
-        c = dict(zip(("kind", "num_op", "den_op", "pad"), m.cols[k]))
-        c.update(fields)
-        m.cols[k] = (c["kind"], c["num_op"], c["den_op"], c["pad"])
-    return mutate
-
-
-def _first(m, want):
-    return next(t for t, o in enumerate(m.ops) if want(o))
-
-
-def _op(want, **fields):
-    def mutate(m):
-        t = _first(m, want)
-        o = dict(zip(("op", "a", "b"), m.ops[t]))
-        o.update(fields)
-        m.ops[t] = (o["op"], o["a"], o["b"])
-    return mutate
-
-
 def is_state_x0(o):
     return o == (air.OP_LOAD, 0, 2)
 
@@ -139,35 +110,20 @@ REFUSALS = [
 
 @pytest.mark.parametrize("build,mutate,code,says", [c[1:] for c in REFUSALS], ids=[c[0] for c in REFUSALS])
 def test_decoder_refuses_and_the_builder_raises(hip_lib, build, mutate, code, says):
-    desc, keep = build().build()
-    assert check_rec(hip_lib, desc) == _lib.SP_OK
-    b = build()
-    mutate(b.main)
-    with pytest.raises(ValueError) as e:          # the builder's mirror, rule for rule
-        b.main.check(N)
-    assert says.split(" (")[0] in str(e.value), str(e.value)
-    # the same lists as C structs, past the builder
-    main, main_keep = air.main_desc(b.main.input_cols, b.main.ops, b.main.consts, b.main.cols)
-    desc.main_desc = main
-    assert check_rec(hip_lib, desc) == code
-    message = hip_lib.sp_last_error().decode()
-    assert says in message and message.startswith("sp_air_main_check_rec: main program: "), message
-    with pytest.raises(api.SpError) as e:
-        api.air_main_check(desc, N)
-    assert e.value.code == code
+    decoder_refuses_and_the_builder_raises(hip_lib, "rec", build, mutate, says, N, code, mirror=says.split(" (")[0])
 
 
 def test_periodic_reads_need_the_periodic_columns(hip_lib):
     desc, keep = mixed_builder().build()
-    assert check_rec(hip_lib, desc, ext=False) == INVALID
+    assert check_with(hip_lib, "rec", desc, N, ext=False) == INVALID
     assert "reads periodic column 0, and the statement has 0" in hip_lib.sp_last_error().decode()
     ext = air.ext_of(desc)
     ext.periodic = None
     assert hip_lib.sp_air_main_check_rec(ctypes.byref(desc), ctypes.byref(ext), ctypes.byref(desc.main_desc), ctypes.c_uint64(N)) == INVALID
     desc, keep = C.plain_pair(S).build()           # no op 6: no ext needed
-    assert check_rec(hip_lib, desc, ext=False) == _lib.SP_OK
-    assert check_rec(hip_lib, desc, n=4) == INVALID and "l = 3" in hip_lib.sp_last_error().decode()     # blocks of 8 rows on 4
-    assert check_rec(hip_lib, desc, n=8) == _lib.SP_OK                                                    # the whole trace is one block
+    assert check_with(hip_lib, "rec", desc, N, ext=False) == _lib.SP_OK
+    assert check_with(hip_lib, "rec", desc, 4) == INVALID and "l = 3" in hip_lib.sp_last_error().decode()     # blocks of 8 rows on 4
+    assert check_with(hip_lib, "rec", desc, 8) == _lib.SP_OK                                                    # the whole trace is one block
     with pytest.raises(ValueError, match="l = 3"):
         C.plain_pair(S).main.evaluate([[1]] * 4)
 
@@ -176,23 +132,23 @@ def test_periodic_reads_need_the_periodic_columns(hip_lib):
 def test_host_built_auxiliary_kinds_stay_unsupported(hip_lib, kind):
     desc, keep = C.plain_pair(S).build()
     desc.aux_kind = kind
-    assert check_rec(hip_lib, desc) == UNSUPPORTED and "aux_kind" in hip_lib.sp_last_error().decode()
+    assert check_with(hip_lib, "rec", desc, N) == UNSUPPORTED and "aux_kind" in hip_lib.sp_last_error().decode()
 
 
 def test_the_old_entry_points_refuse_both(hip_lib):
     """Kind 5 is an unknown kind and op 6 a malformed op everywhere but through the _rec entry points."""
     desc, keep = C.plain_pair(S).build()
-    assert check_old(hip_lib, desc) == INVALID and "derived column 0 has an unknown kind" in hip_lib.sp_last_error().decode()
+    assert check_with(hip_lib, "", desc, N) == INVALID and "derived column 0 has an unknown kind" in hip_lib.sp_last_error().decode()
     for b in (mixed_builder(), mimc_builder()):
         desc, keep = b.build()
-        assert check_old(hip_lib, desc) == INVALID and "malformed op" in hip_lib.sp_last_error().decode()
+        assert check_with(hip_lib, "", desc, N) == INVALID and "malformed op" in hip_lib.sp_last_error().decode()
     # a row-local column that reads a periodic column, and no chain at all
     b = air.AirBuilder(2, [0], 1, periodic=[[1, 2]], main_inputs=1)
     b.main.value(b.main.load(0, 0) + b.main.periodic(1, 0))
     b.constraint(b.load(0, 0) - b.load(0, 0), degree=1, exemptions=0)
     desc, keep = b.build()
-    assert air.needs_rec(desc) and check_rec(hip_lib, desc) == _lib.SP_OK
-    assert check_old(hip_lib, desc) == INVALID and "malformed op" in hip_lib.sp_last_error().decode()
+    assert air.needs_rec(desc) and check_with(hip_lib, "rec", desc, N) == _lib.SP_OK
+    assert check_with(hip_lib, "", desc, N) == INVALID and "malformed op" in hip_lib.sp_last_error().decode()
     assert [int(r[1]) for r in b.main.evaluate([[10], [20], [30], [40]])] == [12, 21, 32, 41]
 
 

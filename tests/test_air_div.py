@@ -14,6 +14,7 @@ import chain_airs as C
 import div_airs as D
 import div_ref as R
 import link_airs as L
+from air_main_checks import _col, check_with, decoder_refuses_and_the_builder_raises
 from lambdaworks_cairo_prover_amd import _lib, air, api
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -36,13 +37,6 @@ def test_symbols_are_declared_everywhere_and_the_abi_is_7(hip_lib):
         assert name in declared and name in rust and name in _lib.NEWEST_SYMBOLS and hasattr(hip_lib, name), name
     assert int(re.search(r"#define SP_ABI_VERSION\s+(\d+)", header).group(1)) == _lib.SP_ABI_VERSION == hip_lib.sp_abi_version() == 7
     assert int(re.search(r"#define SP_AIR_OP_DIV\s+(\d+)", header).group(1)) == air.OP_DIV == 7
-
-
-def check_with(lib, suffix, desc, n=N):
-    if suffix == "":
-        return lib.sp_air_main_check(ctypes.byref(desc), ctypes.byref(desc.main_desc), ctypes.c_uint64(n))
-    x = air.ext_of(desc)
-    return getattr(lib, f"sp_air_main_check_{suffix}")(ctypes.byref(desc), ctypes.byref(x), ctypes.byref(desc.main_desc), ctypes.c_uint64(n))
 
 
 def mixed_builder(link=LINK):
@@ -78,11 +72,11 @@ def test_the_helpers_and_the_example_pass_the_decoder(hip_lib):
     for b in (mixed_builder(), mixed_builder(link=1), ec_builder(), D.plain_div(S)):
         desc, keep = b.build()
         assert air.needs_div(desc) and air.main_suffix(desc) == "div"
-        assert check_with(hip_lib, "div", desc) == _lib.SP_OK, hip_lib.sp_last_error()
+        assert check_with(hip_lib, "div", desc, N) == _lib.SP_OK, hip_lib.sp_last_error()
         api.air_main_check(desc, N)
         assert [air.route(desc, c)[0] for c in ("prove", "check_trace")] == ["sp_air_prove_div", "sp_air_check_trace_div"]
         assert not air.route(desc, "verify")[0].endswith("_div")
-        del desc.main_needs_div                      # a descriptor put together by hand is looked through
+        del desc.main_features                       # a descriptor put together by hand is looked through
         assert air.needs_div(desc) and air.main_suffix(desc) == "div"
 
 
@@ -92,8 +86,8 @@ def test_the_suffix_is_div_only_where_a_descriptor_needs_it(hip_lib):
                     (D.poly_only(S), "rec")):
         desc, keep = b.build()
         assert not air.needs_div(desc) and air.main_suffix(desc) == want
-        assert check_with(hip_lib, "div", desc) == _lib.SP_OK, hip_lib.sp_last_error()      # the _div entry points take what the others take
-        del desc.main_needs_div
+        assert check_with(hip_lib, "div", desc, N) == _lib.SP_OK, hip_lib.sp_last_error()      # the _div entry points take what the others take
+        del desc.main_features
         assert not air.needs_div(desc) and air.main_suffix(desc) == want
 
 
@@ -103,23 +97,15 @@ def test_the_entry_points_before_call_op_7_malformed_as_ever(hip_lib, suffix):
     for b in cases:
         desc, keep = b.build()
         t = next(t for t, o in enumerate(b.main.ops) if o[0] == air.OP_DIV)
-        assert check_with(hip_lib, suffix, desc) == INVALID
+        assert check_with(hip_lib, suffix, desc, N) == INVALID
         name = "sp_air_main_check" + ("_" + suffix if suffix else "")
         assert hip_lib.sp_last_error().decode() == f"{name}: " + MALFORMED_BEFORE.format(t=t)
         with pytest.raises(ValueError, match=f"main program: malformed op {t} \\(LOAD, CONST, ADD, SUB, MUL over earlier ops, PERIODIC only\\)"):
-            b.main.check(N, divs=False)
+            b.main.check(N, level=air.MainLevel[suffix.upper() or "MAIN"])
 
 
 # ---- the refusal table: the same mutation on the builder's lists and, through main_desc, on the C structs.  mixed: derived columns
 # 0 .. 2 are group A, 3 and 4 group B, 5 and 6 group C, 7 .. 22 group D, 23 the VALUE, 24 the SUM.
-def _col(k, **fields):
-    def mutate(m):
-        c = dict(zip(("kind", "num_op", "den_op", "pad"), m.cols[k]))
-        c.update(fields)
-        m.cols[k] = (c["kind"], c["num_op"], c["den_op"], c["pad"])
-    return mutate
-
-
 def _a_quotient(m, nth=1):
     """The nth op 7 of the program (0: the dead one over a zero)."""
     return [t for t, o in enumerate(m.ops) if o[0] == air.OP_DIV][nth]
@@ -184,25 +170,12 @@ REFUSALS = [
 
 @pytest.mark.parametrize("mutate,says", [c[1:] for c in REFUSALS], ids=[c[0] for c in REFUSALS])
 def test_decoder_refuses_and_the_builder_raises_word_for_word(hip_lib, mutate, says):
-    desc, keep = mixed_builder().build()
-    assert check_with(hip_lib, "div", desc) == _lib.SP_OK
-    b = mixed_builder()
-    assert _a_quotient(b.main) == 15
-    mutate(b.main)
-    with pytest.raises(ValueError) as e:          # the builder's mirror, rule for rule
-        b.main.check(N)
-    assert str(e.value).startswith("main program: " + says), str(e.value)
-    # the same lists as C structs, past the builder
-    main, main_keep = air.main_desc(b.main.input_cols, b.main.ops, b.main.consts, b.main.cols)
-    desc.main_desc = main
-    assert check_with(hip_lib, "div", desc) == INVALID
-    message = hip_lib.sp_last_error().decode()
+    assert _a_quotient(mixed_builder().main) == 15
+    raised, message = decoder_refuses_and_the_builder_raises(hip_lib, "div", mixed_builder, mutate, says, N)
+    assert raised.startswith("main program: " + says), raised
     assert message.startswith("sp_air_main_check_div: main program: " + says), message
     if "quotient" in says:
-        assert message == "sp_air_main_check_div: " + str(e.value)
-    with pytest.raises(api.SpError) as e:
-        api.air_main_check(desc, N)
-    assert e.value.code == INVALID
+        assert message == "sp_air_main_check_div: " + raised
 
 
 def test_null_arguments(hip_lib):

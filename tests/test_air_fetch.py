@@ -11,6 +11,7 @@ import pytest
 
 import fetch_airs as F
 import fetch_ref as R
+from air_main_checks import _col, _op, check_with, decoder_refuses_and_the_builder_raises
 from lambdaworks_cairo_prover_amd import _lib, air, api
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -38,15 +39,6 @@ def test_the_limits_call(hip_lib):
     want = {"key_bits": air.MAIN_FETCH_MAX_KEY_BITS, "group": air.MAIN_FETCH_MAX_GROUP, "columns": air.MAIN_FETCH_MAX_COLS}
     assert api.air_main_fetch_limits() == {"key_bits": 64, "group": 16, "columns": 64} == want
     assert hip_lib.sp_air_main_fetch_limits(None) == INVALID
-
-
-def check_with(lib, suffix, desc, n=N):
-    x = air.ext_of(desc)
-    return getattr(lib, f"sp_air_main_check_{suffix}")(ctypes.byref(desc), ctypes.byref(x), ctypes.byref(desc.main_desc), ctypes.c_uint64(n))
-
-
-def check_fetch(lib, desc, n=N):
-    return check_with(lib, "fetch", desc, n)
 
 
 # ---- the model against the plain reference --------------------------------------------------------------------------------------
@@ -167,26 +159,18 @@ def test_the_helpers_and_the_examples_pass_the_decoder(hip_lib):
     for b in builders():
         desc, keep = b.build()
         assert air.needs_fetch(desc) and air.main_suffix(desc) == "fetch"
-        assert check_fetch(hip_lib, desc, 256) == _lib.SP_OK, hip_lib.sp_last_error()
+        assert check_with(hip_lib, "fetch", desc, 256) == _lib.SP_OK, hip_lib.sp_last_error()
         api.air_main_check(desc, 256)
         assert [air.route(desc, c)[0] for c in ("prove", "check_trace")] == ["sp_air_prove_fetch", "sp_air_check_trace_fetch"]
         assert not air.route(desc, "verify")[0].endswith("_fetch")
     # programs without a FETCH column go where they went, and the new decoder takes them too
     for b, suffix in ((air.zero_count(N, 3), "main"), (air.mimc_blocks(N, 8, [7] * 8, 0), "rec"), (air.xor_lookup(256, 4), "lk")):
         desc, keep = b.build()
-        assert not air.needs_fetch(desc) and air.main_suffix(desc) == suffix and check_fetch(hip_lib, desc, 256) == _lib.SP_OK
+        assert not air.needs_fetch(desc) and air.main_suffix(desc) == suffix and check_with(hip_lib, "fetch", desc, 256) == _lib.SP_OK
     # a descriptor put together by hand is looked through
     desc, keep = F.input_fetch(1).build()
-    del desc.main_needs_fetch
+    del desc.main_features
     assert air.needs_fetch(desc)
-
-
-def _col(k, **fields):
-    def mutate(m):
-        c = dict(zip(("kind", "num_op", "den_op", "pad"), m.cols[k]))
-        c.update(fields)
-        m.cols[k] = (c["kind"], c["num_op"], c["den_op"], c["pad"])
-    return mutate
 
 
 def _pad(k, key_bits=None, v_op=None, high=0):
@@ -195,15 +179,6 @@ def _pad(k, key_bits=None, v_op=None, high=0):
         bits = pad & 255 if key_bits is None else key_bits
         v = (pad >> 8) & 65535 if v_op is None else v_op
         m.cols[k] = (kind, num_op, den_op, bits + 256 * v + high)
-    return mutate
-
-
-def _op(want, **fields):
-    def mutate(m):
-        t = next(t for t, o in enumerate(m.ops) if want(o))
-        o = dict(zip(("op", "a", "b"), m.ops[t]))
-        o.update(fields)
-        m.ops[t] = (o["op"], o["a"], o["b"])
     return mutate
 
 
@@ -257,22 +232,7 @@ REFUSALS = [
 
 @pytest.mark.parametrize("build,mutate,says", [c[1:] for c in REFUSALS], ids=[c[0] for c in REFUSALS])
 def test_decoder_refuses_and_the_builder_raises(hip_lib, build, mutate, says):
-    desc, keep = build().build()
-    assert check_fetch(hip_lib, desc) == _lib.SP_OK, hip_lib.sp_last_error()
-    b = build()
-    mutate(b.main)
-    with pytest.raises(ValueError) as e:          # the builder's mirror, word for word
-        b.main.check(N)
-    assert says in str(e.value), str(e.value)
-    # the same lists as C structs, past the builder
-    main, main_keep = air.main_desc(b.main.input_cols, b.main.ops, b.main.consts, b.main.cols)
-    desc.main_desc = main
-    assert check_fetch(hip_lib, desc) == INVALID
-    message = hip_lib.sp_last_error().decode()
-    assert says in message and message.startswith("sp_air_main_check_fetch: main program: "), message
-    with pytest.raises(api.SpError) as e:
-        api.air_main_check(desc, N)
-    assert e.value.code == INVALID
+    decoder_refuses_and_the_builder_raises(hip_lib, "fetch", build, mutate, says, N)
 
 
 def test_the_older_entry_points_call_kind_7_unknown(hip_lib):
@@ -282,18 +242,18 @@ def test_the_older_entry_points_call_kind_7_unknown(hip_lib):
         for suffix in ("div", "link", "lk", "rec"):
             if suffix == "rec" and any(c[0] == air.MAIN_COUNT for c in b.main.cols[:k]):
                 continue                                               # (the COUNT column before it is the unknown kind there)
-            assert check_with(hip_lib, suffix, desc) == INVALID, suffix
+            assert check_with(hip_lib, suffix, desc, N) == INVALID, suffix
             message = hip_lib.sp_last_error().decode()
             assert says in message and message.startswith(f"sp_air_main_check_{suffix}: main program: "), message
-        # the mirror follows the decoder the program would be routed to: without the builder's declaration, or on the keyword, kind 7
+        # the mirror follows the decoder the program would be routed to: without the builder's declaration, or at the level below, kind 7
         # is unknown
         with pytest.raises(ValueError, match=says):
-            b.main.check(N, fetches=False, divs=True)
+            b.main.check(N, level=air.MainLevel.DIV)
         b.main.check(N)
-        b.main.fetches = False
+        b.main.level = air.MainLevel.DIV
         with pytest.raises(ValueError, match=says):
             b.main.check(N)
-        b.main.check(N, fetches=True)
+        b.main.check(N, level=air.MainLevel.FETCH)
 
 
 def test_null_arguments(hip_lib):

@@ -11,6 +11,7 @@ import pytest
 
 import chain_airs as C
 import link_airs as L
+from air_main_checks import _col, _first, _op, check_with, decoder_refuses_and_the_builder_raises
 from lambdaworks_cairo_prover_amd import _lib, air, api
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -35,11 +36,6 @@ def test_symbols_are_declared_everywhere_and_the_abi_is_7(hip_lib):
     assert hip_lib.sp_air_main_link_limits(None) == INVALID
 
 
-def check_with(lib, suffix, desc, n=N):
-    x = air.ext_of(desc)
-    return getattr(lib, f"sp_air_main_check_{suffix}")(ctypes.byref(desc), ctypes.byref(x), ctypes.byref(desc.main_desc), ctypes.c_uint64(n))
-
-
 def mixed_builder():
     return L.mixed(S, LINK, L.periodic_columns(random.Random(3)))[0]
 
@@ -56,7 +52,7 @@ def test_the_helpers_and_the_examples_pass_the_decoder(hip_lib):
     for b in (mixed_builder(), sponge_builder(), merkle_builder(), L.plain_link(S, LINK), L.link_permutation(S, LINK)):
         desc, keep = b.build()
         assert air.needs_link(desc) and air.main_suffix(desc) == "link"
-        assert check_with(hip_lib, "link", desc) == _lib.SP_OK, hip_lib.sp_last_error()
+        assert check_with(hip_lib, "link", desc, N) == _lib.SP_OK, hip_lib.sp_last_error()
         api.air_main_check(desc, N)
         assert [air.route(desc, c)[0] for c in ("prove", "check_trace")] == ["sp_air_prove_link", "sp_air_check_trace_link"]
         assert not air.route(desc, "verify")[0].endswith("_link")
@@ -67,11 +63,11 @@ def test_the_suffix_is_link_only_where_a_descriptor_needs_it(hip_lib):
                     (C.mixed(8, C.periodic_columns(random.Random(7)))[0], "rec")):
         desc, keep = b.build()
         assert not air.needs_link(desc) and air.main_suffix(desc) == want
-        assert check_with(hip_lib, "link", desc) == _lib.SP_OK, hip_lib.sp_last_error()     # the _link entry points take what the others take
-        del desc.main_needs_link                                                             # a descriptor put together by hand is looked through
+        assert check_with(hip_lib, "link", desc, N) == _lib.SP_OK, hip_lib.sp_last_error()     # the _link entry points take what the others take
+        del desc.main_features                                                               # a descriptor put together by hand is looked through
         assert not air.needs_link(desc) and air.main_suffix(desc) == want
     desc, keep = sponge_builder().build()
-    del desc.main_needs_link
+    del desc.main_features
     assert air.needs_link(desc) and air.main_suffix(desc) == "link"
     # a group opened with link=1 is today's group, bit for bit
     b = air.AirBuilder(3, [0], 1, main_inputs=1)
@@ -86,38 +82,17 @@ def test_the_entry_points_before_refuse_a_linked_descriptor_as_ever(hip_lib, suf
     """There the bits at and above 16 belong to j: a j out of sequence, with the code and the message of before."""
     for b in (sponge_builder(), mixed_builder()):
         desc, keep = b.build()
-        assert check_with(hip_lib, suffix, desc) == INVALID
+        assert check_with(hip_lib, suffix, desc, N) == INVALID
         message = hip_lib.sp_last_error().decode()
         assert message.startswith(f"sp_air_main_check_{suffix}: main program: derived column 0 is a CHAIN column with j = {256 * LOG_LINK} out of sequence "
                                   "(no group is open: j = 0 opens one)"), message
         with pytest.raises(ValueError, match=f"derived column 0 is a CHAIN column with j = {256 * LOG_LINK} out of sequence"):
-            b.main.check(N, links=False)
+            b.main.check(N, level=air.MainLevel[suffix.upper()])
 
 
 # ---- the refusal table: the same mutation on the builder's lists (ops [(op, a, b)], cols [(kind, num_op, den_op, pad)]) and, through
 # build(), on the C structs.  mixed: derived columns 0 .. 2 are group A (main columns 2 .. 4, linked), 3 and 4 group B (k = 0), 5 .. 20
 # group C (linked), 21 the VALUE, 22 the SUM.
-def _col(k, **fields):
-    def mutate(m):
-        c = dict(zip(("kind", "num_op", "den_op", "pad"), m.cols[k]))
-        c.update(fields)
-        m.cols[k] = (c["kind"], c["num_op"], c["den_op"], c["pad"])
-    return mutate
-
-
-def _first(m, want):
-    return next(t for t, o in enumerate(m.ops) if want(o))
-
-
-def _op(want, **fields):
-    def mutate(m):
-        t = _first(m, want)
-        o = dict(zip(("op", "a", "b"), m.ops[t]))
-        o.update(fields)
-        m.ops[t] = (o["op"], o["a"], o["b"])
-    return mutate
-
-
 def is_load_x0(o):       # the first of them is the carry that the seed of x1 reads
     return o == (air.OP_LOAD, 0, 2)
 
@@ -160,28 +135,13 @@ REFUSALS = [
 
 @pytest.mark.parametrize("mutate,says", [c[1:] for c in REFUSALS], ids=[c[0] for c in REFUSALS])
 def test_decoder_refuses_and_the_builder_raises(hip_lib, mutate, says):
-    desc, keep = mixed_builder().build()
-    assert check_with(hip_lib, "link", desc) == _lib.SP_OK
-    b = mixed_builder()
-    mutate(b.main)
-    with pytest.raises(ValueError) as e:          # the builder's mirror, rule for rule
-        b.main.check(N)
-    assert says.split(" (")[0] in str(e.value), str(e.value)
-    # the same lists as C structs, past the builder
-    main, main_keep = air.main_desc(b.main.input_cols, b.main.ops, b.main.consts, b.main.cols)
-    desc.main_desc = main
-    assert check_with(hip_lib, "link", desc) == INVALID
-    message = hip_lib.sp_last_error().decode()
-    assert says in message and message.startswith("sp_air_main_check_link: main program: "), message
-    with pytest.raises(api.SpError) as e:
-        api.air_main_check(desc, N)
-    assert e.value.code == INVALID
+    decoder_refuses_and_the_builder_raises(hip_lib, "link", mixed_builder, mutate, says, N, mirror=says.split(" (")[0])
 
 
 def test_a_run_is_held_against_n(hip_lib):
     desc, keep = L.plain_link(S, LINK).build()
-    assert check_with(hip_lib, "link", desc, n=8) == INVALID and "l + k = 4" in hip_lib.sp_last_error().decode()      # runs of 16 rows on 8
-    assert check_with(hip_lib, "link", desc, n=16) == _lib.SP_OK                                                       # the whole trace is one run
+    assert check_with(hip_lib, "link", desc, 8) == INVALID and "l + k = 4" in hip_lib.sp_last_error().decode()      # runs of 16 rows on 8
+    assert check_with(hip_lib, "link", desc, 16) == _lib.SP_OK                                                       # the whole trace is one run
     with pytest.raises(ValueError, match="l \\+ k = 4"):
         L.plain_link(S, LINK).main.evaluate([[1]] * 8)
 

@@ -10,6 +10,7 @@ import re
 import pytest
 
 import lookup_airs as L
+from air_main_checks import _col, _op, check_with, decoder_refuses_and_the_builder_raises
 from lambdaworks_cairo_prover_amd import _lib, air, api
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -38,20 +39,6 @@ def test_the_limits_call(hip_lib):
     assert hip_lib.sp_air_main_count_limits(None) == INVALID
 
 
-def check_lk(lib, desc, n=N, ext=True):
-    x = air.ext_of(desc) if ext else None
-    return lib.sp_air_main_check_lk(ctypes.byref(desc), None if x is None else ctypes.byref(x), ctypes.byref(desc.main_desc), ctypes.c_uint64(n))
-
-
-def check_rec(lib, desc, n=N):
-    x = air.ext_of(desc)
-    return lib.sp_air_main_check_rec(ctypes.byref(desc), ctypes.byref(x), ctypes.byref(desc.main_desc), ctypes.c_uint64(n))
-
-
-def check_old(lib, desc, n=N):
-    return lib.sp_air_main_check(ctypes.byref(desc), ctypes.byref(desc.main_desc), ctypes.c_uint64(n))
-
-
 def periodic8():
     rng = random.Random(3)
     return [rng.randrange(P) for _ in range(L.MIXED_PERIOD)]
@@ -77,41 +64,24 @@ def test_the_helpers_and_the_examples_pass_the_decoder(hip_lib):
     for b in builders:
         desc, keep = b.build()
         assert air.needs_lk(desc)
-        assert check_lk(hip_lib, desc, 256) == _lib.SP_OK, hip_lib.sp_last_error()
+        assert check_with(hip_lib, "lk", desc, 256) == _lib.SP_OK, hip_lib.sp_last_error()
         api.air_main_check(desc, 256)
         assert [air.route(desc, c)[0] for c in ("prove", "check_trace")] == ["sp_air_prove_lk", "sp_air_check_trace_lk"]
         assert not air.route(desc, "verify")[0].endswith("_lk")
     # programs without a COUNT column go where they went, and the new decoder takes them too
     desc, keep = air.zero_count(N, 3).build()
-    assert not air.needs_lk(desc) and air.route(desc, "prove")[0] == "sp_air_prove_main" and check_lk(hip_lib, desc) == _lib.SP_OK
+    assert not air.needs_lk(desc) and air.route(desc, "prove")[0] == "sp_air_prove_main" and check_with(hip_lib, "lk", desc, N) == _lib.SP_OK
     keys = [7] * 8
     desc, keep = air.mimc_blocks(N, 8, keys, 0).build()
-    assert not air.needs_lk(desc) and air.route(desc, "prove")[0] == "sp_air_prove_rec" and check_lk(hip_lib, desc) == _lib.SP_OK
+    assert not air.needs_lk(desc) and air.route(desc, "prove")[0] == "sp_air_prove_rec" and check_with(hip_lib, "lk", desc, N) == _lib.SP_OK
     # a descriptor put together by hand is looked through
     desc, keep = L.plain_count().build()
-    del desc.main_needs_lk
+    del desc.main_features
     assert air.needs_lk(desc)
 
 
 # ---- the refusal table: the same mutation on the builder's lists (ops [(op, a, b)], cols [(kind, num_op, den_op, pad)]) and, through
 # build(), on the C structs.  mixed: derived column 0 is the VALUE (main column 2), 1 the COUNT, 2 the SUM.
-def _col(k, **fields):
-    def mutate(m):
-        c = dict(zip(("kind", "num_op", "den_op", "pad"), m.cols[k]))
-        c.update(fields)
-        m.cols[k] = (c["kind"], c["num_op"], c["den_op"], c["pad"])
-    return mutate
-
-
-def _op(want, **fields):
-    def mutate(m):
-        t = next(t for t, o in enumerate(m.ops) if want(o))
-        o = dict(zip(("op", "a", "b"), m.ops[t]))
-        o.update(fields)
-        m.ops[t] = (o["op"], o["a"], o["b"])
-    return mutate
-
-
 def _seventeenth(m):
     m.cols[16] = (air.MAIN_COUNT, m.cols[15][1], m.cols[15][2], 32)
 
@@ -131,40 +101,25 @@ REFUSALS = [
 
 @pytest.mark.parametrize("build,mutate,says", [c[1:] for c in REFUSALS], ids=[c[0] for c in REFUSALS])
 def test_decoder_refuses_and_the_builder_raises(hip_lib, build, mutate, says):
-    desc, keep = build().build()
-    assert check_lk(hip_lib, desc) == _lib.SP_OK
-    b = build()
-    mutate(b.main)
-    with pytest.raises(ValueError) as e:          # the builder's mirror, rule for rule
-        b.main.check(N)
-    assert says.split(" (")[0] in str(e.value), str(e.value)
-    # the same lists as C structs, past the builder
-    main, main_keep = air.main_desc(b.main.input_cols, b.main.ops, b.main.consts, b.main.cols)
-    desc.main_desc = main
-    assert check_lk(hip_lib, desc) == INVALID
-    message = hip_lib.sp_last_error().decode()
-    assert says in message and message.startswith("sp_air_main_check_lk: main program: "), message
-    with pytest.raises(api.SpError) as e:
-        api.air_main_check(desc, N)
-    assert e.value.code == INVALID
+    decoder_refuses_and_the_builder_raises(hip_lib, "lk", build, mutate, says, N, mirror=says.split(" (")[0])
 
 
 def test_the_older_entry_points_call_kind_6_unknown(hip_lib):
     for b, k in ((mixed_builder(), 1), (L.plain_count(), 0), (air.table_lookup_main(N, [3, 5, 5, 9], 8), 0)):
         desc, keep = b.build()
         says = f"derived column {k} has an unknown kind"
-        assert check_rec(hip_lib, desc) == INVALID and says in hip_lib.sp_last_error().decode()
+        assert check_with(hip_lib, "rec", desc, N) == INVALID and says in hip_lib.sp_last_error().decode()
         if not any(o[0] == air.OP_PERIODIC for o in b.main.ops):     # (op 6 is a malformed op there, and the ops are judged first)
-            assert check_old(hip_lib, desc) == INVALID and says in hip_lib.sp_last_error().decode()
-        # the mirror follows the decoder the program would be routed to: without the builder's declaration, or on the keyword, kind 6
+            assert check_with(hip_lib, "", desc, N) == INVALID and says in hip_lib.sp_last_error().decode()
+        # the mirror follows the decoder the program would be routed to: without the builder's declaration, or at the level below, kind 6
         # is unknown
         with pytest.raises(ValueError, match=says):
-            b.main.check(N, lookups=False)
+            b.main.check(N, level=air.MainLevel.REC)
         b.main.check(N)
-        b.main.lookups = False
+        b.main.level = air.MainLevel.REC
         with pytest.raises(ValueError, match=says):
             b.main.check(N)
-        b.main.check(N, lookups=True)
+        b.main.check(N, level=air.MainLevel.LK)
 
 
 def test_null_arguments(hip_lib):
@@ -178,7 +133,7 @@ def test_null_arguments(hip_lib):
     bad = air.ext_of(desc)
     bad.size -= 8
     assert hip_lib.sp_air_main_check_lk(ctypes.byref(desc), ctypes.byref(bad), ctypes.byref(desc.main_desc), n) == INVALID
-    assert check_lk(hip_lib, desc, ext=False) == _lib.SP_OK            # no op 6: no ext needed
+    assert check_with(hip_lib, "lk", desc, N, ext=False) == _lib.SP_OK            # no op 6: no ext needed
 
 
 def test_builder_arguments():
