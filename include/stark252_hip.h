@@ -82,8 +82,9 @@ const char* sp_version(void);
  * sp_air_main_trace, sp_air_main_check and sp_air_main_desc_size, then sp_air_prove_rec, sp_air_check_trace_rec, sp_air_main_trace_rec,
  * sp_air_main_check_rec and sp_air_main_chain_limits, then sp_air_prove_lk, sp_air_check_trace_lk, sp_air_main_trace_lk, sp_air_main_check_lk
  * and sp_air_main_count_limits, then sp_air_prove_link, sp_air_check_trace_link, sp_air_main_trace_link, sp_air_main_check_link and
- * sp_air_main_link_limits, then sp_air_prove_div, sp_air_check_trace_div, sp_air_main_trace_div and sp_air_main_check_div, and last
- * sp_air_prove_fetch, sp_air_check_trace_fetch, sp_air_main_trace_fetch, sp_air_main_check_fetch and sp_air_main_fetch_limits).  A binding compares it (and sp_air_desc_size against its own idea of the struct) when it loads the library, so
+ * sp_air_main_link_limits, then sp_air_prove_div, sp_air_check_trace_div, sp_air_main_trace_div and sp_air_main_check_div, then
+ * sp_air_prove_fetch, sp_air_check_trace_fetch, sp_air_main_trace_fetch, sp_air_main_check_fetch and sp_air_main_fetch_limits, and last
+ * sp_air_prove_word, sp_air_check_trace_word, sp_air_main_trace_word, sp_air_main_check_word and sp_air_main_word_limits).  A binding compares it (and sp_air_desc_size against its own idea of the struct) when it loads the library, so
  * a stale build fails at load time with "rebuild the library" instead of with a missing symbol or shifted fields later. */
 #define SP_ABI_VERSION 7
 int sp_abi_version(void);
@@ -808,6 +809,41 @@ int sp_air_main_check_fetch(const sp_air_desc* air, const sp_air_ext* ext, const
 /* out[0] = the most key bits of a FETCH column (64), out[1] = the most FETCH columns that share one sort and one search (16), out[2] =
  * the most FETCH columns of one main program (64) */
 int sp_air_main_fetch_limits(uint32_t out[3]);
+
+/* ---- Limbs and bitwise words in a main program: the 16-bit limbs of a range check, the fields of an instruction word, AND, XOR and OR
+ * of two words are row-local functions of a value's CANONICAL INTEGER int(v), 0 <= int(v) < p - the one thing the field ops of a program
+ * cannot express; a BIT column is the one-bit case.  Through the _word entry points - and only through them: everywhere else kinds 8
+ * and 9 stay unknown kinds - a main program may hold columns of kind */
+#define SP_AIR_MAIN_LIMB        8  /* z_i = (int(N(i)) >> lo) mod 2^width                                                                  */
+#define SP_AIR_MAIN_WORD        9  /* z_i = int(N(i)) AND / OR / XOR int(D(i))                                                             */
+/* LIMB: num_op names N, den_op must be SP_AIR_AUX_NO_DEN (as for a BIT column), and pad = lo + 256 width with 1 <= width and lo + width
+ * <= 252 (so lo <= 251); a bit at or above 16 is refused.  width = 1 gives the cells of BIT lo, lo = 0 and width = 252 gives N.  Every
+ * canonical integer has limbs: there is no run-time error.
+ * WORD: num_op names N, den_op names D (SP_AIR_AUX_NO_DEN is refused), and pad = fn + 256 bits: fn (bits 0 - 7) 0 AND, 1 OR, 2 XOR, bits
+ * (bits 8 - 15) in 1 .. 251; a bit at or above 16 is refused.  2^251 < p, so every result is a canonical integer.  An operand at or above
+ * 2^bits on any row fails the call with SP_E_INVALID_ARG, "a word operand is out of range on some row (both operands of a WORD column
+ * must be below 2^bits as canonical integers)": nothing is returned and the context goes on.  It is reported behind a key out of range
+ * and a fetched key in no table row, and before a zero denominator of the same program.
+ * Both kinds are row-local: N and D follow the rules of a VALUE column's operands - earlier columns only, at shifts 0 .. 7 (wrapping),
+ * periodic columns (op 6), behind no op 7 - and any later column of any kind may read them: the X of a COUNT or FETCH column, a chain
+ * seed, a scan.  LIMB columns with one N share one pass out of Montgomery form, WORD columns with one N, D and bits two.  Shifts,
+ * rotations, NOT, add-with-carry and comparisons are a LIMB and a VALUE column - rotl(x, r) over w bits = limb(x, 0, w - r) 2^r +
+ * limb(x, w - r, r) - and have no kind of their own.  The _word entry points accept everything the _fetch ones do; they refuse, with
+ * SP_E_INVALID_ARG and a message that names the column, before anything is sized: a pad with a bit at or above 16, a LIMB with width 0,
+ * with lo + width > 252 or with a denominator, a WORD without a second operand, with fn > 2 or with bits 0 or above 251, an operand
+ * beyond the program, behind an op 7 or reading a column that is not an earlier one.  The proof is unchanged: the same table gives the
+ * same bytes.  Argument lists as the _fetch entry points. */
+int sp_air_prove_word(sp_ctx* ctx, const sp_air_desc* air, const sp_air_ext* ext, const sp_air_boundary_desc* bvals, const sp_air_main_desc* main,
+                      const void* inputs, uint64_t n, const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len);
+int sp_air_check_trace_word(sp_ctx* ctx, const sp_air_desc* air, const sp_air_ext* ext, const sp_air_boundary_desc* bvals, const sp_air_main_desc* main,
+                            const void* inputs, uint64_t n, const sp_proof_options* opt, const uint8_t* rap, sp_air_violation* out, uint32_t cap,
+                            uint32_t* n_out);
+int sp_air_main_trace_word(sp_ctx* ctx, const sp_air_desc* air, const sp_air_ext* ext, const sp_air_main_desc* main, const void* inputs, uint64_t n,
+                           uint8_t* rows_out);
+int sp_air_main_check_word(const sp_air_desc* air, const sp_air_ext* ext, const sp_air_main_desc* main, uint64_t n);
+/* out[0] = the most lo + width of a LIMB column (252), out[1] = the most bits of a WORD column (251), out[2] = the number of WORD
+ * functions (3: fn 0 .. 2), out[3] = 0 */
+int sp_air_main_word_limits(uint32_t out[4]);
 
 /* verify::<Stark252PrimeField, A> (reference src/starks/verifier.rs:559-657) on the host CPU: 1 accept, 0 reject (also for
  * malformed proofs or descriptors). */

@@ -215,6 +215,10 @@ MAIN_COUNT_MAX_KEY_BITS, MAIN_COUNT_MAX_COLS = 64, 16   # sp_air_main_count_limi
 MAIN_LINK_MAX_LOG, MAIN_LINK_MAX_WIDTH = 62, 16         # sp_air_main_link_limits
 MAIN_FETCH = SP_AIR_MAIN_FETCH = 7                      # sp_air_main_column.kind of a looked-up value (the _fetch entry points)
 MAIN_FETCH_MAX_KEY_BITS, MAIN_FETCH_MAX_GROUP, MAIN_FETCH_MAX_COLS = 64, 16, 64   # sp_air_main_fetch_limits
+MAIN_LIMB = SP_AIR_MAIN_LIMB = 8                        # sp_air_main_column.kind of a limb of a canonical integer (the _word entry points)
+MAIN_WORD = SP_AIR_MAIN_WORD = 9                        # ... and of the AND, OR or XOR of two (the _word entry points)
+MAIN_LIMB_MAX_END, MAIN_WORD_MAX_BITS, MAIN_WORD_FUNCTIONS = 252, 251, 3   # sp_air_main_word_limits
+WORD_AND, WORD_OR, WORD_XOR = range(3)                  # the fn of a WORD column's pad
 INPUTS_HOST, INPUTS_DEVICE = 0, 1    # sp_air_main_desc.input_location
 
 
@@ -271,12 +275,25 @@ def needs_pub(desc):
 class MainLevel(enum.IntEnum):
     """The entry points a main-trace program goes through, in the order of sp::AirMainLevel (air_desc.h): each level's decoder knows what
     the levels below it know, and the entry points carry its suffix (sp_air_prove_rec, sp_air_main_check_rec, ...; sp_air_main_trace and
-    sp_air_main_check at MAIN)."""
+    sp_air_main_check at MAIN).  MainLevel.WORD, the level above FETCH, is the one member of MainLevelWord below: it orders, compares and
+    carries its suffix like a member, and iterating MainLevel goes on giving the six levels MAIN .. FETCH."""
     MAIN, REC, LK, LINK, DIV, FETCH = range(6)
 
     @property
     def suffix(self):
         return self.name.lower()
+
+
+class MainLevelWord(enum.IntEnum):
+    """sp::AirMainLevel::Word, the _word entry points (LIMB and WORD columns), reached as MainLevel.WORD.  An enumeration of its own:
+    an IntEnum with members cannot be extended, and what iterates MainLevel - tests/test_air_main_level.py holds each of its six levels
+    against the library and a worked example - goes on seeing those six; tests/test_air_word.py holds this one the same way."""
+    WORD = 6
+
+    suffix = MainLevel.suffix
+
+
+MainLevel.WORD = MainLevelWord.WORD
 
 
 # What in a main program demands each level above MAIN: a test of a column's (kind, pad) and a test of an op code (None: no such thing).
@@ -286,6 +303,7 @@ _MAIN_DEMANDS = {
     MainLevel.LINK: (lambda kind, pad: kind == MAIN_CHAIN and pad >> 16 != 0, None),          # a pad that carries k >= 1: runs of 2^k blocks
     MainLevel.DIV: (None, lambda op: op == OP_DIV),                                           # a quotient behind a chain group
     MainLevel.FETCH: (lambda kind, pad: kind == MAIN_FETCH, None),                            # a looked-up value
+    MainLevel.WORD: (lambda kind, pad: kind in (MAIN_LIMB, MAIN_WORD), None),                 # a limb or a bitwise word
 }
 
 
@@ -325,6 +343,7 @@ def needs_lk(desc): return MainLevel.LK in main_features(desc)
 def needs_link(desc): return MainLevel.LINK in main_features(desc)
 def needs_div(desc): return MainLevel.DIV in main_features(desc)
 def needs_fetch(desc): return MainLevel.FETCH in main_features(desc)
+def needs_word(desc): return MainLevel.WORD in main_features(desc)
 
 
 def route(desc, call):
@@ -722,7 +741,20 @@ class MainProgram(_Program):
                                        Returns the column as a Value (a load at shift 0).  A key that no table row holds fails the
                                        call (SP_E_INVALID_ARG; ValueError in evaluate): idle rows point at a key the table holds.
         fetch_many(X, T, [V...], key_bits)   one column per V, declared as one run: the device sorts the table and searches once for
-                                       up to 16 of them - the fields of an instruction word.  At most 64 FETCH columns."""
+                                       up to 16 of them - the fields of an instruction word.  At most 64 FETCH columns.
+
+    Pieces of a value's canonical integer int(x), 0 <= int(x) < p, wider than one bit, and bitwise functions of two
+    (sp_air_prove_word), are row-local again:
+
+        limb(x, lo, width)             z_i = (int(x(i)) >> lo) mod 2^width, 1 <= width, lo + width <= 252: a 16-bit limb of a range
+                                       check, a field of an instruction word.  Returns the column's index.
+        limbs(x, width, count)         `count` consecutive limbs of `width` bits from bit 0, one column each; they share x (the
+                                       device takes it out of Montgomery form once per row)
+        word_and(x, y, bits), word_or, word_xor   z_i = int(x(i)) AND / OR / XOR int(y(i)), 1 <= bits <= 251.  An x or y at or above
+                                       2^bits on some row fails the call (SP_E_INVALID_ARG; ValueError in evaluate).  Columns with one
+                                       x, y and bits share their two passes out of Montgomery form.
+        A shift, a rotation, NOT, an add with carry or a comparison is a limb and a value: rotl(x, r) over w bits is
+        value(limb(x, 0, w - r) 2^r + limb(x, w - r, r))."""
 
     def __init__(self, input_cols, main_cols, periodic_cols=()):
         if not 1 <= input_cols < main_cols:
@@ -732,13 +764,14 @@ class MainProgram(_Program):
         self.periodic_cols = periodic_cols   # the owning AirBuilder's periodic columns: what periodic() may read
         self.cols = []                       # (kind, num_op, den_op, pad)
         self._open = None                    # the chain group between chain() and step()
-        # the entry points whose decoder check() mirrors: multiplicity(), chain(link > 1), div() and fetch_many() raise it
+        # the entry points whose decoder check() mirrors: multiplicity(), chain(link > 1), div(), fetch_many(), limb() and word_*() raise it
         self.level = MainLevel.REC
 
     lookups = property(lambda self: self.level >= MainLevel.LK)     # what was declared, as the level says it
     links = property(lambda self: self.level >= MainLevel.LINK)
     divs = property(lambda self: self.level >= MainLevel.DIV)
     fetches = property(lambda self: self.level >= MainLevel.FETCH)
+    words = property(lambda self: self.level >= MainLevel.WORD)
 
     def load(self, shift, col):
         if not 0 <= shift <= AUX_MAX_SHIFT:
@@ -868,6 +901,38 @@ class MainProgram(_Program):
         cols = [self._column(MAIN_FETCH, x, table_key, key_bits + 256 * v.i) for v in values]
         return [self.load(0, c) for c in cols]
 
+    def limb(self, x, lo, width):
+        """Bits lo .. lo + width - 1 of the canonical integer of x (see the class): a LIMB column; returns its index."""
+        if lo < 0 or width < 1 or lo + width > MAIN_LIMB_MAX_END:
+            raise ValueError(f"main program: a limb of {width} bits from bit {lo} (1 <= width, 0 <= lo, lo + width <= {MAIN_LIMB_MAX_END})")
+        self.level = max(self.level, MainLevel.WORD)
+        return self._column(MAIN_LIMB, x, None, lo + 256 * width)
+
+    def limbs(self, x, width, count):
+        """`count` consecutive limbs of `width` bits of x from bit 0, one column each (they share x: one group on the device)."""
+        if count < 1 or width < 1 or width * count > MAIN_LIMB_MAX_END:
+            raise ValueError(f"main program: {count} limbs of {width} bits (at least one, and width * count <= {MAIN_LIMB_MAX_END})")
+        x = self._lift(x)
+        return [self.limb(x, j * width, width) for j in range(count)]
+
+    def _word(self, fn, x, y, bits):
+        if y is None:
+            raise ValueError("main program: a word column needs two operands")
+        if not 1 <= bits <= MAIN_WORD_MAX_BITS:
+            raise ValueError(f"main program: words of {bits} bits (1 .. {MAIN_WORD_MAX_BITS})")
+        self.level = max(self.level, MainLevel.WORD)
+        return self._column(MAIN_WORD, x, y, fn + 256 * bits)
+
+    def word_and(self, x, y, bits):
+        """int(x) AND int(y) of two values below 2^bits (see the class): a WORD column; returns its index."""
+        return self._word(WORD_AND, x, y, bits)
+
+    def word_or(self, x, y, bits):
+        return self._word(WORD_OR, x, y, bits)
+
+    def word_xor(self, x, y, bits):
+        return self._word(WORD_XOR, x, y, bits)
+
     def reads(self):
         """Per op: one more than the highest derived column its value depends on (0: inputs only) - what the decoder follows."""
         return self._reads(False)
@@ -893,10 +958,11 @@ class MainProgram(_Program):
         broken.  n: the trace length a chain group's block length is held against (None: not yet known).  level: the MainLevel whose
         decoder is mirrored (None: self.level, where the program would be routed after what was declared).  Below LK kind 6 is an
         unknown kind; below LINK the bits of a CHAIN column's pad at and above 16 belong to j; below DIV op 7 is a malformed op; below
-        FETCH kind 7 is an unknown kind.  The _main entry points' refusal of chain columns and op 6 was never modelled here, and is not:
-        MAIN is judged as REC."""
+        FETCH kind 7 is an unknown kind; below WORD kinds 8 and 9 are.  The _main entry points' refusal of chain columns and op 6 was
+        never modelled here, and is not: MAIN is judged as REC."""
         level = self.level if level is None else level
         lookups, links, divs, fetches = (level >= at for at in (MainLevel.LK, MainLevel.LINK, MainLevel.DIV, MainLevel.FETCH))
+        words = level >= MainLevel.WORD
         pos = (lambda pad: (pad >> 8) & 255) if links else (lambda pad: pad >> 8)
         n_count = n_fetch = 0
         if self._open is not None:
@@ -919,8 +985,33 @@ class MainProgram(_Program):
         g0 = g_end = 0      # the chain group that column k belongs to is [g0, g_end), when k < g_end
         for k, (kind, num_op, den_op, pad) in enumerate(self.cols):
             den = den_op != AUX_NO_DEN
-            if not MAIN_VALUE <= kind <= (MAIN_FETCH if fetches else MAIN_COUNT if lookups else MAIN_CHAIN):
+            if not MAIN_VALUE <= kind <= (MAIN_WORD if words else MAIN_FETCH if fetches else MAIN_COUNT if lookups else MAIN_CHAIN):
                 raise ValueError(f"main program: derived column {k} has an unknown kind")
+            if kind in (MAIN_LIMB, MAIN_WORD):
+                limb, low, high = kind == MAIN_LIMB, pad & 255, (pad >> 8) & 255      # LIMB: lo, width; WORD: fn, bits
+                who = f"main program: derived column {k} is a {'LIMB' if limb else 'WORD'} column"
+                if pad >> 16:
+                    raise ValueError(f"{who} whose pad has a bit at or above 16 (pad = {'lo + 256 width' if limb else 'fn + 256 bits'})")
+                if limb and den:
+                    raise ValueError(f"{who} and takes no denominator")
+                if not limb and not den:
+                    raise ValueError(f"{who} without a second operand (den_op names it)")
+                if limb and high == 0:
+                    raise ValueError(f"{who} with width = 0 (1 <= width, lo + width <= {MAIN_LIMB_MAX_END})")
+                if limb and low + high > MAIN_LIMB_MAX_END:
+                    raise ValueError(f"{who} with lo + width = {low + high} (1 <= width, lo + width <= {MAIN_LIMB_MAX_END})")
+                if not limb and low >= MAIN_WORD_FUNCTIONS:
+                    raise ValueError(f"{who} with fn = {low} (0 AND, 1 OR, 2 XOR)")
+                if not limb and not 1 <= high <= MAIN_WORD_MAX_BITS:
+                    raise ValueError(f"{who} with bits = {high} (1 .. {MAIN_WORD_MAX_BITS})")
+                if not 0 <= num_op < len(self.ops) or (den and not 0 <= den_op < len(self.ops)):
+                    raise ValueError(f"main program: derived column {k} names an op beyond the program")
+                if quot[num_op] or (den and quot[den_op]):
+                    raise ValueError(f"main program: derived column {k} {refused}")
+                r = max(reads[num_op], reads[den_op] if den else 0)
+                if r > k:
+                    raise ValueError(f"main program: derived column {k} reads derived column {r - 1}, which is not an earlier one")
+                continue
             if kind == MAIN_FETCH:
                 key_bits, v_op = pad & 255, (pad >> 8) & 65535
                 if pad >> 24:
@@ -1018,7 +1109,8 @@ class MainProgram(_Program):
         batch inversion per op and step, over the blocks or runs; ValueError on a zero under one that a seed or a step reaches.  A COUNT
         column is a dictionary count of X, read on the first row of each table value; ValueError on a key at or above 2^key_bits.  A
         FETCH column is a dictionary from each table key to the first row that holds it; ValueError on a key out of range (the COUNT
-        columns' words) or on a looked-up key that no row holds."""
+        columns' words) or on a looked-up key that no row holds.  LIMB and WORD columns are Python's shifts, masks and bitwise operators
+        on the integers; ValueError, in the device's words, on a WORD operand at or above 2^bits."""
         import numpy as np
         self.check(len(input_rows))
         rows = input_rows if not isinstance(input_rows, np.ndarray) else input_rows.astype(object)
@@ -1096,6 +1188,18 @@ class MainProgram(_Program):
                 if any(v not in first for v in xs):
                     raise ValueError("main program: a fetched key is in no table row")
                 m[:, self.input_cols + k] = [vs[first[v]] for v in xs]
+                continue
+            if kind == MAIN_LIMB:
+                lo, mask = pad & 255, (1 << ((pad >> 8) & 255)) - 1
+                m[:, self.input_cols + k] = [(int(x) >> lo) & mask for x in need(num_op)]
+                continue
+            if kind == MAIN_WORD:
+                fn, bits = pad & 255, (pad >> 8) & 255
+                xs, ys = [int(v) for v in need(num_op)], [int(v) for v in need(den_op)]
+                if any(v >> bits for v in xs) or any(v >> bits for v in ys):
+                    raise ValueError("main program: a word operand is out of range on some row (both operands of a WORD column must be below 2^bits "
+                                     "as canonical integers)")
+                m[:, self.input_cols + k] = [x & y if fn == WORD_AND else x | y if fn == WORD_OR else x ^ y for x, y in zip(xs, ys)]
                 continue
             t = need(num_op)
             if den_op != AUX_NO_DEN:
@@ -2175,6 +2279,95 @@ def rom_reads_trace(inputs):
         counts[addr_r] = counts.get(addr_r, 0) + 1
     return [[addr_w, val_w, addr_r, inputs[first[addr_r]][1], counts.get(addr_w, 0) if first[addr_w] == j else 0]
             for j, (addr_w, val_w, addr_r) in enumerate(inputs)]
+
+
+# ---- limbs and bitwise words: two worked examples ---------------------------------------------------------------------------------
+def limb_range_check(n, limb_bits, count=2):
+    """Every x_i is below 2^(limb_bits count), by limbs (the shape of Cairo's range-check builtin): one input x (column 0); the device
+    builds its `count` limbs of limb_bits bits (columns 1 .. count, MainProgram.limbs: one group) and m_j = multiplicity(limb_j, T,
+    limb_bits) for each (columns count + 1 .. 2 count), T periodic column 0, which holds all 2^limb_bits values (at most n of them).
+    One recomposition constraint x = sum_j 2^(j limb_bits) limb_j on every row, and per limb the LogUp running sum of table_lookup
+    (auxiliary column j, under one challenge).  The caller uploads n values where the table has n x (1 + 2 count); with bits() the same
+    range would take limb_bits count committed columns instead of count."""
+    if not (1 <= limb_bits <= MAIN_COUNT_MAX_KEY_BITS and 1 <= count <= MAIN_COUNT_MAX_COLS and limb_bits * count <= MAIN_WORD_MAX_BITS):
+        raise ValueError(f"limb_range_check: {count} limbs of {limb_bits} bits (at most {MAIN_COUNT_MAX_COLS} limbs, {MAIN_WORD_MAX_BITS} bits in all)")
+    if (1 << limb_bits) > n:
+        raise ValueError(f"limb_range_check: {1 << limb_bits} table entries on {n} rows")
+    main_cols = 1 + 2 * count
+    b = AirBuilder(main_cols, [0, 1], 2, aux_cols=count, n_rap=1, aux_kind=AUX_PROGRAM, periodic=[list(range(1 << limb_bits))], main_inputs=1)
+    m = b.main
+    limbs = m.limbs(m.load(0, 0), limb_bits, count)
+    mults = [m.multiplicity(m.load(0, c), m.periodic(0, 0), limb_bits) for c in limbs]
+    total = None
+    for j, c in enumerate(limbs):
+        term = b.load(0, c) * (1 << (j * limb_bits))
+        total = term if total is None else total + term
+    b.constraint(total - b.load(0, 0), degree=1, exemptions=0)
+    for j, (c, mult) in enumerate(zip(limbs, mults)):
+        _logup_sum(b, b.load(0, c), b.aux.load(0, c), mult, main_cols + j)
+    return b
+
+
+def limb_range_check_inputs(n, limb_bits, count, rng):
+    """(n, 1) Python ints below 2^(limb_bits count) from rng.randrange: the input column of limb_range_check."""
+    return [[rng.randrange(1 << (limb_bits * count))] for _ in range(n)]
+
+
+def limb_range_check_trace(inputs, limb_bits, count):
+    """The whole main table of limb_range_check as (n, 1 + 2 count) Python ints, from its input rows: shifts, masks and counts."""
+    n, mask = len(inputs), (1 << limb_bits) - 1
+    limbs = [[(int(x) % P >> (j * limb_bits)) & mask for j in range(count)] for (x,) in inputs]
+    counts = [{} for _ in range(count)]
+    for row in limbs:
+        for j, v in enumerate(row):
+            counts[j][v] = counts[j].get(v, 0) + 1
+    # (T(i) = i mod 2^limb_bits: the first row that holds a table value is the value itself)
+    return [[int(inputs[i][0]) % P] + limbs[i] + [counts[j].get(i, 0) if i <= mask else 0 for j in range(count)] for i in range(n)]
+
+
+def word_ops(n, bits):
+    """a = x AND y, o = x OR y and e = x XOR y on every row, for `bits`-bit x and y (the shape of Cairo's bitwise builtin, at a width a
+    bit decomposition can still pin down).  Inputs x and y (columns 0 and 1); the device builds the bits of x (columns 2 .. 1 + bits)
+    and of y (the next `bits` columns) - BIT columns - and the three WORD columns a, o, e behind them.  Constraints, all of degree 2 on
+    every row, with no auxiliary segment and no periodic column: every bit is a bit, the two recompositions, a = sum_j 2^j xb_j yb_j,
+    e = x + y - 2 a and o = x + y - a.  degree_bound_factor 1."""
+    if not 1 <= bits <= 16:
+        raise ValueError(f"word_ops: {bits} bits (1 .. 16: 2 bits + 5 transition constraints, and a descriptor takes 64)")
+    b = AirBuilder(5 + 2 * bits, [0], 1, main_inputs=2)
+    m = b.main
+    xb, yb = m.bits(m.load(0, 0), bits), m.bits(m.load(0, 1), bits)
+    a, o, e = m.word_and(m.load(0, 0), m.load(0, 1), bits), m.word_or(m.load(0, 0), m.load(0, 1), bits), m.word_xor(m.load(0, 0), m.load(0, 1), bits)
+    for c in xb + yb:
+        v = b.load(0, c)
+        b.constraint(v * (v - 1), degree=2, exemptions=0)
+    x, y = b.load(0, 0), b.load(0, 1)
+    for value, cols in ((x, xb), (y, yb)):
+        total = None
+        for j, c in enumerate(cols):
+            term = b.load(0, c) * (1 << j)
+            total = term if total is None else total + term
+        b.constraint(total - value, degree=1, exemptions=0)
+    both = None
+    for j, (cx, cy) in enumerate(zip(xb, yb)):
+        term = b.load(0, cx) * b.load(0, cy) * (1 << j)
+        both = term if both is None else both + term
+    b.constraint(both - b.load(0, a), degree=2, exemptions=0)
+    b.constraint(b.load(0, e) - (x + y - b.load(0, a) * 2), degree=1, exemptions=0)
+    b.constraint(b.load(0, o) - (x + y - b.load(0, a)), degree=1, exemptions=0)
+    return b
+
+
+def word_ops_inputs(n, bits, rng):
+    """(n, 2) Python ints [x, y] below 2^bits from rng.randrange; the first rows hold the all-ones and the all-zeros words."""
+    top = (1 << bits) - 1
+    rows = [[rng.randrange(top + 1), rng.randrange(top + 1)] for _ in range(n)]
+    rows[:3] = [[top, 0], [top, top], [0, 0]]
+    return rows
+
+
+def word_ops_trace(inputs, bits):
+    """The whole main table of word_ops as (n, 5 + 2 bits) Python ints, from its input rows."""
+    return [[x, y] + [(x >> j) & 1 for j in range(bits)] + [(y >> j) & 1 for j in range(bits)] + [x & y, x | y, x ^ y] for x, y in inputs]
 
 
 # ---- quotients in chain steps: a worked example -----------------------------------------------------------------------------------

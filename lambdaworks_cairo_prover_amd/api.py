@@ -591,6 +591,14 @@ def air_main_link_limits():
     return {"link_log": int(out[0]), "width": int(out[1])}
 
 
+def air_main_word_limits():
+    """sp_air_main_word_limits: {"limb_end": the most lo + width of a LIMB column, "bits": the most bits of a WORD column, "functions": the
+    number of WORD functions (fn 0 AND, 1 OR, 2 XOR)}."""
+    out = (ctypes.c_uint32 * 4)()
+    check(_lib.load().sp_air_main_word_limits(out))
+    return {"limb_end": int(out[0]), "bits": int(out[1]), "functions": int(out[2])}
+
+
 def air_main_fetch_limits():
     """sp_air_main_fetch_limits: {"key_bits": the most key bits of a FETCH column, "group": the most FETCH columns that share one sort and
     one search, "columns": the most FETCH columns of one main program}."""

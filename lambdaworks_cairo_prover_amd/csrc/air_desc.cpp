@@ -159,10 +159,12 @@ std::string validate_aux_program(const AirAuxHost& aux, uint32_t main_cols, uint
 // with link): op 7 DIV over earlier ops, behind the seeds and steps of CHAIN columns only; a column of any other kind that depends on
 // one is refused, and without div op 7 is a malformed op.  fetch (the _fetch entry points, with div): SP_AIR_MAIN_FETCH columns too - a
 // table key, pad = key_bits (1 .. 64) + 256 v_op below 2^24, X, T and V over earlier columns and behind no op 7, at most 64 of them;
-// without fetch kind 7 is an unknown kind.
+// without fetch kind 7 is an unknown kind.  word (the _word entry points, with fetch): SP_AIR_MAIN_LIMB columns too - no denominator,
+// pad = lo + 256 width below 2^16, 1 <= width, lo + width <= 252 - and SP_AIR_MAIN_WORD columns - a second operand, pad = fn + 256 bits
+// below 2^16, fn 0 .. 2, bits 1 .. 251 -, both over earlier columns and behind no op 7; without word kinds 8 and 9 are unknown kinds.
 std::string main_from_c(const AirDescHost& air, const sp_air_main_desc* m, uint64_t n, uint32_t n_periodic, AirMainLevel level, AirMainHost& out) {
     const bool rec = air_main_allows_chains(level), lk = air_main_allows_counts(level), link = air_main_allows_runs(level);
-    const bool div = air_main_allows_quotients(level), fetch = air_main_allows_fetches(level);
+    const bool div = air_main_allows_quotients(level), fetch = air_main_allows_fetches(level), word = air_main_allows_words(level);
     if (m->size != sizeof(sp_air_main_desc)) return "main program: sp_air_main_desc.size is not sizeof(sp_air_main_desc)";
     if (!m->ops || !m->consts || !m->cols) return "main program: null ops, consts or cols";
     if (m->input_cols == 0 || m->n_cols == 0 || (uint64_t)m->input_cols + m->n_cols != air.main_cols)
@@ -209,7 +211,27 @@ std::string main_from_c(const AirDescHost& air, const sp_air_main_desc* m, uint6
         const sp_air_main_column& c = m->cols[k];
         const std::string who = "main program: derived column " + std::to_string(k);
         const bool den = c.den_op != SP_AIR_AUX_NO_DEN;
-        if (c.kind > (fetch ? SP_AIR_MAIN_FETCH : lk ? SP_AIR_MAIN_COUNT : rec ? SP_AIR_MAIN_CHAIN : SP_AIR_MAIN_PRODUCT)) return who + " has an unknown kind";
+        if (c.kind > (word ? SP_AIR_MAIN_WORD : fetch ? SP_AIR_MAIN_FETCH : lk ? SP_AIR_MAIN_COUNT : rec ? SP_AIR_MAIN_CHAIN : SP_AIR_MAIN_PRODUCT))
+            return who + " has an unknown kind";
+        if (c.kind == SP_AIR_MAIN_LIMB || c.kind == SP_AIR_MAIN_WORD) {   // (row-local, as a BIT column: the rules of a VALUE column's operands)
+            const bool limb = c.kind == SP_AIR_MAIN_LIMB;
+            const uint32_t low = c.pad & 255u, high = (c.pad >> 8) & 255u;   // LIMB: lo, width; WORD: fn, bits
+            if (c.pad >> 16)
+                return who + (limb ? " is a LIMB column whose pad has a bit at or above 16 (pad = lo + 256 width)" : " is a WORD column whose pad has a bit at or above 16 (pad = fn + 256 bits)");
+            if (limb && den) return who + " is a LIMB column and takes no denominator";
+            if (!limb && !den) return who + " is a WORD column without a second operand (den_op names it)";
+            if (limb && high == 0) return who + " is a LIMB column with width = 0 (1 <= width, lo + width <= 252)";
+            if (limb && low + high > AIR_MAIN_LIMB_MAX_END)
+                return who + " is a LIMB column with lo + width = " + std::to_string(low + high) + " (1 <= width, lo + width <= 252)";
+            if (!limb && low >= AIR_MAIN_WORD_FUNCTIONS) return who + " is a WORD column with fn = " + std::to_string(low) + " (0 AND, 1 OR, 2 XOR)";
+            if (!limb && (high == 0 || high > AIR_MAIN_WORD_MAX_BITS)) return who + " is a WORD column with bits = " + std::to_string(high) + " (1 .. 251)";
+            if (c.num_op >= n_ops || (den && c.den_op >= n_ops)) return who + " names an op beyond the program";
+            if (quot[c.num_op] || (den && quot[c.den_op])) return quotient_refused(who);
+            const uint32_t r = std::max(reads[c.num_op], den ? reads[c.den_op] : 0u);
+            if (r > k) return who + " reads derived column " + std::to_string(r - 1) + ", which is not an earlier one";
+            cols.push_back(AirMainColumnHost{c.kind, c.num_op, c.den_op, low, r, 0u, 0u, 0u, 0u, 0u, high});
+            continue;
+        }
         if (c.kind == SP_AIR_MAIN_FETCH) {
             const uint32_t key_bits = c.pad & 255u, v_op = (c.pad >> 8) & 65535u;
             if (c.pad >> 24) return who + " is a FETCH column whose pad has a bit at or above 24 (pad = key_bits + 256 v_op)";
@@ -330,7 +352,7 @@ std::string air_statement_from_c(const sp_air_desc* d, const sp_air_aux_desc* au
     if (main) {
         // (only the _rec, _lk, _link and _div entry points let a main program hold chain columns and read the periodic columns, only
         // _lk, _link and _div COUNT columns, only _link and _div runs of blocks, only _div quotients behind chain seeds and steps; the
-        // _fetch entry points all of that and FETCH columns)
+        // _fetch entry points all of that and FETCH columns, the _word entry points LIMB and WORD columns on top)
         const std::string refused = main_from_c(air, main, n, st.n_periodic(), st.main_level, st.main.emplace());
         if (!refused.empty()) return refused;
     }

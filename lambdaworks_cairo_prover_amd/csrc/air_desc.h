@@ -53,11 +53,13 @@ struct AirAuxHost {
 // chain_link: the k of a CHAIN column's pad through the _link entry points - runs of 2^k blocks, a seed inside a run reads the last
 // state of the block before it (0: every block on its own, and always 0 through every other entry point).
 // value_op: the v_op of a FETCH column's pad (its X is num_op, its T den_op, its key_bits the low byte of the pad), 0 for the other kinds.
+// width: the width of a LIMB column (its lo is `bit`) or the bits of a WORD column (its fn is `bit`), 0 for the other kinds.
 constexpr uint32_t AIR_MAIN_CHAIN_MAX_WIDTH = 16;
 constexpr uint32_t AIR_MAIN_LINK_MAX_LOG = 62;   // (l >= 1 and l + k <= log2 n <= 63)
 constexpr uint32_t AIR_MAIN_COUNT_MAX_KEY_BITS = 64, AIR_MAIN_COUNT_MAX_COLS = 16;
 constexpr uint32_t AIR_MAIN_FETCH_MAX_KEY_BITS = 64, AIR_MAIN_FETCH_MAX_GROUP = 16, AIR_MAIN_FETCH_MAX_COLS = 64;
-struct AirMainColumnHost { uint32_t kind, num_op, den_op, bit, reads, chain_log = 0, chain_pos = 0, key_bits = 0, chain_link = 0, value_op = 0; };
+constexpr uint32_t AIR_MAIN_LIMB_MAX_END = 252, AIR_MAIN_WORD_MAX_BITS = 251, AIR_MAIN_WORD_FUNCTIONS = 3;   // (lo + width <= 252; 2^251 < p)
+struct AirMainColumnHost { uint32_t kind, num_op, den_op, bit, reads, chain_log = 0, chain_pos = 0, key_bits = 0, chain_link = 0, value_op = 0, width = 0; };
 struct AirMainHost {
     uint32_t input_cols = 0, input_location = 0;   // 0: the inputs are host memory, 1: device memory
     std::vector<AirOpHost> ops;
@@ -128,12 +130,14 @@ fe air_root_of_unity(int order);
 //   Link   (the _link entry points) a chain group's blocks may form runs seeded from the block before
 //   Div    (the _div entry points) op 7 DIV behind the seeds and steps of CHAIN columns: quotients inside a recurrence
 //   Fetch  (the _fetch entry points) FETCH columns too, looked-up values
-enum class AirMainLevel : uint8_t { Main, Rec, Lk, Link, Div, Fetch };
+//   Word   (the _word entry points) LIMB and WORD columns too, limbs and bitwise functions of canonical integers
+enum class AirMainLevel : uint8_t { Main, Rec, Lk, Link, Div, Fetch, Word };
 inline bool air_main_allows_chains(AirMainLevel l) { return l >= AirMainLevel::Rec; }   // (and op 6)
 inline bool air_main_allows_counts(AirMainLevel l) { return l >= AirMainLevel::Lk; }
 inline bool air_main_allows_runs(AirMainLevel l) { return l >= AirMainLevel::Link; }
 inline bool air_main_allows_quotients(AirMainLevel l) { return l >= AirMainLevel::Div; }
 inline bool air_main_allows_fetches(AirMainLevel l) { return l >= AirMainLevel::Fetch; }
+inline bool air_main_allows_words(AirMainLevel l) { return l >= AirMainLevel::Word; }
 
 // Everything a prover, a trace check or a verifier is told about a program AIR: the descriptor (its strides inside) and its optional
 // parts, each present or not.  aux_reads_periodic: whether the auxiliary program may read the periodic columns with op 6 (the _pub
@@ -176,6 +180,10 @@ struct AirStatement {
 // main_level Fetch (the _fetch entry points only; it brings Div with it): the main program may also hold SP_AIR_MAIN_FETCH columns - at
 // most 64, each with a table key (den_op), pad = key_bits (1 .. 64) + 256 v_op below 2^24, X, T and V over earlier columns and behind
 // no op 7; without it kind 7 is an unknown kind, as ever.  A key in no table row is a matter of the rows: SP_E_INVALID_ARG from the call.
+// main_level Word (the _word entry points only; it brings Fetch with it): the main program may also hold SP_AIR_MAIN_LIMB columns - no
+// denominator, pad = lo + 256 width below 2^16, 1 <= width, lo + width <= 252 - and SP_AIR_MAIN_WORD columns - a second operand
+// (den_op), pad = fn + 256 bits below 2^16, fn 0 .. 2, bits 1 .. 251 -, their operands over earlier columns and behind no op 7;
+// without it kinds 8 and 9 are unknown kinds.  A WORD operand at or above 2^bits is a matter of the rows: SP_E_INVALID_ARG from the call.
 // The constraint program itself is checked where it is turned into what runs it (build_air_program, air_verify_host).
 // An sp_air_ext is taken apart by the entry point that receives it; this is the one thing it checks first: null, or what is wrong.
 inline const char* air_ext_refusal(const sp_air_ext* ext) { return ext && ext->size != sizeof(sp_air_ext) ? "sp_air_ext.size is not sizeof(sp_air_ext)" : nullptr; }

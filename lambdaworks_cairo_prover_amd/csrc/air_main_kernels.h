@@ -1,6 +1,6 @@
 // Derived main-trace columns of a program AIR on the device (include/stark252_hip.h sp_air_main_desc): per-row terms from a
 // straight-line program over the main columns that exist already, then what each kind needs on top - a zero guard in front of the
-// chunk's one batch inversion (INV_OR_ZERO), the bits of a value (BIT).  VALUE, SUM and PRODUCT columns go on through
+// chunk's one batch inversion (INV_OR_ZERO), the bits of a value (BIT), its limbs (LIMB), two values' AND, OR or XOR (WORD).  VALUE, SUM and PRODUCT columns go on through
 // air_aux_apply_den and air_aux_scan (air_aux_kernels.h).  One lane per row, 256-lane blocks, every store coalesced into a column.
 // CHAIN columns (block recurrences) are the exception: one lane per block of rows, which walks its block (air_main_chain).
 #pragma once
@@ -49,5 +49,16 @@ int air_main_zero_guard(hipStream_t st, fe* ws, fe* cols, const uint32_t* tab, u
 // e in [first, first + count), with (col, bit) = etab[2 e], etab[2 e + 1] (bit <= 251): cols[col * n + i] = that bit of its canonical
 // integer, as the field element 0 or 1.
 int air_main_bits(hipStream_t st, const fe* ws, fe* cols, const uint32_t* gtab, const uint32_t* etab, uint32_t n_groups, uint64_t n);
+// LIMB: group g < n_groups is gtab[3 g .. 3 g + 2] = (slot, first, count): the value ws[slot * n + i] leaves Montgomery form once, and for
+// e in [first, first + count), with (col, lo, width) = etab[3 e .. 3 e + 2] (1 <= width, lo + width <= 252): cols[col * n + i] =
+// (that canonical integer >> lo) mod 2^width as a field element (air_words.h air_int_limb).
+int air_main_limbs(hipStream_t st, const fe* ws, fe* cols, const uint32_t* gtab, const uint32_t* etab, uint32_t n_groups, uint64_t n);
+// WORD: group g < n_groups is gtab[4 g .. 4 g + 3] = (slot, first, count, bits), 1 <= bits <= 251: a = ws[slot * n + i] and b =
+// ws[(slot + 1) * n + i] leave Montgomery form once, and for e in [first, first + count), with (col, fn) = etab[2 e], etab[2 e + 1]:
+// cols[col * n + i] = (a AND / OR / XOR b) mod 2^bits for fn = 0 / 1 / 2 (air_int_word).  A lane whose a or b is at or above 2^bits
+// stores AIR_MAIN_FLAG_WORD_RANGE to *range_flag (a plain store; every such lane stores the same word) and writes its cells all the
+// same: every cell is written once.
+constexpr int AIR_MAIN_FLAG_WORD_RANGE = 1;
+int air_main_words(hipStream_t st, const fe* ws, fe* cols, const uint32_t* gtab, const uint32_t* etab, uint32_t n_groups, uint64_t n, int* range_flag);
 
 }  // namespace sp

@@ -1,6 +1,7 @@
 // Derived main-trace columns of a program AIR on gfx950 (see air_main_kernels.h).
 #include "air_main_kernels.h"
 #include "air_interp.h"
+#include "air_words.h"
 
 namespace sp {
 
@@ -216,6 +217,55 @@ __global__ void __launch_bounds__(256) air_main_bits_kernel(const fe* __restrict
 int air_main_bits(hipStream_t st, const fe* ws, fe* cols, const uint32_t* gtab, const uint32_t* etab, uint32_t n_groups, uint64_t n) {
     if (n_groups == 0) return SP_OK;
     hipLaunchKernelGGL(air_main_bits_kernel, dim3((unsigned)((n + 255) / 256), n_groups), dim3(256), 0, st, ws, cols, gtab, etab, n);
+    SP_HIP_CHECK(hipGetLastError());
+    return SP_OK;
+}
+
+// ---- limbs and bitwise words: row-local functions of a value's canonical integer -------------------------------------------------
+// The shape of the bits kernel: one lane per row, blockIdx.y the group, the group's value out of Montgomery form once, then one
+// column per entry.  lo and width come from the table and are the same for every lane, so air_int_limb's selects, shift amount and
+// masks are scalars.  Each entry pays one fe_to_mont (a field product) and one 32-byte store, coalesced with the neighbours' into the
+// column.  No LDS, no scratch.
+__global__ void __launch_bounds__(256) air_main_limbs_kernel(const fe* __restrict__ ws, fe* __restrict__ cols, const uint32_t* __restrict__ gtab,
+                                                             const uint32_t* __restrict__ etab, uint64_t n) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t slot = gtab[3 * blockIdx.y], first = gtab[3 * blockIdx.y + 1], count = gtab[3 * blockIdx.y + 2];
+    const fe raw = fe_from_mont(fe_ld(ws + (uint64_t)slot * n + i));
+    for (uint32_t e = first; e < first + count; ++e) {
+        const uint32_t col = etab[3 * e], lo = etab[3 * e + 1], width = etab[3 * e + 2];
+        fe_st(cols + (uint64_t)col * n + i, fe_to_mont(air_int_limb(raw, lo, width)));
+    }
+}
+
+int air_main_limbs(hipStream_t st, const fe* ws, fe* cols, const uint32_t* gtab, const uint32_t* etab, uint32_t n_groups, uint64_t n) {
+    if (n_groups == 0) return SP_OK;
+    hipLaunchKernelGGL(air_main_limbs_kernel, dim3((unsigned)((n + 255) / 256), n_groups), dim3(256), 0, st, ws, cols, gtab, etab, n);
+    SP_HIP_CHECK(hipGetLastError());
+    return SP_OK;
+}
+
+// Two values out of Montgomery form per row and group.  The range test is a compare and a plain store of the flag value - every lane
+// that stores stores the same word, and no lane leaves early -; air_int_word masks its result to `bits`, so every cell is written once
+// and holds a canonical integer whatever the operands were.
+__global__ void __launch_bounds__(256) air_main_words_kernel(const fe* __restrict__ ws, fe* __restrict__ cols, const uint32_t* __restrict__ gtab,
+                                                             const uint32_t* __restrict__ etab, uint64_t n, int* __restrict__ range_flag) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t slot = gtab[4 * blockIdx.y], first = gtab[4 * blockIdx.y + 1], count = gtab[4 * blockIdx.y + 2], bits = gtab[4 * blockIdx.y + 3];
+    const fe a = fe_from_mont(fe_ld(ws + (uint64_t)slot * n + i));
+    const fe b = fe_from_mont(fe_ld(ws + (uint64_t)(slot + 1) * n + i));
+    if (air_int_exceeds(a, bits) || air_int_exceeds(b, bits)) *range_flag = AIR_MAIN_FLAG_WORD_RANGE;
+    for (uint32_t e = first; e < first + count; ++e) {
+        const uint32_t col = etab[2 * e], fn = etab[2 * e + 1];
+        fe_st(cols + (uint64_t)col * n + i, fe_to_mont(air_int_word(a, b, fn, bits)));
+    }
+}
+
+int air_main_words(hipStream_t st, const fe* ws, fe* cols, const uint32_t* gtab, const uint32_t* etab, uint32_t n_groups, uint64_t n, int* range_flag) {
+    if (n_groups == 0) return SP_OK;
+    if (!range_flag) return SP_E_INVALID_ARG;
+    hipLaunchKernelGGL(air_main_words_kernel, dim3((unsigned)((n + 255) / 256), n_groups), dim3(256), 0, st, ws, cols, gtab, etab, n, range_flag);
     SP_HIP_CHECK(hipGetLastError());
     return SP_OK;
 }

@@ -79,7 +79,7 @@ struct ScopedDevAlloc {
 };
 // The pinned flag slot (64 bytes): flags that ride to the host behind the work they belong to.  presort_malformed and presort_wide_key
 // stay adjacent and in the order of SIDE_PRESORT_MALFORMED, SIDE_PRESORT_WIDE_KEY: launch_aux_presort fills both with one copy.
-struct HostFlags { int presort_malformed, presort_wide_key, _pad[2], trace_build_oob, auxp_zero_den, auxp_bad_key, auxp_missing_key; };
+struct HostFlags { int presort_malformed, presort_wide_key, _pad[2], trace_build_oob, auxp_zero_den, auxp_bad_key, auxp_missing_key, auxp_bad_word; };
 // flags of the side-stream work (device): DEEP inverses, boundary inverses, the presort's malformed input / key beyond its bits
 enum SideFlag { SIDE_DEEP_INV = 0, SIDE_BND_INV, SIDE_PRESORT_MALFORMED, SIDE_PRESORT_WIDE_KEY, SIDE_FLAGS };
 
@@ -122,7 +122,9 @@ class StarkProver : public sp_deletable {
     // zero under a quotient is the same SP_E_ZERO_INVERSE -, every other group the instantiation it always launched.  At Fetch a run of
     // FETCH columns (SP_AIR_MAIN_FETCH) that share X, T and key_bits is a chunk of its own too: two key passes, V's terms, one radix sort
     // of the table's pairs and air_main_fetch; a key in no table row is SP_E_INVALID_ARG once the root is back, behind the key range and
-    // ahead of a zero denominator.
+    // ahead of a zero denominator.  At Word LIMB and WORD columns (SP_AIR_MAIN_LIMB, SP_AIR_MAIN_WORD) are members of a row-local chunk,
+    // grouped by their operands as BIT columns are: air_main_limbs and air_main_words behind the chunk's one pass of terms; a WORD
+    // operand at or above 2^bits is SP_E_INVALID_ARG once the root is back, behind a missing key and ahead of a zero denominator.
     int commit_main_program(const AirStatement& st, const uint8_t* inputs, uint8_t root_out[32]);
     // the same table without the commitment, to host memory: row-major n x main_cols, context encoding (sp_air_main_trace)
     int main_program_table(const AirStatement& st, const uint8_t* inputs, uint8_t* rows_out);

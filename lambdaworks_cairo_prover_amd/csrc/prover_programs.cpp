@@ -241,11 +241,12 @@ int StarkProver::commit_aux_program(const AirStatement& st, const std::vector<fe
 // Chunks as above (at most max(1, AUXP_CHUNK_ELEMS / n) columns), and a chunk also ends before a column that reads a derived column
 // of the chunk itself: LOADs wrap around the trace, so a column must be complete - its scan included - before anything reads it, and
 // the stream orders one chunk behind the other.  od_.auxp_buf / od_.auxp_ws: the auxiliary program runs later on the same stream.
-// Every chunk places three programs and five word tables in the upload block, whatever its kind uses of them.
+// Every chunk places three programs and nine word tables in the upload block, whatever its kind uses of them.
 struct MainChunk {
     // RowLocal: one pass of the interpreter (air_aux_terms), then what each column kind needs on top.  Workspace slots, n elements
     //   each: first the ones the batch inversion takes (the D of VALUE / SUM / PRODUCT columns, the guarded N of INV_OR_ZERO columns),
-    //   then one per group of BIT columns that share their N.
+    //   then one per group of BIT columns that share their N, one per group of LIMB columns that share their N, and two (N, then D) per
+    //   group of WORD columns that share N, D and bits.
     // Chain: a chain group (SP_AIR_MAIN_CHAIN), a chunk of its own that ends the chunk before it: the seeds' program and the steps',
     //   each with an OUT per group column, and one launch of air_main_chain - a lane per block, or per run of 2^log_k blocks of a
     //   linked group; nothing of the group is read before that launch is over, which the stream's order guarantees.  No workspace.
@@ -269,10 +270,11 @@ struct MainChunk {
     size_t o_prog[N_PROG] = {0, 0, 0};
     bool periodic = false;                   // one of the chunk's programs reads a periodic column
     // RowLocal
-    uint32_t n_inv = 0, n_slots = 0;                              // n_inv: slots the batch inversion takes; n_slots: those and the BIT groups'
+    uint32_t n_inv = 0, n_slots = 0;                              // n_inv: slots the batch inversion takes; n_slots: those and the BIT, LIMB and WORD groups'
     std::vector<uint32_t> kinds, den_col, guard, gtab, etab;     // kinds: 0 product / 1 sum per column (read for scanned columns only)
+    std::vector<uint32_t> limb_gtab, limb_etab, word_gtab, word_etab;   // air_main_limbs' and air_main_words' tables (air_main_kernels.h)
     std::vector<std::pair<uint32_t, uint32_t>> scans;            // runs of SUM / PRODUCT columns: (first, count)
-    size_t o_kinds = 0, o_den = 0, o_guard = 0, o_gtab = 0, o_etab = 0;
+    size_t o_kinds = 0, o_den = 0, o_guard = 0, o_gtab = 0, o_etab = 0, o_limb_gtab = 0, o_limb_etab = 0, o_word_gtab = 0, o_word_etab = 0;
     // Chain
     uint32_t log_s = 0, log_k = 0;           // blocks of 2^log_s rows; log_k >= 1: runs of 2^log_k blocks
     bool divides = false;                    // the slotted seed or step program holds an op 7: the launch takes the zero flag
@@ -283,11 +285,11 @@ struct MainChunk {
 struct MainPlan {
     std::vector<MainChunk> chunks;
     uint32_t chunk = 0, max_slots = 0, max_inv = 0;
-    bool any_count = false, any_fetch = false;
+    bool any_count = false, any_fetch = false, any_word = false;
     uint32_t max_fetch = 0;                  // the widest FETCH group
     size_t o_consts = 0, bytes = 0;          // the upload block: the constants, per chunk its programs and tables, the periodic columns
     PeriodicUpload per;
-    uint64_t ws_elems = 0;                   // the workspace; the words of the key-range flag and the missing-key flag lie behind it
+    uint64_t ws_elems = 0;                   // the workspace; the words of the key-range, the missing-key and the word-range flag lie behind it
 };
 
 // Planning: the chunks and their programs, the upload block's layout and the workspace's size.  No HIP call.
@@ -362,7 +364,9 @@ static int plan_main_program(const AirStatement& st, uint64_t n, MainPlan& P) {
             P.max_fetch = std::max(P.max_fetch, ch.kc);
         } else {
             struct BitGroup { uint32_t num_op; std::vector<uint32_t> entries; };
-            std::vector<BitGroup> groups;
+            struct WordGroup { uint32_t num_op, den_op, bits; std::vector<uint32_t> entries; };
+            std::vector<BitGroup> groups, limbs;
+            std::vector<WordGroup> words;
             for (; ch.kc < P.chunk && k0 + ch.kc < K && mp.cols[k0 + ch.kc].reads <= k0 && mp.cols[k0 + ch.kc].kind != SP_AIR_MAIN_CHAIN &&
                    mp.cols[k0 + ch.kc].kind != SP_AIR_MAIN_COUNT && mp.cols[k0 + ch.kc].kind != SP_AIR_MAIN_FETCH; ++ch.kc) {
                 const AirMainColumnHost& c = mp.cols[k0 + ch.kc];
@@ -378,6 +382,25 @@ static int plan_main_program(const AirStatement& st, uint64_t n, MainPlan& P) {
                     if (g == groups.size()) groups.push_back(BitGroup{c.num_op, {}});
                     groups[g].entries.push_back(ch.kc);
                     groups[g].entries.push_back(c.bit);
+                    continue;
+                }
+                if (c.kind == SP_AIR_MAIN_LIMB) {   // (col, lo, width) beside the others of its N
+                    if (c.width == 0 || c.bit + c.width > AIR_MAIN_LIMB_MAX_END) { sp_set_error("commit_main_program: a LIMB column the decoder should have refused"); return SP_E_INVALID_ARG; }
+                    size_t g = 0;
+                    while (g < limbs.size() && limbs[g].num_op != c.num_op) ++g;
+                    if (g == limbs.size()) limbs.push_back(BitGroup{c.num_op, {}});
+                    limbs[g].entries.insert(limbs[g].entries.end(), {ch.kc, c.bit, c.width});
+                    continue;
+                }
+                if (c.kind == SP_AIR_MAIN_WORD) {   // (col, fn) beside the others of its N, D and bits
+                    if (c.width == 0 || c.width > AIR_MAIN_WORD_MAX_BITS || c.bit >= AIR_MAIN_WORD_FUNCTIONS || c.den_op >= n_src) {
+                        sp_set_error("commit_main_program: a WORD column the decoder should have refused");
+                        return SP_E_INVALID_ARG;
+                    }
+                    size_t g = 0;
+                    while (g < words.size() && (words[g].num_op != c.num_op || words[g].den_op != c.den_op || words[g].bits != c.width)) ++g;
+                    if (g == words.size()) words.push_back(WordGroup{c.num_op, c.den_op, c.width, {}});
+                    words[g].entries.insert(words[g].entries.end(), {ch.kc, c.bit});
                     continue;
                 }
                 if (c.kind == SP_AIR_MAIN_INV_OR_ZERO) {
@@ -396,6 +419,19 @@ static int plan_main_program(const AirStatement& st, uint64_t n, MainPlan& P) {
                 ch.gtab.push_back(ch.n_slots++); ch.gtab.push_back((uint32_t)ch.etab.size() / 2); ch.gtab.push_back((uint32_t)g.entries.size() / 2);
                 ch.etab.insert(ch.etab.end(), g.entries.begin(), g.entries.end());
             }
+            for (const BitGroup& g : limbs) {
+                outs[g.num_op].push_back(AIR_AUX_DEN_TAG + ch.n_slots);
+                ch.limb_gtab.insert(ch.limb_gtab.end(), {ch.n_slots++, (uint32_t)ch.limb_etab.size() / 3, (uint32_t)g.entries.size() / 3});
+                ch.limb_etab.insert(ch.limb_etab.end(), g.entries.begin(), g.entries.end());
+            }
+            for (const WordGroup& g : words) {   // N's slot, D's behind it
+                outs[g.num_op].push_back(AIR_AUX_DEN_TAG + ch.n_slots);
+                outs[g.den_op].push_back(AIR_AUX_DEN_TAG + ch.n_slots + 1);
+                ch.word_gtab.insert(ch.word_gtab.end(), {ch.n_slots, (uint32_t)ch.word_etab.size() / 2, (uint32_t)g.entries.size() / 2, g.bits});
+                ch.n_slots += 2;
+                ch.word_etab.insert(ch.word_etab.end(), g.entries.begin(), g.entries.end());
+                P.any_word = true;
+            }
             SP_TRY(program(outs, ch, MainChunk::TERMS));
             P.max_slots = std::max(P.max_slots, ch.n_slots);
             P.max_inv = std::max(P.max_inv, ch.n_inv);
@@ -410,6 +446,7 @@ static int plan_main_program(const AirStatement& st, uint64_t n, MainPlan& P) {
     for (MainChunk& ch : P.chunks) {
         for (int w = 0; w < MainChunk::N_PROG; ++w) ch.o_prog[w] = lay.place(sizeof(AirOpDev) * std::max<size_t>(1, ch.prog[w].size()));
         ch.o_kinds = words(ch.kinds); ch.o_den = words(ch.den_col); ch.o_guard = words(ch.guard); ch.o_gtab = words(ch.gtab); ch.o_etab = words(ch.etab);
+        ch.o_limb_gtab = words(ch.limb_gtab); ch.o_limb_etab = words(ch.limb_etab); ch.o_word_gtab = words(ch.word_gtab); ch.o_word_etab = words(ch.word_etab);
     }
     const AirPeriodicHost* periodic = air_main_allows_chains(st.main_level) && st.periodic ? &*st.periodic : nullptr;
     if (any_periodic && !periodic) { sp_set_error("commit_main_program: op 6 without periodic columns (the decoder should have refused it)"); return SP_E_INVALID_ARG; }
@@ -427,7 +464,8 @@ static int plan_main_program(const AirStatement& st, uint64_t n, MainPlan& P) {
 
 // Launching: the ingest, the upload and the chunks one behind the other.  The key-range flag of the COUNT and FETCH columns is a word of
 // its own behind the workspace, so that no batch inversion before or behind overwrites it; the missing-key flag of the FETCH columns is
-// the word behind that one, so that neither a key pass nor a batch inversion does (both lie inside the one element behind ws_elems).
+// the word behind that one, so that neither a key pass nor a batch inversion does, and the range flag of the WORD columns the word behind
+// that, which air_main_words alone writes (all three lie inside the one element behind ws_elems).
 int StarkProver::build_main_program(const AirStatement& st, const uint8_t* inputs) {
     const AirMainHost& mp = *st.main;
     const uint32_t I = mp.input_cols, K = (uint32_t)mp.cols.size();
@@ -448,12 +486,14 @@ int StarkProver::build_main_program(const AirStatement& st, const uint8_t* input
         for (int w = 0; w < MainChunk::N_PROG; ++w)
             if (!ch.prog[w].empty()) std::memcpy(up.data() + ch.o_prog[w], ch.prog[w].data(), sizeof(AirOpDev) * ch.prog[w].size());
         put(ch.o_kinds, ch.kinds); put(ch.o_den, ch.den_col); put(ch.o_guard, ch.guard); put(ch.o_gtab, ch.gtab); put(ch.o_etab, ch.etab);
+        put(ch.o_limb_gtab, ch.limb_gtab); put(ch.o_limb_etab, ch.limb_etab); put(ch.o_word_gtab, ch.word_gtab); put(ch.o_word_etab, ch.word_etab);
     }
     P.per.fill(up.data());
     SP_TRY(grow(od_.auxp_ws, P.ws_elems + 1));
     SP_TRY(ensure_host_flags());
     host_flags().auxp_bad_key = 0;
     host_flags().auxp_missing_key = 0;
+    host_flags().auxp_bad_word = 0;
     // --- ingest: the plain staged copy (the inputs are a small part of the table; their raw rows sit in the segment's LDE area,
     //     which is written only by the transforms behind the last chunk), then rows -> columns [0, I)
     if (mp.input_location == 1) {
@@ -469,7 +509,9 @@ int StarkProver::build_main_program(const AirStatement& st, const uint8_t* input
     fe* ws = od_.auxp_ws.p;
     int* key_flag = reinterpret_cast<int*>(ws + P.ws_elems);
     int* miss_flag = key_flag + 1;
+    int* word_flag = key_flag + 2;
     if (P.any_count || P.any_fetch) SP_HIP_CHECK(hipMemsetAsync(key_flag, 0, (P.any_fetch ? 2 : 1) * sizeof(int), c_->stream));
+    if (P.any_word) SP_HIP_CHECK(hipMemsetAsync(word_flag, 0, sizeof(int), c_->stream));
     const SortScratch s(ws, n_, 4);   // a COUNT column: X's pairs in keys / rows [0] and [1], T's in [2] and [3]
     const SortScratch f(ws, n_, 3);   // a FETCH group: T's pairs in keys / rows [0] and [1], X's in [2]; the table values behind
     fe* fetch_vals = ws + SortScratch::elems(n_, 3);
@@ -511,6 +553,8 @@ int StarkProver::build_main_program(const AirStatement& st, const uint8_t* input
                 SP_TRY(air_aux_apply_den(c_->stream, cols, ws, tab(ch.o_den), ch.n_inv, n_));
             }
             SP_TRY(air_main_bits(c_->stream, ws, cols, tab(ch.o_gtab), tab(ch.o_etab), (uint32_t)ch.gtab.size() / 3, n_));
+            SP_TRY(air_main_limbs(c_->stream, ws, cols, tab(ch.o_limb_gtab), tab(ch.o_limb_etab), (uint32_t)ch.limb_gtab.size() / 3, n_));
+            SP_TRY(air_main_words(c_->stream, ws, cols, tab(ch.o_word_gtab), tab(ch.o_word_etab), (uint32_t)ch.word_gtab.size() / 4, n_, word_flag));
             for (const auto& run : ch.scans)
                 SP_TRY(air_aux_scan(c_->stream, cols + (uint64_t)run.first * n_, n_, run.second, tab(ch.o_kinds) + run.first, block_tot));
             break;
@@ -520,11 +564,12 @@ int StarkProver::build_main_program(const AirStatement& st, const uint8_t* input
     SP_HIP_CHECK(hipMemcpyAsync(&host_flags().auxp_zero_den, c_->d_flag, sizeof(int), hipMemcpyDeviceToHost, c_->stream));
     if (P.any_count || P.any_fetch) SP_HIP_CHECK(hipMemcpyAsync(&host_flags().auxp_bad_key, key_flag, sizeof(int), hipMemcpyDeviceToHost, c_->stream));
     if (P.any_fetch) SP_HIP_CHECK(hipMemcpyAsync(&host_flags().auxp_missing_key, miss_flag, sizeof(int), hipMemcpyDeviceToHost, c_->stream));
+    if (P.any_word) SP_HIP_CHECK(hipMemcpyAsync(&host_flags().auxp_bad_word, word_flag, sizeof(int), hipMemcpyDeviceToHost, c_->stream));
     return SP_OK;
 }
 
-// What the flags say once the stream has drained: the key range first (as commit_aux_program), then a missing key, then a zero
-// denominator.
+// What the flags say once the stream has drained: the key range first (as commit_aux_program), then a missing key, then a word operand
+// out of range, then a zero denominator.
 static int main_program_verdict(const HostFlags& f) {
     if (f.auxp_bad_key == AIR_AUX_FLAG_KEY_RANGE) {
         sp_set_error("commit_main_program: a lookup key is out of range on some row (X and T of a COUNT column must be below 2^key_bits as canonical integers)");
@@ -532,6 +577,10 @@ static int main_program_verdict(const HostFlags& f) {
     }
     if (f.auxp_missing_key == AIR_MAIN_FLAG_MISSING_KEY) {
         sp_set_error("commit_main_program: a fetched key is in no table row (every X of a FETCH column must equal the T of some row)");
+        return SP_E_INVALID_ARG;
+    }
+    if (f.auxp_bad_word == AIR_MAIN_FLAG_WORD_RANGE) {
+        sp_set_error("commit_main_program: a word operand is out of range on some row (both operands of a WORD column must be below 2^bits as canonical integers)");
         return SP_E_INVALID_ARG;
     }
     if (f.auxp_zero_den) { sp_set_error("commit_main_program: a derived main column's denominator is zero on some row"); return SP_E_ZERO_INVERSE; }
