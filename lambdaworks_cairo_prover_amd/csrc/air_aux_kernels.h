@@ -15,7 +15,7 @@ constexpr uint32_t AIR_AUX_MAX_SHIFT = 7;
 
 // One thread per row: evaluates the program once and writes every N and D it names (column-major, coalesced across rows).
 // trace: [main_cols][n] natural order; consts: the aux constants followed by the RAP challenges.
-// pcols / pvals (both null for a program without op 6, which then launches the kernel without them): the periodic columns an op 6
+// pcols / pvals (both null for a program without op 6, which then launches the instantiation that reads neither): the periodic columns an op 6
 // reads, a = row shift, b = column k: pvals[off_k + ((i + a) mod period_k)] - the raw values, as the exact trace check reads them.
 // A row-local chunk of the main program (build_main_program) runs through the same call: trace then holds the inputs and the derived
 // columns of earlier chunks, num is the chunk's first column and den the workspace - OUT AIR_AUX_DEN_TAG + s stores into slot s at

@@ -6,47 +6,33 @@ namespace sp {
 
 // ---- per-row terms ------------------------------------------------------------------------------------------
 // The program runs in the shared interpreter (air_interp.h): LOAD takes the row shift itself, and an OUT stores into the num / den
-// column it names.  Two kernels share the body: a program without op 6 runs the one without periodic columns (PER = false leaves no
-// test for op 6 in it); one with table reads gets the columns' descriptors and raw values.
-template <bool PER, class Periodic, class Out>
+// column it names.  A program without op 6 runs the PER = false instantiation, which has no test for op 6 in it and does not read
+// pcols / pvals; one with table reads gets the columns' descriptors and raw values through AirRowPeriodic.
+template <bool PER, class Out>
 __device__ __forceinline__ void air_aux_run_row(const fe* __restrict__ trace, uint64_t n, uint64_t i, const AirOpDev* __restrict__ ops, uint32_t n_ops,
-                                                const fe* __restrict__ consts, Periodic periodic, Out out) {
-    air_run_program<PER>(
-        ops, n_ops, consts,
-        [&](uint32_t shift, uint32_t col) { return fe_ld(trace + (uint64_t)col * n + ((i + shift) & (n - 1))); },   // n is a power of two
-        periodic, out);
+                                                const fe* __restrict__ consts, const AirPeriodicCol* __restrict__ pcols, const fe* __restrict__ pvals, Out out) {
+    auto load = [&](uint32_t shift, uint32_t col) { return fe_ld(trace + (uint64_t)col * n + ((i + shift) & (n - 1))); };   // n is a power of two
+    if constexpr (PER) air_run_program<true>(ops, n_ops, consts, load, AirRowPeriodic{pcols, pvals, i}, out);
+    else air_run_program<false>(ops, n_ops, consts, load, AirNoPeriodic{}, out);
 }
-template <bool PER, class Periodic>
-__device__ __forceinline__ void air_aux_terms_row(const fe* __restrict__ trace, uint64_t n, uint64_t i, const AirOpDev* __restrict__ ops, uint32_t n_ops,
-                                                  const fe* __restrict__ consts, fe* __restrict__ num, fe* __restrict__ den, Periodic periodic) {
-    air_aux_run_row<PER>(trace, n, i, ops, n_ops, consts, periodic, [&](uint32_t a, const fe& val) {
+
+template <bool PER>
+__global__ void __launch_bounds__(256) air_aux_terms_kernel(const fe* __restrict__ trace, uint64_t n, const AirOpDev* __restrict__ ops, uint32_t n_ops,
+                                                            const fe* __restrict__ consts, fe* __restrict__ num, fe* __restrict__ den,
+                                                            const AirPeriodicCol* __restrict__ pcols, const fe* __restrict__ pvals) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    air_aux_run_row<PER>(trace, n, i, ops, n_ops, consts, pcols, pvals, [&](uint32_t a, const fe& val) {
         fe* dst = a < AIR_AUX_DEN_TAG ? num + (uint64_t)a * n : den + (uint64_t)(a - AIR_AUX_DEN_TAG) * n;
         fe_st(dst + i, val);
     });
 }
 
-__global__ void __launch_bounds__(256) air_aux_terms_kernel(const fe* __restrict__ trace, uint64_t n, const AirOpDev* __restrict__ ops, uint32_t n_ops,
-                                                            const fe* __restrict__ consts, fe* __restrict__ num, fe* __restrict__ den) {
-    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    air_aux_terms_row<false>(trace, n, i, ops, n_ops, consts, num, den, AirNoPeriodic{});
-}
-
-// op 6 through AirRowPeriodic (air_interp.h)
-__global__ void __launch_bounds__(256) air_aux_terms_periodic_kernel(const fe* __restrict__ trace, uint64_t n, const AirOpDev* __restrict__ ops, uint32_t n_ops,
-                                                                     const fe* __restrict__ consts, fe* __restrict__ num, fe* __restrict__ den,
-                                                                     const AirPeriodicCol* __restrict__ pcols, const fe* __restrict__ pvals) {
-    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    air_aux_terms_row<true>(trace, n, i, ops, n_ops, consts, num, den, AirRowPeriodic{pcols, pvals, i});
-}
-
 int air_aux_terms(hipStream_t st, const fe* trace, uint64_t n, const AirOpDev* ops, uint32_t n_ops, const fe* consts, fe* num, fe* den,
                   const AirPeriodicCol* pcols, const fe* pvals) {
     if (n == 0 || (n & (n - 1)) || (pcols == nullptr) != (pvals == nullptr)) return SP_E_INVALID_ARG;
-    const dim3 grid((unsigned)((n + 255) / 256));
-    if (pcols) hipLaunchKernelGGL(air_aux_terms_periodic_kernel, grid, dim3(256), 0, st, trace, n, ops, n_ops, consts, num, den, pcols, pvals);
-    else hipLaunchKernelGGL(air_aux_terms_kernel, grid, dim3(256), 0, st, trace, n, ops, n_ops, consts, num, den);
+    auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, trace, n, ops, n_ops, consts, num, den, pcols, pvals); };
+    pcols ? launch(air_aux_terms_kernel<true>) : launch(air_aux_terms_kernel<false>);
     SP_HIP_CHECK(hipGetLastError());
     return SP_OK;
 }
@@ -55,11 +41,14 @@ int air_aux_terms(hipStream_t st, const fe* trace, uint64_t n, const AirOpDev* o
 // Key pass: the same program shape, OUT a < AIR_AUX_DEN_TAG storing carried value a at vals[a * n + i] and OUT AIR_AUX_DEN_TAG the
 // group's key: out of Montgomery form, its low 64 bits and the row become the pair the radix sort takes; anything above key_bits
 // raises the flag (the sort then orders the low bits, all in bounds, and the host refuses the proof).
-template <bool PER, class Periodic>
-__device__ __forceinline__ void air_aux_sort_terms_row(const fe* __restrict__ trace, uint64_t n, uint64_t i, const AirOpDev* __restrict__ ops, uint32_t n_ops,
-                                                       const fe* __restrict__ consts, fe* __restrict__ vals, uint64_t* __restrict__ keys, uint32_t* __restrict__ idx,
-                                                       uint32_t key_bits, int* __restrict__ flag, Periodic periodic) {
-    air_aux_run_row<PER>(trace, n, i, ops, n_ops, consts, periodic, [&](uint32_t a, const fe& val) {
+template <bool PER>
+__global__ void __launch_bounds__(256) air_aux_sort_terms_kernel(const fe* __restrict__ trace, uint64_t n, const AirOpDev* __restrict__ ops, uint32_t n_ops,
+                                                                 const fe* __restrict__ consts, fe* __restrict__ vals, uint64_t* __restrict__ keys,
+                                                                 uint32_t* __restrict__ idx, uint32_t key_bits, int* __restrict__ flag,
+                                                                 const AirPeriodicCol* __restrict__ pcols, const fe* __restrict__ pvals) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    air_aux_run_row<PER>(trace, n, i, ops, n_ops, consts, pcols, pvals, [&](uint32_t a, const fe& val) {
         if (a < AIR_AUX_DEN_TAG) { fe_st(vals + (uint64_t)a * n + i, val); return; }
         const fe raw = fe_from_mont(val);
         const uint64_t key = (uint64_t)raw.v[0] | ((uint64_t)raw.v[1] << 32);
@@ -69,28 +58,14 @@ __device__ __forceinline__ void air_aux_sort_terms_row(const fe* __restrict__ tr
         idx[i] = (uint32_t)i;
     });
 }
-__global__ void __launch_bounds__(256) air_aux_sort_terms_kernel(const fe* __restrict__ trace, uint64_t n, const AirOpDev* __restrict__ ops, uint32_t n_ops,
-                                                                 const fe* __restrict__ consts, fe* __restrict__ vals, uint64_t* __restrict__ keys,
-                                                                 uint32_t* __restrict__ idx, uint32_t key_bits, int* __restrict__ flag) {
-    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    air_aux_sort_terms_row<false>(trace, n, i, ops, n_ops, consts, vals, keys, idx, key_bits, flag, AirNoPeriodic{});
-}
-__global__ void __launch_bounds__(256) air_aux_sort_terms_periodic_kernel(const fe* __restrict__ trace, uint64_t n, const AirOpDev* __restrict__ ops, uint32_t n_ops,
-                                                                          const fe* __restrict__ consts, fe* __restrict__ vals, uint64_t* __restrict__ keys,
-                                                                          uint32_t* __restrict__ idx, uint32_t key_bits, int* __restrict__ flag,
-                                                                          const AirPeriodicCol* __restrict__ pcols, const fe* __restrict__ pvals) {
-    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    air_aux_sort_terms_row<true>(trace, n, i, ops, n_ops, consts, vals, keys, idx, key_bits, flag, AirRowPeriodic{pcols, pvals, i});
-}
 
 int air_aux_sort_terms(hipStream_t st, const fe* trace, uint64_t n, const AirOpDev* ops, uint32_t n_ops, const fe* consts, fe* vals, uint64_t* keys,
                        uint32_t* idx, uint32_t key_bits, int* flag, const AirPeriodicCol* pcols, const fe* pvals) {
     if (n == 0 || (n & (n - 1)) || n >= (1ull << 32) || key_bits == 0 || key_bits > 64 || (pcols == nullptr) != (pvals == nullptr)) return SP_E_INVALID_ARG;
-    const dim3 grid((unsigned)((n + 255) / 256));
-    if (pcols) hipLaunchKernelGGL(air_aux_sort_terms_periodic_kernel, grid, dim3(256), 0, st, trace, n, ops, n_ops, consts, vals, keys, idx, key_bits, flag, pcols, pvals);
-    else hipLaunchKernelGGL(air_aux_sort_terms_kernel, grid, dim3(256), 0, st, trace, n, ops, n_ops, consts, vals, keys, idx, key_bits, flag);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, trace, n, ops, n_ops, consts, vals, keys, idx, key_bits, flag, pcols, pvals);
+    };
+    pcols ? launch(air_aux_sort_terms_kernel<true>) : launch(air_aux_sort_terms_kernel<false>);
     SP_HIP_CHECK(hipGetLastError());
     return SP_OK;
 }

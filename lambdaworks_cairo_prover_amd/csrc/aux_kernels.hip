@@ -229,31 +229,44 @@ void aux_workspace_carve(AuxWorkspace& w, void* base, uint64_t n, uint64_t pm_ca
     w.n = n; w.pm_cap = pm_cap;
 }
 
-int cairo_aux_presort(hipStream_t st, AuxWorkspace& w, const fe* mem_cols, uint64_t n, const fe* pm_addr_host, const fe* pm_val_host,
-                      uint64_t pm, int* flag, int* wide_flag) {
-    if (n != w.n || pm > w.pm_cap || pm > 4 * n) { sp_set_error("aux trace: workspace too small"); return SP_E_INVALID_ARG; }
+static dim3 ax_blocks(uint64_t x) { return dim3((unsigned)((x + 255) / 256)); }
+
+// What needs no challenge: the public memory up, the memory accesses substituted and sorted (stable, by address, looking at key_bits
+// bits of it; a key beyond them raises *wide_flag where there is one), the counting sort of the 3n 16-bit offsets.
+static int aux_sorts(hipStream_t st, AuxWorkspace& w, const fe* mem_cols, uint64_t n, const fe* pm_addr_host, const fe* pm_val_host, uint64_t pm, int* flag,
+                     uint32_t key_bits, int* wide_flag, bool all_limbs) {
     const uint64_t M = 4 * n, M3 = 3 * n;
-    auto blocks = [](uint64_t x) { return dim3((unsigned)((x + 255) / 256)); };
     if (pm) {
         SP_HIP_CHECK(hipMemcpyAsync(w.pm_addr, pm_addr_host, sizeof(fe) * pm, hipMemcpyHostToDevice, st));
         SP_HIP_CHECK(hipMemcpyAsync(w.pm_val, pm_val_host, sizeof(fe) * pm, hipMemcpyHostToDevice, st));
     }
+    hipLaunchKernelGGL(aux_keys_kernel, ax_blocks(M), dim3(256), 0, st, mem_cols, n, w.pm_addr, w.pm_val, pm, w.a_aux, w.v_aux, w.keys_in, w.idx_in, flag, key_bits,
+                       wide_flag, all_limbs ? 1 : 0);
+    SP_TRY(radix_sort_pairs_u64(st, w.keys_in, w.keys_out, w.idx_in, w.idx_out, M, key_bits, w.sort_tmp));
+    // 256-bit addresses: three more stable sorts, by the next limb each, of the order reached so far (LSD over four 64-bit digits
+    // = the reference's stable sort by `representative()`)
+    for (uint32_t limb = 1; all_limbs && limb < 4; ++limb) {
+        hipLaunchKernelGGL(aux_limb_keys_kernel, ax_blocks(M), dim3(256), 0, st, w.a_aux, w.idx_out, M, limb, w.keys_in, w.idx_in);
+        SP_TRY(radix_sort_pairs_u64(st, w.keys_in, w.keys_out, w.idx_in, w.idx_out, M, 64, w.sort_tmp));
+    }
+    hipLaunchKernelGGL(aux_gather_pairs_kernel, ax_blocks(M), dim3(256), 0, st, w.a_aux, w.v_aux, w.idx_out, M, w.a_s, w.v_s);
+    hipLaunchKernelGGL(rc_keys_kernel, ax_blocks(M3), dim3(256), 0, st, mem_cols + 8 * n, n, w.rc_keys, flag);
+    SP_TRY(counting_sort_u16(st, w.rc_keys, w.rc_sorted, M3, w.hist));
+    return SP_OK;
+}
+
+int cairo_aux_presort(hipStream_t st, AuxWorkspace& w, const fe* mem_cols, uint64_t n, const fe* pm_addr_host, const fe* pm_val_host,
+                      uint64_t pm, int* flag, int* wide_flag) {
+    if (n != w.n || pm > w.pm_cap || pm > 4 * n) { sp_set_error("aux trace: workspace too small"); return SP_E_INVALID_ARG; }
     // The memory of a valid run is continuous (every address up to the largest is accessed, execution_trace.rs:195-255 fills the
     // holes), so its 4n addresses are below 4n + |public memory|: the sort looks at log2(8n) key bits - three 8-bit digit passes
     // at 2^20 rows instead of eight - and a key beyond them raises *wide_flag, on which the caller falls back to all 64.
     uint32_t key_bits = 4;
     while ((1ULL << key_bits) < 8 * n && key_bits < 64) ++key_bits;
-    hipLaunchKernelGGL(aux_keys_kernel, blocks(M), dim3(256), 0, st, mem_cols, n, w.pm_addr, w.pm_val, pm, w.a_aux, w.v_aux, w.keys_in, w.idx_in, flag,
-                       key_bits, wide_flag, 0);
-    SP_TRY(radix_sort_pairs_u64(st, w.keys_in, w.keys_out, w.idx_in, w.idx_out, M, key_bits, w.sort_tmp));
-    hipLaunchKernelGGL(aux_gather_pairs_kernel, blocks(M), dim3(256), 0, st, w.a_aux, w.v_aux, w.idx_out, M, w.a_s, w.v_s);
-    hipLaunchKernelGGL(rc_keys_kernel, blocks(M3), dim3(256), 0, st, mem_cols + 8 * n, n, w.rc_keys, flag);
-    SP_TRY(counting_sort_u16(st, w.rc_keys, w.rc_sorted, M3, w.hist));
+    SP_TRY(aux_sorts(st, w, mem_cols, n, pm_addr_host, pm_val_host, pm, flag, key_bits, wide_flag, false));
     SP_HIP_CHECK(hipGetLastError());
     return SP_OK;
 }
-
-static dim3 ax_blocks(uint64_t x) { return dim3((unsigned)((x + 255) / 256)); }
 
 int cairo_aux_sorted_columns(hipStream_t st, AuxWorkspace& w, uint64_t n, fe* out) {
     hipLaunchKernelGGL(aux_sorted_columns_kernel, ax_blocks(n), dim3(256), 0, st, n, w.rc_sorted, w.a_s, w.v_s, out);
@@ -291,29 +304,9 @@ int cairo_aux_trace_device(hipStream_t st, AuxWorkspace& w, const fe* mem_cols, 
                            uint64_t pm, const fe rap[3], fe* out, int* flag, hipStream_t side, hipEvent_t ev_fork, hipEvent_t ev_join, bool presorted, bool all_limbs) {
     if (n != w.n || pm > w.pm_cap || pm > 4 * n) { sp_set_error("aux trace: workspace too small"); return SP_E_INVALID_ARG; }
     AuxConsts K; K.alpha = rap[0]; K.z = rap[1]; K.zrc = rap[2];
-    const uint64_t M = 4 * n, M3 = 3 * n;
     const bool fork = side && ev_fork && ev_join;
     hipStream_t rs = fork ? side : st;            // stream of the range-check half
-    if (!presorted) {
-        if (pm) {
-            SP_HIP_CHECK(hipMemcpyAsync(w.pm_addr, pm_addr_host, sizeof(fe) * pm, hipMemcpyHostToDevice, st));
-            SP_HIP_CHECK(hipMemcpyAsync(w.pm_val, pm_val_host, sizeof(fe) * pm, hipMemcpyHostToDevice, st));
-        }
-        // memory: substitute, sort (stable, by address); range check: counting sort of the 3n 16-bit offsets
-        int* no_wide = nullptr;
-        hipLaunchKernelGGL(aux_keys_kernel, ax_blocks(M), dim3(256), 0, st, mem_cols, n, w.pm_addr, w.pm_val, pm, w.a_aux, w.v_aux, w.keys_in, w.idx_in, flag, 64u, no_wide,
-                           all_limbs ? 1 : 0);
-        SP_TRY(radix_sort_pairs_u64(st, w.keys_in, w.keys_out, w.idx_in, w.idx_out, M, 64, w.sort_tmp));
-        // 256-bit addresses: three more stable sorts, by the next limb each, of the order reached so far (LSD over four 64-bit digits
-        // = the reference's stable sort by `representative()`)
-        for (uint32_t limb = 1; all_limbs && limb < 4; ++limb) {
-            hipLaunchKernelGGL(aux_limb_keys_kernel, ax_blocks(M), dim3(256), 0, st, w.a_aux, w.idx_out, M, limb, w.keys_in, w.idx_in);
-            SP_TRY(radix_sort_pairs_u64(st, w.keys_in, w.keys_out, w.idx_in, w.idx_out, M, 64, w.sort_tmp));
-        }
-        hipLaunchKernelGGL(aux_gather_pairs_kernel, ax_blocks(M), dim3(256), 0, st, w.a_aux, w.v_aux, w.idx_out, M, w.a_s, w.v_s);
-        hipLaunchKernelGGL(rc_keys_kernel, ax_blocks(M3), dim3(256), 0, st, mem_cols + 8 * n, n, w.rc_keys, flag);
-        SP_TRY(counting_sort_u16(st, w.rc_keys, w.rc_sorted, M3, w.hist));
-    }
+    if (!presorted) SP_TRY(aux_sorts(st, w, mem_cols, n, pm_addr_host, pm_val_host, pm, flag, 64u, nullptr, all_limbs));
     if (fork) {
         SP_HIP_CHECK(hipEventRecord(ev_fork, st));   // the trace columns, the sorts and the cleared flag are behind this point
         SP_HIP_CHECK(hipStreamWaitEvent(side, ev_fork, 0));

@@ -3,6 +3,8 @@
 // Host code only.
 #include "prover_internal.h"
 #include "sort_kernels.h"
+#include <array>
+#include <cstddef>
 #include <cstring>
 
 namespace sp {
@@ -80,6 +82,17 @@ struct SortScratch {
     }
 };
 
+// The group of this key, appended if new: columns that share an operand share one pass over it (BIT and LIMB columns their N, WORD
+// columns N, D and bits, sorted columns their key).  A linear search: a chunk has few groups.
+template <class Group, class Key>
+static Group& group_of(std::vector<Group>& groups, const Key& key) {
+    for (Group& g : groups)
+        if (g.key == key) return g;
+    groups.emplace_back();
+    groups.back().key = key;
+    return groups.back();
+}
+
 int StarkProver::commit_aux_program(const AirStatement& st, const std::vector<fe>& rap, uint8_t root_out[32]) {
     const AirAuxHost& aux = *st.aux;
     const uint32_t K = (uint32_t)aux.cols.size();
@@ -98,15 +111,14 @@ int StarkProver::commit_aux_program(const AirStatement& st, const std::vector<fe
     // --- per sort group: its key columns (rebuilt from the sorted keys) and its carried columns in passes of at most `chunk`; the
     //     first pass also stores the key (OUT AIR_AUX_DEN_TAG)
     struct SortPass { bool periodic; std::vector<AirOpDev> ops; std::vector<uint32_t> col_of; size_t o_ops, o_col; };
-    struct SortGroup { uint32_t key_op, key_bits; std::vector<uint32_t> key_cols, carried; std::vector<SortPass> passes; size_t o_keycol; };
+    struct SortGroup { uint32_t key = 0, key_bits = 0; std::vector<uint32_t> key_cols, carried; std::vector<SortPass> passes; size_t o_keycol = 0; };   // key: its op
     std::vector<SortGroup> groups;
     for (uint32_t k = 0; k < K; ++k) {
         const AirAuxColumnHost& c = aux.cols[k];
         if (c.kind != SP_AIR_AUX_SORTED) continue;
-        size_t g = 0;
-        while (g < groups.size() && groups[g].key_op != c.den_op) ++g;
-        if (g == groups.size()) { groups.emplace_back(); groups[g].key_op = c.den_op; groups[g].key_bits = c.key_bits; }
-        (c.num_op == c.den_op ? groups[g].key_cols : groups[g].carried).push_back(k);
+        SortGroup& g = group_of(groups, c.den_op);
+        if (g.key_cols.empty() && g.carried.empty()) g.key_bits = c.key_bits;   // (the group's first column)
+        (c.num_op == c.den_op ? g.key_cols : g.carried).push_back(k);
     }
     uint32_t max_carried = 0;
     for (SortGroup& g : groups) {
@@ -117,7 +129,7 @@ int StarkProver::commit_aux_program(const AirStatement& st, const std::vector<fe
                 outs[aux.cols[g.carried[j]].num_op].push_back((uint32_t)ps.col_of.size());
                 ps.col_of.push_back(g.carried[j]);
             }
-            if (j0 == 0) outs[g.key_op].push_back(AIR_AUX_DEN_TAG);
+            if (j0 == 0) outs[g.key].push_back(AIR_AUX_DEN_TAG);
             SP_TRY(program(outs, ps.ops, ps.periodic));
             max_carried = std::max(max_carried, (uint32_t)ps.col_of.size());
             g.passes.push_back(std::move(ps));
@@ -241,7 +253,7 @@ int StarkProver::commit_aux_program(const AirStatement& st, const std::vector<fe
 // Chunks as above (at most max(1, AUXP_CHUNK_ELEMS / n) columns), and a chunk also ends before a column that reads a derived column
 // of the chunk itself: LOADs wrap around the trace, so a column must be complete - its scan included - before anything reads it, and
 // the stream orders one chunk behind the other.  od_.auxp_buf / od_.auxp_ws: the auxiliary program runs later on the same stream.
-// Every chunk places three programs and nine word tables in the upload block, whatever its kind uses of them.
+// A chunk places the programs and word tables its kind fills in the upload block, and no others.
 struct MainChunk {
     // RowLocal: one pass of the interpreter (air_aux_terms), then what each column kind needs on top.  Workspace slots, n elements
     //   each: first the ones the batch inversion takes (the D of VALUE / SUM / PRODUCT columns, the guarded N of INV_OR_ZERO columns),
@@ -271,10 +283,12 @@ struct MainChunk {
     bool periodic = false;                   // one of the chunk's programs reads a periodic column
     // RowLocal
     uint32_t n_inv = 0, n_slots = 0;                              // n_inv: slots the batch inversion takes; n_slots: those and the BIT, LIMB and WORD groups'
-    std::vector<uint32_t> kinds, den_col, guard, gtab, etab;     // kinds: 0 product / 1 sum per column (read for scanned columns only)
-    std::vector<uint32_t> limb_gtab, limb_etab, word_gtab, word_etab;   // air_main_limbs' and air_main_words' tables (air_main_kernels.h)
+    // KINDS: 0 product / 1 sum per column (read for scanned columns only); DEN_COL: air_aux_apply_den's table; GUARD: air_main_zero_guard's;
+    // BIT_G / BIT_E, LIMB_G / LIMB_E and WORD_G / WORD_E: the group and entry tables of air_main_bits, air_main_limbs and air_main_words
+    enum Tab { KINDS, DEN_COL, GUARD, BIT_G, BIT_E, LIMB_G, LIMB_E, WORD_G, WORD_E, N_TAB };
+    std::vector<uint32_t> tab[N_TAB];
+    size_t o_tab[N_TAB] = {};
     std::vector<std::pair<uint32_t, uint32_t>> scans;            // runs of SUM / PRODUCT columns: (first, count)
-    size_t o_kinds = 0, o_den = 0, o_guard = 0, o_gtab = 0, o_etab = 0, o_limb_gtab = 0, o_limb_etab = 0, o_word_gtab = 0, o_word_etab = 0;
     // Chain
     uint32_t log_s = 0, log_k = 0;           // blocks of 2^log_s rows; log_k >= 1: runs of 2^log_k blocks
     bool divides = false;                    // the slotted seed or step program holds an op 7: the launch takes the zero flag
@@ -286,10 +300,11 @@ struct MainPlan {
     std::vector<MainChunk> chunks;
     uint32_t chunk = 0, max_slots = 0, max_inv = 0;
     bool any_count = false, any_fetch = false, any_word = false;
+    bool any_verdict() const { return any_count || any_fetch || any_word; }   // the three verdict words behind the workspace are in use
     uint32_t max_fetch = 0;                  // the widest FETCH group
     size_t o_consts = 0, bytes = 0;          // the upload block: the constants, per chunk its programs and tables, the periodic columns
     PeriodicUpload per;
-    uint64_t ws_elems = 0;                   // the workspace; the words of the key-range, the missing-key and the word-range flag lie behind it
+    uint64_t ws_elems = 0;                   // the workspace; the three verdict words lie behind it
 };
 
 // Planning: the chunks and their programs, the upload block's layout and the workspace's size.  No HIP call.
@@ -363,33 +378,28 @@ static int plan_main_program(const AirStatement& st, uint64_t n, MainPlan& P) {
             P.any_fetch = true;
             P.max_fetch = std::max(P.max_fetch, ch.kc);
         } else {
-            struct BitGroup { uint32_t num_op; std::vector<uint32_t> entries; };
-            struct WordGroup { uint32_t num_op, den_op, bits; std::vector<uint32_t> entries; };
-            std::vector<BitGroup> groups, limbs;
+            struct LimbGroup { uint32_t key = 0; std::vector<uint32_t> entries; };                  // key: N's op
+            struct WordGroup { std::array<uint32_t, 3> key{}; std::vector<uint32_t> entries; };     // key: N's op, D's op, bits
+            std::vector<LimbGroup> bits, limbs;
             std::vector<WordGroup> words;
             for (; ch.kc < P.chunk && k0 + ch.kc < K && mp.cols[k0 + ch.kc].reads <= k0 && mp.cols[k0 + ch.kc].kind != SP_AIR_MAIN_CHAIN &&
                    mp.cols[k0 + ch.kc].kind != SP_AIR_MAIN_COUNT && mp.cols[k0 + ch.kc].kind != SP_AIR_MAIN_FETCH; ++ch.kc) {
                 const AirMainColumnHost& c = mp.cols[k0 + ch.kc];
                 const bool scanned = c.kind == SP_AIR_MAIN_SUM || c.kind == SP_AIR_MAIN_PRODUCT;
-                ch.kinds.push_back(c.kind == SP_AIR_MAIN_SUM ? 1u : 0u);
+                ch.tab[MainChunk::KINDS].push_back(c.kind == SP_AIR_MAIN_SUM ? 1u : 0u);
                 if (scanned) {
                     if (!ch.scans.empty() && ch.scans.back().first + ch.scans.back().second == ch.kc) ++ch.scans.back().second;
                     else ch.scans.emplace_back(ch.kc, 1u);
                 }
-                if (c.kind == SP_AIR_MAIN_BIT) {
-                    size_t g = 0;
-                    while (g < groups.size() && groups[g].num_op != c.num_op) ++g;
-                    if (g == groups.size()) groups.push_back(BitGroup{c.num_op, {}});
-                    groups[g].entries.push_back(ch.kc);
-                    groups[g].entries.push_back(c.bit);
+                if (c.kind == SP_AIR_MAIN_BIT) {    // (col, bit) beside the others of its N
+                    std::vector<uint32_t>& e = group_of(bits, c.num_op).entries;
+                    e.insert(e.end(), {ch.kc, c.bit});
                     continue;
                 }
                 if (c.kind == SP_AIR_MAIN_LIMB) {   // (col, lo, width) beside the others of its N
                     if (c.width == 0 || c.bit + c.width > AIR_MAIN_LIMB_MAX_END) { sp_set_error("commit_main_program: a LIMB column the decoder should have refused"); return SP_E_INVALID_ARG; }
-                    size_t g = 0;
-                    while (g < limbs.size() && limbs[g].num_op != c.num_op) ++g;
-                    if (g == limbs.size()) limbs.push_back(BitGroup{c.num_op, {}});
-                    limbs[g].entries.insert(limbs[g].entries.end(), {ch.kc, c.bit, c.width});
+                    std::vector<uint32_t>& e = group_of(limbs, c.num_op).entries;
+                    e.insert(e.end(), {ch.kc, c.bit, c.width});
                     continue;
                 }
                 if (c.kind == SP_AIR_MAIN_WORD) {   // (col, fn) beside the others of its N, D and bits
@@ -397,39 +407,39 @@ static int plan_main_program(const AirStatement& st, uint64_t n, MainPlan& P) {
                         sp_set_error("commit_main_program: a WORD column the decoder should have refused");
                         return SP_E_INVALID_ARG;
                     }
-                    size_t g = 0;
-                    while (g < words.size() && (words[g].num_op != c.num_op || words[g].den_op != c.den_op || words[g].bits != c.width)) ++g;
-                    if (g == words.size()) words.push_back(WordGroup{c.num_op, c.den_op, c.width, {}});
-                    words[g].entries.insert(words[g].entries.end(), {ch.kc, c.bit});
+                    std::vector<uint32_t>& e = group_of(words, std::array<uint32_t, 3>{c.num_op, c.den_op, c.width}).entries;
+                    e.insert(e.end(), {ch.kc, c.bit});
                     continue;
                 }
                 if (c.kind == SP_AIR_MAIN_INV_OR_ZERO) {
                     outs[c.num_op].push_back(AIR_AUX_DEN_TAG + ch.n_inv);
-                    ch.guard.push_back(ch.n_inv); ch.guard.push_back(ch.kc);
-                    ch.den_col.push_back(ch.kc);
+                    ch.tab[MainChunk::GUARD].insert(ch.tab[MainChunk::GUARD].end(), {ch.n_inv, ch.kc});
+                    ch.tab[MainChunk::DEN_COL].push_back(ch.kc);
                     ++ch.n_inv;
                     continue;
                 }
                 outs[c.num_op].push_back(ch.kc);
-                if (c.den_op != SP_AIR_AUX_NO_DEN) { outs[c.den_op].push_back(AIR_AUX_DEN_TAG + ch.n_inv); ch.den_col.push_back(ch.kc); ++ch.n_inv; }
+                if (c.den_op != SP_AIR_AUX_NO_DEN) { outs[c.den_op].push_back(AIR_AUX_DEN_TAG + ch.n_inv); ch.tab[MainChunk::DEN_COL].push_back(ch.kc); ++ch.n_inv; }
             }
             ch.n_slots = ch.n_inv;
-            for (const BitGroup& g : groups) {
-                outs[g.num_op].push_back(AIR_AUX_DEN_TAG + ch.n_slots);
-                ch.gtab.push_back(ch.n_slots++); ch.gtab.push_back((uint32_t)ch.etab.size() / 2); ch.gtab.push_back((uint32_t)g.entries.size() / 2);
-                ch.etab.insert(ch.etab.end(), g.entries.begin(), g.entries.end());
-            }
-            for (const BitGroup& g : limbs) {
-                outs[g.num_op].push_back(AIR_AUX_DEN_TAG + ch.n_slots);
-                ch.limb_gtab.insert(ch.limb_gtab.end(), {ch.n_slots++, (uint32_t)ch.limb_etab.size() / 3, (uint32_t)g.entries.size() / 3});
-                ch.limb_etab.insert(ch.limb_etab.end(), g.entries.begin(), g.entries.end());
-            }
+            // a group's slot, and its entries - 2 words each for a BIT group, 3 for a LIMB group - behind those of the groups before it
+            auto place_groups = [&](const std::vector<LimbGroup>& groups, MainChunk::Tab g_tab, MainChunk::Tab e_tab, uint32_t words_each) {
+                std::vector<uint32_t> &gtab = ch.tab[g_tab], &etab = ch.tab[e_tab];
+                for (const LimbGroup& g : groups) {
+                    outs[g.key].push_back(AIR_AUX_DEN_TAG + ch.n_slots);
+                    gtab.insert(gtab.end(), {ch.n_slots++, (uint32_t)etab.size() / words_each, (uint32_t)g.entries.size() / words_each});
+                    etab.insert(etab.end(), g.entries.begin(), g.entries.end());
+                }
+            };
+            place_groups(bits, MainChunk::BIT_G, MainChunk::BIT_E, 2);
+            place_groups(limbs, MainChunk::LIMB_G, MainChunk::LIMB_E, 3);
             for (const WordGroup& g : words) {   // N's slot, D's behind it
-                outs[g.num_op].push_back(AIR_AUX_DEN_TAG + ch.n_slots);
-                outs[g.den_op].push_back(AIR_AUX_DEN_TAG + ch.n_slots + 1);
-                ch.word_gtab.insert(ch.word_gtab.end(), {ch.n_slots, (uint32_t)ch.word_etab.size() / 2, (uint32_t)g.entries.size() / 2, g.bits});
+                std::vector<uint32_t> &gtab = ch.tab[MainChunk::WORD_G], &etab = ch.tab[MainChunk::WORD_E];
+                outs[g.key[0]].push_back(AIR_AUX_DEN_TAG + ch.n_slots);
+                outs[g.key[1]].push_back(AIR_AUX_DEN_TAG + ch.n_slots + 1);
+                gtab.insert(gtab.end(), {ch.n_slots, (uint32_t)etab.size() / 2, (uint32_t)g.entries.size() / 2, g.key[2]});
                 ch.n_slots += 2;
-                ch.word_etab.insert(ch.word_etab.end(), g.entries.begin(), g.entries.end());
+                etab.insert(etab.end(), g.entries.begin(), g.entries.end());
                 P.any_word = true;
             }
             SP_TRY(program(outs, ch, MainChunk::TERMS));
@@ -441,12 +451,12 @@ static int plan_main_program(const AirStatement& st, uint64_t n, MainPlan& P) {
     }
     // --- one upload: the constants, per chunk its programs and tables, the periodic columns an op 6 reads (st.periodic)
     UploadLayout lay;
-    auto words = [&](const std::vector<uint32_t>& v) { return lay.place(sizeof(uint32_t) * std::max<size_t>(1, v.size())); };
     P.o_consts = lay.place(sizeof(fe) * std::max<size_t>(1, mp.consts.size()));
     for (MainChunk& ch : P.chunks) {
-        for (int w = 0; w < MainChunk::N_PROG; ++w) ch.o_prog[w] = lay.place(sizeof(AirOpDev) * std::max<size_t>(1, ch.prog[w].size()));
-        ch.o_kinds = words(ch.kinds); ch.o_den = words(ch.den_col); ch.o_guard = words(ch.guard); ch.o_gtab = words(ch.gtab); ch.o_etab = words(ch.etab);
-        ch.o_limb_gtab = words(ch.limb_gtab); ch.o_limb_etab = words(ch.limb_etab); ch.o_word_gtab = words(ch.word_gtab); ch.o_word_etab = words(ch.word_etab);
+        for (int w = 0; w < MainChunk::N_PROG; ++w)
+            if (!ch.prog[w].empty()) ch.o_prog[w] = lay.place(sizeof(AirOpDev) * ch.prog[w].size());
+        for (int w = 0; w < MainChunk::N_TAB; ++w)
+            if (!ch.tab[w].empty()) ch.o_tab[w] = lay.place(sizeof(uint32_t) * ch.tab[w].size());
     }
     const AirPeriodicHost* periodic = air_main_allows_chains(st.main_level) && st.periodic ? &*st.periodic : nullptr;
     if (any_periodic && !periodic) { sp_set_error("commit_main_program: op 6 without periodic columns (the decoder should have refused it)"); return SP_E_INVALID_ARG; }
@@ -462,10 +472,10 @@ static int plan_main_program(const AirStatement& st, uint64_t n, MainPlan& P) {
     return SP_OK;
 }
 
-// Launching: the ingest, the upload and the chunks one behind the other.  The key-range flag of the COUNT and FETCH columns is a word of
-// its own behind the workspace, so that no batch inversion before or behind overwrites it; the missing-key flag of the FETCH columns is
-// the word behind that one, so that neither a key pass nor a batch inversion does, and the range flag of the WORD columns the word behind
-// that, which air_main_words alone writes (all three lie inside the one element behind ws_elems).
+// Launching: the ingest, the upload and the chunks one behind the other.  The three verdict words lie inside the one element behind
+// ws_elems, in the order of HostFlags' auxp_bad_key, auxp_missing_key and auxp_bad_word, which one copy fills: the key-range flag of
+// the COUNT and FETCH columns, which no batch inversion before or behind overwrites there; the missing-key flag of the FETCH columns,
+// which neither a key pass nor a batch inversion does; the range flag of the WORD columns, which air_main_words alone writes.
 int StarkProver::build_main_program(const AirStatement& st, const uint8_t* inputs) {
     const AirMainHost& mp = *st.main;
     const uint32_t I = mp.input_cols, K = (uint32_t)mp.cols.size();
@@ -481,19 +491,18 @@ int StarkProver::build_main_program(const AirStatement& st, const uint8_t* input
     std::vector<uint8_t>& up = h_auxp_up_;
     up.assign(P.bytes, 0);
     fill_consts_then_rap(up.data() + P.o_consts, mp.consts, {});
-    auto put = [&](size_t at, const std::vector<uint32_t>& v) { if (!v.empty()) std::memcpy(up.data() + at, v.data(), sizeof(uint32_t) * v.size()); };
     for (const MainChunk& ch : P.chunks) {
         for (int w = 0; w < MainChunk::N_PROG; ++w)
             if (!ch.prog[w].empty()) std::memcpy(up.data() + ch.o_prog[w], ch.prog[w].data(), sizeof(AirOpDev) * ch.prog[w].size());
-        put(ch.o_kinds, ch.kinds); put(ch.o_den, ch.den_col); put(ch.o_guard, ch.guard); put(ch.o_gtab, ch.gtab); put(ch.o_etab, ch.etab);
-        put(ch.o_limb_gtab, ch.limb_gtab); put(ch.o_limb_etab, ch.limb_etab); put(ch.o_word_gtab, ch.word_gtab); put(ch.o_word_etab, ch.word_etab);
+        for (int w = 0; w < MainChunk::N_TAB; ++w)
+            if (!ch.tab[w].empty()) std::memcpy(up.data() + ch.o_tab[w], ch.tab[w].data(), sizeof(uint32_t) * ch.tab[w].size());
     }
     P.per.fill(up.data());
     SP_TRY(grow(od_.auxp_ws, P.ws_elems + 1));
     SP_TRY(ensure_host_flags());
-    host_flags().auxp_bad_key = 0;
-    host_flags().auxp_missing_key = 0;
-    host_flags().auxp_bad_word = 0;
+    static_assert(offsetof(HostFlags, auxp_missing_key) == offsetof(HostFlags, auxp_bad_key) + sizeof(int) &&
+                  offsetof(HostFlags, auxp_bad_word) == offsetof(HostFlags, auxp_bad_key) + 2 * sizeof(int), "the verdict words are copied as one block");
+    host_flags().auxp_bad_key = host_flags().auxp_missing_key = host_flags().auxp_bad_word = 0;
     // --- ingest: the plain staged copy (the inputs are a small part of the table; their raw rows sit in the segment's LDE area,
     //     which is written only by the transforms behind the last chunk), then rows -> columns [0, I)
     if (mp.input_location == 1) {
@@ -510,19 +519,19 @@ int StarkProver::build_main_program(const AirStatement& st, const uint8_t* input
     int* key_flag = reinterpret_cast<int*>(ws + P.ws_elems);
     int* miss_flag = key_flag + 1;
     int* word_flag = key_flag + 2;
-    if (P.any_count || P.any_fetch) SP_HIP_CHECK(hipMemsetAsync(key_flag, 0, (P.any_fetch ? 2 : 1) * sizeof(int), c_->stream));
-    if (P.any_word) SP_HIP_CHECK(hipMemsetAsync(word_flag, 0, sizeof(int), c_->stream));
+    if (P.any_verdict()) SP_HIP_CHECK(hipMemsetAsync(key_flag, 0, 3 * sizeof(int), c_->stream));
     const SortScratch s(ws, n_, 4);   // a COUNT column: X's pairs in keys / rows [0] and [1], T's in [2] and [3]
     const SortScratch f(ws, n_, 3);   // a FETCH group: T's pairs in keys / rows [0] and [1], X's in [2]; the table values behind
     fe* fetch_vals = ws + SortScratch::elems(n_, 3);
     fe* scratch = ws + (uint64_t)P.max_slots * n_;
     fe* block_tot = scratch + (uint64_t)P.max_inv * n_;
-    auto tab = [&](size_t at) { return reinterpret_cast<const uint32_t*>(od_.auxp_buf.p + at); };
+    auto tab = [&](const MainChunk& ch, MainChunk::Tab w) { return ch.tab[w].empty() ? nullptr : reinterpret_cast<const uint32_t*>(od_.auxp_buf.p + ch.o_tab[w]); };
+    auto count = [](const MainChunk& ch, MainChunk::Tab w, uint32_t words_each) { return (uint32_t)ch.tab[w].size() / words_each; };
     for (const MainChunk& ch : P.chunks) {
         fe* cols = d_trace_ + (uint64_t)(I + ch.k0) * n_;
-        const AirOpDev* const prog[MainChunk::N_PROG] = {reinterpret_cast<const AirOpDev*>(od_.auxp_buf.p + ch.o_prog[0]), reinterpret_cast<const AirOpDev*>(od_.auxp_buf.p + ch.o_prog[1]),
-                                                         reinterpret_cast<const AirOpDev*>(od_.auxp_buf.p + ch.o_prog[2])};
-        const uint32_t n_prog[MainChunk::N_PROG] = {(uint32_t)ch.prog[0].size(), (uint32_t)ch.prog[1].size(), (uint32_t)ch.prog[2].size()};
+        const AirOpDev* prog[MainChunk::N_PROG];   // (a program the chunk's kind does not have: no ops, and not read)
+        uint32_t n_prog[MainChunk::N_PROG];
+        for (int w = 0; w < MainChunk::N_PROG; ++w) { prog[w] = reinterpret_cast<const AirOpDev*>(od_.auxp_buf.p + ch.o_prog[w]); n_prog[w] = (uint32_t)ch.prog[w].size(); }
         const AirPeriodicCol* pc = ch.periodic ? P.per.cols_dev(od_.auxp_buf.p) : nullptr;
         const fe* pv = ch.periodic ? P.per.vals_dev(od_.auxp_buf.p) : nullptr;
         switch (ch.kind) {
@@ -547,24 +556,22 @@ int StarkProver::build_main_program(const AirStatement& st, const uint8_t* input
         case MainChunk::Kind::RowLocal:
             // OUT a < AIR_AUX_DEN_TAG stores N of chunk column a, OUT AIR_AUX_DEN_TAG + s stores into workspace slot s
             SP_TRY(air_aux_terms(c_->stream, d_trace_, n_, prog[MainChunk::TERMS], n_prog[MainChunk::TERMS], consts_dev, cols, ws, pc, pv));
-            SP_TRY(air_main_zero_guard(c_->stream, ws, cols, tab(ch.o_guard), (uint32_t)ch.guard.size() / 2, n_));
+            SP_TRY(air_main_zero_guard(c_->stream, ws, cols, tab(ch, MainChunk::GUARD), count(ch, MainChunk::GUARD, 2), n_));
             if (ch.n_inv) {
                 SP_TRY(batch_inverse(c_->stream, ws, scratch, (uint64_t)ch.n_inv * n_, c_->d_flag));
-                SP_TRY(air_aux_apply_den(c_->stream, cols, ws, tab(ch.o_den), ch.n_inv, n_));
+                SP_TRY(air_aux_apply_den(c_->stream, cols, ws, tab(ch, MainChunk::DEN_COL), ch.n_inv, n_));
             }
-            SP_TRY(air_main_bits(c_->stream, ws, cols, tab(ch.o_gtab), tab(ch.o_etab), (uint32_t)ch.gtab.size() / 3, n_));
-            SP_TRY(air_main_limbs(c_->stream, ws, cols, tab(ch.o_limb_gtab), tab(ch.o_limb_etab), (uint32_t)ch.limb_gtab.size() / 3, n_));
-            SP_TRY(air_main_words(c_->stream, ws, cols, tab(ch.o_word_gtab), tab(ch.o_word_etab), (uint32_t)ch.word_gtab.size() / 4, n_, word_flag));
+            SP_TRY(air_main_bits(c_->stream, ws, cols, tab(ch, MainChunk::BIT_G), tab(ch, MainChunk::BIT_E), count(ch, MainChunk::BIT_G, 3), n_));
+            SP_TRY(air_main_limbs(c_->stream, ws, cols, tab(ch, MainChunk::LIMB_G), tab(ch, MainChunk::LIMB_E), count(ch, MainChunk::LIMB_G, 3), n_));
+            SP_TRY(air_main_words(c_->stream, ws, cols, tab(ch, MainChunk::WORD_G), tab(ch, MainChunk::WORD_E), count(ch, MainChunk::WORD_G, 4), n_, word_flag));
             for (const auto& run : ch.scans)
-                SP_TRY(air_aux_scan(c_->stream, cols + (uint64_t)run.first * n_, n_, run.second, tab(ch.o_kinds) + run.first, block_tot));
+                SP_TRY(air_aux_scan(c_->stream, cols + (uint64_t)run.first * n_, n_, run.second, tab(ch, MainChunk::KINDS) + run.first, block_tot));
             break;
         }
     }
     // the zero-denominator flag rides behind the columns; whoever reads the root (or the table) back waits for it
     SP_HIP_CHECK(hipMemcpyAsync(&host_flags().auxp_zero_den, c_->d_flag, sizeof(int), hipMemcpyDeviceToHost, c_->stream));
-    if (P.any_count || P.any_fetch) SP_HIP_CHECK(hipMemcpyAsync(&host_flags().auxp_bad_key, key_flag, sizeof(int), hipMemcpyDeviceToHost, c_->stream));
-    if (P.any_fetch) SP_HIP_CHECK(hipMemcpyAsync(&host_flags().auxp_missing_key, miss_flag, sizeof(int), hipMemcpyDeviceToHost, c_->stream));
-    if (P.any_word) SP_HIP_CHECK(hipMemcpyAsync(&host_flags().auxp_bad_word, word_flag, sizeof(int), hipMemcpyDeviceToHost, c_->stream));
+    if (P.any_verdict()) SP_HIP_CHECK(hipMemcpyAsync(&host_flags().auxp_bad_key, key_flag, 3 * sizeof(int), hipMemcpyDeviceToHost, c_->stream));
     return SP_OK;
 }
 

@@ -19,7 +19,7 @@ class ZeroDenominator(Exception):
 
 
 def inv(d):
-    """1 / d by the extended Euclid of Python's pow (a tenth of the time of pow(d, P - 2, P), which div_ref uses: hand_table is what the
+    """1 / d by the extended Euclid of Python's pow (a tenth of the time of pow(d, P - 2, P), which program_ref uses: hand_table is what the
     tests can afford at 8192 rows)."""
     if d % P == 0:
         raise ZeroDenominator

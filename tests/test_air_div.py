@@ -1,7 +1,7 @@
 """Quotients in chain steps (op 7, the _div entry points) without a GPU: the new symbols in the header, the binding and the Rust block,
 the builder's rules, the decoder's verdicts through sp_air_main_check_div - and those of every older entry point on the same
 descriptors -, the builder's mirror of them, and the Python-integer model (MainProgram.evaluate, AirBuilder.check_trace) against a
-plain per-cell reference (div_ref), hand-written loops (div_airs.hand_table) and an affine curve adder on air.ec_subset_sum.  Every
+plain per-cell reference (program_ref), hand-written loops (div_airs.hand_table) and an affine curve adder on air.ec_subset_sum.  Every
 comparison is exact."""
 import ctypes
 import os
@@ -14,6 +14,7 @@ import chain_airs as C
 import div_airs as D
 import div_ref as R
 import link_airs as L
+import program_ref
 from air_main_checks import _col, check_with, decoder_refuses_and_the_builder_raises
 from lambdaworks_cairo_prover_amd import _lib, air, api
 
@@ -200,7 +201,7 @@ def test_model_reference_and_hand_table_agree(n, s, link):
     b, cols = D.mixed(s, link, periodic)
     rows, hand = D.mixed_inputs(n, s, link, periodic, rng)       # (asserts that the reference meets no zero)
     model = [[int(x) for x in r] for r in b.main.evaluate(rows)]
-    ref = R.table_of(b.main, rows)
+    ref = program_ref.main_table(b.main, rows)
     assert cols == {"x0": 2, "x1": 3, "x2": 4, "y0": 5, "y1": 6, "z0": 7, "w0": 9, "v": 25, "r": 26}
     for i in range(n):
         assert model[i] == hand[i] == ref[i], i
@@ -213,7 +214,7 @@ def test_ec_subset_sum_is_clean_and_names_what_breaks():
     b, rows, points, shift, result = D.ec_case(N, s, random.Random(21))
     assert b.check_trace(rows) == []
     full = [[int(x) for x in r] for r in b.main.evaluate(rows)]
-    assert full == R.ec_subset_sum_table(rows, s, points, shift) == R.table_of(b.main, rows)
+    assert full == R.ec_subset_sum_table(rows, s, points, shift) == program_ref.main_table(b.main, rows)
     assert b.check_trace(full) == []                                           # the whole table, as ever
     for first in range(0, N, s):                                                # every block is the sum of its own bits
         acc = shift
@@ -243,12 +244,12 @@ def test_a_zero_denominator_raises_in_the_model_where_it_is_reached():
     assert b.check_trace(rows) == []
     rows[5] = [P - 2]                                           # a + 2 = 0 on a row where no seed is evaluated: nothing to refuse
     b.main.evaluate(rows)
-    R.table_of(b.main, rows)
+    program_ref.main_table(b.main, rows)
     rows[8] = [P - 2]
     with pytest.raises(ValueError, match="a denominator of a quotient \\(op 7\\) is zero on some row"):
         b.main.evaluate(rows)
-    with pytest.raises(R.ZeroDenominator):
-        R.table_of(b.main, rows)
+    with pytest.raises(program_ref.ZeroDenominator):
+        program_ref.main_table(b.main, rows)
     # an accumulator that meets the point it is to add has no chord
     s = 8
     points, shift = D.ec_points(s)

@@ -1,7 +1,7 @@
 """Looked-up values in a main program (SP_AIR_MAIN_FETCH, the _fetch entry points) without a GPU: the new symbols in the header, the
 binding and the Rust block, the decoder's verdicts through sp_air_main_check_fetch - and the older entry points' on the same descriptors
 -, the builder's mirror of them, and the Python-integer model (MainProgram.evaluate, AirBuilder.check_trace) against the plain
-reference of fetch_ref and the worked examples' own tables."""
+reference of program_ref and the worked examples' own tables."""
 import ctypes
 import os
 import random
@@ -10,7 +10,7 @@ import re
 import pytest
 
 import fetch_airs as F
-import fetch_ref as R
+import program_ref as R
 from air_main_checks import _col, _op, check_with, decoder_refuses_and_the_builder_raises
 from lambdaworks_cairo_prover_amd import _lib, air, api
 

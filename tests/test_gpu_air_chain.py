@@ -4,14 +4,12 @@ the entry points that existed before.  Every comparison is exact."""
 import ctypes
 import random
 
-import numpy as np
 import pytest
 
 import chain_airs as C
 import oracle_lib as O
+from air_device_checks import OPTIONS, device_inputs_give_the_same_bytes, model_ints, prove_full, table_ints, to_bytes, two_ranks_give_the_one_rank_bytes
 from lambdaworks_cairo_prover_amd import _lib, air, api
-from rank_procs import run_ranks
-from test_gpu_air_main import OPTIONS, model_ints, prove_full, table_ints, to_bytes
 
 pytestmark = pytest.mark.gpu
 P = air.P
@@ -129,18 +127,8 @@ def test_chain_beside_an_auxiliary_program(hip_ctx, oracle):
 
 
 def test_inputs_in_device_memory_give_the_same_bytes(hip_ctx):
-    import torch
-    n, s = 256, 16
-    options = api.ProofOptions(*MIMC_OPTIONS)
-    b, rows, keys = C.mimc_case(n, s, random.Random(13))
-    desc, keep = b.build()
-    host = to_bytes(rows)
-    want = hip_ctx.air_prove(desc, host, options)
-    dev = torch.from_numpy(host).to("cuda:0")
-    assert hip_ctx.air_prove(desc, dev, options) == want
-    assert desc.main_desc.input_location == air.INPUTS_DEVICE
-    assert np.array_equal(hip_ctx.air_main_trace(desc, dev), hip_ctx.air_main_trace(desc, host))
-    assert hip_ctx.air_prove(desc, host, options) == want and desc.main_desc.input_location == air.INPUTS_HOST
+    b, rows, keys = C.mimc_case(256, 16, random.Random(13))
+    device_inputs_give_the_same_bytes(hip_ctx, b, rows, api.ProofOptions(*MIMC_OPTIONS))
 
 
 def test_malformed_chain_is_refused_and_the_context_goes_on(hip_ctx):
@@ -172,24 +160,6 @@ def _rank_case(n, s):
     return C.mimc_case(n, s, random.Random(31))
 
 
-def _chain_body(rank, world, n, s, options):
-    ctx = api.Context(device=0)
-    ctx.set_collective(world, rank, api.StagedAllGather())
-    ctx.set_option(api.SP_OPT_FRI_SHARD_MIN_LOG, 5)
-    b, rows, keys = _rank_case(n, s)
-    desc, keep = b.build()
-    proof = ctx.air_prove(desc, to_bytes(rows), api.ProofOptions(*options))
-    ctx.close()
-    return proof
-
-
 def test_two_ranks_give_the_one_rank_bytes(hip_ctx):
     """Every rank ingests the inputs and builds every chain column itself: no exchange before the commitment."""
-    n, s, options = 4096, 8, MIMC_OPTIONS
-    b, rows, keys = _rank_case(n, s)
-    desc, keep = b.build()
-    want = hip_ctx.air_prove(desc, to_bytes(rows), api.ProofOptions(*options))
-    assert api.air_verify(want, desc, api.ProofOptions(*options))
-    got = run_ranks(2, _chain_body, (n, s, options), timeout=600)
-    for r in range(2):
-        assert got[r] == want, (r, got[r][:400])
+    two_ranks_give_the_one_rank_bytes(hip_ctx, _rank_case, (4096, 8), MIMC_OPTIONS)

@@ -4,15 +4,14 @@ model's whole table through the entry points that existed before.  Every compari
 import ctypes
 import random
 
-import numpy as np
 import pytest
 
 import div_airs as D
 import div_ref as R
 import oracle_lib as O
+import program_ref
+from air_device_checks import OPTIONS, device_inputs_give_the_same_bytes, model_ints, prove_full, table_ints, to_bytes, two_ranks_give_the_one_rank_bytes
 from lambdaworks_cairo_prover_amd import _lib, air, api
-from rank_procs import run_ranks
-from test_gpu_air_main import OPTIONS, model_ints, prove_full, table_ints, to_bytes
 
 pytestmark = pytest.mark.gpu
 P = air.P
@@ -27,7 +26,7 @@ def test_table_equals_the_model_and_the_references_cell_for_cell(hip_ctx, n, s, 
     The program (div_airs.mixed): DIV in steps only, DIV in a linked seed that reads a carry, a polynomial group beside them - the
     launch without a flag -, a group of sixteen quotients, a quotient of a quotient, one shared by two next values, a dead DIV over
     zero, op 6 in some groups and none in others, a VALUE and a SUM behind them.  The hand table is the reference that chose the inputs;
-    the per-cell evaluator div_ref, one modular exponentiation a quotient, joins it at 64 rows (at 8192 it alone takes ten seconds).
+    the per-cell evaluator program_ref, one modular exponentiation a quotient, joins it at 64 rows (at 8192 it alone takes ten seconds).
     Twice on one context with a polynomial-only program between: the kept workspace, and the launch with a null flag pointer."""
     rng = random.Random(n + s + link)
     periodic = D.periodic_columns(rng)
@@ -38,7 +37,7 @@ def test_table_equals_the_model_and_the_references_cell_for_cell(hip_ctx, n, s, 
     want = model_ints(b, rows)
     assert want == hand
     if n == 64:
-        assert want == R.table_of(b.main, rows)
+        assert want == program_ref.main_table(b.main, rows)
     poly = D.poly_only(s)
     poly_desc, poly_keep = poly.build()
     poly_rows = [[r[0]] for r in rows]
@@ -93,7 +92,7 @@ def test_plain_div_proof_bytes_equal_the_oracles(hip_ctx, oracle, options):
     assert b.check_trace(rows) == []
     desc, keep = b.build()
     full = to_bytes(model_ints(b, rows))
-    assert model_ints(b, rows) == R.table_of(b.main, rows)
+    assert model_ints(b, rows) == program_ref.main_table(b.main, rows)
     got = hip_ctx.air_prove(desc, to_bytes(rows), api.ProofOptions(*options))
     assert got == prove_full(hip_ctx, desc, full, options, "pub") == prove_full(hip_ctx, desc, full, options, "ext")
     assert got == O.program_air_prove(desc, full, options)
@@ -101,19 +100,8 @@ def test_plain_div_proof_bytes_equal_the_oracles(hip_ctx, oracle, options):
 
 
 def test_inputs_in_device_memory_give_the_same_bytes(hip_ctx):
-    import torch
-    n, s = 256, 8
-    options = api.ProofOptions(*DIV_OPTIONS)
-    b, rows, points, shift, result = D.ec_case(n, s, random.Random(13))
-    desc, keep = b.build()
-    host = to_bytes(rows)
-    want = hip_ctx.air_prove(desc, host, options)
-    assert api.air_verify(want, desc, options)
-    dev = torch.from_numpy(host).to("cuda:0")
-    assert hip_ctx.air_prove(desc, dev, options) == want
-    assert desc.main_desc.input_location == air.INPUTS_DEVICE
-    assert np.array_equal(hip_ctx.air_main_trace(desc, dev), hip_ctx.air_main_trace(desc, host))
-    assert hip_ctx.air_prove(desc, host, options) == want and desc.main_desc.input_location == air.INPUTS_HOST
+    b, rows = D.ec_case(256, 8, random.Random(13))[:2]
+    device_inputs_give_the_same_bytes(hip_ctx, b, rows, api.ProofOptions(*DIV_OPTIONS))
 
 
 # ---- what is refused ----------------------------------------------------------------------------------------------------------
@@ -172,25 +160,6 @@ def _rank_case(n, s):
     return D.ec_case(n, s, random.Random(31))
 
 
-def _div_body(rank, world, n, s, options):
-    ctx = api.Context(device=0)
-    ctx.set_collective(world, rank, api.StagedAllGather())
-    ctx.set_option(api.SP_OPT_FRI_SHARD_MIN_LOG, 5)
-    b = _rank_case(n, s)[0]
-    rows = _rank_case(n, s)[1]
-    desc, keep = b.build()
-    proof = ctx.air_prove(desc, to_bytes(rows), api.ProofOptions(*options))
-    ctx.close()
-    return proof
-
-
 def test_two_ranks_give_the_one_rank_bytes(hip_ctx):
     """Every rank ingests the inputs and builds every column itself: no exchange before the commitment."""
-    n, s, options = 4096, 8, DIV_OPTIONS
-    b, rows = _rank_case(n, s)[:2]
-    desc, keep = b.build()
-    want = hip_ctx.air_prove(desc, to_bytes(rows), api.ProofOptions(*options))
-    assert api.air_verify(want, desc, api.ProofOptions(*options))
-    got = run_ranks(2, _div_body, (n, s, options), timeout=600)
-    for r in range(2):
-        assert got[r] == want, (r, got[r][:400])
+    two_ranks_give_the_one_rank_bytes(hip_ctx, _rank_case, (4096, 8), DIV_OPTIONS)

@@ -1,38 +1,22 @@
 """Looked-up values on the device (sp_air_prove_fetch, sp_air_check_trace_fetch, sp_air_main_trace_fetch): the FETCH columns equal the
-plain reference of fetch_ref cell for cell, grouping changes no cell, and a proof from the input columns has the bytes of the proof from
+plain reference of program_ref cell for cell, grouping changes no cell, and a proof from the input columns has the bytes of the proof from
 the whole table through the entry points that existed before.  Every comparison is exact."""
 import ctypes
 import random
 
-import numpy as np
 import pytest
 
 import fetch_airs as F
-import fetch_ref as R
+import program_ref as R
+from air_device_checks import (LK_OPTIONS, device_inputs_give_the_same_bytes, model_ints, prove_full, same_table, table_ints, three_calls, to_bytes,
+                               two_ranks_give_the_one_rank_bytes)
 from lambdaworks_cairo_prover_amd import _lib, air, api
-from rank_procs import run_ranks
-from test_gpu_air_lookup import LK_OPTIONS
-from test_gpu_air_main import model_ints, prove_full, table_ints, to_bytes
 
 pytestmark = pytest.mark.gpu
 P = air.P
 INVALID = _lib.SP_E_INVALID_ARG
 OUT_OF_RANGE = "a lookup key is out of range on some row"
 MISSING = "a fetched key is in no table row"
-
-
-def device_table(ctx, b, rows):
-    desc, keep = b.build()
-    got = ctx.air_main_trace(desc, to_bytes(rows))
-    assert got.shape == (len(rows), b.main_cols, 32)
-    return table_ints(got)
-
-
-def same_table(ctx, b, rows):
-    got, want = device_table(ctx, b, rows), R.main_table(b.main, rows)
-    for i in range(len(rows)):
-        assert got[i] == want[i], i
-    return want
 
 
 # ---- cell equality ----------------------------------------------------------------------------------------------------------
@@ -129,25 +113,10 @@ def test_rom_reads_proves_as_its_whole_table(hip_ctx, options, n, key_bits):
 
 
 def test_inputs_in_device_memory_give_the_same_bytes(hip_ctx):
-    import torch
-    n, options = 256, api.ProofOptions(*LK_OPTIONS[0])
-    b = air.xor_fetch(n, 4)
-    desc, keep = b.build()
-    host = to_bytes(air.xor_fetch_inputs(n, 4, random.Random(13)))
-    want = hip_ctx.air_prove(desc, host, options)
-    dev = torch.from_numpy(host).to("cuda:0")
-    assert hip_ctx.air_prove(desc, dev, options) == want
-    assert desc.main_desc.input_location == air.INPUTS_DEVICE
-    assert np.array_equal(hip_ctx.air_main_trace(desc, dev), hip_ctx.air_main_trace(desc, host))
-    assert hip_ctx.air_prove(desc, host, options) == want and desc.main_desc.input_location == air.INPUTS_HOST
+    device_inputs_give_the_same_bytes(hip_ctx, air.xor_fetch(256, 4), air.xor_fetch_inputs(256, 4, random.Random(13)), api.ProofOptions(*LK_OPTIONS[0]))
 
 
 # ---- keys that break the call ------------------------------------------------------------------------------------------------------
-def three_calls(ctx, desc, rows, options):
-    data = to_bytes(rows)
-    return (lambda: ctx.air_prove(desc, data, options), lambda: ctx.air_main_trace(desc, data), lambda: ctx.air_check_trace(desc, data, options))
-
-
 def _rom_case(n):
     """rom_reads with 16 key bits whose written addresses lie in 1000 .. 1000 + n - 1: keys above and below every table key exist."""
     rng = random.Random(n)
@@ -225,24 +194,6 @@ def test_the_older_entry_points_call_kind_7_unknown(hip_ctx):
 
 
 # ---- two ranks ------------------------------------------------------------------------------------------------------------------
-def _fetch_body(rank, world, n, options):
-    ctx = api.Context(device=0)
-    ctx.set_collective(world, rank, api.StagedAllGather())
-    ctx.set_option(api.SP_OPT_FRI_SHARD_MIN_LOG, 5)
-    b, rows = _rom_case(n)
-    desc, keep = b.build()
-    proof = ctx.air_prove(desc, to_bytes(rows), api.ProofOptions(*options))
-    ctx.close()
-    return proof
-
-
 def test_two_ranks_give_the_one_rank_bytes(hip_ctx):
     """Every rank ingests the inputs and builds the FETCH and COUNT columns itself: no exchange before the commitment."""
-    n, options = 4096, LK_OPTIONS[0]
-    b, rows = _rom_case(n)
-    desc, keep = b.build()
-    want = hip_ctx.air_prove(desc, to_bytes(rows), api.ProofOptions(*options))
-    assert api.air_verify(want, desc, api.ProofOptions(*options))
-    got = run_ranks(2, _fetch_body, (n, options), timeout=600)
-    for r in range(2):
-        assert got[r] == want, (r, got[r][:400])
+    two_ranks_give_the_one_rank_bytes(hip_ctx, _rom_case, (4096,), LK_OPTIONS[0])

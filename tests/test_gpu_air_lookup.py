@@ -2,34 +2,24 @@
 Python-integer model cell for cell, and a proof from the input columns has the bytes of the proof from the model's whole table through
 the entry points that existed before.  Every comparison is exact."""
 import ctypes
+import functools
 import random
 
 import numpy as np
 import pytest
 
+import air_device_checks
 import lookup_airs as L
 import oracle_lib as O
+from air_device_checks import (LK_OPTIONS, device_inputs_give_the_same_bytes, model_ints, prove_full, table_ints, three_calls, to_bytes,
+                               two_ranks_give_the_one_rank_bytes)
 from lambdaworks_cairo_prover_amd import _lib, air, api
-from rank_procs import run_ranks
-from test_gpu_air_main import OPTIONS, model_ints, prove_full, table_ints, to_bytes
 
 pytestmark = pytest.mark.gpu
 P = air.P
 INVALID = _lib.SP_E_INVALID_ARG
-# The lookup argument's constraint has degree 3 under degree_bound_factor 2: the composition has 2n coefficients, which needs a blowup
-# above 2 (test_gpu_air_chain.MIMC_OPTIONS) - the option set with blowup 2 runs with blowup 4 here.
-LK_OPTIONS = [o if o[0] > 2 else (4,) + tuple(o[1:]) for o in OPTIONS]
 OUT_OF_RANGE = "a lookup key is out of range on some row"
-
-
-def same_table(ctx, b, rows):
-    desc, keep = b.build()
-    got = ctx.air_main_trace(desc, to_bytes(rows))
-    assert got.shape == (len(rows), b.main_cols, 32)
-    got, want = table_ints(got), model_ints(b, rows)
-    for i in range(len(rows)):
-        assert got[i] == want[i], i
-    return want
+same_table = functools.partial(air_device_checks.same_table, model=True)      # the plain reference, and the Python model beside it
 
 
 # ---- cell equality ----------------------------------------------------------------------------------------------------------
@@ -149,11 +139,6 @@ def test_value_outside_the_table_is_proved_rejected_and_reported(hip_ctx):
     assert hip_ctx.air_check_trace(desc, to_bytes(rows), rap=[0x5eed]) == want
 
 
-def three_calls(ctx, desc, rows, options):
-    data = to_bytes(rows)
-    return (lambda: ctx.air_prove(desc, data, options), lambda: ctx.air_main_trace(desc, data), lambda: ctx.air_check_trace(desc, data, options))
-
-
 @pytest.mark.parametrize("side", ["x", "t"])
 def test_key_out_of_range_is_refused_and_the_context_goes_on(hip_ctx, side):
     """On X only and on T only, on one row of 4096 (the second sort tile); the sorts and the searches ran on the low bits, in bounds."""
@@ -224,17 +209,7 @@ def test_malformed_count_is_refused_and_the_context_goes_on(hip_ctx):
 
 
 def test_inputs_in_device_memory_give_the_same_bytes(hip_ctx):
-    import torch
-    n, options = 256, api.ProofOptions(*LK_OPTIONS[0])
-    b = air.xor_lookup(n, 4)
-    desc, keep = b.build()
-    host = to_bytes(air.xor_lookup_inputs(n, 4, random.Random(13)))
-    want = hip_ctx.air_prove(desc, host, options)
-    dev = torch.from_numpy(host).to("cuda:0")
-    assert hip_ctx.air_prove(desc, dev, options) == want
-    assert desc.main_desc.input_location == air.INPUTS_DEVICE
-    assert np.array_equal(hip_ctx.air_main_trace(desc, dev), hip_ctx.air_main_trace(desc, host))
-    assert hip_ctx.air_prove(desc, host, options) == want and desc.main_desc.input_location == air.INPUTS_HOST
+    device_inputs_give_the_same_bytes(hip_ctx, air.xor_lookup(256, 4), air.xor_lookup_inputs(256, 4, random.Random(13)), api.ProofOptions(*LK_OPTIONS[0]))
 
 
 # ---- two ranks ------------------------------------------------------------------------------------------------------------------
@@ -242,24 +217,6 @@ def _rank_case(n):
     return L.lookup_case(n, 64, 16, random.Random(31))
 
 
-def _lookup_body(rank, world, n, options):
-    ctx = api.Context(device=0)
-    ctx.set_collective(world, rank, api.StagedAllGather())
-    ctx.set_option(api.SP_OPT_FRI_SHARD_MIN_LOG, 5)
-    b, rows, table = _rank_case(n)
-    desc, keep = b.build()
-    proof = ctx.air_prove(desc, to_bytes(rows), api.ProofOptions(*options))
-    ctx.close()
-    return proof
-
-
 def test_two_ranks_give_the_one_rank_bytes(hip_ctx):
     """Every rank ingests the inputs and builds the COUNT column itself: no exchange before the commitment."""
-    n, options = 4096, LK_OPTIONS[0]
-    b, rows, table = _rank_case(n)
-    desc, keep = b.build()
-    want = hip_ctx.air_prove(desc, to_bytes(rows), api.ProofOptions(*options))
-    assert api.air_verify(want, desc, api.ProofOptions(*options))
-    got = run_ranks(2, _lookup_body, (n, options), timeout=600)
-    for r in range(2):
-        assert got[r] == want, (r, got[r][:400])
+    two_ranks_give_the_one_rank_bytes(hip_ctx, _rank_case, (4096,), LK_OPTIONS[0])

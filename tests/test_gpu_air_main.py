@@ -4,48 +4,15 @@ the entry points that existed before.  Every comparison is exact."""
 import ctypes
 import random
 
-import numpy as np
 import pytest
 
 import main_program_airs as M
 import oracle_lib as O
+from air_device_checks import OPTIONS, device_inputs_give_the_same_bytes, model_ints, prove_full, table_ints, to_bytes, two_ranks_give_the_one_rank_bytes
 from lambdaworks_cairo_prover_amd import _lib, air, api
-from rank_procs import run_ranks
 
 pytestmark = pytest.mark.gpu
 P = air.P
-OPTIONS = [(4, 3, 3, 1), (2, 4, 7, 0)]
-
-
-def to_bytes(rows):
-    return air.ints_to_bytes(np.array(rows, dtype=object))
-
-
-def table_ints(table):
-    return [[int(x) for x in row] for row in air.trace_to_ints(table)]
-
-
-def model_ints(builder, rows):
-    return [[int(x) for x in row] for row in builder.main.evaluate(rows)]
-
-
-def prove_full(ctx, desc, full, options, entry):
-    """The proof of the whole table through sp_air_prove_pub or sp_air_prove_ext: the descriptor's parts, no main program."""
-    lib = _lib.load()
-    ext = air.ext_of(desc)
-    opt = api.ProofOptions(*options).to_c()
-    out, ln = ctypes.POINTER(ctypes.c_uint8)(), ctypes.c_uint64()
-    a = np.ascontiguousarray(full, dtype=np.uint8)
-    assert a.shape[1] == desc.main_cols
-    ptr = a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
-    if entry == "pub":
-        bv = getattr(desc, "boundary_desc", None)
-        rc = lib.sp_air_prove_pub(ctx._h, ctypes.byref(desc), ctypes.byref(ext), None if bv is None else ctypes.byref(bv), ptr, ctypes.c_uint64(a.shape[0]),
-                                  ctypes.byref(opt), ctypes.byref(out), ctypes.byref(ln))
-    else:
-        rc = lib.sp_air_prove_ext(ctx._h, ctypes.byref(desc), ctypes.byref(ext), ptr, ctypes.c_uint64(a.shape[0]), ctypes.byref(opt), ctypes.byref(out), ctypes.byref(ln))
-    _lib.check(rc)
-    return ctx._take_proof(out, ln)
 
 
 def examples(n, rng):
@@ -170,17 +137,8 @@ def test_main_program_beside_a_periodic_column_and_a_stride(hip_ctx):
 
 
 def test_inputs_in_device_memory_give_the_same_bytes(hip_ctx):
-    import torch
-    n, options = 256, api.ProofOptions(4, 3, 3, 1)
-    for name, b, rows in examples(n, random.Random(13)):
-        desc, keep = b.build()
-        host = to_bytes(rows)
-        want = hip_ctx.air_prove(desc, host, options)
-        dev = torch.from_numpy(host).to("cuda:0")
-        assert hip_ctx.air_prove(desc, dev, options) == want, name
-        assert desc.main_desc.input_location == air.INPUTS_DEVICE
-        assert np.array_equal(hip_ctx.air_main_trace(desc, dev), hip_ctx.air_main_trace(desc, host)), name
-        assert hip_ctx.air_prove(desc, host, options) == want and desc.main_desc.input_location == air.INPUTS_HOST
+    for name, b, rows in examples(256, random.Random(13)):
+        device_inputs_give_the_same_bytes(hip_ctx, b, rows, api.ProofOptions(4, 3, 3, 1), name)
 
 
 # ---- traces and statements that are wrong -------------------------------------------------------------------------------------
@@ -264,24 +222,6 @@ def _zero_count_case(n):
     return air.zero_count(n, len([z for z in zeros if z < n - 1])), air.zero_count_inputs(n, zeros, random.Random(31))
 
 
-def _main_body(rank, world, n, options):
-    ctx = api.Context(device=0)
-    ctx.set_collective(world, rank, api.StagedAllGather())
-    ctx.set_option(api.SP_OPT_FRI_SHARD_MIN_LOG, 5)
-    b, rows = _zero_count_case(n)
-    desc, keep = b.build()
-    proof = ctx.air_prove(desc, to_bytes(rows), api.ProofOptions(*options))
-    ctx.close()
-    return proof
-
-
 def test_two_ranks_give_the_one_rank_bytes(hip_ctx):
     """Every rank ingests the inputs and builds every derived column itself: no exchange before the commitment."""
-    n, options = 4096, (4, 3, 3, 1)
-    b, rows = _zero_count_case(n)
-    desc, keep = b.build()
-    want = hip_ctx.air_prove(desc, to_bytes(rows), api.ProofOptions(*options))
-    assert api.air_verify(want, desc, api.ProofOptions(*options))
-    got = run_ranks(2, _main_body, (n, options), timeout=600)
-    for r in range(2):
-        assert got[r] == want, (r, got[r][:400])
+    two_ranks_give_the_one_rank_bytes(hip_ctx, _zero_count_case, (4096,), (4, 3, 3, 1))

@@ -1,19 +1,20 @@
 """Limbs and bitwise words on the device (sp_air_prove_word, sp_air_check_trace_word, sp_air_main_trace_word): the LIMB and WORD
-columns equal the plain reference of word_ref cell for cell, grouping and chunking change no cell, and a proof from the input columns
+columns equal the plain reference of program_ref cell for cell, grouping and chunking change no cell, and a proof from the input columns
 has the bytes of the proof from the whole table through the entry points that existed before.  Every comparison is exact."""
 import ctypes
+import functools
 import random
 
 import numpy as np
 import pytest
 
+import air_device_checks
 import oracle_lib as O
+import program_ref as R
 import word_airs as W
-import word_ref as R
+from air_device_checks import (LK_OPTIONS, OPTIONS, device_inputs_give_the_same_bytes, model_ints, prove_full, table_ints, three_calls, to_bytes,
+                               two_ranks_give_the_one_rank_bytes)
 from lambdaworks_cairo_prover_amd import _lib, air, api
-from rank_procs import run_ranks
-from test_gpu_air_lookup import LK_OPTIONS
-from test_gpu_air_main import OPTIONS, model_ints, prove_full, table_ints, to_bytes
 
 pytestmark = pytest.mark.gpu
 P = air.P
@@ -23,19 +24,7 @@ MISSING = "a fetched key is in no table row"
 OTHER_BITS = {1: 251, 32: 33, 33: 32, 64: 17, 251: 1}
 
 
-def device_table(ctx, b, rows):
-    desc, keep = b.build()
-    assert air.main_suffix(desc) == "word"
-    got = ctx.air_main_trace(desc, to_bytes(rows))
-    assert got.shape == (len(rows), b.main_cols, 32)
-    return table_ints(got)
-
-
-def same_table(ctx, b, rows):
-    got, want = device_table(ctx, b, rows), R.main_table(b.main, rows)
-    for i in range(len(rows)):
-        assert got[i] == want[i], i
-    return want
+same_table = functools.partial(air_device_checks.same_table, suffix="word")
 
 
 # ---- cell equality ----------------------------------------------------------------------------------------------------------
@@ -141,26 +130,10 @@ def test_limb_range_check_proves_as_its_whole_table(hip_ctx, options, n, limb_bi
 
 
 def test_inputs_in_device_memory_give_the_same_bytes(hip_ctx):
-    import torch
-    n, options = 256, api.ProofOptions(*LK_OPTIONS[0])
-    b = air.limb_range_check(n, 4, 2)
-    desc, keep = b.build()
-    host = to_bytes(air.limb_range_check_inputs(n, 4, 2, random.Random(13)))
-    want = hip_ctx.air_prove(desc, host, options)
-    dev = torch.from_numpy(host).to("cuda:0")
-    assert dev.dtype == torch.uint8
-    assert hip_ctx.air_prove(desc, dev, options) == want
-    assert desc.main_desc.input_location == air.INPUTS_DEVICE
-    assert np.array_equal(hip_ctx.air_main_trace(desc, dev), hip_ctx.air_main_trace(desc, host))
-    assert hip_ctx.air_prove(desc, host, options) == want and desc.main_desc.input_location == air.INPUTS_HOST
+    device_inputs_give_the_same_bytes(hip_ctx, air.limb_range_check(256, 4, 2), air.limb_range_check_inputs(256, 4, 2, random.Random(13)), api.ProofOptions(*LK_OPTIONS[0]))
 
 
 # ---- operands that break the call ---------------------------------------------------------------------------------------------
-def three_calls(ctx, desc, rows, options):
-    data = to_bytes(rows)
-    return (lambda: ctx.air_prove(desc, data, options), lambda: ctx.air_main_trace(desc, data), lambda: ctx.air_check_trace(desc, data, options))
-
-
 @pytest.mark.parametrize("value", [1 << 8, P - 1], ids=["two-to-the-bits", "p-minus-1"])
 @pytest.mark.parametrize("side", [0, 1], ids=["x", "y"])
 def test_operand_out_of_range_is_refused_and_the_context_goes_on(hip_ctx, side, value):
@@ -232,22 +205,10 @@ def test_the_older_entry_points_call_kinds_8_and_9_unknown(hip_ctx):
 
 
 # ---- two ranks ------------------------------------------------------------------------------------------------------------------
-def _word_body(rank, world, n, options):
-    ctx = api.Context(device=0)
-    ctx.set_collective(world, rank, api.StagedAllGather())
-    ctx.set_option(api.SP_OPT_FRI_SHARD_MIN_LOG, 5)
-    desc, keep = air.limb_range_check(n, 4, 2).build()
-    proof = ctx.air_prove(desc, to_bytes(air.limb_range_check_inputs(n, 4, 2, random.Random(n))), api.ProofOptions(*options))
-    ctx.close()
-    return proof
+def _rank_case(n):
+    return air.limb_range_check(n, 4, 2), air.limb_range_check_inputs(n, 4, 2, random.Random(n))
 
 
 def test_two_ranks_give_the_one_rank_bytes(hip_ctx):
     """Every rank ingests the inputs and builds the LIMB and COUNT columns itself: no exchange before the commitment."""
-    n, options = 256, LK_OPTIONS[0]
-    desc, keep = air.limb_range_check(n, 4, 2).build()
-    want = hip_ctx.air_prove(desc, to_bytes(air.limb_range_check_inputs(n, 4, 2, random.Random(n))), api.ProofOptions(*options))
-    assert api.air_verify(want, desc, api.ProofOptions(*options))
-    got = run_ranks(2, _word_body, (n, options), timeout=600)
-    for r in range(2):
-        assert got[r] == want, (r, got[r][:400])
+    two_ranks_give_the_one_rank_bytes(hip_ctx, _rank_case, (256,), LK_OPTIONS[0])
