@@ -10,6 +10,14 @@
 // elements (G*32 B contiguous per row -> coalesced) together with the twiddles of exactly those butterflies.
 // All memory orders are chosen so the prover never needs a bit-reversal pass: iNTT leaves coefficients
 // bit-reversed, the LDE consumes them bit-reversed and emits natural order.
+//
+// ntt.hip, device side: ntt_pass_kernel<DIF, LOADM, STOREM, CONTIG, GTW> runs tile map, twiddles, load | stages | store.
+// TileMap maps the block id to tile and vector (XCD order, the coset-major split) and a tile element to its position() in
+// memory and its lidx() in LDS; LdsPlanes is the tile or the twiddle table in LDS; global_tw() addresses the transform's
+// table; load_tile and store_tile move the tile.  The twiddle staging and the stages themselves (radix-4 units of both
+// directions, the radix-2 stage, the DIT pass's fused last-pair store) stand in the kernel body.
+// Host side: every driver hands its pass list, the fields all passes share and a per-pass hook (buffers, strides, load and
+// store modes, post_table / scalar on the last pass) to the one pass loop, run_passes.
 #pragma once
 #include "common.h"
 #include <map>
@@ -54,6 +62,7 @@ struct NttPassArgs {
 
 enum NttLoadMode { NTT_LOAD_INPLACE = 0, NTT_LOAD_GATHER_BITREV = 1, NTT_LOAD_EXPAND = 2 };
 enum NttStoreMode { NTT_STORE_INPLACE = 0, NTT_STORE_SCATTER_BITREV = 1 };
+struct PassGeom;   // one entry of a transform's pass list: (s, r, g)
 
 class NttEngine {
   public:
@@ -97,8 +106,13 @@ class NttEngine {
 
   private:
     int launch_pass(bool dif, int load_mode, int store_mode, const NttPassArgs& a, uint32_t batch);
+    // The one pass loop behind the six drivers above (ntt.hip): walks a geometry() list in DIT or DIF order, fills what follows from
+    // the list (s, r, g, the pass-local table of the direction, weak_out) and lets the driver's hook name buffers, strides and modes.
+    struct PassJob;
+    template <class Hook>
+    int run_passes(bool dif, const std::vector<PassGeom>& geo, const NttPassArgs& common, uint32_t batch, Hook hook);
     hipStream_t stream_;
-    // twiddles of a whole transform: pyramid + stage_tw = 1, or roots(k) + stage_tw = 0
+    // what the passes of a whole size-2^k transform share: logM = logL = k and the twiddles, pyramid + stage_tw = 1 or roots(k) + stage_tw = 0
     int transform_twiddles(int k, NttPassArgs* a);
     std::map<int, fe*> roots_;       // stand-alone tables (no pyramid covered k and none could be allocated)
     std::vector<fe*> pyramids_;      // the last one is the largest; older ones stay alive for kernels in flight and cached roots()

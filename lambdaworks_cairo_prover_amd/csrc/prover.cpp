@@ -320,9 +320,7 @@ int StarkProver::commit_segment_resident(int segment, uint32_t cols, uint8_t roo
         SP_TRY(finish(blocks.size() - 1));
         if (K == 1) SP_TRY(c_->ntt->lde_coset_major(coeffs, lde, (int)logn_, (int)logb_, cols, n_, Nl_, (int)logG_, (int)rank_));
     } else {
-        SP_TRY(c_->ntt->dif_natural_to_bitrev_inverse(coeffs, (int)logn_, cols, n_, d_t1_, d_trace_ + (uint64_t)col0 * n_));
-        // evaluate_offset_fft on the LDE coset (reference prover.rs:161-185)
-        SP_TRY(c_->ntt->lde_coset_major(coeffs, lde, (int)logn_, (int)logb_, cols, n_, Nl_, (int)logG_, (int)rank_));
+        SP_TRY(interpolate_extend(d_trace_ + (uint64_t)col0 * n_, coeffs, lde, cols));
     }
     // batch_commit (reference prover.rs:96-104) straight from the column-major LDE
     SP_TRY(commit_columns(lde, Nl_, cols, segment == 0 ? tree_main_ : tree_aux_, root_out));

@@ -224,6 +224,13 @@ class StarkProver : public sp_deletable {
     int commit_columns(const fe* cols_dev, uint64_t stride, uint32_t ncols, TreeBuf& tree, uint8_t root_out[32]) {
         return commit_local(cols_dev, stride, ncols, Nl_, lde_order(), tree, root_out);
     }
+    // Round 1 of `cols` columns: interpolate_fft (natural-order trace -> bit-reversed coefficients, n^-1 h^j folded in through d_t1_),
+    // then evaluate_offset_fft onto this rank's cosets, coset-major (reference trace.rs:104-110, prover.rs:161-185).  Every array
+    // holds its columns back to back: n_ elements apart in trace and coeffs, Nl_ apart in lde.
+    int interpolate_extend(const fe* trace, fe* coeffs, fe* lde, uint32_t cols) {
+        SP_TRY(c_->ntt->dif_natural_to_bitrev_inverse(coeffs, (int)logn_, cols, n_, d_t1_, trace));
+        return c_->ntt->lde_coset_major(coeffs, lde, (int)logn_, (int)logb_, cols, n_, Nl_, (int)logG_, (int)rank_);
+    }
     int commit_segment_resident(int segment, uint32_t cols, uint8_t root_out[32]);
     // the ingest and the derived columns of commit_main_program, queued on the compute stream; the zero-denominator flag is on its way
     // to host_flags().auxp_zero_den behind them (prover_programs.cpp: a plan made without a HIP call, then the launches)

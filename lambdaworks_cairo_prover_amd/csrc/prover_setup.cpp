@@ -261,8 +261,7 @@ int StarkProver::warm_round1() {
         const uint32_t tc = std::max<uint32_t>(1, (uint32_t)(cols * frac)), slice = std::max<uint32_t>(1, cols / 8);
         for (uint32_t c0 = 0; c0 < tc && !stop; c0 += slice) {
             const uint32_t w = std::min(slice, tc - c0);
-            SP_TRY(c_->ntt->dif_natural_to_bitrev_inverse(d_coeffs_ + (uint64_t)(col0 + c0) * n_, (int)logn_, w, n_, d_t1_, d_trace_ + (uint64_t)(col0 + c0) * n_));
-            SP_TRY(c_->ntt->lde_coset_major(d_coeffs_ + (uint64_t)(col0 + c0) * n_, d_lde_ + (uint64_t)(col0 + c0) * Nl_, (int)logn_, (int)logb_, w, n_, Nl_, (int)logG_, (int)rank_));
+            SP_TRY(interpolate_extend(d_trace_ + (uint64_t)(col0 + c0) * n_, d_coeffs_ + (uint64_t)(col0 + c0) * n_, d_lde_ + (uint64_t)(col0 + c0) * Nl_, w));
             SP_TRY(wait_stream());
             stop = cancelled();
         }

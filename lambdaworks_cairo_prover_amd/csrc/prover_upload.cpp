@@ -133,8 +133,7 @@ int StarkProver::commit_trace_columns(int segment, const uint8_t* cols_host, uin
         if (col_enc >= 0) SP_TRY(decode_elements(c_->stream, col_enc, reinterpret_cast<const uint8_t*>(dst), (uint64_t)w * n_, dst));
         if (!sharded_interp) {
             // interpolate_fft + evaluate_offset_fft of this group (reference trace.rs:104-110, prover.rs:161-185)
-            SP_TRY(c_->ntt->dif_natural_to_bitrev_inverse(coeffs + (uint64_t)c0 * n_, (int)logn_, w, n_, d_t1_, dst));
-            SP_TRY(c_->ntt->lde_coset_major(coeffs + (uint64_t)c0 * n_, lde + (uint64_t)c0 * Nl_, (int)logn_, (int)logb_, w, n_, Nl_, (int)logG_, (int)rank_));
+            SP_TRY(interpolate_extend(dst, coeffs + (uint64_t)c0 * n_, lde + (uint64_t)c0 * Nl_, w));
             if (segment == 0) SP_TRY(maybe_leaf_head(cols, c0 + w, lde));
         }
         SP_HIP_CHECK(hipEventRecord(up_ev_[g].done, c_->stream));
@@ -575,8 +574,7 @@ int StarkProver::commit_trace_pipelined(int segment, const uint8_t* rows_host, u
                     SP_TRY(decode_elements(c_->stream, c_->enc, reinterpret_cast<const uint8_t*>(trace + (uint64_t)gc0 * n_), (uint64_t)w * n_, trace + (uint64_t)gc0 * n_));
                     if (!window_only) {
                         // interpolate_fft + evaluate_offset_fft of this group (reference trace.rs:104-110, prover.rs:161-185)
-                        SP_TRY(c_->ntt->dif_natural_to_bitrev_inverse(coeffs + (uint64_t)gc0 * n_, (int)logn_, w, n_, d_t1_, trace + (uint64_t)gc0 * n_));
-                        SP_TRY(c_->ntt->lde_coset_major(coeffs + (uint64_t)gc0 * n_, lde + (uint64_t)gc0 * Nl_, (int)logn_, (int)logb_, w, n_, Nl_, 0, 0));
+                        SP_TRY(interpolate_extend(trace + (uint64_t)gc0 * n_, coeffs + (uint64_t)gc0 * n_, lde + (uint64_t)gc0 * Nl_, w));   // one GPU here: logG_ = rank_ = 0
                         for (uint32_t j = 0; j < w; ++j) extended[gc0 - c_begin + j] = 1;
                         while (extended_prefix < cols && extended[extended_prefix]) ++extended_prefix;
                         if (segment == 0) SP_TRY(maybe_leaf_head(cols, extended_prefix, lde));

@@ -60,7 +60,9 @@ def test_ntt_2_22_properties(hip_ctx, oracle):
     assert np.array_equal(y, oracle.ntt(raw))
 
 
-@pytest.mark.parametrize("k,blowup,cols", [(3, 2, 1), (6, 4, 3), (10, 4, 2), (12, 8, 2), (13, 16, 1)])
+# blowup 1 is the only way to the in-place contiguous DIT pass: a tile smaller than the work-group (k = 3), a whole 1024-element tile
+# that runs its stages in pairs (k = 10), one contiguous and one strided pass (k = 12)
+@pytest.mark.parametrize("k,blowup,cols", [(3, 2, 1), (6, 4, 3), (10, 4, 2), (12, 8, 2), (13, 16, 1), (3, 1, 1), (10, 1, 2), (12, 1, 2)])
 def test_lde_matches_oracle(hip_ctx, oracle, k, blowup, cols):
     rng = random.Random(3000 + k)
     n = 1 << k
