@@ -84,7 +84,8 @@ const char* sp_version(void);
  * and sp_air_main_count_limits, then sp_air_prove_link, sp_air_check_trace_link, sp_air_main_trace_link, sp_air_main_check_link and
  * sp_air_main_link_limits, then sp_air_prove_div, sp_air_check_trace_div, sp_air_main_trace_div and sp_air_main_check_div, then
  * sp_air_prove_fetch, sp_air_check_trace_fetch, sp_air_main_trace_fetch, sp_air_main_check_fetch and sp_air_main_fetch_limits, and last
- * sp_air_prove_word, sp_air_check_trace_word, sp_air_main_trace_word, sp_air_main_check_word and sp_air_main_word_limits).  A binding compares it (and sp_air_desc_size against its own idea of the struct) when it loads the library, so
+ * sp_air_prove_word, sp_air_check_trace_word, sp_air_main_trace_word, sp_air_main_check_word and sp_air_main_word_limits, and after them
+ * sp_air_prove_int, sp_air_check_trace_int, sp_air_main_trace_int, sp_air_main_check_int and sp_air_main_int_limits).  A binding compares it (and sp_air_desc_size against its own idea of the struct) when it loads the library, so
  * a stale build fails at load time with "rebuild the library" instead of with a missing symbol or shifted fields later. */
 #define SP_ABI_VERSION 7
 int sp_abi_version(void);
@@ -844,6 +845,42 @@ int sp_air_main_check_word(const sp_air_desc* air, const sp_air_ext* ext, const 
 /* out[0] = the most lo + width of a LIMB column (252), out[1] = the most bits of a WORD column (251), out[2] = the number of WORD
  * functions (3: fn 0 .. 2), out[3] = 0 */
 int sp_air_main_word_limits(uint32_t out[4]);
+
+/* ---- Integer ops in chain steps: a recurrence whose next state is an integer function of the state - the rotations, additions
+ * modulo 2^w, XORs, ANDs and ORs of a round of an ARX cipher, of SHA-2 or of Blake.  A LIMB or WORD column is row-local and may not
+ * read its own group, so it cannot stand inside a step.  Through the _int entry points - and only through them: everywhere else ops
+ * 8 .. 11 stay the malformed ops they were - a main program may hold */
+#define SP_AIR_OP_LIMB 8           /* op 8  LIMB a = earlier op, b = lo + 256 width (an immediate)  -> (int(value(a)) >> lo) mod 2^width */
+#define SP_AIR_OP_AND  9           /* op 9  AND  a, b = earlier ops  -> int(value(a)) AND int(value(b))                            */
+#define SP_AIR_OP_OR   10          /* op 10 OR   a, b = earlier ops  -> int(value(a)) OR  int(value(b))                            */
+#define SP_AIR_OP_XOR  11          /* op 11 XOR  a, b = earlier ops  -> int(value(a)) XOR int(value(b))                            */
+/* behind the SEED or the STEP op of an SP_AIR_MAIN_CHAIN column, exactly where op 7 may stand.  int(v) is the canonical integer,
+ * 0 <= int(v) < p, as for kinds 8 and 9.  LIMB: 1 <= width and lo + width <= 252, the limits of a LIMB column; every canonical integer
+ * has limbs, so it has no run-time error.  AND, OR and XOR take no `bits`: both operands must be below 2^251 as canonical integers, and
+ * since 2^251 < p every result is canonical.  An operand at or above 2^251 on any row its group evaluates fails the call with
+ * SP_E_INVALID_ARG, "an integer op's operand is out of range on some row (both operands of an AND, OR or XOR op must be below 2^251 as
+ * canonical integers)": nothing is returned and the context goes on.  It is reported behind a key out of range and a fetched key in no
+ * table row, and before a zero denominator of the same program - a WORD column's place, and where a WORD column of the same program is
+ * out of range too, either of the two messages may come back.  Only the ops a group's seeds or steps reach are evaluated.  Rotation,
+ * shift, NOT and addition or subtraction modulo 2^w have no op: rotl(x, r) over w bits = limb(x, 0, w - r) 2^r + limb(x, w - r, r), and
+ * (x + y) mod 2^w = limb(x + y, 0, w).  Each integer op takes its operands out of Montgomery form and its result back: the cost of two
+ * to three field products.  Every other kind stays as it is: a VALUE, INV_OR_ZERO, BIT, SUM, PRODUCT, COUNT, FETCH, LIMB or WORD
+ * column whose operand depends on an op 8 .. 11 is refused with SP_E_INVALID_ARG and a message that names the column - a row-local
+ * limb or word is a LIMB or WORD column.  The decoder also refuses, naming the op: a LIMB op with width 0 or with lo + width > 252, and
+ * operands that are not earlier values.  Constraint programs, auxiliary programs and boundary programs know no op 8 .. 11.  The _int
+ * entry points accept everything the _word ones do; the proof is unchanged: the same table gives the same bytes.  Argument lists as
+ * the _word entry points. */
+int sp_air_prove_int(sp_ctx* ctx, const sp_air_desc* air, const sp_air_ext* ext, const sp_air_boundary_desc* bvals, const sp_air_main_desc* main,
+                     const void* inputs, uint64_t n, const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len);
+int sp_air_check_trace_int(sp_ctx* ctx, const sp_air_desc* air, const sp_air_ext* ext, const sp_air_boundary_desc* bvals, const sp_air_main_desc* main,
+                           const void* inputs, uint64_t n, const sp_proof_options* opt, const uint8_t* rap, sp_air_violation* out, uint32_t cap,
+                           uint32_t* n_out);
+int sp_air_main_trace_int(sp_ctx* ctx, const sp_air_desc* air, const sp_air_ext* ext, const sp_air_main_desc* main, const void* inputs, uint64_t n,
+                          uint8_t* rows_out);
+int sp_air_main_check_int(const sp_air_desc* air, const sp_air_ext* ext, const sp_air_main_desc* main, uint64_t n);
+/* out[0] = the most lo + width of a LIMB op (252), out[1] = the bits an AND / OR / XOR operand must stay below 2^ of (251), out[2] = the
+ * number of integer ops (4: ops 8 .. 11), out[3] = 0 */
+int sp_air_main_int_limits(uint32_t out[4]);
 
 /* verify::<Stark252PrimeField, A> (reference src/starks/verifier.rs:559-657) on the host CPU: 1 accept, 0 reject (also for
  * malformed proofs or descriptors). */

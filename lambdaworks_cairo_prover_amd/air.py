@@ -52,7 +52,17 @@ P = 2**251 + 17 * 2**192 + 1
 
 OP_LOAD, OP_CONST, OP_ADD, OP_SUB, OP_MUL, OP_OUT, OP_PERIODIC = range(7)
 OP_DIV = 7      # a main-trace program only, behind the seed or step of a CHAIN column (sp_air_prove_div)
-_TWO_VALUES = (OP_ADD, OP_SUB, OP_MUL, OP_DIV)   # the ops whose a and b name earlier values
+# Integer ops of a main-trace program, behind the seed or step of a CHAIN column too (sp_air_prove_int): functions of the canonical integer
+OP_INT_LIMB, OP_INT_AND, OP_INT_OR, OP_INT_XOR = 8, 9, 10, 11   # LIMB: a = a value, b = lo + 256 width (an immediate); the others: two values
+_INT_OPS = (OP_INT_LIMB, OP_INT_AND, OP_INT_OR, OP_INT_XOR)
+INT_OP_BITS = 251                                # both operands of AND, OR and XOR stay below 2^251 < p
+_TWO_VALUES = (OP_ADD, OP_SUB, OP_MUL, OP_DIV, OP_INT_AND, OP_INT_OR, OP_INT_XOR)   # the ops whose a and b name earlier values
+_ONE_VALUE = (OP_INT_LIMB,)                      # the ops whose a names an earlier value and whose b is an immediate
+
+
+def _value_operands(op, a, b):
+    """The earlier values an op reads: what every operand walk follows."""
+    return (a, b) if op in _TWO_VALUES else (a,) if op in _ONE_VALUE else ()
 MAX_OFFSETS, MAX_TRANSITIONS = 8, 64
 AUX_TRACE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint8))
 
@@ -276,7 +286,8 @@ class MainLevel(enum.IntEnum):
     """The entry points a main-trace program goes through, in the order of sp::AirMainLevel (air_desc.h): each level's decoder knows what
     the levels below it know, and the entry points carry its suffix (sp_air_prove_rec, sp_air_main_check_rec, ...; sp_air_main_trace and
     sp_air_main_check at MAIN).  MainLevel.WORD, the level above FETCH, is the one member of MainLevelWord below: it orders, compares and
-    carries its suffix like a member, and iterating MainLevel goes on giving the six levels MAIN .. FETCH."""
+    carries its suffix like a member, and iterating MainLevel goes on giving the six levels MAIN .. FETCH.  MainLevel.INT, above WORD, is
+    the one member of MainLevelInt in the same way."""
     MAIN, REC, LK, LINK, DIV, FETCH = range(6)
 
     @property
@@ -296,6 +307,17 @@ class MainLevelWord(enum.IntEnum):
 MainLevel.WORD = MainLevelWord.WORD
 
 
+class MainLevelInt(enum.IntEnum):
+    """sp::AirMainLevel::Int, the _int entry points (ops 8 .. 11 behind chain seeds and steps), reached as MainLevel.INT: an enumeration
+    of its own for the reason MainLevelWord is one; tests/test_air_int.py holds it against the library."""
+    INT = 7
+
+    suffix = MainLevel.suffix
+
+
+MainLevel.INT = MainLevelInt.INT
+
+
 # What in a main program demands each level above MAIN: a test of a column's (kind, pad) and a test of an op code (None: no such thing).
 _MAIN_DEMANDS = {
     MainLevel.REC: (lambda kind, pad: kind == MAIN_CHAIN, lambda op: op == OP_PERIODIC),      # a chain column, a read of a periodic column
@@ -304,6 +326,7 @@ _MAIN_DEMANDS = {
     MainLevel.DIV: (None, lambda op: op == OP_DIV),                                           # a quotient behind a chain group
     MainLevel.FETCH: (lambda kind, pad: kind == MAIN_FETCH, None),                            # a looked-up value
     MainLevel.WORD: (lambda kind, pad: kind in (MAIN_LIMB, MAIN_WORD), None),                 # a limb or a bitwise word
+    MainLevel.INT: (None, lambda op: op in _INT_OPS),                                         # an integer op behind a chain group
 }
 
 
@@ -344,6 +367,7 @@ def needs_link(desc): return MainLevel.LINK in main_features(desc)
 def needs_div(desc): return MainLevel.DIV in main_features(desc)
 def needs_fetch(desc): return MainLevel.FETCH in main_features(desc)
 def needs_word(desc): return MainLevel.WORD in main_features(desc)
+def needs_int(desc): return MainLevel.INT in main_features(desc)
 
 
 def route(desc, call):
@@ -480,17 +504,17 @@ def _reachable(ops, targets, done=lambda u: False):
         if u in todo or done(u):
             continue
         todo.add(u)
-        if ops[u][0] in _TWO_VALUES:
-            stack += [ops[u][1], ops[u][2]]
+        stack += _value_operands(*ops[u])
     return sorted(todo)
 
 
-def _interpret(ops, which, vals, unknown, const, load=None, periodic=None, div=None, out=None):
+def _interpret(ops, which, vals, unknown, const, load=None, periodic=None, div=None, out=None, integer=None):
     """vals[t] for the ops `which` (ascending) of `ops`: the one place the op codes are dispatched.  The values are whatever supports
     + - * % - Python integers, or numpy object arrays, one vectorised operation per op.  What differs between the callers comes as
     callables, and an op whose callable is None is unknown to the caller, as is any other code: ValueError(unknown(t, op)).
     const(a) fetches a constant (or a challenge), load(a, b) reads a cell, periodic(a, b) reads op 6, div(num, den) is op 7's quotient and
-    out(a, value) takes an OUT (whose own value is what it returns)."""
+    out(a, value) takes an OUT (whose own value is what it returns); integer(op, x, y) is an op 8 .. 11 - y the immediate of a LIMB, the
+    second value of the others."""
     for t in which:
         op, a, b = ops[t]
         if op == OP_ADD:
@@ -509,6 +533,8 @@ def _interpret(ops, which, vals, unknown, const, load=None, periodic=None, div=N
             v = div(vals[a], vals[b])
         elif op == OP_OUT and out is not None:
             v = out(a, vals[b])
+        elif op in _INT_OPS and integer is not None:
+            v = integer(op, vals[a], b if op == OP_INT_LIMB else vals[b])
         else:
             raise ValueError(unknown(t, op))
         vals[t] = v
@@ -754,7 +780,17 @@ class MainProgram(_Program):
                                        2^bits on some row fails the call (SP_E_INVALID_ARG; ValueError in evaluate).  Columns with one
                                        x, y and bits share their two passes out of Montgomery form.
         A shift, a rotation, NOT, an add with carry or a comparison is a limb and a value: rotl(x, r) over w bits is
-        value(limb(x, 0, w - r) 2^r + limb(x, w - r, r))."""
+        value(limb(x, 0, w - r) 2^r + limb(x, w - r, r)).
+
+    A recurrence whose next state is an integer function of the state - a round of an ARX cipher, of SHA-2 or of Blake - takes the same
+    functions as values inside a seed or a step (sp_air_prove_int), where a column cannot stand:
+
+        int_limb(x, lo, width)         (int(x) >> lo) mod 2^width as a value (op 8), 1 <= width, lo + width <= 252
+        int_and(x, y), int_or, int_xor int(x) AND / OR / XOR int(y) as a value (ops 9 .. 11).  An x or y at or above 2^251 on a row the
+                                       group evaluates fails the call (SP_E_INVALID_ARG; ValueError in evaluate)
+        int_rotl(x, r, bits), int_rotr(x, r, bits), int_add(x, y, bits)   a rotation of a `bits`-wide word and (x + y) mod 2^bits, written
+                                       with int_limb and field ops
+        Like a quotient, such a value may feed anything, but only the seed or the step of a chain group may depend on it."""
 
     def __init__(self, input_cols, main_cols, periodic_cols=()):
         if not 1 <= input_cols < main_cols:
@@ -772,6 +808,7 @@ class MainProgram(_Program):
     divs = property(lambda self: self.level >= MainLevel.DIV)
     fetches = property(lambda self: self.level >= MainLevel.FETCH)
     words = property(lambda self: self.level >= MainLevel.WORD)
+    ints = property(lambda self: self.level >= MainLevel.INT)
 
     def load(self, shift, col):
         if not 0 <= shift <= AUX_MAX_SHIFT:
@@ -800,6 +837,49 @@ class MainProgram(_Program):
             raise ValueError("main program: the operands of a quotient must be values of this program")
         self.level = max(self.level, MainLevel.DIV)
         return self._emit(OP_DIV, num.i, den.i)
+
+    def _own(self, *values):
+        values = [self._lift(v) for v in values]
+        if any(v.b is not self for v in values):
+            raise ValueError("main program: the operands of an integer op must be values of this program")
+        self.level = max(self.level, MainLevel.INT)
+        return values
+
+    def int_limb(self, x, lo, width):
+        """(int(x) >> lo) mod 2^width as a value (op 8): see the class.  Legal behind the seed or step of a chain group only."""
+        if lo < 0 or width < 1 or lo + width > MAIN_LIMB_MAX_END:
+            raise ValueError(f"main program: a limb of {width} bits from bit {lo} (1 <= width, 0 <= lo, lo + width <= {MAIN_LIMB_MAX_END})")
+        x, = self._own(x)
+        return self._emit(OP_INT_LIMB, x.i, lo + 256 * width)
+
+    def int_and(self, x, y):
+        """int(x) AND int(y) of two values below 2^251 as a value (op 9): see the class."""
+        x, y = self._own(x, y)
+        return self._emit(OP_INT_AND, x.i, y.i)
+
+    def int_or(self, x, y):
+        x, y = self._own(x, y)
+        return self._emit(OP_INT_OR, x.i, y.i)
+
+    def int_xor(self, x, y):
+        x, y = self._own(x, y)
+        return self._emit(OP_INT_XOR, x.i, y.i)
+
+    def int_rotl(self, x, r, bits):
+        """x, below 2^bits, rotated left by r of its `bits` bits: limb(x, 0, bits - r) 2^r + limb(x, bits - r, r)."""
+        r %= bits
+        if r == 0:
+            return self.int_limb(x, 0, bits)
+        x, = self._own(x)
+        return self.int_limb(x, 0, bits - r) * (1 << r) + self.int_limb(x, bits - r, r)
+
+    def int_rotr(self, x, r, bits):
+        return self.int_rotl(x, -r % bits, bits)
+
+    def int_add(self, x, y, bits):
+        """(x + y) mod 2^bits, for x + y below 2^252 as a canonical integer: limb(x + y, 0, bits)."""
+        x, y = self._own(x, y)
+        return self.int_limb(x + y, 0, bits)
 
     def chain(self, period, seeds, width=None, link=1):
         """Opens a chain group of len(seeds) columns in blocks of `period` rows (see the class); returns its ChainGroup.  link = L > 1
@@ -943,26 +1023,33 @@ class MainProgram(_Program):
             if op == OP_LOAD:
                 reads.append(max(0, b - self.input_cols + 1) if a or not shifted_only else 0)
             else:
-                reads.append(max(reads[a], reads[b]) if op in _TWO_VALUES else 0)
+                reads.append(max((reads[u] for u in _value_operands(op, a, b)), default=0))
         return reads
 
     def _quotients(self):
         """Per op: whether its value depends on a quotient (op 7) - the decoder's mark of the same name."""
         quot = []
         for op, a, b in self.ops:
-            quot.append(op == OP_DIV or (op in _TWO_VALUES and (quot[a] or quot[b])))
+            quot.append(op == OP_DIV or any(quot[u] for u in _value_operands(op, a, b)))
         return quot
+
+    def _integers(self):
+        """Per op: whether its value depends on an integer op 8 .. 11 - the decoder's other chain-only mark."""
+        ints = []
+        for op, a, b in self.ops:
+            ints.append(op in _INT_OPS or any(ints[u] for u in _value_operands(op, a, b)))
+        return ints
 
     def check(self, n=None, level=None):
         """The decoder's rules (air_statement_from_c), for a program whose lists were filled by hand too: ValueError naming the first one
         broken.  n: the trace length a chain group's block length is held against (None: not yet known).  level: the MainLevel whose
         decoder is mirrored (None: self.level, where the program would be routed after what was declared).  Below LK kind 6 is an
         unknown kind; below LINK the bits of a CHAIN column's pad at and above 16 belong to j; below DIV op 7 is a malformed op; below
-        FETCH kind 7 is an unknown kind; below WORD kinds 8 and 9 are.  The _main entry points' refusal of chain columns and op 6 was
+        FETCH kind 7 is an unknown kind; below WORD kinds 8 and 9 are; below INT ops 8 .. 11 are malformed ops.  The _main entry points' refusal of chain columns and op 6 was
         never modelled here, and is not: MAIN is judged as REC."""
         level = self.level if level is None else level
         lookups, links, divs, fetches = (level >= at for at in (MainLevel.LK, MainLevel.LINK, MainLevel.DIV, MainLevel.FETCH))
-        words = level >= MainLevel.WORD
+        words, ints = level >= MainLevel.WORD, level >= MainLevel.INT
         pos = (lambda pad: (pad >> 8) & 255) if links else (lambda pad: pad >> 8)
         n_count = n_fetch = 0
         if self._open is not None:
@@ -975,13 +1062,33 @@ class MainProgram(_Program):
             ok = ((op == OP_LOAD and 0 <= a <= AUX_MAX_SHIFT and 0 <= b < self.main_cols) or (op == OP_CONST and 0 <= a < len(self.consts)) or
                   (op in (OP_ADD, OP_SUB, OP_MUL) and 0 <= a < t and 0 <= b < t) or (op == OP_PERIODIC and 0 <= a <= AUX_MAX_SHIFT) or
                   (divs and op == OP_DIV and 0 <= a < t and 0 <= b < t))
+            if ints and op in _INT_OPS:
+                earlier = [0 <= u < t and self.ops[u][0] != OP_OUT for u in _value_operands(op, a, b)]
+                if not all(earlier):
+                    raise ValueError(f"main program: op {t} is an integer op (op {op}) whose operands are not earlier values (LIMB: a; AND / OR / XOR: a and b)")
+                if op == OP_INT_LIMB and b >> 8 == 0:
+                    raise ValueError(f"main program: op {t} is a LIMB op with width = 0 (b = lo + 256 width, 1 <= width, lo + width <= {MAIN_LIMB_MAX_END})")
+                if op == OP_INT_LIMB and (b & 255) + (b >> 8) > MAIN_LIMB_MAX_END:
+                    raise ValueError(f"main program: op {t} is a LIMB op with lo + width = {(b & 255) + (b >> 8)} (b = lo + 256 width, 1 <= width, "
+                                     f"lo + width <= {MAIN_LIMB_MAX_END})")
+                ok = True
+            if not ok and ints:
+                raise ValueError(f"main program: malformed op {t} (LOAD, CONST, ADD, SUB, MUL, DIV, LIMB, AND, OR, XOR over earlier ops, PERIODIC only)")
             if not ok and divs:
                 raise ValueError(f"main program: malformed op {t} (LOAD, CONST, ADD, SUB, MUL, DIV over earlier ops, PERIODIC only)")
             if not ok:
                 raise ValueError(f"main program: malformed op {t} (LOAD, CONST, ADD, SUB, MUL over earlier ops, PERIODIC only)")
-        reads, shifted, quot = self.reads(), self._reads(True), self._quotients()
+        reads, shifted, quot, integers = self.reads(), self._reads(True), self._quotients(), self._integers()
         refused = ("depends on a quotient (op 7), which only the seed or the step of a CHAIN column may: a row-local quotient is a VALUE "
                    "column's N / D")
+        refused_int = ("depends on an integer op (ops 8 .. 11), which only the seed or the step of a CHAIN column may: a row-local limb or word "
+                       "is a LIMB or WORD column")
+
+        def chain_only(k, *operands):   # (the quotient's refusal first, as the decoder)
+            if any(quot[u] for u in operands):
+                raise ValueError(f"main program: derived column {k} {refused}")
+            if any(integers[u] for u in operands):
+                raise ValueError(f"main program: derived column {k} {refused_int}")
         g0 = g_end = 0      # the chain group that column k belongs to is [g0, g_end), when k < g_end
         for k, (kind, num_op, den_op, pad) in enumerate(self.cols):
             den = den_op != AUX_NO_DEN
@@ -1006,8 +1113,7 @@ class MainProgram(_Program):
                     raise ValueError(f"{who} with bits = {high} (1 .. {MAIN_WORD_MAX_BITS})")
                 if not 0 <= num_op < len(self.ops) or (den and not 0 <= den_op < len(self.ops)):
                     raise ValueError(f"main program: derived column {k} names an op beyond the program")
-                if quot[num_op] or (den and quot[den_op]):
-                    raise ValueError(f"main program: derived column {k} {refused}")
+                chain_only(k, num_op, *([den_op] if den else []))
                 r = max(reads[num_op], reads[den_op] if den else 0)
                 if r > k:
                     raise ValueError(f"main program: derived column {k} reads derived column {r - 1}, which is not an earlier one")
@@ -1024,8 +1130,7 @@ class MainProgram(_Program):
                     raise ValueError(f"main program: derived column {k} names an op beyond the program")
                 if v_op >= len(self.ops) or self.ops[v_op][0] == OP_OUT:
                     raise ValueError(f"main program: derived column {k} is a FETCH column with v_op = {v_op}, which is beyond the program or an OUT")
-                if quot[num_op] or quot[den_op] or quot[v_op]:
-                    raise ValueError(f"main program: derived column {k} {refused}")
+                chain_only(k, num_op, den_op, v_op)
                 r = max(reads[num_op], reads[den_op], reads[v_op])
                 if r > k:
                     raise ValueError(f"main program: derived column {k} reads derived column {r - 1}, which is not an earlier one")
@@ -1040,8 +1145,7 @@ class MainProgram(_Program):
                     raise ValueError(f"main program: derived column {k} is a COUNT column with key_bits = {pad} (1 .. {MAIN_COUNT_MAX_KEY_BITS})")
                 if not (0 <= num_op < len(self.ops) and 0 <= den_op < len(self.ops)):
                     raise ValueError(f"main program: derived column {k} names an op beyond the program")
-                if quot[num_op] or quot[den_op]:
-                    raise ValueError(f"main program: derived column {k} {refused}")
+                chain_only(k, num_op, den_op)
                 r = max(reads[num_op], reads[den_op])
                 if r > k:
                     raise ValueError(f"main program: derived column {k} reads derived column {r - 1}, which is not an earlier one")
@@ -1090,8 +1194,7 @@ class MainProgram(_Program):
                 continue
             if not 0 <= num_op < len(self.ops) or (den and not 0 <= den_op < len(self.ops)):
                 raise ValueError(f"main program: derived column {k} names an op beyond the program")
-            if quot[num_op] or (den and quot[den_op]):
-                raise ValueError(f"main program: derived column {k} {refused}")
+            chain_only(k, num_op, *([den_op] if den else []))
             if den and kind in (MAIN_INV_OR_ZERO, MAIN_BIT):
                 raise ValueError(f"main program: derived column {k} is an INV_OR_ZERO or a BIT and takes no denominator")
             if kind == MAIN_BIT and not 0 <= pad <= MAIN_MAX_BIT:
@@ -1110,7 +1213,9 @@ class MainProgram(_Program):
         column is a dictionary count of X, read on the first row of each table value; ValueError on a key at or above 2^key_bits.  A
         FETCH column is a dictionary from each table key to the first row that holds it; ValueError on a key out of range (the COUNT
         columns' words) or on a looked-up key that no row holds.  LIMB and WORD columns are Python's shifts, masks and bitwise operators
-        on the integers; ValueError, in the device's words, on a WORD operand at or above 2^bits."""
+        on the integers; ValueError, in the device's words, on a WORD operand at or above 2^bits.  An integer op 8 .. 11 behind a seed or
+        a step is the same on the rows its group evaluates; ValueError, in the device's words, on an AND, OR or XOR operand at or
+        above 2^251."""
         import numpy as np
         self.check(len(input_rows))
         rows = input_rows if not isinstance(input_rows, np.ndarray) else input_rows.astype(object)
@@ -1129,10 +1234,22 @@ class MainProgram(_Program):
             except ValueError:
                 raise ValueError("main program: a denominator of a quotient (op 7) is zero on some row") from None
 
+        def integer(op, x, y):    # ops 8 .. 11 on the canonical integers, element by element
+            xs = [int(v) for v in x]
+            if op == OP_INT_LIMB:
+                lo, mask = y & 255, (1 << (y >> 8)) - 1
+                return np.array([(v >> lo) & mask for v in xs], dtype=object)
+            ys = [int(v) for v in y]
+            if any(v >> INT_OP_BITS for v in xs) or any(v >> INT_OP_BITS for v in ys):
+                raise ValueError("main program: an integer op's operand is out of range on some row (both operands of an AND, OR or XOR op must be "
+                                 "below 2^251 as canonical integers)")
+            fn = {OP_INT_AND: int.__and__, OP_INT_OR: int.__or__, OP_INT_XOR: int.__xor__}[op]
+            return np.array([fn(u, v) for u, v in zip(xs, ys)], dtype=object)
+
         def need(t):
             """The value of op t on all rows.  (check() lets no row-local column reach an op 7: kept for a program it was not asked about.)"""
             _interpret(self.ops, _reachable(self.ops, [t], lambda u: vals[u] is not None), vals, unknown, lambda a: np.full(n, self.consts[a], dtype=object),
-                       load=lambda a, b: np.roll(m[:, b], -a), periodic=lambda a, b: periodic[b][(np.arange(n) + a) % len(periodic[b])], div=quotient)
+                       load=lambda a, b: np.roll(m[:, b], -a), periodic=lambda a, b: periodic[b][(np.arange(n) + a) % len(periodic[b])], div=quotient, integer=integer)
             return vals[t]
 
         def run(targets, rows, first, state):
@@ -1140,7 +1257,7 @@ class MainProgram(_Program):
             got = {}
             _interpret(self.ops, _reachable(self.ops, targets), got, unknown, lambda a: np.full(len(rows), self.consts[a], dtype=object),
                        load=lambda a, b: state[b - first] if first <= b < first + len(state) else m[(rows + a) % n, b],
-                       periodic=lambda a, b: periodic[b][(rows + a) % len(periodic[b])], div=quotient)
+                       periodic=lambda a, b: periodic[b][(rows + a) % len(periodic[b])], div=quotient, integer=integer)
             return [got[u] for u in targets]
 
         periodic = [np.array(values, dtype=object) for values in self.periodic_cols]
@@ -2438,3 +2555,106 @@ def ec_subset_sum_result(bits, points, shift):
 def ec_subset_sum_inputs(n, rng):
     """(n, 1) Python ints: a random bit on every row."""
     return [[rng.randrange(2)] for _ in range(n)]
+
+
+# ---- integer ops in chain steps: a worked example ----------------------------------------------------------------------------------
+def _arx_round(x, y, key, bits, alpha, beta):
+    """One round of the Speck-like permutation of arx_chain on two `bits`-wide words: (x', y', the sum before it is reduced)."""
+    mask = (1 << bits) - 1
+    a, r = alpha % bits, beta % bits
+    total = (((x >> a) | (x << (bits - a))) & mask) + y + key
+    x2 = total & mask
+    return x2, (((y << r) | (y >> (bits - r))) & mask) ^ x2, total
+
+
+def arx_chain(n, s, keys, digest, bits=16, alpha=7, beta=2):
+    """n / s independent Speck-like permutations over two `bits`-wide words, one per block of s rows (the shape of an ARX cipher's
+    rounds, and of the additions, rotations and XORs of a SHA-2 or Blake compression): the caller uploads the words a and b (columns 0
+    and 1, below 2^bits, of which only the rows = 0 (mod s) matter) and the device builds the rest (sp_air_prove_int).  Columns 2 and 3
+    are the chain group (x, y) with seeds a and b and the step - integer ops inside a recurrence -
+
+        x' = (rotr(x, alpha) + y + K) mod 2^bits,    y' = rotl(y, beta) xor x'
+
+    K periodic column 0 (period s, values below 2^bits); periodic column 1 is sel = [1] (s - 1) + [0].  Behind the group, all row-local:
+    the bits of x (columns 4 .. 3 + bits) and of y (the next `bits`) - BIT columns - and the two carry bits c_j = limb(rotr(x) + y + K,
+    bits + j, 1) - LIMB columns, rotr(x) written linearly over x's bits.  Constraints under degree_bound_factor 2, no exemption: every
+    bit and carry is a bit; the two recompositions; sel (x' + 2^bits (c_0 + 2 c_1) - rotr(x) - y - K); per bit j sel (yb'_j - r_j - xb'_j +
+    2 r_j xb'_j) with r_j = yb_((j - beta) mod bits) - sel switches both off where a block ends -; x - a and y - b on the rows = 0
+    (mod s).  The boundary constraint x_(s-1) = digest is block 0's public digest (arx_chain_digest).  At bits = 16: 38 columns and 55
+    transition constraints.  No auxiliary segment."""
+    if s < 2 or s & (s - 1) or s > n or len(keys) != s:
+        raise ValueError(f"arx_chain: blocks of {s} rows with {len(keys)} keys on {n} rows (a power of two in 2 .. n, one key per row of a block)")
+    if not 2 <= bits <= 16 or not 0 < alpha % bits or not 0 < beta % bits:
+        raise ValueError(f"arx_chain: {bits}-bit words rotated by {alpha} and {beta} (2 .. 16 bits - 3 bits + 7 transition constraints, and a descriptor "
+                         "takes 64 -, rotations that are no multiple of the width)")
+    if any(not 0 <= int(k) < 1 << bits for k in keys):
+        raise ValueError(f"arx_chain: a key outside 0 .. 2^{bits} - 1")
+    alpha, beta = alpha % bits, beta % bits
+    b = AirBuilder(6 + 2 * bits, [0, 1], 2, periodic=[list(keys), [1] * (s - 1) + [0]], main_inputs=2)
+    m = b.main
+    g = m.chain(s, [m.load(0, 0), m.load(0, 1)])
+    x2 = m.int_add(m.int_rotr(g.state(0), alpha, bits) + g.state(1), m.periodic(0, 0), bits)
+    g.step([x2, m.int_xor(m.int_rotl(g.state(1), beta, bits), x2)])
+    cx, cy = g.cols
+    xb, yb = m.bits(m.load(0, cx), bits), m.bits(m.load(0, cy), bits)
+
+    def rotr_of_bits(load):
+        total = None
+        for j in range(bits):
+            term = load(0, xb[(j + alpha) % bits]) * (1 << j)
+            total = term if total is None else total + term
+        return total
+
+    total = rotr_of_bits(m.load) + m.load(0, cy) + m.periodic(0, 0)
+    carry = [m.limb(total, bits + j, 1) for j in range(2)]
+    for c in xb + yb + carry:
+        v = b.load(0, c)
+        b.constraint(v * (v - 1), degree=2, exemptions=0)
+    for col, cols in ((cx, xb), (cy, yb)):
+        word = None
+        for j, c in enumerate(cols):
+            term = b.load(0, c) * (1 << j)
+            word = term if word is None else word + term
+        b.constraint(word - b.load(0, col), degree=1, exemptions=0)
+    sel = b.periodic(0, 1)
+    b.constraint(sel * (b.load(1, cx) + (b.load(0, carry[0]) + b.load(0, carry[1]) * 2) * (1 << bits) - rotr_of_bits(b.load) - b.load(0, cy) - b.periodic(0, 0)),
+                 degree=2, exemptions=0)
+    for j in range(bits):
+        r, nx = b.load(0, yb[(j - beta) % bits]), b.load(1, xb[j])
+        b.constraint(sel * (b.load(1, yb[j]) - r - nx + r * nx * 2), degree=3, exemptions=0)
+    b.constraint(b.load(0, cx) - b.load(0, 0), degree=1, exemptions=0, period=s, offset=0)
+    b.constraint(b.load(0, cy) - b.load(0, 1), degree=1, exemptions=0, period=s, offset=0)
+    b.boundary(cx, s - 1, digest)
+    return b
+
+
+def arx_chain_digest(words, s, keys, bits=16, alpha=7, beta=2):
+    """x on the last row of the block seeded from words = (a, b): the public digest of arx_chain (rounds 0 .. s - 2; the last key is read
+    by the carries alone)."""
+    x, y = int(words[0]), int(words[1])
+    for t in range(s - 1):
+        x, y, _ = _arx_round(x, y, int(keys[t]), bits, alpha, beta)
+    return x
+
+
+def arx_chain_inputs(n, s, rng, bits=16):
+    """(n, 2) Python ints [a, b] below 2^bits from rng.randrange: two words on every row = 0 (mod s), the caller's filler on the others;
+    the first blocks hold the all-ones and the all-zeros words."""
+    top = (1 << bits) - 1
+    rows = [[rng.randrange(top + 1), rng.randrange(top + 1)] for _ in range(n)]
+    for block, words in enumerate(([top, top], [0, 0], [top, 0])):
+        if block * s < n:
+            rows[block * s] = list(words)
+    return rows
+
+
+def arx_chain_trace(inputs, s, keys, bits=16, alpha=7, beta=2):
+    """The whole main table of arx_chain as (n, 6 + 2 bits) Python ints, from its input rows: shifts, masks and Python's operators."""
+    table = []
+    for i, (a, b) in enumerate(inputs):
+        t = i % s
+        x, y = (int(a), int(b)) if t == 0 else nxt
+        x2, y2, total = _arx_round(x, y, int(keys[t]), bits, alpha, beta)
+        nxt = (x2, y2)
+        table.append([int(a), int(b), x, y] + [(x >> j) & 1 for j in range(bits)] + [(y >> j) & 1 for j in range(bits)] + [(total >> (bits + j)) & 1 for j in range(2)])
+    return table

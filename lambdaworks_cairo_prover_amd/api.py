@@ -599,6 +599,14 @@ def air_main_word_limits():
     return {"limb_end": int(out[0]), "bits": int(out[1]), "functions": int(out[2])}
 
 
+def air_main_int_limits():
+    """sp_air_main_int_limits: {"limb_end": the most lo + width of a LIMB op (op 8), "bits": the bits an AND, OR or XOR operand stays below
+    2^ of, "ops": the number of integer ops (8 .. 11)}."""
+    out = (ctypes.c_uint32 * 4)()
+    check(_lib.load().sp_air_main_int_limits(out))
+    return {"limb_end": int(out[0]), "bits": int(out[1]), "ops": int(out[2])}
+
+
 def air_main_fetch_limits():
     """sp_air_main_fetch_limits: {"key_bits": the most key bits of a FETCH column, "group": the most FETCH columns that share one sort and
     one search, "columns": the most FETCH columns of one main program}."""

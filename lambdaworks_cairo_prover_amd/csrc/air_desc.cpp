@@ -15,7 +15,7 @@ fe air_root_of_unity(int order) {   // the field's 2^192-th root, squared down
 }
 
 size_t air_program_first_bad_op(const std::vector<AirOpHost>& ops, uint32_t load_a_end, uint32_t load_b_end, size_t n_values, uint32_t n_out,
-                                uint32_t n_periodic, bool div) {
+                                uint32_t n_periodic, bool div, bool ints) {
     auto value = [&](uint32_t i, size_t t) { return i < t && ops[i].op != 5; };   // an earlier op that produces a value
     for (size_t t = 0; t < ops.size(); ++t) {
         const AirOpHost& o = ops[t];
@@ -27,6 +27,8 @@ size_t air_program_first_bad_op(const std::vector<AirOpHost>& ops, uint32_t load
             case 5: ok = o.a < n_out && value(o.b, t); break;
             case 6: ok = o.a < load_a_end && o.b < n_periodic; break;
             case 7: ok = div && value(o.a, t) && value(o.b, t); break;
+            case 8: ok = ints && value(o.a, t) && (o.b >> 8) >= 1 && (o.b & 255u) + (o.b >> 8) <= AIR_MAIN_LIMB_MAX_END; break;
+            case 9: case 10: case 11: ok = ints && value(o.a, t) && value(o.b, t); break;
             default: ok = false;
         }
         if (!ok) return t;
@@ -162,9 +164,12 @@ std::string validate_aux_program(const AirAuxHost& aux, uint32_t main_cols, uint
 // without fetch kind 7 is an unknown kind.  word (the _word entry points, with fetch): SP_AIR_MAIN_LIMB columns too - no denominator,
 // pad = lo + 256 width below 2^16, 1 <= width, lo + width <= 252 - and SP_AIR_MAIN_WORD columns - a second operand, pad = fn + 256 bits
 // below 2^16, fn 0 .. 2, bits 1 .. 251 -, both over earlier columns and behind no op 7; without word kinds 8 and 9 are unknown kinds.
+// ints (the _int entry points, with word): ops 8 LIMB and 9 .. 11 AND / OR / XOR over earlier ops, behind the seeds and steps of CHAIN
+// columns only, as op 7; a column of any other kind that depends on one is refused, and without ints they are malformed ops.
 std::string main_from_c(const AirDescHost& air, const sp_air_main_desc* m, uint64_t n, uint32_t n_periodic, AirMainLevel level, AirMainHost& out) {
     const bool rec = air_main_allows_chains(level), lk = air_main_allows_counts(level), link = air_main_allows_runs(level);
     const bool div = air_main_allows_quotients(level), fetch = air_main_allows_fetches(level), word = air_main_allows_words(level);
+    const bool ints = air_main_allows_int_ops(level);
     if (m->size != sizeof(sp_air_main_desc)) return "main program: sp_air_main_desc.size is not sizeof(sp_air_main_desc)";
     if (!m->ops || !m->consts || !m->cols) return "main program: null ops, consts or cols";
     if (m->input_cols == 0 || m->n_cols == 0 || (uint64_t)m->input_cols + m->n_cols != air.main_cols)
@@ -180,7 +185,19 @@ std::string main_from_c(const AirDescHost& air, const sp_air_main_desc* m, uint6
                 return "main program: op " + std::to_string(t) + " reads periodic column " + std::to_string(ops[t].b) + ", and the statement has " +
                        std::to_string(n_periodic) + " (ext->periodic)";
     // (no OUT target; a periodic column only through the _rec entry points: elsewhere ops 0 .. 4 are all that is left)
-    const size_t bad = air_program_first_bad_op(ops, AIR_LIMIT_AUX_SHIFT + 1, air.main_cols, m->n_consts, 0, rec ? n_periodic : 0u, div);
+    const size_t bad = air_program_first_bad_op(ops, AIR_LIMIT_AUX_SHIFT + 1, air.main_cols, m->n_consts, 0, rec ? n_periodic : 0u, div, ints);
+    if (bad < n_ops && ints && air_op_is_integer(ops[bad].op)) {   // (what is wrong with an integer op, by name)
+        const AirOpHost& o = ops[bad];
+        const std::string who = "main program: op " + std::to_string(bad);
+        const auto earlier = [&](uint32_t i) { return i < bad && ops[i].op != 5; };
+        if (!earlier(o.a) || (o.op != 8 && !earlier(o.b)))
+            return who + " is an integer op (op " + std::to_string(o.op) + ") whose operands are not earlier values (LIMB: a; AND / OR / XOR: a and b)";
+        if ((o.b >> 8) == 0) return who + " is a LIMB op with width = 0 (b = lo + 256 width, 1 <= width, lo + width <= 252)";
+        return who + " is a LIMB op with lo + width = " + std::to_string((o.b & 255u) + (o.b >> 8)) + " (b = lo + 256 width, 1 <= width, lo + width <= 252)";
+    }
+    if (bad < n_ops && ints)
+        return "main program: malformed op " + std::to_string(bad) + " (LOAD needs a shift of 0 .. 7 and a main column, CONST a constant, ADD / SUB / MUL / DIV / "
+               "AND / OR / XOR earlier ops, LIMB an earlier op and lo + 256 width, op 6 a shift of 0 .. 7 and a periodic column; there is no OUT and no RAP challenge)";
     if (bad < n_ops && div)
         return "main program: malformed op " + std::to_string(bad) + " (LOAD needs a shift of 0 .. 7 and a main column, CONST a constant, ADD / SUB / MUL / DIV "
                "earlier ops, op 6 a shift of 0 .. 7 and a periodic column; there is no OUT and no RAP challenge)";
@@ -188,19 +205,26 @@ std::string main_from_c(const AirDescHost& air, const sp_air_main_desc* m, uint6
         return "main program: malformed op " + std::to_string(bad) + " (LOAD needs a shift of 0 .. 7 and a main column, CONST a constant, ADD / SUB / MUL earlier "
                "ops; there is no OUT and no RAP challenge, and op 6 - a shift of 0 .. 7 and a periodic column - only through the _rec entry points)";
     // reads[t]: one more than the highest derived column the value of op t depends on (0: inputs only); shifted[t]: the same over the
-    // LOADs at a shift other than 0 alone (what a chain's step may not do to its own group); quot[t]: the value of op t depends on a
-    // quotient (an op 7 is op t or stands behind it), which only the seed and the step of a CHAIN column may
+    // LOADs at a shift other than 0 alone (what a chain's step may not do to its own group); chain_only[t]: the value of op t depends on
+    // a chain-only op - CHAIN_QUOT: a quotient (an op 7 is op t or stands behind it), CHAIN_INT: an integer op 8 .. 11 -, which only the
+    // seed and the step of a CHAIN column may
+    constexpr uint8_t CHAIN_QUOT = 1, CHAIN_INT = 2;
     std::vector<uint32_t> reads(n_ops, 0), shifted(n_ops, 0);
-    std::vector<uint8_t> quot(n_ops, 0);
-    const auto quotient_refused = [](const std::string& who) {
-        return who + " depends on a quotient (op 7), which only the seed or the step of a CHAIN column may: a row-local quotient is a VALUE column's N / D";
+    std::vector<uint8_t> chain_only(n_ops, 0);
+    const auto chain_only_refused = [](const std::string& who, uint8_t marks) {
+        if (marks & CHAIN_QUOT)
+            return who + " depends on a quotient (op 7), which only the seed or the step of a CHAIN column may: a row-local quotient is a VALUE column's N / D";
+        return who + " depends on an integer op (ops 8 .. 11), which only the seed or the step of a CHAIN column may: a row-local limb or word is a LIMB or WORD column";
     };
     for (size_t t = 0; t < n_ops; ++t) {
         const AirOpHost& o = ops[t];
         if (o.op == 0 && o.b >= m->input_cols) { reads[t] = o.b - m->input_cols + 1; shifted[t] = o.a ? reads[t] : 0u; }
         else if (air_op_takes_two_values(o.op)) {
             reads[t] = std::max(reads[o.a], reads[o.b]); shifted[t] = std::max(shifted[o.a], shifted[o.b]);
-            quot[t] = o.op == 7 || quot[o.a] || quot[o.b];
+            chain_only[t] = (o.op == 7 ? CHAIN_QUOT : air_op_is_integer(o.op) ? CHAIN_INT : 0) | chain_only[o.a] | chain_only[o.b];
+        } else if (air_op_takes_one_value(o.op)) {   // (b is lo + 256 width, no value)
+            reads[t] = reads[o.a]; shifted[t] = shifted[o.a];
+            chain_only[t] = CHAIN_INT | chain_only[o.a];
         }
     }
     std::vector<AirMainColumnHost> cols;
@@ -226,7 +250,7 @@ std::string main_from_c(const AirDescHost& air, const sp_air_main_desc* m, uint6
             if (!limb && low >= AIR_MAIN_WORD_FUNCTIONS) return who + " is a WORD column with fn = " + std::to_string(low) + " (0 AND, 1 OR, 2 XOR)";
             if (!limb && (high == 0 || high > AIR_MAIN_WORD_MAX_BITS)) return who + " is a WORD column with bits = " + std::to_string(high) + " (1 .. 251)";
             if (c.num_op >= n_ops || (den && c.den_op >= n_ops)) return who + " names an op beyond the program";
-            if (quot[c.num_op] || (den && quot[c.den_op])) return quotient_refused(who);
+            if (const uint8_t marks = chain_only[c.num_op] | (den ? chain_only[c.den_op] : 0)) return chain_only_refused(who, marks);
             const uint32_t r = std::max(reads[c.num_op], den ? reads[c.den_op] : 0u);
             if (r > k) return who + " reads derived column " + std::to_string(r - 1) + ", which is not an earlier one";
             cols.push_back(AirMainColumnHost{c.kind, c.num_op, c.den_op, low, r, 0u, 0u, 0u, 0u, 0u, high});
@@ -239,7 +263,7 @@ std::string main_from_c(const AirDescHost& air, const sp_air_main_desc* m, uint6
             if (key_bits == 0 || key_bits > AIR_MAIN_FETCH_MAX_KEY_BITS) return who + " is a FETCH column with key_bits = " + std::to_string(key_bits) + " (1 .. 64)";
             if (c.num_op >= n_ops || c.den_op >= n_ops) return who + " names an op beyond the program";
             if (v_op >= n_ops || ops[v_op].op == 5) return who + " is a FETCH column with v_op = " + std::to_string(v_op) + ", which is beyond the program or an OUT";
-            if (quot[c.num_op] || quot[c.den_op] || quot[v_op]) return quotient_refused(who);
+            if (const uint8_t marks = chain_only[c.num_op] | chain_only[c.den_op] | chain_only[v_op]) return chain_only_refused(who, marks);
             const uint32_t r = std::max(std::max(reads[c.num_op], reads[c.den_op]), reads[v_op]);
             if (r > k) return who + " reads derived column " + std::to_string(r - 1) + ", which is not an earlier one";
             if (++n_fetch > AIR_MAIN_FETCH_MAX_COLS) return who + " is the program's FETCH column number " + std::to_string(n_fetch) + " (at most 64)";
@@ -250,7 +274,7 @@ std::string main_from_c(const AirDescHost& air, const sp_air_main_desc* m, uint6
             if (!den) return who + " is a COUNT column without a table (den_op names the table value)";
             if (c.pad == 0 || c.pad > AIR_MAIN_COUNT_MAX_KEY_BITS) return who + " is a COUNT column with key_bits = " + std::to_string(c.pad) + " (1 .. 64)";
             if (c.num_op >= n_ops || c.den_op >= n_ops) return who + " names an op beyond the program";
-            if (quot[c.num_op] || quot[c.den_op]) return quotient_refused(who);
+            if (const uint8_t marks = chain_only[c.num_op] | chain_only[c.den_op]) return chain_only_refused(who, marks);
             const uint32_t r = std::max(reads[c.num_op], reads[c.den_op]);
             if (r > k) return who + " reads derived column " + std::to_string(r - 1) + ", which is not an earlier one";
             if (++n_count > AIR_MAIN_COUNT_MAX_COLS) return who + " is the program's COUNT column number " + std::to_string(n_count) + " (at most 16)";
@@ -290,7 +314,7 @@ std::string main_from_c(const AirDescHost& air, const sp_air_main_desc* m, uint6
             continue;
         }
         if (c.num_op >= n_ops || (den && c.den_op >= n_ops)) return who + " names an op beyond the program";
-        if (quot[c.num_op] || (den && quot[c.den_op])) return quotient_refused(who);
+        if (const uint8_t marks = chain_only[c.num_op] | (den ? chain_only[c.den_op] : 0)) return chain_only_refused(who, marks);
         if (den && (c.kind == SP_AIR_MAIN_INV_OR_ZERO || c.kind == SP_AIR_MAIN_BIT)) return who + " is an INV_OR_ZERO or a BIT and takes no denominator";
         if (c.kind == SP_AIR_MAIN_BIT && c.pad > 251) return who + " names bit " + std::to_string(c.pad) + " (0 .. 251)";
         const uint32_t r = std::max(reads[c.num_op], den ? reads[c.den_op] : 0u);
@@ -352,7 +376,8 @@ std::string air_statement_from_c(const sp_air_desc* d, const sp_air_aux_desc* au
     if (main) {
         // (only the _rec, _lk, _link and _div entry points let a main program hold chain columns and read the periodic columns, only
         // _lk, _link and _div COUNT columns, only _link and _div runs of blocks, only _div quotients behind chain seeds and steps; the
-        // _fetch entry points all of that and FETCH columns, the _word entry points LIMB and WORD columns on top)
+        // _fetch entry points all of that and FETCH columns, the _word entry points LIMB and WORD columns on top, the _int entry points
+        // ops 8 .. 11 behind chain seeds and steps on top of that)
         const std::string refused = main_from_c(air, main, n, st.n_periodic(), st.main_level, st.main.emplace());
         if (!refused.empty()) return refused;
     }

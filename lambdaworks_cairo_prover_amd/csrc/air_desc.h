@@ -59,6 +59,7 @@ constexpr uint32_t AIR_MAIN_LINK_MAX_LOG = 62;   // (l >= 1 and l + k <= log2 n 
 constexpr uint32_t AIR_MAIN_COUNT_MAX_KEY_BITS = 64, AIR_MAIN_COUNT_MAX_COLS = 16;
 constexpr uint32_t AIR_MAIN_FETCH_MAX_KEY_BITS = 64, AIR_MAIN_FETCH_MAX_GROUP = 16, AIR_MAIN_FETCH_MAX_COLS = 64;
 constexpr uint32_t AIR_MAIN_LIMB_MAX_END = 252, AIR_MAIN_WORD_MAX_BITS = 251, AIR_MAIN_WORD_FUNCTIONS = 3;   // (lo + width <= 252; 2^251 < p)
+constexpr uint32_t AIR_MAIN_INT_OPS = 4;   // ops 8 .. 11; the LIMB op shares AIR_MAIN_LIMB_MAX_END, AND / OR / XOR take operands below 2^AIR_MAIN_WORD_MAX_BITS
 struct AirMainColumnHost { uint32_t kind, num_op, den_op, bit, reads, chain_log = 0, chain_pos = 0, key_bits = 0, chain_link = 0, value_op = 0, width = 0; };
 struct AirMainHost {
     uint32_t input_cols = 0, input_location = 0;   // 0: the inputs are host memory, 1: device memory
@@ -115,11 +116,18 @@ bool air_resolve_boundary_into(const AirBoundaryHost& bvals, const std::vector<f
 // OUTs, an OUT one of n_out targets and such an op (n_out 0: no OUT at all), a PERIODIC a < load_a_end and one of n_periodic
 // periodic columns (0: the program cannot read any).  Returns the index of the first op that breaks them, ops.size() when none
 // does.  div (a main-trace program through the _div entry points, and nothing else): op 7 DIV takes two earlier ops that are not OUTs
-// too; without it op 7 is the unknown op it always was.
+// too; without it op 7 is the unknown op it always was.  ints (a main-trace program through the _int entry points, and nothing else):
+// op 8 LIMB takes one such op and the immediate b = lo + 256 width with 1 <= width and lo + width <= 252, ops 9 .. 11 AND / OR / XOR two
+// such ops; without it they are the unknown ops they always were.
 size_t air_program_first_bad_op(const std::vector<AirOpHost>& ops, uint32_t load_a_end, uint32_t load_b_end, size_t n_values, uint32_t n_out,
-                                uint32_t n_periodic, bool div = false);
-// ADD, SUB, MUL and DIV: the ops whose a and b name earlier values (what the slot assignment and the operand walks follow)
-inline bool air_op_takes_two_values(uint8_t op) { return (op >= 2 && op <= 4) || op == 7; }
+                                uint32_t n_periodic, bool div = false, bool ints = false);
+// ADD, SUB, MUL, DIV and the integer AND, OR and XOR: the ops whose a and b name earlier values (what the slot assignment and the
+// operand walks follow).  Op 8, the integer LIMB, has one: its a names an earlier value, its b is the immediate lo + 256 width, which
+// nothing remaps and nothing takes for a slot.
+inline bool air_op_takes_two_values(uint8_t op) { return (op >= 2 && op <= 4) || op == 7 || (op >= 9 && op <= 11); }
+inline bool air_op_takes_one_value(uint8_t op) { return op == 8; }
+// ops 8 .. 11: functions of a value's canonical integer, behind a chain group's seeds and steps only (main_level Int)
+inline bool air_op_is_integer(uint8_t op) { return op >= 8 && op <= 11; }
 // the primitive root of unity of order 2^order (lambdaworks get_primitive_root_of_unity)
 fe air_root_of_unity(int order);
 
@@ -131,13 +139,15 @@ fe air_root_of_unity(int order);
 //   Div    (the _div entry points) op 7 DIV behind the seeds and steps of CHAIN columns: quotients inside a recurrence
 //   Fetch  (the _fetch entry points) FETCH columns too, looked-up values
 //   Word   (the _word entry points) LIMB and WORD columns too, limbs and bitwise functions of canonical integers
-enum class AirMainLevel : uint8_t { Main, Rec, Lk, Link, Div, Fetch, Word };
+//   Int    (the _int entry points) ops 8 .. 11 behind the seeds and steps of CHAIN columns: integer functions inside a recurrence
+enum class AirMainLevel : uint8_t { Main, Rec, Lk, Link, Div, Fetch, Word, Int };
 inline bool air_main_allows_chains(AirMainLevel l) { return l >= AirMainLevel::Rec; }   // (and op 6)
 inline bool air_main_allows_counts(AirMainLevel l) { return l >= AirMainLevel::Lk; }
 inline bool air_main_allows_runs(AirMainLevel l) { return l >= AirMainLevel::Link; }
 inline bool air_main_allows_quotients(AirMainLevel l) { return l >= AirMainLevel::Div; }
 inline bool air_main_allows_fetches(AirMainLevel l) { return l >= AirMainLevel::Fetch; }
 inline bool air_main_allows_words(AirMainLevel l) { return l >= AirMainLevel::Word; }
+inline bool air_main_allows_int_ops(AirMainLevel l) { return l >= AirMainLevel::Int; }
 
 // Everything a prover, a trace check or a verifier is told about a program AIR: the descriptor (its strides inside) and its optional
 // parts, each present or not.  aux_reads_periodic: whether the auxiliary program may read the periodic columns with op 6 (the _pub
@@ -184,6 +194,10 @@ struct AirStatement {
 // denominator, pad = lo + 256 width below 2^16, 1 <= width, lo + width <= 252 - and SP_AIR_MAIN_WORD columns - a second operand
 // (den_op), pad = fn + 256 bits below 2^16, fn 0 .. 2, bits 1 .. 251 -, their operands over earlier columns and behind no op 7;
 // without it kinds 8 and 9 are unknown kinds.  A WORD operand at or above 2^bits is a matter of the rows: SP_E_INVALID_ARG from the call.
+// main_level Int (the _int entry points only; it brings Word with it): ops 8 LIMB a, lo + 256 width and 9 .. 11 AND / OR / XOR a b over
+// earlier ops, behind the seed or step op of a CHAIN column only, as op 7 - a column of any other kind whose operand depends on one is
+// refused (a row-local limb or word is a LIMB or WORD column); without it they are malformed ops, as ever.  An AND / OR / XOR operand
+// at or above 2^251 is a matter of the rows: SP_E_INVALID_ARG from the call.
 // The constraint program itself is checked where it is turned into what runs it (build_air_program, air_verify_host).
 // An sp_air_ext is taken apart by the entry point that receives it; this is the one thing it checks first: null, or what is wrong.
 inline const char* air_ext_refusal(const sp_air_ext* ext) { return ext && ext->size != sizeof(sp_air_ext) ? "sp_air_ext.size is not sizeof(sp_air_ext)" : nullptr; }

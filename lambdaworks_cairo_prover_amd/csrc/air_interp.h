@@ -8,6 +8,7 @@
 // PER = false leaves no test for op 6 in the generated code: a program without periodic columns runs the code it always ran.
 #pragma once
 #include "stark_kernels.h"
+#include "air_words.h"
 
 namespace sp {
 
@@ -35,11 +36,26 @@ __device__ __noinline__ inline fe air_quotient(fe num, fe den, int* __restrict__
     return fe_mul(num, fe_inv(den));
 }
 
+// ops 8 .. 11 of a chain group's seed and step programs: functions of the canonical integer (air_words.h), so a value leaves
+// Montgomery form, is worked on and goes back - a field product each way.  The op's immediates are the same for every lane, so the
+// shift amounts and masks stay scalar; the operands arrive by value, out of the value file, and nothing here indexes a register.
+// LIMB: b = lo + 256 width.
+__device__ __forceinline__ fe air_int_op_limb(const fe& a, uint32_t b) { return fe_to_mont(air_int_limb(fe_from_mont(a), b & 255u, b >> 8)); }
+// AND / OR / XOR (fn = op - 9) of two operands below 2^251.  An operand beyond that is a compare and a plain store of the flag value -
+// every lane that stores stores the same word, and no lane leaves early -; the result is masked to 251 bits, a canonical integer
+// whatever the operands were.
+__device__ __forceinline__ fe air_int_op_word(const fe& a, const fe& b, uint32_t fn, int* __restrict__ range_flag) {
+    const fe x = fe_from_mont(a), y = fe_from_mont(b);
+    if (air_int_exceeds(x, AIR_INT_OP_BITS) || air_int_exceeds(y, AIR_INT_OP_BITS)) *range_flag = AIR_INT_OP_FLAG_RANGE;
+    return fe_to_mont(air_int_word(x, y, fn, AIR_INT_OP_BITS));
+}
+
 // DIV = false leaves no test for op 7 either: every consumer but the chain kernel's DIV instantiations compiles the code it compiled
-// before, and zero_flag is not looked at.
-template <bool PER, bool DIV = false, class Load, class Periodic, class Out>
+// before, and zero_flag is not looked at.  INT = false does the same for ops 8 .. 11 and range_flag: only the chain kernel's INT
+// instantiations know them.
+template <bool PER, bool DIV = false, bool INT = false, class Load, class Periodic, class Out>
 __device__ __forceinline__ void air_run_program(const AirOpDev* __restrict__ ops, uint32_t n_ops, const fe* __restrict__ consts, Load load,
-                                                Periodic periodic, Out out, int* __restrict__ zero_flag = nullptr) {
+                                                Periodic periodic, Out out, int* __restrict__ zero_flag = nullptr, int* __restrict__ range_flag = nullptr) {
     fe v[AIR_MAX_LIVE];
     for (uint32_t t = 0; t < n_ops; ++t) {
         const AirOpDev o = ops[t];
@@ -59,6 +75,10 @@ __device__ __forceinline__ void air_run_program(const AirOpDev* __restrict__ ops
             default:
                 if constexpr (DIV) {
                     if (o.op == 7) { r = air_quotient(v[o.a], v[o.b], zero_flag); break; }
+                }
+                if constexpr (INT) {
+                    if (o.op == 8) { r = air_int_op_limb(v[o.a], o.b); break; }
+                    if (o.op >= 9) { r = air_int_op_word(v[o.a], v[o.b], o.op - 9u, range_flag); break; }
                 }
                 out(o.a, v[o.b]);
                 continue;

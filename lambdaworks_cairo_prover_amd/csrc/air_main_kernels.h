@@ -23,10 +23,16 @@ namespace sp {
 // device memory, zeroed by the caller): the programs may hold op 7 DIV a b = v[a] / v[b], one fe_inv per lane and op; a lane that meets
 // a zero denominator stores 1 there (a plain store; every such lane stores the same word) and goes on with a quotient of zero, so all
 // its stores stay where they belong and the caller refuses the table once the stream has drained.
+// range_flag: null for a group whose programs hold no op 8 .. 11 - it launches the instantiation it always launched.  Non-null (the
+// WORD columns' verdict word, zeroed by the caller): the programs may hold op 8 LIMB a, lo + 256 width = (int(v[a]) >> lo) mod 2^width
+// and ops 9 .. 11 AND / OR / XOR a b over the canonical integers of v[a] and v[b] (air_words.h); a lane whose AND / OR / XOR operand is
+// at or above 2^251 stores AIR_MAIN_FLAG_INT_RANGE there (a plain store; every such lane stores the same word) and goes on with the
+// result masked to 251 bits, so every cell is written once and holds a canonical integer.
 constexpr uint32_t AIR_MAIN_CHAIN_WIDTH = 16;
+constexpr int AIR_MAIN_FLAG_INT_RANGE = 2;   // (beside AIR_MAIN_FLAG_WORD_RANGE, in the same word; air_words.h AIR_INT_OP_FLAG_RANGE)
 int air_main_chain(hipStream_t st, fe* trace, uint64_t n, uint32_t log_s, uint32_t log_k, uint32_t first_col, uint32_t w, const AirOpDev* seed_ops,
                    uint32_t n_seed, const AirOpDev* step_ops, uint32_t n_step, const fe* consts, const AirPeriodicCol* pcols = nullptr,
-                   const fe* pvals = nullptr, int* zero_flag = nullptr);
+                   const fe* pvals = nullptr, int* zero_flag = nullptr, int* range_flag = nullptr);
 // One COUNT column (a lookup multiplicity): kx the n looked-up keys in ascending order, kt the n table keys in ascending order - sorted
 // stably, rows[p] the row that table key p came from - all from air_aux_sort_terms and radix_sort_pairs_u64.  One lane per p: on the
 // head of a run of equal table keys (p == 0 or kt[p] != kt[p - 1]) z = upper_bound(kx, kt[p]) - lower_bound(kx, kt[p]), elsewhere

@@ -2,6 +2,7 @@
 #include "air_main_kernels.h"
 #include "air_interp.h"
 #include "air_words.h"
+#include <type_traits>
 
 namespace sp {
 
@@ -24,12 +25,17 @@ namespace sp {
 // dominated by its inversions, tens of microseconds each against well under one for a polynomial op -, and zero_flag is the word a
 // lane that meets a zero denominator stores 1 to.  An instantiation of its own too: zero_flag is not read without it, and a group
 // without an op 7 launches the code it always launched, whatever entry point its program came through.
-template <bool PER, bool LINKED, bool DIV>
+// INT (a group whose seed or step program holds an op 8 .. 11): the interpreter knows the integer LIMB, AND, OR and XOR (air_interp.h) -
+// each takes its operands out of Montgomery form and its result back, two to three field products beside a handful of scalar-masked
+// limb operations, so a round of an ARX cipher costs what as many MULs would -, and range_flag is the word a lane whose AND / OR / XOR
+// operand is at or above 2^251 stores AIR_MAIN_FLAG_INT_RANGE to.  An instantiation of its own as well, for the same reason:
+// range_flag is not read without it.  The ops add no per-lane array: operands and results pass through the interpreter's value file.
+template <bool PER, bool LINKED, bool DIV, bool INT>
 __global__ void __launch_bounds__(64) air_main_chain_kernel(fe* __restrict__ group, const fe* __restrict__ trace, uint64_t n, uint32_t log_s, uint32_t first_col,
                                                             uint32_t w, const AirOpDev* __restrict__ seed_ops, uint32_t n_seed,
                                                             const AirOpDev* __restrict__ step_ops, uint32_t n_step, const fe* __restrict__ consts,
                                                             const AirPeriodicCol* __restrict__ pcols, const fe* __restrict__ pvals, uint32_t log_k,
-                                                            int* __restrict__ zero_flag) {
+                                                            int* __restrict__ zero_flag, int* __restrict__ range_flag) {
     const uint32_t log_run = LINKED ? log_s + log_k : log_s;
     const uint64_t L = (uint64_t)blockIdx.x * 64 + threadIdx.x;
     if (L >= (n >> log_run)) return;   // (with fewer than 64 blocks or runs the only wave is partly empty)
@@ -49,9 +55,11 @@ __global__ void __launch_bounds__(64) air_main_chain_kernel(fe* __restrict__ gro
             fe_st(group + (uint64_t)j * n + i, next[j]);
         }
     };
-    auto run = [&](const AirOpDev* ops, uint32_t n_ops, auto load) {
-        if constexpr (PER) air_run_program<true, DIV>(ops, n_ops, consts, load, periodic, to_next, zero_flag);
-        else air_run_program<false, DIV>(ops, n_ops, consts, load, AirNoPeriodic{}, to_next, zero_flag);
+    // (always inlined: a linked group calls it with one load functor for seeds and steps, and an out-of-line copy would take its
+    // arguments and the captured arrays through the call's stack)
+    auto run = [&](const AirOpDev* ops, uint32_t n_ops, auto load) __attribute__((always_inline)) {
+        if constexpr (PER) air_run_program<true, DIV, INT>(ops, n_ops, consts, load, periodic, to_next, zero_flag, range_flag);
+        else air_run_program<false, DIV, INT>(ops, n_ops, consts, load, AirNoPeriodic{}, to_next, zero_flag, range_flag);
     };
     auto block = [&](auto seed_load) {   // the seeds on the block's first row, then its s - 1 steps; leaves i on the block's last row
         run(seed_ops, n_seed, seed_load);
@@ -72,10 +80,10 @@ __global__ void __launch_bounds__(64) air_main_chain_kernel(fe* __restrict__ gro
 }
 
 // log_k = 0: an unlinked group, one lane per block; log_k >= 1: runs of 2^log_k blocks, one lane per run.  zero_flag non-null: the
-// programs hold an op 7.
+// programs hold an op 7; range_flag non-null: they hold an op 8 .. 11.
 int air_main_chain(hipStream_t st, fe* trace, uint64_t n, uint32_t log_s, uint32_t log_k, uint32_t first_col, uint32_t w, const AirOpDev* seed_ops,
                    uint32_t n_seed, const AirOpDev* step_ops, uint32_t n_step, const fe* consts, const AirPeriodicCol* pcols, const fe* pvals,
-                   int* zero_flag) {
+                   int* zero_flag, int* range_flag) {
     if (n == 0 || (n & (n - 1)) || log_s == 0 || log_s + log_k >= 64 || (1ull << (log_s + log_k)) > n || w == 0 || w > AIR_MAIN_CHAIN_WIDTH ||
         (pcols == nullptr) != (pvals == nullptr))
         return SP_E_INVALID_ARG;
@@ -84,13 +92,15 @@ int air_main_chain(hipStream_t st, fe* trace, uint64_t n, uint32_t log_s, uint32
     fe* group = trace + (uint64_t)first_col * n;
     auto launch = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, grid, dim3(64), 0, st, group, trace, n, log_s, first_col, w, seed_ops, n_seed, step_ops, n_step, consts, pcols, pvals, log_k,
-                           zero_flag);
+                           zero_flag, range_flag);
     };
-    if (zero_flag) {
-        if (log_k == 0) pcols ? launch(air_main_chain_kernel<true, false, true>) : launch(air_main_chain_kernel<false, false, true>);
-        else pcols ? launch(air_main_chain_kernel<true, true, true>) : launch(air_main_chain_kernel<false, true, true>);
-    } else if (log_k == 0) pcols ? launch(air_main_chain_kernel<true, false, false>) : launch(air_main_chain_kernel<false, false, false>);
-    else pcols ? launch(air_main_chain_kernel<true, true, false>) : launch(air_main_chain_kernel<false, true, false>);
+    auto pick = [&](auto div, auto ints) {   // (the two switches as types: one ladder over PER and LINKED for the four pairs)
+        constexpr bool DIV = decltype(div)::value, INT = decltype(ints)::value;
+        if (log_k == 0) pcols ? launch(air_main_chain_kernel<true, false, DIV, INT>) : launch(air_main_chain_kernel<false, false, DIV, INT>);
+        else pcols ? launch(air_main_chain_kernel<true, true, DIV, INT>) : launch(air_main_chain_kernel<false, true, DIV, INT>);
+    };
+    if (range_flag) zero_flag ? pick(std::true_type{}, std::true_type{}) : pick(std::false_type{}, std::true_type{});
+    else zero_flag ? pick(std::true_type{}, std::false_type{}) : pick(std::false_type{}, std::false_type{});
     SP_HIP_CHECK(hipGetLastError());
     return SP_OK;
 }

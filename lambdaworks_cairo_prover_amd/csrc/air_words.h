@@ -1,7 +1,7 @@
 // The two integer functions of a main-trace program (include/stark252_hip.h SP_AIR_MAIN_LIMB, SP_AIR_MAIN_WORD) over the canonical
 // integer of a field element: eight little-endian 32-bit limbs, out of Montgomery form (fe_from_mont).  They are what the shared
 // interpreter (air_interp.h, field ops only) cannot express.  Here, and not in a kernel, so that an integer op of a chain group's step
-// - a SHA-, Blake- or Keccak-style round - can call them one day.  lo, width, bits and fn are the same for every lane: every shift
+// - a SHA-, Blake- or Keccak-style round - can call them too (air_interp.h, ops 8 .. 11).  lo, width, bits and fn are the same for every lane: every shift
 // amount and mask below is a scalar, and no value's registers are indexed with a run-time index.
 #pragma once
 #include "fp.h"
@@ -9,6 +9,10 @@
 namespace sp {
 
 constexpr uint32_t AIR_WORD_AND = 0, AIR_WORD_OR = 1, AIR_WORD_XOR = 2;
+// The integer ops of a chain step (ops 9 .. 11, fn = op - 9): operands below 2^251 < p, and the value a lane that meets a larger one
+// stores to the WORD columns' verdict word.
+constexpr uint32_t AIR_INT_OP_BITS = 251;
+constexpr int AIR_INT_OP_FLAG_RANGE = 2;
 
 // Limb l of the mask 2^bits - 1 (bits <= 256).
 SP_HD uint32_t air_low_mask_limb(uint32_t bits, uint32_t l) {

@@ -125,6 +125,9 @@ class StarkProver : public sp_deletable {
     // ahead of a zero denominator.  At Word LIMB and WORD columns (SP_AIR_MAIN_LIMB, SP_AIR_MAIN_WORD) are members of a row-local chunk,
     // grouped by their operands as BIT columns are: air_main_limbs and air_main_words behind the chunk's one pass of terms; a WORD
     // operand at or above 2^bits is SP_E_INVALID_ARG once the root is back, behind a missing key and ahead of a zero denominator.
+    // At Int a chain group whose slotted seed or step program still holds an op 8 .. 11 launches the kernel's INT instantiation with
+    // the WORD columns' verdict word - an AND, OR or XOR operand at or above 2^251 is the same SP_E_INVALID_ARG, under a value of its
+    // own -, every other group the instantiation it always launched.
     int commit_main_program(const AirStatement& st, const uint8_t* inputs, uint8_t root_out[32]);
     // the same table without the commitment, to host memory: row-major n x main_cols, context encoding (sp_air_main_trace)
     int main_program_table(const AirStatement& st, const uint8_t* inputs, uint8_t* rows_out);

@@ -19,21 +19,23 @@ static constexpr uint64_t AUXP_CHUNK_ELEMS = 1ull << 22;
 
 // The program `src` with an OUT behind every op whose value is wanted - outs[t]: the codes op t is stored under - (a value then lives
 // only until it is stored), slots by air_assign_slots (which drops what these OUTs do not need).  reads_periodic: an op 6 is among
-// what air_assign_slots kept, a table read that feeds one of these OUTs; divides: an op 7 is among them, a quotient that does.
+// what air_assign_slots kept, a table read that feeds one of these OUTs; divides: an op 7 is among them, a quotient that does; integers:
+// an op 8 .. 11 is, an integer function that does.
 static int program_with_outs(const std::vector<AirOpHost>& src, const std::vector<std::vector<uint32_t>>& outs, const char* live_error,
-                             std::vector<AirOpDev>& dev, bool& reads_periodic, bool& divides) {
+                             std::vector<AirOpDev>& dev, bool& reads_periodic, bool& divides, bool& integers) {
     std::vector<AirOpHost> ext;
     std::vector<uint32_t> at(src.size());
     for (size_t t = 0; t < src.size(); ++t) {
         AirOpHost o = src[t];
         if (air_op_takes_two_values(o.op)) { o.a = at[o.a]; o.b = at[o.b]; }   // (LOAD, CONST and PERIODIC name cells, not values)
+        else if (air_op_takes_one_value(o.op)) o.a = at[o.a];                  // (an integer LIMB: b is lo + 256 width)
         at[t] = (uint32_t)ext.size();
         ext.push_back(o);
         for (uint32_t code : outs[t]) ext.push_back(AirOpHost{5, code, at[t]});
     }
     SP_TRY(air_assign_slots(ext, dev, live_error));
-    reads_periodic = divides = false;
-    for (const AirOpDev& o : dev) { reads_periodic |= o.op == 6; divides |= o.op == 7; }
+    reads_periodic = divides = integers = false;
+    for (const AirOpDev& o : dev) { reads_periodic |= o.op == 6; divides |= o.op == 7; integers |= air_op_is_integer(o.op); }
     return SP_OK;
 }
 
@@ -103,8 +105,8 @@ int StarkProver::commit_aux_program(const AirStatement& st, const std::vector<fe
     const uint32_t n_src = (uint32_t)aux.ops.size();
     bool any_periodic = false;
     auto program = [&](const std::vector<std::vector<uint32_t>>& outs, std::vector<AirOpDev>& dev, bool& reads_periodic) -> int {
-        bool divides = false;   // (never: validate_aux_program knows no op 7)
-        SP_TRY(program_with_outs(aux.ops, outs, "aux program: more than 64 values alive at once", dev, reads_periodic, divides));
+        bool divides = false, integers = false;   // (never: validate_aux_program knows no op 7 .. 11)
+        SP_TRY(program_with_outs(aux.ops, outs, "aux program: more than 64 values alive at once", dev, reads_periodic, divides, integers));
         any_periodic |= reads_periodic;
         return SP_OK;
     };
@@ -262,7 +264,8 @@ struct MainChunk {
     // Chain: a chain group (SP_AIR_MAIN_CHAIN), a chunk of its own that ends the chunk before it: the seeds' program and the steps',
     //   each with an OUT per group column, and one launch of air_main_chain - a lane per block, or per run of 2^log_k blocks of a
     //   linked group; nothing of the group is read before that launch is over, which the stream's order guarantees.  No workspace.
-    //   A group whose programs hold an op 7 (divides) hands the launch the zero-denominator flag the batch inversions share.
+    //   A group whose programs hold an op 7 (divides) hands the launch the zero-denominator flag the batch inversions share, one
+    //   whose programs hold an op 8 .. 11 (integers) the range flag the WORD columns share.
     // Count: a COUNT column (SP_AIR_MAIN_COUNT), a chunk of its own too: X's program and T's, each with the one OUT of a key pass; two
     //   launches of air_aux_sort_terms (keys out of Montgomery form, the row beside each), two radix sorts - the table's carries its
     //   rows - and one launch of air_main_count, which writes every cell of the column.  Its arrays (4 x [n] keys, 4 x [n] rows, the
@@ -292,6 +295,7 @@ struct MainChunk {
     // Chain
     uint32_t log_s = 0, log_k = 0;           // blocks of 2^log_s rows; log_k >= 1: runs of 2^log_k blocks
     bool divides = false;                    // the slotted seed or step program holds an op 7: the launch takes the zero flag
+    bool integers = false;                   // it holds an op 8 .. 11: the launch takes the range flag
     // Count, Fetch
     uint32_t key_bits = 0;
 };
@@ -299,8 +303,8 @@ struct MainChunk {
 struct MainPlan {
     std::vector<MainChunk> chunks;
     uint32_t chunk = 0, max_slots = 0, max_inv = 0;
-    bool any_count = false, any_fetch = false, any_word = false;
-    bool any_verdict() const { return any_count || any_fetch || any_word; }   // the three verdict words behind the workspace are in use
+    bool any_count = false, any_fetch = false, any_word = false, any_int = false;
+    bool any_verdict() const { return any_count || any_fetch || any_word || any_int; }   // the three verdict words behind the workspace are in use
     uint32_t max_fetch = 0;                  // the widest FETCH group
     size_t o_consts = 0, bytes = 0;          // the upload block: the constants, per chunk its programs and tables, the periodic columns
     PeriodicUpload per;
@@ -315,8 +319,8 @@ static int plan_main_program(const AirStatement& st, uint64_t n, MainPlan& P) {
     bool any_periodic = false;
     // (a chunk's programs share one flag)
     auto program = [&](const std::vector<std::vector<uint32_t>>& outs, MainChunk& ch, int which) -> int {
-        bool reads_periodic = false, divides = false;
-        SP_TRY(program_with_outs(mp.ops, outs, "main program: more than 64 values alive at once", ch.prog[which], reads_periodic, divides));
+        bool reads_periodic = false, divides = false, integers = false;
+        SP_TRY(program_with_outs(mp.ops, outs, "main program: more than 64 values alive at once", ch.prog[which], reads_periodic, divides, integers));
         ch.periodic |= reads_periodic;
         any_periodic |= reads_periodic;
         // (only the chain kernel's DIV instantiations know op 7, and only the statement's level lets it in)
@@ -325,6 +329,13 @@ static int plan_main_program(const AirStatement& st, uint64_t n, MainPlan& P) {
             return SP_E_INVALID_ARG;
         }
         ch.divides |= divides;
+        // (nor does anything else know ops 8 .. 11: the chain kernel's INT instantiations alone)
+        if (integers && (ch.kind != MainChunk::Kind::Chain || !air_main_allows_int_ops(st.main_level))) {
+            sp_set_error("commit_main_program: an integer op (8 .. 11) outside a chain group's programs (the decoder should have refused it)");
+            return SP_E_INVALID_ARG;
+        }
+        ch.integers |= integers;
+        P.any_int |= integers;
         return SP_OK;
     };
     for (uint32_t k0 = 0; k0 < K;) {
@@ -475,7 +486,8 @@ static int plan_main_program(const AirStatement& st, uint64_t n, MainPlan& P) {
 // Launching: the ingest, the upload and the chunks one behind the other.  The three verdict words lie inside the one element behind
 // ws_elems, in the order of HostFlags' auxp_bad_key, auxp_missing_key and auxp_bad_word, which one copy fills: the key-range flag of
 // the COUNT and FETCH columns, which no batch inversion before or behind overwrites there; the missing-key flag of the FETCH columns,
-// which neither a key pass nor a batch inversion does; the range flag of the WORD columns, which air_main_words alone writes.
+// which neither a key pass nor a batch inversion does; the range flag of the WORD columns, which air_main_words writes, and a chain
+// group with integer ops with a value of its own (AIR_MAIN_FLAG_INT_RANGE).
 int StarkProver::build_main_program(const AirStatement& st, const uint8_t* inputs) {
     const AirMainHost& mp = *st.main;
     const uint32_t I = mp.input_cols, K = (uint32_t)mp.cols.size();
@@ -537,7 +549,7 @@ int StarkProver::build_main_program(const AirStatement& st, const uint8_t* input
         switch (ch.kind) {
         case MainChunk::Kind::Chain:
             SP_TRY(air_main_chain(c_->stream, d_trace_, n_, ch.log_s, ch.log_k, I + ch.k0, ch.kc, prog[MainChunk::SEED], n_prog[MainChunk::SEED], prog[MainChunk::STEP],
-                                  n_prog[MainChunk::STEP], consts_dev, pc, pv, ch.divides ? c_->d_flag : nullptr));
+                                  n_prog[MainChunk::STEP], consts_dev, pc, pv, ch.divides ? c_->d_flag : nullptr, ch.integers ? word_flag : nullptr));
             break;
         case MainChunk::Kind::Count:   // key passes, sorts (the sorted pairs end up in keys / rows [1] and [3]), the join
             SP_TRY(air_aux_sort_terms(c_->stream, d_trace_, n_, prog[MainChunk::KEY_X], n_prog[MainChunk::KEY_X], consts_dev, nullptr, s.keys[0], s.rows[0], ch.key_bits, key_flag, pc, pv));
@@ -576,7 +588,7 @@ int StarkProver::build_main_program(const AirStatement& st, const uint8_t* input
 }
 
 // What the flags say once the stream has drained: the key range first (as commit_aux_program), then a missing key, then a word operand
-// out of range, then a zero denominator.
+// or an integer op's out of range (one word: whichever stored last), then a zero denominator.
 static int main_program_verdict(const HostFlags& f) {
     if (f.auxp_bad_key == AIR_AUX_FLAG_KEY_RANGE) {
         sp_set_error("commit_main_program: a lookup key is out of range on some row (X and T of a COUNT column must be below 2^key_bits as canonical integers)");
@@ -588,6 +600,10 @@ static int main_program_verdict(const HostFlags& f) {
     }
     if (f.auxp_bad_word == AIR_MAIN_FLAG_WORD_RANGE) {
         sp_set_error("commit_main_program: a word operand is out of range on some row (both operands of a WORD column must be below 2^bits as canonical integers)");
+        return SP_E_INVALID_ARG;
+    }
+    if (f.auxp_bad_word == AIR_MAIN_FLAG_INT_RANGE) {
+        sp_set_error("commit_main_program: an integer op's operand is out of range on some row (both operands of an AND, OR or XOR op must be below 2^251 as canonical integers)");
         return SP_E_INVALID_ARG;
     }
     if (f.auxp_zero_den) { sp_set_error("commit_main_program: a derived main column's denominator is zero on some row"); return SP_E_ZERO_INVERSE; }

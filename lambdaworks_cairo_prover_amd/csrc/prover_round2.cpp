@@ -133,12 +133,14 @@ int air_assign_slots(const std::vector<AirOpHost>& ops, std::vector<AirOpDev>& d
         const AirOpHost& o = ops[t];
         if (o.op == 5) { live[t] = 1; live[o.b] = 1; }
         else if (live[t] && air_op_takes_two_values(o.op)) { live[o.a] = 1; live[o.b] = 1; }
+        else if (live[t] && air_op_takes_one_value(o.op)) live[o.a] = 1;   // (an integer LIMB: b is an immediate)
     }
     std::vector<uint32_t> last_use(n_src, 0);
     for (uint32_t t = 0; t < n_src; ++t) {
         if (!live[t]) continue;
         const AirOpHost& o = ops[t];
         if (air_op_takes_two_values(o.op)) { last_use[o.a] = t; last_use[o.b] = t; }
+        else if (air_op_takes_one_value(o.op)) last_use[o.a] = t;
         else if (o.op == 5) last_use[o.b] = t;
     }
     std::vector<uint16_t> slot_of(n_src, 0), free_slots;
@@ -151,6 +153,7 @@ int air_assign_slots(const std::vector<AirOpHost>& ops, std::vector<AirOpDev>& d
         AirOpDev d{};
         d.op = o.op;
         if (air_op_takes_two_values(o.op)) { d.a = slot_of[o.a]; d.b = slot_of[o.b]; }
+        else if (air_op_takes_one_value(o.op)) { d.a = slot_of[o.a]; d.b = (uint16_t)o.b; }
         else if (o.op == 5) { d.a = (uint16_t)o.a; d.b = slot_of[o.b]; }
         else { d.a = (uint16_t)o.a; d.b = (uint16_t)o.b; }
         for (uint32_t v : dying[t]) free_slots.push_back(slot_of[v]);   // operands read before the result is written

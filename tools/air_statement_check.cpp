@@ -82,19 +82,19 @@ struct Parts {
 // use: which parts go to the decoder (x p s b m r R l L, upper case P: the auxiliary program may read the periodic columns; m: the main
 // program, for which the AIR gets its six main columns first; r / R the chain program with and without the _rec policy; l / L the
 // lookup program under the _lk policy and under the _rec policy alone; k the chain program under the _link policy; d the chain program
-// under the _div policy)
+// under the _div policy, i under the _int policy)
 void run(const char* label, const char* use, bool want_ok, const std::function<void(Parts&)>& patch) {
     Parts p;
     if (std::strchr(use, 'm')) p.with_main();
-    if (std::strchr(use, 'r') || std::strchr(use, 'R') || std::strchr(use, 'l') || std::strchr(use, 'L') || std::strchr(use, 'k') || std::strchr(use, 'd')) p.with_chain();
+    if (std::strchr(use, 'r') || std::strchr(use, 'R') || std::strchr(use, 'l') || std::strchr(use, 'L') || std::strchr(use, 'k') || std::strchr(use, 'd') || std::strchr(use, 'i')) p.with_chain();
     patch(p);
     auto has = [&](char c) { return std::strchr(use, c) != nullptr; };
     using sp::AirMainLevel;   // the highest level a use-letter implies wins
-    const AirMainLevel level = has('d') ? AirMainLevel::Div : has('k') ? AirMainLevel::Link : has('l') ? AirMainLevel::Lk : has('r') || has('L') ? AirMainLevel::Rec : AirMainLevel::Main;
+    const AirMainLevel level = has('i') ? AirMainLevel::Int : has('d') ? AirMainLevel::Div : has('k') ? AirMainLevel::Link : has('l') ? AirMainLevel::Lk : has('r') || has('L') ? AirMainLevel::Rec : AirMainLevel::Main;
     sp::AirStatement st;
     const std::string refused = sp::air_statement_from_c(&p.d, has('x') ? &p.aux : nullptr, has('p') ? &p.per : nullptr, has('s') ? &p.sd : nullptr,
                                                          has('b') ? &p.bv : nullptr, has('P'), 16, st,
-                                                         has('m') ? &p.mp : has('r') || has('R') || has('k') || has('d') ? &p.rp : has('l') || has('L') ? &p.lp : nullptr,
+                                                         has('m') ? &p.mp : has('r') || has('R') || has('k') || has('d') || has('i') ? &p.rp : has('l') || has('L') ? &p.lp : nullptr,
                                                          level);
     const bool ok = refused.empty();
     if (ok != want_ok) { ++failures; std::printf("FAIL %-44s wanted %s, got %s\n", label, want_ok ? "accepted" : "refused", ok ? "accepted" : refused.c_str()); return; }
@@ -103,8 +103,8 @@ void run(const char* label, const char* use, bool want_ok, const std::function<v
     // the model on what was accepted: stride plan and zerofier, periodic columns as polynomials, boundary values under a challenge
     sp::AirStridePlan plan;
     bool fine = sp::air_stride_plan(st.air, 16, plan) && st.aux.has_value() == has('x') && st.periodic.has_value() == has('p') && st.bvals.has_value() == has('b') &&
-                (st.aux_periodic() != nullptr) == (has('P') && has('p')) && st.main.has_value() == (has('m') || has('r') || has('l') || has('k') || has('d')) &&
-                st.main_level == (has('d') ? AirMainLevel::Div : has('k') ? AirMainLevel::Link : has('l') ? AirMainLevel::Lk : has('r') ? AirMainLevel::Rec : AirMainLevel::Main) && !st.unsupported;
+                (st.aux_periodic() != nullptr) == (has('P') && has('p')) && st.main.has_value() == (has('m') || has('r') || has('l') || has('k') || has('d') || has('i')) &&
+                st.main_level == (has('i') ? AirMainLevel::Int : has('d') ? AirMainLevel::Div : has('k') ? AirMainLevel::Link : has('l') ? AirMainLevel::Lk : has('r') ? AirMainLevel::Rec : AirMainLevel::Main) && !st.unsupported;
     if (st.main && has('l') && !has('r') && st.main->cols.size() == 3) {   // what the prover's chunking reads of a COUNT column
         const auto& c = st.main->cols;
         fine = fine && c[1].kind == SP_AIR_MAIN_COUNT && c[1].key_bits == p.lcols[1].pad && c[1].num_op == 3 && c[1].den_op == 1 && c[1].reads == 1 && c[0].key_bits == 0 &&
@@ -347,6 +347,38 @@ int main() {
     run("div: DIV in a step without any policy", "pR", false, step_divides);
     run("div: a DIV that nothing reaches through the _link policy", "pk", false, with_quotient);
     run("div: a DIV that nothing reaches through the _rec policy", "pr", false, with_quotient);
+    // ---- integer ops behind chain seeds and steps (the _int policy, use 'i'): ops 8 .. 11 over earlier ops, and nowhere else
+    const auto step_is = [](sp_air_op o) { return [=](Parts& p) { p.rops[4] = o; }; };
+    const auto third_behind_int = [](uint32_t kind, uint32_t num_op, uint32_t den_op, uint32_t pad) {   // op 7 becomes x OR K, op 8 stays behind it
+        return [=](Parts& p) { p.rp.n_ops = 9; p.rops[7] = sp_air_op{10, 0, 0, 1, 0}; p.rcols[2] = sp_air_main_column{kind, num_op, den_op, pad}; };
+    };
+    run("int: a chain program without the ops", "pi", true, none);
+    run("int: LIMB in a step", "pi", true, step_is(sp_air_op{8, 0, 2, 8 + 256 * 16, 0}));
+    run("int: the widest LIMB", "pi", true, step_is(sp_air_op{8, 0, 2, 0 + 256 * 252, 0}));
+    run("int: the top bit", "pi", true, step_is(sp_air_op{8, 0, 2, 251 + 256, 0}));
+    run("int: AND, OR and XOR in a step", "pi", true, [](Parts& p) { p.rops[4] = sp_air_op{9, 0, 2, 3, 0}; p.rops[5] = sp_air_op{11, 0, 4, 1, 0}; });
+    run("int: XOR in a seed", "pi", true, [](Parts& p) { p.rp.n_ops = 9; p.rops[7] = sp_air_op{11, 0, 0, 1, 0}; p.rcols[0].den_op = 7; });
+    run("int: beside op 7", "pi", true, [](Parts& p) { p.rops[4].op = 7; p.rops[5] = sp_air_op{8, 0, 4, 31 + 256 * 40, 0}; });
+    run("int: an integer op that nothing reaches", "pi", true, [](Parts& p) { p.rp.n_ops = 9; p.rops[7] = sp_air_op{10, 0, 0, 1, 0}; });
+    run("int: LIMB with width 0", "pi", false, step_is(sp_air_op{8, 0, 2, 8, 0}));
+    run("int: LIMB with lo + width = 253", "pi", false, step_is(sp_air_op{8, 0, 2, 200 + 256 * 53, 0}));
+    run("int: LIMB whose operand is later", "pi", false, step_is(sp_air_op{8, 0, 5, 256, 0}));
+    run("int: LIMB whose operand is itself", "pi", false, step_is(sp_air_op{8, 0, 4, 256, 0}));
+    run("int: AND whose operand is itself", "pi", false, step_is(sp_air_op{9, 0, 2, 4, 0}));
+    run("int: XOR whose operand is beyond the program", "pi", false, step_is(sp_air_op{11, 0, 2, 9, 0}));
+    run("int: op 12", "pi", false, step_is(sp_air_op{12, 0, 2, 3, 0}));
+    run("int: a VALUE that is an integer op", "pi", false, third_behind_int(SP_AIR_MAIN_VALUE, 7, SP_AIR_AUX_NO_DEN, 0));
+    run("int: a VALUE behind an integer op", "pi", false, third_behind_int(SP_AIR_MAIN_VALUE, 8, SP_AIR_AUX_NO_DEN, 0));
+    run("int: a BIT behind an integer op", "pi", false, third_behind_int(SP_AIR_MAIN_BIT, 8, SP_AIR_AUX_NO_DEN, 3));
+    run("int: a COUNT whose T is behind an integer op", "pi", false, third_behind_int(SP_AIR_MAIN_COUNT, 0, 8, 16));
+    run("int: a FETCH whose V is an integer op", "pi", false, third_behind_int(SP_AIR_MAIN_FETCH, 0, 0, 16 + 256 * 7));
+    run("int: a LIMB column behind an integer op", "pi", false, third_behind_int(SP_AIR_MAIN_LIMB, 8, SP_AIR_AUX_NO_DEN, 256 * 8));
+    run("int: a WORD column whose D is behind an integer op", "pi", false, third_behind_int(SP_AIR_MAIN_WORD, 0, 8, 2 + 256 * 8));
+    run("int: a LIMB column over the input beside the group", "pi", true, [](Parts& p) { p.rcols[2] = sp_air_main_column{SP_AIR_MAIN_LIMB, 0, SP_AIR_AUX_NO_DEN, 256 * 8}; });
+    run("int: LIMB in a step through the _div policy", "pd", false, step_is(sp_air_op{8, 0, 2, 8 + 256 * 16, 0}));
+    run("int: XOR in a step through the _rec policy", "pr", false, step_is(sp_air_op{11, 0, 2, 3, 0}));
+    run("int: op 6 without periodic columns", "i", false, none);
+    run("aux: op 8 through the _int policy", "xpi", false, [](Parts& p) { p.aux_ops[2].op = 8; });
     run("aux: op 7", "x", false, [](Parts& p) { p.aux_ops[2].op = 7; });
     run("aux: op 7 through the _div policy", "xpd", false, [](Parts& p) { p.aux_ops[2].op = 7; });
     run("no main column", "", false, [](Parts& p) { p.d.main_cols = 0; p.ops[2] = sp_air_op{1, 0, 0, 0, 0}; });
