@@ -85,7 +85,8 @@ const char* sp_version(void);
  * sp_air_main_link_limits, then sp_air_prove_div, sp_air_check_trace_div, sp_air_main_trace_div and sp_air_main_check_div, then
  * sp_air_prove_fetch, sp_air_check_trace_fetch, sp_air_main_trace_fetch, sp_air_main_check_fetch and sp_air_main_fetch_limits, and last
  * sp_air_prove_word, sp_air_check_trace_word, sp_air_main_trace_word, sp_air_main_check_word and sp_air_main_word_limits, and after them
- * sp_air_prove_int, sp_air_check_trace_int, sp_air_main_trace_int, sp_air_main_check_int and sp_air_main_int_limits).  A binding compares it (and sp_air_desc_size against its own idea of the struct) when it loads the library, so
+ * sp_air_prove_int, sp_air_check_trace_int, sp_air_main_trace_int, sp_air_main_check_int and sp_air_main_int_limits, and last
+ * sp_air_prove_multi, sp_air_check_trace_multi, sp_air_main_trace_multi, sp_air_main_check_multi and sp_air_main_multi_limits).  A binding compares it (and sp_air_desc_size against its own idea of the struct) when it loads the library, so
  * a stale build fails at load time with "rebuild the library" instead of with a missing symbol or shifted fields later. */
 #define SP_ABI_VERSION 7
 int sp_abi_version(void);
@@ -881,6 +882,40 @@ int sp_air_main_check_int(const sp_air_desc* air, const sp_air_ext* ext, const s
 /* out[0] = the most lo + width of a LIMB op (252), out[1] = the bits an AND / OR / XOR operand must stay below 2^ of (251), out[2] = the
  * number of integer ops (4: ops 8 .. 11), out[3] = 0 */
 int sp_air_main_int_limits(uint32_t out[4]);
+
+/* ---- One multiplicity column for several looked-up columns: the usual shape of a lookup argument - the limbs of a range check, the
+ * bytes of a word, a dozen cells in one 16-bit table - under ONE multiplicity column.  Through the _multi entry points - and only
+ * through them: everywhere else op 12 stays a malformed op and such a pad a key_bits out of range - an SP_AIR_MAIN_COUNT column may be
+ * a joint column: bit 8 of its pad is set (pad = key_bits + 256, key_bits 1 .. 64), den_op names the table value T as before, and
+ * num_op names a list of 1 .. 16 looked-up values X_0 .. X_(L-1), made of cells of */
+#define SP_AIR_OP_ALSO 12          /* op 12 ALSO a = an earlier value op (one X_k), b = an earlier op 12 (the rest of the list) or 0xFFFF (its end) */
+#define SP_AIR_MAIN_COUNT_LIST 256 /* bit 8 of a COUNT column's pad: num_op names a list */
+#define SP_AIR_LIST_END 0xFFFF
+/* X_0 is the a of the cell num_op names, X_1 the a of the cell its b names, and so on.  The column is
+ *   z_i = sum_k #{ j in [0, n) : X_k(j) = T(i) } if no row i' < i has T(i') = T(i), else 0,
+ * and everything else is a COUNT column's rule: X_k and T are ordinary values over the inputs, earlier derived columns at shifts 0 .. 7
+ * and periodic columns; a value of some X_k that no T holds is counted nowhere; a canonical integer of any X_k(j) or T(i) at or above
+ * 2^key_bits fails the call with SP_E_INVALID_ARG and the COUNT columns' own words ("a lookup key is out of range on some row"), in
+ * their place in the order of verdicts; n < 2^32.  A cell has no value: it is never an operand of a value op, takes none of the 64
+ * live values and is never sent to the device.  Joint and plain COUNT columns count together against the 16 a program may hold.  The
+ * decoder refuses, naming the column (or the op): a pad with a bit above 8; bit 8 with a num_op that is no cell, and a cell as the
+ * num_op of a column without it; a cell whose a is no earlier value op, or whose b is neither 0xFFFF nor an earlier cell; a list of
+ * more than 16 cells; a cell as an operand, as a den_op, as a FETCH column's v_op or behind a column of any other kind; an X_k behind an
+ * op 7 or an op 8 .. 11, or one that reads a column that is not an earlier one; key_bits 0 or above 64; a joint column without a
+ * table.  A COUNT column without bit 8 is the column it was, bit for bit and launch for launch.  The device sorts the table once,
+ * searches it from every looked-up key and adds into one 64-bit counter per table position.  The _multi entry points accept everything
+ * the _int ones do; the proof is unchanged: the same table gives the same bytes.  Argument lists as the _int entry points. */
+int sp_air_prove_multi(sp_ctx* ctx, const sp_air_desc* air, const sp_air_ext* ext, const sp_air_boundary_desc* bvals, const sp_air_main_desc* main,
+                       const void* inputs, uint64_t n, const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len);
+int sp_air_check_trace_multi(sp_ctx* ctx, const sp_air_desc* air, const sp_air_ext* ext, const sp_air_boundary_desc* bvals, const sp_air_main_desc* main,
+                             const void* inputs, uint64_t n, const sp_proof_options* opt, const uint8_t* rap, sp_air_violation* out, uint32_t cap,
+                             uint32_t* n_out);
+int sp_air_main_trace_multi(sp_ctx* ctx, const sp_air_desc* air, const sp_air_ext* ext, const sp_air_main_desc* main, const void* inputs, uint64_t n,
+                            uint8_t* rows_out);
+int sp_air_main_check_multi(const sp_air_desc* air, const sp_air_ext* ext, const sp_air_main_desc* main, uint64_t n);
+/* out[0] = the most looked-up values of a joint COUNT column (16), out[1] = the most key bits (64), out[2] = the most COUNT columns of
+ * one main program, joint and plain together (16), out[3] = 0 */
+int sp_air_main_multi_limits(uint32_t out[4]);
 
 /* verify::<Stark252PrimeField, A> (reference src/starks/verifier.rs:559-657) on the host CPU: 1 accept, 0 reject (also for
  * malformed proofs or descriptors). */

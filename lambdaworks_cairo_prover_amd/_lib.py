@@ -50,7 +50,8 @@ class CairoPublicInputsC(ctypes.Structure):
 
 # The entry points added most recently, probed at load time beside the version number (api.py binds symbols lazily: a stale build would
 # otherwise fail with AttributeError in the middle of a run instead of with "rebuild the library" here).
-NEWEST_SYMBOLS = ("sp_air_prove_int", "sp_air_check_trace_int", "sp_air_main_trace_int", "sp_air_main_check_int", "sp_air_main_int_limits",
+NEWEST_SYMBOLS = ("sp_air_prove_multi", "sp_air_check_trace_multi", "sp_air_main_trace_multi", "sp_air_main_check_multi", "sp_air_main_multi_limits",
+                  "sp_air_prove_int", "sp_air_check_trace_int", "sp_air_main_trace_int", "sp_air_main_check_int", "sp_air_main_int_limits",
                   "sp_air_prove_word", "sp_air_check_trace_word", "sp_air_main_trace_word", "sp_air_main_check_word", "sp_air_main_word_limits",
                   "sp_air_prove_fetch", "sp_air_check_trace_fetch", "sp_air_main_trace_fetch", "sp_air_main_check_fetch", "sp_air_main_fetch_limits",
                   "sp_air_prove_div", "sp_air_check_trace_div", "sp_air_main_trace_div", "sp_air_main_check_div",

@@ -57,12 +57,22 @@ OP_INT_LIMB, OP_INT_AND, OP_INT_OR, OP_INT_XOR = 8, 9, 10, 11   # LIMB: a = a va
 _INT_OPS = (OP_INT_LIMB, OP_INT_AND, OP_INT_OR, OP_INT_XOR)
 INT_OP_BITS = 251                                # both operands of AND, OR and XOR stay below 2^251 < p
 _TWO_VALUES = (OP_ADD, OP_SUB, OP_MUL, OP_DIV, OP_INT_AND, OP_INT_OR, OP_INT_XOR)   # the ops whose a and b name earlier values
+# A list cell of a joint COUNT column (sp_air_prove_multi): a = one looked-up value, b = the cell of the rest of the list or LIST_END.  It has no value.
+OP_ALSO, LIST_END, MAIN_COUNT_LIST, MAIN_COUNT_MAX_LIST = 12, 0xFFFF, 256, 16
 _ONE_VALUE = (OP_INT_LIMB,)                      # the ops whose a names an earlier value and whose b is an immediate
 
 
 def _value_operands(op, a, b):
-    """The earlier values an op reads: what every operand walk follows."""
+    """The earlier values an op reads: what every operand walk follows.  A list cell (op 12) is a leaf: it holds a list and no value."""
     return (a, b) if op in _TWO_VALUES else (a,) if op in _ONE_VALUE else ()
+
+
+def _marked_operands(op, a, b):
+    """What the decoder's marks of an op (reads, quotients, integers) are taken over: its value operands, and for a list cell - which
+    stands for its whole list there - its looked-up value and the cell of the rest."""
+    if op == OP_ALSO:
+        return (a,) if b == LIST_END else (a, b)
+    return _value_operands(op, a, b)
 MAX_OFFSETS, MAX_TRANSITIONS = 8, 64
 AUX_TRACE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint8))
 
@@ -287,7 +297,7 @@ class MainLevel(enum.IntEnum):
     the levels below it know, and the entry points carry its suffix (sp_air_prove_rec, sp_air_main_check_rec, ...; sp_air_main_trace and
     sp_air_main_check at MAIN).  MainLevel.WORD, the level above FETCH, is the one member of MainLevelWord below: it orders, compares and
     carries its suffix like a member, and iterating MainLevel goes on giving the six levels MAIN .. FETCH.  MainLevel.INT, above WORD, is
-    the one member of MainLevelInt in the same way."""
+    the one member of MainLevelInt in the same way, and MainLevel.MULTI, above INT, the one member of MainLevelMulti."""
     MAIN, REC, LK, LINK, DIV, FETCH = range(6)
 
     @property
@@ -318,6 +328,17 @@ class MainLevelInt(enum.IntEnum):
 MainLevel.INT = MainLevelInt.INT
 
 
+class MainLevelMulti(enum.IntEnum):
+    """sp::AirMainLevel::Multi, the _multi entry points (a COUNT column over a list of looked-up values, op 12), reached as
+    MainLevel.MULTI: an enumeration of its own for the reason MainLevelWord is one; tests/test_air_multi.py holds it against the library."""
+    MULTI = 8
+
+    suffix = MainLevel.suffix
+
+
+MainLevel.MULTI = MainLevelMulti.MULTI
+
+
 # What in a main program demands each level above MAIN: a test of a column's (kind, pad) and a test of an op code (None: no such thing).
 _MAIN_DEMANDS = {
     MainLevel.REC: (lambda kind, pad: kind == MAIN_CHAIN, lambda op: op == OP_PERIODIC),      # a chain column, a read of a periodic column
@@ -327,6 +348,7 @@ _MAIN_DEMANDS = {
     MainLevel.FETCH: (lambda kind, pad: kind == MAIN_FETCH, None),                            # a looked-up value
     MainLevel.WORD: (lambda kind, pad: kind in (MAIN_LIMB, MAIN_WORD), None),                 # a limb or a bitwise word
     MainLevel.INT: (None, lambda op: op in _INT_OPS),                                         # an integer op behind a chain group
+    MainLevel.MULTI: (lambda kind, pad: kind == MAIN_COUNT and pad & MAIN_COUNT_LIST != 0, lambda op: op == OP_ALSO),   # a joint multiplicity, a list cell
 }
 
 
@@ -368,6 +390,7 @@ def needs_div(desc): return MainLevel.DIV in main_features(desc)
 def needs_fetch(desc): return MainLevel.FETCH in main_features(desc)
 def needs_word(desc): return MainLevel.WORD in main_features(desc)
 def needs_int(desc): return MainLevel.INT in main_features(desc)
+def needs_multi(desc): return MainLevel.MULTI in main_features(desc)
 
 
 def route(desc, call):
@@ -790,7 +813,13 @@ class MainProgram(_Program):
                                        group evaluates fails the call (SP_E_INVALID_ARG; ValueError in evaluate)
         int_rotl(x, r, bits), int_rotr(x, r, bits), int_add(x, y, bits)   a rotation of a `bits`-wide word and (x + y) mod 2^bits, written
                                        with int_limb and field ops
-        Like a quotient, such a value may feed anything, but only the seed or the step of a chain group may depend on it."""
+        Like a quotient, such a value may feed anything, but only the seed or the step of a chain group may depend on it.
+
+    The usual shape of a lookup argument - many columns looked up in one table under ONE multiplicity column (sp_air_prove_multi):
+
+        multiplicity_many(xs, table, key_bits)   z_i = the number of (k, j) with xs[k](j) = table(i) on the first row of each table value,
+                                       0 on its repeats: a joint COUNT column over 1 .. 16 looked-up values, each as the x of
+                                       multiplicity(); the device sorts the table once and searches it from every looked-up key."""
 
     def __init__(self, input_cols, main_cols, periodic_cols=()):
         if not 1 <= input_cols < main_cols:
@@ -809,6 +838,7 @@ class MainProgram(_Program):
     fetches = property(lambda self: self.level >= MainLevel.FETCH)
     words = property(lambda self: self.level >= MainLevel.WORD)
     ints = property(lambda self: self.level >= MainLevel.INT)
+    multis = property(lambda self: self.level >= MainLevel.MULTI)
 
     def load(self, shift, col):
         if not 0 <= shift <= AUX_MAX_SHIFT:
@@ -956,6 +986,36 @@ class MainProgram(_Program):
         self.level = max(self.level, MainLevel.LK)
         return self._column(MAIN_COUNT, x, table, key_bits)
 
+    def multiplicity_many(self, xs, table, key_bits=64):
+        """One multiplicity column for the 1 .. 16 looked-up values xs in one table (see the class): a joint COUNT column - bit 8 of its
+        pad, its num_op the first of a list of op 12 cells, one per x - (sp_air_prove_multi); returns its index."""
+        xs = list(xs)
+        if table is None:
+            raise ValueError("main program: a multiplicity column needs a table value")
+        if not 1 <= len(xs) <= MAIN_COUNT_MAX_LIST:
+            raise ValueError(f"main program: a multiplicity column over {len(xs)} looked-up values (1 .. {MAIN_COUNT_MAX_LIST})")
+        if not 1 <= key_bits <= MAIN_COUNT_MAX_KEY_BITS:
+            raise ValueError(f"main program: key_bits {key_bits} outside 1 .. {MAIN_COUNT_MAX_KEY_BITS}")
+        if sum(1 for c in self.cols if c[0] == MAIN_COUNT) >= MAIN_COUNT_MAX_COLS:
+            raise ValueError(f"main program: more than {MAIN_COUNT_MAX_COLS} multiplicity columns")
+        xs = [self._lift(x) for x in xs]
+        if any(x.b is not self for x in xs):
+            raise ValueError("main program: the looked-up values of a multiplicity column must be values of this program")
+        table = self._lift(table)
+        cell = LIST_END
+        for x in reversed(xs):      # X_0 is the a of the cell the column names, X_1 that of its b, ...
+            cell = self._emit(OP_ALSO, x.i, cell).i
+        self.level = max(self.level, MainLevel.MULTI)
+        return self._column(MAIN_COUNT, Value(self, cell), table, key_bits + MAIN_COUNT_LIST)
+
+    def list_of(self, cell):
+        """The ops X_0, X_1, .. of the list that starts at the op 12 `cell`."""
+        xs = []
+        while cell != LIST_END:
+            _, a, cell = self.ops[cell]
+            xs.append(a)
+        return xs
+
     def fetch(self, x, table_key, table_value, key_bits=64):
         """The value of the table row whose key is x (see the class): a FETCH column; returns it as a Value."""
         return self.fetch_many(x, table_key, [table_value], key_bits)[0]
@@ -1023,21 +1083,21 @@ class MainProgram(_Program):
             if op == OP_LOAD:
                 reads.append(max(0, b - self.input_cols + 1) if a or not shifted_only else 0)
             else:
-                reads.append(max((reads[u] for u in _value_operands(op, a, b)), default=0))
+                reads.append(max((reads[u] for u in _marked_operands(op, a, b)), default=0))
         return reads
 
     def _quotients(self):
         """Per op: whether its value depends on a quotient (op 7) - the decoder's mark of the same name."""
         quot = []
         for op, a, b in self.ops:
-            quot.append(op == OP_DIV or any(quot[u] for u in _value_operands(op, a, b)))
+            quot.append(op == OP_DIV or any(quot[u] for u in _marked_operands(op, a, b)))
         return quot
 
     def _integers(self):
         """Per op: whether its value depends on an integer op 8 .. 11 - the decoder's other chain-only mark."""
         ints = []
         for op, a, b in self.ops:
-            ints.append(op in _INT_OPS or any(ints[u] for u in _value_operands(op, a, b)))
+            ints.append(op in _INT_OPS or any(ints[u] for u in _marked_operands(op, a, b)))
         return ints
 
     def check(self, n=None, level=None):
@@ -1045,11 +1105,12 @@ class MainProgram(_Program):
         broken.  n: the trace length a chain group's block length is held against (None: not yet known).  level: the MainLevel whose
         decoder is mirrored (None: self.level, where the program would be routed after what was declared).  Below LK kind 6 is an
         unknown kind; below LINK the bits of a CHAIN column's pad at and above 16 belong to j; below DIV op 7 is a malformed op; below
-        FETCH kind 7 is an unknown kind; below WORD kinds 8 and 9 are; below INT ops 8 .. 11 are malformed ops.  The _main entry points' refusal of chain columns and op 6 was
+        FETCH kind 7 is an unknown kind; below WORD kinds 8 and 9 are; below INT ops 8 .. 11 are malformed ops; below MULTI op 12 is one and
+        a COUNT column's pad with bit 8 a key_bits out of range.  The _main entry points' refusal of chain columns and op 6 was
         never modelled here, and is not: MAIN is judged as REC."""
         level = self.level if level is None else level
         lookups, links, divs, fetches = (level >= at for at in (MainLevel.LK, MainLevel.LINK, MainLevel.DIV, MainLevel.FETCH))
-        words, ints = level >= MainLevel.WORD, level >= MainLevel.INT
+        words, ints, multis = level >= MainLevel.WORD, level >= MainLevel.INT, level >= MainLevel.MULTI
         pos = (lambda pad: (pad >> 8) & 255) if links else (lambda pad: pad >> 8)
         n_count = n_fetch = 0
         if self._open is not None:
@@ -1062,6 +1123,17 @@ class MainProgram(_Program):
             ok = ((op == OP_LOAD and 0 <= a <= AUX_MAX_SHIFT and 0 <= b < self.main_cols) or (op == OP_CONST and 0 <= a < len(self.consts)) or
                   (op in (OP_ADD, OP_SUB, OP_MUL) and 0 <= a < t and 0 <= b < t) or (op == OP_PERIODIC and 0 <= a <= AUX_MAX_SHIFT) or
                   (divs and op == OP_DIV and 0 <= a < t and 0 <= b < t))
+            if multis:      # (a list cell, and what takes one for a value, by name)
+                def cell(u, t=t):
+                    return 0 <= u < t and self.ops[u][0] == OP_ALSO
+                if op == OP_ALSO:
+                    if not 0 <= a < t or self.ops[a][0] in (OP_OUT, OP_ALSO):
+                        raise ValueError(f"main program: op {t} is a list cell (op 12) whose a = {a} is no earlier value op (a cell names one looked-up value, and no cell)")
+                    if b != LIST_END and not cell(b):
+                        raise ValueError(f"main program: op {t} is a list cell (op 12) whose b = {b} is neither 0xFFFF nor an earlier cell (b names the rest of the list)")
+                    ok = True
+                elif any(cell(u) for u in _value_operands(op, a, b)) or (op == OP_OUT and cell(b)):
+                    raise ValueError(f"main program: op {t} takes a list cell (op 12) for an operand, and a cell has no value")
             if ints and op in _INT_OPS:
                 earlier = [0 <= u < t and self.ops[u][0] != OP_OUT for u in _value_operands(op, a, b)]
                 if not all(earlier):
@@ -1089,11 +1161,20 @@ class MainProgram(_Program):
                 raise ValueError(f"main program: derived column {k} {refused}")
             if any(integers[u] for u in operands):
                 raise ValueError(f"main program: derived column {k} {refused_int}")
+        def is_cell(t):
+            return 0 <= t < len(self.ops) and self.ops[t][0] == OP_ALSO
+        list_len = []       # of an op 12: the cells of its list, itself included
+        for op, a, b in self.ops:
+            list_len.append(1 + (list_len[b] if b != LIST_END else 0) if op == OP_ALSO else 0)
         g0 = g_end = 0      # the chain group that column k belongs to is [g0, g_end), when k < g_end
         for k, (kind, num_op, den_op, pad) in enumerate(self.cols):
             den = den_op != AUX_NO_DEN
             if not MAIN_VALUE <= kind <= (MAIN_WORD if words else MAIN_FETCH if fetches else MAIN_COUNT if lookups else MAIN_CHAIN):
                 raise ValueError(f"main program: derived column {k} has an unknown kind")
+            joint = multis and kind == MAIN_COUNT and pad & MAIN_COUNT_LIST != 0
+            if multis and ((den and is_cell(den_op)) or (not joint and is_cell(num_op)) or (kind == MAIN_FETCH and is_cell((pad >> 8) & 65535))):
+                raise ValueError(f"main program: derived column {k} names a list cell (op 12), which only the num_op of a COUNT column with bit 8 of its pad may "
+                                 "(a cell has no value)")
             if kind in (MAIN_LIMB, MAIN_WORD):
                 limb, low, high = kind == MAIN_LIMB, pad & 255, (pad >> 8) & 255      # LIMB: lo, width; WORD: fn, bits
                 who = f"main program: derived column {k} is a {'LIMB' if limb else 'WORD'} column"
@@ -1141,10 +1222,19 @@ class MainProgram(_Program):
             if kind == MAIN_COUNT:
                 if not den:
                     raise ValueError(f"main program: derived column {k} is a COUNT column without a table (den_op names the table value)")
-                if not 1 <= pad <= MAIN_COUNT_MAX_KEY_BITS:
-                    raise ValueError(f"main program: derived column {k} is a COUNT column with key_bits = {pad} (1 .. {MAIN_COUNT_MAX_KEY_BITS})")
+                if multis and pad >> 9:
+                    raise ValueError(f"main program: derived column {k} is a COUNT column whose pad has a bit above 8 (pad = key_bits, and + 256 when num_op names "
+                                     "a list of looked-up values)")
+                key_bits = pad & 255 if joint else pad
+                if not 1 <= key_bits <= MAIN_COUNT_MAX_KEY_BITS:
+                    raise ValueError(f"main program: derived column {k} is a COUNT column with key_bits = {key_bits} (1 .. {MAIN_COUNT_MAX_KEY_BITS})")
                 if not (0 <= num_op < len(self.ops) and 0 <= den_op < len(self.ops)):
                     raise ValueError(f"main program: derived column {k} names an op beyond the program")
+                if joint and not is_cell(num_op):
+                    raise ValueError(f"main program: derived column {k} is a COUNT column with bit 8 of its pad whose num_op = {num_op} is no list cell (op 12 names "
+                                     "the looked-up values)")
+                if joint and list_len[num_op] > MAIN_COUNT_MAX_LIST:
+                    raise ValueError(f"main program: derived column {k} is a COUNT column with a list of more than {MAIN_COUNT_MAX_LIST} looked-up values")
                 chain_only(k, num_op, den_op)
                 r = max(reads[num_op], reads[den_op])
                 if r > k:
@@ -1283,7 +1373,12 @@ class MainProgram(_Program):
                             state = run([self.cols[k + j][1] for j in range(w)], rows + t, first, state)
                 continue
             if kind == MAIN_COUNT:
-                xs, ts = [int(v) for v in need(num_op)], [int(v) for v in need(den_op)]
+                if pad & MAIN_COUNT_LIST:   # a joint column: every looked-up value of the list, one after the other
+                    pad &= 255
+                    xs = [int(v) for x_op in self.list_of(num_op) for v in need(x_op)]
+                else:
+                    xs = [int(v) for v in need(num_op)]
+                ts = [int(v) for v in need(den_op)]
                 if any(v >> pad for v in xs) or any(v >> pad for v in ts):
                     raise ValueError("main program: a lookup key is out of range on some row")
                 counts, seen = {}, set()
@@ -2440,6 +2535,86 @@ def limb_range_check_trace(inputs, limb_bits, count):
             counts[j][v] = counts[j].get(v, 0) + 1
     # (T(i) = i mod 2^limb_bits: the first row that holds a table value is the value itself)
     return [[int(inputs[i][0]) % P] + limbs[i] + [counts[j].get(i, 0) if i <= mask else 0 for j in range(count)] for i in range(n)]
+
+
+def limb_range_check_joint(n, limb_bits, count=2):
+    """limb_range_check under ONE multiplicity column (sp_air_prove_multi) - another statement of the same range check: one input x
+    (column 0), its `count` limbs (columns 1 .. count, one limbs() group) and m = multiplicity_many(limbs, T, limb_bits) (column count +
+    1), T periodic column 0, which holds all 2^limb_bits values; 2^limb_bits <= n / 2, so the table entry on the last row is a repeat and
+    m is 0 there.  count + 2 main columns where limb_range_check has 1 + 2 count, and the table is sorted once.
+
+    A transition constraint has degree at most 3, so the LogUp sum over count + 1 fractions takes helper columns: auxiliary column p <
+    ceil(count / 2) is u_p, the running sum of 1 / (gamma - a) + 1 / (gamma - b) over limbs a = 2 p and b = 2 p + 1 (of 1 / (gamma - a)
+    alone for the last limb of an odd count): u_p(0) = 0 and (u_p' - u_p) (gamma - a) (gamma - b) = (gamma - a) + (gamma - b), degree 3.
+    The last auxiliary column is v, the running sum of m / (gamma - T) - sum_k 1 / (gamma - limb_k), which the device builds from the
+    one fraction: v(0) = 0 and ((v' - v) + sum_p (u_p' - u_p)) (gamma - T) = m, degree 2.  Both leave the last row out (the u_p do not
+    close), so that row is a public padding row: x(n - 1) = 0 and limb_k(n - 1) = 0 are boundary constraints, and v(n - 1) = count /
+    gamma (boundary_from) is the term of the row the constraints skip, since the whole sum is zero.  The recomposition constraint
+    x = sum_j 2^(j limb_bits) limb_j holds on every row, as in limb_range_check.  ceil(count / 2) + 1 auxiliary columns against count."""
+    if not (1 <= limb_bits <= MAIN_COUNT_MAX_KEY_BITS and 1 <= count <= MAIN_COUNT_MAX_LIST and limb_bits * count <= MAIN_WORD_MAX_BITS):
+        raise ValueError(f"limb_range_check_joint: {count} limbs of {limb_bits} bits (at most {MAIN_COUNT_MAX_LIST} limbs, {MAIN_WORD_MAX_BITS} bits in all)")
+    if (2 << limb_bits) > n:
+        raise ValueError(f"limb_range_check_joint: {1 << limb_bits} table entries on {n} rows (at most n / 2: the last row's entry must be a repeat)")
+    main_cols, pairs = count + 2, (count + 1) // 2
+    b = AirBuilder(main_cols, [0, 1], 2, aux_cols=pairs + 1, n_rap=1, aux_kind=AUX_PROGRAM, periodic=[list(range(1 << limb_bits))], main_inputs=1)
+    m = b.main
+    limbs = m.limbs(m.load(0, 0), limb_bits, count)
+    mult = m.multiplicity_many([m.load(0, c) for c in limbs], m.periodic(0, 0), limb_bits)
+    total = None
+    for j, c in enumerate(limbs):
+        term = b.load(0, c) * (1 << (j * limb_bits))
+        total = term if total is None else total + term
+    b.constraint(total - b.load(0, 0), degree=1, exemptions=0)
+    gamma, g = b.rap(0), b.aux.rap(0)
+    steps = None        # sum_p (u_p' - u_p)
+    for p in range(pairs):
+        u_col, members = main_cols + p, limbs[2 * p:2 * p + 2]
+        ds = [gamma - b.load(0, c) for c in members]
+        step = b.load(1, u_col) - b.load(0, u_col)
+        if len(ds) == 2:
+            b.constraint(step * ds[0] * ds[1] - ds[0] - ds[1], degree=3, exemptions=1)
+        else:
+            b.constraint(step * ds[0] - 1, degree=2, exemptions=1)
+        b.boundary(u_col, 0, 0)
+        steps = step if steps is None else steps + step
+        xs = [g - b.aux.load(0, c) for c in members]
+        if len(xs) == 2:
+            b.aux.running_sum(xs[0] + xs[1], xs[0] * xs[1])
+        else:
+            b.aux.running_sum(1, xs[0])
+    v_col = main_cols + pairs
+    b.constraint((b.load(1, v_col) - b.load(0, v_col) + steps) * (gamma - b.periodic(0, 0)) - b.load(0, mult), degree=2, exemptions=1)
+    b.boundary(v_col, 0, 0)
+    # v as one fraction: N / D with D = (g - T) prod_k (g - limb_k), N = m prod_k (g - limb_k) - (g - T) sum_k prod_(j != k) (g - limb_j)
+    xs, xt = [g - b.aux.load(0, c) for c in limbs], g - b.aux.table(0, 0)
+    prod, others = xs[0], b.aux.const(1)     # over the limbs so far: their product, and the sum over k of the products without k
+    for x in xs[1:]:
+        others, prod = others * x + prod, prod * x
+    b.aux.running_sum(b.aux.load(0, mult) * prod - xt * others, xt * prod)
+    b.boundary(0, n - 1, 0)
+    for c in limbs:
+        b.boundary(c, n - 1, 0)
+    b.boundary_from(v_col, n - 1, b.public.const(count), b.public.rap(0))
+    return b
+
+
+def limb_range_check_joint_inputs(n, limb_bits, count, rng):
+    """(n, 1) Python ints below 2^(limb_bits count) from rng.randrange, the last row the public padding row x = 0: the input column of
+    limb_range_check_joint."""
+    return [[rng.randrange(1 << (limb_bits * count))] for _ in range(n - 1)] + [[0]]
+
+
+def limb_range_check_joint_trace(inputs, limb_bits, count):
+    """The whole main table of limb_range_check_joint as (n, count + 2) Python ints, from its input rows: shifts, masks and one count
+    over all limbs of all rows."""
+    n, mask = len(inputs), (1 << limb_bits) - 1
+    limbs = [[(int(x) % P >> (j * limb_bits)) & mask for j in range(count)] for (x,) in inputs]
+    counts = {}
+    for row in limbs:
+        for v in row:
+            counts[v] = counts.get(v, 0) + 1
+    # (T(i) = i mod 2^limb_bits: the first row that holds a table value is the value itself)
+    return [[int(inputs[i][0]) % P] + limbs[i] + [counts.get(i, 0) if i <= mask else 0] for i in range(n)]
 
 
 def word_ops(n, bits):

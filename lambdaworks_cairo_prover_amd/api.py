@@ -607,6 +607,14 @@ def air_main_int_limits():
     return {"limb_end": int(out[0]), "bits": int(out[1]), "ops": int(out[2])}
 
 
+def air_main_multi_limits():
+    """sp_air_main_multi_limits: {"list": the most looked-up values of a joint COUNT column (b.main.multiplicity_many), "key_bits": its most
+    key bits, "columns": the most COUNT columns of one main program, joint and plain together}."""
+    out = (ctypes.c_uint32 * 4)()
+    check(_lib.load().sp_air_main_multi_limits(out))
+    return {"list": int(out[0]), "key_bits": int(out[1]), "columns": int(out[2])}
+
+
 def air_main_fetch_limits():
     """sp_air_main_fetch_limits: {"key_bits": the most key bits of a FETCH column, "group": the most FETCH columns that share one sort and
     one search, "columns": the most FETCH columns of one main program}."""

@@ -15,8 +15,8 @@ fe air_root_of_unity(int order) {   // the field's 2^192-th root, squared down
 }
 
 size_t air_program_first_bad_op(const std::vector<AirOpHost>& ops, uint32_t load_a_end, uint32_t load_b_end, size_t n_values, uint32_t n_out,
-                                uint32_t n_periodic, bool div, bool ints) {
-    auto value = [&](uint32_t i, size_t t) { return i < t && ops[i].op != 5; };   // an earlier op that produces a value
+                                uint32_t n_periodic, bool div, bool ints, bool lists) {
+    auto value = [&](uint32_t i, size_t t) { return i < t && ops[i].op != 5 && ops[i].op != AIR_OP_ALSO; };   // an earlier op that produces a value
     for (size_t t = 0; t < ops.size(); ++t) {
         const AirOpHost& o = ops[t];
         bool ok;
@@ -29,6 +29,7 @@ size_t air_program_first_bad_op(const std::vector<AirOpHost>& ops, uint32_t load
             case 7: ok = div && value(o.a, t) && value(o.b, t); break;
             case 8: ok = ints && value(o.a, t) && (o.b >> 8) >= 1 && (o.b & 255u) + (o.b >> 8) <= AIR_MAIN_LIMB_MAX_END; break;
             case 9: case 10: case 11: ok = ints && value(o.a, t) && value(o.b, t); break;
+            case 12: ok = lists && value(o.a, t) && (o.b == AIR_LIST_END || (o.b < t && ops[o.b].op == AIR_OP_ALSO)); break;
             default: ok = false;
         }
         if (!ok) return t;
@@ -166,10 +167,13 @@ std::string validate_aux_program(const AirAuxHost& aux, uint32_t main_cols, uint
 // below 2^16, fn 0 .. 2, bits 1 .. 251 -, both over earlier columns and behind no op 7; without word kinds 8 and 9 are unknown kinds.
 // ints (the _int entry points, with word): ops 8 LIMB and 9 .. 11 AND / OR / XOR over earlier ops, behind the seeds and steps of CHAIN
 // columns only, as op 7; a column of any other kind that depends on one is refused, and without ints they are malformed ops.
+// lists (the _multi entry points, with ints): a COUNT column whose pad carries bit 8 (pad = key_bits + 256) counts a list of 1 .. 16
+// looked-up values, the op 12 cells from its num_op on, all over earlier columns and behind no op 7 .. 11; a cell is nothing else of
+// any column and no operand, and without lists op 12 is a malformed op and such a pad a key_bits out of range.
 std::string main_from_c(const AirDescHost& air, const sp_air_main_desc* m, uint64_t n, uint32_t n_periodic, AirMainLevel level, AirMainHost& out) {
     const bool rec = air_main_allows_chains(level), lk = air_main_allows_counts(level), link = air_main_allows_runs(level);
     const bool div = air_main_allows_quotients(level), fetch = air_main_allows_fetches(level), word = air_main_allows_words(level);
-    const bool ints = air_main_allows_int_ops(level);
+    const bool ints = air_main_allows_int_ops(level), lists = air_main_allows_lists(level);
     if (m->size != sizeof(sp_air_main_desc)) return "main program: sp_air_main_desc.size is not sizeof(sp_air_main_desc)";
     if (!m->ops || !m->consts || !m->cols) return "main program: null ops, consts or cols";
     if (m->input_cols == 0 || m->n_cols == 0 || (uint64_t)m->input_cols + m->n_cols != air.main_cols)
@@ -185,7 +189,18 @@ std::string main_from_c(const AirDescHost& air, const sp_air_main_desc* m, uint6
                 return "main program: op " + std::to_string(t) + " reads periodic column " + std::to_string(ops[t].b) + ", and the statement has " +
                        std::to_string(n_periodic) + " (ext->periodic)";
     // (no OUT target; a periodic column only through the _rec entry points: elsewhere ops 0 .. 4 are all that is left)
-    const size_t bad = air_program_first_bad_op(ops, AIR_LIMIT_AUX_SHIFT + 1, air.main_cols, m->n_consts, 0, rec ? n_periodic : 0u, div, ints);
+    const size_t bad = air_program_first_bad_op(ops, AIR_LIMIT_AUX_SHIFT + 1, air.main_cols, m->n_consts, 0, rec ? n_periodic : 0u, div, ints, lists);
+    if (bad < n_ops && lists) {   // (what is wrong with a list cell, or with an op that takes one for a value, by name)
+        const AirOpHost& o = ops[bad];
+        const std::string who = "main program: op " + std::to_string(bad);
+        const auto cell = [&](uint32_t i) { return i < bad && ops[i].op == AIR_OP_ALSO; };
+        if (o.op == AIR_OP_ALSO && (o.a >= bad || ops[o.a].op == 5 || ops[o.a].op == AIR_OP_ALSO))
+            return who + " is a list cell (op 12) whose a = " + std::to_string(o.a) + " is no earlier value op (a cell names one looked-up value, and no cell)";
+        if (o.op == AIR_OP_ALSO)
+            return who + " is a list cell (op 12) whose b = " + std::to_string(o.b) + " is neither 0xFFFF nor an earlier cell (b names the rest of the list)";
+        if ((air_op_takes_two_values(o.op) && (cell(o.a) || cell(o.b))) || (air_op_takes_one_value(o.op) && cell(o.a)) || (o.op == 5 && cell(o.b)))
+            return who + " takes a list cell (op 12) for an operand, and a cell has no value";
+    }
     if (bad < n_ops && ints && air_op_is_integer(ops[bad].op)) {   // (what is wrong with an integer op, by name)
         const AirOpHost& o = ops[bad];
         const std::string who = "main program: op " + std::to_string(bad);
@@ -211,6 +226,7 @@ std::string main_from_c(const AirDescHost& air, const sp_air_main_desc* m, uint6
     constexpr uint8_t CHAIN_QUOT = 1, CHAIN_INT = 2;
     std::vector<uint32_t> reads(n_ops, 0), shifted(n_ops, 0);
     std::vector<uint8_t> chain_only(n_ops, 0);
+    std::vector<uint32_t> list_len(n_ops, 0);   // of an op 12: the cells of its list, itself included (capped one above the limit)
     const auto chain_only_refused = [](const std::string& who, uint8_t marks) {
         if (marks & CHAIN_QUOT)
             return who + " depends on a quotient (op 7), which only the seed or the step of a CHAIN column may: a row-local quotient is a VALUE column's N / D";
@@ -225,8 +241,18 @@ std::string main_from_c(const AirDescHost& air, const sp_air_main_desc* m, uint6
         } else if (air_op_takes_one_value(o.op)) {   // (b is lo + 256 width, no value)
             reads[t] = reads[o.a]; shifted[t] = shifted[o.a];
             chain_only[t] = CHAIN_INT | chain_only[o.a];
+        } else if (o.op == AIR_OP_ALSO) {   // a cell stands for its whole list: what any X of it reads, and how many there are
+            const bool more = o.b != AIR_LIST_END;
+            reads[t] = std::max(reads[o.a], more ? reads[o.b] : 0u); shifted[t] = std::max(shifted[o.a], more ? shifted[o.b] : 0u);
+            chain_only[t] = chain_only[o.a] | (more ? chain_only[o.b] : 0);
+            list_len[t] = std::min<uint32_t>(1u + (more ? list_len[o.b] : 0u), AIR_MAIN_COUNT_MAX_LIST + 1);
         }
     }
+    // (a cell is the num_op of a joint COUNT column and nothing else of any column)
+    const auto is_cell = [&](uint32_t t) { return t < n_ops && ops[t].op == AIR_OP_ALSO; };
+    const auto cell_refused = [](const std::string& who) {
+        return who + " names a list cell (op 12), which only the num_op of a COUNT column with bit 8 of its pad may (a cell has no value)";
+    };
     std::vector<AirMainColumnHost> cols;
     cols.reserve(m->n_cols);
     uint32_t g0 = 0, g_end = 0;   // the chain group that column k belongs to is [g0, g_end), when k < g_end
@@ -237,6 +263,10 @@ std::string main_from_c(const AirDescHost& air, const sp_air_main_desc* m, uint6
         const bool den = c.den_op != SP_AIR_AUX_NO_DEN;
         if (c.kind > (word ? SP_AIR_MAIN_WORD : fetch ? SP_AIR_MAIN_FETCH : lk ? SP_AIR_MAIN_COUNT : rec ? SP_AIR_MAIN_CHAIN : SP_AIR_MAIN_PRODUCT))
             return who + " has an unknown kind";
+        const bool joint = lists && c.kind == SP_AIR_MAIN_COUNT && (c.pad & AIR_MAIN_COUNT_LIST_BIT);
+        if (lists && ((den && is_cell(c.den_op)) || (!joint && is_cell(c.num_op)) ||
+                      (c.kind == SP_AIR_MAIN_FETCH && is_cell((c.pad >> 8) & 65535u))))
+            return cell_refused(who);
         if (c.kind == SP_AIR_MAIN_LIMB || c.kind == SP_AIR_MAIN_WORD) {   // (row-local, as a BIT column: the rules of a VALUE column's operands)
             const bool limb = c.kind == SP_AIR_MAIN_LIMB;
             const uint32_t low = c.pad & 255u, high = (c.pad >> 8) & 255u;   // LIMB: lo, width; WORD: fn, bits
@@ -272,13 +302,19 @@ std::string main_from_c(const AirDescHost& air, const sp_air_main_desc* m, uint6
         }
         if (c.kind == SP_AIR_MAIN_COUNT) {
             if (!den) return who + " is a COUNT column without a table (den_op names the table value)";
-            if (c.pad == 0 || c.pad > AIR_MAIN_COUNT_MAX_KEY_BITS) return who + " is a COUNT column with key_bits = " + std::to_string(c.pad) + " (1 .. 64)";
+            if (lists && (c.pad >> 9)) return who + " is a COUNT column whose pad has a bit above 8 (pad = key_bits, and + 256 when num_op names a list of looked-up values)";
+            const uint32_t key_bits = joint ? c.pad & 255u : c.pad;
+            if (key_bits == 0 || key_bits > AIR_MAIN_COUNT_MAX_KEY_BITS) return who + " is a COUNT column with key_bits = " + std::to_string(key_bits) + " (1 .. 64)";
             if (c.num_op >= n_ops || c.den_op >= n_ops) return who + " names an op beyond the program";
+            if (joint && !is_cell(c.num_op))
+                return who + " is a COUNT column with bit 8 of its pad whose num_op = " + std::to_string(c.num_op) + " is no list cell (op 12 names the looked-up values)";
+            if (joint && list_len[c.num_op] > AIR_MAIN_COUNT_MAX_LIST) return who + " is a COUNT column with a list of more than 16 looked-up values";
             if (const uint8_t marks = chain_only[c.num_op] | chain_only[c.den_op]) return chain_only_refused(who, marks);
             const uint32_t r = std::max(reads[c.num_op], reads[c.den_op]);
             if (r > k) return who + " reads derived column " + std::to_string(r - 1) + ", which is not an earlier one";
             if (++n_count > AIR_MAIN_COUNT_MAX_COLS) return who + " is the program's COUNT column number " + std::to_string(n_count) + " (at most 16)";
-            cols.push_back(AirMainColumnHost{c.kind, c.num_op, c.den_op, 0u, r, 0u, 0u, c.pad});
+            cols.push_back(AirMainColumnHost{c.kind, c.num_op, c.den_op, 0u, r, 0u, 0u, key_bits});
+            cols.back().list_len = joint ? list_len[c.num_op] : 0u;
             continue;
         }
         if (c.kind == SP_AIR_MAIN_CHAIN) {

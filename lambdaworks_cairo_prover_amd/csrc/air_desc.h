@@ -54,13 +54,17 @@ struct AirAuxHost {
 // state of the block before it (0: every block on its own, and always 0 through every other entry point).
 // value_op: the v_op of a FETCH column's pad (its X is num_op, its T den_op, its key_bits the low byte of the pad), 0 for the other kinds.
 // width: the width of a LIMB column (its lo is `bit`) or the bits of a WORD column (its fn is `bit`), 0 for the other kinds.
+// list_len: the L of a joint COUNT column, whose num_op names the first of L op 12 cells (X_0 the a of that cell, X_1 that of its b, ..),
+// 0 for a COUNT column of the old form and for the other kinds.
 constexpr uint32_t AIR_MAIN_CHAIN_MAX_WIDTH = 16;
 constexpr uint32_t AIR_MAIN_LINK_MAX_LOG = 62;   // (l >= 1 and l + k <= log2 n <= 63)
 constexpr uint32_t AIR_MAIN_COUNT_MAX_KEY_BITS = 64, AIR_MAIN_COUNT_MAX_COLS = 16;
 constexpr uint32_t AIR_MAIN_FETCH_MAX_KEY_BITS = 64, AIR_MAIN_FETCH_MAX_GROUP = 16, AIR_MAIN_FETCH_MAX_COLS = 64;
 constexpr uint32_t AIR_MAIN_LIMB_MAX_END = 252, AIR_MAIN_WORD_MAX_BITS = 251, AIR_MAIN_WORD_FUNCTIONS = 3;   // (lo + width <= 252; 2^251 < p)
+// A joint COUNT column (main_level Multi): bit 8 of its pad, and its num_op names a list of op 12 cells, one per looked-up value
+constexpr uint32_t AIR_MAIN_COUNT_LIST_BIT = 256, AIR_MAIN_COUNT_MAX_LIST = 16, AIR_OP_ALSO = 12, AIR_LIST_END = 0xFFFF;
 constexpr uint32_t AIR_MAIN_INT_OPS = 4;   // ops 8 .. 11; the LIMB op shares AIR_MAIN_LIMB_MAX_END, AND / OR / XOR take operands below 2^AIR_MAIN_WORD_MAX_BITS
-struct AirMainColumnHost { uint32_t kind, num_op, den_op, bit, reads, chain_log = 0, chain_pos = 0, key_bits = 0, chain_link = 0, value_op = 0, width = 0; };
+struct AirMainColumnHost { uint32_t kind, num_op, den_op, bit, reads, chain_log = 0, chain_pos = 0, key_bits = 0, chain_link = 0, value_op = 0, width = 0, list_len = 0; };
 struct AirMainHost {
     uint32_t input_cols = 0, input_location = 0;   // 0: the inputs are host memory, 1: device memory
     std::vector<AirOpHost> ops;
@@ -118,9 +122,11 @@ bool air_resolve_boundary_into(const AirBoundaryHost& bvals, const std::vector<f
 // does.  div (a main-trace program through the _div entry points, and nothing else): op 7 DIV takes two earlier ops that are not OUTs
 // too; without it op 7 is the unknown op it always was.  ints (a main-trace program through the _int entry points, and nothing else):
 // op 8 LIMB takes one such op and the immediate b = lo + 256 width with 1 <= width and lo + width <= 252, ops 9 .. 11 AND / OR / XOR two
-// such ops; without it they are the unknown ops they always were.
+// such ops; without it they are the unknown ops they always were.  lists (a main-trace program through the _multi entry points, and
+// nothing else): op 12 ALSO is a list cell - a an earlier value, b an earlier op 12 or 0xFFFF -, which has no value: no value op takes
+// one for an operand; without it op 12 is the unknown op it always was.
 size_t air_program_first_bad_op(const std::vector<AirOpHost>& ops, uint32_t load_a_end, uint32_t load_b_end, size_t n_values, uint32_t n_out,
-                                uint32_t n_periodic, bool div = false, bool ints = false);
+                                uint32_t n_periodic, bool div = false, bool ints = false, bool lists = false);
 // ADD, SUB, MUL, DIV and the integer AND, OR and XOR: the ops whose a and b name earlier values (what the slot assignment and the
 // operand walks follow).  Op 8, the integer LIMB, has one: its a names an earlier value, its b is the immediate lo + 256 width, which
 // nothing remaps and nothing takes for a slot.
@@ -140,7 +146,8 @@ fe air_root_of_unity(int order);
 //   Fetch  (the _fetch entry points) FETCH columns too, looked-up values
 //   Word   (the _word entry points) LIMB and WORD columns too, limbs and bitwise functions of canonical integers
 //   Int    (the _int entry points) ops 8 .. 11 behind the seeds and steps of CHAIN columns: integer functions inside a recurrence
-enum class AirMainLevel : uint8_t { Main, Rec, Lk, Link, Div, Fetch, Word, Int };
+//   Multi  (the _multi entry points) joint COUNT columns too: one multiplicity column for a list of looked-up values (op 12)
+enum class AirMainLevel : uint8_t { Main, Rec, Lk, Link, Div, Fetch, Word, Int, Multi };
 inline bool air_main_allows_chains(AirMainLevel l) { return l >= AirMainLevel::Rec; }   // (and op 6)
 inline bool air_main_allows_counts(AirMainLevel l) { return l >= AirMainLevel::Lk; }
 inline bool air_main_allows_runs(AirMainLevel l) { return l >= AirMainLevel::Link; }
@@ -148,6 +155,7 @@ inline bool air_main_allows_quotients(AirMainLevel l) { return l >= AirMainLevel
 inline bool air_main_allows_fetches(AirMainLevel l) { return l >= AirMainLevel::Fetch; }
 inline bool air_main_allows_words(AirMainLevel l) { return l >= AirMainLevel::Word; }
 inline bool air_main_allows_int_ops(AirMainLevel l) { return l >= AirMainLevel::Int; }
+inline bool air_main_allows_lists(AirMainLevel l) { return l >= AirMainLevel::Multi; }
 
 // Everything a prover, a trace check or a verifier is told about a program AIR: the descriptor (its strides inside) and its optional
 // parts, each present or not.  aux_reads_periodic: whether the auxiliary program may read the periodic columns with op 6 (the _pub
@@ -198,6 +206,10 @@ struct AirStatement {
 // earlier ops, behind the seed or step op of a CHAIN column only, as op 7 - a column of any other kind whose operand depends on one is
 // refused (a row-local limb or word is a LIMB or WORD column); without it they are malformed ops, as ever.  An AND / OR / XOR operand
 // at or above 2^251 is a matter of the rows: SP_E_INVALID_ARG from the call.
+// main_level Multi (the _multi entry points only; it brings Int with it): a COUNT column's pad may carry bit 8 (pad = key_bits + 256),
+// and its num_op then names a list of 1 .. 16 cells of op 12 ALSO - a: an earlier value, one looked-up value; b: an earlier cell, the
+// rest of the list, or 0xFFFF -; the column counts all of them against its one table.  A cell has no value: it is no operand, no OUT,
+// no den_op and stands behind no other column.  Without it op 12 is a malformed op and such a pad a key_bits out of range, as ever.
 // The constraint program itself is checked where it is turned into what runs it (build_air_program, air_verify_host).
 // An sp_air_ext is taken apart by the entry point that receives it; this is the one thing it checks first: null, or what is wrong.
 inline const char* air_ext_refusal(const sp_air_ext* ext) { return ext && ext->size != sizeof(sp_air_ext) ? "sp_air_ext.size is not sizeof(sp_air_ext)" : nullptr; }

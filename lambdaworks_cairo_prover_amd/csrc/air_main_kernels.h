@@ -38,6 +38,18 @@ int air_main_chain(hipStream_t st, fe* trace, uint64_t n, uint32_t log_s, uint32
 // head of a run of equal table keys (p == 0 or kt[p] != kt[p - 1]) z = upper_bound(kx, kt[p]) - lower_bound(kx, kt[p]), elsewhere
 // z = 0; col[rows[p]] = z as a field element.  rows is a permutation of 0 .. n - 1: every cell of col is written once.  n < 2^32.
 int air_main_count(hipStream_t st, const uint64_t* kx, const uint64_t* kt, const uint32_t* rows, uint64_t n, fe* col);
+// A joint COUNT column (one multiplicity column for the L = n_keys looked-up values of a list), in two calls.
+// air_main_list_keys: the key pass of the looked-up values - one launch of the interpreter whose OUT AIR_AUX_DEN_TAG + k, k < n_keys,
+// stores key k of row i at keys[k * n + i], out of Montgomery form; a canonical integer at or above 2^key_bits stores
+// AIR_AUX_FLAG_KEY_RANGE to *flag, the word air_aux_sort_terms uses.  keys holds n_keys * n words.
+int air_main_list_keys(hipStream_t st, const fe* trace, uint64_t n, const AirOpDev* ops, uint32_t n_ops, const fe* consts, uint64_t* keys, uint32_t n_keys,
+                       uint32_t key_bits, int* flag, const AirPeriodicCol* pcols = nullptr, const fe* pvals = nullptr);
+// air_main_count_many: kx the n_lists * n looked-up keys in any order, kt the n table keys in ascending order - sorted stably, rows[p]
+// the row that table key p came from -, counters n words that the caller has zeroed on the same stream.  First one lane per looked-up
+// key: p = lower_bound(kt, key) over [0, n), and where kt[p] == key one is added to counters[p], the head of the key's run of equal
+// table keys - lanes of a wave that hit one head add their sum in one atomic.  Then one lane per p: col[rows[p]] = counters[p] on the
+// head of a run, zero behind it, as a field element: every cell of col is written once.  1 <= n_lists <= 16, n < 2^32.
+int air_main_count_many(hipStream_t st, const uint64_t* kx, uint32_t n_lists, const uint64_t* kt, const uint32_t* rows, uint64_t n, uint64_t* counters, fe* col);
 // A group of w FETCH columns (looked-up values) that share their keys: kx the n looked-up keys in ROW order, kt the n table keys in
 // ascending order - sorted stably, rows[p] the row that table key p came from -, vals[j * n + r] the table value of group column j on
 // row r.  One lane per row i: p = lower_bound(kt, kx[i]) over [0, n) - the head of the run of equal table keys, its lowest row -, found

@@ -141,6 +141,104 @@ int air_main_count(hipStream_t st, const uint64_t* kx, const uint64_t* kt, const
     return SP_OK;
 }
 
+// ---- joint lookup multiplicities: several looked-up values under one column, counted into the sorted table ------------------------
+// The looked-up keys are not sorted: the table is, once, and every looked-up key searches it.
+// Key pass of the L looked-up values of a joint COUNT column: the key pass of a sorted column (air_aux_sort_terms_kernel) with L OUTs
+// and no rows - OUT AIR_AUX_DEN_TAG + k stores key k of row i at keys[k * n + i], out of Montgomery form, its range held against
+// key_bits into the same flag word.  An OUT code outside [AIR_AUX_DEN_TAG, AIR_AUX_DEN_TAG + n_keys) stores nothing: the stores stay
+// inside keys whatever the program holds.
+template <bool PER>
+__global__ void __launch_bounds__(256) air_main_list_keys_kernel(const fe* __restrict__ trace, uint64_t n, const AirOpDev* __restrict__ ops, uint32_t n_ops,
+                                                                 const fe* __restrict__ consts, uint64_t* __restrict__ keys, uint32_t n_keys, uint32_t key_bits,
+                                                                 int* __restrict__ flag, const AirPeriodicCol* __restrict__ pcols, const fe* __restrict__ pvals) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    auto load = [&](uint32_t shift, uint32_t col) { return fe_ld(trace + (uint64_t)col * n + ((i + shift) & (n - 1))); };   // n is a power of two
+    auto out = [&](uint32_t a, const fe& val) {
+        const uint32_t k = a - AIR_AUX_DEN_TAG;
+        if (a < AIR_AUX_DEN_TAG || k >= n_keys) return;
+        const fe raw = fe_from_mont(val);
+        const uint64_t key = (uint64_t)raw.v[0] | ((uint64_t)raw.v[1] << 32);
+        const uint32_t high = raw.v[2] | raw.v[3] | raw.v[4] | raw.v[5] | raw.v[6] | raw.v[7];
+        if (high || (key_bits < 64 && (key >> key_bits))) atomicExch(flag, AIR_AUX_FLAG_KEY_RANGE);
+        keys[(uint64_t)k * n + i] = key;
+    };
+    if constexpr (PER) air_run_program<true>(ops, n_ops, consts, load, AirRowPeriodic{pcols, pvals, i}, out);
+    else air_run_program<false>(ops, n_ops, consts, load, AirNoPeriodic{}, out);
+}
+
+int air_main_list_keys(hipStream_t st, const fe* trace, uint64_t n, const AirOpDev* ops, uint32_t n_ops, const fe* consts, uint64_t* keys, uint32_t n_keys,
+                       uint32_t key_bits, int* flag, const AirPeriodicCol* pcols, const fe* pvals) {
+    if (n == 0 || (n & (n - 1)) || n >= (1ull << 32) || n_keys == 0 || key_bits == 0 || key_bits > 64 || !keys || !flag || (pcols == nullptr) != (pvals == nullptr))
+        return SP_E_INVALID_ARG;
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, trace, n, ops, n_ops, consts, keys, n_keys, key_bits, flag, pcols, pvals);
+    };
+    pcols ? launch(air_main_list_keys_kernel<true>) : launch(air_main_list_keys_kernel<false>);
+    SP_HIP_CHECK(hipGetLastError());
+    return SP_OK;
+}
+
+// One lane per looked-up key: q = k n + i < total = L n, so the lanes of a wave hold neighbouring rows of one X_k.  The search is the
+// one of air_main_fetch_kernel - the lower bound of the key in kt, the head of its run of equal table keys; lo, hi and every probe stay
+// in [0, n) whatever the arrays hold, and kt[n] is never read.  A key that is found adds 1 to the 64-bit counter of its head (L n may
+// pass 2^32), a key in no table row adds nothing.  Padding rows all look up one value, so without more every lane of every wave would
+// queue on one address: the lanes of a wave that hit the same head combine first.  Each turn of the loop takes the head of the first
+// lane still waiting (a wave-uniform value out of v_readlane), votes which lanes wait for the same head, and lets that first lane add
+// the number of votes in one atomic; a wave on one address is through in one turn and one atomic, a wave on 64 different heads in 64
+// turns of a few scalar instructions each - less than its 64 searches' dependent loads.  Integer adds commute: the counters do not
+// depend on the order of arrival.  No lane leaves before the loop: a lane beyond `total` or without a match just never waits.
+__global__ void __launch_bounds__(256) air_main_count_many_kernel(const uint64_t* __restrict__ kx, uint64_t total, const uint64_t* __restrict__ kt, uint64_t n,
+                                                                  unsigned long long* __restrict__ counters) {
+    const uint64_t q = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    uint32_t head = 0;
+    bool waiting = false;
+    if (q < total) {
+        const uint64_t key = kx[q];
+        uint64_t lo = 0, hi = n;   // lower bound: first kt >= key
+        while (lo < hi) {
+            const uint64_t mid = lo + ((hi - lo) >> 1);
+            if (kt[mid] < key) lo = mid + 1; else hi = mid;
+        }
+        const uint64_t p = lo < n ? lo : n - 1;
+        waiting = lo < n && kt[p] == key;
+        head = (uint32_t)p;   // (p < n < 2^32)
+    }
+    const uint32_t lane = threadIdx.x & 63u;
+    for (;;) {
+        const unsigned long long todo = __ballot(waiting);
+        if (todo == 0) break;
+        const uint32_t first = (uint32_t)__ffsll(todo) - 1u;
+        const uint32_t at = (uint32_t)__builtin_amdgcn_readlane((int)head, (int)first);
+        const bool same = waiting && head == at;
+        const unsigned long long votes = __ballot(same);
+        if (lane == first && at < n) atomicAdd(counters + at, (unsigned long long)__popcll(votes));
+        waiting = waiting && !same;
+    }
+}
+
+// One lane per sorted table position p: the counter on the head of a run of equal table keys - the stable sort put the run's lowest row
+// there -, zero behind it, to the row the sort carried along.  rows is a permutation of 0 .. n - 1, so every cell of the column is
+// written exactly once, as in air_main_count_kernel.
+__global__ void __launch_bounds__(256) air_main_count_store_kernel(const unsigned long long* __restrict__ counters, const uint64_t* __restrict__ kt,
+                                                                   const uint32_t* __restrict__ rows, uint64_t n, fe* __restrict__ col) {
+    const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    const uint32_t row = rows[p];
+    const uint64_t z = (p == 0 || kt[p - 1] != kt[p]) ? counters[p] : 0;
+    if (row < n) fe_st(col + row, fe_from_u64(z));
+}
+
+int air_main_count_many(hipStream_t st, const uint64_t* kx, uint32_t n_lists, const uint64_t* kt, const uint32_t* rows, uint64_t n, uint64_t* counters, fe* col) {
+    if (n == 0 || n >= (1ull << 32) || n_lists == 0 || n_lists > 16 || !kx || !kt || !rows || !counters || !col) return SP_E_INVALID_ARG;
+    const uint64_t total = (uint64_t)n_lists * n;
+    unsigned long long* cnt = reinterpret_cast<unsigned long long*>(counters);
+    hipLaunchKernelGGL(air_main_count_many_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, kx, total, kt, n, cnt);
+    hipLaunchKernelGGL(air_main_count_store_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, cnt, kt, rows, n, col);
+    SP_HIP_CHECK(hipGetLastError());
+    return SP_OK;
+}
+
 // ---- looked-up values: the join of the looked-up keys, in row order, against the sorted table keys -----------------------------
 // One lane per row i, so the w stores of a lane are coalesced with its neighbours' into the group's columns.  The search is one
 // chain of dependent 8-byte loads out of kt, which the sort has just left in the L2 (log2 n + 1 of them); neighbouring rows look up

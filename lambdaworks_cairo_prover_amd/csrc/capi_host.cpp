@@ -141,6 +141,14 @@ int sp_air_main_int_limits(uint32_t out[4]) {
     out[0] = sp::AIR_MAIN_LIMB_MAX_END; out[1] = sp::AIR_MAIN_WORD_MAX_BITS; out[2] = sp::AIR_MAIN_INT_OPS; out[3] = 0;
     return SP_OK;
 }
+int sp_air_main_check_multi(const sp_air_desc* d, const sp_air_ext* ext, const sp_air_main_desc* mp, uint64_t n) {
+    return air_main_check("sp_air_main_check_multi", d, ext, sp::AirMainLevel::Multi, mp, n);
+}
+int sp_air_main_multi_limits(uint32_t out[4]) {
+    if (!out) return SP_E_INVALID_ARG;
+    out[0] = sp::AIR_MAIN_COUNT_MAX_LIST; out[1] = sp::AIR_MAIN_COUNT_MAX_KEY_BITS; out[2] = sp::AIR_MAIN_COUNT_MAX_COLS; out[3] = 0;
+    return SP_OK;
+}
 int sp_air_main_link_limits(uint32_t out[2]) {
     if (!out) return SP_E_INVALID_ARG;
     out[0] = sp::AIR_MAIN_LINK_MAX_LOG; out[1] = sp::AIR_MAIN_CHAIN_MAX_WIDTH;

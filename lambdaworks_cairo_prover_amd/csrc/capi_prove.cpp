@@ -473,7 +473,7 @@ int sp_air_check_trace_pub(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ex
 // (SP_AIR_MAIN_CHAIN) and reads of the periodic columns (op 6), _lk for lookup multiplicities (SP_AIR_MAIN_COUNT) too, _link for chain
 // groups that link their blocks into runs (the k of a CHAIN column's pad), _div for quotients (op 7) behind chain seeds and steps,
 // _fetch for looked-up values (SP_AIR_MAIN_FETCH), _word for limbs and bitwise words (SP_AIR_MAIN_LIMB, SP_AIR_MAIN_WORD), _int for the
-// integer ops 8 .. 11 behind chain seeds and steps.
+// integer ops 8 .. 11 behind chain seeds and steps, _multi for COUNT columns over a list of looked-up values (op 12).
 namespace {
 using sp::AirMainLevel;
 int air_prove_main(AirMainLevel level, sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const sp_air_boundary_desc* bv, const sp_air_main_desc* mp,
@@ -601,6 +601,18 @@ int sp_air_check_trace_int(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ex
 }
 int sp_air_main_trace_int(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const sp_air_main_desc* mp, const void* inputs, uint64_t n, uint8_t* rows_out) {
     return air_main_trace_ext("sp_air_main_trace_int", AirMainLevel::Int, c, d, ext, mp, inputs, n, rows_out);
+}
+
+int sp_air_prove_multi(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const sp_air_boundary_desc* bv, const sp_air_main_desc* mp, const void* inputs,
+                       uint64_t n, const sp_proof_options* opt, uint8_t** proof_out, uint64_t* proof_len) {
+    return air_prove_main(AirMainLevel::Multi, c, d, ext, bv, mp, inputs, n, opt, proof_out, proof_len);
+}
+int sp_air_check_trace_multi(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const sp_air_boundary_desc* bv, const sp_air_main_desc* mp, const void* inputs,
+                             uint64_t n, const sp_proof_options* opt, const uint8_t* rap, sp_air_violation* out, uint32_t cap, uint32_t* n_out) {
+    return air_check_trace_main(AirMainLevel::Multi, c, d, ext, bv, mp, inputs, n, opt, rap, out, cap, n_out);
+}
+int sp_air_main_trace_multi(sp_ctx* c, const sp_air_desc* d, const sp_air_ext* ext, const sp_air_main_desc* mp, const void* inputs, uint64_t n, uint8_t* rows_out) {
+    return air_main_trace_ext("sp_air_main_trace_multi", AirMainLevel::Multi, c, d, ext, mp, inputs, n, rows_out);
 }
 
 }  // extern "C"

@@ -128,6 +128,10 @@ class StarkProver : public sp_deletable {
     // At Int a chain group whose slotted seed or step program still holds an op 8 .. 11 launches the kernel's INT instantiation with
     // the WORD columns' verdict word - an AND, OR or XOR operand at or above 2^251 is the same SP_E_INVALID_ARG, under a value of its
     // own -, every other group the instantiation it always launched.
+    // At Multi a joint COUNT column (bit 8 of its pad, a list of op 12 cells behind num_op) is a chunk of its own: the table's key pass
+    // and its sort - the only one -, one key pass for all looked-up values, and air_main_count_many, which searches the sorted table
+    // from every looked-up key and adds into counters zeroed on the stream on every run; a key out of range is the COUNT columns'
+    // verdict.  A COUNT column without bit 8 launches what it always launched.
     int commit_main_program(const AirStatement& st, const uint8_t* inputs, uint8_t root_out[32]);
     // the same table without the commitment, to host memory: row-major n x main_cols, context encoding (sp_air_main_trace)
     int main_program_table(const AirStatement& st, const uint8_t* inputs, uint8_t* rows_out);

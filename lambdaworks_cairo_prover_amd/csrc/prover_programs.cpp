@@ -27,6 +27,9 @@ static int program_with_outs(const std::vector<AirOpHost>& src, const std::vecto
     std::vector<uint32_t> at(src.size());
     for (size_t t = 0; t < src.size(); ++t) {
         AirOpHost o = src[t];
+        // (a list cell of a joint COUNT column: a leaf that holds a list, no value - never uploaded.  Its at[t] stays 0 and must never be
+        // read: the decoder lets no value op and no OUT name a cell, so nothing below remaps an operand through it)
+        if (o.op == AIR_OP_ALSO) continue;
         if (air_op_takes_two_values(o.op)) { o.a = at[o.a]; o.b = at[o.b]; }   // (LOAD, CONST and PERIODIC name cells, not values)
         else if (air_op_takes_one_value(o.op)) o.a = at[o.a];                  // (an integer LIMB: b is lo + 256 width)
         at[t] = (uint32_t)ext.size();
@@ -276,7 +279,13 @@ struct MainChunk {
     //   order -, one of air_aux_terms into kc workspace slots, one radix sort of the table's pairs and one launch of air_main_fetch,
     //   which writes every cell of the group.  Its arrays (3 x [n] keys, 3 x [n] rows, the radix histograms) lie at the start of the
     //   workspace, the kc slots behind them.
-    enum class Kind { RowLocal, Chain, Count, Fetch };
+    // CountMany: a joint COUNT column (bit 8 of its pad: one multiplicity column for the L looked-up values of a list), a chunk of
+    //   its own as a COUNT column is.  T's program with the one OUT of a key pass and the L looked-up values' with an OUT each: one
+    //   launch of air_aux_sort_terms and one radix sort - the table's, the only sort -, one launch of air_main_list_keys and
+    //   air_main_count_many, which searches the sorted table from every looked-up key, adds into n 64-bit counters (zeroed on the
+    //   stream on every run) and writes every cell of the column.  Its arrays (2 x [n] keys, 2 x [n] rows, the radix histograms, then
+    //   L x [n] keys and [n] counters) lie at the start of the workspace.
+    enum class Kind { RowLocal, Chain, Count, Fetch, CountMany };
     static constexpr int N_PROG = 3;
     static constexpr int TERMS = 0, STEP = 0, SEED = 1, KEY_X = 0, KEY_T = 1, TABLE_V = 2;   // which of prog[] a kind's programs are
     Kind kind = Kind::RowLocal;
@@ -296,16 +305,20 @@ struct MainChunk {
     uint32_t log_s = 0, log_k = 0;           // blocks of 2^log_s rows; log_k >= 1: runs of 2^log_k blocks
     bool divides = false;                    // the slotted seed or step program holds an op 7: the launch takes the zero flag
     bool integers = false;                   // it holds an op 8 .. 11: the launch takes the range flag
-    // Count, Fetch
+    // Count, Fetch, CountMany
     uint32_t key_bits = 0;
+    // CountMany
+    uint32_t n_lists = 0;                    // L, the looked-up values of the list
 };
 
 struct MainPlan {
     std::vector<MainChunk> chunks;
     uint32_t chunk = 0, max_slots = 0, max_inv = 0;
-    bool any_count = false, any_fetch = false, any_word = false, any_int = false;
+    bool any_count = false, any_fetch = false, any_word = false, any_int = false;   // (any_count: COUNT columns of either form)
+    bool any_plain_count = false;            // a COUNT column of the old form: its four pair sets
     bool any_verdict() const { return any_count || any_fetch || any_word || any_int; }   // the three verdict words behind the workspace are in use
     uint32_t max_fetch = 0;                  // the widest FETCH group
+    uint32_t max_lists = 0;                  // the longest list of a joint COUNT column (0: none)
     size_t o_consts = 0, bytes = 0;          // the upload block: the constants, per chunk its programs and tables, the periodic columns
     PeriodicUpload per;
     uint64_t ws_elems = 0;                   // the workspace; the three verdict words lie behind it
@@ -356,6 +369,27 @@ static int plan_main_program(const AirStatement& st, uint64_t n, MainPlan& P) {
             if (ch.kc > AIR_MAIN_CHAIN_WIDTH || ch.log_s + ch.log_k >= 64 || n >> (ch.log_s + ch.log_k) == 0) { sp_set_error("commit_main_program: a chain group the decoder should have refused"); return SP_E_INVALID_ARG; }
             SP_TRY(program(seeds, ch, MainChunk::SEED));
             SP_TRY(program(outs, ch, MainChunk::STEP));
+        } else if (mp.cols[k0].kind == SP_AIR_MAIN_COUNT && mp.cols[k0].list_len) {
+            const AirMainColumnHost& c = mp.cols[k0];
+            std::vector<std::vector<uint32_t>> table(n_src);
+            bool fine = air_main_allows_lists(st.main_level) && c.key_bits >= 1 && c.key_bits <= 64 && c.den_op < n_src && c.list_len <= AIR_MAIN_COUNT_MAX_LIST;
+            uint32_t cell = c.num_op;
+            for (uint32_t k = 0; fine && k < c.list_len; ++k) {   // X_k is the a of the k-th cell; the last cell's b ends the list
+                fine = cell < n_src && mp.ops[cell].op == AIR_OP_ALSO && mp.ops[cell].a < n_src;
+                if (!fine) break;
+                outs[mp.ops[cell].a].push_back(AIR_AUX_DEN_TAG + k);
+                cell = mp.ops[cell].b;
+            }
+            if (!fine || cell != AIR_LIST_END) { sp_set_error("commit_main_program: a joint COUNT column the decoder should have refused"); return SP_E_INVALID_ARG; }
+            table[c.den_op].push_back(AIR_AUX_DEN_TAG);
+            ch.kind = MainChunk::Kind::CountMany;
+            ch.kc = 1;
+            ch.key_bits = c.key_bits;
+            ch.n_lists = c.list_len;
+            SP_TRY(program(outs, ch, MainChunk::KEY_X));
+            SP_TRY(program(table, ch, MainChunk::KEY_T));
+            P.any_count = true;
+            P.max_lists = std::max(P.max_lists, ch.n_lists);
         } else if (mp.cols[k0].kind == SP_AIR_MAIN_COUNT) {
             const AirMainColumnHost& c = mp.cols[k0];
             std::vector<std::vector<uint32_t>> table(n_src);
@@ -367,7 +401,7 @@ static int plan_main_program(const AirStatement& st, uint64_t n, MainPlan& P) {
             ch.key_bits = c.key_bits;
             SP_TRY(program(outs, ch, MainChunk::KEY_X));
             SP_TRY(program(table, ch, MainChunk::KEY_T));
-            P.any_count = true;
+            P.any_count = P.any_plain_count = true;
         } else if (mp.cols[k0].kind == SP_AIR_MAIN_FETCH) {
             const AirMainColumnHost& c = mp.cols[k0];
             std::vector<std::vector<uint32_t>> table(n_src), values(n_src);
@@ -478,7 +512,9 @@ static int plan_main_program(const AirStatement& st, uint64_t n, MainPlan& P) {
     //     counts:  4 x [n] keys, 4 x [n] rows, the radix sort's histograms (all in units of 32 bytes)
     //     fetches: 3 x [n] keys, 3 x [n] rows, the radix sort's histograms, [max_fetch][n] table values
     if ((P.any_count || P.any_fetch) && n >= (1ull << 32)) { sp_set_error("commit_main_program: COUNT and FETCH columns need a trace of fewer than 2^32 rows"); return SP_E_INVALID_ARG; }
-    P.ws_elems = std::max(((uint64_t)P.max_slots + P.max_inv) * n + (uint64_t)P.chunk * air_aux_scan_blocks(n), P.any_count ? SortScratch::elems(n, 4) : 0);
+    //     joint counts: 2 x [n] keys, 2 x [n] rows, the radix sort's histograms, [max_lists][n] looked-up keys, [n] counters
+    P.ws_elems = std::max(((uint64_t)P.max_slots + P.max_inv) * n + (uint64_t)P.chunk * air_aux_scan_blocks(n), P.any_plain_count ? SortScratch::elems(n, 4) : 0);
+    if (P.max_lists) P.ws_elems = std::max(P.ws_elems, SortScratch::elems(n, 2) + ((uint64_t)P.max_lists + 1) * SortScratch::keys_el(n));
     if (P.any_fetch) P.ws_elems = std::max(P.ws_elems, SortScratch::elems(n, 3) + (uint64_t)P.max_fetch * n);
     return SP_OK;
 }
@@ -535,6 +571,9 @@ int StarkProver::build_main_program(const AirStatement& st, const uint8_t* input
     const SortScratch s(ws, n_, 4);   // a COUNT column: X's pairs in keys / rows [0] and [1], T's in [2] and [3]
     const SortScratch f(ws, n_, 3);   // a FETCH group: T's pairs in keys / rows [0] and [1], X's in [2]; the table values behind
     fe* fetch_vals = ws + SortScratch::elems(n_, 3);
+    const SortScratch j(ws, n_, 2);   // a joint COUNT column: T's pairs in keys / rows [0] and [1]; the looked-up keys and the counters behind
+    uint64_t* list_keys = reinterpret_cast<uint64_t*>(ws + SortScratch::elems(n_, 2));
+    uint64_t* list_counters = list_keys + (uint64_t)P.max_lists * 4 * SortScratch::keys_el(n_);
     fe* scratch = ws + (uint64_t)P.max_slots * n_;
     fe* block_tot = scratch + (uint64_t)P.max_inv * n_;
     auto tab = [&](const MainChunk& ch, MainChunk::Tab w) { return ch.tab[w].empty() ? nullptr : reinterpret_cast<const uint32_t*>(od_.auxp_buf.p + ch.o_tab[w]); };
@@ -557,6 +596,13 @@ int StarkProver::build_main_program(const AirStatement& st, const uint8_t* input
             SP_TRY(radix_sort_pairs_u64(c_->stream, s.keys[0], s.keys[1], s.rows[0], s.rows[1], n_, ch.key_bits, s.radix));
             SP_TRY(radix_sort_pairs_u64(c_->stream, s.keys[2], s.keys[3], s.rows[2], s.rows[3], n_, ch.key_bits, s.radix));
             SP_TRY(air_main_count(c_->stream, s.keys[1], s.keys[3], s.rows[3], n_, cols));
+            break;
+        case MainChunk::Kind::CountMany:   // the table's key pass and sort (into keys / rows [1]), the looked-up keys, search and add, store
+            SP_HIP_CHECK(hipMemsetAsync(list_counters, 0, sizeof(uint64_t) * n_, c_->stream));
+            SP_TRY(air_aux_sort_terms(c_->stream, d_trace_, n_, prog[MainChunk::KEY_T], n_prog[MainChunk::KEY_T], consts_dev, nullptr, j.keys[0], j.rows[0], ch.key_bits, key_flag, pc, pv));
+            SP_TRY(radix_sort_pairs_u64(c_->stream, j.keys[0], j.keys[1], j.rows[0], j.rows[1], n_, ch.key_bits, j.radix));
+            SP_TRY(air_main_list_keys(c_->stream, d_trace_, n_, prog[MainChunk::KEY_X], n_prog[MainChunk::KEY_X], consts_dev, list_keys, ch.n_lists, ch.key_bits, key_flag, pc, pv));
+            SP_TRY(air_main_count_many(c_->stream, list_keys, ch.n_lists, j.keys[1], j.rows[1], n_, list_counters, cols));
             break;
         case MainChunk::Kind::Fetch:   // key passes (X's pairs stay in row order), V's terms, the table's sort (into keys / rows [1]), the join
             SP_TRY(air_aux_sort_terms(c_->stream, d_trace_, n_, prog[MainChunk::KEY_T], n_prog[MainChunk::KEY_T], consts_dev, nullptr, f.keys[0], f.rows[0], ch.key_bits, key_flag, pc, pv));

@@ -51,7 +51,9 @@ struct Parts {
     sp_air_main_desc rp{};
     // a main program with a lookup multiplicity (use 'l': through the _lk policy, 'L': through the _rec policy alone): x the one input;
     // v = x + K (VALUE, op 6), m = COUNT of X = v in T = K with 16 key bits, the running sum of m one row ahead; and one of 17 COUNT columns
-    sp_air_op lops[5] = {{0, 0, 0, 0, 0}, {6, 0, 0, 0, 0}, {2, 0, 0, 1, 0}, {0, 0, 0, 1, 0}, {0, 0, 1, 2, 0}};
+    // (ops 5 and 6, beyond n_ops until a case of the _multi policy - use 'j' - asks for them: the list cells of X = v and of X = x, v;
+    // ops 7 .. 22 are there for a case to fill)
+    sp_air_op lops[23] = {{0, 0, 0, 0, 0}, {6, 0, 0, 0, 0}, {2, 0, 0, 1, 0}, {0, 0, 0, 1, 0}, {0, 0, 1, 2, 0}, {12, 0, 3, 0xFFFF, 0}, {12, 0, 0, 5, 0}};
     sp_air_main_column lcols[3] = {{SP_AIR_MAIN_VALUE, 2, SP_AIR_AUX_NO_DEN, 0}, {SP_AIR_MAIN_COUNT, 3, 1, 16}, {SP_AIR_MAIN_SUM, 4, SP_AIR_AUX_NO_DEN, 0}};
     sp_air_main_column many_lcols[17];
     sp_air_main_desc lp{};
@@ -82,19 +84,19 @@ struct Parts {
 // use: which parts go to the decoder (x p s b m r R l L, upper case P: the auxiliary program may read the periodic columns; m: the main
 // program, for which the AIR gets its six main columns first; r / R the chain program with and without the _rec policy; l / L the
 // lookup program under the _lk policy and under the _rec policy alone; k the chain program under the _link policy; d the chain program
-// under the _div policy, i under the _int policy)
+// under the _div policy, i under the _int policy, j the lookup program under the _multi policy)
 void run(const char* label, const char* use, bool want_ok, const std::function<void(Parts&)>& patch) {
     Parts p;
     if (std::strchr(use, 'm')) p.with_main();
-    if (std::strchr(use, 'r') || std::strchr(use, 'R') || std::strchr(use, 'l') || std::strchr(use, 'L') || std::strchr(use, 'k') || std::strchr(use, 'd') || std::strchr(use, 'i')) p.with_chain();
+    if (std::strchr(use, 'r') || std::strchr(use, 'R') || std::strchr(use, 'l') || std::strchr(use, 'L') || std::strchr(use, 'k') || std::strchr(use, 'd') || std::strchr(use, 'i') || std::strchr(use, 'j')) p.with_chain();
     patch(p);
     auto has = [&](char c) { return std::strchr(use, c) != nullptr; };
     using sp::AirMainLevel;   // the highest level a use-letter implies wins
-    const AirMainLevel level = has('i') ? AirMainLevel::Int : has('d') ? AirMainLevel::Div : has('k') ? AirMainLevel::Link : has('l') ? AirMainLevel::Lk : has('r') || has('L') ? AirMainLevel::Rec : AirMainLevel::Main;
+    const AirMainLevel level = has('j') ? AirMainLevel::Multi : has('i') ? AirMainLevel::Int : has('d') ? AirMainLevel::Div : has('k') ? AirMainLevel::Link : has('l') ? AirMainLevel::Lk : has('r') || has('L') ? AirMainLevel::Rec : AirMainLevel::Main;
     sp::AirStatement st;
     const std::string refused = sp::air_statement_from_c(&p.d, has('x') ? &p.aux : nullptr, has('p') ? &p.per : nullptr, has('s') ? &p.sd : nullptr,
                                                          has('b') ? &p.bv : nullptr, has('P'), 16, st,
-                                                         has('m') ? &p.mp : has('r') || has('R') || has('k') || has('d') || has('i') ? &p.rp : has('l') || has('L') ? &p.lp : nullptr,
+                                                         has('m') ? &p.mp : has('r') || has('R') || has('k') || has('d') || has('i') ? &p.rp : has('l') || has('L') || has('j') ? &p.lp : nullptr,
                                                          level);
     const bool ok = refused.empty();
     if (ok != want_ok) { ++failures; std::printf("FAIL %-44s wanted %s, got %s\n", label, want_ok ? "accepted" : "refused", ok ? "accepted" : refused.c_str()); return; }
@@ -103,12 +105,20 @@ void run(const char* label, const char* use, bool want_ok, const std::function<v
     // the model on what was accepted: stride plan and zerofier, periodic columns as polynomials, boundary values under a challenge
     sp::AirStridePlan plan;
     bool fine = sp::air_stride_plan(st.air, 16, plan) && st.aux.has_value() == has('x') && st.periodic.has_value() == has('p') && st.bvals.has_value() == has('b') &&
-                (st.aux_periodic() != nullptr) == (has('P') && has('p')) && st.main.has_value() == (has('m') || has('r') || has('l') || has('k') || has('d') || has('i')) &&
-                st.main_level == (has('i') ? AirMainLevel::Int : has('d') ? AirMainLevel::Div : has('k') ? AirMainLevel::Link : has('l') ? AirMainLevel::Lk : has('r') ? AirMainLevel::Rec : AirMainLevel::Main) && !st.unsupported;
+                (st.aux_periodic() != nullptr) == (has('P') && has('p')) && st.main.has_value() == (has('m') || has('r') || has('l') || has('k') || has('d') || has('i') || has('j')) &&
+                st.main_level == (has('j') ? AirMainLevel::Multi : has('i') ? AirMainLevel::Int : has('d') ? AirMainLevel::Div : has('k') ? AirMainLevel::Link : has('l') ? AirMainLevel::Lk : has('r') ? AirMainLevel::Rec : AirMainLevel::Main) && !st.unsupported;
     if (st.main && has('l') && !has('r') && st.main->cols.size() == 3) {   // what the prover's chunking reads of a COUNT column
         const auto& c = st.main->cols;
         fine = fine && c[1].kind == SP_AIR_MAIN_COUNT && c[1].key_bits == p.lcols[1].pad && c[1].num_op == 3 && c[1].den_op == 1 && c[1].reads == 1 && c[0].key_bits == 0 &&
                c[2].key_bits == 0 && c[2].reads == 2;
+    }
+    if (st.main && has('j') && !has('i') && st.main->cols.size() == 3) {   // what the prover's chunking reads of a joint COUNT column: the list's length, the key bits apart
+        const auto& c = st.main->cols;
+        const bool joint = (p.lcols[1].pad & 256u) != 0;
+        uint32_t cells = 0;
+        for (uint32_t t = joint ? p.lcols[1].num_op : 0xFFFFu; t != 0xFFFFu; t = p.lops[t].b) ++cells;
+        fine = fine && c[1].kind == SP_AIR_MAIN_COUNT && c[1].key_bits == (p.lcols[1].pad & 255u) && c[1].list_len == cells && c[1].num_op == p.lcols[1].num_op &&
+               c[1].den_op == 1 && c[1].reads == 1 && c[0].list_len == 0 && c[2].list_len == 0 && st.main->ops.size() == p.lp.n_ops;
     }
     if (st.main && has('d')) {   // what the prover's chunking reads behind a quotient: the ops as they came, reads through op 7
         const auto& c = st.main->cols;
@@ -379,6 +389,49 @@ int main() {
     run("int: XOR in a step through the _rec policy", "pr", false, step_is(sp_air_op{11, 0, 2, 3, 0}));
     run("int: op 6 without periodic columns", "i", false, none);
     run("aux: op 8 through the _int policy", "xpi", false, [](Parts& p) { p.aux_ops[2].op = 8; });
+    // ---- one COUNT column over a list of looked-up values (the _multi policy, use 'j'): bit 8 of the pad, op 12 cells behind num_op
+    const auto joint = [](uint32_t n_ops, uint32_t num_op, uint32_t den_op, uint32_t pad) {
+        return [=](Parts& p) { p.lp.n_ops = n_ops; p.lcols[1] = sp_air_main_column{SP_AIR_MAIN_COUNT, num_op, den_op, pad}; };
+    };
+    const auto joint_and = [&](const std::function<void(Parts&)>& more) { return [=](Parts& p) { joint(7, 6, 1, 16 + 256)(p); more(p); }; };
+    run("multi: a lookup program without a list", "pj", true, none);
+    run("multi: cells that no column names", "pj", true, [](Parts& p) { p.lp.n_ops = 7; });
+    run("multi: a list of two", "pj", true, joint(7, 6, 1, 16 + 256));
+    run("multi: a list of one", "pj", true, joint(6, 5, 1, 64 + 256));
+    run("multi: one key bit", "pj", true, joint(7, 6, 1, 1 + 256));
+    run("multi: a list of sixteen", "pj", true, [&](Parts& p) { for (uint16_t t = 7; t < 21; ++t) p.lops[t] = sp_air_op{12, 0, 0, (uint16_t)(t - 1), 0}; joint(21, 20, 1, 16 + 256)(p); });
+    run("multi: a list of seventeen", "pj", false, [&](Parts& p) { for (uint16_t t = 7; t < 22; ++t) p.lops[t] = sp_air_op{12, 0, 0, (uint16_t)(t - 1), 0}; joint(22, 21, 1, 16 + 256)(p); });
+    run("multi: a pad with bit 9", "pj", false, joint(7, 6, 1, 16 + 256 + 512));
+    run("multi: a pad with bit 31", "pj", false, joint(7, 6, 1, 16 + 256 + (1u << 31)));
+    run("multi: bit 8 and a num_op that is no cell", "pj", false, joint(7, 3, 1, 16 + 256));
+    run("multi: a cell behind a column without bit 8", "pj", false, joint(7, 6, 1, 16));
+    run("multi: key_bits 0", "pj", false, joint(7, 6, 1, 256));
+    run("multi: key_bits 65", "pj", false, joint(7, 6, 1, 65 + 256));
+    run("multi: no table", "pj", false, joint(7, 6, SP_AIR_AUX_NO_DEN, 16 + 256));
+    run("multi: a cell as the table", "pj", false, joint(7, 6, 5, 16 + 256));
+    run("multi: a num_op beyond the program", "pj", false, joint(7, 7, 1, 16 + 256));
+    run("multi: a cell whose a is itself", "pj", false, joint_and([](Parts& p) { p.lops[5].a = 5; }));
+    run("multi: a cell whose a is later", "pj", false, joint_and([](Parts& p) { p.lops[5].a = 6; }));
+    run("multi: a cell whose a is a cell", "pj", false, joint_and([](Parts& p) { p.lops[6].a = 5; }));
+    run("multi: a cell whose b is a value", "pj", false, joint_and([](Parts& p) { p.lops[6].b = 3; }));
+    run("multi: a cell whose b is itself", "pj", false, joint_and([](Parts& p) { p.lops[6].b = 6; }));
+    run("multi: a cell whose b is beyond the program", "pj", false, joint_and([](Parts& p) { p.lops[5].b = 0xFFFE; }));
+    run("multi: an ADD of a cell", "pj", false, joint_and([](Parts& p) { p.lp.n_ops = 8; p.lops[7] = sp_air_op{2, 0, 6, 0, 0}; }));
+    run("multi: a MUL by a cell", "pj", false, joint_and([](Parts& p) { p.lp.n_ops = 8; p.lops[7] = sp_air_op{4, 0, 0, 5, 0}; }));
+    run("multi: an OUT of a cell", "pj", false, joint_and([](Parts& p) { p.lp.n_ops = 8; p.lops[7] = sp_air_op{5, 0, 0, 6, 0}; }));
+    run("multi: a VALUE that is a cell", "pj", false, joint_and([](Parts& p) { p.lcols[0].num_op = 5; }));
+    run("multi: a SUM over a cell", "pj", false, joint_and([](Parts& p) { p.lcols[2].den_op = 6; }));
+    run("multi: an X that reads its own column", "pj", false, joint_and([](Parts& p) { p.lops[5].a = 4; }));
+    run("multi: an X behind a quotient", "pj", false, joint_and([](Parts& p) { p.lp.n_ops = 9; p.lops[7] = sp_air_op{7, 0, 0, 1, 0}; p.lops[8] = sp_air_op{12, 0, 7, 6, 0}; p.lcols[1].num_op = 8; }));
+    run("multi: an X behind an integer op", "pj", false, joint_and([](Parts& p) { p.lp.n_ops = 9; p.lops[7] = sp_air_op{8, 0, 0, 256 * 8, 0}; p.lops[8] = sp_air_op{12, 0, 7, 0xFFFF, 0}; p.lcols[1].num_op = 8; }));
+    run("multi: op 13", "pj", false, joint_and([](Parts& p) { p.lp.n_ops = 8; p.lops[7] = sp_air_op{13, 0, 0, 1, 0}; }));
+    run("multi: a seventeenth COUNT column, joint", "pj", false, [](Parts& p) { p.many_counts(17); p.lp.n_ops = 7; p.many_lcols[16] = sp_air_main_column{SP_AIR_MAIN_COUNT, 6, 1, 64 + 256}; });
+    run("multi: sixteen COUNT columns, one joint", "pj", true, [](Parts& p) { p.many_counts(16); p.lp.n_ops = 7; p.many_lcols[15] = sp_air_main_column{SP_AIR_MAIN_COUNT, 6, 1, 64 + 256}; });
+    run("multi: a cell through the _lk policy", "pl", false, joint(7, 6, 1, 16 + 256));
+    run("multi: bit 8 through the _lk policy", "pl", false, joint(5, 3, 1, 16 + 256));
+    run("multi: cells that no column names through the _lk policy", "pl", false, [](Parts& p) { p.lp.n_ops = 7; });
+    run("multi: the chain program through the _multi policy", "pij", true, [](Parts& p) { (void)p; });
+    run("aux: op 12 through the _multi policy", "xpj", false, [](Parts& p) { p.aux_ops[2].op = 12; });
     run("aux: op 7", "x", false, [](Parts& p) { p.aux_ops[2].op = 7; });
     run("aux: op 7 through the _div policy", "xpd", false, [](Parts& p) { p.aux_ops[2].op = 7; });
     run("no main column", "", false, [](Parts& p) { p.d.main_cols = 0; p.ops[2] = sp_air_op{1, 0, 0, 0, 0}; });
