@@ -86,7 +86,8 @@ const char* sp_version(void);
  * sp_air_prove_fetch, sp_air_check_trace_fetch, sp_air_main_trace_fetch, sp_air_main_check_fetch and sp_air_main_fetch_limits, and last
  * sp_air_prove_word, sp_air_check_trace_word, sp_air_main_trace_word, sp_air_main_check_word and sp_air_main_word_limits, and after them
  * sp_air_prove_int, sp_air_check_trace_int, sp_air_main_trace_int, sp_air_main_check_int and sp_air_main_int_limits, and last
- * sp_air_prove_multi, sp_air_check_trace_multi, sp_air_main_trace_multi, sp_air_main_check_multi and sp_air_main_multi_limits).  A binding compares it (and sp_air_desc_size against its own idea of the struct) when it loads the library, so
+ * sp_air_prove_multi, sp_air_check_trace_multi, sp_air_main_trace_multi, sp_air_main_check_multi and sp_air_main_multi_limits, and after them sp_lde_dev,
+ * sp_intt_bitrev_dev and sp_ntt_plan).  A binding compares it (and sp_air_desc_size against its own idea of the struct) when it loads the library, so
  * a stale build fails at load time with "rebuild the library" instead of with a missing symbol or shifted fields later. */
 #define SP_ABI_VERSION 7
 int sp_abi_version(void);
@@ -230,6 +231,49 @@ int sp_ntt_dev(sp_ctx* ctx, void* data_dev, uint64_t n, uint32_t batch, int inve
  * (column-major: column j at coeffs + j*n*32): out column j holds n*blowup evaluations p_j(coset * w_N^i). */
 int sp_lde(sp_ctx* ctx, const uint8_t* coeffs, uint64_t n, uint32_t cols, uint32_t blowup, const uint8_t* coset,
            uint8_t* out);
+
+/* ---- the transform drivers as the prover itself calls them, on device memory (tests compare them element by element) ----
+ * All three are asynchronous on the context stream like sp_ntt_dev, take buffers in the DEVICE layout and strides in ELEMENTS, and
+ * validate every argument before the first launch: SP_E_INVALID_ARG for a size that is no power of two, n * blowup beyond 2^30,
+ * shard_log > log2(blowup), shard_rank >= 2^shard_log, a stride shorter than the array it separates, a null buffer, cols / batch of 0
+ * or beyond what one launch holds, and source and destination extents that overlap (src == data included).  Nothing is launched then.
+ *
+ * sp_lde_dev: the low-degree extension of `cols` polynomials from their bit-reversed, h-scaled coefficients - entry pos of column v, at
+ * coeffs_dev + (v * src_stride + pos) * 32, holds c_rev(pos) * h^rev(pos) (rev over log2 n bits), what sp_intt_bitrev_dev leaves with
+ * post_table[pos] = h^rev(pos) / n.  With b_loc = blowup >> shard_log the rank computes the cosets c = c_loc * 2^shard_log + shard_rank,
+ * c_loc < b_loc, and column v of the output starts at out_dev + v * dst_stride * 32 (dst_stride >= n * b_loc):
+ *   order SP_LDE_NATURAL (NttEngine::lde_from_bitrev):      element q * b_loc + c_loc = p_v(h w_N^(q * blowup + c)), q < n;
+ *   order SP_LDE_COSET_MAJOR (NttEngine::lde_coset_major):  element c_loc * n + m     = p_v(h w_N^(m * blowup + c)), m < n.
+ * sp_intt_bitrev_dev (NttEngine::dif_natural_to_bitrev_inverse): `batch` vectors of n natural-order evaluations at data_dev + v * stride
+ * * 32, in place: position pos receives post_table_dev[pos] * n * c_rev(pos), c = the interpolating coefficients (the transform is
+ * unscaled; post_table_dev - n entries, shared by the vectors - usually carries the 1 / n), canonical.  post_table_dev NULL: no
+ * factor.  src_dev non-NULL: read the evaluations from that array (same stride) and leave it untouched. */
+enum { SP_LDE_NATURAL = 0, SP_LDE_COSET_MAJOR = 1 };
+int sp_lde_dev(sp_ctx* ctx, const void* coeffs_dev, void* out_dev, uint64_t n, uint32_t blowup, uint32_t cols, uint64_t src_stride,
+               uint64_t dst_stride, int order, uint32_t shard_log, uint32_t shard_rank);
+int sp_intt_bitrev_dev(sp_ctx* ctx, void* data_dev, uint64_t n, uint32_t batch, uint64_t stride, const void* post_table_dev,
+                       const void* src_dev);
+/* The pass list a transform driver launches, from the code that launches it (csrc/ntt.hip ntt_plan), without a context or a GPU:
+ * driver = SP_NTT_DRIVER_*, 2^k elements per vector, blowup 2^logb and 2^shard_log shards (both 0 unless the driver is one of the two
+ * LDEs), `batch` vectors.  Up to `cap` passes are written to out (nullable) in execution order, *count_out (required) receives how
+ * many the driver launches; SP_E_INVALID_ARG for an unknown driver, k + logb > 30, shard_log > logb, batch 0 and cap < count. */
+enum { SP_NTT_DRIVER_FORWARD_NATURAL = 0, SP_NTT_DRIVER_INVERSE_NATURAL = 1, SP_NTT_DRIVER_DIT_BITREV_TO_NATURAL = 2,
+       SP_NTT_DRIVER_INTT_BITREV = 3, SP_NTT_DRIVER_LDE_NATURAL = 4, SP_NTT_DRIVER_LDE_COSET_MAJOR = 5 };
+typedef struct {
+    uint32_t dif;          /* 1: decimation in frequency with inverse roots, 0: decimation in time */
+    uint32_t load, store;  /* load: 0 in place, 1 bit-reversal gather, 2 expand (replicated LDE input); store: 0 in place, 1 bit-reversal scatter */
+    uint32_t contig, gtw;  /* contiguous tile; twiddles from the transform's table (0: the pass-local table) */
+    uint32_t s, r, g;      /* LOCAL stride 2^s, 2^r rows, 2^g adjacent elements per row */
+    uint32_t radix4;       /* stages run in pairs (1024-element tiles with r >= 2) */
+    uint32_t xcd_map;      /* work-groups dealt to the XCDs by tile */
+    uint32_t weak_out;     /* stores values below 2p (every pass but the last) */
+    uint32_t stage_tw;     /* reads per-stage twiddle tables where the context could allocate them */
+    uint32_t log_len;      /* log2 of the array the pass addresses */
+    uint32_t tiles;        /* work-groups per vector */
+    uint32_t vectors;      /* vectors per launch (columns x local cosets in the coset-major LDE) */
+    uint32_t coset_count;  /* coset-major LDE: local cosets per column, else 0 */
+} sp_ntt_pass;
+int sp_ntt_plan(int driver, uint32_t k, uint32_t logb, uint32_t shard_log, uint32_t batch, sp_ntt_pass* out, uint32_t cap, uint32_t* count_out);
 
 /* MerkleTree::<BatchKeccak256Tree|Keccak256Tree>::build (prover.rs:96-104, fri_commitment.rs:39; backends
  * config.rs:10-20): n_leaves rows of fe_per_leaf elements (row-major); leaf = Keccak256(row as 32-byte BE

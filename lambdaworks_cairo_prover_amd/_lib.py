@@ -48,9 +48,16 @@ class CairoPublicInputsC(ctypes.Structure):
                 ("n_public_memory", ctypes.c_uint64), ("public_memory", ctypes.c_void_p), ("num_steps", ctypes.c_uint64)]
 
 
+class NttPassC(ctypes.Structure):
+    """sp_ntt_pass: one launch of a transform driver's pass list (sp_ntt_plan)."""
+    _fields_ = [(name, ctypes.c_uint32) for name in ("dif", "load", "store", "contig", "gtw", "s", "r", "g", "radix4", "xcd_map", "weak_out",
+                                                      "stage_tw", "log_len", "tiles", "vectors", "coset_count")]
+
+
 # The entry points added most recently, probed at load time beside the version number (api.py binds symbols lazily: a stale build would
 # otherwise fail with AttributeError in the middle of a run instead of with "rebuild the library" here).
-NEWEST_SYMBOLS = ("sp_air_prove_multi", "sp_air_check_trace_multi", "sp_air_main_trace_multi", "sp_air_main_check_multi", "sp_air_main_multi_limits",
+NEWEST_SYMBOLS = ("sp_lde_dev", "sp_intt_bitrev_dev", "sp_ntt_plan",
+                  "sp_air_prove_multi", "sp_air_check_trace_multi", "sp_air_main_trace_multi", "sp_air_main_check_multi", "sp_air_main_multi_limits",
                   "sp_air_prove_int", "sp_air_check_trace_int", "sp_air_main_trace_int", "sp_air_main_check_int", "sp_air_main_int_limits",
                   "sp_air_prove_word", "sp_air_check_trace_word", "sp_air_main_trace_word", "sp_air_main_check_word", "sp_air_main_word_limits",
                   "sp_air_prove_fetch", "sp_air_check_trace_fetch", "sp_air_main_trace_fetch", "sp_air_main_check_fetch", "sp_air_main_fetch_limits",

@@ -11,7 +11,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import (SP_FE_CANON_BE, SP_FE_MONT_LIMBS, CairoPublicInputsC, ConfigC, ProofOptionsC, SpError, check)
+from ._lib import (SP_FE_CANON_BE, SP_FE_MONT_LIMBS, CairoPublicInputsC, ConfigC, NttPassC, ProofOptionsC, SpError, check)
 
 __all__ = ["ProofOptions", "Context", "CairoRun", "generate_prover_args_fibonacci", "SpError", "P", "felts_to_bytes",
            "bytes_to_felts", "SP_FE_CANON_BE", "SP_FE_MONT_LIMBS"]
@@ -340,6 +340,19 @@ class Context:
     def ntt_dev(self, data_ptr, n, batch=1, inverse=False):
         check(self._lib.sp_ntt_dev(self._h, ctypes.c_void_p(data_ptr), ctypes.c_uint64(n), ctypes.c_uint32(batch), int(bool(inverse)), None))
 
+    def lde_dev(self, coeffs_ptr, out_ptr, n, blowup, cols, src_stride, dst_stride, order, shard_log=0, shard_rank=0):
+        """sp_lde_dev: the prover's LDE drivers on device memory (asynchronous) - bit-reversed, h-scaled coefficients in, the evaluations
+        of this rank's cosets out, order LDE_NATURAL (lde_from_bitrev) or LDE_COSET_MAJOR (lde_coset_major); strides in elements."""
+        check(self._lib.sp_lde_dev(self._h, ctypes.c_void_p(coeffs_ptr), ctypes.c_void_p(out_ptr), ctypes.c_uint64(n), ctypes.c_uint32(blowup),
+                                   ctypes.c_uint32(cols), ctypes.c_uint64(src_stride), ctypes.c_uint64(dst_stride), int(order),
+                                   ctypes.c_uint32(shard_log), ctypes.c_uint32(shard_rank)))
+
+    def intt_bitrev_dev(self, data_ptr, n, batch, stride, post_table_ptr=None, src_ptr=None):
+        """sp_intt_bitrev_dev: natural-order evaluations -> post_table[pos] * n * c_rev(pos) in place on device memory (asynchronous);
+        src_ptr: read the evaluations from another array and leave it untouched."""
+        check(self._lib.sp_intt_bitrev_dev(self._h, ctypes.c_void_p(data_ptr), ctypes.c_uint64(n), ctypes.c_uint32(batch), ctypes.c_uint64(stride),
+                                           ctypes.c_void_p(post_table_ptr), ctypes.c_void_p(src_ptr)))
+
     def last_kernel_ms(self):
         ms = ctypes.c_float()
         check(self._lib.sp_last_kernel_ms(self._h, ctypes.byref(ms)))
@@ -355,6 +368,20 @@ class Context:
 
     def sync(self):
         check(self._lib.sp_sync(self._h))
+
+
+LDE_NATURAL, LDE_COSET_MAJOR = 0, 1
+NTT_DRIVERS = ("forward_natural", "inverse_natural", "dit_bitrev_to_natural", "intt_bitrev", "lde_natural", "lde_coset_major")   # SP_NTT_DRIVER_*
+NTT_PASS_FIELDS = tuple(name for name, _ in NttPassC._fields_)
+
+
+def ntt_plan(driver, k, logb=0, shard_log=0, batch=1):
+    """sp_ntt_plan: the passes a transform driver (a name of NTT_DRIVERS or its number) launches, as a list of dicts over NTT_PASS_FIELDS,
+    in execution order - from the code that launches them, without a context or a GPU."""
+    d = NTT_DRIVERS.index(driver) if isinstance(driver, str) else int(driver)
+    passes, count = (NttPassC * 8)(), ctypes.c_uint32()
+    check(_lib.load().sp_ntt_plan(d, ctypes.c_uint32(k), ctypes.c_uint32(logb), ctypes.c_uint32(shard_log), ctypes.c_uint32(batch), passes, 8, ctypes.byref(count)))
+    return [{name: getattr(passes[i], name) for name in NTT_PASS_FIELDS} for i in range(count.value)]
 
 
 def host_cpus():
@@ -959,7 +986,8 @@ Context.comm_selftest = _ctx_comm_selftest
 Context.comm_measure = _ctx_comm_measure
 Context.comm_time_ms = _ctx_comm_time_ms
 Context.set_option = _ctx_set_option
-__all__ += ["cairo_verify", "proof_file_bytes", "proof_file_verify", "StagedAllGather", "StagedAsyncAllGather", "shard_global_index", "interleave_shards",
+__all__ += ["ntt_plan", "LDE_NATURAL", "LDE_COSET_MAJOR", "NTT_DRIVERS", "NTT_PASS_FIELDS",
+            "cairo_verify", "proof_file_bytes", "proof_file_verify", "StagedAllGather", "StagedAsyncAllGather", "shard_global_index", "interleave_shards",
             "SP_OPT_FRI_SHARD_MIN_LOG", "SP_OPT_SHARD_INTERPOLATION", "SP_OPT_UPLOAD_THREADS", "SP_OPT_MERKLE_BACKEND", "SP_OPT_MERKLE_ONE_COLUMN_ROWS", "SP_OPT_DEVICE_TRACE", "SP_OPT_LINK_GBS", "SP_OPT_HOST_RANKS", "host_cpu_budget", "last_error", "model_shard_interpolation",
             "SP_MERKLE_KECCAK256", "SP_MERKLE_POSEIDON", "poseidon_host", "host_bind_to_device",
             "SP_PREWARM_KERNELS", "SP_PREWARM_CLOCKS", "SP_PREWARM_HOST_ROWS", "SP_PREWARM_ALL"]

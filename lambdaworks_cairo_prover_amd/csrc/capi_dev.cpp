@@ -643,6 +643,79 @@ int sp_lde(sp_ctx* c, const uint8_t* coeffs, uint64_t n, uint32_t cols, uint32_t
     return SP_OK;
 }
 
+// ---- the transform drivers as the prover calls them (sp_lde_dev, sp_intt_bitrev_dev) and their pass lists (sp_ntt_plan) ----
+namespace {
+// [p, p + ((vectors - 1) * stride + len) * 32): the bytes `vectors` arrays of `len` elements at `stride` elements span
+bool extents_overlap(const void* a, uint64_t a_elems, const void* b, uint64_t b_elems) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a0 < b0 + b_elems * sizeof(fe) && b0 < a0 + a_elems * sizeof(fe);
+}
+// *out = (vectors - 1) * stride + len, the elements `vectors` arrays of `len` at `stride` span; false when that does not fit 2^48
+// elements (2^53 bytes: no device holds it, and nothing computed from it below can wrap)
+bool span_elems(uint64_t vectors, uint64_t stride, uint64_t len, uint64_t* out) {
+    uint64_t prod = 0;
+    if (vectors == 0 || __builtin_mul_overflow(vectors - 1, stride, &prod) || __builtin_add_overflow(prod, len, out)) return false;
+    return *out < (1ull << 48);
+}
+// vectors x 2^logL elements in one launch: the launcher refuses 2^31 work-groups and a tile may be a single element
+bool launch_fits(uint64_t vectors, int logL) { return vectors >= 1 && vectors < (1ull << 31) && (vectors << logL) < (1ull << 31); }
+static_assert((int)NTT_DRV_FORWARD_NATURAL == SP_NTT_DRIVER_FORWARD_NATURAL && (int)NTT_DRV_INVERSE_NATURAL == SP_NTT_DRIVER_INVERSE_NATURAL &&
+              (int)NTT_DRV_DIT_BITREV_TO_NATURAL == SP_NTT_DRIVER_DIT_BITREV_TO_NATURAL && (int)NTT_DRV_DIF_NATURAL_TO_BITREV_INVERSE == SP_NTT_DRIVER_INTT_BITREV &&
+              (int)NTT_DRV_LDE_FROM_BITREV == SP_NTT_DRIVER_LDE_NATURAL && (int)NTT_DRV_LDE_COSET_MAJOR == SP_NTT_DRIVER_LDE_COSET_MAJOR,
+              "sp_ntt_plan hands the header's driver numbers to ntt_plan");
+static_assert(NTT_LOAD_GATHER_BITREV == 1 && NTT_LOAD_EXPAND == 2 && NTT_STORE_SCATTER_BITREV == 1, "sp_ntt_pass documents these numbers");
+}  // namespace
+
+int sp_lde_dev(sp_ctx* c, const void* coeffs_dev, void* out_dev, uint64_t n, uint32_t blowup, uint32_t cols, uint64_t src_stride,
+               uint64_t dst_stride, int order, uint32_t shard_log, uint32_t shard_rank) {
+    if (!c || !coeffs_dev || !out_dev || cols == 0) return SP_E_INVALID_ARG;
+    if (order != SP_LDE_NATURAL && order != SP_LDE_COSET_MAJOR) { sp_set_error("sp_lde_dev: unknown order"); return SP_E_INVALID_ARG; }
+    const int k = sp_log2_exact(n), lb = sp_log2_exact(blowup);
+    if (k < 0 || lb < 0 || k + lb > 30) { sp_set_error("sp_lde_dev: n and blowup must be powers of two, n * blowup <= 2^30"); return SP_E_INVALID_ARG; }
+    if (shard_log > (uint32_t)lb || shard_rank >= (1u << shard_log)) { sp_set_error("sp_lde_dev: shard_log <= log2(blowup) and shard_rank < 2^shard_log"); return SP_E_INVALID_ARG; }
+    const uint64_t b_loc = (uint64_t)blowup >> shard_log, out_len = n * b_loc;
+    if (src_stride < n || dst_stride < out_len) { sp_set_error("sp_lde_dev: src_stride >= n and dst_stride >= n * (blowup >> shard_log)"); return SP_E_INVALID_ARG; }
+    uint64_t src_span = 0, dst_span = 0;
+    if (!launch_fits((uint64_t)cols * b_loc, k) || !span_elems(cols, src_stride, n, &src_span) || !span_elems(cols, dst_stride, out_len, &dst_span)) { sp_set_error("sp_lde_dev: too many columns for one launch, or strides beyond any allocation"); return SP_E_INVALID_ARG; }
+    if (extents_overlap(coeffs_dev, src_span, out_dev, dst_span)) { sp_set_error("sp_lde_dev: coefficients and output overlap"); return SP_E_INVALID_ARG; }
+    SP_HIP_CHECK(hipSetDevice(c->device));
+    const fe* src = reinterpret_cast<const fe*>(coeffs_dev);
+    fe* dst = reinterpret_cast<fe*>(out_dev);
+    if (order == SP_LDE_COSET_MAJOR) return c->ntt->lde_coset_major(src, dst, k, lb, cols, src_stride, dst_stride, (int)shard_log, (int)shard_rank);
+    return c->ntt->lde_from_bitrev(src, dst, k, lb, cols, src_stride, dst_stride, (int)shard_log, (int)shard_rank);
+}
+
+int sp_intt_bitrev_dev(sp_ctx* c, void* data_dev, uint64_t n, uint32_t batch, uint64_t stride, const void* post_table_dev, const void* src_dev) {
+    if (!c || !data_dev || batch == 0) return SP_E_INVALID_ARG;
+    const int k = sp_log2_exact(n);
+    if (k < 0 || k > 30) { sp_set_error("sp_intt_bitrev_dev: n must be a power of two <= 2^30"); return SP_E_INVALID_ARG; }
+    if (stride < n) { sp_set_error("sp_intt_bitrev_dev: stride >= n"); return SP_E_INVALID_ARG; }
+    uint64_t span = 0;
+    if (!launch_fits(batch, k) || !span_elems(batch, stride, n, &span)) { sp_set_error("sp_intt_bitrev_dev: too many vectors for one launch, or a stride beyond any allocation"); return SP_E_INVALID_ARG; }
+    if (src_dev && extents_overlap(src_dev, span, data_dev, span)) { sp_set_error("sp_intt_bitrev_dev: src overlaps data (pass NULL to transform in place)"); return SP_E_INVALID_ARG; }
+    if (post_table_dev && extents_overlap(post_table_dev, n, data_dev, span)) { sp_set_error("sp_intt_bitrev_dev: post_table overlaps data"); return SP_E_INVALID_ARG; }
+    SP_HIP_CHECK(hipSetDevice(c->device));
+    return c->ntt->dif_natural_to_bitrev_inverse(reinterpret_cast<fe*>(data_dev), k, batch, stride, reinterpret_cast<const fe*>(post_table_dev),
+                                                 reinterpret_cast<const fe*>(src_dev));
+}
+
+int sp_ntt_plan(int driver, uint32_t k, uint32_t logb, uint32_t shard_log, uint32_t batch, sp_ntt_pass* out, uint32_t cap, uint32_t* count_out) {
+    if (!count_out || batch == 0 || driver < SP_NTT_DRIVER_FORWARD_NATURAL || driver > SP_NTT_DRIVER_LDE_COSET_MAJOR) return SP_E_INVALID_ARG;
+    const bool lde = driver == SP_NTT_DRIVER_LDE_NATURAL || driver == SP_NTT_DRIVER_LDE_COSET_MAJOR;
+    if (k > 30 || logb > 30 || k + logb > 30 || shard_log > logb || (!lde && logb != 0)) { sp_set_error("sp_ntt_plan: k + logb <= 30, shard_log <= logb, logb = 0 unless the driver is an LDE"); return SP_E_INVALID_ARG; }
+    if (!launch_fits((uint64_t)batch << (logb - shard_log), (int)k)) { sp_set_error("sp_ntt_plan: too many vectors for one launch"); return SP_E_INVALID_ARG; }
+    const std::vector<NttPlannedPass> plan = ntt_plan((NttDriver)driver, (int)k, (int)logb, (int)shard_log, batch);
+    *count_out = (uint32_t)plan.size();
+    if (!out) return SP_OK;
+    if (cap < plan.size()) { sp_set_error("sp_ntt_plan: the driver launches more passes than cap"); return SP_E_INVALID_ARG; }
+    for (size_t i = 0; i < plan.size(); ++i) {
+        const NttPlannedPass& p = plan[i];
+        out[i] = sp_ntt_pass{p.dif ? 1u : 0u, (uint32_t)p.load, (uint32_t)p.store, p.contig ? 1u : 0u, p.gtw ? 1u : 0u, p.s, p.r, p.g,
+                             p.radix4, p.xcd_map, p.weak_out, p.stage_tw, p.logL, p.tiles, p.vectors, p.coset_count};
+    }
+    return SP_OK;
+}
+
 // The periodic-column table of the prover (prover.cpp air_periodic_tables: the routine composition_air calls), for one column,
 // handed back in natural order: out[j b + c] = table entry (c, j).  Canonical big-endian whatever the context's encoding.
 int sp_air_periodic_lde(sp_ctx* c, const sp_air_periodic_column* col, uint64_t n, uint32_t blowup, const uint8_t coset[32], uint8_t* out) {

@@ -16,8 +16,10 @@
 // memory and its lidx() in LDS; LdsPlanes is the tile or the twiddle table in LDS; global_tw() addresses the transform's
 // table; load_tile and store_tile move the tile.  The twiddle staging and the stages themselves (radix-4 units of both
 // directions, the radix-2 stage, the DIT pass's fused last-pair store) stand in the kernel body.
-// Host side: every driver hands its pass list, the fields all passes share and a per-pass hook (buffers, strides, load and
-// store modes, post_table / scalar on the last pass) to the one pass loop, run_passes.
+// Host side: ntt_plan() turns (driver, k, logb, shard_log, batch) into the pass list as it is launched - kernel variant, local
+// s / r / g, tile count, LDS bytes, radix4 / xcd_map / weak_out / stage_tw - without touching the device; every driver hands that list,
+// the fields all passes share and a per-pass hook (buffers, strides, post_table / scalar on the last pass) to the one pass loop,
+// run_passes, which launches exactly what the list says.  sp_ntt_plan (capi_dev.cpp) hands the same list to tests.
 #pragma once
 #include "common.h"
 #include <map>
@@ -55,14 +57,34 @@ struct NttPassArgs {
     // 1 on every pass but the last one of a transform: the stored data is only brought below 2p; 0: canonical values.
     uint32_t weak_out;
     uint32_t stage_tw;    // 1: big_tw is the pyramid, stage J reads its own dense table (adjacent columns = adjacent entries)
-    uint32_t radix4;      // two stages per LDS round trip (filled in by the launcher)
-    uint32_t batch;       // vectors per launch (filled in by the launcher)
+    uint32_t radix4;      // two stages per LDS round trip (from the plan)
+    uint32_t batch;       // vectors per launch (from the plan)
     uint32_t xcd_map;     // 1: XCD-aware block -> (tile, vector) mapping (needs tiles % 8 == 0)
 };
 
 enum NttLoadMode { NTT_LOAD_INPLACE = 0, NTT_LOAD_GATHER_BITREV = 1, NTT_LOAD_EXPAND = 2 };
 enum NttStoreMode { NTT_STORE_INPLACE = 0, NTT_STORE_SCATTER_BITREV = 1 };
-struct PassGeom;   // one entry of a transform's pass list: (s, r, g)
+
+// The six drivers of the engine, as ntt_plan and sp_ntt_plan name them (the values are the SP_NTT_DRIVER_* of the C header).
+enum NttDriver { NTT_DRV_FORWARD_NATURAL = 0, NTT_DRV_INVERSE_NATURAL = 1, NTT_DRV_DIT_BITREV_TO_NATURAL = 2,
+                 NTT_DRV_DIF_NATURAL_TO_BITREV_INVERSE = 3, NTT_DRV_LDE_FROM_BITREV = 4, NTT_DRV_LDE_COSET_MAJOR = 5 };
+// One launch of ntt_pass_kernel as a driver will make it, in execution order.
+struct NttPlannedPass {
+    bool dif;                 // Gentleman-Sande (inverse roots) or Cooley-Tukey
+    int load, store;          // NttLoadMode, NttStoreMode
+    bool contig, gtw;         // template flags CONTIG and GTW of the instantiation
+    uint32_t s, r, g;         // LOCAL stride 2^s, 2^r rows, 2^g adjacent elements per row
+    uint32_t radix4, xcd_map, weak_out;
+    uint32_t stage_tw;        // 1: reads the pyramid of per-stage tables when the engine has one (whole transforms of a -DSP_NTT_STAGE_TW=1 build)
+    uint32_t logL;            // log2 of the array the pass addresses (per vector, per coset in the coset-major LDE)
+    uint32_t tiles;           // work-groups per vector
+    uint32_t vectors;         // vectors per launch (columns x local cosets in the coset-major LDE)
+    uint32_t coset_count;     // coset-major LDE: local cosets per column; 0: plain vectors
+    size_t lds;               // dynamic LDS bytes of the launch
+};
+// The passes driver `drv` launches for 2^k elements per vector, blowup 2^logb, 2^shard_log shards and `batch` vectors (logb and
+// shard_log count for the two LDE drivers only).  Pure host arithmetic: no device, no engine.
+std::vector<NttPlannedPass> ntt_plan(NttDriver drv, int k, int logb, int shard_log, uint32_t batch);
 
 class NttEngine {
   public:
@@ -105,12 +127,12 @@ class NttEngine {
     hipStream_t stream() const { return stream_; }
 
   private:
-    int launch_pass(bool dif, int load_mode, int store_mode, const NttPassArgs& a, uint32_t batch);
-    // The one pass loop behind the six drivers above (ntt.hip): walks a geometry() list in DIT or DIF order, fills what follows from
-    // the list (s, r, g, the pass-local table of the direction, weak_out) and lets the driver's hook name buffers, strides and modes.
+    int launch_pass(const NttPlannedPass& p, const NttPassArgs& a);
+    // The one pass loop behind the six drivers above (ntt.hip): walks an ntt_plan() list, fills what follows from the list (s, r, g, the
+    // pass-local table of the direction, weak_out, radix4, xcd_map, the launch's vector count) and lets the driver's hook name buffers and strides.
     struct PassJob;
     template <class Hook>
-    int run_passes(bool dif, const std::vector<PassGeom>& geo, const NttPassArgs& common, uint32_t batch, Hook hook);
+    int run_passes(const std::vector<NttPlannedPass>& plan, const NttPassArgs& common, Hook hook);
     hipStream_t stream_;
     // what the passes of a whole size-2^k transform share: logM = logL = k and the twiddles, pyramid + stage_tw = 1 or roots(k) + stage_tw = 0
     int transform_twiddles(int k, NttPassArgs* a);

@@ -536,37 +536,26 @@ int NttEngine::inv_roots_small(int k, const fe** out) {
 }
 
 template <bool DIF, int LM, int SM, bool CONTIG, bool GTW>
-static int launch_t(hipStream_t st, const NttPassArgs& a, uint32_t batch) {
-    uint32_t tile_log = a.r + a.g;
-    uint32_t tiles = 1u << (a.logL - tile_log);
-    size_t lds = ((size_t)2 << tile_log) * sizeof(uint4) + ((size_t)1 << a.r) * sizeof(uint4);
-    if (!CONTIG) lds = ((size_t)3 << tile_log) * sizeof(uint4);   // tile + the global twiddles of its stages j < r (j < r - 1 in pairs, below)
-    else if (GTW) lds = ((size_t)2 << tile_log) * sizeof(uint4) + ((size_t)2 << a.r) * sizeof(uint4);
-    NttPassArgs b = a;
-    b.batch = batch;
-    b.xcd_map = (tiles % 8 == 0) ? 1u : 0u;
-    // two stages per LDS round trip on the tiles that give every thread a unit (a half-empty work-group loses more than the
-    // saved round trips)
-    b.radix4 = (a.r >= 2 && (1u << tile_log) == 4u * NTT_THREADS) ? 1u : 0u;
-    if (!CONTIG && b.radix4) lds = ((size_t)5 << (tile_log - 1)) * sizeof(uint4);
-    if ((uint64_t)tiles * batch >= (1ull << 31)) { sp_set_error("ntt: batch too large for one launch"); return SP_E_INVALID_ARG; }
-    hipLaunchKernelGGL((ntt_pass_kernel<DIF, LM, SM, CONTIG, GTW>), dim3(tiles * batch), dim3(NTT_THREADS), lds, st, b);
+static int launch_t(hipStream_t st, const NttPlannedPass& p, const NttPassArgs& a) {
+    if ((uint64_t)p.tiles * p.vectors >= (1ull << 31)) { sp_set_error("ntt: batch too large for one launch"); return SP_E_INVALID_ARG; }
+    hipLaunchKernelGGL((ntt_pass_kernel<DIF, LM, SM, CONTIG, GTW>), dim3(p.tiles * p.vectors), dim3(NTT_THREADS), p.lds, st, a);
     SP_HIP_CHECK(hipGetLastError());
     return SP_OK;
 }
 
-int NttEngine::launch_pass(bool dif, int lm, int sm, const NttPassArgs& a, uint32_t batch) {
-    bool contig = a.s == 0 && lm != NTT_LOAD_EXPAND;
-    if (!dif) {
-        if (contig && a.coset_count) return launch_t<false, NTT_LOAD_INPLACE, NTT_STORE_INPLACE, true, true>(stream_, a, batch);
-        if (contig && lm == NTT_LOAD_INPLACE) return launch_t<false, NTT_LOAD_INPLACE, NTT_STORE_INPLACE, true, false>(stream_, a, batch);
-        if (contig && lm == NTT_LOAD_GATHER_BITREV) return launch_t<false, NTT_LOAD_GATHER_BITREV, NTT_STORE_INPLACE, true, false>(stream_, a, batch);
-        if (!contig && lm == NTT_LOAD_INPLACE) return launch_t<false, NTT_LOAD_INPLACE, NTT_STORE_INPLACE, false, true>(stream_, a, batch);
-        if (!contig && lm == NTT_LOAD_EXPAND) return launch_t<false, NTT_LOAD_EXPAND, NTT_STORE_INPLACE, false, true>(stream_, a, batch);
-    } else {
-        if (contig && sm == NTT_STORE_INPLACE) return launch_t<true, NTT_LOAD_INPLACE, NTT_STORE_INPLACE, true, false>(stream_, a, batch);
-        if (contig && sm == NTT_STORE_SCATTER_BITREV) return launch_t<true, NTT_LOAD_INPLACE, NTT_STORE_SCATTER_BITREV, true, false>(stream_, a, batch);
-        if (!contig) return launch_t<true, NTT_LOAD_INPLACE, NTT_STORE_INPLACE, false, true>(stream_, a, batch);
+// The instantiation a planned pass names (plan_launch below chose contig and gtw).
+int NttEngine::launch_pass(const NttPlannedPass& p, const NttPassArgs& a) {
+    const int lm = p.load, sm = p.store;
+    if (!p.dif) {
+        if (p.contig && p.gtw && lm == NTT_LOAD_INPLACE) return launch_t<false, NTT_LOAD_INPLACE, NTT_STORE_INPLACE, true, true>(stream_, p, a);
+        if (p.contig && !p.gtw && lm == NTT_LOAD_INPLACE) return launch_t<false, NTT_LOAD_INPLACE, NTT_STORE_INPLACE, true, false>(stream_, p, a);
+        if (p.contig && !p.gtw && lm == NTT_LOAD_GATHER_BITREV) return launch_t<false, NTT_LOAD_GATHER_BITREV, NTT_STORE_INPLACE, true, false>(stream_, p, a);
+        if (!p.contig && p.gtw && lm == NTT_LOAD_INPLACE) return launch_t<false, NTT_LOAD_INPLACE, NTT_STORE_INPLACE, false, true>(stream_, p, a);
+        if (!p.contig && p.gtw && lm == NTT_LOAD_EXPAND) return launch_t<false, NTT_LOAD_EXPAND, NTT_STORE_INPLACE, false, true>(stream_, p, a);
+    } else if (lm == NTT_LOAD_INPLACE) {
+        if (p.contig && !p.gtw && sm == NTT_STORE_INPLACE) return launch_t<true, NTT_LOAD_INPLACE, NTT_STORE_INPLACE, true, false>(stream_, p, a);
+        if (p.contig && !p.gtw && sm == NTT_STORE_SCATTER_BITREV) return launch_t<true, NTT_LOAD_INPLACE, NTT_STORE_SCATTER_BITREV, true, false>(stream_, p, a);
+        if (!p.contig && p.gtw && sm == NTT_STORE_INPLACE) return launch_t<true, NTT_LOAD_INPLACE, NTT_STORE_INPLACE, false, true>(stream_, p, a);
     }
     sp_set_error("ntt: unsupported pass mode");
     return SP_E_UNSUPPORTED;
@@ -616,25 +605,106 @@ static std::vector<PassGeom> transform_geometry(int k, int contig_cap, uint64_t 
     return geo;
 }
 
-// One pass as a driver's hook sees it: the runner has filled s, r, g, small_tw and weak_out, the hook names the buffers and modes.
+// What launching one pass of local (s, r, g) on arrays of 2^logL elements comes to: the kernel variant, tiles, LDS, pairs, XCD order.
+// A contiguous pass reads the pass-local table unless it runs the cosets of the coset-major LDE, whose twiddles carry the coset index
+// (the transform's table, GTW); strided passes - the EXPAND pass even at local stride 0 - always read the transform's table.
+static NttPlannedPass plan_launch(bool dif, int load, int store, const PassGeom& g, uint32_t logL, uint32_t vectors, uint32_t coset_count) {
+    NttPlannedPass p{};
+    p.dif = dif; p.load = load; p.store = store;
+    p.s = (uint32_t)g.s; p.r = (uint32_t)g.r; p.g = (uint32_t)g.g;
+    p.logL = logL; p.vectors = vectors; p.coset_count = coset_count;
+    p.contig = g.s == 0 && load != NTT_LOAD_EXPAND;
+    p.gtw = !p.contig || (!dif && coset_count != 0);
+    const uint32_t tile_log = p.r + p.g;
+    p.tiles = 1u << (logL - tile_log);
+    p.xcd_map = (p.tiles % 8 == 0) ? 1u : 0u;
+    // two stages per LDS round trip on the tiles that give every thread a unit (a half-empty work-group loses more than the
+    // saved round trips)
+    p.radix4 = (p.r >= 2 && (1u << tile_log) == 4u * NTT_THREADS) ? 1u : 0u;
+    p.lds = ((size_t)2 << tile_log) * sizeof(uint4) + ((size_t)1 << p.r) * sizeof(uint4);
+    if (!p.contig) p.lds = ((size_t)3 << tile_log) * sizeof(uint4);   // tile + the global twiddles of its stages j < r (j < r - 1 in pairs, below)
+    else if (p.gtw) p.lds = ((size_t)2 << tile_log) * sizeof(uint4) + ((size_t)2 << p.r) * sizeof(uint4);
+    if (!p.contig && p.radix4) p.lds = ((size_t)5 << (tile_log - 1)) * sizeof(uint4);
+    return p;
+}
+
+std::vector<NttPlannedPass> ntt_plan(NttDriver drv, int k, int logb, int shard_log, uint32_t batch) {
+    std::vector<PassGeom> geo;
+    bool dif = false;
+    int first_load = NTT_LOAD_INPLACE, last_store = NTT_STORE_INPLACE;
+    uint32_t logL = (uint32_t)k, vectors = batch, coset_count = 0, stage_tw = (SP_NTT_STAGE_TW && k <= 31) ? 1u : 0u;
+    switch (drv) {
+        case NTT_DRV_FORWARD_NATURAL:
+            geo = transform_geometry(k, NTT_TILE_LOG - NTT_STRIDED_G_LOG, batch);
+            first_load = NTT_LOAD_GATHER_BITREV;
+            break;
+        case NTT_DRV_INVERSE_NATURAL:
+            geo = transform_geometry(k, NTT_TILE_LOG - NTT_STRIDED_G_LOG, batch);
+            dif = true; last_store = NTT_STORE_SCATTER_BITREV;
+            break;
+        case NTT_DRV_DIT_BITREV_TO_NATURAL:
+            if (k == 0) return {};
+            geo = transform_geometry(k, NTT_MAX_CONTIG_LOG, batch);
+            break;
+        case NTT_DRV_DIF_NATURAL_TO_BITREV_INVERSE: {
+            // beyond one tile the contiguous pass is kept short (2^7 rows x 8 contiguous runs): a 2^10-row pass stages a 16 KB
+            // twiddle table per 32 KB tile and fits only three work-groups per CU (measured 55 % of the strided passes' rate)
+            constexpr int contig_cap = 7;
+            geo = transform_geometry(k, contig_cap, batch);
+            dif = true;
+            break;
+        }
+        case NTT_DRV_LDE_FROM_BITREV: {
+            if (logb == 0) return ntt_plan(NTT_DRV_DIT_BITREV_TO_NATURAL, k, 0, 0, batch);   // plain evaluation: copy, then the DIT in place
+            const int K = k + logb;
+            geo = geometry(K, logb, NTT_MAX_CONTIG_LOG, ((uint64_t)batch << (K - shard_log)) * sizeof(fe));
+            if (geo.empty()) geo.push_back({logb, 0, std::min(logb, NTT_STRIDED_G_LOG)});   // k == 0: constant polynomial replicated
+            for (PassGeom& g : geo) {
+                g.s -= shard_log;               // local stride
+                g.g = std::min(g.g, g.s);       // adjacent elements per row cannot exceed the local stride
+            }
+            logL = (uint32_t)(K - shard_log); first_load = NTT_LOAD_EXPAND; stage_tw = 0;
+            break;
+        }
+        case NTT_DRV_LDE_COSET_MAJOR:
+            coset_count = 1u << (logb - shard_log);
+            vectors = batch * coset_count;
+            geo = transform_geometry(k, NTT_TILE_LOG - NTT_STRIDED_G_LOG, (uint64_t)batch * coset_count);
+            stage_tw = 0;
+            break;
+    }
+    // DIT runs the list first to last, DIF last to first
+    std::vector<NttPlannedPass> plan;
+    for (size_t step = 0; step < geo.size(); ++step) {
+        const bool last = step + 1 == geo.size();
+        NttPlannedPass p = plan_launch(dif, step == 0 ? first_load : NTT_LOAD_INPLACE, last ? last_store : NTT_STORE_INPLACE,
+                                       geo[dif ? geo.size() - 1 - step : step], logL, vectors, coset_count);
+        p.weak_out = !last;
+        p.stage_tw = stage_tw;
+        plan.push_back(p);
+    }
+    return plan;
+}
+
+// One pass as a driver's hook sees it: the runner has filled what the plan says, the hook names the buffers.
 struct NttEngine::PassJob {
     NttPassArgs a;
-    int load = NTT_LOAD_INPLACE, store = NTT_STORE_INPLACE;
     void io(const fe* src, fe* dst, uint64_t src_stride, uint64_t dst_stride) { a.src = src; a.dst = dst; a.src_vec_stride = src_stride; a.dst_vec_stride = dst_stride; }
 };
-// Runs the passes of `geo` first to last (DIT) or last to first (DIF, with the inverse pass-local tables).  `common` carries what
-// all passes share (twiddle source, logM, logL, shifts, coset fields); hook(step, last, job) sees every pass in execution order.
+// Runs the passes of `plan` in order (the inverse pass-local tables for DIF).  `common` carries what all passes share (twiddle
+// source, logM, logL, shifts, coset fields); hook(step, last, job) sees every pass in execution order.
 template <class Hook>
-int NttEngine::run_passes(bool dif, const std::vector<PassGeom>& geo, const NttPassArgs& common, uint32_t batch, Hook hook) {
-    for (size_t step = 0; step < geo.size(); ++step) {
-        const PassGeom& p = geo[dif ? geo.size() - 1 - step : step];
-        const bool last = step + 1 == geo.size();
+int NttEngine::run_passes(const std::vector<NttPlannedPass>& plan, const NttPassArgs& common, Hook hook) {
+    for (size_t step = 0; step < plan.size(); ++step) {
+        const NttPlannedPass& p = plan[step];
+        const bool last = step + 1 == plan.size();
         PassJob job{common};
         job.a.s = p.s; job.a.r = p.r; job.a.g = p.g;
-        SP_TRY(dif ? inv_roots_small(p.r, &job.a.small_tw) : roots(p.r, &job.a.small_tw));
-        job.a.weak_out = !last;
+        SP_TRY(p.dif ? inv_roots_small((int)p.r, &job.a.small_tw) : roots((int)p.r, &job.a.small_tw));
+        job.a.weak_out = p.weak_out; job.a.radix4 = p.radix4; job.a.xcd_map = p.xcd_map; job.a.batch = p.vectors;
+        job.a.stage_tw = (p.stage_tw && common.stage_tw) ? 1u : 0u;   // (the plan assumes the pyramid; transform_twiddles knows whether it is there)
         hook(step, last, job);
-        SP_TRY(launch_pass(dif, job.load, job.store, job.a, batch));
+        SP_TRY(launch_pass(p, job.a));
     }
     return SP_OK;
 }
@@ -643,17 +713,14 @@ int NttEngine::dit_bitrev_to_natural(fe* data, int k, uint32_t batch, uint64_t s
     if (k == 0) return SP_OK;
     NttPassArgs c{};
     SP_TRY(transform_twiddles(k, &c));
-    return run_passes(false, transform_geometry(k, NTT_MAX_CONTIG_LOG, batch), c, batch,
+    return run_passes(ntt_plan(NTT_DRV_DIT_BITREV_TO_NATURAL, k, 0, 0, batch), c,
                       [&](size_t, bool, PassJob& j) { j.io(data, data, stride, stride); });
 }
 
 int NttEngine::dif_natural_to_bitrev_inverse(fe* data, int k, uint32_t batch, uint64_t stride, const fe* post_table, const fe* src) {
     NttPassArgs c{};
     SP_TRY(transform_twiddles(k, &c));
-    // beyond one tile the contiguous pass is kept short (2^7 rows x 8 contiguous runs): a 2^10-row pass stages a 16 KB
-    // twiddle table per 32 KB tile and fits only three work-groups per CU (measured 55 % of the strided passes' rate)
-    constexpr int contig_cap = 7;
-    return run_passes(true, transform_geometry(k, contig_cap, batch), c, batch, [&](size_t step, bool last, PassJob& j) {
+    return run_passes(ntt_plan(NTT_DRV_DIF_NATURAL_TO_BITREV_INVERSE, k, 0, 0, batch), c, [&](size_t step, bool last, PassJob& j) {
         j.io(src && step == 0 ? src : data, data, stride, stride);   // the first pass executed may read another array (same stride)
         if (last) j.a.post_table = post_table;
     });
@@ -662,17 +729,17 @@ int NttEngine::dif_natural_to_bitrev_inverse(fe* data, int k, uint32_t batch, ui
 int NttEngine::forward_natural(const fe* src, fe* dst, int k, uint32_t batch, uint64_t ss, uint64_t ds, fe* final_dst) {
     NttPassArgs c{};
     SP_TRY(transform_twiddles(k, &c));
-    const std::vector<PassGeom> geo = transform_geometry(k, NTT_TILE_LOG - NTT_STRIDED_G_LOG, batch);
+    const std::vector<NttPlannedPass> plan = ntt_plan(NTT_DRV_FORWARD_NATURAL, k, 0, 0, batch);
     // ping-pong: pass 1 src -> dst (gather, must be out of place); if final_dst is given (same stride as src), pass 2
     // writes dst -> final_dst and later passes run in place there, so the result lands in final_dst without a copy.
     fe* const rest = final_dst ? final_dst : dst;
     const uint64_t rs = final_dst ? ss : ds;
-    SP_TRY(run_passes(false, geo, c, batch, [&](size_t step, bool, PassJob& j) {
-        if (step == 0) { j.io(src, dst, ss, ds); j.load = NTT_LOAD_GATHER_BITREV; }
+    SP_TRY(run_passes(plan, c, [&](size_t step, bool, PassJob& j) {
+        if (step == 0) j.io(src, dst, ss, ds);
         else if (step == 1) j.io(dst, rest, ds, rs);
         else j.io(rest, rest, rs, rs);
     }));
-    if (final_dst && geo.size() == 1)
+    if (final_dst && plan.size() == 1)
         for (uint32_t v = 0; v < batch; ++v)
             SP_HIP_CHECK(hipMemcpyAsync(final_dst + v * ss, dst + v * ds, sizeof(fe) << k, hipMemcpyDeviceToDevice, stream_));
     return SP_OK;
@@ -683,18 +750,18 @@ int NttEngine::inverse_natural(fe* data, fe* tmp, int k, uint32_t batch, uint64_
     // bit-reversal scatter goes tmp -> data (a scatter must never run in place: other tiles still read their rows).
     NttPassArgs c{};
     SP_TRY(transform_twiddles(k, &c));
-    const std::vector<PassGeom> geo = transform_geometry(k, NTT_TILE_LOG - NTT_STRIDED_G_LOG, batch);
+    const std::vector<NttPlannedPass> plan = ntt_plan(NTT_DRV_INVERSE_NATURAL, k, 0, 0, batch);
     if (!d_scalar_) SP_HIP_CHECK(hipMalloc(&d_scalar_, sizeof(fe)));
     fe ninv = fe_inv(fe_from_u64(1ULL << k));
     SP_HIP_CHECK(hipMemcpyAsync(d_scalar_, &ninv, sizeof(fe), hipMemcpyHostToDevice, stream_));
-    const bool one_pass = geo.size() == 1;
+    const bool one_pass = plan.size() == 1;
     if (one_pass) {
         for (uint32_t v = 0; v < batch; ++v)
             SP_HIP_CHECK(hipMemcpyAsync(tmp + v * stride, data + v * stride, sizeof(fe) << k, hipMemcpyDeviceToDevice, stream_));
     }
-    return run_passes(true, geo, c, batch, [&](size_t step, bool last, PassJob& j) {
+    return run_passes(plan, c, [&](size_t step, bool last, PassJob& j) {
         j.io(step == 0 && !one_pass ? data : tmp, last ? data : tmp, stride, stride);
-        if (last) { j.store = NTT_STORE_SCATTER_BITREV; j.a.scalar = d_scalar_; }
+        if (last) j.a.scalar = d_scalar_;
     });
 }
 
@@ -711,15 +778,9 @@ int NttEngine::lde_from_bitrev(const fe* coeffs, fe* dst, int k, int logb, uint3
     SP_TRY(roots(K, &c.big_tw));
     c.logM = K; c.logL = (uint32_t)(K - shard_log); c.log_expand = logb;
     c.tw_shift = (uint32_t)shard_log; c.tw_low = (uint32_t)shard_rank;   // local index -> global: (index << shard_log) | rank
-    std::vector<PassGeom> geo = geometry(K, logb, NTT_MAX_CONTIG_LOG, ((uint64_t)batch << (K - shard_log)) * sizeof(fe));
-    if (geo.empty()) {  // k == 0: constant polynomial replicated
-        geo.push_back({logb, 0, std::min(logb, NTT_STRIDED_G_LOG)});
-    }
-    return run_passes(false, geo, c, batch, [&](size_t step, bool, PassJob& j) {
-        if (step == 0) { j.io(coeffs, dst, ss, ds); j.load = NTT_LOAD_EXPAND; }
+    return run_passes(ntt_plan(NTT_DRV_LDE_FROM_BITREV, k, logb, shard_log, batch), c, [&](size_t step, bool, PassJob& j) {
+        if (step == 0) j.io(coeffs, dst, ss, ds);
         else j.io(dst, dst, ds, ds);
-        j.a.s -= (uint32_t)shard_log;            // local stride
-        j.a.g = std::min(j.a.g, j.a.s);          // adjacent elements per row cannot exceed the local stride
     });
 }
 
@@ -738,8 +799,7 @@ int NttEngine::lde_coset_major(const fe* coeffs, fe* dst, int k, int logb, uint3
     c.logM = K; c.logL = (uint32_t)k;
     c.tw_shift = (uint32_t)logb; c.tw_low = (uint32_t)shard_rank; c.shard_log = (uint32_t)shard_log;
     c.coset_count = b_loc; c.dst_coset_stride = n;
-    return run_passes(false, transform_geometry(k, NTT_TILE_LOG - NTT_STRIDED_G_LOG, (uint64_t)batch * b_loc), c, batch * b_loc,
-                      [&](size_t step, bool, PassJob& j) {
+    return run_passes(ntt_plan(NTT_DRV_LDE_COSET_MAJOR, k, logb, shard_log, batch), c, [&](size_t step, bool, PassJob& j) {
         if (step == 0) j.io(coeffs, dst, ss, ds);          // every coset reads the same coefficients
         else { j.io(dst, dst, ds, ds); j.a.src_coset_stride = n; }
     });

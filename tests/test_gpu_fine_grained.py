@@ -97,26 +97,7 @@ def test_batch_inverse(hip_ctx, oracle):
             hip_ctx.batch_inverse(api.felts_to_bytes(y))
 
 
-class _HipBuffer:
-    """Device memory through the HIP runtime the library itself is linked against (importing torch after the library has
-    initialised HIP would bring a second runtime into the process)."""
-
-    def __init__(self, host: np.ndarray):
-        import ctypes
-        self._ct = ctypes
-        self._hip = ctypes.CDLL("libamdhip64.so")
-        self.nbytes = host.nbytes
-        self.ptr = ctypes.c_void_p()
-        assert self._hip.hipMalloc(ctypes.byref(self.ptr), ctypes.c_size_t(self.nbytes)) == 0
-        assert self._hip.hipMemcpy(self.ptr, host.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(self.nbytes), 1) == 0
-
-    def to_host(self, dtype=np.uint8):
-        out = np.empty(self.nbytes, dtype=np.uint8)
-        assert self._hip.hipMemcpy(out.ctypes.data_as(self._ct.c_void_p), self.ptr, self._ct.c_size_t(self.nbytes), 2) == 0
-        return out
-
-    def free(self):
-        self._hip.hipFree(self.ptr)
+from hip_buffers import HipBuffer as _HipBuffer      # device memory through the HIP runtime the library itself is linked against
 
 
 @pytest.mark.parametrize("k,batch", [(10, 1), (13, 5), (22, 1)])

@@ -3,25 +3,13 @@ both directions and batched: every element equals the CPU oracle's.  The strided
 table inside one "pyramid" per engine (csrc/ntt.h, NttEngine::stage_tables); fresh contexts that meet a small size after a large one and a
 large one after a small one cover the reuse and the growth of that allocation.  The same file passes when the library is built with
 -DSP_NTT_STAGE_TW=0 (single-table addressing)."""
-import ctypes
-
 import numpy as np
 import pytest
 
+from hip_buffers import HipBuffer
 from lambdaworks_cairo_prover_amd import api
 
 pytestmark = pytest.mark.gpu
-
-_hip = None
-
-
-def _runtime():
-    """The HIP runtime the library itself is linked against (no second runtime in the process)."""
-    global _hip
-    if _hip is None:
-        _hip = ctypes.CDLL("libamdhip64.so")
-    return _hip
-
 
 def _residues(k, batch, seed):
     """batch columns of 2^k uniform residues below 2^251 (< p), canonical big-endian bytes; p - 1, p - 2, 0 and 1 among them."""
@@ -34,19 +22,12 @@ def _residues(k, batch, seed):
 
 def _ntt_dev(ctx, cols, inverse):
     """sp_ntt_dev on device-layout columns (batch, n, 32) -> the result as canonical big-endian bytes."""
-    hip = _runtime()
     batch, n = cols.shape[0], cols.shape[1]
     host = np.ascontiguousarray(np.concatenate([api.fe_to_device(c) for c in cols]))
-    ptr = ctypes.c_void_p()
-    assert hip.hipMalloc(ctypes.byref(ptr), ctypes.c_size_t(host.nbytes)) == 0
-    try:
-        assert hip.hipMemcpy(ptr, host.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(host.nbytes), 1) == 0
-        ctx.ntt_dev(ptr.value, n, batch, inverse=inverse)
+    with HipBuffer(host) as d:
+        ctx.ntt_dev(d.address, n, batch, inverse=inverse)
         ctx.sync()
-        out = np.empty(host.nbytes, dtype=np.uint8)
-        assert hip.hipMemcpy(out.ctypes.data_as(ctypes.c_void_p), ptr, ctypes.c_size_t(host.nbytes), 2) == 0
-    finally:
-        hip.hipFree(ptr)
+        out = d.to_host()
     return api.fe_from_device(out.reshape(-1, 32)).reshape(batch, n, 32)
 
 
